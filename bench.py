@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the wmix DSP hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 --gpus N > 1 outside a torchrun environment starts N rank processes of this script itself (one per GPU, RCCL);
 under torchrun (WORLD_SIZE set) --gpus must equal WORLD_SIZE.
@@ -12,8 +12,11 @@ collective except the one RCCL broadcast of the shared AEC far-end frame
 (SURVEY.md section 8e), so scaling is weak: every rank owns the full per-GPU batch.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying
-`roofline` (dominant kernel, HIP-event timed) and `cpu_baseline` (the oracle
-timed on this box's host cores, rank 0 / N=1 only, bounded sample).
+`roofline` (dominant kernel, HIP-event timed inside the timed region).  A plain run sets up, warms up, times the K
+steps, writes --dump-outputs and prints that line, nothing else.  --full adds what takes work of its own: the per-stage
+breakdown, the in-run parity proof against the oracle, the PCIe-inclusive rate, `cpu_baseline` (the oracle timed on
+this box's host cores, rank 0 / N=1 only, bounded sample) and, on the default line, the other BASELINE configs and a
+short paced run.
 """
 import argparse
 import ctypes as C
@@ -29,6 +32,29 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BYTES = 60 << 20  # --dump-outputs: every array of the dump together, as written (under 64 MB with the .npy headers)
+DUMP_SEED = 20261016   # --dump-outputs: the row sample taken when the outputs are larger than DUMP_BYTES
+
+
+def _dump_outputs(outputs, out_dir):
+    """--dump-outputs DIR: `outputs` ({name: tensor whose first axis is the stream / frame / group}, what the last timed step handed
+    its caller) as DIR/<name>.npy.  Samples, codes and float32 values are written as float32 (exact for every one of them), wider
+    integers as float64.  When the arrays together would exceed DUMP_BYTES, every array keeps the same fraction of its rows: a
+    sorted sample drawn with DUMP_SEED, so that the same arguments give the same rows on any build."""
+    os.makedirs(out_dir, exist_ok=True)
+    wide = (torch.int32, torch.int64, torch.uint32, torch.float64)
+
+    def as_float(t):
+        return t.to(torch.float64 if t.dtype in wide else torch.float32)
+    full = sum(t.numel() * (8 if t.dtype in wide else 4) for t in outputs.values())
+    keep = min(1.0, DUMP_BYTES / full) if full else 1.0
+    for name, t in outputs.items():
+        t = t.detach()
+        if keep < 1.0:
+            rows = t.shape[0]
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, max(1, int(rows * keep)), replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(as_float(t).cpu().numpy()))
 
 
 # ----------------------------------------------------------------------------- workloads
@@ -66,6 +92,11 @@ class G711Workload:
 
     def dominant_ms(self):
         return float(np.mean([a.elapsed_time(b) for a, b in self.ev])) if self.ev else None
+
+    def outputs(self):
+        """the last step's codes and decoded samples, one row per 80-sample frame"""
+        rows = (lambda t: t.view(-1, 80)) if self.code.numel() % 80 == 0 else (lambda t: t.view(-1, 1))
+        return {"codes": rows(self.code), "decoded": rows(self.back)}
 
     def config(self):
         return {"workload": self.name, "frames_per_step_per_gpu": self.n_frames, "frame": "80 x int16 (10 ms @ 8 kHz mono)"}
@@ -204,6 +235,9 @@ class NsWorkload:
     def stage_ms(self):
         return {"ns": self.t.mean_ms("ns")}
 
+    def outputs(self):
+        return {"out": self.work[0]}  # [S, pkt]: every stream's packet of the last step
+
     def config(self):
         return {"workload": self.name, "streams_per_gpu": self.n_frames, "frame": "160 x int16 (10 ms @ 16 kHz mono)",
                 "sum_order": "reference (the only one the library has)",
@@ -316,6 +350,9 @@ class NsxWorkload:
     def stage_ms(self):
         return {"nsx": self.t.mean_ms("nsx")}
 
+    def outputs(self):
+        return {"out": self.work[0]}  # [S, pkt]: every stream's packet of the last step
+
     def config(self):
         return {"workload": self.name, "streams_per_gpu": self.n_frames, "frame": "160 x int16 (10 ms @ 16 kHz mono)",
                 "input": "noise A=3000 + 3000 sin(0.01 t) gated every 100 frames (SURVEY 8d recipe), 256 distinct streams x %d "
@@ -412,6 +449,9 @@ class AecmWorkload:
     def stage_ms(self):
         return {"aecm (far + near kernels)": self.t.mean_ms("aecm")}
 
+    def outputs(self):
+        return {"out": self.work[0]}  # [S, pkt]: every stream's packet of the last step
+
     def config(self):
         return {"workload": self.name, "streams_per_gpu": self.n_frames, "frame": "160 x int16 (10 ms @ 16 kHz mono)",
                 "far_end": "shared" + (", RCCL broadcast from rank 0 each step" if self.dist is not None else ", resident in HBM"),
@@ -503,6 +543,9 @@ class RtpChainWorkload:
 
     def stage_ms(self):
         return {"ingest + ns + aec + agc + vad + egress": self.t.mean_ms("step")}
+
+    def outputs(self):
+        return {"datagrams_out": self.d_out}  # [S, 172]
 
     def config(self):
         return {"workload": self.name, "streams_per_gpu": self.S, "frame": "172-byte RTP/PCMA datagram = 160 x int16 (20 ms @ 8 kHz mono)",
@@ -606,6 +649,9 @@ class MfftWorkload:
 
     def stage_ms(self):
         return {"fftr": self.t.mean_ms("fftr")}
+
+    def outputs(self):
+        return {"amplitude": self.out["a"]}  # [S, 1024]
 
     def config(self):
         return {"workload": self.name, "transforms_per_step_per_gpu": self.n_frames, "frame": "1024 x float32"}
@@ -840,6 +886,9 @@ class ChainWorkload:
             d["aec_near_kernel (timed region)"] = self.near_ms / self.aec_launches
         return d
 
+    def outputs(self):
+        return {"out": self.work if self.tick_major else self.work.transpose(0, 1)}  # [S, P, pkt]
+
     def parity_check(self):
         """Replays 16 sampled streams through the oracle chain for exactly the packets this run fed (priming, warm-up,
         timed and breakdown steps) and compares every packet recorded outside the timed region; the packets behind the
@@ -1028,7 +1077,7 @@ class NsAgcMix32kWorkload:
             self.mix.load(self.src, 1280, 32000, 2)
             self.mix.set(3200, 0, 1)
             return self.mix.drain(160)
-        out = self.t.run("mix", timed, mix)
+        out = self.drained = self.t.run("mix", timed, mix)
         if timed is not True:
             self.rec.append((step_index, self.work[0, self.watch].clone(), out[self.groups].clone()))
 
@@ -1037,6 +1086,10 @@ class NsAgcMix32kWorkload:
 
     def stage_ms(self):
         return {k: self.t.mean_ms(k) for k in ("ns", "agc", "mix")}
+
+    def outputs(self):
+        # every source's NS + AGC packet [S, 640] and every mix group's drained 10 ms of the 8 kHz ring [S / 8, 80]
+        return {"sources_out": self.work[0], "mix_drained": self.drained}
 
     def parity_check(self):
         """The 32 sources of 4 sampled mix groups replayed through the oracle's NS + AGC (2 x 32 kHz, R channel = high band,
@@ -1176,6 +1229,10 @@ class ConferenceWorkload:
             d["aec_far_kernel (timed region)"] = self.far_ms / self.aec_launches
             d["aec_near_kernel (timed region)"] = self.near_ms / self.aec_launches
         return d
+
+    def outputs(self):
+        # the groups' played packages and far-ends [G, 160], the record streams processed in place and zoomed to 1 x 8000 [S, 160]
+        return {"play": self.play, "far_end": self.tb.far(), "record": self.rec, "record_1x8000": self.zoom}
 
     def config(self):
         return {"workload": self.name, "record_streams_per_gpu": self.S, "sources_per_gpu": self.G * self.N, "mix_groups": self.G,
@@ -1330,6 +1387,9 @@ class StubCpuWorkload:
 
     def dominant_ms(self):
         return None
+
+    def outputs(self):
+        return {"acc": self.acc}  # [streams, 160] int32
 
     def config(self):
         return {"workload": self.name, "streams_per_gpu": self.n_frames, "far_chunk": self.FC, "broadcasts": self.n_bcast,
@@ -1802,7 +1862,16 @@ def main():
     ap.add_argument("--resident", action="store_true", help="--paced: rows resident in HBM, no PCIe inside the tick")
     ap.add_argument("--paced-search", default="", help="--paced: comma-separated stream counts, ascending; stops at the first with a miss")
     ap.add_argument("--no-realtime", action="store_true", help="default workload on one GPU: leave out the short paced run (`realtime` block)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-stage breakdown, in-run parity proof, PCIe-inclusive rate, CPU "
+                         "baseline and, on the default line, the other BASELINE configs and a short paced run (--no-cpu, --no-configs "
+                         "and --no-realtime leave parts out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32, or "
+                         "float64 for wider integers); at most %d MB in all, a fixed seeded sample of rows beyond that" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.dump_outputs and args.paced:
+        ap.error("--dump-outputs belongs to the stepped benchmark, not to --paced")
 
     if args.paced:
         torch.cuda.set_device(0)
@@ -1879,6 +1948,8 @@ def main():
             torch.cuda.synchronize()
 
     n_prime, elapsed, host_elapsed = _measure(wl, args, on_gpu, sync_all)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(wl.outputs(), args.dump_outputs)  # before any further step moves the buffers on
     per_rank_ms = [elapsed / args.steps * 1e3]
     per_rank_frames = [wl.n_frames]
     rank_devices = [rank_device]
@@ -1896,12 +1967,13 @@ def main():
             devs = [d["device"] for d in rank_devices]
             assert len(set(devs)) == world, "ranks share a device: %s" % rank_devices
 
-    # per-stage breakdown: a few extra steps with every launch bracketed by events, outside the timed region
-    for _ in range(min(args.steps, 16)):
+    # --full, per-stage breakdown: a few extra steps with every launch bracketed by events, outside the timed region
+    for _ in range(min(args.steps, 16) if args.full else 0):
         wl.step("all")
-    sync_all()
+    if args.full:
+        sync_all()
 
-    if hasattr(wl, "measure_pcie") and rank == 0 and (dist is None or not isinstance(wl, ChainWorkload)):
+    if args.full and hasattr(wl, "measure_pcie") and rank == 0 and (dist is None or not isinstance(wl, ChainWorkload)):
         # (several ranks: the chain workloads stream nothing, and every rank replays its own streams further down)
         parity_early = wl.parity_check()  # before the streaming steps advance the state past what was recorded
         # at least 200 streamed steps whatever --steps says: the pipeline's fill and drain (three slots) are not part of its rate
@@ -1942,8 +2014,6 @@ def main():
         "host_wall_ms_per_step": host_elapsed / args.steps * 1e3,
         "scaling": "strong" if args.total_streams else "weak", "vs_baseline": None, "dtype": wl.dtype, "data": "synthetic",
         "config": dict(wl.config(), primed_steps=n_prime), "roofline": roofline,
-        "stage_ms": wl.stage_ms() if hasattr(wl, "stage_ms") else None,
-        "stage_ms_source": "mean over up to 16 extra steps after the timed region, outliers beyond 5x the median dropped (inside the timed region only the dominant kernel carries events)",
         "whole_step_hbm_frac": round(value / world * wl.bytes_per_frame / 1e9 / HBM_PEAK_GBS, 5),
         "total_streams": args.total_streams or None,
         "per_rank_ms_per_step": [round(x, 5) for x in per_rank_ms],
@@ -1956,7 +2026,11 @@ def main():
         # which build of the library measured this ("default" = the product; anything else is a developer variant, loaded on purpose)
         "build": (_lib.build_info() if on_gpu else None),
     }
-    if hasattr(wl, "parity_check"):
+    if args.full:
+        out["stage_ms"] = wl.stage_ms() if hasattr(wl, "stage_ms") else None
+        out["stage_ms_source"] = ("mean over up to 16 extra steps after the timed region, outliers beyond 5x the median dropped (inside the "
+                                  "timed region only the dominant kernel carries events)")
+    if args.full and hasattr(wl, "parity_check"):
         if dist is not None:
             # every rank replays its own sampled streams through the oracle (ranks > 0 received the far-end only through the
             # broadcast); rank 0 prints all of them
@@ -1968,12 +2042,12 @@ def main():
         else:
             out["parity_checked"] = (parity_early or wl.parity_check()) if rank == 0 else None
     if rank == 0:
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = wl.cpu_baseline(args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
         plain = (args.packets_per_step, args.interval_ms, args.cohorts, args.coalesce, args.streams, args.total_streams, args.far_ends) == (1, 10, 1, False, 0, 0, 1)
-        if world == 1 and dist is None and on_gpu and args.workload == DEFAULT_WORKLOAD and plain and not args.no_configs:
+        if args.full and world == 1 and dist is None and on_gpu and args.workload == DEFAULT_WORKLOAD and plain and not args.no_configs:
             # the other four BASELINE configs on the same line, each measured and proven in this very run; the headline's
             # handles are released first (the 8 kHz config alone holds 131 072 streams of state)
             wl.chain.close()

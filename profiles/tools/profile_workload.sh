@@ -13,7 +13,7 @@ OUT=$R/gpurun_out/$ROUND/$WL
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 STEPS=40
-CMD="python3 $R/bench.py --no-cpu --no-configs --workload $WL --steps $STEPS --warmup 8 $*"
+CMD="python3 $R/bench.py --full --no-cpu --no-configs --workload $WL --steps $STEPS --warmup 8 $*"
 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o p --output-format csv -- $CMD > "$OUT/bench_under_stats.log" 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o p --output-format csv -- $CMD > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o p --output-format csv -- $CMD > /dev/null 2>&1

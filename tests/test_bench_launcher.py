@@ -17,7 +17,7 @@ def _run(args, env_extra=None, timeout=240):
 
 
 def test_gpus_flag_starts_that_many_ranks():
-    r = _run(["--gpus", "2", "--workload", "stub_cpu", "--steps", "5", "--warmup", "2", "--prime", "3", "--no-cpu"])
+    r = _run(["--gpus", "2", "--workload", "stub_cpu", "--steps", "5", "--warmup", "2", "--prime", "3", "--no-cpu", "--full"])
     assert r.returncode == 0, r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -64,8 +64,8 @@ def test_eight_ranks_shard_a_non_divisible_stream_count():
     parity record on rank 0's one line, inside a time bound."""
     import time
     t0 = time.monotonic()
-    r = _run(["--gpus", "8", "--workload", "stub_cpu", "--total-streams", "37", "--steps", "6", "--warmup", "2", "--prime", "4", "--no-cpu"],
-             timeout=300)
+    r = _run(["--gpus", "8", "--workload", "stub_cpu", "--total-streams", "37", "--steps", "6", "--warmup", "2", "--prime", "4", "--no-cpu",
+              "--full"], timeout=300)
     took = time.monotonic() - t0
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -90,7 +90,7 @@ def test_eight_ranks_far_end_in_chunks():
     import pytest
     for K, want_bcast in ((1, 18), (8, 3), (100, 1)):
         r = _run(["--gpus", "8", "--workload", "stub_cpu", "--total-streams", "37", "--steps", "6", "--warmup", "2", "--prime", "4", "--no-cpu",
-                  "--far-chunk", str(K)], timeout=300)
+                  "--full", "--far-chunk", str(K)], timeout=300)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
         assert d["n_gpus"] == 8 and d["config"]["far_chunk"] == K and d["config"]["broadcasts"] == want_bcast
@@ -103,7 +103,7 @@ def test_eight_ranks_under_the_drivers_own_launch_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                         "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "8",
-                        "--workload", "stub_cpu", "--steps", "3", "--warmup", "1", "--prime", "0", "--no-cpu"],
+                        "--workload", "stub_cpu", "--steps", "3", "--warmup", "1", "--prime", "0", "--no-cpu", "--full"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -121,3 +121,45 @@ def test_rank_stdout_is_kept_and_shown_when_the_launch_fails():
     r = _run(["--gpus", "2", "--workload", "stub_cpu", "--steps", "2", "--warmup", "0", "--prime", "0", "--no-cpu"],
              {"WMIX_STUB_FAIL_RANK": "1", "WMIX_STUB_CHATTER": "1"}, timeout=120)
     assert r.returncode == 7 and "---- stdout of rank 1 ----" in r.stderr and "stub rank 1 says hello" in r.stderr
+
+
+def test_a_plain_run_times_its_steps_and_nothing_more(tmp_path):
+    """Without --full the line carries the headline figure alone: no breakdown steps, no parity replay, no CPU baseline.
+    --dump-outputs writes what the last timed step left for the caller, and the same arguments write the same arrays."""
+    import numpy as np
+    got = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        r = _run(["--gpus", "2", "--workload", "stub_cpu", "--steps", "5", "--warmup", "2", "--prime", "3", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+        assert not {"parity_checked", "parity_checked_ranks", "stage_ms"} & set(line)
+        # 3 priming + 2 warm-up + 5 timed steps, not one more
+        assert line["config"]["far_sum"] == sum(range(1, 11)) and line["config"]["broadcasts"] == 10
+        got.append(np.load(d / "acc.npy"))
+    # rank 0's stream s added the far-end of every step (1 .. 10) and its global id s % 5 once per step
+    want = sum(range(1, 11)) + 10 * np.arange(4)[:, None] + np.zeros((1, 160))
+    assert got[0].dtype == np.float64 and np.array_equal(got[0], want) and np.array_equal(got[0], got[1])
+
+
+def test_dump_outputs_stays_within_64_mb_with_a_fixed_sample(tmp_path):
+    """Outputs larger than the dump's budget (the G.711 line's 2^20 frames) keep the same seeded rows on every run."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    g = torch.Generator().manual_seed(3)
+    big = {"codes": torch.randint(0, 256, (1 << 20, 80), dtype=torch.uint8, generator=g),
+           "decoded": torch.randint(-32768, 32768, (1 << 20, 80), dtype=torch.int16, generator=g)}
+    for d in ("a", "b"):
+        b._dump_outputs(big, str(tmp_path / d))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10 ** 6
+    a, c = np.load(tmp_path / "a" / "decoded.npy"), np.load(tmp_path / "b" / "decoded.npy")
+    assert a.dtype == np.float32 and a.shape[1] == 80 and 0 < a.shape[0] < 1 << 20 and np.array_equal(a, c)
+    # the sampled rows are input rows, in input order
+    rows = {bytes(r) for r in big["decoded"].numpy()}
+    assert all(bytes(r.astype(np.int16)) in rows for r in a[:64])

@@ -1,7 +1,7 @@
 """Drop-in boundary, SURVEY.md section 8b: the unchanged daemon objects of the reference link against libwmix_amd.so and
 every boundary symbol -- the src/webrtc.h and src/g711codec.h groups dynamically, the src/wmix.h group through the
-weaken + daemon_shim.o recipe of INTEGRATION.md section 2 -- resolves to our library.  Build container only: the
-reference tree does not exist on the GPU box."""
+weaken + daemon_shim.o recipe of INTEGRATION.md section 2 -- resolves to our library.  The daemon's objects are the ones
+oracle/Makefile's `ref` target builds into oracle/_ref/daemon/ (build() runs it where the reference sources are)."""
 import os
 import subprocess
 
@@ -10,7 +10,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="needs /root/reference (build container only)")
+@pytest.mark.skipif(not os.path.isfile(os.path.join(ROOT, "oracle", "_ref", "daemon", "wmix.o")),
+                    reason="oracle/_ref/daemon/wmix.o not built (oracle/Makefile ref needs the reference sources)")
 def test_daemon_links_against_libwmix_amd(wmx):
     r = subprocess.run(["bash", os.path.join(ROOT, "tools_dev", "link_daemon.sh")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr

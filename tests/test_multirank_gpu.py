@@ -20,7 +20,7 @@ def test_two_ranks_real_kernels_far_end_through_the_broadcast():
     env.update(WMIX_BENCH_ONE_GPU_GLOO="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     # children of their own: this process makes no GPU call for them
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "chain", "--streams", "512",
-                        "--steps", "6", "--warmup", "2", "--prime", "60", "--spinup", "4", "--no-cpu"],
+                        "--steps", "6", "--warmup", "2", "--prime", "60", "--spinup", "4", "--no-cpu", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -44,7 +44,7 @@ def test_rccl_itself_under_the_multi_rank_code_path():
     env.update(WMIX_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29617", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "chain", "--streams", "512",
-                        "--steps", "6", "--warmup", "2", "--prime", "60", "--spinup", "4", "--no-cpu"],
+                        "--steps", "6", "--warmup", "2", "--prime", "60", "--spinup", "4", "--no-cpu", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -57,7 +57,7 @@ def test_rccl_itself_under_the_multi_rank_code_path():
     # --far-chunk 8: ONE RCCL broadcast per 8 steps, the next chunk in flight while this one computes
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29621", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "chain", "--streams", "512",
-                        "--steps", "6", "--warmup", "2", "--prime", "60", "--spinup", "4", "--no-cpu", "--far-chunk", "8"],
+                        "--steps", "6", "--warmup", "2", "--prime", "60", "--spinup", "4", "--no-cpu", "--full", "--far-chunk", "8"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -71,7 +71,7 @@ def test_one_rank_under_the_launcher_measures_what_the_direct_line_measures():
     Also: the rank's device is its LOCAL_RANK and is reported."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--gpus", "1", "--workload", "chain", "--steps", "40", "--warmup", "5", "--no-cpu"]
+    common = ["--gpus", "1", "--workload", "chain", "--steps", "40", "--warmup", "5", "--no-cpu", "--full"]
     a = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, env=env, capture_output=True, text=True, timeout=900)
     assert a.returncode == 0, a.stderr[-3000:]
     b = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",

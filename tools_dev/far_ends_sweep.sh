@@ -5,7 +5,7 @@ O=gpurun_out/r06
 mkdir -p $O
 TAG=${1:-a}
 for n in 1 256 4096 65536; do
-  timeout -k 10 300 python3 bench.py --far-ends $n --steps 200 --no-cpu --no-configs > $O/far_ends_${TAG}_$n.json 2> $O/far_ends_${TAG}_$n.err || { echo "N=$n failed"; tail -n 5 $O/far_ends_${TAG}_$n.err; break; }
+  timeout -k 10 300 python3 bench.py --far-ends $n --steps 200 --full --no-cpu --no-configs > $O/far_ends_${TAG}_$n.json 2> $O/far_ends_${TAG}_$n.err || { echo "N=$n failed"; tail -n 5 $O/far_ends_${TAG}_$n.err; break; }
 done
 python3 - <<PY
 import json,glob

@@ -1,28 +1,27 @@
 #!/bin/bash
-# link_daemon.sh -- build container only (needs /root/reference): link the UNCHANGED wmix daemon objects against
-# libwmix_amd.so and show, in the linker's own words, which definition of every boundary symbol wins.
+# link_daemon.sh -- link the UNCHANGED wmix daemon objects against libwmix_amd.so and show, in the linker's own words,
+# which definition of every boundary symbol wins.
 #
-#   * src/{wmix,wmixTask,wmixMem,rtp,wav,delay}.c compiled from where they lie, with the reference Makefile's flags
-#     (no -O; MP3/AAC/SPEEX off because their third-party libs are not built here), WITHOUT src/webrtc.c and
-#     src/g711codec.c -- that is INTEGRATION.md section 2;
+#   * src/{wmix,wmixTask,wmixMem,rtp,wav,delay}.c as oracle/Makefile's `ref` target compiles them into oracle/_ref/daemon/
+#     (the reference Makefile's flags: no -O; MP3/AAC/SPEEX off because their third-party libs are not built), WITHOUT
+#     src/webrtc.c and src/g711codec.c -- that is INTEGRATION.md section 2;
 #   * the wmix.h group lives in wmix.o itself: the four symbols are weakened with objcopy and
 #     wmix_amd/csrc/daemon_shim.c supplies the strong definitions that forward into libwmix_amd.so;
 #   * the platform HAL (plat_*: ALSA, not in this image) and the codec wrappers stay undefined -- nothing is stubbed,
 #     the executable is linked with --unresolved-symbols=ignore-all and never run.
 #
-# Nothing from the reference is copied into the repo: objects, map and binary live in a temp dir that is deleted.
+# Nothing from the reference is copied into the repo: the weakened copies, map and binary live in a temp dir that is deleted.
 # Output: one line per boundary symbol "sym <- provider", then OK / FAIL.  Exit 0 only if every symbol is ours.
 set -euo pipefail
-REF=${REF:-/root/reference}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 LIB=$ROOT/wmix_amd/libwmix_amd.so
-[ -d "$REF/src" ] || { echo "no $REF: nothing to link"; exit 3; }
+OBJ=$ROOT/oracle/_ref/daemon
+[ -f "$OBJ/wmix.o" ] || { echo "no $OBJ/wmix.o (oracle/Makefile ref builds it): nothing to link"; exit 3; }
 [ -f "$LIB" ] || { echo "libwmix_amd.so not built"; exit 2; }
-T=$(mktemp -d /tmp/wmixlink.XXXXXX)
+T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
-DEF="-DMAKE_MP3=0 -DMAKE_AAC=0 -DMAKE_SPEEX=0 -DMAKE_SPEEX_BETA3=0 -DMAKE_MATH_FFT=0"
 for f in wmix wmixTask wmixMem rtp wav delay; do
-    gcc -w -c $DEF -I"$REF/src" -I"$REF/platform/alsa" "$REF/src/$f.c" -o "$T/$f.o"
+    cp "$OBJ/$f.o" "$T/$f.o"
 done
 GROUP="wmix_load_data wmix_pcm_zoom wmix_len_of_out wmix_len_of_in"
 DSP="vad_init vad_process vad_release aec_init aec_process2 aec_release ns_init ns_process ns_release agc_init agc_process agc_addition agc_release PCM2G711a G711a2PCM"

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc "$@" -d "$OUT" -o p --output-format csv -- python3 $R/bench.py --no-cpu --steps 20 --warmup 4 ${WMX_PMC_WORKLOAD:+--workload $WMX_PMC_WORKLOAD} > "$OUT/log.txt" 2>&1
+rocprofv3 --kernel-trace --pmc "$@" -d "$OUT" -o p --output-format csv -- python3 $R/bench.py --full --no-cpu --steps 20 --warmup 4 ${WMX_PMC_WORKLOAD:+--workload $WMX_PMC_WORKLOAD} > "$OUT/log.txt" 2>&1
 cd "$R"
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections, re

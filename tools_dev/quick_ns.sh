@@ -1,5 +1,5 @@
 # developer helper: NS parity tests + the default bench line
 T=${1:-t}
 python -m pytest tests/test_ns_gpu.py tests/test_configs_gpu.py -m gpu -x -q > gpurun_out/${T}_pytest.log 2>&1; echo pytest rc=$?; tail -3 gpurun_out/${T}_pytest.log
-python bench.py --steps 40 --warmup 8 --no-cpu > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err; python -c "
-import json;d=json.load(open('gpurun_out/${T}_bench.json'));print(d['ms_per_step'],d['stage_ms'],d['roofline']['frac'])"
+python bench.py --steps 40 --warmup 8 --full --no-cpu | python -c "
+import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print(d['ms_per_step'],d['stage_ms'],d['roofline']['frac'])"

@@ -27,7 +27,7 @@ case $cmd in
     export WMIX_AMD_ALLOW_VARIANT_BUILD=1
     for w in $wl; do for rep in 1 2; do for n in "" "$@"; do
       L=$R/wmix_amd/libwmix_amd.so; [ -n "$n" ] && L=$B/lib_$n.so
-      WMIX_AMD_LIB=$L python $R/bench.py --workload $w --no-cpu --no-configs --steps 300 | python -c '
+      WMIX_AMD_LIB=$L python $R/bench.py --workload $w --full --no-cpu --no-configs --steps 300 | python -c '
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(sys.argv[1], sys.argv[2] or "product", d["build"], round(d["ms_per_step"], 4), (d["roofline"] or {}).get("avg_launch_ms"), (d.get("parity_checked") or {}).get("max_lsb"))' "$w" "$n"
