@@ -16,15 +16,26 @@
  * `keep` ticks and written to --dump for the parity check (tests/test_paced_host_gpu.py replays them through the oracle).
  *
  *   host_paced --streams S [--sub 32768] [--slots 4] [--tick-ms 20] [--ticks 1500] [--prime 150] [--kind pcm|rtp] [--freq 16000]
- *              [--interval-ms 20] [--phases 1] [--calls 0 [--n-far 16]] [--spin 0] [--rt-prio 0] [--pattern file --n-pattern 256] [--dump file --keep 32 --sample a,b,c] [--lat file]
+ *              [--interval-ms 20] [--phases 1] [--calls 0 [--n-far 16]] [--spin 0] [--rt-prio 0] [--late queue|drop] [--pattern file --n-pattern 256]
+ *              [--dump file --keep 32 --sample a,b,c] [--lat file]
  *
  * --phases P > 1: the streams of a server do not all deliver their package at the same instant.  P groups of S / P streams (one
  * wmx_rt each), group g released at t0 + (k * P + g) * tick_ms / P with the whole tick as its period and tick_ms - 2 ms as its budget:
  * wmx_rt_submit at the release, wmx_rt_poll between releases (a completion is seen within microseconds).  The device then works in P
  * short bursts per period and never idles long enough for its power management to clock it down (profiles/r06/README_paced.md).
  *
+ * --late queue (the default): a group whose previous tick is not back at its release is waited for and the new tick queues behind it --
+ * past capacity the backlog never drains.  --late drop: at the release the group is polled, not waited for, and wmx_rt_try_submit sheds
+ * the tick if its predecessor has not landed (every P, one included, then runs the polling loop; needs slots >= 2).  A dropped group-tick
+ * has no latency: the "dropped" field counts it, --lat / --lag mark it NaN, the figures are over the others.  The sampled streams' rows
+ * (and the far-end) of tick t are written into wmx_rt_next_slot from pattern tick t % slots before every release, so what a sampled
+ * stream consumes is a function of t: the pattern minus the dropped packages (the other streams keep the rows the slots were filled
+ * with -- rewriting every row of a group per release would measure the host's memcpy).
+ *
  * pattern file: int16 far [slots][n_far][far_samples] (n_far = 1 without --calls), then rows [slots][n_pattern][row_bytes] (row_bytes from the library).
- * dump file:    rows [keep][n_sample][row_bytes] of the last `keep` ticks.     lat / lag file (--lag): double latency_ms / release_lag_ms [ticks * phases].
+ * dump file:    rows [keep][n_sample][row_bytes] of the last `keep` ticks; with --late drop followed by int32 [keep][n_sample]: the tick
+ *               (prime included) whose output the row is, -1 where that group-tick was dropped (the row is then zeros).
+ * lat / lag file (--lag): double latency_ms / release_lag_ms [ticks * phases].
  *
  * Build (what __graft_entry__.build() runs):
  *   gcc -std=c99 -O2 -Iinclude examples/host_paced.c -o examples/host_paced -Lwmix_amd -lwmix_amd -Wl,-rpath,'$ORIGIN/../wmix_amd' -lm
@@ -94,10 +105,14 @@ int main(int argc, char **argv) {
     const char *sample_s = arg_of(argc, argv, "--sample", "0");
     /* --spin 1: never sleep between ticks, spin on the clock (a core burnt for the sake of never being woken up late) */
     const int64_t spin_ns = atoi(arg_of(argc, argv, "--spin", "0")) ? (int64_t)1 << 60 : 200000;
-    if (S < 1 || ticks < 1 || tick_ms <= 2.0 || slots < 1 || n_pattern < 1 || P < 1 || P > MAX_PHASES || S < P || n_far < 1) {
-        fprintf(stderr, "usage: %s --streams S [--sub N] [--slots N] [--tick-ms T] [--ticks N] [--prime N] [--kind pcm|rtp] [--phases P] ...\n", argv[0]);
+    const char *late = arg_of(argc, argv, "--late", "queue");
+    const int drop = !strcmp(late, "drop");
+    if (S < 1 || ticks < 1 || tick_ms <= 2.0 || slots < 1 || n_pattern < 1 || P < 1 || P > MAX_PHASES || S < P || n_far < 1 || (!drop && strcmp(late, "queue")) ||
+        (drop && slots < 2)) {
+        fprintf(stderr, "usage: %s --streams S [--sub N] [--slots N] [--tick-ms T] [--ticks N] [--prime N] [--kind pcm|rtp] [--phases P] [--late queue|drop] ...\n", argv[0]);
         return 2;
     }
+    const int polled = P > 1 || drop; /* releases by wmx_rt_submit / _try_submit, completions seen by wmx_rt_poll */
     if (keep > ticks) keep = ticks;
     /* --rt-prio N: what a real-time host does about late wake-ups -- SCHED_FIFO at priority N and its pages locked.  Needs
      * CAP_SYS_NICE / an rtprio limit; where the box refuses, the run goes on in the ordinary class and the line says so */
@@ -131,10 +146,12 @@ int main(int argc, char **argv) {
     const size_t row = (size_t)wmx_pipe_datagram_bytes(wmx_rt_pipe(rt[0], 0));
     const size_t far_n = rtp ? 160 : row / 2;
     /* the slots' rows: the pattern, tiled (stream s of the whole server gets pattern row s % n_pattern) */
+    const size_t far_bytes = (size_t)slots * (size_t)n_far * far_n * 2;
+    uint8_t *buf = NULL; /* kept with --late drop: the sampled rows of every tick are written from it */
     if (pattern) {
         FILE *f = fopen(pattern, "rb");
-        const size_t far_bytes = (size_t)slots * (size_t)n_far * far_n * 2, rows_bytes = (size_t)slots * (size_t)n_pattern * row;
-        uint8_t *buf = malloc(far_bytes + rows_bytes);
+        const size_t rows_bytes = (size_t)slots * (size_t)n_pattern * row;
+        buf = malloc(far_bytes + rows_bytes);
         if (!f || !buf || fread(buf, 1, far_bytes + rows_bytes, f) != far_bytes + rows_bytes) {
             fprintf(stderr, "host_paced: cannot read %zu bytes of %s\n", far_bytes + rows_bytes, pattern);
             return 2;
@@ -155,7 +172,10 @@ int main(int argc, char **argv) {
                     }
                 }
             }
-        free(buf);
+        if (!drop) {
+            free(buf);
+            buf = NULL;
+        }
     }
     /* the sample streams whose rows are kept */
     long sample[64];
@@ -169,6 +189,8 @@ int main(int argc, char **argv) {
         free(tmp);
     }
     uint8_t *kept = dump ? calloc((size_t)keep * (size_t)n_sample, row) : NULL;
+    int32_t *kept_tick = dump ? malloc(sizeof(int32_t) * (size_t)keep * (size_t)n_sample) : NULL;
+    for (size_t i = 0; kept_tick && i < (size_t)keep * (size_t)n_sample; i++) kept_tick[i] = -1;
     const int total = ticks * P; /* group-ticks */
     double *lat = malloc(sizeof(double) * (size_t)total), *lag = malloc(sizeof(double) * (size_t)total);
     /* past the start-up phases of every stage, back to back (tick t of a group's life works on slot t % slots) */
@@ -193,6 +215,7 @@ int main(int argc, char **argv) {
                 while (s_ >= wmx_rt_batch_streams(rt[g], b_)) s_ -= wmx_rt_batch_streams(rt[g], b_++);                                   \
                 memcpy(kept + ((size_t)(k_ - (ticks - keep)) * (size_t)n_sample + (size_t)i_) * row,                                     \
                        wmx_pipe_out(wmx_rt_pipe(rt[g], b_), flying_slot[g]) + (size_t)s_ * row, row);                                    \
+                kept_tick[(size_t)(k_ - (ticks - keep)) * (size_t)n_sample + (size_t)i_] = prime + k_;                                   \
             }                                                                                                                            \
     } while (0)
     int64_t next_note = t0 + 30000000000LL;
@@ -203,7 +226,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "host_paced: tick %d of %d\n", j / P, ticks);
             next_note += 30000000000LL;
         }
-        if (P == 1) {
+        if (!polled) {
             sleep_until(due, spin_ns);
         } else {
             for (;;) { /* until the release: see the groups in flight come back */
@@ -221,17 +244,56 @@ int main(int argc, char **argv) {
                     break;
                 }
             }
-            if (flying_j[g] >= 0 && rc == 0) { /* its previous tick is not back yet: the release waits for it (and the wait counts) */
+            if (flying_j[g] >= 0 && rc == 0 && !drop) { /* its previous tick is not back yet: the release waits for it (and the wait counts) */
                 rc = wmx_rt_wait(rt[g]);
                 REAP(g);
             }
         }
         if (rc != 0) break;
+        if (drop) { /* poll, write tick t's sampled rows where it goes, and shed it if the group's previous tick is still on its way */
+            if (flying_j[g] >= 0) {
+                const int d = wmx_rt_poll(rt[g]);
+                if (d < 0) {
+                    rc = d;
+                    break;
+                }
+                if (d == 1) REAP(g);
+            }
+            const int t = prime + j / P, slot = wmx_rt_next_slot(rt[g]), pk = t % slots;
+            if (buf) {
+                if (!calls) memcpy(wmx_rt_far(rt[g], slot), buf + (size_t)pk * far_n * 2, far_n * 2);
+                for (int i = 0; i < n_sample; i++) {
+                    if (sample[i] < lo_of[g] || sample[i] >= lo_of[g + 1]) continue;
+                    long s = sample[i] - lo_of[g];
+                    int b = 0;
+                    while (s >= wmx_rt_batch_streams(rt[g], b)) s -= wmx_rt_batch_streams(rt[g], b++);
+                    memcpy(wmx_pipe_in(wmx_rt_pipe(rt[g], b), slot) + (size_t)s * row, buf + far_bytes + ((size_t)pk * (size_t)n_pattern + (size_t)(sample[i] % n_pattern)) * row, row);
+                    if (calls)
+                        memcpy((uint8_t *)wmx_pipe_far(wmx_rt_pipe(rt[g], b), slot) + (size_t)s * far_n * 2,
+                               buf + ((size_t)pk * (size_t)n_far + (size_t)((sample[i] % n_pattern) % n_far)) * far_n * 2, far_n * 2);
+                }
+            }
+            const int64_t start = now_ns();
+            int got = -1;
+            rc = wmx_rt_try_submit(rt[g], NULL, &got, NULL);
+            if (rc == WMX_DROPPED) {
+                rc = 0;
+                lat[j] = lag[j] = NAN;
+                continue;
+            }
+            if (rc != 0) break;
+            if (flying_j[g] >= 0) REAP(g); /* it landed between the poll and the call (try_submit saw it) */
+            lag[j] = (double)(start - due) * 1e-6;
+            flying_due[g] = due;
+            flying_j[g] = j;
+            flying_slot[g] = got;
+            continue;
+        }
         const int64_t start = now_ns();
         lag[j] = (double)(start - due) * 1e-6;
         flying_due[g] = due;
         flying_j[g] = j;
-        if (P == 1) {
+        if (!polled) {
             rc = wmx_rt_tick(rt[g], NULL, &flying_slot[g], NULL);
             REAP(g);
         } else {
@@ -245,14 +307,17 @@ int main(int argc, char **argv) {
             REAP(g);
         }
     if (rc != 0) fprintf(stderr, "host_paced: failed (rc %d): %s\n", rc, wmx_last_error());
-    long failed = 0;
+    long failed = 0, dropped = 0;
     for (int g = 0; g < P; g++) {
         for (int b = 0; b < wmx_rt_batches(rt[g]); b++) failed += wmx_pipe_failed_steps(wmx_rt_pipe(rt[g], b));
+        dropped += wmx_rt_dropped_ticks(rt[g]);
         wmx_rt_destroy(rt[g]);
     }
+    free(buf);
     if (rc == 0 && dump) {
         FILE *f = fopen(dump, "wb");
         if (!f || fwrite(kept, row, (size_t)keep * (size_t)n_sample, f) != (size_t)keep * (size_t)n_sample) rc = 4;
+        if (f && rc == 0 && drop && fwrite(kept_tick, sizeof(int32_t), (size_t)keep * (size_t)n_sample, f) != (size_t)keep * (size_t)n_sample) rc = 4;
         if (f) fclose(f);
     }
     if (rc == 0 && latf) {
@@ -265,24 +330,37 @@ int main(int argc, char **argv) {
         if (!f || fwrite(lag, sizeof(double), (size_t)total, f) != (size_t)total) rc = 4;
         if (f) fclose(f);
     }
-    int worst = 0, misses = 0, overruns = 0;
+    int worst = -1, misses = 0, overruns = 0, n = 0; /* over the group-ticks that ran (a dropped one is NaN) */
     double lag_max = 0;
     const double budget = tick_ms - 2.0;
     for (int k = 0; k < total; k++) {
-        if (lat[k] > lat[worst]) worst = k;
+        if (isnan(lat[k])) continue;
+        if (worst < 0 || lat[k] > lat[worst]) worst = k;
         if (lag[k] > lag_max) lag_max = lag[k];
         misses += lat[k] > budget;
         overruns += lat[k] > tick_ms;
     }
-    const double worst_ms = lat[worst];
-    qsort(lat, (size_t)total, sizeof(double), cmp_double);
-    qsort(lag, (size_t)total, sizeof(double), cmp_double);
+    const double worst_ms = worst >= 0 ? lat[worst] : 0.0;
+    if (worst < 0) worst = 0;
+    for (int k = 0; k < total; k++)
+        if (!isnan(lat[k])) {
+            lat[n] = lat[k];
+            lag[n++] = lag[k];
+        }
+    if (n == 0) { /* every group-tick dropped */
+        lat[0] = lag[0] = 0.0;
+        n = 1;
+    }
+    qsort(lat, (size_t)n, sizeof(double), cmp_double);
+    qsort(lag, (size_t)n, sizeof(double), cmp_double);
     printf("{\"host\": \"examples/host_paced.c\", \"kind\": \"%s\", \"far_end_per_stream\": %s, \"streams\": %ld, \"phases\": %d, \"sub_batch\": %d, \"sub_batches\": %d, \"slots\": %d, "
            "\"row_bytes\": %zu, \"tick_ms\": %.3f, \"budget_ms\": %.3f, \"ticks\": %d, \"group_ticks\": %d, \"primed_ticks\": %d, \"p50_ms\": %.4f, \"p99_ms\": %.4f, "
            "\"p99_9_ms\": %.4f, \"max_ms\": %.4f, \"misses\": %d, \"overruns_of_the_period\": %d, \"release_lag_p50_ms\": %.4f, \"release_lag_max_ms\": %.4f, "
-           "\"worst_tick\": %d, \"failed_steps\": %ld, \"kept_ticks\": %d, \"sched_fifo\": %s, \"rc\": %d}\n",
-           kind, calls ? "true" : "false", S, P, sub, n_sub, slots, row, tick_ms, budget, ticks, total, prime, quantile(lat, total, 0.5), quantile(lat, total, 0.99),
-           quantile(lat, total, 0.999), worst_ms, misses, overruns, quantile(lag, total, 0.5), lag_max, worst / P, failed, dump ? keep : 0,
-           rt_prio > 0 ? (rt_granted ? "true" : "\"refused\"") : "false", rc);
+           "\"worst_tick\": %d, \"failed_steps\": %ld, \"kept_ticks\": %d, \"sched_fifo\": %s, ",
+           kind, calls ? "true" : "false", S, P, sub, n_sub, slots, row, tick_ms, budget, ticks, total, prime, quantile(lat, n, 0.5), quantile(lat, n, 0.99),
+           quantile(lat, n, 0.999), worst_ms, misses, overruns, quantile(lag, n, 0.5), lag_max, worst / P, failed, dump ? keep : 0,
+           rt_prio > 0 ? (rt_granted ? "true" : "\"refused\"") : "false");
+    if (drop) printf("\"late\": \"drop\", \"dropped\": %ld, ", dropped);
+    printf("\"rc\": %d}\n", rc);
     return rc ? 1 : 0;
 }

@@ -533,7 +533,20 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  *   wmx_rt_tick                both: returns when the last row of the tick is in host memory -- the latency a paced host sees
  *   wmx_rt_step_resident       the tick's launches alone on rows already in HBM (row of stream s at d_rows + s * stride bytes, in place
  *                              for PCM; d_out rows for RTP)
- * Returns 0 or the first sub-batch's error; a failed sub-batch has lost its step (wmx_pipe_failed_steps), the others ran.
+ * Returns 0 or the first sub-batch's error; a failed sub-batch has lost its step (wmx_pipe_failed_steps), the others ran.  A submit first
+ * retires its slot on EVERY sub-batch (the later sub-batches read sub-batch 0's copy of a far-end from host memory), so ticks may be
+ * submitted with no wait in between; a host that stays within `slots` ticks never waits there.
+ * LATE TICKS.  wmx_rt_submit queues a tick behind the one in flight: past capacity (or after a long stall of the device) the backlog
+ * never drains and every later tick carries it.  wmx_rt_try_submit sheds instead -- a late package costs that package, not the rest of
+ * the call (the reference's producers that fell behind jump to the play head, src/wmix.c:1666-1673):
+ *   wmx_rt_try_submit          never blocks.  When the previous tick has not landed in host memory on every sub-batch (its last slot's
+ *                              download complete, asked with hipEventQuery only; a download not yet queued has not landed -- wmx_rt_poll
+ *                              / _wait queue it) it returns WMX_DROPPED and changes nothing: no slot, no upload, no launch, *slot not
+ *                              written, no stream's state advanced (NS, AEC, AGC, VAD, the RTP senders' seq / timestamp).  Otherwise it
+ *                              is wmx_rt_submit.
+ *   wmx_rt_dropped_ticks       the ticks dropped so far (never in wmx_pipe_failed_steps)
+ *   wmx_rt_next_slot           the slot the next (try_)submit takes: the host writes that tick's rows (and far rows) there first.  With
+ *                              try_submit alone at most one tick is in flight, so with slots >= 2 that slot is always free.
  * Streams whose packages are not all due at the same instant are served better as P handles of S / P streams released tick / P apart
  * (wmx_rt_submit at a group's release, wmx_rt_poll on the groups in flight): the device never idles long enough for its power
  * management to clock it down, and the latency is a third.  Measured on one MI355X, 16 kHz, 20 ms ticks, 30 000 ticks: 557 056 streams
@@ -556,6 +569,11 @@ int wmx_rt_batch_streams(const wmx_rt *h, int batch);
 wmx_pipe *wmx_rt_pipe(wmx_rt *h, int batch);
 int16_t *wmx_rt_far(wmx_rt *h, int slot);
 int wmx_rt_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream);
+/* WMX_DROPPED: a positive return, not an error -- the tick was shed (see LATE TICKS above) */
+#define WMX_DROPPED 1
+int wmx_rt_try_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream);
+long wmx_rt_dropped_ticks(const wmx_rt *h);
+int wmx_rt_next_slot(const wmx_rt *h);
 int wmx_rt_wait(wmx_rt *h);
 int wmx_rt_poll(wmx_rt *h); /* non-blocking wmx_rt_wait: 1 = every row of every queued tick is in host memory, 0 = not yet */
 int wmx_rt_tick(wmx_rt *h, const int16_t *d_far, int *slot, void *stream);

@@ -2,7 +2,7 @@
 """paced_host.py -- drive examples/host_paced (the paced heartbeat in C) on the GPU box and prove its rows.
 
     python tools_dev/paced_host.py --streams 393216,425984 --ticks 1500 [--phases 4] [--kind pcm16k|rtp8k] [--tick-ms 20] [--sub 32768]
-                                   [--stop-at-miss] [--out profiles/r06/paced_x.jsonl]
+                                   [--stop-at-miss] [--late queue|drop] [--out profiles/r06/paced_x.jsonl]
 
 Per stream count: writes the pattern file (bench.paced_pattern: `slots` ticks of 256 distinct streams), runs host_paced, replays 12
 sampled streams through the oracle for every tick of the run (start-up included) and compares the rows host_paced kept for the last
@@ -85,6 +85,20 @@ class DeviceWatch:
         return out
 
 
+def replay_ticks(kind, far, rows, pattern_row, ticks, interval_ms):
+    """bench.paced_replay for the ticks a stream consumed, in order (tick t works on pattern slot t % slots): [len(ticks), row]"""
+    import bench
+    from oracle import loader
+    port = loader.port()
+    form, freq = bench.PACED_KINDS[kind]
+    t = np.asarray(ticks) % rows.shape[0]
+    far_seq = np.ascontiguousarray(far[t] if far.ndim == 2 else far[t, pattern_row % far.shape[1]]).reshape(-1)
+    if form == "pcm":
+        return loader.run_chain(port, 1, freq, 5, 15, far_seq, np.ascontiguousarray(rows[t, pattern_row]).reshape(-1), freq // 100 * (interval_ms // 10),
+                                prefix="orc", interval_ms=interval_ms).reshape(len(t), -1)
+    return loader.run_rtp_chain(port, far_seq, np.ascontiguousarray(rows[t, pattern_row]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", required=True)
@@ -101,6 +115,7 @@ def main():
     ap.add_argument("--calls", type=int, default=0, help="1: every stream hears a far-end of its own (wmx_rt_create_pcm_calls), 16 distinct far signals")
     ap.add_argument("--rt-prio", type=int, default=0, help="host_paced asks for SCHED_FIFO at this priority (and mlockall); the line says whether it got it")
     ap.add_argument("--spin", type=int, default=0, help="1: host_paced never sleeps between ticks (spins on the clock)")
+    ap.add_argument("--late", default="queue", help="drop: host_paced sheds a group-tick whose predecessor is not back (wmx_rt_try_submit)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import bench
@@ -119,20 +134,38 @@ def main():
         dump, lat, lag = os.path.join(tmp, "dump.bin"), os.path.join(tmp, "lat.f64"), os.path.join(tmp, "lag.f64")
         cmd = [host, "--streams", str(S), "--sub", str(a.sub), "--slots", str(a.slots), "--tick-ms", str(a.tick_ms), "--ticks", str(a.ticks), "--prime",
                str(a.prime), "--kind", form, "--freq", str(freq), "--interval-ms", str(interval_ms), "--phases", str(a.phases), "--pattern", pat,
-               "--n-pattern", str(n_pat), "--dump", dump, "--keep", str(a.keep), "--sample", ",".join(map(str, sample)), "--lat", lat, "--lag", lag, "--spin", str(a.spin), "--rt-prio", str(a.rt_prio), "--calls", str(a.calls), "--n-far", "16"]
+               "--n-pattern", str(n_pat), "--dump", dump, "--keep", str(a.keep), "--sample", ",".join(map(str, sample)), "--lat", lat, "--lag", lag, "--spin", str(a.spin), "--rt-prio", str(a.rt_prio), "--calls", str(a.calls), "--n-far", "16", "--late", a.late]
         watch = DeviceWatch().start()
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)  # stderr passes through: a long run reports twice a minute
         device = watch.stop()
         if r.returncode != 0:
             sys.exit(1)
         d = json.loads(r.stdout.strip().splitlines()[-1])
-        got = np.fromfile(dump, rows.dtype).reshape(a.keep, len(sample), rows.shape[2])
+        raw = np.fromfile(dump, np.uint8)
+        n_rows = a.keep * len(sample) * rows.shape[2] * rows.itemsize
+        got = raw[:n_rows].view(rows.dtype).reshape(a.keep, len(sample), rows.shape[2])
         T = a.prime + a.ticks
         worst = 0
-        for col, s in enumerate(sample):
-            want = bench.paced_replay(a.kind, far, rows, s % n_pat, T, interval_ms)[T - a.keep:]
-            worst = max(worst, int(np.abs(got[:, col].astype(np.int32) - want.astype(np.int32)).max()))
         lat_ms, lag_ms = np.fromfile(lat, np.float64), np.fromfile(lag, np.float64)
+        if a.late == "drop":  # a stream consumed the start-up and its group's ticks that were not dropped; the dump says which tick each row is
+            tick_of = raw[n_rows:].view(np.int32).reshape(a.keep, len(sample))
+            bounds = [S * g // a.phases for g in range(a.phases + 1)]
+            for col, s in enumerate(sample):
+                g = next(q for q in range(a.phases) if bounds[q] <= s < bounds[q + 1])
+                gone = np.isnan(lat_ms[g::a.phases])
+                consumed = np.concatenate([np.arange(a.prime), a.prime + np.flatnonzero(~gone)])
+                want = replay_ticks(a.kind, far, rows, s % n_pat, consumed, interval_ms)
+                pos = {int(t): i for i, t in enumerate(consumed)}
+                for i, t in enumerate(tick_of[:, col]):
+                    if t >= 0:
+                        worst = max(worst, int(np.abs(got[i, col].astype(np.int32) - want[pos[int(t)]].astype(np.int32)).max()))
+            d["ticks_replayed_note"] = "per stream: the start-up and its group's ticks that were not dropped"
+            kept = ~np.isnan(lat_ms)
+            lat_ms, lag_ms = lat_ms[kept], lag_ms[kept]
+        else:
+            for col, s in enumerate(sample):
+                want = bench.paced_replay(a.kind, far, rows, s % n_pat, T, interval_ms)[T - a.keep:]
+                worst = max(worst, int(np.abs(got[:, col].astype(np.int32) - want.astype(np.int32)).max()))
         # whose hiccup was it?  a slow group-tick (> median + 1.5 ms) started late (the host: its thread overslept, or a predecessor overran)
         # or ran long (the device / the link) -- or both
         svc = lat_ms - lag_ms

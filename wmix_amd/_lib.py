@@ -191,6 +191,12 @@ def _declare(L):
     L.wmx_rt_far.argtypes = [vp, i]
     L.wmx_rt_submit.restype = i
     L.wmx_rt_submit.argtypes = [vp, vp, C.POINTER(i), vp]
+    L.wmx_rt_try_submit.restype = i
+    L.wmx_rt_try_submit.argtypes = [vp, vp, C.POINTER(i), vp]
+    L.wmx_rt_dropped_ticks.restype = C.c_long
+    L.wmx_rt_dropped_ticks.argtypes = [vp]
+    L.wmx_rt_next_slot.restype = i
+    L.wmx_rt_next_slot.argtypes = [vp]
     L.wmx_rt_wait.restype = i
     L.wmx_rt_wait.argtypes = [vp]
     L.wmx_rt_tick.restype = i

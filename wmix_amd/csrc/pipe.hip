@@ -236,6 +236,20 @@ static int pipe_flush(wmx_pipe *h, hipEvent_t gate) {
 
 }  // extern "C"
 
+// Slot k's previous step has left the device (its download queued if it was still owed, then waited for): the slot's buffers are free.
+// Completes only what earlier submits promised; a slot not in flight costs nothing.
+int wmx::pipe_retire(wmx_pipe *h, int k) {
+    wmx_pipe::Slot &s = h->slot[(size_t)k];
+    if (!s.in_flight) return 0;
+    if (h->pending == k) {  // one slot only: its download cannot wait for the next ingest
+        const int rc = pipe_flush(h, s.ev_done);
+        if (rc != 0) return rc;
+    }
+    WMX_HIP(hipEventSynchronize(s.ev_out));
+    s.in_flight = false;
+    return 0;
+}
+
 // wmx_pipe_submit (and the sub-batch form of rt.hip).
 //
 // FAILING CLEAN (round-5 VERDICT weak 6).  Nothing of the pipe's own bookkeeping -- the rotation `next`, `pending`, a slot's
@@ -252,13 +266,9 @@ int wmx::pipe_submit(wmx_pipe *h, const int16_t *d_far, int *slot, void *stream,
     wmx_pipe::Slot &s = h->slot[(size_t)k];
     hipStream_t main = wmx::as_stream(stream);
     // taking the slot: these calls only complete what earlier submits promised (the slot's previous download)
-    if (s.in_flight) {
-        if (h->pending == k) {  // one slot only: its download cannot wait for the next ingest
-            const int rc = pipe_flush(h, s.ev_done);
-            if (rc != 0) return rc;
-        }
-        WMX_HIP(hipEventSynchronize(s.ev_out));  // the slot's previous result has left the device: its buffers are free
-        s.in_flight = false;
+    {
+        const int rc = wmx::pipe_retire(h, k);
+        if (rc != 0) return rc;
     }
     if (flush_for && flush_for != h && h->pending >= 0) {  // a sub-batch whose own download of an earlier tick nobody waited for
         const int rc = pipe_flush(h, h->slot[(size_t)h->pending].ev_done);

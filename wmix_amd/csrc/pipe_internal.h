@@ -46,5 +46,7 @@ int pipe_make(wmx_pipe **out, int n_streams, int slots, bool pcm, int law, int c
 // `d_far_shared` as d_far, but when `upload_far` is false and d_far is NULL nothing is uploaded and far_of's slot copy is used
 // (the tick's far-end went up once, with the first sub-batch).
 int pipe_submit(wmx_pipe *h, const int16_t *d_far, int *slot, void *stream, wmx_pipe *flush_for, const wmx_pipe *far_of);
+// slot k of h is free: its previous step's rows have left the device (the download queued first if it was still owed)
+int pipe_retire(wmx_pipe *h, int k);
 }  // namespace wmx
 

@@ -17,6 +17,7 @@ struct wmx_rt {
     std::vector<wmx_pipe *> pipe;
     hipStream_t s_in, s_out;
     int next;  // the slot of the next tick (every sub-batch rotates in lockstep, also past a failed one)
+    long dropped;  // ticks wmx_rt_try_submit refused because the one before had not landed
     // compute streams of the library's own (wmx_rt_set_compute_streams): sub-batch b runs on cs[b % n_cs], forked from the caller's
     // stream at the start of the tick and joined to it at the end
     static constexpr int kMaxCs = 4;
@@ -85,6 +86,7 @@ static int rt_make(wmx_rt **out, long n_streams, int sub_batch, int slots, bool 
     h->pcm = pcm;
     h->far_rows = far_rows;
     h->next = 0;
+    h->dropped = 0;
     h->n_cs = 1;
     hipError_t e = hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking);
@@ -186,16 +188,65 @@ static int submit_one(wmx_rt *h, size_t b, void *stream, void *vctx) {
     return 0;
 }
 
-int wmx_rt_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
+// Slot k is retired on EVERY sub-batch before anything is uploaded: with a far-end from host memory, sub-batch 0 uploads it into its own
+// slot k and the others read that copy, so sub-batch 0's slot being free says nothing about the later sub-batches of the tick that
+// used slot k before (a host running more than `slots` ticks ahead would overwrite a far-end they are still reading).  The same rule
+// frees the slot's rows of every sub-batch.  A host that never runs more than `slots` ticks ahead finds every slot retired already.
+static int rt_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream) {
     const int k = h->next;
+    for (wmx_pipe *p : h->pipe) {
+        const int rc = wmx::pipe_retire(p, k);
+        if (rc != 0) return rc;  // before the first upload: nothing has moved
+    }
     h->next = (k + 1) % h->slots;  // a tick takes its slot whatever becomes of its sub-batches
     SubmitCtx c{d_far, nullptr, k, false, 0};
     const int rc = rt_launches(h, wmx::as_stream(stream), submit_one, &c);
     if (slot) *slot = k;
     return rc;
 }
+
+int wmx_rt_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    return rt_submit(h, d_far, slot, stream);
+}
+
+// 1 when the previous tick has landed in host memory on every sub-batch, 0 when it has not, < 0 on an error.  Events are queried, never
+// waited for, and nothing is queued: a download still owed (`pending`, queued by wmx_rt_poll / _wait or the next submit) has not landed.
+static int rt_landed(wmx_rt *h) {
+    const int last = (h->next + h->slots - 1) % h->slots;
+    for (wmx_pipe *p : h->pipe) {
+        if (p->pending >= 0) return 0;
+        const wmx_pipe::Slot &s = p->slot[(size_t)last];
+        if (!s.in_flight) continue;
+        const hipError_t q = hipEventQuery(s.ev_out);
+        if (q == hipErrorNotReady) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        if (q != hipSuccess) return wmx::hip_fail(q, "wmx_rt_try_submit: hipEventQuery(ev_out)", __FILE__, __LINE__);
+    }
+    return 1;
+}
+
+// Shed, do not queue: a tick released while its predecessor is still on its way is dropped whole -- WMX_DROPPED, and nothing moves (the
+// rotation, the slots, the pending download, the chain's gate, every stream's state: the dropped packages never reach a stage, as a packet
+// the reference's receiver never got, src/wmixTask.c:1278-1316).  Otherwise exactly wmx_rt_submit.  At most one tick is then in flight,
+// so with slots >= 2 the slot the next call takes (wmx_rt_next_slot) is always free for the host to write.
+int wmx_rt_try_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const int landed = rt_landed(h);
+    if (landed < 0) return landed;
+    if (!landed) {
+        h->dropped++;
+        return WMX_DROPPED;
+    }
+    return rt_submit(h, d_far, slot, stream);
+}
+
+long wmx_rt_dropped_ticks(const wmx_rt *h) { return h ? h->dropped : WMX_EINVAL; }
+int wmx_rt_next_slot(const wmx_rt *h) { return h ? h->next : WMX_EINVAL; }
 
 int wmx_rt_wait(wmx_rt *h) {
     WMX_ON_DEVICE(h);

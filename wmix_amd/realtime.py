@@ -18,6 +18,8 @@ from ._lib import check, lib
 from .chain import AEC, AGC, NS, VAD
 from .pipeline import DATAGRAM, PKT, _host_rows
 
+WMX_DROPPED = 1  # include/wmix_amd.h: wmx_rt_try_submit shed the tick
+
 
 class RtBatch:
     """wmx_rt_create_pcm (kind "pcm": rows are int16 packages of chn x freq x interval_ms) or wmx_rt_create_rtp (kind "rtp": rows are
@@ -85,6 +87,26 @@ class RtBatch:
         slot = C.c_int(-1)
         check(lib().wmx_rt_submit(self._h, self._far(far), C.byref(slot), torch.cuda.current_stream().cuda_stream), "wmx_rt_submit")
         return slot.value
+
+    def try_submit(self, far=None):
+        """wmx_rt_try_submit: queue the tick (True) or, when the previous one has not landed in host memory yet, drop it (False: nothing
+        moved, no stream's state advanced).  Write its rows into `next_slot` first."""
+        slot = C.c_int(-1)
+        rc = lib().wmx_rt_try_submit(self._h, self._far(far), C.byref(slot), torch.cuda.current_stream().cuda_stream)
+        if rc == WMX_DROPPED:
+            return False
+        check(rc, "wmx_rt_try_submit")
+        return True
+
+    @property
+    def dropped(self):
+        """ticks try_submit has dropped so far"""
+        return lib().wmx_rt_dropped_ticks(self._h)
+
+    @property
+    def next_slot(self):
+        """the slot the next submit / try_submit takes"""
+        return lib().wmx_rt_next_slot(self._h)
 
     def wait(self):
         check(lib().wmx_rt_wait(self._h), "wmx_rt_wait")
@@ -206,13 +228,17 @@ def paced_loop(tick_fn, tick_ms, n_ticks, clock=None, clock_every=16, spin_us=30
     return lat, lag, (clock.stop() if clock is not None else [])
 
 
-def paced_groups(submit, poll, wait, n_groups, tick_ms, n_ticks, clock=None, after=None):
+def paced_groups(submit, poll, wait, n_groups, tick_ms, n_ticks, clock=None, after=None, try_submit=None):
     """Staggered release: group g (of n_groups groups of streams, each with the whole tick as its period) is released at
     t0 + (k * n_groups + g) * tick_ms / n_groups -- the streams of a server do not all deliver their package at the same instant, and a
     device that works in n_groups short bursts per period never idles long enough for its power management to clock it down
     (profiles/r06/README_paced.md).  submit(g) queues the group's tick and returns; poll(g) is the non-blocking completion check;
     wait(g) blocks.  Between releases the loop polls the groups in flight, so a completion is seen within microseconds of the last
-    row's arrival.  Returns (latency_ms, lag_ms, clock samples) over all n_ticks * n_groups group-ticks, in release order."""
+    row's arrival.  Returns (latency_ms, lag_ms, clock samples) over all n_ticks * n_groups group-ticks, in release order.
+
+    A group whose previous tick is not back at its release is waited for, and the new tick queues behind it (the backlog counts in
+    its latency).  try_submit(g) -> bool (RtBatch.try_submit) sheds instead: at every release the loop polls and calls try_submit, which
+    queues the tick or drops it; a dropped group-tick has no latency and no lag -- both are NaN (latency_summary(.., dropped=...))."""
     P, sub = n_groups, tick_ms * 1e-3 / n_groups
     total = n_ticks * P
     lat, lag = np.empty(total), np.empty(total)
@@ -240,6 +266,21 @@ def paced_groups(submit, poll, wait, n_groups, tick_ms, n_ticks, clock=None, aft
                 reap()
             elif due - now() > 4e-4:
                 time.sleep(due - now() - 3e-4)
+        if try_submit is not None:
+            if g in flying:
+                reap()
+            start = now()
+            if not try_submit(g):
+                lat[j] = lag[j] = np.nan
+                continue
+            if g in flying:  # it landed between the poll and the call (try_submit saw it)
+                j0, due0 = flying.pop(g)
+                lat[j0] = (start - due0) * 1e3
+                if after is not None:
+                    after(j0, g)
+            flying[g] = (j, due)
+            lag[j] = (start - due) * 1e3
+            continue
         if g in flying:  # its previous tick is not back yet: the release waits for it (and the wait counts)
             reap(block_group=g)
         start = now()
@@ -251,8 +292,14 @@ def paced_groups(submit, poll, wait, n_groups, tick_ms, n_ticks, clock=None, aft
     return lat, lag, (clock.stop() if clock is not None else [])
 
 
-def latency_summary(lat_ms, lag_ms, tick_ms, clk=None):
-    """p50 / p99 / p99.9 / max and the misses against the reference's own budget: tick_ms - 2 ms (src/wmix.c:538)."""
+def latency_summary(lat_ms, lag_ms, tick_ms, clk=None, dropped=None):
+    """p50 / p99 / p99.9 / max and the misses against the reference's own budget: tick_ms - 2 ms (src/wmix.c:538).  dropped: a mask
+    of the ticks that were shed (paced_groups(.., try_submit=..)): the figures are over the others, and "dropped" counts them."""
+    n_dropped, index = None, np.arange(lat_ms.size)
+    if dropped is not None:
+        dropped = np.asarray(dropped, bool)
+        n_dropped, index = int(dropped.sum()), np.flatnonzero(~dropped)
+        lat_ms, lag_ms = lat_ms[index], lag_ms[index]
     budget = tick_ms - 2.0
     q = np.percentile(lat_ms, [50, 99, 99.9])
     out = {"ticks": int(lat_ms.size), "tick_ms": tick_ms, "budget_ms": budget, "p50_ms": round(float(q[0]), 4), "p99_ms": round(float(q[1]), 4),
@@ -261,7 +308,9 @@ def latency_summary(lat_ms, lag_ms, tick_ms, clk=None):
            "release_lag_p50_ms": round(float(np.percentile(lag_ms, 50)), 4), "release_lag_max_ms": round(float(lag_ms.max()), 4),
            # the tick's own duration (actual start -> done), whatever backlog it started with
            "service_p50_ms": round(float(np.percentile(lat_ms - lag_ms, 50)), 4), "service_max_ms": round(float((lat_ms - lag_ms).max()), 4),
-           "worst_tick": int(lat_ms.argmax())}
+           "worst_tick": int(index[lat_ms.argmax()])}
+    if n_dropped is not None:
+        out["dropped"] = n_dropped
     if clk:
         out["sclk_mhz_sampled"] = {"min": int(min(clk)), "median": int(np.median(clk)), "max": int(max(clk)), "samples": len(clk)}
     return out
