@@ -3,6 +3,7 @@
 // ranges, with the invariants the kernels rely on asserted on every plan:
 //   aec_ctl.h        AecCtl:  start-up machine, delay filter, ring indices, block counters (echo_cancellation.c:599-872)
 //   aecm_ctl.h       AecmCtl: the same for the AECM (echo_control_mobile.c:233-720, aecm_core.c:569-664)
+//   cohort_reg.h     the cohort registry both cancellers run: ids, control-plane classes, the planning loop of a launch
 //   agc_gain_table.h the gain-table recipe (digital_agc.c:61-257) for every compression gain, limiter on and off
 //   mix_sched.h      zoom / load schedules and the len_of_* walks for every rate and channel pair the daemon can meet
 // VERDICT r02 item 6 / SURVEY section 5.  Run by tools_dev/sanitize_cpu.sh and tests/test_sanitizers.py.
@@ -10,6 +11,7 @@
 #include <cstdlib>
 #include "aec_ctl.h"
 #include "aecm_ctl.h"
+#include "cohort_reg.h"
 #include "agc_gain_table.h"
 #include "mix_sched.h"
 
@@ -94,19 +96,57 @@ static long drive_aecm(int freq, int pkg, int mode_delay) {
 }
 
 
-// wmx_aec_coalesce's host half: two control planes started `lag` packets apart and called with the same delays.  Once their keys
-// (aec_co_key) are equal, every later plan of the younger one must be the older one's plan under the rotations of aec_co_pair --
-// for thousands of packets, with the delay changing on the way (both see the same change).  Returns the packet at which the keys
-// first met, or -1 if they never did.
-static int drive_pair(int freq, int pkg, int lag, int delay0) {
-    AecCtl a, b;
+// b's plan is a's under the rotations of co_pair (wmx_aec_coalesce)
+static void check_rotated(const AecPlan &pa, const AecPlan &pb, const AecPairCheck &pc) {
+    CHECK(pa.has_far == pb.has_far && pa.far_n == pb.far_n && pa.n_part == pb.n_part && pa.has_near == pb.has_near);
+    CHECK(pa.passthrough == pb.passthrough && pa.n_sub == pb.n_sub && pa.n_blk == pb.n_blk);
+    CHECK(pb.pre_wr == (pa.pre_wr + pc.d_pre) % kAecPreLen);
+    for (int q = 0; q < pa.n_part; q++) {
+        CHECK(pb.part[q].pre_rd == (pa.part[q].pre_rd + pc.d_pre) % kAecPreLen);
+        CHECK(pb.part[q].far_slot == (pa.part[q].far_slot + pc.d_far) % kAecFarBlocks);
+    }
+    for (int q = 0; q < pa.n_sub; q++) {
+        CHECK(pa.sub[q].near_wr == (pb.sub[q].near_wr + pc.d_near) % kAecRing && pa.sub[q].out_rd == (pb.sub[q].out_rd + pc.d_out) % kAecRing);
+        CHECK(pa.sub[q].n_blocks == pb.sub[q].n_blocks && pa.sub[q].first_blk == pb.sub[q].first_blk);
+    }
+    for (int q = 0; q < pa.n_blk; q++) {
+        CHECK(pa.blk[q].near_rd == (pb.blk[q].near_rd + pc.d_near) % kAecRing && pa.blk[q].out_wr == (pb.blk[q].out_wr + pc.d_out) % kAecRing);
+        CHECK(pb.blk[q].far_slot == (pa.blk[q].far_slot + pc.d_far) % kAecFarBlocks);
+        CHECK(((pb.blk[q].hist_n - pa.blk[q].hist_n - pc.d_hist) & (kAecHist - 1)) == 0);
+    }
+}
+// the same for the AECM's plane (wmx_aecm_coalesce)
+static void check_rotated(const AecmPlan &pa, const AecmPlan &pb, const AecmPairCheck &pc) {
+    CHECK(pa.has_far == pb.has_far && pa.far_n == pb.far_n && pa.has_near == pb.has_near && pa.passthrough == pb.passthrough);
+    CHECK(pa.n_frames == pb.n_frames && pa.discard_out == pb.discard_out);
+    CHECK(pb.far_w == (pa.far_w + pc.d_ring) % kAecmFarRing);
+    for (int f = 0; f < pa.n_frames && !pa.passthrough; f++) {
+        const AecmFramePlan &fa = pa.fr[f], &fb = pb.fr[f];
+        CHECK((fa.far_src < 0) == (fb.far_src < 0) && fa.old_slot == fb.old_slot && fa.n_blocks == fb.n_blocks);
+        if (fa.far_src >= 0) CHECK(fb.far_src == (fa.far_src + pc.d_ring) % kAecmFarRing);
+        CHECK(fb.ring_w == (fa.ring_w + pc.d_frame) % kAecmFrameRing && fb.out_r == (fa.out_r + pc.d_out) % kAecmFrameRing);
+        for (int q = 0; q < fa.n_blocks; q++) {
+            CHECK(fb.blk_r[q] == (fa.blk_r[q] + pc.d_frame) % kAecmFrameRing && fb.blk_out_w[q] == (fa.blk_out_w[q] + pc.d_out) % kAecmFrameRing);
+            CHECK(((fb.blk_t[q] - fa.blk_t[q] - pc.d_hist) & (kAecmHist - 1)) == 0);
+        }
+    }
+}
+
+// wmx_*_coalesce's host half: two control planes started `lag` packets apart and called with the same delays.  Once their keys
+// (co_key) are equal, every later plan of the younger one must be the older one's plan under the rotations of co_pair --
+// for thousands of packets, with the delay changing on the way at packet `step` (both see the same change).  Returns the packet at
+// which the keys first met, or -1 if they never did.  The AECM's plane has no periodic counters, so planes meet as soon as both are
+// past their start-up with the same phase of the 80-in-64 re-blocking (4 frames: 2 packets at 16 kHz, 4 at 8 kHz).
+template <class Ctl>
+static int drive_pair(int freq, int pkg, int lag, int delay0, int packets, int step) {
+    Ctl a, b;
     a.init(freq);
     b.init(freq);
     int met = -1;
-    AecPairCheck pc{};
-    for (int p = 0; p < 5200; p++) {
-        const int d = p < 3600 ? delay0 : delay0 + 60;  // a step in the reported delay: EstBufDelay moves both planes alike
-        AecPlan pa, pb;
+    typename Ctl::Pair pc{};
+    for (int p = 0; p < packets; p++) {
+        const int d = p < step ? delay0 : delay0 + 60;  // a step in the reported delay: EstBufDelay moves both planes alike
+        typename Ctl::Plan pa, pb;
         std::memset(&pa, 0, sizeof(pa));
         std::memset(&pb, 0, sizeof(pb));
         CHECK(a.buffer_farend(pkg, &pa) == 0);
@@ -114,201 +154,105 @@ static int drive_pair(int freq, int pkg, int lag, int delay0) {
         if (p < lag) continue;
         CHECK(b.buffer_farend(pkg, &pb) == 0);
         CHECK(b.process(pkg, d, &pb) == 0);
+        typename Ctl::Key ka, kb;
         if (met >= 0) {
-            CHECK(pa.has_far == pb.has_far && pa.far_n == pb.far_n && pa.n_part == pb.n_part && pa.has_near == pb.has_near);
-            CHECK(pa.passthrough == pb.passthrough && pa.n_sub == pb.n_sub && pa.n_blk == pb.n_blk);
-            CHECK(pb.pre_wr == (pa.pre_wr + pc.d_pre) % kAecPreLen);
-            for (int q = 0; q < pa.n_part; q++) {
-                CHECK(pb.part[q].pre_rd == (pa.part[q].pre_rd + pc.d_pre) % kAecPreLen);
-                CHECK(pb.part[q].far_slot == (pa.part[q].far_slot + pc.d_far) % kAecFarBlocks);
-            }
-            for (int q = 0; q < pa.n_sub; q++) {
-                CHECK(pa.sub[q].near_wr == (pb.sub[q].near_wr + pc.d_near) % kAecRing && pa.sub[q].out_rd == (pb.sub[q].out_rd + pc.d_out) % kAecRing);
-                CHECK(pa.sub[q].n_blocks == pb.sub[q].n_blocks && pa.sub[q].first_blk == pb.sub[q].first_blk);
-            }
-            for (int q = 0; q < pa.n_blk; q++) {
-                CHECK(pa.blk[q].near_rd == (pb.blk[q].near_rd + pc.d_near) % kAecRing && pa.blk[q].out_wr == (pb.blk[q].out_wr + pc.d_out) % kAecRing);
-                CHECK(pb.blk[q].far_slot == (pa.blk[q].far_slot + pc.d_far) % kAecFarBlocks);
-                CHECK(((pb.blk[q].hist_n - pa.blk[q].hist_n - pc.d_hist) & (kAecHist - 1)) == 0);
-            }
-            AecCoKey ka, kb;
-            CHECK(aec_co_key(a, &ka) && aec_co_key(b, &kb) && ka == kb);  // and the keys stay equal
-        } else {
-            AecCoKey ka, kb;
-            if (aec_co_key(a, &ka) && aec_co_key(b, &kb) && ka == kb) {
-                met = p;
-                aec_co_pair(a, b, 0, 1, &pc);
-            }
+            check_rotated(pa, pb, pc);
+            CHECK(co_key(a, &ka) && co_key(b, &kb) && ka == kb);  // and the keys stay equal
+        } else if (co_key(a, &ka) && co_key(b, &kb) && ka == kb) {
+            met = p;
+            co_pair(a, b, 0, 1, &pc);
         }
     }
     return met;
 }
+static int drive_pair(int freq, int pkg, int lag, int delay0) { return drive_pair<AecCtl>(freq, pkg, lag, delay0, 5200, 3600); }
+static int drive_pair_aecm(int freq, int pkg, int lag, int delay0) { return drive_pair<AecmCtl>(freq, pkg, lag, delay0, 4000, 2500); }
 
-// the same for the AECM's plane (wmx_aecm_coalesce): no periodic counters, so planes meet as soon as both are past their start-up with
-// the same phase of the 80-in-64 re-blocking (4 frames: 2 packets at 16 kHz, 4 at 8 kHz)
-static int drive_pair_aecm(int freq, int pkg, int lag, int delay0) {
-    AecmCtl a, b;
-    a.init(freq);
-    b.init(freq);
-    int met = -1;
-    AecmPairCheck pc{};
-    for (int p = 0; p < 4000; p++) {
-        const int d = p < 2500 ? delay0 : delay0 + 60;
-        AecmPlan pa, pb;
-        std::memset(&pa, 0, sizeof(pa));
-        std::memset(&pb, 0, sizeof(pb));
-        CHECK(a.buffer_farend(pkg, &pa) == 0);
-        CHECK(a.process(pkg, d, &pa) == 0);
-        if (p < lag) continue;
-        CHECK(b.buffer_farend(pkg, &pb) == 0);
-        CHECK(b.process(pkg, d, &pb) == 0);
-        if (met >= 0) {
-            CHECK(pa.has_far == pb.has_far && pa.far_n == pb.far_n && pa.has_near == pb.has_near && pa.passthrough == pb.passthrough);
-            CHECK(pa.n_frames == pb.n_frames && pa.discard_out == pb.discard_out);
-            CHECK(pb.far_w == (pa.far_w + pc.d_ring) % kAecmFarRing);
-            for (int f = 0; f < pa.n_frames && !pa.passthrough; f++) {
-                const AecmFramePlan &fa = pa.fr[f], &fb = pb.fr[f];
-                CHECK((fa.far_src < 0) == (fb.far_src < 0) && fa.old_slot == fb.old_slot && fa.n_blocks == fb.n_blocks);
-                if (fa.far_src >= 0) CHECK(fb.far_src == (fa.far_src + pc.d_ring) % kAecmFarRing);
-                CHECK(fb.ring_w == (fa.ring_w + pc.d_frame) % kAecmFrameRing && fb.out_r == (fa.out_r + pc.d_out) % kAecmFrameRing);
-                for (int q = 0; q < fa.n_blocks; q++) {
-                    CHECK(fb.blk_r[q] == (fa.blk_r[q] + pc.d_frame) % kAecmFrameRing && fb.blk_out_w[q] == (fa.blk_out_w[q] + pc.d_out) % kAecmFrameRing);
-                    CHECK(((fb.blk_t[q] - fa.blk_t[q] - pc.d_hist) & (kAecmHist - 1)) == 0);
-                }
-            }
-            AecmCoKey ka, kb;
-            CHECK(aecm_co_key(a, &ka) && aecm_co_key(b, &kb) && ka == kb);
-        } else {
-            AecmCoKey ka, kb;
-            if (aecm_co_key(a, &ka) && aecm_co_key(b, &kb) && ka == kb) {
-                met = p;
-                aecm_co_pair(a, b, 0, 1, &pc);
-            }
-        }
-    }
-    return met;
-}
-
-
-// ---- control-plane classes against a model that keeps one plane per cohort (aec.hip runs ONE plane per class and hands every member
-//      its plan): random histories -- cohorts added, retired, restarted, imported over, switched off for a while, reporting delays of
-//      their own for a while -- and after every launch the plan a member gets through its class must be the plan its own plane makes.
-struct ClsHost {
-    std::vector<AecCtl> ctl;
-    std::vector<int32_t> lead;
-    std::vector<uint8_t> live;
-    int n_far = 0;
-    bool cls_dirty = false;
+// ---- control-plane classes against a model that keeps one plane per cohort: the registry of aec.hip / aecm.hip (cohort_reg.h) runs
+//      ONE plane per class and hands every member its plan.  Random histories -- cohorts added, retired, restarted, imported over,
+//      switched off for a while, reporting delays of their own for a while -- and after every launch the plan a member gets through its
+//      class must be the plan its own plane makes.
+template <class Pair>
+struct PairList {  // the modules' lists are their comparison kernels' argument
+    Pair p[32];
 };
+template <class Ctl>
 static void drive_classes(int freq, int pkg, uint32_t seed, int n_start, int ticks) {
+    using Plan = typename Ctl::Plan;
     rng_state = seed;
-    ClsHost h;
-    std::vector<AecCtl> model;  // the reference's way: every cohort (handle) its own plane
-    auto add = [&](bool fresh_class) {
-        int id = -1;
-        for (int g = 0; g < h.n_far; g++)
-            if (!h.live[(size_t)g]) {
-                id = g;
-                break;
-            }
-        if (id < 0) {
-            id = h.n_far++;
-            h.ctl.emplace_back();
-            h.lead.push_back(id);
-            h.live.push_back(1);
-            model.emplace_back();
-        }
-        h.live[(size_t)id] = 1;
-        aec_ctl_own(&h, id);  // wmx_aec_reset_cohort
-        h.ctl[(size_t)id].init(freq);
-        if (!fresh_class) aec_ctl_join(&h, id);
-        model[(size_t)id].init(freq);
-        return id;
-    };
-    // wmx_aec_create_groups: made together, one class
-    h.n_far = n_start;
-    h.ctl.resize((size_t)n_start);
-    model.resize((size_t)n_start);
-    for (int g = 0; g < n_start; g++) {
-        h.ctl[(size_t)g].init(freq);
-        model[(size_t)g].init(freq);
-    }
-    h.lead.assign((size_t)n_start, 0);
-    h.live.assign((size_t)n_start, 1);
-    std::vector<int32_t> delay, leaders, plan_of;
+    CohortReg<Ctl, PairList<typename Ctl::Pair>> h;
+    h.init(n_start, freq);  // wmx_*_create: made together, one class
+    std::vector<Ctl> model((size_t)n_start);  // the reference's way: every cohort (handle) its own plane
+    for (Ctl &c : model) c.init(freq);
+    std::vector<int32_t> delay, rc;
     std::vector<uint8_t> on;
     std::vector<int> odd_until((size_t)n_start, 0), off_until((size_t)n_start, 0);
     long shared = 0, launches = 0;
     for (int t = 0; t < ticks; t++) {
         // churn between launches
         const uint32_t r = rnd() % 400;  // something happens every fifth tick or so: classes have time to exist
-        if (r < 4 && h.n_far < 48) {
-            add(false);
-            odd_until.resize((size_t)h.n_far, 0);
-            off_until.resize((size_t)h.n_far, 0);
+        if (r < 4 && h.n() < 48) {  // wmx_*_add_cohort
+            const int id = h.take_id();
+            if (id == (int)model.size()) model.emplace_back();
+            h.restart(id);
+            model[(size_t)id].init(freq);
+            odd_until.resize((size_t)h.n(), 0);
+            off_until.resize((size_t)h.n(), 0);
         } else if (r < 7) {  // retire one
-            const int g = (int)(rnd() % (uint32_t)h.n_far);
-            if (h.live[(size_t)g] && g != 0) {
-                aec_ctl_own(&h, g);
-                h.live[(size_t)g] = 0;
-            }
+            const int g = (int)(rnd() % (uint32_t)h.n());
+            if (h.live[(size_t)g] && g != 0) h.retire(g);
         } else if (r < 10) {  // restart one (aec_release + aec_init of every member)
-            const int g = (int)(rnd() % (uint32_t)h.n_far);
+            const int g = (int)(rnd() % (uint32_t)h.n());
             if (h.live[(size_t)g]) {
-                aec_ctl_own(&h, g);
-                h.ctl[(size_t)g].init(freq);
-                aec_ctl_join(&h, g);
+                h.restart(g);
                 model[(size_t)g].init(freq);
             }
-        } else if (r < 12) {  // import a cohort's plane over another (wmx_aec_import_cohort)
-            const int a = (int)(rnd() % (uint32_t)h.n_far), b = (int)(rnd() % (uint32_t)h.n_far);
+        } else if (r < 12) {  // import a cohort's plane over another (wmx_*_import_cohort)
+            const int a = (int)(rnd() % (uint32_t)h.n()), b = (int)(rnd() % (uint32_t)h.n());
             if (a != b && h.live[(size_t)a] && h.live[(size_t)b]) {
-                const AecCtl blob = aec_ctl(&h, a);
-                aec_ctl_own(&h, b);
-                h.ctl[(size_t)b] = blob;
-                aec_ctl_join(&h, b);
+                h.import(b, h.plane(a));
                 model[(size_t)b] = model[(size_t)a];
             }
         } else if (r < 16) {
-            odd_until[rnd() % (uint32_t)h.n_far] = t + 1 + (int)(rnd() % 40);  // reports a delay of its own for a while
+            odd_until[rnd() % (uint32_t)h.n()] = t + 1 + (int)(rnd() % 40);  // reports a delay of its own for a while
         } else if (r < 19) {
-            off_until[rnd() % (uint32_t)h.n_far] = t + 1 + (int)(rnd() % 30);  // not called for a while
+            off_until[rnd() % (uint32_t)h.n()] = t + 1 + (int)(rnd() % 30);  // not called for a while
         }
-        delay.assign((size_t)h.n_far, 0);
-        on.assign((size_t)h.n_far, 1);
-        for (int g = 0; g < h.n_far; g++) {
+        delay.assign((size_t)h.n(), 0);
+        on.assign((size_t)h.n(), 1);
+        for (int g = 0; g < h.n(); g++) {
             if (odd_until[(size_t)g] > t) delay[(size_t)g] = 40 + 20 * (g % 3);
             if (off_until[(size_t)g] > t) on[(size_t)g] = 0;
         }
-        // the launch, as wmx_aec_run_cohorts does it
-        aec_classes_split(&h, delay.data(), on.data());
-        aec_classes_list(&h, leaders, plan_of);
+        // the launch, as wmx_*_run_cohorts does it: one packet, far and near
+        int rc_first = 0, running = h.begin_run(3, 0, delay.data(), on.data());
+        h.split(delay.data(), on.data());
+        const std::vector<int32_t> &plan_of = h.list_classes();
         h.cls_dirty = false;
-        std::vector<AecPlan> plans(leaders.size());
-        for (size_t c = 0; c < leaders.size(); c++) {
-            const int g = leaders[c];
-            std::memset(&plans[c], 0, sizeof(AecPlan));
-            if (!h.live[(size_t)g] || !on[(size_t)g]) continue;
-            CHECK(h.ctl[(size_t)g].buffer_farend(pkg, &plans[c]) == 0);
-            CHECK(h.ctl[(size_t)g].process(pkg, delay[(size_t)g], &plans[c]) == 0);
-        }
-        for (int g = 0; g < h.n_far; g++) {
-            CHECK(h.lead[(size_t)g] >= 0 && h.lead[(size_t)g] < h.n_far && h.lead[(size_t)h.lead[(size_t)g]] == h.lead[(size_t)g]);  // leaders lead themselves
+        std::vector<Plan> plans(h.cls_leader.size());
+        running = h.running_classes(on.data());
+        h.plan_chunk(plans.data(), 1, 3, pkg, delay.data(), on.data(), &running, &rc_first);
+        CHECK(rc_first == 0);  // buffer_farend and process took every packet
+        for (int g = 0; g < h.n(); g++) {
+            CHECK(h.lead[(size_t)g] >= 0 && h.lead[(size_t)g] < h.n() && h.lead[(size_t)h.lead[(size_t)g]] == h.lead[(size_t)g]);  // leaders lead themselves
             if (!h.live[(size_t)g]) {
                 CHECK(h.lead[(size_t)g] == g);  // a retired cohort leads nobody and follows nobody
                 continue;
             }
             CHECK(h.live[(size_t)h.lead[(size_t)g]]);
-            AecPlan want;
+            Plan want;
             std::memset(&want, 0, sizeof(want));
             if (on[(size_t)g]) {
                 CHECK(model[(size_t)g].buffer_farend(pkg, &want) == 0);
                 CHECK(model[(size_t)g].process(pkg, delay[(size_t)g], &want) == 0);
             }
-            CHECK(std::memcmp(&want, &plans[(size_t)plan_of[(size_t)g]], sizeof(AecPlan)) == 0);
-            CHECK(aec_ctl(&h, g).same_as(model[(size_t)g]));
+            CHECK(std::memcmp(&want, &plans[(size_t)plan_of[(size_t)g]], sizeof(Plan)) == 0);
+            CHECK(h.plane(g).same_as(model[(size_t)g]));
             shared += h.lead[(size_t)g] != g;
         }
+        rc.assign((size_t)h.n(), 1);
+        h.end_run(on.data(), rc.data());
+        for (int32_t v : rc) CHECK(v == 0);
         launches++;
     }
     CHECK(shared > launches / 4);  // the histories do leave cohorts in shared classes (0.7 - 1 follower per launch on average here)
@@ -361,9 +305,12 @@ int main() {
         }
     }
     for (uint32_t seed : {1u, 7u, 99u}) {
-        drive_classes(16000, 160, seed, 12, 3000);
-        drive_classes(8000, 80, seed + 1000, 5, 2500);
-        drive_classes(8000, 160, seed + 2000, 30, 1500);
+        drive_classes<AecCtl>(16000, 160, seed, 12, 3000);
+        drive_classes<AecCtl>(8000, 80, seed + 1000, 5, 2500);
+        drive_classes<AecCtl>(8000, 160, seed + 2000, 30, 1500);
+        drive_classes<AecmCtl>(16000, 160, seed, 12, 3000);
+        drive_classes<AecmCtl>(8000, 80, seed + 1000, 5, 2500);
+        drive_classes<AecmCtl>(8000, 160, seed + 2000, 30, 1500);
     }
     // ---- coalescing: planes meet as soon as the younger one's start-up is over when they are a multiple of the re-blocking period
     //      apart (160-in-64: 2 packets; 80-in-64: 4 packets) -- the core's two block counters count with the stream, not with the plane

@@ -40,6 +40,7 @@
 #include <vector>
 #include "wmx_internal.h"
 #include "aec_ctl.h"
+#include "cohort_hip.h"
 #include "fft_regs.h"
 #include "libm_dev.h"
 
@@ -1452,35 +1453,13 @@ __global__ void aec_clamp_group(int *stream_far, int n_streams, int n_far) {
 struct wmx_aec {
     int device;  // the HIP device the state lives on (current device at create); every entry point switches to it
     int n_streams, chn, freq, pkg;
-    std::vector<wmx::AecCtl> ctl;  // one control plane per far-end group / cohort (n_far of them) -- of which only the LEADERS' are kept
-                                   // up to date, see `lead`
-    // Control-plane classes.  A control plane is index arithmetic on the call pattern (when the handle was made, packet sizes,
-    // reported delays), never on audio: cohorts that were started at the same point and are called alike have EQUAL planes for ever
-    // -- every mix group of a conference server started together, every call set up in the same tick -- although their far-ends
-    // (and so their far-end histories on the device) differ and they can never be merged.  Such cohorts form a class: lead[g] is
-    // the cohort whose AecCtl stands for g's (lead[g] == g: g leads); a launch runs ONE control plane and uploads ONE plan per class
-    // and packet, and the kernels find a cohort's plan through d_plan_of.  ctl[g] of a follower is stale; aec_ctl() reads through,
-    // aec_ctl_own() makes a cohort the owner of an up-to-date copy before anything treats it differently from its class.
-    std::vector<int32_t> lead;         // [n_far]
-    std::vector<int32_t> cls_leader;   // [n_cls] the leaders, compact
-    std::vector<int32_t> h_plan_of[2]; // [n_far] class index of every cohort; alternating sources of the asynchronous upload
-    int h_plan_of_sel;
-    int32_t *d_plan_of;                // [cap_far]
-    bool cls_dirty;                    // lead[] changed: cls_leader / plan_of are rebuilt (and uploaded) by the next launch
+    // the far-end groups / control cohorts (cohort_reg.h, cohort_hip.h): ids 0 .. co.n() - 1, retired ones included (1 = one shared
+    // far-end); their control planes -- one per control-plane class -- far-end slabs (carved into `far`) and 4 plan slots
+    wmx::CohortDev<wmx::AecCtl, wmx::AecPairChecks, 4> co;
     float *d_state;
     float *d_tmpl;   // the state aec_init gives a stream (reset_streams refills from it)
     float *d_consts;
-    float *d_far;  // one allocation carved into AecFarBufs
     wmx::AecFarBufs far;
-    static constexpr int kPlanBufs = 4;
-    wmx::AecPlan *d_plans;   // kPlanBufs x n_far x kAecMaxPktPerLaunch plans, slots used round robin
-    wmx::AecPlan *h_plans;   // pinned mirror: the asynchronous copy reads it in place, so each slot has its own
-    hipEvent_t plan_free[kPlanBufs];  // recorded behind the kernels that read slot i; waited for before slot i is rewritten
-    bool plan_used[kPlanBufs];
-    int plan_sel;
-    int n_far;               // far-end groups / control cohorts in use, retired ones included (1 = one shared far-end): ids 0 .. n_far - 1
-    int cap_far;             // cohorts the device buffers (far slabs, plan slots) are allocated for; grows by doubling
-    std::vector<uint8_t> live;  // [n_far] 0: retired by wmx_aec_retire_cohort (never called, its id is handed out again)
     int *d_stream_far;       // [n_streams] group of each stream, or nullptr while there has only ever been one
     // cohort-sorted, XCD-aware stream order of the near kernel (see aec_near_kernel); rebuilt on the host when memberships changed
     std::vector<int32_t> h_cohort_of;  // [n_streams] host mirror of d_stream_far
@@ -1493,32 +1472,12 @@ struct wmx_aec {
     static constexpr int kOrderEvery = 16;
     wmx::AecNoiseEntry *d_noise_tab;  // cosf / sinf of the comfort noise's 32 768 possible phases (host libm, aec_ctl.h)
                                       // + 64 x (a_k, c_k): k = 1 .. 64 draws of the generator in one step
-    // wmx_aec_coalesce: the pairs whose device comparison is in flight (`b` < 0: dropped, the two were not called identically since)
-    wmx::AecPairChecks co_pairs;
-    int co_n;
-    bool co_inflight;
-    int *d_co_flags, *h_co_flags;  // [kAecCoMax] device result and its pinned copy
-    hipEvent_t co_done;
-    long co_calls;                 // wmx_aec_coalesce calls so far
-    std::vector<long> co_retry_at; // [n_far] a cohort whose comparison failed is not proposed again before this call
-    long last_far_group_stride;    // of the latest run: cohorts that hear private far-end packets are never candidates
-    long co_merged_total;
-    int16_t *d_zero_far;  // a silent far-end packet for near-only calls that need no far data
     wmx::StreamLife life;
     // in-stream timing of the two kernels (wmx_aec_set_timing): event quadruples [far start | far end | near start | near end]
     bool timing;
     std::vector<hipEvent_t> tev;
     size_t tev_used;
-    // The far kernel is one wave per cohort and needs nothing but the far-end packet: a caller that has other work for the
-    // GPU in front of the near kernel (wmx_chain_process: the noise suppressor) lets it run BESIDE that work on this side
-    // stream instead of alone in front of the near kernel (wmx::aec_fork_far).
-    hipStream_t side;
-    hipEvent_t ev_fork, ev_join;
-    bool fork_pending;
     bool no_order;  // WMIX_AMD_AEC_NO_ORDER (developer A/B switch, read at create): streams in slot order whatever their cohorts
-    // per-call scratch kept with the handle (no allocation on the heartbeat's path)
-    std::vector<int> rc_g;           // [n_far] what the wrapper would have returned to the members of each cohort
-    std::vector<int32_t> same_delay; // [n_far] the one reported delay of wmx_aec_run / _run_groups, spread over the cohorts
     // host time spent in the control planes (the per-cohort, per-packet AecCtl loop of wmx_aec_run_cohorts), summed; wmx_aec_host_ctl
     double ctl_seconds;
     long ctl_calls;
@@ -1532,35 +1491,22 @@ int wmx_aec_destroy(wmx_aec *h) {
     if (!h) return 0;
     if (h->d_state) (void)hipFree(h->d_state);
     if (h->d_consts) (void)hipFree(h->d_consts);
-    if (h->d_far) (void)hipFree(h->d_far);
-    if (h->d_plans) (void)hipFree(h->d_plans);
-    if (h->h_plans) (void)hipHostFree(h->h_plans);
     if (h->d_stream_far) (void)hipFree(h->d_stream_far);
-    if (h->d_plan_of) (void)hipFree(h->d_plan_of);
     if (h->d_order) (void)hipFree(h->d_order);
     if (h->d_noise_tab) (void)hipFree(h->d_noise_tab);
-    if (h->d_co_flags) (void)hipFree(h->d_co_flags);
-    if (h->h_co_flags) (void)hipHostFree(h->h_co_flags);
-    if (h->co_done) (void)hipEventDestroy(h->co_done);
     if (h->d_tmpl) (void)hipFree(h->d_tmpl);
+    h->co.release();
     h->life.release();
     for (hipEvent_t ev : h->tev) (void)hipEventDestroy(ev);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    for (int i = 0; i < wmx_aec::kPlanBufs; i++)
-        if (h->plan_free[i]) (void)hipEventDestroy(h->plan_free[i]);
     delete h;
     return 0;
 }
 
-}  // extern "C"
-static void aec_co_drop(wmx_aec *h, int cohort);
-extern "C" {
-
 int wmx_aec_create(wmx_aec **out, int n_streams, int chn, int freq, int interval_ms) {
     return wmx_aec_create_groups(out, n_streams, chn, freq, interval_ms, 1, nullptr);
 }
+
+}  // extern "C"
 
 // The near kernel's stream order: streams sorted by (re-blocking phase, cohort), cut into chunks of one workgroup (4 streams).  The kernel gives
 // XCD x the slots [x W/8, (x + 1) W/8) of the list in sequence; the list is laid out so that the sorted chunks are DEALT to the XCDs in
@@ -1569,25 +1515,9 @@ int wmx_aec_create(wmx_aec **out, int n_streams, int chn, int freq, int interval
 // side by side.  Evenly matters: a packet is 2.5 blocks at 16 kHz, so a cohort runs 2 or 3 blocks in a launch depending on the phase
 // of its re-blocking ring, and eight cohorts of four phases each laid out one per XCD made every launch as long as a 3-block one
 // (0.82 ms instead of 0.70, measured).  Any permutation is CORRECT (a wave finds its stream's cohort in d_stream_far).
-// ---- control-plane classes (see wmx_aec::lead): aec_ctl / aec_ctl_own / aec_ctl_join / aec_classes_split / aec_classes_list live in
-// aec_ctl.h, free of HIP, so that the sanitizer driver can run them against a per-cohort model
-using wmx::aec_ctl;
-using wmx::aec_ctl_own;
-using wmx::aec_ctl_join;
-// cls_leader / plan_of from lead[], and plan_of onto the device in `s` (alternating host sources, like the stream order)
-static int aec_rebuild_classes(wmx_aec *h, hipStream_t s) {
-    const int G = h->n_far;
-    h->h_plan_of_sel ^= 1;
-    std::vector<int32_t> &po = h->h_plan_of[h->h_plan_of_sel];
-    wmx::aec_classes_list(h, h->cls_leader, po);
-    if (G > 1) WMX_HIP_RC(hipMemcpyAsync(h->d_plan_of, po.data(), sizeof(int32_t) * (size_t)G, hipMemcpyHostToDevice, s));
-    h->cls_dirty = false;
-    return 0;
-}
-
 static int aec_rebuild_order(wmx_aec *h, hipStream_t s) {
     using namespace wmx;
-    const int S = h->n_streams, G = h->n_far;
+    const int S = h->n_streams, G = h->co.n();
     constexpr unsigned kOrderRun = 16;  // chunks dealt to one XCD at a time
     const unsigned wgs = (unsigned)((S + kAecWavesPerBlock - 1) / kAecWavesPerBlock), wgs8 = (wgs + 8u * kOrderRun - 1u) / (8u * kOrderRun) * (8u * kOrderRun);
     // sort key: (phase of the cohort's re-blocking ring, cohort id).  The phase decides how many blocks a packet is for the cohort
@@ -1598,7 +1528,7 @@ static int aec_rebuild_order(wmx_aec *h, hipStream_t s) {
     std::vector<int32_t> rank((size_t)G), by((size_t)G);
     for (int g = 0; g < G; g++) by[(size_t)g] = g;
     std::stable_sort(by.begin(), by.end(), [&](int32_t a, int32_t b) {
-        return aec_ctl(h, a).near_fr.avail_read() < aec_ctl(h, b).near_fr.avail_read();
+        return h->co.plane(a).near_fr.avail_read() < h->co.plane(b).near_fr.avail_read();
     });
     for (int r = 0; r < G; r++) rank[(size_t)by[(size_t)r]] = r;
     std::vector<int32_t> start((size_t)G + 1, 0);
@@ -1615,15 +1545,15 @@ static int aec_rebuild_order(wmx_aec *h, hipStream_t s) {
     }
     if (!h->d_order || h->order_wgs != wgs8) {
         if (h->d_order) {
-            WMX_HIP_RC(hipDeviceSynchronize());
+            WMX_HIP(hipDeviceSynchronize());
             (void)hipFree(h->d_order);
             h->d_order = nullptr;
         }
-        WMX_HIP_RC(hipMalloc(reinterpret_cast<void **>(&h->d_order), ord.size() * sizeof(int32_t)));
+        WMX_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_order), ord.size() * sizeof(int32_t)));
         h->order_wgs = wgs8;
     }
     // in stream order behind the launches that read the previous order (pageable source: the runtime stages it before returning)
-    WMX_HIP_RC(hipMemcpyAsync(h->d_order, ord.data(), ord.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    WMX_HIP(hipMemcpyAsync(h->d_order, ord.data(), ord.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     h->order_dirty = false;
     h->order_age = 0;
     return 0;
@@ -1637,7 +1567,7 @@ static size_t aec_far_words() {
 
 static void aec_carve_far(wmx_aec *h) {
     using namespace wmx;
-    float *p = h->d_far;
+    float *p = static_cast<float *>(h->co.d_far);
     h->far.pre = p;
     p += kAecPreLen;
     h->far.tring = p;
@@ -1654,57 +1584,8 @@ static void aec_carve_far(wmx_aec *h) {
     h->far.group_words = aec_far_words();
 }
 
-// Device buffers for `cap` cohorts and launches of up to `pkts` packets: the far-end slabs (existing ones are carried over),
-// and the plan slots.  Growing is a control-plane operation (the device is drained); it doubles, so a batch that
-// gains cohorts one join at a time reallocates a logarithmic number of times.
-static int aec_reserve(wmx_aec *h, int cap) {
-    using namespace wmx;
-    if (cap <= h->cap_far) return 0;
-    WMX_HIP_RC(hipDeviceSynchronize());  // plans and far slabs may be in use by launches in flight
-    const size_t fw = aec_far_words();
-    int ncap = h->cap_far;
-    if (cap > h->cap_far) {
-        ncap = h->cap_far > 0 ? h->cap_far : 1;
-        while (ncap < cap) ncap *= 2;
-    }
-    // everything new is allocated BEFORE anything old is let go: a failure leaves the handle as it was
-    float *nf = nullptr;
-    AecPlan *nd = nullptr, *nh = nullptr;
-    int32_t *npo = nullptr;
-    const size_t plan_bytes = (size_t)wmx_aec::kPlanBufs * ncap * kAecMaxPktPerLaunch * sizeof(AecPlan);
-    hipError_t e = hipSuccess;
-    if (ncap > h->cap_far) {
-        e = hipMalloc(&nf, fw * (size_t)ncap * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&nd, plan_bytes);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&nh), plan_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(&npo, sizeof(int32_t) * (size_t)ncap);
-        if (e == hipSuccess && h->d_far) e = hipMemcpy(nf, h->d_far, fw * (size_t)h->cap_far * sizeof(float), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess)
-            e = hipMemset(nf + fw * (size_t)h->cap_far, 0, fw * (size_t)(ncap - h->cap_far) * sizeof(float));
-    }
-    if (e != hipSuccess) {
-        if (nf) (void)hipFree(nf);
-        if (nd) (void)hipFree(nd);
-        if (nh) (void)hipHostFree(nh);
-        if (npo) (void)hipFree(npo);
-        return hip_fail(e, "growing the cohort buffers", __FILE__, __LINE__);
-    }
-    if (nf) {
-        if (h->d_far) (void)hipFree(h->d_far);
-        if (h->d_plans) (void)hipFree(h->d_plans);
-        if (h->h_plans) (void)hipHostFree(h->h_plans);
-        if (h->d_plan_of) (void)hipFree(h->d_plan_of);
-        h->d_plan_of = npo;
-        h->cls_dirty = true;  // the new array holds nothing yet
-        h->d_far = nf;
-        h->d_plans = nd;  // plan slots: kPlanBufs x [kAecMaxPktPerLaunch][ncap] (a launch uses the first packets x n_far of its slot)
-        h->h_plans = nh;
-        for (int i = 0; i < wmx_aec::kPlanBufs; i++) h->plan_used[i] = false;  // drained above
-        h->cap_far = ncap;
-        aec_carve_far(h);
-    }
-    return 0;
-}
+
+extern "C" {
 
 int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int interval_ms, int n_far, const int32_t *stream_far) {
     using namespace wmx;
@@ -1735,34 +1616,16 @@ int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int i
     h->chn = chn;
     h->freq = freq;
     h->pkg = freq / 1000 * ((freq <= 8000 && interval_ms % 20 == 0) ? 20 : 10);  // src/webrtc.c:239-248
-    h->ctl.resize((size_t)n_far);
-    for (wmx::AecCtl &c : h->ctl) c.init(freq);
-    h->lead.assign((size_t)n_far, 0);  // made together, equal planes: one class led by cohort 0 until something tells them apart
-    h->h_plan_of_sel = 0;
-    h->d_plan_of = nullptr;
-    h->cls_dirty = true;
-    h->live.assign((size_t)n_far, 1);
-    h->d_state = h->d_consts = h->d_far = h->d_tmpl = nullptr;
+    h->co.init(n_far, freq);  // made together, equal planes: one class until something tells them apart
+    h->co.slab_bytes = aec_far_words() * sizeof(float);
+    h->d_state = h->d_consts = h->d_tmpl = nullptr;
     h->timing = false;
     h->ctl_seconds = 0.0;
     h->ctl_calls = 0;
     h->tev_used = 0;
-    h->side = nullptr;
-    h->ev_fork = h->ev_join = nullptr;
-    h->fork_pending = false;
     h->no_order = getenv("WMIX_AMD_AEC_NO_ORDER") != nullptr;
-    h->d_plans = nullptr;
-    h->h_plans = nullptr;
     h->d_stream_far = nullptr;
     h->d_noise_tab = nullptr;
-    h->co_n = 0;
-    h->co_inflight = false;
-    h->d_co_flags = h->h_co_flags = nullptr;
-    h->co_done = nullptr;
-    h->co_calls = 0;
-    h->co_retry_at.assign((size_t)n_far, 0);
-    h->last_far_group_stride = 0;
-    h->co_merged_total = 0;
     h->d_order = nullptr;
     h->order_wgs = 0;
     h->order_dirty = n_far > 1;
@@ -1771,11 +1634,6 @@ int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int i
     h->h_cohort_of.assign((size_t)n_streams, 0);
     if (n_far > 1 && stream_far)
         for (int i = 0; i < n_streams; i++) h->h_cohort_of[(size_t)i] = stream_far[i];
-    h->n_far = n_far;
-    h->cap_far = 0;
-    h->plan_sel = 0;
-    for (int i = 0; i < wmx_aec::kPlanBufs; i++) h->plan_free[i] = nullptr, h->plan_used[i] = false;
-    h->d_zero_far = nullptr;
     // constants: Ooura tables (frozen rdft_w) + the three curves of aec_core.c:49-103
     AecConsts K;
     memset(&K, 0, sizeof(K));
@@ -1811,9 +1669,9 @@ int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int i
     }
     AEC_TRY(hipMalloc(&h->d_state, (size_t)AS_WORDS * n_streams * sizeof(float)));
     AEC_TRY(hipMalloc(&h->d_consts, sizeof(K) + sizeof(PowTables)));  // [AecConsts | PowTables]; only the first part is copied to LDS
-    for (int i = 0; i < wmx_aec::kPlanBufs; i++) AEC_TRY(hipEventCreateWithFlags(&h->plan_free[i], hipEventDisableTiming));
+    for (hipEvent_t &ev : h->co.plan_free) AEC_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     {
-        const int rc = aec_reserve(h, n_far);
+        const int rc = h->co.reserve(n_far, [h] { aec_carve_far(h); });
         if (rc != 0) {
             wmx_aec_destroy(h);
             return rc;
@@ -1864,161 +1722,43 @@ int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int i
 // from now on.
 int wmx_aec_add_cohort(wmx_aec *h, int *cohort, void *stream) {
     WMX_ON_DEVICE(h);
-    using namespace wmx;
     if (!h || !cohort) return WMX_EINVAL;
-    int id = -1;
-    for (int g = 0; g < h->n_far; g++)
-        if (!h->live[(size_t)g]) {
-            id = g;
-            break;
-        }
-    if (id < 0) {
-        id = h->n_far;
-        const int rc = aec_reserve(h, id + 1);
-        if (rc != 0) return rc;
-        h->ctl.resize((size_t)id + 1);
-        h->lead.push_back(id);
-        h->cls_dirty = true;
-        h->live.push_back(1);
-        h->co_retry_at.push_back(0);
-        h->n_far = id + 1;
-    }
-    if (h->n_far > 1 && !h->d_stream_far) {  // so far every stream was in cohort 0 by construction
-        WMX_HIP_RC(hipMalloc(&h->d_stream_far, sizeof(int) * h->n_streams));
-        WMX_HIP_RC(hipMemsetAsync(h->d_stream_far, 0, sizeof(int) * h->n_streams, as_stream(stream)));
-    }
-    h->live[(size_t)id] = 1;
-    *cohort = id;
-    return wmx_aec_reset_cohort(h, id, stream);
+    const int rc = h->co.add(h->d_stream_far, h->n_streams, wmx::as_stream(stream), cohort, [h] { aec_carve_far(h); });
+    return rc != 0 ? rc : wmx_aec_reset_cohort(h, *cohort, stream);
 }
 
 // The cohort's handles were released (aec_release of every member): it is never called again and its id may be handed out by
 // a later wmx_aec_add_cohort.  Streams still mapped to it must be inactive or be moved before the next call.
-int wmx_aec_retire_cohort(wmx_aec *h, int cohort) {
-    if (!h || cohort < 0 || cohort >= h->n_far) return WMX_EINVAL;
-    aec_ctl_own(h, cohort);  // a retired cohort leads nobody
-    h->live[(size_t)cohort] = 0;
-    aec_co_drop(h, cohort);
-    return 0;
-}
+int wmx_aec_retire_cohort(wmx_aec *h, int cohort) { return wmx::retire_cohort(h, cohort); }
 
-}  // extern "C"
-// ---------------------------------------------------------------- coalescing
-// a cohort that is restarted, retired or overwritten is no candidate of a comparison in flight
-static void aec_co_drop(wmx_aec *h, int cohort) {
-    for (int i = 0; i < h->co_n; i++)
-        if (h->co_pairs.p[i].a == cohort || h->co_pairs.p[i].b == cohort) h->co_pairs.p[i].b = -1;
-}
-extern "C" {
-
-// Merge control cohorts whose planes have converged (include/wmix_amd.h).  Each call first completes the merges whose device
-// comparison -- requested by an earlier call -- came back equal, then proposes up to max_pairs new pairs and launches their
-// comparison behind the work already in `stream`.  Nothing here waits for the device.
+// Merge control cohorts whose planes have converged (include/wmix_amd.h; cohort_hip.h: coalesce).  The merged cohorts' member
+// streams get their rings rotated and their new id on the device; their ids are retired, and the id range ends behind the last
+// live cohort again -- switched-off streams that still carry an id beyond it are parked on cohort 0.
 int wmx_aec_coalesce(wmx_aec *h, int max_pairs, int32_t *merged_from, int32_t *merged_into, int cap, int *n_merged, void *stream) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (n_merged) *n_merged = 0;
-    if (!h || max_pairs < 0 || cap < 0 || (cap > 0 && (!merged_from || !merged_into))) return WMX_EINVAL;
-    hipStream_t s = as_stream(stream);
-    h->co_calls++;
-    if (h->n_far < 2 || !h->d_stream_far) return 0;
-    if (!h->d_co_flags) {
-        WMX_HIP(hipMalloc(&h->d_co_flags, sizeof(int) * kAecCoMax));
-        WMX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->h_co_flags), sizeof(int) * kAecCoMax, hipHostMallocDefault));
-        WMX_HIP(hipEventCreateWithFlags(&h->co_done, hipEventDisableTiming));
-    }
-    int merged = 0;
-    if (h->co_inflight) {
-        const hipError_t q = hipEventQuery(h->co_done);
-        if (q == hipErrorNotReady) return 0;  // the comparison has not run yet: nothing new is proposed on top of it
-        if (q != hipSuccess) return hip_fail(q, "hipEventQuery(co_done)", __FILE__, __LINE__);
-        h->co_inflight = false;
-        AecPairChecks go;
-        int n_go = 0;
-        for (int i = 0; i < h->co_n; i++) {
-            AecPairCheck pc = h->co_pairs.p[i];
-            if (pc.b < 0) continue;  // dropped by a call in between
-            AecCoKey ka, kb;
-            const bool ok = h->h_co_flags[i] == 1 && h->live[(size_t)pc.a] && h->live[(size_t)pc.b] &&
-                            aec_co_key(aec_ctl(h, pc.a), &ka) && aec_co_key(aec_ctl(h, pc.b), &kb) && ka == kb;
-            if (!ok) {
-                h->co_retry_at[(size_t)pc.b] = h->co_calls + 64;
-                continue;
-            }
-            if (merged >= cap) continue;  // no room to report it: proposed again by a later call
-            aec_co_pair(aec_ctl(h, pc.a), aec_ctl(h, pc.b), pc.a, pc.b, &pc);  // the positions of NOW (same differences, by the keys)
-            go.p[n_go++] = pc;
-            merged_from[merged] = pc.b;
-            merged_into[merged] = pc.a;
-            merged++;
-        }
-        h->co_n = 0;
-        if (n_go > 0) {
-            hipLaunchKernelGGL(aec_merge_streams, dim3((unsigned)((h->n_streams + 3) / 4)), dim3(256), 0, s, h->d_state, h->d_stream_far,
-                               h->n_streams, go, n_go);
+    auto merge = [h](const AecPairChecks &go, int n_go, hipStream_t s) {
+        hipLaunchKernelGGL(aec_merge_streams, dim3((unsigned)((h->n_streams + 3) / 4)), dim3(256), 0, s, h->d_state, h->d_stream_far, h->n_streams,
+                           go, n_go);
+        WMX_LAUNCH_CHECK();
+        const int nf = h->co.retire_merged(go.p, n_go);
+        for (int32_t &c : h->h_cohort_of)
+            if (h->co.co_into[(size_t)c] >= 0) c = h->co.co_into[(size_t)c];
+        if (nf < h->co.n()) {
+            hipLaunchKernelGGL(aec_clamp_group, dim3((unsigned)((h->n_streams + 255) / 256)), dim3(256), 0, s, h->d_stream_far, h->n_streams, nf);
             WMX_LAUNCH_CHECK();
-            std::vector<int32_t> to((size_t)h->n_far, -1);
-            for (int i = 0; i < n_go; i++) {
-                to[(size_t)go.p[i].b] = go.p[i].a;
-                aec_ctl_own(h, go.p[i].b);  // a retired cohort leads nobody
-                h->live[(size_t)go.p[i].b] = 0;  // retired: its id may be handed out again (wmx_aec_add_cohort)
-            }
             for (int32_t &c : h->h_cohort_of)
-                if (to[(size_t)c] >= 0) c = to[(size_t)c];
-            // the id range ends behind the last live cohort again (plans, far kernel waves and the caller's per-cohort arrays are
-            // sized by it: wmx_aec_cohorts); switched-off streams that still carry an id beyond it are parked on cohort 0
-            int nf = h->n_far;
-            while (nf > 1 && !h->live[(size_t)nf - 1]) nf--;
-            if (nf < h->n_far) {
-                hipLaunchKernelGGL(aec_clamp_group, dim3((unsigned)((h->n_streams + 255) / 256)), dim3(256), 0, s, h->d_stream_far, h->n_streams, nf);
-                WMX_LAUNCH_CHECK();
-                for (int32_t &c : h->h_cohort_of)
-                    if (c >= nf) c = 0;
-                h->n_far = nf;
-                h->ctl.resize((size_t)nf);
-                h->lead.resize((size_t)nf);
-                h->cls_dirty = true;
-                h->live.resize((size_t)nf);
-                h->co_retry_at.resize((size_t)nf);
-            }
-            h->order_dirty = true;
-            h->order_age = wmx_aec::kOrderEvery;  // the next launch sorts the streams by their new cohorts
-            h->co_merged_total += n_go;
+                if (c >= nf) c = 0;
+            h->co.shrink(nf);
         }
-    }
-    if (n_merged) *n_merged = merged;
-    if (max_pairs == 0 || h->last_far_group_stride != 0) return 0;
-    if (max_pairs > kAecCoMax) max_pairs = kAecCoMax;
-    // candidates: the first live cohort with a key leads, every later one with the same key may join it
-    // (the lowest ids survive, so that the id range can shrink behind them); keys meet through a hash of their words
-    std::unordered_multimap<uint64_t, int> leads;
-    leads.reserve((size_t)h->n_far);
-    int n = 0;
-    for (int g = 0; g < h->n_far && n < max_pairs; g++) {
-        if (!h->live[(size_t)g]) continue;
-        AecCoKey k, kl;
-        if (!aec_co_key(aec_ctl(h, g), &k)) continue;
-        uint64_t hash = 1469598103934665603ull;
-        for (int v : k.v) hash = (hash ^ (uint32_t)v) * 1099511628211ull;
-        int lead = -1;
-        const auto range = leads.equal_range(hash);
-        for (auto it = range.first; it != range.second && lead < 0; ++it)
-            if (aec_co_key(aec_ctl(h, it->second), &kl) && kl == k) lead = it->second;
-        if (lead < 0) {
-            leads.emplace(hash, g);
-            continue;
-        }
-        if (h->co_retry_at[(size_t)g] > h->co_calls) continue;
-        aec_co_pair(aec_ctl(h, lead), aec_ctl(h, g), lead, g, &h->co_pairs.p[n++]);
-    }
-    h->co_n = n;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(aec_cohort_equal, dim3((unsigned)n), dim3(256), 0, s, h->far, h->co_pairs, h->d_co_flags);
-    WMX_LAUNCH_CHECK();
-    WMX_HIP(hipMemcpyAsync(h->h_co_flags, h->d_co_flags, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
-    WMX_HIP(hipEventRecord(h->co_done, s));
-    h->co_inflight = true;
-    return 0;
+        h->order_dirty = true;
+        h->order_age = wmx_aec::kOrderEvery;  // the next launch sorts the streams by their new cohorts
+        return 0;
+    };
+    auto equal = [h](int n, hipStream_t s) {
+        hipLaunchKernelGGL(aec_cohort_equal, dim3((unsigned)n), dim3(256), 0, s, h->far, h->co.co_pairs, h->co.d_co_flags);
+    };
+    return coalesce(h, max_pairs, merged_from, merged_into, cap, n_merged, stream, h ? h->d_stream_far : nullptr, merge, equal);
 }
 
 int wmx_aec_packet_samples(const wmx_aec *h) { return h ? h->pkg * h->chn : WMX_EINVAL; }
@@ -2042,14 +1782,9 @@ int wmx_aec_run(wmx_aec *h, int mode, const int16_t *d_far, long far_packet_stri
 
 int wmx_aec_run_groups(wmx_aec *h, int mode, const int16_t *d_far, long far_packet_stride, long far_group_stride, const int16_t *d_near,
                        int16_t *d_out, int n_packets, long stream_stride, long packet_stride, int delay_ms, void *stream) {
-    if (!h) {
-        wmx::set_error("wmx_aec_run: bad argument");
-        return WMX_EINVAL;
-    }
-    // every far-end group in lockstep: same reported delay, all switched on
-    h->same_delay.assign((size_t)h->n_far, delay_ms);
+    // every far-end group in lockstep: same reported delay, all switched on (no handle: wmx_aec_run_cohorts says so)
     return wmx_aec_run_cohorts(h, mode, d_far, far_packet_stride, far_group_stride, d_near, d_out, n_packets, stream_stride, packet_stride,
-                               h->same_delay.data(), nullptr, nullptr, stream);
+                               h ? h->co.same_delays(delay_ms) : nullptr, nullptr, nullptr, stream);
 }
 
 // The general form.  A far-end group is also a control COHORT: its streams were started together (aec_init at the same
@@ -2063,172 +1798,72 @@ int wmx_aec_run_cohorts(wmx_aec *h, int mode, const int16_t *d_far, long far_pac
                         const uint8_t *cohort_on, int32_t *cohort_rc, void *stream) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    // a fork point (wmx::aec_fork_far) belongs to THIS call, whichever way it ends: taken over here, used by the first chunk that
-    // launches, and gone on every other path (argument errors, every cohort switched off) -- a later call must not start its
-    // far kernel on the side stream behind a stale event (round-3 ADVICE)
-    const bool fork_here = h && h->fork_pending;
-    if (h) h->fork_pending = false;
-    if (!h || n_packets < 0 || (mode & 3) == 0 || !delay_ms) {
+    if (!h) {
         set_error("wmx_aec_run: bad argument");
         return WMX_EINVAL;
     }
-    const int G = h->n_far;
-    if (cohort_rc)
-        for (int g = 0; g < G; g++) cohort_rc[g] = 0;
-    if (n_packets == 0) return 0;  // frameNum == 0: nothing to do, whatever the pointers are
-    if (((mode & 1) && !d_far) || ((mode & 2) && (!d_near || !d_out))) {
-        set_error("wmx_aec_run: null buffer");
-        return WMX_EINVAL;
-    }
-    const long per_pkt = (long)h->pkg * h->chn;
-    if ((mode & 2) && (packet_stride < per_pkt || (h->n_streams > 1 && stream_stride < per_pkt))) {
-        set_error("wmx_aec_run: strides (%ld, %ld) smaller than a packet (%ld samples)", stream_stride, packet_stride, per_pkt);
-        return WMX_EINVAL;
-    }
-    if ((mode & 1) && far_packet_stride < per_pkt && n_packets > 1) {
-        set_error("wmx_aec_run: far stride %ld smaller than a packet (%ld samples)", far_packet_stride, per_pkt);
-        return WMX_EINVAL;
-    }
     hipStream_t s = as_stream(stream);
-    const float gpow1np = 0.1f * 12;  // gPow[1] * num_partitions (aec_core.c:1212), evaluated in float like the reference
-    std::vector<int> &rc_g = h->rc_g;  // a cohort whose call was rejected runs nothing after the offending packet
-    rc_g.assign((size_t)G, 0);
-    int rc_first = 0, running = 0;
-    for (int g = 0; g < G; g++) running += (h->live[(size_t)g] && (!cohort_on || cohort_on[g])) ? 1 : 0;
-    h->last_far_group_stride = (mode & 1) ? far_group_stride : h->last_far_group_stride;
-    // pairs whose comparison is in flight (wmx_aec_coalesce) stay candidates only while the two cohorts are called identically
-    for (int i = 0; i < h->co_n; i++) {
-        AecPairCheck &pc = h->co_pairs.p[i];
-        if (pc.b < 0) continue;
-        const bool on_a = !cohort_on || cohort_on[pc.a], on_b = !cohort_on || cohort_on[pc.b];
-        if (on_a != on_b || (on_a && delay_ms[pc.a] != delay_ms[pc.b]) || ((mode & 1) && far_group_stride != 0)) pc.b = -1;
-    }
-    // Everything that can fail for lack of memory happens HERE, before a control plane has moved: a call that returns an error has
-    // advanced neither the host's planes nor the device's far-end history (round-4 ADVICE: the stream order used to be rebuilt --
-    // an allocation and an upload -- between the far and the near kernel of a chunk whose planes had already been advanced).
-    const bool ordered = (mode & 2) && h->d_stream_far != nullptr && !h->no_order;
-    if (ordered && running > 0 && (h->d_order == nullptr || (h->order_dirty && h->order_age >= wmx_aec::kOrderEvery))) {
-        const int rc = aec_rebuild_order(h, s);
-        if (rc != 0) return rc;
-    }
-    // Control-plane classes: a follower that is called differently from its leader in THIS call (switched on / off alone, another
-    // reported delay) takes a plane of its own first.  (wmx_aec_run / _run_groups hand every cohort the same delay and no switches.)
-    if (G > 1 && (cohort_on || delay_ms != h->same_delay.data())) wmx::aec_classes_split(h, delay_ms, cohort_on);
-    bool classes_moved = false;
-    if (h->cls_dirty) {
-        // uploaded in `s`, behind every launch that still reads the old classes; a far kernel forked onto the side stream would not
-        // wait for it (its fork point lies in front of this call): this one launch keeps the far kernel in line
-        const int rc = aec_rebuild_classes(h, s);
-        if (rc != 0) return rc;
-        classes_moved = true;
-    }
-    const int C = (int)h->cls_leader.size();
-    const int32_t *plan_of = G > 1 ? h->d_plan_of : nullptr;
-    running = 0;
-    for (int c = 0; c < C; c++) {
-        const int g = h->cls_leader[(size_t)c];
-        running += (h->live[(size_t)g] && (!cohort_on || cohort_on[g])) ? 1 : 0;
-    }
-    for (int done = 0; done < n_packets && running > 0;) {
-        int chunk = n_packets - done;
-        if (chunk > kAecMaxPktPerLaunch) chunk = kAecMaxPktPerLaunch;
-        // the next plan slot: its pinned host half and its device half are rewritten only after the kernels that read the
-        // device half last have finished, whatever stream they ran on (round-1 ADVICE: the single buffer was reused blindly)
-        const int sel = h->plan_sel;
-        h->plan_sel = (sel + 1) % wmx_aec::kPlanBufs;
-        if (h->plan_used[sel]) WMX_HIP(hipEventSynchronize(h->plan_free[sel]));
-        const size_t slot = (size_t)sel * h->cap_far * kAecMaxPktPerLaunch;
-        AecPlan *hp = h->h_plans + slot, *dp = h->d_plans + slot;  // [packet][class], C apart: chunk x C plans are uploaded
-        int any = 0;
+    bool ordered = false;
+    hipEvent_t *tv = nullptr;
+    auto before = [&](int running) {
+        ordered = (mode & 2) && h->d_stream_far != nullptr && !h->no_order;
+        if (ordered && running > 0 && (h->d_order == nullptr || (h->order_dirty && h->order_age >= wmx_aec::kOrderEvery))) return aec_rebuild_order(h, s);
+        return 0;
+    };
+    // host time of the control planes (wmx_aec_host_ctl)
+    auto plan = [h](auto loop) {
         const auto t_ctl = std::chrono::steady_clock::now();
-        for (int c = 0; c < C; c++) {
-            const int g = h->cls_leader[(size_t)c];  // the class's one control plane
-            const bool on = h->live[(size_t)g] && (!cohort_on || cohort_on[g]) && rc_g[g] == 0;
-            for (int k = 0; k < chunk; k++) {
-                AecPlan &pl = hp[(size_t)k * C + c];
-                memset(&pl, 0, offsetof(AecPlan, blk));
-                if (!on || rc_g[g] != 0) continue;  // has_far = has_near = 0: both kernels skip the packet for this class's cohorts
-                any = 1;
-                if (mode & 1) {
-                    const int r = h->ctl[(size_t)g].buffer_farend(h->pkg, &pl);
-                    if (r != 0) {
-                        pl.has_far = 0;
-                        rc_g[g] = r;
-                        continue;
-                    }
-                }
-                if (mode & 2) {
-                    const int r = h->ctl[(size_t)g].process(h->pkg, delay_ms[g], &pl);
-                    if (r != 0) {  // src/webrtc.c:463-468: the wrapper stops here; nothing of this packet is written
-                        pl.has_near = 0;
-                        rc_g[g] = r;
-                    }
-                }
-            }
-            if (on && rc_g[g] != 0) {
-                running--;
-                if (rc_first == 0) rc_first = rc_g[g];
-            }
-        }
+        const int any = loop();
         h->ctl_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ctl).count();
         h->ctl_calls++;
-        if (any) {
-            // (with many cohorts in one class every far wave would store the same plan into the same line: those read the upload)
-            const int by_value = (chunk == 1 && C == 1 && G == 1) ? 1 : 0;
-            // the far kernel (and the plans it reads) on the side stream when the caller forked it (first chunk of the call only)
-            const bool forked = fork_here && done == 0 && (mode & 2) && !classes_moved;
-            hipStream_t fs = forked ? h->side : s;
-            if (forked) WMX_HIP(hipStreamWaitEvent(fs, h->ev_fork, 0));
-            if (!by_value) WMX_HIP(hipMemcpyAsync(dp, hp, (size_t)C * chunk * sizeof(AecPlan), hipMemcpyHostToDevice, fs));
-            hipEvent_t *tv = nullptr;
-            if (h->timing && (mode & 2)) {
-                if (h->tev_used + 4 > wmx_aec::kMaxTimingEvents) h->tev_used = 0;  // nobody polls: start over on the oldest events
-                if (h->tev_used + 4 > h->tev.size())
-                    for (int k = 0; k < 4; k++) {
-                        hipEvent_t ev;
-                        WMX_HIP(hipEventCreate(&ev));
-                        h->tev.push_back(ev);
-                    }
-                tv = &h->tev[h->tev_used];
-                h->tev_used += 4;
-                WMX_HIP(hipEventRecord(tv[0], fs));
-            }
-            hipLaunchKernelGGL(aec_far_kernel, dim3((unsigned)G), dim3(64), 0, fs, h->far, h->d_consts, dp, chunk, C, plan_of,
-                               d_far ? d_far + (size_t)done * far_packet_stride : nullptr, far_packet_stride, far_group_stride, h->chn, gpow1np,
-                               by_value, hp[0]);
-            WMX_LAUNCH_CHECK();
-            if (tv) WMX_HIP(hipEventRecord(tv[1], fs));
-            if (forked) {
-                WMX_HIP(hipEventRecord(h->ev_join, fs));
-                WMX_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
-            }
-            if (tv) WMX_HIP(hipEventRecord(tv[2], s));
-            if (mode & 2) {
-                const int16_t *nin = d_near + (size_t)done * packet_stride;
-                int16_t *nout = d_out + (size_t)done * packet_stride;
-                if (h->order_age < wmx_aec::kOrderEvery) h->order_age++;  // saturates: a service runs for months
-                const int32_t *order = ordered ? h->d_order : nullptr;
-                const unsigned grid = ordered ? h->order_wgs : (unsigned)((h->n_streams + kAecWavesPerBlock - 1) / kAecWavesPerBlock);
-                const dim3 blk(64 * kAecWavesPerBlock);
-                if (h->freq == 8000)
-                    hipLaunchKernelGGL((aec_near_kernel<1>), dim3(grid), blk, 0, s, h->d_state, h->far, h->d_consts, dp, chunk, C, plan_of,
-                                       h->d_noise_tab, nin, nout, h->n_streams, stream_stride, packet_stride, h->chn, h->pkg, h->d_stream_far,
-                                       h->life.d_active, order);
-                else
-                    hipLaunchKernelGGL((aec_near_kernel<2>), dim3(grid), blk, 0, s, h->d_state, h->far, h->d_consts, dp, chunk, C, plan_of,
-                                       h->d_noise_tab, nin, nout, h->n_streams, stream_stride, packet_stride, h->chn, h->pkg, h->d_stream_far,
-                                       h->life.d_active, order);
-                WMX_LAUNCH_CHECK();
-                if (tv) WMX_HIP(hipEventRecord(tv[3], s));
-            }
-            WMX_HIP(hipEventRecord(h->plan_free[sel], s));
-            h->plan_used[sel] = true;
+        return any;
+    };
+    auto far = [&](hipStream_t fs, const CohortLaunch<AecPlan> &L) {
+        const float gpow1np = 0.1f * 12;  // gPow[1] * num_partitions (aec_core.c:1212), evaluated in float like the reference
+        // (with many cohorts in one class every far wave would store the same plan into the same line: those read the upload)
+        if (!L.by_value) WMX_HIP(hipMemcpyAsync(L.dp, L.hp, (size_t)L.C * L.chunk * sizeof(AecPlan), hipMemcpyHostToDevice, fs));
+        tv = nullptr;
+        if (h->timing && (mode & 2)) {
+            if (h->tev_used + 4 > wmx_aec::kMaxTimingEvents) h->tev_used = 0;  // nobody polls: start over on the oldest events
+            if (h->tev_used + 4 > h->tev.size())
+                for (int k = 0; k < 4; k++) {
+                    hipEvent_t ev;
+                    WMX_HIP(hipEventCreate(&ev));
+                    h->tev.push_back(ev);
+                }
+            tv = &h->tev[h->tev_used];
+            h->tev_used += 4;
+            WMX_HIP(hipEventRecord(tv[0], fs));
         }
-        done += chunk;
-    }
-    if (cohort_rc)
-        for (int g = 0; g < G; g++) cohort_rc[g] = (h->live[(size_t)g] && (!cohort_on || cohort_on[g])) ? rc_g[(size_t)h->lead[(size_t)g]] : 0;
-    return rc_first;
+        hipLaunchKernelGGL(aec_far_kernel, dim3((unsigned)L.G), dim3(64), 0, fs, h->far, h->d_consts, L.dp, L.chunk, L.C, L.plan_of,
+                           d_far ? d_far + (size_t)L.done * far_packet_stride : nullptr, far_packet_stride, far_group_stride, h->chn, gpow1np,
+                           L.by_value, L.hp[0]);
+        WMX_LAUNCH_CHECK();
+        if (tv) WMX_HIP(hipEventRecord(tv[1], fs));
+        return 0;
+    };
+    auto near = [&](const CohortLaunch<AecPlan> &L) {
+        if (tv) WMX_HIP(hipEventRecord(tv[2], s));
+        const int16_t *nin = d_near + (size_t)L.done * packet_stride;
+        int16_t *nout = d_out + (size_t)L.done * packet_stride;
+        if (h->order_age < wmx_aec::kOrderEvery) h->order_age++;  // saturates: a service runs for months
+        const int32_t *order = ordered ? h->d_order : nullptr;
+        const unsigned grid = ordered ? h->order_wgs : (unsigned)((h->n_streams + kAecWavesPerBlock - 1) / kAecWavesPerBlock);
+        const dim3 blk(64 * kAecWavesPerBlock);
+        if (h->freq == 8000)
+            hipLaunchKernelGGL((aec_near_kernel<1>), dim3(grid), blk, 0, s, h->d_state, h->far, h->d_consts, L.dp, L.chunk, L.C, L.plan_of,
+                               h->d_noise_tab, nin, nout, h->n_streams, stream_stride, packet_stride, h->chn, h->pkg, h->d_stream_far,
+                               h->life.d_active, order);
+        else
+            hipLaunchKernelGGL((aec_near_kernel<2>), dim3(grid), blk, 0, s, h->d_state, h->far, h->d_consts, L.dp, L.chunk, L.C, L.plan_of,
+                               h->d_noise_tab, nin, nout, h->n_streams, stream_stride, packet_stride, h->chn, h->pkg, h->d_stream_far,
+                               h->life.d_active, order);
+        WMX_LAUNCH_CHECK();
+        if (tv) WMX_HIP(hipEventRecord(tv[3], s));
+        return 0;
+    };
+    return run_cohorts(h, "wmx_aec_run", mode, d_far, far_packet_stride, far_group_stride, d_near, d_out, n_packets, stream_stride,
+                       packet_stride, delay_ms, cohort_on, cohort_rc, s, before, plan, far, near);
 }
 
 // aec_release + aec_init for the listed streams (src/webrtc.c:217-274, 485-505): InitAec state.  cohort >= 0 also moves them
@@ -2238,8 +1873,8 @@ int wmx_aec_run_cohorts(wmx_aec *h, int mode, const int16_t *d_far, long far_pac
 int wmx_aec_reset_streams(wmx_aec *h, const int32_t *idx, int n, int cohort, void *stream) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || n < 0 || (n > 0 && !idx) || cohort < -1 || cohort >= h->n_far) return WMX_EINVAL;
-    if (cohort >= 0 && h->n_far > 1 && !h->d_stream_far) return WMX_ESTATE;
+    if (!h || n < 0 || (n > 0 && !idx) || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
+    if (cohort >= 0 && h->co.n() > 1 && !h->d_stream_far) return WMX_ESTATE;
     if (n == 0) return 0;
     hipStream_t s = as_stream(stream);
     const int32_t *d_idx = nullptr;
@@ -2259,17 +1894,7 @@ int wmx_aec_reset_streams(wmx_aec *h, const int32_t *idx, int n, int cohort, voi
 // aec_init for a whole cohort's SHARED part: the control plane starts over (start-up phase, empty far-end buffer, ring
 // positions, comfort-noise seed) and the far-end history of the group is cleared.  The member streams are reset with
 // wmx_aec_reset_streams(..., cohort, ...).
-int wmx_aec_reset_cohort(wmx_aec *h, int cohort, void *stream) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || cohort < 0 || cohort >= h->n_far) return WMX_EINVAL;
-    aec_ctl_own(h, cohort);
-    h->ctl[(size_t)cohort].init(h->freq);
-    aec_ctl_join(h, cohort);  // cohorts restarted at the same point of the packet sequence run one control plane
-    aec_co_drop(h, cohort);
-    WMX_HIP(hipMemsetAsync(h->d_far + (size_t)cohort * h->far.group_words, 0, h->far.group_words * sizeof(float), as_stream(stream)));
-    return 0;
-}
+int wmx_aec_reset_cohort(wmx_aec *h, int cohort, void *stream) { return wmx::reset_cohort(h, cohort, stream); }
 
 int wmx_aec_set_active(wmx_aec *h, const uint8_t *host_mask, void *stream) {
     WMX_ON_DEVICE(h);
@@ -2285,7 +1910,7 @@ int wmx_aec_set_active(wmx_aec *h, const uint8_t *host_mask, void *stream) {
 static constexpr uint32_t kAecBlobVersion = 2, kAecCohortBlobVersion = 2;
 int wmx_aec_stream_state_bytes(const wmx_aec *h) { return h ? (int)(sizeof(wmx::BlobHeader) + wmx::AS_WORDS * 4) : WMX_EINVAL; }
 int wmx_aec_cohort_state_bytes(const wmx_aec *h) {
-    return h ? (int)(sizeof(wmx::BlobHeader) + sizeof(wmx::AecCtl) + h->far.group_words * 4) : WMX_EINVAL;
+    return h ? h->co.blob_bytes() : WMX_EINVAL;
 }
 
 int wmx_aec_export_stream(wmx_aec *h, int stream_index, void *host_blob) {
@@ -2302,7 +1927,7 @@ int wmx_aec_export_stream(wmx_aec *h, int stream_index, void *host_blob) {
 int wmx_aec_import_stream(wmx_aec *h, int stream_index, const void *host_blob, int cohort) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams || cohort < -1 || cohort >= h->n_far) return WMX_EINVAL;
+    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
     const int rc = blob_check(host_blob, blob_tag("AEC "), blob_layout((uint32_t)h->freq, kAecBlobVersion), AS_WORDS * 4);
     if (rc) return rc;
     WMX_HIP(hipDeviceSynchronize());
@@ -2319,69 +1944,29 @@ int wmx_aec_import_stream(wmx_aec *h, int stream_index, const void *host_blob, i
 int wmx_aec_export_cohort(wmx_aec *h, int cohort, void *host_blob) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || !host_blob || cohort < 0 || cohort >= h->n_far) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    char *p = static_cast<char *>(host_blob);
-    const size_t fb = h->far.group_words * 4;
-    blob_begin(p, blob_tag("AECc"), blob_layout((uint32_t)h->freq, kAecCohortBlobVersion), (uint32_t)(sizeof(AecCtl) + fb));
-    p += sizeof(BlobHeader);
-    memcpy(p, &aec_ctl(h, cohort), sizeof(AecCtl));
-    WMX_HIP(hipMemcpy(p + sizeof(AecCtl), h->d_far + (size_t)cohort * h->far.group_words, fb, hipMemcpyDeviceToHost));
-    return 0;
+    if (!h || !host_blob || cohort < 0 || cohort >= h->co.n()) return WMX_EINVAL;
+    return h->co.export_blob(cohort, blob_tag("AECc"), blob_layout((uint32_t)h->freq, kAecCohortBlobVersion), host_blob);
 }
 
 int wmx_aec_import_cohort(wmx_aec *h, int cohort, const void *host_blob) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || !host_blob || cohort < 0 || cohort >= h->n_far) return WMX_EINVAL;
-    const size_t fb = h->far.group_words * 4;
-    const int rc = blob_check(host_blob, blob_tag("AECc"), blob_layout((uint32_t)h->freq, kAecCohortBlobVersion), (uint32_t)(sizeof(AecCtl) + fb));
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    const char *p = static_cast<const char *>(host_blob) + sizeof(BlobHeader);
-    aec_ctl_own(h, cohort);
-    memcpy(&h->ctl[(size_t)cohort], p, sizeof(AecCtl));
-    aec_ctl_join(h, cohort);
-    aec_co_drop(h, cohort);
-    WMX_HIP(hipMemcpy(h->d_far + (size_t)cohort * h->far.group_words, p + sizeof(AecCtl), fb, hipMemcpyHostToDevice));
-    return 0;
+    if (!h || !host_blob || cohort < 0 || cohort >= h->co.n()) return WMX_EINVAL;
+    return h->co.import_blob(cohort, blob_tag("AECc"), blob_layout((uint32_t)h->freq, kAecCohortBlobVersion), host_blob);
 }
 
-int wmx_aec_cohorts(const wmx_aec *h) { return h ? h->n_far : WMX_EINVAL; }
-int wmx_aec_cohort_key(const wmx_aec *h, int cohort, int32_t *key11) {
-    if (!h || !key11 || cohort < 0 || cohort >= h->n_far) return WMX_EINVAL;
-    wmx::AecCoKey k;
-    if (!h->live[(size_t)cohort] || !wmx::aec_co_key(aec_ctl(h, cohort), &k)) return 1;  // retired, or still in its start-up
-    for (int i = 0; i < 11; i++) key11[i] = k.v[i];
-    return 0;
-}
-int wmx_aec_live_cohorts(const wmx_aec *h) {
-    if (!h) return WMX_EINVAL;
-    int n = 0;
-    for (uint8_t l : h->live) n += l ? 1 : 0;
-    return n;
-}
+int wmx_aec_cohorts(const wmx_aec *h) { return h ? h->co.n() : WMX_EINVAL; }
+int wmx_aec_cohort_key(const wmx_aec *h, int cohort, int32_t *key11) { return wmx::cohort_key(h, cohort, key11); }
+int wmx_aec_live_cohorts(const wmx_aec *h) { return h ? h->co.live_count() : WMX_EINVAL; }
 
 }  // extern "C"
 
 // Library-internal (wmx_internal.h): from this point of `stream` on, the far-end packets of the NEXT wmx_aec_run_* call on
 // this handle are in place; its far kernel may start here, on the handle's side stream, beside whatever the caller launches
 // on `stream` between now and that call.  The near kernel still runs on `stream`, behind the far kernel.
-int wmx::aec_fork_far(wmx_aec *h, hipStream_t s) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    if (!h->side) {
-        WMX_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-        WMX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        WMX_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
-    WMX_HIP(hipEventRecord(h->ev_fork, s));
-    h->fork_pending = true;
-    return 0;
-}
-
+int wmx::aec_fork_far(wmx_aec *h, hipStream_t s) { return fork_far(h, s); }
 void wmx::aec_cancel_fork(wmx_aec *h) {
-    if (h) h->fork_pending = false;
+    if (h) h->co.fork_pending = false;
 }
 
 extern "C" {

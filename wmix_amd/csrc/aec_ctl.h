@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
+#include <cstddef>
 #include <cstring>
 
 namespace wmx {
@@ -143,7 +144,13 @@ struct RingIdx {
     }
 };
 
+struct AecCoKey;
+struct AecPairCheck;
 struct AecCtl {
+    using Plan = AecPlan;  // the cohort machinery's names (cohort_reg.h)
+    using Key = AecCoKey;
+    using Pair = AecPairCheck;
+    static constexpr int kMaxPktPerLaunch = kAecMaxPktPerLaunch;
     int fs = 0, mult = 1, rate_factor = 1;
     RingIdx near_fr, out_fr, far_buf, far_pre;
     int system_delay = 0, core_known_delay = 0;
@@ -341,7 +348,7 @@ struct AecCoKey {
         return true;
     }
 };
-inline bool aec_co_key(const AecCtl &c, AecCoKey *k) {
+inline bool co_key(const AecCtl &c, AecCoKey *k) {
     if (c.startup_phase) return false;
     const int v[11] = {c.near_fr.avail_read(), c.out_fr.avail_read(), c.far_buf.avail_read(), c.far_pre.avail_read(), c.system_delay,
                        c.core_known_delay, c.knownDelay, c.timeForDelayChange, (int)c.msInSndCardBuf, (int)c.filtDelay, (int)c.lastDelayDiff};
@@ -361,7 +368,7 @@ inline int aec_mod(int x, int m) {
     x %= m;
     return x < 0 ? x + m : x;
 }
-inline void aec_co_pair(const AecCtl &a, const AecCtl &b, int ia, int ib, AecPairCheck *pc) {
+inline void co_pair(const AecCtl &a, const AecCtl &b, int ia, int ib, AecPairCheck *pc) {
     pc->a = ia;
     pc->b = ib;
     pc->d_pre = aec_mod(b.far_pre.rd - a.far_pre.rd, kAecPreLen);
@@ -372,75 +379,9 @@ inline void aec_co_pair(const AecCtl &a, const AecCtl &b, int ia, int ib, AecPai
     pc->pad = 0;
 }
 
-// ---------------------------------------------------------------- control-plane classes (host bookkeeping, no HIP)
-// A control plane is index arithmetic on the call pattern, never on audio: cohorts that were started at the same point and are
-// called alike have EQUAL planes for ever, although their far-ends differ.  H is anything with
-//     std::vector<Ctl> ctl;  std::vector<int32_t> lead;  std::vector<uint8_t> live;  bool cls_dirty;     (Ctl: AecCtl or AecmCtl --
-//     anything with same_as(); lead.size() is the number of cohort ids in use)
-// (wmx_aec in aec.hip; a plain struct in tools_dev/san/host_ctl_san.cpp, where these run under ASan / UBSan against a model that
-// keeps one plane per cohort).  lead[g] = the cohort whose plane stands for g's; ctl[g] of a follower is stale.
-template <class H>
-inline auto aec_ctl(H *h, int g) -> decltype((h->ctl[0])) { return h->ctl[(size_t)h->lead[(size_t)g]]; }
-// cohort g leaves its class with an up-to-date plane of its own (a leader hands the class over to its first follower)
-template <class H>
-inline void aec_ctl_own(H *h, int g) {
-    const int l = h->lead[(size_t)g];
-    if (l != g) {
-        h->ctl[(size_t)g] = h->ctl[(size_t)l];
-        h->lead[(size_t)g] = g;
-        h->cls_dirty = true;
-        return;
-    }
-    int heir = -1;
-    for (int x = 0; x < (int)h->lead.size(); x++)
-        if (x != g && h->lead[(size_t)x] == g) {
-            if (heir < 0) {
-                heir = x;
-                h->ctl[(size_t)x] = h->ctl[(size_t)g];
-            }
-            h->lead[(size_t)x] = heir;
-            h->cls_dirty = true;
-        }
-}
-// cohort g (a leader of itself alone, its plane just rewritten: aec_init, an import) joins a class whose plane is equal, if one of
-// the first few hundred leaders has it -- planes made at the same point of the packet sequence (a bounded search: a miss costs
-// a control plane of its own, nothing else)
-template <class H>
-inline void aec_ctl_join(H *h, int g) {
-    int seen = 0;
-    for (int x = 0; x < (int)h->lead.size() && seen < 256; x++) {
-        if (x == g || h->lead[(size_t)x] != x || !h->live[(size_t)x]) continue;
-        seen++;
-        if (h->ctl[(size_t)x].same_as(h->ctl[(size_t)g])) {
-            h->lead[(size_t)g] = x;
-            h->cls_dirty = true;
-            return;
-        }
-    }
-}
-// in front of a launch: a follower that is called differently from its leader in THIS call (switched on / off alone, another
-// reported delay) takes a plane of its own first.  cohort_on may be null (all on).
-template <class H>
-inline void aec_classes_split(H *h, const int32_t *delay_ms, const uint8_t *cohort_on) {
-    for (int g = 0; g < (int)h->lead.size(); g++) {
-        const int l = h->lead[(size_t)g];
-        if (l == g || !h->live[(size_t)g]) continue;
-        const bool on_g = !cohort_on || cohort_on[g], on_l = !cohort_on || cohort_on[l];
-        if (on_g != on_l || (on_g && delay_ms[g] != delay_ms[l])) aec_ctl_own(h, g);
-    }
-}
-// the leaders, compact, and every cohort's class index
-template <class H>
-inline void aec_classes_list(const H *h, std::vector<int32_t> &leaders, std::vector<int32_t> &plan_of) {
-    const int G = (int)h->lead.size();
-    plan_of.assign((size_t)G, 0);
-    leaders.clear();
-    for (int g = 0; g < G; g++)
-        if (h->lead[(size_t)g] == g) {
-            plan_of[(size_t)g] = (int32_t)leaders.size();
-            leaders.push_back(g);
-        }
-    for (int g = 0; g < G; g++) plan_of[(size_t)g] = plan_of[(size_t)h->lead[(size_t)g]];
-}
+// the planning loop (cohort_reg.h): a plan is cleared up to its blocks (the kernels read only the n_blk the planning writes); a near packet the
+// reference rejects writes nothing (src/webrtc.c:463-468: the wrapper stops there)
+inline void plan_clear(AecPlan *pl) { memset(pl, 0, offsetof(AecPlan, blk)); }
+inline void plan_reject_near(AecPlan *pl) { pl->has_near = 0; }
 
 }  // namespace wmx

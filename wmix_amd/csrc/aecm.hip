@@ -26,6 +26,7 @@
 #include "wmx_internal.h"
 #include "spl_fx.h"
 #include "aecm_ctl.h"
+#include "cohort_hip.h"
 #include "fx_tables.h"
 
 namespace wmx {
@@ -986,51 +987,16 @@ __global__ void aecm_clamp_cohort(int *stream_cohort, int n_streams, int n_cohor
 struct wmx_aecm {
     int device;  // the HIP device the state lives on (current device at create); every entry point switches to it
     int n_streams, chn, freq, pkg;
-    int n_cohorts;
-    std::vector<wmx::AecmCtl> ctl;  // one control plane per cohort -- kept up to date for the LEADERS of the control-plane classes only
-    // control-plane classes, as in aec.hip (wmx_aec::lead; the bookkeeping is aec_ctl.h's, shared): cohorts started together and
-    // called alike run ONE plane and get ONE plan per packet, however many far-ends they hear
-    std::vector<int32_t> lead;         // [n_cohorts]
-    std::vector<int32_t> cls_leader;   // [n_cls]
-    std::vector<int32_t> h_plan_of[2]; // alternating sources of the asynchronous upload
-    int h_plan_of_sel;
-    int32_t *d_plan_of;                // [cap_cohorts]
-    bool cls_dirty;
+    // the cohorts, as in aec.hip (cohort_reg.h, cohort_hip.h): cohorts started together and called alike run ONE plane and get ONE
+    // plan per packet, however many far-ends they hear; 2 plan slots
+    wmx::CohortDev<wmx::AecmCtl, wmx::AecmPairChecks, 2> co;
     int32_t *d_state;
     int32_t *d_tmpl;        // the state aec_init gives a stream (reset_streams refills from it)
     int *d_stream_cohort;   // [n_streams] cohort of each stream, or nullptr with one cohort
     wmx::StreamLife life;
     wmx::AecmConsts *d_consts;
-    void *d_far;  // one allocation carved into AecmFarBufs
     wmx::AecmFarBufs far;
-    wmx::AecmPlan *d_plans[2];  // double-buffered: a chunk's plans stay untouched while its kernels may still run
-    wmx::AecmPlan *h_plans[2];  // pinned mirrors: the asynchronous copy reads them in place
-    hipEvent_t plan_free[2];    // recorded behind the kernels that read d_plans[i]; waited for before it (and its mirror) is rewritten
-    bool plan_used[2];
-    int plan_sel;
-    int cap_cohorts;            // cohorts the far slabs and plan slots are allocated for; grows by doubling (wmx_aecm_add_cohort)
-    size_t far_bytes;           // bytes of one cohort's far-end slab
-    std::vector<uint8_t> live;  // [n_cohorts] 0: retired, never called, the id is handed out again
-    std::vector<int> rc_g;             // per-call scratch kept with the handle
-    std::vector<int32_t> same_delay;
-    // wmx_aecm_coalesce: the pairs whose device comparison is in flight (`b` < 0: dropped)
-    wmx::AecmPairChecks co_pairs;
-    int co_n;
-    bool co_inflight;
-    int *d_co_flags, *h_co_flags;
-    hipEvent_t co_done;
-    long co_calls;
-    std::vector<long> co_retry_at;
-    long last_far_group_stride;
-    // the far kernel on a side stream beside whatever the caller launches in front of the near kernel (wmx::aecm_fork_far; aec.hip)
-    hipStream_t side;
-    hipEvent_t ev_fork, ev_join;
-    bool fork_pending;
 };
-static void aecm_co_drop(wmx_aecm *h, int cohort) {
-    for (int i = 0; i < h->co_n; i++)
-        if (h->co_pairs.p[i].a == cohort || h->co_pairs.p[i].b == cohort) h->co_pairs.p[i].b = -1;
-}
 
 extern "C" {
 
@@ -1039,28 +1005,17 @@ int wmx_aecm_destroy(wmx_aecm *h) {
     if (!h) return 0;
     if (h->d_state) (void)hipFree(h->d_state);
     if (h->d_consts) (void)hipFree(h->d_consts);
-    if (h->d_far) (void)hipFree(h->d_far);
-    if (h->d_plan_of) (void)hipFree(h->d_plan_of);
-    if (h->d_plans[0]) (void)hipFree(h->d_plans[0]);
-    if (h->h_plans[0]) (void)hipHostFree(h->h_plans[0]);
     if (h->d_tmpl) (void)hipFree(h->d_tmpl);
     if (h->d_stream_cohort) (void)hipFree(h->d_stream_cohort);
-    if (h->d_co_flags) (void)hipFree(h->d_co_flags);
-    if (h->h_co_flags) (void)hipHostFree(h->h_co_flags);
-    if (h->co_done) (void)hipEventDestroy(h->co_done);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    h->co.release();
     h->life.release();
-    for (int i = 0; i < 2; i++)
-        if (h->plan_free[i]) (void)hipEventDestroy(h->plan_free[i]);
     delete h;
     return 0;
 }
 
 static void aecm_carve_far(wmx_aecm *h) {  // the far-end allocation (32-bit arrays first: alignment); one slab per cohort
     using namespace wmx;
-    char *p = static_cast<char *>(h->d_far);
+    char *p = static_cast<char *>(h->co.d_far);
     h->far.mean_far = reinterpret_cast<int32_t *>(p);
     p += sizeof(int32_t) * 36;
     h->far.hist_q = reinterpret_cast<int32_t *>(p);
@@ -1076,50 +1031,9 @@ static void aecm_carve_far(wmx_aecm *h) {  // the far-end allocation (32-bit arr
     h->far.frame = reinterpret_cast<int16_t *>(p);
     p += sizeof(int16_t) * kAecmFrameRing;
     h->far.x_prev = reinterpret_cast<int16_t *>(p);
-    h->far.group_bytes = h->far_bytes;
+    h->far.group_bytes = h->co.slab_bytes;
 }
 
-// far slabs and plan slots for `cap` cohorts (existing slabs carried over); everything new is allocated before anything old is let go
-static int aecm_reserve(wmx_aecm *h, int cap) {
-    using namespace wmx;
-    if (cap <= h->cap_cohorts) return 0;
-    WMX_HIP_RC(hipDeviceSynchronize());
-    int ncap = h->cap_cohorts > 0 ? h->cap_cohorts : 1;
-    while (ncap < cap) ncap *= 2;
-    void *nf = nullptr;
-    AecmPlan *nd = nullptr, *nh = nullptr;
-    int32_t *npo = nullptr;
-    const size_t plan_bytes = 2 * (size_t)ncap * kAecmMaxPktPerLaunch * sizeof(AecmPlan);
-    hipError_t e = hipMalloc(&nf, h->far_bytes * (size_t)ncap);
-    if (e == hipSuccess) e = hipMalloc(&npo, sizeof(int32_t) * (size_t)ncap);
-    if (e == hipSuccess) e = hipMalloc(&nd, plan_bytes);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&nh), plan_bytes, hipHostMallocDefault);
-    if (e == hipSuccess && h->d_far) e = hipMemcpy(nf, h->d_far, h->far_bytes * (size_t)h->cap_cohorts, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess)
-        e = hipMemset(static_cast<char *>(nf) + h->far_bytes * (size_t)h->cap_cohorts, 0, h->far_bytes * (size_t)(ncap - h->cap_cohorts));
-    if (e != hipSuccess) {
-        if (nf) (void)hipFree(nf);
-        if (nd) (void)hipFree(nd);
-        if (nh) (void)hipHostFree(nh);
-        if (npo) (void)hipFree(npo);
-        return hip_fail(e, "growing the cohort buffers", __FILE__, __LINE__);
-    }
-    if (h->d_far) (void)hipFree(h->d_far);
-    if (h->d_plan_of) (void)hipFree(h->d_plan_of);
-    h->d_plan_of = npo;
-    h->cls_dirty = true;  // the new array holds nothing yet
-    if (h->d_plans[0]) (void)hipFree(h->d_plans[0]);
-    if (h->h_plans[0]) (void)hipHostFree(h->h_plans[0]);
-    h->d_far = nf;
-    h->d_plans[0] = nd;
-    h->d_plans[1] = nd + (size_t)ncap * kAecmMaxPktPerLaunch;
-    h->h_plans[0] = nh;
-    h->h_plans[1] = nh + (size_t)ncap * kAecmMaxPktPerLaunch;
-    h->plan_used[0] = h->plan_used[1] = false;  // drained above
-    h->cap_cohorts = ncap;
-    aecm_carve_far(h);
-    return 0;
-}
 
 int wmx_aecm_create(wmx_aecm **out, int n_streams, int chn, int freq, int interval_ms) {
     return wmx_aecm_create_cohorts(out, n_streams, chn, freq, interval_ms, 1);
@@ -1147,35 +1061,11 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     h->chn = chn;
     h->freq = freq;
     h->pkg = freq / 1000 * ((freq <= 8000 && interval_ms % 20 == 0) ? 20 : 10);  // src/webrtc.c:239-248
-    h->n_cohorts = n_cohorts;
-    h->ctl.resize((size_t)n_cohorts);
-    for (AecmCtl &c : h->ctl) c.init(freq);
-    h->lead.assign((size_t)n_cohorts, 0);  // made together, equal planes: one class led by cohort 0 until something tells them apart
-    h->h_plan_of_sel = 0;
-    h->d_plan_of = nullptr;
-    h->cls_dirty = true;
+    h->co.init(n_cohorts, freq);  // made together, equal planes: one class until something tells them apart
     h->d_tmpl = nullptr;
     h->d_stream_cohort = nullptr;
-    h->co_n = 0;
-    h->co_inflight = false;
-    h->d_co_flags = h->h_co_flags = nullptr;
-    h->co_done = nullptr;
-    h->co_calls = 0;
-    h->co_retry_at.assign((size_t)n_cohorts, 0);
-    h->last_far_group_stride = 0;
-    h->side = nullptr;
-    h->ev_fork = h->ev_join = nullptr;
-    h->fork_pending = false;
     h->d_state = nullptr;
     h->d_consts = nullptr;
-    h->d_far = nullptr;
-    h->d_plans[0] = h->d_plans[1] = nullptr;
-    h->h_plans[0] = h->h_plans[1] = nullptr;
-    h->plan_free[0] = h->plan_free[1] = nullptr;
-    h->plan_used[0] = h->plan_used[1] = false;
-    h->plan_sel = 0;
-    h->cap_cohorts = 0;
-    h->live.assign((size_t)n_cohorts, 1);
 
     AecmConsts *K = new AecmConsts();
     memset(K, 0, sizeof(*K));
@@ -1228,7 +1118,7 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     }
     const size_t far_raw = sizeof(int16_t) * (kAecmFarRing + 2 * kAecmFrame + kAecmFrameRing + 64 + 8) + sizeof(int32_t) * (36 + kAecmHist) +
                            sizeof(uint16_t) * (size_t)kAecmHist * kAecmBP + sizeof(uint32_t) * kAecmHist + 64;
-    h->far_bytes = (far_raw + 255) / 256 * 256;  // per cohort
+    h->co.slab_bytes = (far_raw + 255) / 256 * 256;  // per cohort
     hipError_t e;
 #define AECM_TRY(x)                                         \
     if ((e = (x)) != hipSuccess) {                          \
@@ -1240,7 +1130,7 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     AECM_TRY(hipMalloc(&h->d_state, (size_t)A_WORDS * n_streams * sizeof(int32_t)));
     AECM_TRY(hipMalloc(&h->d_consts, sizeof(AecmConsts)));
     {
-        const int rc = aecm_reserve(h, n_cohorts);
+        const int rc = h->co.reserve(n_cohorts, [h] { aecm_carve_far(h); });
         if (rc != 0) {
             wmx_aecm_destroy(h);
             delete K;
@@ -1251,8 +1141,7 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
         AECM_TRY(hipMalloc(&h->d_stream_cohort, sizeof(int) * n_streams));
         AECM_TRY(hipMemset(h->d_stream_cohort, 0, sizeof(int) * n_streams));
     }
-    AECM_TRY(hipEventCreateWithFlags(&h->plan_free[0], hipEventDisableTiming));
-    AECM_TRY(hipEventCreateWithFlags(&h->plan_free[1], hipEventDisableTiming));
+    for (hipEvent_t &ev : h->co.plan_free) AECM_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     AECM_TRY(hipMalloc(&h->d_tmpl, A_WORDS * sizeof(int32_t)));
     AECM_TRY(hipMemcpy(h->d_consts, K, sizeof(AecmConsts), hipMemcpyHostToDevice));
     AECM_TRY(hipMemcpy(h->d_tmpl, st.data(), A_WORDS * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1271,185 +1160,60 @@ int wmx_aecm_state_bytes(const wmx_aecm *h) { return h ? (int)wmx::A_WORDS * 4 :
 // Same contract as wmx_aec_run: mode bit 1 = aec_setFrameFar, bit 2 = aec_process, 3 = aec_process2.
 int wmx_aecm_run(wmx_aecm *h, int mode, const int16_t *d_far, long far_packet_stride, const int16_t *d_near, int16_t *d_out, int n_packets,
                  long stream_stride, long packet_stride, int delay_ms, void *stream) {
-    if (!h) {
-        wmx::set_error("wmx_aecm_run: bad argument");
-        return WMX_EINVAL;
-    }
-    h->same_delay.assign((size_t)h->n_cohorts, delay_ms);
     return wmx_aecm_run_cohorts(h, mode, d_far, far_packet_stride, 0, d_near, d_out, n_packets, stream_stride, packet_stride,
-                                h->same_delay.data(), nullptr, nullptr, stream);
+                                h ? h->co.same_delays(delay_ms) : nullptr, nullptr, nullptr, stream);
 }
 
 // Same contract as wmx_aec_run_cohorts (include/wmix_amd.h): one reported delay, one on/off byte and one return code per cohort.
+// A rejected delay: WebRtcAecm_Process has PROCESSED the packet with the delay clamped (state advances) and returns -1; the wmix
+// wrapper then returns without copying its output (src/webrtc.c:382-387).  Same here: the kernel runs the packet but leaves the
+// caller's buffer alone; later packets are not touched.
 int wmx_aecm_run_cohorts(wmx_aecm *h, int mode, const int16_t *d_far, long far_packet_stride, long far_group_stride, const int16_t *d_near,
                          int16_t *d_out, int n_packets, long stream_stride, long packet_stride, const int32_t *delay_ms,
                          const uint8_t *cohort_on, int32_t *cohort_rc, void *stream) {
     WMX_ON_DEVICE(h);
+    if (!h) {
+        wmx::set_error("wmx_aecm_run: bad argument");
+        return WMX_EINVAL;
+    }
     using namespace wmx;
-    using wmx::aec_ctl;
-    // a fork point belongs to THIS call, whichever way it ends (as in wmx_aec_run_cohorts)
-    const bool fork_here = h && h->fork_pending;
-    if (h) h->fork_pending = false;
-    if (!h || n_packets < 0 || (mode & 3) == 0 || !delay_ms) {
-        set_error("wmx_aecm_run: bad argument");
-        return WMX_EINVAL;
-    }
-    const int G = h->n_cohorts;
-    if (cohort_rc)
-        for (int g = 0; g < G; g++) cohort_rc[g] = 0;
-    if (n_packets == 0) return 0;
-    if (((mode & 1) && !d_far) || ((mode & 2) && (!d_near || !d_out))) {
-        set_error("wmx_aecm_run: null buffer");
-        return WMX_EINVAL;
-    }
-    const long per_pkt = (long)h->pkg * h->chn;
-    if ((mode & 2) && (packet_stride < per_pkt || (h->n_streams > 1 && stream_stride < per_pkt))) {
-        set_error("wmx_aecm_run: strides (%ld, %ld) smaller than a packet (%ld samples)", stream_stride, packet_stride, per_pkt);
-        return WMX_EINVAL;
-    }
-    if ((mode & 1) && far_packet_stride < per_pkt && n_packets > 1) {
-        set_error("wmx_aecm_run: far stride %ld smaller than a packet (%ld samples)", far_packet_stride, per_pkt);
-        return WMX_EINVAL;
-    }
     hipStream_t s = as_stream(stream);
-    std::vector<int> &rc_g = h->rc_g;
-    rc_g.assign((size_t)G, 0);
-    int rc_first = 0, running = 0;
-    for (int g = 0; g < G; g++) running += (h->live[(size_t)g] && (!cohort_on || cohort_on[g])) ? 1 : 0;
-    h->last_far_group_stride = (mode & 1) ? far_group_stride : h->last_far_group_stride;
-    // pairs whose comparison is in flight (wmx_aecm_coalesce) stay candidates only while the two cohorts are called identically
-    for (int i = 0; i < h->co_n; i++) {
-        AecmPairCheck &pc = h->co_pairs.p[i];
-        if (pc.b < 0) continue;
-        const bool on_a = !cohort_on || cohort_on[pc.a], on_b = !cohort_on || cohort_on[pc.b];
-        if (on_a != on_b || (on_a && delay_ms[pc.a] != delay_ms[pc.b]) || ((mode & 1) && far_group_stride != 0)) pc.b = -1;
-    }
-    // control-plane classes (aec.hip / aec_ctl.h): a follower that is called differently from its leader in THIS call takes a plane of
-    // its own first; then one plane and one plan per class and packet
-    if (G > 1 && (cohort_on || delay_ms != h->same_delay.data())) wmx::aec_classes_split(h, delay_ms, cohort_on);
-    bool classes_moved = false;
-    if (h->cls_dirty) {
-        // uploaded in `s`, behind every launch that still reads the old classes; a far kernel forked onto the side stream would not
-        // wait for it: this one launch keeps the far kernel in line
-        h->h_plan_of_sel ^= 1;
-        std::vector<int32_t> &po = h->h_plan_of[h->h_plan_of_sel];
-        wmx::aec_classes_list(h, h->cls_leader, po);
-        if (G > 1) WMX_HIP(hipMemcpyAsync(h->d_plan_of, po.data(), sizeof(int32_t) * (size_t)G, hipMemcpyHostToDevice, s));
-        h->cls_dirty = false;
-        classes_moved = true;
-    }
-    const int C = (int)h->cls_leader.size();
-    const int32_t *plan_of = G > 1 ? h->d_plan_of : nullptr;
-    running = 0;
-    for (int c = 0; c < C; c++) {
-        const int g = h->cls_leader[(size_t)c];
-        running += (h->live[(size_t)g] && (!cohort_on || cohort_on[g])) ? 1 : 0;
-    }
-    for (int done = 0; done < n_packets && running > 0;) {
-        int chunk = n_packets - done;
-        if (chunk > kAecmMaxPktPerLaunch) chunk = kAecmMaxPktPerLaunch;
-        // the next plan slot: its pinned host half and its device half are rewritten only after the kernels that read the device
-        // half last have finished, whatever stream they ran on
-        const int sel = h->plan_sel;
-        h->plan_sel ^= 1;
-        if (h->plan_used[sel]) WMX_HIP(hipEventSynchronize(h->plan_free[sel]));
-        AecmPlan *hp = h->h_plans[sel], *dp = h->d_plans[sel];  // [packet][class], C apart: chunk x C plans
-        int any = 0;
-        for (int c = 0; c < C; c++) {
-            const int g = h->cls_leader[(size_t)c];  // the class's one control plane
-            const bool on = h->live[(size_t)g] && (!cohort_on || cohort_on[g]) && rc_g[g] == 0;
-            for (int k = 0; k < chunk; k++) {
-                AecmPlan &pl = hp[(size_t)k * C + c];
-                memset(&pl, 0, sizeof(pl));
-                if (!on || rc_g[g] != 0) continue;  // has_far = has_near = 0: both kernels skip the packet for this class's cohorts
-                any = 1;
-                if (mode & 1) {
-                    const int r = h->ctl[(size_t)g].buffer_farend(h->pkg, &pl);
-                    if (r != 0) {
-                        pl.has_far = 0;
-                        rc_g[g] = r;
-                        continue;
-                    }
-                }
-                if (mode & 2) {
-                    const int r = h->ctl[(size_t)g].process(h->pkg, delay_ms[g], &pl);
-                    if (r != 0) {
-                        // WebRtcAecm_Process has PROCESSED the packet with the delay clamped (state advances) and returns -1; the
-                        // wmix wrapper then returns without copying its output (src/webrtc.c:382-387).  Same here: the kernel
-                        // runs the packet but leaves the caller's buffer alone; later packets are not touched.
-                        pl.discard_out = 1;
-                        rc_g[g] = r;
-                    }
-                }
-            }
-            if (on && rc_g[g] != 0) {
-                running--;
-                if (rc_first == 0) rc_first = rc_g[g];
-            }
-        }
-        if (any) {
-            const int by_value = (chunk == 1 && C == 1 && G == 1) ? 1 : 0;
-            // the far kernel on the side stream when the caller forked it (first chunk of the call only)
-            const bool forked = fork_here && done == 0 && (mode & 2) && !classes_moved;
-            hipStream_t fs = forked ? h->side : s;
-            if (forked) WMX_HIP(hipStreamWaitEvent(fs, h->ev_fork, 0));
-            // every cohort its own class: each far wave fetches ITS plans from the pinned host slot (no copy-engine operation in front of
-            // the launch); classes shared by several cohorts: one small upload, and every member reads the class's plan on the device
-            const bool from_host = !by_value && C == G;
-            if (!by_value && !from_host) WMX_HIP(hipMemcpyAsync(dp, hp, (size_t)C * chunk * sizeof(AecmPlan), hipMemcpyHostToDevice, fs));
-            hipLaunchKernelGGL(aecm_far_kernel, dim3((unsigned)G), dim3(64), 0, fs, h->far, h->d_consts, dp, chunk, C, plan_of,
-                               d_far ? d_far + (size_t)done * far_packet_stride : nullptr, far_packet_stride, far_group_stride, h->chn, by_value,
-                               hp[0], from_host ? hp : nullptr);
-            WMX_LAUNCH_CHECK();
-            if (forked) {
-                WMX_HIP(hipEventRecord(h->ev_join, fs));
-                WMX_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
-            }
-            if (mode & 2) {
-                const unsigned grid = (unsigned)((h->n_streams + kAecmWavesPerBlock - 1) / kAecmWavesPerBlock);
-                hipLaunchKernelGGL(aecm_near_kernel, dim3(grid), dim3(64 * kAecmWavesPerBlock), 0, s, h->d_state, h->far, h->d_consts, dp, chunk, C,
-                                   plan_of, d_near + (size_t)done * packet_stride, d_out + (size_t)done * packet_stride, h->n_streams,
-                                   stream_stride, packet_stride, h->chn, h->pkg, h->freq / 8000, h->d_stream_cohort, h->life.d_active);
-                WMX_LAUNCH_CHECK();
-            }
-            WMX_HIP(hipEventRecord(h->plan_free[sel], s));
-            h->plan_used[sel] = true;
-        }
-        done += chunk;
-    }
-    if (cohort_rc)
-        for (int g = 0; g < G; g++) cohort_rc[g] = (h->live[(size_t)g] && (!cohort_on || cohort_on[g])) ? rc_g[(size_t)h->lead[(size_t)g]] : 0;
-    return rc_first;
+    auto far = [&](hipStream_t fs, const CohortLaunch<AecmPlan> &L) {
+        // every cohort its own class: each far wave fetches ITS plans from the pinned host slot (no copy-engine operation in front of
+        // the launch); classes shared by several cohorts: one small upload, and every member reads the class's plan on the device
+        const bool from_host = !L.by_value && L.C == L.G;
+        if (!L.by_value && !from_host) WMX_HIP(hipMemcpyAsync(L.dp, L.hp, (size_t)L.C * L.chunk * sizeof(AecmPlan), hipMemcpyHostToDevice, fs));
+        hipLaunchKernelGGL(aecm_far_kernel, dim3((unsigned)L.G), dim3(64), 0, fs, h->far, h->d_consts, L.dp, L.chunk, L.C, L.plan_of,
+                           d_far ? d_far + (size_t)L.done * far_packet_stride : nullptr, far_packet_stride, far_group_stride, h->chn, L.by_value,
+                           L.hp[0], from_host ? L.hp : nullptr);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    };
+    auto near = [&](const CohortLaunch<AecmPlan> &L) {
+        const unsigned grid = (unsigned)((h->n_streams + kAecmWavesPerBlock - 1) / kAecmWavesPerBlock);
+        hipLaunchKernelGGL(aecm_near_kernel, dim3(grid), dim3(64 * kAecmWavesPerBlock), 0, s, h->d_state, h->far, h->d_consts, L.dp, L.chunk, L.C,
+                           L.plan_of, d_near + (size_t)L.done * packet_stride, d_out + (size_t)L.done * packet_stride, h->n_streams, stream_stride,
+                           packet_stride, h->chn, h->pkg, h->freq / 8000, h->d_stream_cohort, h->life.d_active);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    };
+    return run_cohorts(h, "wmx_aecm_run", mode, d_far, far_packet_stride, far_group_stride, d_near, d_out, n_packets, stream_stride,
+                       packet_stride, delay_ms, cohort_on, cohort_rc, s, [](int) { return 0; }, [](auto loop) { return loop(); }, far, near);
 }
 
 }  // extern "C"
-// Library-internal (wmx_internal.h): from this point of `stream` on, the far-end packets of the NEXT wmx_aecm_run_* call on this
-// handle are in place; its far kernel may start here, on the handle's side stream, beside whatever the caller launches on `stream`
-// between now and that call (wmx_chain_process: the NSX).  The near kernel still runs on `stream`, behind the far kernel.
-int wmx::aecm_fork_far(wmx_aecm *h, hipStream_t s) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    if (!h->side) {
-        WMX_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-        WMX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        WMX_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
-    WMX_HIP(hipEventRecord(h->ev_fork, s));
-    h->fork_pending = true;
-    return 0;
-}
+// Library-internal (wmx_internal.h): the far kernel of the next wmx_aecm_run_* call may start at this point of `stream`, beside
+// whatever the caller launches between now and that call (wmx_chain_process: the NSX)
+int wmx::aecm_fork_far(wmx_aecm *h, hipStream_t s) { return fork_far(h, s); }
 void wmx::aecm_cancel_fork(wmx_aecm *h) {
-    if (h) h->fork_pending = false;
+    if (h) h->co.fork_pending = false;
 }
 extern "C" {
 
 // stream / cohort migration, as for the float AEC
 static constexpr uint32_t kAecmBlobVersion = 1;  // bump when the meaning of a state word changes (wmx_internal.h: blob_layout)
 int wmx_aecm_stream_state_bytes(const wmx_aecm *h) { return h ? (int)(sizeof(wmx::BlobHeader) + wmx::A_WORDS * 4) : WMX_EINVAL; }
-int wmx_aecm_cohort_state_bytes(const wmx_aecm *h) {
-    return h ? (int)(sizeof(wmx::BlobHeader) + sizeof(wmx::AecmCtl) + h->far.group_bytes) : WMX_EINVAL;
-}
-
+int wmx_aecm_cohort_state_bytes(const wmx_aecm *h) { return h ? h->co.blob_bytes() : WMX_EINVAL; }
 int wmx_aecm_export_stream(wmx_aecm *h, int stream_index, void *host_blob) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
@@ -1464,7 +1228,7 @@ int wmx_aecm_export_stream(wmx_aecm *h, int stream_index, void *host_blob) {
 int wmx_aecm_import_stream(wmx_aecm *h, int stream_index, const void *host_blob, int cohort) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams || cohort < -1 || cohort >= h->n_cohorts) return WMX_EINVAL;
+    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
     const int rc = blob_check(host_blob, blob_tag("AECM"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), A_WORDS * 4);
     if (rc) return rc;
     WMX_HIP(hipDeviceSynchronize());
@@ -1477,203 +1241,61 @@ int wmx_aecm_import_stream(wmx_aecm *h, int stream_index, const void *host_blob,
 int wmx_aecm_export_cohort(wmx_aecm *h, int cohort, void *host_blob) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || !host_blob || cohort < 0 || cohort >= h->n_cohorts) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    char *p = static_cast<char *>(host_blob);
-    blob_begin(p, blob_tag("AEMc"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), (uint32_t)(sizeof(AecmCtl) + h->far.group_bytes));
-    p += sizeof(BlobHeader);
-    memcpy(p, &wmx::aec_ctl(h, cohort), sizeof(AecmCtl));
-    WMX_HIP(hipMemcpy(p + sizeof(AecmCtl), static_cast<char *>(h->d_far) + (size_t)cohort * h->far.group_bytes, h->far.group_bytes,
-                      hipMemcpyDeviceToHost));
-    return 0;
+    if (!h || !host_blob || cohort < 0 || cohort >= h->co.n()) return WMX_EINVAL;
+    return h->co.export_blob(cohort, blob_tag("AEMc"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), host_blob);
 }
 
 int wmx_aecm_import_cohort(wmx_aecm *h, int cohort, const void *host_blob) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || !host_blob || cohort < 0 || cohort >= h->n_cohorts) return WMX_EINVAL;
-    const int rc = blob_check(host_blob, blob_tag("AEMc"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), (uint32_t)(sizeof(AecmCtl) + h->far.group_bytes));
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    const char *p = static_cast<const char *>(host_blob) + sizeof(BlobHeader);
-    wmx::aec_ctl_own(h, cohort);
-    memcpy(&h->ctl[(size_t)cohort], p, sizeof(AecmCtl));
-    wmx::aec_ctl_join(h, cohort);
-    aecm_co_drop(h, cohort);
-    WMX_HIP(hipMemcpy(static_cast<char *>(h->d_far) + (size_t)cohort * h->far.group_bytes, p + sizeof(AecmCtl), h->far.group_bytes,
-                      hipMemcpyHostToDevice));
-    return 0;
+    if (!h || !host_blob || cohort < 0 || cohort >= h->co.n()) return WMX_EINVAL;
+    return h->co.import_blob(cohort, blob_tag("AEMc"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), host_blob);
 }
 
-int wmx_aecm_cohorts(const wmx_aecm *h) { return h ? h->n_cohorts : WMX_EINVAL; }
-int wmx_aecm_cohort_key(const wmx_aecm *h, int cohort, int32_t *key8) {
-    if (!h || !key8 || cohort < 0 || cohort >= h->n_cohorts) return WMX_EINVAL;
-    wmx::AecmCoKey k;
-    if (!h->live[(size_t)cohort] || !wmx::aecm_co_key(wmx::aec_ctl(h, cohort), &k)) return 1;  // retired, or still in its start-up
-    for (int i = 0; i < 8; i++) key8[i] = k.v[i];
-    return 0;
-}
-int wmx_aecm_live_cohorts(const wmx_aecm *h) {
-    if (!h) return WMX_EINVAL;
-    int n = 0;
-    for (uint8_t l : h->live) n += l ? 1 : 0;
-    return n;
-}
+int wmx_aecm_cohorts(const wmx_aecm *h) { return h ? h->co.n() : WMX_EINVAL; }
+int wmx_aecm_cohort_key(const wmx_aecm *h, int cohort, int32_t *key8) { return wmx::cohort_key(h, cohort, key8); }
+int wmx_aecm_live_cohorts(const wmx_aecm *h) { return h ? h->co.live_count() : WMX_EINVAL; }
 
-// wmx_aec_coalesce for the fixed-point canceller (include/wmix_amd.h): completes the merges whose device comparison came back equal,
-// then proposes up to max_pairs new pairs and launches their comparison behind the work already in `stream`.
+// wmx_aec_coalesce for the fixed-point canceller (include/wmix_amd.h; cohort_hip.h: coalesce)
 int wmx_aecm_coalesce(wmx_aecm *h, int max_pairs, int32_t *merged_from, int32_t *merged_into, int cap, int *n_merged, void *stream) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (n_merged) *n_merged = 0;
-    if (!h || max_pairs < 0 || cap < 0 || (cap > 0 && (!merged_from || !merged_into))) return WMX_EINVAL;
-    hipStream_t s = as_stream(stream);
-    h->co_calls++;
-    if (h->n_cohorts < 2 || !h->d_stream_cohort) return 0;
-    if (!h->d_co_flags) {
-        WMX_HIP(hipMalloc(&h->d_co_flags, sizeof(int) * kAecmCoMax));
-        WMX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->h_co_flags), sizeof(int) * kAecmCoMax, hipHostMallocDefault));
-        WMX_HIP(hipEventCreateWithFlags(&h->co_done, hipEventDisableTiming));
-    }
-    int merged = 0;
-    if (h->co_inflight) {
-        const hipError_t q = hipEventQuery(h->co_done);
-        if (q == hipErrorNotReady) return 0;
-        if (q != hipSuccess) return hip_fail(q, "hipEventQuery(co_done)", __FILE__, __LINE__);
-        h->co_inflight = false;
-        AecmPairChecks go;
-        int n_go = 0;
-        for (int i = 0; i < h->co_n; i++) {
-            AecmPairCheck pc = h->co_pairs.p[i];
-            if (pc.b < 0) continue;
-            AecmCoKey ka, kb;
-            const bool ok = h->h_co_flags[i] == 1 && h->live[(size_t)pc.a] && h->live[(size_t)pc.b] &&
-                            aecm_co_key(aec_ctl(h, pc.a), &ka) && aecm_co_key(aec_ctl(h, pc.b), &kb) && ka == kb;
-            if (!ok) {
-                h->co_retry_at[(size_t)pc.b] = h->co_calls + 64;
-                continue;
-            }
-            if (merged >= cap) continue;
-            aecm_co_pair(aec_ctl(h, pc.a), aec_ctl(h, pc.b), pc.a, pc.b, &pc);
-            go.p[n_go++] = pc;
-            merged_from[merged] = pc.b;
-            merged_into[merged] = pc.a;
-            merged++;
-        }
-        h->co_n = 0;
-        if (n_go > 0) {
-            hipLaunchKernelGGL(aecm_merge_streams, dim3((unsigned)((h->n_streams + 3) / 4)), dim3(256), 0, s, h->d_state, h->d_stream_cohort,
-                               h->n_streams, go, n_go);
+    auto merge = [h](const AecmPairChecks &go, int n_go, hipStream_t s) {
+        hipLaunchKernelGGL(aecm_merge_streams, dim3((unsigned)((h->n_streams + 3) / 4)), dim3(256), 0, s, h->d_state, h->d_stream_cohort,
+                           h->n_streams, go, n_go);
+        WMX_LAUNCH_CHECK();
+        const int nc = h->co.retire_merged(go.p, n_go);
+        if (nc < h->co.n()) {
+            hipLaunchKernelGGL(aecm_clamp_cohort, dim3((unsigned)((h->n_streams + 255) / 256)), dim3(256), 0, s, h->d_stream_cohort, h->n_streams, nc);
             WMX_LAUNCH_CHECK();
-            for (int i = 0; i < n_go; i++) {
-                wmx::aec_ctl_own(h, go.p[i].b);  // a retired cohort leads nobody
-                h->live[(size_t)go.p[i].b] = 0;
-            }
-            int nc = h->n_cohorts;
-            while (nc > 1 && !h->live[(size_t)nc - 1]) nc--;
-            if (nc < h->n_cohorts) {
-                hipLaunchKernelGGL(aecm_clamp_cohort, dim3((unsigned)((h->n_streams + 255) / 256)), dim3(256), 0, s, h->d_stream_cohort, h->n_streams, nc);
-                WMX_LAUNCH_CHECK();
-                h->n_cohorts = nc;
-                h->ctl.resize((size_t)nc);
-                h->lead.resize((size_t)nc);
-                h->cls_dirty = true;
-                h->live.resize((size_t)nc);
-                h->co_retry_at.resize((size_t)nc);
-            }
+            h->co.shrink(nc);
         }
-    }
-    if (n_merged) *n_merged = merged;
-    if (max_pairs == 0 || h->last_far_group_stride != 0) return 0;
-    if (max_pairs > kAecmCoMax) max_pairs = kAecmCoMax;
-    std::unordered_multimap<uint64_t, int> leads;
-    leads.reserve((size_t)h->n_cohorts);
-    int n = 0;
-    for (int g = 0; g < h->n_cohorts && n < max_pairs; g++) {
-        if (!h->live[(size_t)g]) continue;
-        AecmCoKey k, kl;
-        if (!aecm_co_key(aec_ctl(h, g), &k)) continue;
-        uint64_t hash = 1469598103934665603ull;
-        for (int v : k.v) hash = (hash ^ (uint32_t)v) * 1099511628211ull;
-        int lead = -1;
-        const auto range = leads.equal_range(hash);
-        for (auto it = range.first; it != range.second && lead < 0; ++it)
-            if (aecm_co_key(aec_ctl(h, it->second), &kl) && kl == k) lead = it->second;
-        if (lead < 0) {
-            leads.emplace(hash, g);
-            continue;
-        }
-        if (h->co_retry_at[(size_t)g] > h->co_calls) continue;
-        aecm_co_pair(aec_ctl(h, lead), aec_ctl(h, g), lead, g, &h->co_pairs.p[n++]);
-    }
-    h->co_n = n;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(aecm_cohort_equal, dim3((unsigned)n), dim3(256), 0, s, h->far, h->co_pairs, h->d_co_flags);
-    WMX_LAUNCH_CHECK();
-    WMX_HIP(hipMemcpyAsync(h->h_co_flags, h->d_co_flags, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
-    WMX_HIP(hipEventRecord(h->co_done, s));
-    h->co_inflight = true;
-    return 0;
+        return 0;
+    };
+    auto equal = [h](int n, hipStream_t s) {
+        hipLaunchKernelGGL(aecm_cohort_equal, dim3((unsigned)n), dim3(256), 0, s, h->far, h->co.co_pairs, h->co.d_co_flags);
+    };
+    return coalesce(h, max_pairs, merged_from, merged_into, cap, n_merged, stream, h ? h->d_stream_cohort : nullptr, merge, equal);
 }
-
 
 // aec_init for a cohort's shared part in the AECM build: control plane, far-end ring, farendOld, far spectrum history
-int wmx_aecm_reset_cohort(wmx_aecm *h, int cohort, void *stream) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || cohort < 0 || cohort >= h->n_cohorts) return WMX_EINVAL;
-    wmx::aec_ctl_own(h, cohort);
-    h->ctl[(size_t)cohort].init(h->freq);
-    wmx::aec_ctl_join(h, cohort);  // cohorts restarted at the same point of the packet sequence run one control plane
-    aecm_co_drop(h, cohort);
-    WMX_HIP(hipMemsetAsync(static_cast<char *>(h->d_far) + (size_t)cohort * h->far.group_bytes, 0, h->far.group_bytes, as_stream(stream)));
-    return 0;
-}
+int wmx_aecm_reset_cohort(wmx_aecm *h, int cohort, void *stream) { return wmx::reset_cohort(h, cohort, stream); }
 
 // A new cohort (a join time of its own), as wmx_aec_add_cohort: a retired id when there is one, else the next, buffers doubling
 int wmx_aecm_add_cohort(wmx_aecm *h, int *cohort, void *stream) {
     WMX_ON_DEVICE(h);
-    using namespace wmx;
     if (!h || !cohort) return WMX_EINVAL;
-    int id = -1;
-    for (int g = 0; g < h->n_cohorts; g++)
-        if (!h->live[(size_t)g]) {
-            id = g;
-            break;
-        }
-    if (id < 0) {
-        id = h->n_cohorts;
-        const int rc = aecm_reserve(h, id + 1);
-        if (rc != 0) return rc;
-        h->ctl.resize((size_t)id + 1);
-        h->lead.push_back(id);
-        h->cls_dirty = true;
-        h->live.push_back(1);
-        h->co_retry_at.push_back(0);
-        h->n_cohorts = id + 1;
-    }
-    if (h->n_cohorts > 1 && !h->d_stream_cohort) {  // so far every stream was in cohort 0 by construction
-        WMX_HIP(hipMalloc(&h->d_stream_cohort, sizeof(int) * h->n_streams));
-        WMX_HIP(hipMemsetAsync(h->d_stream_cohort, 0, sizeof(int) * h->n_streams, as_stream(stream)));
-    }
-    h->live[(size_t)id] = 1;
-    *cohort = id;
-    return wmx_aecm_reset_cohort(h, id, stream);
+    const int rc = h->co.add(h->d_stream_cohort, h->n_streams, wmx::as_stream(stream), cohort, [h] { aecm_carve_far(h); });
+    return rc != 0 ? rc : wmx_aecm_reset_cohort(h, *cohort, stream);
 }
 
-int wmx_aecm_retire_cohort(wmx_aecm *h, int cohort) {
-    if (!h || cohort < 0 || cohort >= h->n_cohorts) return WMX_EINVAL;
-    wmx::aec_ctl_own(h, cohort);  // a retired cohort leads nobody
-    h->live[(size_t)cohort] = 0;
-    aecm_co_drop(h, cohort);
-    return 0;
-}
+int wmx_aecm_retire_cohort(wmx_aecm *h, int cohort) { return wmx::retire_cohort(h, cohort); }
 
 // aec_release + aec_init for the listed streams in the AECM build; cohort >= 0 also makes them members of that cohort
 int wmx_aecm_reset_streams(wmx_aecm *h, const int32_t *idx, int n, int cohort, void *stream) {
     WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || n < 0 || (n > 0 && !idx) || cohort < -1 || cohort >= h->n_cohorts) return WMX_EINVAL;
+    if (!h || n < 0 || (n > 0 && !idx) || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = as_stream(stream);
     const int32_t *d_idx = nullptr;

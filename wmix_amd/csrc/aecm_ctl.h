@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include "aec_ctl.h"  // RingIdx
 
 namespace wmx {
@@ -39,7 +40,13 @@ struct AecmPlan {
     AecmFramePlan fr[2];
 };
 
+struct AecmCoKey;
+struct AecmPairCheck;
 struct AecmCtl {
+    using Plan = AecmPlan;  // the cohort machinery's names (cohort_reg.h)
+    using Key = AecmCoKey;
+    using Pair = AecmPairCheck;
+    static constexpr int kMaxPktPerLaunch = kAecmMaxPktPerLaunch;
     int fs = 0, mult = 1;
     RingIdx farend, frame_ring, out_ring;
     int known_delay = 0, time_for_delay_change = 0, ec_startup = 1, check_buff_size = 1;
@@ -197,7 +204,7 @@ struct AecmCoKey {
         return true;
     }
 };
-inline bool aecm_co_key(const AecmCtl &c, AecmCoKey *k) {
+inline bool co_key(const AecmCtl &c, AecmCoKey *k) {
     if (c.ec_startup) return false;
     const int v[8] = {c.farend.avail_read(), c.frame_ring.avail_read(), c.out_ring.avail_read(), c.known_delay, c.time_for_delay_change,
                       (int)c.ms_in_snd, (int)c.filt_delay, (int)c.last_delay_diff};
@@ -212,7 +219,7 @@ struct AecmPairCheck {
     int d_hist;     // b's history slots         = a's + d_hist   (mod kAecmHist)
     int pad[2];
 };
-inline void aecm_co_pair(const AecmCtl &a, const AecmCtl &b, int ia, int ib, AecmPairCheck *pc) {
+inline void co_pair(const AecmCtl &a, const AecmCtl &b, int ia, int ib, AecmPairCheck *pc) {
     pc->a = ia;
     pc->b = ib;
     pc->d_ring = aec_mod(b.farend.rd - a.farend.rd, kAecmFarRing);
@@ -221,5 +228,10 @@ inline void aecm_co_pair(const AecmCtl &a, const AecmCtl &b, int ia, int ib, Aec
     pc->d_hist = aec_mod(b.block_t - a.block_t, kAecmHist);
     pc->pad[0] = pc->pad[1] = 0;
 }
+
+// the planning loop (cohort_reg.h): the whole plan is cleared; a near packet the reference rejects is processed with the delay
+// clamped (WebRtcAecm_Process has advanced its state) but its output is not copied out (src/webrtc.c:382-387)
+inline void plan_clear(AecmPlan *pl) { memset(pl, 0, sizeof(*pl)); }
+inline void plan_reject_near(AecmPlan *pl) { pl->discard_out = 1; }
 
 }  // namespace wmx

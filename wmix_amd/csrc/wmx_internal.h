@@ -10,7 +10,7 @@
 #include "build_flags.h"
 
 // Fault injection (developer variant only: -DWMX_FAULT_INJECTION, recorded by wmx_build_info and refused by the Python mirror like every
-// variant build).  Every runtime call that goes through WMX_HIP / WMX_HIP_RC first passes a countdown; when it reaches zero the call is
+// variant build).  Every runtime call that goes through WMX_HIP first passes a countdown; when it reaches zero the call is
 // NOT made and reports hipErrorUnknown instead -- "call n of this entry point failed" -- so that tests can walk a fault through every
 // fallible step of an entry point (tests/test_pipe_faults_gpu.py).  Armed by wmx_debug_fail_nth_hip_call(n) or, for the first arming,
 // WMIX_AMD_FAIL_NTH_HIP_CALL=n in the environment; wmx_debug_hip_calls() = calls counted since the last arming.
@@ -23,7 +23,7 @@ hipError_t fault_point();
 #define WMX_FAULT_OR(expr) (expr)
 #endif
 
-#define WMX_HIP_RC(expr)                                                      \
+#define WMX_HIP(expr)                                                         \
     do {                                                                      \
         hipError_t _e = WMX_FAULT_OR(expr);                                   \
         if (_e != hipSuccess) return wmx::hip_fail(_e, #expr, __FILE__, __LINE__); \
@@ -127,10 +127,10 @@ struct SchedCache {
             e.erase(e.begin() + (long)lru);
         }
         int dev = -1;
-        WMX_HIP_RC(hipGetDevice(&dev));
+        WMX_HIP(hipGetDevice(&dev));
         void *p = nullptr;
         if (bytes) {
-            WMX_HIP_RC(hipMalloc(&p, bytes));
+            WMX_HIP(hipMalloc(&p, bytes));
             hipError_t er = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
             if (er != hipSuccess) {
                 (void)hipFree(p);
@@ -144,8 +144,8 @@ struct SchedCache {
     }
     // call after launching the kernel that reads `x` on stream `s`
     int used(Entry *x, hipStream_t s) {
-        if (!x->ev) WMX_HIP_RC(hipEventCreateWithFlags(&x->ev, hipEventDisableTiming));
-        WMX_HIP_RC(hipEventRecord(x->ev, s));
+        if (!x->ev) WMX_HIP(hipEventCreateWithFlags(&x->ev, hipEventDisableTiming));
+        WMX_HIP(hipEventRecord(x->ev, s));
         return 0;
     }
     void clear() {
@@ -179,14 +179,14 @@ struct StreamLife {
                 // kernels in flight still read it, on `s` or on any other stream the caller ran this handle on: the whole
                 // device is drained before the mask goes (a control-plane call, rare)
                 (void)s;
-                WMX_HIP_RC(hipDeviceSynchronize());
+                WMX_HIP(hipDeviceSynchronize());
                 (void)hipFree(d_active);
                 d_active = nullptr;
             }
             return 0;
         }
-        if (!d_active) WMX_HIP_RC(hipMalloc(reinterpret_cast<void **>(&d_active), (size_t)n_streams));
-        WMX_HIP_RC(hipMemcpyAsync(d_active, host_mask, (size_t)n_streams, hipMemcpyHostToDevice, s));
+        if (!d_active) WMX_HIP(hipMalloc(reinterpret_cast<void **>(&d_active), (size_t)n_streams));
+        WMX_HIP(hipMemcpyAsync(d_active, host_mask, (size_t)n_streams, hipMemcpyHostToDevice, s));
         return 0;
     }
     // validates and uploads a reset list; *d_out = device copy, valid for kernels launched on `s` before done(s)
@@ -196,22 +196,22 @@ struct StreamLife {
                 set_error("reset_streams: index %d of the list is stream %d of %d", i, idx[i], n_streams);
                 return WMX_EINVAL;
             }
-        if (idx_used) WMX_HIP_RC(hipEventSynchronize(idx_free));
+        if (idx_used) WMX_HIP(hipEventSynchronize(idx_free));
         if ((size_t)n > idx_cap) {
             if (d_idx) (void)hipFree(d_idx);
             d_idx = nullptr;
             idx_cap = 0;
             const size_t cap = (size_t)n < 256 ? 256 : (size_t)n;
-            WMX_HIP_RC(hipMalloc(reinterpret_cast<void **>(&d_idx), cap * sizeof(int32_t)));
+            WMX_HIP(hipMalloc(reinterpret_cast<void **>(&d_idx), cap * sizeof(int32_t)));
             idx_cap = cap;
         }
-        if (!idx_free) WMX_HIP_RC(hipEventCreateWithFlags(&idx_free, hipEventDisableTiming));
-        WMX_HIP_RC(hipMemcpyAsync(d_idx, idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!idx_free) WMX_HIP(hipEventCreateWithFlags(&idx_free, hipEventDisableTiming));
+        WMX_HIP(hipMemcpyAsync(d_idx, idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         *d_out = d_idx;
         return 0;
     }
     int done(hipStream_t s) {
-        WMX_HIP_RC(hipEventRecord(idx_free, s));
+        WMX_HIP(hipEventRecord(idx_free, s));
         idx_used = true;
         return 0;
     }
@@ -394,12 +394,6 @@ __device__ __forceinline__ void touch_done(int &sink) { asm volatile("s_waitcnt 
 #endif
 
 }  // namespace wmx
-
-#define WMX_HIP(expr)                                                         \
-    do {                                                                      \
-        hipError_t _e = WMX_FAULT_OR(expr);                                   \
-        if (_e != hipSuccess) return wmx::hip_fail(_e, #expr, __FILE__, __LINE__); \
-    } while (0)
 
 #define WMX_LAUNCH_CHECK() WMX_HIP(hipGetLastError())
 
