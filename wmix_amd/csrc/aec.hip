@@ -1660,16 +1660,9 @@ int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int i
         const uint32_t seed0 = 777u;  // aec->seed, aec_core.c:1670
         memcpy(&st[AS_NSEED], &seed0, 4);
     }
-    hipError_t e;
-#define AEC_TRY(x)                                         \
-    if ((e = (x)) != hipSuccess) {                         \
-        int rc = hip_fail(e, #x, __FILE__, __LINE__);      \
-        wmx_aec_destroy(h);                                \
-        return rc;                                         \
-    }
-    AEC_TRY(hipMalloc(&h->d_state, (size_t)AS_WORDS * n_streams * sizeof(float)));
-    AEC_TRY(hipMalloc(&h->d_consts, sizeof(K) + sizeof(PowTables)));  // [AecConsts | PowTables]; only the first part is copied to LDS
-    for (hipEvent_t &ev : h->co.plan_free) AEC_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    WMX_CREATE_TRY(wmx_aec_destroy(h), hipMalloc(&h->d_state, (size_t)AS_WORDS * n_streams * sizeof(float)));
+    WMX_CREATE_TRY(wmx_aec_destroy(h), hipMalloc(&h->d_consts, sizeof(K) + sizeof(PowTables)));  // [AecConsts | PowTables]; only the first part is copied to LDS
+    for (hipEvent_t &ev : h->co.plan_free) WMX_CREATE_TRY(wmx_aec_destroy(h), hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     {
         const int rc = h->co.reserve(n_far, [h] { aec_carve_far(h); });
         if (rc != 0) {
@@ -1678,20 +1671,20 @@ int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int i
         }
     }
     if (n_far > 1) {
-        AEC_TRY(hipMalloc(&h->d_stream_far, sizeof(int) * n_streams));
+        WMX_CREATE_TRY(wmx_aec_destroy(h), hipMalloc(&h->d_stream_far, sizeof(int) * n_streams));
         if (stream_far) {
-            AEC_TRY(hipMemcpy(h->d_stream_far, stream_far, sizeof(int) * n_streams, hipMemcpyHostToDevice));
+            WMX_CREATE_TRY(wmx_aec_destroy(h), hipMemcpy(h->d_stream_far, stream_far, sizeof(int) * n_streams, hipMemcpyHostToDevice));
         } else {
-            AEC_TRY(hipMemset(h->d_stream_far, 0, sizeof(int) * n_streams));
+            WMX_CREATE_TRY(wmx_aec_destroy(h), hipMemset(h->d_stream_far, 0, sizeof(int) * n_streams));
         }
     }
-    AEC_TRY(hipMalloc(&h->d_tmpl, AS_WORDS * sizeof(float)));
-    AEC_TRY(hipMemcpy(h->d_consts, &K, sizeof(K), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_aec_destroy(h), hipMalloc(&h->d_tmpl, AS_WORDS * sizeof(float)));
+    WMX_CREATE_TRY(wmx_aec_destroy(h), hipMemcpy(h->d_consts, &K, sizeof(K), hipMemcpyHostToDevice));
     {
         static_assert(sizeof(AecConsts) % 16 == 0, "PowTables behind AecConsts must stay 16-byte aligned");
         PowTables pt;
         pow_tables(&pt);
-        AEC_TRY(hipMemcpy(reinterpret_cast<char *>(h->d_consts) + sizeof(K), &pt, sizeof(pt), hipMemcpyHostToDevice));
+        WMX_CREATE_TRY(wmx_aec_destroy(h), hipMemcpy(reinterpret_cast<char *>(h->d_consts) + sizeof(K), &pt, sizeof(pt), hipMemcpyHostToDevice));
     }
     {
         // the comfort noise's phase table: made once per process with the host libm, one copy per handle on its device
@@ -1703,15 +1696,14 @@ int wmx_aec_create_groups(wmx_aec **out, int n_streams, int chn, int freq, int i
         // behind it, the generator's k-draw steps, k = 1 .. 64: lane l's draw from the state in front of a block, and the 64-draw step
         uint32_t jump[2 * 64];
         for (int l = 0; l < 64; l++) aec_lcg_jump(l + 1, &jump[2 * l], &jump[2 * l + 1]);
-        AEC_TRY(hipMalloc(&h->d_noise_tab, sizeof(AecNoiseEntry) * kAecNoiseTab + sizeof(jump)));
-        AEC_TRY(hipMemcpy(h->d_noise_tab, tab.data(), sizeof(AecNoiseEntry) * kAecNoiseTab, hipMemcpyHostToDevice));
-        AEC_TRY(hipMemcpy(h->d_noise_tab + kAecNoiseTab, jump, sizeof(jump), hipMemcpyHostToDevice));
+        WMX_CREATE_TRY(wmx_aec_destroy(h), hipMalloc(&h->d_noise_tab, sizeof(AecNoiseEntry) * kAecNoiseTab + sizeof(jump)));
+        WMX_CREATE_TRY(wmx_aec_destroy(h), hipMemcpy(h->d_noise_tab, tab.data(), sizeof(AecNoiseEntry) * kAecNoiseTab, hipMemcpyHostToDevice));
+        WMX_CREATE_TRY(wmx_aec_destroy(h), hipMemcpy(h->d_noise_tab + kAecNoiseTab, jump, sizeof(jump), hipMemcpyHostToDevice));
     }
-    AEC_TRY(hipMemcpy(h->d_tmpl, st.data(), AS_WORDS * sizeof(float), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_aec_destroy(h), hipMemcpy(h->d_tmpl, st.data(), AS_WORDS * sizeof(float), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(aec_fill_state, dim3(1024), dim3(256), 0, nullptr, h->d_state, h->d_tmpl, (int)AS_WORDS, n_streams);
-    AEC_TRY(hipGetLastError());
-    AEC_TRY(hipDeviceSynchronize());
-#undef AEC_TRY
+    WMX_CREATE_TRY(wmx_aec_destroy(h), hipGetLastError());
+    WMX_CREATE_TRY(wmx_aec_destroy(h), hipDeviceSynchronize());
     *out = h;
     return 0;
 }
@@ -1871,24 +1863,23 @@ int wmx_aec_run_cohorts(wmx_aec *h, int mode, const int16_t *d_far, long far_pac
 // A stream's new cohort must have been restarted (wmx_aec_reset_cohort) at the same point of the packet sequence, or the
 // stream inherits ring positions of a control plane that started earlier -- which is what no handle of the reference has.
 int wmx_aec_reset_streams(wmx_aec *h, const int32_t *idx, int n, int cohort, void *stream) {
-    WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || n < 0 || (n > 0 && !idx) || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
-    if (cohort >= 0 && h->co.n() > 1 && !h->d_stream_far) return WMX_ESTATE;
-    if (n == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    const int32_t *d_idx = nullptr;
-    const int rc = h->life.upload(idx, n, h->n_streams, s, &d_idx);
-    if (rc != 0) return rc;
-    const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
-    hipLaunchKernelGGL((fill_rows_idx<float>), dim3(grid), dim3(256), 0, s, h->d_state, (const float *)h->d_tmpl, (int)AS_WORDS, d_idx, n);
-    if (cohort >= 0 && h->d_stream_far) {
-        hipLaunchKernelGGL(aec_set_group, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_stream_far, d_idx, n, cohort);
-        for (int i = 0; i < n; i++) h->h_cohort_of[(size_t)idx[i]] = cohort;
-        h->order_dirty = true;
-    }
-    WMX_LAUNCH_CHECK();
-    return h->life.done(s);
+    int refused = 0;  // what this call's own argument comes to
+    if (h && (cohort < -1 || cohort >= h->co.n()))
+        refused = WMX_EINVAL;
+    else if (h && cohort >= 0 && h->co.n() > 1 && !h->d_stream_far)
+        refused = WMX_ESTATE;
+    return reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
+        hipLaunchKernelGGL((fill_rows_idx<float>), dim3(grid), dim3(256), 0, s, h->d_state, (const float *)h->d_tmpl, (int)AS_WORDS, d_idx, n);
+        if (cohort >= 0 && h->d_stream_far) {
+            hipLaunchKernelGGL(aec_set_group, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_stream_far, d_idx, n, cohort);
+            for (int i = 0; i < n; i++) h->h_cohort_of[(size_t)idx[i]] = cohort;
+            h->order_dirty = true;
+        }
+        WMX_LAUNCH_CHECK();
+        return 0;
+    }, refused);
 }
 
 // aec_init for a whole cohort's SHARED part: the control plane starts over (start-up phase, empty far-end buffer, ring
@@ -1896,49 +1887,34 @@ int wmx_aec_reset_streams(wmx_aec *h, const int32_t *idx, int n, int cohort, voi
 // wmx_aec_reset_streams(..., cohort, ...).
 int wmx_aec_reset_cohort(wmx_aec *h, int cohort, void *stream) { return wmx::reset_cohort(h, cohort, stream); }
 
-int wmx_aec_set_active(wmx_aec *h, const uint8_t *host_mask, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    return h->life.set_active(h->n_streams, host_mask, wmx::as_stream(stream));
-}
+int wmx_aec_set_active(wmx_aec *h, const uint8_t *host_mask, void *stream) { return wmx::set_active(h, host_mask, stream); }
 
 // stream migration: [header | AS_WORDS state words].  The stream's COHORT (control plane + far-end history) travels on its
 // own: [header | AecCtl | the group's far-end buffers]; a destination cohort that received it continues exactly where the
 // source cohort stands, so a stream imported into it behaves as if it had never moved.
-// Format versions of the AEC's blobs (wmx_internal.h: blob_layout).  Stream: 2 since round 5 turned AS_NBLK (the block count) into
+// Format versions of the AEC's blobs (stage_life.h: blob_layout).  Stream: 2 since round 5 turned AS_NBLK (the block count) into
 // AS_NSEED (the comfort-noise generator's state) in place.  Cohort: 2 since round 6 resized the far-end slab.
 static constexpr uint32_t kAecBlobVersion = 2, kAecCohortBlobVersion = 2;
-int wmx_aec_stream_state_bytes(const wmx_aec *h) { return h ? (int)(sizeof(wmx::BlobHeader) + wmx::AS_WORDS * 4) : WMX_EINVAL; }
+static wmx::StreamBlob aec_blob(const wmx_aec *h) {
+    return {wmx::blob_tag("AEC "), wmx::blob_layout((uint32_t)h->freq, kAecBlobVersion), {{h->d_state, 4, wmx::AS_WORDS}}, 0};
+}
+int wmx_aec_stream_state_bytes(const wmx_aec *h) { return wmx::stream_state_bytes(h, aec_blob); }
 int wmx_aec_cohort_state_bytes(const wmx_aec *h) {
     return h ? h->co.blob_bytes() : WMX_EINVAL;
 }
 
-int wmx_aec_export_stream(wmx_aec *h, int stream_index, void *host_blob) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    char *p = static_cast<char *>(host_blob);
-    blob_begin(p, blob_tag("AEC "), blob_layout((uint32_t)h->freq, kAecBlobVersion), AS_WORDS * 4);
-    WMX_HIP(hipMemcpy(p + sizeof(BlobHeader), h->d_state + (size_t)stream_index * AS_WORDS, AS_WORDS * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
+int wmx_aec_export_stream(wmx_aec *h, int stream_index, void *host_blob) { return wmx::export_stream(h, stream_index, host_blob, aec_blob); }
 
 int wmx_aec_import_stream(wmx_aec *h, int stream_index, const void *host_blob, int cohort) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
-    const int rc = blob_check(host_blob, blob_tag("AEC "), blob_layout((uint32_t)h->freq, kAecBlobVersion), AS_WORDS * 4);
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    WMX_HIP(hipMemcpy(h->d_state + (size_t)stream_index * AS_WORDS, static_cast<const char *>(host_blob) + sizeof(BlobHeader), AS_WORDS * 4,
-                      hipMemcpyHostToDevice));
-    if (cohort >= 0 && h->d_stream_far) {
-        WMX_HIP(hipMemcpy(h->d_stream_far + stream_index, &cohort, sizeof(int), hipMemcpyHostToDevice));
-        h->h_cohort_of[(size_t)stream_index] = cohort;
-        h->order_dirty = true;
-    }
-    return 0;
+    const bool cohort_ok = !h || (cohort >= -1 && cohort < h->co.n());
+    return wmx::import_stream(h, stream_index, host_blob, aec_blob, cohort_ok, wmx::NoHook{}, [=](const char *) {
+        if (cohort >= 0 && h->d_stream_far) {
+            WMX_HIP(hipMemcpy(h->d_stream_far + stream_index, &cohort, sizeof(int), hipMemcpyHostToDevice));
+            h->h_cohort_of[(size_t)stream_index] = cohort;
+            h->order_dirty = true;
+        }
+        return 0;
+    });
 }
 
 int wmx_aec_export_cohort(wmx_aec *h, int cohort, void *host_blob) {

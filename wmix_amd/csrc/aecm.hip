@@ -21,6 +21,7 @@
 // One reference quirk is pinned to its well-defined reading: at 8 kHz with 20 ms packets the second 10 ms frame of a
 // packet replays farendOld[1], which WebRtcAecm_Init leaves uninitialised (it clears 160 bytes, not 160 samples,
 // echo_control_mobile.c:211); here it starts as zeros, what a fresh heap gives (tests/golden/make_aecm_golden.py).
+#include <memory>
 #include <unordered_map>
 #include <vector>
 #include "wmx_internal.h"
@@ -1067,8 +1068,8 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     h->d_state = nullptr;
     h->d_consts = nullptr;
 
-    AecmConsts *K = new AecmConsts();
-    memset(K, 0, sizeof(*K));
+    const std::unique_ptr<AecmConsts> K(new AecmConsts());  // (too large for the stack)
+    memset(K.get(), 0, sizeof(*K));
     spl_twiddles(fx_spl_sin1024, &K->tw);
     memcpy(K->sqrt_hanning, fx_aecm_sqrt_hanning, sizeof(fx_aecm_sqrt_hanning));
     memcpy(K->cos360, fx_aecm_cos, sizeof(fx_aecm_cos));
@@ -1119,37 +1120,26 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     const size_t far_raw = sizeof(int16_t) * (kAecmFarRing + 2 * kAecmFrame + kAecmFrameRing + 64 + 8) + sizeof(int32_t) * (36 + kAecmHist) +
                            sizeof(uint16_t) * (size_t)kAecmHist * kAecmBP + sizeof(uint32_t) * kAecmHist + 64;
     h->co.slab_bytes = (far_raw + 255) / 256 * 256;  // per cohort
-    hipError_t e;
-#define AECM_TRY(x)                                         \
-    if ((e = (x)) != hipSuccess) {                          \
-        const int rc = hip_fail(e, #x, __FILE__, __LINE__); \
-        wmx_aecm_destroy(h);                                \
-        delete K;                                           \
-        return rc;                                          \
-    }
-    AECM_TRY(hipMalloc(&h->d_state, (size_t)A_WORDS * n_streams * sizeof(int32_t)));
-    AECM_TRY(hipMalloc(&h->d_consts, sizeof(AecmConsts)));
+    WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_state, (size_t)A_WORDS * n_streams * sizeof(int32_t)));
+    WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_consts, sizeof(AecmConsts)));
     {
         const int rc = h->co.reserve(n_cohorts, [h] { aecm_carve_far(h); });
         if (rc != 0) {
             wmx_aecm_destroy(h);
-            delete K;
             return rc;
         }
     }
     if (n_cohorts > 1) {
-        AECM_TRY(hipMalloc(&h->d_stream_cohort, sizeof(int) * n_streams));
-        AECM_TRY(hipMemset(h->d_stream_cohort, 0, sizeof(int) * n_streams));
+        WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_stream_cohort, sizeof(int) * n_streams));
+        WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMemset(h->d_stream_cohort, 0, sizeof(int) * n_streams));
     }
-    for (hipEvent_t &ev : h->co.plan_free) AECM_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    AECM_TRY(hipMalloc(&h->d_tmpl, A_WORDS * sizeof(int32_t)));
-    AECM_TRY(hipMemcpy(h->d_consts, K, sizeof(AecmConsts), hipMemcpyHostToDevice));
-    AECM_TRY(hipMemcpy(h->d_tmpl, st.data(), A_WORDS * sizeof(int32_t), hipMemcpyHostToDevice));
+    for (hipEvent_t &ev : h->co.plan_free) WMX_CREATE_TRY(wmx_aecm_destroy(h), hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_tmpl, A_WORDS * sizeof(int32_t)));
+    WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMemcpy(h->d_consts, K.get(), sizeof(AecmConsts), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMemcpy(h->d_tmpl, st.data(), A_WORDS * sizeof(int32_t), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(aecm_fill_state, dim3(1024), dim3(256), 0, nullptr, h->d_state, h->d_tmpl, (int)A_WORDS, n_streams);
-    AECM_TRY(hipGetLastError());
-    AECM_TRY(hipDeviceSynchronize());
-#undef AECM_TRY
-    delete K;
+    WMX_CREATE_TRY(wmx_aecm_destroy(h), hipGetLastError());
+    WMX_CREATE_TRY(wmx_aecm_destroy(h), hipDeviceSynchronize());
     *out = h;
     return 0;
 }
@@ -1211,31 +1201,20 @@ void wmx::aecm_cancel_fork(wmx_aecm *h) {
 extern "C" {
 
 // stream / cohort migration, as for the float AEC
-static constexpr uint32_t kAecmBlobVersion = 1;  // bump when the meaning of a state word changes (wmx_internal.h: blob_layout)
-int wmx_aecm_stream_state_bytes(const wmx_aecm *h) { return h ? (int)(sizeof(wmx::BlobHeader) + wmx::A_WORDS * 4) : WMX_EINVAL; }
-int wmx_aecm_cohort_state_bytes(const wmx_aecm *h) { return h ? h->co.blob_bytes() : WMX_EINVAL; }
-int wmx_aecm_export_stream(wmx_aecm *h, int stream_index, void *host_blob) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    char *p = static_cast<char *>(host_blob);
-    blob_begin(p, blob_tag("AECM"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), A_WORDS * 4);
-    WMX_HIP(hipMemcpy(p + sizeof(BlobHeader), h->d_state + (size_t)stream_index * A_WORDS, A_WORDS * 4, hipMemcpyDeviceToHost));
-    return 0;
+static constexpr uint32_t kAecmBlobVersion = 1;  // bump when the meaning of a state word changes (stage_life.h: blob_layout)
+static wmx::StreamBlob aecm_blob(const wmx_aecm *h) {
+    return {wmx::blob_tag("AECM"), wmx::blob_layout((uint32_t)h->freq, kAecmBlobVersion), {{h->d_state, 4, wmx::A_WORDS}}, 0};
 }
+int wmx_aecm_stream_state_bytes(const wmx_aecm *h) { return wmx::stream_state_bytes(h, aecm_blob); }
+int wmx_aecm_cohort_state_bytes(const wmx_aecm *h) { return h ? h->co.blob_bytes() : WMX_EINVAL; }
+int wmx_aecm_export_stream(wmx_aecm *h, int stream_index, void *host_blob) { return wmx::export_stream(h, stream_index, host_blob, aecm_blob); }
 
 int wmx_aecm_import_stream(wmx_aecm *h, int stream_index, const void *host_blob, int cohort) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
-    const int rc = blob_check(host_blob, blob_tag("AECM"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), A_WORDS * 4);
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    WMX_HIP(hipMemcpy(h->d_state + (size_t)stream_index * A_WORDS, static_cast<const char *>(host_blob) + sizeof(BlobHeader), A_WORDS * 4,
-                      hipMemcpyHostToDevice));
-    if (cohort >= 0 && h->d_stream_cohort) WMX_HIP(hipMemcpy(h->d_stream_cohort + stream_index, &cohort, sizeof(int), hipMemcpyHostToDevice));
-    return 0;
+    const bool cohort_ok = !h || (cohort >= -1 && cohort < h->co.n());
+    return wmx::import_stream(h, stream_index, host_blob, aecm_blob, cohort_ok, wmx::NoHook{}, [=](const char *) {
+        if (cohort >= 0 && h->d_stream_cohort) WMX_HIP(hipMemcpy(h->d_stream_cohort + stream_index, &cohort, sizeof(int), hipMemcpyHostToDevice));
+        return 0;
+    });
 }
 
 int wmx_aecm_export_cohort(wmx_aecm *h, int cohort, void *host_blob) {
@@ -1293,26 +1272,18 @@ int wmx_aecm_retire_cohort(wmx_aecm *h, int cohort) { return wmx::retire_cohort(
 
 // aec_release + aec_init for the listed streams in the AECM build; cohort >= 0 also makes them members of that cohort
 int wmx_aecm_reset_streams(wmx_aecm *h, const int32_t *idx, int n, int cohort, void *stream) {
-    WMX_ON_DEVICE(h);
     using namespace wmx;
-    if (!h || n < 0 || (n > 0 && !idx) || cohort < -1 || cohort >= h->co.n()) return WMX_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    const int32_t *d_idx = nullptr;
-    const int rc = h->life.upload(idx, n, h->n_streams, s, &d_idx);
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL((fill_rows_idx<int32_t>), dim3((unsigned)(n < 4096 ? n : 4096)), dim3(256), 0, s, h->d_state, (const int32_t *)h->d_tmpl,
-                       (int)A_WORDS, d_idx, n);
-    if (cohort >= 0 && h->d_stream_cohort)
-        hipLaunchKernelGGL(aecm_set_cohort, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_stream_cohort, d_idx, n, cohort);
-    WMX_LAUNCH_CHECK();
-    return h->life.done(s);
+    const int refused = h && (cohort < -1 || cohort >= h->co.n()) ? WMX_EINVAL : 0;
+    return reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        hipLaunchKernelGGL((fill_rows_idx<int32_t>), dim3((unsigned)(n < 4096 ? n : 4096)), dim3(256), 0, s, h->d_state, (const int32_t *)h->d_tmpl,
+                           (int)A_WORDS, d_idx, n);
+        if (cohort >= 0 && h->d_stream_cohort)
+            hipLaunchKernelGGL(aecm_set_cohort, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_stream_cohort, d_idx, n, cohort);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    }, refused);
 }
 
-int wmx_aecm_set_active(wmx_aecm *h, const uint8_t *host_mask, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    return h->life.set_active(h->n_streams, host_mask, wmx::as_stream(stream));
-}
+int wmx_aecm_set_active(wmx_aecm *h, const uint8_t *host_mask, void *stream) { return wmx::set_active(h, host_mask, stream); }
 
 }  // extern "C"

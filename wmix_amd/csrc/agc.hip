@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
-#include "wmx_internal.h"
+#include "stage_life.h"
 #include "agc_gain_table.h"
 #include "spl_dev.h"
 
@@ -661,21 +661,17 @@ int wmx_agc_destroy(wmx_agc *h) {
 // agc_release + agc_init for the listed streams (src/webrtc.c:694-753, 841-860).  wmx_agc_reset_streams: agc_init with the gain
 // each stream has; wmx_agc_reset_streams_gain: agc_init(..., value, ...) -- the new handles' own compression gain.
 static int agc_reset(wmx_agc *h, const int32_t *idx, int n, const int *value, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h || n < 0 || (n > 0 && !idx)) return WMX_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = wmx::as_stream(stream);
-    const int32_t *d_idx = nullptr;
-    int rc = h->life.upload(idx, n, h->n_streams, s, &d_idx);  // validates the list
-    if (rc != 0) return rc;
-    if (value) {
-        const int t = wmx::agc_table_for(h, *value, s, "wmx_agc_reset_streams_gain");  // agc_init returns NULL: nothing is reset
-        if (t < 0) return t;
-        if ((rc = wmx::agc_point_streams(h, idx, d_idx, n, t, s)) != 0) return rc;
-    }
-    hipLaunchKernelGGL(wmx::agc_fill_state, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_s16, h->d_s32, h->n_streams, d_idx, n);
-    WMX_LAUNCH_CHECK();
-    return h->life.done(s);
+    return wmx::reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        if (value) {
+            const int t = wmx::agc_table_for(h, *value, s, "wmx_agc_reset_streams_gain");  // agc_init returns NULL: nothing is reset
+            if (t < 0) return t;
+            const int rc = wmx::agc_point_streams(h, idx, d_idx, n, t, s);
+            if (rc != 0) return rc;
+        }
+        hipLaunchKernelGGL(wmx::agc_fill_state, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_s16, h->d_s32, h->n_streams, d_idx, n);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    });
 }
 int wmx_agc_reset_streams(wmx_agc *h, const int32_t *idx, int n, void *stream) { return agc_reset(h, idx, n, nullptr, stream); }
 int wmx_agc_reset_streams_gain(wmx_agc *h, const int32_t *idx, int n, int value, void *stream) { return agc_reset(h, idx, n, &value, stream); }
@@ -683,17 +679,10 @@ int wmx_agc_reset_streams_gain(wmx_agc *h, const int32_t *idx, int n, int value,
 // agc_addition for the listed streams (src/webrtc.c:824-839: WebRtcAgc_set_config on a running handle -- the state stays, the
 // table changes).  A value the reference's set_config refuses leaves every stream as it was (agc_addition prints and carries on).
 int wmx_agc_set_gain_streams(wmx_agc *h, const int32_t *idx, int n, int value, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h || n < 0 || (n > 0 && !idx)) return WMX_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = wmx::as_stream(stream);
-    const int32_t *d_idx = nullptr;
-    int rc = h->life.upload(idx, n, h->n_streams, s, &d_idx);  // validates the list
-    if (rc != 0) return rc;
-    const int t = wmx::agc_table_for(h, value, s, "wmx_agc_set_gain_streams");
-    if (t < 0) return t;
-    if ((rc = wmx::agc_point_streams(h, idx, d_idx, n, t, s)) != 0) return rc;
-    return h->life.done(s);
+    return wmx::reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        const int t = wmx::agc_table_for(h, value, s, "wmx_agc_set_gain_streams");
+        return t < 0 ? t : wmx::agc_point_streams(h, idx, d_idx, n, t, s);
+    });
 }
 
 // the compression gain stream i runs with
@@ -702,11 +691,7 @@ int wmx_agc_stream_gain(const wmx_agc *h, int stream_index) {
     return h->table_value[h->stream_table[(size_t)stream_index]];
 }
 
-int wmx_agc_set_active(wmx_agc *h, const uint8_t *host_mask, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    return h->life.set_active(h->n_streams, host_mask, wmx::as_stream(stream));
-}
+int wmx_agc_set_active(wmx_agc *h, const uint8_t *host_mask, void *stream) { return wmx::set_active(h, host_mask, stream); }
 
 // agc_addition for EVERY stream of the batch (src/webrtc.c:824-839): WebRtcAgc_set_config with a new compression gain -> the batch
 // is back on one table (table 0) and on the kernels that know no other.  Returns WMX_EINVAL and changes nothing when the
@@ -753,24 +738,16 @@ int wmx_agc_create(wmx_agc **out, int n_streams, int chn, int freq, int interval
     h->chn = chn;
     h->freq = freq;
     h->pkg = freq / 1000 * (freq <= 16000 ? 10 : 5);  // 5 ms packets at 32 kHz, src/webrtc.c:724-728
-    hipError_t e;
-#define AGC_TRY(x)                                         \
-    if ((e = (x)) != hipSuccess) {                         \
-        int rc = hip_fail(e, #x, __FILE__, __LINE__);      \
-        wmx_agc_destroy(h);                                \
-        return rc;                                         \
-    }
-    AGC_TRY(hipMalloc(&h->d_s16, (size_t)A16_WORDS * n_streams * sizeof(int16_t)));
-    AGC_TRY(hipMalloc(&h->d_s32, (size_t)A32_WORDS * n_streams * sizeof(int32_t)));
-    AGC_TRY(hipMalloc(&h->d_table, (size_t)wmx_agc::kMaxTables * 32 * sizeof(int32_t)));
-    AGC_TRY(hipMalloc(&h->d_stream_table, (size_t)n_streams * sizeof(uint16_t)));
-    AGC_TRY(hipMemset(h->d_stream_table, 0, (size_t)n_streams * sizeof(uint16_t)));
+    WMX_CREATE_TRY(wmx_agc_destroy(h), hipMalloc(&h->d_s16, (size_t)A16_WORDS * n_streams * sizeof(int16_t)));
+    WMX_CREATE_TRY(wmx_agc_destroy(h), hipMalloc(&h->d_s32, (size_t)A32_WORDS * n_streams * sizeof(int32_t)));
+    WMX_CREATE_TRY(wmx_agc_destroy(h), hipMalloc(&h->d_table, (size_t)wmx_agc::kMaxTables * 32 * sizeof(int32_t)));
+    WMX_CREATE_TRY(wmx_agc_destroy(h), hipMalloc(&h->d_stream_table, (size_t)n_streams * sizeof(uint16_t)));
+    WMX_CREATE_TRY(wmx_agc_destroy(h), hipMemset(h->d_stream_table, 0, (size_t)n_streams * sizeof(uint16_t)));
     h->stream_table.assign((size_t)n_streams, (uint16_t)0);
     h->n_off_batch = 0;
     hipLaunchKernelGGL(agc_fill_state, dim3(512), dim3(256), 0, nullptr, h->d_s16, h->d_s32, n_streams, (const int32_t *)nullptr, 0);
-    AGC_TRY(hipGetLastError());
-    AGC_TRY(hipDeviceSynchronize());
-#undef AGC_TRY
+    WMX_CREATE_TRY(wmx_agc_destroy(h), hipGetLastError());
+    WMX_CREATE_TRY(wmx_agc_destroy(h), hipDeviceSynchronize());
     const int rc = wmx_agc_set_gain(h, value);  // agc_init fails (NULL) when set_config fails
     if (rc != 0) {
         wmx_agc_destroy(h);
@@ -782,43 +759,38 @@ int wmx_agc_create(wmx_agc **out, int n_streams, int chn, int freq, int interval
 
 // stream migration: [header | 13 int32 fields | 8 int16 fields | int32 compression gain] -- the gain is the handle's own
 // (WebRtcAgc_set_config's value lives in the reference's handle), so it travels with the stream
-static constexpr uint32_t kAgcBlobVersion = 1;  // bump when the meaning of a state word changes (wmx_internal.h: blob_layout)
-int wmx_agc_stream_state_bytes(const wmx_agc *h) { return h ? (int)(sizeof(wmx::BlobHeader) + wmx::A32_WORDS * 4 + wmx::A16_WORDS * 2 + 4) : WMX_EINVAL; }
+// Version 1 (bump when the meaning of a state word changes, stage_life.h: blob_layout).
+static wmx::StreamBlob agc_blob(const wmx_agc *h) {
+    return {wmx::blob_tag("AGC "), wmx::blob_layout((uint32_t)h->freq, 1), {{h->d_s32, 4, wmx::A32_WORDS, true}, {h->d_s16, 2, wmx::A16_WORDS, true}},
+            sizeof(int32_t)};
+}
+int wmx_agc_stream_state_bytes(const wmx_agc *h) { return wmx::stream_state_bytes(h, agc_blob); }
 
 int wmx_agc_export_stream(wmx_agc *h, int stream_index, void *host_blob) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    char *p = static_cast<char *>(host_blob);
-    blob_begin(p, blob_tag("AGC "), blob_layout((uint32_t)h->freq, kAgcBlobVersion), A32_WORDS * 4 + A16_WORDS * 2 + 4);
-    p += sizeof(BlobHeader);
-    WMX_HIP(column_to_host(reinterpret_cast<int32_t *>(p), h->d_s32, A32_WORDS, h->n_streams, stream_index));
-    WMX_HIP(column_to_host(reinterpret_cast<int16_t *>(p + A32_WORDS * 4), h->d_s16, A16_WORDS, h->n_streams, stream_index));
-    const int32_t value = h->table_value[h->stream_table[(size_t)stream_index]];
-    memcpy(p + A32_WORDS * 4 + A16_WORDS * 2, &value, 4);
-    return 0;
+    return wmx::export_stream(h, stream_index, host_blob, agc_blob, [=](char *tail) {
+        const int32_t value = h->table_value[h->stream_table[(size_t)stream_index]];
+        memcpy(tail, &value, sizeof(value));
+        return 0;
+    });
 }
 
 int wmx_agc_import_stream(wmx_agc *h, int stream_index, const void *host_blob) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    const int rc = blob_check(host_blob, blob_tag("AGC "), blob_layout((uint32_t)h->freq, kAgcBlobVersion), A32_WORDS * 4 + A16_WORDS * 2 + 4);
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    const char *p = static_cast<const char *>(host_blob) + sizeof(BlobHeader);
-    int32_t value;
-    memcpy(&value, p + A32_WORDS * 4 + A16_WORDS * 2, 4);
-    const int t = agc_table_for(h, value, nullptr, "wmx_agc_import_stream");
-    if (t < 0) return t;
-    WMX_HIP(column_from_host(h->d_s32, reinterpret_cast<const int32_t *>(p), A32_WORDS, h->n_streams, stream_index));
-    WMX_HIP(column_from_host(h->d_s16, reinterpret_cast<const int16_t *>(p + A32_WORDS * 4), A16_WORDS, h->n_streams, stream_index));
-    uint16_t &cur = h->stream_table[(size_t)stream_index];
-    h->n_off_batch += (t != 0) - (cur != 0);
-    cur = (uint16_t)t;
-    WMX_HIP(hipMemcpy(h->d_stream_table + stream_index, &cur, sizeof(uint16_t), hipMemcpyHostToDevice));
-    return 0;
+    int t = 0;  // the table of the blob's gain: looked up (it may refuse) before the state is written, pointed to behind it
+    return wmx::import_stream(
+        h, stream_index, host_blob, agc_blob, true,
+        [&](const char *tail) {
+            int32_t value;
+            memcpy(&value, tail, sizeof(value));
+            t = wmx::agc_table_for(h, value, nullptr, "wmx_agc_import_stream");
+            return t < 0 ? t : 0;
+        },
+        [&](const char *) {
+            uint16_t &cur = h->stream_table[(size_t)stream_index];
+            h->n_off_batch += (t != 0) - (cur != 0);
+            cur = (uint16_t)t;
+            WMX_HIP(hipMemcpy(h->d_stream_table + stream_index, &cur, sizeof(uint16_t), hipMemcpyHostToDevice));
+            return 0;
+        });
 }
 
 int wmx_agc_packet_samples(const wmx_agc *h) { return h ? h->pkg * h->chn : WMX_EINVAL; }

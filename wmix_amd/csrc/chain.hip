@@ -8,6 +8,7 @@
 // HIP stream (no host synchronisation, nothing copied), and the per-stream lifetime calls forwarded to every stage.
 // A C host (examples/host_chain.c) needs nothing else of the library for the chain.
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 #include "wmx_internal.h"
 
@@ -31,6 +32,55 @@ struct wmx_chain {
     std::vector<int32_t> stream_cohort_made;
     hipEvent_t gate_after_ns = nullptr;  // recorded behind the noise suppressor's launch by the next process call (wmx::chain_gate_after_ns)
 };
+
+// The chain's stages in the heartbeat's order, and how each takes the per-stream lifetime calls: THE list every fan-out below walks.
+// A chain's blob is its stages' blobs in this order.  (The two cancellers take a cohort; the others do not hear of it.)
+namespace {
+struct Stage {
+    unsigned on, build, build_bit;  // kept by wmx_chain_set_stages(stages) when stages has `on` and (stages & build) == build_bit
+    void *(*get)(const wmx_chain *);
+    void (*drop)(wmx_chain *);  // *_release, the pointer zeroed
+    int (*reset_streams)(wmx_chain *, const int32_t *, int, int cohort, void *);
+    int (*set_active)(wmx_chain *, const uint8_t *, void *);
+    int (*stream_state_bytes)(const wmx_chain *);
+    int (*export_stream)(wmx_chain *, int, void *);
+    int (*import_stream)(wmx_chain *, int, const void *, int cohort);
+    bool kept_by(unsigned stages) const { return (stages & on) && (stages & build) == build_bit; }
+};
+template <auto M, auto Destroy, auto Reset, auto SetActive, auto Bytes, auto Export, auto Import>
+constexpr Stage stage(unsigned on, unsigned build, unsigned build_bit) {
+    using H = std::remove_reference_t<decltype(std::declval<wmx_chain>().*M)>;
+    constexpr bool cohorts = std::is_invocable_v<decltype(Import), H, int, const void *, int>;
+    return {on, build, build_bit,
+            [](const wmx_chain *c) -> void * { return c->*M; },
+            [](wmx_chain *c) { Destroy(c->*M), c->*M = nullptr; },
+            [](wmx_chain *c, const int32_t *idx, int n, int cohort, void *s) {
+                if constexpr (cohorts) return Reset(c->*M, idx, n, cohort, s);
+                else return Reset(c->*M, idx, n, s);
+            },
+            [](wmx_chain *c, const uint8_t *mask, void *s) { return SetActive(c->*M, mask, s); },
+            [](const wmx_chain *c) { return Bytes(c->*M); },
+            [](wmx_chain *c, int i, void *blob) { return Export(c->*M, i, blob); },
+            [](wmx_chain *c, int i, const void *blob, int cohort) {
+                if constexpr (cohorts) return Import(c->*M, i, blob, cohort);
+                else return Import(c->*M, i, blob);
+            }};
+}
+#define WMX_STAGE(m) stage<&wmx_chain::m, wmx_##m##_destroy, wmx_##m##_reset_streams, wmx_##m##_set_active, wmx_##m##_stream_state_bytes, \
+                           wmx_##m##_export_stream, wmx_##m##_import_stream>
+const Stage kStages[] = {WMX_STAGE(ns)(WMX_CHAIN_NS, WMX_CHAIN_NSX, 0),      WMX_STAGE(nsx)(WMX_CHAIN_NS, WMX_CHAIN_NSX, WMX_CHAIN_NSX),
+                         WMX_STAGE(aec)(WMX_CHAIN_AEC, WMX_CHAIN_AECM, 0),   WMX_STAGE(aecm)(WMX_CHAIN_AEC, WMX_CHAIN_AECM, WMX_CHAIN_AECM),
+                         WMX_STAGE(agc)(WMX_CHAIN_AGC, 0, 0),                WMX_STAGE(vad)(WMX_CHAIN_VAD, 0, 0)};
+#undef WMX_STAGE
+// f(stage) for every stage the chain has, until one fails
+template <class F>
+int each_stage(const wmx_chain *h, F f) {
+    int rc = 0;
+    for (const Stage &st : kStages)
+        if (rc == 0 && st.get(h)) rc = f(st);
+    return rc;
+}
+}  // namespace
 
 namespace wmx {
 // For the packet pipeline (pipe.hip): an event the NEXT wmx_chain_process call records on its stream between the noise suppressor and
@@ -56,12 +106,7 @@ extern "C" {
 int wmx_chain_destroy(wmx_chain *h) {
     WMX_ON_DEVICE(h);
     if (!h) return 0;
-    if (h->ns) wmx_ns_destroy(h->ns);
-    if (h->nsx) wmx_nsx_destroy(h->nsx);
-    if (h->aec) wmx_aec_destroy(h->aec);
-    if (h->aecm) wmx_aecm_destroy(h->aecm);
-    if (h->agc) wmx_agc_destroy(h->agc);
-    if (h->vad) wmx_vad_destroy(h->vad);
+    each_stage(h, [h](const Stage &st) { return st.drop(h), 0; });
     delete h;
     return 0;
 }
@@ -126,16 +171,10 @@ int wmx_chain_set_stages(wmx_chain *h, unsigned stages, int agc_value) {
     }
     if (agc_value >= 0) h->agc_value = agc_value;
     // what goes: a stage switched off, or kept on in its OTHER build (float <-> fixed point)
-    const bool ns_goes = h->ns && (!(stages & WMX_CHAIN_NS) || (stages & WMX_CHAIN_NSX));
-    const bool nsx_goes = h->nsx && (!(stages & WMX_CHAIN_NS) || !(stages & WMX_CHAIN_NSX));
-    const bool aec_goes = h->aec && (!(stages & WMX_CHAIN_AEC) || (stages & WMX_CHAIN_AECM));
-    const bool aecm_goes = h->aecm && (!(stages & WMX_CHAIN_AEC) || !(stages & WMX_CHAIN_AECM));
-    if (ns_goes) wmx_ns_destroy(h->ns), h->ns = nullptr;
-    if (nsx_goes) wmx_nsx_destroy(h->nsx), h->nsx = nullptr;
-    if (aec_goes) wmx_aec_destroy(h->aec), h->aec = nullptr;
-    if (aecm_goes) wmx_aecm_destroy(h->aecm), h->aecm = nullptr;
-    if (h->agc && !(stages & WMX_CHAIN_AGC)) wmx_agc_destroy(h->agc), h->agc = nullptr;
-    if (h->vad && !(stages & WMX_CHAIN_VAD)) wmx_vad_destroy(h->vad), h->vad = nullptr;
+    each_stage(h, [=](const Stage &st) {
+        if (!st.kept_by(stages)) st.drop(h);
+        return 0;
+    });
     if (!h->aec && !h->aecm) {  // without a canceller a chain has one cohort
         h->n_cohorts = 1;
         h->zero_delays.assign(1, 0);
@@ -332,28 +371,16 @@ int wmx_chain_process_groups(wmx_chain *h, const int16_t *d_far, long far_packet
 int wmx_chain_reset_streams(wmx_chain *h, const int32_t *idx, int n, int cohort, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
-    int rc = 0;
-    if (rc == 0 && h->ns) rc = wmx_ns_reset_streams(h->ns, idx, n, stream);
-    if (rc == 0 && h->nsx) rc = wmx_nsx_reset_streams(h->nsx, idx, n, stream);
-    if (rc == 0 && h->aec) rc = wmx_aec_reset_streams(h->aec, idx, n, cohort, stream);
-    if (rc == 0 && h->aecm) rc = wmx_aecm_reset_streams(h->aecm, idx, n, cohort, stream);
-    if (rc == 0 && h->agc) rc = wmx_agc_reset_streams(h->agc, idx, n, stream);
-    if (rc == 0 && h->vad) rc = wmx_vad_reset_streams(h->vad, idx, n, stream);
-    return rc;
+    return each_stage(h, [=](const Stage &st) { return st.reset_streams(h, idx, n, cohort, stream); });
 }
 
 int wmx_chain_reset_streams_gain(wmx_chain *h, const int32_t *idx, int n, int cohort, int agc_value, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
-    int rc = 0;
     // the one stage that can refuse (agc_init returns NULL for a gain outside the table's range) goes first: nothing is reset then
-    if (rc == 0 && h->agc) rc = wmx_agc_reset_streams_gain(h->agc, idx, n, agc_value, stream);
-    if (rc == 0 && h->ns) rc = wmx_ns_reset_streams(h->ns, idx, n, stream);
-    if (rc == 0 && h->nsx) rc = wmx_nsx_reset_streams(h->nsx, idx, n, stream);
-    if (rc == 0 && h->aec) rc = wmx_aec_reset_streams(h->aec, idx, n, cohort, stream);
-    if (rc == 0 && h->aecm) rc = wmx_aecm_reset_streams(h->aecm, idx, n, cohort, stream);
-    if (rc == 0 && h->vad) rc = wmx_vad_reset_streams(h->vad, idx, n, stream);
-    return rc;
+    const int rc = h->agc ? wmx_agc_reset_streams_gain(h->agc, idx, n, agc_value, stream) : 0;
+    if (rc != 0) return rc;
+    return each_stage(h, [=](const Stage &st) { return st.on == WMX_CHAIN_AGC ? 0 : st.reset_streams(h, idx, n, cohort, stream); });
 }
 
 int wmx_chain_set_agc_gain_streams(wmx_chain *h, const int32_t *idx, int n, int agc_value, void *stream) {
@@ -408,50 +435,37 @@ int wmx_chain_cohorts(const wmx_chain *h) { return h ? h->n_cohorts : WMX_EINVAL
 // travels separately through wmx_aec_export_cohort / wmx_aec_import_cohort on wmx_chain_aec(h).
 int wmx_chain_stream_state_bytes(const wmx_chain *h) {
     if (!h) return WMX_EINVAL;
-    return (h->ns ? wmx_ns_stream_state_bytes(h->ns) : 0) + (h->nsx ? wmx_nsx_stream_state_bytes(h->nsx) : 0) +
-           (h->aec ? wmx_aec_stream_state_bytes(h->aec) : 0) + (h->aecm ? wmx_aecm_stream_state_bytes(h->aecm) : 0) +
-           (h->agc ? wmx_agc_stream_state_bytes(h->agc) : 0) + (h->vad ? wmx_vad_stream_state_bytes(h->vad) : 0);
+    int bytes = 0;
+    each_stage(h, [&](const Stage &st) { return bytes += st.stream_state_bytes(h), 0; });
+    return bytes;
 }
 
 int wmx_chain_export_stream(wmx_chain *h, int stream_index, void *host_blob) {
     WMX_ON_DEVICE(h);
     if (!h || !host_blob) return WMX_EINVAL;
     char *p = static_cast<char *>(host_blob);
-    int rc = 0;
-    if (rc == 0 && h->ns) rc = wmx_ns_export_stream(h->ns, stream_index, p), p += wmx_ns_stream_state_bytes(h->ns);
-    if (rc == 0 && h->nsx) rc = wmx_nsx_export_stream(h->nsx, stream_index, p), p += wmx_nsx_stream_state_bytes(h->nsx);
-    if (rc == 0 && h->aec) rc = wmx_aec_export_stream(h->aec, stream_index, p), p += wmx_aec_stream_state_bytes(h->aec);
-    if (rc == 0 && h->aecm) rc = wmx_aecm_export_stream(h->aecm, stream_index, p), p += wmx_aecm_stream_state_bytes(h->aecm);
-    if (rc == 0 && h->agc) rc = wmx_agc_export_stream(h->agc, stream_index, p), p += wmx_agc_stream_state_bytes(h->agc);
-    if (rc == 0 && h->vad) rc = wmx_vad_export_stream(h->vad, stream_index, p), p += wmx_vad_stream_state_bytes(h->vad);
-    return rc;
+    return each_stage(h, [&](const Stage &st) {
+        const int rc = st.export_stream(h, stream_index, p);
+        p += st.stream_state_bytes(h);
+        return rc;
+    });
 }
 
 int wmx_chain_import_stream(wmx_chain *h, int stream_index, const void *host_blob, int cohort) {
     WMX_ON_DEVICE(h);
     if (!h || !host_blob) return WMX_EINVAL;
     const char *p = static_cast<const char *>(host_blob);
-    int rc = 0;
-    if (rc == 0 && h->ns) rc = wmx_ns_import_stream(h->ns, stream_index, p), p += wmx_ns_stream_state_bytes(h->ns);
-    if (rc == 0 && h->nsx) rc = wmx_nsx_import_stream(h->nsx, stream_index, p), p += wmx_nsx_stream_state_bytes(h->nsx);
-    if (rc == 0 && h->aec) rc = wmx_aec_import_stream(h->aec, stream_index, p, cohort), p += wmx_aec_stream_state_bytes(h->aec);
-    if (rc == 0 && h->aecm) rc = wmx_aecm_import_stream(h->aecm, stream_index, p, cohort), p += wmx_aecm_stream_state_bytes(h->aecm);
-    if (rc == 0 && h->agc) rc = wmx_agc_import_stream(h->agc, stream_index, p), p += wmx_agc_stream_state_bytes(h->agc);
-    if (rc == 0 && h->vad) rc = wmx_vad_import_stream(h->vad, stream_index, p), p += wmx_vad_stream_state_bytes(h->vad);
-    return rc;
+    return each_stage(h, [&](const Stage &st) {
+        const int rc = st.import_stream(h, stream_index, p, cohort);
+        p += st.stream_state_bytes(h);
+        return rc;
+    });
 }
 
 int wmx_chain_set_active(wmx_chain *h, const uint8_t *host_mask, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
-    int rc = 0;
-    if (rc == 0 && h->ns) rc = wmx_ns_set_active(h->ns, host_mask, stream);
-    if (rc == 0 && h->nsx) rc = wmx_nsx_set_active(h->nsx, host_mask, stream);
-    if (rc == 0 && h->aec) rc = wmx_aec_set_active(h->aec, host_mask, stream);
-    if (rc == 0 && h->aecm) rc = wmx_aecm_set_active(h->aecm, host_mask, stream);
-    if (rc == 0 && h->agc) rc = wmx_agc_set_active(h->agc, host_mask, stream);
-    if (rc == 0 && h->vad) rc = wmx_vad_set_active(h->vad, host_mask, stream);
-    return rc;
+    return each_stage(h, [=](const Stage &st) { return st.set_active(h, host_mask, stream); });
 }
 
 }  // extern "C"

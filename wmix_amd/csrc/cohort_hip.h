@@ -5,7 +5,7 @@
 #pragma once
 #include <type_traits>
 #include "cohort_reg.h"
-#include "wmx_internal.h"
+#include "stage_life.h"  // the blob header (and wmx_internal.h)
 
 namespace wmx {
 

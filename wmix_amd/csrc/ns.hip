@@ -36,7 +36,7 @@
 // of this library produces anything but the reference's result.)
 #include <cmath>
 #include <vector>
-#include "wmx_internal.h"
+#include "stage_life.h"
 #include "fft_ooura.h"
 #include "libm_dev.h"
 #include "ns_layout.h"
@@ -1049,24 +1049,16 @@ int wmx_ns_create(wmx_ns **out, int n_streams, int chn, int freq) {
     else
         build_ns_template<256>(st, consts);
     h->words = st.size();
-    hipError_t e;
-#define NS_TRY(x)                                                  \
-    if ((e = (x)) != hipSuccess) {                                 \
-        int rc = wmx::hip_fail(e, #x, __FILE__, __LINE__);         \
-        wmx_ns_destroy(h);                                         \
-        return rc;                                                 \
-    }
-    NS_TRY(hipMalloc(&h->d_state, h->words * sizeof(float) * (size_t)n_streams));
-    NS_TRY(hipMalloc(&h->d_hist, (size_t)n_streams * 3 * 1000 * sizeof(unsigned short)));
-    NS_TRY(hipMalloc(&h->d_consts, consts.size() * sizeof(float)));
-    NS_TRY(hipMalloc(&h->d_tmpl, st.size() * sizeof(float)));
-    NS_TRY(hipMemcpy(h->d_consts, consts.data(), consts.size() * sizeof(float), hipMemcpyHostToDevice));
-    NS_TRY(hipMemcpy(h->d_tmpl, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
-    NS_TRY(hipMemset(h->d_hist, 0, (size_t)n_streams * 3 * 1000 * sizeof(unsigned short)));
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipMalloc(&h->d_state, h->words * sizeof(float) * (size_t)n_streams));
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipMalloc(&h->d_hist, (size_t)n_streams * 3 * 1000 * sizeof(unsigned short)));
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipMalloc(&h->d_consts, consts.size() * sizeof(float)));
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipMalloc(&h->d_tmpl, st.size() * sizeof(float)));
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipMemcpy(h->d_consts, consts.data(), consts.size() * sizeof(float), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipMemcpy(h->d_tmpl, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipMemset(h->d_hist, 0, (size_t)n_streams * 3 * 1000 * sizeof(unsigned short)));
     hipLaunchKernelGGL(ns_fill_state, dim3(1024), dim3(256), 0, nullptr, h->d_state, h->d_tmpl, (int)h->words, n_streams);
-    NS_TRY(hipGetLastError());
-    NS_TRY(hipDeviceSynchronize());
-#undef NS_TRY
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipGetLastError());
+    WMX_CREATE_TRY(wmx_ns_destroy(h), hipDeviceSynchronize());
     *out = h;
     return 0;
 }
@@ -1085,53 +1077,25 @@ int wmx_ns_destroy(wmx_ns *h) {
 
 // ns_release + ns_init for the listed streams (src/webrtc.c:560-602, 646-661): WebRtcNs_InitCore state, empty histograms
 int wmx_ns_reset_streams(wmx_ns *h, const int32_t *idx, int n, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h || n < 0 || (n > 0 && !idx)) return WMX_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = wmx::as_stream(stream);
-    const int32_t *d_idx = nullptr;
-    const int rc = h->life.upload(idx, n, h->n_streams, s, &d_idx);
-    if (rc != 0) return rc;
-    const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
-    hipLaunchKernelGGL((wmx::fill_rows_idx<float>), dim3(grid), dim3(256), 0, s, h->d_state, (const float *)h->d_tmpl, (int)h->words, d_idx, n);
-    hipLaunchKernelGGL((wmx::fill_rows_idx<unsigned short>), dim3(grid), dim3(256), 0, s, h->d_hist, (const unsigned short *)nullptr, 3000, d_idx, n);
-    WMX_LAUNCH_CHECK();
-    return h->life.done(s);
+    return wmx::reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
+        hipLaunchKernelGGL((wmx::fill_rows_idx<float>), dim3(grid), dim3(256), 0, s, h->d_state, (const float *)h->d_tmpl, (int)h->words, d_idx, n);
+        hipLaunchKernelGGL((wmx::fill_rows_idx<unsigned short>), dim3(grid), dim3(256), 0, s, h->d_hist, (const unsigned short *)nullptr, 3000, d_idx, n);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
-int wmx_ns_set_active(wmx_ns *h, const uint8_t *host_mask, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    return h->life.set_active(h->n_streams, host_mask, wmx::as_stream(stream));
-}
+int wmx_ns_set_active(wmx_ns *h, const uint8_t *host_mask, void *stream) { return wmx::set_active(h, host_mask, stream); }
 
-// stream migration: [header | state words | 3 x 1000 histogram counters]
-static constexpr uint32_t kNsBlobVersion = 1;  // bump when the meaning of a state word changes (wmx_internal.h: blob_layout)
-int wmx_ns_stream_state_bytes(const wmx_ns *h) { return h ? (int)(sizeof(wmx::BlobHeader) + h->words * 4 + 3000 * 2) : WMX_EINVAL; }
-
-int wmx_ns_export_stream(wmx_ns *h, int stream_index, void *host_blob) {
-    WMX_ON_DEVICE(h);
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    char *p = static_cast<char *>(host_blob);
-    wmx::blob_begin(p, wmx::blob_tag("NS  "), wmx::blob_layout((uint32_t)h->L, kNsBlobVersion), (uint32_t)(h->words * 4 + 6000));
-    p += sizeof(wmx::BlobHeader);
-    WMX_HIP(hipMemcpy(p, h->d_state + (size_t)stream_index * h->words, h->words * 4, hipMemcpyDeviceToHost));
-    WMX_HIP(hipMemcpy(p + h->words * 4, h->d_hist + (size_t)stream_index * 3000, 6000, hipMemcpyDeviceToHost));
-    return 0;
+// stream migration: [header | state words | 3 x 1000 histogram counters]; version 1 (bump when the meaning of a state word changes,
+// stage_life.h: blob_layout)
+static wmx::StreamBlob ns_blob(const wmx_ns *h) {
+    return {wmx::blob_tag("NS  "), wmx::blob_layout((uint32_t)h->L, 1), {{h->d_state, 4, h->words}, {h->d_hist, 2, 3000}}, 0};
 }
-
-int wmx_ns_import_stream(wmx_ns *h, int stream_index, const void *host_blob) {
-    WMX_ON_DEVICE(h);
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    const int rc = wmx::blob_check(host_blob, wmx::blob_tag("NS  "), wmx::blob_layout((uint32_t)h->L, kNsBlobVersion), (uint32_t)(h->words * 4 + 6000));
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    const char *p = static_cast<const char *>(host_blob) + sizeof(wmx::BlobHeader);
-    WMX_HIP(hipMemcpy(h->d_state + (size_t)stream_index * h->words, p, h->words * 4, hipMemcpyHostToDevice));
-    WMX_HIP(hipMemcpy(h->d_hist + (size_t)stream_index * 3000, p + h->words * 4, 6000, hipMemcpyHostToDevice));
-    return 0;
-}
+int wmx_ns_stream_state_bytes(const wmx_ns *h) { return wmx::stream_state_bytes(h, ns_blob); }
+int wmx_ns_export_stream(wmx_ns *h, int stream_index, void *host_blob) { return wmx::export_stream(h, stream_index, host_blob, ns_blob); }
+int wmx_ns_import_stream(wmx_ns *h, int stream_index, const void *host_blob) { return wmx::import_stream(h, stream_index, host_blob, ns_blob); }
 
 int wmx_ns_packet_samples(const wmx_ns *h) { return h ? h->pkg * h->chn : WMX_EINVAL; }
 int wmx_ns_state_words(const wmx_ns *h) { return h ? (int)h->words : WMX_EINVAL; }

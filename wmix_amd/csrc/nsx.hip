@@ -21,7 +21,8 @@
 //
 // Integer path: bit-exact against the reference (tests/test_nsx_gpu.py).
 #include <vector>
-#include "wmx_internal.h"
+#include <memory>
+#include "stage_life.h"
 #include "spl_fx.h"
 #include "fx_tables.h"
 
@@ -1189,55 +1190,25 @@ int wmx_nsx_destroy(wmx_nsx *h) {
 
 // ns_release + ns_init for the listed streams in the reference's MAKE_WEBRTC_NSX build (src/webrtc.c:512-521, 560-602)
 int wmx_nsx_reset_streams(wmx_nsx *h, const int32_t *idx, int n, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h || n < 0 || (n > 0 && !idx)) return WMX_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = wmx::as_stream(stream);
-    const int32_t *d_idx = nullptr;
-    const int rc = h->life.upload(idx, n, h->n_streams, s, &d_idx);
-    if (rc != 0) return rc;
-    const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
-    hipLaunchKernelGGL((wmx::fill_rows_idx<int32_t>), dim3(grid), dim3(256), 0, s, h->d_state, (const int32_t *)h->d_tmpl, h->words, d_idx, n);
-    hipLaunchKernelGGL((wmx::fill_rows_idx<int16_t>), dim3(grid), dim3(256), 0, s, h->d_hist, (const int16_t *)nullptr, 3 * wmx::kNsxHist, d_idx, n);
-    WMX_LAUNCH_CHECK();
-    return h->life.done(s);
+    return wmx::reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
+        hipLaunchKernelGGL((wmx::fill_rows_idx<int32_t>), dim3(grid), dim3(256), 0, s, h->d_state, (const int32_t *)h->d_tmpl, h->words, d_idx, n);
+        hipLaunchKernelGGL((wmx::fill_rows_idx<int16_t>), dim3(grid), dim3(256), 0, s, h->d_hist, (const int16_t *)nullptr, 3 * wmx::kNsxHist, d_idx, n);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
-int wmx_nsx_set_active(wmx_nsx *h, const uint8_t *host_mask, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    return h->life.set_active(h->n_streams, host_mask, wmx::as_stream(stream));
-}
+int wmx_nsx_set_active(wmx_nsx *h, const uint8_t *host_mask, void *stream) { return wmx::set_active(h, host_mask, stream); }
 
-// stream migration: [header | state words | 3 x 1000 histogram counters]
-static constexpr uint32_t kNsxBlobVersion = 1;  // bump when the meaning of a state word changes (wmx_internal.h: blob_layout)
-int wmx_nsx_stream_state_bytes(const wmx_nsx *h) { return h ? (int)(sizeof(wmx::BlobHeader) + h->words * 4 + 3 * wmx::kNsxHist * 2) : WMX_EINVAL; }
-
-int wmx_nsx_export_stream(wmx_nsx *h, int stream_index, void *host_blob) {
-    WMX_ON_DEVICE(h);
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    const size_t hb = 3 * wmx::kNsxHist * 2;
-    char *p = static_cast<char *>(host_blob);
-    wmx::blob_begin(p, wmx::blob_tag("NSX "), wmx::blob_layout((uint32_t)h->words, kNsxBlobVersion), (uint32_t)(h->words * 4 + hb));
-    p += sizeof(wmx::BlobHeader);
-    WMX_HIP(hipMemcpy(p, h->d_state + (size_t)stream_index * h->words, (size_t)h->words * 4, hipMemcpyDeviceToHost));
-    WMX_HIP(hipMemcpy(p + (size_t)h->words * 4, h->d_hist + (size_t)stream_index * 3 * wmx::kNsxHist, hb, hipMemcpyDeviceToHost));
-    return 0;
+// stream migration: [header | state words | 3 x 1000 histogram counters]; version 1 (bump when the meaning of a state word changes,
+// stage_life.h: blob_layout)
+static wmx::StreamBlob nsx_blob(const wmx_nsx *h) {
+    return {wmx::blob_tag("NSX "), wmx::blob_layout((uint32_t)h->words, 1), {{h->d_state, 4, (size_t)h->words}, {h->d_hist, 2, 3 * wmx::kNsxHist}}, 0};
 }
-
-int wmx_nsx_import_stream(wmx_nsx *h, int stream_index, const void *host_blob) {
-    WMX_ON_DEVICE(h);
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    const size_t hb = 3 * wmx::kNsxHist * 2;
-    const int rc = wmx::blob_check(host_blob, wmx::blob_tag("NSX "), wmx::blob_layout((uint32_t)h->words, kNsxBlobVersion), (uint32_t)(h->words * 4 + hb));
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    const char *p = static_cast<const char *>(host_blob) + sizeof(wmx::BlobHeader);
-    WMX_HIP(hipMemcpy(h->d_state + (size_t)stream_index * h->words, p, (size_t)h->words * 4, hipMemcpyHostToDevice));
-    WMX_HIP(hipMemcpy(h->d_hist + (size_t)stream_index * 3 * wmx::kNsxHist, p + (size_t)h->words * 4, hb, hipMemcpyHostToDevice));
-    return 0;
-}
+int wmx_nsx_stream_state_bytes(const wmx_nsx *h) { return wmx::stream_state_bytes(h, nsx_blob); }
+int wmx_nsx_export_stream(wmx_nsx *h, int stream_index, void *host_blob) { return wmx::export_stream(h, stream_index, host_blob, nsx_blob); }
+int wmx_nsx_import_stream(wmx_nsx *h, int stream_index, const void *host_blob) { return wmx::import_stream(h, stream_index, host_blob, nsx_blob); }
 
 int wmx_nsx_create(wmx_nsx **out, int n_streams, int chn, int freq) {
     using namespace wmx;
@@ -1270,8 +1241,8 @@ int wmx_nsx_create(wmx_nsx **out, int n_streams, int chn, int freq) {
     else
         nsx_template<256>(st, chn);
     h->words = (int)st.size();
-    NsxConsts *K = new NsxConsts();
-    memset(K, 0, sizeof(*K));
+    const std::unique_ptr<NsxConsts> K(new NsxConsts());  // (too large for the stack)
+    memset(K.get(), 0, sizeof(*K));
     spl_twiddles(fx_spl_sin1024, &K->tw);
     if (h->ana == 256)
         memcpy(K->window, fx_nsx_window256, sizeof(fx_nsx_window256));
@@ -1287,26 +1258,16 @@ int wmx_nsx_create(wmx_nsx **out, int n_streams, int chn, int freq) {
     K->sum_log_index_5 = fx_nsx_sum_log_index[5], K->sum_log_index_65 = fx_nsx_sum_log_index[65];
     K->sum_sq_log_index_5 = fx_nsx_sum_sq_log_index[5], K->sum_sq_log_index_65 = fx_nsx_sum_sq_log_index[65];
     K->determinant_5 = fx_nsx_determinant[5];
-    hipError_t e;
-#define NSX_TRY(x)                                        \
-    if ((e = (x)) != hipSuccess) {                        \
-        const int rc = hip_fail(e, #x, __FILE__, __LINE__); \
-        wmx_nsx_destroy(h);                               \
-        delete K;                                         \
-        return rc;                                        \
-    }
-    NSX_TRY(hipMalloc(&h->d_state, (size_t)h->words * n_streams * sizeof(int32_t)));
-    NSX_TRY(hipMalloc(&h->d_hist, (size_t)3 * kNsxHist * n_streams * sizeof(int16_t)));
-    NSX_TRY(hipMalloc(&h->d_consts, sizeof(NsxConsts)));
-    NSX_TRY(hipMalloc(&h->d_tmpl, st.size() * sizeof(int32_t)));
-    NSX_TRY(hipMemcpy(h->d_consts, K, sizeof(NsxConsts), hipMemcpyHostToDevice));
-    NSX_TRY(hipMemcpy(h->d_tmpl, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    NSX_TRY(hipMemset(h->d_hist, 0, (size_t)3 * kNsxHist * n_streams * sizeof(int16_t)));
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipMalloc(&h->d_state, (size_t)h->words * n_streams * sizeof(int32_t)));
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipMalloc(&h->d_hist, (size_t)3 * kNsxHist * n_streams * sizeof(int16_t)));
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipMalloc(&h->d_consts, sizeof(NsxConsts)));
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipMalloc(&h->d_tmpl, st.size() * sizeof(int32_t)));
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipMemcpy(h->d_consts, K.get(), sizeof(NsxConsts), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipMemcpy(h->d_tmpl, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipMemset(h->d_hist, 0, (size_t)3 * kNsxHist * n_streams * sizeof(int16_t)));
     hipLaunchKernelGGL(nsx_fill_state, dim3(1024), dim3(256), 0, nullptr, h->d_state, h->d_tmpl, h->words, n_streams);
-    NSX_TRY(hipGetLastError());
-    NSX_TRY(hipDeviceSynchronize());
-#undef NSX_TRY
-    delete K;
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipGetLastError());
+    WMX_CREATE_TRY(wmx_nsx_destroy(h), hipDeviceSynchronize());
     *out = h;
     return 0;
 }

@@ -25,7 +25,7 @@
 // backwards afterwards.
 #include <cstdlib>
 #include <vector>
-#include "wmx_internal.h"
+#include "stage_life.h"
 #include "spl_dev.h"
 
 namespace wmx {
@@ -1184,24 +1184,15 @@ int wmx_vad_destroy(wmx_vad *h) {
 
 // vad_release + vad_init for the listed streams (src/webrtc.c:40-82, 153-164): WebRtcVad_InitCore state, reduce = 4
 int wmx_vad_reset_streams(wmx_vad *h, const int32_t *idx, int n, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h || n < 0 || (n > 0 && !idx)) return WMX_EINVAL;
-    if (n == 0) return 0;
-    hipStream_t s = wmx::as_stream(stream);
-    const int32_t *d_idx = nullptr;
-    const int rc = h->life.upload(idx, n, h->n_streams, s, &d_idx);
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL(wmx::vad_fill_idx, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(64), 0, s, h->d_s16, h->d_s32, (const int16_t *)h->d_tmpl,
-                       h->n_streams, d_idx, n);
-    WMX_LAUNCH_CHECK();
-    return h->life.done(s);
+    return wmx::reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        hipLaunchKernelGGL(wmx::vad_fill_idx, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(64), 0, s, h->d_s16, h->d_s32, (const int16_t *)h->d_tmpl,
+                           h->n_streams, d_idx, n);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
-int wmx_vad_set_active(wmx_vad *h, const uint8_t *host_mask, void *stream) {
-    WMX_ON_DEVICE(h);
-    if (!h) return WMX_EINVAL;
-    return h->life.set_active(h->n_streams, host_mask, wmx::as_stream(stream));
-}
+int wmx_vad_set_active(wmx_vad *h, const uint8_t *host_mask, void *stream) { return wmx::set_active(h, host_mask, stream); }
 
 int wmx_vad_create(wmx_vad **out, int n_streams, int chn, int freq, int interval_ms) {
     using namespace wmx;
@@ -1241,54 +1232,26 @@ int wmx_vad_create(wmx_vad **out, int n_streams, int chn, int freq, int interval
     for (int i = 0; i < 96; i++) t[V16_LOW + i] = 10000;
     for (int i = 0; i < 6; i++) t[V16_MEAN_VALUE + i] = 1600;
     t[V16_REDUCE] = 4;
-    hipError_t e;
-#define VAD_TRY(x)                                         \
-    if ((e = (x)) != hipSuccess) {                         \
-        int rc = hip_fail(e, #x, __FILE__, __LINE__);      \
-        wmx_vad_destroy(h);                                \
-        return rc;                                         \
-    }
-    VAD_TRY(hipMalloc(&h->d_s16, (size_t)V16_WORDS * n_streams * sizeof(int16_t)));
-    VAD_TRY(hipMalloc(&h->d_s32, (size_t)V32_WORDS * n_streams * sizeof(int32_t)));
-    VAD_TRY(hipMalloc(&h->d_tmpl, V16_WORDS * sizeof(int16_t)));
-    VAD_TRY(hipMemcpy(h->d_tmpl, t.data(), V16_WORDS * sizeof(int16_t), hipMemcpyHostToDevice));
+    WMX_CREATE_TRY(wmx_vad_destroy(h), hipMalloc(&h->d_s16, (size_t)V16_WORDS * n_streams * sizeof(int16_t)));
+    WMX_CREATE_TRY(wmx_vad_destroy(h), hipMalloc(&h->d_s32, (size_t)V32_WORDS * n_streams * sizeof(int32_t)));
+    WMX_CREATE_TRY(wmx_vad_destroy(h), hipMalloc(&h->d_tmpl, V16_WORDS * sizeof(int16_t)));
+    WMX_CREATE_TRY(wmx_vad_destroy(h), hipMemcpy(h->d_tmpl, t.data(), V16_WORDS * sizeof(int16_t), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(vad_fill_state, dim3(512), dim3(256), 0, nullptr, h->d_s16, h->d_s32, h->d_tmpl, n_streams);
-    VAD_TRY(hipGetLastError());
-    VAD_TRY(hipDeviceSynchronize());
-#undef VAD_TRY
+    WMX_CREATE_TRY(wmx_vad_destroy(h), hipGetLastError());
+    WMX_CREATE_TRY(wmx_vad_destroy(h), hipDeviceSynchronize());
     *out = h;
     return 0;
 }
 
-// stream migration: [header | V32_WORDS int32 fields | V16_WORDS int16 fields]
-static constexpr uint32_t kVadBlobVersion = 1;  // bump when the meaning of a state word changes (wmx_internal.h: blob_layout)
-int wmx_vad_stream_state_bytes(const wmx_vad *h) { return h ? (int)(sizeof(wmx::BlobHeader) + wmx::V32_WORDS * 4 + wmx::V16_WORDS * 2) : WMX_EINVAL; }
-
-int wmx_vad_export_stream(wmx_vad *h, int stream_index, void *host_blob) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    WMX_HIP(hipDeviceSynchronize());
-    char *p = static_cast<char *>(host_blob);
-    blob_begin(p, blob_tag("VAD "), blob_layout((uint32_t)(h->freq + h->interval_ms), kVadBlobVersion), V32_WORDS * 4 + V16_WORDS * 2);
-    p += sizeof(BlobHeader);
-    WMX_HIP(column_to_host(reinterpret_cast<int32_t *>(p), h->d_s32, V32_WORDS, h->n_streams, stream_index));
-    WMX_HIP(column_to_host(reinterpret_cast<int16_t *>(p + V32_WORDS * 4), h->d_s16, V16_WORDS, h->n_streams, stream_index));
-    return 0;
+// stream migration: [header | V32_WORDS int32 fields | V16_WORDS int16 fields]; version 1 (bump when the meaning of a state word
+// changes, stage_life.h: blob_layout)
+static wmx::StreamBlob vad_blob(const wmx_vad *h) {
+    return {wmx::blob_tag("VAD "), wmx::blob_layout((uint32_t)(h->freq + h->interval_ms), 1),
+            {{h->d_s32, 4, wmx::V32_WORDS, true}, {h->d_s16, 2, wmx::V16_WORDS, true}}, 0};
 }
-
-int wmx_vad_import_stream(wmx_vad *h, int stream_index, const void *host_blob) {
-    WMX_ON_DEVICE(h);
-    using namespace wmx;
-    if (!h || !host_blob || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
-    const int rc = blob_check(host_blob, blob_tag("VAD "), blob_layout((uint32_t)(h->freq + h->interval_ms), kVadBlobVersion), V32_WORDS * 4 + V16_WORDS * 2);
-    if (rc) return rc;
-    WMX_HIP(hipDeviceSynchronize());
-    const char *p = static_cast<const char *>(host_blob) + sizeof(BlobHeader);
-    WMX_HIP(column_from_host(h->d_s32, reinterpret_cast<const int32_t *>(p), V32_WORDS, h->n_streams, stream_index));
-    WMX_HIP(column_from_host(h->d_s16, reinterpret_cast<const int16_t *>(p + V32_WORDS * 4), V16_WORDS, h->n_streams, stream_index));
-    return 0;
-}
+int wmx_vad_stream_state_bytes(const wmx_vad *h) { return wmx::stream_state_bytes(h, vad_blob); }
+int wmx_vad_export_stream(wmx_vad *h, int stream_index, void *host_blob) { return wmx::export_stream(h, stream_index, host_blob, vad_blob); }
+int wmx_vad_import_stream(wmx_vad *h, int stream_index, const void *host_blob) { return wmx::import_stream(h, stream_index, host_blob, vad_blob); }
 
 int wmx_vad_packet_samples(const wmx_vad *h) { return h ? h->pkg * h->chn : WMX_EINVAL; }
 

@@ -155,124 +155,6 @@ struct SchedCache {
     ~SchedCache() { clear(); }
 };
 
-// Per-stream lifetime inside a batch.  The reference creates every handle lazily, releases it when its flag drops or recording
-// idles and creates a new one later (src/wmix.c:565-600, 617-618, 635-636, 683-684, 702-703, 783-813): streams of a batch join,
-// leave and restart on their own.  Two device-side facilities serve that without a new batch:
-//   * an ACTIVE mask [n_streams] (1 = the stream is processed; 0 = its state, and its PCM rows, are left alone, like a handle
-//     nobody calls); nullptr = every stream is active;
-//   * RESET of a list of streams to the state *_init gives (release + init), by a refill kernel of the module.
-// The index list of a reset is staged in a device buffer that is rewritten only after the kernel that read it last has
-// finished (an event, like the AEC plan slots).
-struct StreamLife {
-    uint8_t *d_active = nullptr;
-    int32_t *d_idx = nullptr;
-    size_t idx_cap = 0;
-    hipEvent_t idx_free = nullptr;
-    bool idx_used = false;
-    StreamLife() = default;
-    StreamLife(const StreamLife &) = delete;
-    StreamLife &operator=(const StreamLife &) = delete;
-    // host_mask: n_streams bytes, or nullptr for "all active" (the mask is dropped)
-    int set_active(int n_streams, const uint8_t *host_mask, hipStream_t s) {
-        if (!host_mask) {
-            if (d_active) {
-                // kernels in flight still read it, on `s` or on any other stream the caller ran this handle on: the whole
-                // device is drained before the mask goes (a control-plane call, rare)
-                (void)s;
-                WMX_HIP(hipDeviceSynchronize());
-                (void)hipFree(d_active);
-                d_active = nullptr;
-            }
-            return 0;
-        }
-        if (!d_active) WMX_HIP(hipMalloc(reinterpret_cast<void **>(&d_active), (size_t)n_streams));
-        WMX_HIP(hipMemcpyAsync(d_active, host_mask, (size_t)n_streams, hipMemcpyHostToDevice, s));
-        return 0;
-    }
-    // validates and uploads a reset list; *d_out = device copy, valid for kernels launched on `s` before done(s)
-    int upload(const int32_t *idx, int n, int n_streams, hipStream_t s, const int32_t **d_out) {
-        for (int i = 0; i < n; i++)
-            if (idx[i] < 0 || idx[i] >= n_streams) {
-                set_error("reset_streams: index %d of the list is stream %d of %d", i, idx[i], n_streams);
-                return WMX_EINVAL;
-            }
-        if (idx_used) WMX_HIP(hipEventSynchronize(idx_free));
-        if ((size_t)n > idx_cap) {
-            if (d_idx) (void)hipFree(d_idx);
-            d_idx = nullptr;
-            idx_cap = 0;
-            const size_t cap = (size_t)n < 256 ? 256 : (size_t)n;
-            WMX_HIP(hipMalloc(reinterpret_cast<void **>(&d_idx), cap * sizeof(int32_t)));
-            idx_cap = cap;
-        }
-        if (!idx_free) WMX_HIP(hipEventCreateWithFlags(&idx_free, hipEventDisableTiming));
-        WMX_HIP(hipMemcpyAsync(d_idx, idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        *d_out = d_idx;
-        return 0;
-    }
-    int done(hipStream_t s) {
-        WMX_HIP(hipEventRecord(idx_free, s));
-        idx_used = true;
-        return 0;
-    }
-    void release() {
-        if (d_active) (void)hipFree(d_active);
-        if (d_idx) (void)hipFree(d_idx);
-        if (idx_free) (void)hipEventDestroy(idx_free);
-        d_active = nullptr;
-        d_idx = nullptr;
-        idx_free = nullptr;
-        idx_cap = 0;
-        idx_used = false;
-    }
-};
-
-// Stream migration (wmx_<m>_export_stream / _import_stream): a stream's complete state as a self-describing host blob --
-// a header that names the module and its layout, then the bytes.  Blocking calls (a control-plane operation): the device is
-// drained first, so the blob is the state after every call made so far.
-struct BlobHeader {
-    uint32_t magic;    // 'WMXS'
-    uint32_t module;   // four characters
-    uint32_t layout;   // module-defined: sizes that must agree between exporter and importer (e.g. words per stream, rate)
-    uint32_t bytes;    // payload bytes behind the header
-};
-constexpr uint32_t kBlobMagic = 0x53584d57u;
-// The FORMAT VERSION of a module's blob rides in the top byte of `layout` (rates and word counts stay far below 2^24).  A module bumps
-// its version whenever the MEANING of a state word changes, even if tag, layout and size do not: round 5 turned the AEC's block count
-// (AS_NBLK) into the comfort-noise generator's state (AS_NSEED) in place, and a blob exported by the build before would have been
-// accepted and replayed with the old block count as the seed (round-5 ADVICE, medium).  Blobs of rounds 1-5 carry version 0 and are
-// refused with WMX_ESTATE.
-inline uint32_t blob_layout(uint32_t layout, uint32_t version) { return (layout & 0x00ffffffu) | (version << 24); }
-inline uint32_t blob_tag(const char (&t)[5]) { return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24); }
-inline void blob_begin(void *blob, uint32_t module, uint32_t layout, uint32_t bytes) {
-    BlobHeader hd{kBlobMagic, module, layout, bytes};
-    memcpy(blob, &hd, sizeof(hd));
-}
-// 0, or WMX_ESTATE when the blob was made by another module / layout
-inline int blob_check(const void *blob, uint32_t module, uint32_t layout, uint32_t bytes) {
-    BlobHeader hd;
-    memcpy(&hd, blob, sizeof(hd));
-    if (hd.magic != kBlobMagic || hd.module != module || hd.layout != layout || hd.bytes != bytes) {
-        if (hd.magic == kBlobMagic && hd.module == module && (hd.layout >> 24) != (layout >> 24))
-            set_error("import: the blob is format version %u of this module, this library reads version %u (the meaning of a state word "
-                      "changed in between: re-export from a stream of this build)", hd.layout >> 24, layout >> 24);
-        else
-            set_error("import: the blob is not a state of this module / format (module %08x layout %u bytes %u, expected %08x %u %u)", hd.module,
-                      hd.layout & 0x00ffffffu, hd.bytes, module, layout & 0x00ffffffu, bytes);
-        return WMX_ESTATE;
-    }
-    return 0;
-}
-// field-major device arrays ([field][n_streams]): one stream's column to / from a packed host array
-template <class T>
-inline hipError_t column_to_host(T *host, const T *dev, int fields, int n_streams, int stream) {
-    return hipMemcpy2D(host, sizeof(T), dev + stream, (size_t)n_streams * sizeof(T), sizeof(T), (size_t)fields, hipMemcpyDeviceToHost);
-}
-template <class T>
-inline hipError_t column_from_host(T *dev, const T *host, int fields, int n_streams, int stream) {
-    return hipMemcpy2D(dev + stream, (size_t)n_streams * sizeof(T), host, sizeof(T), sizeof(T), (size_t)fields, hipMemcpyHostToDevice);
-}
-
 // Pinned HOST memory mapped into the device, for the legacy adapters' small buffers: two runtime copies around a launch cost several
 // times the work of a few hundred samples (wmix_pcm_zoom of one package: 43 us with copies).  The kernel reads and writes the mapped
 // buffer over PCIe instead: memcpy in, one launch, one synchronisation, memcpy out.
