@@ -12,13 +12,15 @@
  * -- for n_groups daemons with n_src sources and n_rec record streams each, in the 1 x 8000 Hz format all three platform
  * directories of the reference ship.
  *
- *   host_tick src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform alsa|hi3516|t31] [--rwtest]
+ *   host_tick src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform alsa|hi3516|t31] [--rwtest] [--bridge P]
  *
  * src.i16    int16 [n_ticks][n_groups][n_src][20 ms of (src_freq, src_chn)]   what the task threads play
  * local.i16  int16 [n_ticks][n_groups * n_rec][160]                          the rooms without their loudspeakers
  * out.i16    int16 [n_ticks][ n_groups play | n_groups far | n_groups * n_rec record ][160]
  * --platform: PLAT_AEC_INTERVALMS / PLAT_PLAY_CORRECT of platform/<name>/plat.h (400 ms / 3200 B, 700 / 0, 0 / 0; default alsa)
  * --rwtest:   wmix->rwTest (src/wmix.c:714-732)
+ * --bridge P: the groups are n_groups / P conferences of P call legs (n_rec must be 1): every leg's heartbeat output is loaded into the
+ *             rings of the other legs of its conference, so each leg is played everybody except itself (wmx_tick_bridge)
  * Prints one JSON line.  tests/test_host_chain_gpu.py compares out.i16 with one oracle daemon per group.
  *
  * Build (what __graft_entry__.build() runs):
@@ -73,16 +75,18 @@ static double now_ms(void) {
 
 int main(int argc, char **argv) {
     if (argc < 10) {
-        fprintf(stderr, "usage: %s src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform name] [--rwtest]\n", argv[0]);
+        fprintf(stderr, "usage: %s src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform name] [--rwtest] [--bridge P]\n", argv[0]);
         return 2;
     }
     const int G = atoi(argv[4]), n_src = atoi(argv[5]), R = atoi(argv[6]), T = atoi(argv[7]), sfreq = atoi(argv[8]), schn = atoi(argv[9]);
-    int aec_ms = 400, rwtest = 0;
+    int aec_ms = 400, rwtest = 0, bridge = 0;
     long correct = -1; /* -1: the library's default = platform/alsa */
     const char *platform = "alsa";
     for (int i = 10; i < argc; i++) {
         if (!strcmp(argv[i], "--rwtest")) {
             rwtest = 1;
+        } else if (!strcmp(argv[i], "--bridge") && i + 1 < argc) {
+            bridge = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "--platform") && i + 1 < argc) {
             platform = argv[++i];
             if (!strcmp(platform, "alsa")) {
@@ -116,6 +120,7 @@ int main(int argc, char **argv) {
     WMX_OK(wmx_tick_create(&h, G, R, 1, 8000, 20, aec_ms, 5, WMX_CHAIN_NS | WMX_CHAIN_AEC | WMX_CHAIN_AGC | WMX_CHAIN_VAD));
     if (correct >= 0) WMX_OK(wmx_tick_set_play_correct(h, (uint32_t)correct));
     if (rwtest) WMX_OK(wmx_tick_rw_test(h, 1));
+    if (bridge) WMX_OK(wmx_tick_bridge(h, bridge));
     if (wmx_tick_package_samples(h) != PKG) return 5;
     int16_t *d_src = NULL, *d_play = NULL, *d_rec = NULL, *d_zoom = NULL;
     HIP_OK(hipMalloc((void **)&d_src, (size_t)G * n_src * srow * 2));
@@ -156,7 +161,9 @@ int main(int argc, char **argv) {
     FILE *f = fopen(argv[3], "wb");
     int rc = (!f || fwrite(out, 2, (size_t)T * out_row, f) != (size_t)T * out_row) ? 7 : 0;
     if (f) fclose(f);
-    printf("{\"groups\": %d, \"sources\": %d, \"record_streams\": %d, \"ticks\": %d, \"platform\": \"%s\", \"aec_delay_ms\": %d, \"rw_test\": %d, "
-           "\"wall_ms\": %.3f, \"ms_per_tick\": %.4f, \"rc\": %d}\n", G, n_src, R, T, platform, aec_ms, rwtest, wall, wall / T, rc);
+    printf("{\"groups\": %d, \"sources\": %d, \"record_streams\": %d, \"ticks\": %d, \"platform\": \"%s\", \"aec_delay_ms\": %d, \"rw_test\": %d, ", G,
+           n_src, R, T, platform, aec_ms, rwtest);
+    if (bridge) printf("\"bridge_parties\": %d, ", bridge);
+    printf("\"wall_ms\": %.3f, \"ms_per_tick\": %.4f, \"rc\": %d}\n", wall, wall / T, rc);
     return rc;
 }

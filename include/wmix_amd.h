@@ -423,6 +423,20 @@ int wmx_mix_set_play_correct(wmx_mix *m, uint32_t bytes);
 int wmx_mix_ring_bytes(const wmx_mix *m);
 int wmx_mix_load(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, int n_src,
                  long group_stride, long source_stride, int reduce, uint32_t *head, uint32_t *tick, void *stream);
+/* The bridge load: a mixer whose n_groups rings are read as n_groups / parties conferences of `parties` consecutive rings; ring
+ * c*parties+q is what participant q of conference c hears -- everybody except themself.
+ * For every conference c and every q: the ring c*parties+q afterwards holds what the reference's ring holds after
+ * wmix_load_data(source s of conference c) for s = 0 .. parties-1, s != q, s not muted, in index order, every call from
+ * the cursor (*head, *tick) -- wmx_mix_load's cursor rule, formats, reduce rule, look-ahead note and return values.
+ * Source s of conference c at d_src + c*conf_stride + s*source_stride (int16 elements).  d_mute: NULL or n_groups bytes
+ * ON THE DEVICE, non-zero = that participant's source is not loaded anywhere (they still hear the others).
+ * One launch, every source read once: the saturating add is order dependent, so this is NOT "total minus own"
+ * (wmix_amd/csrc/mix_minus.h).  WMX_EINVAL, nothing launched: parties < 2, parties > WMX_MIX_MAX_PARTIES, n_groups % parties != 0,
+ * and whatever wmx_mix_load refuses. */
+#define WMX_MIX_MAX_PARTIES 32
+int wmx_mix_load_minus(wmx_mix *m, int parties, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
+                       long conf_stride, long source_stride, const uint8_t *d_mute, int reduce, uint32_t *head, uint32_t *tick,
+                       void *stream);
 int wmx_mix_drain(wmx_mix *m, int16_t *d_out, uint32_t bytes, long out_stride, void *stream);
 int wmx_mix_export(const wmx_mix *m, int group, int16_t *host_ring, uint32_t *head_off, uint32_t *tick);
 
@@ -624,6 +638,16 @@ int wmx_tick_play_ns(wmx_tick *h, int on);
  * first record stream back into the group's play ring (wmix_load_data with the heartbeat's own cursor, reduce 1) before the zoom;
  * switching it off forgets the cursor (:728-732) */
 int wmx_tick_rw_test(wmx_tick *h, int on);
+/* The conference bridge.  parties >= 2: the tick's groups are n_groups / parties conferences of call legs (needs rec_per_group == 1,
+ * n_groups % parties == 0, rwTest off; else WMX_EINVAL).  While on, wmx_tick_record loads the chain's output of every participant
+ * into the rings of the OTHER participants of its conference (wmx_mix_load_minus with a cursor of the bridge's own, reduce 1) before
+ * the zoom -- the place and the arguments of the rwTest load (src/wmix.c:716-726) -- so participant q is played everybody except
+ * themself, and the echo canceller of leg q is given exactly what leg q was played.  parties == 0: off, the cursor is forgotten.
+ * wmx_tick_rw_test(h, 1) while the bridge is on returns WMX_EINVAL. */
+int wmx_tick_bridge(wmx_tick *h, int parties);
+/* host_mask: n_groups bytes, non-zero = that participant is muted (loaded nowhere, still hears the others); NULL = nobody.  Copied
+ * into a buffer the handle owns, on `stream`. */
+int wmx_tick_bridge_mute(wmx_tick *h, const uint8_t *host_mask, void *stream);
 /* the daemon of another platform directory: PLAT_AEC_INTERVALMS (alsa 400, hi3516 700, t31 0; plat.h:14/19) is wmx_tick_create's
  * aec_delay_ms -- the FIFO gets AEC_FIFO_PKG_NUM = aec_delay_ms / interval_ms + 2 slots (src/wmixConf.h:141) -- and PLAT_PLAY_CORRECT is
  * set here (wmx_mix_set_play_correct on the tick's rings; default platform/alsa's) */

@@ -1,0 +1,142 @@
+"""bridge_bench.py -- what the conference bridge costs, one JSON line.
+
+1. wmx_mix_load_minus against what a user without it has to do for the same rings: gather the P - 1 foreign sources of every ring into
+   a staging tensor (torch indexing) and one wmx_mix_load(n_src = P - 1) on the same mixer.  Both results are compared on sampled
+   conferences before any time is reported.  Device events around every repetition, the two sides alternating; per side the median
+   and the spread of the medians of 5 consecutive blocks of repetitions (what "the same thing measured again" gives in this run).
+2. The bridge tick with all four stages beside the same wmx_tick with the bridge off: the difference is the bridge's cost per tick.
+
+Bytes of the new call, from shapes: every ring column reads P sources, reads P ring samples and writes P ring samples, 2 B each.
+
+    python tools_dev/bridge_bench.py [--sizes 4096x8x8000,65536x8x16000] [--reps 200] [--tick 4096x8] [--out file.json]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from wmix_amd.mix import MixBatch  # noqa: E402
+from wmix_amd.tick import TickBatch  # noqa: E402
+
+HBM_ACHIEVABLE = 6.3e12  # bytes / s a streaming kernel reaches on this part (MI355X: 8 TB/s spec)
+BLOCKS = 5
+
+
+def stats(ms):
+    ms = np.asarray(ms)
+    blocks = [float(np.median(b)) for b in np.array_split(ms, BLOCKS)]
+    med = float(np.median(ms))
+    return {"median_ms": round(med, 5), "block_medians_ms": [round(b, 5) for b in blocks], "spread": round((max(blocks) - min(blocks)) / med, 4)}
+
+
+def alternate(sides, reps, warmup=20):
+    """sides: callables; every repetition runs each once between its own pair of events -> per-side lists of milliseconds"""
+    for _ in range(warmup):
+        for f in sides:
+            f()
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for _ in sides]
+    for r in range(reps):
+        for k, f in enumerate(sides):
+            ev[k][r][0].record()
+            f()
+            ev[k][r][1].record()
+    torch.cuda.synchronize()
+    return [[a.elapsed_time(b) for a, b in side] for side in ev]
+
+
+def load_minus_vs_gather(n_conf, P, freq, reps):
+    per = freq // 1000 * 20  # one 20 ms package, 1 channel, the ring's own format
+    n = n_conf * P
+    mb = MixBatch(n, 1, freq)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    src = torch.randint(-20000, 20000, (n_conf, P, per), dtype=torch.int16, device="cuda", generator=g)
+    foreign = torch.tensor([[s for s in range(P) if s != q] for q in range(P)], device="cuda")  # [P, P - 1], index order
+
+    def gather_and_load(head, tick):
+        staging = src[:, foreign].reshape(n, P - 1, per)
+        return mb.load(staging, per * 2, freq, 1, head=head, tick=tick)
+
+    # ---- the same rings?  Both from silence, at two cursors that do not overlap, on the same mixer
+    mb.set(0, 0, 1)
+    mb.set_play_correct(0)
+    ha, _ = mb.load_minus(src, P, per * 2, freq, 1, head=0, tick=0)
+    hb, _ = gather_and_load(4 * per * 2, 4 * per * 2)
+    assert ha == per * 2 and hb == 5 * per * 2
+    sample = sorted({0, 1, n_conf // 2, n_conf - 1})
+    for c in sample:
+        for q in range(P):
+            ring = mb.export(c * P + q)[0]
+            assert ring[:per].any() and np.array_equal(ring[:per], ring[4 * per:5 * per]), ("rings differ", c, q)
+            assert not ring[5 * per:].any() and not ring[per:4 * per].any()
+    # ---- time: each side keeps its own running cursor, like a source that plays on
+    cur = {"new": (NULL, 0), "old": (NULL, 0)}
+
+    def new():
+        cur["new"] = mb.load_minus(src, P, per * 2, freq, 1, head=cur["new"][0], tick=cur["new"][1])
+
+    def old():
+        cur["old"] = gather_and_load(*cur["old"])
+
+    t_new, t_old = alternate([new, old], reps)
+    mb.close()
+    a, b = stats(t_new), stats(t_old)
+    moved = n_conf * per * P * 6
+    return {"conferences": n_conf, "parties": P, "ring": "1x%d" % freq, "package_samples": per, "rings_checked": len(sample) * P,
+            "load_minus": a, "gather_then_load": b, "ratio": round(b["median_ms"] / a["median_ms"], 2),
+            "faster_by_more_than_the_spread": bool(b["median_ms"] - a["median_ms"] > max(a["spread"] * a["median_ms"], b["spread"] * b["median_ms"])),
+            "load_minus_bytes": moved, "load_minus_TBs": round(moved / (a["median_ms"] * 1e-3) / 1e12, 3),
+            "share_of_achievable_hbm": round(moved / (a["median_ms"] * 1e-3) / HBM_ACHIEVABLE, 3)}
+
+
+def bridge_tick(n_conf, P, reps):
+    n = n_conf * P
+    from wmix_amd import synth
+    base = synth.conference_inputs(11, reps + 40, 1, 64, 8000, 1)[1]  # [T, 64, 160] talkers, repeated over the batch
+    local = torch.from_numpy(np.ascontiguousarray(base)).to("cuda")
+    idx = torch.arange(n, device="cuda") % 64
+    ticks = [TickBatch(n, 1), TickBatch(n, 1)]  # 1 x 8000 Hz, 20 ms, NS | AEC | AGC | VAD
+    ticks[0].bridge(P)
+    rec = [torch.zeros((n, 160), dtype=torch.int16, device="cuda") for _ in ticks]
+    step = [0, 0]
+
+    def side(k):
+        def f():
+            rec[k].copy_(local[step[k] % local.shape[0]][idx])
+            ticks[k].run(rec[k])
+            step[k] += 1
+        return f
+
+    t_on, t_off = alternate([side(0), side(1)], reps)
+    for t in ticks:
+        t.close()
+    a, b = stats(t_on), stats(t_off)
+    return {"conferences": n_conf, "parties": P, "stages": "NS|AEC|AGC|VAD", "bridge_on": a, "bridge_off": b,
+            "bridge_costs_ms_per_tick": round(a["median_ms"] - b["median_ms"], 5)}
+
+
+NULL = 0xFFFFFFFF
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="4096x8x8000,65536x8x16000", help="conferences x parties x ring rate, comma separated")
+    ap.add_argument("--tick", default="4096x8", help="conferences x parties of the tick measurement; empty = skip")
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
+    res = {"tool": "bridge_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps, "load": [], "tick": None}
+    for s in [x for x in args.sizes.split(",") if x]:
+        n_conf, P, freq = (int(v) for v in s.split("x"))
+        res["load"].append(load_minus_vs_gather(n_conf, P, freq, args.reps))
+    if args.tick:
+        n_conf, P = (int(v) for v in args.tick.split("x"))
+        res["tick"] = bridge_tick(n_conf, P, args.reps)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")

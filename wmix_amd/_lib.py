@@ -219,6 +219,10 @@ def _declare(L):
     L.wmx_tick_play_ns.argtypes = [vp, i]
     L.wmx_tick_rw_test.restype = i
     L.wmx_tick_rw_test.argtypes = [vp, i]
+    L.wmx_tick_bridge.restype = i
+    L.wmx_tick_bridge.argtypes = [vp, i]
+    L.wmx_tick_bridge_mute.restype = i
+    L.wmx_tick_bridge_mute.argtypes = [vp, vp, vp]
     L.wmx_tick_set_play_correct.restype = i
     L.wmx_tick_set_play_correct.argtypes = [vp, C.c_uint32]
     L.wmx_tick_package_samples.restype = i
@@ -402,6 +406,8 @@ def _declare(L):
     L.wmx_mix_ring_bytes.argtypes = [vp]
     L.wmx_mix_load.restype = i
     L.wmx_mix_load.argtypes = [vp, vp, u32, i, i, i, i, C.c_long, C.c_long, i, C.POINTER(u32), C.POINTER(u32), vp]
+    L.wmx_mix_load_minus.restype = i
+    L.wmx_mix_load_minus.argtypes = [vp, i, vp, u32, i, i, i, C.c_long, C.c_long, vp, i, C.POINTER(u32), C.POINTER(u32), vp]
     L.wmx_mix_drain.restype = i
     L.wmx_mix_drain.argtypes = [vp, vp, u32, C.c_long, vp]
     L.wmx_mix_export.restype = i

@@ -18,6 +18,7 @@
 #include "wmx_internal.h"
 #include "../../include/wmix_compat.h"
 #include "mix_sched.h"
+#include "mix_minus.h"
 
 namespace wmx {
 namespace {
@@ -88,6 +89,64 @@ __global__ __launch_bounds__(256) void drain_kernel(int16_t *__restrict__ rings,
     }
 }
 
+// load_kernel's evaluation of one schedule entry for one source (that kernel keeps its own copy: it is not touched)
+__device__ __forceinline__ int16_t load_entry_value(const int16_t *__restrict__ p, const LoadEntry e, int rdce) {
+    int16_t v;
+    if (e.k < 0) {
+        v = p[e.src];
+    } else {
+        const int16_t prev = p[e.src - e.step];
+        const float st = (float)((int)p[e.src] - (int)prev) / (float)e.n2;
+        float sum = st;
+        for (int j = 0; j < e.k; j++) sum += st;
+        v = (int16_t)((float)prev + sum);
+    }
+    return (int16_t)(v / rdce);
+}
+
+// The bridge load (mix_minus.h): one thread = one ring-sample column of one conference, i.e. the same sample position in the
+// `parties` consecutive rings of that conference.  Every source is evaluated ONCE.  Forward sweep: y[q] = F_q(ring_q) with the
+// running prefix map; backward sweep: ring_q = G_q(y[q]) with the running suffix map.  PMAX is the compile-time bound that keeps
+// c[] and y[] in registers (fully unrolled, `q < parties` predicates): no scratch.  A muted source adds 0, which is what
+// not calling wmix_load_data for it leaves.
+template <int PMAX>
+__global__ __launch_bounds__(256) void load_minus_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
+                                                         const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t head_sample, int parties,
+                                                         long conf_stride, long source_stride, const uint8_t *__restrict__ mute, int rdce,
+                                                         int n_conf) {
+    const size_t total = (size_t)n_out * n_conf;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t i = (uint32_t)(t % n_out);
+        const size_t conf = t / n_out;
+        const LoadEntry e = sch[i];
+        uint32_t pos = head_sample + i;
+        pos -= (pos >= ring_samples) ? ring_samples * (pos / ring_samples) : 0;
+        int16_t *col = rings + conf * (size_t)parties * ring_samples + pos;
+        const int16_t *sc = src + conf * conf_stride;
+        const uint8_t *mc = mute ? mute + conf * (size_t)parties : nullptr;
+        int c[PMAX], y[PMAX];
+        ClampMap f = clamp_map_identity();
+#pragma unroll
+        for (int q = 0; q < PMAX; q++) {
+            c[q] = 0;
+            y[q] = 0;
+            if (q < parties) {
+                if (!mc || !mc[q]) c[q] = load_entry_value(sc + (size_t)q * source_stride, e, rdce);
+                y[q] = clamp_map_apply(f, col[(size_t)q * ring_samples]);
+                f = clamp_map_then_add(f, (int16_t)c[q]);
+            }
+        }
+        ClampMap g = clamp_map_identity();
+#pragma unroll
+        for (int q = PMAX - 1; q >= 0; q--) {
+            if (q < parties) {
+                col[(size_t)q * ring_samples] = clamp_map_apply(g, (int16_t)y[q]);
+                g = clamp_map_add_then((int16_t)c[q], g);
+            }
+        }
+    }
+}
+
 // A growable device buffer owned by its (usually thread_local) object: freed when the owner dies -- a finished task
 // thread of the daemon gives its staging buffers back -- except while the process is exiting (runtime_exiting()).
 struct DevVec {
@@ -147,6 +206,51 @@ struct wmx_mix {
     wmx::SchedCache sched;  // load schedules per source format, never rewritten (see SchedCache)
     std::vector<wmx::LoadEntry> sch;
 };
+
+// What wmx_mix_load and wmx_mix_load_minus share on the host: where the call starts (the reference's cursor rule), the schedule of
+// its source format, and the cursor the call ends with.
+static int load_begin(wmx_mix *m, const char *who, uint32_t srcU8Len, int freq, int channels, int sample, uint32_t &head_off, uint32_t &tk,
+                      wmx::SchedCache::Entry **out) {
+    using namespace wmx;
+    if (head_off == UINT32_MAX || tk < m->tick) {  // src/wmix.c:1666-1673
+        head_off = m->head_off + m->play_correct;
+        tk = m->tick + m->play_correct;
+        if (head_off >= m->ring_bytes) head_off = 0;
+    }
+    const uint64_t k0 = ((uint64_t)srcU8Len << 32) | (uint32_t)freq, k1 = ((uint64_t)(uint8_t)channels << 8) | (uint8_t)sample;
+    SchedCache::Entry *ent = m->sched.find(k0, k1);
+    if (!ent) {
+        if (!load_schedule(m->chn, m->freq, srcU8Len, (uint16_t)freq, (uint8_t)channels, (uint8_t)sample, m->sch)) {
+            set_error("%s: rate ratio needs more than 64 fill samples (the reference overruns repairBuff here)", who);
+            return WMX_EINVAL;
+        }
+        // More than one ring of output would make two threads of the launch read-modify-write the same ring sample (the
+        // reference adds them one after the other); nothing in the daemon loads more than a few packets per call.
+        if (m->sch.size() > m->ring_bytes / 2) {
+            set_error("%s: %zu output samples do not fit the %u-sample ring in one call", who, m->sch.size(), m->ring_bytes / 2);
+            return WMX_EINVAL;
+        }
+        const int rc = m->sched.add(k0, k1, m->sch.data(), m->sch.size() * sizeof(LoadEntry), m->sch.size(), &ent);
+        if (rc) return rc;
+    }
+    *out = ent;
+    return 0;
+}
+
+// cursor bookkeeping, src/wmix.c:1942-1956
+static void load_end(const wmx_mix *m, uint32_t n_out, uint32_t head_off, uint32_t tk, uint32_t *head, uint32_t *tick) {
+    uint32_t tickAdd = n_out * 2, new_head = head_off + tickAdd;
+    new_head %= m->ring_bytes;
+    if (tk < m->tick) {
+        new_head = m->head_off + tickAdd;
+        tickAdd += m->tick;
+        if (new_head >= m->ring_bytes) new_head -= m->ring_bytes;
+    } else {
+        tickAdd += tk;
+    }
+    *tick = tickAdd;
+    *head = new_head;
+}
 
 extern "C" {
 
@@ -318,27 +422,9 @@ int wmx_mix_load(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, 
     }
     if (!d_src || srcU8Len < 1) return 0;  // reference returns the head unchanged (src/wmix.c:1663-1664)
     uint32_t head_off = *head, tk = *tick;
-    if (head_off == UINT32_MAX || tk < m->tick) {  // src/wmix.c:1666-1673
-        head_off = m->head_off + m->play_correct;
-        tk = m->tick + m->play_correct;
-        if (head_off >= m->ring_bytes) head_off = 0;
-    }
-    const uint64_t k0 = ((uint64_t)srcU8Len << 32) | (uint32_t)freq, k1 = ((uint64_t)(uint8_t)channels << 8) | (uint8_t)sample;
-    SchedCache::Entry *ent = m->sched.find(k0, k1);
-    if (!ent) {
-        if (!load_schedule(m->chn, m->freq, srcU8Len, (uint16_t)freq, (uint8_t)channels, (uint8_t)sample, m->sch)) {
-            set_error("wmx_mix_load: rate ratio needs more than 64 fill samples (the reference overruns repairBuff here)");
-            return WMX_EINVAL;
-        }
-        // More than one ring of output would make two threads of the launch read-modify-write the same ring sample (the
-        // reference adds them one after the other); nothing in the daemon loads more than a few packets per call.
-        if (m->sch.size() > m->ring_bytes / 2) {
-            set_error("wmx_mix_load: %zu output samples do not fit the %u-sample ring in one call", m->sch.size(), m->ring_bytes / 2);
-            return WMX_EINVAL;
-        }
-        const int rc = m->sched.add(k0, k1, m->sch.data(), m->sch.size() * sizeof(LoadEntry), m->sch.size(), &ent);
-        if (rc) return rc;
-    }
+    SchedCache::Entry *ent = nullptr;
+    const int rcb = load_begin(m, "wmx_mix_load", srcU8Len, freq, channels, sample, head_off, tk, &ent);
+    if (rcb) return rcb;
     const uint32_t n_out = (uint32_t)ent->n;
     const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
     hipStream_t s = as_stream(stream);
@@ -350,18 +436,43 @@ int wmx_mix_load(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, 
         const int rcu = m->sched.used(ent, s);
         if (rcu) return rcu;
     }
-    // cursor bookkeeping, src/wmix.c:1942-1956
-    uint32_t tickAdd = n_out * 2, new_head = head_off + tickAdd;
-    new_head %= m->ring_bytes;
-    if (tk < m->tick) {
-        new_head = m->head_off + tickAdd;
-        tickAdd += m->tick;
-        if (new_head >= m->ring_bytes) new_head -= m->ring_bytes;
-    } else {
-        tickAdd += tk;
+    load_end(m, n_out, head_off, tk, head, tick);
+    return 0;
+}
+
+// The bridge load (include/wmix_amd.h): the mixer's rings read as n_groups / parties conferences of `parties` consecutive rings.
+// One launch; every source is read once (load_minus_kernel, mix_minus.h).
+int wmx_mix_load_minus(wmx_mix *m, int parties, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, long conf_stride,
+                       long source_stride, const uint8_t *d_mute, int reduce, uint32_t *head, uint32_t *tick, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m || !head || !tick) {
+        set_error("wmx_mix_load_minus: bad argument");
+        return WMX_EINVAL;
     }
-    *tick = tickAdd;
-    *head = new_head;
+    if (parties < 2 || parties > WMX_MIX_MAX_PARTIES || m->n_groups % parties != 0) {
+        set_error("wmx_mix_load_minus: parties=%d must be 2 .. %d and divide the mixer's %d rings", parties, WMX_MIX_MAX_PARTIES, m->n_groups);
+        return WMX_EINVAL;
+    }
+    if (!d_src || srcU8Len < 1) return 0;  // like wmx_mix_load
+    uint32_t head_off = *head, tk = *tick;
+    SchedCache::Entry *ent = nullptr;
+    const int rcb = load_begin(m, "wmx_mix_load_minus", srcU8Len, freq, channels, sample, head_off, tk, &ent);
+    if (rcb) return rcb;
+    const uint32_t n_out = (uint32_t)ent->n;
+    const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
+    hipStream_t s = as_stream(stream);
+    if (n_out) {
+        const int n_conf = m->n_groups / parties;
+        const unsigned grid = stream_grid((size_t)n_out * n_conf, 256);
+        auto kernel = parties <= 4 ? load_minus_kernel<4> : parties <= 8 ? load_minus_kernel<8> : parties <= 16 ? load_minus_kernel<16> : load_minus_kernel<32>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out,
+                           head_off / 2, parties, conf_stride, source_stride, d_mute, rdce, n_conf);
+        WMX_LAUNCH_CHECK();
+        const int rcu = m->sched.used(ent, s);
+        if (rcu) return rcu;
+    }
+    load_end(m, n_out, head_off, tk, head, tick);
     return 0;
 }
 

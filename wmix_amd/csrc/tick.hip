@@ -31,6 +31,10 @@ struct wmx_tick {
     int16_t *d_far;   // [n_groups][pkg] playPkgBuff_get()'s packet of every group
     bool rw_test = false;                    // wmix->rwTest (src/wmix.c:714-732)
     uint32_t rw_head = UINT32_MAX, rw_tick = 0;  // rwTestHead / tick, the heartbeat's static cursor (:531-532)
+    int bridge = 0;                              // wmx_tick_bridge: participants per conference, 0 = off
+    uint32_t br_head = UINT32_MAX, br_tick = 0;  // the bridge's cursor: one for all pairs, they start together and move alike
+    uint8_t *d_mute = nullptr;                   // [n_groups] muted participants; nullptr = nobody
+    std::vector<uint8_t> h_mute;                 // what the upload in flight reads
 };
 
 extern "C" {
@@ -44,6 +48,7 @@ int wmx_tick_destroy(wmx_tick *h) {
     if (h->play_ns) wmx_ns_destroy(h->play_ns);
     if (h->d_play) (void)hipFree(h->d_play);
     if (h->d_far) (void)hipFree(h->d_far);
+    if (h->d_mute) (void)hipFree(h->d_mute);
     delete h;
     return 0;
 }
@@ -113,8 +118,51 @@ int wmx_tick_set_play_correct(wmx_tick *h, uint32_t bytes) { return h ? wmx_mix_
 // cursor is forgotten (rwTestHead = 0, tick = 0, :728-732).
 int wmx_tick_rw_test(wmx_tick *h, int on) {
     if (!h) return WMX_EINVAL;
+    if (on && h->bridge) {
+        wmx::set_error("wmx_tick_rw_test: the bridge is on (the two loads would feed the same rings)");
+        return WMX_EINVAL;
+    }
     h->rw_test = on != 0;
     if (!on) h->rw_head = UINT32_MAX, h->rw_tick = 0;
+    return 0;
+}
+
+// The conference bridge: the tick's groups read as conferences of `parties` call legs.  A tick with rec_per_group == 1 already gives
+// every group its own ring, FIFO row, far-end and control cohort; the bridge adds the one thing a room with one loudspeaker does not
+// have: wmx_tick_record loads every participant's chain output into the rings of the others (wmx_mix_load_minus), where the rwTest
+// load sits in the heartbeat (src/wmix.c:716-726).
+int wmx_tick_bridge(wmx_tick *h, int parties) {
+    if (!h) return WMX_EINVAL;
+    if (parties == 0) {
+        h->bridge = 0;
+        h->br_head = UINT32_MAX, h->br_tick = 0;
+        return 0;
+    }
+    if (parties < 2 || parties > WMX_MIX_MAX_PARTIES || h->n_groups % parties != 0 || h->rec_per_group != 1 || h->rw_test) {
+        wmx::set_error("wmx_tick_bridge: parties=%d needs 2 .. %d, n_groups=%d a multiple of it, rec_per_group=%d == 1 and rwTest off", parties,
+                       WMX_MIX_MAX_PARTIES, h->n_groups, h->rec_per_group);
+        return WMX_EINVAL;
+    }
+    if (h->bridge != parties) h->br_head = UINT32_MAX, h->br_tick = 0;
+    h->bridge = parties;
+    return 0;
+}
+
+int wmx_tick_bridge_mute(wmx_tick *h, const uint8_t *host_mask, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    hipStream_t s = wmx::as_stream(stream);
+    if (!h->d_mute) {
+        if (!host_mask) return 0;
+        WMX_HIP(hipMalloc(&h->d_mute, (size_t)h->n_groups));
+    }
+    // the copy's source is pageable memory of the handle: the previous upload must have left it before it is rewritten
+    WMX_HIP(hipStreamSynchronize(s));
+    if (host_mask)
+        h->h_mute.assign(host_mask, host_mask + h->n_groups);
+    else
+        h->h_mute.assign((size_t)h->n_groups, 0);
+    WMX_HIP(hipMemcpyAsync(h->d_mute, h->h_mute.data(), (size_t)h->n_groups, hipMemcpyHostToDevice, s));
     return 0;
 }
 
@@ -193,6 +241,11 @@ int wmx_tick_record(wmx_tick *h, int16_t *d_rec, long rec_stride, int16_t *d_rec
     if (h->rw_test) {  // :716-726: buffSrc, `ret` bytes, WMIX_FREQ x WMIX_CHN x WMIX_SAMPLE, rwTestHead, reduce 1, &tick
         rc = wmx_mix_load(h->mix, d_rec, (uint32_t)h->pkg * 2, h->freq, h->chn, 16, 1, (long)h->rec_per_group * rec_stride, 0, 1, &h->rw_head,
                           &h->rw_tick, stream);
+        if (rc != 0) return rc;
+    }
+    if (h->bridge) {  // every leg's output into the rings of the other legs of its conference
+        rc = wmx_mix_load_minus(h->mix, h->bridge, d_rec, (uint32_t)h->pkg * 2, h->freq, h->chn, 16, (long)h->bridge * rec_stride, rec_stride,
+                                h->d_mute, 1, &h->br_head, &h->br_tick, stream);
         if (rc != 0) return rc;
     }
     if (d_rec_1x8000) {

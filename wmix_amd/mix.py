@@ -56,6 +56,21 @@ class MixBatch:
                                  reduce, C.byref(h), C.byref(t), torch.cuda.current_stream().cuda_stream), "wmx_mix_load")
         return h.value, t.value
 
+    def load_minus(self, src, parties, src_bytes, freq, channels, mute=None, head=NULL_HEAD, tick=0, reduce=1, sample=16):
+        """The bridge load (wmx_mix_load_minus): the rings are n_groups / parties conferences of `parties` consecutive rings, and ring q
+        of a conference receives every source of that conference except its own, in index order.  src int16 CUDA [n_conf, parties,
+        >= src_bytes/2 + look-ahead]; mute: None or uint8 CUDA [n_groups], non-zero = that source is loaded nowhere.  Returns (head,
+        tick) after the call."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.dim() == 3 and src.stride(2) == 1
+        assert src.shape[1] == parties and src.shape[0] * parties == self.n_groups
+        if mute is not None:
+            assert mute.is_cuda and mute.dtype == torch.uint8 and mute.is_contiguous() and mute.numel() == self.n_groups
+        h, t = C.c_uint32(head), C.c_uint32(tick)
+        check(lib().wmx_mix_load_minus(self._h, parties, src.data_ptr(), src_bytes, freq, channels, sample, src.stride(0), src.stride(1),
+                                       mute.data_ptr() if mute is not None else None, reduce, C.byref(h), C.byref(t),
+                                       torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus")
+        return h.value, t.value
+
     def drain(self, n_bytes):
         out = torch.empty(self.n_groups, n_bytes // 2, dtype=torch.int16, device="cuda")
         check(lib().wmx_mix_drain(self._h, out.data_ptr(), n_bytes, out.stride(0), torch.cuda.current_stream().cuda_stream), "wmx_mix_drain")

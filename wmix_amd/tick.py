@@ -64,6 +64,21 @@ class TickBatch:
         """wmix->rwTest: the heartbeat loads what it recorded back into the play ring (src/wmix.c:714-732)."""
         check(lib().wmx_tick_rw_test(self._h, 1 if on else 0), "wmx_tick_rw_test")
 
+    def bridge(self, parties):
+        """The conference bridge (wmx_tick_bridge): the groups are n_groups / parties conferences of call legs, and record() loads every
+        leg's output into the rings of the other legs of its conference.  Needs rec_per_group == 1 and rwTest off; 0 switches it off."""
+        check(lib().wmx_tick_bridge(self._h, int(parties)), "wmx_tick_bridge")
+
+    def bridge_mute(self, mask=None):
+        """mask: n_groups values, non-zero = that participant is loaded nowhere (and still hears the others); None = nobody."""
+        import numpy as np
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            assert m.size == self.n_groups
+        check(lib().wmx_tick_bridge_mute(self._h, m.ctypes.data if m is not None else None, torch.cuda.current_stream().cuda_stream),
+              "wmx_tick_bridge_mute")
+
     def play(self, play=None):
         """The play side of one package; returns the groups' far-end packages (a VIEW of the handle's own [n_groups, pkg] rows:
         valid until the next play)."""
