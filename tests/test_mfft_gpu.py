@@ -111,21 +111,16 @@ def test_reference_host_signatures(wmx, oracle_port, n):
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     for kind, name in enumerate(("FFT", "FFTR", "IFFT", "IFFTR")):
         fn = getattr(wmx, name)
-        fn.restype = None
         o_r, o_i, o_a, o_p = f4(), f4(), f4(), f4()
         if kind < 2:
-            fn.argtypes = [C.c_void_p] * 6 + [C.c_uint]
             fn(p(re), p(im), p(o_r), p(o_i), p(o_a), None, n)
         else:
-            fn.argtypes = [C.c_void_p] * 4 + [C.c_uint]
             fn(p(re), p(im), p(o_r), p(o_i), n)
         want = loader.mfft(oracle_port, kind, re, im, n, prefix="orc")
         assert same_bits(o_r, want["r"]) and same_bits(o_i, want["i"])
         if kind < 2:
             assert same_bits(o_a, want["a"])
     # fft_stream
-    wmx.fft_stream.restype = None
-    wmx.fft_stream.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
     st_len = n if n >= 128 else 512
     pool, af = np.zeros(st_len, np.float32), np.zeros(st_len, np.float32)
     chunks = mfft_input(64 * 5, 5)[0].reshape(5, 64)

@@ -12,6 +12,7 @@ from conftest import GOLDEN
 sys.path.insert(0, GOLDEN)
 from make_mix_golden import LOAD_CASES, ZOOM_CASES, load_input, zoom_input  # noqa: E402
 from test_mix_oracle import _bind, orc_load, orc_zoom  # noqa: E402
+from wmix_amd._lib import WMix_Point as Point, WMix_Struct_Head as Head  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(GOLDEN, "mix_golden.npz"))
@@ -71,22 +72,8 @@ def test_other_ring_formats_vs_oracle(cuda, oracle_port, ring_chn, ring_freq):
         assert np.array_equal(rings[0], want) and (t, h) == tuple(meta[-1])
 
 
-class Point(C.Union):
-    _fields_ = [("U8", C.c_void_p)]
-
-
-class Head(C.Structure):  # WMix_Struct_Head (include/wmix_compat.h)
-    _fields_ = [("objAo", C.c_void_p), ("objAi", C.c_void_p), ("buff", C.c_void_p), ("start", Point), ("end", Point), ("head", Point),
-                ("tail", Point), ("run", C.c_bool), ("loopWord", C.c_uint8), ("loopWordRecord", C.c_uint8), ("loopWordFifo", C.c_uint8),
-                ("loopWordRtp", C.c_uint8), ("tick", C.c_uint32), ("thread_sys", C.c_uint32), ("thread_record", C.c_uint32),
-                ("thread_play", C.c_uint32), ("playRun", C.c_bool), ("recordRun", C.c_bool), ("shmemRun", C.c_int), ("msg_key", C.c_int),
-                ("msg_fd", C.c_int), ("reduceMode", C.c_uint8)]
-
-
 def legacy_load(wmx, freq, chn, rmode, rarg, nsrc, sbytes, start, src):
     """nsrc calls of the legacy wmix_load_data (NULL head each) into a fresh 1 x 8000 host ring -> (ring, [(tick, head)])"""
-    wmx.wmix_load_data.restype = Point
-    wmx.wmix_load_data.argtypes = [C.POINTER(Head), Point, C.c_uint32, C.c_uint16, C.c_uint8, C.c_uint8, Point, C.c_uint8, C.POINTER(C.c_uint32)]
     ring = np.zeros(16000 // 2 + 8, np.int16)
     w = Head()
     w.start.U8 = ring.ctypes.data
@@ -144,8 +131,6 @@ def test_play_correct_of_the_other_platform_builds(cuda, oracle_port, platform):
 
 def test_legacy_wmix_load_data_signature(wmx):
     """WMix_Point wmix_load_data(WMix_Struct*, ...) over a host ring (src/wmix.h:40-49), default 1 x 8000 ring."""
-    wmx.wmix_load_data.restype = Point
-    wmx.wmix_load_data.argtypes = [C.POINTER(Head), Point, C.c_uint32, C.c_uint16, C.c_uint8, C.c_uint8, Point, C.c_uint8, C.POINTER(C.c_uint32)]
     i = 2
     freq, chn, rmode, rarg, nsrc, sbytes, start = LOAD_CASES[i]
     src = load_input(i, nsrc, sbytes)
@@ -188,29 +173,12 @@ def test_full_size_mix_properties(cuda):
     mb.close()
 
 
-def _legacy_types(wmx):
-    class Point(C.Union):
-        _fields_ = [("U8", C.c_void_p)]
-
-    class Head(C.Structure):  # WMix_Struct_Head (include/wmix_compat.h)
-        _fields_ = [("objAo", C.c_void_p), ("objAi", C.c_void_p), ("buff", C.c_void_p), ("start", Point), ("end", Point), ("head", Point),
-                    ("tail", Point), ("run", C.c_bool), ("loopWord", C.c_uint8), ("loopWordRecord", C.c_uint8), ("loopWordFifo", C.c_uint8),
-                    ("loopWordRtp", C.c_uint8), ("tick", C.c_uint32), ("thread_sys", C.c_uint32), ("thread_record", C.c_uint32),
-                    ("thread_play", C.c_uint32), ("playRun", C.c_bool), ("recordRun", C.c_bool), ("shmemRun", C.c_int), ("msg_key", C.c_int),
-                    ("msg_fd", C.c_int), ("reduceMode", C.c_uint8)]
-
-    wmx.wmix_load_data.restype = Point
-    wmx.wmix_load_data.argtypes = [C.POINTER(Head), Point, C.c_uint32, C.c_uint16, C.c_uint8, C.c_uint8, Point, C.c_uint8, C.POINTER(C.c_uint32)]
-    return Point, Head
-
-
 def test_legacy_load_data_touches_only_its_span(wmx, oracle_port):
     """The reference writes ring bytes [head, head + n_out*2) and nothing else while other threads work on the ring
     (src/wmix.c:1347-1352, 1678-1702).  A second thread keeps rewriting ring samples OUTSIDE the span during many legacy
     calls (ctypes releases the GIL for the call): none of its writes may be lost or resurrected, and the span itself
     must equal the oracle's ring, including across the wrap.  Also: the copy branch must not read behind the source."""
     import threading
-    Point, Head = _legacy_types(wmx)
     _bind(oracle_port)
     ring = np.zeros(8000 + 8, np.int16)
     w = Head()

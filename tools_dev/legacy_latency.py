@@ -79,6 +79,7 @@ def packet_edge_latency(n_calls=600, warm=100):
     """The task threads' per-packet legacy calls on host pointers: PCM2G711a / G711a2PCM of one RTP payload (160 samples,
     src/wmixTask.c:1139, 1282), wmix_pcm_zoom of one 20 ms package (src/wmix.c:730).  Microseconds per call (mean, p99)."""
     from wmix_amd import _lib
+    from wmix_amd._lib import WMix_Point as Point, WMix_Struct_Head as Head
     W = _lib.lib()
     rng = np.random.default_rng(3)
     pcm = rng.integers(-20000, 20000, 160, dtype=np.int16)
@@ -86,18 +87,9 @@ def packet_edge_latency(n_calls=600, warm=100):
     back = np.zeros(160, np.int16)
     big = rng.integers(-20000, 20000, 1280, dtype=np.int16)  # 20 ms of 2 x 16000
     small = np.zeros(1280, np.int16)
-    for f in (W.PCM2G711a, W.G711a2PCM):
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        f.restype = C.c_int
-    W.wmix_pcm_zoom.argtypes = [C.c_uint8, C.c_uint16, C.c_void_p, C.c_uint32, C.c_uint8, C.c_uint16, C.c_void_p]
-    W.wmix_pcm_zoom.restype = C.c_uint32
     calls = {"PCM2G711a_160": lambda: W.PCM2G711a(pcm.ctypes.data, codes.ctypes.data, 320, 0),
              "G711a2PCM_160": lambda: W.G711a2PCM(codes.ctypes.data, back.ctypes.data, 160, 0),
              "wmix_pcm_zoom_2x16000_to_1x8000_20ms": lambda: W.wmix_pcm_zoom(2, 16000, big.ctypes.data, 2560, 1, 8000, small.ctypes.data)}
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_mix_gpu import Head, Point  # the WMix_Struct head as ctypes (tests/test_mix_gpu.py)
-    W.wmix_load_data.restype = Point
-    W.wmix_load_data.argtypes = [C.POINTER(Head), Point, C.c_uint32, C.c_uint16, C.c_uint8, C.c_uint8, Point, C.c_uint8, C.POINTER(C.c_uint32)]
     ring = np.zeros(8008, np.int16)
     w = Head()
     w.start.U8, w.end.U8, w.head.U8 = ring.ctypes.data, ring.ctypes.data + 16000, ring.ctypes.data
@@ -112,8 +104,6 @@ def packet_edge_latency(n_calls=600, warm=100):
     calls["wmix_load_data_2x16000_20ms"] = load
     x = rng.standard_normal(1024).astype(np.float32)
     o = [np.zeros(1024, np.float32) for _ in range(4)]
-    W.FFTR.argtypes = [C.c_void_p] * 6 + [C.c_uint]
-    W.FFTR.restype = None
     calls["FFTR_1024"] = lambda: W.FFTR(x.ctypes.data, None, o[0].ctypes.data, o[1].ctypes.data, o[2].ctypes.data, o[3].ctypes.data, 1024)
     out = {}
     for name, fn in calls.items():
