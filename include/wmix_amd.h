@@ -203,7 +203,8 @@ int wmx_agc_import_stream(wmx_agc *h, int stream_index, const void *host_blob);
  * d_far + p*far_packet_stride); near/out packet p of stream s at s*stream_stride + p*packet_stride;
  * d_out may alias d_near.  delay_ms is the reported sound-card delay (the daemon passes 0).
  * Returns 0, a WMX_E* error, or -1 where the reference wrapper would return non-zero (delay outside
- * [0,500]: the offending packet is left unwritten and nothing after it runs).
+ * [0,500]: the offending packet HAS been processed with the delay clamped, as WebRtcAec_Process does,
+ * so the state has moved on; its output is left unwritten and nothing after it runs).
  * Float path: same operation order as the reference and the same powf (glibc's algorithm, restated
  * in csrc/libm_dev.h); tests require bit-exactness. */
 typedef struct wmx_aec wmx_aec;

@@ -15,6 +15,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF_DIR = os.path.join(HERE, "_ref")
 PORT_SO = os.path.join(HERE, "build", "liboracle.so")
+COV_DIR = os.path.join(HERE, "build", "cov")
 REF_SO = os.path.join(REF_DIR, "libwmixref.so")
 REF_MIX = os.path.join(REF_DIR, "ref_mix_driver")
 
@@ -65,16 +66,38 @@ def _fn(lib, name, restype, argtypes):
 
 def port():
     """Our C restatement (built on demand: plain gcc, a few seconds).  WMIX_ORACLE_SAN=1: the AddressSanitizer +
-    UndefinedBehaviorSanitizer build of the same sources (oracle/Makefile `san`; needs the ASan runtime preloaded)."""
+    UndefinedBehaviorSanitizer build of the same sources (oracle/Makefile `san`; needs the ASan runtime preloaded).
+    WMIX_ORACLE_COV=1: the build with gcc's branch counters (oracle/Makefile `cov`); the counters land in oracle/build/cov/ when the
+    process ends or at cov_dump() (tools_dev/oracle_branches.py reads them)."""
     global _port
     if _port is None:
-        if os.environ.get("WMIX_ORACLE_SAN") == "1":
+        if os.environ.get("WMIX_ORACLE_COV") == "1":
+            subprocess.check_call(["make", "-s", "-C", HERE, "cov"])
+            # libgcov writes to the path the object was compiled at; strip all of it and put this tree's directory in front
+            os.environ.setdefault("GCOV_PREFIX", COV_DIR)
+            os.environ.setdefault("GCOV_PREFIX_STRIP", "64")
+            _port = C.CDLL(os.path.join(COV_DIR, "liboracle_cov.so"))
+        elif os.environ.get("WMIX_ORACLE_SAN") == "1":
             subprocess.check_call(["make", "-s", "-C", HERE, "san"])
             _port = C.CDLL(os.path.join(HERE, "build", "liboracle_san.so"))
         else:
             build_port()
             _port = C.CDLL(PORT_SO)
     return _port
+
+
+def cov_reset():
+    """Coverage build only: zero the branch counters (per-input attribution: cov_reset(), run the input, cov_dump())."""
+    port().orc_cov_reset()
+
+
+def cov_dump():
+    """Coverage build only: write the counters collected since the last reset to COV_DIR/*.gcda."""
+    d = os.environ.get("GCOV_PREFIX", COV_DIR)
+    for f in os.listdir(d):
+        if f.endswith(".gcda"):  # libgcov MERGES into a file it finds: start from nothing
+            os.unlink(os.path.join(d, f))
+    port().orc_cov_dump()
 
 
 def ref():
@@ -233,6 +256,49 @@ def run_aec_delays(lib, chn, freq, interval_ms, far, near, frames_per_call, dela
     rc = fn(chn, freq, interval_ms, far, near, out, frames_per_call, n_calls, d)
     assert rc == 0, rc
     return out
+
+
+def run_canceller_calls(lib, stage, chn, freq, interval_ms, far, near, frames_per_call, delays, prefix="ref"):
+    """ONE canceller handle (stage "aec": the float one, "aecm": the build with the reference's AECM switch) driven call by call with
+    aec_process2 and the reported delay of each call, and kept alive over calls that fail: a delay outside [0, 500] ms makes the
+    wrapper return -1 with that call's output unwritten (src/webrtc.c:382-387, 410-483) while the handle's state has moved on.  The
+    whole-run drivers stop at the first such call; the daemon does not.  Output starts as a copy of the near end (an unwritten call
+    keeps its input, as in place).  Returns (out, return code per call).  prefix "ref": the real wrapper functions of
+    oracle/_ref/libwmixref.so (aec_* / aecm_aec_*); "orc": the restatement's handle API."""
+    far = np.ascontiguousarray(far, dtype=np.int16)
+    near = np.ascontiguousarray(near, dtype=np.int16)
+    out = near.copy()
+    per = frames_per_call * chn
+    n_calls = near.size // per
+    d = np.asarray(delays, dtype=np.int64)
+    assert d.shape == (n_calls,) and stage in ("aec", "aecm")
+    vp = C.c_void_p
+    if prefix == "orc":
+        h = _fn(lib, "orc_%s_init" % stage, vp, [C.c_int, C.c_int, C.c_int])(chn, freq, interval_ms)
+        rel = _fn(lib, "orc_%s_release" % stage, None, [vp])
+        if stage == "aec":
+            p2 = _fn(lib, "orc_aec_process2", C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int])
+            call = lambda f, x, o, dl: p2(h, f, x, o, frames_per_call, dl)  # noqa: E731
+        else:
+            r3 = _fn(lib, "orc_aecm_run", C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int])
+            call = lambda f, x, o, dl: r3(h, 3, f, x, o, frames_per_call, dl)  # noqa: E731
+    else:
+        pre = "aec_" if stage == "aec" else "aecm_aec_"
+        h = _fn(lib, pre + "init", vp, [C.c_int, C.c_int, C.c_int, vp])(chn, freq, interval_ms, None)
+        rel = _fn(lib, pre + "release", None, [vp])
+        p2 = _fn(lib, pre + "process2", C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int])
+        call = lambda f, x, o, dl: p2(h, f, x, o, frames_per_call, dl)  # noqa: E731
+    assert h, "%s init returned NULL" % stage
+    rcs = np.zeros(n_calls, np.int32)
+    tmp = np.zeros(per, np.int16)
+    try:
+        for c in range(n_calls):
+            rcs[c] = call(far[c * per:].ctypes.data, near[c * per:].ctypes.data, tmp.ctypes.data, int(d[c]))
+            if rcs[c] == 0:
+                out[c * per:(c + 1) * per] = tmp
+    finally:
+        rel(h)
+    return out, rcs
 
 
 def run_aecm(lib, chn, freq, interval_ms, far, near, frames_per_call, delay_ms=0, split=0, prefix="ref", expect_rc=0):

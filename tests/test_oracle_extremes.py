@@ -69,3 +69,23 @@ def test_port_equals_reference_on_perfect_echoes_and_tones(oracle_port, oracle_r
         x = x.astype(np.int16)
         assert np.array_equal(L.run_ns(oracle_port, 1, freq, x, pkt, prefix="orc"), L.run_ns(oracle_ref, 1, freq, x, pkt, prefix="ref"))
         assert np.array_equal(L.run_nsx(oracle_port, 1, freq, x, pkt, prefix="orc"), L.run_nsx(oracle_ref, 1, freq, x, pkt, prefix="ref"))
+
+
+def _catalogue():
+    import branch_inputs as B
+    return B.CATALOGUE
+
+
+@pytest.mark.parametrize("entry", _catalogue(), ids=lambda e: e.name)
+def test_port_equals_reference_on_the_branch_catalogue(oracle_port, oracle_ref, entry):
+    """tests/branch_inputs.py: the inputs aimed at the branches no other signal takes.  A rarely taken branch restated wrongly in the
+    oracle would otherwise only move the error from the kernel to its checker.  Bit for bit in every stage, the float ones included
+    (port and reference run on the same host, with the same libm), and the same return code from every call.  NSX and AECM entries go
+    through the reference's nsx_ns_* / aecm_aec_* builds."""
+    import branch_inputs as B
+    data = B.make(entry)
+    a, rc_a = B.run(oracle_port, entry, "orc", data=data)
+    b, rc_b = B.run(oracle_ref, entry, "ref", data=data)
+    assert (rc_a is None and rc_b is None) or np.array_equal(rc_a, rc_b), entry.name
+    d = np.flatnonzero(a != b)
+    assert d.size == 0, "%s: %d samples differ, first at %d" % (entry.name, d.size, d[0])

@@ -1302,9 +1302,10 @@ __global__ __attribute__((amdgpu_waves_per_eu(WMX_AEC_WAVES, WMX_AEC_WAVES))) __
         const size_t off = (size_t)sidx * stream_stride + (size_t)p * packet_stride;
         const int16_t *in = near_pcm + off;
         int16_t *out = out_pcm + off;
+        const bool keep = pl.has_near != kAecNearDiscard;  // a rejected call moves the state and writes nothing (plan_reject_near)
         if (pl.passthrough) {
             // start-up phase: AEC disabled, out = near (echo_cancellation.c:651-657); left channel to all channels
-            for (int i = lane; i < pkg; i += 64) {
+            for (int i = lane; keep && i < pkg; i += 64) {
                 const int16_t v = in[i * chn];
                 for (int c = 0; c < chn; c++) out[i * chn + c] = v;
             }
@@ -1323,7 +1324,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(WMX_AEC_WAVES, WMX_AEC_WAVES))) __
             wave_sync();
             for (int k = 0; k < sp.n_blocks; k++)
                 aec_block<MULT>(K, consts_g + kAecConstNearWords, powtab, W, taps, F, pl.blk[sp.first_blk + k], noise_tab, lane);
-            for (int i = opaque_lane(lane); i < kAecFrame; i += 64) {
+            for (int i = opaque_lane(lane); keep && i < kAecFrame; i += 64) {
                 const int16_t v = (int16_t)AEC_ST(AS_OUT_RING + ring_at(sp.out_rd, i));
                 for (int c = 0; c < chn; c++) out[(s * kAecFrame + i) * chn + c] = v;
             }

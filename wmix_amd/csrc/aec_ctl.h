@@ -83,10 +83,11 @@ struct AecPartPlan {
     int pre_rd;    // far_pre ring position of the partition's 128 samples
     int far_slot;  // far ring slot written
 };
+constexpr int kAecNearDiscard = 2;
 struct AecPlan {
     int has_far;       // BufferFarend part present: write `far_n` samples at pre_wr, then n_part partitions
     int far_n, pre_wr, n_part;
-    int has_near;      // Process part present
+    int has_near;      // Process part present (kAecNearDiscard: present, but the reference rejected the call -- see plan_reject_near)
     int passthrough;   // start-up phase: out = near
     int n_sub, n_blk;
     AecSubPlan sub[2];
@@ -379,9 +380,14 @@ inline void co_pair(const AecCtl &a, const AecCtl &b, int ia, int ib, AecPairChe
     pc->pad = 0;
 }
 
-// the planning loop (cohort_reg.h): a plan is cleared up to its blocks (the kernels read only the n_blk the planning writes); a near packet the
-// reference rejects writes nothing (src/webrtc.c:463-468: the wrapper stops there)
+// the planning loop (cohort_reg.h): a plan is cleared up to its blocks (the kernels read only the n_blk the planning writes).  A near packet
+// the reference rejects for its reported delay (outside [0, 500] ms) has been PROCESSED by WebRtcAec_Process with the delay clamped
+// -- start-up counters, delay estimate, blocks and all (echo_cancellation.c:341-409) -- before the wrapper drops its output
+// (src/webrtc.c:463-468): the plan stays, both kernels run it, only the copy to the caller's buffer is left out.  (A packet refused
+// for its length has planned nothing: has_near is still 0.)
 inline void plan_clear(AecPlan *pl) { memset(pl, 0, offsetof(AecPlan, blk)); }
-inline void plan_reject_near(AecPlan *pl) { pl->has_near = 0; }
+inline void plan_reject_near(AecPlan *pl) {
+    if (pl->has_near) pl->has_near = kAecNearDiscard;
+}
 
 }  // namespace wmx
