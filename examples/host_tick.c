@@ -13,6 +13,7 @@
  * directories of the reference ship.
  *
  *   host_tick src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform alsa|hi3516|t31] [--rwtest] [--bridge P]
+ *             [--bridge-sizes a,b,c,...]
  *
  * src.i16    int16 [n_ticks][n_groups][n_src][20 ms of (src_freq, src_chn)]   what the task threads play
  * local.i16  int16 [n_ticks][n_groups * n_rec][160]                          the rooms without their loudspeakers
@@ -21,6 +22,8 @@
  * --rwtest:   wmix->rwTest (src/wmix.c:714-732)
  * --bridge P: the groups are n_groups / P conferences of P call legs (n_rec must be 1): every leg's heartbeat output is loaded into the
  *             rings of the other legs of its conference, so each leg is played everybody except itself (wmx_tick_bridge)
+ * --bridge-sizes a,b,c,...: conferences of different sizes: the first a groups are conference 0, the next b conference 1, and so on;
+ *             the groups that remain are idle legs, in no conference (wmx_tick_bridge_conferences; n_rec must be 1)
  * Prints one JSON line.  tests/test_host_chain_gpu.py compares out.i16 with one oracle daemon per group.
  *
  * Build (what __graft_entry__.build() runs):
@@ -75,11 +78,12 @@ static double now_ms(void) {
 
 int main(int argc, char **argv) {
     if (argc < 10) {
-        fprintf(stderr, "usage: %s src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform name] [--rwtest] [--bridge P]\n", argv[0]);
+        fprintf(stderr, "usage: %s src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform name] [--rwtest] [--bridge P] [--bridge-sizes a,b,..]\n", argv[0]);
         return 2;
     }
     const int G = atoi(argv[4]), n_src = atoi(argv[5]), R = atoi(argv[6]), T = atoi(argv[7]), sfreq = atoi(argv[8]), schn = atoi(argv[9]);
     int aec_ms = 400, rwtest = 0, bridge = 0;
+    const char *bridge_sizes = NULL;
     long correct = -1; /* -1: the library's default = platform/alsa */
     const char *platform = "alsa";
     for (int i = 10; i < argc; i++) {
@@ -87,6 +91,8 @@ int main(int argc, char **argv) {
             rwtest = 1;
         } else if (!strcmp(argv[i], "--bridge") && i + 1 < argc) {
             bridge = atoi(argv[++i]);
+        } else if (!strcmp(argv[i], "--bridge-sizes") && i + 1 < argc) {
+            bridge_sizes = argv[++i];
         } else if (!strcmp(argv[i], "--platform") && i + 1 < argc) {
             platform = argv[++i];
             if (!strcmp(platform, "alsa")) {
@@ -121,6 +127,25 @@ int main(int argc, char **argv) {
     if (correct >= 0) WMX_OK(wmx_tick_set_play_correct(h, (uint32_t)correct));
     if (rwtest) WMX_OK(wmx_tick_rw_test(h, 1));
     if (bridge) WMX_OK(wmx_tick_bridge(h, bridge));
+    int n_conf = 0;
+    int32_t *conf_off = NULL, *conf_members = NULL;
+    if (bridge_sizes) { /* the list goes to the library as it stands: what is wrong with it is the library's to say */
+        conf_off = calloc(strlen(bridge_sizes) + 2, sizeof(int32_t));
+        if (!conf_off) return 2;
+        for (const char *p = bridge_sizes; *p;) {
+            char *end = NULL;
+            long v = strtol(p, &end, 10);
+            if (end == p || (*end && *end != ',') || v < 0 || v > 1000000) v = -1, end = (char *)p + strcspn(p, ","); /* not a size */
+            conf_off[n_conf + 1] = conf_off[n_conf] + (int32_t)v;
+            n_conf++;
+            p = *end ? end + 1 : end;
+        }
+        const int32_t total = conf_off[n_conf] > 0 ? conf_off[n_conf] : 0;
+        conf_members = calloc((size_t)total + 1, sizeof(int32_t));
+        if (!conf_members) return 2;
+        for (int32_t r = 0; r < total; r++) conf_members[r] = r; /* consecutive groups; one past n_groups - 1 is refused */
+        WMX_OK(wmx_tick_bridge_conferences(h, n_conf, conf_off, conf_members, NULL));
+    }
     if (wmx_tick_package_samples(h) != PKG) return 5;
     int16_t *d_src = NULL, *d_play = NULL, *d_rec = NULL, *d_zoom = NULL;
     HIP_OK(hipMalloc((void **)&d_src, (size_t)G * n_src * srow * 2));
@@ -164,6 +189,11 @@ int main(int argc, char **argv) {
     printf("{\"groups\": %d, \"sources\": %d, \"record_streams\": %d, \"ticks\": %d, \"platform\": \"%s\", \"aec_delay_ms\": %d, \"rw_test\": %d, ", G,
            n_src, R, T, platform, aec_ms, rwtest);
     if (bridge) printf("\"bridge_parties\": %d, ", bridge);
+    if (bridge_sizes) {
+        printf("\"bridge_sizes\": [");
+        for (int c = 0; c < n_conf; c++) printf("%s%d", c ? ", " : "", (int)(conf_off[c + 1] - conf_off[c]));
+        printf("], ");
+    }
     printf("\"wall_ms\": %.3f, \"ms_per_tick\": %.4f, \"rc\": %d}\n", wall, wall / T, rc);
     return rc;
 }

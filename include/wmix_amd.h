@@ -438,6 +438,30 @@ int wmx_mix_load(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, 
 int wmx_mix_load_minus(wmx_mix *m, int parties, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
                        long conf_stride, long source_stride, const uint8_t *d_mute, int reduce, uint32_t *head, uint32_t *tick,
                        void *stream);
+/* The bridge load for conferences of different sizes whose legs join and leave.  A layout is n_conf conferences; conference c is the
+ * ordered list host_members[host_off[c] .. host_off[c+1]) of ring indices (host_off[0] == 0, n_conf + 1 entries).  The indices of a
+ * conference need not be consecutive or ascending: list order is the order of the saturating adds.  A ring is in at most one
+ * conference; a ring in none is an idle leg (nothing is loaded into it, its source is not read).  A conference of 0 or 1 members is a
+ * placeholder that keeps its index and loads nothing.  The layout is copied into buffers the handle owns, on `stream`; n_conf == 0
+ * clears it.  wmx_mix_conferences: the n_conf in force.
+ * wmx_mix_load_minus_conf: for every conference c of >= 2 members and every member q, the ring of q afterwards holds what the
+ * reference's ring holds after wmix_load_data(source of member s) for every member s != q that is not muted, in list order, every
+ * call from conference c's cursor (head[c], tick[c]) -- wmx_mix_load's cursor rule, formats, reduce rule, look-ahead note and return
+ * values.  They all end at the same cursor, which is written back to head[c], tick[c]; a conference of fewer than 2 members gets
+ * head[c] = UINT32_MAX, tick[c] = 0 (its cursor is forgotten).  So a leg that joins a running conference is loaded from the
+ * conference's cursor, a conference that forms starts from a fresh one -- which may be the START of the ring (src/wmix.c:1666-1673),
+ * so conferences alive together can write at different ring positions for good -- and a leg that leaves plays out what was loaded
+ * ahead of its play head.  Source of ring r at d_src + r*source_stride (int16 elements); d_mute: NULL or n_groups bytes ON THE DEVICE,
+ * by ring index; head / tick: HOST arrays of n_conf entries, in and out.  At most one launch per size class (<= 4, <= 8, <= 16,
+ * <= 32 members) that has a conference; a call that finds every conference where the previous one left it relative to the others
+ * uploads nothing (wmix_amd/csrc/bridge_layout.h).
+ * WMX_EINVAL, nothing launched, rings, layout and cursors unchanged: a conference of more than WMX_MIX_MAX_PARTIES members, a ring
+ * index outside [0, n_groups), a ring listed twice (in one conference or in two), host_off that does not ascend from 0,
+ * wmx_mix_load_minus_conf without a layout, and whatever wmx_mix_load refuses. */
+int wmx_mix_set_conferences(wmx_mix *m, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream);
+int wmx_mix_conferences(const wmx_mix *m);
+int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
+                            long source_stride, const uint8_t *d_mute, int reduce, uint32_t *head, uint32_t *tick, void *stream);
 int wmx_mix_drain(wmx_mix *m, int16_t *d_out, uint32_t bytes, long out_stride, void *stream);
 int wmx_mix_export(const wmx_mix *m, int group, int16_t *host_ring, uint32_t *head_off, uint32_t *tick);
 
@@ -649,6 +673,15 @@ int wmx_tick_bridge(wmx_tick *h, int parties);
 /* host_mask: n_groups bytes, non-zero = that participant is muted (loaded nowhere, still hears the others); NULL = nobody.  Copied
  * into a buffer the handle owns, on `stream`. */
 int wmx_tick_bridge_mute(wmx_tick *h, const uint8_t *host_mask, void *stream);
+/* The bridge with conferences of different sizes whose legs join and leave: the layout of wmx_mix_set_conferences over the tick's
+ * groups (needs rec_per_group == 1).  Called between ticks, it replaces the layout; while one is in force wmx_tick_record calls
+ * wmx_mix_load_minus_conf where wmx_tick_bridge calls wmx_mix_load_minus.  Conference identity is the index c and the handle keeps
+ * (head[c], tick[c]) across the change: a conference that had 2 or more members and still has keeps its cursor, any other starts from
+ * a fresh one when it next loads.  A leg's ring, FIFO row and chain state are never touched; fresh NS / AEC / AGC / VAD handles for a
+ * new call in a slot are wmx_chain_reset_streams' business (wmx_tick_chain).  n_conf == 0 switches it off and forgets every cursor.
+ * wmx_tick_bridge_mute works unchanged (the mask is by ring).  It excludes wmx_tick_rw_test(h, 1) and wmx_tick_bridge(h, parties > 0),
+ * and each of them excludes it: WMX_EINVAL. */
+int wmx_tick_bridge_conferences(wmx_tick *h, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream);
 /* the daemon of another platform directory: PLAT_AEC_INTERVALMS (alsa 400, hi3516 700, t31 0; plat.h:14/19) is wmx_tick_create's
  * aec_delay_ms -- the FIFO gets AEC_FIFO_PKG_NUM = aec_delay_ms / interval_ms + 2 slots (src/wmixConf.h:141) -- and PLAT_PLAY_CORRECT is
  * set here (wmx_mix_set_play_correct on the tick's rings; default platform/alsa's) */

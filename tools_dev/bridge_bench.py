@@ -8,7 +8,17 @@
 
 Bytes of the new call, from shapes: every ring column reads P sources, reads P ring samples and writes P ring samples, 2 B each.
 
-    python tools_dev/bridge_bench.py [--sizes 4096x8x8000,65536x8x16000] [--reps 200] [--tick 4096x8] [--out file.json]"""
+    python tools_dev/bridge_bench.py [--sizes 4096x8x8000,65536x8x16000] [--reps 200] [--tick 4096x8] [--out file.json]
+
+--ragged measures the bridge over a layout (wmx_mix_load_minus_conf) instead, for the leg counts of --sizes:
+a. the same legs both ways: equal consecutive conferences of P = 4 and P = 32 through the layout against wmx_mix_load_minus (the untouched
+   uniform kernel of the same build) on the same rings; compared on sampled rings before any time is reported.
+b. a telephony mix of 4 096 conferences (70 % of 2 legs, 20 % of 3, 8 % of 4 - 8, 2 % of 9 - 32) through the layout against what a caller
+   without it has to do: every conference padded to 32 with muted legs through wmx_mix_load_minus.  The load time per tick and the rings
+   (= FIFO rows = chain streams) the layout saves.
+Device events around every repetition; they include the host's work between the launches (the cursor rule over every conference).
+
+    python tools_dev/bridge_bench.py --ragged --out profiles/bridge/bridge_ragged_bench.json"""
 import argparse
 import json
 import os
@@ -119,15 +129,110 @@ def bridge_tick(n_conf, P, reps):
 
 NULL = 0xFFFFFFFF
 
+
+def same_legs_both_ways(n_legs, P, freq, reps):
+    per = freq // 1000 * 20
+    n_conf = n_legs // P
+    n = n_conf * P
+    mb = MixBatch(n, 1, freq)
+    g = torch.Generator(device="cuda").manual_seed(6)
+    src = torch.randint(-20000, 20000, (n, per), dtype=torch.int16, device="cuda", generator=g)
+    mb.set_conferences([list(range(c * P, c * P + P)) for c in range(n_conf)])
+    mb.set(0, 0, 1)
+    mb.set_play_correct(0)
+    # ---- the same rings?  Both from silence, at two cursors that do not overlap
+    ha, _ = mb.load_minus(src.view(n_conf, P, per), P, per * 2, freq, 1, head=0, tick=0)
+    hb, tb = mb.load_minus_conf(src, per * 2, freq, 1, head=np.full(n_conf, 4 * per * 2, np.uint32), tick=np.full(n_conf, 4 * per * 2, np.uint32))
+    assert ha == per * 2 and (hb == 5 * per * 2).all()
+    sample = sorted({0, 1, n_conf // 2, n_conf - 1})
+    for c in sample:
+        for q in range(P):
+            ring = mb.export(c * P + q)[0]
+            assert ring[:per].any() and np.array_equal(ring[:per], ring[4 * per:5 * per]), ("rings differ", c, q)
+    cur = {"old": (NULL, 0), "new": (hb, tb)}
+
+    def new():
+        cur["new"] = mb.load_minus_conf(src, per * 2, freq, 1, head=cur["new"][0], tick=cur["new"][1])
+
+    def old():
+        cur["old"] = mb.load_minus(src.view(n_conf, P, per), P, per * 2, freq, 1, head=cur["old"][0], tick=cur["old"][1])
+
+    t_new, t_old = alternate([new, old], reps)
+    mb.close()
+    a, b = stats(t_new), stats(t_old)
+    moved = n_conf * per * P * 6
+    return {"legs": n, "conferences": n_conf, "parties": P, "ring": "1x%d" % freq, "rings_checked": len(sample) * P, "load_minus_conf": a,
+            "load_minus": b, "ratio_conf_over_uniform": round(a["median_ms"] / b["median_ms"], 3),
+            "load_minus_conf_TBs": round(moved / (a["median_ms"] * 1e-3) / 1e12, 3), "load_minus_TBs": round(moved / (b["median_ms"] * 1e-3) / 1e12, 3)}
+
+
+def telephony_sizes(n_conf=4096):
+    """70 % of 2 legs, 20 % of 3, 8 % of 4 - 8, 2 % of 9 - 32, in a shuffled order"""
+    n3, n48, n932 = round(0.20 * n_conf), round(0.08 * n_conf), round(0.02 * n_conf)
+    sizes = [2] * (n_conf - n3 - n48 - n932) + [3] * n3 + [4 + k % 5 for k in range(n48)] + [9 + k % 24 for k in range(n932)]
+    np.random.default_rng(8).shuffle(sizes)
+    return [int(v) for v in sizes]
+
+
+def telephony_against_padding(reps, freq=8000):
+    per = freq // 1000 * 20
+    sizes = telephony_sizes()
+    n_conf, legs, padded = len(sizes), sum(sizes), len(sizes) * 32
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    ragged, pad = MixBatch(legs, 1, freq), MixBatch(padded, 1, freq)
+    ragged.set_conferences([list(range(off[c], off[c + 1])) for c in range(n_conf)])
+    g = torch.Generator(device="cuda").manual_seed(7)
+    src = torch.randint(-20000, 20000, (legs, per), dtype=torch.int16, device="cuda", generator=g)
+    # the padded form: conference c owns rings 32 c .. 32 c + 31, the legs in front, the rest muted filler
+    slot = np.concatenate([32 * c + np.arange(sizes[c]) for c in range(n_conf)])
+    src_pad = torch.zeros((padded, per), dtype=torch.int16, device="cuda")
+    src_pad[torch.from_numpy(slot).to("cuda")] = src
+    mute = np.ones(padded, np.uint8)
+    mute[slot] = 0
+    mute = torch.from_numpy(mute).to("cuda")
+    for m in (ragged, pad):
+        m.set(0, 0, 1)
+        m.set_play_correct(0)
+    cur = {"new": ragged.load_minus_conf(src, per * 2, freq, 1), "old": pad.load_minus(src_pad.view(n_conf, 32, per), 32, per * 2, freq, 1, mute=mute)}
+    for c in sorted({0, 1, n_conf // 2, n_conf - 1}):  # the same rings?
+        for q in range(sizes[c]):
+            a, b = ragged.export(int(off[c]) + q)[0], pad.export(32 * c + q)[0]
+            assert a.any() and np.array_equal(a, b), ("rings differ", c, q)
+
+    def new():
+        cur["new"] = ragged.load_minus_conf(src, per * 2, freq, 1, head=cur["new"][0], tick=cur["new"][1])
+
+    def old():
+        cur["old"] = pad.load_minus(src_pad.view(n_conf, 32, per), 32, per * 2, freq, 1, mute=mute, head=cur["old"][0], tick=cur["old"][1])
+
+    t_new, t_old = alternate([new, old], reps)
+    ragged.close()
+    pad.close()
+    a, b = stats(t_new), stats(t_old)
+    hist = {str(k): sizes.count(k) for k in sorted(set(sizes))}
+    return {"conferences": n_conf, "sizes": hist, "ring": "1x%d" % freq, "legs": legs, "padded_legs": padded, "layout_load": a, "padded_to_32_load": b,
+            "ratio_padded_over_layout": round(b["median_ms"] / a["median_ms"], 2),
+            "rings_fifo_rows_and_chain_streams_saved": padded - legs, "ring_bytes_saved": (padded - legs) * 2 * freq}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="4096x8x8000,65536x8x16000", help="conferences x parties x ring rate, comma separated")
     ap.add_argument("--tick", default="4096x8", help="conferences x parties of the tick measurement; empty = skip")
     ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--ragged", action="store_true", help="the bridge over a layout: same legs both ways, a telephony mix against padding")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
     res = {"tool": "bridge_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps, "load": [], "tick": None}
+    if args.ragged:
+        res = {"tool": "bridge_bench --ragged", "device": torch.cuda.get_device_name(0), "reps": args.reps, "same_legs": [], "telephony": None}
+        for s in [x for x in args.sizes.split(",") if x]:
+            n_conf, P, freq = (int(v) for v in s.split("x"))
+            for parties in (4, 32):
+                res["same_legs"].append(same_legs_both_ways(n_conf * P, parties, freq, args.reps))
+        res["telephony"] = telephony_against_padding(args.reps)
+        args.sizes = args.tick = ""
     for s in [x for x in args.sizes.split(",") if x]:
         n_conf, P, freq = (int(v) for v in s.split("x"))
         res["load"].append(load_minus_vs_gather(n_conf, P, freq, args.reps))

@@ -19,6 +19,7 @@
 #include "../../include/wmix_compat.h"
 #include "mix_sched.h"
 #include "mix_minus.h"
+#include "bridge_layout.h"
 
 namespace wmx {
 namespace {
@@ -147,6 +148,53 @@ __global__ __launch_bounds__(256) void load_minus_kernel(int16_t *__restrict__ r
     }
 }
 
+// The bridge load over a layout (bridge_layout.h): load_minus_kernel's two sweeps with the ring and source addresses taken from the
+// member list.  One thread = one ring-sample column of one conference of this size class (`tab`: {offset into members, size} per slot;
+// `lead`: the slot's start column relative to base_sample).  A slot's columns are dealt out in whole waves (n_pad = n_out rounded up to
+// the wave, the lanes past n_out idle), so the slot is wave-uniform: the table entry, the member indices and the mute bytes are scalar
+// loads and the ring / source bases scalar arithmetic.  The members of a conference are distinct rings and a ring is in one conference
+// only (bridge_layout_build), so no two threads touch the same ring sample.
+template <int PMAX>
+__global__ __launch_bounds__(256) void load_minus_conf_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
+                                                              const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t n_pad,
+                                                              uint32_t base_sample, const int32_t *__restrict__ tab,
+                                                              const uint32_t *__restrict__ lead, const int32_t *__restrict__ members,
+                                                              long source_stride, const uint8_t *__restrict__ mute, int rdce, int n_slots) {
+    const size_t total = (size_t)n_pad * n_slots;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t i = (uint32_t)(t % n_pad);
+        // n_pad, the block and the grid's stride are multiples of the wave: every lane of a wave computes the same slot
+        const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t / n_pad));
+        if (i >= n_out) continue;
+        const LoadEntry e = sch[i];
+        uint32_t pos = base_sample + lead[slot] + i;  // each of the three < ring_samples
+        pos -= (pos >= ring_samples) ? ring_samples * (pos / ring_samples) : 0;
+        const int32_t *mem = members + tab[2 * (size_t)slot];
+        const int n = tab[2 * (size_t)slot + 1];
+        int c[PMAX], y[PMAX];
+        ClampMap f = clamp_map_identity();
+#pragma unroll
+        for (int q = 0; q < PMAX; q++) {
+            c[q] = 0;
+            y[q] = 0;
+            if (q < n) {
+                const size_t r = (size_t)mem[q];
+                if (!mute || !mute[r]) c[q] = load_entry_value(src + r * source_stride, e, rdce);
+                y[q] = clamp_map_apply(f, rings[r * ring_samples + pos]);
+                f = clamp_map_then_add(f, (int16_t)c[q]);
+            }
+        }
+        ClampMap g = clamp_map_identity();
+#pragma unroll
+        for (int q = PMAX - 1; q >= 0; q--) {
+            if (q < n) {
+                rings[(size_t)mem[q] * ring_samples + pos] = clamp_map_apply(g, (int16_t)y[q]);
+                g = clamp_map_add_then((int16_t)c[q], g);
+            }
+        }
+    }
+}
+
 // A growable device buffer owned by its (usually thread_local) object: freed when the owner dies -- a finished task
 // thread of the daemon gives its staging buffers back -- except while the process is exiting (runtime_exiting()).
 struct DevVec {
@@ -205,6 +253,14 @@ struct wmx_mix {
     uint8_t *h_rings = nullptr;  // set when the rings are pinned host memory mapped into the device (the legacy adapter's one ring)
     wmx::SchedCache sched;  // load schedules per source format, never rewritten (see SchedCache)
     std::vector<wmx::LoadEntry> sch;
+    // wmx_mix_set_conferences: the layout, what the device holds of it (the member list, {offset, size} per slot, the leads), and
+    // the host copies an upload in flight reads
+    wmx::BridgeLayout conf;
+    wmx::BridgeLeads conf_leads;
+    std::vector<uint32_t> conf_next, h_conf_lead;
+    int32_t *d_conf_members = nullptr, *d_conf_tab = nullptr;
+    uint32_t *d_conf_lead = nullptr;
+    size_t conf_cap_members = 0, conf_cap_slots = 0;
 };
 
 // What wmx_mix_load and wmx_mix_load_minus share on the host: where the call starts (the reference's cursor rule), the schedule of
@@ -345,6 +401,9 @@ int wmx_mix_destroy(wmx_mix *m) {
         (void)hipHostFree(m->h_rings);
     else if (m->d_rings)
         (void)hipFree(m->d_rings);
+    if (m->d_conf_members) (void)hipFree(m->d_conf_members);
+    if (m->d_conf_tab) (void)hipFree(m->d_conf_tab);
+    if (m->d_conf_lead) (void)hipFree(m->d_conf_lead);
     delete m;
     return 0;
 }
@@ -474,6 +533,89 @@ int wmx_mix_load_minus(wmx_mix *m, int parties, const int16_t *d_src, uint32_t s
     }
     load_end(m, n_out, head_off, tk, head, tick);
     return 0;
+}
+
+// The layout of the bridge load below (include/wmix_amd.h, bridge_layout.h).  Validated and sorted into the size classes on the host;
+// the member list and the {offset, size} table go to buffers the handle owns.  A refusal leaves the layout in force as it is.
+int wmx_mix_set_conferences(wmx_mix *m, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    BridgeLayout l;
+    if (const char *why = bridge_layout_build(l, m->n_groups, n_conf, host_off, host_members)) {
+        set_error("wmx_mix_set_conferences: %s (n_conf=%d, %d rings, at most %d members each)", why, n_conf, m->n_groups, WMX_MIX_MAX_PARTIES);
+        return WMX_EINVAL;
+    }
+    hipStream_t s = as_stream(stream);
+    // the uploads' sources are pageable memory of the handle, and a launch in flight may still read the buffers that grow here
+    WMX_HIP(hipStreamSynchronize(s));
+    if (l.members.size() > m->conf_cap_members) {
+        if (m->d_conf_members) (void)hipFree(m->d_conf_members);
+        m->d_conf_members = nullptr, m->conf_cap_members = 0;
+        WMX_HIP(hipMalloc(&m->d_conf_members, l.members.size() * sizeof(int32_t)));
+        m->conf_cap_members = l.members.size();
+    }
+    if ((size_t)l.slots() > m->conf_cap_slots) {
+        if (m->d_conf_tab) (void)hipFree(m->d_conf_tab);
+        if (m->d_conf_lead) (void)hipFree(m->d_conf_lead);
+        m->d_conf_tab = nullptr, m->d_conf_lead = nullptr, m->conf_cap_slots = 0;
+        WMX_HIP(hipMalloc(&m->d_conf_tab, (size_t)l.slots() * 2 * sizeof(int32_t)));
+        WMX_HIP(hipMalloc(&m->d_conf_lead, (size_t)l.slots() * sizeof(uint32_t)));
+        m->conf_cap_slots = (size_t)l.slots();
+    }
+    m->conf = std::move(l);
+    m->conf_leads.valid = false;  // the slots are other conferences now
+    if (!m->conf.members.empty())
+        WMX_HIP(hipMemcpyAsync(m->d_conf_members, m->conf.members.data(), m->conf.members.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (!m->conf.tab.empty())
+        WMX_HIP(hipMemcpyAsync(m->d_conf_tab, m->conf.tab.data(), m->conf.tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+int wmx_mix_conferences(const wmx_mix *m) { return m ? m->conf.n_conf : WMX_EINVAL; }
+
+// The bridge load over the layout: at most one launch per non-empty size class.  The cursor rule runs on the host once per distinct
+// start value (bridge_plan_load); a call after which every lead is what the device already holds uploads nothing.
+int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, long source_stride,
+                            const uint8_t *d_mute, int reduce, uint32_t *head, uint32_t *tick, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m || !head || !tick) {
+        set_error("wmx_mix_load_minus_conf: bad argument");
+        return WMX_EINVAL;
+    }
+    if (m->conf.n_conf < 1) {
+        set_error("wmx_mix_load_minus_conf: no layout (wmx_mix_set_conferences)");
+        return WMX_EINVAL;
+    }
+    if (!d_src || srcU8Len < 1) return 0;  // like wmx_mix_load
+    // the schedule of the source format, and wmx_mix_load's refusals; a cursor that the rule leaves alone keeps load_begin to that
+    uint32_t h0 = 0, t0 = m->tick;
+    SchedCache::Entry *ent = nullptr;
+    const int rcb = load_begin(m, "wmx_mix_load_minus_conf", srcU8Len, freq, channels, sample, h0, t0, &ent);
+    if (rcb) return rcb;
+    const uint32_t n_out = (uint32_t)ent->n;
+    const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
+    hipStream_t s = as_stream(stream);
+    const BridgeMixState ms{m->head_off, m->tick, m->play_correct, m->ring_bytes};
+    const BridgePlan plan = bridge_plan_load(m->conf, ms, n_out, head, tick, m->conf_leads, m->conf_next);
+    if (plan.upload) {
+        WMX_HIP(hipStreamSynchronize(s));  // the previous upload must have left h_conf_lead before it is rewritten
+        m->h_conf_lead = m->conf_leads.lead;
+        WMX_HIP(hipMemcpyAsync(m->d_conf_lead, m->h_conf_lead.data(), m->h_conf_lead.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    }
+    for (int k = 0; k < kBridgeClasses && n_out; k++) {
+        const int first = m->conf.class_begin[k], n_slots = m->conf.class_begin[k + 1] - first;
+        if (!n_slots) continue;
+        const uint32_t n_pad = (n_out + 63) / 64 * 64;  // whole waves per conference: the slot is wave-uniform
+        const unsigned grid = stream_grid((size_t)n_pad * n_slots, 256);
+        auto kernel = k == 0 ? load_minus_conf_kernel<4> : k == 1 ? load_minus_conf_kernel<8> : k == 2 ? load_minus_conf_kernel<16> : load_minus_conf_kernel<32>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out,
+                           n_pad, plan.base_sample, (const int32_t *)m->d_conf_tab + 2 * (size_t)first, (const uint32_t *)m->d_conf_lead + first,
+                           (const int32_t *)m->d_conf_members, source_stride, d_mute, rdce, n_slots);
+        WMX_LAUNCH_CHECK();
+    }
+    return n_out && m->conf.slots() ? m->sched.used(ent, s) : 0;
 }
 
 // the play thread's drain (src/wmix.c:1347-1366): read `bytes` at the ring head into d_out (per group), zero what

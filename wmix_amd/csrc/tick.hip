@@ -18,6 +18,7 @@
 // folds (round-4 VERDICT "next" 3).  The record streams of group g are the rows g * R .. g * R + R - 1.
 #include <vector>
 #include "wmx_internal.h"
+#include "bridge_layout.h"
 
 struct wmx_tick {
     int device;  // first member of every handle (wmx_handle_device)
@@ -33,6 +34,9 @@ struct wmx_tick {
     uint32_t rw_head = UINT32_MAX, rw_tick = 0;  // rwTestHead / tick, the heartbeat's static cursor (:531-532)
     int bridge = 0;                              // wmx_tick_bridge: participants per conference, 0 = off
     uint32_t br_head = UINT32_MAX, br_tick = 0;  // the bridge's cursor: one for all pairs, they start together and move alike
+    bool conf_on = false;                        // wmx_tick_bridge_conferences: a layout is in force
+    std::vector<int32_t> conf_sizes;             // its conferences' sizes, for the carrying-over of the cursors
+    std::vector<uint32_t> conf_head, conf_tick;  // one cursor per conference index
     uint8_t *d_mute = nullptr;                   // [n_groups] muted participants; nullptr = nobody
     std::vector<uint8_t> h_mute;                 // what the upload in flight reads
 };
@@ -118,7 +122,7 @@ int wmx_tick_set_play_correct(wmx_tick *h, uint32_t bytes) { return h ? wmx_mix_
 // cursor is forgotten (rwTestHead = 0, tick = 0, :728-732).
 int wmx_tick_rw_test(wmx_tick *h, int on) {
     if (!h) return WMX_EINVAL;
-    if (on && h->bridge) {
+    if (on && (h->bridge || h->conf_on)) {
         wmx::set_error("wmx_tick_rw_test: the bridge is on (the two loads would feed the same rings)");
         return WMX_EINVAL;
     }
@@ -143,8 +147,39 @@ int wmx_tick_bridge(wmx_tick *h, int parties) {
                        WMX_MIX_MAX_PARTIES, h->n_groups, h->rec_per_group);
         return WMX_EINVAL;
     }
+    if (h->conf_on) {
+        wmx::set_error("wmx_tick_bridge: a layout of wmx_tick_bridge_conferences is in force (the two loads would feed the same rings)");
+        return WMX_EINVAL;
+    }
     if (h->bridge != parties) h->br_head = UINT32_MAX, h->br_tick = 0;
     h->bridge = parties;
+    return 0;
+}
+
+// The bridge over a layout (include/wmix_amd.h, bridge_layout.h): conferences of different sizes whose legs join and leave between
+// ticks.  The mixer validates and keeps the layout; the tick keeps one cursor per conference index and carries it over.
+int wmx_tick_bridge_conferences(wmx_tick *h, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (n_conf == 0) {
+        const int rc = wmx_mix_set_conferences(h->mix, 0, nullptr, nullptr, stream);
+        if (rc) return rc;
+        h->conf_on = false;
+        h->conf_sizes.clear(), h->conf_head.clear(), h->conf_tick.clear();
+        return 0;
+    }
+    if (h->rec_per_group != 1 || h->rw_test || h->bridge) {
+        wmx::set_error("wmx_tick_bridge_conferences: needs rec_per_group=%d == 1, rwTest off and wmx_tick_bridge off", h->rec_per_group);
+        return WMX_EINVAL;
+    }
+    wmx::BridgeLayout now;  // the sizes of the new layout; the mixer's own check is the one that refuses
+    const int rc = wmx_mix_set_conferences(h->mix, n_conf, host_off, host_members, stream);
+    if (rc) return rc;
+    (void)wmx::bridge_layout_build(now, h->n_groups, n_conf, host_off, host_members);
+    wmx::bridge_cursors_carry(h->conf_sizes, now, h->conf_head, h->conf_tick);
+    h->conf_sizes.resize((size_t)n_conf);
+    for (int c = 0; c < n_conf; c++) h->conf_sizes[(size_t)c] = now.size(c);
+    h->conf_on = true;
     return 0;
 }
 
@@ -246,6 +281,11 @@ int wmx_tick_record(wmx_tick *h, int16_t *d_rec, long rec_stride, int16_t *d_rec
     if (h->bridge) {  // every leg's output into the rings of the other legs of its conference
         rc = wmx_mix_load_minus(h->mix, h->bridge, d_rec, (uint32_t)h->pkg * 2, h->freq, h->chn, 16, (long)h->bridge * rec_stride, rec_stride,
                                 h->d_mute, 1, &h->br_head, &h->br_tick, stream);
+        if (rc != 0) return rc;
+    }
+    if (h->conf_on) {  // the same over the layout, every conference from its own cursor
+        rc = wmx_mix_load_minus_conf(h->mix, d_rec, (uint32_t)h->pkg * 2, h->freq, h->chn, 16, rec_stride, h->d_mute, 1, h->conf_head.data(),
+                                     h->conf_tick.data(), stream);
         if (rc != 0) return rc;
     }
     if (d_rec_1x8000) {

@@ -71,6 +71,36 @@ class MixBatch:
                                        torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus")
         return h.value, t.value
 
+    def set_conferences(self, conferences):
+        """The layout of load_minus_conf (wmx_mix_set_conferences): a list of conferences, each the ordered list of its members' ring
+        indices -- not necessarily consecutive or ascending; a ring in at most one; 0 or 1 members = a placeholder that keeps its index;
+        at most 32 members.  An empty list clears the layout."""
+        off = np.zeros(len(conferences) + 1, np.int32)
+        off[1:] = np.cumsum([len(c) for c in conferences])
+        members = np.ascontiguousarray([r for c in conferences for r in c], dtype=np.int32)
+        check(lib().wmx_mix_set_conferences(self._h, len(conferences), off.ctypes.data, members.ctypes.data if members.size else None,
+                                            torch.cuda.current_stream().cuda_stream), "wmx_mix_set_conferences")
+
+    def conferences(self):
+        return lib().wmx_mix_conferences(self._h)
+
+    def load_minus_conf(self, src, src_bytes, freq, channels, mute=None, head=None, tick=None, reduce=1, sample=16):
+        """The bridge load over the layout (wmx_mix_load_minus_conf): the ring of every member of a conference receives the sources of
+        the conference's other members, in list order, from the conference's own cursor.  src int16 CUDA [n_groups, >= src_bytes/2 +
+        look-ahead], row r = the source of ring r; mute: None or uint8 CUDA [n_groups] by ring; head / tick: one per conference (None =
+        no cursor yet).  Returns (heads, ticks) after the call as uint32 arrays."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.dim() == 2 and src.stride(1) == 1 and src.shape[0] == self.n_groups
+        if mute is not None:
+            assert mute.is_cuda and mute.dtype == torch.uint8 and mute.is_contiguous() and mute.numel() == self.n_groups
+        n = max(self.conferences(), 0)
+        h = np.full(n, NULL_HEAD, np.uint32) if head is None else np.array(head, dtype=np.uint32)
+        t = np.zeros(n, np.uint32) if tick is None else np.array(tick, dtype=np.uint32)
+        assert h.size == n and t.size == n
+        check(lib().wmx_mix_load_minus_conf(self._h, src.data_ptr(), src_bytes, freq, channels, sample, src.stride(0),
+                                            mute.data_ptr() if mute is not None else None, reduce, h.ctypes.data, t.ctypes.data,
+                                            torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus_conf")
+        return h, t
+
     def drain(self, n_bytes):
         out = torch.empty(self.n_groups, n_bytes // 2, dtype=torch.int16, device="cuda")
         check(lib().wmx_mix_drain(self._h, out.data_ptr(), n_bytes, out.stride(0), torch.cuda.current_stream().cuda_stream), "wmx_mix_drain")

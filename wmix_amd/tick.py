@@ -69,6 +69,18 @@ class TickBatch:
         leg's output into the rings of the other legs of its conference.  Needs rec_per_group == 1 and rwTest off; 0 switches it off."""
         check(lib().wmx_tick_bridge(self._h, int(parties)), "wmx_tick_bridge")
 
+    def bridge_conferences(self, conferences):
+        """The bridge over a layout (wmx_tick_bridge_conferences): a list of conferences, each the ordered list of its legs' group
+        indices (MixBatch.set_conferences).  Called between ticks it replaces the layout; a conference (its index is its identity) that
+        had two or more legs and still has keeps its cursor, so a leg that joins is loaded from there and the others hear no gap; one
+        that forms starts from a fresh cursor; a leg that leaves plays out what it was loaded.  An empty list switches it off."""
+        import numpy as np
+        off = np.zeros(len(conferences) + 1, np.int32)
+        off[1:] = np.cumsum([len(c) for c in conferences])
+        members = np.ascontiguousarray([r for c in conferences for r in c], dtype=np.int32)
+        check(lib().wmx_tick_bridge_conferences(self._h, len(conferences), off.ctypes.data, members.ctypes.data if members.size else None,
+                                                torch.cuda.current_stream().cuda_stream), "wmx_tick_bridge_conferences")
+
     def bridge_mute(self, mask=None):
         """mask: n_groups values, non-zero = that participant is loaded nowhere (and still hears the others); None = nobody."""
         import numpy as np
