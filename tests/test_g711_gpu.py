@@ -59,7 +59,15 @@ def g711_law(law):
 
 @pytest.mark.parametrize("law", ["a", "u"])
 def test_reference_host_signatures(wmx, oracle_port, law):
-    """PCM2G711x / G711x2PCM / g711x_encode / g711x_decode over HOST buffers (src/g711codec.h:24-34)."""
+    """PCM2G711x / G711x2PCM / g711x_encode / g711x_decode over HOST buffers (src/g711codec.h:24-34); PCM2G711x / G711x2PCM also at
+    the last size the adapter stages in mapped memory (16 384 samples) and the first it copies (16 385)."""
+    for n in (16384, 16385):
+        x = np.random.default_rng(n).integers(-32768, 32768, size=n, dtype=np.int16)
+        enc, dec = np.zeros(n + 8, np.uint8), np.zeros(n + 8, np.int16)
+        assert getattr(wmx, "PCM2G711" + law)(C.c_void_p(x.ctypes.data), C.c_void_p(enc.ctypes.data), 2 * n, 0) == n
+        assert np.array_equal(enc[:n], orc_encode(oracle_port, law, x)[0]) and not enc[n:].any()
+        assert getattr(wmx, "G711%s2PCM" % law)(C.c_void_p(enc.ctypes.data), C.c_void_p(dec.ctypes.data), n, 0) == 2 * n
+        assert np.array_equal(dec[:n], orc_decode(oracle_port, law, enc[:n])[0]) and not dec[n:].any()
     pcm = G["wav_excerpt"]
     out = np.zeros(pcm.size, np.uint8)
     r = getattr(wmx, "PCM2G711" + law)(C.c_void_p(pcm.ctypes.data), C.c_void_p(out.ctypes.data), pcm.size * 2, 0)

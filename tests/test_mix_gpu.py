@@ -11,6 +11,7 @@ from conftest import GOLDEN
 
 sys.path.insert(0, GOLDEN)
 from make_mix_golden import LOAD_CASES, ZOOM_CASES, load_input, zoom_input  # noqa: E402
+from test_g711_oracle import orc_encode  # noqa: E402
 from test_mix_oracle import _bind, orc_load, orc_zoom  # noqa: E402
 from wmix_amd._lib import WMix_Point as Point, WMix_Struct_Head as Head  # noqa: E402
 
@@ -72,6 +73,20 @@ def test_other_ring_formats_vs_oracle(cuda, oracle_port, ring_chn, ring_freq):
         assert np.array_equal(rings[0], want) and (t, h) == tuple(meta[-1])
 
 
+@pytest.mark.parametrize("ic,ifr,oc,ofr,in_bytes", [(1, 8000, 2, 16000, 13106), (1, 8000, 2, 16000, 13108), (2, 32000, 1, 8000, 58252),
+                                                    (2, 32000, 1, 8000, 58256)])
+def test_legacy_zoom_either_side_of_the_mapped_threshold(wmx, oracle_port, ic, ifr, oc, ofr, in_bytes):
+    """The legacy wmix_pcm_zoom stages up to 64 KB of input plus output in mapped memory and copies above that: the last size of the one
+    and the first of the other, per direction, against the restatement; nothing is written behind the returned length."""
+    _bind(oracle_port)
+    x = np.random.default_rng(in_bytes).integers(-30000, 30000, in_bytes // 2, dtype=np.int16)
+    want = orc_zoom(oracle_port, ic, ifr, x, oc, ofr)
+    assert (in_bytes + want.size * 2 <= 65536) == (in_bytes in (13106, 58252))
+    out = np.full(want.size + 64, 0x5A5A, np.int16)
+    n = wmx.wmix_pcm_zoom(ic, ifr, x.ctypes.data_as(C.c_void_p), in_bytes, oc, ofr, out.ctypes.data_as(C.c_void_p))
+    assert n == want.size * 2 and np.array_equal(out[:want.size], want) and (out[want.size:] == 0x5A5A).all()
+
+
 def legacy_load(wmx, freq, chn, rmode, rarg, nsrc, sbytes, start, src):
     """nsrc calls of the legacy wmix_load_data (NULL head each) into a fresh 1 x 8000 host ring -> (ring, [(tick, head)])"""
     ring = np.zeros(16000 // 2 + 8, np.int16)
@@ -127,6 +142,17 @@ def test_play_correct_of_the_other_platform_builds(cuda, oracle_port, platform):
                          capture_output=True, text=True, timeout=300)  # not inside the ring: every call refuses, the ring stays empty
     assert bad.returncode == 0 and "WMIX_AMD_PLAY_CORRECT=16001" in bad.stderr and not np.load(out).any()
     os.remove(out)
+
+
+@pytest.mark.parametrize("start,nsrc", [(0, 1), (12000, 2)])
+@pytest.mark.parametrize("sbytes", [65536, 65540])
+def test_legacy_load_data_either_side_of_the_mapped_threshold(wmx, oracle_port, sbytes, start, nsrc):
+    """The legacy wmix_load_data stages a source of up to 64 KB in mapped memory and copies a larger one: 2 x 32000 sources of 65 536 and
+    65 540 bytes into the 1 x 8000 ring against the restatement, from the ring's start and -- two sources from 12 000 -- across its wrap."""
+    src = np.random.default_rng(sbytes + start).integers(-20000, 20000, size=nsrc * sbytes // 2 + 8, dtype=np.int16)
+    want, meta = orc_load(oracle_port, 1, 8000, 32000, 2, 1, 1, nsrc, sbytes, start, src)
+    ring, got = legacy_load(wmx, 32000, 2, 1, 1, nsrc, sbytes, start, src)
+    assert np.array_equal(ring, want) and got == [(int(t), int(h)) for t, h in meta]
 
 
 def test_legacy_wmix_load_data_signature(wmx):
@@ -279,18 +305,23 @@ def test_variable_chunk_sizes_walk_through_the_schedule_cache(cuda, wmx, oracle_
             assert need.value == want.size * 2 and np.array_equal(got, want), (rep, k)
 
 
-def test_legacy_adapters_on_short_lived_task_threads(wmx):
+def test_legacy_adapters_on_short_lived_task_threads(wmx, oracle_port):
     """The daemon starts a thread per play / record task (src/wmixTask.c) and those threads call wmix_pcm_zoom /
-    wmix_load_data; their staging buffers and device ring are thread-local and must go back when the thread ends
-    (round-2 ADVICE: they were leaked).  200 threads, each converting once: free device memory afterwards is what it was."""
+    wmix_load_data / the G.711 calls; their staging buffers and device ring are thread-local and must go back when the thread ends
+    (round-2 ADVICE: they were leaked).  200 threads, each converting once -- one package through the zoom, and a G.711 encode and a
+    load large enough to be staged in device memory: free device memory afterwards is what it was."""
     import threading
     import torch
     x = (np.arange(640) * 37 % 2000 - 1000).astype(np.int16)
+    big = (np.arange(65540 // 2) * 37 % 2000 - 1000).astype(np.int16)
 
     def task(res, i):
         out = np.zeros(640, np.int16)
         n = wmx.wmix_pcm_zoom(2, 32000, x.ctypes.data_as(C.c_void_p), 1280, 1, 8000, out.ctypes.data_as(C.c_void_p))
-        res[i] = (n, out[:80].copy())
+        codes = np.zeros(16385, np.uint8)
+        enc = wmx.g711a_encode(C.c_void_p(codes.ctypes.data), C.c_void_p(big.ctypes.data), 16385)
+        ring, meta = legacy_load(wmx, 32000, 2, 1, 1, 1, 65540, 0, big)
+        res[i] = (n, out[:80].copy(), enc, codes, meta, ring)
 
     res = {}
     t = threading.Thread(target=task, args=(res, -1))
@@ -305,4 +336,9 @@ def test_legacy_adapters_on_short_lived_task_threads(wmx):
     torch.cuda.synchronize()
     free1 = torch.cuda.mem_get_info()[0]
     assert all(res[i][0] == 160 and np.array_equal(res[i][1], res[-1][1]) for i in range(200))
+    want_ring, want_meta = orc_load(oracle_port, 1, 8000, 32000, 2, 1, 1, 1, 65540, 0, big)
+    assert res[-1][2] == 16385 and np.array_equal(res[-1][3], orc_encode(oracle_port, "a", big[:16385])[0])
+    assert res[-1][4] == [(int(t), int(h)) for t, h in want_meta] and np.array_equal(res[-1][5], want_ring)
+    assert all(res[i][2] == 16385 and np.array_equal(res[i][3], res[-1][3]) and res[i][4] == res[-1][4] and np.array_equal(res[i][5], res[-1][5])
+               for i in range(200))
     assert free0 - free1 < 8 << 20, "device memory shrank by %d bytes over 200 task threads" % (free0 - free1)

@@ -1,6 +1,6 @@
 // compat_webrtc.hip -- the reference's per-handle wrapper API (src/webrtc.h:32-61) exported
 // unchanged over HOST buffers, as thin adapters over a batch of ONE stream: each call stages
-// the caller's int16 buffer in mapped pinned memory, launches the batched kernel on the HANDLE'S OWN
+// the caller's int16 buffer (legacy_stage.h), launches the batched kernel on the HANDLE'S OWN
 // non-blocking stream and waits for that stream alone (never the NULL stream: wmx_internal.h).
 // This is what lets the wmix daemon link against libwmix_amd.so instead of src/webrtc.c + the
 // five libwebrtc*.so; throughput comes from the wmx_* batch API, not from here.
@@ -9,88 +9,63 @@
 // caller's `bool *debug` and print only when it is set; in == out aliasing is fine; frameNum is
 // in frames (chn samples each) and must be a multiple of the packet size.
 #include <cstdlib>
-#include <cstring>
 #include <mutex>
-#include "wmx_internal.h"
+#include "legacy_stage.h"
 #include "../../include/wmix_compat.h"
 
 namespace {
 
-// The handle's staging buffer: PINNED HOST memory mapped into the device's address space.  A legacy call moves a few hundred bytes;
-// two runtime copies around the launch cost more than the work (round 5: ~ 45 us per call, of which the kernel ~ 8).  The kernels
-// read the packet straight out of this buffer and write the result back into it over PCIe -- two plain memcpy calls on the host,
-// one launch, one synchronisation.
-struct DevBuf {
-    int16_t *p = nullptr;  // the device's view (what the wmx_* entry points get)
-    int16_t *host = nullptr;
-    size_t cap = 0;  // int16 elements
-    bool ensure(size_t n) {
-        if (n <= cap) return true;
-        if (host) (void)hipHostFree(host);
-        host = p = nullptr;
-        cap = 0;
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, n * sizeof(int16_t), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            if (hp) (void)hipHostFree(hp);
-            return false;
-        }
-        host = static_cast<int16_t *>(hp);
-        p = static_cast<int16_t *>(dp);
-        cap = n;
-        return true;
-    }
-    bool in(const int16_t *src, size_t n_elems) {
-        memcpy(host, src, n_elems * sizeof(int16_t));
-        return true;
-    }
-    // the launches of this call (on the handle's stream) have finished and their writes are in host memory
-    bool out(int16_t *dst, size_t n_elems, hipStream_t s) {
-        if (hipStreamSynchronize(s) != hipSuccess) return false;
-        memcpy(dst, host, n_elems * sizeof(int16_t));
-        return true;
-    }
-    ~DevBuf() {
-        if (host && !wmx::runtime_exiting()) (void)hipHostFree(host);
-    }
+// What the four handle kinds share.  The staging is mapped at every size (legacy_stage.h: a legacy call moves a few hundred bytes);
+// device memory and copies only when the pinned allocation fails.
+struct HandleCompat {
+    hipStream_t s = nullptr;  // this handle's launch stream (wmx_internal.h: legacy_stream_create)
+    int chn, freq, pkg;
+    bool *debug;
+    wmx::Stage stage;  // region 0: the buffer processed in place (near, for the AEC); region 1: the AEC's far end
 };
 
-struct NsHandleCompat {
-    hipStream_t s = nullptr;  // this handle's launch stream (wmx_internal.h: legacy_stream_create)
+struct NsHandleCompat : HandleCompat {
     wmx_ns *batch;    // float NS (the reference's default build) ...
     wmx_nsx *batchx;  // ... or the fixed-point NSX (its MAKE_WEBRTC_NSX build): exactly one is set
-    int chn, freq, pkg;
-    bool *debug;
-    DevBuf buf;
 };
 
-struct VadHandleCompat {
-    hipStream_t s = nullptr;  // this handle's launch stream (wmx_internal.h: legacy_stream_create)
+struct VadHandleCompat : HandleCompat {
     wmx_vad *batch;
-    int chn, freq, pkg;
-    bool *debug;
-    DevBuf buf;
 };
 
-struct AgcHandleCompat {
-    hipStream_t s = nullptr;  // this handle's launch stream (wmx_internal.h: legacy_stream_create)
+struct AgcHandleCompat : HandleCompat {
     // agc_addition comes from the daemon's message thread while the record thread is inside agc_process (src/wmix.c:1070 beside :684-690);
     // the reference has no lock there and lives with it, the batch's host-side tables need one
     std::mutex mu;
     wmx_agc *batch;
-    int chn, freq, pkg;
-    bool *debug;
-    DevBuf buf;
 };
 
-struct AecHandleCompat {
-    hipStream_t s = nullptr;
+struct AecHandleCompat : HandleCompat {
     wmx_aec *batch;    // float AEC (the reference's default build) ...
     wmx_aecm *batchm;  // ... or the fixed-point AECM (its `#undef MAKE_WEBRTC_AEC` build): exactly one is set
-    int chn, freq, pkg;
-    bool *debug;
-    DevBuf far, near;
 };
+
+// One call on a handle: `given` int16 of each input that is there go into a region of `n` (whole packets; the tail of a partial last
+// packet is whatever the region held before), launch(buf, far) runs on the handle's stream, `given` int16 of region 0 come back to
+// `out`, and the stream has been waited for.  Returns the launch's result, else the staging's.  A launch that returns -1 is the
+// reference's own mid-buffer return (AEC only; no WMX_E* or HIP failure is -1): the packets before the offending one were written,
+// so the result still comes back.  An input that is not given gets a null device pointer: aec_run_host's callers pass far for mode & 1 and
+// near for mode & 2, which is what wmx_aec_run / wmx_aecm_run expect of the mode.
+template <class Launch>
+int staged_run(HandleCompat *h, const int16_t *in, const int16_t *far, int16_t *out, size_t n, size_t given, size_t n_far, Launch launch) {
+    wmx::Stage &st = h->stage;
+    const size_t bytes = given * sizeof(int16_t), room = n * sizeof(int16_t), room_far = n_far * sizeof(int16_t);
+    int rc = st.begin(room + room_far, wmx::Stage::kAlways, {room, room_far});
+    if (rc) return rc;
+    if (in) rc = st.put(0, in, bytes, h->s);
+    if (!rc && far) rc = st.put(1, far, bytes, h->s);
+    if (!rc) {
+        rc = launch(in ? st.dev<int16_t>(0) : nullptr, far ? st.dev<int16_t>(1) : nullptr);
+        if ((rc == 0 || rc == -1) && out) st.get(0, out, bytes);
+    }
+    const int waited = st.finish(h->s);  // aec_setFrameFar too: the far region is reused by the next call
+    return rc ? rc : waited;
+}
 
 // shared body of aec_setFrameFar / aec_process / aec_process2 (src/webrtc.c:286-483)
 int aec_run_host(AecHandleCompat *h, int mode, int16_t *far, int16_t *nearp, int16_t *out, int frameNum, int delayms) {
@@ -98,24 +73,10 @@ int aec_run_host(AecHandleCompat *h, int mode, int16_t *far, int16_t *nearp, int
     const int n_packets = (total + per_pkt - 1) / per_pkt;
     if (n_packets <= 0) return 0;
     const size_t n = (size_t)n_packets * per_pkt;
-    bool ok = true;
-    if (mode & 1) ok = ok && h->far.ensure(n) && h->far.in(far, (size_t)total);
-    if (mode & 2) ok = ok && h->near.ensure(n) && h->near.in(nearp, (size_t)total);
-    int rc = -1;
-    if (ok) {
-        rc = h->batchm ? wmx_aecm_run(h->batchm, mode, (mode & 1) ? h->far.p : nullptr, per_pkt, (mode & 2) ? h->near.p : nullptr,
-                                      (mode & 2) ? h->near.p : nullptr, n_packets, 0, per_pkt, delayms, h->s)
-                       : wmx_aec_run(h->batch, mode, (mode & 1) ? h->far.p : nullptr, per_pkt, (mode & 2) ? h->near.p : nullptr,
-                                     (mode & 2) ? h->near.p : nullptr, n_packets, 0, per_pkt, delayms, h->s);
-        if (rc == 0 || rc == -1) {
-            // rc == -1: the reference returned mid-buffer; packets before the offending one were written
-            if (mode & 2) {
-                if (!h->near.out(out, (size_t)total, h->s)) rc = -1;
-            } else if (hipStreamSynchronize(h->s) != hipSuccess) {  // aec_setFrameFar: the far buffer is reused by the next call
-                rc = -1;
-            }
-        }
-    }
+    const int rc = staged_run(h, nearp, far, out, n, (size_t)total, n, [&](int16_t *d_near, int16_t *d_far) {
+        return h->batchm ? wmx_aecm_run(h->batchm, mode, d_far, per_pkt, d_near, d_near, n_packets, 0, per_pkt, delayms, h->s)
+                         : wmx_aec_run(h->batch, mode, d_far, per_pkt, d_near, d_near, n_packets, 0, per_pkt, delayms, h->s);
+    });
     if (rc != 0) {
         (void)hipGetLastError();
         if (h->debug && *h->debug) printf("WebRtcAecX_Process failed !!, ret %d \r\n", rc);
@@ -207,11 +168,9 @@ void vad_process(void *fp, int16_t *frame, int frameNum) {
     const int packets = (frameNum + h->pkg - 1) / h->pkg;
     if (packets <= 0) return;
     const size_t n = (size_t)packets * h->pkg * h->chn, given = (size_t)frameNum * h->chn;
-    bool ok = h->buf.ensure(n);
-    ok = ok && h->buf.in(frame, given);
-    ok = ok && wmx_vad_process(h->batch, h->buf.p, packets, 1, 0, (long)n, h->s) == 0;
-    ok = ok && h->buf.out(frame, given, h->s);
-    if (!ok) {
+    const int rc = staged_run(h, frame, nullptr, frame, n, given, 0,
+                              [&](int16_t *buf, int16_t *) { return wmx_vad_process(h->batch, buf, packets, 1, 0, (long)n, h->s); });
+    if (rc) {
         (void)hipGetLastError();
         fprintf(stderr, "wmix_amd: vad_process failed on the GPU: %s\n", wmx_last_error());
     }
@@ -255,11 +214,9 @@ int agc_process(void *fp, int16_t *frame, int16_t *frameOut, int frameNum) {
     if (n_packets <= 0) return 0;
     const size_t n = (size_t)n_packets * per_pkt;
     std::lock_guard<std::mutex> lock(h->mu);
-    bool ok = h->buf.ensure(n);
-    ok = ok && h->buf.in(frame, (size_t)total);
-    ok = ok && wmx_agc_process(h->batch, h->buf.p, h->buf.p, n_packets, 0, per_pkt, h->s) == 0;
-    ok = ok && h->buf.out(frameOut, (size_t)total, h->s);
-    if (!ok) {
+    const int rc = staged_run(h, frame, nullptr, frameOut, n, (size_t)total, 0,
+                              [&](int16_t *buf, int16_t *) { return wmx_agc_process(h->batch, buf, buf, n_packets, 0, per_pkt, h->s); });
+    if (rc) {
         (void)hipGetLastError();
         if (h->debug && *h->debug) printf("WebRtcAgc_Process failed !!, ret %d \r\n", -1);
         fprintf(stderr, "wmix_amd: agc_process failed on the GPU: %s\n", wmx_last_error());
@@ -325,12 +282,10 @@ void ns_process(void *fp, int16_t *frame, int16_t *frameOut, int frameNum) {
     const int n_packets = (total + per_pkt - 1) / per_pkt;  // the reference loop runs while cLen < realFrameLen
     if (n_packets <= 0) return;
     const size_t n = (size_t)n_packets * per_pkt;
-    bool ok = h->buf.ensure(n);
-    ok = ok && h->buf.in(frame, (size_t)total);
-    ok = ok && (h->batchx ? wmx_nsx_process(h->batchx, h->buf.p, h->buf.p, n_packets, 0, per_pkt, h->s)
-                          : wmx_ns_process(h->batch, h->buf.p, h->buf.p, n_packets, 0, per_pkt, h->s)) == 0;
-    ok = ok && h->buf.out(frameOut, (size_t)total, h->s);
-    if (!ok) {
+    const int rc = staged_run(h, frame, nullptr, frameOut, n, (size_t)total, 0, [&](int16_t *buf, int16_t *) {
+        return h->batchx ? wmx_nsx_process(h->batchx, buf, buf, n_packets, 0, per_pkt, h->s) : wmx_ns_process(h->batch, buf, buf, n_packets, 0, per_pkt, h->s);
+    });
+    if (rc) {
         (void)hipGetLastError();
         fprintf(stderr, "wmix_amd: ns_process failed on the GPU: %s\n", wmx_last_error());
     }

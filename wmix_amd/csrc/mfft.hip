@@ -15,8 +15,7 @@
 #include <mutex>
 #include <utility>
 #include <vector>
-#include <cstring>
-#include "wmx_internal.h"
+#include "legacy_stage.h"
 #include "fft_ooura.h"  // wave_sync
 #include "../../include/wmix_compat.h"
 
@@ -771,45 +770,27 @@ extern "C" int wmx_mfft_stream(int n_streams, const float *d_in, unsigned in_len
 // ------------------------------------------------------------------ legacy signatures (math/fft.h:19-51): one transform,
 // host arrays, NULLs as in the reference
 namespace {
-constexpr size_t kLegacyMappedMax = 1u << 20;  // bytes of staging up to which a legacy call goes through a mapped pinned buffer
+// One transform of a few KB (the daemon's spectrum display: N = 1024, src/wmix.c:1124-1137).  Every size check_size admits stages at
+// most 6 * 4 * kMfftMaxN = 96 KB: under this threshold, so these calls are mapped at every size (legacy_stage.h) and copied only
+// when the pinned allocation fails.
+constexpr size_t kLegacyMappedMax = 1u << 20;
+static_assert(6 * sizeof(float) * kMfftMaxN <= kLegacyMappedMax, "a legacy transform must stay under the mapped threshold");
 
 int legacy(int kind, float *in_re, float *in_im, float *out_re, float *out_im, float *out_af, float *out_pf, unsigned n) {
     unsigned m;
     if (check_size(n, &m)) return -1;
-    float *d = nullptr;
     const size_t bytes = (size_t)n * sizeof(float);
-    // One transform of a few KB (the daemon's spectrum display: N = 1024, src/wmix.c:1124-1137): a device allocation and six copies
-    // around the launch cost many times the work.  Pinned host memory mapped into the device instead, owned by the calling thread:
-    // memcpy in, one launch, one synchronisation, memcpy out.
-    static thread_local MapVec mv;
+    static thread_local Stage st;  // regions: in re, in im, out re, out im, out AF, out PF
     hipStream_t ts = wmx::thread_stream();  // the calling thread's own non-blocking stream (wmx_internal.h)
-    if (6 * bytes <= kLegacyMappedMax && mv.ensure(6 * bytes) == 0) {
-        float *hst = reinterpret_cast<float *>(mv.host), *dv = reinterpret_cast<float *>(mv.dev);
-        if (in_re) memcpy(hst, in_re, bytes);
-        if (in_im) memcpy(hst + n, in_im, bytes);
-        if (wmx_mfft(kind, 1, n, in_re ? dv : nullptr, in_im ? dv + n : nullptr, out_re ? dv + 2 * n : nullptr, out_im ? dv + 3 * n : nullptr,
-                     out_af ? dv + 4 * n : nullptr, out_pf ? dv + 5 * n : nullptr, ts) != 0 ||
-            hipStreamSynchronize(ts) != hipSuccess)
-            return -1;
-        float *outs[4] = {out_re, out_im, out_af, out_pf};
-        for (int k = 0; k < 4; k++)
-            if (outs[k]) memcpy(outs[k], hst + (size_t)(2 + k) * n, bytes);
-        return 0;
-    }
-    if (hipMalloc(&d, 6 * bytes) != hipSuccess) return -1;
-    float *d_ir = in_re ? d : nullptr, *d_ii = in_im ? d + n : nullptr;
-    float *d_or = out_re ? d + 2 * n : nullptr, *d_oi = out_im ? d + 3 * n : nullptr;
-    float *d_af = out_af ? d + 4 * n : nullptr, *d_pf = out_pf ? d + 5 * n : nullptr;
-    int rc = 0;
-    if (in_re && hipMemcpyAsync(d_ir, in_re, bytes, hipMemcpyHostToDevice, ts) != hipSuccess) rc = -1;
-    if (in_im && hipMemcpyAsync(d_ii, in_im, bytes, hipMemcpyHostToDevice, ts) != hipSuccess) rc = -1;
-    if (!rc) rc = wmx_mfft(kind, 1, n, d_ir, d_ii, d_or, d_oi, d_af, d_pf, ts);
-    float *outs[4] = {out_re, out_im, out_af, out_pf}, *devs[4] = {d_or, d_oi, d_af, d_pf};
-    for (int k = 0; k < 4 && !rc; k++)
-        if (outs[k] && hipMemcpyAsync(outs[k], devs[k], bytes, hipMemcpyDeviceToHost, ts) != hipSuccess) rc = -1;
-    if (hipStreamSynchronize(ts) != hipSuccess) rc = -1;  // also on failure: nothing of this call may still touch `d`
-    (void)hipFree(d);
-    return rc;
+    if (st.begin(6 * bytes, kLegacyMappedMax, {bytes, bytes, bytes, bytes, bytes, bytes})) return -1;
+    float *host[6] = {in_re, in_im, out_re, out_im, out_af, out_pf}, *d[6];
+    for (int k = 0; k < 6; k++) d[k] = host[k] ? st.dev<float>(k) : nullptr;
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; k++) ok = !host[k] || st.put(k, host[k], bytes, ts) == 0;
+    ok = ok && wmx_mfft(kind, 1, n, d[0], d[1], d[2], d[3], d[4], d[5], ts) == 0;
+    for (int k = 2; k < 6 && ok; k++)
+        if (host[k]) st.get(k, host[k], bytes);
+    return st.finish(ts) == 0 && ok ? 0 : -1;
 }
 }  // namespace
 
@@ -828,30 +809,17 @@ extern "C" void IFFTR(float inReal[], float inImag[], float outReal[], float out
 extern "C" void fft_stream(float in[], unsigned int inLen, float stream[], unsigned int stLen, float outAF[], float outPF[]) {
     unsigned m;
     if (!in || !stream || inLen == 0 || 2 * inLen > stLen || check_size(stLen, &m)) return;
-    float *d = nullptr;
     const size_t sb = (size_t)stLen * sizeof(float), ib = (size_t)inLen * sizeof(float);
-    static thread_local MapVec mv;
+    static thread_local Stage st;  // regions: the pool, out AF, out PF, in
     hipStream_t ts = wmx::thread_stream();
-    if (3 * sb + ib <= kLegacyMappedMax && mv.ensure(3 * sb + ib) == 0) {
-        float *hst = reinterpret_cast<float *>(mv.host), *dv = reinterpret_cast<float *>(mv.dev);
-        memcpy(hst, stream, sb);
-        memcpy(hst + 3 * (size_t)stLen, in, ib);
-        if (wmx_mfft_stream(1, dv + 3 * (size_t)stLen, inLen, dv, stLen, outAF ? dv + stLen : nullptr, outPF ? dv + 2 * (size_t)stLen : nullptr,
-                            ts) != 0 ||
-            hipStreamSynchronize(ts) != hipSuccess)
-            return;
-        memcpy(stream, hst, sb);
-        if (outAF) memcpy(outAF, hst + stLen, sb);
-        if (outPF) memcpy(outPF, hst + 2 * (size_t)stLen, sb);
-        return;
+    if (st.begin(3 * sb + ib, kLegacyMappedMax, {sb, sb, sb, ib})) return;
+    bool ok = st.put(0, stream, sb, ts) == 0 && st.put(3, in, ib, ts) == 0;
+    ok = ok && wmx_mfft_stream(1, st.dev<const float>(3), inLen, st.dev<float>(0), stLen, outAF ? st.dev<float>(1) : nullptr,
+                               outPF ? st.dev<float>(2) : nullptr, ts) == 0;
+    if (ok) {
+        st.get(0, stream, sb);
+        if (outAF) st.get(1, outAF, sb);
+        if (outPF) st.get(2, outPF, sb);
     }
-    if (hipMalloc(&d, 3 * sb + ib) != hipSuccess) return;
-    float *d_pool = d, *d_af = d + stLen, *d_pf = d + 2 * stLen, *d_in = d + 3 * stLen;
-    bool ok = hipMemcpyAsync(d_pool, stream, sb, hipMemcpyHostToDevice, ts) == hipSuccess && hipMemcpyAsync(d_in, in, ib, hipMemcpyHostToDevice, ts) == hipSuccess;
-    ok = ok && wmx_mfft_stream(1, d_in, inLen, d_pool, stLen, outAF ? d_af : nullptr, outPF ? d_pf : nullptr, ts) == 0;
-    ok = ok && hipMemcpyAsync(stream, d_pool, sb, hipMemcpyDeviceToHost, ts) == hipSuccess;
-    if (ok && outAF) ok = hipMemcpyAsync(outAF, d_af, sb, hipMemcpyDeviceToHost, ts) == hipSuccess;
-    if (ok && outPF) ok = hipMemcpyAsync(outPF, d_pf, sb, hipMemcpyDeviceToHost, ts) == hipSuccess;
-    (void)hipStreamSynchronize(ts);
-    (void)hipFree(d);
+    (void)st.finish(ts);
 }

@@ -15,7 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "wmx_internal.h"
+#include "legacy_stage.h"
 #include "../../include/wmix_compat.h"
 #include "mix_sched.h"
 #include "mix_minus.h"
@@ -195,42 +195,7 @@ __global__ __launch_bounds__(256) void load_minus_conf_kernel(int16_t *__restric
     }
 }
 
-// A growable device buffer owned by its (usually thread_local) object: freed when the owner dies -- a finished task
-// thread of the daemon gives its staging buffers back -- except while the process is exiting (runtime_exiting()).
-struct DevVec {
-    void *p = nullptr;
-    size_t cap = 0;
-    int device = -1;
-    DevVec() = default;
-    DevVec(const DevVec &) = delete;
-    DevVec &operator=(const DevVec &) = delete;
-    int ensure(size_t bytes) {
-        int dev = -1;
-        WMX_HIP(hipGetDevice(&dev));
-        if (dev != device && p) {  // the thread moved to another device: the old buffer is of no use there
-            DeviceScope on(device);
-            (void)hipFree(p);
-            p = nullptr;
-            cap = 0;
-        }
-        device = dev;
-        if (bytes <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        WMX_HIP(hipMalloc(&p, bytes));
-        cap = bytes;
-        return 0;
-    }
-    ~DevVec() {
-        if (p && !runtime_exiting()) {
-            DeviceScope on(device);
-            (void)hipFree(p);
-        }
-    }
-};
-
-constexpr size_t kMappedMaxBytes = 64 * 1024;  // above this the DMA engines win: the copy path
+constexpr size_t kMappedMaxBytes = 64 * 1024;  // legacy staging (legacy_stage.h): above this the DMA engines win, the call is copied
 
 }  // namespace
 
@@ -371,27 +336,17 @@ int wmx_pcm_zoom(int inChn, int inFreq, const int16_t *d_in, uint32_t inLen, int
 // legacy host form, src/wmix.h:122-127
 uint32_t wmix_pcm_zoom(uint8_t inChn, uint16_t inFreq, uint8_t *in, uint32_t inLen, uint8_t outChn, uint16_t outFreq, uint8_t *out) {
     using namespace wmx;
-    static thread_local DevVec a, b;
-    static thread_local MapVec ma, mb;
+    static thread_local Stage st;  // region 0: in, region 1: out
     if (inLen == 0 || !in || !out || !inFreq || !outFreq || !inChn || !outChn) return 0;
     const uint32_t need = wmix_len_of_out(inChn, inFreq, inLen, outChn, outFreq);  // what the reference's callers size `out` by
     uint32_t n = 0;
     // the calling thread's own non-blocking stream, and only that one is waited for (wmx_internal.h: thread_stream)
     hipStream_t ts = thread_stream();
-    if ((size_t)inLen + need <= kMappedMaxBytes && ma.ensure(inLen + 16) == 0 && mb.ensure((size_t)need + 16) == 0) {
-        memcpy(ma.host, in, inLen);
-        if (wmx_pcm_zoom(inChn, inFreq, (const int16_t *)ma.dev, inLen, outChn, outFreq, (int16_t *)mb.dev, need + 16, 0, 0, 1, &n, ts) != 0)
-            return 0;
-        if (hipStreamSynchronize(ts) != hipSuccess) return 0;
-        if (n) memcpy(out, mb.host, n);
-        return n;
-    }
-    if (a.ensure(inLen + 16) || b.ensure((size_t)need + 16)) return 0;
-    if (hipMemcpyAsync(a.p, in, inLen, hipMemcpyHostToDevice, ts) != hipSuccess || hipStreamSynchronize(ts) != hipSuccess) return 0;
-    if (wmx_pcm_zoom(inChn, inFreq, (const int16_t *)a.p, inLen, outChn, outFreq, (int16_t *)b.p, need + 16, 0, 0, 1, &n, ts) != 0)
-        return 0;
-    if (n && (hipMemcpyAsync(out, b.p, n, hipMemcpyDeviceToHost, ts) != hipSuccess || hipStreamSynchronize(ts) != hipSuccess)) return 0;
-    return n;
+    if (st.begin((size_t)inLen + need, kMappedMaxBytes, {(size_t)inLen + 16, (size_t)need + 16})) return 0;
+    const bool ok = st.put(0, in, inLen, ts) == 0 &&
+                    wmx_pcm_zoom(inChn, inFreq, st.dev<const int16_t>(0), inLen, outChn, outFreq, st.dev<int16_t>(1), need + 16, 0, 0, 1, &n, ts) == 0;
+    if (ok) st.get(1, out, n);
+    return st.finish(ts) == 0 && ok ? n : 0;
 }
 
 int wmx_mix_destroy(wmx_mix *m) {
@@ -671,13 +626,12 @@ WMix_Point wmix_load_data(WMix_Struct_Head *wmix, WMix_Point src, uint32_t srcU8
         }
     };
     static thread_local MixOwner owner;
-    static thread_local DevVec d_src;
     wmx_mix *&m = owner.m;
     if (!m || m->chn != ring_chn || m->freq != ring_freq) {
         if (m) wmx_mix_destroy(m);
         m = nullptr;
         if (wmx_mix_create(&m, 1, ring_chn, ring_freq) != 0) return pHead;
-        {  // this ring only ever holds the span of one call: pinned host memory the kernel works on over PCIe (see MapVec)
+        {  // this ring only ever holds the span of one call: pinned host memory the kernel works on over PCIe (see legacy_stage.h)
             void *hp = nullptr, *dp = nullptr;
             if (hipHostMalloc(&hp, m->ring_bytes, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
                 (void)hipFree(m->d_rings);
@@ -726,36 +680,31 @@ WMix_Point wmix_load_data(WMix_Struct_Head *wmix, WMix_Point src, uint32_t srcU8
     // down-sampling branches never read ahead, and neither does the adapter
     const bool reads_ahead = sample == 16 && (channels == 1 || channels == 2) && (int)freq < m->freq;
     const size_t src_bytes = (size_t)srcU8Len + (reads_ahead ? 2 * channels : 0);
-    uint8_t *ring = (uint8_t *)m->d_rings;
-    static thread_local MapVec m_src;
+    static thread_local Stage st;
     // six task threads of the daemon load side by side (src/wmixTask.c:85, 973, 1311, 1484, 1704, 1927): each on its own non-blocking
     // stream, waiting for that stream alone (wmx_internal.h: thread_stream)
     hipStream_t ts = thread_stream();
-    if (m->h_rings && src_bytes <= kMappedMaxBytes && m_src.ensure(src_bytes + 8) == 0) {
-        memcpy(m_src.host, src.U8, src_bytes);
-        if (first) memcpy(m->h_rings + span_off, wmix->start.U8 + span_off, first);
-        if (second) memcpy(m->h_rings, wmix->start.U8, second);
-        bool okm = wmx_mix_load(m, (const int16_t *)m_src.dev, srcU8Len, freq, channels, sample, 1, 0, 0, reduce, &h, &t, ts) == 0;
-        okm = okm && hipStreamSynchronize(ts) == hipSuccess;
-        if (!okm) {
-            (void)hipGetLastError();
-            fprintf(stderr, "wmix_amd: wmix_load_data failed on the GPU: %s\n", wmx_last_error());
-            return pHead;
+    // the span between the caller's ring and ours, split at the wrap: plain memcpy when ours is the mapped one, else copies on the stream
+    const bool ring_mapped = m->h_rings != nullptr;
+    auto move_span = [&](bool up) {
+        const uint32_t at[2] = {span_off, 0}, len[2] = {first, second};
+        for (int k = 0; k < 2; k++) {
+            uint8_t *theirs = wmix->start.U8 + at[k], *ours = (ring_mapped ? m->h_rings : (uint8_t *)m->d_rings) + at[k];
+            uint8_t *dst = up ? ours : theirs, *from = up ? theirs : ours;
+            if (!len[k]) continue;
+            if (ring_mapped)
+                memcpy(dst, from, len[k]);
+            else if (hipMemcpyAsync(dst, from, len[k], up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, ts) != hipSuccess)
+                return false;
         }
-        if (first) memcpy(wmix->start.U8 + span_off, m->h_rings + span_off, first);
-        if (second) memcpy(wmix->start.U8, m->h_rings, second);
-        *tick = t;
-        pHead.U8 = wmix->start.U8 + h;
-        return pHead;
-    }
-    bool ok = d_src.ensure(src_bytes + 8) == 0;
-    ok = ok && hipMemcpyAsync(d_src.p, src.U8, src_bytes, hipMemcpyHostToDevice, ts) == hipSuccess;
-    ok = ok && (!first || hipMemcpyAsync(ring + span_off, wmix->start.U8 + span_off, first, hipMemcpyHostToDevice, ts) == hipSuccess);
-    ok = ok && (!second || hipMemcpyAsync(ring, wmix->start.U8, second, hipMemcpyHostToDevice, ts) == hipSuccess);
-    ok = ok && wmx_mix_load(m, (const int16_t *)d_src.p, srcU8Len, freq, channels, sample, 1, 0, 0, reduce, &h, &t, ts) == 0;
-    ok = ok && (!first || hipMemcpyAsync(wmix->start.U8 + span_off, ring + span_off, first, hipMemcpyDeviceToHost, ts) == hipSuccess);
-    ok = ok && (!second || hipMemcpyAsync(wmix->start.U8, ring, second, hipMemcpyDeviceToHost, ts) == hipSuccess);
-    ok = ok && hipStreamSynchronize(ts) == hipSuccess;
+        return true;
+    };
+    bool ok = st.begin(src_bytes, kMappedMaxBytes, {src_bytes + 8}) == 0;
+    ok = ok && st.put(0, src.U8, src_bytes, ts) == 0 && move_span(true);
+    ok = ok && wmx_mix_load(m, st.dev<const int16_t>(0), srcU8Len, freq, channels, sample, 1, 0, 0, reduce, &h, &t, ts) == 0;
+    if (!ring_mapped) ok = ok && move_span(false);  // stream copies: queued before the one wait
+    ok = (st.finish(ts) == 0) && ok;
+    if (ring_mapped) ok = ok && move_span(false);  // memcpy: the kernel's writes are in host memory after the wait
     if (!ok) {
         (void)hipGetLastError();
         fprintf(stderr, "wmix_amd: wmix_load_data failed on the GPU: %s\n", wmx_last_error());

@@ -155,39 +155,6 @@ struct SchedCache {
     ~SchedCache() { clear(); }
 };
 
-// Pinned HOST memory mapped into the device, for the legacy adapters' small buffers: two runtime copies around a launch cost several
-// times the work of a few hundred samples (wmix_pcm_zoom of one package: 43 us with copies).  The kernel reads and writes the mapped
-// buffer over PCIe instead: memcpy in, one launch, one synchronisation, memcpy out.
-struct MapVec {
-    uint8_t *host = nullptr, *dev = nullptr;
-    size_t cap = 0;
-    MapVec() = default;
-    MapVec(const MapVec &) = delete;
-    MapVec &operator=(const MapVec &) = delete;
-    inline int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (host) (void)hipHostFree(host);
-        host = dev = nullptr;
-        cap = 0;
-        void *hp = nullptr, *dp = nullptr;
-        const hipError_t e = hipHostMalloc(&hp, bytes < 4096 ? 4096 : bytes, hipHostMallocMapped | hipHostMallocPortable);
-        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(mapped)", __FILE__, __LINE__);
-        if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipHostFree(hp);
-            set_error("hipHostGetDevicePointer failed");
-            return WMX_ENODEV;
-        }
-        host = static_cast<uint8_t *>(hp);
-        dev = static_cast<uint8_t *>(dp);
-        cap = bytes < 4096 ? 4096 : bytes;
-        return 0;
-    }
-    ~MapVec() {
-        if (host && !runtime_exiting()) (void)hipHostFree(host);
-    }
-};
-
 // The legacy adapters' launch streams (round-5 VERDICT weak 4).  The reference calls its per-handle functions from many threads at once --
 // wmix_load_data from six task threads, agc_addition from the message thread, the four-call heartbeat from the record thread (SURVEY 8b
 // "Threading"; src/wmixTask.c:85, 973, 1311, 1484, 1704, 1927; src/wmix.c:1070) -- and rounds 1-5 put every one of those launches on the
