@@ -13,7 +13,7 @@
  * directories of the reference ship.
  *
  *   host_tick src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform alsa|hi3516|t31] [--rwtest] [--bridge P]
- *             [--bridge-sizes a,b,c,...]
+ *             [--bridge-sizes a,b,c,...] [--speakers N[,floor[,shift]]]
  *
  * src.i16    int16 [n_ticks][n_groups][n_src][20 ms of (src_freq, src_chn)]   what the task threads play
  * local.i16  int16 [n_ticks][n_groups * n_rec][160]                          the rooms without their loudspeakers
@@ -24,6 +24,9 @@
  *             rings of the other legs of its conference, so each leg is played everybody except itself (wmx_tick_bridge)
  * --bridge-sizes a,b,c,...: conferences of different sizes: the first a groups are conference 0, the next b conference 1, and so on;
  *             the groups that remain are idle legs, in no conference (wmx_tick_bridge_conferences; n_rec must be 1)
+ * --speakers N[,floor[,shift]]: with --bridge or --bridge-sizes, only the loudest N legs of a conference are loaded into the others'
+ *             rings, chosen on the device from every tick's heartbeat output (wmx_tick_bridge_speakers; floor 0 and shift 3 when not
+ *             given); the JSON line then says how many legs were speaking in the last tick
  * Prints one JSON line.  tests/test_host_chain_gpu.py compares out.i16 with one oracle daemon per group.
  *
  * Build (what __graft_entry__.build() runs):
@@ -78,12 +81,12 @@ static double now_ms(void) {
 
 int main(int argc, char **argv) {
     if (argc < 10) {
-        fprintf(stderr, "usage: %s src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform name] [--rwtest] [--bridge P] [--bridge-sizes a,b,..]\n", argv[0]);
+        fprintf(stderr, "usage: %s src.i16 local.i16 out.i16 n_groups n_src n_rec n_ticks src_freq src_chn [--platform name] [--rwtest] [--bridge P] [--bridge-sizes a,b,..] [--speakers N[,floor[,shift]]]\n", argv[0]);
         return 2;
     }
     const int G = atoi(argv[4]), n_src = atoi(argv[5]), R = atoi(argv[6]), T = atoi(argv[7]), sfreq = atoi(argv[8]), schn = atoi(argv[9]);
     int aec_ms = 400, rwtest = 0, bridge = 0;
-    const char *bridge_sizes = NULL;
+    const char *bridge_sizes = NULL, *speakers = NULL;
     long correct = -1; /* -1: the library's default = platform/alsa */
     const char *platform = "alsa";
     for (int i = 10; i < argc; i++) {
@@ -93,6 +96,8 @@ int main(int argc, char **argv) {
             bridge = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "--bridge-sizes") && i + 1 < argc) {
             bridge_sizes = argv[++i];
+        } else if (!strcmp(argv[i], "--speakers") && i + 1 < argc) {
+            speakers = argv[++i];
         } else if (!strcmp(argv[i], "--platform") && i + 1 < argc) {
             platform = argv[++i];
             if (!strcmp(platform, "alsa")) {
@@ -146,6 +151,21 @@ int main(int argc, char **argv) {
         for (int32_t r = 0; r < total; r++) conf_members[r] = r; /* consecutive groups; one past n_groups - 1 is refused */
         WMX_OK(wmx_tick_bridge_conferences(h, n_conf, conf_off, conf_members, NULL));
     }
+    int spk_max = 0, spk_shift = 3;
+    unsigned spk_floor = 0;
+    if (speakers) { /* what is wrong with the numbers is the library's to say; what is not a number is not passed on */
+        if (!bridge && !bridge_sizes) {
+            fprintf(stderr, "host_tick: --speakers needs --bridge or --bridge-sizes\n");
+            return 2;
+        }
+        int used = 0;
+        const int got = sscanf(speakers, "%d%n,%u%n,%d%n", &spk_max, &used, &spk_floor, &used, &spk_shift, &used);
+        if (got < 1 || speakers[used] != '\0') {
+            fprintf(stderr, "host_tick: --speakers N[,floor[,shift]], not '%s'\n", speakers);
+            return 2;
+        }
+        WMX_OK(wmx_tick_bridge_speakers(h, spk_max, spk_floor, spk_shift));
+    }
     if (wmx_tick_package_samples(h) != PKG) return 5;
     int16_t *d_src = NULL, *d_play = NULL, *d_rec = NULL, *d_zoom = NULL;
     HIP_OK(hipMalloc((void **)&d_src, (size_t)G * n_src * srow * 2));
@@ -182,6 +202,14 @@ int main(int argc, char **argv) {
         HIP_OK(hipMemcpy(o + (size_t)2 * G * PKG, d_rec, S * PKG * 2, hipMemcpyDeviceToHost));
     }
     const double wall = now_ms() - t0;
+    int speaking_legs = 0;
+    if (spk_max) { /* who was loaded in the last tick */
+        uint8_t *speaking = calloc((size_t)G, 1);
+        if (!speaking) return 2;
+        WMX_OK(wmx_tick_bridge_speaking(h, speaking, NULL, NULL));
+        for (int g = 0; g < G; g++) speaking_legs += speaking[g] != 0;
+        free(speaking);
+    }
     wmx_tick_destroy(h);
     FILE *f = fopen(argv[3], "wb");
     int rc = (!f || fwrite(out, 2, (size_t)T * out_row, f) != (size_t)T * out_row) ? 7 : 0;
@@ -194,6 +222,7 @@ int main(int argc, char **argv) {
         for (int c = 0; c < n_conf; c++) printf("%s%d", c ? ", " : "", (int)(conf_off[c + 1] - conf_off[c]));
         printf("], ");
     }
+    if (speakers) printf("\"speakers\": %d, \"speakers_floor\": %u, \"speakers_shift\": %d, \"speaking\": %d, ", spk_max, spk_floor, spk_shift, speaking_legs);
     printf("\"wall_ms\": %.3f, \"ms_per_tick\": %.4f, \"rc\": %d}\n", wall, wall / T, rc);
     return rc;
 }

@@ -462,6 +462,32 @@ int wmx_mix_set_conferences(wmx_mix *m, int n_conf, const int32_t *host_off, con
 int wmx_mix_conferences(const wmx_mix *m);
 int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
                             long source_stride, const uint8_t *d_mute, int reduce, uint32_t *head, uint32_t *tick, void *stream);
+/* Talker selection on the device: of the legs of a conference only the loudest max_speakers are loaded into the others' rings.  The
+ * call goes in front of the bridge load it feeds and writes that load's d_mute: wmx_mix_select_speakers addresses sources and indexes
+ * masks like wmx_mix_load_minus, wmx_mix_select_speakers_conf like wmx_mix_load_minus_conf (the layout in force).
+ * The rule is integer and exact (wmix_amd/csrc/speakers.h).  The mixer keeps one uint32 envelope env[r] per ring, zero at first.  For
+ * the member at list position p (ring r) of a conference of at least 2 members:
+ *   level    = sum of |x| over the srcU8Len / 2 int16 elements of the leg's source row as they lie there (all channels, before
+ *              resampling and the reduce division; |-32768| = 32768)
+ *   env'     = max(level, env - (env >> decay_shift)), stored for every member, the host-muted ones too
+ *   eligible = !d_mute[r] && env' >= floor
+ *   rank     = the eligible members s of the conference with env'[s] > env'[p], or env'[s] == env'[p] and s < p (list positions)
+ *   speaking = eligible && rank < max_speakers;   d_mute_out[r] = !speaking
+ * Every other ring (in no conference, or in one of 0 or 1 members) gets speaking = 0, d_mute_out = 1 and keeps its env.
+ * d_mute: the host's mute, NULL or n_groups bytes ON THE DEVICE by ring; d_mute_out: n_groups bytes ON THE DEVICE.  Every source
+ * element is read once; no host synchronisation, no upload and no allocation after the first call.
+ * WMX_EINVAL, nothing launched, env unchanged: max_speakers outside 1 .. WMX_MIX_MAX_PARTIES, decay_shift outside 0 .. 31, a NULL
+ * d_src or d_mute_out, a row of more than 131 071 elements (its level could overflow), the _conf form without a layout, and what the
+ * corresponding load refuses about parties and n_groups.
+ * wmx_mix_reset_speakers: env = 0 for the n rings host_idx lists (NULL = every ring), on `stream`: what a new call in a reused slot
+ * does.  wmx_mix_export_speakers: env and speaking of every ring (n_groups entries each; either may be NULL) as the work queued on
+ * `stream` leaves them; blocking. */
+int wmx_mix_select_speakers(wmx_mix *m, int parties, const int16_t *d_src, uint32_t srcU8Len, long conf_stride, long source_stride,
+                            const uint8_t *d_mute, int max_speakers, uint32_t floor, int decay_shift, uint8_t *d_mute_out, void *stream);
+int wmx_mix_select_speakers_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, long source_stride, const uint8_t *d_mute,
+                                 int max_speakers, uint32_t floor, int decay_shift, uint8_t *d_mute_out, void *stream);
+int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
+int wmx_mix_export_speakers(const wmx_mix *m, uint32_t *host_env, uint8_t *host_speaking, void *stream);
 int wmx_mix_drain(wmx_mix *m, int16_t *d_out, uint32_t bytes, long out_stride, void *stream);
 int wmx_mix_export(const wmx_mix *m, int group, int16_t *host_ring, uint32_t *head_off, uint32_t *tick);
 
@@ -682,6 +708,16 @@ int wmx_tick_bridge_mute(wmx_tick *h, const uint8_t *host_mask, void *stream);
  * wmx_tick_bridge_mute works unchanged (the mask is by ring).  It excludes wmx_tick_rw_test(h, 1) and wmx_tick_bridge(h, parties > 0),
  * and each of them excludes it: WMX_EINVAL. */
 int wmx_tick_bridge_conferences(wmx_tick *h, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream);
+/* Talker selection in the tick (wmx_mix_select_speakers / _conf on the tick's mixer).  May be called at any time and takes effect while
+ * either bridge form is on: wmx_tick_record then runs the selection on the chain's output, between the chain and the bridge load, with
+ * the mask of wmx_tick_bridge_mute as the host's mute and a mask buffer of the tick's own as the load's d_mute.  max_speakers == 0
+ * (the default) switches it off: the tick's launches are then what they are without it.  Switching off does not clear env; a new call
+ * in a reused slot clears its own with wmx_mix_reset_speakers(wmx_tick_mix(h), ..), next to its wmx_chain_reset_streams.
+ * WMX_EINVAL: max_speakers outside 0 .. WMX_MIX_MAX_PARTIES, decay_shift outside 0 .. 31.
+ * wmx_tick_bridge_speaking: who was speaking in the last tick and every ring's envelope (wmx_mix_export_speakers; n_groups entries
+ * each, either may be NULL; blocking). */
+int wmx_tick_bridge_speakers(wmx_tick *h, int max_speakers, uint32_t floor, int decay_shift);
+int wmx_tick_bridge_speaking(wmx_tick *h, uint8_t *host_speaking, uint32_t *host_env, void *stream);
 /* the daemon of another platform directory: PLAT_AEC_INTERVALMS (alsa 400, hi3516 700, t31 0; plat.h:14/19) is wmx_tick_create's
  * aec_delay_ms -- the FIFO gets AEC_FIFO_PKG_NUM = aec_delay_ms / interval_ms + 2 slots (src/wmixConf.h:141) -- and PLAT_PLAY_CORRECT is
  * set here (wmx_mix_set_play_correct on the tick's rings; default platform/alsa's) */

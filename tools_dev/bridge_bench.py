@@ -18,7 +18,15 @@ b. a telephony mix of 4 096 conferences (70 % of 2 legs, 20 % of 3, 8 % of 4 - 8
    (= FIFO rows = chain streams) the layout saves.
 Device events around every repetition; they include the host's work between the launches (the cursor rule over every conference).
 
-    python tools_dev/bridge_bench.py --ragged --out profiles/bridge/bridge_ragged_bench.json"""
+    python tools_dev/bridge_bench.py --ragged --out profiles/bridge/bridge_ragged_bench.json
+
+--speakers N measures the talker selection (wmx_mix_select_speakers, with --ragged wmx_mix_select_speakers_conf) on the same shapes: per
+tick the selection alone, the bridge load alone over every leg (the load kernels are what they were before the selection existed), and
+the selection followed by the load it feeds (the load then skips the sources of the legs that are not speaking).  The mask of the first
+call is compared with numpy's ranking of the rows' levels before any time is reported; the sides alternate, device events around each.
+
+    python tools_dev/bridge_bench.py --speakers 3 --out profiles/bridge/bridge_speakers_bench.json
+    python tools_dev/bridge_bench.py --speakers 3 --ragged --out profiles/bridge/bridge_speakers_ragged_bench.json"""
 import argparse
 import json
 import os
@@ -215,16 +223,95 @@ def telephony_against_padding(reps, freq=8000):
             "rings_fifo_rows_and_chain_streams_saved": padded - legs, "ring_bytes_saved": (padded - legs) * 2 * freq}
 
 
+def speakers_against_load(layout, P, n, freq, max_speakers, reps, what):
+    """layout: None = the uniform form with P consecutive legs per conference; else the list of conferences of the layout form"""
+    per = freq // 1000 * 20
+    mb = MixBatch(n, 1, freq)
+    g = torch.Generator(device="cuda").manual_seed(9)
+    src = torch.randint(-20000, 20000, (n, per), dtype=torch.int16, device="cuda", generator=g)
+    if layout is not None:
+        mb.set_conferences(layout)
+    confs = layout if layout is not None else [list(range(c * P, c * P + P)) for c in range(n // P)]
+    mb.set(0, 0, 1)
+    mb.set_play_correct(0)
+    mask = torch.empty(n, dtype=torch.uint8, device="cuda")
+    shaped = src.view(n // P, P, per) if layout is None else src
+
+    def select():
+        if layout is None:
+            mb.select_speakers(shaped, P, per * 2, max_speakers, 0, 3, out=mask)
+        else:
+            mb.select_speakers_conf(shaped, per * 2, max_speakers, 0, 3, out=mask)
+
+    # ---- the same speakers?  The first call finds every envelope at zero: env' is the row's level, floor 0
+    select()
+    got, level = mask.cpu().numpy(), src.to(torch.int64).abs().sum(1).cpu().numpy()
+    sample = sorted({0, 1, len(confs) // 2, len(confs) - 1})
+    for c in sample:
+        mem = confs[c]
+        order = sorted(range(len(mem)), key=lambda p: (-level[mem[p]], p))[:max_speakers]
+        want = [0 if p in order else 1 for p in range(len(mem))]
+        assert len(mem) < 2 or got[mem].tolist() == want, ("speakers differ", c)
+    assert np.array_equal(mb.export_speakers()[1][confs[sample[-1]]], level[confs[sample[-1]]]) or len(confs[sample[-1]]) < 2
+    cur = {}
+
+    def load(key, mute):
+        def f():
+            if layout is None:
+                h, t = cur.get(key, (NULL, 0))
+                cur[key] = mb.load_minus(shaped, P, per * 2, freq, 1, mute=mute, head=h, tick=t)
+            else:
+                h, t = cur.get(key, (None, None))
+                cur[key] = mb.load_minus_conf(shaped, per * 2, freq, 1, mute=mute, head=h, tick=t)
+        return f
+
+    load_all, load_sel = load("all", None), load("sel", mask)
+
+    def select_then_load():
+        select()
+        load_sel()
+
+    t_sel, t_all, t_both = alternate([select, load_all, select_then_load], reps)
+    mb.close()
+    a, b, c = stats(t_sel), stats(t_all), stats(t_both)
+    live = sum(len(m) for m in confs if len(m) >= 2)
+    read = live * per * 2
+    return {"what": what, "legs": n, "conferences": len(confs), "legs_in_conferences": live, "ring": "1x%d" % freq, "package_samples": per,
+            "max_speakers": max_speakers, "conferences_checked": len(sample), "select": a, "load_every_leg": b, "select_then_load": c,
+            "select_over_load": round(a["median_ms"] / b["median_ms"], 3),
+            "select_then_load_over_load": round(c["median_ms"] / b["median_ms"], 3),
+            "select_source_bytes": read, "select_TBs": round(read / (a["median_ms"] * 1e-3) / 1e12, 3)}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="4096x8x8000,65536x8x16000", help="conferences x parties x ring rate, comma separated")
     ap.add_argument("--tick", default="4096x8", help="conferences x parties of the tick measurement; empty = skip")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--ragged", action="store_true", help="the bridge over a layout: same legs both ways, a telephony mix against padding")
+    ap.add_argument("--speakers", type=int, default=0, help="measure the talker selection with this max_speakers instead (uniform shapes, or --ragged)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
     res = {"tool": "bridge_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps, "load": [], "tick": None}
+    if args.speakers:
+        res = {"tool": "bridge_bench --speakers %d%s" % (args.speakers, " --ragged" if args.ragged else ""), "device": torch.cuda.get_device_name(0),
+               "reps": args.reps, "runs": "the builder's own, one process, the sides alternating", "speakers": []}
+        for s in [x for x in args.sizes.split(",") if x]:
+            n_conf, P, freq = (int(v) for v in s.split("x"))
+            if not args.ragged:
+                res["speakers"].append(speakers_against_load(None, P, n_conf * P, freq, args.speakers, args.reps, "uniform %dx%d" % (n_conf, P)))
+                continue
+            for parties in (4, 32):  # the same legs as equal consecutive conferences through the layout
+                lay = [list(range(c * parties, c * parties + parties)) for c in range(n_conf * P // parties)]
+                res["speakers"].append(speakers_against_load(lay, parties, n_conf * P, freq, args.speakers, args.reps, "layout %dx%d" % (len(lay), parties)))
+        if args.ragged:
+            sizes = telephony_sizes()
+            off = np.concatenate([[0], np.cumsum(sizes)])
+            lay = [list(range(off[c], off[c + 1])) for c in range(len(sizes))]
+            res["speakers"].append(speakers_against_load(lay, 0, int(off[-1]), 8000, args.speakers, args.reps, "telephony mix of %d conferences" % len(sizes)))
+        args.sizes = args.tick = ""
+        args.ragged = False
     if args.ragged:
         res = {"tool": "bridge_bench --ragged", "device": torch.cuda.get_device_name(0), "reps": args.reps, "same_legs": [], "telephony": None}
         for s in [x for x in args.sizes.split(",") if x]:

@@ -20,6 +20,7 @@
 #include "mix_sched.h"
 #include "mix_minus.h"
 #include "bridge_layout.h"
+#include "speakers.h"
 
 namespace wmx {
 namespace {
@@ -195,6 +196,77 @@ __global__ __launch_bounds__(256) void load_minus_conf_kernel(int16_t *__restric
     }
 }
 
+// ---- talker selection (speakers.h)
+__device__ __forceinline__ uint32_t abs_sum_pair(uint32_t w) { return speakers_abs16((int16_t)(w & 0xffffu)) + speakers_abs16((int16_t)(w >> 16)); }
+
+// the rings the selection kernel does not visit: nobody speaks there
+__global__ __launch_bounds__(256) void speakers_clear_kernel(uint8_t *__restrict__ speaking, uint8_t *__restrict__ mute_out, int n_groups) {
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n_groups; r += gridDim.x * blockDim.x) {
+        speaking[r] = 0;
+        mute_out[r] = 1;
+    }
+}
+
+// One wave = one conference (a slot of the layout when `tab` is given, else `parties` consecutive rings), the workgroup's waves on
+// conferences of their own.  The wave's lanes are dealt out to the members, L = the largest power of two with n * L <= 64 lanes each
+// (32 for a two-party call, 2 for 32 legs): the L lanes of a member stride its source row -- the elements in front of the first
+// 16-byte boundary and behind the last one singly, the rest as 16-byte loads, so a row that is not aligned (source_stride is the
+// caller's) is read the same way and every element once -- and an xor-shuffle over the L lanes gives the row's level.  Then lane p
+// is member p: its env' (speakers.h), the rank from the n envelopes read lane by lane, and the three stores.  No LDS, no atomics.
+__global__ __launch_bounds__(256) void select_speakers_kernel(const int16_t *__restrict__ src, uint32_t n_el, int parties, long conf_stride,
+                                                              long source_stride, const int32_t *__restrict__ tab,
+                                                              const int32_t *__restrict__ members, const uint8_t *__restrict__ mute,
+                                                              int max_speakers, uint32_t floor, int decay_shift, uint32_t *__restrict__ env,
+                                                              uint8_t *__restrict__ speaking, uint8_t *__restrict__ mute_out, int n_slots) {
+    const int lane = (int)(threadIdx.x & 63u), waves = (int)(blockDim.x >> 6);
+    for (int w = (int)blockIdx.x * waves + (int)(threadIdx.x >> 6); w < n_slots; w += (int)gridDim.x * waves) {
+        const int slot = __builtin_amdgcn_readfirstlane(w);  // the conference is wave-uniform: the table entry is a scalar load
+        const int32_t *mem = tab ? members + tab[2 * (size_t)slot] : nullptr;
+        const int n = tab ? tab[2 * (size_t)slot + 1] : parties;  // 2 .. 32
+        int shift = 5;  // log2 of L
+        while ((n << shift) > 64) shift--;
+        const int L = 1 << shift, q = lane >> shift, sub = lane & (L - 1);
+        uint32_t sum = 0;
+        if (q < n) {
+            const int16_t *row = mem ? src + (size_t)mem[q] * source_stride : src + (size_t)slot * conf_stride + (size_t)q * source_stride;
+            uint32_t head = (8u - (uint32_t)(((uintptr_t)row & 15u) >> 1)) & 7u;  // elements in front of the 16-byte boundary
+            if (head > n_el) head = n_el;
+            const uint32_t body = (n_el - head) / 8;  // whole 16-byte pieces, none past the row's end
+            for (uint32_t i = (uint32_t)sub; i < head; i += (uint32_t)L) sum += speakers_abs16(row[i]);
+            const uint4 *v = reinterpret_cast<const uint4 *>(row + head);
+            for (uint32_t c = (uint32_t)sub; c < body; c += (uint32_t)L) {
+                const uint4 x = v[c];
+                sum += abs_sum_pair(x.x) + abs_sum_pair(x.y) + abs_sum_pair(x.z) + abs_sum_pair(x.w);
+            }
+            for (uint32_t i = head + body * 8 + (uint32_t)sub; i < n_el; i += (uint32_t)L) sum += speakers_abs16(row[i]);
+        }
+        for (int o = L >> 1; o > 0; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o);
+        // lane p = member p
+        const uint32_t level = (uint32_t)__shfl((int)sum, (lane << shift) & 63);
+        const bool member = lane < n;
+        size_t r = 0;
+        uint32_t e = 0;
+        bool eligible = false;
+        if (member) {
+            r = mem ? (size_t)mem[lane] : (size_t)slot * parties + lane;
+            e = speakers_env_next(env[r], level, decay_shift);
+            eligible = speakers_eligible(mute && mute[r], e, floor);
+        }
+        const unsigned long long eligible_lanes = __ballot(eligible);
+        int rank = 0;
+        for (int s = 0; s < n; s++) {  // s is wave-uniform: a lane read, no LDS traffic
+            const uint32_t es = (uint32_t)__builtin_amdgcn_readlane((int)e, s);
+            rank += ((eligible_lanes >> s) & 1ull) && speakers_outranks(es, s, e, lane);
+        }
+        if (member) {
+            const bool sp = eligible && rank < max_speakers;
+            env[r] = e;
+            speaking[r] = sp ? 1 : 0;
+            mute_out[r] = sp ? 0 : 1;
+        }
+    }
+}
+
 constexpr size_t kMappedMaxBytes = 64 * 1024;  // legacy staging (legacy_stage.h): above this the DMA engines win, the call is copied
 
 }  // namespace
@@ -226,6 +298,12 @@ struct wmx_mix {
     int32_t *d_conf_members = nullptr, *d_conf_tab = nullptr;
     uint32_t *d_conf_lead = nullptr;
     size_t conf_cap_members = 0, conf_cap_slots = 0;
+    // talker selection (speakers.h): one envelope and one speaking flag per ring, made by the first call that needs them (one block:
+    // d_speaking lies behind the envelopes); the index list of wmx_mix_reset_speakers
+    uint32_t *d_env = nullptr;
+    uint8_t *d_speaking = nullptr;
+    int32_t *d_reset_idx = nullptr;
+    size_t reset_cap = 0;
 };
 
 // What wmx_mix_load and wmx_mix_load_minus share on the host: where the call starts (the reference's cursor rule), the schedule of
@@ -359,6 +437,8 @@ int wmx_mix_destroy(wmx_mix *m) {
     if (m->d_conf_members) (void)hipFree(m->d_conf_members);
     if (m->d_conf_tab) (void)hipFree(m->d_conf_tab);
     if (m->d_conf_lead) (void)hipFree(m->d_conf_lead);
+    if (m->d_env) (void)hipFree(m->d_env);
+    if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
     delete m;
     return 0;
 }
@@ -571,6 +651,142 @@ int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
         WMX_LAUNCH_CHECK();
     }
     return n_out && m->conf.slots() ? m->sched.used(ent, s) : 0;
+}
+
+// ---- talker selection (include/wmix_amd.h, speakers.h)
+// the envelopes and the speaking flags, zero, from the first call that needs them on
+static int speakers_state(wmx_mix *m) {
+    if (m->d_env) return 0;
+    const size_t n = (size_t)m->n_groups;
+    void *p = nullptr;
+    WMX_HIP(hipMalloc(&p, n * sizeof(uint32_t) + n));
+    hipError_t e = hipMemset(p, 0, n * sizeof(uint32_t) + n);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return wmx::hip_fail(e, "hipMemset(speakers)", __FILE__, __LINE__);
+    }
+    m->d_env = static_cast<uint32_t *>(p);
+    m->d_speaking = reinterpret_cast<uint8_t *>(m->d_env + n);
+    return 0;
+}
+
+static int speakers_check(const char *who, const void *m, const void *d_src, uint32_t srcU8Len, int max_speakers, int decay_shift,
+                          const void *d_mute_out) {
+    using namespace wmx;
+    if (!m || !d_src || !d_mute_out) {
+        set_error("%s: bad argument", who);
+        return WMX_EINVAL;
+    }
+    if (!speakers_params_ok(max_speakers, decay_shift)) {
+        set_error("%s: max_speakers=%d must be 1 .. %d and decay_shift=%d 0 .. 31", who, max_speakers, WMX_MIX_MAX_PARTIES, decay_shift);
+        return WMX_EINVAL;
+    }
+    if (!speakers_len_ok(srcU8Len)) {
+        set_error("%s: the level of a row of %u elements can overflow 32 bits (at most %u)", who, srcU8Len / 2, kSpeakersMaxElements);
+        return WMX_EINVAL;
+    }
+    return 0;
+}
+
+// one wave per conference, four to a workgroup
+static int speakers_launch(wmx_mix *m, int n_slots, int parties, const int16_t *d_src, uint32_t srcU8Len, long conf_stride, long source_stride,
+                           const int32_t *tab, const int32_t *members, const uint8_t *d_mute, int max_speakers, uint32_t floor,
+                           int decay_shift, uint8_t *d_mute_out, hipStream_t s) {
+    using namespace wmx;
+    if (n_slots < 1) return 0;
+    const unsigned grid = stream_grid((size_t)n_slots * 64, 256);
+    hipLaunchKernelGGL(select_speakers_kernel, dim3(grid), dim3(256), 0, s, d_src, srcU8Len / 2, parties, conf_stride, source_stride, tab, members,
+                       d_mute, max_speakers, floor, decay_shift, m->d_env, m->d_speaking, d_mute_out, n_slots);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wmx_mix_select_speakers(wmx_mix *m, int parties, const int16_t *d_src, uint32_t srcU8Len, long conf_stride, long source_stride,
+                            const uint8_t *d_mute, int max_speakers, uint32_t floor, int decay_shift, uint8_t *d_mute_out, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    const int rcc = speakers_check("wmx_mix_select_speakers", m, d_src, srcU8Len, max_speakers, decay_shift, d_mute_out);
+    if (rcc) return rcc;
+    if (parties < 2 || parties > WMX_MIX_MAX_PARTIES || m->n_groups % parties != 0) {  // wmx_mix_load_minus
+        set_error("wmx_mix_select_speakers: parties=%d must be 2 .. %d and divide the mixer's %d rings", parties, WMX_MIX_MAX_PARTIES, m->n_groups);
+        return WMX_EINVAL;
+    }
+    const int rcs = speakers_state(m);
+    if (rcs) return rcs;
+    // every ring is a member of a conference: nothing to clear
+    return speakers_launch(m, m->n_groups / parties, parties, d_src, srcU8Len, conf_stride, source_stride, nullptr, nullptr, d_mute, max_speakers,
+                           floor, decay_shift, d_mute_out, as_stream(stream));
+}
+
+// Over the layout: the table and the member list are what wmx_mix_set_conferences left on the device, and one launch visits the slots
+// of every size class (the kernel has no compile-time bound on the size).  The clear in front of it covers the idle rings and the
+// members of placeholders.
+int wmx_mix_select_speakers_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, long source_stride, const uint8_t *d_mute,
+                                 int max_speakers, uint32_t floor, int decay_shift, uint8_t *d_mute_out, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    const int rcc = speakers_check("wmx_mix_select_speakers_conf", m, d_src, srcU8Len, max_speakers, decay_shift, d_mute_out);
+    if (rcc) return rcc;
+    if (m->conf.n_conf < 1) {
+        set_error("wmx_mix_select_speakers_conf: no layout (wmx_mix_set_conferences)");
+        return WMX_EINVAL;
+    }
+    const int rcs = speakers_state(m);
+    if (rcs) return rcs;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(speakers_clear_kernel, dim3(stream_grid((size_t)m->n_groups, 256)), dim3(256), 0, s, m->d_speaking, d_mute_out, m->n_groups);
+    WMX_LAUNCH_CHECK();
+    return speakers_launch(m, m->conf.slots(), 0, d_src, srcU8Len, 0, source_stride, m->d_conf_tab, m->d_conf_members, d_mute, max_speakers, floor,
+                           decay_shift, d_mute_out, s);
+}
+
+int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m || (host_idx && n < 0)) return WMX_EINVAL;
+    for (int i = 0; host_idx && i < n; i++)
+        if (host_idx[i] < 0 || host_idx[i] >= m->n_groups) {
+            set_error("wmx_mix_reset_speakers: ring %d is outside the mixer's %d", (int)host_idx[i], m->n_groups);
+            return WMX_EINVAL;
+        }
+    const bool fresh = !m->d_env;
+    const int rcs = speakers_state(m);
+    if (rcs || fresh) return rcs;  // just made: zero already
+    hipStream_t s = as_stream(stream);
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(m->d_env, 0, (size_t)m->n_groups * sizeof(uint32_t), s));
+        return 0;
+    }
+    if (n == 0) return 0;
+    WMX_HIP(hipStreamSynchronize(s));  // a reset in flight may still read the list that is rewritten here
+    if ((size_t)n > m->reset_cap) {
+        if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
+        m->d_reset_idx = nullptr, m->reset_cap = 0;
+        WMX_HIP(hipMalloc(&m->d_reset_idx, (size_t)n * sizeof(int32_t)));
+        m->reset_cap = (size_t)n;
+    }
+    WMX_HIP(hipMemcpy(m->d_reset_idx, host_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((fill_rows_idx<uint32_t>), dim3(stream_grid((size_t)n * 64, 64)), dim3(64), 0, s, m->d_env, (const uint32_t *)nullptr, 1,
+                       (const int32_t *)m->d_reset_idx, n);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wmx_mix_export_speakers(const wmx_mix *m, uint32_t *host_env, uint8_t *host_speaking, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    const size_t n = (size_t)m->n_groups;
+    if (!m->d_env) {  // no selection has run on this mixer
+        if (host_env) memset(host_env, 0, n * sizeof(uint32_t));
+        if (host_speaking) memset(host_speaking, 0, n);
+        return 0;
+    }
+    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+    if (host_env) WMX_HIP(hipMemcpy(host_env, m->d_env, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (host_speaking) WMX_HIP(hipMemcpy(host_speaking, m->d_speaking, n, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // the play thread's drain (src/wmix.c:1347-1366): read `bytes` at the ring head into d_out (per group), zero what

@@ -39,6 +39,9 @@ struct wmx_tick {
     std::vector<uint32_t> conf_head, conf_tick;  // one cursor per conference index
     uint8_t *d_mute = nullptr;                   // [n_groups] muted participants; nullptr = nobody
     std::vector<uint8_t> h_mute;                 // what the upload in flight reads
+    int spk_max = 0, spk_shift = 0;              // wmx_tick_bridge_speakers: the loudest spk_max legs of a conference are loaded; 0 = off
+    uint32_t spk_floor = 0;
+    uint8_t *d_spk_mute = nullptr;               // [n_groups] the selection's mask, the bridge load's d_mute while it is on
 };
 
 extern "C" {
@@ -53,6 +56,7 @@ int wmx_tick_destroy(wmx_tick *h) {
     if (h->d_play) (void)hipFree(h->d_play);
     if (h->d_far) (void)hipFree(h->d_far);
     if (h->d_mute) (void)hipFree(h->d_mute);
+    if (h->d_spk_mute) (void)hipFree(h->d_spk_mute);
     delete h;
     return 0;
 }
@@ -201,6 +205,27 @@ int wmx_tick_bridge_mute(wmx_tick *h, const uint8_t *host_mask, void *stream) {
     return 0;
 }
 
+// Talker selection (include/wmix_amd.h, speakers.h): while on and a bridge form is on, wmx_tick_record puts wmx_mix_select_speakers /
+// _conf between the chain and the bridge load.  Off leaves the envelopes as they are.
+int wmx_tick_bridge_speakers(wmx_tick *h, int max_speakers, uint32_t floor, int decay_shift) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (max_speakers < 0 || max_speakers > WMX_MIX_MAX_PARTIES || decay_shift < 0 || decay_shift > 31) {
+        wmx::set_error("wmx_tick_bridge_speakers: max_speakers=%d must be 0 .. %d and decay_shift=%d 0 .. 31", max_speakers, WMX_MIX_MAX_PARTIES,
+                       decay_shift);
+        return WMX_EINVAL;
+    }
+    if (max_speakers && !h->d_spk_mute) WMX_HIP(hipMalloc(&h->d_spk_mute, (size_t)h->n_groups));
+    h->spk_max = max_speakers;
+    h->spk_floor = floor;
+    h->spk_shift = decay_shift;
+    return 0;
+}
+
+int wmx_tick_bridge_speaking(wmx_tick *h, uint8_t *host_speaking, uint32_t *host_env, void *stream) {
+    return h ? wmx_mix_export_speakers(h->mix, host_env, host_speaking, stream) : WMX_EINVAL;
+}
+
 // webrtcEnable[WR_NS_PA] (src/wmix.c:1370-1386): the played package goes through ns_process on its way out -- BEFORE playPkgBuff_add,
 // so the echo cancellers hear the suppressed playback too.  on = 1: ns_init of one suppressor per group (the switch coming on);
 // on = 0: ns_release.
@@ -278,13 +303,24 @@ int wmx_tick_record(wmx_tick *h, int16_t *d_rec, long rec_stride, int16_t *d_rec
                           &h->rw_tick, stream);
         if (rc != 0) return rc;
     }
+    const uint8_t *load_mute = h->d_mute;
+    if (h->spk_max && (h->bridge || h->conf_on)) {  // who is loaded this tick: decided on the chain's output, where it lies
+        if (h->bridge)
+            rc = wmx_mix_select_speakers(h->mix, h->bridge, d_rec, (uint32_t)h->pkg * 2, (long)h->bridge * rec_stride, rec_stride, h->d_mute,
+                                         h->spk_max, h->spk_floor, h->spk_shift, h->d_spk_mute, stream);
+        else
+            rc = wmx_mix_select_speakers_conf(h->mix, d_rec, (uint32_t)h->pkg * 2, rec_stride, h->d_mute, h->spk_max, h->spk_floor, h->spk_shift,
+                                              h->d_spk_mute, stream);
+        if (rc != 0) return rc;
+        load_mute = h->d_spk_mute;
+    }
     if (h->bridge) {  // every leg's output into the rings of the other legs of its conference
         rc = wmx_mix_load_minus(h->mix, h->bridge, d_rec, (uint32_t)h->pkg * 2, h->freq, h->chn, 16, (long)h->bridge * rec_stride, rec_stride,
-                                h->d_mute, 1, &h->br_head, &h->br_tick, stream);
+                                load_mute, 1, &h->br_head, &h->br_tick, stream);
         if (rc != 0) return rc;
     }
     if (h->conf_on) {  // the same over the layout, every conference from its own cursor
-        rc = wmx_mix_load_minus_conf(h->mix, d_rec, (uint32_t)h->pkg * 2, h->freq, h->chn, 16, rec_stride, h->d_mute, 1, h->conf_head.data(),
+        rc = wmx_mix_load_minus_conf(h->mix, d_rec, (uint32_t)h->pkg * 2, h->freq, h->chn, 16, rec_stride, load_mute, 1, h->conf_head.data(),
                                      h->conf_tick.data(), stream);
         if (rc != 0) return rc;
     }

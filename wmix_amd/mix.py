@@ -101,6 +101,49 @@ class MixBatch:
                                             torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus_conf")
         return h, t
 
+    def _mute_pair(self, mute, out):
+        if mute is not None:
+            assert mute.is_cuda and mute.dtype == torch.uint8 and mute.is_contiguous() and mute.numel() == self.n_groups
+        if out is None:
+            out = torch.empty(self.n_groups, dtype=torch.uint8, device="cuda")
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == self.n_groups
+        return mute.data_ptr() if mute is not None else None, out
+
+    def select_speakers(self, src, parties, src_bytes, max_speakers, floor=0, decay_shift=3, mute=None, out=None):
+        """Talker selection in front of load_minus (wmx_mix_select_speakers): of every conference only the loudest max_speakers legs stay
+        un-muted.  src as for load_minus; mute: the host's mute, None or uint8 CUDA [n_groups]; out: uint8 CUDA [n_groups] to write (made
+        when None).  Returns the mask to pass to load_minus as `mute`."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.dim() == 3 and src.stride(2) == 1
+        assert src.shape[1] == parties and src.shape[0] * parties == self.n_groups
+        mp, out = self._mute_pair(mute, out)
+        check(lib().wmx_mix_select_speakers(self._h, parties, src.data_ptr(), src_bytes, src.stride(0), src.stride(1), mp, max_speakers, floor,
+                                            decay_shift, out.data_ptr(), torch.cuda.current_stream().cuda_stream), "wmx_mix_select_speakers")
+        return out
+
+    def select_speakers_conf(self, src, src_bytes, max_speakers, floor=0, decay_shift=3, mute=None, out=None):
+        """The same over the layout (wmx_mix_select_speakers_conf), in front of load_minus_conf: src [n_groups, >= src_bytes / 2], row r =
+        the source of ring r.  Rings outside every conference of two or more members come out muted."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.dim() == 2 and src.stride(1) == 1 and src.shape[0] == self.n_groups
+        mp, out = self._mute_pair(mute, out)
+        check(lib().wmx_mix_select_speakers_conf(self._h, src.data_ptr(), src_bytes, src.stride(0), mp, max_speakers, floor, decay_shift,
+                                                 out.data_ptr(), torch.cuda.current_stream().cuda_stream), "wmx_mix_select_speakers_conf")
+        return out
+
+    def reset_speakers(self, rings=None):
+        """env = 0 for the listed rings (None = every ring): what a new call in a reused slot does"""
+        idx = None if rings is None else np.ascontiguousarray(rings, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_mix_reset_speakers(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                           torch.cuda.current_stream().cuda_stream), "wmx_mix_reset_speakers")
+
+    def export_speakers(self):
+        """(speaking uint8 [n_groups], env uint32 [n_groups]) as the work queued on the current stream leaves them"""
+        env, speaking = np.zeros(self.n_groups, np.uint32), np.zeros(self.n_groups, np.uint8)
+        check(lib().wmx_mix_export_speakers(self._h, env.ctypes.data, speaking.ctypes.data, torch.cuda.current_stream().cuda_stream),
+              "wmx_mix_export_speakers")
+        return speaking, env
+
     def drain(self, n_bytes):
         out = torch.empty(self.n_groups, n_bytes // 2, dtype=torch.int16, device="cuda")
         check(lib().wmx_mix_drain(self._h, out.data_ptr(), n_bytes, out.stride(0), torch.cuda.current_stream().cuda_stream), "wmx_mix_drain")

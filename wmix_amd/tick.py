@@ -91,6 +91,19 @@ class TickBatch:
         check(lib().wmx_tick_bridge_mute(self._h, m.ctypes.data if m is not None else None, torch.cuda.current_stream().cuda_stream),
               "wmx_tick_bridge_mute")
 
+    def bridge_speakers(self, max_speakers, floor=0, decay_shift=3):
+        """Talker selection (wmx_tick_bridge_speakers): while a bridge form is on, record() loads only the loudest max_speakers legs of
+        every conference, chosen on the device from this tick's chain output (MixBatch.select_speakers).  0 switches it off."""
+        check(lib().wmx_tick_bridge_speakers(self._h, int(max_speakers), int(floor), int(decay_shift)), "wmx_tick_bridge_speakers")
+
+    def bridge_speaking(self):
+        """(speaking uint8 [n_groups], env uint32 [n_groups]) of the last record(): who was loaded, and every leg's envelope"""
+        import numpy as np
+        speaking, env = np.zeros(self.n_groups, np.uint8), np.zeros(self.n_groups, np.uint32)
+        check(lib().wmx_tick_bridge_speaking(self._h, speaking.ctypes.data, env.ctypes.data, torch.cuda.current_stream().cuda_stream),
+              "wmx_tick_bridge_speaking")
+        return speaking, env
+
     def play(self, play=None):
         """The play side of one package; returns the groups' far-end packages (a VIEW of the handle's own [n_groups, pkg] rows:
         valid until the next play)."""
