@@ -742,6 +742,9 @@ int wmx_debug_fft(int kind, int n_batch, void *d_data, int32_t *d_aux, void *str
 /* Developer / test hook: the NS kernels' table-driven log (kind 0, x >= 1) and exp (kind 1) evaluated on the host from
  * the same source (wmix_amd/csrc/libm_dev.h), for sweeping against libm without a GPU. */
 int wmx_debug_ns_libm(int kind, const float *x, float *y, size_t n);
+/* Developer / test hook: the float NS kernel's analysis window for L = 128 (8 kHz) or 256 (16 / 32 kHz) as its constants block holds
+ * it, L floats to a HOST buffer; needs no device. */
+int wmx_debug_ns_window(int L, float *host_window);
 /* Developer / test hook: the NS kernels' division for ordinary operands (wmix_amd/csrc/libm_dev.h div_ordinary: the
  * compiler's own fp32 division sequence without its rescaling and special-case instructions) beside `a / b`, on the device
  * (device pointers) and compiled for the host. */

@@ -15,5 +15,5 @@ for k in range(nf):
     if k==nf-8: f(buf,1)
     nb.process_packet_major(d[k:k+1])
 f(buf,0); v=np.array(buf[:14],dtype=np.float64)
-names=['load+window+energy1','fft fwd','spectrum+log','7 sums','noise est (quantiles)','startup/snr loop','3 sums+flat','lrt loop (log)','ksum+prior+exp loop','noise update+wiener','ifft','td+energy2','synth+hb','output']
+names=['load+window+zero gate','fft fwd','spectrum+log','6 sums','noise est (quantiles)','startup/snr loop+lrt loop (log)','4 sums+flat','features+histograms','prior+exp loop','noise update+wiener','ifft','td','2 energies+synth+hb','output']
 for n,x in zip(names,v): print('%-24s %8.1f Mcyc %5.1f%%'%(n,x/1e6,100*x/v.sum()))

@@ -243,21 +243,26 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             if (chn == 2) ST(Y::HB_BUF + i) = hb[k];
         }
     }
-    // window + energy (ns_core.c:1071-1072 / 1241-1242)
+    // window + energy (ns_core.c:1071-1072 / 1241-1242).  The frame's energy is used twice: `== 0` gates the frame, and the sum itself
+    // scales the output once block_ind is past kStartupLong.  The sum of non-negative finite terms from +0 is zero exactly when every
+    // term is (no term underflows: the smallest non-zero window[i]^2 is a normal float, tests/test_ns_window_terms.py, and a non-zero
+    // int16 sample is at least 1), so the gate is a ballot over the terms, and the terms wait in registers for the one place that
+    // needs their ordered sum, where they run beside the output energy's as a second lane chain.
+    float e1[NT];
+    bool any_term = false;
 #pragma unroll
     for (int k = 0; k < NT; k++) {
         const int i = lane + 64 * k;
         const float w = K.window[i] * buf[k];
         W.fa[i] = w;
-        tdst[i] = w * w;
+        e1[k] = w * w;
+        any_term |= e1[k] != 0.0f;
     }
-    wave_sync();
-    const float energy1 = sum_range(tdst, 0, L, lane);
     wave_sync();
     NS_PROF(0);
 
     float hb_gain = 1.f;
-    const bool zero_frame = (energy1 == 0.0f);
+    const bool zero_frame = __builtin_amdgcn_ballot_w64(any_term) == 0;
     float t_re[(Y::M + 63) / 64], t_im[(Y::M + 63) / 64], t_prev[(Y::M + 63) / 64], t_snrq[(Y::M + 63) / 64];
 
     if (!zero_frame) {
@@ -270,7 +275,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 
         NS_RELANE();
         rdft_forward<NC>(W.fa, &K.tab, lane);
-        if (lane < Y::MP - M) W.r0[M + lane] = 0.f;  // the window-energy stage above spilled into r0's zero tail
+        if (lane < Y::MP - M) W.r0[M + lane] = 0.f;  // the previous frame's time-domain stages (tdst) spilled into r0's zero tail
         NS_PROF(1);
 
         NS_RELANE();
@@ -312,15 +317,19 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         wave_sync();
         NS_PROF(2);
         // ordered reductions over the bins (ns_core.c:1089-1101, :540, :608)
-        float signal_energy, sum_magn, flat_num, avg_pause, sum_log_magn = 0.f, sum_log_i_log_magn = 0.f;
+        float signal_energy, sum_magn, avg_magn, flat_mean, avg_pause, sum_log_magn = 0.f, sum_log_i_log_magn = 0.f;
         {
             const float *mine =
                 lane == 1 ? W.magn : (lane == 2 ? W.r2 : (lane == 3 ? W.pause : (lane == 4 ? W.snrp : (lane == 5 ? W.r1 : W.r0))));
             const float acc = sum_lanes<Y::MP / 4>(mine);
-            signal_energy = lane_value(acc, 0);
+            // the four divisions by M the frame makes of these sums, each in its own lane: one division sequence for the wave
+            // instead of one per wave-uniform quotient (same operands, same operation)
+            const float mean = acc / ((float)M);
+            signal_energy = lane_value(mean, 0);
             sum_magn = lane_value(acc, 1);
-            flat_num = lane_value(acc, 2);
-            avg_pause = lane_value(acc, 3);
+            avg_magn = lane_value(mean, 1);
+            flat_mean = lane_value(mean, 2);
+            avg_pause = lane_value(mean, 3);
             if (startup) {
                 sum_log_magn = lane_value(acc, 4);
                 sum_log_i_log_magn = lane_value(acc, 5);
@@ -329,7 +338,6 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         const float magn0 = W.magn[0];
         wave_sync();
         NS_PROF(3);
-        signal_energy = signal_energy / ((float)M);
 
         NS_RELANE();
         // ---- NoiseEstimation (ns_core.c:217-285)
@@ -393,7 +401,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         NS_PROF(4);
         // ---- start-up white/pink parametric noise model (ns_core.c:1108-1160); parametricNoise kept in r1
         if (startup) {
-            const float white = SCF(S_WHITE) + sum_magn / ((float)M) * overdrive;
+            const float white = SCF(S_WHITE) + avg_magn * overdrive;
             ST(Y::S_WHITE) = white;
             const float sum_log_i = K.logi[Y::MP - 2], sum_log_i_sq = K.logi[Y::MP - 1];
             float t1 = sum_log_i_sq * ((float)(M - kStartBand));
@@ -445,8 +453,6 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         NS_RELANE();
         // ---- ComputeSnr (ns_core.c:566-588); prev is reused by the Wiener filter (:996).  Same loop: the terms of
         //      the spectral-difference sums (ns_core.c:612-620), which need avg_pause / avg_magn only.
-        avg_pause = avg_pause / ((float)M);
-        const float avg_magn = sum_magn / ((float)M);
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int b0 = lane + 64 * k;
@@ -463,10 +469,28 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             t_prev[k] = pe;
             t_snrq[k] = sq;
             if (!ok) continue;
-            W.snrp[b] = 0.98f * pe + (1.f - 0.98f) * sq;
             W.r0[b] = dm * dp;
             W.r2[b] = dp * dp;
             W.lmagn[b] = dm * dm;  // lmagn is dead from here on
+        }
+        // ---- the per-bin average of the log likelihood ratio (SpeechNoiseProb, ns_core.c:642-749).  It needs the two SNR
+        //      estimates and nothing FeatureUpdate writes, so it runs here, where its ordered sum can join the three of
+        //      FeatureUpdate as a fourth lane chain.  sprob is free until the speech probability itself is written.
+#pragma unroll
+        for (int k = 0; k < NI; k++) {
+            const int b0 = lane + 64 * k;
+            const bool ok = (64 * k + 63 < M) || b0 < M;  // see the noise estimation loop
+            const int b = ok ? b0 : M - 1;
+            // the prior SNR (ComputeSnr, ns_core.c:566-588): only this lane's bin is needed, so a register and not an LDS array
+            const float sp = 0.98f * t_prev[k] + (1.f - 0.98f) * t_snrq[k];
+            const float t1 = 1.f + 2.f * sp;
+            const float t2 = div_ordinary(2.f * sp, t1 + 0.0001f);  // 0 <= sp < 2^38 (a magnitude over a denominator >= 1e-4), t1 >= 1
+            const float bessel = (t_snrq[k] + 1.f) * t2;
+            float v = pf_lrt[k];
+            v += 0.5f * (bessel - fast_log_ge1(t1, K.lm) - v);
+            if (!ok) continue;
+            ST(Y::LOG_LRT + b) = v;
+            W.sprob[b] = v;
         }
         wave_sync();
         NS_PROF(5);
@@ -476,22 +500,20 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             float den = sum_magn;
             den -= magn0;
             den = den / (float)M;
-            const float num = flat_num / (float)M;
-            const float tmp = fast_exp(num, K.lm) / den;
+            const float tmp = fast_exp(flat_mean, K.lm) / den;
             feat_flat += 0.3f * (tmp - feat_flat);
         }
-        float cov, var_pause, var_magn;
+        float cov, var_pause, var_magn, ksum;
         {
-            const float acc = sum_lanes<Y::MP / 4>(lane == 1 ? W.r2 : (lane == 2 ? W.lmagn : W.r0));
-            cov = lane_value(acc, 0);
-            var_pause = lane_value(acc, 1);
-            var_magn = lane_value(acc, 2);
+            const float acc = sum_lanes<Y::MP / 4>(lane == 1 ? W.r2 : (lane == 2 ? W.lmagn : (lane == 3 ? W.sprob : W.r0)));
+            const float mean = acc / ((float)M);  // one division sequence, as above
+            cov = lane_value(mean, 0);
+            var_pause = lane_value(mean, 1);
+            var_magn = lane_value(mean, 2);
+            ksum = lane_value(mean, 3);
         }
         wave_sync();
         NS_PROF(6);
-        cov = cov / ((float)M);
-        var_pause = var_pause / ((float)M);
-        var_magn = var_magn / ((float)M);
         float feat_acc = SCF(S_FEAT_ACC) + signal_energy;
         float feat_diff = SCF(S_FEAT_DIFF);
         {
@@ -662,26 +684,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         ST(Y::S_FEAT_ACC) = feat_acc;
 
         NS_RELANE();
-        // ---- SpeechNoiseProb (ns_core.c:642-749)
-#pragma unroll
-        for (int k = 0; k < NI; k++) {
-            const int b0 = lane + 64 * k;
-            const bool ok = (64 * k + 63 < M) || b0 < M;  // see the noise estimation loop
-            const int b = ok ? b0 : M - 1;
-            const float sp = W.snrp[b];
-            const float t1 = 1.f + 2.f * sp;
-            const float t2 = div_ordinary(2.f * sp, t1 + 0.0001f);  // 0 <= sp < 2^38 (a magnitude over a denominator >= 1e-4), t1 >= 1
-            const float bessel = (t_snrq[k] + 1.f) * t2;
-            float v = pf_lrt[k];
-            v += 0.5f * (bessel - fast_log_ge1(t1, K.lm) - v);
-            if (!ok) continue;
-            ST(Y::LOG_LRT + b) = v;
-            W.r0[b] = v;
-        }
-        wave_sync();
         NS_PROF(7);
-        float ksum = sum_range(W.r0, 0, M, lane);
-        ksum = ksum / (float)(M);
+        // ---- SpeechNoiseProb (ns_core.c:642-749); its per-bin loop and the sum of its terms ran with the feature sums above
         feat_lrt = ksum;
         ST(Y::S_FEAT_LRT) = feat_lrt;
         float prior = SCF(S_PRIOR);
@@ -712,7 +716,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             const int b0 = lane + 64 * k;
             const bool ok = (64 * k + 63 < M) || b0 < M;
             const int b = ok ? b0 : M - 1;
-            float inv = fast_exp(-W.r0[b], K.lm);
+            float inv = fast_exp(-W.sprob[b], K.lm);  // still the log likelihood ratio average of this bin
             inv = gain_prior * inv;
             const float spb = 1.f / (1.f + inv);
             if (ok) W.sprob[b] = spb;
@@ -798,7 +802,13 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         NS_PROF(11);
         float factor = 1.f;
         if (block_ind > kStartupLong) {  // gainmap == 1 for policy 2
-            const float energy2 = sum_range(tdst, 0, L, lane);
+            // the terms of the input energy go where the work array was (each lane has read its own elements of it above);
+            // then both energies in index order, lane 0 the output's and lane 1 the input's
+#pragma unroll
+            for (int k = 0; k < NT; k++) W.fa[lane + 64 * k] = e1[k];
+            wave_sync();
+            const float acc = sum_lanes<L / 4>(lane == 1 ? W.fa : tdst);
+            const float energy2 = lane_value(acc, 0), energy1 = lane_value(acc, 1);
             float gain = sqrtf(energy2 / (energy1 + 1.f));
             float factor1 = 1.f, factor2 = 1.f;
             if (gain > 0.5f) {
@@ -1190,5 +1200,18 @@ extern "C" int wmx_debug_ns_libm(int kind, const float *x, float *y, size_t n) {
     if (!x || !y || kind < 0 || kind > 2) return WMX_EINVAL;
     for (size_t i = 0; i < n; i++)
         y[i] = kind == 0 ? wmx::fast_log_ge1(x[i], tab) : (kind == 1 ? wmx::fast_exp(x[i], tab) : wmx::fast_tanh(x[i], tab));
+    return 0;
+}
+
+// The analysis window as the kernels hold it (the constants block wmx_ns_create uploads), on the host and without a device: L = 128
+// (8 kHz) or 256.  ns_frame's zero-frame gate rests on a property of these floats (tests/test_ns_window_terms.py).
+extern "C" int wmx_debug_ns_window(int L, float *host_window) {
+    if (!host_window || (L != 128 && L != 256)) return WMX_EINVAL;
+    std::vector<float> st, consts;
+    if (L == 128)
+        build_ns_template<128>(st, consts);
+    else
+        build_ns_template<256>(st, consts);
+    std::memcpy(host_window, consts.data() + wmx::kFftTableWords, sizeof(float) * L);
     return 0;
 }
