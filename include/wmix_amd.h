@@ -488,6 +488,39 @@ int wmx_mix_select_speakers_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU
                                  int max_speakers, uint32_t floor, int decay_shift, uint8_t *d_mute_out, void *stream);
 int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
 int wmx_mix_export_speakers(const wmx_mix *m, uint32_t *host_env, uint8_t *host_speaking, void *stream);
+/* The bridge load with a cursor per leg, for legs whose packets come early, late or not at all (an RTP leg delivers 0 .. 3 datagrams
+ * in a tick).  Every wmix_thread_rtp_recv_pcma keeps a cursor of its own and calls wmix_load_data once per datagram that arrived
+ * (src/wmixTask.c:1266-1316); here the mixer keeps one cursor (head, tick) per ring ON THE DEVICE, fresh (UINT32_MAX, 0) at first
+ * and after wmx_mix_reset_leg_cursors, and a tick brings up to max_packets packets per leg: packet k of ring r at d_src +
+ * r*source_stride + k*packet_stride (int16 elements), all of one format and one srcU8Len; wmx_mix_load's look-ahead note holds for
+ * every packet row.  d_len: n_groups x max_packets uint32 ON THE DEVICE; slot k of leg r is a call if and only if
+ * d_len[r*max_packets + k] == srcU8Len, any other value means the slot made no call, in the middle of a burst too.
+ * Over the layout in force (wmx_mix_set_conferences): for every conference of >= 2 members, every member q and every member s != q
+ * in list order, the ring of q afterwards holds what the reference's ring holds after wmix_load_data(packet k of s, &cursor of s)
+ * for the slots k that are calls, in slot order; every call starts where leg s's previous call ended, in this tick or an earlier
+ * one -- wmx_mix_load's cursor rule (a leg that fell behind the play head jumps to head + play_correct, one that runs ahead writes
+ * further ahead), formats, reduce rule and return values.  d_mute (NULL or n_groups bytes ON THE DEVICE, by ring): a muted leg's
+ * calls are made with zeros (WCT_SILENCE, src/wmixTask.c:1307-1309): its cursor moves, no ring changes.  A leg without a valid slot
+ * makes no call and its cursor stays, so it falls behind as the play head moves and jumps when it returns.  A ring in no conference,
+ * or in one of 0 or 1 members, keeps its cursor and receives nothing.
+ * The one departure from the reference: a call whose end cursor would lie more than one ring ahead of the mixer's tick is not made,
+ * nor are that leg's later slots of this tick (the reference laps the play head there and adds to what is queued); dropped[r] counts
+ * the calls left out.
+ * No host synchronisation, no upload and no allocation after the first call: one small kernel applies the cursor rule per leg
+ * (wmix_amd/csrc/leg_cursor.h), then at most one load launch per size class (<= 4, <= 8, <= 16, <= 32 members) that has a conference;
+ * every source element is read once.
+ * WMX_EINVAL, nothing launched, rings, layout and cursors unchanged: no layout in force, max_packets outside 1 ..
+ * WMX_MIX_MAX_LEG_PACKETS, a NULL d_src or d_len, max_packets packets that do not fit the ring, and whatever wmx_mix_load refuses about
+ * the format.
+ * wmx_mix_reset_leg_cursors: a fresh cursor and dropped = 0 for the n rings host_idx lists (NULL = every ring), on `stream`: what a
+ * new call in a reused slot does.  wmx_mix_export_leg_cursors: head, tick and dropped of every ring (n_groups entries each; any may
+ * be NULL) as the work queued on `stream` leaves them; blocking. */
+#define WMX_MIX_MAX_LEG_PACKETS 4
+int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
+                            long source_stride, long packet_stride, int max_packets, const uint32_t *d_len, const uint8_t *d_mute,
+                            int reduce, void *stream);
+int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
+int wmx_mix_export_leg_cursors(const wmx_mix *m, uint32_t *host_head, uint32_t *host_tick, uint32_t *host_dropped, void *stream);
 int wmx_mix_drain(wmx_mix *m, int16_t *d_out, uint32_t bytes, long out_stride, void *stream);
 int wmx_mix_export(const wmx_mix *m, int group, int16_t *host_ring, uint32_t *head_off, uint32_t *tick);
 
@@ -529,6 +562,18 @@ int wmx_rtp_egress(wmx_rtp *h, int in_chn, int in_freq, const int16_t *d_pcm, ui
                    int out_freq, uint8_t *d_packets, long packet_stride, uint32_t *packet_bytes, void *stream);
 int wmx_rtp_ingest(int n_streams, const uint8_t *d_packets, long packet_stride, int16_t *d_pcm, long pcm_stride,
                    uint32_t *d_pcm_bytes, uint16_t *d_seq_raw, void *stream);
+/* Ingest for legs that deliver up to max_packets datagrams in a tick, in front of wmx_mix_load_minus_legs: the receive loop's
+ * `ret > 0 && retSize > 0` (src/wmixTask.c:1278-1284) per datagram slot.  Datagram slot k of leg r at d_packets + r*leg_stride +
+ * k*packet_stride (bytes); d_recv_bytes: n_legs x max_packets int32 ON THE DEVICE, what recvfrom returned for the slot (<= 0 =
+ * nothing there, the row is not read).  PCM row of slot k of leg r at d_pcm + r*source_stride + k*pcm_packet_stride (int16
+ * elements).  Payload size by payload type and the decode are wmx_rtp_ingest's; d_len[r*max_packets + k] = 320 for a slot that is a
+ * call, 0 otherwise -- and then the slot's 160 PCM elements are zeroed, so a level taken over slot-0 rows is 0 for an absent leg.
+ * d_seq_raw (optional, n_legs x max_packets): as wmx_rtp_ingest leaves it for a slot where something arrived, 0 otherwise.
+ * WMX_EINVAL: a NULL d_packets, d_recv_bytes, d_pcm or d_len, max_packets outside 1 .. 4, rows that overlap (packet_stride < 172,
+ * pcm_packet_stride < 160, or a leg stride shorter than its max_packets rows). */
+int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride,
+                        const int32_t *d_recv_bytes, int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len,
+                        uint16_t *d_seq_raw, void *stream);
 int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timestamp);
 
 /* ------------------------------------------------------------------ the packet edge as a pipeline

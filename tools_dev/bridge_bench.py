@@ -26,7 +26,16 @@ the selection followed by the load it feeds (the load then skips the sources of 
 call is compared with numpy's ranking of the rows' levels before any time is reported; the sides alternate, device events around each.
 
     python tools_dev/bridge_bench.py --speakers 3 --out profiles/bridge/bridge_speakers_bench.json
-    python tools_dev/bridge_bench.py --speakers 3 --ragged --out profiles/bridge/bridge_speakers_ragged_bench.json"""
+    python tools_dev/bridge_bench.py --speakers 3 --ragged --out profiles/bridge/bridge_speakers_ragged_bench.json
+
+--legs measures the bridge load with a cursor per leg (wmx_mix_load_minus_legs) on the telephony mix of --ragged, beside
+wmx_mix_load_minus_conf on the same layout in the same run: (a) steady arrivals, one valid packet per leg and tick, max_packets 1 -- the
+rings of the first call are compared with the common-cursor load's before any time is reported; (b) a jittered script, max_packets 3
+(per leg and tick 1/4 nothing, 1/8 two at once, 1/8 two with an invalid slot between them, 1/2 one; a cycle of 16 ticks).  Every
+repetition moves every side's play head on by one package first (host state only, no launch), so that the legs' cursors neither run
+into the overrun bound nor fall behind for good.  The sides alternate, device events around each.
+
+    python tools_dev/bridge_bench.py --legs --out profiles/bridge/bridge_legs_bench.json"""
 import argparse
 import json
 import os
@@ -223,6 +232,60 @@ def telephony_against_padding(reps, freq=8000):
             "rings_fifo_rows_and_chain_streams_saved": padded - legs, "ring_bytes_saved": (padded - legs) * 2 * freq}
 
 
+def legs_against_conf(reps, freq=8000):
+    per = freq // 1000 * 20
+    sizes = telephony_sizes()
+    n_conf, legs = len(sizes), sum(sizes)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    layout = [list(range(off[c], off[c + 1])) for c in range(n_conf)]
+    g = torch.Generator(device="cuda").manual_seed(12)
+    src = torch.randint(-20000, 20000, (legs, 3, per), dtype=torch.int16, device="cuda", generator=g)
+    one = torch.full((legs, 1), per * 2, dtype=torch.int32, device="cuda")
+    u = torch.randint(0, 8, (16, legs), device="cuda", generator=g)
+    script = torch.zeros((16, legs, 3), dtype=torch.int32, device="cuda")
+    script[:, :, 0] = torch.where(u >= 2, per * 2, 0)
+    script[:, :, 1] = torch.where(u == 2, per * 2, torch.where(u == 3, per * 2 - 2, 0))
+    script[:, :, 2] = torch.where(u == 3, per * 2, 0)
+    mixers = {k: MixBatch(legs, 1, freq) for k in ("conf", "steady", "jitter")}
+    for m in mixers.values():
+        m.set_conferences(layout)
+        m.set(0, 0, 1)
+    # ---- steady arrivals from fresh cursors: the same rings as the common-cursor load?
+    cur = {"conf": mixers["conf"].load_minus_conf(src[:, 0], per * 2, freq, 1)}
+    mixers["steady"].load_minus_legs(src[:, :1], per * 2, freq, 1, one)
+    for c in sorted({0, 1, n_conf // 2, n_conf - 1}):
+        for q in range(sizes[c]):
+            a, b = mixers["conf"].export(int(off[c]) + q)[0], mixers["steady"].export(int(off[c]) + q)[0]
+            assert a.any() and np.array_equal(a, b), ("rings differ", c, q)
+    step = {k: 0 for k in mixers}
+
+    def play_on(k):  # the play thread's bookkeeping of one package, without its launch
+        step[k] += 1
+        mixers[k].set(step[k] * per * 2 % (2 * freq), step[k] * per * 2, 1)
+
+    def conf():
+        play_on("conf")
+        cur["conf"] = mixers["conf"].load_minus_conf(src[:, 0], per * 2, freq, 1, head=cur["conf"][0], tick=cur["conf"][1])
+
+    def steady():
+        play_on("steady")
+        mixers["steady"].load_minus_legs(src[:, :1], per * 2, freq, 1, one)
+
+    def jitter():
+        play_on("jitter")
+        mixers["jitter"].load_minus_legs(src, per * 2, freq, 1, script[step["jitter"] % 16])
+
+    t_conf, t_steady, t_jitter = alternate([conf, steady, jitter], reps)
+    dropped = {k: int(mixers[k].export_leg_cursors()[2].sum()) for k in ("steady", "jitter")}
+    for m in mixers.values():
+        m.close()
+    a, b, c = stats(t_conf), stats(t_steady), stats(t_jitter)
+    return {"conferences": n_conf, "sizes": {str(k): sizes.count(k) for k in sorted(set(sizes))}, "ring": "1x%d" % freq, "legs": legs,
+            "load_minus_conf": a, "legs_steady_max_packets_1": b, "legs_jitter_max_packets_3": c,
+            "packets_per_leg_and_tick_jitter": round(float((script == per * 2).sum()) / (16 * legs), 3), "calls_dropped": dropped,
+            "ratio_steady_over_conf": round(b["median_ms"] / a["median_ms"], 3), "ratio_jitter_over_conf": round(c["median_ms"] / a["median_ms"], 3)}
+
+
 def speakers_against_load(layout, P, n, freq, max_speakers, reps, what):
     """layout: None = the uniform form with P consecutive legs per conference; else the list of conferences of the layout form"""
     per = freq // 1000 * 20
@@ -290,10 +353,16 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--ragged", action="store_true", help="the bridge over a layout: same legs both ways, a telephony mix against padding")
     ap.add_argument("--speakers", type=int, default=0, help="measure the talker selection with this max_speakers instead (uniform shapes, or --ragged)")
+    ap.add_argument("--legs", action="store_true", help="the bridge load with a cursor per leg beside wmx_mix_load_minus_conf, same layout")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
     res = {"tool": "bridge_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps, "load": [], "tick": None}
+    if args.legs:
+        res = {"tool": "bridge_bench --legs", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+               "runs": "the builder's own, one process, the sides alternating", "legs": legs_against_conf(args.reps)}
+        args.sizes = args.tick = ""
+        args.ragged, args.speakers = False, 0
     if args.speakers:
         res = {"tool": "bridge_bench --speakers %d%s" % (args.speakers, " --ragged" if args.ragged else ""), "device": torch.cuda.get_device_name(0),
                "reps": args.reps, "runs": "the builder's own, one process, the sides alternating", "speakers": []}

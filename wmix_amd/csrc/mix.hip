@@ -21,6 +21,7 @@
 #include "mix_minus.h"
 #include "bridge_layout.h"
 #include "speakers.h"
+#include "leg_cursor.h"
 
 namespace wmx {
 namespace {
@@ -267,6 +268,143 @@ __global__ __launch_bounds__(256) void select_speakers_kernel(const int16_t *__r
     }
 }
 
+// ---- a cursor per leg (leg_cursor.h)
+// What the cursor kernel leaves for the load kernels.  Per ring: where the calls its leg makes in this launch start (a ring sample,
+// reduced into the ring), how many ring samples they cover (0: none, or muted), and the slot each came from.  Per layout slot: the
+// conference's window, from the earliest start to the latest end among its members, relative to the play head.
+struct LegSpanEntry {
+    uint32_t start, len, slots, pad;
+};
+
+// One wave = one conference of the layout, lane p = member p (select_speakers_kernel's dealing).  The lane reads which of its leg's
+// slots are calls (d_len), applies the rule (at most WMX_MIX_MAX_LEG_PACKETS steps) and writes the span, the new cursor and the drop
+// count; an xor-shuffle over the wave gives the window.  Rings outside every conference of two or more members are not visited:
+// their cursors stay.  A cursor read from memory never indexes anything as it is: the span's start is reduced into the ring here.
+__global__ __launch_bounds__(256) void leg_cursor_kernel(const int32_t *__restrict__ tab, const int32_t *__restrict__ members,
+                                                         const uint32_t *__restrict__ len, uint32_t srcU8Len, int max_packets,
+                                                         const uint8_t *__restrict__ mute, LegMixState ms, uint32_t n_out,
+                                                         uint32_t *__restrict__ head, uint32_t *__restrict__ tick,
+                                                         uint32_t *__restrict__ dropped, LegSpanEntry *__restrict__ span,
+                                                         uint2 *__restrict__ win, int n_groups, int n_slots) {
+    const int lane = (int)(threadIdx.x & 63u), waves = (int)(blockDim.x >> 6);
+    const uint32_t ring_samples = ms.ring_bytes / 2, head_sample = (ms.head_off / 2) % ring_samples;
+    for (int w = (int)blockIdx.x * waves + (int)(threadIdx.x >> 6); w < n_slots; w += (int)gridDim.x * waves) {
+        const int slot = __builtin_amdgcn_readfirstlane(w);
+        const int32_t *mem = members + tab[2 * (size_t)slot];
+        int n = tab[2 * (size_t)slot + 1];
+        n = n < 0 ? 0 : (n > kBridgeMaxParties ? kBridgeMaxParties : n);
+        uint32_t lo = UINT32_MAX, hi = 0;  // the window in samples behind the play head: [lo, hi)
+        if (lane < n) {
+            const int32_t r = mem[lane];
+            if (r >= 0 && r < n_groups) {
+                uint32_t valid = 0;
+                for (int k = 0; k < kLegMaxPackets; k++)
+                    if (k < max_packets && len[(size_t)r * max_packets + k] == srcU8Len) valid |= 1u << k;
+                if (valid) {
+                    const LegSpan s = leg_cursor_span(ms, n_out, LegCursor{head[r], tick[r]}, valid, max_packets);
+                    head[r] = s.after.head;
+                    tick[r] = s.after.tick;
+                    if (s.dropped) dropped[r] += s.dropped;
+                    LegSpanEntry e{(s.start / 2) % ring_samples, (mute && mute[r]) ? 0u : s.count * n_out, s.slots, 0u};
+                    span[r] = e;
+                    if (e.len) {
+                        lo = e.start >= head_sample ? e.start - head_sample : e.start + ring_samples - head_sample;
+                        hi = lo + e.len;
+                    }
+                } else {
+                    span[r] = LegSpanEntry{0u, 0u, 0u, 0u};
+                }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t l2 = (uint32_t)__shfl_xor((int)lo, o), h2 = (uint32_t)__shfl_xor((int)hi, o);
+            lo = l2 < lo ? l2 : lo;
+            hi = h2 > hi ? h2 : hi;
+        }
+        if (lane == 0) {
+            uint32_t wlen = hi > lo ? hi - lo : 0u;
+            if (wlen > ring_samples) wlen = ring_samples;  // every ring column once
+            uint32_t wstart = wlen ? head_sample + lo : 0u;
+            wstart -= wstart >= ring_samples ? ring_samples : 0u;
+            win[slot] = make_uint2(wstart, wlen);
+        }
+    }
+}
+
+// The bridge load with a cursor per leg: load_minus_conf_kernel's two sweeps, with each source's value looked up through its
+// span.  One thread = one ring column of one conference of this size class; the columns are those of the conference's window.  A
+// slot is dealt n_pad columns (whole waves, so the slot is wave-uniform and its table entry, window, member indices and spans are
+// scalar loads); a window longer than that is walked in strides of n_pad, a wave whose first column lies behind the window's end
+// exits.  A source whose span does not cover the column adds 0, which is what not calling wmix_load_data leaves; a column no
+// source covers is not written.  A leg's span covers no ring sample twice (leg_cursor.h), a ring is in one conference only and a
+// column is one thread's: no two threads touch the same ring sample.
+template <int PMAX>
+__global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
+                                                              const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t n_pad,
+                                                              const int32_t *__restrict__ tab, const uint2 *__restrict__ win,
+                                                              const LegSpanEntry *__restrict__ span, const int32_t *__restrict__ members,
+                                                              long source_stride, long packet_stride, int rdce, int n_groups, int n_slots) {
+    const size_t total = (size_t)n_pad * n_slots;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t / n_pad));
+        const uint2 w = win[slot];
+        const uint32_t wstart = w.x < ring_samples ? w.x : 0u, wlen = w.y < ring_samples ? w.y : ring_samples;
+        const int32_t *mem = members + tab[2 * (size_t)slot];
+        int n = tab[2 * (size_t)slot + 1];
+        n = n > PMAX ? PMAX : n;
+        for (uint32_t col = (uint32_t)(t % n_pad); col < wlen; col += n_pad) {
+            uint32_t pos = wstart + col;  // both < ring_samples
+            pos -= pos >= ring_samples ? ring_samples : 0u;
+            int c[PMAX], y[PMAX];
+            bool any = false;
+            ClampMap f = clamp_map_identity();
+#pragma unroll
+            for (int q = 0; q < PMAX; q++) {
+                c[q] = 0;
+                y[q] = 0;
+                if (q < n) {
+                    const int32_t ri = mem[q];
+                    const size_t r = (size_t)(ri >= 0 && ri < n_groups ? ri : 0);
+                    const LegSpanEntry e = span[r];
+                    const uint32_t st = e.start < ring_samples ? e.start : 0u;
+                    const uint32_t d = pos >= st ? pos - st : pos + ring_samples - st;
+                    if (d < e.len && d < (uint32_t)kLegMaxPackets * n_out) {
+                        const uint32_t j = (d >= n_out) + (d >= 2 * n_out) + (d >= 3 * n_out);  // the call, 0 .. 3, and its sample
+                        const uint32_t k = (e.slots >> (2u * j)) & 3u;
+                        c[q] = load_entry_value(src + r * source_stride + (size_t)k * packet_stride, sch[d - j * n_out], rdce);
+                        any = true;
+                    }
+                    y[q] = clamp_map_apply(f, rings[r * ring_samples + pos]);
+                    f = clamp_map_then_add(f, (int16_t)c[q]);
+                }
+            }
+            if (!any) continue;
+            ClampMap g = clamp_map_identity();
+#pragma unroll
+            for (int q = PMAX - 1; q >= 0; q--) {
+                if (q < n) {
+                    const int32_t ri = mem[q];
+                    const size_t r = (size_t)(ri >= 0 && ri < n_groups ? ri : 0);
+                    rings[r * ring_samples + pos] = clamp_map_apply(g, (int16_t)y[q]);
+                    g = clamp_map_add_then((int16_t)c[q], g);
+                }
+            }
+        }
+    }
+}
+
+// fresh cursors (leg_cursor_fresh) and no drops for the listed rings, or for every ring
+__global__ __launch_bounds__(256) void leg_reset_kernel(uint32_t *__restrict__ head, uint32_t *__restrict__ tick, uint32_t *__restrict__ dropped,
+                                                        const int32_t *__restrict__ idx, int n, int n_groups) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int r = idx ? idx[i] : i;
+        if (r < 0 || r >= n_groups) continue;
+        head[r] = UINT32_MAX;
+        tick[r] = 0;
+        dropped[r] = 0;
+    }
+}
+
 constexpr size_t kMappedMaxBytes = 64 * 1024;  // legacy staging (legacy_stage.h): above this the DMA engines win, the call is copied
 
 }  // namespace
@@ -304,6 +442,11 @@ struct wmx_mix {
     uint8_t *d_speaking = nullptr;
     int32_t *d_reset_idx = nullptr;
     size_t reset_cap = 0;
+    // a cursor per leg (leg_cursor.h): head, tick and the drop count of every ring, the span table and the windows the cursor kernel
+    // writes for the load kernels (one block, made by the first call that needs it)
+    uint32_t *d_leg_head = nullptr, *d_leg_tick = nullptr, *d_leg_dropped = nullptr;
+    wmx::LegSpanEntry *d_leg_span = nullptr;
+    uint2 *d_leg_win = nullptr;
 };
 
 // What wmx_mix_load and wmx_mix_load_minus share on the host: where the call starts (the reference's cursor rule), the schedule of
@@ -439,6 +582,7 @@ int wmx_mix_destroy(wmx_mix *m) {
     if (m->d_conf_lead) (void)hipFree(m->d_conf_lead);
     if (m->d_env) (void)hipFree(m->d_env);
     if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
+    if (m->d_leg_span) (void)hipFree(m->d_leg_span);
     delete m;
     return 0;
 }
@@ -651,6 +795,141 @@ int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
         WMX_LAUNCH_CHECK();
     }
     return n_out && m->conf.slots() ? m->sched.used(ent, s) : 0;
+}
+
+// ---- a cursor per leg (include/wmix_amd.h, leg_cursor.h)
+// the cursors (fresh), the drop counts (zero), the span table and the windows, from the first call that needs them on: one block,
+// the 16-byte span entries in front.  A layout has at most n_groups / 2 conferences that load.
+static int legs_state(wmx_mix *m) {
+    using namespace wmx;
+    if (m->d_leg_span) return 0;
+    const size_t n = (size_t)m->n_groups, n_win = n / 2 + 1;
+    const size_t bytes = n * sizeof(LegSpanEntry) + n_win * sizeof(uint2) + 3 * n * sizeof(uint32_t);
+    void *p = nullptr;
+    WMX_HIP(hipMalloc(&p, bytes));
+    LegSpanEntry *span = static_cast<LegSpanEntry *>(p);
+    uint2 *win = reinterpret_cast<uint2 *>(span + n);
+    uint32_t *head = reinterpret_cast<uint32_t *>(win + n_win);
+    hipError_t e = hipMemset(p, 0, bytes);
+    if (e == hipSuccess) e = hipMemset(head, 0xff, n * sizeof(uint32_t));  // UINT32_MAX: no cursor yet
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "hipMemset(leg cursors)", __FILE__, __LINE__);
+    }
+    m->d_leg_span = span;
+    m->d_leg_win = win;
+    m->d_leg_head = head;
+    m->d_leg_tick = head + n;
+    m->d_leg_dropped = head + 2 * n;
+    return 0;
+}
+
+// The bridge load with a cursor per leg: the cursor kernel (one wave per conference), then at most one load launch per non-empty size
+// class.  Which slots are calls is known on the device only, so nothing of the cursors passes through the host.
+int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, long source_stride,
+                            long packet_stride, int max_packets, const uint32_t *d_len, const uint8_t *d_mute, int reduce, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m || !d_src || !d_len) {
+        set_error("wmx_mix_load_minus_legs: bad argument");
+        return WMX_EINVAL;
+    }
+    if (m->conf.n_conf < 1) {
+        set_error("wmx_mix_load_minus_legs: no layout (wmx_mix_set_conferences)");
+        return WMX_EINVAL;
+    }
+    if (max_packets < 1 || max_packets > WMX_MIX_MAX_LEG_PACKETS) {
+        set_error("wmx_mix_load_minus_legs: max_packets=%d must be 1 .. %d", max_packets, WMX_MIX_MAX_LEG_PACKETS);
+        return WMX_EINVAL;
+    }
+    if (srcU8Len < 1) return 0;  // like wmx_mix_load
+    uint32_t h0 = 0, t0 = m->tick;  // a cursor the rule leaves alone keeps load_begin to the schedule and wmx_mix_load's refusals
+    SchedCache::Entry *ent = nullptr;
+    const int rcb = load_begin(m, "wmx_mix_load_minus_legs", srcU8Len, freq, channels, sample, h0, t0, &ent);
+    if (rcb) return rcb;
+    const uint32_t n_out = (uint32_t)ent->n;
+    if ((uint64_t)n_out * (uint32_t)max_packets > m->ring_bytes / 2) {
+        set_error("wmx_mix_load_minus_legs: %d packets of %u output samples do not fit the %u-sample ring in one call", max_packets, n_out,
+                  m->ring_bytes / 2);
+        return WMX_EINVAL;
+    }
+    const int rcs = legs_state(m);
+    if (rcs) return rcs;
+    const int n_slots = m->conf.slots();
+    if (!n_out || !n_slots) return 0;
+    const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
+    hipStream_t s = as_stream(stream);
+    const LegMixState ms{m->head_off, m->tick, m->play_correct, m->ring_bytes};
+    hipLaunchKernelGGL(leg_cursor_kernel, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0, s, (const int32_t *)m->d_conf_tab,
+                       (const int32_t *)m->d_conf_members, d_len, srcU8Len, max_packets, d_mute, ms, n_out, m->d_leg_head, m->d_leg_tick,
+                       m->d_leg_dropped, m->d_leg_span, m->d_leg_win, m->n_groups, n_slots);
+    WMX_LAUNCH_CHECK();
+    // whole waves per conference, enough for the longest window of legs that write side by side; a longer one is walked in strides
+    const uint32_t n_pad = (n_out * (uint32_t)max_packets + 63) / 64 * 64;
+    for (int k = 0; k < kBridgeClasses; k++) {
+        const int first = m->conf.class_begin[k], n_class = m->conf.class_begin[k + 1] - first;
+        if (!n_class) continue;
+        const unsigned grid = stream_grid((size_t)n_pad * n_class, 256);
+        auto kernel = k == 0 ? load_minus_legs_kernel<4> : k == 1 ? load_minus_legs_kernel<8> : k == 2 ? load_minus_legs_kernel<16> : load_minus_legs_kernel<32>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out, n_pad,
+                           (const int32_t *)m->d_conf_tab + 2 * (size_t)first, (const uint2 *)m->d_leg_win + first,
+                           (const LegSpanEntry *)m->d_leg_span, (const int32_t *)m->d_conf_members, source_stride, packet_stride, rdce,
+                           m->n_groups, n_class);
+        WMX_LAUNCH_CHECK();
+    }
+    return m->sched.used(ent, s);
+}
+
+int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m || (host_idx && n < 0)) return WMX_EINVAL;
+    for (int i = 0; host_idx && i < n; i++)
+        if (host_idx[i] < 0 || host_idx[i] >= m->n_groups) {
+            set_error("wmx_mix_reset_leg_cursors: ring %d is outside the mixer's %d", (int)host_idx[i], m->n_groups);
+            return WMX_EINVAL;
+        }
+    const bool fresh = !m->d_leg_span;
+    const int rcs = legs_state(m);
+    if (rcs || fresh) return rcs;  // just made: fresh already
+    hipStream_t s = as_stream(stream);
+    if (host_idx && n == 0) return 0;
+    const int count = host_idx ? n : m->n_groups;
+    if (host_idx) {
+        WMX_HIP(hipStreamSynchronize(s));  // a reset in flight may still read the list that is rewritten here
+        if ((size_t)n > m->reset_cap) {
+            if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
+            m->d_reset_idx = nullptr, m->reset_cap = 0;
+            WMX_HIP(hipMalloc(&m->d_reset_idx, (size_t)n * sizeof(int32_t)));
+            m->reset_cap = (size_t)n;
+        }
+        WMX_HIP(hipMemcpy(m->d_reset_idx, host_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(leg_reset_kernel, dim3(stream_grid((size_t)count, 256)), dim3(256), 0, s, m->d_leg_head, m->d_leg_tick, m->d_leg_dropped,
+                       host_idx ? (const int32_t *)m->d_reset_idx : (const int32_t *)nullptr, count, m->n_groups);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wmx_mix_export_leg_cursors(const wmx_mix *m, uint32_t *host_head, uint32_t *host_tick, uint32_t *host_dropped, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    const size_t n = (size_t)m->n_groups;
+    if (!m->d_leg_span) {  // no leg has loaded on this mixer
+        for (size_t r = 0; r < n; r++) {
+            if (host_head) host_head[r] = UINT32_MAX;
+            if (host_tick) host_tick[r] = 0;
+            if (host_dropped) host_dropped[r] = 0;
+        }
+        return 0;
+    }
+    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+    if (host_head) WMX_HIP(hipMemcpy(host_head, m->d_leg_head, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (host_tick) WMX_HIP(hipMemcpy(host_tick, m->d_leg_tick, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (host_dropped) WMX_HIP(hipMemcpy(host_dropped, m->d_leg_dropped, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---- talker selection (include/wmix_amd.h, speakers.h)

@@ -125,6 +125,43 @@ __global__ __launch_bounds__(256) void rtp_egress_wide_kernel(const int16_t *__r
     }
 }
 
+// Ingest for legs that deliver 0 .. max_packets datagrams in a tick (wmx_rtp_ingest_legs): rtp_ingest_wide_kernel's four codes per
+// lane (WIDE: rows on 4 / 8-byte boundaries) or one code per lane, dealt over (leg, slot, piece).  A slot where nothing arrived
+// (recv_bytes <= 0: its datagram row is not read) or whose payload type is not G.711 made no call: len 0 and a zeroed PCM row.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void rtp_ingest_legs_kernel(const uint8_t *__restrict__ packets, long leg_stride, long packet_stride,
+                                                               const int32_t *__restrict__ recv_bytes, int16_t *pcm, long source_stride,
+                                                               long pcm_packet_stride, uint32_t *len, uint16_t *seq_raw, int max_packets,
+                                                               int n_legs) {
+    constexpr int kPieces = WIDE ? kRtpWords : kRtpG711Payload;
+    const size_t total = (size_t)n_legs * max_packets * kPieces;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t row = t / kPieces;  // leg * max_packets + slot
+        const int c = (int)(t - row * kPieces);
+        const size_t leg = row / (size_t)max_packets, k = row - leg * (size_t)max_packets;
+        const uint8_t *pkt = packets + leg * leg_stride + k * packet_stride;
+        int16_t *dst = pcm + leg * source_stride + k * pcm_packet_stride;
+        const bool there = recv_bytes[row] > 0;
+        const int pt = there ? pkt[1] & 0x7F : -1;
+        const bool g711 = pt == 8 || pt == 0;  // src/rtp.c:88-95
+        if (WIDE) {
+            uint2 o = make_uint2(0u, 0u);
+            if (g711) {
+                const uint32_t w = *reinterpret_cast<const uint32_t *>(pkt + kRtpHeader + 4 * c);
+                o.x = ((uint32_t)dec_alaw(w & 0xFF) & 0xFFFFu) | ((uint32_t)dec_alaw((w >> 8) & 0xFF) << 16);  // G711a2PCM whatever the pt
+                o.y = ((uint32_t)dec_alaw((w >> 16) & 0xFF) & 0xFFFFu) | ((uint32_t)dec_alaw(w >> 24) << 16);
+            }
+            *reinterpret_cast<uint2 *>(dst + 4 * c) = o;
+        } else {
+            dst[c] = g711 ? (int16_t)dec_alaw(pkt[kRtpHeader + c]) : (int16_t)0;
+        }
+        if (c == 0) {
+            len[row] = g711 ? (uint32_t)kRtpG711Payload * 2 : 0u;
+            if (seq_raw) seq_raw[row] = there ? (uint16_t)(pkt[2] | (pkt[3] << 8)) : (uint16_t)0;  // as stored: rtp_recv does not ntohs
+        }
+    }
+}
+
 inline bool aligned_to(const void *p, long stride_bytes, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0 && stride_bytes % a == 0; }
 
 }  // namespace
@@ -229,6 +266,27 @@ int wmx_rtp_ingest(int n_streams, const uint8_t *d_packets, long packet_stride, 
     else
         hipLaunchKernelGGL(rtp_ingest_kernel, dim3((unsigned)n_streams), dim3(64), 0, as_stream(stream), d_packets, packet_stride, d_pcm,
                            pcm_stride, d_pcm_bytes, d_seq_raw, n_streams);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride, const int32_t *d_recv_bytes,
+                        int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len, uint16_t *d_seq_raw, void *stream) {
+    if (n_legs < 0 || max_packets < 1 || max_packets > 4 || !d_packets || !d_recv_bytes || !d_pcm || !d_len ||
+        packet_stride < kRtpHeader + kRtpG711Payload || pcm_packet_stride < kRtpG711Payload ||
+        (n_legs > 1 && (leg_stride < packet_stride * max_packets || source_stride < pcm_packet_stride * max_packets))) {
+        set_error("wmx_rtp_ingest_legs: bad arguments");
+        return WMX_EINVAL;
+    }
+    if (n_legs == 0) return 0;
+    const size_t rows = (size_t)n_legs * max_packets;
+    if (aligned_to(d_packets, packet_stride, 4) && leg_stride % 4 == 0 && aligned_to(d_pcm, pcm_packet_stride * 2, 8) && (source_stride * 2) % 8 == 0)
+        hipLaunchKernelGGL((rtp_ingest_legs_kernel<true>), dim3(wmx::stream_grid(rows * kRtpWords, 256)), dim3(256), 0, as_stream(stream), d_packets,
+                           leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw, max_packets, n_legs);
+    else
+        hipLaunchKernelGGL((rtp_ingest_legs_kernel<false>), dim3(wmx::stream_grid(rows * kRtpG711Payload, 256)), dim3(256), 0, as_stream(stream),
+                           d_packets, leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw,
+                           max_packets, n_legs);
     WMX_LAUNCH_CHECK();
     return 0;
 }

@@ -101,6 +101,34 @@ class MixBatch:
                                             torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus_conf")
         return h, t
 
+    def load_minus_legs(self, src, src_bytes, freq, channels, lens, mute=None, reduce=1, sample=16):
+        """The bridge load with a cursor per leg (wmx_mix_load_minus_legs), over the layout in force: legs whose packets come early, late
+        or not at all.  src int16 CUDA [n_groups, max_packets, >= src_bytes/2 + look-ahead], packet k of ring r; lens uint32 (or
+        int32) CUDA [n_groups, max_packets]: slot k of leg r is a call if and only if lens[r, k] == src_bytes; mute: None or uint8
+        CUDA [n_groups] by ring (a muted leg's cursor moves, no ring changes).  The cursors live on the device: export_leg_cursors."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.dim() == 3 and src.stride(2) == 1 and src.shape[0] == self.n_groups
+        assert lens.is_cuda and lens.dtype in (torch.int32, torch.uint32) and lens.is_contiguous() and tuple(lens.shape) == tuple(src.shape[:2])
+        if mute is not None:
+            assert mute.is_cuda and mute.dtype == torch.uint8 and mute.is_contiguous() and mute.numel() == self.n_groups
+        check(lib().wmx_mix_load_minus_legs(self._h, src.data_ptr(), src_bytes, freq, channels, sample, src.stride(0), src.stride(1),
+                                            src.shape[1], lens.data_ptr(), mute.data_ptr() if mute is not None else None, reduce,
+                                            torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus_legs")
+
+    def reset_leg_cursors(self, rings=None):
+        """a fresh cursor and dropped = 0 for the listed rings (None = every ring): what a new call in a reused slot does"""
+        idx = None if rings is None else np.ascontiguousarray(rings, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_mix_reset_leg_cursors(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                              torch.cuda.current_stream().cuda_stream), "wmx_mix_reset_leg_cursors")
+
+    def export_leg_cursors(self):
+        """(head, tick, dropped), uint32 [n_groups] each, as the work queued on the current stream leaves them"""
+        h, t, d = (np.zeros(self.n_groups, np.uint32) for _ in range(3))
+        check(lib().wmx_mix_export_leg_cursors(self._h, h.ctypes.data, t.ctypes.data, d.ctypes.data, torch.cuda.current_stream().cuda_stream),
+              "wmx_mix_export_leg_cursors")
+        return h, t, d
+
     def _mute_pair(self, mute, out):
         if mute is not None:
             assert mute.is_cuda and mute.dtype == torch.uint8 and mute.is_contiguous() and mute.numel() == self.n_groups

@@ -56,3 +56,20 @@ def ingest(packets):
     check(lib().wmx_rtp_ingest(n, packets.data_ptr(), packets.stride(0), pcm.data_ptr(), pcm.stride(0), nbytes.data_ptr(), seq.data_ptr(),
                                torch.cuda.current_stream().cuda_stream), "wmx_rtp_ingest")
     return pcm, nbytes, seq
+
+
+def ingest_legs(packets, recv_bytes, look_ahead=0):
+    """Legs that deliver up to max_packets datagrams in a tick (wmx_rtp_ingest_legs), laid out for MixBatch.load_minus_legs.
+    packets uint8 CUDA [n_legs, max_packets, >= 172]; recv_bytes int32 CUDA [n_legs, max_packets], what recvfrom returned per slot
+    (<= 0: nothing there).  -> (pcm int16 [n_legs, max_packets, 160 + look_ahead], lens int32 [n_legs, max_packets] (320 or 0),
+    seq_raw int16 [n_legs, max_packets]); the PCM row of a slot that made no call is zero."""
+    assert packets.is_cuda and packets.dtype == torch.uint8 and packets.dim() == 3 and packets.stride(2) == 1
+    n, k = packets.shape[:2]
+    assert recv_bytes.is_cuda and recv_bytes.dtype == torch.int32 and recv_bytes.is_contiguous() and tuple(recv_bytes.shape) == (n, k)
+    pcm = torch.zeros((n, k, 160 + look_ahead), dtype=torch.int16, device=packets.device)
+    lens = torch.zeros((n, k), dtype=torch.int32, device=packets.device)
+    seq = torch.zeros((n, k), dtype=torch.int16, device=packets.device)
+    check(lib().wmx_rtp_ingest_legs(n, k, packets.data_ptr(), packets.stride(0), packets.stride(1), recv_bytes.data_ptr(), pcm.data_ptr(),
+                                    pcm.stride(0), pcm.stride(1), lens.data_ptr(), seq.data_ptr(), torch.cuda.current_stream().cuda_stream),
+          "wmx_rtp_ingest_legs")
+    return pcm, lens, seq
