@@ -1,0 +1,196 @@
+/* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
+ *
+ *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
+ *
+ * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
+ * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
+ * the slot, and reads the datagrams to send from the slot's out rows once it has left the device.  The rows of tick t + 1 are written
+ * while tick t is in flight (K slots, default 3; a slot is waited for only when its turn comes again).
+ * --sizes a,b,c: conferences of a, b, c consecutive legs; legs behind them are in no conference.  --speakers: talker selection.
+ * The network is the script of host_tick --bridge-rtp: one 64-bit LCG; per tick and leg u = next % 8 -- 0, 1: nothing arrives; 2: two
+ * datagrams in slots 0 and 1; 3: two in slots 0 and 2, recvfrom said -1 for slot 1; else one in slot 0 -- and per datagram that arrives
+ * v = next % 16 (0: payload type 96, not G.711; 1: PCMU; else PCMA), then 160 payload bytes next & 255; seq counts per leg.
+ * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
+#define _POSIX_C_SOURCE 200809L
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+#include "wmix_amd.h"
+
+#define RTP_SLOTS 3
+#define RTP_BYTES 172
+
+#define WMX_OK(call)                                                                         \
+    do {                                                                                     \
+        int rc_ = (call);                                                                    \
+        if (rc_ != 0) {                                                                      \
+            fprintf(stderr, "host_conf: %s = %d: %s\n", #call, rc_, wmx_last_error());       \
+            return 4;                                                                        \
+        }                                                                                    \
+    } while (0)
+
+static double now_ms(void) {
+    struct timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
+}
+
+static uint64_t lcg_state;
+static uint32_t lcg_next(void) {
+    lcg_state = lcg_state * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(lcg_state >> 33);
+}
+
+/* --sizes a,b,c: consecutive legs.  The list goes to the library as it stands: what is wrong with it is the library's to say */
+static int parse_sizes(const char *sizes, int32_t **off_out, int32_t **members_out) {
+    int n_conf = 0;
+    int32_t *conf_off = calloc(strlen(sizes) + 2, sizeof(int32_t));
+    if (!conf_off) return -1;
+    for (const char *p = sizes; *p;) {
+        char *end = NULL;
+        long v = strtol(p, &end, 10);
+        if (end == p || (*end && *end != ',') || v < 0 || v > 1000000) v = -1, end = (char *)p + strcspn(p, ","); /* not a size */
+        conf_off[n_conf + 1] = conf_off[n_conf] + (int32_t)v;
+        n_conf++;
+        p = *end ? end + 1 : end;
+    }
+    const int32_t total = conf_off[n_conf] > 0 ? conf_off[n_conf] : 0;
+    int32_t *conf_members = calloc((size_t)total + 1, sizeof(int32_t));
+    if (!conf_members) return -1;
+    for (int32_t r = 0; r < total; r++) conf_members[r] = r;
+    *off_out = conf_off, *members_out = conf_members;
+    return n_conf;
+}
+
+/* one tick of the network into a slot's rows */
+static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) {
+    long arrived = 0;
+    memset(in, 0xEE, (size_t)G * RTP_SLOTS * row);
+    for (int g = 0; g < G; g++) {
+        const uint32_t u = lcg_next() % 8;
+        int32_t *rv = recv + (size_t)g * RTP_SLOTS;
+        rv[0] = u >= 2 ? RTP_BYTES : 0;
+        rv[1] = u == 2 ? RTP_BYTES : (u == 3 ? -1 : 0);
+        rv[2] = u == 3 ? RTP_BYTES : 0;
+        for (int k = 0; k < RTP_SLOTS; k++) {
+            if (rv[k] <= 0) continue;
+            uint8_t *pk = in + ((size_t)g * RTP_SLOTS + k) * row;
+            const uint32_t v = lcg_next() % 16;
+            memset(pk, 0, 12);
+            pk[0] = 2u << 6;
+            pk[1] = (uint8_t)(0x80 | (v == 0 ? 96 : (v == 1 ? 0 : 8)));
+            pk[2] = (uint8_t)(seq[g] >> 8), pk[3] = (uint8_t)seq[g];
+            seq[g]++;
+            for (int i = 0; i < 160; i++) pk[12 + i] = (uint8_t)(lcg_next() & 255);
+            arrived++;
+        }
+    }
+    return arrived;
+}
+
+int main(int argc, char **argv) {
+    const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]\n";
+    if (argc < 4) {
+        fprintf(stderr, usage, argv[0]);
+        return 2;
+    }
+    const int G = atoi(argv[2]), T = atoi(argv[3]);
+    const char *sizes = NULL, *speakers = NULL, *platform = "alsa";
+    unsigned long seed = 0;
+    int slots = 3, have_seed = 0;
+    long correct = -1; /* -1: the library's default = platform/alsa */
+    for (int i = 4; i < argc; i++) {
+        if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
+            sizes = argv[++i];
+        } else if (!strcmp(argv[i], "--seed") && i + 1 < argc) {
+            seed = strtoul(argv[++i], NULL, 10), have_seed = 1;
+        } else if (!strcmp(argv[i], "--slots") && i + 1 < argc) {
+            slots = atoi(argv[++i]);
+        } else if (!strcmp(argv[i], "--speakers") && i + 1 < argc) {
+            speakers = argv[++i];
+        } else if (!strcmp(argv[i], "--platform") && i + 1 < argc) {
+            platform = argv[++i];
+            if (!strcmp(platform, "alsa")) {
+                correct = 3200;
+            } else if (!strcmp(platform, "hi3516") || !strcmp(platform, "t31")) {
+                correct = 0;
+            } else {
+                fprintf(stderr, "host_conf: no platform directory '%s' in the reference\n", platform);
+                return 2;
+            }
+        } else {
+            fprintf(stderr, "host_conf: what is '%s'?\n", argv[i]);
+            return 2;
+        }
+    }
+    if (!sizes || !have_seed) {
+        fprintf(stderr, "host_conf: --sizes and --seed are needed\n");
+        fprintf(stderr, usage, argv[0]);
+        return 2;
+    }
+    if (G < 1 || T < 1) return 2;
+    int max_speakers = 0, shift = 3;
+    unsigned long floor_level = 0;
+    if (speakers && sscanf(speakers, "%d,%lu,%d", &max_speakers, &floor_level, &shift) < 1) {
+        fprintf(stderr, "host_conf: --speakers N[,floor[,shift]]\n");
+        return 2;
+    }
+    int32_t *conf_off = NULL, *conf_members = NULL;
+    const int n_conf = parse_sizes(sizes, &conf_off, &conf_members);
+    if (n_conf < 0) return 2;
+
+    wmx_conf *h = NULL;
+    WMX_OK(wmx_conf_create(&h, G, slots, RTP_SLOTS, WMX_LAW_A));
+    if (correct >= 0) WMX_OK(wmx_conf_set_play_correct(h, (uint32_t)correct));
+    WMX_OK(wmx_conf_set_conferences(h, n_conf, conf_off, conf_members, NULL));
+    if (speakers) WMX_OK(wmx_conf_speakers(h, max_speakers, (uint32_t)floor_level, shift));
+    const int row = wmx_conf_in_row_bytes(h);
+    uint8_t *out = calloc((size_t)T * G * RTP_BYTES, 1);
+    uint16_t *seq = calloc((size_t)G, sizeof(uint16_t));
+    int *tick_of = malloc((size_t)slots * sizeof(int)); /* the tick whose datagrams a slot still owes, or -1 */
+    if (!out || !seq || !tick_of || row < RTP_BYTES) return 2;
+    for (int k = 0; k < slots; k++) tick_of[k] = -1;
+    lcg_state = seed;
+    long arrived = 0;
+    const double t0 = now_ms();
+#define COLLECT(k)                                                                                              \
+    do {                                                                                                        \
+        if (tick_of[k] >= 0) {                                                                                  \
+            WMX_OK(wmx_conf_wait(h, (k)));                                                                      \
+            memcpy(out + (size_t)tick_of[k] * G * RTP_BYTES, wmx_conf_out(h, (k)), (size_t)G * RTP_BYTES);      \
+            tick_of[k] = -1;                                                                                    \
+        }                                                                                                       \
+    } while (0)
+    arrived += arrivals(wmx_conf_in(h, 0), wmx_conf_recv(h, 0), row, seq, G);
+    for (int t = 0; t < T; t++) {
+        int k = -1;
+        WMX_OK(wmx_conf_submit(h, &k, NULL));
+        tick_of[k] = t;
+        if (t + 1 < T) { /* the network of tick t + 1 while tick t is in flight; that slot's own earlier tick has to have left first */
+            const int nk = wmx_conf_next_slot(h);
+            COLLECT(nk);
+            arrived += arrivals(wmx_conf_in(h, nk), wmx_conf_recv(h, nk), row, seq, G);
+        }
+    }
+    for (int k = 0; k < slots; k++) COLLECT(k);
+    const double wall = now_ms() - t0;
+    uint32_t *dropped = calloc((size_t)G, sizeof(uint32_t));
+    if (!dropped) return 2;
+    WMX_OK(wmx_conf_export_legs(h, NULL, NULL, dropped, NULL, NULL, NULL));
+    unsigned long n_dropped = 0;
+    for (int g = 0; g < G; g++) n_dropped += dropped[g];
+    uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
+    for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
+    wmx_conf_destroy(h);
+    FILE *f = fopen(argv[1], "wb");
+    int rc = (!f || fwrite(out, 1, (size_t)T * G * RTP_BYTES, f) != (size_t)T * G * RTP_BYTES) ? 7 : 0;
+    if (f) fclose(f);
+    printf("{\"groups\": %d, \"ticks\": %d, \"platform\": \"%s\", \"bridge_rtp_seed\": %lu, \"bridge_sizes\": [", G, T, platform, seed);
+    for (int c = 0; c < n_conf; c++) printf("%s%d", c ? ", " : "", (int)(conf_off[c + 1] - conf_off[c]));
+    printf("], \"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
+           "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
+           slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);
+    return rc;
+}

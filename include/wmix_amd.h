@@ -488,6 +488,18 @@ int wmx_mix_select_speakers_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU
                                  int max_speakers, uint32_t floor, int decay_shift, uint8_t *d_mute_out, void *stream);
 int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
 int wmx_mix_export_speakers(const wmx_mix *m, uint32_t *host_env, uint8_t *host_speaking, void *stream);
+/* Talker selection over leg packets, in front of wmx_mix_load_minus_legs: that call's layout, addressing (packet k of ring r at d_src +
+ * r*source_stride + k*packet_stride) and d_len convention (slot k of ring r is a call if and only if d_len[r*max_packets + k] ==
+ * srcU8Len).  The rule above with one change: level = the maximum, over the slots of the leg that are calls, of the level of that
+ * slot's row; a leg with no call this tick has level 0.  So a leg whose slot 0 is a hole and whose packet sits in a later slot is as
+ * loud as its packet.  Envelope, hold, floor, ranking and ties as above; d_mute_out is written for every ring and env stored for every
+ * member.  With max_packets == 1 and every slot a call the result is wmx_mix_select_speakers_conf's.  One wave per conference, the rows
+ * of the slots that are calls read once; no host synchronisation, no upload and no allocation after the first call.
+ * WMX_EINVAL, nothing launched, env unchanged: what the _conf form refuses, max_packets outside 1 .. WMX_MIX_MAX_LEG_PACKETS, a NULL
+ * d_len, rows that overlap (packet_stride < srcU8Len / 2 with more than one slot, source_stride shorter than a leg's slots). */
+int wmx_mix_select_speakers_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, long source_stride, long packet_stride,
+                                 int max_packets, const uint32_t *d_len, const uint8_t *d_mute, int max_speakers, uint32_t floor,
+                                 int decay_shift, uint8_t *d_mute_out, void *stream);
 /* The bridge load with a cursor per leg, for legs whose packets come early, late or not at all (an RTP leg delivers 0 .. 3 datagrams
  * in a tick).  Every wmix_thread_rtp_recv_pcma keeps a cursor of its own and calls wmix_load_data once per datagram that arrived
  * (src/wmixTask.c:1266-1316); here the mixer keeps one cursor (head, tick) per ring ON THE DEVICE, fresh (UINT32_MAX, 0) at first
@@ -521,6 +533,10 @@ int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
                             int reduce, void *stream);
 int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
 int wmx_mix_export_leg_cursors(const wmx_mix *m, uint32_t *host_head, uint32_t *host_tick, uint32_t *host_dropped, void *stream);
+/* wmx_mix_reset_rings: zero the n rings host_idx lists (NULL = every ring), on `stream`: a new call in a reused slot must not hear what
+ * the old call had loaded ahead of the play head.  Head and tick are the mixer's, not the ring's, and stay.  A bad index: WMX_EINVAL,
+ * nothing reset. */
+int wmx_mix_reset_rings(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
 int wmx_mix_drain(wmx_mix *m, int16_t *d_out, uint32_t bytes, long out_stride, void *stream);
 int wmx_mix_export(const wmx_mix *m, int group, int16_t *host_ring, uint32_t *head_off, uint32_t *tick);
 
@@ -574,6 +590,17 @@ int wmx_rtp_ingest(int n_streams, const uint8_t *d_packets, long packet_stride, 
 int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride,
                         const int32_t *d_recv_bytes, int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len,
                         uint16_t *d_seq_raw, void *stream);
+/* Play and send in one kernel, for a mixer whose rings are 1 x 8000 and a sender set with as many streams as the mixer has rings: per
+ * ring, the 160 samples at the ring head are read, zeroed as the play thread does (src/wmix.c:1351-1352), encoded with the handle's law
+ * and written behind the 12-byte header; then head and tick advance as wmx_mix_drain advances them, seq and timestamp as
+ * wmx_rtp_egress does.  Datagrams, rings, head, tick, seq and timestamp afterwards are byte for byte those of wmx_mix_drain(320 bytes)
+ * followed by wmx_rtp_egress(1, 8000 -> 1, 8000); the PCM row between the two never exists.  *packet_bytes (optional) receives 172.
+ * WMX_EINVAL, nothing launched, nothing advanced: another ring format, a ring count that is not the sender count, a NULL h, m or
+ * d_packets, packet_stride < 172, a mixer and senders on different devices.
+ * wmx_rtp_reset_streams: seq = timestamp = 0 for the n senders host_idx lists (NULL = all), on `stream`: what
+ * wmix_thread_rtp_send_pcma starts a call from (src/wmixTask.c:1058).  A bad index: WMX_EINVAL, nothing reset. */
+int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet_stride, uint32_t *packet_bytes, void *stream);
+int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
 int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timestamp);
 
 /* ------------------------------------------------------------------ the packet edge as a pipeline
@@ -624,6 +651,56 @@ int wmx_pipe_step_resident(wmx_pipe *h, const uint8_t *d_in, long in_stride, con
                            void *stream);
 wmx_chain *wmx_pipe_chain(wmx_pipe *h);
 wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
+
+/* ------------------------------------------------------------------ a conference bridge of RTP/G.711 legs as a pipeline
+ * What one wmix_thread_rtp_recv_pcma per leg (src/wmixTask.c:1266-1316), the play thread (src/wmix.c:1347-1366) and one
+ * wmix_thread_rtp_send_pcma per leg (src/wmixTask.c:1058-1143) do, for n_legs legs per 20 ms tick with only datagrams crossing PCIe.
+ * A wmx_conf owns a mixer of n_legs rings of 1 x 8000, n_legs senders, and `slots` (1 .. 16) sets of PINNED host rows with their device
+ * twins, a copy-in and a copy-out stream and the events between them, all made once.  A leg delivers 0 .. max_packets (1 .. 4)
+ * datagrams in a tick:
+ *   wmx_conf_in(h, slot)    n_legs x max_packets datagram rows of wmx_conf_in_row_bytes() = 176 bytes (172 used; 4-byte boundaries)
+ *   wmx_conf_recv(h, slot)  n_legs x max_packets int32: what recvfrom returned for the row (<= 0: nothing there, the row is not read)
+ *   wmx_conf_out(h, slot)   n_legs x 172 bytes: the datagram to send to each leg
+ *   wmx_conf_submit(h, &slot, stream)  takes the NEXT slot (round robin; wmx_conf_next_slot names it beforehand), uploads its in and
+ *                  recv rows on the copy-in stream and, behind them on `stream`: wmx_rtp_ingest_legs -> wmx_mix_select_speakers_legs
+ *                  (if selection is on) -> wmx_mix_load_minus_legs (reduce 1, 320-byte packages of 1 x 8000) -> wmx_rtp_egress_rings;
+ *                  then the download of the out rows on the copy-out stream.  Returns at once; blocks only when that slot is still in
+ *                  flight from `slots` submits ago.  With three slots the upload of tick t + 1 and the download of tick t - 1 run
+ *                  beside the launches of tick t.  No allocation, no host synchronisation, no upload beyond the slot's rows.
+ *   wmx_conf_wait(h, slot)  blocks until that slot's datagrams are in its out rows (slot < 0: every slot); wmx_conf_poll: 1 / 0
+ *   wmx_conf_step_resident  the launches alone, on rows that are on the device already (same shapes, rows contiguous)
+ * Setters, between submits, each ordered on `stream`: wmx_conf_set_conferences (wmx_mix_set_conferences over the legs);
+ * wmx_conf_mute (n_legs bytes by leg in HOST memory, NULL = nobody; a muted leg's cursor moves, no ring changes);
+ * wmx_conf_speakers (max_speakers 0 = off, else wmx_mix_select_speakers_legs' arguments: the host's mute goes into the selection and
+ * the selection's mask into the load); wmx_conf_set_play_correct (wmx_mix_set_play_correct); wmx_conf_reset_legs: what a new call in a
+ * used slot needs -- a fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0 -- for the n legs host_idx lists
+ * (NULL = all).  wmx_conf_export_legs: head, tick, dropped, env (uint32) and speaking (uint8) of every leg, any pointer NULL; blocking.
+ * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
+ * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
+ * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
+ * step with no layout in force (no slot is taken); a leg index outside the handle (nothing is reset).  A submit that fails before its
+ * first launch has advanced nothing; the rotation and the slots in flight are as before any failed submit. */
+typedef struct wmx_conf wmx_conf;
+int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int law);
+int wmx_conf_destroy(wmx_conf *h);
+int wmx_conf_set_conferences(wmx_conf *h, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream);
+int wmx_conf_mute(wmx_conf *h, const uint8_t *host_mask, void *stream);
+int wmx_conf_speakers(wmx_conf *h, int max_speakers, uint32_t floor, int decay_shift);
+int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);
+int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
+int wmx_conf_slots(const wmx_conf *h);
+int wmx_conf_in_row_bytes(const wmx_conf *h);
+uint8_t *wmx_conf_in(wmx_conf *h, int slot);
+int32_t *wmx_conf_recv(wmx_conf *h, int slot);
+const uint8_t *wmx_conf_out(wmx_conf *h, int slot);
+int wmx_conf_next_slot(const wmx_conf *h);
+int wmx_conf_submit(wmx_conf *h, int *slot, void *stream);
+int wmx_conf_wait(wmx_conf *h, int slot);
+int wmx_conf_poll(wmx_conf *h, int slot);
+int wmx_conf_step_resident(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream);
+int wmx_conf_export_legs(wmx_conf *h, uint32_t *head, uint32_t *tick, uint32_t *dropped, uint32_t *env, uint8_t *speaking, void *stream);
+wmx_mix *wmx_conf_mix(wmx_conf *h);
+wmx_rtp *wmx_conf_senders(wmx_conf *h);
 
 /* ------------------------------------------------------------------ the paced heartbeat over S streams in host memory
  * The reference's record thread is a PACED loop: one package of WMIX_INTERVAL_MS (20 ms, src/wmixConf.h:112) per tick, the tick's work

@@ -35,7 +35,17 @@ rings of the first call are compared with the common-cursor load's before any ti
 repetition moves every side's play head on by one package first (host state only, no launch), so that the legs' cursors neither run
 into the overrun bound nor fall behind for good.  The sides alternate, device events around each.
 
-    python tools_dev/bridge_bench.py --legs --out profiles/bridge/bridge_legs_bench.json"""
+    python tools_dev/bridge_bench.py --legs --out profiles/bridge/bridge_legs_bench.json
+
+--pipe measures the bridge of RTP/G.711 legs end to end on the telephony mix of --ragged, datagrams from and to host memory, milliseconds
+of wall clock per tick over blocks of ticks, three ways in one process, the sides alternating block by block: (a) the composition
+examples/host_tick.c --bridge-rtp makes -- blocking copies, wmx_rtp_ingest_legs, wmx_mix_load_minus_legs on a tick's mixer, wmx_tick_play,
+wmx_rtp_egress; (b) wmx_conf with 3 slots, the arrivals already in the slots' pinned rows (a host's recvfrom writes there), the datagrams
+read where they land; (c) wmx_conf_step_resident alone on rows that are on the device.  The three send the same datagrams for the first
+ticks before any time is reported.  Beside them the device time (events) of wmx_mix_drain + wmx_rtp_egress and of wmx_rtp_egress_rings
+on twin mixers of as many rings.
+
+    python tools_dev/bridge_bench.py --pipe --out profiles/bridge/bridge_pipe_bench.json"""
 import argparse
 import json
 import os
@@ -286,6 +296,128 @@ def legs_against_conf(reps, freq=8000):
             "ratio_steady_over_conf": round(b["median_ms"] / a["median_ms"], 3), "ratio_jitter_over_conf": round(c["median_ms"] / a["median_ms"], 3)}
 
 
+def conf_pipe(reps):
+    import ctypes as C
+    import time
+    from wmix_amd._lib import check, lib
+    from wmix_amd.conf import ConfBridge
+    from wmix_amd.rtp import RtpSenders
+    L = lib()
+    sizes = telephony_sizes()
+    n_conf, legs = len(sizes), sum(sizes)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    layout = [list(range(off[c], off[c + 1])) for c in range(n_conf)]
+    CYC = 3  # the script is a cycle of as many ticks as the handle has slots: every slot keeps its tick's rows
+    rng = np.random.default_rng(13)
+    u = rng.integers(0, 8, (CYC, legs))
+    recv = np.zeros((CYC, legs, 3), np.int32)
+    recv[:, :, 0] = np.where(u >= 2, 172, 0)
+    recv[:, :, 1] = np.where(u == 2, 172, np.where(u == 3, -1, 0))
+    recv[:, :, 2] = np.where(u == 3, 172, 0)
+    pk = rng.integers(0, 256, (CYC, legs, 3, 176), dtype=np.uint8)
+    pk[..., :12] = 0
+    pk[..., 0], pk[..., 1] = 0x80, 0x88
+    stream = torch.cuda.current_stream().cuda_stream
+    # (a) the parent's composition
+    tk, snd = TickBatch(legs, 1, stages=0), RtpSenders(legs)
+    tk.bridge_conferences(layout)
+    check(L.wmx_tick_set_play_correct(tk._h, 0), "wmx_tick_set_play_correct")  # every side: what is loaded is played in the same tick
+    mix_a = L.wmx_tick_mix(tk._h)
+    h_in, h_recv = [torch.from_numpy(pk[i]) for i in range(CYC)], [torch.from_numpy(recv[i]) for i in range(CYC)]
+    d_in, d_recv = torch.zeros((legs, 3, 176), dtype=torch.uint8, device="cuda"), torch.zeros((legs, 3), dtype=torch.int32, device="cuda")
+    d_pcm, d_len = torch.zeros((legs, 3, 164), dtype=torch.int16, device="cuda"), torch.zeros((legs, 3), dtype=torch.int32, device="cuda")
+    d_play, d_out = torch.zeros((legs, 160), dtype=torch.int16, device="cuda"), torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+    out_a = torch.zeros((legs, 172), dtype=torch.uint8)
+    step = {"a": 0, "b": 0, "c": 0}
+
+    def parent():
+        i = step["a"] % CYC
+        step["a"] += 1
+        d_in.copy_(h_in[i])      # pageable host memory: blocking
+        d_recv.copy_(h_recv[i])
+        check(L.wmx_rtp_ingest_legs(legs, 3, d_in.data_ptr(), 3 * 176, 176, d_recv.data_ptr(), d_pcm.data_ptr(), 3 * 164, 164, d_len.data_ptr(), None,
+                                    stream), "wmx_rtp_ingest_legs")
+        check(L.wmx_mix_load_minus_legs(mix_a, d_pcm.data_ptr(), 320, 8000, 1, 16, 3 * 164, 164, 3, d_len.data_ptr(), None, 1, stream),
+              "wmx_mix_load_minus_legs")
+        tk.play(d_play)
+        snd.egress(d_play, 1, 8000, 1, 8000, packets=d_out)
+        out_a.copy_(d_out)       # blocking
+        return out_a
+
+    # (b) the handle, 3 slots
+    cb = ConfBridge(legs, 3, 3)
+    cb.set_conferences(layout)
+    cb.set_play_correct(0)
+    for k in range(3):
+        cb.rows_in[k][:] = pk[k]
+        cb.recv[k][:] = recv[k]
+
+    def handle():
+        step["b"] += 1
+        return cb.submit()
+
+    # (c) the launches alone
+    cr = ConfBridge(legs, 1, 3)
+    cr.set_conferences(layout)
+    cr.set_play_correct(0)
+    r_in, r_recv = torch.from_numpy(pk).cuda(), torch.from_numpy(recv).cuda()
+    r_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+
+    def resident():
+        i = step["c"] % CYC
+        step["c"] += 1
+        cr.step_resident(r_in[i], r_recv[i], r_out)
+
+    # ---- the same datagrams?
+    for t in range(2 * CYC):
+        a = parent().numpy().copy()
+        k = handle()
+        cb.wait(k)
+        resident()
+        assert np.array_equal(a, cb.rows_out[k]) and np.array_equal(a, r_out.cpu().numpy()), ("datagrams differ, tick", t)
+        assert (a[:, 12:] != 0xD5).any()
+
+    def wall(f, n, end):
+        t0 = time.perf_counter()
+        for _ in range(n):
+            f()
+        end()
+        return (time.perf_counter() - t0) * 1e3 / n
+
+    per_block = max(reps // BLOCKS, 8)
+    ms = {"a": [], "b": [], "c": []}
+    for _ in range(BLOCKS + 1):  # the first block warms up
+        ms["a"].append(wall(parent, per_block, torch.cuda.synchronize))
+        ms["b"].append(wall(handle, per_block, lambda: cb.wait(-1)))
+        ms["c"].append(wall(resident, per_block, torch.cuda.synchronize))
+    side = lambda v: {"median_ms_per_tick": round(float(np.median(v[1:])), 5), "block_ms_per_tick": [round(x, 5) for x in v[1:]]}  # noqa: E731
+    a, b, c = side(ms["a"]), side(ms["b"]), side(ms["c"])
+    dropped = {"conf": int(cb.export_legs()["dropped"].sum()), "resident": int(cr.export_legs()["dropped"].sum())}
+    # ---- the fused play-and-send kernel beside the pair it replaces
+    pair, fused, s2, s3 = MixBatch(legs, 1, 8000), MixBatch(legs, 1, 8000), RtpSenders(legs), RtpSenders(legs)
+    p_play, p_out, f_out = torch.zeros_like(d_play), torch.zeros_like(d_out), torch.zeros_like(d_out)
+
+    def drain_then_egress():
+        check(L.wmx_mix_drain(pair._h, p_play.data_ptr(), 320, 160, stream), "wmx_mix_drain")
+        check(L.wmx_rtp_egress(s2._h, 1, 8000, p_play.data_ptr(), 320, 160, 1, 8000, p_out.data_ptr(), 172, None, stream), "wmx_rtp_egress")
+
+    def egress_rings():
+        check(L.wmx_rtp_egress_rings(s3._h, fused._h, f_out.data_ptr(), 172, None, stream), "wmx_rtp_egress_rings")
+
+    t_pair, t_fused = alternate([drain_then_egress, egress_rings], reps)
+    assert torch.equal(p_out, f_out)
+    kp, kf = stats(t_pair), stats(t_fused)
+    for x in (tk, snd, cb, cr, pair, fused, s2, s3):
+        x.close()
+    return {"conferences": n_conf, "sizes": {str(k): sizes.count(k) for k in sorted(set(sizes))}, "legs": legs, "max_packets": 3,
+            "packets_per_leg_and_tick": round(float((recv > 0).sum()) / (CYC * legs), 3), "ticks_per_block": per_block, "datagram_ticks_checked": 2 * CYC,
+            "a_host_tick_bridge_rtp_composition": a, "b_wmx_conf_3_slots": b, "c_step_resident": c,
+            "b_over_c": round(b["median_ms_per_tick"] / c["median_ms_per_tick"], 3), "a_over_b": round(a["median_ms_per_tick"] / b["median_ms_per_tick"], 3),
+            "b_nearer_to_c_than_to_a": bool(b["median_ms_per_tick"] - c["median_ms_per_tick"] < a["median_ms_per_tick"] - b["median_ms_per_tick"]),
+            "calls_dropped": dropped, "drain_then_egress": kp, "egress_rings": kf,
+            "fused_over_pair": round(kf["median_ms"] / kp["median_ms"], 3)}
+
+
 def speakers_against_load(layout, P, n, freq, max_speakers, reps, what):
     """layout: None = the uniform form with P consecutive legs per conference; else the list of conferences of the layout form"""
     per = freq // 1000 * 20
@@ -354,6 +486,7 @@ if __name__ == "__main__":
     ap.add_argument("--ragged", action="store_true", help="the bridge over a layout: same legs both ways, a telephony mix against padding")
     ap.add_argument("--speakers", type=int, default=0, help="measure the talker selection with this max_speakers instead (uniform shapes, or --ragged)")
     ap.add_argument("--legs", action="store_true", help="the bridge load with a cursor per leg beside wmx_mix_load_minus_conf, same layout")
+    ap.add_argument("--pipe", action="store_true", help="the bridge of RTP/G.711 legs end to end: the parent's composition, wmx_conf, the launches alone")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
@@ -361,6 +494,11 @@ if __name__ == "__main__":
     if args.legs:
         res = {"tool": "bridge_bench --legs", "device": torch.cuda.get_device_name(0), "reps": args.reps,
                "runs": "the builder's own, one process, the sides alternating", "legs": legs_against_conf(args.reps)}
+        args.sizes = args.tick = ""
+        args.ragged, args.speakers = False, 0
+    if args.pipe:
+        res = {"tool": "bridge_bench --pipe", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps)}
         args.sizes = args.tick = ""
         args.ragged, args.speakers = False, 0
     if args.speakers:

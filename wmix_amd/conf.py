@@ -1,0 +1,125 @@
+"""Host-side mirror of wmx_conf (wmix_amd/csrc/conf.hip): a conference bridge of RTP/G.711 legs in one handle, datagram in, datagram out.
+The slots' pinned host rows are numpy views; everything else happens in the library."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._lib import check, lib
+from .rtp import LAW
+
+OUT_ROW = 172
+
+
+def _view(ptr, shape, dtype):
+    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    return np.frombuffer((C.c_uint8 * n).from_address(ptr), dtype=dtype).reshape(shape)
+
+
+class ConfBridge:
+    def __init__(self, n_legs, slots=3, max_packets=3, law="a"):
+        self._h = C.c_void_p()
+        rc = lib().wmx_conf_create(C.byref(self._h), n_legs, slots, max_packets, LAW[law])
+        if rc != 0:
+            self._h = None
+            check(rc, "wmx_conf_create")
+        self.n_legs, self.slots, self.max_packets = n_legs, slots, max_packets
+        self.in_row = lib().wmx_conf_in_row_bytes(self._h)
+        L = lib()
+        # datagram rows [n_legs, max_packets, 176], what recvfrom returned [n_legs, max_packets], datagrams out [n_legs, 172]
+        self.rows_in = [_view(L.wmx_conf_in(self._h, k), (n_legs, max_packets, self.in_row), np.uint8) for k in range(slots)]
+        self.recv = [_view(L.wmx_conf_recv(self._h, k), (n_legs, max_packets), np.int32) for k in range(slots)]
+        self.rows_out = [_view(L.wmx_conf_out(self._h, k), (n_legs, OUT_ROW), np.uint8) for k in range(slots)]
+
+    @staticmethod
+    def _stream():
+        return torch.cuda.current_stream().cuda_stream
+
+    def set_conferences(self, conferences):
+        """a list of conferences, each the ordered list of its legs (MixBatch.set_conferences); an empty list clears the layout"""
+        off = np.zeros(len(conferences) + 1, np.int32)
+        off[1:] = np.cumsum([len(c) for c in conferences])
+        members = np.ascontiguousarray([r for c in conferences for r in c], dtype=np.int32)
+        check(lib().wmx_conf_set_conferences(self._h, len(conferences), off.ctypes.data, members.ctypes.data if members.size else None,
+                                             self._stream()), "wmx_conf_set_conferences")
+
+    def mute(self, mask=None):
+        """the host's mute by leg (non-zero = loaded nowhere), None = nobody"""
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        assert m is None or m.size == self.n_legs
+        check(lib().wmx_conf_mute(self._h, None if m is None else m.ctypes.data, self._stream()), "wmx_conf_mute")
+
+    def speakers(self, max_speakers, floor=0, decay_shift=3):
+        """talker selection in front of the load (0 = off)"""
+        check(lib().wmx_conf_speakers(self._h, max_speakers, floor, decay_shift), "wmx_conf_speakers")
+
+    def set_play_correct(self, n_bytes):
+        check(lib().wmx_conf_set_play_correct(self._h, n_bytes), "wmx_conf_set_play_correct")
+
+    def reset_legs(self, legs=None):
+        """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0 (None = every leg)"""
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_conf_reset_legs(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, self._stream()),
+              "wmx_conf_reset_legs")
+
+    def next_slot(self):
+        return lib().wmx_conf_next_slot(self._h)
+
+    def submit(self):
+        """queue the next slot (its rows_in / recv hold the tick's arrivals); returns the slot, whose rows_out are valid after wait(slot)"""
+        k = C.c_int(-1)
+        check(lib().wmx_conf_submit(self._h, C.byref(k), self._stream()), "wmx_conf_submit")
+        return k.value
+
+    def wait(self, slot=-1):
+        check(lib().wmx_conf_wait(self._h, slot), "wmx_conf_wait")
+
+    def poll(self, slot=-1):
+        rc = lib().wmx_conf_poll(self._h, slot)
+        if rc < 0:
+            check(rc, "wmx_conf_poll")
+        return bool(rc)
+
+    def step_resident(self, d_in, d_recv, d_out=None):
+        """the launches alone: d_in uint8 CUDA [n_legs, max_packets, 176], d_recv int32 CUDA [n_legs, max_packets] -> uint8 [n_legs, 172]"""
+        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous() and tuple(d_in.shape) == (self.n_legs, self.max_packets, self.in_row)
+        assert d_recv.is_cuda and d_recv.dtype == torch.int32 and d_recv.is_contiguous() and tuple(d_recv.shape) == (self.n_legs, self.max_packets)
+        if d_out is None:
+            d_out = torch.zeros((self.n_legs, OUT_ROW), dtype=torch.uint8, device=d_in.device)
+        assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and tuple(d_out.shape) == (self.n_legs, OUT_ROW)
+        check(lib().wmx_conf_step_resident(self._h, d_in.data_ptr(), d_recv.data_ptr(), d_out.data_ptr(), self._stream()), "wmx_conf_step_resident")
+        return d_out
+
+    def export_legs(self):
+        """dict(head, tick, dropped, env: uint32 [n_legs]; speaking: uint8 [n_legs]) as the work queued on the current stream leaves them"""
+        r = {k: np.zeros(self.n_legs, np.uint32) for k in ("head", "tick", "dropped", "env")}
+        r["speaking"] = np.zeros(self.n_legs, np.uint8)
+        check(lib().wmx_conf_export_legs(self._h, r["head"].ctypes.data, r["tick"].ctypes.data, r["dropped"].ctypes.data, r["env"].ctypes.data,
+                                         r["speaking"].ctypes.data, self._stream()), "wmx_conf_export_legs")
+        return r
+
+    def export_ring(self, leg):
+        """(ring int16, head_off, tick) of one leg's ring (wmx_mix_export)"""
+        ring = np.zeros(8000, np.int16)
+        h, t = C.c_uint32(0), C.c_uint32(0)
+        check(lib().wmx_mix_export(lib().wmx_conf_mix(self._h), leg, ring.ctypes.data, C.byref(h), C.byref(t)), "wmx_mix_export")
+        return ring, h.value, t.value
+
+    def sender_state(self, leg):
+        s, t = C.c_uint16(0), C.c_uint32(0)
+        check(lib().wmx_rtp_export(lib().wmx_conf_senders(self._h), leg, C.byref(s), C.byref(t)), "wmx_rtp_export")
+        return s.value, t.value
+
+    def close(self):
+        if self._h:
+            self.rows_in = self.recv = self.rows_out = None  # views of memory that goes away
+            lib().wmx_conf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,350 @@
+// conf.hip -- a conference bridge of RTP/G.711 legs in one handle, datagram in, datagram out (host code only: it sequences copies and
+// launches, like pipe.hip).
+//
+// What the daemon runs as one wmix_thread_rtp_recv_pcma per leg (src/wmixTask.c:1266-1316: rtp_recv -> G711a2PCM -> wmix_load_data with
+// the thread's own cursor), the play thread (src/wmix.c:1347-1366) and one wmix_thread_rtp_send_pcma per leg (src/wmixTask.c:1058-1143),
+// for n_legs legs per 20 ms tick with only datagrams crossing PCIe:
+//
+//     host rows --H2D--> wmx_rtp_ingest_legs -> [wmx_mix_select_speakers_legs] -> wmx_mix_load_minus_legs -> wmx_rtp_egress_rings --D2H--> host
+//
+// PER SLOT (made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a 4-byte
+// boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and three events.  PER HANDLE: the mixer
+// (rings, layout, leg cursors, envelopes), the senders, the PCM rows between ingest and load, d_len, the host's mute and the mask
+// talker selection writes for the load, the copy-in and the copy-out stream.  wmx_conf_submit(slot k) queues H2D on the copy-in stream
+// -> (event) -> the launches on the caller's stream -> (event) -> D2H on the copy-out stream -> (event) and returns at once: with three
+// slots the upload of tick t + 1 and the download of tick t - 1 run beside the launches of tick t.  The per-handle buffers are shared
+// by every tick, so the handle takes ONE compute stream, like wmx_pipe.
+#include <vector>
+#include "wmx_internal.h"
+
+namespace {
+constexpr int kInRow = 176;    // a datagram row in: 172 bytes, rows on 4-byte boundaries
+constexpr int kOutRow = 172;   // 12-byte RTP header + 160 G.711 codes
+constexpr int kPcmRow = 160;   // the 20 ms of one datagram, 1 x 8000
+constexpr uint32_t kPcmBytes = 2 * kPcmRow;
+}  // namespace
+
+struct wmx_conf {
+    int device;  // first member of every handle (wmx_handle_device)
+    int n_legs, slots, max_packets;
+    wmx_mix *mix;
+    wmx_rtp *snd;
+    int16_t *d_pcm;    // [n_legs][max_packets][160] between ingest and load
+    uint32_t *d_len;   // [n_legs][max_packets] 320 for a slot that is a call
+    uint8_t *d_mute;   // [n_legs] the host's mute
+    uint8_t *d_mask;   // [n_legs] what selection leaves for the load
+    uint8_t *h_mute;   // pinned: the upload's source
+    bool mute_on;
+    int max_speakers, decay_shift;  // max_speakers 0: selection off
+    uint32_t floor;
+    struct Slot {
+        uint8_t *h_in, *h_out;
+        int32_t *h_recv;
+        uint8_t *d_in, *d_out;
+        int32_t *d_recv;
+        hipEvent_t ev_in, ev_done, ev_out;
+        bool in_flight;
+    };
+    std::vector<Slot> slot;
+    hipStream_t s_in, s_out;
+    int next;
+};
+
+// the launches of one tick on rows that are on the device
+static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream) {
+    const int K = h->max_packets;
+    int rc = wmx_rtp_ingest_legs(h->n_legs, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len, nullptr, stream);
+    if (rc != 0) return rc;
+    const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
+    if (h->max_speakers > 0) {
+        rc = wmx_mix_select_speakers_legs(h->mix, h->d_pcm, kPcmBytes, (long)K * kPcmRow, kPcmRow, K, h->d_len, host_mute, h->max_speakers, h->floor,
+                                          h->decay_shift, h->d_mask, stream);
+        if (rc != 0) return rc;
+        load_mute = h->d_mask;
+    }
+    rc = wmx_mix_load_minus_legs(h->mix, h->d_pcm, kPcmBytes, 8000, 1, 16, (long)K * kPcmRow, kPcmRow, K, h->d_len, load_mute, 1, stream);
+    if (rc != 0) return rc;
+    uint32_t bytes = 0;
+    rc = wmx_rtp_egress_rings(h->snd, h->mix, d_out, kOutRow, &bytes, stream);
+    if (rc == 0 && bytes != (uint32_t)kOutRow) {
+        wmx::set_error("wmx_conf: egress made %u-byte datagrams", bytes);
+        return WMX_ESTATE;
+    }
+    return rc;
+}
+
+static bool conf_slot_ok(const wmx_conf *h, int slot) { return h && slot >= 0 && slot < h->slots; }
+
+extern "C" {
+
+int wmx_conf_destroy(wmx_conf *h) {
+    WMX_ON_DEVICE(h);
+    if (!h) return 0;
+    (void)hipDeviceSynchronize();
+    for (wmx_conf::Slot &s : h->slot) {
+        if (s.h_in) (void)hipHostFree(s.h_in);
+        if (s.h_out) (void)hipHostFree(s.h_out);
+        if (s.h_recv) (void)hipHostFree(s.h_recv);
+        if (s.d_in) (void)hipFree(s.d_in);
+        if (s.d_out) (void)hipFree(s.d_out);
+        if (s.d_recv) (void)hipFree(s.d_recv);
+        if (s.ev_in) (void)hipEventDestroy(s.ev_in);
+        if (s.ev_done) (void)hipEventDestroy(s.ev_done);
+        if (s.ev_out) (void)hipEventDestroy(s.ev_out);
+    }
+    if (h->s_in) (void)hipStreamDestroy(h->s_in);
+    if (h->s_out) (void)hipStreamDestroy(h->s_out);
+    if (h->d_pcm) (void)hipFree(h->d_pcm);
+    if (h->d_len) (void)hipFree(h->d_len);
+    if (h->d_mute) (void)hipFree(h->d_mute);  // d_mask lies behind it
+    if (h->h_mute) (void)hipHostFree(h->h_mute);
+    if (h->mix) wmx_mix_destroy(h->mix);
+    if (h->snd) wmx_rtp_destroy(h->snd);
+    delete h;
+    return 0;
+}
+
+// law: WMX_LAW_A or WMX_LAW_U of what is SENT; every payload received is decoded as A-law, as the reference's receive thread does
+int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int law) {
+    if (!out) return WMX_EINVAL;
+    *out = nullptr;
+    if (n_legs < 1 || slots < 1 || slots > 16 || max_packets < 1 || max_packets > WMX_MIX_MAX_LEG_PACKETS || (law != WMX_LAW_A && law != WMX_LAW_U)) {
+        wmx::set_error("wmx_conf_create: n_legs=%d slots=%d (1 .. 16) max_packets=%d (1 .. %d) law=%d", n_legs, slots, max_packets,
+                       WMX_MIX_MAX_LEG_PACKETS, law);
+        return WMX_EINVAL;
+    }
+    wmx_conf *h = new wmx_conf();
+    if ((h->device = wmx::current_device()) < 0) {
+        delete h;
+        return WMX_ENODEV;
+    }
+    h->n_legs = n_legs;
+    h->slots = slots;
+    h->max_packets = max_packets;
+    h->slot.assign((size_t)slots, wmx_conf::Slot{});
+    const size_t rows = (size_t)n_legs * (size_t)max_packets;
+    int rc = wmx_mix_create(&h->mix, n_legs, 1, 8000);
+    if (rc == 0) rc = wmx_rtp_create(&h->snd, n_legs, law);
+    // the cursors and the envelopes are made by the first call that needs them: here, so that no submit allocates
+    if (rc == 0) rc = wmx_mix_reset_leg_cursors(h->mix, nullptr, 0, nullptr);
+    if (rc == 0) rc = wmx_mix_reset_speakers(h->mix, nullptr, 0, nullptr);
+    if (rc == 0) {
+        hipError_t e = hipMalloc(&h->d_pcm, rows * kPcmRow * sizeof(int16_t));
+        if (e == hipSuccess) e = hipMalloc(&h->d_len, rows * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&h->d_mute, 2 * (size_t)n_legs);
+        if (e == hipSuccess) e = hipMemset(h->d_mute, 0, 2 * (size_t)n_legs);
+        if (e == hipSuccess) e = hipMemset(h->d_len, 0, rows * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(h->d_pcm, 0, rows * kPcmRow * sizeof(int16_t));
+        if (e == hipSuccess) h->d_mask = h->d_mute + n_legs;
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&h->h_mute), (size_t)n_legs, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking);
+        for (wmx_conf::Slot &s : h->slot) {
+            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.h_in), rows * kInRow, hipHostMallocDefault);
+            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.h_recv), rows * sizeof(int32_t), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.h_out), (size_t)n_legs * kOutRow, hipHostMallocDefault);
+            if (e == hipSuccess) e = hipMalloc(&s.d_in, rows * kInRow);
+            if (e == hipSuccess) e = hipMalloc(&s.d_recv, rows * sizeof(int32_t));
+            if (e == hipSuccess) e = hipMalloc(&s.d_out, (size_t)n_legs * kOutRow);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming);
+            if (e == hipSuccess) {
+                memset(s.h_in, 0, rows * kInRow);
+                memset(s.h_recv, 0, rows * sizeof(int32_t));
+                memset(s.h_out, 0, (size_t)n_legs * kOutRow);
+            }
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = wmx::hip_fail(e, "wmx_conf_create: buffers / streams / events", __FILE__, __LINE__);
+    }
+    if (rc != 0) {
+        wmx_conf_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+// ---- setters: between submits, each ordered on `stream`
+int wmx_conf_set_conferences(wmx_conf *h, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_mix_set_conferences(h->mix, n_conf, host_off, host_members, stream);
+}
+
+// host_mask: n_legs bytes by leg, non-zero = that leg is loaded nowhere (it still hears the others); NULL = nobody is muted
+int wmx_conf_mute(wmx_conf *h, const uint8_t *host_mask, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (!host_mask) {
+        h->mute_on = false;
+        return 0;
+    }
+    hipStream_t s = wmx::as_stream(stream);
+    WMX_HIP(hipStreamSynchronize(s));  // an earlier upload has left h_mute, and no launch in flight reads a mask half written
+    memcpy(h->h_mute, host_mask, (size_t)h->n_legs);
+    WMX_HIP(hipMemcpyAsync(h->d_mute, h->h_mute, (size_t)h->n_legs, hipMemcpyHostToDevice, s));
+    h->mute_on = true;
+    return 0;
+}
+
+// max_speakers 0 = selection off; else the arguments of wmx_mix_select_speakers_legs
+int wmx_conf_speakers(wmx_conf *h, int max_speakers, uint32_t floor, int decay_shift) {
+    if (!h) return WMX_EINVAL;
+    if (max_speakers < 0 || max_speakers > WMX_MIX_MAX_PARTIES || decay_shift < 0 || decay_shift > 31) {
+        wmx::set_error("wmx_conf_speakers: max_speakers=%d must be 0 .. %d and decay_shift=%d 0 .. 31", max_speakers, WMX_MIX_MAX_PARTIES, decay_shift);
+        return WMX_EINVAL;
+    }
+    h->max_speakers = max_speakers;
+    h->floor = floor;
+    h->decay_shift = decay_shift;
+    return 0;
+}
+
+int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
+
+// a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0
+int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
+    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
+    for (int i = 0; host_idx && i < n; i++)  // before the first of the four: a bad index resets nothing
+        if (host_idx[i] < 0 || host_idx[i] >= h->n_legs) {
+            wmx::set_error("wmx_conf_reset_legs: leg %d is outside the handle's %d", (int)host_idx[i], h->n_legs);
+            return WMX_EINVAL;
+        }
+    int rc = wmx_mix_reset_leg_cursors(h->mix, host_idx, n, stream);
+    if (rc == 0) rc = wmx_mix_reset_speakers(h->mix, host_idx, n, stream);
+    if (rc == 0) rc = wmx_mix_reset_rings(h->mix, host_idx, n, stream);
+    if (rc == 0) rc = wmx_rtp_reset_streams(h->snd, host_idx, n, stream);
+    return rc;
+}
+
+// ---- the slots' pinned rows
+int wmx_conf_slots(const wmx_conf *h) { return h ? h->slots : WMX_EINVAL; }
+int wmx_conf_in_row_bytes(const wmx_conf *h) { return h ? kInRow : WMX_EINVAL; }
+uint8_t *wmx_conf_in(wmx_conf *h, int slot) { return conf_slot_ok(h, slot) ? h->slot[(size_t)slot].h_in : nullptr; }
+int32_t *wmx_conf_recv(wmx_conf *h, int slot) { return conf_slot_ok(h, slot) ? h->slot[(size_t)slot].h_recv : nullptr; }
+const uint8_t *wmx_conf_out(wmx_conf *h, int slot) { return conf_slot_ok(h, slot) ? h->slot[(size_t)slot].h_out : nullptr; }
+int wmx_conf_next_slot(const wmx_conf *h) { return h ? h->next : WMX_EINVAL; }
+wmx_mix *wmx_conf_mix(wmx_conf *h) { return h ? h->mix : nullptr; }
+wmx_rtp *wmx_conf_senders(wmx_conf *h) { return h ? h->snd : nullptr; }
+
+// One tick on rows that are on the device already: d_in n_legs x max_packets rows of 176 bytes, d_recv n_legs x max_packets,
+// d_out n_legs x 172 bytes.
+int wmx_conf_step_resident(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !d_in || !d_recv || !d_out) {
+        wmx::set_error("wmx_conf_step_resident: bad argument");
+        return WMX_EINVAL;
+    }
+    if (wmx_mix_conferences(h->mix) < 1) {
+        wmx::set_error("wmx_conf_step_resident: no layout (wmx_conf_set_conferences)");
+        return WMX_EINVAL;
+    }
+    return conf_launches(h, d_in, d_recv, d_out, stream);
+}
+
+// Queue the next slot: its in / recv rows must hold this tick's arrivals.  Blocks only if that slot is still in flight from `slots`
+// submits ago.  A failure before the first launch has advanced nothing; a later one has lost the tick (the cursors that moved stay
+// moved, as a receive thread's do), and in both cases the rotation and the slots in flight are as before and the streams are drained.
+int wmx_conf_submit(wmx_conf *h, int *slot, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (wmx_mix_conferences(h->mix) < 1) {
+        wmx::set_error("wmx_conf_submit: no layout (wmx_conf_set_conferences)");
+        return WMX_EINVAL;
+    }
+    const int k = h->next;
+    wmx_conf::Slot &s = h->slot[(size_t)k];
+    hipStream_t main = wmx::as_stream(stream);
+    if (s.in_flight) {  // only completes what an earlier submit promised
+        WMX_HIP(hipEventSynchronize(s.ev_out));
+        s.in_flight = false;
+    }
+    const size_t rows = (size_t)h->n_legs * (size_t)h->max_packets;
+    auto uploads = [&]() -> int {
+        WMX_HIP(hipMemcpyAsync(s.d_in, s.h_in, rows * kInRow, hipMemcpyHostToDevice, h->s_in));
+        WMX_HIP(hipMemcpyAsync(s.d_recv, s.h_recv, rows * sizeof(int32_t), hipMemcpyHostToDevice, h->s_in));
+        WMX_HIP(hipEventRecord(s.ev_in, h->s_in));
+        WMX_HIP(hipStreamWaitEvent(main, s.ev_in, 0));
+        return 0;
+    };
+    int rc = uploads();
+    if (rc != 0) {
+        (void)hipStreamSynchronize(h->s_in);  // whatever was queued has read the rows: they may be rewritten and submitted again
+        (void)hipGetLastError();
+        return rc;
+    }
+    auto launches = [&]() -> int {
+        const int r = conf_launches(h, s.d_in, s.d_recv, s.d_out, stream);
+        if (r != 0) return r;
+        WMX_HIP(hipEventRecord(s.ev_done, main));
+        WMX_HIP(hipStreamWaitEvent(h->s_out, s.ev_done, 0));
+        WMX_HIP(hipMemcpyAsync(s.h_out, s.d_out, (size_t)h->n_legs * kOutRow, hipMemcpyDeviceToHost, h->s_out));
+        WMX_HIP(hipEventRecord(s.ev_out, h->s_out));
+        return 0;
+    };
+    rc = launches();
+    if (rc != 0) {
+        char why[512];
+        snprintf(why, sizeof(why), "%s", wmx_last_error());
+        (void)hipStreamSynchronize(h->s_in);
+        (void)hipStreamSynchronize(main);
+        (void)hipStreamSynchronize(h->s_out);
+        (void)hipGetLastError();
+        wmx::set_error("wmx_conf_submit: the tick is lost (%s)", why);
+        return rc;
+    }
+    h->next = (k + 1) % h->slots;
+    s.in_flight = true;
+    if (slot) *slot = k;
+    return 0;
+}
+
+// Blocks until the slot's datagrams are in its out rows (at once for a slot that is not in flight); slot < 0: every slot.
+int wmx_conf_wait(wmx_conf *h, int slot) {
+    WMX_ON_DEVICE(h);
+    if (!h || slot >= h->slots) return WMX_EINVAL;
+    for (int k = 0; k < h->slots; k++) {
+        if (slot >= 0 && k != slot) continue;
+        wmx_conf::Slot &s = h->slot[(size_t)k];
+        if (s.in_flight) {
+            WMX_HIP(hipEventSynchronize(s.ev_out));
+            s.in_flight = false;
+        }
+    }
+    return 0;
+}
+
+// Non-blocking wmx_conf_wait: 1 = the rows of `slot` (< 0: of every slot) are in host memory, 0 = still on their way.
+int wmx_conf_poll(wmx_conf *h, int slot) {
+    WMX_ON_DEVICE(h);
+    if (!h || slot >= h->slots) return WMX_EINVAL;
+    int done = 1;
+    for (int k = 0; k < h->slots; k++) {
+        if (slot >= 0 && k != slot) continue;
+        wmx_conf::Slot &s = h->slot[(size_t)k];
+        if (!s.in_flight) continue;
+        const hipError_t q = hipEventQuery(s.ev_out);
+        if (q == hipSuccess) {
+            s.in_flight = false;
+        } else if (q == hipErrorNotReady) {
+            (void)hipGetLastError();
+            done = 0;
+        } else {
+            return wmx::hip_fail(q, "hipEventQuery(ev_out)", __FILE__, __LINE__);
+        }
+    }
+    return done;
+}
+
+// head, tick, dropped (uint32), env (uint32) and speaking (uint8) of every leg as the work queued on `stream` leaves them; any pointer
+// may be NULL; blocking
+int wmx_conf_export_legs(wmx_conf *h, uint32_t *head, uint32_t *tick, uint32_t *dropped, uint32_t *env, uint8_t *speaking, void *stream) {
+    if (!h) return WMX_EINVAL;
+    int rc = 0;
+    if (head || tick || dropped) rc = wmx_mix_export_leg_cursors(h->mix, head, tick, dropped, stream);
+    if (rc == 0 && (env || speaking)) rc = wmx_mix_export_speakers(h->mix, env, speaking, stream);
+    return rc;
+}
+
+}  // extern "C"

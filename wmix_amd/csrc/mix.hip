@@ -268,6 +268,90 @@ __global__ __launch_bounds__(256) void select_speakers_kernel(const int16_t *__r
     }
 }
 
+// the part of a row's level that lane `sub` of the L lanes dealt to the row sums: select_speakers_kernel's walk (elements in front of
+// the first 16-byte boundary and behind the last one singly, the rest as 16-byte loads), every element once over the L lanes
+__device__ __forceinline__ uint32_t abs_sum_part(const int16_t *__restrict__ row, uint32_t n_el, uint32_t sub, uint32_t L) {
+    uint32_t sum = 0;
+    uint32_t head = (8u - (uint32_t)(((uintptr_t)row & 15u) >> 1)) & 7u;
+    if (head > n_el) head = n_el;
+    const uint32_t body = (n_el - head) / 8;
+    for (uint32_t i = sub; i < head; i += L) sum += speakers_abs16(row[i]);
+    const uint4 *v = reinterpret_cast<const uint4 *>(row + head);
+    for (uint32_t c = sub; c < body; c += L) {
+        const uint4 x = v[c];
+        sum += abs_sum_pair(x.x) + abs_sum_pair(x.y) + abs_sum_pair(x.z) + abs_sum_pair(x.w);
+    }
+    for (uint32_t i = head + body * 8 + sub; i < n_el; i += L) sum += speakers_abs16(row[i]);
+    return sum;
+}
+
+// Talker selection over leg packets (speakers.h: speakers_level_legs): select_speakers_kernel's dealing -- one wave = one conference
+// of the layout, L lanes per member -- with the level taken over the leg's slots.  The L lanes of a member read which of its slots are
+// calls (len == srcU8Len; the same words in every lane of the member), stride the rows of those slots only, and an xor-shuffle per
+// slot gives that slot's level; the largest is the leg's.  The shuffles run outside every branch: a lane whose slot is no call brings
+// 0.  Then lane p is member p, as there.  Rings outside every conference of two or more members are the clear kernel's.
+__global__ __launch_bounds__(256) void select_speakers_legs_kernel(const int16_t *__restrict__ src, uint32_t n_el, uint32_t srcU8Len,
+                                                                   long source_stride, long packet_stride, int max_packets,
+                                                                   const uint32_t *__restrict__ len, const int32_t *__restrict__ tab,
+                                                                   const int32_t *__restrict__ members, const uint8_t *__restrict__ mute,
+                                                                   int max_speakers, uint32_t floor, int decay_shift, uint32_t *__restrict__ env,
+                                                                   uint8_t *__restrict__ speaking, uint8_t *__restrict__ mute_out, int n_groups,
+                                                                   int n_slots) {
+    const int lane = (int)(threadIdx.x & 63u), waves = (int)(blockDim.x >> 6);
+    for (int w = (int)blockIdx.x * waves + (int)(threadIdx.x >> 6); w < n_slots; w += (int)gridDim.x * waves) {
+        const int slot = __builtin_amdgcn_readfirstlane(w);
+        const int32_t *mem = members + tab[2 * (size_t)slot];
+        int n = tab[2 * (size_t)slot + 1];  // 2 .. 32
+        n = n < 0 ? 0 : (n > kBridgeMaxParties ? kBridgeMaxParties : n);
+        int shift = 5;  // log2 of L
+        while ((n << shift) > 64) shift--;
+        const int L = 1 << shift, q = lane >> shift, sub = lane & (L - 1);
+        uint32_t sum[kLegMaxPackets];
+#pragma unroll
+        for (int k = 0; k < kLegMaxPackets; k++) sum[k] = 0;
+        if (q < n) {
+            const int32_t ri = mem[q];
+            if (ri >= 0 && ri < n_groups) {
+                const int16_t *rows = src + (size_t)ri * source_stride;
+#pragma unroll
+                for (int k = 0; k < kLegMaxPackets; k++)
+                    if (k < max_packets && len[(size_t)ri * max_packets + k] == srcU8Len)
+                        sum[k] = abs_sum_part(rows + (size_t)k * packet_stride, n_el, (uint32_t)sub, (uint32_t)L);
+            }
+        }
+        uint32_t best = 0;
+#pragma unroll
+        for (int k = 0; k < kLegMaxPackets; k++) {
+            uint32_t s = sum[k];
+            for (int o = L >> 1; o > 0; o >>= 1) s += (uint32_t)__shfl_xor((int)s, o);
+            best = s > best ? s : best;
+        }
+        // lane p = member p
+        const uint32_t level = (uint32_t)__shfl((int)best, (lane << shift) & 63);
+        const int32_t rl = lane < n ? mem[lane] : -1;
+        const bool member = rl >= 0 && rl < n_groups;
+        const size_t r = member ? (size_t)rl : 0;
+        uint32_t e = 0;
+        bool eligible = false;
+        if (member) {
+            e = speakers_env_next(env[r], level, decay_shift);
+            eligible = speakers_eligible(mute && mute[r], e, floor);
+        }
+        const unsigned long long eligible_lanes = __ballot(eligible);
+        int rank = 0;
+        for (int s = 0; s < n; s++) {  // s is wave-uniform: a lane read, no LDS traffic
+            const uint32_t es = (uint32_t)__builtin_amdgcn_readlane((int)e, s);
+            rank += ((eligible_lanes >> s) & 1ull) && speakers_outranks(es, s, e, lane);
+        }
+        if (member) {
+            const bool sp = eligible && rank < max_speakers;
+            env[r] = e;
+            speaking[r] = sp ? 1 : 0;
+            mute_out[r] = sp ? 0 : 1;
+        }
+    }
+}
+
 // ---- a cursor per leg (leg_cursor.h)
 // What the cursor kernel leaves for the load kernels.  Per ring: where the calls its leg makes in this launch start (a ring sample,
 // reduced into the ring), how many ring samples they cover (0: none, or muted), and the slot each came from.  Per layout slot: the
@@ -448,6 +532,15 @@ struct wmx_mix {
     wmx::LegSpanEntry *d_leg_span = nullptr;
     uint2 *d_leg_win = nullptr;
 };
+
+// rtp.hip's view of the mixer (wmx_rtp_egress_rings plays the rings itself) and wmx_mix_drain's bookkeeping for it
+wmx::MixPlayView wmx::mix_play_view(const wmx_mix *m) {
+    return MixPlayView{m->device, m->n_groups, m->chn, m->freq, m->ring_bytes, m->head_off, m->d_rings};
+}
+void wmx::mix_played(wmx_mix *m, uint32_t bytes) {
+    m->head_off = (m->head_off + bytes) % m->ring_bytes;
+    m->tick += bytes;
+}
 
 // What wmx_mix_load and wmx_mix_load_minus share on the host: where the call starts (the reference's cursor rule), the schedule of
 // its source format, and the cursor the call ends with.
@@ -1018,6 +1111,68 @@ int wmx_mix_select_speakers_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU
     WMX_LAUNCH_CHECK();
     return speakers_launch(m, m->conf.slots(), 0, d_src, srcU8Len, 0, source_stride, m->d_conf_tab, m->d_conf_members, d_mute, max_speakers, floor,
                            decay_shift, d_mute_out, s);
+}
+
+// Over the layout and the legs' packet slots, in front of wmx_mix_load_minus_legs: that call's addressing and d_len convention.
+int wmx_mix_select_speakers_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, long source_stride, long packet_stride, int max_packets,
+                                 const uint32_t *d_len, const uint8_t *d_mute, int max_speakers, uint32_t floor, int decay_shift,
+                                 uint8_t *d_mute_out, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    const int rcc = speakers_check("wmx_mix_select_speakers_legs", m, d_src, srcU8Len, max_speakers, decay_shift, d_mute_out);
+    if (rcc) return rcc;
+    if (!d_len) {
+        set_error("wmx_mix_select_speakers_legs: bad argument");
+        return WMX_EINVAL;
+    }
+    if (max_packets < 1 || max_packets > WMX_MIX_MAX_LEG_PACKETS) {
+        set_error("wmx_mix_select_speakers_legs: max_packets=%d must be 1 .. %d", max_packets, WMX_MIX_MAX_LEG_PACKETS);
+        return WMX_EINVAL;
+    }
+    const long n_el = (long)(srcU8Len / 2);
+    if ((max_packets > 1 && packet_stride < n_el) || (m->n_groups > 1 && source_stride < (long)(max_packets - 1) * packet_stride + n_el) ||
+        packet_stride < 0) {
+        set_error("wmx_mix_select_speakers_legs: rows of %ld elements overlap (packet_stride=%ld, source_stride=%ld, max_packets=%d)", n_el,
+                  packet_stride, source_stride, max_packets);
+        return WMX_EINVAL;
+    }
+    if (m->conf.n_conf < 1) {
+        set_error("wmx_mix_select_speakers_legs: no layout (wmx_mix_set_conferences)");
+        return WMX_EINVAL;
+    }
+    const int rcs = speakers_state(m);
+    if (rcs) return rcs;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(speakers_clear_kernel, dim3(stream_grid((size_t)m->n_groups, 256)), dim3(256), 0, s, m->d_speaking, d_mute_out, m->n_groups);
+    WMX_LAUNCH_CHECK();
+    const int n_slots = m->conf.slots();
+    if (n_slots < 1) return 0;
+    hipLaunchKernelGGL(select_speakers_legs_kernel, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0, s, d_src, srcU8Len / 2, srcU8Len,
+                       source_stride, packet_stride, max_packets, d_len, (const int32_t *)m->d_conf_tab, (const int32_t *)m->d_conf_members, d_mute,
+                       max_speakers, floor, decay_shift, m->d_env, m->d_speaking, d_mute_out, m->n_groups, n_slots);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// What a new call in a reused slot does to its ring: what the old call loaded ahead of the play head is gone.  Head and tick are the
+// mixer's, not the ring's, and stay.
+int wmx_mix_reset_rings(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m || (host_idx && n < 0)) return WMX_EINVAL;
+    for (int i = 0; host_idx && i < n; i++)
+        if (host_idx[i] < 0 || host_idx[i] >= m->n_groups) {
+            set_error("wmx_mix_reset_rings: ring %d is outside the mixer's %d", (int)host_idx[i], m->n_groups);
+            return WMX_EINVAL;
+        }
+    hipStream_t s = as_stream(stream);
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(m->d_rings, 0, (size_t)m->ring_bytes * m->n_groups, s));
+        return 0;
+    }
+    for (int i = 0; i < n; i++)  // a handful of legs at a time: one fill each, nothing of the list goes to the device
+        WMX_HIP(hipMemsetAsync((uint8_t *)m->d_rings + (size_t)host_idx[i] * m->ring_bytes, 0, m->ring_bytes, s));
+    return 0;
 }
 
 int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {

@@ -162,6 +162,66 @@ __global__ __launch_bounds__(256) void rtp_ingest_legs_kernel(const uint8_t *__r
     }
 }
 
+// Play and send in one kernel (wmx_rtp_egress_rings): what drain_kernel (mix.hip) followed by the egress kernels above do for a ring
+// of 1 x 8000, where the zoom is the identity -- the 160 samples at the ring head never pass through a PCM row in HBM.  One lane takes
+// FOUR codes, dealt over (ring, word) pairs.  WIDE_IN: the head is a multiple of four samples, so (the ring's length is one too) every
+// lane's four samples are one aligned 8-byte piece that does not straddle the ring's end: one load, one store of zeros (the play thread
+// zeroes what it has read, src/wmix.c:1351-1352).  Otherwise sample by sample, each reduced into the ring.  WIDE_OUT: datagram rows on
+// 4-byte boundaries, the codes and the header as 32-bit stores; otherwise byte by byte.
+template <bool WIDE_IN, bool WIDE_OUT>
+__global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, uint32_t head_sample, int law,
+                                                                uint32_t *seq, uint32_t *ts, uint8_t *__restrict__ packets, long packet_stride,
+                                                                int n_rings, int pt) {
+    const size_t total = (size_t)n_rings * kRtpWords;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int ring = (int)(t / kRtpWords), j = (int)(t - (size_t)ring * kRtpWords);
+        int16_t *rg = rings + (size_t)ring * ring_samples;
+        uint8_t *pkt = packets + (size_t)ring * packet_stride;
+        uint32_t pos = head_sample + 4u * (uint32_t)j;  // head_sample < ring_samples, 4 j < 160 <= ring_samples
+        pos -= pos >= ring_samples ? ring_samples : 0u;
+        int v[4];
+        if (WIDE_IN) {
+            uint2 *p = reinterpret_cast<uint2 *>(rg + pos);
+            const uint2 x = *p;
+            *p = make_uint2(0u, 0u);
+            v[0] = (int16_t)(x.x & 0xFFFFu), v[1] = (int16_t)(x.x >> 16), v[2] = (int16_t)(x.y & 0xFFFFu), v[3] = (int16_t)(x.y >> 16);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                uint32_t q = pos + (uint32_t)i;
+                q -= q >= ring_samples ? ring_samples : 0u;
+                v[i] = rg[q];
+                rg[q] = 0;
+            }
+        }
+        uint32_t c[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) c[i] = (uint32_t)(law == WMX_LAW_A ? enc_alaw(v[i]) : enc_ulaw(v[i])) & 0xFFu;
+        if (WIDE_OUT) {
+            *reinterpret_cast<uint32_t *>(pkt + kRtpHeader + 4 * j) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) pkt[kRtpHeader + 4 * j + i] = (uint8_t)c[i];
+        }
+        if (j == 0) {
+            const uint32_t tt = ts[ring] + (uint32_t)kRtpG711Payload;  // timestamp += ret / chn, before the send
+            const uint32_t sq = seq[ring] & 0xFFFFu;
+            // v = 2, p = x = 0, cc = 0 | m = 1, pt | seq, timestamp big endian on the wire | ssrc = 0 (src/wmixTask.c:1058)
+            const uint32_t h0 = (2u << 6) | ((0x80u | (uint32_t)pt) << 8) | ((sq >> 8) << 16) | ((sq & 0xFFu) << 24);
+            const uint32_t h1 = (tt >> 24) | (((tt >> 16) & 0xFFu) << 8) | (((tt >> 8) & 0xFFu) << 16) | ((tt & 0xFFu) << 24);
+            if (WIDE_OUT) {
+                uint32_t *hd = reinterpret_cast<uint32_t *>(pkt);
+                hd[0] = h0, hd[1] = h1, hd[2] = 0;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++) pkt[i] = (uint8_t)(h0 >> (8 * i)), pkt[4 + i] = (uint8_t)(h1 >> (8 * i)), pkt[8 + i] = 0;
+            }
+            ts[ring] = tt;
+            seq[ring] = (sq + 1) & 0xFFFFu;  // rtpHeader.seq++ after the send (uint16 wrap)
+        }
+    }
+}
+
 inline bool aligned_to(const void *p, long stride_bytes, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0 && stride_bytes % a == 0; }
 
 }  // namespace
@@ -288,6 +348,68 @@ int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, l
                            d_packets, leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw,
                            max_packets, n_legs);
     WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// Play and send in one launch: wmx_mix_drain(320 bytes) followed by wmx_rtp_egress(1, 8000 -> 1, 8000), byte for byte, for a mixer of
+// 1 x 8000 rings and as many senders as it has rings.
+int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet_stride, uint32_t *packet_bytes, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !m || !d_packets) {
+        set_error("wmx_rtp_egress_rings: bad arguments");
+        return WMX_EINVAL;
+    }
+    const MixPlayView v = mix_play_view(m);
+    if (v.chn != 1 || v.freq != kRtpG711Payload * 50) {
+        set_error("wmx_rtp_egress_rings: rings of %d x %d, not 1 x 8000 (wmx_mix_drain + wmx_rtp_egress convert)", v.chn, v.freq);
+        return WMX_EINVAL;
+    }
+    if (v.n_groups != h->n_streams) {
+        set_error("wmx_rtp_egress_rings: %d rings, %d senders", v.n_groups, h->n_streams);
+        return WMX_EINVAL;
+    }
+    if (v.device != h->device) {
+        set_error("wmx_rtp_egress_rings: the mixer is on device %d, the senders on %d", v.device, h->device);
+        return WMX_EINVAL;
+    }
+    if (packet_stride < kRtpHeader + kRtpG711Payload) {
+        set_error("wmx_rtp_egress_rings: packet_stride %ld < %d", packet_stride, kRtpHeader + kRtpG711Payload);
+        return WMX_EINVAL;
+    }
+    const uint32_t ring_samples = v.ring_bytes / 2, head_sample = (v.head_off / 2) % ring_samples;
+    const bool wide_in = head_sample % 4 == 0 && ring_samples % 4 == 0 && reinterpret_cast<uintptr_t>(v.d_rings) % 8 == 0;
+    const bool wide_out = aligned_to(d_packets, packet_stride, 4);
+    auto kernel = wide_in ? (wide_out ? rtp_egress_rings_kernel<true, true> : rtp_egress_rings_kernel<true, false>)
+                          : (wide_out ? rtp_egress_rings_kernel<false, true> : rtp_egress_rings_kernel<false, false>);
+    const int pt = h->law == WMX_LAW_A ? 8 : 0;  // RTP_PAYLOAD_TYPE_PCMA / PCMU, src/rtp.h:21-24
+    hipLaunchKernelGGL(kernel, dim3(wmx::stream_grid((size_t)h->n_streams * kRtpWords, 256)), dim3(256), 0, as_stream(stream), v.d_rings,
+                       ring_samples, head_sample, h->law, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt);
+    WMX_LAUNCH_CHECK();
+    mix_played(m, 2u * kRtpG711Payload);
+    if (packet_bytes) *packet_bytes = (uint32_t)(kRtpHeader + kRtpG711Payload);
+    return 0;
+}
+
+// seq = timestamp = 0 for the listed senders (NULL = all), on `stream`: what wmix_thread_rtp_send_pcma starts a call from
+// (src/wmixTask.c:1058)
+int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
+    for (int i = 0; host_idx && i < n; i++)
+        if (host_idx[i] < 0 || host_idx[i] >= h->n_streams) {
+            set_error("wmx_rtp_reset_streams: sender %d is outside the handle's %d", (int)host_idx[i], h->n_streams);
+            return WMX_EINVAL;
+        }
+    hipStream_t s = as_stream(stream);
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(h->d_seq, 0, sizeof(uint32_t) * h->n_streams, s));
+        WMX_HIP(hipMemsetAsync(h->d_ts, 0, sizeof(uint32_t) * h->n_streams, s));
+        return 0;
+    }
+    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
+        WMX_HIP(hipMemsetAsync(h->d_seq + host_idx[i], 0, sizeof(uint32_t), s));
+        WMX_HIP(hipMemsetAsync(h->d_ts + host_idx[i], 0, sizeof(uint32_t), s));
+    }
     return 0;
 }
 

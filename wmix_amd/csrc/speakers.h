@@ -90,4 +90,42 @@ inline void speakers_step(int n_groups, int n_conf, const int32_t *off, const in
     }
 }
 
+// ---- legs that deliver 0 .. max_packets packets in a tick (wmx_mix_select_speakers_legs, in front of wmx_mix_load_minus_legs)
+// The rule above with one change: slot k of a leg is a call if and only if len[k] == srcU8Len, and
+//   level = the maximum, over the slots of the leg that are calls, of speakers_level(row of that slot); no call this tick: 0
+// so a leg whose slot 0 is a hole and whose packet sits in a later slot is as loud as its packet.  `rows`: the leg's slot 0, slot k
+// packet_stride int16 elements behind it; `len`: the leg's max_packets entries.
+constexpr int kSpeakersMaxLegPackets = 4;  // WMX_MIX_MAX_LEG_PACKETS (include/wmix_amd.h)
+
+WMX_SPK_FN uint32_t speakers_level_legs(const int16_t *rows, long packet_stride, int max_packets, const uint32_t *len, uint32_t srcU8Len) {
+    uint32_t level = 0;
+    for (int k = 0; k < max_packets; k++) {
+        if (len[k] != srcU8Len) continue;
+        const uint32_t l = speakers_level(rows + (long)k * packet_stride, srcU8Len / 2);
+        level = l > level ? l : level;
+    }
+    return level;
+}
+
+// speakers_step for such legs: slot k of ring r at rows + r * source_stride + k * packet_stride, len[r * max_packets + k]
+inline void speakers_step_legs(int n_groups, int n_conf, const int32_t *off, const int32_t *members, const int16_t *rows, long source_stride,
+                               long packet_stride, int max_packets, const uint32_t *len, uint32_t srcU8Len, const uint8_t *host_mute,
+                               int max_speakers, uint32_t floor, int decay_shift, uint32_t *env, uint8_t *speaking, uint8_t *mute_out) {
+    for (int r = 0; r < n_groups; r++) speaking[r] = 0, mute_out[r] = 1;
+    for (int c = 0; c < n_conf; c++) {
+        const int n = off[c + 1] - off[c];
+        if (n < 2 || n > kSpeakersMaxParties) continue;
+        const int32_t *mem = members + off[c];
+        uint32_t level[kSpeakersMaxParties], e[kSpeakersMaxParties];
+        uint8_t muted[kSpeakersMaxParties], sp[kSpeakersMaxParties];
+        for (int p = 0; p < n; p++) {
+            level[p] = speakers_level_legs(rows + (long)mem[p] * source_stride, packet_stride, max_packets, len + (long)mem[p] * max_packets, srcU8Len);
+            e[p] = env[mem[p]];
+            muted[p] = host_mute && host_mute[mem[p]];
+        }
+        speakers_conference(n, level, muted, e, max_speakers, floor, decay_shift, sp);
+        for (int p = 0; p < n; p++) env[mem[p]] = e[p], speaking[mem[p]] = sp[p], mute_out[mem[p]] = !sp[p];
+    }
+}
+
 }  // namespace wmx

@@ -189,6 +189,15 @@ void chain_cohorts_when_made(wmx_chain *h, int n_cohorts, const int32_t *stream_
 // give the identity (the reference's memcpy branch).  Defined in mix.hip.
 void zoom_gather_list(int inChn, int inFreq, uint32_t inLen, int outChn, int outFreq, std::vector<int32_t> &idx);
 
+// rtp.hip -> mix.hip: what wmx_rtp_egress_rings reads of a mixer, and the advance of head and tick that wmx_mix_drain makes
+struct MixPlayView {
+    int device, n_groups, chn, freq;
+    uint32_t ring_bytes, head_off;
+    int16_t *d_rings;
+};
+MixPlayView mix_play_view(const wmx_mix *m);
+void mix_played(wmx_mix *m, uint32_t bytes);
+
 #ifdef __HIPCC__
 // Lane-per-stream kernels (VAD, AGC) walk their state field by field along a sequential dependency chain, one wave
 // per SIMD: every first touch of a field would expose a full HBM round trip.  touch_line() requests a line up front

@@ -157,6 +157,25 @@ class MixBatch:
                                                  out.data_ptr(), torch.cuda.current_stream().cuda_stream), "wmx_mix_select_speakers_conf")
         return out
 
+    def select_speakers_legs(self, src, src_bytes, lens, max_speakers, floor=0, decay_shift=3, mute=None, out=None):
+        """The same over leg packets (wmx_mix_select_speakers_legs), in front of load_minus_legs: src [n_groups, max_packets, >= src_bytes /
+        2] and lens [n_groups, max_packets] as there; a leg's level is the largest level among its slots that are calls, 0 without one."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.dim() == 3 and src.stride(2) == 1 and src.shape[0] == self.n_groups
+        assert lens.is_cuda and lens.dtype in (torch.int32, torch.uint32) and lens.is_contiguous() and tuple(lens.shape) == tuple(src.shape[:2])
+        mp, out = self._mute_pair(mute, out)
+        check(lib().wmx_mix_select_speakers_legs(self._h, src.data_ptr(), src_bytes, src.stride(0), src.stride(1), src.shape[1], lens.data_ptr(),
+                                                 mp, max_speakers, floor, decay_shift, out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+              "wmx_mix_select_speakers_legs")
+        return out
+
+    def reset_rings(self, rings=None):
+        """zero the listed rings (None = every ring): a new call in a reused slot does not hear what the old one loaded ahead"""
+        idx = None if rings is None else np.ascontiguousarray(rings, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_mix_reset_rings(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                        torch.cuda.current_stream().cuda_stream), "wmx_mix_reset_rings")
+
     def reset_speakers(self, rings=None):
         """env = 0 for the listed rings (None = every ring): what a new call in a reused slot does"""
         idx = None if rings is None else np.ascontiguousarray(rings, dtype=np.int32)

@@ -29,6 +29,27 @@ class RtpSenders:
               "wmx_rtp_egress")
         return packets[:, : size.value]
 
+    def egress_rings(self, mix, packets=None):
+        """Play and send in one kernel (wmx_rtp_egress_rings): the 20 ms at the head of every 1 x 8000 ring of `mix` (a MixBatch with as
+        many rings as there are senders) -> uint8 CUDA [n_streams, 172]; the rings are zeroed there and head and tick advance as in
+        MixBatch.drain(320)."""
+        if packets is None:
+            packets = torch.zeros((self.n, 172), dtype=torch.uint8, device="cuda")
+        assert packets.is_cuda and packets.dtype == torch.uint8 and packets.dim() == 2 and packets.shape[0] == self.n and packets.stride(1) == 1
+        size = C.c_uint32(0)
+        check(lib().wmx_rtp_egress_rings(self._h, mix._h, packets.data_ptr(), packets.stride(0), C.byref(size),
+                                         torch.cuda.current_stream().cuda_stream), "wmx_rtp_egress_rings")
+        return packets[:, : size.value]
+
+    def reset_streams(self, streams=None):
+        """seq = timestamp = 0 for the listed senders (None = all): a new call"""
+        import numpy as np
+        idx = None if streams is None else np.ascontiguousarray(streams, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_rtp_reset_streams(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                          torch.cuda.current_stream().cuda_stream), "wmx_rtp_reset_streams")
+
     def state(self, stream=0):
         s, t = C.c_uint16(0), C.c_uint32(0)
         check(lib().wmx_rtp_export(self._h, stream, C.byref(s), C.byref(t)), "wmx_rtp_export")
