@@ -1,6 +1,7 @@
 /* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
+ *             [--sequence G] [--audio-only]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -10,6 +11,10 @@
  * The network is the script of host_tick --bridge-rtp: one 64-bit LCG; per tick and leg u = next % 8 -- 0, 1: nothing arrives; 2: two
  * datagrams in slots 0 and 1; 3: two in slots 0 and 2, recvfrom said -1 for slot 1; else one in slot 0 -- and per datagram that arrives
  * v = next % 16 (0: payload type 96, not G.711; 1: PCMU; else PCMA), then 160 payload bytes next & 255; seq counts per leg.
+ * --sequence G: the legs are reordered, de-duplicated and gap-filled by RTP sequence number (wmx_conf_sequence, gaps of up to G packets
+ * become silence) and the JSON line also carries the five counters summed over the legs.  --audio-only: every datagram of the script is
+ * PCMA (v == 0 too), so the script has no gap of its own: a datagram of payload type 96 consumes a sequence number and brings no audio,
+ * which sequencing treats as a lost packet.
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -65,6 +70,7 @@ static int parse_sizes(const char *sizes, int32_t **off_out, int32_t **members_o
 }
 
 /* one tick of the network into a slot's rows */
+static int audio_only;
 static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) {
     long arrived = 0;
     memset(in, 0xEE, (size_t)G * RTP_SLOTS * row);
@@ -80,7 +86,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) 
             const uint32_t v = lcg_next() % 16;
             memset(pk, 0, 12);
             pk[0] = 2u << 6;
-            pk[1] = (uint8_t)(0x80 | (v == 0 ? 96 : (v == 1 ? 0 : 8)));
+            pk[1] = (uint8_t)(0x80 | (v == 0 && !audio_only ? 96 : (v == 1 ? 0 : 8)));
             pk[2] = (uint8_t)(seq[g] >> 8), pk[3] = (uint8_t)seq[g];
             seq[g]++;
             for (int i = 0; i < 160; i++) pk[12 + i] = (uint8_t)(lcg_next() & 255);
@@ -91,7 +97,8 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) 
 }
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]\n";
+    const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
+                        " [--sequence G] [--audio-only]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -99,7 +106,7 @@ int main(int argc, char **argv) {
     const int G = atoi(argv[2]), T = atoi(argv[3]);
     const char *sizes = NULL, *speakers = NULL, *platform = "alsa";
     unsigned long seed = 0;
-    int slots = 3, have_seed = 0;
+    int slots = 3, have_seed = 0, max_gap = -1; /* max_gap -1: sequencing off */
     long correct = -1; /* -1: the library's default = platform/alsa */
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
@@ -110,6 +117,11 @@ int main(int argc, char **argv) {
             slots = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "--speakers") && i + 1 < argc) {
             speakers = argv[++i];
+        } else if (!strcmp(argv[i], "--sequence") && i + 1 < argc) {
+            max_gap = atoi(argv[++i]);
+            if (max_gap < 0) max_gap = WMX_MIX_MAX_LEG_PACKETS; /* not a gap: the library says so */
+        } else if (!strcmp(argv[i], "--audio-only")) {
+            audio_only = 1;
         } else if (!strcmp(argv[i], "--platform") && i + 1 < argc) {
             platform = argv[++i];
             if (!strcmp(platform, "alsa")) {
@@ -146,6 +158,7 @@ int main(int argc, char **argv) {
     if (correct >= 0) WMX_OK(wmx_conf_set_play_correct(h, (uint32_t)correct));
     WMX_OK(wmx_conf_set_conferences(h, n_conf, conf_off, conf_members, NULL));
     if (speakers) WMX_OK(wmx_conf_speakers(h, max_speakers, (uint32_t)floor_level, shift));
+    if (max_gap >= 0) WMX_OK(wmx_conf_sequence(h, 1, max_gap));
     const int row = wmx_conf_in_row_bytes(h);
     uint8_t *out = calloc((size_t)T * G * RTP_BYTES, 1);
     uint16_t *seq = calloc((size_t)G, sizeof(uint16_t));
@@ -181,6 +194,15 @@ int main(int argc, char **argv) {
     WMX_OK(wmx_conf_export_legs(h, NULL, NULL, dropped, NULL, NULL, NULL));
     unsigned long n_dropped = 0;
     for (int g = 0; g < G; g++) n_dropped += dropped[g];
+    unsigned long seq_sum[5] = {0, 0, 0, 0, 0}; /* lost, late, dup, resync, overflow over the legs */
+    if (max_gap >= 0) {
+        uint32_t *cnt = calloc((size_t)G * 5, sizeof(uint32_t));
+        if (!cnt) return 2;
+        WMX_OK(wmx_conf_export_sequence(h, NULL, NULL, cnt, cnt + G, cnt + 2 * (size_t)G, cnt + 3 * (size_t)G, cnt + 4 * (size_t)G, NULL));
+        for (int c = 0; c < 5; c++)
+            for (int g = 0; g < G; g++) seq_sum[c] += cnt[(size_t)c * G + g];
+        free(cnt);
+    }
     uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
@@ -189,7 +211,11 @@ int main(int argc, char **argv) {
     if (f) fclose(f);
     printf("{\"groups\": %d, \"ticks\": %d, \"platform\": \"%s\", \"bridge_rtp_seed\": %lu, \"bridge_sizes\": [", G, T, platform, seed);
     for (int c = 0; c < n_conf; c++) printf("%s%d", c ? ", " : "", (int)(conf_off[c + 1] - conf_off[c]));
-    printf("], \"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
+    printf("], ");
+    if (max_gap >= 0)
+        printf("\"sequence\": %d, \"lost\": %lu, \"late\": %lu, \"dup\": %lu, \"resync\": %lu, \"overflow\": %lu, ", max_gap, seq_sum[0], seq_sum[1],
+               seq_sum[2], seq_sum[3], seq_sum[4]);
+    printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);
     return rc;

@@ -531,6 +531,17 @@ int wmx_mix_select_speakers_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU
 int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
                             long source_stride, long packet_stride, int max_packets, const uint32_t *d_len, const uint8_t *d_mute,
                             int reduce, void *stream);
+/* The same load fed a CALL LIST per leg instead of the valid slots in slot order (wmx_rtp_sequence_legs writes the lists).  d_calls:
+ * n_groups uint32 ON THE DEVICE, WMX_RTP_CALLS_* below; leg r makes WMX_RTP_CALLS_COUNT calls in list order, each with the cursor rule
+ * above.  A silence call is a call with zeros (WCT_SILENCE): the cursor moves by one packet, no ring changes; a column that only
+ * silence covers is not written.  d_len still says which rows are readable: a data call that names a slot k with
+ * d_len[r*max_packets + k] != srcU8Len (or k >= max_packets) is made as a silence call.  The lap rule drops from the list's tail and
+ * counts in dropped[r].  With every list "the valid slots in slot order, no silence" rings and cursors are byte for byte
+ * wmx_mix_load_minus_legs'.  Refuses what that call refuses, and a NULL d_calls, and a ring that does not hold
+ * WMX_MIX_MAX_LEG_PACKETS calls (a list may hold that many whatever max_packets is). */
+int wmx_mix_load_minus_legs_calls(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
+                                  long source_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                                  const uint32_t *d_calls, const uint8_t *d_mute, int reduce, void *stream);
 int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
 int wmx_mix_export_leg_cursors(const wmx_mix *m, uint32_t *host_head, uint32_t *host_tick, uint32_t *host_dropped, void *stream);
 /* wmx_mix_reset_rings: zero the n rings host_idx lists (NULL = every ring), on `stream`: a new call in a reused slot must not hear what
@@ -602,6 +613,41 @@ int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, l
 int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet_stride, uint32_t *packet_bytes, void *stream);
 int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
 int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timestamp);
+/* Reorder, de-duplicate and gap-fill legs by RTP sequence number, between wmx_rtp_ingest_legs and the selection / the load
+ * (wmix_amd/csrc/leg_seq.h holds the rule).  The reference makes one wmix_load_data call per datagram in arrival order and never reads
+ * the sequence number: a lost packet moves every later one 20 ms early, a duplicate is mixed twice, two packets swapped on the wire are
+ * mixed swapped.  Here the handle keeps, per leg (its n_streams), `synced` and `next` -- the sequence number of the next call position
+ * -- and the counters lost, late, dup, resync, overflow, ON THE DEVICE, and one launch (one lane per leg) decides which calls the leg
+ * makes this tick and in which order.  Slot k of leg r is `ok` when d_len[r*max_packets + k] == 320 (what ingest left; an unknown
+ * payload type is not ok, so a packet that consumed a sequence number without audio becomes a gap); its sequence number s is header
+ * byte 2 * 256 + byte 3, read from d_seq_raw (n_legs x max_packets, as wmx_rtp_ingest_legs leaves it, no ntohs: swapped here).
+ *   no slot ok: no calls, state unchanged.  Not synced: synced = 1, next = s of the first ok slot.
+ *   (uint16)(next - s) in 1 .. WMX_RTP_SEQ_MISORDER: LATE, discarded.  Every other ok slot is a candidate at forward distance
+ *   u = (uint16)(s - next); candidates ascending by u, ties by slot; the same u as the predecessor: a DUPlicate, discarded.
+ *   Walk with pos = 0: gap = u - pos; gap > max_gap: RESYNC (a sender that restarted; no silence, gap = 0); else the candidate needs
+ *   gap silence calls (LOST += gap) and one data call; when they do not fit in what is left of WMX_MIX_MAX_LEG_PACKETS calls it and
+ *   every later candidate are discarded (OVERFLOW counts them); else pos = u + 1.  A packet more than WMX_RTP_SEQ_MISORDER back is
+ *   far ahead in uint16 arithmetic and resyncs.  next += pos; no trailing silence -- what has not come may come next tick.
+ * d_calls[r] receives the list (WMX_RTP_CALLS_*): for wmx_mix_load_minus_legs_calls; every discarded slot gets d_len = 0, so talker
+ * selection behind this stage does not hear late packets or duplicates.  max_gap 0 .. 3.  No atomics, no host synchronisation, no
+ * upload, no allocation after the first call (wmx_rtp_reset_sequence counts as one).
+ * OUT OF SCOPE: placing a late packet into its still-unplayed gap; SSRC changes; timestamp-based placement; concealment other than
+ * silence.
+ * WMX_EINVAL, nothing launched, state unchanged: a NULL h, d_seq_raw, d_len or d_calls, max_packets outside 1 .. 4, max_gap outside
+ * 0 .. 3.
+ * wmx_rtp_reset_sequence: unsynced and counters 0 for the n legs host_idx lists (NULL = all), on `stream`: a new call may start at any
+ * sequence number.  A bad index: WMX_EINVAL, nothing reset.
+ * wmx_rtp_export_sequence: next (uint16), synced (uint8) and the counters (uint32), n_streams entries each, any pointer NULL, as the
+ * work queued on `stream` leaves them; blocking. */
+#define WMX_RTP_SEQ_MISORDER 16
+#define WMX_RTP_CALLS_COUNT(c) ((c) & 7u)                           /* 0 .. WMX_MIX_MAX_LEG_PACKETS */
+#define WMX_RTP_CALLS_SLOT(c, j) (((c) >> (4 + 4 * (j))) & 3u)      /* the slot call j reads */
+#define WMX_RTP_CALLS_SILENCE(c, j) (((c) >> (6 + 4 * (j))) & 1u)   /* call j is made with zeros */
+int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16_t *d_seq_raw, uint32_t *d_len, uint32_t *d_calls,
+                          void *stream);
+int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
+int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup,
+                            uint32_t *resync, uint32_t *overflow, void *stream);
 
 /* ------------------------------------------------------------------ the packet edge as a pipeline
  * What wmix_thread_rtp_recv_pcma, the record heartbeat and wmix_thread_rtp_send_pcma do for one stream per 20 ms
@@ -675,6 +721,11 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * the selection's mask into the load); wmx_conf_set_play_correct (wmx_mix_set_play_correct); wmx_conf_reset_legs: what a new call in a
  * used slot needs -- a fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0 -- for the n legs host_idx lists
  * (NULL = all).  wmx_conf_export_legs: head, tick, dropped, env (uint32) and speaking (uint8) of every leg, any pointer NULL; blocking.
+ * wmx_conf_sequence(h, on, max_gap): between submits.  Off (the default) is the launch sequence above, the reference's arrival order.
+ * On, a tick is wmx_rtp_ingest_legs (which then also leaves the sequence numbers) -> wmx_rtp_sequence_legs(max_gap) -> the selection
+ * if on (it sees the rewritten d_len) -> wmx_mix_load_minus_legs_calls -> wmx_rtp_egress_rings; its buffers are made at create.
+ * wmx_conf_reset_legs also resets the listed legs' sequence state: a new call may start at any sequence number without counting a
+ * resync.  wmx_conf_export_sequence: wmx_rtp_export_sequence of the handle's legs.  max_gap outside 0 .. 3: WMX_EINVAL.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -686,6 +737,9 @@ int wmx_conf_destroy(wmx_conf *h);
 int wmx_conf_set_conferences(wmx_conf *h, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream);
 int wmx_conf_mute(wmx_conf *h, const uint8_t *host_mask, void *stream);
 int wmx_conf_speakers(wmx_conf *h, int max_speakers, uint32_t floor, int decay_shift);
+int wmx_conf_sequence(wmx_conf *h, int on, int max_gap);
+int wmx_conf_export_sequence(wmx_conf *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup,
+                             uint32_t *resync, uint32_t *overflow, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
 int wmx_conf_slots(const wmx_conf *h);

@@ -43,7 +43,12 @@ examples/host_tick.c --bridge-rtp makes -- blocking copies, wmx_rtp_ingest_legs,
 wmx_rtp_egress; (b) wmx_conf with 3 slots, the arrivals already in the slots' pinned rows (a host's recvfrom writes there), the datagrams
 read where they land; (c) wmx_conf_step_resident alone on rows that are on the device.  The three send the same datagrams for the first
 ticks before any time is reported.  Beside them the device time (events) of wmx_mix_drain + wmx_rtp_egress and of wmx_rtp_egress_rings
-on twin mixers of as many rings.
+on twin mixers of as many rings.  And (d), (e): the handle and the resident step again with sequencing on (wmx_conf_sequence, max_gap 3).
+The script is a cycle of three ticks, so a leg's sequence numbers cannot count on for ever: they count through the cycle, and (d) and
+(e) forget the sequence state at the cycle's start (wmx_rtp_reset_sequence of every leg: one memset per three ticks, inside the timed
+region).  Every packet is then in order -- a data call in slot order, none is silence, none is discarded, every counter stays 0 -- so
+the load does the work it does with sequencing off and (d) - (b), (e) - (c) are the sequencer's launch, the call-list path of the load
+and a third of that memset.
 
     python tools_dev/bridge_bench.py --pipe --out profiles/bridge/bridge_pipe_bench.json"""
 import argparse
@@ -317,6 +322,10 @@ def conf_pipe(reps):
     pk = rng.integers(0, 256, (CYC, legs, 3, 176), dtype=np.uint8)
     pk[..., :12] = 0
     pk[..., 0], pk[..., 1] = 0x80, 0x88
+    there = recv > 0
+    before = np.cumsum(there.sum(axis=2), axis=0) - there.sum(axis=2)  # datagrams of the leg in the cycle's earlier ticks
+    number = np.where(there, before[:, :, None] + np.cumsum(there, axis=2) - 1, 0)  # sequence numbers that count through the cycle
+    pk[..., 2], pk[..., 3] = number >> 8, number & 255
     stream = torch.cuda.current_stream().cuda_stream
     # (a) the parent's composition
     tk, snd = TickBatch(legs, 1, stages=0), RtpSenders(legs)
@@ -368,6 +377,34 @@ def conf_pipe(reps):
         step["c"] += 1
         cr.step_resident(r_in[i], r_recv[i], r_out)
 
+    # (d), (e) the same two with sequencing on
+    cs = ConfBridge(legs, 3, 3)
+    ce = ConfBridge(legs, 1, 3)
+    for x in (cs, ce):
+        x.set_conferences(layout)
+        x.set_play_correct(0)
+        x.sequence(True, 3)
+    for k in range(3):
+        cs.rows_in[k][:] = pk[k]
+        cs.recv[k][:] = recv[k]
+    e_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+    step["d"] = step["e"] = 0
+
+    def new_cycle(bridge, i):
+        if i == 0:
+            check(L.wmx_rtp_reset_sequence(L.wmx_conf_senders(bridge._h), None, 0, stream), "wmx_rtp_reset_sequence")
+
+    def handle_seq():
+        new_cycle(cs, step["d"] % CYC)
+        step["d"] += 1
+        return cs.submit()
+
+    def resident_seq():
+        i = step["e"] % CYC
+        step["e"] += 1
+        new_cycle(ce, i)
+        ce.step_resident(r_in[i], r_recv[i], e_out)
+
     # ---- the same datagrams?
     for t in range(2 * CYC):
         a = parent().numpy().copy()
@@ -375,6 +412,10 @@ def conf_pipe(reps):
         cb.wait(k)
         resident()
         assert np.array_equal(a, cb.rows_out[k]) and np.array_equal(a, r_out.cpu().numpy()), ("datagrams differ, tick", t)
+        k = handle_seq()
+        cs.wait(k)
+        resident_seq()
+        assert np.array_equal(a, cs.rows_out[k]) and np.array_equal(a, e_out.cpu().numpy()), ("datagrams differ with sequencing on, tick", t)
         assert (a[:, 12:] != 0xD5).any()
 
     def wall(f, n, end):
@@ -385,13 +426,18 @@ def conf_pipe(reps):
         return (time.perf_counter() - t0) * 1e3 / n
 
     per_block = max(reps // BLOCKS, 8)
-    ms = {"a": [], "b": [], "c": []}
+    ms = {"a": [], "b": [], "c": [], "d": [], "e": []}
     for _ in range(BLOCKS + 1):  # the first block warms up
         ms["a"].append(wall(parent, per_block, torch.cuda.synchronize))
         ms["b"].append(wall(handle, per_block, lambda: cb.wait(-1)))
         ms["c"].append(wall(resident, per_block, torch.cuda.synchronize))
+        ms["d"].append(wall(handle_seq, per_block, lambda: cs.wait(-1)))
+        ms["e"].append(wall(resident_seq, per_block, torch.cuda.synchronize))
     side = lambda v: {"median_ms_per_tick": round(float(np.median(v[1:])), 5), "block_ms_per_tick": [round(x, 5) for x in v[1:]]}  # noqa: E731
-    a, b, c = side(ms["a"]), side(ms["b"]), side(ms["c"])
+    a, b, c, d, e = side(ms["a"]), side(ms["b"]), side(ms["c"]), side(ms["d"]), side(ms["e"])
+    sq = cs.export_sequence()
+    seq_counters = {name: int(sq[name].sum()) for name in ("lost", "late", "dup", "resync", "overflow")}
+    assert not any(seq_counters.values()), seq_counters  # the script is in order
     dropped = {"conf": int(cb.export_legs()["dropped"].sum()), "resident": int(cr.export_legs()["dropped"].sum())}
     # ---- the fused play-and-send kernel beside the pair it replaces
     pair, fused, s2, s3 = MixBatch(legs, 1, 8000), MixBatch(legs, 1, 8000), RtpSenders(legs), RtpSenders(legs)
@@ -407,11 +453,14 @@ def conf_pipe(reps):
     t_pair, t_fused = alternate([drain_then_egress, egress_rings], reps)
     assert torch.equal(p_out, f_out)
     kp, kf = stats(t_pair), stats(t_fused)
-    for x in (tk, snd, cb, cr, pair, fused, s2, s3):
+    for x in (tk, snd, cb, cr, cs, ce, pair, fused, s2, s3):
         x.close()
     return {"conferences": n_conf, "sizes": {str(k): sizes.count(k) for k in sorted(set(sizes))}, "legs": legs, "max_packets": 3,
             "packets_per_leg_and_tick": round(float((recv > 0).sum()) / (CYC * legs), 3), "ticks_per_block": per_block, "datagram_ticks_checked": 2 * CYC,
             "a_host_tick_bridge_rtp_composition": a, "b_wmx_conf_3_slots": b, "c_step_resident": c,
+            "d_wmx_conf_3_slots_sequencing_on": d, "e_step_resident_sequencing_on": e,
+            "d_minus_b_ms": round(d["median_ms_per_tick"] - b["median_ms_per_tick"], 5),
+            "e_minus_c_ms": round(e["median_ms_per_tick"] - c["median_ms_per_tick"], 5), "sequence_counters_of_d": seq_counters,
             "b_over_c": round(b["median_ms_per_tick"] / c["median_ms_per_tick"], 3), "a_over_b": round(a["median_ms_per_tick"] / b["median_ms_per_tick"], 3),
             "b_nearer_to_c_than_to_a": bool(b["median_ms_per_tick"] - c["median_ms_per_tick"] < a["median_ms_per_tick"] - b["median_ms_per_tick"]),
             "calls_dropped": dropped, "drain_then_egress": kp, "egress_rings": kf,

@@ -53,11 +53,26 @@ class ConfBridge:
         """talker selection in front of the load (0 = off)"""
         check(lib().wmx_conf_speakers(self._h, max_speakers, floor, decay_shift), "wmx_conf_speakers")
 
+    def sequence(self, on, max_gap=3):
+        """reorder, de-duplicate and gap-fill the legs by RTP sequence number (wmx_conf_sequence); off = the reference's arrival order"""
+        check(lib().wmx_conf_sequence(self._h, 1 if on else 0, max_gap), "wmx_conf_sequence")
+
+    def export_sequence(self):
+        """dict(next: uint16, synced: uint8, lost, late, dup, resync, overflow: uint32; [n_legs] each) as the work queued on the current
+        stream leaves them"""
+        r = {k: np.zeros(self.n_legs, np.uint32) for k in ("lost", "late", "dup", "resync", "overflow")}
+        r["next"], r["synced"] = np.zeros(self.n_legs, np.uint16), np.zeros(self.n_legs, np.uint8)
+        check(lib().wmx_conf_export_sequence(self._h, r["next"].ctypes.data, r["synced"].ctypes.data, r["lost"].ctypes.data, r["late"].ctypes.data,
+                                             r["dup"].ctypes.data, r["resync"].ctypes.data, r["overflow"].ctypes.data, self._stream()),
+              "wmx_conf_export_sequence")
+        return r
+
     def set_play_correct(self, n_bytes):
         check(lib().wmx_conf_set_play_correct(self._h, n_bytes), "wmx_conf_set_play_correct")
 
     def reset_legs(self, legs=None):
-        """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0 (None = every leg)"""
+        """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced
+        (None = every leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

@@ -7,6 +7,9 @@
 //
 //     host rows --H2D--> wmx_rtp_ingest_legs -> [wmx_mix_select_speakers_legs] -> wmx_mix_load_minus_legs -> wmx_rtp_egress_rings --D2H--> host
 //
+// With sequencing on (wmx_conf_sequence) the ingest also leaves the sequence numbers, wmx_rtp_sequence_legs turns them into a call list
+// per leg and rewrites d_len in front of the selection, and the load is wmx_mix_load_minus_legs_calls.
+//
 // PER SLOT (made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a 4-byte
 // boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and three events.  PER HANDLE: the mixer
 // (rings, layout, leg cursors, envelopes), the senders, the PCM rows between ingest and load, d_len, the host's mute and the mask
@@ -31,6 +34,10 @@ struct wmx_conf {
     wmx_rtp *snd;
     int16_t *d_pcm;    // [n_legs][max_packets][160] between ingest and load
     uint32_t *d_len;   // [n_legs][max_packets] 320 for a slot that is a call
+    uint16_t *d_seq;   // [n_legs][max_packets] header bytes 2..3 as stored (sequencing on)
+    uint32_t *d_calls; // [n_legs] the call list the sequencer leaves for the load
+    bool seq_on;
+    int max_gap;
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -53,8 +60,13 @@ struct wmx_conf {
 // the launches of one tick on rows that are on the device
 static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream) {
     const int K = h->max_packets;
-    int rc = wmx_rtp_ingest_legs(h->n_legs, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len, nullptr, stream);
+    int rc = wmx_rtp_ingest_legs(h->n_legs, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len,
+                                 h->seq_on ? h->d_seq : nullptr, stream);
     if (rc != 0) return rc;
+    if (h->seq_on) {  // in front of the selection: it must not hear a late packet or a duplicate
+        rc = wmx_rtp_sequence_legs(h->snd, K, h->max_gap, h->d_seq, h->d_len, h->d_calls, stream);
+        if (rc != 0) return rc;
+    }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
     if (h->max_speakers > 0) {
         rc = wmx_mix_select_speakers_legs(h->mix, h->d_pcm, kPcmBytes, (long)K * kPcmRow, kPcmRow, K, h->d_len, host_mute, h->max_speakers, h->floor,
@@ -62,7 +74,11 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         if (rc != 0) return rc;
         load_mute = h->d_mask;
     }
-    rc = wmx_mix_load_minus_legs(h->mix, h->d_pcm, kPcmBytes, 8000, 1, 16, (long)K * kPcmRow, kPcmRow, K, h->d_len, load_mute, 1, stream);
+    if (h->seq_on)
+        rc = wmx_mix_load_minus_legs_calls(h->mix, h->d_pcm, kPcmBytes, 8000, 1, 16, (long)K * kPcmRow, kPcmRow, K, h->d_len, h->d_calls, load_mute, 1,
+                                           stream);
+    else
+        rc = wmx_mix_load_minus_legs(h->mix, h->d_pcm, kPcmBytes, 8000, 1, 16, (long)K * kPcmRow, kPcmRow, K, h->d_len, load_mute, 1, stream);
     if (rc != 0) return rc;
     uint32_t bytes = 0;
     rc = wmx_rtp_egress_rings(h->snd, h->mix, d_out, kOutRow, &bytes, stream);
@@ -96,6 +112,7 @@ int wmx_conf_destroy(wmx_conf *h) {
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
     if (h->d_pcm) (void)hipFree(h->d_pcm);
     if (h->d_len) (void)hipFree(h->d_len);
+    if (h->d_calls) (void)hipFree(h->d_calls);  // d_seq lies behind it
     if (h->d_mute) (void)hipFree(h->d_mute);  // d_mask lies behind it
     if (h->h_mute) (void)hipHostFree(h->h_mute);
     if (h->mix) wmx_mix_destroy(h->mix);
@@ -128,9 +145,14 @@ int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int 
     // the cursors and the envelopes are made by the first call that needs them: here, so that no submit allocates
     if (rc == 0) rc = wmx_mix_reset_leg_cursors(h->mix, nullptr, 0, nullptr);
     if (rc == 0) rc = wmx_mix_reset_speakers(h->mix, nullptr, 0, nullptr);
+    if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, nullptr, 0, nullptr);
     if (rc == 0) {
         hipError_t e = hipMalloc(&h->d_pcm, rows * kPcmRow * sizeof(int16_t));
         if (e == hipSuccess) e = hipMalloc(&h->d_len, rows * sizeof(uint32_t));
+        const size_t calls_bytes = (size_t)n_legs * sizeof(uint32_t), seq_bytes = rows * sizeof(uint16_t);
+        if (e == hipSuccess) e = hipMalloc(&h->d_calls, calls_bytes + 4 + seq_bytes);
+        if (e == hipSuccess) e = hipMemset(h->d_calls, 0, calls_bytes + 4 + seq_bytes);
+        if (e == hipSuccess) h->d_seq = reinterpret_cast<uint16_t *>(h->d_calls + (n_legs + 1) / 2 * 2);  // on an 8-byte boundary
         if (e == hipSuccess) e = hipMalloc(&h->d_mute, 2 * (size_t)n_legs);
         if (e == hipSuccess) e = hipMemset(h->d_mute, 0, 2 * (size_t)n_legs);
         if (e == hipSuccess) e = hipMemset(h->d_len, 0, rows * sizeof(uint32_t));
@@ -201,9 +223,22 @@ int wmx_conf_speakers(wmx_conf *h, int max_speakers, uint32_t floor, int decay_s
     return 0;
 }
 
+// on != 0: the legs' packets are put in sequence order, late packets and duplicates make no call and a gap of up to max_gap packets
+// becomes silence calls (wmx_rtp_sequence_legs); 0: the reference's arrival order.  Between submits.
+int wmx_conf_sequence(wmx_conf *h, int on, int max_gap) {
+    if (!h) return WMX_EINVAL;
+    if (max_gap < 0 || max_gap > WMX_MIX_MAX_LEG_PACKETS - 1) {
+        wmx::set_error("wmx_conf_sequence: max_gap=%d must be 0 .. %d", max_gap, WMX_MIX_MAX_LEG_PACKETS - 1);
+        return WMX_EINVAL;
+    }
+    h->seq_on = on != 0;
+    h->max_gap = max_gap;
+    return 0;
+}
+
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
 
-// a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0
+// a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
     for (int i = 0; host_idx && i < n; i++)  // before the first of the four: a bad index resets nothing
@@ -215,6 +250,7 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0) rc = wmx_mix_reset_speakers(h->mix, host_idx, n, stream);
     if (rc == 0) rc = wmx_mix_reset_rings(h->mix, host_idx, n, stream);
     if (rc == 0) rc = wmx_rtp_reset_streams(h->snd, host_idx, n, stream);
+    if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, host_idx, n, stream);
     return rc;
 }
 
@@ -335,6 +371,13 @@ int wmx_conf_poll(wmx_conf *h, int slot) {
         }
     }
     return done;
+}
+
+// the sequence rule's state of every leg (wmx_rtp_export_sequence); any pointer may be NULL; blocking
+int wmx_conf_export_sequence(wmx_conf *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup, uint32_t *resync,
+                             uint32_t *overflow, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_export_sequence(h->snd, next, synced, lost, late, dup, resync, overflow, stream);
 }
 
 // head, tick, dropped (uint32), env (uint32) and speaking (uint8) of every leg as the work queued on `stream` leaves them; any pointer

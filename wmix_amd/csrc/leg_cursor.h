@@ -103,4 +103,31 @@ WMX_LEG_FN LegSpan leg_cursor_span(const LegMixState &m, uint32_t n_out, LegCurs
     return s;
 }
 
+// The same for a call list (leg_seq.h: count in bits 0..2, call j in bits 4+4j..: two bits of source slot, one bit "silence"), in
+// list order.  A silence call is a call with zeros (WCT_SILENCE, src/wmixTask.c:1307-1309): it moves the cursor by n_out like a data
+// call and can jump or drop like one.  `silence`: bit j set when the j-th call MADE adds nothing.
+struct LegSpanCalls {
+    LegSpan span;
+    uint32_t silence;
+};
+
+WMX_LEG_FN LegSpanCalls leg_cursor_span_calls(const LegMixState &m, uint32_t n_out, LegCursor c, uint32_t calls) {
+    LegSpanCalls s{LegSpan{0u, 0u, 0u, 0u, c}, 0u};
+    uint32_t n = calls & 7u;
+    n = n > (uint32_t)kLegMaxPackets ? (uint32_t)kLegMaxPackets : n;
+    for (uint32_t j = 0; j < n; j++) {
+        const LegCall call = leg_cursor_call(m, n_out, s.span.after);
+        if (call.drop) {  // the lap rule: this call and the list's tail are left out
+            s.span.dropped = n - j;
+            break;
+        }
+        if (s.span.count == 0) s.span.start = call.start;
+        s.span.slots |= ((calls >> (4u + 4u * j)) & 3u) << (2u * s.span.count);
+        s.silence |= ((calls >> (6u + 4u * j)) & 1u) << s.span.count;
+        s.span.count++;
+        s.span.after = call.after;
+    }
+    return s;
+}
+
 }  // namespace wmx

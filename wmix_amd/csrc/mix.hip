@@ -364,12 +364,17 @@ struct LegSpanEntry {
 // slots are calls (d_len), applies the rule (at most WMX_MIX_MAX_LEG_PACKETS steps) and writes the span, the new cursor and the drop
 // count; an xor-shuffle over the wave gives the window.  Rings outside every conference of two or more members are not visited:
 // their cursors stay.  A cursor read from memory never indexes anything as it is: the span's start is reduced into the ring here.
+// CALLS (wmx_mix_load_minus_legs_calls): the leg's calls are those of its call list (leg_seq.h), in list order, instead of its valid
+// slots in slot order; a data call that names a slot that is not readable (d_len) is made with zeros, and the span's pad carries the
+// silence mask of the calls made.
+template <bool CALLS>
 __global__ __launch_bounds__(256) void leg_cursor_kernel(const int32_t *__restrict__ tab, const int32_t *__restrict__ members,
                                                          const uint32_t *__restrict__ len, uint32_t srcU8Len, int max_packets,
                                                          const uint8_t *__restrict__ mute, LegMixState ms, uint32_t n_out,
                                                          uint32_t *__restrict__ head, uint32_t *__restrict__ tick,
                                                          uint32_t *__restrict__ dropped, LegSpanEntry *__restrict__ span,
-                                                         uint2 *__restrict__ win, int n_groups, int n_slots) {
+                                                         uint2 *__restrict__ win, int n_groups, int n_slots,
+                                                         const uint32_t *__restrict__ calls) {
     const int lane = (int)(threadIdx.x & 63u), waves = (int)(blockDim.x >> 6);
     const uint32_t ring_samples = ms.ring_bytes / 2, head_sample = (ms.head_off / 2) % ring_samples;
     for (int w = (int)blockIdx.x * waves + (int)(threadIdx.x >> 6); w < n_slots; w += (int)gridDim.x * waves) {
@@ -384,12 +389,28 @@ __global__ __launch_bounds__(256) void leg_cursor_kernel(const int32_t *__restri
                 uint32_t valid = 0;
                 for (int k = 0; k < kLegMaxPackets; k++)
                     if (k < max_packets && len[(size_t)r * max_packets + k] == srcU8Len) valid |= 1u << k;
+                uint32_t list = 0, silence = 0;
+                if (CALLS) {
+                    list = calls[r];
+                    uint32_t n_calls = list & 7u;
+                    n_calls = n_calls > (uint32_t)kLegMaxPackets ? (uint32_t)kLegMaxPackets : n_calls;
+                    for (uint32_t j = 0; j < n_calls; j++)  // a data call whose slot's row is not readable: a call with zeros
+                        if (!((valid >> ((list >> (4u + 4u * j)) & 3u)) & 1u)) list |= 1u << (6u + 4u * j);
+                    valid = n_calls;
+                }
                 if (valid) {
-                    const LegSpan s = leg_cursor_span(ms, n_out, LegCursor{head[r], tick[r]}, valid, max_packets);
+                    LegSpan s;
+                    if (CALLS) {
+                        const LegSpanCalls sc = leg_cursor_span_calls(ms, n_out, LegCursor{head[r], tick[r]}, list);
+                        s = sc.span;
+                        silence = sc.silence;
+                    } else {
+                        s = leg_cursor_span(ms, n_out, LegCursor{head[r], tick[r]}, valid, max_packets);
+                    }
                     head[r] = s.after.head;
                     tick[r] = s.after.tick;
                     if (s.dropped) dropped[r] += s.dropped;
-                    LegSpanEntry e{(s.start / 2) % ring_samples, (mute && mute[r]) ? 0u : s.count * n_out, s.slots, 0u};
+                    LegSpanEntry e{(s.start / 2) % ring_samples, (mute && mute[r]) ? 0u : s.count * n_out, s.slots, silence};
                     span[r] = e;
                     if (e.len) {
                         lo = e.start >= head_sample ? e.start - head_sample : e.start + ring_samples - head_sample;
@@ -421,8 +442,9 @@ __global__ __launch_bounds__(256) void leg_cursor_kernel(const int32_t *__restri
 // scalar loads); a window longer than that is walked in strides of n_pad, a wave whose first column lies behind the window's end
 // exits.  A source whose span does not cover the column adds 0, which is what not calling wmix_load_data leaves; a column no
 // source covers is not written.  A leg's span covers no ring sample twice (leg_cursor.h), a ring is in one conference only and a
-// column is one thread's: no two threads touch the same ring sample.
-template <int PMAX>
+// column is one thread's: no two threads touch the same ring sample.  CALLS: a call whose bit in the span's silence mask (pad) is set
+// adds 0 like a source that does not cover the column.
+template <int PMAX, bool CALLS>
 __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
                                                               const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t n_pad,
                                                               const int32_t *__restrict__ tab, const uint2 *__restrict__ win,
@@ -454,9 +476,11 @@ __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restric
                     const uint32_t d = pos >= st ? pos - st : pos + ring_samples - st;
                     if (d < e.len && d < (uint32_t)kLegMaxPackets * n_out) {
                         const uint32_t j = (d >= n_out) + (d >= 2 * n_out) + (d >= 3 * n_out);  // the call, 0 .. 3, and its sample
-                        const uint32_t k = (e.slots >> (2u * j)) & 3u;
-                        c[q] = load_entry_value(src + r * source_stride + (size_t)k * packet_stride, sch[d - j * n_out], rdce);
-                        any = true;
+                        if (!CALLS || !((e.pad >> j) & 1u)) {
+                            const uint32_t k = (e.slots >> (2u * j)) & 3u;
+                            c[q] = load_entry_value(src + r * source_stride + (size_t)k * packet_stride, sch[d - j * n_out], rdce);
+                            any = true;
+                        }
                     }
                     y[q] = clamp_map_apply(f, rings[r * ring_samples + pos]);
                     f = clamp_map_then_add(f, (int16_t)c[q]);
@@ -919,32 +943,35 @@ static int legs_state(wmx_mix *m) {
 }
 
 // The bridge load with a cursor per leg: the cursor kernel (one wave per conference), then at most one load launch per non-empty size
-// class.  Which slots are calls is known on the device only, so nothing of the cursors passes through the host.
-int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, long source_stride,
-                            long packet_stride, int max_packets, const uint32_t *d_len, const uint8_t *d_mute, int reduce, void *stream) {
+// class.  Which slots are calls is known on the device only, so nothing of the cursors passes through the host.  d_calls: NULL for
+// wmx_mix_load_minus_legs (the valid slots in slot order), the call lists for wmx_mix_load_minus_legs_calls.
+static int load_minus_legs_any(const char *who, wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
+                               long source_stride, long packet_stride, int max_packets, const uint32_t *d_len, const uint32_t *d_calls,
+                               bool with_calls, const uint8_t *d_mute, int reduce, void *stream) {
     WMX_ON_DEVICE(m);
     using namespace wmx;
-    if (!m || !d_src || !d_len) {
-        set_error("wmx_mix_load_minus_legs: bad argument");
+    if (!m || !d_src || !d_len || (with_calls && !d_calls)) {
+        set_error("%s: bad argument", who);
         return WMX_EINVAL;
     }
     if (m->conf.n_conf < 1) {
-        set_error("wmx_mix_load_minus_legs: no layout (wmx_mix_set_conferences)");
+        set_error("%s: no layout (wmx_mix_set_conferences)", who);
         return WMX_EINVAL;
     }
     if (max_packets < 1 || max_packets > WMX_MIX_MAX_LEG_PACKETS) {
-        set_error("wmx_mix_load_minus_legs: max_packets=%d must be 1 .. %d", max_packets, WMX_MIX_MAX_LEG_PACKETS);
+        set_error("%s: max_packets=%d must be 1 .. %d", who, max_packets, WMX_MIX_MAX_LEG_PACKETS);
         return WMX_EINVAL;
     }
     if (srcU8Len < 1) return 0;  // like wmx_mix_load
     uint32_t h0 = 0, t0 = m->tick;  // a cursor the rule leaves alone keeps load_begin to the schedule and wmx_mix_load's refusals
     SchedCache::Entry *ent = nullptr;
-    const int rcb = load_begin(m, "wmx_mix_load_minus_legs", srcU8Len, freq, channels, sample, h0, t0, &ent);
+    const int rcb = load_begin(m, who, srcU8Len, freq, channels, sample, h0, t0, &ent);
     if (rcb) return rcb;
     const uint32_t n_out = (uint32_t)ent->n;
-    if ((uint64_t)n_out * (uint32_t)max_packets > m->ring_bytes / 2) {
-        set_error("wmx_mix_load_minus_legs: %d packets of %u output samples do not fit the %u-sample ring in one call", max_packets, n_out,
-                  m->ring_bytes / 2);
+    // a call list holds up to WMX_MIX_MAX_LEG_PACKETS calls whatever max_packets is: silence calls need no slot
+    const int span_calls = with_calls ? WMX_MIX_MAX_LEG_PACKETS : max_packets;
+    if ((uint64_t)n_out * (uint32_t)span_calls > m->ring_bytes / 2) {
+        set_error("%s: %d packets of %u output samples do not fit the %u-sample ring in one call", who, span_calls, n_out, m->ring_bytes / 2);
         return WMX_EINVAL;
     }
     const int rcs = legs_state(m);
@@ -954,17 +981,24 @@ int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
     const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
     hipStream_t s = as_stream(stream);
     const LegMixState ms{m->head_off, m->tick, m->play_correct, m->ring_bytes};
-    hipLaunchKernelGGL(leg_cursor_kernel, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0, s, (const int32_t *)m->d_conf_tab,
-                       (const int32_t *)m->d_conf_members, d_len, srcU8Len, max_packets, d_mute, ms, n_out, m->d_leg_head, m->d_leg_tick,
-                       m->d_leg_dropped, m->d_leg_span, m->d_leg_win, m->n_groups, n_slots);
+    hipLaunchKernelGGL(with_calls ? leg_cursor_kernel<true> : leg_cursor_kernel<false>, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0,
+                       s, (const int32_t *)m->d_conf_tab, (const int32_t *)m->d_conf_members, d_len, srcU8Len, max_packets, d_mute, ms, n_out,
+                       m->d_leg_head, m->d_leg_tick, m->d_leg_dropped, m->d_leg_span, m->d_leg_win, m->n_groups, n_slots, d_calls);
     WMX_LAUNCH_CHECK();
     // whole waves per conference, enough for the longest window of legs that write side by side; a longer one is walked in strides
-    const uint32_t n_pad = (n_out * (uint32_t)max_packets + 63) / 64 * 64;
+    const uint32_t n_pad = (n_out * (uint32_t)span_calls + 63) / 64 * 64;
     for (int k = 0; k < kBridgeClasses; k++) {
         const int first = m->conf.class_begin[k], n_class = m->conf.class_begin[k + 1] - first;
         if (!n_class) continue;
         const unsigned grid = stream_grid((size_t)n_pad * n_class, 256);
-        auto kernel = k == 0 ? load_minus_legs_kernel<4> : k == 1 ? load_minus_legs_kernel<8> : k == 2 ? load_minus_legs_kernel<16> : load_minus_legs_kernel<32>;
+        auto kernel = with_calls ? (k == 0   ? load_minus_legs_kernel<4, true>
+                                    : k == 1 ? load_minus_legs_kernel<8, true>
+                                    : k == 2 ? load_minus_legs_kernel<16, true>
+                                             : load_minus_legs_kernel<32, true>)
+                                 : (k == 0   ? load_minus_legs_kernel<4, false>
+                                    : k == 1 ? load_minus_legs_kernel<8, false>
+                                    : k == 2 ? load_minus_legs_kernel<16, false>
+                                             : load_minus_legs_kernel<32, false>);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out, n_pad,
                            (const int32_t *)m->d_conf_tab + 2 * (size_t)first, (const uint2 *)m->d_leg_win + first,
                            (const LegSpanEntry *)m->d_leg_span, (const int32_t *)m->d_conf_members, source_stride, packet_stride, rdce,
@@ -972,6 +1006,20 @@ int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
         WMX_LAUNCH_CHECK();
     }
     return m->sched.used(ent, s);
+}
+
+int wmx_mix_load_minus_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, long source_stride,
+                            long packet_stride, int max_packets, const uint32_t *d_len, const uint8_t *d_mute, int reduce, void *stream) {
+    return load_minus_legs_any("wmx_mix_load_minus_legs", m, d_src, srcU8Len, freq, channels, sample, source_stride, packet_stride, max_packets,
+                               d_len, nullptr, false, d_mute, reduce, stream);
+}
+
+// The same with a call list per leg (wmx_rtp_sequence_legs): calls in list order, a silence call moves the cursor and adds nothing.
+int wmx_mix_load_minus_legs_calls(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, long source_stride,
+                                  long packet_stride, int max_packets, const uint32_t *d_len, const uint32_t *d_calls, const uint8_t *d_mute,
+                                  int reduce, void *stream) {
+    return load_minus_legs_any("wmx_mix_load_minus_legs_calls", m, d_src, srcU8Len, freq, channels, sample, source_stride, packet_stride,
+                               max_packets, d_len, d_calls, true, d_mute, reduce, stream);
 }
 
 int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {

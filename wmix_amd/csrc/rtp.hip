@@ -11,6 +11,7 @@
 #include <vector>
 #include "wmx_internal.h"
 #include "g711_dev.h"
+#include "leg_seq.h"
 
 struct wmx_rtp {
     int device;  // the HIP device the state lives on (current device at create); every entry point switches to it
@@ -19,6 +20,9 @@ struct wmx_rtp {
     uint32_t *d_ts;   // per stream: timestamp
     wmx::SchedCache sched;  // gather list per egress format, never rewritten (see SchedCache)
     std::vector<int32_t> idx;
+    // the sequence rule's state per leg (leg_seq.h), made by the first call that needs it: kSeqWords arrays of n_streams uint32 in
+    // one block -- synced, next, lost, late, dup, resync, overflow
+    uint32_t *d_sq;
 };
 
 namespace wmx {
@@ -222,6 +226,52 @@ __global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restri
     }
 }
 
+// The sequence rule (leg_seq.h) for every leg, one lane per leg: the lane reads its leg's up to four slots (d_len: which are calls;
+// d_seq_raw: header bytes 2..3 as stored, swapped here), sorts the candidates' keys in registers, walks them, writes the call list,
+// zeroes d_len of the slots that make no call and stores the state it read.  WIDE: max_packets == 4 and d_seq_raw on an 8-byte
+// boundary -- the four sequence numbers are one 8-byte load.  No lane touches another leg's words: no atomics.
+constexpr int kSeqWords = 7;
+template <bool WIDE>
+__global__ __launch_bounds__(256) void rtp_sequence_legs_kernel(const uint16_t *__restrict__ seq_raw, uint32_t *__restrict__ len,
+                                                                 uint32_t *__restrict__ calls, uint32_t *__restrict__ sq, int max_packets,
+                                                                 uint32_t max_gap, int n_legs) {
+    const size_t n = (size_t)n_legs;
+    for (size_t leg = blockIdx.x * (size_t)blockDim.x + threadIdx.x; leg < n; leg += (size_t)gridDim.x * blockDim.x) {
+        uint32_t raw[kSeqMaxCalls] = {0u, 0u, 0u, 0u}, ok = 0;
+        if (WIDE) {
+            const uint2 w = *reinterpret_cast<const uint2 *>(seq_raw + leg * kSeqMaxCalls);
+            raw[0] = w.x & 0xFFFFu, raw[1] = w.x >> 16, raw[2] = w.y & 0xFFFFu, raw[3] = w.y >> 16;
+        }
+#pragma unroll
+        for (int k = 0; k < kSeqMaxCalls; k++) {
+            if (k >= max_packets) continue;
+            if (!WIDE) raw[k] = seq_raw[leg * (size_t)max_packets + k];
+            if (len[leg * (size_t)max_packets + k] == 2u * kRtpG711Payload) ok |= 1u << k;
+        }
+        if (!ok) {  // no calls, state unchanged
+            calls[leg] = 0u;
+            continue;
+        }
+        uint32_t seq[kSeqMaxCalls];
+#pragma unroll
+        for (int k = 0; k < kSeqMaxCalls; k++) seq[k] = ((raw[k] & 0xFFu) << 8) | ((raw[k] >> 8) & 0xFFu);  // ntohs
+        LegSeqState st{sq[leg], sq[n + leg], sq[2 * n + leg], sq[3 * n + leg], sq[4 * n + leg], sq[5 * n + leg], sq[6 * n + leg]};
+        const LegSeqState was = st;
+        const LegSeqTick r = leg_seq_tick(st, seq, ok, max_gap);
+        calls[leg] = r.calls;
+#pragma unroll
+        for (int k = 0; k < kSeqMaxCalls; k++)
+            if (k < max_packets && ((r.discard >> k) & 1u)) len[leg * (size_t)max_packets + k] = 0u;
+        sq[leg] = st.synced;
+        sq[n + leg] = st.next;
+        if (st.lost != was.lost) sq[2 * n + leg] = st.lost;
+        if (st.late != was.late) sq[3 * n + leg] = st.late;
+        if (st.dup != was.dup) sq[4 * n + leg] = st.dup;
+        if (st.resync != was.resync) sq[5 * n + leg] = st.resync;
+        if (st.overflow != was.overflow) sq[6 * n + leg] = st.overflow;
+    }
+}
+
 inline bool aligned_to(const void *p, long stride_bytes, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0 && stride_bytes % a == 0; }
 
 }  // namespace
@@ -249,6 +299,7 @@ int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
     h->n_streams = n_streams;
     h->law = law;
     h->d_seq = h->d_ts = nullptr;
+    h->d_sq = nullptr;
     hipError_t e = hipMalloc(&h->d_seq, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMalloc(&h->d_ts, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMemset(h->d_seq, 0, sizeof(uint32_t) * n_streams);  // rtp_header(..., seq 0, timestamp 0, ssrc 0)
@@ -267,6 +318,7 @@ int wmx_rtp_destroy(wmx_rtp *h) {
     if (!h) return 0;
     if (h->d_seq) (void)hipFree(h->d_seq);
     if (h->d_ts) (void)hipFree(h->d_ts);
+    if (h->d_sq) (void)hipFree(h->d_sq);
     delete h;
     return 0;
 }
@@ -409,6 +461,85 @@ int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stre
     for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
         WMX_HIP(hipMemsetAsync(h->d_seq + host_idx[i], 0, sizeof(uint32_t), s));
         WMX_HIP(hipMemsetAsync(h->d_ts + host_idx[i], 0, sizeof(uint32_t), s));
+    }
+    return 0;
+}
+
+// ---- the sequence rule per leg (include/wmix_amd.h, leg_seq.h)
+// the state, all zero (unsynced, counters 0), from the first call that needs it on
+static int seq_state(wmx_rtp *h) {
+    if (h->d_sq) return 0;
+    const size_t bytes = (size_t)kSeqWords * h->n_streams * sizeof(uint32_t);
+    uint32_t *p = nullptr;
+    WMX_HIP(hipMalloc(&p, bytes));
+    hipError_t e = hipMemset(p, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "hipMemset(sequence state)", __FILE__, __LINE__);
+    }
+    h->d_sq = p;
+    return 0;
+}
+
+int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16_t *d_seq_raw, uint32_t *d_len, uint32_t *d_calls,
+                          void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !d_seq_raw || !d_len || !d_calls || max_packets < 1 || max_packets > kSeqMaxCalls || max_gap < 0 || max_gap > kSeqMaxCalls - 1) {
+        set_error("wmx_rtp_sequence_legs: max_packets=%d must be 1 .. %d, max_gap=%d 0 .. %d, and no pointer NULL", max_packets, kSeqMaxCalls,
+                  max_gap, kSeqMaxCalls - 1);
+        return WMX_EINVAL;
+    }
+    const int rcs = seq_state(h);
+    if (rcs) return rcs;
+    const bool wide = max_packets == kSeqMaxCalls && reinterpret_cast<uintptr_t>(d_seq_raw) % 8 == 0;
+    hipLaunchKernelGGL(wide ? rtp_sequence_legs_kernel<true> : rtp_sequence_legs_kernel<false>, dim3(wmx::stream_grid((size_t)h->n_streams, 256)),
+                       dim3(256), 0, as_stream(stream), d_seq_raw, d_len, d_calls, h->d_sq, max_packets, (uint32_t)max_gap, h->n_streams);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// unsynced and counters 0 for the listed legs (NULL = all), on `stream`: a new call may start at any sequence number
+int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
+    for (int i = 0; host_idx && i < n; i++)
+        if (host_idx[i] < 0 || host_idx[i] >= h->n_streams) {
+            set_error("wmx_rtp_reset_sequence: leg %d is outside the handle's %d", (int)host_idx[i], h->n_streams);
+            return WMX_EINVAL;
+        }
+    const bool fresh = !h->d_sq;
+    const int rcs = seq_state(h);
+    if (rcs || fresh) return rcs;  // just made: unsynced already
+    hipStream_t s = as_stream(stream);
+    const size_t pitch = (size_t)h->n_streams * sizeof(uint32_t);
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(h->d_sq, 0, (size_t)kSeqWords * pitch, s));
+        return 0;
+    }
+    for (int i = 0; i < n; i++)  // a handful of legs at a time: the leg's word in each of the arrays, nothing of the list goes to the device
+        WMX_HIP(hipMemset2DAsync(h->d_sq + host_idx[i], pitch, 0, sizeof(uint32_t), kSeqWords, s));
+    return 0;
+}
+
+// next (uint16), synced (uint8) and the five counters (uint32) of every leg as the work queued on `stream` leaves them; any pointer may
+// be NULL; blocking
+int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup, uint32_t *resync,
+                            uint32_t *overflow, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const size_t n = (size_t)h->n_streams;
+    std::vector<uint32_t> w((size_t)kSeqWords * n, 0u);  // no leg has been sequenced on this handle: all zero
+    if (h->d_sq) {
+        WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+        WMX_HIP(hipMemcpy(w.data(), h->d_sq, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    uint32_t *const out[5] = {lost, late, dup, resync, overflow};
+    for (size_t r = 0; r < n; r++) {
+        if (synced) synced[r] = (uint8_t)(w[r] != 0);
+        if (next) next[r] = (uint16_t)w[n + r];
+        for (int c = 0; c < 5; c++)
+            if (out[c]) out[c][r] = w[(size_t)(2 + c) * n + r];
     }
     return 0;
 }

@@ -114,6 +114,19 @@ class MixBatch:
                                             src.shape[1], lens.data_ptr(), mute.data_ptr() if mute is not None else None, reduce,
                                             torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus_legs")
 
+    def load_minus_legs_calls(self, src, src_bytes, freq, channels, lens, calls, mute=None, reduce=1, sample=16):
+        """load_minus_legs fed a call list per leg (wmx_mix_load_minus_legs_calls; RtpSenders.sequence_legs writes the lists): calls
+        int32 (or uint32) CUDA [n_groups]; leg r makes its list's calls in list order, a silence call moves the cursor and adds nothing,
+        a data call whose slot's lens != src_bytes is made as silence."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.dim() == 3 and src.stride(2) == 1 and src.shape[0] == self.n_groups
+        assert lens.is_cuda and lens.dtype in (torch.int32, torch.uint32) and lens.is_contiguous() and tuple(lens.shape) == tuple(src.shape[:2])
+        assert calls.is_cuda and calls.dtype in (torch.int32, torch.uint32) and calls.is_contiguous() and calls.numel() == self.n_groups
+        if mute is not None:
+            assert mute.is_cuda and mute.dtype == torch.uint8 and mute.is_contiguous() and mute.numel() == self.n_groups
+        check(lib().wmx_mix_load_minus_legs_calls(self._h, src.data_ptr(), src_bytes, freq, channels, sample, src.stride(0), src.stride(1),
+                                                  src.shape[1], lens.data_ptr(), calls.data_ptr(), mute.data_ptr() if mute is not None else None,
+                                                  reduce, torch.cuda.current_stream().cuda_stream), "wmx_mix_load_minus_legs_calls")
+
     def reset_leg_cursors(self, rings=None):
         """a fresh cursor and dropped = 0 for the listed rings (None = every ring): what a new call in a reused slot does"""
         idx = None if rings is None else np.ascontiguousarray(rings, dtype=np.int32)

@@ -50,6 +50,41 @@ class RtpSenders:
         check(lib().wmx_rtp_reset_streams(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
                                           torch.cuda.current_stream().cuda_stream), "wmx_rtp_reset_streams")
 
+    def sequence_legs(self, seq_raw, lens, max_gap=3, calls=None):
+        """Reorder, de-duplicate and gap-fill by RTP sequence number (wmx_rtp_sequence_legs), between ingest_legs and the load: seq_raw
+        int16 (or uint16) CUDA [n_streams, max_packets] and lens int32 (or uint32) CUDA [n_streams, max_packets] as ingest_legs leaves
+        them.  lens is REWRITTEN (0 for a slot that makes no call); -> calls int32 CUDA [n_streams], the call lists for
+        MixBatch.load_minus_legs_calls."""
+        assert seq_raw.is_cuda and seq_raw.dtype in (torch.int16, torch.uint16) and seq_raw.is_contiguous() and seq_raw.dim() == 2
+        assert seq_raw.shape[0] == self.n
+        assert lens.is_cuda and lens.dtype in (torch.int32, torch.uint32) and lens.is_contiguous() and tuple(lens.shape) == tuple(seq_raw.shape)
+        if calls is None:
+            calls = torch.zeros(self.n, dtype=torch.int32, device=lens.device)
+        assert calls.is_cuda and calls.dtype in (torch.int32, torch.uint32) and calls.is_contiguous() and calls.numel() == self.n
+        check(lib().wmx_rtp_sequence_legs(self._h, seq_raw.shape[1], max_gap, seq_raw.data_ptr(), lens.data_ptr(), calls.data_ptr(),
+                                          torch.cuda.current_stream().cuda_stream), "wmx_rtp_sequence_legs")
+        return calls
+
+    def reset_sequence(self, legs=None):
+        """unsynced and counters 0 for the listed legs (None = all): a new call may start at any sequence number"""
+        import numpy as np
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_rtp_reset_sequence(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                           torch.cuda.current_stream().cuda_stream), "wmx_rtp_reset_sequence")
+
+    def export_sequence(self):
+        """dict(next: uint16, synced: uint8, lost, late, dup, resync, overflow: uint32; [n_streams] each) as the work queued on the
+        current stream leaves them"""
+        import numpy as np
+        r = {k: np.zeros(self.n, np.uint32) for k in ("lost", "late", "dup", "resync", "overflow")}
+        r["next"], r["synced"] = np.zeros(self.n, np.uint16), np.zeros(self.n, np.uint8)
+        check(lib().wmx_rtp_export_sequence(self._h, r["next"].ctypes.data, r["synced"].ctypes.data, r["lost"].ctypes.data, r["late"].ctypes.data,
+                                            r["dup"].ctypes.data, r["resync"].ctypes.data, r["overflow"].ctypes.data,
+                                            torch.cuda.current_stream().cuda_stream), "wmx_rtp_export_sequence")
+        return r
+
     def state(self, stream=0):
         s, t = C.c_uint16(0), C.c_uint32(0)
         check(lib().wmx_rtp_export(self._h, stream, C.byref(s), C.byref(t)), "wmx_rtp_export")
