@@ -1,7 +1,7 @@
 /* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
- *             [--sequence G] [--audio-only]
+ *             [--sequence G] [--audio-only] [--ulaw-every N]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -15,6 +15,9 @@
  * become silence) and the JSON line also carries the five counters summed over the legs.  --audio-only: every datagram of the script is
  * PCMA (v == 0 too), so the script has no gap of its own: a datagram of payload type 96 consumes a sequence number and brings no audio,
  * which sequencing treats as a lost packet.
+ * --ulaw-every N: every N-th leg (N - 1, 2 N - 1, ...) negotiated PCMU: its G.711 datagrams carry payload type 0, it is decoded as
+ * mu-law and answered in mu-law (wmx_conf_set_codecs: WMX_CODEC_PCMU, WMX_LAW_U); the other legs stay at the default.  The JSON line
+ * then also carries the number of such legs and the refused counters summed over the legs (wmx_conf_export_codecs).
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -70,7 +73,8 @@ static int parse_sizes(const char *sizes, int32_t **off_out, int32_t **members_o
 }
 
 /* one tick of the network into a slot's rows */
-static int audio_only;
+static int audio_only, ulaw_every; /* ulaw_every 0: no leg negotiated PCMU */
+static int is_ulaw_leg(int g) { return ulaw_every > 0 && g % ulaw_every == ulaw_every - 1; }
 static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) {
     long arrived = 0;
     memset(in, 0xEE, (size_t)G * RTP_SLOTS * row);
@@ -86,7 +90,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) 
             const uint32_t v = lcg_next() % 16;
             memset(pk, 0, 12);
             pk[0] = 2u << 6;
-            pk[1] = (uint8_t)(0x80 | (v == 0 && !audio_only ? 96 : (v == 1 ? 0 : 8)));
+            pk[1] = (uint8_t)(0x80 | (v == 0 && !audio_only ? 96 : (v == 1 || is_ulaw_leg(g) ? 0 : 8)));
             pk[2] = (uint8_t)(seq[g] >> 8), pk[3] = (uint8_t)seq[g];
             seq[g]++;
             for (int i = 0; i < 160; i++) pk[12 + i] = (uint8_t)(lcg_next() & 255);
@@ -98,7 +102,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) 
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
-                        " [--sequence G] [--audio-only]\n";
+                        " [--sequence G] [--audio-only] [--ulaw-every N]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -122,6 +126,12 @@ int main(int argc, char **argv) {
             if (max_gap < 0) max_gap = WMX_MIX_MAX_LEG_PACKETS; /* not a gap: the library says so */
         } else if (!strcmp(argv[i], "--audio-only")) {
             audio_only = 1;
+        } else if (!strcmp(argv[i], "--ulaw-every") && i + 1 < argc) {
+            ulaw_every = atoi(argv[++i]);
+            if (ulaw_every < 1) {
+                fprintf(stderr, "host_conf: --ulaw-every N, N >= 1\n");
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--platform") && i + 1 < argc) {
             platform = argv[++i];
             if (!strcmp(platform, "alsa")) {
@@ -159,6 +169,13 @@ int main(int argc, char **argv) {
     WMX_OK(wmx_conf_set_conferences(h, n_conf, conf_off, conf_members, NULL));
     if (speakers) WMX_OK(wmx_conf_speakers(h, max_speakers, (uint32_t)floor_level, shift));
     if (max_gap >= 0) WMX_OK(wmx_conf_sequence(h, 1, max_gap));
+    int n_ulaw = 0;
+    for (int g = 0; g < G; g++) {
+        const int32_t leg = g;
+        if (!is_ulaw_leg(g)) continue;
+        WMX_OK(wmx_conf_set_codecs(h, &leg, 1, WMX_CODEC_PCMU, WMX_LAW_U, NULL));
+        n_ulaw++;
+    }
     const int row = wmx_conf_in_row_bytes(h);
     uint8_t *out = calloc((size_t)T * G * RTP_BYTES, 1);
     uint16_t *seq = calloc((size_t)G, sizeof(uint16_t));
@@ -203,6 +220,14 @@ int main(int argc, char **argv) {
             for (int g = 0; g < G; g++) seq_sum[c] += cnt[(size_t)c * G + g];
         free(cnt);
     }
+    unsigned long n_refused = 0;
+    if (ulaw_every > 0) {
+        uint32_t *refused = calloc((size_t)G, sizeof(uint32_t));
+        if (!refused) return 2;
+        WMX_OK(wmx_conf_export_codecs(h, NULL, NULL, refused, NULL));
+        for (int g = 0; g < G; g++) n_refused += refused[g];
+        free(refused);
+    }
     uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
@@ -215,6 +240,7 @@ int main(int argc, char **argv) {
     if (max_gap >= 0)
         printf("\"sequence\": %d, \"lost\": %lu, \"late\": %lu, \"dup\": %lu, \"resync\": %lu, \"overflow\": %lu, ", max_gap, seq_sum[0], seq_sum[1],
                seq_sum[2], seq_sum[3], seq_sum[4]);
+    if (ulaw_every > 0) printf("\"ulaw_every\": %d, \"ulaw_legs\": %d, \"refused\": %lu, ", ulaw_every, n_ulaw, n_refused);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

@@ -648,6 +648,37 @@ int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16
 int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
 int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup,
                             uint32_t *resync, uint32_t *overflow, void *stream);
+/* A G.711 codec per stream, as each call negotiated it (wmix_amd/csrc/leg_codec.h holds the rule).  The reference's receive thread
+ * accepts payload types 8 and 0 alike and decodes both with G711a2PCM (src/rtp.c:88-95, src/wmixTask.c:1282), and a send thread has one
+ * law.  Here the handle keeps, per stream and ON THE DEVICE, in_codec, out_law and a `refused` counter:
+ *   arrived = recvfrom returned > 0 for the slot; pt = header byte 1 & 0x7F; g711 = arrived && (pt == 8 || pt == 0)
+ *   WMX_CODEC_REFERENCE (the default)  a call when g711, decoded as A-law whatever the pt: the reference, and wmx_rtp_ingest_legs
+ *   WMX_CODEC_PCMA                     a call when g711 && pt == 8, decoded as A-law
+ *   WMX_CODEC_PCMU                     a call when g711 && pt == 0, decoded as mu-law (G711u2PCM, src/g711codec.c)
+ *   WMX_CODEC_BY_PT                    a call when g711, decoded as mu-law if pt == 0, else as A-law
+ *   refused = arrived && !call, in every mode (telephone-event packets, the AAC tag, the other law on a strict leg): refused[stream]++.
+ * A refused slot is what a slot of another payload type is for wmx_rtp_ingest_legs: d_len = 0 and a zeroed PCM row, d_seq_raw written;
+ * as everything downstream goes by d_len it is invisible to wmx_rtp_sequence_legs (not late, not a duplicate, does not sync), to talker
+ * selection and to the load.  out_law: WMX_LAW_A sends payload type 8 and PCM2G711a, WMX_LAW_U payload type 0 and PCM2G711u, per stream
+ * in wmx_rtp_egress and wmx_rtp_egress_rings (whose identity with wmx_mix_drain + wmx_rtp_egress holds with mixed laws); initially
+ * the law of wmx_rtp_create.  A handle on which no stream ever left the default runs the launches of a handle that knows no codecs.
+ * wmx_rtp_set_codecs: in_codec and out_law for the n streams host_idx lists (NULL = all), on `stream`; no host synchronisation and no
+ * upload.  The refused counts stay.  WMX_EINVAL, nothing changed: an index outside the handle, an in_codec outside 0 .. 3, an out_law
+ * that is neither law.  wmx_rtp_reset_streams and wmx_rtp_reset_sequence keep a stream's codec (a new call sets its own);
+ * wmx_rtp_reset_sequence zeroes its refused count with the other receive counters.
+ * wmx_rtp_export_codecs: in_codec, out_law (uint8) and refused (uint32), n_streams entries each, any pointer NULL, as the work queued
+ * on `stream` leaves them; blocking.
+ * wmx_rtp_ingest_legs_codecs: wmx_rtp_ingest_legs (same layouts, same refusals) for n_legs = the handle's streams with the rule above
+ * per leg.  No allocation after the first call on the handle (wmx_rtp_set_codecs counts as one). */
+#define WMX_CODEC_REFERENCE 0
+#define WMX_CODEC_PCMA 1
+#define WMX_CODEC_PCMU 2
+#define WMX_CODEC_BY_PT 3
+int wmx_rtp_set_codecs(wmx_rtp *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
+int wmx_rtp_export_codecs(wmx_rtp *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
+int wmx_rtp_ingest_legs_codecs(wmx_rtp *h, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride,
+                               const int32_t *d_recv_bytes, int16_t *d_pcm, long source_stride, long pcm_packet_stride,
+                               uint32_t *d_len, uint16_t *d_seq_raw, void *stream);
 
 /* ------------------------------------------------------------------ the packet edge as a pipeline
  * What wmix_thread_rtp_recv_pcma, the record heartbeat and wmix_thread_rtp_send_pcma do for one stream per 20 ms
@@ -708,7 +739,7 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  *   wmx_conf_recv(h, slot)  n_legs x max_packets int32: what recvfrom returned for the row (<= 0: nothing there, the row is not read)
  *   wmx_conf_out(h, slot)   n_legs x 172 bytes: the datagram to send to each leg
  *   wmx_conf_submit(h, &slot, stream)  takes the NEXT slot (round robin; wmx_conf_next_slot names it beforehand), uploads its in and
- *                  recv rows on the copy-in stream and, behind them on `stream`: wmx_rtp_ingest_legs -> wmx_mix_select_speakers_legs
+ *                  recv rows on the copy-in stream and, behind them on `stream`: wmx_rtp_ingest_legs_codecs -> wmx_mix_select_speakers_legs
  *                  (if selection is on) -> wmx_mix_load_minus_legs (reduce 1, 320-byte packages of 1 x 8000) -> wmx_rtp_egress_rings;
  *                  then the download of the out rows on the copy-out stream.  Returns at once; blocks only when that slot is still in
  *                  flight from `slots` submits ago.  With three slots the upload of tick t + 1 and the download of tick t - 1 run
@@ -722,14 +753,23 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * used slot needs -- a fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0 -- for the n legs host_idx lists
  * (NULL = all).  wmx_conf_export_legs: head, tick, dropped, env (uint32) and speaking (uint8) of every leg, any pointer NULL; blocking.
  * wmx_conf_sequence(h, on, max_gap): between submits.  Off (the default) is the launch sequence above, the reference's arrival order.
- * On, a tick is wmx_rtp_ingest_legs (which then also leaves the sequence numbers) -> wmx_rtp_sequence_legs(max_gap) -> the selection
+ * On, a tick is wmx_rtp_ingest_legs_codecs (which then also leaves the sequence numbers) -> wmx_rtp_sequence_legs(max_gap) -> the selection
  * if on (it sees the rewritten d_len) -> wmx_mix_load_minus_legs_calls -> wmx_rtp_egress_rings; its buffers are made at create.
  * wmx_conf_reset_legs also resets the listed legs' sequence state: a new call may start at any sequence number without counting a
  * resync.  wmx_conf_export_sequence: wmx_rtp_export_sequence of the handle's legs.  max_gap outside 0 .. 3: WMX_EINVAL.
+ * wmx_conf_set_codecs(h, host_idx, n, in_codec, out_law, stream): between submits; a G.711 codec per leg, as each call negotiated it
+ * (wmx_rtp_set_codecs over the legs, NULL = all).  The default is the reference's behaviour -- WMX_CODEC_REFERENCE: whatever arrives
+ * with payload type 8 or 0 is decoded as A-law -- and the `law` of wmx_conf_create is every leg's initial out_law.  WMX_CODEC_PCMA /
+ * WMX_CODEC_PCMU accept only their own payload type and decode with their own law, WMX_CODEC_BY_PT decodes each packet by its payload
+ * type; a packet that arrived and makes no call is REFUSED: counted per leg, and invisible to sequencing, selection and the load.  So
+ * an A-law leg and a mu-law leg of one conference hear each other, each in its own codec.  wmx_conf_reset_legs keeps the listed legs'
+ * codecs and zeroes their refused counts.  wmx_conf_export_codecs: in_codec, out_law (uint8) and refused (uint32) of every leg, any
+ * pointer NULL; blocking.  A handle that never sets a codec runs the launches it ran before there were any.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
- * step with no layout in force (no slot is taken); a leg index outside the handle (nothing is reset).  A submit that fails before its
+ * step with no layout in force (no slot is taken); a leg index outside the handle (nothing is reset, no codec set); an in_codec outside
+ * 0 .. 3 or an out_law that is neither law.  A submit that fails before its
  * first launch has advanced nothing; the rotation and the slots in flight are as before any failed submit. */
 typedef struct wmx_conf wmx_conf;
 int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int law);
@@ -740,6 +780,8 @@ int wmx_conf_speakers(wmx_conf *h, int max_speakers, uint32_t floor, int decay_s
 int wmx_conf_sequence(wmx_conf *h, int on, int max_gap);
 int wmx_conf_export_sequence(wmx_conf *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup,
                              uint32_t *resync, uint32_t *overflow, void *stream);
+int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
+int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
 int wmx_conf_slots(const wmx_conf *h);

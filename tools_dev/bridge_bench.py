@@ -50,7 +50,10 @@ region).  Every packet is then in order -- a data call in slot order, none is si
 the load does the work it does with sequencing off and (d) - (b), (e) - (c) are the sequencer's launch, the call-list path of the load
 and a third of that memset.
 
-    python tools_dev/bridge_bench.py --pipe --out profiles/bridge/bridge_pipe_bench.json"""
+    python tools_dev/bridge_bench.py --pipe --out profiles/bridge/bridge_pipe_bench.json
+--pipe --ulaw-every N adds (f), (g): the handle and the resident step again with a codec per leg (wmx_conf_set_codecs): every N-th leg is
+WMX_CODEC_PCMU in and mu-law out and its datagrams carry payload type 0, the other legs stay at the default; the launches are the per-leg
+ones for every leg.  (f) and (g) send the same datagrams, each leg in its own payload type, before any time is reported."""
 import argparse
 import json
 import os
@@ -301,7 +304,7 @@ def legs_against_conf(reps, freq=8000):
             "ratio_steady_over_conf": round(b["median_ms"] / a["median_ms"], 3), "ratio_jitter_over_conf": round(c["median_ms"] / a["median_ms"], 3)}
 
 
-def conf_pipe(reps):
+def conf_pipe(reps, ulaw_every=0):
     import ctypes as C
     import time
     from wmix_amd._lib import check, lib
@@ -405,6 +408,39 @@ def conf_pipe(reps):
         new_cycle(ce, i)
         ce.step_resident(r_in[i], r_recv[i], e_out)
 
+    # (f), (g) the same two with a codec per leg: every ulaw_every-th leg on PCMU both ways, the others at the default
+    mixed = ulaw_every > 0
+    if mixed:
+        ulaw = np.arange(legs) % ulaw_every == ulaw_every - 1
+        pk_u = pk.copy()
+        pk_u[:, ulaw, :, 1] = 0x80
+        cf, cg = ConfBridge(legs, 3, 3), ConfBridge(legs, 1, 3)
+        for x in (cf, cg):
+            x.set_conferences(layout)
+            x.set_play_correct(0)
+            x.set_codecs(np.flatnonzero(ulaw), "pcmu", "u")  # one call of many legs: set-up, outside the timed blocks
+        for k in range(3):
+            cf.rows_in[k][:] = pk_u[k]
+            cf.recv[k][:] = recv[k]
+        u_in, g_out = torch.from_numpy(pk_u).cuda(), torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+        step["g"] = 0
+
+        def handle_mixed():
+            return cf.submit()
+
+        def resident_mixed():
+            i = step["g"] % CYC
+            step["g"] += 1
+            cg.step_resident(u_in[i], r_recv[i], g_out)
+
+        for t in range(2 * CYC):
+            k = handle_mixed()
+            cf.wait(k)
+            resident_mixed()
+            f_rows = cf.rows_out[k].copy()
+            assert np.array_equal(f_rows, g_out.cpu().numpy()), ("datagrams differ with mixed codecs, tick", t)
+            assert (f_rows[ulaw, 1] == 0x80).all() and (f_rows[~ulaw, 1] == 0x88).all() and (f_rows[ulaw, 12:] != 0xFF).any()
+
     # ---- the same datagrams?
     for t in range(2 * CYC):
         a = parent().numpy().copy()
@@ -426,13 +462,16 @@ def conf_pipe(reps):
         return (time.perf_counter() - t0) * 1e3 / n
 
     per_block = max(reps // BLOCKS, 8)
-    ms = {"a": [], "b": [], "c": [], "d": [], "e": []}
+    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": []}
     for _ in range(BLOCKS + 1):  # the first block warms up
         ms["a"].append(wall(parent, per_block, torch.cuda.synchronize))
         ms["b"].append(wall(handle, per_block, lambda: cb.wait(-1)))
         ms["c"].append(wall(resident, per_block, torch.cuda.synchronize))
         ms["d"].append(wall(handle_seq, per_block, lambda: cs.wait(-1)))
         ms["e"].append(wall(resident_seq, per_block, torch.cuda.synchronize))
+        if mixed:
+            ms["f"].append(wall(handle_mixed, per_block, lambda: cf.wait(-1)))
+            ms["g"].append(wall(resident_mixed, per_block, torch.cuda.synchronize))
     side = lambda v: {"median_ms_per_tick": round(float(np.median(v[1:])), 5), "block_ms_per_tick": [round(x, 5) for x in v[1:]]}  # noqa: E731
     a, b, c, d, e = side(ms["a"]), side(ms["b"]), side(ms["c"]), side(ms["d"]), side(ms["e"])
     sq = cs.export_sequence()
@@ -453,9 +492,18 @@ def conf_pipe(reps):
     t_pair, t_fused = alternate([drain_then_egress, egress_rings], reps)
     assert torch.equal(p_out, f_out)
     kp, kf = stats(t_pair), stats(t_fused)
+    more = {}
+    if mixed:
+        f, g = side(ms["f"]), side(ms["g"])
+        more = {"ulaw_every": ulaw_every, "ulaw_legs": int(ulaw.sum()), "f_wmx_conf_3_slots_mixed_codecs": f, "g_step_resident_mixed_codecs": g,
+                "f_minus_b_ms": round(f["median_ms_per_tick"] - b["median_ms_per_tick"], 5),
+                "g_minus_c_ms": round(g["median_ms_per_tick"] - c["median_ms_per_tick"], 5),
+                "refused_of_f": int(cf.export_codecs()["refused"].sum())}
+        cf.close()
+        cg.close()
     for x in (tk, snd, cb, cr, cs, ce, pair, fused, s2, s3):
         x.close()
-    return {"conferences": n_conf, "sizes": {str(k): sizes.count(k) for k in sorted(set(sizes))}, "legs": legs, "max_packets": 3,
+    return {**more, "conferences": n_conf, "sizes": {str(k): sizes.count(k) for k in sorted(set(sizes))}, "legs": legs, "max_packets": 3,
             "packets_per_leg_and_tick": round(float((recv > 0).sum()) / (CYC * legs), 3), "ticks_per_block": per_block, "datagram_ticks_checked": 2 * CYC,
             "a_host_tick_bridge_rtp_composition": a, "b_wmx_conf_3_slots": b, "c_step_resident": c,
             "d_wmx_conf_3_slots_sequencing_on": d, "e_step_resident_sequencing_on": e,
@@ -536,6 +584,7 @@ if __name__ == "__main__":
     ap.add_argument("--speakers", type=int, default=0, help="measure the talker selection with this max_speakers instead (uniform shapes, or --ragged)")
     ap.add_argument("--legs", action="store_true", help="the bridge load with a cursor per leg beside wmx_mix_load_minus_conf, same layout")
     ap.add_argument("--pipe", action="store_true", help="the bridge of RTP/G.711 legs end to end: the parent's composition, wmx_conf, the launches alone")
+    ap.add_argument("--ulaw-every", type=int, default=0, help="with --pipe: two more sides, every N-th leg on PCMU both ways (a codec per leg)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
@@ -547,7 +596,7 @@ if __name__ == "__main__":
         args.ragged, args.speakers = False, 0
     if args.pipe:
         res = {"tool": "bridge_bench --pipe", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps)}
+               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every)}
         args.sizes = args.tick = ""
         args.ragged, args.speakers = False, 0
     if args.speakers:

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .rtp import LAW
+from .rtp import CODEC, LAW
 
 OUT_ROW = 172
 
@@ -67,12 +67,28 @@ class ConfBridge:
               "wmx_conf_export_sequence")
         return r
 
+    def set_codecs(self, legs, in_codec, out_law):
+        """a G.711 codec per leg, as each call negotiated it (wmx_conf_set_codecs), between submits: in_codec "reference" (the default:
+        A-law whatever arrives), "pcma", "pcmu" or "by_pt" (or WMX_CODEC_* 0 .. 3), out_law "a" / "u"; legs None = every leg"""
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_conf_set_codecs(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, CODEC[in_codec],
+                                        LAW[out_law], self._stream()), "wmx_conf_set_codecs")
+
+    def export_codecs(self):
+        """dict(in_codec, out_law: uint8 [n_legs]; refused: uint32 [n_legs]) as the work queued on the current stream leaves them"""
+        r = {"in_codec": np.zeros(self.n_legs, np.uint8), "out_law": np.zeros(self.n_legs, np.uint8), "refused": np.zeros(self.n_legs, np.uint32)}
+        check(lib().wmx_conf_export_codecs(self._h, r["in_codec"].ctypes.data, r["out_law"].ctypes.data, r["refused"].ctypes.data, self._stream()),
+              "wmx_conf_export_codecs")
+        return r
+
     def set_play_correct(self, n_bytes):
         check(lib().wmx_conf_set_play_correct(self._h, n_bytes), "wmx_conf_set_play_correct")
 
     def reset_legs(self, legs=None):
-        """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced
-        (None = every leg)"""
+        """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
+        refused = 0; the leg keeps its codec (None = every leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

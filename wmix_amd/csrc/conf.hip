@@ -5,10 +5,12 @@
 // the thread's own cursor), the play thread (src/wmix.c:1347-1366) and one wmix_thread_rtp_send_pcma per leg (src/wmixTask.c:1058-1143),
 // for n_legs legs per 20 ms tick with only datagrams crossing PCIe:
 //
-//     host rows --H2D--> wmx_rtp_ingest_legs -> [wmx_mix_select_speakers_legs] -> wmx_mix_load_minus_legs -> wmx_rtp_egress_rings --D2H--> host
+//     host rows --H2D--> wmx_rtp_ingest_legs_codecs -> [wmx_mix_select_speakers_legs] -> wmx_mix_load_minus_legs -> wmx_rtp_egress_rings --D2H--> host
 //
 // With sequencing on (wmx_conf_sequence) the ingest also leaves the sequence numbers, wmx_rtp_sequence_legs turns them into a call list
-// per leg and rewrites d_len in front of the selection, and the load is wmx_mix_load_minus_legs_calls.
+// per leg and rewrites d_len in front of the selection, and the load is wmx_mix_load_minus_legs_calls.  The ingest and the egress
+// apply each leg's own G.711 codec (wmx_conf_set_codecs; wmix_amd/csrc/leg_codec.h); a handle that never sets one runs the
+// reference's A-law-whatever-arrives and one law out.
 //
 // PER SLOT (made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a 4-byte
 // boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and three events.  PER HANDLE: the mixer
@@ -60,8 +62,8 @@ struct wmx_conf {
 // the launches of one tick on rows that are on the device
 static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream) {
     const int K = h->max_packets;
-    int rc = wmx_rtp_ingest_legs(h->n_legs, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len,
-                                 h->seq_on ? h->d_seq : nullptr, stream);
+    int rc = wmx_rtp_ingest_legs_codecs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len,
+                                        h->seq_on ? h->d_seq : nullptr, stream);
     if (rc != 0) return rc;
     if (h->seq_on) {  // in front of the selection: it must not hear a late packet or a duplicate
         rc = wmx_rtp_sequence_legs(h->snd, K, h->max_gap, h->d_seq, h->d_len, h->d_calls, stream);
@@ -121,7 +123,8 @@ int wmx_conf_destroy(wmx_conf *h) {
     return 0;
 }
 
-// law: WMX_LAW_A or WMX_LAW_U of what is SENT; every payload received is decoded as A-law, as the reference's receive thread does
+// law: WMX_LAW_A or WMX_LAW_U of what is SENT, every leg's initial out_law; every payload received is decoded as A-law, as the
+// reference's receive thread does, until wmx_conf_set_codecs says what a leg negotiated
 int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int law) {
     if (!out) return WMX_EINVAL;
     *out = nullptr;
@@ -146,6 +149,7 @@ int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int 
     if (rc == 0) rc = wmx_mix_reset_leg_cursors(h->mix, nullptr, 0, nullptr);
     if (rc == 0) rc = wmx_mix_reset_speakers(h->mix, nullptr, 0, nullptr);
     if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, nullptr, 0, nullptr);
+    if (rc == 0) rc = wmx_rtp_set_codecs(h->snd, nullptr, 0, WMX_CODEC_REFERENCE, law, nullptr);
     if (rc == 0) {
         hipError_t e = hipMalloc(&h->d_pcm, rows * kPcmRow * sizeof(int16_t));
         if (e == hipSuccess) e = hipMalloc(&h->d_len, rows * sizeof(uint32_t));
@@ -236,9 +240,22 @@ int wmx_conf_sequence(wmx_conf *h, int on, int max_gap) {
     return 0;
 }
 
+// a G.711 codec per leg (wmx_rtp_set_codecs over the legs; NULL = all): between submits, ordered on `stream`
+int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_set_codecs(h->snd, host_idx, n, in_codec, out_law, stream);
+}
+
+// in_codec, out_law (uint8) and refused (uint32) of every leg (wmx_rtp_export_codecs); any pointer may be NULL; blocking
+int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_export_codecs(h->snd, in_codec, out_law, refused, stream);
+}
+
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
 
-// a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced
+// a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
+// refused = 0; the leg keeps its codec
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
     for (int i = 0; host_idx && i < n; i++)  // before the first of the four: a bad index resets nothing

@@ -12,6 +12,7 @@
 #include "wmx_internal.h"
 #include "g711_dev.h"
 #include "leg_seq.h"
+#include "leg_codec.h"
 
 struct wmx_rtp {
     int device;  // the HIP device the state lives on (current device at create); every entry point switches to it
@@ -23,6 +24,12 @@ struct wmx_rtp {
     // the sequence rule's state per leg (leg_seq.h), made by the first call that needs it: kSeqWords arrays of n_streams uint32 in
     // one block -- synced, next, lost, late, dup, resync, overflow
     uint32_t *d_sq;
+    // the codec rule's state per stream (leg_codec.h), made by the first call that needs it, one block: refused (uint32), in_codec and
+    // out_law (uint8).  codecs_default: no stream has left in_codec REFERENCE / out_law = law, so the launches are those of a handle
+    // that knows no codecs
+    uint32_t *d_refused;
+    uint8_t *d_in_codec, *d_out_law;
+    bool codecs_default;
 };
 
 namespace wmx {
@@ -31,16 +38,27 @@ namespace {
 constexpr int kRtpHeader = 12;      // RTP_HEADER_SIZE, src/rtp.h:33
 constexpr int kRtpG711Payload = 160;  // RTP_PCMA_PKT_SIZE, src/rtp.h:31
 
+// LAW: WMX_LAW_A / WMX_LAW_U for every stream of the launch (payload type `pt`), or kLawPerStream: laws[stream] (leg_codec.h)
+constexpr int kLawPerStream = 2;
+template <int LAW>
+__device__ __forceinline__ uint32_t enc_law(int law, int v) {
+    if (LAW == WMX_LAW_A) return enc_alaw(v);
+    if (LAW == WMX_LAW_U) return enc_ulaw(v);
+    return law == WMX_LAW_A ? enc_alaw(v) : enc_ulaw(v);
+}
+
 template <int LAW>
 __global__ void rtp_egress_kernel(const int16_t *__restrict__ pcm, long pcm_stride, const int32_t *__restrict__ idx, int n_codes,
                                   int codes_per_ts, uint32_t *seq, uint32_t *ts, uint8_t *packets, long packet_stride, int n_streams,
-                                  int pt) {
+                                  int pt, const uint8_t *__restrict__ laws) {
     const int stream = blockIdx.y;
     if (stream >= n_streams) return;
+    const int law = LAW == kLawPerStream ? (int)laws[stream] : LAW;
+    if (LAW == kLawPerStream) pt = (int)leg_codec_out_pt(law);
     const int16_t *src = pcm + (size_t)stream * pcm_stride;
     uint8_t *pkt = packets + (size_t)stream * packet_stride;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_codes; i += gridDim.x * blockDim.x)
-        pkt[kRtpHeader + i] = (uint8_t)(LAW == WMX_LAW_A ? enc_alaw(src[idx[i]]) : enc_ulaw(src[idx[i]]));
+        pkt[kRtpHeader + i] = (uint8_t)enc_law<LAW>(law, src[idx[i]]);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const uint32_t t = ts[stream] + (uint32_t)codes_per_ts;  // timestamp += ret / chn, before the send
         const uint32_t s = seq[stream] & 0xFFFFu;
@@ -104,7 +122,8 @@ __global__ __launch_bounds__(256) void rtp_ingest_wide_kernel(const uint8_t *__r
 template <int LAW>
 __global__ __launch_bounds__(256) void rtp_egress_wide_kernel(const int16_t *__restrict__ pcm, long pcm_stride, const int32_t *__restrict__ idx,
                                                                int n_codes, int codes_per_ts, uint32_t *seq, uint32_t *ts, uint8_t *packets,
-                                                               long packet_stride, int n_streams, int pt) {
+                                                               long packet_stride, int n_streams, int pt_all,
+                                                               const uint8_t *__restrict__ laws) {
     const int words = n_codes >> 2;  // n_codes is a multiple of 4 here
     const size_t total = (size_t)n_streams * words;
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
@@ -112,7 +131,9 @@ __global__ __launch_bounds__(256) void rtp_egress_wide_kernel(const int16_t *__r
         const int16_t *src = pcm + (size_t)stream * pcm_stride;
         uint8_t *pkt = packets + (size_t)stream * packet_stride;
         const int4 ix = *reinterpret_cast<const int4 *>(idx + 4 * j);
-        auto enc = [](int v) -> uint32_t { return LAW == WMX_LAW_A ? enc_alaw(v) : enc_ulaw(v); };
+        const int law = LAW == kLawPerStream ? (int)laws[stream] : LAW;
+        const int pt = LAW == kLawPerStream ? (int)leg_codec_out_pt(law) : pt_all;
+        auto enc = [=](int v) -> uint32_t { return enc_law<LAW>(law, v); };
         *reinterpret_cast<uint32_t *>(pkt + kRtpHeader + 4 * j) =
             (enc(src[ix.x]) & 0xFF) | ((enc(src[ix.y]) & 0xFF) << 8) | ((enc(src[ix.z]) & 0xFF) << 16) | (enc(src[ix.w]) << 24);
         if (j == 0) {
@@ -166,21 +187,69 @@ __global__ __launch_bounds__(256) void rtp_ingest_legs_kernel(const uint8_t *__r
     }
 }
 
+// The same ingest with the codec rule per leg (wmx_rtp_ingest_legs_codecs, leg_codec.h): which slots make a call and with which law
+// their payload is decoded is the leg's in_codec's to say.  PER_LEG false: every leg is WMX_CODEC_REFERENCE (in_codec is not read) --
+// rtp_ingest_legs_kernel plus the count.  A row's lanes all decide alike from the row's header; neighbouring rows, and so the lanes of
+// one wave, may decode with different laws: both decoders are evaluated and one is selected.  refused[leg] counts the leg's slots
+// where something arrived that made no call: one atomic add by the row's first lane -- up to max_packets lanes add to one word, and no
+// lane of the launch reads it.
+template <bool WIDE, bool PER_LEG>
+__global__ __launch_bounds__(256) void rtp_ingest_legs_codecs_kernel(const uint8_t *__restrict__ packets, long leg_stride, long packet_stride,
+                                                                      const int32_t *__restrict__ recv_bytes, int16_t *pcm, long source_stride,
+                                                                      long pcm_packet_stride, uint32_t *len, uint16_t *seq_raw, int max_packets,
+                                                                      int n_legs, const uint8_t *__restrict__ in_codec, uint32_t *refused) {
+    constexpr int kPieces = WIDE ? kRtpWords : kRtpG711Payload;
+    const size_t total = (size_t)n_legs * max_packets * kPieces;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t row = t / kPieces;  // leg * max_packets + slot
+        const int c = (int)(t - row * kPieces);
+        const size_t leg = row / (size_t)max_packets, k = row - leg * (size_t)max_packets;
+        const uint8_t *pkt = packets + leg * leg_stride + k * packet_stride;
+        int16_t *dst = pcm + leg * source_stride + k * pcm_packet_stride;
+        const bool there = recv_bytes[row] > 0;
+        const uint32_t pt = there ? pkt[1] & 0x7Fu : 0u;
+        const uint32_t what = leg_codec_slot(there, pt, PER_LEG ? (uint32_t)in_codec[leg] : kCodecReference);
+        const bool call = (what & kLegCodecCall) != 0u, ulaw = PER_LEG && (what & kLegCodecUlaw) != 0u;
+        auto dec = [=](uint32_t code) -> uint32_t { return (uint32_t)(PER_LEG && ulaw ? dec_ulaw(code) : dec_alaw(code)); };
+        if (WIDE) {
+            uint2 o = make_uint2(0u, 0u);
+            if (call) {
+                const uint32_t w = *reinterpret_cast<const uint32_t *>(pkt + kRtpHeader + 4 * c);
+                o.x = (dec(w & 0xFF) & 0xFFFFu) | (dec((w >> 8) & 0xFF) << 16);
+                o.y = (dec((w >> 16) & 0xFF) & 0xFFFFu) | (dec(w >> 24) << 16);
+            }
+            *reinterpret_cast<uint2 *>(dst + 4 * c) = o;
+        } else {
+            dst[c] = call ? (int16_t)dec(pkt[kRtpHeader + c]) : (int16_t)0;
+        }
+        if (c == 0) {
+            len[row] = call ? (uint32_t)kRtpG711Payload * 2 : 0u;
+            if (seq_raw) seq_raw[row] = there ? (uint16_t)(pkt[2] | (pkt[3] << 8)) : (uint16_t)0;  // as stored: rtp_recv does not ntohs
+            if (what & kLegCodecRefused) atomicAdd(refused + leg, 1u);
+        }
+    }
+}
+
 // Play and send in one kernel (wmx_rtp_egress_rings): what drain_kernel (mix.hip) followed by the egress kernels above do for a ring
 // of 1 x 8000, where the zoom is the identity -- the 160 samples at the ring head never pass through a PCM row in HBM.  One lane takes
 // FOUR codes, dealt over (ring, word) pairs.  WIDE_IN: the head is a multiple of four samples, so (the ring's length is one too) every
 // lane's four samples are one aligned 8-byte piece that does not straddle the ring's end: one load, one store of zeros (the play thread
 // zeroes what it has read, src/wmix.c:1351-1352).  Otherwise sample by sample, each reduced into the ring.  WIDE_OUT: datagram rows on
 // 4-byte boundaries, the codes and the header as 32-bit stores; otherwise byte by byte.
-template <bool WIDE_IN, bool WIDE_OUT>
-__global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, uint32_t head_sample, int law,
+// PER_RING: law and payload type are the ring's own (laws[ring], leg_codec.h).  A wave of 64 lanes spans more than one ring (40 words per
+// ring), so its lanes may hold different laws: both encoders are evaluated and one is selected per lane; which lane writes the header
+// (j == 0) does not depend on the law.
+template <bool WIDE_IN, bool WIDE_OUT, bool PER_RING>
+__global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, uint32_t head_sample, int law_all,
                                                                 uint32_t *seq, uint32_t *ts, uint8_t *__restrict__ packets, long packet_stride,
-                                                                int n_rings, int pt) {
+                                                                int n_rings, int pt_all, const uint8_t *__restrict__ laws) {
     const size_t total = (size_t)n_rings * kRtpWords;
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         const int ring = (int)(t / kRtpWords), j = (int)(t - (size_t)ring * kRtpWords);
         int16_t *rg = rings + (size_t)ring * ring_samples;
         uint8_t *pkt = packets + (size_t)ring * packet_stride;
+        const int law = PER_RING ? (int)laws[ring] : law_all;
+        const int pt = PER_RING ? (int)leg_codec_out_pt(law) : pt_all;
         uint32_t pos = head_sample + 4u * (uint32_t)j;  // head_sample < ring_samples, 4 j < 160 <= ring_samples
         pos -= pos >= ring_samples ? ring_samples : 0u;
         int v[4];
@@ -300,6 +369,9 @@ int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
     h->law = law;
     h->d_seq = h->d_ts = nullptr;
     h->d_sq = nullptr;
+    h->d_refused = nullptr;
+    h->d_in_codec = h->d_out_law = nullptr;
+    h->codecs_default = true;
     hipError_t e = hipMalloc(&h->d_seq, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMalloc(&h->d_ts, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMemset(h->d_seq, 0, sizeof(uint32_t) * n_streams);  // rtp_header(..., seq 0, timestamp 0, ssrc 0)
@@ -319,6 +391,7 @@ int wmx_rtp_destroy(wmx_rtp *h) {
     if (h->d_seq) (void)hipFree(h->d_seq);
     if (h->d_ts) (void)hipFree(h->d_ts);
     if (h->d_sq) (void)hipFree(h->d_sq);
+    if (h->d_refused) (void)hipFree(h->d_refused);  // in_codec and out_law lie behind it
     delete h;
     return 0;
 }
@@ -347,20 +420,18 @@ int wmx_rtp_egress(wmx_rtp *h, int in_chn, int in_freq, const int16_t *d_pcm, ui
     if (packet_bytes) *packet_bytes = (uint32_t)(kRtpHeader + n_codes);
     const dim3 block(256), grid((unsigned)((n_codes + 255) / 256 > 0 ? (n_codes + 255) / 256 : 1), (unsigned)h->n_streams);
     const int pt = h->law == WMX_LAW_A ? 8 : 0;  // RTP_PAYLOAD_TYPE_PCMA / PCMU, src/rtp.h:21-24
+    const uint8_t *laws = h->codecs_default ? nullptr : h->d_out_law;  // per stream once a stream has left the default (leg_codec.h)
     if (n_codes >= 4 && n_codes % 4 == 0 && aligned_to(d_packets, packet_stride, 4)) {  // four codes per lane (the gather list is 16-byte aligned)
         const unsigned wgrid = wmx::stream_grid((size_t)h->n_streams * (n_codes / 4), 256);
-        if (h->law == WMX_LAW_A)
-            hipLaunchKernelGGL((rtp_egress_wide_kernel<WMX_LAW_A>), dim3(wgrid), block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes,
-                               n_codes / out_chn, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt);
-        else
-            hipLaunchKernelGGL((rtp_egress_wide_kernel<WMX_LAW_U>), dim3(wgrid), block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes,
-                               n_codes / out_chn, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt);
-    } else if (h->law == WMX_LAW_A)
-        hipLaunchKernelGGL((rtp_egress_kernel<WMX_LAW_A>), grid, block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes,
-                           n_codes / out_chn, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt);
-    else
-        hipLaunchKernelGGL((rtp_egress_kernel<WMX_LAW_U>), grid, block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes,
-                           n_codes / out_chn, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt);
+        auto kernel = laws ? rtp_egress_wide_kernel<kLawPerStream>
+                           : (h->law == WMX_LAW_A ? rtp_egress_wide_kernel<WMX_LAW_A> : rtp_egress_wide_kernel<WMX_LAW_U>);
+        hipLaunchKernelGGL(kernel, dim3(wgrid), block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes, n_codes / out_chn, h->d_seq,
+                           h->d_ts, d_packets, packet_stride, h->n_streams, pt, laws);
+    } else {
+        auto kernel = laws ? rtp_egress_kernel<kLawPerStream> : (h->law == WMX_LAW_A ? rtp_egress_kernel<WMX_LAW_A> : rtp_egress_kernel<WMX_LAW_U>);
+        hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes, n_codes / out_chn, h->d_seq, h->d_ts,
+                           d_packets, packet_stride, h->n_streams, pt, laws);
+    }
     WMX_LAUNCH_CHECK();
     return h->sched.used(ent, as_stream(stream));
 }
@@ -431,11 +502,15 @@ int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet
     const uint32_t ring_samples = v.ring_bytes / 2, head_sample = (v.head_off / 2) % ring_samples;
     const bool wide_in = head_sample % 4 == 0 && ring_samples % 4 == 0 && reinterpret_cast<uintptr_t>(v.d_rings) % 8 == 0;
     const bool wide_out = aligned_to(d_packets, packet_stride, 4);
-    auto kernel = wide_in ? (wide_out ? rtp_egress_rings_kernel<true, true> : rtp_egress_rings_kernel<true, false>)
-                          : (wide_out ? rtp_egress_rings_kernel<false, true> : rtp_egress_rings_kernel<false, false>);
+    const uint8_t *laws = h->codecs_default ? nullptr : h->d_out_law;  // per ring once a stream has left the default (leg_codec.h)
+    auto kernel = wide_in ? (wide_out ? rtp_egress_rings_kernel<true, true, false> : rtp_egress_rings_kernel<true, false, false>)
+                          : (wide_out ? rtp_egress_rings_kernel<false, true, false> : rtp_egress_rings_kernel<false, false, false>);
+    if (laws)
+        kernel = wide_in ? (wide_out ? rtp_egress_rings_kernel<true, true, true> : rtp_egress_rings_kernel<true, false, true>)
+                         : (wide_out ? rtp_egress_rings_kernel<false, true, true> : rtp_egress_rings_kernel<false, false, true>);
     const int pt = h->law == WMX_LAW_A ? 8 : 0;  // RTP_PAYLOAD_TYPE_PCMA / PCMU, src/rtp.h:21-24
     hipLaunchKernelGGL(kernel, dim3(wmx::stream_grid((size_t)h->n_streams * kRtpWords, 256)), dim3(256), 0, as_stream(stream), v.d_rings,
-                       ring_samples, head_sample, h->law, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt);
+                       ring_samples, head_sample, h->law, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt, laws);
     WMX_LAUNCH_CHECK();
     mix_played(m, 2u * kRtpG711Payload);
     if (packet_bytes) *packet_bytes = (uint32_t)(kRtpHeader + kRtpG711Payload);
@@ -499,7 +574,8 @@ int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16
     return 0;
 }
 
-// unsynced and counters 0 for the listed legs (NULL = all), on `stream`: a new call may start at any sequence number
+// unsynced and counters 0 (the refused count of the codec rule among them) for the listed legs (NULL = all), on `stream`: a new call
+// may start at any sequence number
 int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
@@ -508,11 +584,15 @@ int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *str
             set_error("wmx_rtp_reset_sequence: leg %d is outside the handle's %d", (int)host_idx[i], h->n_streams);
             return WMX_EINVAL;
         }
+    hipStream_t s = as_stream(stream);
+    const size_t pitch = (size_t)h->n_streams * sizeof(uint32_t);
+    if (h->d_refused) {  // the receive side's other counter (leg_codec.h); the leg's codec stays
+        if (!host_idx) WMX_HIP(hipMemsetAsync(h->d_refused, 0, pitch, s));
+        for (int i = 0; host_idx && i < n; i++) WMX_HIP(hipMemsetAsync(h->d_refused + host_idx[i], 0, sizeof(uint32_t), s));
+    }
     const bool fresh = !h->d_sq;
     const int rcs = seq_state(h);
     if (rcs || fresh) return rcs;  // just made: unsynced already
-    hipStream_t s = as_stream(stream);
-    const size_t pitch = (size_t)h->n_streams * sizeof(uint32_t);
     if (!host_idx) {
         WMX_HIP(hipMemsetAsync(h->d_sq, 0, (size_t)kSeqWords * pitch, s));
         return 0;
@@ -541,6 +621,106 @@ int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_
         for (int c = 0; c < 5; c++)
             if (out[c]) out[c][r] = w[(size_t)(2 + c) * n + r];
     }
+    return 0;
+}
+
+// ---- the codec rule per stream (include/wmix_amd.h, leg_codec.h)
+// the state -- refused 0, in_codec REFERENCE, out_law the law of create -- from the first call that needs it on
+static int codec_state(wmx_rtp *h) {
+    if (h->d_refused) return 0;
+    const size_t n = (size_t)h->n_streams, bytes = n * sizeof(uint32_t) + 2 * n;
+    uint8_t *p = nullptr;
+    WMX_HIP(hipMalloc(&p, bytes));
+    hipError_t e = hipMemset(p, 0, n * sizeof(uint32_t) + n);
+    if (e == hipSuccess) e = hipMemset(p + n * sizeof(uint32_t) + n, h->law, n);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "hipMemset(codec state)", __FILE__, __LINE__);
+    }
+    h->d_refused = reinterpret_cast<uint32_t *>(p);
+    h->d_in_codec = p + n * sizeof(uint32_t);
+    h->d_out_law = h->d_in_codec + n;
+    return 0;
+}
+
+// in_codec (WMX_CODEC_*) and out_law (WMX_LAW_*) of the listed streams (NULL = all), on `stream`; the refused counts stay
+int wmx_rtp_set_codecs(wmx_rtp *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
+    if (!leg_codec_valid(in_codec) || !leg_law_valid(out_law)) {
+        set_error("wmx_rtp_set_codecs: in_codec %d must be WMX_CODEC_REFERENCE .. WMX_CODEC_BY_PT and out_law %d WMX_LAW_A or WMX_LAW_U", in_codec,
+                  out_law);
+        return WMX_EINVAL;
+    }
+    for (int i = 0; host_idx && i < n; i++)
+        if (host_idx[i] < 0 || host_idx[i] >= h->n_streams) {
+            set_error("wmx_rtp_set_codecs: stream %d is outside the handle's %d", (int)host_idx[i], h->n_streams);
+            return WMX_EINVAL;
+        }
+    const int rcs = codec_state(h);
+    if (rcs) return rcs;
+    hipStream_t s = as_stream(stream);
+    const bool is_default = in_codec == WMX_CODEC_REFERENCE && out_law == h->law;
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(h->d_in_codec, in_codec, (size_t)h->n_streams, s));
+        WMX_HIP(hipMemsetAsync(h->d_out_law, out_law, (size_t)h->n_streams, s));
+        h->codecs_default = is_default;
+        return 0;
+    }
+    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
+        WMX_HIP(hipMemsetAsync(h->d_in_codec + host_idx[i], in_codec, 1, s));
+        WMX_HIP(hipMemsetAsync(h->d_out_law + host_idx[i], out_law, 1, s));
+    }
+    if (n > 0 && !is_default) h->codecs_default = false;
+    return 0;
+}
+
+// in_codec, out_law (uint8) and refused (uint32) of every stream as the work queued on `stream` leaves them; any pointer may be NULL;
+// blocking
+int wmx_rtp_export_codecs(wmx_rtp *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const size_t n = (size_t)h->n_streams;
+    if (!h->d_refused) {  // no codec has been set and nothing ingested on this handle
+        for (size_t r = 0; r < n; r++) {
+            if (in_codec) in_codec[r] = (uint8_t)WMX_CODEC_REFERENCE;
+            if (out_law) out_law[r] = (uint8_t)h->law;
+            if (refused) refused[r] = 0u;
+        }
+        return 0;
+    }
+    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+    if (in_codec) WMX_HIP(hipMemcpy(in_codec, h->d_in_codec, n, hipMemcpyDeviceToHost));
+    if (out_law) WMX_HIP(hipMemcpy(out_law, h->d_out_law, n, hipMemcpyDeviceToHost));
+    if (refused) WMX_HIP(hipMemcpy(refused, h->d_refused, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// wmx_rtp_ingest_legs for the handle's streams as legs, with the codec rule per leg
+int wmx_rtp_ingest_legs_codecs(wmx_rtp *h, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride,
+                               const int32_t *d_recv_bytes, int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len,
+                               uint16_t *d_seq_raw, void *stream) {
+    WMX_ON_DEVICE(h);
+    const int n_legs = h ? h->n_streams : 0;
+    if (!h || max_packets < 1 || max_packets > 4 || !d_packets || !d_recv_bytes || !d_pcm || !d_len ||
+        packet_stride < kRtpHeader + kRtpG711Payload || pcm_packet_stride < kRtpG711Payload ||
+        (n_legs > 1 && (leg_stride < packet_stride * max_packets || source_stride < pcm_packet_stride * max_packets))) {
+        set_error("wmx_rtp_ingest_legs_codecs: bad arguments");
+        return WMX_EINVAL;
+    }
+    const int rcs = codec_state(h);
+    if (rcs) return rcs;
+    const size_t rows = (size_t)n_legs * max_packets;
+    const bool wide = aligned_to(d_packets, packet_stride, 4) && leg_stride % 4 == 0 && aligned_to(d_pcm, pcm_packet_stride * 2, 8) &&
+                      (source_stride * 2) % 8 == 0;
+    const bool per_leg = !h->codecs_default;
+    auto kernel = wide ? (per_leg ? rtp_ingest_legs_codecs_kernel<true, true> : rtp_ingest_legs_codecs_kernel<true, false>)
+                       : (per_leg ? rtp_ingest_legs_codecs_kernel<false, true> : rtp_ingest_legs_codecs_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(wmx::stream_grid(rows * (wide ? kRtpWords : kRtpG711Payload), 256)), dim3(256), 0, as_stream(stream), d_packets,
+                       leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw, max_packets, n_legs,
+                       h->d_in_codec, h->d_refused);
+    WMX_LAUNCH_CHECK();
     return 0;
 }
 

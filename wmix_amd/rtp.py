@@ -7,6 +7,8 @@ import torch
 from ._lib import check, lib
 
 LAW = {"a": 0, "u": 1, 0: 0, 1: 1}
+# WMX_CODEC_* (include/wmix_amd.h): what a leg negotiated for the packets it sends us
+CODEC = {"reference": 0, "pcma": 1, "pcmu": 2, "by_pt": 3, 0: 0, 1: 1, 2: 2, 3: 3}
 
 
 class RtpSenders:
@@ -84,6 +86,37 @@ class RtpSenders:
                                             r["dup"].ctypes.data, r["resync"].ctypes.data, r["overflow"].ctypes.data,
                                             torch.cuda.current_stream().cuda_stream), "wmx_rtp_export_sequence")
         return r
+
+    def set_codecs(self, streams, in_codec, out_law):
+        """in_codec ("reference", "pcma", "pcmu", "by_pt") and out_law ("a", "u") of the listed streams (None = all): wmx_rtp_set_codecs"""
+        import numpy as np
+        idx = None if streams is None else np.ascontiguousarray(streams, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_rtp_set_codecs(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, CODEC[in_codec],
+                                       LAW[out_law], torch.cuda.current_stream().cuda_stream), "wmx_rtp_set_codecs")
+
+    def export_codecs(self):
+        """dict(in_codec, out_law: uint8 [n_streams]; refused: uint32 [n_streams]) as the work queued on the current stream leaves them"""
+        import numpy as np
+        r = {"in_codec": np.zeros(self.n, np.uint8), "out_law": np.zeros(self.n, np.uint8), "refused": np.zeros(self.n, np.uint32)}
+        check(lib().wmx_rtp_export_codecs(self._h, r["in_codec"].ctypes.data, r["out_law"].ctypes.data, r["refused"].ctypes.data,
+                                          torch.cuda.current_stream().cuda_stream), "wmx_rtp_export_codecs")
+        return r
+
+    def ingest_legs(self, packets, recv_bytes, look_ahead=0):
+        """ingest_legs() below for this handle's streams as legs, each with its own codec (wmx_rtp_ingest_legs_codecs): a slot that
+        arrived and makes no call under the leg's in_codec is counted in export_codecs()["refused"]"""
+        assert packets.is_cuda and packets.dtype == torch.uint8 and packets.dim() == 3 and packets.stride(2) == 1 and packets.shape[0] == self.n
+        n, k = packets.shape[:2]
+        assert recv_bytes.is_cuda and recv_bytes.dtype == torch.int32 and recv_bytes.is_contiguous() and tuple(recv_bytes.shape) == (n, k)
+        pcm = torch.zeros((n, k, 160 + look_ahead), dtype=torch.int16, device=packets.device)
+        lens = torch.zeros((n, k), dtype=torch.int32, device=packets.device)
+        seq = torch.zeros((n, k), dtype=torch.int16, device=packets.device)
+        check(lib().wmx_rtp_ingest_legs_codecs(self._h, k, packets.data_ptr(), packets.stride(0), packets.stride(1), recv_bytes.data_ptr(),
+                                               pcm.data_ptr(), pcm.stride(0), pcm.stride(1), lens.data_ptr(), seq.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream), "wmx_rtp_ingest_legs_codecs")
+        return pcm, lens, seq
 
     def state(self, stream=0):
         s, t = C.c_uint16(0), C.c_uint32(0)
