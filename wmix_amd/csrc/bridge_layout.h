@@ -18,6 +18,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+#include "mix_cursor.h"
 
 namespace wmx {
 
@@ -99,32 +100,12 @@ inline void bridge_cursors_carry(const std::vector<int32_t> &old_sizes, const Br
     }
 }
 
-// what the cursor rule reads of the mixer (wmx_mix: head_off, tick, play_correct, ring_bytes)
-struct BridgeMixState {
-    uint32_t head_off, tick, play_correct, ring_bytes;
-};
-
-// One wmix_load_data call's cursor arithmetic, as load_begin / load_end of mix.hip do it for wmx_mix_load: where a call that is
-// handed (head, tick) starts (src/wmix.c:1666-1673), and the cursor it ends with after n_out ring samples (:1942-1956).
+// One wmix_load_data call's cursor arithmetic (mix_cursor.h): where a call that is handed (head, tick) starts, and the cursor it ends
+// with after n_out ring samples.
 inline void bridge_cursor_step(const BridgeMixState &m, uint32_t n_out, uint32_t &head, uint32_t &tick, uint32_t &start) {
-    uint32_t head_off = head, tk = tick;
-    if (head_off == UINT32_MAX || tk < m.tick) {
-        head_off = m.head_off + m.play_correct;
-        tk = m.tick + m.play_correct;
-        if (head_off >= m.ring_bytes) head_off = 0;
-    }
-    start = head_off;
-    uint32_t tickAdd = n_out * 2, new_head = head_off + tickAdd;
-    new_head %= m.ring_bytes;
-    if (tk < m.tick) {
-        new_head = m.head_off + tickAdd;
-        tickAdd += m.tick;
-        if (new_head >= m.ring_bytes) new_head -= m.ring_bytes;
-    } else {
-        tickAdd += tk;
-    }
-    tick = tickAdd;
-    head = new_head;
+    mix_cursor_begin(m, head, tick);
+    start = head;
+    mix_cursor_end(m, n_out, head, tick);
 }
 
 // the leads the device holds (one per slot, in ring samples), and whether it holds any

@@ -258,11 +258,8 @@ int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_
 // refused = 0; the leg keeps its codec
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    for (int i = 0; host_idx && i < n; i++)  // before the first of the four: a bad index resets nothing
-        if (host_idx[i] < 0 || host_idx[i] >= h->n_legs) {
-            wmx::set_error("wmx_conf_reset_legs: leg %d is outside the handle's %d", (int)host_idx[i], h->n_legs);
-            return WMX_EINVAL;
-        }
+    // before the first of the five: a bad index resets nothing
+    if (wmx::idx_check(host_idx, n, h->n_legs, "wmx_conf_reset_legs: leg", "handle")) return WMX_EINVAL;
     int rc = wmx_mix_reset_leg_cursors(h->mix, host_idx, n, stream);
     if (rc == 0) rc = wmx_mix_reset_speakers(h->mix, host_idx, n, stream);
     if (rc == 0) rc = wmx_mix_reset_rings(h->mix, host_idx, n, stream);

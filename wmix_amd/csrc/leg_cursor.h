@@ -5,8 +5,8 @@
 // datagram that arrived (:1278-1316), so a leg's cursor moves by the packets IT delivered.  wmix_load_data's cursor rule is the jitter
 // buffer: a sender that fell behind the play head (tick < wmix->tick), or has no cursor yet, jumps to head + VIEW_PLAY_CORRECT -- or
 // to the START of the ring when that lies behind its end (src/wmix.c:1666-1673); one that runs ahead writes further ahead, and the
-// bookkeeping behind the samples moves head and tick by what was written (:1942-1956).  leg_cursor_call restates both for one leg
-// and one packet in the reference's uint32 arithmetic, as load_begin / load_end of mix.hip do for a host cursor.
+// bookkeeping behind the samples moves head and tick by what was written (:1942-1956).  leg_cursor_call applies both (mix_cursor.h)
+// for one leg and one packet, as load_begin / load_end of mix.hip do for a host cursor.
 //
 // The one rule that is not the reference's: a call whose end cursor would lie more than one ring ahead of the mixer's tick is not
 // made (`drop`; the cursor stays).  The reference laps the play head there and adds to samples that are still queued.  A leg's
@@ -17,21 +17,15 @@
 // beside the oracle's orc_load_data.
 #pragma once
 #include <cstdint>
+#include "mix_cursor.h"
 
-#if defined(__HIPCC__)
-#define WMX_LEG_FN __host__ __device__ inline
-#else
-#define WMX_LEG_FN inline
-#endif
+#define WMX_LEG_FN WMX_CURSOR_FN
 
 namespace wmx {
 
 constexpr int kLegMaxPackets = 4;  // WMX_MIX_MAX_LEG_PACKETS (include/wmix_amd.h)
 
-// what the rule reads of the mixer (wmx_mix: head_off, tick, play_correct, ring_bytes)
-struct LegMixState {
-    uint32_t head_off, tick, play_correct, ring_bytes;
-};
+using LegMixState = BridgeMixState;
 
 struct LegCursor {
     uint32_t head, tick;  // head == UINT32_MAX: no cursor yet (the reference's NULL head)
@@ -47,25 +41,12 @@ struct LegCall {
 
 // one wmix_load_data call of n_out ring samples handed the cursor c
 WMX_LEG_FN LegCall leg_cursor_call(const LegMixState &m, uint32_t n_out, LegCursor c) {
-    uint32_t head_off = c.head, tk = c.tick;
-    if (head_off == UINT32_MAX || tk < m.tick) {  // src/wmix.c:1666-1673
-        head_off = m.head_off + m.play_correct;
-        tk = m.tick + m.play_correct;
-        if (head_off >= m.ring_bytes) head_off = 0;
-    }
-    uint32_t tickAdd = n_out * 2, new_head = head_off + tickAdd;  // src/wmix.c:1942-1956
-    new_head %= m.ring_bytes;
-    if (tk < m.tick) {
-        new_head = m.head_off + tickAdd;
-        tickAdd += m.tick;
-        if (new_head >= m.ring_bytes) new_head -= m.ring_bytes;
-    } else {
-        tickAdd += tk;
-    }
     LegCall r;
-    r.start = head_off;
-    r.after = LegCursor{new_head, tickAdd};
-    r.drop = (uint32_t)(tickAdd - m.tick) > m.ring_bytes;
+    r.after = c;
+    mix_cursor_begin(m, r.after.head, r.after.tick);
+    r.start = r.after.head;
+    mix_cursor_end(m, n_out, r.after.head, r.after.tick);
+    r.drop = (uint32_t)(r.after.tick - m.tick) > m.ring_bytes;
     if (r.drop) r.after = c;
     return r;
 }

@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include "legacy_stage.h"
 #include "../../include/wmix_compat.h"
@@ -45,6 +46,22 @@ __device__ __forceinline__ int16_t volume_add(int16_t a, int16_t b) {  // src/wm
     return (int16_t)(s < -32768 ? -32768 : (s > 32767 ? 32767 : s));
 }
 
+// one schedule entry evaluated for one source: the sample itself, or the reference's linear "repair" fill when up-sampling
+__device__ __forceinline__ int16_t load_entry_value(const int16_t *__restrict__ p, const LoadEntry e, int rdce) {
+    int16_t v;
+    if (e.k < 0) {
+        v = p[e.src];
+    } else {
+        // repairBuff[k] = prev + (k+1 times accumulated) step, float adds in the reference's order
+        const int16_t prev = p[e.src - e.step];
+        const float st = (float)((int)p[e.src] - (int)prev) / (float)e.n2;
+        float sum = st;
+        for (int j = 0; j < e.k; j++) sum += st;
+        v = (int16_t)((float)prev + sum);
+    }
+    return (int16_t)(v / rdce);
+}
+
 // one thread = one ring sample of one group; all `n_src` sources are accumulated in order
 __global__ __launch_bounds__(256) void load_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
                                                    const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t head_sample, int n_src,
@@ -59,21 +76,7 @@ __global__ __launch_bounds__(256) void load_kernel(int16_t *__restrict__ rings, 
         int16_t *dst = rings + g * (size_t)ring_samples + pos;
         int16_t acc = *dst;
         const int16_t *sg = src + g * group_stride;
-        for (int s = 0; s < n_src; s++) {
-            const int16_t *p = sg + (size_t)s * source_stride;
-            int16_t v;
-            if (e.k < 0) {
-                v = p[e.src];
-            } else {
-                // repairBuff[k] = prev + (k+1 times accumulated) step, float adds in the reference's order
-                const int16_t prev = p[e.src - e.step];
-                const float st = (float)((int)p[e.src] - (int)prev) / (float)e.n2;
-                float sum = st;
-                for (int j = 0; j < e.k; j++) sum += st;
-                v = (int16_t)((float)prev + sum);
-            }
-            acc = volume_add(acc, (int16_t)(v / rdce));
-        }
+        for (int s = 0; s < n_src; s++) acc = volume_add(acc, load_entry_value(sg + (size_t)s * source_stride, e, rdce));
         *dst = acc;
     }
 }
@@ -92,26 +95,41 @@ __global__ __launch_bounds__(256) void drain_kernel(int16_t *__restrict__ rings,
     }
 }
 
-// load_kernel's evaluation of one schedule entry for one source (that kernel keeps its own copy: it is not touched)
-__device__ __forceinline__ int16_t load_entry_value(const int16_t *__restrict__ p, const LoadEntry e, int rdce) {
-    int16_t v;
-    if (e.k < 0) {
-        v = p[e.src];
-    } else {
-        const int16_t prev = p[e.src - e.step];
-        const float st = (float)((int)p[e.src] - (int)prev) / (float)e.n2;
-        float sum = st;
-        for (int j = 0; j < e.k; j++) sum += st;
-        v = (int16_t)((float)prev + sum);
+// The two sweeps of the bridge load (mix_minus.h) over one ring-sample column of a conference of n members: the same sample position
+// in the members' rings.  Every source is evaluated ONCE.  Forward sweep: y[q] = F_q(ring_q) with the running prefix map; backward
+// sweep: ring_q = G_q(y[q]) with the running suffix map.  PMAX is the compile-time bound that keeps c[] and y[] in registers (fully
+// unrolled, `q < n` predicates): no scratch.  load_minus_conf_kernel keeps a copy of the sweeps (see there).  ring(q): the address of member q's sample in this column.  value(q, c): sets c to what
+// source q adds and returns true, or returns false and leaves the 0 -- a muted source, or one that does not cover the column, adds 0,
+// which is what not calling wmix_load_data for it leaves.  SKIP_EMPTY: a column for which every value() returned false is not written.
+// The kernels' closures capture BY VALUE and are taken by reference here: with reference captures the compiler no longer hoists the
+// schedule entry's per-column arithmetic out of the sweep (5 % more instructions, 2 % more time on 65 536 conferences of 8).
+template <int PMAX, bool SKIP_EMPTY, class Ring, class Value>
+__device__ __forceinline__ void minus_sweeps(int n, const Ring &ring, const Value &value) {
+    int c[PMAX], y[PMAX];
+    bool any = false;
+    ClampMap f = clamp_map_identity();
+#pragma unroll
+    for (int q = 0; q < PMAX; q++) {
+        c[q] = 0;
+        y[q] = 0;
+        if (q < n) {
+            any |= value(q, c[q]);
+            y[q] = clamp_map_apply(f, *ring(q));
+            f = clamp_map_then_add(f, (int16_t)c[q]);
+        }
     }
-    return (int16_t)(v / rdce);
+    if (SKIP_EMPTY && !any) return;
+    ClampMap g = clamp_map_identity();
+#pragma unroll
+    for (int q = PMAX - 1; q >= 0; q--) {
+        if (q < n) {
+            *ring(q) = clamp_map_apply(g, (int16_t)y[q]);
+            g = clamp_map_add_then((int16_t)c[q], g);
+        }
+    }
 }
 
-// The bridge load (mix_minus.h): one thread = one ring-sample column of one conference, i.e. the same sample position in the
-// `parties` consecutive rings of that conference.  Every source is evaluated ONCE.  Forward sweep: y[q] = F_q(ring_q) with the
-// running prefix map; backward sweep: ring_q = G_q(y[q]) with the running suffix map.  PMAX is the compile-time bound that keeps
-// c[] and y[] in registers (fully unrolled, `q < parties` predicates): no scratch.  A muted source adds 0, which is what
-// not calling wmix_load_data for it leaves.
+// The bridge load: one thread = one ring-sample column of one conference, the `parties` consecutive rings of that conference.
 template <int PMAX>
 __global__ __launch_bounds__(256) void load_minus_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
                                                          const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t head_sample, int parties,
@@ -127,35 +145,24 @@ __global__ __launch_bounds__(256) void load_minus_kernel(int16_t *__restrict__ r
         int16_t *col = rings + conf * (size_t)parties * ring_samples + pos;
         const int16_t *sc = src + conf * conf_stride;
         const uint8_t *mc = mute ? mute + conf * (size_t)parties : nullptr;
-        int c[PMAX], y[PMAX];
-        ClampMap f = clamp_map_identity();
-#pragma unroll
-        for (int q = 0; q < PMAX; q++) {
-            c[q] = 0;
-            y[q] = 0;
-            if (q < parties) {
-                if (!mc || !mc[q]) c[q] = load_entry_value(sc + (size_t)q * source_stride, e, rdce);
-                y[q] = clamp_map_apply(f, col[(size_t)q * ring_samples]);
-                f = clamp_map_then_add(f, (int16_t)c[q]);
-            }
-        }
-        ClampMap g = clamp_map_identity();
-#pragma unroll
-        for (int q = PMAX - 1; q >= 0; q--) {
-            if (q < parties) {
-                col[(size_t)q * ring_samples] = clamp_map_apply(g, (int16_t)y[q]);
-                g = clamp_map_add_then((int16_t)c[q], g);
-            }
-        }
+        minus_sweeps<PMAX, false>(
+            parties, [=](int q) { return col + (size_t)q * ring_samples; },
+            [=](int q, int &c) {
+                if (mc && mc[q]) return false;
+                c = load_entry_value(sc + (size_t)q * source_stride, e, rdce);
+                return true;
+            });
     }
 }
 
-// The bridge load over a layout (bridge_layout.h): load_minus_kernel's two sweeps with the ring and source addresses taken from the
-// member list.  One thread = one ring-sample column of one conference of this size class (`tab`: {offset into members, size} per slot;
+// The bridge load over a layout (bridge_layout.h): the ring and source addresses are taken from the member list.  One thread = one
+// ring-sample column of one conference of this size class (`tab`: {offset into members, size} per slot;
 // `lead`: the slot's start column relative to base_sample).  A slot's columns are dealt out in whole waves (n_pad = n_out rounded up to
 // the wave, the lanes past n_out idle), so the slot is wave-uniform: the table entry, the member indices and the mute bytes are scalar
 // loads and the ring / source bases scalar arithmetic.  The members of a conference are distinct rings and a ring is in one conference
 // only (bridge_layout_build), so no two threads touch the same ring sample.
+// This kernel writes minus_sweeps' two sweeps out itself: through the shared function its 32-wide instantiation compiled to 86 VGPRs
+// for 84 and measured 0.6 - 0.9 % slower on 16 384 conferences of 32 (DESIGN_HISTORY.md); the other two kernels lose nothing.
 template <int PMAX>
 __global__ __launch_bounds__(256) void load_minus_conf_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
                                                               const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t n_pad,
@@ -208,12 +215,57 @@ __global__ __launch_bounds__(256) void speakers_clear_kernel(uint8_t *__restrict
     }
 }
 
+// the part of a row's level that lane `sub` of the L lanes dealt to the row sums: the elements in front of the first
+// 16-byte boundary and behind the last one singly, the rest as 16-byte loads, so a row that is not aligned (source_stride is the
+// caller's) is read the same way, and every element once over the L lanes
+__device__ __forceinline__ uint32_t abs_sum_part(const int16_t *__restrict__ row, uint32_t n_el, uint32_t sub, uint32_t L) {
+    uint32_t sum = 0;
+    uint32_t head = (8u - (uint32_t)(((uintptr_t)row & 15u) >> 1)) & 7u;  // elements in front of the 16-byte boundary
+    if (head > n_el) head = n_el;
+    const uint32_t body = (n_el - head) / 8;  // whole 16-byte pieces, none past the row's end
+    for (uint32_t i = sub; i < head; i += L) sum += speakers_abs16(row[i]);
+    const uint4 *v = reinterpret_cast<const uint4 *>(row + head);
+    for (uint32_t c = sub; c < body; c += L) {
+        const uint4 x = v[c];
+        sum += abs_sum_pair(x.x) + abs_sum_pair(x.y) + abs_sum_pair(x.z) + abs_sum_pair(x.w);
+    }
+    for (uint32_t i = head + body * 8 + sub; i < n_el; i += L) sum += speakers_abs16(row[i]);
+    return sum;
+}
+
+// Lane p = member p, for the whole wave outside every divergent branch (a ballot and lane reads): the member's env' from its level
+// (speakers.h), the rank from the n envelopes read lane by lane, and the three stores to ring r.  A lane that is no member brings
+// nothing and stores nothing.
+template <class RingOf>
+__device__ __forceinline__ void speakers_rank_store(bool member, const RingOf &ring_of, uint32_t level, int n, int lane, const uint8_t *__restrict__ mute,
+                                                    int max_speakers, uint32_t floor, int decay_shift, uint32_t *__restrict__ env,
+                                                    uint8_t *__restrict__ speaking, uint8_t *__restrict__ mute_out) {
+    size_t r = 0;
+    uint32_t e = 0;
+    bool eligible = false;
+    if (member) {
+        r = ring_of();
+        e = speakers_env_next(env[r], level, decay_shift);
+        eligible = speakers_eligible(mute && mute[r], e, floor);
+    }
+    const unsigned long long eligible_lanes = __ballot(eligible);
+    int rank = 0;
+    for (int s = 0; s < n; s++) {  // s is wave-uniform: a lane read, no LDS traffic
+        const uint32_t es = (uint32_t)__builtin_amdgcn_readlane((int)e, s);
+        rank += ((eligible_lanes >> s) & 1ull) && speakers_outranks(es, s, e, lane);
+    }
+    if (member) {
+        const bool sp = eligible && rank < max_speakers;
+        env[r] = e;
+        speaking[r] = sp ? 1 : 0;
+        mute_out[r] = sp ? 0 : 1;
+    }
+}
+
 // One wave = one conference (a slot of the layout when `tab` is given, else `parties` consecutive rings), the workgroup's waves on
 // conferences of their own.  The wave's lanes are dealt out to the members, L = the largest power of two with n * L <= 64 lanes each
-// (32 for a two-party call, 2 for 32 legs): the L lanes of a member stride its source row -- the elements in front of the first
-// 16-byte boundary and behind the last one singly, the rest as 16-byte loads, so a row that is not aligned (source_stride is the
-// caller's) is read the same way and every element once -- and an xor-shuffle over the L lanes gives the row's level.  Then lane p
-// is member p: its env' (speakers.h), the rank from the n envelopes read lane by lane, and the three stores.  No LDS, no atomics.
+// (32 for a two-party call, 2 for 32 legs): the L lanes of a member stride its source row (abs_sum_part) and an xor-shuffle over the
+// L lanes gives the row's level.  Then lane p is member p (speakers_rank_store).  No LDS, no atomics.
 __global__ __launch_bounds__(256) void select_speakers_kernel(const int16_t *__restrict__ src, uint32_t n_el, int parties, long conf_stride,
                                                               long source_stride, const int32_t *__restrict__ tab,
                                                               const int32_t *__restrict__ members, const uint8_t *__restrict__ mute,
@@ -230,59 +282,15 @@ __global__ __launch_bounds__(256) void select_speakers_kernel(const int16_t *__r
         uint32_t sum = 0;
         if (q < n) {
             const int16_t *row = mem ? src + (size_t)mem[q] * source_stride : src + (size_t)slot * conf_stride + (size_t)q * source_stride;
-            uint32_t head = (8u - (uint32_t)(((uintptr_t)row & 15u) >> 1)) & 7u;  // elements in front of the 16-byte boundary
-            if (head > n_el) head = n_el;
-            const uint32_t body = (n_el - head) / 8;  // whole 16-byte pieces, none past the row's end
-            for (uint32_t i = (uint32_t)sub; i < head; i += (uint32_t)L) sum += speakers_abs16(row[i]);
-            const uint4 *v = reinterpret_cast<const uint4 *>(row + head);
-            for (uint32_t c = (uint32_t)sub; c < body; c += (uint32_t)L) {
-                const uint4 x = v[c];
-                sum += abs_sum_pair(x.x) + abs_sum_pair(x.y) + abs_sum_pair(x.z) + abs_sum_pair(x.w);
-            }
-            for (uint32_t i = head + body * 8 + (uint32_t)sub; i < n_el; i += (uint32_t)L) sum += speakers_abs16(row[i]);
+            sum = abs_sum_part(row, n_el, (uint32_t)sub, (uint32_t)L);
         }
         for (int o = L >> 1; o > 0; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o);
         // lane p = member p
         const uint32_t level = (uint32_t)__shfl((int)sum, (lane << shift) & 63);
         const bool member = lane < n;
-        size_t r = 0;
-        uint32_t e = 0;
-        bool eligible = false;
-        if (member) {
-            r = mem ? (size_t)mem[lane] : (size_t)slot * parties + lane;
-            e = speakers_env_next(env[r], level, decay_shift);
-            eligible = speakers_eligible(mute && mute[r], e, floor);
-        }
-        const unsigned long long eligible_lanes = __ballot(eligible);
-        int rank = 0;
-        for (int s = 0; s < n; s++) {  // s is wave-uniform: a lane read, no LDS traffic
-            const uint32_t es = (uint32_t)__builtin_amdgcn_readlane((int)e, s);
-            rank += ((eligible_lanes >> s) & 1ull) && speakers_outranks(es, s, e, lane);
-        }
-        if (member) {
-            const bool sp = eligible && rank < max_speakers;
-            env[r] = e;
-            speaking[r] = sp ? 1 : 0;
-            mute_out[r] = sp ? 0 : 1;
-        }
+        speakers_rank_store(member, [=] { return mem ? (size_t)mem[lane] : (size_t)slot * parties + lane; }, level, n, lane, mute, max_speakers,
+                            floor, decay_shift, env, speaking, mute_out);
     }
-}
-
-// the part of a row's level that lane `sub` of the L lanes dealt to the row sums: select_speakers_kernel's walk (elements in front of
-// the first 16-byte boundary and behind the last one singly, the rest as 16-byte loads), every element once over the L lanes
-__device__ __forceinline__ uint32_t abs_sum_part(const int16_t *__restrict__ row, uint32_t n_el, uint32_t sub, uint32_t L) {
-    uint32_t sum = 0;
-    uint32_t head = (8u - (uint32_t)(((uintptr_t)row & 15u) >> 1)) & 7u;
-    if (head > n_el) head = n_el;
-    const uint32_t body = (n_el - head) / 8;
-    for (uint32_t i = sub; i < head; i += L) sum += speakers_abs16(row[i]);
-    const uint4 *v = reinterpret_cast<const uint4 *>(row + head);
-    for (uint32_t c = sub; c < body; c += L) {
-        const uint4 x = v[c];
-        sum += abs_sum_pair(x.x) + abs_sum_pair(x.y) + abs_sum_pair(x.z) + abs_sum_pair(x.w);
-    }
-    for (uint32_t i = head + body * 8 + sub; i < n_el; i += L) sum += speakers_abs16(row[i]);
-    return sum;
 }
 
 // Talker selection over leg packets (speakers.h: speakers_level_legs): select_speakers_kernel's dealing -- one wave = one conference
@@ -330,25 +338,8 @@ __global__ __launch_bounds__(256) void select_speakers_legs_kernel(const int16_t
         const uint32_t level = (uint32_t)__shfl((int)best, (lane << shift) & 63);
         const int32_t rl = lane < n ? mem[lane] : -1;
         const bool member = rl >= 0 && rl < n_groups;
-        const size_t r = member ? (size_t)rl : 0;
-        uint32_t e = 0;
-        bool eligible = false;
-        if (member) {
-            e = speakers_env_next(env[r], level, decay_shift);
-            eligible = speakers_eligible(mute && mute[r], e, floor);
-        }
-        const unsigned long long eligible_lanes = __ballot(eligible);
-        int rank = 0;
-        for (int s = 0; s < n; s++) {  // s is wave-uniform: a lane read, no LDS traffic
-            const uint32_t es = (uint32_t)__builtin_amdgcn_readlane((int)e, s);
-            rank += ((eligible_lanes >> s) & 1ull) && speakers_outranks(es, s, e, lane);
-        }
-        if (member) {
-            const bool sp = eligible && rank < max_speakers;
-            env[r] = e;
-            speaking[r] = sp ? 1 : 0;
-            mute_out[r] = sp ? 0 : 1;
-        }
+        speakers_rank_store(member, [=] { return (size_t)rl; }, level, n, lane, mute, max_speakers, floor, decay_shift, env, speaking,
+                            mute_out);
     }
 }
 
@@ -436,7 +427,7 @@ __global__ __launch_bounds__(256) void leg_cursor_kernel(const int32_t *__restri
     }
 }
 
-// The bridge load with a cursor per leg: load_minus_conf_kernel's two sweeps, with each source's value looked up through its
+// The bridge load with a cursor per leg: load_minus_conf_kernel's addressing, with each source's value looked up through its
 // span.  One thread = one ring column of one conference of this size class; the columns are those of the conference's window.  A
 // slot is dealt n_pad columns (whole waves, so the slot is wave-uniform and its table entry, window, member indices and spans are
 // scalar loads); a window longer than that is walked in strides of n_pad, a wave whose first column lies behind the window's end
@@ -461,42 +452,25 @@ __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restric
         for (uint32_t col = (uint32_t)(t % n_pad); col < wlen; col += n_pad) {
             uint32_t pos = wstart + col;  // both < ring_samples
             pos -= pos >= ring_samples ? ring_samples : 0u;
-            int c[PMAX], y[PMAX];
-            bool any = false;
-            ClampMap f = clamp_map_identity();
-#pragma unroll
-            for (int q = 0; q < PMAX; q++) {
-                c[q] = 0;
-                y[q] = 0;
-                if (q < n) {
-                    const int32_t ri = mem[q];
-                    const size_t r = (size_t)(ri >= 0 && ri < n_groups ? ri : 0);
+            // a member index read from memory never addresses anything as it is
+            auto ring_of = [=](int q) {
+                const int32_t ri = mem[q];
+                return (size_t)(ri >= 0 && ri < n_groups ? ri : 0);
+            };
+            minus_sweeps<PMAX, true>(
+                n, [=](int q) { return rings + ring_of(q) * ring_samples + pos; },
+                [=](int q, int &c) {
+                    const size_t r = ring_of(q);
                     const LegSpanEntry e = span[r];
                     const uint32_t st = e.start < ring_samples ? e.start : 0u;
                     const uint32_t d = pos >= st ? pos - st : pos + ring_samples - st;
-                    if (d < e.len && d < (uint32_t)kLegMaxPackets * n_out) {
-                        const uint32_t j = (d >= n_out) + (d >= 2 * n_out) + (d >= 3 * n_out);  // the call, 0 .. 3, and its sample
-                        if (!CALLS || !((e.pad >> j) & 1u)) {
-                            const uint32_t k = (e.slots >> (2u * j)) & 3u;
-                            c[q] = load_entry_value(src + r * source_stride + (size_t)k * packet_stride, sch[d - j * n_out], rdce);
-                            any = true;
-                        }
-                    }
-                    y[q] = clamp_map_apply(f, rings[r * ring_samples + pos]);
-                    f = clamp_map_then_add(f, (int16_t)c[q]);
-                }
-            }
-            if (!any) continue;
-            ClampMap g = clamp_map_identity();
-#pragma unroll
-            for (int q = PMAX - 1; q >= 0; q--) {
-                if (q < n) {
-                    const int32_t ri = mem[q];
-                    const size_t r = (size_t)(ri >= 0 && ri < n_groups ? ri : 0);
-                    rings[r * ring_samples + pos] = clamp_map_apply(g, (int16_t)y[q]);
-                    g = clamp_map_add_then((int16_t)c[q], g);
-                }
-            }
+                    if (d >= e.len || d >= (uint32_t)kLegMaxPackets * n_out) return false;
+                    const uint32_t j = (d >= n_out) + (d >= 2 * n_out) + (d >= 3 * n_out);  // the call, 0 .. 3, and its sample
+                    if (CALLS && ((e.pad >> j) & 1u)) return false;
+                    const uint32_t k = (e.slots >> (2u * j)) & 3u;
+                    c = load_entry_value(src + r * source_stride + (size_t)k * packet_stride, sch[d - j * n_out], rdce);
+                    return true;
+                });
         }
     }
 }
@@ -566,16 +540,11 @@ void wmx::mix_played(wmx_mix *m, uint32_t bytes) {
     m->tick += bytes;
 }
 
-// What wmx_mix_load and wmx_mix_load_minus share on the host: where the call starts (the reference's cursor rule), the schedule of
-// its source format, and the cursor the call ends with.
-static int load_begin(wmx_mix *m, const char *who, uint32_t srcU8Len, int freq, int channels, int sample, uint32_t &head_off, uint32_t &tk,
-                      wmx::SchedCache::Entry **out) {
+static wmx::BridgeMixState cursor_state(const wmx_mix *m) { return wmx::BridgeMixState{m->head_off, m->tick, m->play_correct, m->ring_bytes}; }
+
+// The schedule of a source format, from the handle's cache or made and uploaded here, and wmx_mix_load's refusals.
+static int load_sched(wmx_mix *m, const char *who, uint32_t srcU8Len, int freq, int channels, int sample, wmx::SchedCache::Entry **out) {
     using namespace wmx;
-    if (head_off == UINT32_MAX || tk < m->tick) {  // src/wmix.c:1666-1673
-        head_off = m->head_off + m->play_correct;
-        tk = m->tick + m->play_correct;
-        if (head_off >= m->ring_bytes) head_off = 0;
-    }
     const uint64_t k0 = ((uint64_t)srcU8Len << 32) | (uint32_t)freq, k1 = ((uint64_t)(uint8_t)channels << 8) | (uint8_t)sample;
     SchedCache::Entry *ent = m->sched.find(k0, k1);
     if (!ent) {
@@ -596,19 +565,28 @@ static int load_begin(wmx_mix *m, const char *who, uint32_t srcU8Len, int freq, 
     return 0;
 }
 
-// cursor bookkeeping, src/wmix.c:1942-1956
+// What wmx_mix_load and wmx_mix_load_minus share on the host: where the call starts (mix_cursor.h) and the
+// schedule of its source format; and the cursor the call ends with.
+static int load_begin(wmx_mix *m, const char *who, uint32_t srcU8Len, int freq, int channels, int sample, uint32_t &head_off, uint32_t &tk,
+                      wmx::SchedCache::Entry **out) {
+    wmx::mix_cursor_begin(cursor_state(m), head_off, tk);
+    return load_sched(m, who, srcU8Len, freq, channels, sample, out);
+}
+
 static void load_end(const wmx_mix *m, uint32_t n_out, uint32_t head_off, uint32_t tk, uint32_t *head, uint32_t *tick) {
-    uint32_t tickAdd = n_out * 2, new_head = head_off + tickAdd;
-    new_head %= m->ring_bytes;
-    if (tk < m->tick) {
-        new_head = m->head_off + tickAdd;
-        tickAdd += m->tick;
-        if (new_head >= m->ring_bytes) new_head -= m->ring_bytes;
-    } else {
-        tickAdd += tk;
-    }
-    *tick = tickAdd;
-    *head = new_head;
+    wmx::mix_cursor_end(cursor_state(m), n_out, head_off, tk);
+    *head = head_off;
+    *tick = tk;
+}
+
+// The instantiation of a bridge load kernel for size class cls (bridge_layout.h).  `of` is handed the class's bound PMAX as a
+// compile-time constant and names the kernel:
+//     auto kernel = kernel_of_class(cls, [](auto pmax) { return load_minus_kernel<decltype(pmax)::value>; });
+template <class Of>
+static auto kernel_of_class(int cls, Of of) {
+    using std::integral_constant;
+    return cls == 0 ? of(integral_constant<int, 4>()) : cls == 1 ? of(integral_constant<int, 8>()) : cls == 2 ? of(integral_constant<int, 16>())
+                                                                                                           : of(integral_constant<int, 32>());
 }
 
 extern "C" {
@@ -820,7 +798,7 @@ int wmx_mix_load_minus(wmx_mix *m, int parties, const int16_t *d_src, uint32_t s
     if (n_out) {
         const int n_conf = m->n_groups / parties;
         const unsigned grid = stream_grid((size_t)n_out * n_conf, 256);
-        auto kernel = parties <= 4 ? load_minus_kernel<4> : parties <= 8 ? load_minus_kernel<8> : parties <= 16 ? load_minus_kernel<16> : load_minus_kernel<32>;
+        auto kernel = kernel_of_class(bridge_size_class(parties), [](auto pmax) { return load_minus_kernel<decltype(pmax)::value>; });
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out,
                            head_off / 2, parties, conf_stride, source_stride, d_mute, rdce, n_conf);
         WMX_LAUNCH_CHECK();
@@ -885,16 +863,13 @@ int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
         return WMX_EINVAL;
     }
     if (!d_src || srcU8Len < 1) return 0;  // like wmx_mix_load
-    // the schedule of the source format, and wmx_mix_load's refusals; a cursor that the rule leaves alone keeps load_begin to that
-    uint32_t h0 = 0, t0 = m->tick;
     SchedCache::Entry *ent = nullptr;
-    const int rcb = load_begin(m, "wmx_mix_load_minus_conf", srcU8Len, freq, channels, sample, h0, t0, &ent);
+    const int rcb = load_sched(m, "wmx_mix_load_minus_conf", srcU8Len, freq, channels, sample, &ent);
     if (rcb) return rcb;
     const uint32_t n_out = (uint32_t)ent->n;
     const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
     hipStream_t s = as_stream(stream);
-    const BridgeMixState ms{m->head_off, m->tick, m->play_correct, m->ring_bytes};
-    const BridgePlan plan = bridge_plan_load(m->conf, ms, n_out, head, tick, m->conf_leads, m->conf_next);
+    const BridgePlan plan = bridge_plan_load(m->conf, cursor_state(m), n_out, head, tick, m->conf_leads, m->conf_next);
     if (plan.upload) {
         WMX_HIP(hipStreamSynchronize(s));  // the previous upload must have left h_conf_lead before it is rewritten
         m->h_conf_lead = m->conf_leads.lead;
@@ -905,7 +880,7 @@ int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
         if (!n_slots) continue;
         const uint32_t n_pad = (n_out + 63) / 64 * 64;  // whole waves per conference: the slot is wave-uniform
         const unsigned grid = stream_grid((size_t)n_pad * n_slots, 256);
-        auto kernel = k == 0 ? load_minus_conf_kernel<4> : k == 1 ? load_minus_conf_kernel<8> : k == 2 ? load_minus_conf_kernel<16> : load_minus_conf_kernel<32>;
+        auto kernel = kernel_of_class(k, [](auto pmax) { return load_minus_conf_kernel<decltype(pmax)::value>; });
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out,
                            n_pad, plan.base_sample, (const int32_t *)m->d_conf_tab + 2 * (size_t)first, (const uint32_t *)m->d_conf_lead + first,
                            (const int32_t *)m->d_conf_members, source_stride, d_mute, rdce, n_slots);
@@ -920,25 +895,15 @@ int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
 static int legs_state(wmx_mix *m) {
     using namespace wmx;
     if (m->d_leg_span) return 0;
-    const size_t n = (size_t)m->n_groups, n_win = n / 2 + 1;
-    const size_t bytes = n * sizeof(LegSpanEntry) + n_win * sizeof(uint2) + 3 * n * sizeof(uint32_t);
+    const size_t n = (size_t)m->n_groups, n_win = n / 2 + 1, head_off = n * sizeof(LegSpanEntry) + n_win * sizeof(uint2);
     void *p = nullptr;
-    WMX_HIP(hipMalloc(&p, bytes));
-    LegSpanEntry *span = static_cast<LegSpanEntry *>(p);
-    uint2 *win = reinterpret_cast<uint2 *>(span + n);
-    uint32_t *head = reinterpret_cast<uint32_t *>(win + n_win);
-    hipError_t e = hipMemset(p, 0, bytes);
-    if (e == hipSuccess) e = hipMemset(head, 0xff, n * sizeof(uint32_t));  // UINT32_MAX: no cursor yet
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return hip_fail(e, "hipMemset(leg cursors)", __FILE__, __LINE__);
-    }
-    m->d_leg_span = span;
-    m->d_leg_win = win;
-    m->d_leg_head = head;
-    m->d_leg_tick = head + n;
-    m->d_leg_dropped = head + 2 * n;
+    const int rc = zeroed_block(&p, head_off + 3 * n * sizeof(uint32_t), "hipMemset(leg cursors)", head_off, 0xff, n * sizeof(uint32_t));
+    if (rc) return rc;  // 0xff: UINT32_MAX, no cursor yet
+    m->d_leg_span = static_cast<LegSpanEntry *>(p);
+    m->d_leg_win = reinterpret_cast<uint2 *>(m->d_leg_span + n);
+    m->d_leg_head = reinterpret_cast<uint32_t *>(m->d_leg_win + n_win);
+    m->d_leg_tick = m->d_leg_head + n;
+    m->d_leg_dropped = m->d_leg_head + 2 * n;
     return 0;
 }
 
@@ -963,9 +928,8 @@ static int load_minus_legs_any(const char *who, wmx_mix *m, const int16_t *d_src
         return WMX_EINVAL;
     }
     if (srcU8Len < 1) return 0;  // like wmx_mix_load
-    uint32_t h0 = 0, t0 = m->tick;  // a cursor the rule leaves alone keeps load_begin to the schedule and wmx_mix_load's refusals
     SchedCache::Entry *ent = nullptr;
-    const int rcb = load_begin(m, who, srcU8Len, freq, channels, sample, h0, t0, &ent);
+    const int rcb = load_sched(m, who, srcU8Len, freq, channels, sample, &ent);
     if (rcb) return rcb;
     const uint32_t n_out = (uint32_t)ent->n;
     // a call list holds up to WMX_MIX_MAX_LEG_PACKETS calls whatever max_packets is: silence calls need no slot
@@ -980,9 +944,8 @@ static int load_minus_legs_any(const char *who, wmx_mix *m, const int16_t *d_src
     if (!n_out || !n_slots) return 0;
     const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
     hipStream_t s = as_stream(stream);
-    const LegMixState ms{m->head_off, m->tick, m->play_correct, m->ring_bytes};
     hipLaunchKernelGGL(with_calls ? leg_cursor_kernel<true> : leg_cursor_kernel<false>, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0,
-                       s, (const int32_t *)m->d_conf_tab, (const int32_t *)m->d_conf_members, d_len, srcU8Len, max_packets, d_mute, ms, n_out,
+                       s, (const int32_t *)m->d_conf_tab, (const int32_t *)m->d_conf_members, d_len, srcU8Len, max_packets, d_mute, cursor_state(m), n_out,
                        m->d_leg_head, m->d_leg_tick, m->d_leg_dropped, m->d_leg_span, m->d_leg_win, m->n_groups, n_slots, d_calls);
     WMX_LAUNCH_CHECK();
     // whole waves per conference, enough for the longest window of legs that write side by side; a longer one is walked in strides
@@ -991,14 +954,8 @@ static int load_minus_legs_any(const char *who, wmx_mix *m, const int16_t *d_src
         const int first = m->conf.class_begin[k], n_class = m->conf.class_begin[k + 1] - first;
         if (!n_class) continue;
         const unsigned grid = stream_grid((size_t)n_pad * n_class, 256);
-        auto kernel = with_calls ? (k == 0   ? load_minus_legs_kernel<4, true>
-                                    : k == 1 ? load_minus_legs_kernel<8, true>
-                                    : k == 2 ? load_minus_legs_kernel<16, true>
-                                             : load_minus_legs_kernel<32, true>)
-                                 : (k == 0   ? load_minus_legs_kernel<4, false>
-                                    : k == 1 ? load_minus_legs_kernel<8, false>
-                                    : k == 2 ? load_minus_legs_kernel<16, false>
-                                             : load_minus_legs_kernel<32, false>);
+        auto kernel = with_calls ? kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, true>; })
+                                 : kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, false>; });
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out, n_pad,
                            (const int32_t *)m->d_conf_tab + 2 * (size_t)first, (const uint2 *)m->d_leg_win + first,
                            (const LegSpanEntry *)m->d_leg_span, (const int32_t *)m->d_conf_members, source_stride, packet_stride, rdce,
@@ -1026,11 +983,7 @@ int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *
     WMX_ON_DEVICE(m);
     using namespace wmx;
     if (!m || (host_idx && n < 0)) return WMX_EINVAL;
-    for (int i = 0; host_idx && i < n; i++)
-        if (host_idx[i] < 0 || host_idx[i] >= m->n_groups) {
-            set_error("wmx_mix_reset_leg_cursors: ring %d is outside the mixer's %d", (int)host_idx[i], m->n_groups);
-            return WMX_EINVAL;
-        }
+    if (idx_check(host_idx, n, m->n_groups, "wmx_mix_reset_leg_cursors: ring", "mixer")) return WMX_EINVAL;
     const bool fresh = !m->d_leg_span;
     const int rcs = legs_state(m);
     if (rcs || fresh) return rcs;  // just made: fresh already
@@ -1038,14 +991,8 @@ int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *
     if (host_idx && n == 0) return 0;
     const int count = host_idx ? n : m->n_groups;
     if (host_idx) {
-        WMX_HIP(hipStreamSynchronize(s));  // a reset in flight may still read the list that is rewritten here
-        if ((size_t)n > m->reset_cap) {
-            if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
-            m->d_reset_idx = nullptr, m->reset_cap = 0;
-            WMX_HIP(hipMalloc(&m->d_reset_idx, (size_t)n * sizeof(int32_t)));
-            m->reset_cap = (size_t)n;
-        }
-        WMX_HIP(hipMemcpy(m->d_reset_idx, host_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        const int rcu = upload_idx(m->d_reset_idx, m->reset_cap, host_idx, n, s);
+        if (rcu) return rcu;
     }
     hipLaunchKernelGGL(leg_reset_kernel, dim3(stream_grid((size_t)count, 256)), dim3(256), 0, s, m->d_leg_head, m->d_leg_tick, m->d_leg_dropped,
                        host_idx ? (const int32_t *)m->d_reset_idx : (const int32_t *)nullptr, count, m->n_groups);
@@ -1079,13 +1026,8 @@ static int speakers_state(wmx_mix *m) {
     if (m->d_env) return 0;
     const size_t n = (size_t)m->n_groups;
     void *p = nullptr;
-    WMX_HIP(hipMalloc(&p, n * sizeof(uint32_t) + n));
-    hipError_t e = hipMemset(p, 0, n * sizeof(uint32_t) + n);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return wmx::hip_fail(e, "hipMemset(speakers)", __FILE__, __LINE__);
-    }
+    const int rc = wmx::zeroed_block(&p, n * sizeof(uint32_t) + n, "hipMemset(speakers)");
+    if (rc) return rc;
     m->d_env = static_cast<uint32_t *>(p);
     m->d_speaking = reinterpret_cast<uint8_t *>(m->d_env + n);
     return 0;
@@ -1208,11 +1150,7 @@ int wmx_mix_reset_rings(wmx_mix *m, const int32_t *host_idx, int n, void *stream
     WMX_ON_DEVICE(m);
     using namespace wmx;
     if (!m || (host_idx && n < 0)) return WMX_EINVAL;
-    for (int i = 0; host_idx && i < n; i++)
-        if (host_idx[i] < 0 || host_idx[i] >= m->n_groups) {
-            set_error("wmx_mix_reset_rings: ring %d is outside the mixer's %d", (int)host_idx[i], m->n_groups);
-            return WMX_EINVAL;
-        }
+    if (idx_check(host_idx, n, m->n_groups, "wmx_mix_reset_rings: ring", "mixer")) return WMX_EINVAL;
     hipStream_t s = as_stream(stream);
     if (!host_idx) {
         WMX_HIP(hipMemsetAsync(m->d_rings, 0, (size_t)m->ring_bytes * m->n_groups, s));
@@ -1227,11 +1165,7 @@ int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *str
     WMX_ON_DEVICE(m);
     using namespace wmx;
     if (!m || (host_idx && n < 0)) return WMX_EINVAL;
-    for (int i = 0; host_idx && i < n; i++)
-        if (host_idx[i] < 0 || host_idx[i] >= m->n_groups) {
-            set_error("wmx_mix_reset_speakers: ring %d is outside the mixer's %d", (int)host_idx[i], m->n_groups);
-            return WMX_EINVAL;
-        }
+    if (idx_check(host_idx, n, m->n_groups, "wmx_mix_reset_speakers: ring", "mixer")) return WMX_EINVAL;
     const bool fresh = !m->d_env;
     const int rcs = speakers_state(m);
     if (rcs || fresh) return rcs;  // just made: zero already
@@ -1241,14 +1175,8 @@ int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *str
         return 0;
     }
     if (n == 0) return 0;
-    WMX_HIP(hipStreamSynchronize(s));  // a reset in flight may still read the list that is rewritten here
-    if ((size_t)n > m->reset_cap) {
-        if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
-        m->d_reset_idx = nullptr, m->reset_cap = 0;
-        WMX_HIP(hipMalloc(&m->d_reset_idx, (size_t)n * sizeof(int32_t)));
-        m->reset_cap = (size_t)n;
-    }
-    WMX_HIP(hipMemcpy(m->d_reset_idx, host_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    const int rcu = upload_idx(m->d_reset_idx, m->reset_cap, host_idx, n, s);
+    if (rcu) return rcu;
     hipLaunchKernelGGL((fill_rows_idx<uint32_t>), dim3(stream_grid((size_t)n * 64, 64)), dim3(64), 0, s, m->d_env, (const uint32_t *)nullptr, 1,
                        (const int32_t *)m->d_reset_idx, n);
     WMX_LAUNCH_CHECK();
@@ -1359,20 +1287,24 @@ WMix_Point wmix_load_data(WMix_Struct_Head *wmix, WMix_Point src, uint32_t srcU8
     uint32_t h = head.U8 ? (uint32_t)(head.U8 - wmix->start.U8) : UINT32_MAX, t = *tick;
     // The reference touches ring bytes [head, head + n_out*2) only, while other task threads and the play thread work on
     // the same ring without a lock (src/wmix.c:1347-1352, 1678-1702).  So does this adapter: the span the call will write
-    // is worked out first (same cursor rule and schedule as wmx_mix_load), only that span goes up, and only it comes
-    // back.  Between the two copies the adapter is a read-modify-write like the reference's per-sample `*pHead = ...`,
-    // just longer: it gives no more atomicity than the reference does, and no less outside the span.
-    uint32_t span_off = h;
-    if (span_off == UINT32_MAX || t < m->tick) {  // src/wmix.c:1666-1673, as in wmx_mix_load
-        span_off = m->head_off + m->play_correct;
-        if (span_off >= m->ring_bytes) span_off = 0;
-    }
+    // is worked out first (the cursor rule, then the schedule, which wmx_mix_load finds in the handle's cache afterwards), only
+    // that span goes up, and only it comes back.  Between the two copies the adapter is a read-modify-write like the reference's
+    // per-sample `*pHead = ...`, just longer: it gives no more atomicity than the reference does, and no less outside the span.
+    uint32_t span_off = h, span_tick = t;
+    mix_cursor_begin(cursor_state(m), span_off, span_tick);
     if (span_off >= size || (span_off & 1)) return pHead;
-    if (!load_schedule(m->chn, m->freq, srcU8Len, freq, channels, sample, m->sch) || m->sch.size() > size / 2) {
-        fprintf(stderr, "wmix_amd: wmix_load_data: unsupported rate ratio or more than one ring of output\n");
+    SchedCache::Entry *ent = nullptr;
+    int rcb;
+    {
+        DeviceScope on(m->device);  // the schedule goes where wmx_mix_load reads it
+        rcb = on.err == hipSuccess ? load_sched(m, "wmix_load_data", srcU8Len, freq, channels, sample, &ent)
+                                   : hip_fail(on.err, "hipSetDevice", __FILE__, __LINE__);
+    }
+    if (rcb) {
+        fprintf(stderr, "wmix_amd: %s\n", rcb == WMX_EINVAL ? "wmix_load_data: unsupported rate ratio or more than one ring of output" : wmx_last_error());
         return pHead;
     }
-    const uint32_t span = (uint32_t)m->sch.size() * 2;
+    const uint32_t span = (uint32_t)ent->n * 2;
     const uint32_t first = span < size - span_off ? span : size - span_off, second = span - first;  // split at the wrap
     // the up-sampling fill interpolates towards the frame behind the last one (src/wmix.c:1857,1914); the copy and
     // down-sampling branches never read ahead, and neither does the adapter

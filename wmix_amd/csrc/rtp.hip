@@ -47,6 +47,20 @@ __device__ __forceinline__ uint32_t enc_law(int law, int v) {
     return law == WMX_LAW_A ? enc_alaw(v) : enc_ulaw(v);
 }
 
+// The first two words of rtp_send's network-order header (src/rtp.c:35-70) as a little-endian machine stores them: v = 2, p = x = 0,
+// cc = 0 | m = 1, pt | seq, timestamp big endian on the wire.  The third word, ssrc, is 0 (src/wmixTask.c:1058).
+__device__ __forceinline__ uint2 rtp_header_words(uint32_t pt, uint32_t sq, uint32_t tt) {
+    return make_uint2((2u << 6) | ((0x80u | pt) << 8) | ((sq >> 8) << 16) | ((sq & 0xFFu) << 24),
+                      (tt >> 24) | (((tt >> 16) & 0xFFu) << 8) | (((tt >> 8) & 0xFFu) << 16) | ((tt & 0xFFu) << 24));
+}
+
+// the four codes of one payload word decoded to four samples, the first in the low half of x
+template <class Dec>
+__device__ __forceinline__ uint2 dec4(uint32_t w, const Dec &dec) {
+    return make_uint2(((uint32_t)dec(w & 0xFF) & 0xFFFFu) | ((uint32_t)dec((w >> 8) & 0xFF) << 16),
+                      ((uint32_t)dec((w >> 16) & 0xFF) & 0xFFFFu) | ((uint32_t)dec(w >> 24) << 16));
+}
+
 template <int LAW>
 __global__ void rtp_egress_kernel(const int16_t *__restrict__ pcm, long pcm_stride, const int32_t *__restrict__ idx, int n_codes,
                                   int codes_per_ts, uint32_t *seq, uint32_t *ts, uint8_t *packets, long packet_stride, int n_streams,
@@ -107,10 +121,8 @@ __global__ __launch_bounds__(256) void rtp_ingest_wide_kernel(const uint8_t *__r
         const bool g711 = pt == 8 || pt == 0;  // src/rtp.c:88-95 (AAC-tagged packets: not G.711, size 0 here)
         if (g711) {
             const uint32_t w = *reinterpret_cast<const uint32_t *>(pkt + kRtpHeader + 4 * c);
-            uint2 o;  // G711a2PCM whatever the pt
-            o.x = ((uint32_t)dec_alaw(w & 0xFF) & 0xFFFFu) | ((uint32_t)dec_alaw((w >> 8) & 0xFF) << 16);
-            o.y = ((uint32_t)dec_alaw((w >> 16) & 0xFF) & 0xFFFFu) | ((uint32_t)dec_alaw(w >> 24) << 16);
-            *reinterpret_cast<uint2 *>(pcm + (size_t)stream * pcm_stride + 4 * c) = o;
+            // G711a2PCM whatever the pt
+            *reinterpret_cast<uint2 *>(pcm + (size_t)stream * pcm_stride + 4 * c) = dec4(w, [](uint32_t code) { return dec_alaw(code); });
         }
         if (c == 0) {
             if (pcm_bytes) pcm_bytes[stream] = g711 ? (uint32_t)kRtpG711Payload * 2 : 0u;
@@ -140,60 +152,24 @@ __global__ __launch_bounds__(256) void rtp_egress_wide_kernel(const int16_t *__r
             const uint32_t tt = ts[stream] + (uint32_t)codes_per_ts;  // timestamp += ret / chn, before the send
             const uint32_t sq = seq[stream] & 0xFFFFu;
             uint32_t *hd = reinterpret_cast<uint32_t *>(pkt);
-            // v = 2, p = x = 0, cc = 0 | m = 1, pt | seq, timestamp big endian on the wire | ssrc = 0 (src/wmixTask.c:1058)
-            hd[0] = (2u << 6) | ((0x80u | (uint32_t)pt) << 8) | ((sq >> 8) << 16) | ((sq & 0xFFu) << 24);
-            hd[1] = (tt >> 24) | (((tt >> 16) & 0xFFu) << 8) | (((tt >> 8) & 0xFFu) << 16) | ((tt & 0xFFu) << 24);
-            hd[2] = 0;
+            const uint2 hw = rtp_header_words((uint32_t)pt, sq, tt);
+            hd[0] = hw.x, hd[1] = hw.y, hd[2] = 0;
             ts[stream] = tt;
             seq[stream] = (sq + 1) & 0xFFFFu;  // rtpHeader.seq++ after the send (uint16 wrap)
         }
     }
 }
 
-// Ingest for legs that deliver 0 .. max_packets datagrams in a tick (wmx_rtp_ingest_legs): rtp_ingest_wide_kernel's four codes per
-// lane (WIDE: rows on 4 / 8-byte boundaries) or one code per lane, dealt over (leg, slot, piece).  A slot where nothing arrived
-// (recv_bytes <= 0: its datagram row is not read) or whose payload type is not G.711 made no call: len 0 and a zeroed PCM row.
-template <bool WIDE>
-__global__ __launch_bounds__(256) void rtp_ingest_legs_kernel(const uint8_t *__restrict__ packets, long leg_stride, long packet_stride,
-                                                               const int32_t *__restrict__ recv_bytes, int16_t *pcm, long source_stride,
-                                                               long pcm_packet_stride, uint32_t *len, uint16_t *seq_raw, int max_packets,
-                                                               int n_legs) {
-    constexpr int kPieces = WIDE ? kRtpWords : kRtpG711Payload;
-    const size_t total = (size_t)n_legs * max_packets * kPieces;
-    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t row = t / kPieces;  // leg * max_packets + slot
-        const int c = (int)(t - row * kPieces);
-        const size_t leg = row / (size_t)max_packets, k = row - leg * (size_t)max_packets;
-        const uint8_t *pkt = packets + leg * leg_stride + k * packet_stride;
-        int16_t *dst = pcm + leg * source_stride + k * pcm_packet_stride;
-        const bool there = recv_bytes[row] > 0;
-        const int pt = there ? pkt[1] & 0x7F : -1;
-        const bool g711 = pt == 8 || pt == 0;  // src/rtp.c:88-95
-        if (WIDE) {
-            uint2 o = make_uint2(0u, 0u);
-            if (g711) {
-                const uint32_t w = *reinterpret_cast<const uint32_t *>(pkt + kRtpHeader + 4 * c);
-                o.x = ((uint32_t)dec_alaw(w & 0xFF) & 0xFFFFu) | ((uint32_t)dec_alaw((w >> 8) & 0xFF) << 16);  // G711a2PCM whatever the pt
-                o.y = ((uint32_t)dec_alaw((w >> 16) & 0xFF) & 0xFFFFu) | ((uint32_t)dec_alaw(w >> 24) << 16);
-            }
-            *reinterpret_cast<uint2 *>(dst + 4 * c) = o;
-        } else {
-            dst[c] = g711 ? (int16_t)dec_alaw(pkt[kRtpHeader + c]) : (int16_t)0;
-        }
-        if (c == 0) {
-            len[row] = g711 ? (uint32_t)kRtpG711Payload * 2 : 0u;
-            if (seq_raw) seq_raw[row] = there ? (uint16_t)(pkt[2] | (pkt[3] << 8)) : (uint16_t)0;  // as stored: rtp_recv does not ntohs
-        }
-    }
-}
-
-// The same ingest with the codec rule per leg (wmx_rtp_ingest_legs_codecs, leg_codec.h): which slots make a call and with which law
-// their payload is decoded is the leg's in_codec's to say.  PER_LEG false: every leg is WMX_CODEC_REFERENCE (in_codec is not read) --
-// rtp_ingest_legs_kernel plus the count.  A row's lanes all decide alike from the row's header; neighbouring rows, and so the lanes of
-// one wave, may decode with different laws: both decoders are evaluated and one is selected.  refused[leg] counts the leg's slots
-// where something arrived that made no call: one atomic add by the row's first lane -- up to max_packets lanes add to one word, and no
-// lane of the launch reads it.
-template <bool WIDE, bool PER_LEG>
+// Ingest for legs that deliver 0 .. max_packets datagrams in a tick (wmx_rtp_ingest_legs, wmx_rtp_ingest_legs_codecs):
+// rtp_ingest_wide_kernel's four codes per lane (WIDE: rows on 4 / 8-byte boundaries) or one code per lane, dealt over (leg, slot,
+// piece).  A slot where nothing arrived (recv_bytes <= 0: its datagram row is not read) or that the codec rule (leg_codec.h) refuses
+// made no call: len 0 and a zeroed PCM row.  Which slots make a call and with which law their payload is decoded is the leg's in_codec's
+// to say.  PER_LEG false: every leg is WMX_CODEC_REFERENCE (in_codec is not read) -- a G.711 payload type makes a call, decoded as
+// A-law whatever the pt (src/rtp.c:88-95).  A row's lanes all decide alike from the row's header; neighbouring rows, and so the lanes
+// of one wave, may decode with different laws: both decoders are evaluated and one is selected.  COUNT: refused[leg] counts the leg's
+// slots where something arrived that made no call: one atomic add by the row's first lane -- up to max_packets lanes add to one word,
+// and no lane of the launch reads it.  COUNT false (no handle, wmx_rtp_ingest_legs): refused is not touched.
+template <bool WIDE, bool PER_LEG, bool COUNT>
 __global__ __launch_bounds__(256) void rtp_ingest_legs_codecs_kernel(const uint8_t *__restrict__ packets, long leg_stride, long packet_stride,
                                                                       const int32_t *__restrict__ recv_bytes, int16_t *pcm, long source_stride,
                                                                       long pcm_packet_stride, uint32_t *len, uint16_t *seq_raw, int max_packets,
@@ -213,11 +189,7 @@ __global__ __launch_bounds__(256) void rtp_ingest_legs_codecs_kernel(const uint8
         auto dec = [=](uint32_t code) -> uint32_t { return (uint32_t)(PER_LEG && ulaw ? dec_ulaw(code) : dec_alaw(code)); };
         if (WIDE) {
             uint2 o = make_uint2(0u, 0u);
-            if (call) {
-                const uint32_t w = *reinterpret_cast<const uint32_t *>(pkt + kRtpHeader + 4 * c);
-                o.x = (dec(w & 0xFF) & 0xFFFFu) | (dec((w >> 8) & 0xFF) << 16);
-                o.y = (dec((w >> 16) & 0xFF) & 0xFFFFu) | (dec(w >> 24) << 16);
-            }
+            if (call) o = dec4(*reinterpret_cast<const uint32_t *>(pkt + kRtpHeader + 4 * c), dec);
             *reinterpret_cast<uint2 *>(dst + 4 * c) = o;
         } else {
             dst[c] = call ? (int16_t)dec(pkt[kRtpHeader + c]) : (int16_t)0;
@@ -225,7 +197,7 @@ __global__ __launch_bounds__(256) void rtp_ingest_legs_codecs_kernel(const uint8
         if (c == 0) {
             len[row] = call ? (uint32_t)kRtpG711Payload * 2 : 0u;
             if (seq_raw) seq_raw[row] = there ? (uint16_t)(pkt[2] | (pkt[3] << 8)) : (uint16_t)0;  // as stored: rtp_recv does not ntohs
-            if (what & kLegCodecRefused) atomicAdd(refused + leg, 1u);
+            if (COUNT && (what & kLegCodecRefused)) atomicAdd(refused + leg, 1u);
         }
     }
 }
@@ -279,9 +251,8 @@ __global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restri
         if (j == 0) {
             const uint32_t tt = ts[ring] + (uint32_t)kRtpG711Payload;  // timestamp += ret / chn, before the send
             const uint32_t sq = seq[ring] & 0xFFFFu;
-            // v = 2, p = x = 0, cc = 0 | m = 1, pt | seq, timestamp big endian on the wire | ssrc = 0 (src/wmixTask.c:1058)
-            const uint32_t h0 = (2u << 6) | ((0x80u | (uint32_t)pt) << 8) | ((sq >> 8) << 16) | ((sq & 0xFFu) << 24);
-            const uint32_t h1 = (tt >> 24) | (((tt >> 16) & 0xFFu) << 8) | (((tt >> 8) & 0xFFu) << 16) | ((tt & 0xFFu) << 24);
+            const uint2 hw = rtp_header_words((uint32_t)pt, sq, tt);
+            const uint32_t h0 = hw.x, h1 = hw.y;
             if (WIDE_OUT) {
                 uint32_t *hd = reinterpret_cast<uint32_t *>(pkt);
                 hd[0] = h0, hd[1] = h1, hd[2] = 0;
@@ -453,25 +424,44 @@ int wmx_rtp_ingest(int n_streams, const uint8_t *d_packets, long packet_stride, 
     return 0;
 }
 
-int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride, const int32_t *d_recv_bytes,
-                        int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len, uint16_t *d_seq_raw, void *stream) {
+// what wmx_rtp_ingest_legs and wmx_rtp_ingest_legs_codecs share: the argument check, and the launch (d_refused NULL: no count;
+// d_in_codec NULL: every leg is WMX_CODEC_REFERENCE)
+static int ingest_legs_check(const char *who, int n_legs, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride,
+                             const int32_t *d_recv_bytes, const int16_t *d_pcm, long source_stride, long pcm_packet_stride,
+                             const uint32_t *d_len) {
     if (n_legs < 0 || max_packets < 1 || max_packets > 4 || !d_packets || !d_recv_bytes || !d_pcm || !d_len ||
         packet_stride < kRtpHeader + kRtpG711Payload || pcm_packet_stride < kRtpG711Payload ||
         (n_legs > 1 && (leg_stride < packet_stride * max_packets || source_stride < pcm_packet_stride * max_packets))) {
-        set_error("wmx_rtp_ingest_legs: bad arguments");
+        set_error("%s: bad arguments", who);
         return WMX_EINVAL;
     }
+    return 0;
+}
+
+static int ingest_legs_launch(int n_legs, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride,
+                              const int32_t *d_recv_bytes, int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len,
+                              uint16_t *d_seq_raw, const uint8_t *d_in_codec, uint32_t *d_refused, void *stream) {
     if (n_legs == 0) return 0;
     const size_t rows = (size_t)n_legs * max_packets;
-    if (aligned_to(d_packets, packet_stride, 4) && leg_stride % 4 == 0 && aligned_to(d_pcm, pcm_packet_stride * 2, 8) && (source_stride * 2) % 8 == 0)
-        hipLaunchKernelGGL((rtp_ingest_legs_kernel<true>), dim3(wmx::stream_grid(rows * kRtpWords, 256)), dim3(256), 0, as_stream(stream), d_packets,
-                           leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw, max_packets, n_legs);
-    else
-        hipLaunchKernelGGL((rtp_ingest_legs_kernel<false>), dim3(wmx::stream_grid(rows * kRtpG711Payload, 256)), dim3(256), 0, as_stream(stream),
-                           d_packets, leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw,
-                           max_packets, n_legs);
+    const bool wide = aligned_to(d_packets, packet_stride, 4) && leg_stride % 4 == 0 && aligned_to(d_pcm, pcm_packet_stride * 2, 8) &&
+                      (source_stride * 2) % 8 == 0;
+    auto kernel = !d_refused   ? (wide ? rtp_ingest_legs_codecs_kernel<true, false, false> : rtp_ingest_legs_codecs_kernel<false, false, false>)
+                  : d_in_codec ? (wide ? rtp_ingest_legs_codecs_kernel<true, true, true> : rtp_ingest_legs_codecs_kernel<false, true, true>)
+                               : (wide ? rtp_ingest_legs_codecs_kernel<true, false, true> : rtp_ingest_legs_codecs_kernel<false, false, true>);
+    hipLaunchKernelGGL(kernel, dim3(wmx::stream_grid(rows * (wide ? kRtpWords : kRtpG711Payload), 256)), dim3(256), 0, as_stream(stream), d_packets,
+                       leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw, max_packets, n_legs,
+                       d_in_codec, d_refused);
     WMX_LAUNCH_CHECK();
     return 0;
+}
+
+int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, long leg_stride, long packet_stride, const int32_t *d_recv_bytes,
+                        int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len, uint16_t *d_seq_raw, void *stream) {
+    const int rc = ingest_legs_check("wmx_rtp_ingest_legs", n_legs, max_packets, d_packets, leg_stride, packet_stride, d_recv_bytes, d_pcm,
+                                     source_stride, pcm_packet_stride, d_len);
+    return rc ? rc
+              : ingest_legs_launch(n_legs, max_packets, d_packets, leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride,
+                                   d_len, d_seq_raw, nullptr, nullptr, stream);
 }
 
 // Play and send in one launch: wmx_mix_drain(320 bytes) followed by wmx_rtp_egress(1, 8000 -> 1, 8000), byte for byte, for a mixer of
@@ -522,11 +512,7 @@ int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet
 int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    for (int i = 0; host_idx && i < n; i++)
-        if (host_idx[i] < 0 || host_idx[i] >= h->n_streams) {
-            set_error("wmx_rtp_reset_streams: sender %d is outside the handle's %d", (int)host_idx[i], h->n_streams);
-            return WMX_EINVAL;
-        }
+    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_streams: sender", "handle")) return WMX_EINVAL;
     hipStream_t s = as_stream(stream);
     if (!host_idx) {
         WMX_HIP(hipMemsetAsync(h->d_seq, 0, sizeof(uint32_t) * h->n_streams, s));
@@ -544,16 +530,10 @@ int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stre
 // the state, all zero (unsynced, counters 0), from the first call that needs it on
 static int seq_state(wmx_rtp *h) {
     if (h->d_sq) return 0;
-    const size_t bytes = (size_t)kSeqWords * h->n_streams * sizeof(uint32_t);
-    uint32_t *p = nullptr;
-    WMX_HIP(hipMalloc(&p, bytes));
-    hipError_t e = hipMemset(p, 0, bytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return hip_fail(e, "hipMemset(sequence state)", __FILE__, __LINE__);
-    }
-    h->d_sq = p;
+    void *p = nullptr;
+    const int rc = zeroed_block(&p, (size_t)kSeqWords * h->n_streams * sizeof(uint32_t), "hipMemset(sequence state)");
+    if (rc) return rc;
+    h->d_sq = static_cast<uint32_t *>(p);
     return 0;
 }
 
@@ -579,11 +559,7 @@ int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16
 int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    for (int i = 0; host_idx && i < n; i++)
-        if (host_idx[i] < 0 || host_idx[i] >= h->n_streams) {
-            set_error("wmx_rtp_reset_sequence: leg %d is outside the handle's %d", (int)host_idx[i], h->n_streams);
-            return WMX_EINVAL;
-        }
+    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_sequence: leg", "handle")) return WMX_EINVAL;
     hipStream_t s = as_stream(stream);
     const size_t pitch = (size_t)h->n_streams * sizeof(uint32_t);
     if (h->d_refused) {  // the receive side's other counter (leg_codec.h); the leg's codec stays
@@ -628,18 +604,12 @@ int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_
 // the state -- refused 0, in_codec REFERENCE, out_law the law of create -- from the first call that needs it on
 static int codec_state(wmx_rtp *h) {
     if (h->d_refused) return 0;
-    const size_t n = (size_t)h->n_streams, bytes = n * sizeof(uint32_t) + 2 * n;
-    uint8_t *p = nullptr;
-    WMX_HIP(hipMalloc(&p, bytes));
-    hipError_t e = hipMemset(p, 0, n * sizeof(uint32_t) + n);
-    if (e == hipSuccess) e = hipMemset(p + n * sizeof(uint32_t) + n, h->law, n);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return hip_fail(e, "hipMemset(codec state)", __FILE__, __LINE__);
-    }
-    h->d_refused = reinterpret_cast<uint32_t *>(p);
-    h->d_in_codec = p + n * sizeof(uint32_t);
+    const size_t n = (size_t)h->n_streams, law_off = n * sizeof(uint32_t) + n;
+    void *p = nullptr;
+    const int rc = zeroed_block(&p, law_off + n, "hipMemset(codec state)", law_off, h->law, n);
+    if (rc) return rc;
+    h->d_refused = static_cast<uint32_t *>(p);
+    h->d_in_codec = static_cast<uint8_t *>(p) + n * sizeof(uint32_t);
     h->d_out_law = h->d_in_codec + n;
     return 0;
 }
@@ -653,11 +623,7 @@ int wmx_rtp_set_codecs(wmx_rtp *h, const int32_t *host_idx, int n, int in_codec,
                   out_law);
         return WMX_EINVAL;
     }
-    for (int i = 0; host_idx && i < n; i++)
-        if (host_idx[i] < 0 || host_idx[i] >= h->n_streams) {
-            set_error("wmx_rtp_set_codecs: stream %d is outside the handle's %d", (int)host_idx[i], h->n_streams);
-            return WMX_EINVAL;
-        }
+    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_set_codecs: stream", "handle")) return WMX_EINVAL;
     const int rcs = codec_state(h);
     if (rcs) return rcs;
     hipStream_t s = as_stream(stream);
@@ -702,26 +668,13 @@ int wmx_rtp_ingest_legs_codecs(wmx_rtp *h, int max_packets, const uint8_t *d_pac
                                const int32_t *d_recv_bytes, int16_t *d_pcm, long source_stride, long pcm_packet_stride, uint32_t *d_len,
                                uint16_t *d_seq_raw, void *stream) {
     WMX_ON_DEVICE(h);
-    const int n_legs = h ? h->n_streams : 0;
-    if (!h || max_packets < 1 || max_packets > 4 || !d_packets || !d_recv_bytes || !d_pcm || !d_len ||
-        packet_stride < kRtpHeader + kRtpG711Payload || pcm_packet_stride < kRtpG711Payload ||
-        (n_legs > 1 && (leg_stride < packet_stride * max_packets || source_stride < pcm_packet_stride * max_packets))) {
-        set_error("wmx_rtp_ingest_legs_codecs: bad arguments");
-        return WMX_EINVAL;
-    }
+    const int rcc = ingest_legs_check("wmx_rtp_ingest_legs_codecs", h ? h->n_streams : -1, max_packets, d_packets, leg_stride, packet_stride,
+                                      d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len);
+    if (rcc) return rcc;
     const int rcs = codec_state(h);
     if (rcs) return rcs;
-    const size_t rows = (size_t)n_legs * max_packets;
-    const bool wide = aligned_to(d_packets, packet_stride, 4) && leg_stride % 4 == 0 && aligned_to(d_pcm, pcm_packet_stride * 2, 8) &&
-                      (source_stride * 2) % 8 == 0;
-    const bool per_leg = !h->codecs_default;
-    auto kernel = wide ? (per_leg ? rtp_ingest_legs_codecs_kernel<true, true> : rtp_ingest_legs_codecs_kernel<true, false>)
-                       : (per_leg ? rtp_ingest_legs_codecs_kernel<false, true> : rtp_ingest_legs_codecs_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(wmx::stream_grid(rows * (wide ? kRtpWords : kRtpG711Payload), 256)), dim3(256), 0, as_stream(stream), d_packets,
-                       leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len, d_seq_raw, max_packets, n_legs,
-                       h->d_in_codec, h->d_refused);
-    WMX_LAUNCH_CHECK();
-    return 0;
+    return ingest_legs_launch(h->n_streams, max_packets, d_packets, leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride,
+                              pcm_packet_stride, d_len, d_seq_raw, h->codecs_default ? nullptr : h->d_in_codec, h->d_refused, stream);
 }
 
 int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timestamp) {

@@ -69,6 +69,48 @@ inline unsigned stream_grid(size_t work_items, unsigned block) {
     return (unsigned)(need < cap ? need : cap);
 }
 
+// ---- what the entry points that take a list of indices share (mix.hip, rtp.hip, conf.hip)
+// Every host_idx[i] of the n (NULL: no list, nothing to check) lies inside the handle's `count`; otherwise WMX_EINVAL and the error
+// text "<what> <index> is outside the <whose>'s <count>".
+static inline int idx_check(const int32_t *host_idx, int n, int count, const char *what, const char *whose) {
+    for (int i = 0; host_idx && i < n; i++)
+        if (host_idx[i] < 0 || host_idx[i] >= count) {
+            set_error("%s %d is outside the %s's %d", what, (int)host_idx[i], whose, count);
+            return WMX_EINVAL;
+        }
+    return 0;
+}
+
+// A device block of state made by the first call that needs it: zero, except fill_bytes at fill_off that hold the byte `fill`;
+// complete on the device when this returns.
+static inline int zeroed_block(void **out, size_t bytes, const char *what, size_t fill_off = 0, int fill = 0, size_t fill_bytes = 0) {
+    void *p = nullptr;
+    WMX_HIP(hipMalloc(&p, bytes));
+    hipError_t e = hipMemset(p, 0, bytes);
+    if (e == hipSuccess && fill_bytes) e = hipMemset(static_cast<uint8_t *>(p) + fill_off, fill, fill_bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, what, __FILE__, __LINE__);
+    }
+    *out = p;
+    return 0;
+}
+
+// The n indices of a host list in a device buffer the handle keeps and grows: a launch in flight on `s` may still read the list that
+// is rewritten here, so the stream is waited for first.
+static inline int upload_idx(int32_t *&d_idx, size_t &cap, const int32_t *host_idx, int n, hipStream_t s) {
+    WMX_HIP(hipStreamSynchronize(s));
+    if ((size_t)n > cap) {
+        if (d_idx) (void)hipFree(d_idx);
+        d_idx = nullptr, cap = 0;
+        WMX_HIP(hipMalloc(&d_idx, (size_t)n * sizeof(int32_t)));
+        cap = (size_t)n;
+    }
+    WMX_HIP(hipMemcpy(d_idx, host_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
 // True once the process has begun to exit (an atexit handler registered when the library is loaded, i.e. after the HIP
 // runtime's own handlers, so it runs before them; also the library's destructor).  Thread-local owners of device memory
 // free it normally when their thread ends and leave it alone only then: the HIP runtime may already be gone, and a
