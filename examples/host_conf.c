@@ -1,7 +1,7 @@
 /* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
- *             [--sequence G] [--audio-only] [--ulaw-every N]
+ *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -15,6 +15,8 @@
  * become silence) and the JSON line also carries the five counters summed over the legs.  --audio-only: every datagram of the script is
  * PCMA (v == 0 too), so the script has no gap of its own: a datagram of payload type 96 consumes a sequence number and brings no audio,
  * which sequencing treats as a lost packet.
+ * --conceal (only meaningful with --sequence G): the silence of a gap is synthesised from the leg's own history (wmx_conf_conceal) and
+ * the JSON line also carries the packets concealed, summed over the legs.
  * --ulaw-every N: every N-th leg (N - 1, 2 N - 1, ...) negotiated PCMU: its G.711 datagrams carry payload type 0, it is decoded as
  * mu-law and answered in mu-law (wmx_conf_set_codecs: WMX_CODEC_PCMU, WMX_LAW_U); the other legs stay at the default.  The JSON line
  * then also carries the number of such legs and the refused counters summed over the legs (wmx_conf_export_codecs).
@@ -102,7 +104,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) 
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
-                        " [--sequence G] [--audio-only] [--ulaw-every N]\n";
+                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -110,7 +112,7 @@ int main(int argc, char **argv) {
     const int G = atoi(argv[2]), T = atoi(argv[3]);
     const char *sizes = NULL, *speakers = NULL, *platform = "alsa";
     unsigned long seed = 0;
-    int slots = 3, have_seed = 0, max_gap = -1; /* max_gap -1: sequencing off */
+    int slots = 3, have_seed = 0, max_gap = -1, conceal = 0; /* max_gap -1: sequencing off */
     long correct = -1; /* -1: the library's default = platform/alsa */
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
@@ -124,6 +126,8 @@ int main(int argc, char **argv) {
         } else if (!strcmp(argv[i], "--sequence") && i + 1 < argc) {
             max_gap = atoi(argv[++i]);
             if (max_gap < 0) max_gap = WMX_MIX_MAX_LEG_PACKETS; /* not a gap: the library says so */
+        } else if (!strcmp(argv[i], "--conceal")) {
+            conceal = 1;
         } else if (!strcmp(argv[i], "--audio-only")) {
             audio_only = 1;
         } else if (!strcmp(argv[i], "--ulaw-every") && i + 1 < argc) {
@@ -169,6 +173,7 @@ int main(int argc, char **argv) {
     WMX_OK(wmx_conf_set_conferences(h, n_conf, conf_off, conf_members, NULL));
     if (speakers) WMX_OK(wmx_conf_speakers(h, max_speakers, (uint32_t)floor_level, shift));
     if (max_gap >= 0) WMX_OK(wmx_conf_sequence(h, 1, max_gap));
+    if (conceal) WMX_OK(wmx_conf_conceal(h, 1));
     int n_ulaw = 0;
     for (int g = 0; g < G; g++) {
         const int32_t leg = g;
@@ -220,6 +225,14 @@ int main(int argc, char **argv) {
             for (int g = 0; g < G; g++) seq_sum[c] += cnt[(size_t)c * G + g];
         free(cnt);
     }
+    unsigned long n_concealed = 0;
+    if (conceal) {
+        uint32_t *cnt = calloc((size_t)G, sizeof(uint32_t));
+        if (!cnt) return 2;
+        WMX_OK(wmx_conf_export_conceal(h, cnt, NULL));
+        for (int g = 0; g < G; g++) n_concealed += cnt[g];
+        free(cnt);
+    }
     unsigned long n_refused = 0;
     if (ulaw_every > 0) {
         uint32_t *refused = calloc((size_t)G, sizeof(uint32_t));
@@ -240,6 +253,7 @@ int main(int argc, char **argv) {
     if (max_gap >= 0)
         printf("\"sequence\": %d, \"lost\": %lu, \"late\": %lu, \"dup\": %lu, \"resync\": %lu, \"overflow\": %lu, ", max_gap, seq_sum[0], seq_sum[1],
                seq_sum[2], seq_sum[3], seq_sum[4]);
+    if (conceal) printf("\"conceal\": 1, \"concealed\": %lu, ", n_concealed);
     if (ulaw_every > 0) printf("\"ulaw_every\": %d, \"ulaw_legs\": %d, \"refused\": %lu, ", ulaw_every, n_ulaw, n_refused);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",

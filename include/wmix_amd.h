@@ -631,8 +631,8 @@ int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timest
  * d_calls[r] receives the list (WMX_RTP_CALLS_*): for wmx_mix_load_minus_legs_calls; every discarded slot gets d_len = 0, so talker
  * selection behind this stage does not hear late packets or duplicates.  max_gap 0 .. 3.  No atomics, no host synchronisation, no
  * upload, no allocation after the first call (wmx_rtp_reset_sequence counts as one).
- * OUT OF SCOPE: placing a late packet into its still-unplayed gap; SSRC changes; timestamp-based placement; concealment other than
- * silence.
+ * OUT OF SCOPE: placing a late packet into its still-unplayed gap; SSRC changes; timestamp-based placement.  (What a silence call
+ * sounds like is wmx_rtp_conceal_legs' business, below.)
  * WMX_EINVAL, nothing launched, state unchanged: a NULL h, d_seq_raw, d_len or d_calls, max_packets outside 1 .. 4, max_gap outside
  * 0 .. 3.
  * wmx_rtp_reset_sequence: unsynced and counters 0 for the n legs host_idx lists (NULL = all), on `stream`: a new call may start at any
@@ -648,6 +648,42 @@ int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16
 int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
 int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup,
                             uint32_t *resync, uint32_t *overflow, void *stream);
+/* Conceal lost packets from each leg's own history, between wmx_rtp_sequence_legs (and the selection) and the load
+ * (wmix_amd/csrc/leg_plc.h holds the rule).  The sequence rule makes a gap of 1 .. 3 lost packets that many WCT_SILENCE calls: the cursor
+ * stays right, and every other leg of the conference hears 20 .. 60 ms of hard zero cut into speech, with a click at both edges.  The
+ * reference has no counterpart.  Here the handle keeps, per leg (its n_streams) and ON THE DEVICE, hist[320] int16 -- the last 320
+ * samples the leg emitted, newest at index 319, all 0 when fresh -- and a counter `concealed`, and one launch rewrites every leg's
+ * calls of the tick into rows that are all data.  Integer arithmetic; >> is an arithmetic shift on int32.
+ *   Input per leg: its PCM rows (slot k of leg r at d_pcm + r*source_stride + k*pcm_packet_stride, int16 elements), d_len (n_legs x
+ *   max_packets) and the call list d_calls[r] exactly as wmx_rtp_sequence_legs leaves them (WMX_RTP_CALLS_*), walked in list order.  A
+ *   data call that names a slot k >= max_packets, or a slot with d_len != 320, is a silence call, as the load treats it.
+ *   A RUN is a maximal sequence of consecutive silence calls in the list.  At the start of a run: h0 = hist is frozen; q[i] = h0[i] >> 4
+ *   (|q| <= 2048); for every lag L in 40 .. 120, c(L) = sum over i = 160 .. 319 of q[i] * q[i - L] (i - L >= 40; |c| <= 160 * 2^22 <
+ *   2^31); L* = the smallest L with the largest c(L).  No normalisation, no threshold: an all-zero history gives L* = 40 and zeros out.
+ *   SYNTHESIS: sample i of the n-th silence call of the run (n = 1, 2, ..) has k = (n - 1) * 160 + i, s = h0[320 - L* + (k mod L*)],
+ *   g = max(0, 32768 - 68 * k), y = (s * g) >> 15.  concealed += 1 per synthesised packet.
+ *   BLEND: a data call that directly follows a run of n_s silence calls in the same list, x its row: for i in 0 .. 31, cont = the
+ *   synthesis formula at k = n_s * 160 + i and y[i] = (x[i] * i + cont * (32 - i)) >> 5; for i in 32 .. 159, y[i] = x[i].  A data call
+ *   not preceded by silence in the list -- the first call, a data call after another, a resync -- is emitted unchanged.
+ *   HISTORY: after each call its 160 emitted samples are appended to hist, keeping the last 320.  The history follows the list, not the
+ *   load's lap rule (a call the load later drops has still been heard by the history), and mute does not enter the rule: a muted leg's
+ *   state advances, and the load writes zeros for it as before.
+ * Out: d_pcm_out, n_legs x 4 x 160 int16, the emitted rows in call order (rows j >= count are not written), and d_len_out, n_legs x
+ * 4 uint32: 320 for j < count, else 0 -- every call has become a data call, so wmx_mix_load_minus_legs with max_packets = 4,
+ * source_stride 640 and packet_stride 160 consumes them unchanged.  A leg with no calls has unchanged state and a d_len_out row of
+ * zeros.  d_pcm, d_len and d_calls are only read.  One launch (one wave per leg); no atomics, no host synchronisation, no upload, no
+ * allocation after the first call (wmx_rtp_reset_conceal counts as one).
+ * STILL OUT OF SCOPE: placing a late packet into its unplayed gap, timestamp-based placement, comfort noise.
+ * WMX_EINVAL, nothing launched, state unchanged: a NULL pointer, max_packets outside 1 .. 4, rows that overlap (pcm_packet_stride <
+ * 160, a source_stride shorter than a leg's max_packets rows, repaired rows that overlap the rows they are made from).
+ * wmx_rtp_reset_conceal: hist = 0 and concealed = 0 for the n legs host_idx lists (NULL = all), on `stream`.  A bad index: WMX_EINVAL,
+ * nothing reset.
+ * wmx_rtp_export_conceal: hist (n_streams x 320 int16) and concealed (n_streams uint32), either pointer NULL, as the work queued on
+ * `stream` leaves them; blocking. */
+int wmx_rtp_conceal_legs(wmx_rtp *h, int max_packets, const int16_t *d_pcm, long source_stride, long pcm_packet_stride,
+                         const uint32_t *d_len, const uint32_t *d_calls, int16_t *d_pcm_out, uint32_t *d_len_out, void *stream);
+int wmx_rtp_reset_conceal(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
+int wmx_rtp_export_conceal(wmx_rtp *h, int16_t *hist, uint32_t *concealed, void *stream);
 /* A G.711 codec per stream, as each call negotiated it (wmix_amd/csrc/leg_codec.h holds the rule).  The reference's receive thread
  * accepts payload types 8 and 0 alike and decodes both with G711a2PCM (src/rtp.c:88-95, src/wmixTask.c:1282), and a send thread has one
  * law.  Here the handle keeps, per stream and ON THE DEVICE, in_codec, out_law and a `refused` counter:
@@ -765,6 +801,13 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * an A-law leg and a mu-law leg of one conference hear each other, each in its own codec.  wmx_conf_reset_legs keeps the listed legs'
  * codecs and zeroes their refused counts.  wmx_conf_export_codecs: in_codec, out_law (uint8) and refused (uint32) of every leg, any
  * pointer NULL; blocking.  A handle that never sets a codec runs the launches it ran before there were any.
+ * wmx_conf_conceal(h, on): between submits; off is the default.  With sequencing on and concealment on a tick is
+ * wmx_rtp_ingest_legs_codecs -> wmx_rtp_sequence_legs -> the selection if on (unchanged: it sees the rewritten d_len and the rows as
+ * they arrived, and does not hear synthesised audio) -> wmx_rtp_conceal_legs -> wmx_mix_load_minus_legs on the repaired rows with
+ * max_packets = 4 -> wmx_rtp_egress_rings.  With sequencing off the stage is not launched and its state does not move; with
+ * concealment off the launches are those of a handle that never heard of it.  The repaired rows and the history are made the first time
+ * it is switched on, never inside a submit.  wmx_conf_reset_legs also resets the listed legs' concealment state.
+ * wmx_conf_export_conceal: concealed (uint32) of every leg (wmx_rtp_export_conceal); blocking.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -780,6 +823,8 @@ int wmx_conf_speakers(wmx_conf *h, int max_speakers, uint32_t floor, int decay_s
 int wmx_conf_sequence(wmx_conf *h, int on, int max_gap);
 int wmx_conf_export_sequence(wmx_conf *h, uint16_t *next, uint8_t *synced, uint32_t *lost, uint32_t *late, uint32_t *dup,
                              uint32_t *resync, uint32_t *overflow, void *stream);
+int wmx_conf_conceal(wmx_conf *h, int on);
+int wmx_conf_export_conceal(wmx_conf *h, uint32_t *concealed, void *stream);
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
 int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);

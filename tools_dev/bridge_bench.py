@@ -51,6 +51,12 @@ the load does the work it does with sequencing off and (d) - (b), (e) - (c) are 
 and a third of that memset.
 
     python tools_dev/bridge_bench.py --pipe --out profiles/bridge/bridge_pipe_bench.json
+And (h), (i): the handle and the resident step with sequencing and concealment on (wmx_conf_conceal): (h) - (d), (i) - (e) are the
+concealment's launch and the plain load on four repaired slots in place of the call-list load.  --pipe --loss-every N takes one packet in
+N out of the script on all sides alike -- the packet with sequence number s of leg g when (g + s) % N == N - 1; its number is consumed
+-- so that the sequencer makes silence calls and the concealment's run path is paid for; the sides with sequencing on then send other
+datagrams than those without, and only handle and resident step of a kind are compared.
+    python tools_dev/bridge_bench.py --pipe --loss-every 50 --out profiles/bridge/bridge_conceal_bench.json
 --pipe --ulaw-every N adds (f), (g): the handle and the resident step again with a codec per leg (wmx_conf_set_codecs): every N-th leg is
 WMX_CODEC_PCMU in and mu-law out and its datagrams carry payload type 0, the other legs stay at the default; the launches are the per-leg
 ones for every leg.  (f) and (g) send the same datagrams, each leg in its own payload type, before any time is reported."""
@@ -304,7 +310,7 @@ def legs_against_conf(reps, freq=8000):
             "ratio_steady_over_conf": round(b["median_ms"] / a["median_ms"], 3), "ratio_jitter_over_conf": round(c["median_ms"] / a["median_ms"], 3)}
 
 
-def conf_pipe(reps, ulaw_every=0):
+def conf_pipe(reps, ulaw_every=0, loss_every=0):
     import ctypes as C
     import time
     from wmix_amd._lib import check, lib
@@ -329,6 +335,9 @@ def conf_pipe(reps, ulaw_every=0):
     before = np.cumsum(there.sum(axis=2), axis=0) - there.sum(axis=2)  # datagrams of the leg in the cycle's earlier ticks
     number = np.where(there, before[:, :, None] + np.cumsum(there, axis=2) - 1, 0)  # sequence numbers that count through the cycle
     pk[..., 2], pk[..., 3] = number >> 8, number & 255
+    if loss_every > 0:  # the packet with sequence number s of leg g never arrives when (g + s) % N == N - 1: its number is consumed
+        gone = there & ((np.arange(legs)[None, :, None] + number) % loss_every == loss_every - 1)
+        recv = np.where(gone, 0, recv).astype(np.int32)
     stream = torch.cuda.current_stream().cuda_stream
     # (a) the parent's composition
     tk, snd = TickBatch(legs, 1, stages=0), RtpSenders(legs)
@@ -408,6 +417,31 @@ def conf_pipe(reps, ulaw_every=0):
         new_cycle(ce, i)
         ce.step_resident(r_in[i], r_recv[i], e_out)
 
+    # (h), (i) the same two with sequencing and concealment on; the histories live on through the cycles
+    ch = ConfBridge(legs, 3, 3)
+    ci = ConfBridge(legs, 1, 3)
+    for x in (ch, ci):
+        x.set_conferences(layout)
+        x.set_play_correct(0)
+        x.sequence(True, 3)
+        x.conceal(True)
+    for k in range(3):
+        ch.rows_in[k][:] = pk[k]
+        ch.recv[k][:] = recv[k]
+    i_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+    step["h"] = step["i"] = 0
+
+    def handle_plc():
+        new_cycle(ch, step["h"] % CYC)
+        step["h"] += 1
+        return ch.submit()
+
+    def resident_plc():
+        i = step["i"] % CYC
+        step["i"] += 1
+        new_cycle(ci, i)
+        ci.step_resident(r_in[i], r_recv[i], i_out)
+
     # (f), (g) the same two with a codec per leg: every ulaw_every-th leg on PCMU both ways, the others at the default
     mixed = ulaw_every > 0
     if mixed:
@@ -451,7 +485,16 @@ def conf_pipe(reps, ulaw_every=0):
         k = handle_seq()
         cs.wait(k)
         resident_seq()
-        assert np.array_equal(a, cs.rows_out[k]) and np.array_equal(a, e_out.cpu().numpy()), ("datagrams differ with sequencing on, tick", t)
+        d_rows = cs.rows_out[k].copy()
+        assert np.array_equal(d_rows, e_out.cpu().numpy()), ("handle and resident step differ with sequencing on, tick", t)
+        k = handle_plc()
+        ch.wait(k)
+        resident_plc()
+        h_rows = ch.rows_out[k].copy()
+        assert np.array_equal(h_rows, i_out.cpu().numpy()), ("handle and resident step differ with concealment on, tick", t)
+        if loss_every == 0:  # in order and complete: neither stage changes a datagram
+            assert np.array_equal(a, d_rows), ("datagrams differ with sequencing on, tick", t)
+            assert np.array_equal(a, h_rows), ("datagrams differ with concealment on, tick", t)
         assert (a[:, 12:] != 0xD5).any()
 
     def wall(f, n, end):
@@ -462,13 +505,15 @@ def conf_pipe(reps, ulaw_every=0):
         return (time.perf_counter() - t0) * 1e3 / n
 
     per_block = max(reps // BLOCKS, 8)
-    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": []}
+    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": [], "h": [], "i": []}
     for _ in range(BLOCKS + 1):  # the first block warms up
         ms["a"].append(wall(parent, per_block, torch.cuda.synchronize))
         ms["b"].append(wall(handle, per_block, lambda: cb.wait(-1)))
         ms["c"].append(wall(resident, per_block, torch.cuda.synchronize))
         ms["d"].append(wall(handle_seq, per_block, lambda: cs.wait(-1)))
         ms["e"].append(wall(resident_seq, per_block, torch.cuda.synchronize))
+        ms["h"].append(wall(handle_plc, per_block, lambda: ch.wait(-1)))
+        ms["i"].append(wall(resident_plc, per_block, torch.cuda.synchronize))
         if mixed:
             ms["f"].append(wall(handle_mixed, per_block, lambda: cf.wait(-1)))
             ms["g"].append(wall(resident_mixed, per_block, torch.cuda.synchronize))
@@ -476,7 +521,10 @@ def conf_pipe(reps, ulaw_every=0):
     a, b, c, d, e = side(ms["a"]), side(ms["b"]), side(ms["c"]), side(ms["d"]), side(ms["e"])
     sq = cs.export_sequence()
     seq_counters = {name: int(sq[name].sum()) for name in ("lost", "late", "dup", "resync", "overflow")}
-    assert not any(seq_counters.values()), seq_counters  # the script is in order
+    assert loss_every > 0 or not any(seq_counters.values()), seq_counters  # the script is in order
+    h, i = side(ms["h"]), side(ms["i"])
+    concealed_h = int(ch.export_conceal().sum())
+    assert (concealed_h > 0) == (seq_counters["lost"] > 0)
     dropped = {"conf": int(cb.export_legs()["dropped"].sum()), "resident": int(cr.export_legs()["dropped"].sum())}
     # ---- the fused play-and-send kernel beside the pair it replaces
     pair, fused, s2, s3 = MixBatch(legs, 1, 8000), MixBatch(legs, 1, 8000), RtpSenders(legs), RtpSenders(legs)
@@ -501,7 +549,11 @@ def conf_pipe(reps, ulaw_every=0):
                 "refused_of_f": int(cf.export_codecs()["refused"].sum())}
         cf.close()
         cg.close()
-    for x in (tk, snd, cb, cr, cs, ce, pair, fused, s2, s3):
+    more.update({"loss_every": loss_every, "packets_lost_from_the_script_per_cycle": int((there & (recv <= 0)).sum()),
+                 "h_wmx_conf_3_slots_sequencing_and_concealment_on": h, "i_step_resident_sequencing_and_concealment_on": i,
+                 "h_minus_d_ms": round(h["median_ms_per_tick"] - d["median_ms_per_tick"], 5),
+                 "i_minus_e_ms": round(i["median_ms_per_tick"] - e["median_ms_per_tick"], 5), "concealed_of_h": concealed_h})
+    for x in (tk, snd, cb, cr, cs, ce, ch, ci, pair, fused, s2, s3):
         x.close()
     return {**more, "conferences": n_conf, "sizes": {str(k): sizes.count(k) for k in sorted(set(sizes))}, "legs": legs, "max_packets": 3,
             "packets_per_leg_and_tick": round(float((recv > 0).sum()) / (CYC * legs), 3), "ticks_per_block": per_block, "datagram_ticks_checked": 2 * CYC,
@@ -585,6 +637,7 @@ if __name__ == "__main__":
     ap.add_argument("--legs", action="store_true", help="the bridge load with a cursor per leg beside wmx_mix_load_minus_conf, same layout")
     ap.add_argument("--pipe", action="store_true", help="the bridge of RTP/G.711 legs end to end: the parent's composition, wmx_conf, the launches alone")
     ap.add_argument("--ulaw-every", type=int, default=0, help="with --pipe: two more sides, every N-th leg on PCMU both ways (a codec per leg)")
+    ap.add_argument("--loss-every", type=int, default=0, help="with --pipe: one packet in N never arrives, on all sides alike: the run path of the concealment")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
@@ -596,7 +649,7 @@ if __name__ == "__main__":
         args.ragged, args.speakers = False, 0
     if args.pipe:
         res = {"tool": "bridge_bench --pipe", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every)}
+               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every, args.loss_every)}
         args.sizes = args.tick = ""
         args.ragged, args.speakers = False, 0
     if args.speakers:

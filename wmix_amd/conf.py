@@ -67,6 +67,17 @@ class ConfBridge:
               "wmx_conf_export_sequence")
         return r
 
+    def conceal(self, on):
+        """with sequencing on: a gap's silence calls are synthesised from the leg's own history and the packet behind the gap is
+        cross-faded in (wmx_conf_conceal), between submits; off (the default) = zeros"""
+        check(lib().wmx_conf_conceal(self._h, 1 if on else 0), "wmx_conf_conceal")
+
+    def export_conceal(self):
+        """concealed: uint32 [n_legs], the packets synthesised per leg, as the work queued on the current stream leaves them"""
+        concealed = np.zeros(self.n_legs, np.uint32)
+        check(lib().wmx_conf_export_conceal(self._h, concealed.ctypes.data, self._stream()), "wmx_conf_export_conceal")
+        return concealed
+
     def set_codecs(self, legs, in_codec, out_law):
         """a G.711 codec per leg, as each call negotiated it (wmx_conf_set_codecs), between submits: in_codec "reference" (the default:
         A-law whatever arrives), "pcma", "pcmu" or "by_pt" (or WMX_CODEC_* 0 .. 3), out_law "a" / "u"; legs None = every leg"""
@@ -88,7 +99,7 @@ class ConfBridge:
 
     def reset_legs(self, legs=None):
         """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-        refused = 0; the leg keeps its codec (None = every leg)"""
+        refused = 0, the concealment history and count zero; the leg keeps its codec (None = every leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

@@ -10,7 +10,9 @@
 // With sequencing on (wmx_conf_sequence) the ingest also leaves the sequence numbers, wmx_rtp_sequence_legs turns them into a call list
 // per leg and rewrites d_len in front of the selection, and the load is wmx_mix_load_minus_legs_calls.  The ingest and the egress
 // apply each leg's own G.711 codec (wmx_conf_set_codecs; wmix_amd/csrc/leg_codec.h); a handle that never sets one runs the
-// reference's A-law-whatever-arrives and one law out.
+// reference's A-law-whatever-arrives and one law out.  With concealment on as well (wmx_conf_conceal) wmx_rtp_conceal_legs stands
+// between the selection and the load: it turns every leg's list into rows that are all data -- a lost packet synthesised from the
+// leg's own history (wmix_amd/csrc/leg_plc.h) -- and the load is wmx_mix_load_minus_legs on those.
 //
 // PER SLOT (made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a 4-byte
 // boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and three events.  PER HANDLE: the mixer
@@ -40,6 +42,9 @@ struct wmx_conf {
     uint32_t *d_calls; // [n_legs] the call list the sequencer leaves for the load
     bool seq_on;
     int max_gap;
+    bool conceal_on;      // only with seq_on: wmx_rtp_conceal_legs between the selection and the load
+    int16_t *d_rep;       // [n_legs][4][160] the repaired rows, made when concealment is first switched on
+    uint32_t *d_rep_len;  // [n_legs][4], behind them
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -76,7 +81,12 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         if (rc != 0) return rc;
         load_mute = h->d_mask;
     }
-    if (h->seq_on)
+    if (h->seq_on && h->conceal_on) {  // every call becomes a data call: the plain load, four slots
+        constexpr int C = WMX_MIX_MAX_LEG_PACKETS;
+        rc = wmx_rtp_conceal_legs(h->snd, K, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len, h->d_calls, h->d_rep, h->d_rep_len, stream);
+        if (rc != 0) return rc;
+        rc = wmx_mix_load_minus_legs(h->mix, h->d_rep, kPcmBytes, 8000, 1, 16, (long)C * kPcmRow, kPcmRow, C, h->d_rep_len, load_mute, 1, stream);
+    } else if (h->seq_on)
         rc = wmx_mix_load_minus_legs_calls(h->mix, h->d_pcm, kPcmBytes, 8000, 1, 16, (long)K * kPcmRow, kPcmRow, K, h->d_len, h->d_calls, load_mute, 1,
                                            stream);
     else
@@ -115,6 +125,7 @@ int wmx_conf_destroy(wmx_conf *h) {
     if (h->d_pcm) (void)hipFree(h->d_pcm);
     if (h->d_len) (void)hipFree(h->d_len);
     if (h->d_calls) (void)hipFree(h->d_calls);  // d_seq lies behind it
+    if (h->d_rep) (void)hipFree(h->d_rep);  // d_rep_len lies behind it
     if (h->d_mute) (void)hipFree(h->d_mute);  // d_mask lies behind it
     if (h->h_mute) (void)hipHostFree(h->h_mute);
     if (h->mix) wmx_mix_destroy(h->mix);
@@ -240,6 +251,31 @@ int wmx_conf_sequence(wmx_conf *h, int on, int max_gap) {
     return 0;
 }
 
+// on != 0: with sequencing on, the silence calls of a gap are synthesised from the leg's own history and the packet behind the gap is
+// cross-faded in (wmx_rtp_conceal_legs); 0 (the default): zeros, the launches of a handle that never heard of it.  Between submits.
+// The repaired rows and the history are made the first time it is switched on.
+int wmx_conf_conceal(wmx_conf *h, int on) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (on && !h->d_rep) {
+        const size_t rows = (size_t)h->n_legs * WMX_MIX_MAX_LEG_PACKETS;
+        void *p = nullptr;
+        int rc = wmx::zeroed_block(&p, rows * (kPcmRow * sizeof(int16_t) + sizeof(uint32_t)), "hipMemset(repaired rows)");
+        if (rc == 0 && (rc = wmx_rtp_reset_conceal(h->snd, nullptr, 0, nullptr)) != 0) (void)hipFree(p);
+        if (rc != 0) return rc;
+        h->d_rep = static_cast<int16_t *>(p);
+        h->d_rep_len = reinterpret_cast<uint32_t *>(h->d_rep + rows * kPcmRow);
+    }
+    h->conceal_on = on != 0;
+    return 0;
+}
+
+// concealed (uint32) of every leg (wmx_rtp_export_conceal); blocking
+int wmx_conf_export_conceal(wmx_conf *h, uint32_t *concealed, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_export_conceal(h->snd, nullptr, concealed, stream);
+}
+
 // a G.711 codec per leg (wmx_rtp_set_codecs over the legs; NULL = all): between submits, ordered on `stream`
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
     if (!h) return WMX_EINVAL;
@@ -255,16 +291,17 @@ int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uin
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
 
 // a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-// refused = 0; the leg keeps its codec
+// refused = 0, the concealment history and count zero; the leg keeps its codec
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    // before the first of the five: a bad index resets nothing
+    // before the first of them: a bad index resets nothing
     if (wmx::idx_check(host_idx, n, h->n_legs, "wmx_conf_reset_legs: leg", "handle")) return WMX_EINVAL;
     int rc = wmx_mix_reset_leg_cursors(h->mix, host_idx, n, stream);
     if (rc == 0) rc = wmx_mix_reset_speakers(h->mix, host_idx, n, stream);
     if (rc == 0) rc = wmx_mix_reset_rings(h->mix, host_idx, n, stream);
     if (rc == 0) rc = wmx_rtp_reset_streams(h->snd, host_idx, n, stream);
     if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, host_idx, n, stream);
+    if (rc == 0 && h->d_rep) rc = wmx_rtp_reset_conceal(h->snd, host_idx, n, stream);  // never switched on: no state to reset
     return rc;
 }
 

@@ -12,6 +12,7 @@
 #include "wmx_internal.h"
 #include "g711_dev.h"
 #include "leg_seq.h"
+#include "leg_plc.h"
 #include "leg_codec.h"
 
 struct wmx_rtp {
@@ -30,6 +31,10 @@ struct wmx_rtp {
     uint32_t *d_refused;
     uint8_t *d_in_codec, *d_out_law;
     bool codecs_default;
+    // the concealment rule's state per leg (leg_plc.h), made by the first call that needs it, one block: hist (kPlcHist int16 per leg),
+    // behind it concealed (uint32)
+    int16_t *d_plc_hist;
+    uint32_t *d_plc_concealed;
 };
 
 namespace wmx {
@@ -312,6 +317,149 @@ __global__ __launch_bounds__(256) void rtp_sequence_legs_kernel(const uint16_t *
     }
 }
 
+// ---- the concealment rule (leg_plc.h) for every leg: ONE WAVE PER LEG, kPlcLegsPerBlock legs per block; no wave waits for another.
+// A leg whose list holds no silence call takes a wave-uniform early path: its rows are copied to the repaired rows in call order and
+// the history becomes the last 320 samples emitted, registers only.  Otherwise the wave lays a TIMELINE into LDS -- the history, then
+// every call's emitted row behind it -- so that the history in front of call j is timeline[160 j .. 160 j + 320) and nothing is ever
+// rolled.  At the start of a run q = h0 >> 4 goes to LDS, lane l scores lag 40 + l and (l < 17) lag 104 + l with 160 multiply-adds
+// each -- q[i] is one address for the wave, q[i - L] one int16 per lane, descending: no bank conflict -- and six xor steps find the
+// arg-max, ties to the smaller lag.  All 64 lanes then synthesise (and blend) two samples each per pass.  Per leg 1920 + 640 bytes of
+// LDS.  Samples move in pairs: WIDE (rows in and out on 4-byte boundaries) one 32-bit access per pair, otherwise two 16-bit ones; the
+// handle's history and the LDS are always 32-bit.  A lane writes only its own leg's rows, history and counter: no atomics.
+constexpr int kPlcLegsPerBlock = 4;
+constexpr int kPlcPairs = kPlcRow / 2, kPlcHistPairs = kPlcHist / 2;
+constexpr int kPlcTimeline = kPlcHist + kSeqMaxCalls * kPlcRow;
+
+// LDS hand-off between lanes of one wave: the hardware runs a wave's LDS instructions in issue order, the compiler must keep it
+__device__ __forceinline__ void plc_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+template <bool WIDE>
+__device__ __forceinline__ uint32_t plc_load2(const int16_t *p, int pair) {
+    if (WIDE) return *reinterpret_cast<const uint32_t *>(p + 2 * pair);
+    return (uint32_t)(uint16_t)p[2 * pair] | ((uint32_t)(uint16_t)p[2 * pair + 1] << 16);
+}
+template <bool WIDE>
+__device__ __forceinline__ void plc_store2(int16_t *p, int pair, uint32_t v) {
+    if (WIDE) {
+        *reinterpret_cast<uint32_t *>(p + 2 * pair) = v;
+    } else {
+        p[2 * pair] = (int16_t)(v & 0xFFFFu);
+        p[2 * pair + 1] = (int16_t)(v >> 16);
+    }
+}
+__device__ __forceinline__ uint32_t plc_pack(int32_t lo, int32_t hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
+
+template <bool WIDE>
+__global__ __launch_bounds__(64 * kPlcLegsPerBlock) void rtp_conceal_legs_kernel(const int16_t *__restrict__ pcm, long source_stride,
+                                                                                  long packet_stride, const uint32_t *__restrict__ len,
+                                                                                  const uint32_t *__restrict__ calls_in, int max_packets,
+                                                                                  int16_t *__restrict__ pcm_out, uint32_t *__restrict__ len_out,
+                                                                                  int16_t *__restrict__ hist, uint32_t *__restrict__ concealed,
+                                                                                  int n_legs) {
+    __shared__ __attribute__((aligned(16))) int16_t timeline[kPlcLegsPerBlock][kPlcTimeline];
+    __shared__ __attribute__((aligned(16))) int16_t qs[kPlcLegsPerBlock][kPlcHist];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const size_t leg = blockIdx.x * (size_t)kPlcLegsPerBlock + (size_t)w;
+    if (leg >= (size_t)n_legs) return;  // the whole wave
+    const uint32_t calls = (uint32_t)__builtin_amdgcn_readfirstlane((int)calls_in[leg]);
+    const uint32_t count = leg_plc_count(calls);
+    uint32_t readable = 0;
+#pragma unroll
+    for (int k = 0; k < kSeqMaxCalls; k++)
+        if (k < max_packets) readable |= leg_plc_readable(len[leg * (size_t)max_packets + k]) << k;
+    readable = (uint32_t)__builtin_amdgcn_readfirstlane((int)readable);
+    uint32_t sil = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++)
+        if (j < count && leg_plc_silence(calls, j, readable)) sil |= 1u << j;
+    if (lane < kSeqMaxCalls) len_out[leg * kSeqMaxCalls + lane] = (uint32_t)lane < count ? kPlcRowBytes : 0u;
+    if (count == 0u) return;  // no calls: the state stays
+    const int16_t *src = pcm + leg * source_stride;
+    int16_t *dst = pcm_out + leg * (size_t)(kSeqMaxCalls * kPlcRow);
+    int16_t *hs = hist + leg * (size_t)kPlcHist;
+    const bool second = lane < kPlcPairs - 64;  // a row is 80 pairs: every lane one, the first 16 another
+
+    if (sil == 0u) {  // data calls only
+        if (count == 1u) {  // the older half of the history is its newer half; read and written by disjoint pairs
+            const uint32_t a = plc_load2<true>(hs, kPlcPairs + lane), b = second ? plc_load2<true>(hs, kPlcPairs + 64 + lane) : 0u;
+            plc_store2<true>(hs, lane, a);
+            if (second) plc_store2<true>(hs, 64 + lane, b);
+        }
+        for (uint32_t j = 0; j < count; j++) {
+            const int16_t *row = src + leg_calls_slot(calls, j) * packet_stride;
+            const uint32_t a = plc_load2<WIDE>(row, lane), b = second ? plc_load2<WIDE>(row, 64 + lane) : 0u;
+            plc_store2<WIDE>(dst + j * kPlcRow, lane, a);
+            if (second) plc_store2<WIDE>(dst + j * kPlcRow, 64 + lane, b);
+            if (j + 2u >= count) {  // one of the last two: it stays in the history
+                int16_t *hrow = hs + (j + 2u - count) * kPlcRow;
+                plc_store2<true>(hrow, lane, a);
+                if (second) plc_store2<true>(hrow, 64 + lane, b);
+            }
+        }
+        return;
+    }
+
+    int16_t *tl = timeline[w], *q = qs[w];
+    for (int p = lane; p < kPlcHistPairs; p += 64) plc_store2<true>(tl, p, plc_load2<true>(hs, p));
+    const int16_t *h0 = tl;
+    int32_t lag = kPlcLagMin, run = 0;
+    uint32_t made = 0;
+    for (uint32_t j = 0; j < count; j++) {
+        int16_t *y = tl + kPlcHist + j * kPlcRow, *out = dst + j * kPlcRow;
+        if ((sil >> j) & 1u) {
+            if (run == 0) {
+                h0 = tl + j * kPlcRow;
+                plc_wave_sync();  // what the calls in front of this one appended
+                for (int p = lane; p < kPlcHistPairs; p += 64) {
+                    const uint32_t v = plc_load2<true>(h0, p);
+                    plc_store2<true>(q, p, plc_pack(leg_plc_q((int16_t)(v & 0xFFFFu)), leg_plc_q((int16_t)(v >> 16))));
+                }
+                plc_wave_sync();
+                int32_t L = kPlcLagMin + lane, c = leg_plc_score(q, L);
+                if (lane <= kPlcLagMax - kPlcLagMin - 64) {
+                    const int32_t L2 = kPlcLagMin + 64 + lane, c2 = leg_plc_score(q, L2);
+                    if (leg_plc_better(c2, L2, c, L)) c = c2, L = L2;
+                }
+                for (int o = 32; o > 0; o >>= 1) {
+                    const int32_t c2 = __shfl_xor(c, o, 64), L2 = __shfl_xor(L, o, 64);
+                    if (leg_plc_better(c2, L2, c, L)) c = c2, L = L2;
+                }
+                lag = __builtin_amdgcn_readfirstlane(L);
+            }
+            for (int p = lane; p < kPlcPairs; p += 64) {
+                const int32_t k = run * kPlcRow + 2 * p;
+                const uint32_t v = plc_pack(leg_plc_synth(h0[leg_plc_index(k, lag)], k), leg_plc_synth(h0[leg_plc_index(k + 1, lag)], k + 1));
+                plc_store2<true>(y, p, v);
+                plc_store2<WIDE>(out, p, v);
+            }
+            run++;
+            made++;
+        } else {
+            const int16_t *row = src + leg_calls_slot(calls, j) * packet_stride;
+            for (int p = lane; p < kPlcPairs; p += 64) {
+                uint32_t v = plc_load2<WIDE>(row, p);
+                if (run > 0 && 2 * p < kPlcBlend) {
+                    const int32_t i = 2 * p, k = run * kPlcRow + i;
+                    v = plc_pack(leg_plc_blend((int16_t)(v & 0xFFFFu), leg_plc_synth(h0[leg_plc_index(k, lag)], k), i),
+                                 leg_plc_blend((int16_t)(v >> 16), leg_plc_synth(h0[leg_plc_index(k + 1, lag)], k + 1), i + 1));
+                }
+                plc_store2<true>(y, p, v);
+                plc_store2<WIDE>(out, p, v);
+            }
+            run = 0;
+        }
+    }
+    plc_wave_sync();
+    const int16_t *last = tl + count * kPlcRow;  // the last 320 samples emitted
+    for (int p = lane; p < kPlcHistPairs; p += 64) plc_store2<true>(hs, p, plc_load2<true>(last, p));
+    if (lane == 0) concealed[leg] += made;
+}
+
 inline bool aligned_to(const void *p, long stride_bytes, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0 && stride_bytes % a == 0; }
 
 }  // namespace
@@ -343,6 +491,8 @@ int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
     h->d_refused = nullptr;
     h->d_in_codec = h->d_out_law = nullptr;
     h->codecs_default = true;
+    h->d_plc_hist = nullptr;
+    h->d_plc_concealed = nullptr;
     hipError_t e = hipMalloc(&h->d_seq, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMalloc(&h->d_ts, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMemset(h->d_seq, 0, sizeof(uint32_t) * n_streams);  // rtp_header(..., seq 0, timestamp 0, ssrc 0)
@@ -363,6 +513,7 @@ int wmx_rtp_destroy(wmx_rtp *h) {
     if (h->d_ts) (void)hipFree(h->d_ts);
     if (h->d_sq) (void)hipFree(h->d_sq);
     if (h->d_refused) (void)hipFree(h->d_refused);  // in_codec and out_law lie behind it
+    if (h->d_plc_hist) (void)hipFree(h->d_plc_hist);  // concealed lies behind it
     delete h;
     return 0;
 }
@@ -597,6 +748,87 @@ int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_
         for (int c = 0; c < 5; c++)
             if (out[c]) out[c][r] = w[(size_t)(2 + c) * n + r];
     }
+    return 0;
+}
+
+// ---- the concealment rule per leg (include/wmix_amd.h, leg_plc.h)
+// the state, all zero (a fresh history, concealed 0), from the first call that needs it on
+static int plc_state(wmx_rtp *h) {
+    if (h->d_plc_hist) return 0;
+    const size_t hist_bytes = (size_t)h->n_streams * kPlcHist * sizeof(int16_t);
+    void *p = nullptr;
+    const int rc = zeroed_block(&p, hist_bytes + (size_t)h->n_streams * sizeof(uint32_t), "hipMemset(concealment state)");
+    if (rc) return rc;
+    h->d_plc_hist = static_cast<int16_t *>(p);
+    h->d_plc_concealed = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(p) + hist_bytes);
+    return 0;
+}
+
+int wmx_rtp_conceal_legs(wmx_rtp *h, int max_packets, const int16_t *d_pcm, long source_stride, long pcm_packet_stride, const uint32_t *d_len,
+                         const uint32_t *d_calls, int16_t *d_pcm_out, uint32_t *d_len_out, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !d_pcm || !d_len || !d_calls || !d_pcm_out || !d_len_out || max_packets < 1 || max_packets > kSeqMaxCalls) {
+        set_error("wmx_rtp_conceal_legs: max_packets=%d must be 1 .. %d, and no pointer NULL", max_packets, kSeqMaxCalls);
+        return WMX_EINVAL;
+    }
+    const size_t n = (size_t)h->n_streams;
+    if (pcm_packet_stride < kPlcRow || (n > 1 && source_stride < pcm_packet_stride * max_packets)) {
+        set_error("wmx_rtp_conceal_legs: rows that overlap (pcm_packet_stride %ld < %d, or source_stride %ld shorter than %d rows)",
+                  pcm_packet_stride, kPlcRow, source_stride, max_packets);
+        return WMX_EINVAL;
+    }
+    const int16_t *in_end = d_pcm + (n - 1) * (size_t)source_stride + (size_t)(max_packets - 1) * pcm_packet_stride + kPlcRow;
+    const int16_t *out_end = d_pcm_out + n * (size_t)(kSeqMaxCalls * kPlcRow);
+    if (reinterpret_cast<uintptr_t>(d_pcm) < reinterpret_cast<uintptr_t>(out_end) &&
+        reinterpret_cast<uintptr_t>(d_pcm_out) < reinterpret_cast<uintptr_t>(in_end)) {
+        set_error("wmx_rtp_conceal_legs: the repaired rows overlap the rows they are made from");
+        return WMX_EINVAL;
+    }
+    const int rcs = plc_state(h);
+    if (rcs) return rcs;
+    const bool wide = aligned_to(d_pcm, pcm_packet_stride * 2, 4) && (source_stride * 2) % 4 == 0 && reinterpret_cast<uintptr_t>(d_pcm_out) % 4 == 0;
+    hipLaunchKernelGGL(wide ? rtp_conceal_legs_kernel<true> : rtp_conceal_legs_kernel<false>,
+                       dim3((unsigned)((n + kPlcLegsPerBlock - 1) / kPlcLegsPerBlock)), dim3(64 * kPlcLegsPerBlock), 0, as_stream(stream), d_pcm,
+                       source_stride, pcm_packet_stride, d_len, d_calls, max_packets, d_pcm_out, d_len_out, h->d_plc_hist, h->d_plc_concealed,
+                       h->n_streams);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// a fresh history and concealed = 0 for the listed legs (NULL = all), on `stream`: a new call does not repeat the old call's voice
+int wmx_rtp_reset_conceal(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
+    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_conceal: leg", "handle")) return WMX_EINVAL;
+    const bool fresh = !h->d_plc_hist;
+    const int rcs = plc_state(h);
+    if (rcs || fresh) return rcs;  // just made: zero already
+    hipStream_t s = as_stream(stream);
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(h->d_plc_hist, 0, (size_t)h->n_streams * (kPlcHist * sizeof(int16_t) + sizeof(uint32_t)), s));
+        return 0;
+    }
+    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
+        WMX_HIP(hipMemsetAsync(h->d_plc_hist + (size_t)host_idx[i] * kPlcHist, 0, kPlcHist * sizeof(int16_t), s));
+        WMX_HIP(hipMemsetAsync(h->d_plc_concealed + host_idx[i], 0, sizeof(uint32_t), s));
+    }
+    return 0;
+}
+
+// hist (n_streams x 320 int16, newest last) and concealed (uint32) of every leg as the work queued on `stream` leaves them; any pointer
+// may be NULL; blocking
+int wmx_rtp_export_conceal(wmx_rtp *h, int16_t *hist, uint32_t *concealed, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const size_t n = (size_t)h->n_streams;
+    if (!h->d_plc_hist) {  // no leg has been concealed on this handle: all zero
+        if (hist) memset(hist, 0, n * kPlcHist * sizeof(int16_t));
+        if (concealed) memset(concealed, 0, n * sizeof(uint32_t));
+        return 0;
+    }
+    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+    if (hist) WMX_HIP(hipMemcpy(hist, h->d_plc_hist, n * kPlcHist * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if (concealed) WMX_HIP(hipMemcpy(concealed, h->d_plc_concealed, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

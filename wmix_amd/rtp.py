@@ -87,6 +87,44 @@ class RtpSenders:
                                             torch.cuda.current_stream().cuda_stream), "wmx_rtp_export_sequence")
         return r
 
+    def conceal_legs(self, pcm, lens, calls, rows_out=None, lens_out=None):
+        """Conceal lost packets from each leg's own history (wmx_rtp_conceal_legs), between sequence_legs and the load: pcm int16 CUDA
+        [n_streams, max_packets, >= 160], lens int32 (or uint32) CUDA [n_streams, max_packets] and calls int32 (or uint32) CUDA
+        [n_streams] as sequence_legs leaves them; none of them is written.  -> (rows int16 CUDA [n_streams, 4, 160] in call order,
+        lens_out int32 CUDA [n_streams, 4]: 320 per call), what MixBatch.load_minus_legs takes with four slots.  Rows behind a leg's
+        calls are not written."""
+        assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() == 3 and pcm.stride(2) == 1 and pcm.shape[0] == self.n and pcm.shape[2] >= 160
+        k = pcm.shape[1]
+        assert lens.is_cuda and lens.dtype in (torch.int32, torch.uint32) and lens.is_contiguous() and tuple(lens.shape) == (self.n, k)
+        assert calls.is_cuda and calls.dtype in (torch.int32, torch.uint32) and calls.is_contiguous() and calls.numel() == self.n
+        if rows_out is None:
+            rows_out = torch.zeros((self.n, 4, 160), dtype=torch.int16, device=pcm.device)
+        if lens_out is None:
+            lens_out = torch.zeros((self.n, 4), dtype=torch.int32, device=pcm.device)
+        assert rows_out.is_cuda and rows_out.dtype == torch.int16 and rows_out.is_contiguous() and tuple(rows_out.shape) == (self.n, 4, 160)
+        assert lens_out.is_cuda and lens_out.dtype in (torch.int32, torch.uint32) and lens_out.is_contiguous() and tuple(lens_out.shape) == (self.n, 4)
+        check(lib().wmx_rtp_conceal_legs(self._h, k, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), lens.data_ptr(), calls.data_ptr(),
+                                         rows_out.data_ptr(), lens_out.data_ptr(), torch.cuda.current_stream().cuda_stream), "wmx_rtp_conceal_legs")
+        return rows_out, lens_out
+
+    def reset_conceal(self, legs=None):
+        """a fresh history and concealed = 0 for the listed legs (None = all)"""
+        import numpy as np
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_rtp_reset_conceal(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                          torch.cuda.current_stream().cuda_stream), "wmx_rtp_reset_conceal")
+
+    def export_conceal(self):
+        """dict(hist: int16 [n_streams, 320], newest last; concealed: uint32 [n_streams]) as the work queued on the current stream
+        leaves them"""
+        import numpy as np
+        r = {"hist": np.zeros((self.n, 320), np.int16), "concealed": np.zeros(self.n, np.uint32)}
+        check(lib().wmx_rtp_export_conceal(self._h, r["hist"].ctypes.data, r["concealed"].ctypes.data, torch.cuda.current_stream().cuda_stream),
+              "wmx_rtp_export_conceal")
+        return r
+
     def set_codecs(self, streams, in_codec, out_law):
         """in_codec ("reference", "pcma", "pcmu", "by_pt") and out_law ("a", "u") of the listed streams (None = all): wmx_rtp_set_codecs"""
         import numpy as np
