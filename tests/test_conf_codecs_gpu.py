@@ -59,9 +59,9 @@ class CodecReplay(Replay):
                     self.senders[g][i] = b
                 self.out_law[g] = out_law
 
-    def decode(self, pk, recv):
+    def decode(self, pk, recv, slots=K):
         rows, lens, _ = ingest(self.dec, pk, recv, self.in_codec, self.refused)
-        pcm = np.zeros((self.n, K, 161), np.int16)
+        pcm = np.zeros((self.n, slots, 161), np.int16)
         pcm[:, :, :160] = rows
         return pcm, lens
 
@@ -135,6 +135,23 @@ def test_every_datagram_is_the_replays(cuda, story, slots, mode):
     cb.close()
 
 
+def replay_sequenced(lib, pk, recv, select, codecs):
+    """the replay with sequence(True, 3) and speakers(*select); codecs: the legs as START sets them, else every leg at the default
+    -> (datagrams, the sequence model, per tick (speaking, env), the replay)"""
+    rp, model, spk = CodecReplay(lib, G), LegsSeqModel(G), SpeakersLegsModel(G)
+    if codecs:
+        start(rp)
+    out, sel = np.zeros((T, G, 172), np.uint8), []
+    for t in range(T):
+        pcm, lens = rp.decode(pk[t], recv[t])
+        _, new_lens, lists = model.tick(seq_raw_of(pk[t], recv[t]), lens, 3)
+        sp, mute = spk.step_legs(LAYOUT, pcm, new_lens, 320, select[0], select[1], select[2], None)
+        sel.append((sp.copy(), spk.env.copy()))
+        rows, rlens = repaired_rows(pcm, lists)
+        out[t] = rp.tick(rows, rlens, LAYOUT, mute)
+    return out, model, sel, rp
+
+
 def test_a_refused_packet_is_not_late_not_a_duplicate_and_not_heard(cuda, oracle_port, story):
     """sequence(True, 3) and speakers(2, floor, 3) on: the sequence model and the selection model are fed d_len as the codec rule leaves
     it.  A refused packet has consumed a sequence number, so what the sequence rule sees of it is a gap: lost, never late or dup."""
@@ -148,18 +165,7 @@ def test_a_refused_packet_is_not_late_not_a_duplicate_and_not_heard(cuda, oracle
     select = (2, int(np.percentile(levels, 40)), 3)
 
     def replay(codecs):
-        rp, model, spk = CodecReplay(oracle_port, G), LegsSeqModel(G), SpeakersLegsModel(G)
-        if codecs:
-            start(rp)
-        out, sel = np.zeros((T, G, 172), np.uint8), []
-        for t in range(T):
-            pcm, lens = rp.decode(pk[t], recv[t])
-            _, new_lens, lists = model.tick(seq_raw_of(pk[t], recv[t]), lens, 3)
-            sp, mute = spk.step_legs(LAYOUT, pcm, new_lens, 320, select[0], select[1], select[2], None)
-            sel.append((sp.copy(), spk.env.copy()))
-            rows, rlens = repaired_rows(pcm, lists)
-            out[t] = rp.tick(rows, rlens, LAYOUT, mute)
-        return out, model, sel, rp
+        return replay_sequenced(oracle_port, pk, recv, select, codecs)
 
     want, model, sel, rp = replay(True)
     deaf, deaf_model, _, _ = replay(False)

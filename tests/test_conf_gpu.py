@@ -31,10 +31,10 @@ class Replay:
             self.init(s, 0)
         self.orc, self.n = LegsOracle(lib, n, (1, 8000), 1, L.PLATFORMS[platform][1]), n
 
-    def decode(self, pk, recv):
-        pcm, lens = np.zeros((self.n, K, 161), np.int16), np.zeros((self.n, K), np.uint32)
+    def decode(self, pk, recv, slots=K):
+        pcm, lens = np.zeros((self.n, slots, 161), np.int16), np.zeros((self.n, slots), np.uint32)
         for g in range(self.n):
-            for k in range(K):
+            for k in range(slots):
                 if recv[g, k] > 0:
                     row, dec = np.ascontiguousarray(pk[g, k]), np.zeros(160, np.int16)
                     lens[g, k] = self.ing(row.ctypes.data, dec.ctypes.data, None)
@@ -92,7 +92,7 @@ def run(cb, pk, recv, mode, before=None, after=None):
         if before and t in before:
             before[t](cb)
         if mode == "resident":
-            rows = np.zeros((n, K, cb.in_row), np.uint8)
+            rows = np.zeros((n, recv.shape[2], cb.in_row), np.uint8)
             rows[:, :, :172] = pk[t]
             out[t] = cb.step_resident(torch.from_numpy(rows).cuda(), torch.from_numpy(recv[t]).cuda()).cpu().numpy()
         else:
@@ -115,9 +115,9 @@ def script(oracle_port):
     return pk, recv, want
 
 
-def bridge(n=G, slots=3, layout=LAYOUT):
+def bridge(n=G, slots=3, layout=LAYOUT, max_packets=K):
     from wmix_amd.conf import ConfBridge
-    cb = ConfBridge(n, slots, K)
+    cb = ConfBridge(n, slots, max_packets)
     if layout is not None:
         cb.set_conferences(layout)
     return cb

@@ -16,16 +16,16 @@ IN_CONF = sorted(g for c in LAYOUT for g in c)
 QUIET = np.array([0xD5, 0x55, 0xD4, 0x54, 0xD7, 0x57], np.uint8)  # A-law codes of the smallest samples
 
 
-def clean_script(seed, steady=False, quiet=False):
+def clean_script(seed, steady=False, quiet=False, legs=G, ticks=T):
     """packets[t][g]: the list of (seq, payload type, 160 codes) that leg g delivers in tick t, in order, every one PCMA or PCMU.
     steady: one packet per tick and leg; else none, one or two.  The legs start at different numbers, one just below the uint16 wrap."""
     rng = np.random.default_rng(seed)
-    seq = [int(s) for s in rng.choice([0, 65520, 1234, 40000], size=G)]
+    seq = [int(s) for s in rng.choice([0, 65520, 1234, 40000], size=legs)]
     seq[2] = 65520
     packets = []
-    for t in range(T):
+    for t in range(ticks):
         packets.append([])
-        for g in range(G):
+        for g in range(legs):
             now = []
             for _ in range(1 if steady else int(rng.choice([0, 1, 1, 1, 1, 2]))):
                 codes = rng.choice(QUIET, size=160) if quiet else rng.integers(0, 256, size=160).astype(np.uint8)
@@ -35,48 +35,50 @@ def clean_script(seed, steady=False, quiet=False):
     return packets
 
 
-def impair(packets, seed):
+def impair(packets, seed, in_conf=IN_CONF, ticks=T, slots=K, restarts=((1, 12), (4, 20), (7, 28))):
     """-> (the impaired script, how often each kind was applied on a leg that is in a conference): packets swapped inside a tick,
-    sent twice, lost (the number is consumed, nothing arrives), delivered a tick late, and three senders that restart at a far number"""
+    sent twice, lost (the number is consumed, nothing arrives), delivered a tick late, and three senders that restart at a far number.
+    No leg ends up with more than `slots` packets in a tick."""
     rng = np.random.default_rng(seed)
     out = [[list(now) for now in tick] for tick in packets]
     kinds = dict.fromkeys(("swap", "dup", "loss", "late", "restart"), 0)
-    for g, since in ((1, 12), (4, 20), (7, 28)):
-        for t in range(since, T):
+    for g, since in restarts:
+        for t in range(since, ticks):
             out[t][g] = [((s + 20000) % 65536, pt, codes) for s, pt, codes in out[t][g]]
         kinds["restart"] += 1
-    for t in range(2, T - 1):
-        for g in IN_CONF:
+    for t in range(2, ticks - 1):
+        for g in in_conf:
             now, what = out[t][g], int(rng.integers(0, 12))
             if what == 0 and len(now) == 2:
                 now.reverse()
                 kinds["swap"] += 1
-            elif what == 1 and 1 <= len(now) <= 2:
+            elif what == 1 and 1 <= len(now) < slots:
                 now.insert(int(rng.integers(0, len(now) + 1)), now[int(rng.integers(0, len(now)))])
                 kinds["dup"] += 1
             elif what == 2 and now:
                 now.pop(int(rng.integers(0, len(now))))
                 kinds["loss"] += 1
-            elif what in (3, 4) and now and len(out[t + 1][g]) <= 2:
+            elif what in (3, 4) and now and len(out[t + 1][g]) < slots:
                 out[t + 1][g].insert(0, now.pop(0))  # of two, the first: the second is loaded before it comes
                 kinds["late"] += 1
     return out, kinds
 
 
-def rows_of(packets, seed=1):
+def rows_of(packets, seed=1, legs=G, ticks=T, slots=K):
     """the script as the handle takes it: datagram rows [T, G, K, 172] and what recvfrom returned [T, G, K]; now and then slot 1 is a
-    failed recvfrom between two datagrams, or the only datagram sits in slot 2"""
+    failed recvfrom between two datagrams, or the only datagram sits in slot 2 (with other slot counts: the slot in front of the last,
+    the last)"""
     rng = np.random.default_rng(seed)
-    pk, recv = np.full((T, G, K, 172), 0xEE, np.uint8), np.zeros((T, G, K), np.int32)
-    for t in range(T):
-        for g in range(G):
+    pk, recv = np.full((ticks, legs, slots, 172), 0xEE, np.uint8), np.zeros((ticks, legs, slots), np.int32)
+    for t in range(ticks):
+        for g in range(legs):
             now = packets[t][g]
-            assert len(now) <= K
-            slots = list(range(len(now)))
-            if len(now) < K and now and rng.integers(0, 4) == 0:
-                slots[-1] = K - 1
-                recv[t, g, K - 2] = -1
-            for k, (s, pt, codes) in zip(slots, now):
+            assert len(now) <= slots
+            at = list(range(len(now)))
+            if len(now) < slots and now and rng.integers(0, 4) == 0:
+                at[-1] = slots - 1
+                recv[t, g, slots - 2] = -1
+            for k, (s, pt, codes) in zip(at, now):
                 recv[t, g, k] = 172
                 pk[t, g, k, :12] = 0
                 pk[t, g, k, 0], pk[t, g, k, 1] = 0x80, 0x80 | pt
