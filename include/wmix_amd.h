@@ -1002,9 +1002,20 @@ wmx_pkgfifo *wmx_tick_fifo(wmx_tick *h);
  * (wmix_amd/csrc/fft_debug.hip lists the kinds: Ooura rdft 128 / 256 through the LDS executor, aec_rdft_128 through the LDS,
  * 16-lane-register and one-point-per-lane executors, the SPL fixed-point real FFT of orders 7 and 8). */
 int wmx_debug_fft(int kind, int n_batch, void *d_data, int32_t *d_aux, void *stream);
-/* Developer / test hook: the NS kernels' table-driven log (kind 0, x >= 1) and exp (kind 1) evaluated on the host from
- * the same source (wmix_amd/csrc/libm_dev.h), for sweeping against libm without a GPU. */
+/* Developer / test hook: the NS kernels' table-driven log (kind 0, x >= 1), exp (kind 1) and tanh (kind 2) evaluated on the host
+ * from the same source (wmix_amd/csrc/libm_dev.h), for sweeping against libm without a GPU. */
 int wmx_debug_ns_libm(int kind, const float *x, float *y, size_t n);
+/* ... and on the device (device pointers; synchronises `stream`), with the tables in LDS as the kernels hold them.  kind 0 .. 2 as
+ * above (arguments outside a routine's guard take the library routine behind it), 3: exp in double, rounded to float, 4:
+ * x / pow(a, b) in double, rounded to float (d_a, d_b are read for this kind only and may be NULL otherwise), 5: sqrtf. */
+int wmx_debug_ns_libm_device(int kind, const float *d_x, const float *d_a, const float *d_b, float *d_y, size_t n, void *stream);
+/* ... and the double that kinds 0 .. 2 hold before they round it to float (kind 2: of |x|), on the host and on the device; NaN for an
+ * argument outside the routine's guard.  Host and device run the same IEEE operations: the doubles are equal bit for bit. */
+int wmx_debug_ns_libm_dbl(int kind, const float *x, double *y, size_t n);
+int wmx_debug_ns_libm_dbl_device(int kind, const float *d_x, double *d_y, size_t n, void *stream);
+/* Developer / test hook: the library routines of the AEC kernels on the device (device pointers; synchronises `stream`).
+ * kind 0: log in double, rounded to float, 1: sqrtf. */
+int wmx_debug_aec_libm_device(int kind, const float *d_x, float *d_y, size_t n, void *stream);
 /* Developer / test hook: the float NS kernel's analysis window for L = 128 (8 kHz) or 256 (16 / 32 kHz) as its constants block holds
  * it, L floats to a HOST buffer; needs no device. */
 int wmx_debug_ns_window(int L, float *host_window);

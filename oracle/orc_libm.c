@@ -17,6 +17,25 @@ void orc_libm_tanh(const float *x, float *y, size_t n)
 {
     for (size_t i = 0; i < n; i++) y[i] = (float)tanh((double)x[i]);
 }
+/* the start-up pink-noise model, ns_core.c:1111-1153: `num / pow(base, exp)` on floats, which C evaluates in double and the assignment rounds */
+void orc_libm_div_pow(const float *num, const float *base, const float *e, float *y, size_t n)
+{
+    for (size_t i = 0; i < n; i++) y[i] = (float)((double)num[i] / pow((double)base[i], (double)e[i]));
+}
+/* the same three expressions BEFORE the rounding to float: how far each double lies from the nearest float rounding boundary decides
+ * whether another fp64 library, a few double ulps away, must round to the same float (tests/test_libm_gpu.py) */
+void orc_libm_log_dbl(const float *x, double *y, size_t n)
+{
+    for (size_t i = 0; i < n; i++) y[i] = log((double)x[i]);
+}
+void orc_libm_exp_dbl(const float *x, double *y, size_t n)
+{
+    for (size_t i = 0; i < n; i++) y[i] = exp((double)x[i]);
+}
+void orc_libm_div_pow_dbl(const float *num, const float *base, const float *e, double *y, size_t n)
+{
+    for (size_t i = 0; i < n; i++) y[i] = (double)num[i] / pow((double)base[i], (double)e[i]);
+}
 /* aec_core.c:278 calls the float routine powf directly */
 void orc_libm_powf(const float *x, const float *e, float *y, size_t n)
 {

@@ -21,26 +21,47 @@ def _product(wmx, kind, x):
     return y
 
 
-def test_log_sweep(wmx, oracle_port):
+def _log_arguments():
     """every argument class the NS produces: magn = |X| + 1 in [1, 1e8], 1 + 2 snr; dense next to 1 where log -> 0"""
     rng = np.random.default_rng(11)
-    x = np.concatenate([
+    return np.concatenate([
         1 + rng.random(3_000_000) * 1e-4, 1 + rng.random(3_000_000), np.exp(rng.random(6_000_000) * 18.5),
         np.float32(1) + np.arange(0, 4096, dtype=np.float32) * np.float32(2 ** -23),  # the first floats above 1
         2.0 ** np.arange(0, 40), np.array([1.0, 3.0e7, 3.3e38, np.inf, 0.5, 0.0, -1.0, np.nan]),  # last ones: fallback path
     ]).astype(np.float32)
+
+
+def _exp_arguments():
+    """exp(-logLrt), exp(lquantile), exp(flatness): [-120, 90] incl. float-denormal results, overflow, specials"""
+    rng = np.random.default_rng(12)
+    return np.concatenate([
+        rng.random(6_000_000) * -120, rng.random(4_000_000) * 40 - 10, rng.random(1_000_000) * 2e-3 - 1e-3,
+        np.arange(-110, 95, 0.25), np.array([0.0, -0.0, 88.72, 88.73, 100, 710, -710, -800, np.inf, -np.inf, np.nan]),
+    ]).astype(np.float32)
+
+
+def _tanh_arguments():
+    """the three indicator arguments width * (feature - threshold) of ns_core.c:700-731: a few units either side of 0,
+    dense next to 0 (tanh x ~ x) and in the saturating tail; plus the high-band gain argument and specials"""
+    rng = np.random.default_rng(14)
+    return np.concatenate([
+        rng.random(4_000_000) * 16 - 8, rng.random(2_000_000) * 60 - 30, (rng.random(2_000_000) * 2 - 1) * 1e-2,
+        (rng.random(1_000_000) * 2 - 1) * 1e-6, np.arange(-25, 25, 1 / 64), 10.0 ** np.arange(-40, 3, 0.5),
+        np.array([0.0, -0.0, 0.0054, 0.0055, 19.9, 20.0, 20.1, 88, -88, 1e30, -1e30, np.inf, -np.inf, np.nan]),
+    ]).astype(np.float32)
+
+
+def test_log_sweep(wmx, oracle_port):
+    """every argument class the NS produces (_log_arguments)"""
+    x = _log_arguments()
     with np.errstate(all="ignore"):
         got, want = _product(wmx, 0, x), _run(oracle_port.orc_libm_log, x)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
 def test_exp_sweep(wmx, oracle_port):
-    """exp(-logLrt), exp(lquantile), exp(flatness): [-120, 90] incl. float-denormal results, overflow, specials"""
-    rng = np.random.default_rng(12)
-    x = np.concatenate([
-        rng.random(6_000_000) * -120, rng.random(4_000_000) * 40 - 10, rng.random(1_000_000) * 2e-3 - 1e-3,
-        np.arange(-110, 95, 0.25), np.array([0.0, -0.0, 88.72, 88.73, 100, 710, -710, -800, np.inf, -np.inf, np.nan]),
-    ]).astype(np.float32)
+    """exp(-logLrt), exp(lquantile), exp(flatness) (_exp_arguments)"""
+    x = _exp_arguments()
     with np.errstate(all="ignore"):
         got, want = _product(wmx, 1, x), _run(oracle_port.orc_libm_exp, x)
     nan = np.isnan(want)
@@ -49,14 +70,8 @@ def test_exp_sweep(wmx, oracle_port):
 
 
 def test_tanh_sweep(wmx, oracle_port):
-    """the three indicator arguments width * (feature - threshold) of ns_core.c:700-731: a few units either side of 0,
-    dense next to 0 (tanh x ~ x) and in the saturating tail; plus the high-band gain argument and specials"""
-    rng = np.random.default_rng(14)
-    x = np.concatenate([
-        rng.random(4_000_000) * 16 - 8, rng.random(2_000_000) * 60 - 30, (rng.random(2_000_000) * 2 - 1) * 1e-2,
-        (rng.random(1_000_000) * 2 - 1) * 1e-6, np.arange(-25, 25, 1 / 64), 10.0 ** np.arange(-40, 3, 0.5),
-        np.array([0.0, -0.0, 0.0054, 0.0055, 19.9, 20.0, 20.1, 88, -88, 1e30, -1e30, np.inf, -np.inf, np.nan]),
-    ]).astype(np.float32)
+    """the NS's indicator and high-band gain arguments (_tanh_arguments)"""
+    x = _tanh_arguments()
     with np.errstate(all="ignore"):
         got, want = _product(wmx, 2, x), _run(oracle_port.orc_libm_tanh, x)
     nan = np.isnan(want)
@@ -122,3 +137,6 @@ def test_pow_sweep_on_the_device(wmx, cuda, oracle_port):
 
 def test_rejects_bad_arguments(wmx):
     assert wmx.wmx_debug_ns_libm(5, None, None, 0) == -10001
+    x, y = np.ones(2, np.float32), np.zeros(2, np.float64)
+    assert wmx.wmx_debug_ns_libm_dbl(3, x.ctypes.data, y.ctypes.data, 2) == -10001 and wmx.wmx_debug_ns_libm_dbl(0, None, y.ctypes.data, 2) == -10001
+    assert wmx.wmx_debug_ns_libm_dbl(0, x.ctypes.data, None, 2) == -10001

@@ -1992,7 +1992,8 @@ int wmx_aec_timing(wmx_aec *h, int *n_launches, double *far_ms, double *near_ms)
 }  // extern "C"
 
 // The same on the DEVICE (device pointers), through the kernel's own out-of-line aec_powf: what the vector ALU's fused
-// multiply-adds, conversions and subnormals make of the routine, swept against the host's powf by tests/test_libm_gpu.py.
+// multiply-adds, conversions and subnormals make of the routine, swept against the host's powf by
+// test_pow_sweep_on_the_device (tests/test_libm_tables.py); tests/test_libm_gpu.py sweeps the other routines the same way.
 namespace wmx {
 namespace {
 __global__ void dbg_pow_kernel(const float *__restrict__ x, const float *__restrict__ e, float *__restrict__ y, size_t n,
@@ -2019,6 +2020,29 @@ extern "C" int wmx_debug_pow_device(const float *d_x, const float *d_e, float *d
     if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
     (void)hipFree(d_tab);
     return e == hipSuccess ? 0 : hip_fail(e, "wmx_debug_pow_device", __FILE__, __LINE__);
+}
+
+// The two library routines the AEC kernels call besides powf, on the DEVICE (device pointers) and compiled with this file's flags:
+// kind 0: log_d(x), ocml's fp64 log rounded to float, which sets overDrive from hNlFbMin; kind 1: sqrtf(x).  Swept against glibc's
+// log and the correctly rounded square root by tests/test_libm_gpu.py.
+namespace wmx {
+namespace {
+__global__ __launch_bounds__(256) void dbg_aec_libm_kernel(int kind, const float *__restrict__ x, float *__restrict__ y, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        y[i] = kind == 0 ? log_d(x[i]) : sqrtf(x[i]);
+}
+}  // namespace
+}  // namespace wmx
+
+extern "C" int wmx_debug_aec_libm_device(int kind, const float *d_x, float *d_y, size_t n, void *stream) {
+    using namespace wmx;
+    if (!d_x || !d_y || kind < 0 || kind > 1) return WMX_EINVAL;
+    if (n == 0) return 0;
+    if (current_device() < 0) return WMX_ENODEV;
+    hipLaunchKernelGGL(dbg_aec_libm_kernel, dim3(stream_grid(n, 256)), dim3(256), 0, as_stream(stream), kind, d_x, d_y, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "wmx_debug_aec_libm_device", __FILE__, __LINE__);
 }
 
 // Host-side evaluation of the AEC's table-driven powf (libm_dev.h), same source as the kernel, for CPU sweeps against

@@ -12,9 +12,6 @@
 namespace wmx {
 
 __device__ __noinline__ static float log_d(float x) { return (float)log((double)x); }
-// tanh of a promoted float, rounded back (ns_core.c:700,1321); out of line so that its fp64 coefficients are not hoisted
-// out of the callers' packet loops and held (or spilled) there
-__device__ __noinline__ static float tanh_d(float x) { return (float)tanh((double)x); }
 // the start-up pink-noise model (ns_core.c:1111-1153, first 50 blocks only): exp and x / pow(b, e) in double, rounded back
 __device__ __noinline__ static float exp_d(float x) { return (float)exp((double)x); }
 __device__ __noinline__ static float div_pow_d(float num, float base, float e) { return (float)((double)num / pow((double)base, (double)e)); }
@@ -116,8 +113,11 @@ inline void ns_libm_tables(NsLibmTables *t) {
     }
 }
 
-__host__ __device__ __forceinline__ float fast_log_ge1(float x, const NsLibmTables &M) {
-    if (!(x >= 1.0f && x < 3.0e38f)) return slow_log(x);  // never taken on the NS's arguments (|X| + 1, 1 + 2 snr)
+// Each routine is a `_dbl` core, which returns the double BEFORE the rounding to float and is defined inside the routine's guard
+// only, and the routine itself: guard, core, rounding.  The kernels call the routines; the cores exist by themselves so that a
+// device sweep can compare that double with the host's, bit for bit (tests/test_libm_gpu.py): an error of an ulp of double -- a
+// table entry that is off, say -- moves the FLOAT in one argument of 2^28 and no sweep of floats finds it.
+__host__ __device__ __forceinline__ double fast_log_ge1_dbl(float x, const NsLibmTables &M) {  // 1 <= x < 3e38
     unsigned u;
     __builtin_memcpy(&u, &x, 4);
     const int e = (int)(u >> 23) - 127;
@@ -138,12 +138,14 @@ __host__ __device__ __forceinline__ float fast_log_ge1(float x, const NsLibmTabl
     p = p * r;  // log1p(r) = r - r^2/2 + ... + r^9/9
     const double ed = (double)e;
     constexpr double kLn2Hi = 0x1.62e42fefa38p-1, kLn2Lo = 0x1.ef35793c7673p-45;  // ln2 split: e * hi is exact for |e| < 2^11
-    return (float)(fma(ed, kLn2Hi, t.y) + fma(ed, kLn2Lo, p));
+    return fma(ed, kLn2Hi, t.y) + fma(ed, kLn2Lo, p);
+}
+__host__ __device__ __forceinline__ float fast_log_ge1(float x, const NsLibmTables &M) {
+    if (!(x >= 1.0f && x < 3.0e38f)) return slow_log(x);  // never taken on the NS's arguments (|X| + 1, 1 + 2 snr)
+    return (float)fast_log_ge1_dbl(x, M);
 }
 
-__host__ __device__ __forceinline__ float fast_exp(float xf, const NsLibmTables &M) {
-    const double x = (double)xf;
-    if (!(x > -700.0 && x < 700.0)) return slow_exp(xf);  // overflow / deep underflow / NaN: the library routine
+__host__ __device__ __forceinline__ double fast_exp_dbl(double x, const NsLibmTables &M) {  // -700 < x < 700
     constexpr double kInv = 0x1.71547652b82fep+6;                                   // 64 / ln2
     constexpr double kHi = 0x1.62e42fefa0000p-7, kLo = 0x1.cf79abc9e3b3ap-46;       // ln2 / 64, kHi * k exact for |k| < 2^21
     const double kd = rint(x * kInv);
@@ -164,15 +166,15 @@ __host__ __device__ __forceinline__ float fast_exp(float xf, const NsLibmTables 
     bits += (long long)(k >> 6) << 52;
     double z;
     __builtin_memcpy(&z, &bits, 8);
-    return (float)z;
+    return z;
+}
+__host__ __device__ __forceinline__ float fast_exp(float xf, const NsLibmTables &M) {
+    const double x = (double)xf;
+    if (!(x > -700.0 && x < 700.0)) return slow_exp(xf);  // overflow / deep underflow / NaN: the library routine
+    return (float)fast_exp_dbl(x, M);
 }
 
-__host__ __device__ __forceinline__ float fast_tanh(float xf, const NsLibmTables &M) {
-    const double a2 = 2.0 * fabs((double)xf);
-    if (!(a2 < 40.0)) {
-        if (a2 != a2) return xf + xf;  // NaN in, (quiet) NaN out, like the library routine
-        return xf < 0.f ? -1.0f : 1.0f;
-    }
+__host__ __device__ __forceinline__ double fast_tanh_dbl(double a2, const NsLibmTables &M) {  // tanh(a2 / 2), 0 <= a2 < 40
     constexpr double kInv = 0x1.71547652b82fep+6;                              // 64 / ln2
     constexpr double kHi = 0x1.62e42fefa0000p-7, kLo = 0x1.cf79abc9e3b3ap-46;  // ln2 / 64 in two parts
     const double kd = rint(a2 * kInv);
@@ -198,7 +200,15 @@ __host__ __device__ __forceinline__ float fast_tanh(float xf, const NsLibmTables
         __builtin_memcpy(&z, &bits, 8);
         E = z - 1.0;
     }
-    const double th = E / (E + 2.0);
+    return E / (E + 2.0);
+}
+__host__ __device__ __forceinline__ float fast_tanh(float xf, const NsLibmTables &M) {
+    const double a2 = 2.0 * fabs((double)xf);
+    if (!(a2 < 40.0)) {
+        if (a2 != a2) return xf + xf;  // NaN in, (quiet) NaN out, like the library routine
+        return xf < 0.f ? -1.0f : 1.0f;
+    }
+    const double th = fast_tanh_dbl(a2, M);
     return copysignf((float)th, xf);
 }
 

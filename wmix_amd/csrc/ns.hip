@@ -1188,7 +1188,20 @@ extern "C" int wmx_debug_div_host(const float *a, const float *b, float *q, size
     return 0;
 }
 
-// Host-side evaluation of the NS's table-driven log / exp (libm_dev.h) -- the same source the kernels compile, run on
+// The double a table-driven routine holds BEFORE its rounding to float (libm_dev.h, the `_dbl` cores), kind 0: log, 1: exp, 2: tanh of
+// |x|; NaN for an argument outside the routine's guard, where the routine does not get that far.  One function for host and device.
+namespace wmx {
+namespace {
+__host__ __device__ __forceinline__ double ns_libm_dbl(int kind, float x, const NsLibmTables &M) {
+    const double d = (double)x, a2 = 2.0 * fabs(d), none = __builtin_nan("");
+    if (kind == 0) return x >= 1.0f && x < 3.0e38f ? fast_log_ge1_dbl(x, M) : none;
+    if (kind == 1) return d > -700.0 && d < 700.0 ? fast_exp_dbl(d, M) : none;
+    return a2 < 40.0 ? fast_tanh_dbl(a2, M) : none;
+}
+}  // namespace
+}  // namespace wmx
+
+// Host-side evaluation of the NS's table-driven log / exp / tanh (libm_dev.h) -- the same source the kernels compile, run on
 // the CPU so that the `-m "not gpu"` tests can sweep millions of arguments against glibc.  kind 0: log (x >= 1), 1: exp, 2: tanh.
 extern "C" int wmx_debug_ns_libm(int kind, const float *x, float *y, size_t n) {
     static wmx::NsLibmTables tab;
@@ -1201,6 +1214,98 @@ extern "C" int wmx_debug_ns_libm(int kind, const float *x, float *y, size_t n) {
     for (size_t i = 0; i < n; i++)
         y[i] = kind == 0 ? wmx::fast_log_ge1(x[i], tab) : (kind == 1 ? wmx::fast_exp(x[i], tab) : wmx::fast_tanh(x[i], tab));
     return 0;
+}
+// ... and the double before the rounding (ns_libm_dbl above)
+extern "C" int wmx_debug_ns_libm_dbl(int kind, const float *x, double *y, size_t n) {
+    static wmx::NsLibmTables tab;
+    static bool init = false;
+    if (!init) {
+        wmx::ns_libm_tables(&tab);
+        init = true;
+    }
+    if (!x || !y || kind < 0 || kind > 2) return WMX_EINVAL;
+    for (size_t i = 0; i < n; i++) y[i] = wmx::ns_libm_dbl(kind, x[i], tab);
+    return 0;
+}
+
+// The same routines on the DEVICE (device pointers), called the way ns_kernel calls them: the tables copied into LDS first and read
+// through a reference to that copy, fma_c as the inline v_fma_f64, the fp64 conversions, the division and the float-subnormal
+// results as the compiler emits them for gfx950 -- and, behind them, ocml's fp64 log / exp / pow and the fp32 sqrt.  Swept against the
+// host evaluation above and against glibc by tests/test_libm_gpu.py.  kind 0: fast_log_ge1(x), 1: fast_exp(x), 2: tanh_call(x),
+// 3: exp_d(x), 4: div_pow_d(x, a, b), 5: sqrtf(x); arguments outside the guards of 0 .. 2 take slow_log / slow_exp = log_d / exp_d.
+// The occupancy attributes are ns_kernel's own: the compiler hands a kernel's register budget down to the out-of-line routines it
+// calls (log_d, exp_d, div_pow_d, tanh_call), as the widest range over all their callers; a caller with another budget would have
+// them -- and with them the production kernels -- compiled differently (tools_dev/kernel_meta.py shows it).
+namespace wmx {
+namespace {
+__global__ __launch_bounds__(64 * kNsWavesPerBlock) __attribute__((amdgpu_waves_per_eu(NsOcc<128>::kWaves, NsOcc<128>::kWaves))) void dbg_ns_libm_kernel(int kind, const float *__restrict__ x, const float *__restrict__ a,
+                                                          const float *__restrict__ b, float *__restrict__ y, size_t n,
+                                                          const float *__restrict__ tab) {
+    __shared__ NsLibmTables lm;
+    {
+        float *dst = reinterpret_cast<float *>(&lm);
+        for (int i = threadIdx.x; i < kNsLibmWords; i += blockDim.x) dst[i] = tab[i];
+    }
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float v = x[i];
+        float r;
+        switch (kind) {
+            case 0: r = fast_log_ge1(v, lm); break;
+            case 1: r = fast_exp(v, lm); break;
+            case 2: r = tanh_call(v, &lm); break;
+            case 3: r = exp_d(v); break;
+            case 4: r = div_pow_d(v, a[i], b[i]); break;
+            default: r = sqrtf(v); break;
+        }
+        y[i] = r;
+    }
+}
+// kinds 0 .. 2 before their rounding to float (ns_libm_dbl), same tables in LDS, same occupancy attributes
+__global__ __launch_bounds__(64 * kNsWavesPerBlock) __attribute__((amdgpu_waves_per_eu(NsOcc<128>::kWaves, NsOcc<128>::kWaves))) void dbg_ns_libm_dbl_kernel(
+    int kind, const float *__restrict__ x, double *__restrict__ y, size_t n, const float *__restrict__ tab) {
+    __shared__ NsLibmTables lm;
+    {
+        float *dst = reinterpret_cast<float *>(&lm);
+        for (int i = threadIdx.x; i < kNsLibmWords; i += blockDim.x) dst[i] = tab[i];
+    }
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = ns_libm_dbl(kind, x[i], lm);
+}
+// the tables on the device, the launch, the wait: what the two hooks below share
+template <typename Launch>
+int with_device_tables(void *stream, const char *who, Launch launch) {
+    if (current_device() < 0) return WMX_ENODEV;
+    NsLibmTables tab;
+    ns_libm_tables(&tab);
+    float *d_tab = nullptr;
+    WMX_HIP(hipMalloc(reinterpret_cast<void **>(&d_tab), sizeof(tab)));
+    hipError_t e = hipMemcpy(d_tab, &tab, sizeof(tab), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch(d_tab);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    (void)hipFree(d_tab);
+    return e == hipSuccess ? 0 : hip_fail(e, who, __FILE__, __LINE__);
+}
+}  // namespace
+}  // namespace wmx
+extern "C" int wmx_debug_ns_libm_device(int kind, const float *d_x, const float *d_a, const float *d_b, float *d_y, size_t n, void *stream) {
+    using namespace wmx;
+    if (!d_x || !d_y || kind < 0 || kind > 5 || (kind == 4 && (!d_a || !d_b))) return WMX_EINVAL;
+    if (n == 0) return 0;
+    return with_device_tables(stream, "wmx_debug_ns_libm_device", [&](const float *d_tab) {
+        hipLaunchKernelGGL(dbg_ns_libm_kernel, dim3(stream_grid(n, 256)), dim3(64 * kNsWavesPerBlock), 0, as_stream(stream), kind, d_x, d_a, d_b, d_y, n, d_tab);
+    });
+}
+extern "C" int wmx_debug_ns_libm_dbl_device(int kind, const float *d_x, double *d_y, size_t n, void *stream) {
+    using namespace wmx;
+    if (!d_x || !d_y || kind < 0 || kind > 2) return WMX_EINVAL;
+    if (n == 0) return 0;
+    return with_device_tables(stream, "wmx_debug_ns_libm_dbl_device", [&](const float *d_tab) {
+        hipLaunchKernelGGL(dbg_ns_libm_dbl_kernel, dim3(stream_grid(n, 256)), dim3(64 * kNsWavesPerBlock), 0, as_stream(stream), kind, d_x, d_y, n, d_tab);
+    });
 }
 
 // The analysis window as the kernels hold it (the constants block wmx_ns_create uploads), on the host and without a device: L = 128
