@@ -1,7 +1,7 @@
 /* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
- *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N]
+ *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -20,6 +20,9 @@
  * --ulaw-every N: every N-th leg (N - 1, 2 N - 1, ...) negotiated PCMU: its G.711 datagrams carry payload type 0, it is decoded as
  * mu-law and answered in mu-law (wmx_conf_set_codecs: WMX_CODEC_PCMU, WMX_LAW_U); the other legs stay at the default.  The JSON line
  * then also carries the number of such legs and the refused counters summed over the legs (wmx_conf_export_codecs).
+ * --dtmf: the handle listens to every leg's keypad with suppression on (wmx_conf_dtmf, event payload type 101); leg 0 presses `5` in
+ * band for 100 ms and leg 1 sends `#` as RFC 4733 packets (ticks 5 .. 9), and the JSON line also carries the keys read back
+ * (wmx_conf_export_dtmf): per report the leg, the key and whether it came from a packet.
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -28,6 +31,7 @@
 #include <string.h>
 #include <time.h>
 #include "wmix_amd.h"
+#include "wmix_compat.h" /* linear2alaw / linear2ulaw for the key pressed in band */
 
 #define RTP_SLOTS 3
 #define RTP_BYTES 172
@@ -77,10 +81,51 @@ static int parse_sizes(const char *sizes, int32_t **off_out, int32_t **members_o
 /* one tick of the network into a slot's rows */
 static int audio_only, ulaw_every; /* ulaw_every 0: no leg negotiated PCMU */
 static int is_ulaw_leg(int g) { return ulaw_every > 0 && g % ulaw_every == ulaw_every - 1; }
-static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) {
+/* --dtmf: in the ticks DTMF_FROM .. DTMF_FROM + DTMF_PACKETS - 1 leg 0 presses the key `5` in band -- 770 Hz + 1336 Hz, each sine the
+ * integer oscillator y[n] = ((c y[n-1]) >> 14) - y[n-2] with c = 2 cos w and y[0] = 4000 sin w in Q14, carried from packet to packet --
+ * and leg 1 sends the key `#` as RFC 4733 packets of payload type 101: one timestamp, the last with the end bit.  What the script
+ * had drawn for these legs in these ticks is replaced; every other leg's script is as without the flag. */
+#define DTMF_FROM 5
+#define DTMF_PACKETS 5
+#define DTMF_EVENT_PT 101
+static int dtmf;
+static int32_t osc[2][2] = {{0, -((4000 * 9315) >> 14)}, {0, -((4000 * 14206) >> 14)}}; /* y[n-1], y[n-2] */
+static void dtmf_packets(uint8_t *pk0, int32_t *rv, int g, int t, uint16_t *seq) {
+    static const int32_t coef[2] = {26956, 16325};
+    rv[0] = RTP_BYTES, rv[1] = rv[2] = 0;
+    memset(pk0, 0, RTP_BYTES);
+    pk0[0] = 2u << 6;
+    pk0[2] = (uint8_t)(*seq >> 8), pk0[3] = (uint8_t)*seq;
+    (*seq)++;
+    if (g == 0) {
+        pk0[1] = (uint8_t)(0x80 | (is_ulaw_leg(0) ? 0 : 8));
+        for (int i = 0; i < 160; i++) {
+            int32_t v = 0;
+            for (int f = 0; f < 2; f++) {
+                const int32_t y = (int32_t)(((int64_t)coef[f] * osc[f][0]) >> 14) - osc[f][1];
+                osc[f][1] = osc[f][0], osc[f][0] = y;
+                v += y;
+            }
+            pk0[12 + i] = is_ulaw_leg(0) ? linear2ulaw(v) : linear2alaw(v);
+        }
+    } else {
+        const uint32_t ts = 160u * DTMF_FROM, duration = 160u * (uint32_t)(t - DTMF_FROM + 1);
+        const int last = t == DTMF_FROM + DTMF_PACKETS - 1;
+        pk0[1] = (uint8_t)((t == DTMF_FROM ? 0x80 : 0) | DTMF_EVENT_PT);
+        pk0[4] = (uint8_t)(ts >> 24), pk0[5] = (uint8_t)(ts >> 16), pk0[6] = (uint8_t)(ts >> 8), pk0[7] = (uint8_t)ts;
+        pk0[12] = 11; /* `#` */
+        pk0[13] = (uint8_t)((last ? 0x80 : 0) | 10);
+        pk0[14] = (uint8_t)(duration >> 8), pk0[15] = (uint8_t)duration;
+        rv[0] = 16;
+    }
+}
+
+static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G, int t) {
     long arrived = 0;
     memset(in, 0xEE, (size_t)G * RTP_SLOTS * row);
     for (int g = 0; g < G; g++) {
+        const uint16_t seq_was = seq[g];
+        const long arrived_was = arrived;
         const uint32_t u = lcg_next() % 8;
         int32_t *rv = recv + (size_t)g * RTP_SLOTS;
         rv[0] = u >= 2 ? RTP_BYTES : 0;
@@ -98,13 +143,18 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G) 
             for (int i = 0; i < 160; i++) pk[12 + i] = (uint8_t)(lcg_next() & 255);
             arrived++;
         }
+        if (dtmf && g < 2 && t >= DTMF_FROM && t < DTMF_FROM + DTMF_PACKETS) {
+            seq[g] = seq_was;
+            dtmf_packets(in + (size_t)g * RTP_SLOTS * row, rv, g, t, &seq[g]);
+            arrived = arrived_was + 1;
+        }
     }
     return arrived;
 }
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
-                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N]\n";
+                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -128,6 +178,8 @@ int main(int argc, char **argv) {
             if (max_gap < 0) max_gap = WMX_MIX_MAX_LEG_PACKETS; /* not a gap: the library says so */
         } else if (!strcmp(argv[i], "--conceal")) {
             conceal = 1;
+        } else if (!strcmp(argv[i], "--dtmf")) {
+            dtmf = 1;
         } else if (!strcmp(argv[i], "--audio-only")) {
             audio_only = 1;
         } else if (!strcmp(argv[i], "--ulaw-every") && i + 1 < argc) {
@@ -174,6 +226,7 @@ int main(int argc, char **argv) {
     if (speakers) WMX_OK(wmx_conf_speakers(h, max_speakers, (uint32_t)floor_level, shift));
     if (max_gap >= 0) WMX_OK(wmx_conf_sequence(h, 1, max_gap));
     if (conceal) WMX_OK(wmx_conf_conceal(h, 1));
+    if (dtmf) WMX_OK(wmx_conf_dtmf(h, 1, 1, DTMF_EVENT_PT));
     int n_ulaw = 0;
     for (int g = 0; g < G; g++) {
         const int32_t leg = g;
@@ -198,7 +251,7 @@ int main(int argc, char **argv) {
             tick_of[k] = -1;                                                                                    \
         }                                                                                                       \
     } while (0)
-    arrived += arrivals(wmx_conf_in(h, 0), wmx_conf_recv(h, 0), row, seq, G);
+    arrived += arrivals(wmx_conf_in(h, 0), wmx_conf_recv(h, 0), row, seq, G, 0);
     for (int t = 0; t < T; t++) {
         int k = -1;
         WMX_OK(wmx_conf_submit(h, &k, NULL));
@@ -206,7 +259,7 @@ int main(int argc, char **argv) {
         if (t + 1 < T) { /* the network of tick t + 1 while tick t is in flight; that slot's own earlier tick has to have left first */
             const int nk = wmx_conf_next_slot(h);
             COLLECT(nk);
-            arrived += arrivals(wmx_conf_in(h, nk), wmx_conf_recv(h, nk), row, seq, G);
+            arrived += arrivals(wmx_conf_in(h, nk), wmx_conf_recv(h, nk), row, seq, G, t + 1);
         }
     }
     for (int k = 0; k < slots; k++) COLLECT(k);
@@ -241,6 +294,14 @@ int main(int argc, char **argv) {
         for (int g = 0; g < G; g++) n_refused += refused[g];
         free(refused);
     }
+    uint32_t *key_count = NULL; /* --dtmf: count and ring of every leg */
+    uint8_t *key_ring = NULL;
+    if (dtmf) {
+        key_count = calloc((size_t)G, sizeof(uint32_t));
+        key_ring = calloc((size_t)G, 8);
+        if (!key_count || !key_ring) return 2;
+        WMX_OK(wmx_conf_export_dtmf(h, key_count, key_ring, NULL));
+    }
     uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
@@ -255,6 +316,16 @@ int main(int argc, char **argv) {
                seq_sum[2], seq_sum[3], seq_sum[4]);
     if (conceal) printf("\"conceal\": 1, \"concealed\": %lu, ", n_concealed);
     if (ulaw_every > 0) printf("\"ulaw_every\": %d, \"ulaw_legs\": %d, \"refused\": %lu, ", ulaw_every, n_ulaw, n_refused);
+    if (dtmf) {
+        printf("\"dtmf\": 1, \"dtmf_keys\": [");
+        int first = 1;
+        for (int g = 0; g < G; g++)
+            for (uint32_t n = key_count[g] > 8 ? key_count[g] - 8 : 0; n < key_count[g]; n++, first = 0) {
+                const uint8_t b = key_ring[(size_t)g * 8 + (n & 7)];
+                printf("%s{\"leg\": %d, \"key\": \"%c\", \"packet\": %d}", first ? "" : ", ", g, "0123456789*#ABCD"[b & 15], b >> 7);
+            }
+        printf("], ");
+    }
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

@@ -684,6 +684,45 @@ int wmx_rtp_conceal_legs(wmx_rtp *h, int max_packets, const int16_t *d_pcm, long
                          const uint32_t *d_len, const uint32_t *d_calls, int16_t *d_pcm_out, uint32_t *d_len_out, void *stream);
 int wmx_rtp_reset_conceal(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
 int wmx_rtp_export_conceal(wmx_rtp *h, int16_t *hist, uint32_t *concealed, void *stream);
+/* DTMF per leg, heard in band and read from RFC 4733 telephone-event packets, between wmx_rtp_ingest_legs_codecs (and
+ * wmx_rtp_sequence_legs) and the selection / the load (wmix_amd/csrc/leg_dtmf.h holds the rule).  The reference has no counterpart: a
+ * key pressed in band is mixed as loud voice and an event packet is an unknown payload type.  Here the handle keeps, per leg (its
+ * n_streams) and ON THE DEVICE, the debounce state, the last event timestamp, a counter `count` and ring[8], and one launch judges
+ * every block of every leg.  Integer arithmetic.
+ *   DIGIT CODES are the RFC 4733 event numbers: 0 .. 9 the keys 0 .. 9, 10 `*`, 11 `#`, 12 .. 15 A .. D; keypad (row r, column c) is
+ *   code {1,2,3,12, 4,5,6,13, 7,8,9,14, 10,0,11,15}[4 r + c].
+ *   A BLOCK is the 160 samples of one data call (d_len == 320).  For f = 697, 770, 852, 941 (rows), 1209, 1336, 1477, 1633 (columns),
+ *   coef = 27980, 26956, 25701, 24219, 19073, 16325, 13085, 9315: from s1 = s2 = 0, s0 = x[n] + ((coef * s1) >> 14) - s2; s2 = s1;
+ *   s1 = s0 over n = 0 .. 159, then P = s1 * s1 + s2 * s2 - ((coef * s1) >> 14) * s2 (int64).  E = sum of x[n]^2; r*, c* the row and the
+ *   column with the largest P, ties to the lower index.  The block is a TONE of the digit at (r*, c*) when P_r* >= 400000000 and P_c* >=
+ *   400000000, P_c* <= 4 P_r* and P_r* <= 8 P_c*, 8 P_i <= P_r* for every other row and 8 P_i <= P_c* for every other column, and
+ *   P_r* + P_c* >= 32 E.
+ *   The leg's blocks are taken in the order the load makes its calls: d_calls NULL, the slots with d_len == 320 in slot order; else
+ *   the list d_calls[r] as wmx_rtp_sequence_legs leaves it, where a silence call, or a data call that names a row that is not readable,
+ *   is a block that is not a tone.  A leg with no block keeps its state.
+ *   DEBOUNCE: cand = the previous block's digit or none, cur = the digit that is down or none.  A tone of d with cand == d and cur != d
+ *   reports d once and sets cur = d; a block that is not a tone behind one that was not a tone either sets cur = none; then cand = this
+ *   block's digit or none.  A key fills two consecutive packets before it is reported.
+ *   EVENT PACKETS are read from the datagram rows (d_in, d_recv: what wmx_rtp_ingest_legs_codecs was given), whatever the list says:
+ *   every slot in slot order with d_recv >= 16, (byte 1 & 0x7F) == event_pt and event = byte 12 <= 15 reports `event` once when the leg
+ *   has no last event timestamp or bytes 4 .. 7 differ from it, and stores those four bytes: retransmissions and end packets of one key
+ *   press report nothing more.  Events above 15 are ignored.  The packet stays refused for the audio path.
+ *   REPORT: report number n (from 0) of a leg is ring[n & 7] = code | 0x80 from a packet, code heard in band; count counts them; a
+ *   tick's packet reports are stored before its in-band reports.  A host that polls at least every 8 reports reads every digit.
+ *   suppress != 0: every block that is a tone (its own decision, not the debounced one) is zeroed in d_pcm IN PLACE, d_len unchanged: a
+ *   data call of zeros for the selection, the concealment history and the load behind this stage.
+ * One launch (half a wave per leg); no atomics, no host synchronisation, no upload, no allocation after the first call
+ * (wmx_rtp_reset_dtmf counts as one).  OUT OF SCOPE: generating DTMF towards a leg, events above 15, a block other than the packet.
+ * WMX_EINVAL, nothing launched, state unchanged: a NULL pointer other than d_calls, max_packets outside 1 .. 4, event_pt outside
+ * 96 .. 127, rows that overlap (packet_stride < 172, pcm_packet_stride < 160, a leg stride shorter than its max_packets rows).
+ * wmx_rtp_reset_dtmf: the fresh state for the n legs host_idx lists (NULL = all), on `stream`.  A bad index: WMX_EINVAL, nothing reset.
+ * wmx_rtp_export_dtmf: count (n_streams uint32) and ring (n_streams x 8 uint8), either pointer NULL, as the work queued on `stream`
+ * leaves them; blocking. */
+int wmx_rtp_detect_dtmf_legs(wmx_rtp *h, int max_packets, const uint8_t *d_in, long leg_stride, long packet_stride,
+                             const int32_t *d_recv, int16_t *d_pcm, long source_stride, long pcm_packet_stride, const uint32_t *d_len,
+                             const uint32_t *d_calls, int event_pt, int suppress, void *stream);
+int wmx_rtp_reset_dtmf(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
+int wmx_rtp_export_dtmf(wmx_rtp *h, uint32_t *count, uint8_t *ring, void *stream);
 /* A G.711 codec per stream, as each call negotiated it (wmix_amd/csrc/leg_codec.h holds the rule).  The reference's receive thread
  * accepts payload types 8 and 0 alike and decodes both with G711a2PCM (src/rtp.c:88-95, src/wmixTask.c:1282), and a send thread has one
  * law.  Here the handle keeps, per stream and ON THE DEVICE, in_codec, out_law and a `refused` counter:
@@ -808,6 +847,13 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * concealment off the launches are those of a handle that never heard of it.  The repaired rows and the history are made the first time
  * it is switched on, never inside a submit.  wmx_conf_reset_legs also resets the listed legs' concealment state.
  * wmx_conf_export_conceal: concealed (uint32) of every leg (wmx_rtp_export_conceal); blocking.
+ * wmx_conf_dtmf(h, on, suppress, event_pt): between submits; off is the default.  On, wmx_rtp_detect_dtmf_legs runs behind the ingest
+ * (behind wmx_rtp_sequence_legs with sequencing on, on its call list) and in front of the selection: with suppress != 0 the selection,
+ * the concealment history and the load see a key pressed in band as a data call of zeros -- the other legs do not hear it and it wins
+ * no talker slot.  event_pt 96 .. 127 is the payload type the legs negotiated for telephone-event (101 in most offers); outside:
+ * WMX_EINVAL.  Off, the launches are those of a handle that never heard of it; the state is made the first time it is switched on,
+ * never inside a submit.  wmx_conf_reset_legs also resets the listed legs' DTMF state.  wmx_conf_export_dtmf: count (uint32) and ring
+ * (8 uint8) of every leg (wmx_rtp_export_dtmf), either pointer NULL; blocking.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -825,6 +871,8 @@ int wmx_conf_export_sequence(wmx_conf *h, uint16_t *next, uint8_t *synced, uint3
                              uint32_t *resync, uint32_t *overflow, void *stream);
 int wmx_conf_conceal(wmx_conf *h, int on);
 int wmx_conf_export_conceal(wmx_conf *h, uint32_t *concealed, void *stream);
+int wmx_conf_dtmf(wmx_conf *h, int on, int suppress, int event_pt);
+int wmx_conf_export_dtmf(wmx_conf *h, uint32_t *count, uint8_t *ring, void *stream);
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
 int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);

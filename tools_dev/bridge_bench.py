@@ -57,6 +57,9 @@ N out of the script on all sides alike -- the packet with sequence number s of l
 -- so that the sequencer makes silence calls and the concealment's run path is paid for; the sides with sequencing on then send other
 datagrams than those without, and only handle and resident step of a kind are compared.
     python tools_dev/bridge_bench.py --pipe --loss-every 50 --out profiles/bridge/bridge_conceal_bench.json
+And (j), (k): the handle and the resident step of (b), (c) with DTMF on and suppression on (wmx_conf_dtmf): (j) - (b), (k) - (c) are the
+detector's launch.  The script is noise: no block is a tone, no row is zeroed, no key is reported, the datagrams are those of (b).
+    python tools_dev/bridge_bench.py --pipe --ulaw-every 2 --out file.json    (profiles/bridge/bridge_dtmf_bench.json is made of such runs)
 --pipe --ulaw-every N adds (f), (g): the handle and the resident step again with a codec per leg (wmx_conf_set_codecs): every N-th leg is
 WMX_CODEC_PCMU in and mu-law out and its datagrams carry payload type 0, the other legs stay at the default; the launches are the per-leg
 ones for every leg.  (f) and (g) send the same datagrams, each leg in its own payload type, before any time is reported."""
@@ -442,6 +445,28 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
         new_cycle(ci, i)
         ci.step_resident(r_in[i], r_recv[i], i_out)
 
+    # (j), (k) the handle and the resident step of (b), (c) with DTMF on and suppression on: the script is noise, so no block is a tone, no
+    # row is zeroed and nothing is reported -- what a bridge pays per tick while nobody presses a key
+    cj = ConfBridge(legs, 3, 3)
+    ck = ConfBridge(legs, 1, 3)
+    for x in (cj, ck):
+        x.set_conferences(layout)
+        x.set_play_correct(0)
+        x.dtmf(True, suppress=True)
+    for k in range(3):
+        cj.rows_in[k][:] = pk[k]
+        cj.recv[k][:] = recv[k]
+    k_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+    step["k"] = 0
+
+    def handle_dtmf():
+        return cj.submit()
+
+    def resident_dtmf():
+        i = step["k"] % CYC
+        step["k"] += 1
+        ck.step_resident(r_in[i], r_recv[i], k_out)
+
     # (f), (g) the same two with a codec per leg: every ulaw_every-th leg on PCMU both ways, the others at the default
     mixed = ulaw_every > 0
     if mixed:
@@ -496,6 +521,10 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
             assert np.array_equal(a, d_rows), ("datagrams differ with sequencing on, tick", t)
             assert np.array_equal(a, h_rows), ("datagrams differ with concealment on, tick", t)
         assert (a[:, 12:] != 0xD5).any()
+        k = handle_dtmf()
+        cj.wait(k)
+        resident_dtmf()
+        assert np.array_equal(a, cj.rows_out[k]) and np.array_equal(a, k_out.cpu().numpy()), ("datagrams differ with DTMF on, tick", t)
 
     def wall(f, n, end):
         t0 = time.perf_counter()
@@ -505,7 +534,7 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
         return (time.perf_counter() - t0) * 1e3 / n
 
     per_block = max(reps // BLOCKS, 8)
-    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": [], "h": [], "i": []}
+    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": [], "h": [], "i": [], "j": [], "k": []}
     for _ in range(BLOCKS + 1):  # the first block warms up
         ms["a"].append(wall(parent, per_block, torch.cuda.synchronize))
         ms["b"].append(wall(handle, per_block, lambda: cb.wait(-1)))
@@ -514,6 +543,8 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
         ms["e"].append(wall(resident_seq, per_block, torch.cuda.synchronize))
         ms["h"].append(wall(handle_plc, per_block, lambda: ch.wait(-1)))
         ms["i"].append(wall(resident_plc, per_block, torch.cuda.synchronize))
+        ms["j"].append(wall(handle_dtmf, per_block, lambda: cj.wait(-1)))
+        ms["k"].append(wall(resident_dtmf, per_block, torch.cuda.synchronize))
         if mixed:
             ms["f"].append(wall(handle_mixed, per_block, lambda: cf.wait(-1)))
             ms["g"].append(wall(resident_mixed, per_block, torch.cuda.synchronize))
@@ -553,7 +584,13 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
                  "h_wmx_conf_3_slots_sequencing_and_concealment_on": h, "i_step_resident_sequencing_and_concealment_on": i,
                  "h_minus_d_ms": round(h["median_ms_per_tick"] - d["median_ms_per_tick"], 5),
                  "i_minus_e_ms": round(i["median_ms_per_tick"] - e["median_ms_per_tick"], 5), "concealed_of_h": concealed_h})
-    for x in (tk, snd, cb, cr, cs, ce, ch, ci, pair, fused, s2, s3):
+    j, k = side(ms["j"]), side(ms["k"])
+    keys_of_j = int(cj.export_dtmf()["count"].sum())
+    assert keys_of_j == 0, keys_of_j  # the script is noise
+    more.update({"j_wmx_conf_3_slots_dtmf_on": j, "k_step_resident_dtmf_on": k,
+                 "j_minus_b_ms": round(j["median_ms_per_tick"] - b["median_ms_per_tick"], 5),
+                 "k_minus_c_ms": round(k["median_ms_per_tick"] - c["median_ms_per_tick"], 5), "keys_reported_of_j": keys_of_j})
+    for x in (tk, snd, cb, cr, cs, ce, ch, ci, cj, ck, pair, fused, s2, s3):
         x.close()
     return {**more, "conferences": n_conf, "sizes": {str(k): sizes.count(k) for k in sorted(set(sizes))}, "legs": legs, "max_packets": 3,
             "packets_per_leg_and_tick": round(float((recv > 0).sum()) / (CYC * legs), 3), "ticks_per_block": per_block, "datagram_ticks_checked": 2 * CYC,

@@ -78,6 +78,18 @@ class ConfBridge:
         check(lib().wmx_conf_export_conceal(self._h, concealed.ctypes.data, self._stream()), "wmx_conf_export_conceal")
         return concealed
 
+    def dtmf(self, on, suppress=False, event_pt=101):
+        """listen to every leg's keypad, in band and in RFC 4733 packets of payload type event_pt (wmx_conf_dtmf), between submits;
+        suppress: a key pressed in band is not mixed and wins no talker slot; off (the default) = the launches of before"""
+        check(lib().wmx_conf_dtmf(self._h, 1 if on else 0, 1 if suppress else 0, event_pt), "wmx_conf_dtmf")
+
+    def export_dtmf(self):
+        """dict(count: uint32 [n_legs], the digits reported per leg; ring: uint8 [n_legs, 8], report n at ring[n & 7] -- the RFC 4733
+        event number 0 .. 15, bit 7 set when it came from a packet) as the work queued on the current stream leaves them"""
+        r = {"count": np.zeros(self.n_legs, np.uint32), "ring": np.zeros((self.n_legs, 8), np.uint8)}
+        check(lib().wmx_conf_export_dtmf(self._h, r["count"].ctypes.data, r["ring"].ctypes.data, self._stream()), "wmx_conf_export_dtmf")
+        return r
+
     def set_codecs(self, legs, in_codec, out_law):
         """a G.711 codec per leg, as each call negotiated it (wmx_conf_set_codecs), between submits: in_codec "reference" (the default:
         A-law whatever arrives), "pcma", "pcmu" or "by_pt" (or WMX_CODEC_* 0 .. 3), out_law "a" / "u"; legs None = every leg"""
@@ -99,7 +111,8 @@ class ConfBridge:
 
     def reset_legs(self, legs=None):
         """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-        refused = 0, the concealment history and count zero; the leg keeps its codec (None = every leg)"""
+        refused = 0, the concealment history and count zero, no key down and no digit reported; the leg keeps its codec (None = every
+        leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

@@ -45,6 +45,8 @@ struct wmx_conf {
     bool conceal_on;      // only with seq_on: wmx_rtp_conceal_legs between the selection and the load
     int16_t *d_rep;       // [n_legs][4][160] the repaired rows, made when concealment is first switched on
     uint32_t *d_rep_len;  // [n_legs][4], behind them
+    bool dtmf_on, dtmf_suppress, dtmf_made;  // wmx_rtp_detect_dtmf_legs in front of the selection; made: the senders hold its state
+    int dtmf_pt;
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -72,6 +74,11 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
     if (rc != 0) return rc;
     if (h->seq_on) {  // in front of the selection: it must not hear a late packet or a duplicate
         rc = wmx_rtp_sequence_legs(h->snd, K, h->max_gap, h->d_seq, h->d_len, h->d_calls, stream);
+        if (rc != 0) return rc;
+    }
+    if (h->dtmf_on) {  // in front of the selection: it and the load must see a suppressed row
+        rc = wmx_rtp_detect_dtmf_legs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len,
+                                      h->seq_on ? h->d_calls : nullptr, h->dtmf_pt, h->dtmf_suppress ? 1 : 0, stream);
         if (rc != 0) return rc;
     }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
@@ -276,6 +283,33 @@ int wmx_conf_export_conceal(wmx_conf *h, uint32_t *concealed, void *stream) {
     return wmx_rtp_export_conceal(h->snd, nullptr, concealed, stream);
 }
 
+// on != 0: every leg's keypad is listened to, in band and in RFC 4733 packets of payload type event_pt (wmx_rtp_detect_dtmf_legs);
+// suppress != 0: a block that is a tone goes on as zeros.  0 (the default): the launches of a handle that never heard of it.  Between
+// submits.  The state is made the first time it is switched on.
+int wmx_conf_dtmf(wmx_conf *h, int on, int suppress, int event_pt) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (event_pt < 96 || event_pt > 127) {
+        wmx::set_error("wmx_conf_dtmf: event_pt=%d must be 96 .. 127 (a dynamic payload type; 101 in most offers)", event_pt);
+        return WMX_EINVAL;
+    }
+    if (on && !h->dtmf_made) {
+        const int rc = wmx_rtp_reset_dtmf(h->snd, nullptr, 0, nullptr);
+        if (rc != 0) return rc;
+        h->dtmf_made = true;
+    }
+    h->dtmf_on = on != 0;
+    h->dtmf_suppress = suppress != 0;
+    h->dtmf_pt = event_pt;
+    return 0;
+}
+
+// count (uint32) and ring (8 uint8) of every leg (wmx_rtp_export_dtmf); blocking
+int wmx_conf_export_dtmf(wmx_conf *h, uint32_t *count, uint8_t *ring, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_export_dtmf(h->snd, count, ring, stream);
+}
+
 // a G.711 codec per leg (wmx_rtp_set_codecs over the legs; NULL = all): between submits, ordered on `stream`
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
     if (!h) return WMX_EINVAL;
@@ -291,7 +325,7 @@ int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uin
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
 
 // a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-// refused = 0, the concealment history and count zero; the leg keeps its codec
+// refused = 0, the concealment history and count zero, the DTMF state fresh; the leg keeps its codec
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
     // before the first of them: a bad index resets nothing
@@ -302,6 +336,7 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0) rc = wmx_rtp_reset_streams(h->snd, host_idx, n, stream);
     if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, host_idx, n, stream);
     if (rc == 0 && h->d_rep) rc = wmx_rtp_reset_conceal(h->snd, host_idx, n, stream);  // never switched on: no state to reset
+    if (rc == 0 && h->dtmf_made) rc = wmx_rtp_reset_dtmf(h->snd, host_idx, n, stream);  // a new call inherits no half key press
     return rc;
 }
 

@@ -14,6 +14,7 @@
 #include "leg_seq.h"
 #include "leg_plc.h"
 #include "leg_codec.h"
+#include "leg_dtmf.h"
 
 struct wmx_rtp {
     int device;  // the HIP device the state lives on (current device at create); every entry point switches to it
@@ -35,6 +36,10 @@ struct wmx_rtp {
     // behind it concealed (uint32)
     int16_t *d_plc_hist;
     uint32_t *d_plc_concealed;
+    // the DTMF rule's state per leg (leg_dtmf.h), made by the first call that needs it, one block: ring (8 bytes per leg, one uint64),
+    // behind it count, ts and flags (uint32 each)
+    uint64_t *d_dtmf_ring;
+    uint32_t *d_dtmf_count, *d_dtmf_ts, *d_dtmf_flags;
 };
 
 namespace wmx {
@@ -460,6 +465,112 @@ __global__ __launch_bounds__(64 * kPlcLegsPerBlock) void rtp_conceal_legs_kernel
     if (lane == 0) concealed[leg] += made;
 }
 
+// ---- the DTMF rule (leg_dtmf.h) for every leg: HALF A WAVE PER LEG, kDtmfLegsPerBlock legs per block; no lane waits for a lane of
+// another wave.  A leg's up to four blocks times eight frequencies are 32 chains, one per lane: lane l of the leg's 32 runs frequency
+// l & 7 over block l >> 3.  The leg's 32 lanes stage its readable rows into LDS pair by pair (WIDE: rows on 4-byte boundaries, one
+// 32-bit load per pair; otherwise two 16-bit ones), then every chain walks its row two samples per 32-bit LDS read: the eight lanes
+// of a block read one address (a broadcast), and rows are kDtmfLdsRow = 164 samples = 82 words apart, so the four blocks of a leg
+// stand on banks 0, 18, 4 and 22 -- no two on one.  Every lane also sums the energy of the row it walks.  The eight powers of a block
+// reach each of its lanes by cross-lane moves, each lane takes the header's decision, and the four decisions reach the leg's lanes
+// the same way.  With suppress the leg's lanes zero the rows of the blocks that are tones.  The leg's first lane then reads the event
+// packets' header bytes and walks the debounce over the decisions -- a short serial tail -- and stores the state it changed.  A lane
+// writes only its own leg's rows and state: no atomics.  Per block of legs 8 x 4 x 328 bytes of LDS.
+constexpr int kDtmfLegsPerBlock = 8;
+constexpr int kDtmfLdsRow = 164;
+constexpr int kDtmfPairs = kDtmfRow / 2;
+
+__device__ __forceinline__ int64_t dtmf_shfl64(int64_t v, int src) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v & 0xFFFFFFFFu), src, 64);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v >> 32), src, 64);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(32 * kDtmfLegsPerBlock) void rtp_detect_dtmf_legs_kernel(const uint8_t *__restrict__ packets, long leg_stride,
+                                                                                       long packet_stride, const int32_t *__restrict__ recv,
+                                                                                       int16_t *pcm, long source_stride, long pcm_packet_stride,
+                                                                                       const uint32_t *__restrict__ len,
+                                                                                       const uint32_t *__restrict__ calls_in, int max_packets,
+                                                                                       uint32_t event_pt, int suppress, uint64_t *ring,
+                                                                                       uint32_t *count, uint32_t *ts, uint32_t *flags, int n_legs) {
+    __shared__ __attribute__((aligned(16))) int16_t staged[kDtmfLegsPerBlock][kSeqMaxCalls][kDtmfLdsRow];
+    const int hl = (int)(threadIdx.x & 31u), half = (int)(threadIdx.x >> 5);
+    const int wave_lane = (int)(threadIdx.x & 63u);
+    const size_t leg = blockIdx.x * (size_t)kDtmfLegsPerBlock + (size_t)half;
+    const bool live = leg < (size_t)n_legs;
+    uint32_t list = 0, blocks = 0, quiet = (1u << kSeqMaxCalls) - 1u;  // quiet bit j: block j is none, or not to be read
+    if (live) {
+        uint32_t readable = 0;
+#pragma unroll
+        for (int k = 0; k < kSeqMaxCalls; k++)
+            if (k < max_packets) readable |= leg_plc_readable(len[leg * (size_t)max_packets + k]) << k;
+        list = leg_dtmf_list(calls_in != nullptr, calls_in ? calls_in[leg] : 0u, readable, max_packets);
+        blocks = leg_plc_count(list);
+        quiet = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++)
+            if (j >= blocks || leg_plc_silence(list, j, readable)) quiet |= 1u << j;
+    }
+    int16_t *rows = pcm + (live ? leg : 0) * (size_t)source_stride;
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++) {
+        if ((quiet >> j) & 1u) continue;
+        const int16_t *row = rows + leg_calls_slot(list, j) * pcm_packet_stride;
+        for (int p = hl; p < kDtmfPairs; p += 32) plc_store2<true>(staged[half][j], p, plc_load2<WIDE>(row, p));
+    }
+    plc_wave_sync();  // a leg's lanes are lanes of one wave
+
+    const int j = hl >> 3, f = hl & 7;
+    const bool mine = !((quiet >> j) & 1u);
+    int64_t power = 0, energy = 0;
+    if (mine) {
+        const int32_t coef = leg_dtmf_coef(f);
+        const int16_t *x = staged[half][j];
+        int32_t s1 = 0, s2 = 0;
+        for (int p = 0; p < kDtmfPairs; p++) {
+            const uint32_t v = plc_load2<true>(x, p);
+            const int32_t a = (int16_t)(v & 0xFFFFu), b = (int16_t)(v >> 16);
+            leg_dtmf_step(s1, s2, coef, a);
+            leg_dtmf_step(s1, s2, coef, b);
+            energy = leg_dtmf_energy(leg_dtmf_energy(energy, a), b);
+        }
+        power = leg_dtmf_power(s1, s2, coef);
+    }
+    int64_t p8[kDtmfFreqs];
+#pragma unroll
+    for (int i = 0; i < kDtmfFreqs; i++) p8[i] = dtmf_shfl64(power, (wave_lane & ~7) + i);
+    const int32_t digit = mine ? leg_dtmf_decide(p8, energy) : kDtmfNone;
+    int32_t d[kSeqMaxCalls];
+#pragma unroll
+    for (int i = 0; i < kSeqMaxCalls; i++) d[i] = __shfl(digit, (wave_lane & 32) + 8 * i, 64);
+
+    if (suppress) {
+#pragma unroll
+        for (uint32_t i = 0; i < (uint32_t)kSeqMaxCalls; i++) {
+            if (d[i] == kDtmfNone) continue;  // a tone: the leg is live and the block has a row
+            int16_t *row = rows + leg_calls_slot(list, i) * pcm_packet_stride;
+            for (int p = hl; p < kDtmfPairs; p += 32) plc_store2<WIDE>(row, p, 0u);
+        }
+    }
+    if (!live || hl != 0) return;
+    LegDtmfState st{count[leg], ring[leg], ts[leg], flags[leg]};
+    const LegDtmfState was = st;
+#pragma unroll
+    for (int k = 0; k < kSeqMaxCalls; k++) {
+        if (k >= max_packets) continue;
+        const int32_t got = recv[leg * (size_t)max_packets + k];
+        if (got < (int32_t)kDtmfMinEventBytes) continue;  // the row is read only where enough arrived
+        const uint8_t *pkt = packets + leg * (size_t)leg_stride + (size_t)k * packet_stride;
+        leg_dtmf_packet(st, got, pkt[1], pkt[12], leg_dtmf_word(pkt + 4), event_pt);
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < (uint32_t)kSeqMaxCalls; i++)
+        if (i < blocks) leg_dtmf_debounce(st, d[i]);
+    if (st.count != was.count) count[leg] = st.count, ring[leg] = st.ring;
+    if (st.ts != was.ts) ts[leg] = st.ts;
+    if (st.flags != was.flags) flags[leg] = st.flags;
+}
+
 inline bool aligned_to(const void *p, long stride_bytes, int a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0 && stride_bytes % a == 0; }
 
 }  // namespace
@@ -493,6 +604,8 @@ int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
     h->codecs_default = true;
     h->d_plc_hist = nullptr;
     h->d_plc_concealed = nullptr;
+    h->d_dtmf_ring = nullptr;
+    h->d_dtmf_count = h->d_dtmf_ts = h->d_dtmf_flags = nullptr;
     hipError_t e = hipMalloc(&h->d_seq, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMalloc(&h->d_ts, sizeof(uint32_t) * n_streams);
     if (e == hipSuccess) e = hipMemset(h->d_seq, 0, sizeof(uint32_t) * n_streams);  // rtp_header(..., seq 0, timestamp 0, ssrc 0)
@@ -514,6 +627,7 @@ int wmx_rtp_destroy(wmx_rtp *h) {
     if (h->d_sq) (void)hipFree(h->d_sq);
     if (h->d_refused) (void)hipFree(h->d_refused);  // in_codec and out_law lie behind it
     if (h->d_plc_hist) (void)hipFree(h->d_plc_hist);  // concealed lies behind it
+    if (h->d_dtmf_ring) (void)hipFree(h->d_dtmf_ring);  // count, ts and flags lie behind it
     delete h;
     return 0;
 }
@@ -829,6 +943,88 @@ int wmx_rtp_export_conceal(wmx_rtp *h, int16_t *hist, uint32_t *concealed, void 
     WMX_HIP(hipStreamSynchronize(as_stream(stream)));
     if (hist) WMX_HIP(hipMemcpy(hist, h->d_plc_hist, n * kPlcHist * sizeof(int16_t), hipMemcpyDeviceToHost));
     if (concealed) WMX_HIP(hipMemcpy(concealed, h->d_plc_concealed, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the DTMF rule per leg (include/wmix_amd.h, leg_dtmf.h)
+// the state, all zero (nothing reported, no key down, no event timestamp), from the first call that needs it on
+static int dtmf_state(wmx_rtp *h) {
+    if (h->d_dtmf_ring) return 0;
+    const size_t n = (size_t)h->n_streams;
+    void *p = nullptr;
+    const int rc = zeroed_block(&p, n * (sizeof(uint64_t) + 3 * sizeof(uint32_t)), "hipMemset(DTMF state)");
+    if (rc) return rc;
+    h->d_dtmf_ring = static_cast<uint64_t *>(p);
+    h->d_dtmf_count = reinterpret_cast<uint32_t *>(h->d_dtmf_ring + n);
+    h->d_dtmf_ts = h->d_dtmf_count + n;
+    h->d_dtmf_flags = h->d_dtmf_ts + n;
+    return 0;
+}
+
+int wmx_rtp_detect_dtmf_legs(wmx_rtp *h, int max_packets, const uint8_t *d_in, long leg_stride, long packet_stride, const int32_t *d_recv,
+                             int16_t *d_pcm, long source_stride, long pcm_packet_stride, const uint32_t *d_len, const uint32_t *d_calls,
+                             int event_pt, int suppress, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !d_in || !d_recv || !d_pcm || !d_len || max_packets < 1 || max_packets > kSeqMaxCalls || event_pt < 96 || event_pt > 127) {
+        set_error("wmx_rtp_detect_dtmf_legs: max_packets=%d must be 1 .. %d, event_pt=%d 96 .. 127, and no pointer but d_calls NULL", max_packets,
+                  kSeqMaxCalls, event_pt);
+        return WMX_EINVAL;
+    }
+    const size_t n = (size_t)h->n_streams;
+    if (packet_stride < kRtpHeader + kRtpG711Payload || pcm_packet_stride < kDtmfRow ||
+        (n > 1 && (leg_stride < packet_stride * max_packets || source_stride < pcm_packet_stride * max_packets))) {
+        set_error("wmx_rtp_detect_dtmf_legs: rows that overlap (packet_stride %ld < %d, pcm_packet_stride %ld < %d, or a leg stride shorter than %d rows)",
+                  packet_stride, kRtpHeader + kRtpG711Payload, pcm_packet_stride, kDtmfRow, max_packets);
+        return WMX_EINVAL;
+    }
+    const int rcs = dtmf_state(h);
+    if (rcs) return rcs;
+    const bool wide = aligned_to(d_pcm, pcm_packet_stride * 2, 4) && (source_stride * 2) % 4 == 0;
+    hipLaunchKernelGGL(wide ? rtp_detect_dtmf_legs_kernel<true> : rtp_detect_dtmf_legs_kernel<false>,
+                       dim3((unsigned)((n + kDtmfLegsPerBlock - 1) / kDtmfLegsPerBlock)), dim3(32 * kDtmfLegsPerBlock), 0, as_stream(stream), d_in,
+                       leg_stride, packet_stride, d_recv, d_pcm, source_stride, pcm_packet_stride, d_len, d_calls, max_packets, (uint32_t)event_pt,
+                       suppress ? 1 : 0, h->d_dtmf_ring, h->d_dtmf_count, h->d_dtmf_ts, h->d_dtmf_flags, h->n_streams);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// nothing reported, no key down and no event timestamp for the listed legs (NULL = all), on `stream`: a new call does not inherit half a
+// key press
+int wmx_rtp_reset_dtmf(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
+    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_dtmf: leg", "handle")) return WMX_EINVAL;
+    const bool fresh = !h->d_dtmf_ring;
+    const int rcs = dtmf_state(h);
+    if (rcs || fresh) return rcs;  // just made: zero already
+    hipStream_t s = as_stream(stream);
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(h->d_dtmf_ring, 0, (size_t)h->n_streams * (sizeof(uint64_t) + 3 * sizeof(uint32_t)), s));
+        return 0;
+    }
+    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
+        WMX_HIP(hipMemsetAsync(h->d_dtmf_ring + host_idx[i], 0, sizeof(uint64_t), s));
+        WMX_HIP(hipMemsetAsync(h->d_dtmf_count + host_idx[i], 0, sizeof(uint32_t), s));
+        WMX_HIP(hipMemsetAsync(h->d_dtmf_ts + host_idx[i], 0, sizeof(uint32_t), s));
+        WMX_HIP(hipMemsetAsync(h->d_dtmf_flags + host_idx[i], 0, sizeof(uint32_t), s));
+    }
+    return 0;
+}
+
+// count (uint32) and ring (n_streams x 8 uint8) of every leg as the work queued on `stream` leaves them; either pointer may be NULL;
+// blocking
+int wmx_rtp_export_dtmf(wmx_rtp *h, uint32_t *count, uint8_t *ring, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const size_t n = (size_t)h->n_streams;
+    if (!h->d_dtmf_ring) {  // no leg has been listened to on this handle: all zero
+        if (count) memset(count, 0, n * sizeof(uint32_t));
+        if (ring) memset(ring, 0, n * 8);
+        return 0;
+    }
+    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+    if (count) WMX_HIP(hipMemcpy(count, h->d_dtmf_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (ring) WMX_HIP(hipMemcpy(ring, h->d_dtmf_ring, n * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

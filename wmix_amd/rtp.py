@@ -125,6 +125,42 @@ class RtpSenders:
               "wmx_rtp_export_conceal")
         return r
 
+    def detect_dtmf_legs(self, packets, recv_bytes, pcm, lens, calls=None, event_pt=101, suppress=False):
+        """DTMF per leg, heard in band and read from RFC 4733 packets (wmx_rtp_detect_dtmf_legs), between ingest_legs (and
+        sequence_legs) and the selection / the load: packets uint8 CUDA [n_streams, max_packets, >= 172] and recv_bytes int32 CUDA
+        [n_streams, max_packets] as ingest_legs was given them, pcm int16 CUDA [n_streams, max_packets, >= 160] and lens as it (or
+        sequence_legs) left them, calls the call lists of sequence_legs or None for slot order.  With suppress the rows of pcm that
+        are a tone are ZEROED in place; nothing else is written.  The digits are read with export_dtmf()."""
+        assert packets.is_cuda and packets.dtype == torch.uint8 and packets.dim() == 3 and packets.stride(2) == 1 and packets.shape[0] == self.n
+        k = packets.shape[1]
+        assert recv_bytes.is_cuda and recv_bytes.dtype == torch.int32 and recv_bytes.is_contiguous() and tuple(recv_bytes.shape) == (self.n, k)
+        assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() == 3 and pcm.stride(2) == 1 and tuple(pcm.shape[:2]) == (self.n, k)
+        assert pcm.shape[2] >= 160 and packets.shape[2] >= 172
+        assert lens.is_cuda and lens.dtype in (torch.int32, torch.uint32) and lens.is_contiguous() and tuple(lens.shape) == (self.n, k)
+        assert calls is None or (calls.is_cuda and calls.dtype in (torch.int32, torch.uint32) and calls.is_contiguous() and calls.numel() == self.n)
+        check(lib().wmx_rtp_detect_dtmf_legs(self._h, k, packets.data_ptr(), packets.stride(0), packets.stride(1), recv_bytes.data_ptr(),
+                                             pcm.data_ptr(), pcm.stride(0), pcm.stride(1), lens.data_ptr(),
+                                             None if calls is None else calls.data_ptr(), event_pt, 1 if suppress else 0,
+                                             torch.cuda.current_stream().cuda_stream), "wmx_rtp_detect_dtmf_legs")
+
+    def reset_dtmf(self, legs=None):
+        """nothing reported, no key down and no event timestamp for the listed legs (None = all)"""
+        import numpy as np
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_rtp_reset_dtmf(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                       torch.cuda.current_stream().cuda_stream), "wmx_rtp_reset_dtmf")
+
+    def export_dtmf(self):
+        """dict(count: uint32 [n_streams], the digits reported per leg; ring: uint8 [n_streams, 8], report n at ring[n & 7], bit 7 set
+        when it came from a packet) as the work queued on the current stream leaves them"""
+        import numpy as np
+        r = {"count": np.zeros(self.n, np.uint32), "ring": np.zeros((self.n, 8), np.uint8)}
+        check(lib().wmx_rtp_export_dtmf(self._h, r["count"].ctypes.data, r["ring"].ctypes.data, torch.cuda.current_stream().cuda_stream),
+              "wmx_rtp_export_dtmf")
+        return r
+
     def set_codecs(self, streams, in_codec, out_law):
         """in_codec ("reference", "pcma", "pcmu", "by_pt") and out_law ("a", "u") of the listed streams (None = all): wmx_rtp_set_codecs"""
         import numpy as np
