@@ -134,6 +134,21 @@ int wmx_nsx_set_active(wmx_nsx *h, const uint8_t *host_mask, void *stream);
 int wmx_nsx_stream_state_bytes(const wmx_nsx *h);
 int wmx_nsx_export_stream(wmx_nsx *h, int stream_index, void *host_blob);
 int wmx_nsx_import_stream(wmx_nsx *h, int stream_index, const void *host_blob);
+/* The ragged form for the legs of a conference bridge, on a handle created with chn == 1, freq == 8000: stream g is leg g, and a tick
+ * brings it 0 .. max_packets (1 .. WMX_MIX_MAX_LEG_PACKETS) rows of 160 samples (20 ms), slot k at d_pcm + g * leg_stride +
+ * k * packet_stride (strides in samples), with d_len[g * max_packets + k] == 320 where the slot holds a row.  The leg's rows are taken
+ * in the order the load makes its calls (wmix_amd/csrc/leg_dtmf.h): d_calls NULL, the slots with d_len == 320 in slot order; else
+ * d_calls[g] is the leg's call list (WMX_RTP_CALLS_*, what wmx_rtp_sequence_legs leaves), walked in list order, where a silence call
+ * or a data call naming a row that is not readable feeds NOTHING -- a lost packet is not 20 ms of zeros to the noise estimator.  Each
+ * row taken is two 80-sample blocks of the suppressor, processed in place; the bits are those of wmx_nsx_process over the same rows in
+ * the same order.  A leg with no row this tick touches nothing: its state is neither loaded nor stored.  A row that is not taken --
+ * a late packet, a duplicate, a refused packet -- keeps its bytes.  wmx_nsx_set_active's mask holds here too.
+ * ALIGNMENT: d_pcm on a 2-byte boundary (the rows are read and written sample by sample as int16; the strides count samples, so
+ * every row then is).  Nothing wider is needed.
+ * WMX_EINVAL, nothing launched: a handle that is not 1 x 8000; max_packets outside 1 .. 4; d_pcm or d_len NULL; rows that overlap
+ * (packet_stride < 160, or with more than one leg leg_stride < max_packets * packet_stride); d_pcm on an odd address. */
+int wmx_nsx_process_legs(wmx_nsx *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                         const uint32_t *d_calls, void *stream);
 
 /* ------------------------------------------------------------------ VAD (voice-activity gate)
  * Batched form of vad_init / vad_process / vad_release (src/webrtc.h:32-36, src/webrtc.c:40-164):
@@ -854,6 +869,17 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * WMX_EINVAL.  Off, the launches are those of a handle that never heard of it; the state is made the first time it is switched on,
  * never inside a submit.  wmx_conf_reset_legs also resets the listed legs' DTMF state.  wmx_conf_export_dtmf: count (uint32) and ring
  * (8 uint8) of every leg (wmx_rtp_export_dtmf), either pointer NULL; blocking.
+ * wmx_conf_denoise(h, on): between submits; off is the default.  On, wmx_nsx_process_legs runs behind the ingest, behind
+ * wmx_rtp_sequence_legs (it is given the call list exactly when the sequencer ran) and behind wmx_rtp_detect_dtmf_legs, and in front of
+ * the selection: every row a leg's load will consume goes through that leg's own fixed-point noise suppressor (a wmx_nsx stream of
+ * 1 x 8000 with the policy ns_init sets), in place, in the order the load consumes them.  The keypad is judged on the row as it
+ * arrived, and a suppressed key goes in as the zeros it became; the selection, the concealment history and the load all see the
+ * cleaned rows, so a steadily noisy leg neither holds a talker slot nor is repeated by concealment.  A lost packet feeds the
+ * suppressor nothing; a late, duplicate or refused packet is not touched.  Mute and selection act at the load: a muted leg's rows are
+ * cleaned all the same.  Off, the launches are those of a handle that never heard of it and the suppressor's state does not move; the
+ * suppressor is made the first time it is switched on, never inside a submit, and switching off and on again keeps its state.
+ * wmx_conf_reset_legs also resets the listed legs' suppressor state.  wmx_conf_denoiser: the legs' wmx_nsx (NULL until the first
+ * switch-on), for wmx_nsx_export_stream / wmx_nsx_import_stream on a leg.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -873,6 +899,8 @@ int wmx_conf_conceal(wmx_conf *h, int on);
 int wmx_conf_export_conceal(wmx_conf *h, uint32_t *concealed, void *stream);
 int wmx_conf_dtmf(wmx_conf *h, int on, int suppress, int event_pt);
 int wmx_conf_export_dtmf(wmx_conf *h, uint32_t *count, uint8_t *ring, void *stream);
+int wmx_conf_denoise(wmx_conf *h, int on);
+wmx_nsx *wmx_conf_denoiser(wmx_conf *h);
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
 int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);

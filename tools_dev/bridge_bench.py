@@ -62,7 +62,15 @@ detector's launch.  The script is noise: no block is a tone, no row is zeroed, n
     python tools_dev/bridge_bench.py --pipe --ulaw-every 2 --out file.json    (profiles/bridge/bridge_dtmf_bench.json is made of such runs)
 --pipe --ulaw-every N adds (f), (g): the handle and the resident step again with a codec per leg (wmx_conf_set_codecs): every N-th leg is
 WMX_CODEC_PCMU in and mu-law out and its datagrams carry payload type 0, the other legs stay at the default; the launches are the per-leg
-ones for every leg.  (f) and (g) send the same datagrams, each leg in its own payload type, before any time is reported."""
+ones for every leg.  (f) and (g) send the same datagrams, each leg in its own payload type, before any time is reported.
+--pipe --denoise adds (l), (m): the handle and the resident step of (b), (c) with denoising on (wmx_conf_denoise): (l) - (b), (m) - (c)
+are the launch of wmx_nsx_process_legs, every row of the script through its leg's suppressor.  --steady makes the script of every side
+one packet per leg and tick in slot 0.  Beside them the new kernel alone, device time (events), on as many legs: wmx_nsx_process_legs on
+one row per leg against wmx_nsx_process on a dense plane of the same rows -- the dense side twice in every repetition, so that its
+own run-to-run spread stands beside the difference -- and then with one leg in eight sending against the dense call, which must
+process everyone.  Every side's rows are put back in front of every call, outside the timed region: a row cleaned over and over is
+silence, and silence takes the suppressor's short path.
+    python tools_dev/bridge_bench.py --pipe --denoise --steady --out profiles/bridge/bridge_denoise_bench.json"""
 import argparse
 import json
 import os
@@ -313,7 +321,49 @@ def legs_against_conf(reps, freq=8000):
             "ratio_steady_over_conf": round(b["median_ms"] / a["median_ms"], 3), "ratio_jitter_over_conf": round(c["median_ms"] / a["median_ms"], 3)}
 
 
-def conf_pipe(reps, ulaw_every=0, loss_every=0):
+def denoise_kernel(legs, reps):
+    """wmx_nsx_process_legs beside wmx_nsx_process on the same rows: device milliseconds per launch"""
+    from wmix_amd.nsx import NsxBatch
+    rng = np.random.default_rng(17)
+    noise = np.clip(np.round(rng.normal(0, 400, (legs, 160))), -32768, 32767).astype(np.int16)
+    src = torch.from_numpy(noise).cuda()
+    every, sparse_of = torch.full((legs, 3), 0, dtype=torch.int32, device="cuda"), torch.full((legs, 3), 0, dtype=torch.int32, device="cuda")
+    every[:, 0] = 320
+    sparse_of[::8, 0] = 320
+    handles = [NsxBatch(legs, 1, 8000) for _ in range(4)]
+    dense_rows = [torch.zeros((legs, 2, 80), dtype=torch.int16, device="cuda") for _ in range(2)]
+    leg_rows = [torch.zeros((legs, 3, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
+
+    def dense(k):
+        return (lambda: dense_rows[k].view(legs, 160).copy_(src)), (lambda: handles[k].process(dense_rows[k]))
+
+    def ragged(k, lens):
+        return (lambda: leg_rows[k][:, 0].copy_(src)), (lambda: handles[2 + k].process_legs(leg_rows[k], lens))
+
+    sides = [dense(0), ragged(0, every), dense(1), ragged(1, sparse_of)]
+    for prepare, f in sides * 20:
+        prepare()
+        f()
+    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for _ in sides]
+    for r in range(reps):
+        for k, (prepare, f) in enumerate(sides):
+            prepare()
+            ev[k][r][0].record()
+            f()
+            ev[k][r][1].record()
+    torch.cuda.synchronize()
+    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
+    d0, full, d1, sparse = (stats([a.elapsed_time(b) for a, b in side]) for side in ev)
+    for h in handles:
+        h.close()
+    return {"legs": legs, "rows_per_leg": 1, "blocks_per_row": 2, "wmx_nsx_process_dense": d0, "wmx_nsx_process_dense_again": d1,
+            "wmx_nsx_process_legs_every_leg": full, "wmx_nsx_process_legs_one_leg_in_eight": sparse,
+            "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4), "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4),
+            "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
+
+
+def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False):
     import ctypes as C
     import time
     from wmix_amd._lib import check, lib
@@ -326,7 +376,7 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
     layout = [list(range(off[c], off[c + 1])) for c in range(n_conf)]
     CYC = 3  # the script is a cycle of as many ticks as the handle has slots: every slot keeps its tick's rows
     rng = np.random.default_rng(13)
-    u = rng.integers(0, 8, (CYC, legs))
+    u = np.full((CYC, legs), 4) if steady else rng.integers(0, 8, (CYC, legs))
     recv = np.zeros((CYC, legs, 3), np.int32)
     recv[:, :, 0] = np.where(u >= 2, 172, 0)
     recv[:, :, 1] = np.where(u == 2, 172, np.where(u == 3, -1, 0))
@@ -467,6 +517,33 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
         step["k"] += 1
         ck.step_resident(r_in[i], r_recv[i], k_out)
 
+    # (l), (m) the handle and the resident step of (b), (c) with denoising on: every row of the script through its leg's suppressor
+    if denoise:
+        cl, cm = ConfBridge(legs, 3, 3), ConfBridge(legs, 1, 3)
+        for x in (cl, cm):
+            x.set_conferences(layout)
+            x.set_play_correct(0)
+            x.denoise(True)
+        for k in range(3):
+            cl.rows_in[k][:] = pk[k]
+            cl.recv[k][:] = recv[k]
+        m_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+        step["m"] = 0
+
+        def handle_dn():
+            return cl.submit()
+
+        def resident_dn():
+            i = step["m"] % CYC
+            step["m"] += 1
+            cm.step_resident(r_in[i], r_recv[i], m_out)
+
+        for t in range(2 * CYC):
+            k = handle_dn()
+            cl.wait(k)
+            resident_dn()
+            assert np.array_equal(cl.rows_out[k], m_out.cpu().numpy()), ("handle and resident step differ with denoising on, tick", t)
+
     # (f), (g) the same two with a codec per leg: every ulaw_every-th leg on PCMU both ways, the others at the default
     mixed = ulaw_every > 0
     if mixed:
@@ -534,7 +611,7 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
         return (time.perf_counter() - t0) * 1e3 / n
 
     per_block = max(reps // BLOCKS, 8)
-    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": [], "h": [], "i": [], "j": [], "k": []}
+    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": [], "h": [], "i": [], "j": [], "k": [], "l": [], "m": []}
     for _ in range(BLOCKS + 1):  # the first block warms up
         ms["a"].append(wall(parent, per_block, torch.cuda.synchronize))
         ms["b"].append(wall(handle, per_block, lambda: cb.wait(-1)))
@@ -545,6 +622,9 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
         ms["i"].append(wall(resident_plc, per_block, torch.cuda.synchronize))
         ms["j"].append(wall(handle_dtmf, per_block, lambda: cj.wait(-1)))
         ms["k"].append(wall(resident_dtmf, per_block, torch.cuda.synchronize))
+        if denoise:
+            ms["l"].append(wall(handle_dn, per_block, lambda: cl.wait(-1)))
+            ms["m"].append(wall(resident_dn, per_block, torch.cuda.synchronize))
         if mixed:
             ms["f"].append(wall(handle_mixed, per_block, lambda: cf.wait(-1)))
             ms["g"].append(wall(resident_mixed, per_block, torch.cuda.synchronize))
@@ -584,6 +664,13 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0):
                  "h_wmx_conf_3_slots_sequencing_and_concealment_on": h, "i_step_resident_sequencing_and_concealment_on": i,
                  "h_minus_d_ms": round(h["median_ms_per_tick"] - d["median_ms_per_tick"], 5),
                  "i_minus_e_ms": round(i["median_ms_per_tick"] - e["median_ms_per_tick"], 5), "concealed_of_h": concealed_h})
+    if denoise:
+        l_side, m_side = side(ms["l"]), side(ms["m"])
+        more.update({"steady": bool(steady), "l_wmx_conf_3_slots_denoise_on": l_side, "m_step_resident_denoise_on": m_side,
+                     "l_minus_b_ms": round(l_side["median_ms_per_tick"] - b["median_ms_per_tick"], 5),
+                     "m_minus_c_ms": round(m_side["median_ms_per_tick"] - c["median_ms_per_tick"], 5)})
+        cl.close()
+        cm.close()
     j, k = side(ms["j"]), side(ms["k"])
     keys_of_j = int(cj.export_dtmf()["count"].sum())
     assert keys_of_j == 0, keys_of_j  # the script is noise
@@ -675,6 +762,8 @@ if __name__ == "__main__":
     ap.add_argument("--pipe", action="store_true", help="the bridge of RTP/G.711 legs end to end: the parent's composition, wmx_conf, the launches alone")
     ap.add_argument("--ulaw-every", type=int, default=0, help="with --pipe: two more sides, every N-th leg on PCMU both ways (a codec per leg)")
     ap.add_argument("--loss-every", type=int, default=0, help="with --pipe: one packet in N never arrives, on all sides alike: the run path of the concealment")
+    ap.add_argument("--denoise", action="store_true", help="with --pipe: two more sides with denoising on, and the new kernel alone beside the dense call")
+    ap.add_argument("--steady", action="store_true", help="with --pipe: every leg sends one packet per tick, on all sides alike")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bridge_bench.py measures on the GPU; there is nothing to report without one"
@@ -686,7 +775,9 @@ if __name__ == "__main__":
         args.ragged, args.speakers = False, 0
     if args.pipe:
         res = {"tool": "bridge_bench --pipe", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every, args.loss_every)}
+               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every, args.loss_every, args.denoise, args.steady)}
+        if args.denoise:
+            res["denoise_kernel"] = denoise_kernel(res["pipe"]["legs"], args.reps)
         args.sizes = args.tick = ""
         args.ragged, args.speakers = False, 0
     if args.speakers:

@@ -90,6 +90,21 @@ class ConfBridge:
         check(lib().wmx_conf_export_dtmf(self._h, r["count"].ctypes.data, r["ring"].ctypes.data, self._stream()), "wmx_conf_export_dtmf")
         return r
 
+    def denoise(self, on):
+        """every leg's rows go through the leg's own fixed-point noise suppressor behind the DTMF detection and in front of talker
+        selection (wmx_conf_denoise), between submits; off (the default) = the launches of before, and the suppressor's state stays"""
+        check(lib().wmx_conf_denoise(self._h, 1 if on else 0), "wmx_conf_denoise")
+
+    def denoiser_state(self, leg):
+        """the stream blob of one leg's suppressor (wmx_nsx_export_stream on wmx_conf_denoiser), None before the first denoise(True)"""
+        L = lib()
+        nsx = L.wmx_conf_denoiser(self._h)
+        if not nsx:
+            return None
+        blob = np.zeros(L.wmx_nsx_stream_state_bytes(nsx), np.uint8)
+        check(L.wmx_nsx_export_stream(nsx, int(leg), blob.ctypes.data), "wmx_nsx_export_stream")
+        return blob
+
     def set_codecs(self, legs, in_codec, out_law):
         """a G.711 codec per leg, as each call negotiated it (wmx_conf_set_codecs), between submits: in_codec "reference" (the default:
         A-law whatever arrives), "pcma", "pcmu" or "by_pt" (or WMX_CODEC_* 0 .. 3), out_law "a" / "u"; legs None = every leg"""
@@ -111,8 +126,8 @@ class ConfBridge:
 
     def reset_legs(self, legs=None):
         """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-        refused = 0, the concealment history and count zero, no key down and no digit reported; the leg keeps its codec (None = every
-        leg)"""
+        refused = 0, the concealment history and count zero, no key down and no digit reported, the noise suppressor as new; the leg
+        keeps its codec (None = every leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

@@ -12,7 +12,9 @@
 // apply each leg's own G.711 codec (wmx_conf_set_codecs; wmix_amd/csrc/leg_codec.h); a handle that never sets one runs the
 // reference's A-law-whatever-arrives and one law out.  With concealment on as well (wmx_conf_conceal) wmx_rtp_conceal_legs stands
 // between the selection and the load: it turns every leg's list into rows that are all data -- a lost packet synthesised from the
-// leg's own history (wmix_amd/csrc/leg_plc.h) -- and the load is wmx_mix_load_minus_legs on those.
+// leg's own history (wmix_amd/csrc/leg_plc.h) -- and the load is wmx_mix_load_minus_legs on those.  With denoising on
+// (wmx_conf_denoise) wmx_nsx_process_legs stands behind the sequencer and the DTMF detection and in front of the selection: each leg's
+// rows of the tick go through the leg's own fixed-point noise suppressor in place, in the order the load will consume them.
 //
 // PER SLOT (made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a 4-byte
 // boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and three events.  PER HANDLE: the mixer
@@ -47,6 +49,8 @@ struct wmx_conf {
     uint32_t *d_rep_len;  // [n_legs][4], behind them
     bool dtmf_on, dtmf_suppress, dtmf_made;  // wmx_rtp_detect_dtmf_legs in front of the selection; made: the senders hold its state
     int dtmf_pt;
+    bool denoise_on;  // wmx_nsx_process_legs in front of the selection
+    wmx_nsx *nsx;     // a suppressor stream per leg, made when denoising is first switched on
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -81,6 +85,10 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
                                       h->seq_on ? h->d_calls : nullptr, h->dtmf_pt, h->dtmf_suppress ? 1 : 0, stream);
         if (rc != 0) return rc;
     }
+    if (h->denoise_on) {  // behind the keypad, which is judged on the row as it arrived; selection, concealment and the load see the cleaned rows
+        rc = wmx_nsx_process_legs(h->nsx, h->d_pcm, (long)K * kPcmRow, kPcmRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
+        if (rc != 0) return rc;
+    }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
     if (h->max_speakers > 0) {
         rc = wmx_mix_select_speakers_legs(h->mix, h->d_pcm, kPcmBytes, (long)K * kPcmRow, kPcmRow, K, h->d_len, host_mute, h->max_speakers, h->floor,
@@ -106,6 +114,14 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         return WMX_ESTATE;
     }
     return rc;
+}
+
+// the listed legs' suppressor streams (NULL = all) as ns_init leaves them
+static int conf_reset_denoiser(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
+    if (host_idx) return n > 0 ? wmx_nsx_reset_streams(h->nsx, host_idx, n, stream) : 0;
+    std::vector<int32_t> all((size_t)h->n_legs);
+    for (int g = 0; g < h->n_legs; g++) all[(size_t)g] = g;
+    return wmx_nsx_reset_streams(h->nsx, all.data(), h->n_legs, stream);
 }
 
 static bool conf_slot_ok(const wmx_conf *h, int slot) { return h && slot >= 0 && slot < h->slots; }
@@ -135,6 +151,7 @@ int wmx_conf_destroy(wmx_conf *h) {
     if (h->d_rep) (void)hipFree(h->d_rep);  // d_rep_len lies behind it
     if (h->d_mute) (void)hipFree(h->d_mute);  // d_mask lies behind it
     if (h->h_mute) (void)hipHostFree(h->h_mute);
+    if (h->nsx) wmx_nsx_destroy(h->nsx);
     if (h->mix) wmx_mix_destroy(h->mix);
     if (h->snd) wmx_rtp_destroy(h->snd);
     delete h;
@@ -310,6 +327,23 @@ int wmx_conf_export_dtmf(wmx_conf *h, uint32_t *count, uint8_t *ring, void *stre
     return wmx_rtp_export_dtmf(h->snd, count, ring, stream);
 }
 
+// on != 0: every leg's rows of the tick go through the leg's own fixed-point noise suppressor (wmx_nsx_process_legs: 1 x 8000, the
+// policy ns_init sets) behind the DTMF detection and in front of the selection; 0 (the default): the launches of a handle that never
+// heard of it.  Between submits.  The suppressor is made the first time it is switched on; off and on again keeps its state.
+int wmx_conf_denoise(wmx_conf *h, int on) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (on && !h->nsx) {
+        const int rc = wmx_nsx_create(&h->nsx, h->n_legs, 1, 8000);
+        if (rc != 0) return rc;
+    }
+    h->denoise_on = on != 0;
+    return 0;
+}
+
+// the legs' suppressor, for wmx_nsx_export_stream / wmx_nsx_import_stream on a leg; NULL until denoising is first switched on
+wmx_nsx *wmx_conf_denoiser(wmx_conf *h) { return h ? h->nsx : nullptr; }
+
 // a G.711 codec per leg (wmx_rtp_set_codecs over the legs; NULL = all): between submits, ordered on `stream`
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
     if (!h) return WMX_EINVAL;
@@ -325,7 +359,8 @@ int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uin
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
 
 // a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-// refused = 0, the concealment history and count zero, the DTMF state fresh; the leg keeps its codec
+// refused = 0, the concealment history and count zero, the DTMF state fresh, the noise suppressor as ns_init leaves it; the leg keeps
+// its codec
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
     // before the first of them: a bad index resets nothing
@@ -337,6 +372,7 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, host_idx, n, stream);
     if (rc == 0 && h->d_rep) rc = wmx_rtp_reset_conceal(h->snd, host_idx, n, stream);  // never switched on: no state to reset
     if (rc == 0 && h->dtmf_made) rc = wmx_rtp_reset_dtmf(h->snd, host_idx, n, stream);  // a new call inherits no half key press
+    if (rc == 0 && h->nsx) rc = conf_reset_denoiser(h, host_idx, n, stream);            // nor the old call's noise estimate
     return rc;
 }
 

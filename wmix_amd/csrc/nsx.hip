@@ -25,6 +25,7 @@
 #include "stage_life.h"
 #include "spl_fx.h"
 #include "fx_tables.h"
+#include "leg_dtmf.h"
 
 namespace wmx {
 namespace {
@@ -1130,6 +1131,73 @@ __global__ __launch_bounds__((64 * NsxShape<ANA, CHN>::WPB)) __attribute__((amdg
     }
 }
 
+// The ragged form for the legs of a conference bridge (wmx_nsx_process_legs): 8 kHz mono, one wave per leg like nsx_kernel, but a leg
+// brings 0 .. 4 rows of 160 samples this tick, the count is known only here (len, calls) and the order is the load's: the rule of
+// leg_dtmf.h -- without a call list the readable slots in slot order, with one the list in list order, where a silence call or a
+// data call naming a row that is not readable feeds nothing (a lost packet is not 20 ms of zeros to the noise estimator).  Each row
+// taken is two 80-sample blocks of nsx_block, in place.  The list, the mask of calls taken and every row address are wave-uniform
+// (scalar registers): the walk costs a few scalar instructions per row and nothing per sample.  A leg with no row this tick leaves
+// behind the barrier without having loaded or stored its state; a workgroup none of whose legs has a row leaves before it copies
+// the constants.  A row that is not taken is never addressed.
+__global__ __launch_bounds__((64 * NsxShape<128, 1>::WPB)) __attribute__((amdgpu_waves_per_eu(NsxShape<128, 1>::WPE, NsxShape<128, 1>::WPE))) void nsx_legs_kernel(
+    int32_t *__restrict__ state, int16_t *__restrict__ hist, const NsxConsts *__restrict__ consts, int16_t *pcm, int n_legs, long leg_stride,
+    long packet_stride, int max_packets, const uint32_t *__restrict__ len, const uint32_t *__restrict__ calls_in, int overdrive,
+    int denoise_bound, const uint8_t *__restrict__ active) {
+    using Y = NsxLayout<128>;
+    constexpr int WORDS = Y::WORDS_MONO, BLOCK = 80, WPB = NsxShape<128, 1>::WPB;
+    static_assert(2 * BLOCK == kDtmfRow, "a row of the bridge is two blocks of the 8 kHz suppressor");
+    __shared__ NsxConsts K;
+    __shared__ NsxWave<128, 1> WS[WPB];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const long s = (long)blockIdx.x * WPB + wave;
+    uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
+    if (stream_active(active, (int)s, n_legs)) {
+        uint32_t readable = 0;
+#pragma unroll
+        for (int k = 0; k < kSeqMaxCalls; k++)
+            if (k < max_packets) readable |= leg_plc_readable(len[s * max_packets + k]) << k;
+        list = leg_dtmf_list(calls_in != nullptr, calls_in ? calls_in[s] : 0u, readable, max_packets);
+        const uint32_t count = leg_plc_count(list);
+#pragma unroll
+        for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++)
+            if (j < count && !leg_plc_silence(list, j, readable)) take |= 1u << j;
+    }
+    list = (uint32_t)__builtin_amdgcn_readfirstlane((int)list);
+    take = (uint32_t)__builtin_amdgcn_readfirstlane((int)take);
+    if (!__syncthreads_or(take != 0u)) return;  // nobody in this workgroup sent anything
+    {
+        const int4 *src = reinterpret_cast<const int4 *>(consts);
+        int4 *dst = reinterpret_cast<int4 *>(&K);
+        for (int i = threadIdx.x; i < (int)(sizeof(NsxConsts) / 16); i += blockDim.x) dst[i] = src[i];
+    }
+    NsxWave<128, 1> &W = WS[wave];
+    const bool live = take != 0u;
+    int32_t *st = state + (live ? s : 0) * (long)WORDS;
+    if (live) {
+        const int4 *src = reinterpret_cast<const int4 *>(st);
+        int4 *dst = reinterpret_cast<int4 *>(W.st);
+        for (int i = lane; i < WORDS / 4; i += 64) dst[i] = src[i];
+    }
+    __syncthreads();
+    if (!live) return;
+    const LdsScal sc{&W.st[Y::SCAL]};
+    int16_t *hs = hist + s * (long)(3 * kNsxHist);
+    int16_t *rows = pcm + s * leg_stride;
+#pragma unroll 1
+    for (uint32_t b = 0; b < 2u * (uint32_t)kSeqMaxCalls; b++) {
+        const uint32_t j = b >> 1;
+        if (!((take >> j) & 1u)) continue;
+        int16_t *row = rows + (long)leg_calls_slot(list, j) * packet_stride + (long)(b & 1u) * BLOCK;
+        nsx_block<128, 1>(W, K, sc, hs, row, row, lane, overdrive, denoise_bound);
+    }
+    wave_sync();
+    {
+        int4 *dst = reinterpret_cast<int4 *>(st);
+        const int4 *src = reinterpret_cast<const int4 *>(W.st);
+        for (int i = lane; i < WORDS / 4; i += 64) dst[i] = src[i];
+    }
+}
+
 __global__ void nsx_fill_state(int32_t *state, const int32_t *tmpl, int words, int n_streams) {
     const size_t total = (size_t)words * n_streams;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
@@ -1310,6 +1378,36 @@ int wmx_nsx_process(wmx_nsx *h, const int16_t *d_in, int16_t *d_out, int n_packe
             NSX_LAUNCH(256, 2);
     }
 #undef NSX_LAUNCH
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// the legs of a conference bridge, each with the rows this tick brought it (include/wmix_amd.h; nsx_legs_kernel)
+int wmx_nsx_process_legs(wmx_nsx *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                         const uint32_t *d_calls, void *stream) {
+    WMX_ON_DEVICE(h);
+    using namespace wmx;
+    if (!h || h->chn != 1 || h->freq != 8000) {
+        set_error("wmx_nsx_process_legs: the handle must be 1 x 8000 (it is %d x %d)", h ? h->chn : 0, h ? h->freq : 0);
+        return WMX_EINVAL;
+    }
+    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kSeqMaxCalls) {
+        set_error("wmx_nsx_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kSeqMaxCalls);
+        return WMX_EINVAL;
+    }
+    if (packet_stride < kDtmfRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
+        set_error("wmx_nsx_process_legs: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", packet_stride,
+                  kDtmfRow, leg_stride, max_packets);
+        return WMX_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is
+        set_error("wmx_nsx_process_legs: d_pcm %p is not on a 2-byte boundary (the rows are read and written as int16)", (void *)d_pcm);
+        return WMX_EINVAL;
+    }
+    constexpr int WPB = NsxShape<128, 1>::WPB;
+    hipLaunchKernelGGL(nsx_legs_kernel, dim3((unsigned)((h->n_streams + WPB - 1) / WPB)), dim3(64 * WPB), 0, as_stream(stream), h->d_state,
+                       h->d_hist, h->d_consts, d_pcm, h->n_streams, leg_stride, packet_stride, max_packets, d_len, d_calls, h->overdrive,
+                       h->denoise_bound, h->life.d_active);
     WMX_LAUNCH_CHECK();
     return 0;
 }
