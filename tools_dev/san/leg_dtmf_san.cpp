@@ -17,7 +17,7 @@
 using namespace wmx;
 
 static bool read_row(int16_t *x) {
-    for (int i = 0; i < kDtmfRow; i++) {
+    for (int i = 0; i < kLegRow; i++) {
         int v;
         if (scanf("%d", &v) != 1) return false;
         x[i] = (int16_t)v;
@@ -26,14 +26,14 @@ static bool read_row(int16_t *x) {
 }
 
 static int blocks() {
-    std::vector<int16_t> x(kDtmfRow);
+    std::vector<int16_t> x(kLegRow);
     while (read_row(x.data())) {
         int64_t p[kDtmfFreqs], e = 0;
         const int32_t digit = leg_dtmf_block_digit(x.data(), p, &e);
         int64_t reach = 0;
         for (int f = 0; f < kDtmfFreqs; f++) {
             int32_t s1 = 0, s2 = 0;
-            for (int n = 0; n < kDtmfRow; n++) {
+            for (int n = 0; n < kLegRow; n++) {
                 leg_dtmf_step(s1, s2, leg_dtmf_coef(f), x[n]);
                 const int64_t a = s1 < 0 ? -(int64_t)s1 : (int64_t)s1;
                 reach = a > reach ? a : reach;
@@ -58,11 +58,11 @@ static int ticks() {
         }
         int max_packets, have_calls;
         unsigned calls;
-        if (what[0] != 'T' || scanf("%d %d %u", &max_packets, &have_calls, &calls) != 3 || max_packets < 1 || max_packets > kSeqMaxCalls) return 2;
+        if (what[0] != 'T' || scanf("%d %d %u", &max_packets, &have_calls, &calls) != 3 || max_packets < 1 || max_packets > kLegMaxCalls) return 2;
         std::vector<int32_t> recv((size_t)max_packets);
         std::vector<uint32_t> len((size_t)max_packets);
         std::vector<uint8_t> pk((size_t)max_packets * kDtmfMinEventBytes);
-        std::vector<int16_t> pcm((size_t)max_packets * kDtmfRow);
+        std::vector<int16_t> pcm((size_t)max_packets * kLegRow);
         for (int32_t &r : recv)
             if (scanf("%d", &r) != 1) return 2;
         for (uint32_t &l : len)
@@ -73,10 +73,10 @@ static int ticks() {
                 if (scanf("%u", &b) != 1) return 2;
                 pk[(size_t)k * kDtmfMinEventBytes + i] = (uint8_t)b;
             }
-            if (!read_row(pcm.data() + (size_t)k * kDtmfRow)) return 2;
+            if (!read_row(pcm.data() + (size_t)k * kLegRow)) return 2;
         }
-        int32_t digits[kSeqMaxCalls];
-        const uint32_t n = leg_dtmf_tick(st, pk.data(), (long)kDtmfMinEventBytes, recv.data(), pcm.data(), kDtmfRow, len.data(), max_packets,
+        int32_t digits[kLegMaxCalls];
+        const uint32_t n = leg_dtmf_tick(st, pk.data(), (long)kDtmfMinEventBytes, recv.data(), pcm.data(), kLegRow, len.data(), max_packets,
                                          have_calls != 0, calls, event_pt, suppress != 0, digits);
         printf("%u %d %d %d %d %u", n, digits[0], digits[1], digits[2], digits[3], st.count);
         uint8_t ring[8];

@@ -23,31 +23,31 @@ static void one(int max_packets, uint32_t calls, const uint32_t *len, const int1
         printf("in %d %u", max_packets, calls);
         for (int k = 0; k < max_packets; k++) printf(" %u", len[k]);
         for (int i = 0; i < kPlcHist; i++) printf(" %d", hist[i]);
-        for (int i = 0; i < max_packets * kPlcRow; i++) printf(" %d", rows[i]);
+        for (int i = 0; i < max_packets * kLegRow; i++) printf(" %d", rows[i]);
         printf("\n");
     }
     LegPlcState st;
     for (int i = 0; i < kPlcHist; i++) st.hist[i] = hist[i];
     st.concealed = 0;
     // exactly as many rows as there are calls: a write behind them is the sanitizer's to report
-    const uint32_t count = leg_plc_count(calls);
-    std::vector<int16_t> out((size_t)count * kPlcRow, (int16_t)0x5A5A);
-    uint32_t len_out[kSeqMaxCalls];
-    leg_plc_tick(st, rows, kPlcRow, len, max_packets, calls, out.data(), len_out);
+    const uint32_t count = leg_calls_walked(calls);
+    std::vector<int16_t> out((size_t)count * kLegRow, (int16_t)0x5A5A);
+    uint32_t len_out[kLegMaxCalls];
+    leg_plc_tick(st, rows, kLegRow, len, max_packets, calls, out.data(), len_out);
     printf("%u %u %u %u %u %u", count, len_out[0], len_out[1], len_out[2], len_out[3], st.concealed);
     for (int i = 0; i < kPlcHist; i++) printf(" %d", st.hist[i]);
-    for (uint32_t i = 0; i < count * kPlcRow; i++) printf(" %d", out[i]);
+    for (uint32_t i = 0; i < count * kLegRow; i++) printf(" %d", out[i]);
     printf("\n");
     // what any tick satisfies: the history afterwards is the tail of (history, emitted rows), so a list without calls changes nothing;
     // concealed counts the silence calls
     for (int i = 0; i < kPlcHist; i++) {
-        const int at = (int)count * kPlcRow + i;  // in the sequence history ++ rows
+        const int at = (int)count * kLegRow + i;  // in the sequence history ++ rows
         const int16_t want = at < kPlcHist ? hist[at] : out[(size_t)(at - kPlcHist)];
         if (st.hist[i] != want) bad++;
     }
     uint32_t readable = 0, silent = 0;
-    for (int k = 0; k < max_packets; k++) readable |= leg_plc_readable(len[k]) << k;
-    for (uint32_t j = 0; j < count; j++) silent += leg_plc_silence(calls, j, readable) ? 1u : 0u;
+    for (int k = 0; k < max_packets; k++) readable |= leg_row_readable(len[k]) << k;
+    for (uint32_t j = 0; j < count; j++) silent += leg_calls_adds_nothing(calls, j, readable) ? 1u : 0u;
     if (st.concealed != silent) bad++;
 }
 
@@ -62,9 +62,9 @@ int main(int argc, char **argv) {
         int max_packets;
         unsigned calls;
         while (scanf("%d %u", &max_packets, &calls) == 2) {
-            if (max_packets < 1 || max_packets > kSeqMaxCalls) return 2;
-            uint32_t len[kSeqMaxCalls] = {0u, 0u, 0u, 0u};
-            std::vector<int16_t> hist(kPlcHist), rows((size_t)max_packets * kPlcRow);
+            if (max_packets < 1 || max_packets > kLegMaxCalls) return 2;
+            uint32_t len[kLegMaxCalls] = {0u, 0u, 0u, 0u};
+            std::vector<int16_t> hist(kPlcHist), rows((size_t)max_packets * kLegRow);
             int v;
             for (int k = 0; k < max_packets; k++)
                 if (scanf("%u", &len[k]) != 1) return 2;
@@ -80,7 +80,7 @@ int main(int argc, char **argv) {
         }
     } else {
         const int K = 3;
-        const uint32_t len[kSeqMaxCalls] = {kPlcRowBytes, kPlcRowBytes, 0u, 0u};
+        const uint32_t len[kLegMaxCalls] = {kLegRowBytes, kLegRowBytes, 0u, 0u};
         for (int hk = 0; hk < 8; hk++) {
             int16_t hist[kPlcHist];
             const int period = hk == 3 ? 40 : (hk == 4 ? 50 : 120);
@@ -90,11 +90,11 @@ int main(int argc, char **argv) {
                           : hk == 2 ? (int16_t)32767
                           : hk <= 5 ? (int16_t)(i % period < period / 2 ? 32767 : -32768)
                                     : (int16_t)(rnd() & 0xFFFFu);
-            for (uint32_t count = 0; count <= (uint32_t)kSeqMaxCalls; count++)
+            for (uint32_t count = 0; count <= (uint32_t)kLegMaxCalls; count++)
                 for (uint32_t pick = 0; pick < (1u << count); pick++) {
                     uint32_t calls = 0;
                     for (uint32_t j = 0; j < count; j++) calls = leg_calls_push(calls, (pick >> j) & 1u ? 0u : j % 3u, (pick >> j) & 1u);
-                    int16_t rows[K * kPlcRow];
+                    int16_t rows[K * kLegRow];
                     for (int16_t &s : rows) s = (int16_t)(rnd() & 0xFFFFu);
                     one(K, calls, len, hist, rows, true);
                 }

@@ -19,8 +19,8 @@ static long bad = 0;
 
 static void one(uint32_t max_gap, uint32_t synced, uint32_t next, const long s[4]) {
     LegSeqState st{synced, next, 0u, 0u, 0u, 0u, 0u};
-    uint32_t seq[kSeqMaxCalls] = {0u, 0u, 0u, 0u}, ok = 0;
-    for (int k = 0; k < kSeqMaxCalls; k++)
+    uint32_t seq[kLegMaxCalls] = {0u, 0u, 0u, 0u}, ok = 0;
+    for (int k = 0; k < kLegMaxCalls; k++)
         if (s[k] >= 0) seq[k] = (uint32_t)s[k] & 0xFFFFu, ok |= 1u << k;
     const LegSeqTick r = leg_seq_tick(st, seq, ok, max_gap);
     printf("%u %u %u %u %u %u %u %u %u\n", r.calls, r.discard, st.synced, st.next, st.lost, st.late, st.dup, st.resync, st.overflow);
@@ -28,8 +28,8 @@ static void one(uint32_t max_gap, uint32_t synced, uint32_t next, const long s[4
     // call or discarded, the silence calls are the packets counted lost
     const uint32_t n = leg_calls_count(r.calls);
     uint32_t used = 0, silent = 0;
-    if (n > (uint32_t)kSeqMaxCalls || (r.calls >> (4u + 4u * n)) != 0u) bad++;
-    for (uint32_t j = 0; j < n && j < (uint32_t)kSeqMaxCalls; j++) {
+    if (n > (uint32_t)kLegMaxCalls || (r.calls >> (4u + 4u * n)) != 0u) bad++;
+    for (uint32_t j = 0; j < n && j < (uint32_t)kLegMaxCalls; j++) {
         if (leg_calls_silence(r.calls, j)) {
             silent++;
             continue;
@@ -44,7 +44,7 @@ static void one(uint32_t max_gap, uint32_t synced, uint32_t next, const long s[4
     const LegMixState ms{3200u, 1000000u, 3200u, 16000u};
     const LegSpanCalls sp = leg_cursor_span_calls(ms, 160u, leg_cursor_fresh(), r.calls);
     if (sp.span.count != n || sp.span.dropped != 0u || (n && sp.span.after.tick != ms.tick + ms.play_correct + 320u * n)) bad++;
-    for (uint32_t j = 0; j < n && j < (uint32_t)kSeqMaxCalls; j++)
+    for (uint32_t j = 0; j < n && j < (uint32_t)kLegMaxCalls; j++)
         if (((sp.silence >> j) & 1u) != leg_calls_silence(r.calls, j) || ((sp.span.slots >> (2u * j)) & 3u) != leg_calls_slot(r.calls, j)) bad++;
 }
 

@@ -25,12 +25,14 @@
 // by every tick, so the handle takes ONE compute stream, like wmx_pipe.
 #include <vector>
 #include "wmx_internal.h"
+#include "leg_calls.h"
 
 namespace {
+using wmx::kLegRow;
+using wmx::kLegRowBytes;
 constexpr int kInRow = 176;    // a datagram row in: 172 bytes, rows on 4-byte boundaries
 constexpr int kOutRow = 172;   // 12-byte RTP header + 160 G.711 codes
-constexpr int kPcmRow = 160;   // the 20 ms of one datagram, 1 x 8000
-constexpr uint32_t kPcmBytes = 2 * kPcmRow;
+static_assert(wmx::kLegMaxCalls == WMX_MIX_MAX_LEG_PACKETS, "leg_calls.h and include/wmix_amd.h name one limit");
 }  // namespace
 
 struct wmx_conf {
@@ -73,7 +75,7 @@ struct wmx_conf {
 // the launches of one tick on rows that are on the device
 static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream) {
     const int K = h->max_packets;
-    int rc = wmx_rtp_ingest_legs_codecs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len,
+    int rc = wmx_rtp_ingest_legs_codecs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kLegRow, kLegRow, h->d_len,
                                         h->seq_on ? h->d_seq : nullptr, stream);
     if (rc != 0) return rc;
     if (h->seq_on) {  // in front of the selection: it must not hear a late packet or a duplicate
@@ -81,31 +83,31 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         if (rc != 0) return rc;
     }
     if (h->dtmf_on) {  // in front of the selection: it and the load must see a suppressed row
-        rc = wmx_rtp_detect_dtmf_legs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len,
+        rc = wmx_rtp_detect_dtmf_legs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kLegRow, kLegRow, h->d_len,
                                       h->seq_on ? h->d_calls : nullptr, h->dtmf_pt, h->dtmf_suppress ? 1 : 0, stream);
         if (rc != 0) return rc;
     }
     if (h->denoise_on) {  // behind the keypad, which is judged on the row as it arrived; selection, concealment and the load see the cleaned rows
-        rc = wmx_nsx_process_legs(h->nsx, h->d_pcm, (long)K * kPcmRow, kPcmRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
+        rc = wmx_nsx_process_legs(h->nsx, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
         if (rc != 0) return rc;
     }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
     if (h->max_speakers > 0) {
-        rc = wmx_mix_select_speakers_legs(h->mix, h->d_pcm, kPcmBytes, (long)K * kPcmRow, kPcmRow, K, h->d_len, host_mute, h->max_speakers, h->floor,
-                                          h->decay_shift, h->d_mask, stream);
+        rc = wmx_mix_select_speakers_legs(h->mix, h->d_pcm, kLegRowBytes, (long)K * kLegRow, kLegRow, K, h->d_len, host_mute, h->max_speakers,
+                                          h->floor, h->decay_shift, h->d_mask, stream);
         if (rc != 0) return rc;
         load_mute = h->d_mask;
     }
     if (h->seq_on && h->conceal_on) {  // every call becomes a data call: the plain load, four slots
         constexpr int C = WMX_MIX_MAX_LEG_PACKETS;
-        rc = wmx_rtp_conceal_legs(h->snd, K, h->d_pcm, (long)K * kPcmRow, kPcmRow, h->d_len, h->d_calls, h->d_rep, h->d_rep_len, stream);
+        rc = wmx_rtp_conceal_legs(h->snd, K, h->d_pcm, (long)K * kLegRow, kLegRow, h->d_len, h->d_calls, h->d_rep, h->d_rep_len, stream);
         if (rc != 0) return rc;
-        rc = wmx_mix_load_minus_legs(h->mix, h->d_rep, kPcmBytes, 8000, 1, 16, (long)C * kPcmRow, kPcmRow, C, h->d_rep_len, load_mute, 1, stream);
+        rc = wmx_mix_load_minus_legs(h->mix, h->d_rep, kLegRowBytes, 8000, 1, 16, (long)C * kLegRow, kLegRow, C, h->d_rep_len, load_mute, 1, stream);
     } else if (h->seq_on)
-        rc = wmx_mix_load_minus_legs_calls(h->mix, h->d_pcm, kPcmBytes, 8000, 1, 16, (long)K * kPcmRow, kPcmRow, K, h->d_len, h->d_calls, load_mute, 1,
-                                           stream);
+        rc = wmx_mix_load_minus_legs_calls(h->mix, h->d_pcm, kLegRowBytes, 8000, 1, 16, (long)K * kLegRow, kLegRow, K, h->d_len, h->d_calls, load_mute,
+                                           1, stream);
     else
-        rc = wmx_mix_load_minus_legs(h->mix, h->d_pcm, kPcmBytes, 8000, 1, 16, (long)K * kPcmRow, kPcmRow, K, h->d_len, load_mute, 1, stream);
+        rc = wmx_mix_load_minus_legs(h->mix, h->d_pcm, kLegRowBytes, 8000, 1, 16, (long)K * kLegRow, kLegRow, K, h->d_len, load_mute, 1, stream);
     if (rc != 0) return rc;
     uint32_t bytes = 0;
     rc = wmx_rtp_egress_rings(h->snd, h->mix, d_out, kOutRow, &bytes, stream);
@@ -186,7 +188,7 @@ int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int 
     if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, nullptr, 0, nullptr);
     if (rc == 0) rc = wmx_rtp_set_codecs(h->snd, nullptr, 0, WMX_CODEC_REFERENCE, law, nullptr);
     if (rc == 0) {
-        hipError_t e = hipMalloc(&h->d_pcm, rows * kPcmRow * sizeof(int16_t));
+        hipError_t e = hipMalloc(&h->d_pcm, rows * kLegRow * sizeof(int16_t));
         if (e == hipSuccess) e = hipMalloc(&h->d_len, rows * sizeof(uint32_t));
         const size_t calls_bytes = (size_t)n_legs * sizeof(uint32_t), seq_bytes = rows * sizeof(uint16_t);
         if (e == hipSuccess) e = hipMalloc(&h->d_calls, calls_bytes + 4 + seq_bytes);
@@ -195,7 +197,7 @@ int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int 
         if (e == hipSuccess) e = hipMalloc(&h->d_mute, 2 * (size_t)n_legs);
         if (e == hipSuccess) e = hipMemset(h->d_mute, 0, 2 * (size_t)n_legs);
         if (e == hipSuccess) e = hipMemset(h->d_len, 0, rows * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemset(h->d_pcm, 0, rows * kPcmRow * sizeof(int16_t));
+        if (e == hipSuccess) e = hipMemset(h->d_pcm, 0, rows * kLegRow * sizeof(int16_t));
         if (e == hipSuccess) h->d_mask = h->d_mute + n_legs;
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&h->h_mute), (size_t)n_legs, hipHostMallocDefault);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking);
@@ -284,11 +286,11 @@ int wmx_conf_conceal(wmx_conf *h, int on) {
     if (on && !h->d_rep) {
         const size_t rows = (size_t)h->n_legs * WMX_MIX_MAX_LEG_PACKETS;
         void *p = nullptr;
-        int rc = wmx::zeroed_block(&p, rows * (kPcmRow * sizeof(int16_t) + sizeof(uint32_t)), "hipMemset(repaired rows)");
+        int rc = wmx::zeroed_block(&p, rows * (kLegRow * sizeof(int16_t) + sizeof(uint32_t)), "hipMemset(repaired rows)");
         if (rc == 0 && (rc = wmx_rtp_reset_conceal(h->snd, nullptr, 0, nullptr)) != 0) (void)hipFree(p);
         if (rc != 0) return rc;
         h->d_rep = static_cast<int16_t *>(p);
-        h->d_rep_len = reinterpret_cast<uint32_t *>(h->d_rep + rows * kPcmRow);
+        h->d_rep_len = reinterpret_cast<uint32_t *>(h->d_rep + rows * kLegRow);
     }
     h->conceal_on = on != 0;
     return 0;

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
+#include "wmx_internal.h"  // wave_sync()
 
 namespace wmx {
 
@@ -145,18 +146,7 @@ inline void fft_tables_aec128(FftTables *t) {
 // ---------------------------------------------------------------- device: one wave, data in LDS
 // `a` points to n floats in LDS owned by this wave (packed complex, reference layout);
 // `T` points to the FftTables copy in LDS.  Every lane of the wave must call.  The callers
-// bracket these with wave_sync() (one wave per workgroup).
-
-// Hand-off of LDS data between lanes of ONE wavefront.  The kernels that use this header run one wave per
-// workgroup; a wave's LDS instructions are executed in issue order by the hardware, so a ds_read issued after
-// a ds_write of another lane of the same wave already sees the data.  What is needed is only that the COMPILER
-// keeps the order: a wavefront-scope fence (no s_waitcnt vmcnt(0), no s_barrier -- unlike __syncthreads(),
-// which would also drain every outstanding global load/store at each of the ~40 LDS phases of a block).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
+// bracket these with wave_sync() (wmx_internal.h; one wave per workgroup).
 
 __device__ __forceinline__ int dev_bitrev(int q, int bits) { return (int)(__brev((unsigned)q) >> (32 - bits)); }
 

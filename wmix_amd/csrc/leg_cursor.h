@@ -17,13 +17,12 @@
 // beside the oracle's orc_load_data.
 #pragma once
 #include <cstdint>
+#include "leg_calls.h"
 #include "mix_cursor.h"
 
 #define WMX_LEG_FN WMX_CURSOR_FN
 
 namespace wmx {
-
-constexpr int kLegMaxPackets = 4;  // WMX_MIX_MAX_LEG_PACKETS (include/wmix_amd.h)
 
 using LegMixState = BridgeMixState;
 
@@ -64,7 +63,7 @@ struct LegSpan {
 WMX_LEG_FN LegSpan leg_cursor_span(const LegMixState &m, uint32_t n_out, LegCursor c, uint32_t valid, int max_packets) {
     LegSpan s{0u, 0u, 0u, 0u, c};
     bool stopped = false;
-    for (int k = 0; k < kLegMaxPackets; k++) {
+    for (int k = 0; k < kLegMaxCalls; k++) {
         if (k >= max_packets || !((valid >> k) & 1u)) continue;
         if (stopped) {
             s.dropped++;
@@ -84,9 +83,8 @@ WMX_LEG_FN LegSpan leg_cursor_span(const LegMixState &m, uint32_t n_out, LegCurs
     return s;
 }
 
-// The same for a call list (leg_seq.h: count in bits 0..2, call j in bits 4+4j..: two bits of source slot, one bit "silence"), in
-// list order.  A silence call is a call with zeros (WCT_SILENCE, src/wmixTask.c:1307-1309): it moves the cursor by n_out like a data
-// call and can jump or drop like one.  `silence`: bit j set when the j-th call MADE adds nothing.
+// The same for a call list (leg_calls.h), in list order.  A silence call is a call with zeros (WCT_SILENCE,
+// src/wmixTask.c:1307-1309): it moves the cursor by n_out like a data call and can jump or drop like one.  `silence`: bit j set when the j-th call MADE adds nothing.
 struct LegSpanCalls {
     LegSpan span;
     uint32_t silence;
@@ -94,8 +92,7 @@ struct LegSpanCalls {
 
 WMX_LEG_FN LegSpanCalls leg_cursor_span_calls(const LegMixState &m, uint32_t n_out, LegCursor c, uint32_t calls) {
     LegSpanCalls s{LegSpan{0u, 0u, 0u, 0u, c}, 0u};
-    uint32_t n = calls & 7u;
-    n = n > (uint32_t)kLegMaxPackets ? (uint32_t)kLegMaxPackets : n;
+    const uint32_t n = leg_calls_walked(calls);
     for (uint32_t j = 0; j < n; j++) {
         const LegCall call = leg_cursor_call(m, n_out, s.span.after);
         if (call.drop) {  // the lap rule: this call and the list's tail are left out
@@ -103,8 +100,8 @@ WMX_LEG_FN LegSpanCalls leg_cursor_span_calls(const LegMixState &m, uint32_t n_o
             break;
         }
         if (s.span.count == 0) s.span.start = call.start;
-        s.span.slots |= ((calls >> (4u + 4u * j)) & 3u) << (2u * s.span.count);
-        s.silence |= ((calls >> (6u + 4u * j)) & 1u) << s.span.count;
+        s.span.slots |= leg_calls_slot(calls, j) << (2u * s.span.count);
+        s.silence |= leg_calls_silence(calls, j) << s.span.count;
         s.span.count++;
         s.span.after = call.after;
     }

@@ -24,10 +24,8 @@
 //     P_r* + P_c* >= 32 E
 //   hold.  The numbers are part of the rule.
 //
-// PER LEG AND TICK the leg's blocks are taken in the order the load makes its calls: without a call list the slots k = 0 ..
-// max_packets - 1 with d_len == 320 in slot order; with one, the list wmx_rtp_sequence_legs leaves (leg_seq.h), in list order, where a
-// silence call or a data call naming a row that is not readable (leg_plc_silence of leg_plc.h) is a block that is not a tone.  A leg
-// with no block this tick keeps its state.  Every block is judged on its row as the tick brought it.
+// PER LEG AND TICK the leg's blocks are its calls in the order of leg_calls.h's walk; a call that adds nothing there is a block that is
+// not a tone.  A leg with no block this tick keeps its state.  Every block is judged on its row as the tick brought it.
 //
 // DEBOUNCE.  cand = the previous block's digit or none; cur = the digit that is down or none.  A block that is a tone of d with
 // cand == d and cur != d reports d once and sets cur = d.  A block that is not a tone after a block that was not a tone either sets
@@ -50,13 +48,12 @@
 // written from the text above.
 #pragma once
 #include <cstdint>
-#include "leg_plc.h"
+#include "leg_calls.h"
 
-#define WMX_DTMF_FN WMX_SEQ_FN
+#define WMX_DTMF_FN WMX_CALLS_FN
 
 namespace wmx {
 
-constexpr int kDtmfRow = kPlcRow;  // samples of one block
 constexpr int kDtmfFreqs = 8;
 constexpr int32_t kDtmfNone = -1;
 constexpr int64_t kDtmfMinPower = 400000000;
@@ -146,7 +143,7 @@ WMX_DTMF_FN int32_t leg_dtmf_decide(const int64_t p[kDtmfFreqs], int64_t e) {
 WMX_DTMF_FN int64_t leg_dtmf_goertzel(const int16_t *x, int f) {
     const int32_t coef = leg_dtmf_coef(f);
     int32_t s1 = 0, s2 = 0;
-    for (int n = 0; n < kDtmfRow; n++) leg_dtmf_step(s1, s2, coef, x[n]);
+    for (int n = 0; n < kLegRow; n++) leg_dtmf_step(s1, s2, coef, x[n]);
     return leg_dtmf_power(s1, s2, coef);
 }
 
@@ -154,7 +151,7 @@ WMX_DTMF_FN int64_t leg_dtmf_goertzel(const int16_t *x, int f) {
 WMX_DTMF_FN int32_t leg_dtmf_block_digit(const int16_t *x, int64_t *p_out, int64_t *e_out) {
     int64_t p[kDtmfFreqs], e = 0;
     for (int f = 0; f < kDtmfFreqs; f++) p[f] = leg_dtmf_goertzel(x, f);
-    for (int n = 0; n < kDtmfRow; n++) e = leg_dtmf_energy(e, x[n]);
+    for (int n = 0; n < kLegRow; n++) e = leg_dtmf_energy(e, x[n]);
     for (int f = 0; p_out && f < kDtmfFreqs; f++) p_out[f] = p[f];
     if (e_out) *e_out = e;
     return leg_dtmf_decide(p, e);
@@ -190,43 +187,33 @@ WMX_DTMF_FN void leg_dtmf_debounce(LegDtmfState &st, int32_t digit) {
     leg_dtmf_set(st, leg_dtmf_has_ts(st), digit, cur);
 }
 
-// the leg's blocks of the tick as a call list (leg_seq.h's layout): the list given, or the readable slots in slot order
-WMX_DTMF_FN uint32_t leg_dtmf_list(bool have_calls, uint32_t calls, uint32_t readable, int max_packets) {
-    if (have_calls) return calls;
-    uint32_t list = 0;
-    for (int k = 0; k < kSeqMaxCalls && k < max_packets; k++)
-        if ((readable >> k) & 1u) list = leg_calls_push(list, (uint32_t)k, 0u);
-    return list;
-}
-
 WMX_DTMF_FN uint32_t leg_dtmf_word(const uint8_t *p) {  // four raw bytes as a little-endian machine loads them
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
 // One tick of one leg on the host.  packets: slot k at packets + k * packet_stride; recv, len: max_packets entries; pcm: slot k at
-// pcm + k * pcm_packet_stride, zeroed in place where suppress says so; digits (kSeqMaxCalls entries, may be NULL): the per-block
+// pcm + k * pcm_packet_stride, zeroed in place where suppress says so; digits (kLegMaxCalls entries, may be NULL): the per-block
 // decisions in block order, kDtmfNone behind the last.  -> the number of blocks
 WMX_DTMF_FN uint32_t leg_dtmf_tick(LegDtmfState &st, const uint8_t *packets, long packet_stride, const int32_t *recv, int16_t *pcm,
                                    long pcm_packet_stride, const uint32_t *len, int max_packets, bool have_calls, uint32_t calls,
                                    uint32_t event_pt, bool suppress, int32_t *digits) {
-    for (int k = 0; k < kSeqMaxCalls && k < max_packets; k++) {
+    for (int k = 0; k < kLegMaxCalls && k < max_packets; k++) {
         const uint8_t *pkt = packets + (size_t)k * packet_stride;
         if (recv[k] >= (int32_t)kDtmfMinEventBytes) leg_dtmf_packet(st, recv[k], pkt[1], pkt[12], leg_dtmf_word(pkt + 4), event_pt);
     }
-    uint32_t readable = 0;
-    for (int k = 0; k < kSeqMaxCalls && k < max_packets; k++) readable |= leg_plc_readable(len[k]) << k;
-    const uint32_t list = leg_dtmf_list(have_calls, calls, readable, max_packets), count = leg_plc_count(list);
-    int32_t d[kSeqMaxCalls] = {kDtmfNone, kDtmfNone, kDtmfNone, kDtmfNone};
+    const LegWalk w = leg_calls_walk(len, have_calls, calls, max_packets);
+    const uint32_t list = w.list, count = w.count;
+    int32_t d[kLegMaxCalls] = {kDtmfNone, kDtmfNone, kDtmfNone, kDtmfNone};
     for (uint32_t j = 0; j < count; j++) {
-        if (!leg_plc_silence(list, j, readable)) d[j] = leg_dtmf_block_digit(pcm + (size_t)leg_calls_slot(list, j) * pcm_packet_stride, nullptr, nullptr);
+        if ((w.data >> j) & 1u) d[j] = leg_dtmf_block_digit(pcm + (size_t)leg_calls_slot(list, j) * pcm_packet_stride, nullptr, nullptr);
         leg_dtmf_debounce(st, d[j]);
     }
     for (uint32_t j = 0; suppress && j < count; j++) {
         if (d[j] == kDtmfNone) continue;
         int16_t *row = pcm + (size_t)leg_calls_slot(list, j) * pcm_packet_stride;
-        for (int i = 0; i < kDtmfRow; i++) row[i] = 0;
+        for (int i = 0; i < kLegRow; i++) row[i] = 0;
     }
-    for (int j = 0; digits && j < kSeqMaxCalls; j++) digits[j] = d[j];
+    for (int j = 0; digits && j < kLegMaxCalls; j++) digits[j] = d[j];
     return count;
 }
 

@@ -8,8 +8,8 @@
 // Integers only; >> is an arithmetic shift on int32.
 //
 // Per leg: hist[320], the last 320 samples the leg emitted, newest at 319, zero when fresh; concealed, a counter.
-// Per tick: the leg's PCM rows, d_len and the call list as wmx_rtp_sequence_legs leaves them, walked in list order.  A data call that
-// names a slot k >= max_packets or a slot with d_len != 320 is a silence call, as the load treats it.
+// Per tick: the leg's PCM rows, d_len and the call list as wmx_rtp_sequence_legs leaves them, walked in list order by the one walk
+// of leg_calls.h: a data call that names a row that is not readable is a silence call here, as the load treats it.
 //   A RUN is a maximal sequence of consecutive silence calls of the list.  At its start h0 = hist is frozen, q[i] = h0[i] >> 4
 //   (|q| <= 2048) and for every lag L in 40 .. 120: c(L) = sum over i = 160 .. 319 of q[i] * q[i - L] (i - L >= 40; |c| <= 160 * 2^22
 //   < 2^31).  L* = the smallest L with the largest c(L): no normalisation, no threshold; an all-zero history gives 40 and zeros out.
@@ -25,18 +25,16 @@
 // written from the text above.
 #pragma once
 #include <cstdint>
-#include "leg_seq.h"
+#include "leg_calls.h"
 
-#define WMX_PLC_FN WMX_SEQ_FN
+#define WMX_PLC_FN WMX_CALLS_FN
 
 namespace wmx {
 
-constexpr int kPlcHist = 320;    // samples of history per leg
-constexpr int kPlcRow = 160;     // samples of one call: 20 ms of 1 x 8000
-constexpr int kPlcLagMin = 40;   // 200 Hz
-constexpr int kPlcLagMax = 120;  // 66 Hz
-constexpr int kPlcBlend = 32;    // samples of cross-fade behind a run
-constexpr uint32_t kPlcRowBytes = 2u * kPlcRow;
+constexpr int kPlcHist = 2 * kLegRow;  // samples of history per leg
+constexpr int kPlcLagMin = 40;         // 200 Hz
+constexpr int kPlcLagMax = 120;        // 66 Hz
+constexpr int kPlcBlend = 32;          // samples of cross-fade behind a run
 
 struct LegPlcState {
     int16_t hist[kPlcHist];
@@ -48,7 +46,7 @@ WMX_PLC_FN int32_t leg_plc_q(int32_t h) { return h >> 4; }
 // c(L) over q[0 .. 319]
 WMX_PLC_FN int32_t leg_plc_score(const int16_t *q, int32_t L) {
     int32_t c = 0;
-    for (int i = kPlcHist - kPlcRow; i < kPlcHist; i++) c += (int32_t)q[i] * (int32_t)q[i - L];
+    for (int i = kPlcHist - kLegRow; i < kPlcHist; i++) c += (int32_t)q[i] * (int32_t)q[i - L];
     return c;
 }
 
@@ -68,32 +66,18 @@ WMX_PLC_FN int32_t leg_plc_synth(int32_t s, int32_t k) { return (s * leg_plc_gai
 // sample i < kPlcBlend of the data call behind a run: x from the packet, cont the run continued
 WMX_PLC_FN int32_t leg_plc_blend(int32_t x, int32_t cont, int32_t i) { return (x * i + cont * (kPlcBlend - i)) >> 5; }
 
-// a slot's row is readable: bit k of the mask a leg's tick is walked with (slots k >= max_packets: 0)
-WMX_PLC_FN uint32_t leg_plc_readable(uint32_t len) { return len == kPlcRowBytes ? 1u : 0u; }
-
-// call j of the list is made with zeros by the load: marked so, or it names a row that is not readable
-WMX_PLC_FN bool leg_plc_silence(uint32_t calls, uint32_t j, uint32_t readable) {
-    return leg_calls_silence(calls, j) || !((readable >> leg_calls_slot(calls, j)) & 1u);
-}
-
-WMX_PLC_FN uint32_t leg_plc_count(uint32_t calls) {
-    const uint32_t n = leg_calls_count(calls);
-    return n > (uint32_t)kSeqMaxCalls ? (uint32_t)kSeqMaxCalls : n;
-}
-
 // One tick of one leg.  pcm: the leg's rows, slot k at pcm + k * packet_stride; len: its max_packets entries of d_len; out:
-// kSeqMaxCalls rows of kPlcRow, of which the first `count` are written; len_out: kSeqMaxCalls entries.
+// kLegMaxCalls rows of kLegRow, of which the first `count` are written; len_out: kLegMaxCalls entries.
 WMX_PLC_FN void leg_plc_tick(LegPlcState &st, const int16_t *pcm, long packet_stride, const uint32_t *len, int max_packets, uint32_t calls,
                              int16_t *out, uint32_t *len_out) {
-    const uint32_t count = leg_plc_count(calls);
-    for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++) len_out[j] = j < count ? kPlcRowBytes : 0u;
-    uint32_t readable = 0;
-    for (int k = 0; k < kSeqMaxCalls && k < max_packets; k++) readable |= leg_plc_readable(len[k]) << k;
+    const LegWalk w = leg_calls_walk(len, true, calls, max_packets);
+    const uint32_t count = w.count;
+    for (uint32_t j = 0; j < (uint32_t)kLegMaxCalls; j++) len_out[j] = j < count ? kLegRowBytes : 0u;
     int16_t h0[kPlcHist] = {0}, q[kPlcHist];
     int32_t lag = kPlcLagMin, run = 0;  // run: silence calls of the run so far
     for (uint32_t j = 0; j < count; j++) {
-        int16_t *y = out + (size_t)j * kPlcRow;
-        if (leg_plc_silence(calls, j, readable)) {
+        int16_t *y = out + (size_t)j * kLegRow;
+        if (!((w.data >> j) & 1u)) {
             if (run == 0) {
                 for (int i = 0; i < kPlcHist; i++) h0[i] = st.hist[i], q[i] = (int16_t)leg_plc_q(st.hist[i]);
                 int32_t best = leg_plc_score(q, kPlcLagMin);
@@ -102,17 +86,17 @@ WMX_PLC_FN void leg_plc_tick(LegPlcState &st, const int16_t *pcm, long packet_st
                     if (leg_plc_better(c, L, best, lag)) best = c, lag = L;
                 }
             }
-            for (int i = 0; i < kPlcRow; i++) {
-                const int32_t k = run * kPlcRow + i;
+            for (int i = 0; i < kLegRow; i++) {
+                const int32_t k = run * kLegRow + i;
                 y[i] = (int16_t)leg_plc_synth(h0[leg_plc_index(k, lag)], k);
             }
             run++;
             st.concealed++;
         } else {
             const int16_t *x = pcm + (size_t)leg_calls_slot(calls, j) * packet_stride;
-            for (int i = 0; i < kPlcRow; i++) {
+            for (int i = 0; i < kLegRow; i++) {
                 if (run > 0 && i < kPlcBlend) {
-                    const int32_t k = run * kPlcRow + i;
+                    const int32_t k = run * kLegRow + i;
                     y[i] = (int16_t)leg_plc_blend(x[i], leg_plc_synth(h0[leg_plc_index(k, lag)], k), i);
                 } else {
                     y[i] = x[i];
@@ -121,8 +105,8 @@ WMX_PLC_FN void leg_plc_tick(LegPlcState &st, const int16_t *pcm, long packet_st
             run = 0;
             lag = kPlcLagMin;
         }
-        for (int i = 0; i < kPlcHist - kPlcRow; i++) st.hist[i] = st.hist[i + kPlcRow];
-        for (int i = 0; i < kPlcRow; i++) st.hist[kPlcHist - kPlcRow + i] = y[i];
+        for (int i = 0; i < kPlcHist - kLegRow; i++) st.hist[i] = st.hist[i + kLegRow];
+        for (int i = 0; i < kLegRow; i++) st.hist[kPlcHist - kLegRow + i] = y[i];
     }
 }
 

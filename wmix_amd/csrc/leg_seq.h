@@ -16,7 +16,7 @@
 //   4. every other ok slot is a candidate with forward distance u_k = (uint16)(s_k - next); candidates ascending by u, ties by slot; a
 //      candidate with its predecessor's u is a duplicate: discarded, dup++.
 //   5. walk with pos = 0: gap = u - pos.  gap > max_gap: resync++, the candidate continues with gap 0.  The candidate needs gap silence
-//      calls and one data call; if they do not fit in what is left of kLegMaxPackets calls, it and every later candidate are discarded
+//      calls and one data call; if they do not fit in what is left of kLegMaxCalls calls, it and every later candidate are discarded
 //      (overflow counts them) and the walk ends; else they are emitted, lost += gap, pos = u + 1.  A packet more than
 //      WMX_RTP_SEQ_MISORDER back is a far-ahead candidate by the uint16 arithmetic and resyncs.
 //   6. next += pos.  No trailing silence: a packet that has not come yet may come next tick.
@@ -26,16 +26,12 @@
 // written from the text above.
 #pragma once
 #include <cstdint>
+#include "leg_calls.h"
 
-#if defined(__HIPCC__)
-#define WMX_SEQ_FN __host__ __device__ inline
-#else
-#define WMX_SEQ_FN inline
-#endif
+#define WMX_SEQ_FN WMX_CALLS_FN
 
 namespace wmx {
 
-constexpr int kSeqMaxCalls = 4;        // kLegMaxPackets (leg_cursor.h): calls per leg and tick
 constexpr uint32_t kSeqMisorder = 16;  // WMX_RTP_SEQ_MISORDER (include/wmix_amd.h)
 
 struct LegSeqState {
@@ -44,18 +40,9 @@ struct LegSeqState {
 };
 
 struct LegSeqTick {
-    uint32_t calls;    // the call list (WMX_RTP_CALLS_* of include/wmix_amd.h)
+    uint32_t calls;    // the call list (leg_calls.h)
     uint32_t discard;  // bit k: slot k was ok and makes no call
 };
-
-// the call list's layout
-WMX_SEQ_FN uint32_t leg_calls_count(uint32_t calls) { return calls & 7u; }
-WMX_SEQ_FN uint32_t leg_calls_slot(uint32_t calls, uint32_t j) { return (calls >> (4u + 4u * j)) & 3u; }
-WMX_SEQ_FN uint32_t leg_calls_silence(uint32_t calls, uint32_t j) { return (calls >> (6u + 4u * j)) & 1u; }
-WMX_SEQ_FN uint32_t leg_calls_push(uint32_t calls, uint32_t slot, uint32_t silence) {
-    const uint32_t j = calls & 7u;
-    return ((calls & ~7u) | (j + 1u)) | ((slot | (silence << 2)) << (4u + 4u * j));
-}
 
 WMX_SEQ_FN void leg_seq_cswap(uint32_t &a, uint32_t &b) {
     const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
@@ -63,20 +50,20 @@ WMX_SEQ_FN void leg_seq_cswap(uint32_t &a, uint32_t &b) {
 }
 
 // One tick of one leg.  seq[k]: the sequence number of slot k in host order; ok: bit k set when slot k is a call; max_gap 0 .. 3.
-WMX_SEQ_FN LegSeqTick leg_seq_tick(LegSeqState &st, const uint32_t seq[kSeqMaxCalls], uint32_t ok, uint32_t max_gap) {
+WMX_SEQ_FN LegSeqTick leg_seq_tick(LegSeqState &st, const uint32_t seq[kLegMaxCalls], uint32_t ok, uint32_t max_gap) {
     LegSeqTick r{0u, 0u};
-    ok &= (1u << kSeqMaxCalls) - 1u;
+    ok &= (1u << kLegMaxCalls) - 1u;
     if (!ok) return r;
     if (!st.synced) {
         st.synced = 1u;
-        for (int k = kSeqMaxCalls - 1; k >= 0; k--)
+        for (int k = kLegMaxCalls - 1; k >= 0; k--)
             if ((ok >> k) & 1u) st.next = seq[k] & 0xFFFFu;
     }
     const uint32_t next = st.next & 0xFFFFu;
     // the candidates' keys u << 2 | k (18 bits); a slot that is none sorts behind them
     constexpr uint32_t kNone = 0xFFFFFFFFu;
-    uint32_t key[kSeqMaxCalls];
-    for (int k = 0; k < kSeqMaxCalls; k++) {
+    uint32_t key[kLegMaxCalls];
+    for (int k = 0; k < kLegMaxCalls; k++) {
         key[k] = kNone;
         if (!((ok >> k) & 1u)) continue;
         const uint32_t back = (next - seq[k]) & 0xFFFFu;
@@ -94,7 +81,7 @@ WMX_SEQ_FN LegSeqTick leg_seq_tick(LegSeqState &st, const uint32_t seq[kSeqMaxCa
     leg_seq_cswap(key[1], key[2]);
     uint32_t pos = 0, prev_u = kNone;
     bool full = false;
-    for (int i = 0; i < kSeqMaxCalls; i++) {
+    for (int i = 0; i < kLegMaxCalls; i++) {
         if (key[i] == kNone) continue;
         const uint32_t u = key[i] >> 2, k = key[i] & 3u;
         if (u == prev_u) {
@@ -113,7 +100,7 @@ WMX_SEQ_FN LegSeqTick leg_seq_tick(LegSeqState &st, const uint32_t seq[kSeqMaxCa
             st.resync++;
             gap = 0;
         }
-        if (leg_calls_count(r.calls) + gap + 1u > (uint32_t)kSeqMaxCalls) {
+        if (leg_calls_count(r.calls) + gap + 1u > (uint32_t)kLegMaxCalls) {
             full = true;
             st.overflow++;
             r.discard |= 1u << k;

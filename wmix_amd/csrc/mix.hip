@@ -27,6 +27,8 @@
 namespace wmx {
 namespace {
 
+static_assert(kLegMaxCalls == WMX_MIX_MAX_LEG_PACKETS, "leg_calls.h and include/wmix_amd.h name one limit");
+
 // ---------------------------------------------------------------- kernels
 __global__ __launch_bounds__(256) void zoom_kernel(const int16_t *__restrict__ in, int16_t *__restrict__ out,
                                                    const int32_t *__restrict__ idx, uint32_t n_out, long in_stride, long out_stride,
@@ -314,22 +316,22 @@ __global__ __launch_bounds__(256) void select_speakers_legs_kernel(const int16_t
         int shift = 5;  // log2 of L
         while ((n << shift) > 64) shift--;
         const int L = 1 << shift, q = lane >> shift, sub = lane & (L - 1);
-        uint32_t sum[kLegMaxPackets];
+        uint32_t sum[kLegMaxCalls];
 #pragma unroll
-        for (int k = 0; k < kLegMaxPackets; k++) sum[k] = 0;
+        for (int k = 0; k < kLegMaxCalls; k++) sum[k] = 0;
         if (q < n) {
             const int32_t ri = mem[q];
             if (ri >= 0 && ri < n_groups) {
                 const int16_t *rows = src + (size_t)ri * source_stride;
 #pragma unroll
-                for (int k = 0; k < kLegMaxPackets; k++)
+                for (int k = 0; k < kLegMaxCalls; k++)
                     if (k < max_packets && len[(size_t)ri * max_packets + k] == srcU8Len)
                         sum[k] = abs_sum_part(rows + (size_t)k * packet_stride, n_el, (uint32_t)sub, (uint32_t)L);
             }
         }
         uint32_t best = 0;
 #pragma unroll
-        for (int k = 0; k < kLegMaxPackets; k++) {
+        for (int k = 0; k < kLegMaxCalls; k++) {
             uint32_t s = sum[k];
             for (int o = L >> 1; o > 0; o >>= 1) s += (uint32_t)__shfl_xor((int)s, o);
             best = s > best ? s : best;
@@ -355,7 +357,7 @@ struct LegSpanEntry {
 // slots are calls (d_len), applies the rule (at most WMX_MIX_MAX_LEG_PACKETS steps) and writes the span, the new cursor and the drop
 // count; an xor-shuffle over the wave gives the window.  Rings outside every conference of two or more members are not visited:
 // their cursors stay.  A cursor read from memory never indexes anything as it is: the span's start is reduced into the ring here.
-// CALLS (wmx_mix_load_minus_legs_calls): the leg's calls are those of its call list (leg_seq.h), in list order, instead of its valid
+// CALLS (wmx_mix_load_minus_legs_calls): the leg's calls are those of its call list (leg_calls.h), in list order, instead of its valid
 // slots in slot order; a data call that names a slot that is not readable (d_len) is made with zeros, and the span's pad carries the
 // silence mask of the calls made.
 template <bool CALLS>
@@ -378,15 +380,14 @@ __global__ __launch_bounds__(256) void leg_cursor_kernel(const int32_t *__restri
             const int32_t r = mem[lane];
             if (r >= 0 && r < n_groups) {
                 uint32_t valid = 0;
-                for (int k = 0; k < kLegMaxPackets; k++)
+                for (int k = 0; k < kLegMaxCalls; k++)
                     if (k < max_packets && len[(size_t)r * max_packets + k] == srcU8Len) valid |= 1u << k;
                 uint32_t list = 0, silence = 0;
                 if (CALLS) {
                     list = calls[r];
-                    uint32_t n_calls = list & 7u;
-                    n_calls = n_calls > (uint32_t)kLegMaxPackets ? (uint32_t)kLegMaxPackets : n_calls;
+                    const uint32_t n_calls = leg_calls_walked(list);
                     for (uint32_t j = 0; j < n_calls; j++)  // a data call whose slot's row is not readable: a call with zeros
-                        if (!((valid >> ((list >> (4u + 4u * j)) & 3u)) & 1u)) list |= 1u << (6u + 4u * j);
+                        if (!((valid >> leg_calls_slot(list, j)) & 1u)) list = leg_calls_set_silence(list, j);
                     valid = n_calls;
                 }
                 if (valid) {
@@ -464,7 +465,7 @@ __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restric
                     const LegSpanEntry e = span[r];
                     const uint32_t st = e.start < ring_samples ? e.start : 0u;
                     const uint32_t d = pos >= st ? pos - st : pos + ring_samples - st;
-                    if (d >= e.len || d >= (uint32_t)kLegMaxPackets * n_out) return false;
+                    if (d >= e.len || d >= (uint32_t)kLegMaxCalls * n_out) return false;
                     const uint32_t j = (d >= n_out) + (d >= 2 * n_out) + (d >= 3 * n_out);  // the call, 0 .. 3, and its sample
                     if (CALLS && ((e.pad >> j) & 1u)) return false;
                     const uint32_t k = (e.slots >> (2u * j)) & 3u;

@@ -25,7 +25,7 @@
 #include "stage_life.h"
 #include "spl_fx.h"
 #include "fx_tables.h"
-#include "leg_dtmf.h"
+#include "leg_calls.h"
 
 namespace wmx {
 namespace {
@@ -1132,9 +1132,8 @@ __global__ __launch_bounds__((64 * NsxShape<ANA, CHN>::WPB)) __attribute__((amdg
 }
 
 // The ragged form for the legs of a conference bridge (wmx_nsx_process_legs): 8 kHz mono, one wave per leg like nsx_kernel, but a leg
-// brings 0 .. 4 rows of 160 samples this tick, the count is known only here (len, calls) and the order is the load's: the rule of
-// leg_dtmf.h -- without a call list the readable slots in slot order, with one the list in list order, where a silence call or a
-// data call naming a row that is not readable feeds nothing (a lost packet is not 20 ms of zeros to the noise estimator).  Each row
+// brings 0 .. 4 rows of 160 samples this tick, the count is known only here (len, calls) and the order is the load's: the walk of
+// leg_calls.h, where a call that adds nothing feeds nothing (a lost packet is not 20 ms of zeros to the noise estimator).  Each row
 // taken is two 80-sample blocks of nsx_block, in place.  The list, the mask of calls taken and every row address are wave-uniform
 // (scalar registers): the walk costs a few scalar instructions per row and nothing per sample.  A leg with no row this tick leaves
 // behind the barrier without having loaded or stored its state; a workgroup none of whose legs has a row leaves before it copies
@@ -1145,22 +1144,15 @@ __global__ __launch_bounds__((64 * NsxShape<128, 1>::WPB)) __attribute__((amdgpu
     int denoise_bound, const uint8_t *__restrict__ active) {
     using Y = NsxLayout<128>;
     constexpr int WORDS = Y::WORDS_MONO, BLOCK = 80, WPB = NsxShape<128, 1>::WPB;
-    static_assert(2 * BLOCK == kDtmfRow, "a row of the bridge is two blocks of the 8 kHz suppressor");
+    static_assert(2 * BLOCK == kLegRow, "a row of the bridge is two blocks of the 8 kHz suppressor");
     __shared__ NsxConsts K;
     __shared__ NsxWave<128, 1> WS[WPB];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const long s = (long)blockIdx.x * WPB + wave;
     uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
     if (stream_active(active, (int)s, n_legs)) {
-        uint32_t readable = 0;
-#pragma unroll
-        for (int k = 0; k < kSeqMaxCalls; k++)
-            if (k < max_packets) readable |= leg_plc_readable(len[s * max_packets + k]) << k;
-        list = leg_dtmf_list(calls_in != nullptr, calls_in ? calls_in[s] : 0u, readable, max_packets);
-        const uint32_t count = leg_plc_count(list);
-#pragma unroll
-        for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++)
-            if (j < count && !leg_plc_silence(list, j, readable)) take |= 1u << j;
+        const LegWalk w = leg_calls_walk(len + s * max_packets, calls_in != nullptr, calls_in ? calls_in[s] : 0u, max_packets);
+        list = w.list, take = w.data;
     }
     list = (uint32_t)__builtin_amdgcn_readfirstlane((int)list);
     take = (uint32_t)__builtin_amdgcn_readfirstlane((int)take);
@@ -1184,7 +1176,7 @@ __global__ __launch_bounds__((64 * NsxShape<128, 1>::WPB)) __attribute__((amdgpu
     int16_t *hs = hist + s * (long)(3 * kNsxHist);
     int16_t *rows = pcm + s * leg_stride;
 #pragma unroll 1
-    for (uint32_t b = 0; b < 2u * (uint32_t)kSeqMaxCalls; b++) {
+    for (uint32_t b = 0; b < 2u * (uint32_t)kLegMaxCalls; b++) {
         const uint32_t j = b >> 1;
         if (!((take >> j) & 1u)) continue;
         int16_t *row = rows + (long)leg_calls_slot(list, j) * packet_stride + (long)(b & 1u) * BLOCK;
@@ -1391,13 +1383,13 @@ int wmx_nsx_process_legs(wmx_nsx *h, int16_t *d_pcm, long leg_stride, long packe
         set_error("wmx_nsx_process_legs: the handle must be 1 x 8000 (it is %d x %d)", h ? h->chn : 0, h ? h->freq : 0);
         return WMX_EINVAL;
     }
-    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kSeqMaxCalls) {
-        set_error("wmx_nsx_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kSeqMaxCalls);
+    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls) {
+        set_error("wmx_nsx_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kLegMaxCalls);
         return WMX_EINVAL;
     }
-    if (packet_stride < kDtmfRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
+    if (packet_stride < kLegRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
         set_error("wmx_nsx_process_legs: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", packet_stride,
-                  kDtmfRow, leg_stride, max_packets);
+                  kLegRow, leg_stride, max_packets);
         return WMX_EINVAL;
     }
     if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is

@@ -8,38 +8,139 @@
 // encode.  Ingest replaces rtp_recv's payload-size rule + G711a2PCM (src/rtp.c:86-95, src/wmixTask.c:1278-1282).
 // The zoom's float32 phase walk is data independent and runs once per call on the host (mix.hip) -- the kernel
 // gathers through the list.  Integer path: bit-exact.
+#include <initializer_list>
 #include <vector>
 #include "wmx_internal.h"
 #include "g711_dev.h"
+#include "leg_calls.h"
 #include "leg_seq.h"
 #include "leg_plc.h"
 #include "leg_codec.h"
 #include "leg_dtmf.h"
 
+namespace wmx {
+namespace {
+
+// ---- state per leg: one table, three functions.  A rule's state is ONE device block of columns: column c holds one entry of
+// col[c].bytes per leg, its fresh value the byte col[c].fill repeated, and the columns lie behind one another in table order -- so a
+// table lists its widest column first and every column starts on its entry's alignment.  A state is made by the first call that
+// needs it (make), put back to fresh for a list of legs or for all (reset) and read out (export_to).
+struct LegColumn {
+    size_t bytes;
+    int fill;
+};
+
+struct LegState {
+    static constexpr int kMaxColumns = 7;
+    const char *what = "";  // names the state in an error text
+    size_t n_legs = 0;
+    int n_cols = 0;
+    LegColumn col[kMaxColumns] = {};
+    uint8_t *p = nullptr;  // NULL: not made, every leg is fresh
+
+    LegState() = default;
+    LegState(const char *what_, int n_legs_, std::initializer_list<LegColumn> cols) : what(what_), n_legs((size_t)n_legs_) {
+        for (const LegColumn &c : cols) col[n_cols++] = c;
+    }
+    size_t offset(int c) const {  // of column c in the block; c = n_cols: the block's size
+        size_t per_leg = 0;
+        for (int i = 0; i < c; i++) per_leg += col[i].bytes;
+        return per_leg * n_legs;
+    }
+    template <class T>
+    T *at(int c) const {
+        return p ? reinterpret_cast<T *>(p + offset(c)) : nullptr;
+    }
+    // the columns c .. run_end - 1 hold one fill byte (same_width: and one width): one memset sets them
+    int run_end(int c, bool same_width) const {
+        int e = c + 1;
+        while (e < n_cols && col[e].fill == col[c].fill && (!same_width || col[e].bytes == col[c].bytes)) e++;
+        return e;
+    }
+
+    // the block, fresh and complete on the device when this returns
+    int make() {
+        if (p) return 0;
+        void *q = nullptr;
+        WMX_HIP(hipMalloc(&q, offset(n_cols)));
+        hipError_t e = hipSuccess;
+        for (int c = 0; c < n_cols && e == hipSuccess; c = run_end(c, false))
+            e = hipMemset(static_cast<uint8_t *>(q) + offset(c), col[c].fill, offset(run_end(c, false)) - offset(c));
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return hip_fail(e, what, __FILE__, __LINE__);
+        }
+        p = static_cast<uint8_t *>(q);
+        return 0;
+    }
+
+    // the listed legs (NULL = all) fresh again, on `s`.  A bad index: WMX_EINVAL and nothing touched.  `who` opens the error text.
+    int reset(const char *who, const int32_t *host_idx, int n, hipStream_t s) {
+        if ((host_idx && n < 0) || idx_check(host_idx, n, (int)n_legs, who, "handle")) return WMX_EINVAL;
+        if (!p) return make();  // made just now: fresh already
+        if (!host_idx) {
+            for (int c = 0; c < n_cols; c = run_end(c, false))
+                WMX_HIP(hipMemsetAsync(p + offset(c), col[c].fill, offset(run_end(c, false)) - offset(c), s));
+            return 0;
+        }
+        // a handful of legs at a time: nothing of the list goes to the device.  The leg's entry in each column; columns of one width
+        // are the rows of one 2-D memset
+        for (int i = 0; i < n; i++)
+            for (int c = 0; c < n_cols; c = run_end(c, true)) {
+                uint8_t *entry = p + offset(c) + (size_t)host_idx[i] * col[c].bytes;
+                const int rows = run_end(c, true) - c;
+                if (rows == 1)
+                    WMX_HIP(hipMemsetAsync(entry, col[c].fill, col[c].bytes, s));
+                else
+                    WMX_HIP(hipMemset2DAsync(entry, n_legs * col[c].bytes, col[c].fill, col[c].bytes, (size_t)rows, s));
+            }
+        return 0;
+    }
+
+    // dst[c], where not NULL, takes column c of every leg as the work queued on `s` leaves it; blocking
+    int export_to(std::initializer_list<void *> dst, hipStream_t s) const {
+        if (p) WMX_HIP(hipStreamSynchronize(s));
+        int c = 0;
+        for (void *d : dst) {
+            const size_t bytes = n_legs * col[c].bytes;
+            if (d && p)
+                WMX_HIP(hipMemcpy(d, p + offset(c), bytes, hipMemcpyDeviceToHost));
+            else if (d)
+                memset(d, col[c].fill, bytes);  // never made: fresh
+            c++;
+        }
+        return 0;
+    }
+
+    void destroy() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+};
+
+// the columns of the handle's five states
+enum { kSendSeq, kSendTs };
+enum { kSeqSynced, kSeqNext, kSeqLost, kSeqLate, kSeqDup, kSeqResync, kSeqOverflow, kSeqWords };
+enum { kCodecRefused, kCodecIn, kCodecOutLaw };
+enum { kPlcColHist, kPlcColConcealed };
+enum { kDtmfRing, kDtmfCount, kDtmfTs, kDtmfFlags };
+
+}  // namespace
+}  // namespace wmx
+
 struct wmx_rtp {
     int device;  // the HIP device the state lives on (current device at create); every entry point switches to it
     int n_streams, law;
-    uint32_t *d_seq;  // per stream: sequence number (low 16 bits significant)
-    uint32_t *d_ts;   // per stream: timestamp
     wmx::SchedCache sched;  // gather list per egress format, never rewritten (see SchedCache)
     std::vector<int32_t> idx;
-    // the sequence rule's state per leg (leg_seq.h), made by the first call that needs it: kSeqWords arrays of n_streams uint32 in
-    // one block -- synced, next, lost, late, dup, resync, overflow
-    uint32_t *d_sq;
-    // the codec rule's state per stream (leg_codec.h), made by the first call that needs it, one block: refused (uint32), in_codec and
-    // out_law (uint8).  codecs_default: no stream has left in_codec REFERENCE / out_law = law, so the launches are those of a handle
-    // that knows no codecs
-    uint32_t *d_refused;
-    uint8_t *d_in_codec, *d_out_law;
+    wmx::LegState send;   // per stream, made by create: sequence number (low 16 bits significant), timestamp
+    wmx::LegState seq;    // the sequence rule (leg_seq.h): synced, next, lost, late, dup, resync, overflow, uint32 each
+    wmx::LegState codec;  // the codec rule (leg_codec.h): refused (uint32), in_codec and out_law (uint8)
+    wmx::LegState plc;    // the concealment rule (leg_plc.h): hist (kPlcHist int16), concealed (uint32)
+    wmx::LegState dtmf;   // the DTMF rule (leg_dtmf.h): ring (uint64), count, ts and flags (uint32 each)
+    // no stream has left in_codec REFERENCE / out_law = law, so the launches are those of a handle that knows no codecs
     bool codecs_default;
-    // the concealment rule's state per leg (leg_plc.h), made by the first call that needs it, one block: hist (kPlcHist int16 per leg),
-    // behind it concealed (uint32)
-    int16_t *d_plc_hist;
-    uint32_t *d_plc_concealed;
-    // the DTMF rule's state per leg (leg_dtmf.h), made by the first call that needs it, one block: ring (8 bytes per leg, one uint64),
-    // behind it count, ts and flags (uint32 each)
-    uint64_t *d_dtmf_ring;
-    uint32_t *d_dtmf_count, *d_dtmf_ts, *d_dtmf_flags;
 };
 
 namespace wmx {
@@ -47,6 +148,8 @@ namespace {
 
 constexpr int kRtpHeader = 12;      // RTP_HEADER_SIZE, src/rtp.h:33
 constexpr int kRtpG711Payload = 160;  // RTP_PCMA_PKT_SIZE, src/rtp.h:31
+static_assert(kLegRow == kRtpG711Payload, "a leg's row is one datagram's payload decoded");
+static_assert(kLegMaxCalls == WMX_MIX_MAX_LEG_PACKETS, "leg_calls.h and include/wmix_amd.h name one limit");
 
 // LAW: WMX_LAW_A / WMX_LAW_U for every stream of the launch (payload type `pt`), or kLawPerStream: laws[stream] (leg_codec.h)
 constexpr int kLawPerStream = 2;
@@ -205,7 +308,7 @@ __global__ __launch_bounds__(256) void rtp_ingest_legs_codecs_kernel(const uint8
             dst[c] = call ? (int16_t)dec(pkt[kRtpHeader + c]) : (int16_t)0;
         }
         if (c == 0) {
-            len[row] = call ? (uint32_t)kRtpG711Payload * 2 : 0u;
+            len[row] = call ? kLegRowBytes : 0u;
             if (seq_raw) seq_raw[row] = there ? (uint16_t)(pkt[2] | (pkt[3] << 8)) : (uint16_t)0;  // as stored: rtp_recv does not ntohs
             if (COUNT && (what & kLegCodecRefused)) atomicAdd(refused + leg, 1u);
         }
@@ -280,37 +383,36 @@ __global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restri
 // d_seq_raw: header bytes 2..3 as stored, swapped here), sorts the candidates' keys in registers, walks them, writes the call list,
 // zeroes d_len of the slots that make no call and stores the state it read.  WIDE: max_packets == 4 and d_seq_raw on an 8-byte
 // boundary -- the four sequence numbers are one 8-byte load.  No lane touches another leg's words: no atomics.
-constexpr int kSeqWords = 7;
 template <bool WIDE>
 __global__ __launch_bounds__(256) void rtp_sequence_legs_kernel(const uint16_t *__restrict__ seq_raw, uint32_t *__restrict__ len,
                                                                  uint32_t *__restrict__ calls, uint32_t *__restrict__ sq, int max_packets,
                                                                  uint32_t max_gap, int n_legs) {
     const size_t n = (size_t)n_legs;
     for (size_t leg = blockIdx.x * (size_t)blockDim.x + threadIdx.x; leg < n; leg += (size_t)gridDim.x * blockDim.x) {
-        uint32_t raw[kSeqMaxCalls] = {0u, 0u, 0u, 0u}, ok = 0;
+        uint32_t raw[kLegMaxCalls] = {0u, 0u, 0u, 0u}, ok = 0;
         if (WIDE) {
-            const uint2 w = *reinterpret_cast<const uint2 *>(seq_raw + leg * kSeqMaxCalls);
+            const uint2 w = *reinterpret_cast<const uint2 *>(seq_raw + leg * kLegMaxCalls);
             raw[0] = w.x & 0xFFFFu, raw[1] = w.x >> 16, raw[2] = w.y & 0xFFFFu, raw[3] = w.y >> 16;
         }
 #pragma unroll
-        for (int k = 0; k < kSeqMaxCalls; k++) {
+        for (int k = 0; k < kLegMaxCalls; k++) {
             if (k >= max_packets) continue;
             if (!WIDE) raw[k] = seq_raw[leg * (size_t)max_packets + k];
-            if (len[leg * (size_t)max_packets + k] == 2u * kRtpG711Payload) ok |= 1u << k;
+            ok |= leg_row_readable(len[leg * (size_t)max_packets + k]) << k;
         }
         if (!ok) {  // no calls, state unchanged
             calls[leg] = 0u;
             continue;
         }
-        uint32_t seq[kSeqMaxCalls];
+        uint32_t seq[kLegMaxCalls];
 #pragma unroll
-        for (int k = 0; k < kSeqMaxCalls; k++) seq[k] = ((raw[k] & 0xFFu) << 8) | ((raw[k] >> 8) & 0xFFu);  // ntohs
+        for (int k = 0; k < kLegMaxCalls; k++) seq[k] = ((raw[k] & 0xFFu) << 8) | ((raw[k] >> 8) & 0xFFu);  // ntohs
         LegSeqState st{sq[leg], sq[n + leg], sq[2 * n + leg], sq[3 * n + leg], sq[4 * n + leg], sq[5 * n + leg], sq[6 * n + leg]};
         const LegSeqState was = st;
         const LegSeqTick r = leg_seq_tick(st, seq, ok, max_gap);
         calls[leg] = r.calls;
 #pragma unroll
-        for (int k = 0; k < kSeqMaxCalls; k++)
+        for (int k = 0; k < kLegMaxCalls; k++)
             if (k < max_packets && ((r.discard >> k) & 1u)) len[leg * (size_t)max_packets + k] = 0u;
         sq[leg] = st.synced;
         sq[n + leg] = st.next;
@@ -332,23 +434,17 @@ __global__ __launch_bounds__(256) void rtp_sequence_legs_kernel(const uint16_t *
 // LDS.  Samples move in pairs: WIDE (rows in and out on 4-byte boundaries) one 32-bit access per pair, otherwise two 16-bit ones; the
 // handle's history and the LDS are always 32-bit.  A lane writes only its own leg's rows, history and counter: no atomics.
 constexpr int kPlcLegsPerBlock = 4;
-constexpr int kPlcPairs = kPlcRow / 2, kPlcHistPairs = kPlcHist / 2;
-constexpr int kPlcTimeline = kPlcHist + kSeqMaxCalls * kPlcRow;
+constexpr int kPlcPairs = kLegRow / 2, kPlcHistPairs = kPlcHist / 2;
+constexpr int kPlcTimeline = kPlcHist + kLegMaxCalls * kLegRow;
 
-// LDS hand-off between lanes of one wave: the hardware runs a wave's LDS instructions in issue order, the compiler must keep it
-__device__ __forceinline__ void plc_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
+// two samples of a row as one word (the concealment and the DTMF kernel): WIDE one 32-bit access, otherwise two 16-bit ones
 template <bool WIDE>
-__device__ __forceinline__ uint32_t plc_load2(const int16_t *p, int pair) {
+__device__ __forceinline__ uint32_t pair_load(const int16_t *p, int pair) {
     if (WIDE) return *reinterpret_cast<const uint32_t *>(p + 2 * pair);
     return (uint32_t)(uint16_t)p[2 * pair] | ((uint32_t)(uint16_t)p[2 * pair + 1] << 16);
 }
 template <bool WIDE>
-__device__ __forceinline__ void plc_store2(int16_t *p, int pair, uint32_t v) {
+__device__ __forceinline__ void pair_store(int16_t *p, int pair, uint32_t v) {
     if (WIDE) {
         *reinterpret_cast<uint32_t *>(p + 2 * pair) = v;
     } else {
@@ -356,7 +452,7 @@ __device__ __forceinline__ void plc_store2(int16_t *p, int pair, uint32_t v) {
         p[2 * pair + 1] = (int16_t)(v >> 16);
     }
 }
-__device__ __forceinline__ uint32_t plc_pack(int32_t lo, int32_t hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
+__device__ __forceinline__ uint32_t pair_pack(int32_t lo, int32_t hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
 
 template <bool WIDE>
 __global__ __launch_bounds__(64 * kPlcLegsPerBlock) void rtp_conceal_legs_kernel(const int16_t *__restrict__ pcm, long source_stride,
@@ -372,59 +468,53 @@ __global__ __launch_bounds__(64 * kPlcLegsPerBlock) void rtp_conceal_legs_kernel
     const size_t leg = blockIdx.x * (size_t)kPlcLegsPerBlock + (size_t)w;
     if (leg >= (size_t)n_legs) return;  // the whole wave
     const uint32_t calls = (uint32_t)__builtin_amdgcn_readfirstlane((int)calls_in[leg]);
-    const uint32_t count = leg_plc_count(calls);
-    uint32_t readable = 0;
-#pragma unroll
-    for (int k = 0; k < kSeqMaxCalls; k++)
-        if (k < max_packets) readable |= leg_plc_readable(len[leg * (size_t)max_packets + k]) << k;
-    readable = (uint32_t)__builtin_amdgcn_readfirstlane((int)readable);
-    uint32_t sil = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++)
-        if (j < count && leg_plc_silence(calls, j, readable)) sil |= 1u << j;
-    if (lane < kSeqMaxCalls) len_out[leg * kSeqMaxCalls + lane] = (uint32_t)lane < count ? kPlcRowBytes : 0u;
+    const LegWalk walk = leg_calls_walk(len + leg * (size_t)max_packets, true, calls, max_packets);
+    const uint32_t count = walk.count;
+    // sil bit j: call j is filled from the history
+    const uint32_t sil = ~(uint32_t)__builtin_amdgcn_readfirstlane((int)walk.data) & ((1u << count) - 1u);
+    if (lane < kLegMaxCalls) len_out[leg * kLegMaxCalls + lane] = (uint32_t)lane < count ? kLegRowBytes : 0u;
     if (count == 0u) return;  // no calls: the state stays
     const int16_t *src = pcm + leg * source_stride;
-    int16_t *dst = pcm_out + leg * (size_t)(kSeqMaxCalls * kPlcRow);
+    int16_t *dst = pcm_out + leg * (size_t)(kLegMaxCalls * kLegRow);
     int16_t *hs = hist + leg * (size_t)kPlcHist;
     const bool second = lane < kPlcPairs - 64;  // a row is 80 pairs: every lane one, the first 16 another
 
     if (sil == 0u) {  // data calls only
         if (count == 1u) {  // the older half of the history is its newer half; read and written by disjoint pairs
-            const uint32_t a = plc_load2<true>(hs, kPlcPairs + lane), b = second ? plc_load2<true>(hs, kPlcPairs + 64 + lane) : 0u;
-            plc_store2<true>(hs, lane, a);
-            if (second) plc_store2<true>(hs, 64 + lane, b);
+            const uint32_t a = pair_load<true>(hs, kPlcPairs + lane), b = second ? pair_load<true>(hs, kPlcPairs + 64 + lane) : 0u;
+            pair_store<true>(hs, lane, a);
+            if (second) pair_store<true>(hs, 64 + lane, b);
         }
         for (uint32_t j = 0; j < count; j++) {
             const int16_t *row = src + leg_calls_slot(calls, j) * packet_stride;
-            const uint32_t a = plc_load2<WIDE>(row, lane), b = second ? plc_load2<WIDE>(row, 64 + lane) : 0u;
-            plc_store2<WIDE>(dst + j * kPlcRow, lane, a);
-            if (second) plc_store2<WIDE>(dst + j * kPlcRow, 64 + lane, b);
+            const uint32_t a = pair_load<WIDE>(row, lane), b = second ? pair_load<WIDE>(row, 64 + lane) : 0u;
+            pair_store<WIDE>(dst + j * kLegRow, lane, a);
+            if (second) pair_store<WIDE>(dst + j * kLegRow, 64 + lane, b);
             if (j + 2u >= count) {  // one of the last two: it stays in the history
-                int16_t *hrow = hs + (j + 2u - count) * kPlcRow;
-                plc_store2<true>(hrow, lane, a);
-                if (second) plc_store2<true>(hrow, 64 + lane, b);
+                int16_t *hrow = hs + (j + 2u - count) * kLegRow;
+                pair_store<true>(hrow, lane, a);
+                if (second) pair_store<true>(hrow, 64 + lane, b);
             }
         }
         return;
     }
 
     int16_t *tl = timeline[w], *q = qs[w];
-    for (int p = lane; p < kPlcHistPairs; p += 64) plc_store2<true>(tl, p, plc_load2<true>(hs, p));
+    for (int p = lane; p < kPlcHistPairs; p += 64) pair_store<true>(tl, p, pair_load<true>(hs, p));
     const int16_t *h0 = tl;
     int32_t lag = kPlcLagMin, run = 0;
     uint32_t made = 0;
     for (uint32_t j = 0; j < count; j++) {
-        int16_t *y = tl + kPlcHist + j * kPlcRow, *out = dst + j * kPlcRow;
+        int16_t *y = tl + kPlcHist + j * kLegRow, *out = dst + j * kLegRow;
         if ((sil >> j) & 1u) {
             if (run == 0) {
-                h0 = tl + j * kPlcRow;
-                plc_wave_sync();  // what the calls in front of this one appended
+                h0 = tl + j * kLegRow;
+                wave_sync();  // what the calls in front of this one appended
                 for (int p = lane; p < kPlcHistPairs; p += 64) {
-                    const uint32_t v = plc_load2<true>(h0, p);
-                    plc_store2<true>(q, p, plc_pack(leg_plc_q((int16_t)(v & 0xFFFFu)), leg_plc_q((int16_t)(v >> 16))));
+                    const uint32_t v = pair_load<true>(h0, p);
+                    pair_store<true>(q, p, pair_pack(leg_plc_q((int16_t)(v & 0xFFFFu)), leg_plc_q((int16_t)(v >> 16))));
                 }
-                plc_wave_sync();
+                wave_sync();
                 int32_t L = kPlcLagMin + lane, c = leg_plc_score(q, L);
                 if (lane <= kPlcLagMax - kPlcLagMin - 64) {
                     const int32_t L2 = kPlcLagMin + 64 + lane, c2 = leg_plc_score(q, L2);
@@ -437,31 +527,31 @@ __global__ __launch_bounds__(64 * kPlcLegsPerBlock) void rtp_conceal_legs_kernel
                 lag = __builtin_amdgcn_readfirstlane(L);
             }
             for (int p = lane; p < kPlcPairs; p += 64) {
-                const int32_t k = run * kPlcRow + 2 * p;
-                const uint32_t v = plc_pack(leg_plc_synth(h0[leg_plc_index(k, lag)], k), leg_plc_synth(h0[leg_plc_index(k + 1, lag)], k + 1));
-                plc_store2<true>(y, p, v);
-                plc_store2<WIDE>(out, p, v);
+                const int32_t k = run * kLegRow + 2 * p;
+                const uint32_t v = pair_pack(leg_plc_synth(h0[leg_plc_index(k, lag)], k), leg_plc_synth(h0[leg_plc_index(k + 1, lag)], k + 1));
+                pair_store<true>(y, p, v);
+                pair_store<WIDE>(out, p, v);
             }
             run++;
             made++;
         } else {
             const int16_t *row = src + leg_calls_slot(calls, j) * packet_stride;
             for (int p = lane; p < kPlcPairs; p += 64) {
-                uint32_t v = plc_load2<WIDE>(row, p);
+                uint32_t v = pair_load<WIDE>(row, p);
                 if (run > 0 && 2 * p < kPlcBlend) {
-                    const int32_t i = 2 * p, k = run * kPlcRow + i;
-                    v = plc_pack(leg_plc_blend((int16_t)(v & 0xFFFFu), leg_plc_synth(h0[leg_plc_index(k, lag)], k), i),
+                    const int32_t i = 2 * p, k = run * kLegRow + i;
+                    v = pair_pack(leg_plc_blend((int16_t)(v & 0xFFFFu), leg_plc_synth(h0[leg_plc_index(k, lag)], k), i),
                                  leg_plc_blend((int16_t)(v >> 16), leg_plc_synth(h0[leg_plc_index(k + 1, lag)], k + 1), i + 1));
                 }
-                plc_store2<true>(y, p, v);
-                plc_store2<WIDE>(out, p, v);
+                pair_store<true>(y, p, v);
+                pair_store<WIDE>(out, p, v);
             }
             run = 0;
         }
     }
-    plc_wave_sync();
-    const int16_t *last = tl + count * kPlcRow;  // the last 320 samples emitted
-    for (int p = lane; p < kPlcHistPairs; p += 64) plc_store2<true>(hs, p, plc_load2<true>(last, p));
+    wave_sync();
+    const int16_t *last = tl + count * kLegRow;  // the last 320 samples emitted
+    for (int p = lane; p < kPlcHistPairs; p += 64) pair_store<true>(hs, p, pair_load<true>(last, p));
     if (lane == 0) concealed[leg] += made;
 }
 
@@ -477,7 +567,7 @@ __global__ __launch_bounds__(64 * kPlcLegsPerBlock) void rtp_conceal_legs_kernel
 // writes only its own leg's rows and state: no atomics.  Per block of legs 8 x 4 x 328 bytes of LDS.
 constexpr int kDtmfLegsPerBlock = 8;
 constexpr int kDtmfLdsRow = 164;
-constexpr int kDtmfPairs = kDtmfRow / 2;
+constexpr int kDtmfPairs = kLegRow / 2;
 
 __device__ __forceinline__ int64_t dtmf_shfl64(int64_t v, int src) {
     const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v & 0xFFFFFFFFu), src, 64);
@@ -493,32 +583,24 @@ __global__ __launch_bounds__(32 * kDtmfLegsPerBlock) void rtp_detect_dtmf_legs_k
                                                                                        const uint32_t *__restrict__ calls_in, int max_packets,
                                                                                        uint32_t event_pt, int suppress, uint64_t *ring,
                                                                                        uint32_t *count, uint32_t *ts, uint32_t *flags, int n_legs) {
-    __shared__ __attribute__((aligned(16))) int16_t staged[kDtmfLegsPerBlock][kSeqMaxCalls][kDtmfLdsRow];
+    __shared__ __attribute__((aligned(16))) int16_t staged[kDtmfLegsPerBlock][kLegMaxCalls][kDtmfLdsRow];
     const int hl = (int)(threadIdx.x & 31u), half = (int)(threadIdx.x >> 5);
     const int wave_lane = (int)(threadIdx.x & 63u);
     const size_t leg = blockIdx.x * (size_t)kDtmfLegsPerBlock + (size_t)half;
     const bool live = leg < (size_t)n_legs;
-    uint32_t list = 0, blocks = 0, quiet = (1u << kSeqMaxCalls) - 1u;  // quiet bit j: block j is none, or not to be read
+    uint32_t list = 0, blocks = 0, quiet = (1u << kLegMaxCalls) - 1u;  // quiet bit j: block j is none, or not to be read
     if (live) {
-        uint32_t readable = 0;
-#pragma unroll
-        for (int k = 0; k < kSeqMaxCalls; k++)
-            if (k < max_packets) readable |= leg_plc_readable(len[leg * (size_t)max_packets + k]) << k;
-        list = leg_dtmf_list(calls_in != nullptr, calls_in ? calls_in[leg] : 0u, readable, max_packets);
-        blocks = leg_plc_count(list);
-        quiet = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++)
-            if (j >= blocks || leg_plc_silence(list, j, readable)) quiet |= 1u << j;
+        const LegWalk walk = leg_calls_walk(len + leg * (size_t)max_packets, calls_in != nullptr, calls_in ? calls_in[leg] : 0u, max_packets);
+        list = walk.list, blocks = walk.count, quiet &= ~walk.data;
     }
     int16_t *rows = pcm + (live ? leg : 0) * (size_t)source_stride;
 #pragma unroll
-    for (uint32_t j = 0; j < (uint32_t)kSeqMaxCalls; j++) {
+    for (uint32_t j = 0; j < (uint32_t)kLegMaxCalls; j++) {
         if ((quiet >> j) & 1u) continue;
         const int16_t *row = rows + leg_calls_slot(list, j) * pcm_packet_stride;
-        for (int p = hl; p < kDtmfPairs; p += 32) plc_store2<true>(staged[half][j], p, plc_load2<WIDE>(row, p));
+        for (int p = hl; p < kDtmfPairs; p += 32) pair_store<true>(staged[half][j], p, pair_load<WIDE>(row, p));
     }
-    plc_wave_sync();  // a leg's lanes are lanes of one wave
+    wave_sync();  // a leg's lanes are lanes of one wave
 
     const int j = hl >> 3, f = hl & 7;
     const bool mine = !((quiet >> j) & 1u);
@@ -528,7 +610,7 @@ __global__ __launch_bounds__(32 * kDtmfLegsPerBlock) void rtp_detect_dtmf_legs_k
         const int16_t *x = staged[half][j];
         int32_t s1 = 0, s2 = 0;
         for (int p = 0; p < kDtmfPairs; p++) {
-            const uint32_t v = plc_load2<true>(x, p);
+            const uint32_t v = pair_load<true>(x, p);
             const int32_t a = (int16_t)(v & 0xFFFFu), b = (int16_t)(v >> 16);
             leg_dtmf_step(s1, s2, coef, a);
             leg_dtmf_step(s1, s2, coef, b);
@@ -540,23 +622,23 @@ __global__ __launch_bounds__(32 * kDtmfLegsPerBlock) void rtp_detect_dtmf_legs_k
 #pragma unroll
     for (int i = 0; i < kDtmfFreqs; i++) p8[i] = dtmf_shfl64(power, (wave_lane & ~7) + i);
     const int32_t digit = mine ? leg_dtmf_decide(p8, energy) : kDtmfNone;
-    int32_t d[kSeqMaxCalls];
+    int32_t d[kLegMaxCalls];
 #pragma unroll
-    for (int i = 0; i < kSeqMaxCalls; i++) d[i] = __shfl(digit, (wave_lane & 32) + 8 * i, 64);
+    for (int i = 0; i < kLegMaxCalls; i++) d[i] = __shfl(digit, (wave_lane & 32) + 8 * i, 64);
 
     if (suppress) {
 #pragma unroll
-        for (uint32_t i = 0; i < (uint32_t)kSeqMaxCalls; i++) {
+        for (uint32_t i = 0; i < (uint32_t)kLegMaxCalls; i++) {
             if (d[i] == kDtmfNone) continue;  // a tone: the leg is live and the block has a row
             int16_t *row = rows + leg_calls_slot(list, i) * pcm_packet_stride;
-            for (int p = hl; p < kDtmfPairs; p += 32) plc_store2<WIDE>(row, p, 0u);
+            for (int p = hl; p < kDtmfPairs; p += 32) pair_store<WIDE>(row, p, 0u);
         }
     }
     if (!live || hl != 0) return;
     LegDtmfState st{count[leg], ring[leg], ts[leg], flags[leg]};
     const LegDtmfState was = st;
 #pragma unroll
-    for (int k = 0; k < kSeqMaxCalls; k++) {
+    for (int k = 0; k < kLegMaxCalls; k++) {
         if (k >= max_packets) continue;
         const int32_t got = recv[leg * (size_t)max_packets + k];
         if (got < (int32_t)kDtmfMinEventBytes) continue;  // the row is read only where enough arrived
@@ -564,7 +646,7 @@ __global__ __launch_bounds__(32 * kDtmfLegsPerBlock) void rtp_detect_dtmf_legs_k
         leg_dtmf_packet(st, got, pkt[1], pkt[12], leg_dtmf_word(pkt + 4), event_pt);
     }
 #pragma unroll
-    for (uint32_t i = 0; i < (uint32_t)kSeqMaxCalls; i++)
+    for (uint32_t i = 0; i < (uint32_t)kLegMaxCalls; i++)
         if (i < blocks) leg_dtmf_debounce(st, d[i]);
     if (st.count != was.count) count[leg] = st.count, ring[leg] = st.ring;
     if (st.ts != was.ts) ts[leg] = st.ts;
@@ -597,21 +679,15 @@ int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
     }
     h->n_streams = n_streams;
     h->law = law;
-    h->d_seq = h->d_ts = nullptr;
-    h->d_sq = nullptr;
-    h->d_refused = nullptr;
-    h->d_in_codec = h->d_out_law = nullptr;
     h->codecs_default = true;
-    h->d_plc_hist = nullptr;
-    h->d_plc_concealed = nullptr;
-    h->d_dtmf_ring = nullptr;
-    h->d_dtmf_count = h->d_dtmf_ts = h->d_dtmf_flags = nullptr;
-    hipError_t e = hipMalloc(&h->d_seq, sizeof(uint32_t) * n_streams);
-    if (e == hipSuccess) e = hipMalloc(&h->d_ts, sizeof(uint32_t) * n_streams);
-    if (e == hipSuccess) e = hipMemset(h->d_seq, 0, sizeof(uint32_t) * n_streams);  // rtp_header(..., seq 0, timestamp 0, ssrc 0)
-    if (e == hipSuccess) e = hipMemset(h->d_ts, 0, sizeof(uint32_t) * n_streams);
-    if (e != hipSuccess) {
-        const int rc = hip_fail(e, "wmx_rtp_create: hipMalloc/hipMemset", __FILE__, __LINE__);
+    // the tables.  Every fresh value is zero (unsynced, counters 0, an empty history, no key down) but the codecs'
+    h->send = LegState("wmx_rtp_create: hipMalloc/hipMemset", n_streams, {{4, 0}, {4, 0}});  // rtp_header(..., seq 0, timestamp 0, ssrc 0)
+    h->seq = LegState("hipMemset(sequence state)", n_streams, {{4, 0}, {4, 0}, {4, 0}, {4, 0}, {4, 0}, {4, 0}, {4, 0}});
+    h->codec = LegState("hipMemset(codec state)", n_streams, {{4, 0}, {1, WMX_CODEC_REFERENCE}, {1, law}});
+    h->plc = LegState("hipMemset(concealment state)", n_streams, {{kPlcHist * sizeof(int16_t), 0}, {4, 0}});
+    h->dtmf = LegState("hipMemset(DTMF state)", n_streams, {{8, 0}, {4, 0}, {4, 0}, {4, 0}});
+    const int rc = h->send.make();
+    if (rc) {
         wmx_rtp_destroy(h);
         return rc;
     }
@@ -622,12 +698,7 @@ int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
 int wmx_rtp_destroy(wmx_rtp *h) {
     WMX_ON_DEVICE(h);
     if (!h) return 0;
-    if (h->d_seq) (void)hipFree(h->d_seq);
-    if (h->d_ts) (void)hipFree(h->d_ts);
-    if (h->d_sq) (void)hipFree(h->d_sq);
-    if (h->d_refused) (void)hipFree(h->d_refused);  // in_codec and out_law lie behind it
-    if (h->d_plc_hist) (void)hipFree(h->d_plc_hist);  // concealed lies behind it
-    if (h->d_dtmf_ring) (void)hipFree(h->d_dtmf_ring);  // count, ts and flags lie behind it
+    for (LegState *st : {&h->send, &h->seq, &h->codec, &h->plc, &h->dtmf}) st->destroy();
     delete h;
     return 0;
 }
@@ -656,16 +727,18 @@ int wmx_rtp_egress(wmx_rtp *h, int in_chn, int in_freq, const int16_t *d_pcm, ui
     if (packet_bytes) *packet_bytes = (uint32_t)(kRtpHeader + n_codes);
     const dim3 block(256), grid((unsigned)((n_codes + 255) / 256 > 0 ? (n_codes + 255) / 256 : 1), (unsigned)h->n_streams);
     const int pt = h->law == WMX_LAW_A ? 8 : 0;  // RTP_PAYLOAD_TYPE_PCMA / PCMU, src/rtp.h:21-24
-    const uint8_t *laws = h->codecs_default ? nullptr : h->d_out_law;  // per stream once a stream has left the default (leg_codec.h)
+    // per stream once a stream has left the default (leg_codec.h)
+    const uint8_t *laws = h->codecs_default ? nullptr : h->codec.at<uint8_t>(kCodecOutLaw);
+    uint32_t *d_seq = h->send.at<uint32_t>(kSendSeq), *d_ts = h->send.at<uint32_t>(kSendTs);
     if (n_codes >= 4 && n_codes % 4 == 0 && aligned_to(d_packets, packet_stride, 4)) {  // four codes per lane (the gather list is 16-byte aligned)
         const unsigned wgrid = wmx::stream_grid((size_t)h->n_streams * (n_codes / 4), 256);
         auto kernel = laws ? rtp_egress_wide_kernel<kLawPerStream>
                            : (h->law == WMX_LAW_A ? rtp_egress_wide_kernel<WMX_LAW_A> : rtp_egress_wide_kernel<WMX_LAW_U>);
-        hipLaunchKernelGGL(kernel, dim3(wgrid), block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes, n_codes / out_chn, h->d_seq,
-                           h->d_ts, d_packets, packet_stride, h->n_streams, pt, laws);
+        hipLaunchKernelGGL(kernel, dim3(wgrid), block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes, n_codes / out_chn, d_seq,
+                           d_ts, d_packets, packet_stride, h->n_streams, pt, laws);
     } else {
         auto kernel = laws ? rtp_egress_kernel<kLawPerStream> : (h->law == WMX_LAW_A ? rtp_egress_kernel<WMX_LAW_A> : rtp_egress_kernel<WMX_LAW_U>);
-        hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes, n_codes / out_chn, h->d_seq, h->d_ts,
+        hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), d_pcm, pcm_stride, d_idx, n_codes, n_codes / out_chn, d_seq, d_ts,
                            d_packets, packet_stride, h->n_streams, pt, laws);
     }
     WMX_LAUNCH_CHECK();
@@ -757,7 +830,8 @@ int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet
     const uint32_t ring_samples = v.ring_bytes / 2, head_sample = (v.head_off / 2) % ring_samples;
     const bool wide_in = head_sample % 4 == 0 && ring_samples % 4 == 0 && reinterpret_cast<uintptr_t>(v.d_rings) % 8 == 0;
     const bool wide_out = aligned_to(d_packets, packet_stride, 4);
-    const uint8_t *laws = h->codecs_default ? nullptr : h->d_out_law;  // per ring once a stream has left the default (leg_codec.h)
+    // per ring once a stream has left the default (leg_codec.h)
+    const uint8_t *laws = h->codecs_default ? nullptr : h->codec.at<uint8_t>(kCodecOutLaw);
     auto kernel = wide_in ? (wide_out ? rtp_egress_rings_kernel<true, true, false> : rtp_egress_rings_kernel<true, false, false>)
                           : (wide_out ? rtp_egress_rings_kernel<false, true, false> : rtp_egress_rings_kernel<false, false, false>);
     if (laws)
@@ -765,7 +839,8 @@ int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet
                          : (wide_out ? rtp_egress_rings_kernel<false, true, true> : rtp_egress_rings_kernel<false, false, true>);
     const int pt = h->law == WMX_LAW_A ? 8 : 0;  // RTP_PAYLOAD_TYPE_PCMA / PCMU, src/rtp.h:21-24
     hipLaunchKernelGGL(kernel, dim3(wmx::stream_grid((size_t)h->n_streams * kRtpWords, 256)), dim3(256), 0, as_stream(stream), v.d_rings,
-                       ring_samples, head_sample, h->law, h->d_seq, h->d_ts, d_packets, packet_stride, h->n_streams, pt, laws);
+                       ring_samples, head_sample, h->law, h->send.at<uint32_t>(kSendSeq), h->send.at<uint32_t>(kSendTs), d_packets, packet_stride,
+                       h->n_streams, pt, laws);
     WMX_LAUNCH_CHECK();
     mix_played(m, 2u * kRtpG711Payload);
     if (packet_bytes) *packet_bytes = (uint32_t)(kRtpHeader + kRtpG711Payload);
@@ -776,45 +851,25 @@ int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet
 // (src/wmixTask.c:1058)
 int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(h);
-    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_streams: sender", "handle")) return WMX_EINVAL;
-    hipStream_t s = as_stream(stream);
-    if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(h->d_seq, 0, sizeof(uint32_t) * h->n_streams, s));
-        WMX_HIP(hipMemsetAsync(h->d_ts, 0, sizeof(uint32_t) * h->n_streams, s));
-        return 0;
-    }
-    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
-        WMX_HIP(hipMemsetAsync(h->d_seq + host_idx[i], 0, sizeof(uint32_t), s));
-        WMX_HIP(hipMemsetAsync(h->d_ts + host_idx[i], 0, sizeof(uint32_t), s));
-    }
-    return 0;
+    if (!h) return WMX_EINVAL;
+    return h->send.reset("wmx_rtp_reset_streams: sender", host_idx, n, as_stream(stream));
 }
 
 // ---- the sequence rule per leg (include/wmix_amd.h, leg_seq.h)
-// the state, all zero (unsynced, counters 0), from the first call that needs it on
-static int seq_state(wmx_rtp *h) {
-    if (h->d_sq) return 0;
-    void *p = nullptr;
-    const int rc = zeroed_block(&p, (size_t)kSeqWords * h->n_streams * sizeof(uint32_t), "hipMemset(sequence state)");
-    if (rc) return rc;
-    h->d_sq = static_cast<uint32_t *>(p);
-    return 0;
-}
-
 int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16_t *d_seq_raw, uint32_t *d_len, uint32_t *d_calls,
                           void *stream) {
     WMX_ON_DEVICE(h);
-    if (!h || !d_seq_raw || !d_len || !d_calls || max_packets < 1 || max_packets > kSeqMaxCalls || max_gap < 0 || max_gap > kSeqMaxCalls - 1) {
-        set_error("wmx_rtp_sequence_legs: max_packets=%d must be 1 .. %d, max_gap=%d 0 .. %d, and no pointer NULL", max_packets, kSeqMaxCalls,
-                  max_gap, kSeqMaxCalls - 1);
+    if (!h || !d_seq_raw || !d_len || !d_calls || max_packets < 1 || max_packets > kLegMaxCalls || max_gap < 0 || max_gap > kLegMaxCalls - 1) {
+        set_error("wmx_rtp_sequence_legs: max_packets=%d must be 1 .. %d, max_gap=%d 0 .. %d, and no pointer NULL", max_packets, kLegMaxCalls,
+                  max_gap, kLegMaxCalls - 1);
         return WMX_EINVAL;
     }
-    const int rcs = seq_state(h);
+    const int rcs = h->seq.make();
     if (rcs) return rcs;
-    const bool wide = max_packets == kSeqMaxCalls && reinterpret_cast<uintptr_t>(d_seq_raw) % 8 == 0;
+    const bool wide = max_packets == kLegMaxCalls && reinterpret_cast<uintptr_t>(d_seq_raw) % 8 == 0;
     hipLaunchKernelGGL(wide ? rtp_sequence_legs_kernel<true> : rtp_sequence_legs_kernel<false>, dim3(wmx::stream_grid((size_t)h->n_streams, 256)),
-                       dim3(256), 0, as_stream(stream), d_seq_raw, d_len, d_calls, h->d_sq, max_packets, (uint32_t)max_gap, h->n_streams);
+                       dim3(256), 0, as_stream(stream), d_seq_raw, d_len, d_calls, h->seq.at<uint32_t>(kSeqSynced), max_packets, (uint32_t)max_gap,
+                       h->n_streams);
     WMX_LAUNCH_CHECK();
     return 0;
 }
@@ -823,23 +878,14 @@ int wmx_rtp_sequence_legs(wmx_rtp *h, int max_packets, int max_gap, const uint16
 // may start at any sequence number
 int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(h);
-    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_sequence: leg", "handle")) return WMX_EINVAL;
+    if (!h) return WMX_EINVAL;
     hipStream_t s = as_stream(stream);
-    const size_t pitch = (size_t)h->n_streams * sizeof(uint32_t);
-    if (h->d_refused) {  // the receive side's other counter (leg_codec.h); the leg's codec stays
-        if (!host_idx) WMX_HIP(hipMemsetAsync(h->d_refused, 0, pitch, s));
-        for (int i = 0; host_idx && i < n; i++) WMX_HIP(hipMemsetAsync(h->d_refused + host_idx[i], 0, sizeof(uint32_t), s));
-    }
-    const bool fresh = !h->d_sq;
-    const int rcs = seq_state(h);
-    if (rcs || fresh) return rcs;  // just made: unsynced already
-    if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(h->d_sq, 0, (size_t)kSeqWords * pitch, s));
-        return 0;
-    }
-    for (int i = 0; i < n; i++)  // a handful of legs at a time: the leg's word in each of the arrays, nothing of the list goes to the device
-        WMX_HIP(hipMemset2DAsync(h->d_sq + host_idx[i], pitch, 0, sizeof(uint32_t), kSeqWords, s));
+    const int rc = h->seq.reset("wmx_rtp_reset_sequence: leg", host_idx, n, s);
+    uint32_t *refused = h->codec.at<uint32_t>(kCodecRefused);
+    if (rc || !refused) return rc;
+    // the receive side's other counter (leg_codec.h); the leg's codec stays
+    if (!host_idx) WMX_HIP(hipMemsetAsync(refused, 0, (size_t)h->n_streams * sizeof(uint32_t), s));
+    for (int i = 0; host_idx && i < n; i++) WMX_HIP(hipMemsetAsync(refused + host_idx[i], 0, sizeof(uint32_t), s));
     return 0;
 }
 
@@ -850,61 +896,44 @@ int wmx_rtp_export_sequence(wmx_rtp *h, uint16_t *next, uint8_t *synced, uint32_
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
     const size_t n = (size_t)h->n_streams;
-    std::vector<uint32_t> w((size_t)kSeqWords * n, 0u);  // no leg has been sequenced on this handle: all zero
-    if (h->d_sq) {
-        WMX_HIP(hipStreamSynchronize(as_stream(stream)));
-        WMX_HIP(hipMemcpy(w.data(), h->d_sq, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    uint32_t *const out[5] = {lost, late, dup, resync, overflow};
-    for (size_t r = 0; r < n; r++) {
+    std::vector<uint32_t> w(2 * n);  // synced and next as the device holds them: a word each
+    const int rc = h->seq.export_to({synced ? w.data() : nullptr, next ? w.data() + n : nullptr, lost, late, dup, resync, overflow},
+                                    as_stream(stream));
+    for (size_t r = 0; rc == 0 && r < n; r++) {
         if (synced) synced[r] = (uint8_t)(w[r] != 0);
         if (next) next[r] = (uint16_t)w[n + r];
-        for (int c = 0; c < 5; c++)
-            if (out[c]) out[c][r] = w[(size_t)(2 + c) * n + r];
     }
-    return 0;
+    return rc;
 }
 
 // ---- the concealment rule per leg (include/wmix_amd.h, leg_plc.h)
-// the state, all zero (a fresh history, concealed 0), from the first call that needs it on
-static int plc_state(wmx_rtp *h) {
-    if (h->d_plc_hist) return 0;
-    const size_t hist_bytes = (size_t)h->n_streams * kPlcHist * sizeof(int16_t);
-    void *p = nullptr;
-    const int rc = zeroed_block(&p, hist_bytes + (size_t)h->n_streams * sizeof(uint32_t), "hipMemset(concealment state)");
-    if (rc) return rc;
-    h->d_plc_hist = static_cast<int16_t *>(p);
-    h->d_plc_concealed = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(p) + hist_bytes);
-    return 0;
-}
-
 int wmx_rtp_conceal_legs(wmx_rtp *h, int max_packets, const int16_t *d_pcm, long source_stride, long pcm_packet_stride, const uint32_t *d_len,
                          const uint32_t *d_calls, int16_t *d_pcm_out, uint32_t *d_len_out, void *stream) {
     WMX_ON_DEVICE(h);
-    if (!h || !d_pcm || !d_len || !d_calls || !d_pcm_out || !d_len_out || max_packets < 1 || max_packets > kSeqMaxCalls) {
-        set_error("wmx_rtp_conceal_legs: max_packets=%d must be 1 .. %d, and no pointer NULL", max_packets, kSeqMaxCalls);
+    if (!h || !d_pcm || !d_len || !d_calls || !d_pcm_out || !d_len_out || max_packets < 1 || max_packets > kLegMaxCalls) {
+        set_error("wmx_rtp_conceal_legs: max_packets=%d must be 1 .. %d, and no pointer NULL", max_packets, kLegMaxCalls);
         return WMX_EINVAL;
     }
     const size_t n = (size_t)h->n_streams;
-    if (pcm_packet_stride < kPlcRow || (n > 1 && source_stride < pcm_packet_stride * max_packets)) {
+    if (pcm_packet_stride < kLegRow || (n > 1 && source_stride < pcm_packet_stride * max_packets)) {
         set_error("wmx_rtp_conceal_legs: rows that overlap (pcm_packet_stride %ld < %d, or source_stride %ld shorter than %d rows)",
-                  pcm_packet_stride, kPlcRow, source_stride, max_packets);
+                  pcm_packet_stride, kLegRow, source_stride, max_packets);
         return WMX_EINVAL;
     }
-    const int16_t *in_end = d_pcm + (n - 1) * (size_t)source_stride + (size_t)(max_packets - 1) * pcm_packet_stride + kPlcRow;
-    const int16_t *out_end = d_pcm_out + n * (size_t)(kSeqMaxCalls * kPlcRow);
+    const int16_t *in_end = d_pcm + (n - 1) * (size_t)source_stride + (size_t)(max_packets - 1) * pcm_packet_stride + kLegRow;
+    const int16_t *out_end = d_pcm_out + n * (size_t)(kLegMaxCalls * kLegRow);
     if (reinterpret_cast<uintptr_t>(d_pcm) < reinterpret_cast<uintptr_t>(out_end) &&
         reinterpret_cast<uintptr_t>(d_pcm_out) < reinterpret_cast<uintptr_t>(in_end)) {
         set_error("wmx_rtp_conceal_legs: the repaired rows overlap the rows they are made from");
         return WMX_EINVAL;
     }
-    const int rcs = plc_state(h);
+    const int rcs = h->plc.make();
     if (rcs) return rcs;
     const bool wide = aligned_to(d_pcm, pcm_packet_stride * 2, 4) && (source_stride * 2) % 4 == 0 && reinterpret_cast<uintptr_t>(d_pcm_out) % 4 == 0;
     hipLaunchKernelGGL(wide ? rtp_conceal_legs_kernel<true> : rtp_conceal_legs_kernel<false>,
                        dim3((unsigned)((n + kPlcLegsPerBlock - 1) / kPlcLegsPerBlock)), dim3(64 * kPlcLegsPerBlock), 0, as_stream(stream), d_pcm,
-                       source_stride, pcm_packet_stride, d_len, d_calls, max_packets, d_pcm_out, d_len_out, h->d_plc_hist, h->d_plc_concealed,
-                       h->n_streams);
+                       source_stride, pcm_packet_stride, d_len, d_calls, max_packets, d_pcm_out, d_len_out, h->plc.at<int16_t>(kPlcColHist),
+                       h->plc.at<uint32_t>(kPlcColConcealed), h->n_streams);
     WMX_LAUNCH_CHECK();
     return 0;
 }
@@ -912,21 +941,8 @@ int wmx_rtp_conceal_legs(wmx_rtp *h, int max_packets, const int16_t *d_pcm, long
 // a fresh history and concealed = 0 for the listed legs (NULL = all), on `stream`: a new call does not repeat the old call's voice
 int wmx_rtp_reset_conceal(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(h);
-    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_conceal: leg", "handle")) return WMX_EINVAL;
-    const bool fresh = !h->d_plc_hist;
-    const int rcs = plc_state(h);
-    if (rcs || fresh) return rcs;  // just made: zero already
-    hipStream_t s = as_stream(stream);
-    if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(h->d_plc_hist, 0, (size_t)h->n_streams * (kPlcHist * sizeof(int16_t) + sizeof(uint32_t)), s));
-        return 0;
-    }
-    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
-        WMX_HIP(hipMemsetAsync(h->d_plc_hist + (size_t)host_idx[i] * kPlcHist, 0, kPlcHist * sizeof(int16_t), s));
-        WMX_HIP(hipMemsetAsync(h->d_plc_concealed + host_idx[i], 0, sizeof(uint32_t), s));
-    }
-    return 0;
+    if (!h) return WMX_EINVAL;
+    return h->plc.reset("wmx_rtp_reset_conceal: leg", host_idx, n, as_stream(stream));
 }
 
 // hist (n_streams x 320 int16, newest last) and concealed (uint32) of every leg as the work queued on `stream` leaves them; any pointer
@@ -934,56 +950,34 @@ int wmx_rtp_reset_conceal(wmx_rtp *h, const int32_t *host_idx, int n, void *stre
 int wmx_rtp_export_conceal(wmx_rtp *h, int16_t *hist, uint32_t *concealed, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
-    const size_t n = (size_t)h->n_streams;
-    if (!h->d_plc_hist) {  // no leg has been concealed on this handle: all zero
-        if (hist) memset(hist, 0, n * kPlcHist * sizeof(int16_t));
-        if (concealed) memset(concealed, 0, n * sizeof(uint32_t));
-        return 0;
-    }
-    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
-    if (hist) WMX_HIP(hipMemcpy(hist, h->d_plc_hist, n * kPlcHist * sizeof(int16_t), hipMemcpyDeviceToHost));
-    if (concealed) WMX_HIP(hipMemcpy(concealed, h->d_plc_concealed, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
+    return h->plc.export_to({hist, concealed}, as_stream(stream));
 }
 
 // ---- the DTMF rule per leg (include/wmix_amd.h, leg_dtmf.h)
-// the state, all zero (nothing reported, no key down, no event timestamp), from the first call that needs it on
-static int dtmf_state(wmx_rtp *h) {
-    if (h->d_dtmf_ring) return 0;
-    const size_t n = (size_t)h->n_streams;
-    void *p = nullptr;
-    const int rc = zeroed_block(&p, n * (sizeof(uint64_t) + 3 * sizeof(uint32_t)), "hipMemset(DTMF state)");
-    if (rc) return rc;
-    h->d_dtmf_ring = static_cast<uint64_t *>(p);
-    h->d_dtmf_count = reinterpret_cast<uint32_t *>(h->d_dtmf_ring + n);
-    h->d_dtmf_ts = h->d_dtmf_count + n;
-    h->d_dtmf_flags = h->d_dtmf_ts + n;
-    return 0;
-}
-
 int wmx_rtp_detect_dtmf_legs(wmx_rtp *h, int max_packets, const uint8_t *d_in, long leg_stride, long packet_stride, const int32_t *d_recv,
                              int16_t *d_pcm, long source_stride, long pcm_packet_stride, const uint32_t *d_len, const uint32_t *d_calls,
                              int event_pt, int suppress, void *stream) {
     WMX_ON_DEVICE(h);
-    if (!h || !d_in || !d_recv || !d_pcm || !d_len || max_packets < 1 || max_packets > kSeqMaxCalls || event_pt < 96 || event_pt > 127) {
+    if (!h || !d_in || !d_recv || !d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls || event_pt < 96 || event_pt > 127) {
         set_error("wmx_rtp_detect_dtmf_legs: max_packets=%d must be 1 .. %d, event_pt=%d 96 .. 127, and no pointer but d_calls NULL", max_packets,
-                  kSeqMaxCalls, event_pt);
+                  kLegMaxCalls, event_pt);
         return WMX_EINVAL;
     }
     const size_t n = (size_t)h->n_streams;
-    if (packet_stride < kRtpHeader + kRtpG711Payload || pcm_packet_stride < kDtmfRow ||
+    if (packet_stride < kRtpHeader + kRtpG711Payload || pcm_packet_stride < kLegRow ||
         (n > 1 && (leg_stride < packet_stride * max_packets || source_stride < pcm_packet_stride * max_packets))) {
         set_error("wmx_rtp_detect_dtmf_legs: rows that overlap (packet_stride %ld < %d, pcm_packet_stride %ld < %d, or a leg stride shorter than %d rows)",
-                  packet_stride, kRtpHeader + kRtpG711Payload, pcm_packet_stride, kDtmfRow, max_packets);
+                  packet_stride, kRtpHeader + kRtpG711Payload, pcm_packet_stride, kLegRow, max_packets);
         return WMX_EINVAL;
     }
-    const int rcs = dtmf_state(h);
+    const int rcs = h->dtmf.make();
     if (rcs) return rcs;
     const bool wide = aligned_to(d_pcm, pcm_packet_stride * 2, 4) && (source_stride * 2) % 4 == 0;
     hipLaunchKernelGGL(wide ? rtp_detect_dtmf_legs_kernel<true> : rtp_detect_dtmf_legs_kernel<false>,
                        dim3((unsigned)((n + kDtmfLegsPerBlock - 1) / kDtmfLegsPerBlock)), dim3(32 * kDtmfLegsPerBlock), 0, as_stream(stream), d_in,
                        leg_stride, packet_stride, d_recv, d_pcm, source_stride, pcm_packet_stride, d_len, d_calls, max_packets, (uint32_t)event_pt,
-                       suppress ? 1 : 0, h->d_dtmf_ring, h->d_dtmf_count, h->d_dtmf_ts, h->d_dtmf_flags, h->n_streams);
+                       suppress ? 1 : 0, h->dtmf.at<uint64_t>(kDtmfRing), h->dtmf.at<uint32_t>(kDtmfCount), h->dtmf.at<uint32_t>(kDtmfTs),
+                       h->dtmf.at<uint32_t>(kDtmfFlags), h->n_streams);
     WMX_LAUNCH_CHECK();
     return 0;
 }
@@ -992,23 +986,8 @@ int wmx_rtp_detect_dtmf_legs(wmx_rtp *h, int max_packets, const uint8_t *d_in, l
 // key press
 int wmx_rtp_reset_dtmf(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(h);
-    if (!h || (host_idx && n < 0)) return WMX_EINVAL;
-    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_dtmf: leg", "handle")) return WMX_EINVAL;
-    const bool fresh = !h->d_dtmf_ring;
-    const int rcs = dtmf_state(h);
-    if (rcs || fresh) return rcs;  // just made: zero already
-    hipStream_t s = as_stream(stream);
-    if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(h->d_dtmf_ring, 0, (size_t)h->n_streams * (sizeof(uint64_t) + 3 * sizeof(uint32_t)), s));
-        return 0;
-    }
-    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
-        WMX_HIP(hipMemsetAsync(h->d_dtmf_ring + host_idx[i], 0, sizeof(uint64_t), s));
-        WMX_HIP(hipMemsetAsync(h->d_dtmf_count + host_idx[i], 0, sizeof(uint32_t), s));
-        WMX_HIP(hipMemsetAsync(h->d_dtmf_ts + host_idx[i], 0, sizeof(uint32_t), s));
-        WMX_HIP(hipMemsetAsync(h->d_dtmf_flags + host_idx[i], 0, sizeof(uint32_t), s));
-    }
-    return 0;
+    if (!h) return WMX_EINVAL;
+    return h->dtmf.reset("wmx_rtp_reset_dtmf: leg", host_idx, n, as_stream(stream));
 }
 
 // count (uint32) and ring (n_streams x 8 uint8) of every leg as the work queued on `stream` leaves them; either pointer may be NULL;
@@ -1016,32 +995,10 @@ int wmx_rtp_reset_dtmf(wmx_rtp *h, const int32_t *host_idx, int n, void *stream)
 int wmx_rtp_export_dtmf(wmx_rtp *h, uint32_t *count, uint8_t *ring, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
-    const size_t n = (size_t)h->n_streams;
-    if (!h->d_dtmf_ring) {  // no leg has been listened to on this handle: all zero
-        if (count) memset(count, 0, n * sizeof(uint32_t));
-        if (ring) memset(ring, 0, n * 8);
-        return 0;
-    }
-    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
-    if (count) WMX_HIP(hipMemcpy(count, h->d_dtmf_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (ring) WMX_HIP(hipMemcpy(ring, h->d_dtmf_ring, n * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return h->dtmf.export_to({ring, count}, as_stream(stream));
 }
 
-// ---- the codec rule per stream (include/wmix_amd.h, leg_codec.h)
-// the state -- refused 0, in_codec REFERENCE, out_law the law of create -- from the first call that needs it on
-static int codec_state(wmx_rtp *h) {
-    if (h->d_refused) return 0;
-    const size_t n = (size_t)h->n_streams, law_off = n * sizeof(uint32_t) + n;
-    void *p = nullptr;
-    const int rc = zeroed_block(&p, law_off + n, "hipMemset(codec state)", law_off, h->law, n);
-    if (rc) return rc;
-    h->d_refused = static_cast<uint32_t *>(p);
-    h->d_in_codec = static_cast<uint8_t *>(p) + n * sizeof(uint32_t);
-    h->d_out_law = h->d_in_codec + n;
-    return 0;
-}
-
+// ---- the codec rule per stream (include/wmix_amd.h, leg_codec.h): fresh is refused 0, in_codec REFERENCE, out_law the law of create
 // in_codec (WMX_CODEC_*) and out_law (WMX_LAW_*) of the listed streams (NULL = all), on `stream`; the refused counts stay
 int wmx_rtp_set_codecs(wmx_rtp *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
     WMX_ON_DEVICE(h);
@@ -1052,19 +1009,20 @@ int wmx_rtp_set_codecs(wmx_rtp *h, const int32_t *host_idx, int n, int in_codec,
         return WMX_EINVAL;
     }
     if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_set_codecs: stream", "handle")) return WMX_EINVAL;
-    const int rcs = codec_state(h);
+    const int rcs = h->codec.make();
     if (rcs) return rcs;
     hipStream_t s = as_stream(stream);
+    uint8_t *d_in_codec = h->codec.at<uint8_t>(kCodecIn), *d_out_law = h->codec.at<uint8_t>(kCodecOutLaw);
     const bool is_default = in_codec == WMX_CODEC_REFERENCE && out_law == h->law;
     if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(h->d_in_codec, in_codec, (size_t)h->n_streams, s));
-        WMX_HIP(hipMemsetAsync(h->d_out_law, out_law, (size_t)h->n_streams, s));
+        WMX_HIP(hipMemsetAsync(d_in_codec, in_codec, (size_t)h->n_streams, s));
+        WMX_HIP(hipMemsetAsync(d_out_law, out_law, (size_t)h->n_streams, s));
         h->codecs_default = is_default;
         return 0;
     }
     for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
-        WMX_HIP(hipMemsetAsync(h->d_in_codec + host_idx[i], in_codec, 1, s));
-        WMX_HIP(hipMemsetAsync(h->d_out_law + host_idx[i], out_law, 1, s));
+        WMX_HIP(hipMemsetAsync(d_in_codec + host_idx[i], in_codec, 1, s));
+        WMX_HIP(hipMemsetAsync(d_out_law + host_idx[i], out_law, 1, s));
     }
     if (n > 0 && !is_default) h->codecs_default = false;
     return 0;
@@ -1075,20 +1033,7 @@ int wmx_rtp_set_codecs(wmx_rtp *h, const int32_t *host_idx, int n, int in_codec,
 int wmx_rtp_export_codecs(wmx_rtp *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
-    const size_t n = (size_t)h->n_streams;
-    if (!h->d_refused) {  // no codec has been set and nothing ingested on this handle
-        for (size_t r = 0; r < n; r++) {
-            if (in_codec) in_codec[r] = (uint8_t)WMX_CODEC_REFERENCE;
-            if (out_law) out_law[r] = (uint8_t)h->law;
-            if (refused) refused[r] = 0u;
-        }
-        return 0;
-    }
-    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
-    if (in_codec) WMX_HIP(hipMemcpy(in_codec, h->d_in_codec, n, hipMemcpyDeviceToHost));
-    if (out_law) WMX_HIP(hipMemcpy(out_law, h->d_out_law, n, hipMemcpyDeviceToHost));
-    if (refused) WMX_HIP(hipMemcpy(refused, h->d_refused, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
+    return h->codec.export_to({refused, in_codec, out_law}, as_stream(stream));
 }
 
 // wmx_rtp_ingest_legs for the handle's streams as legs, with the codec rule per leg
@@ -1099,10 +1044,11 @@ int wmx_rtp_ingest_legs_codecs(wmx_rtp *h, int max_packets, const uint8_t *d_pac
     const int rcc = ingest_legs_check("wmx_rtp_ingest_legs_codecs", h ? h->n_streams : -1, max_packets, d_packets, leg_stride, packet_stride,
                                       d_recv_bytes, d_pcm, source_stride, pcm_packet_stride, d_len);
     if (rcc) return rcc;
-    const int rcs = codec_state(h);
+    const int rcs = h->codec.make();
     if (rcs) return rcs;
     return ingest_legs_launch(h->n_streams, max_packets, d_packets, leg_stride, packet_stride, d_recv_bytes, d_pcm, source_stride,
-                              pcm_packet_stride, d_len, d_seq_raw, h->codecs_default ? nullptr : h->d_in_codec, h->d_refused, stream);
+                              pcm_packet_stride, d_len, d_seq_raw, h->codecs_default ? nullptr : h->codec.at<uint8_t>(kCodecIn),
+                              h->codec.at<uint32_t>(kCodecRefused), stream);
 }
 
 int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timestamp) {
@@ -1110,8 +1056,8 @@ int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timest
     if (!h || stream_index < 0 || stream_index >= h->n_streams) return WMX_EINVAL;
     uint32_t s = 0, t = 0;
     WMX_HIP(hipDeviceSynchronize());
-    WMX_HIP(hipMemcpy(&s, h->d_seq + stream_index, 4, hipMemcpyDeviceToHost));
-    WMX_HIP(hipMemcpy(&t, h->d_ts + stream_index, 4, hipMemcpyDeviceToHost));
+    WMX_HIP(hipMemcpy(&s, h->send.at<uint32_t>(kSendSeq) + stream_index, 4, hipMemcpyDeviceToHost));
+    WMX_HIP(hipMemcpy(&t, h->send.at<uint32_t>(kSendTs) + stream_index, 4, hipMemcpyDeviceToHost));
     if (seq) *seq = (uint16_t)s;
     if (timestamp) *timestamp = t;
     return 0;

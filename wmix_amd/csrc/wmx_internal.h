@@ -241,6 +241,15 @@ MixPlayView mix_play_view(const wmx_mix *m);
 void mix_played(wmx_mix *m, uint32_t bytes);
 
 #ifdef __HIPCC__
+// Hand-off of LDS data between lanes of ONE wavefront.  A wave's LDS instructions are executed in issue order by the
+// hardware, so a ds_read issued after a ds_write of another lane of the same wave already sees the data.  What is needed
+// is only that the COMPILER keeps the order: a wavefront-scope fence (no s_waitcnt vmcnt(0), no s_barrier -- unlike
+// __syncthreads(), which would also drain every outstanding global load/store at each of the ~40 LDS phases of a block).
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
 // Lane-per-stream kernels (VAD, AGC) walk their state field by field along a sequential dependency chain, one wave
 // per SIMD: every first touch of a field would expose a full HBM round trip.  touch_line() requests a line up front
 // (result discarded; loads return in order, so ordinary loads behind the touches are still waited for correctly);
