@@ -3,6 +3,7 @@ out.  Every datagram of every tick is compared with the replay of tests/test_hos
 reference ring per leg with a cursor per source leg (LegsOracle), the drain and the oracle's egress, fed by the same scripted arrivals --
 which is wrapped here so that the layout, the mute and the calls can change between ticks.  Bytes, np.array_equal."""
 import ctypes as C
+import time
 
 import numpy as np
 import pytest
@@ -76,8 +77,9 @@ def replay_with(lib, pk, recv, layout_at, mute_at=None, fresh_at=None, select=No
 
 def run(cb, pk, recv, mode, before=None, after=None):
     """the handle over the script.  mode "wait": submit and wait, tick by tick; "ahead": the rows of tick t + 1 are written and submitted
-    before tick t is waited for; "resident": wmx_conf_step_resident on rows that are on the device.  before[t](cb) runs in front of tick
-    t's submit, after(t, cb) behind it."""
+    before tick t is waited for; "poll": as "ahead", but a tick is collected by asking cb.poll(slot) until it says yes (5 s at the most),
+    never by waiting; "resident": wmx_conf_step_resident on rows that are on the device.  before[t](cb) runs in front of tick t's submit,
+    after(t, cb) behind it."""
     import torch
     n_t, n = recv.shape[:2]
     out, queued = np.zeros((n_t, n, 172), np.uint8), []
@@ -85,7 +87,12 @@ def run(cb, pk, recv, mode, before=None, after=None):
     def collect(depth):
         while len(queued) > depth:
             t0, k0 = queued.pop(0)
-            cb.wait(k0)
+            if mode == "poll":
+                deadline = time.monotonic() + 5.0
+                while not cb.poll(k0):
+                    assert time.monotonic() < deadline, "tick %d has not landed in 5 s" % t0
+            else:
+                cb.wait(k0)
             out[t0] = cb.rows_out[k0]
 
     for t in range(n_t):
@@ -101,7 +108,7 @@ def run(cb, pk, recv, mode, before=None, after=None):
             cb.recv[k][:] = recv[t]
             assert cb.submit() == k
             queued.append((t, k))
-            collect(1 if mode == "ahead" else 0)
+            collect(1 if mode in ("ahead", "poll") else 0)
         if after:
             after(t, cb)
     collect(0)
@@ -123,7 +130,7 @@ def bridge(n=G, slots=3, layout=LAYOUT, max_packets=K):
     return cb
 
 
-@pytest.mark.parametrize("slots,mode", [(1, "wait"), (3, "ahead"), (3, "resident")])
+@pytest.mark.parametrize("slots,mode", [(1, "wait"), (3, "ahead"), (3, "resident"), (2, "poll")])
 def test_every_datagram_is_the_replays(cuda, script, slots, mode):
     pk, recv, want = script
     cb = bridge(slots=slots)
@@ -236,6 +243,8 @@ def test_refusals_take_no_slot_and_change_nothing(cuda, wmx, script):
     assert cb.next_slot() == 0
     cb.set_conferences(LAYOUT)
     run(cb, pk[:4], recv[:4], "wait")
+    assert cb.poll(2) and cb.poll(-1)  # a slot that is not in flight, and every slot behind the run: at once
+    assert wmx.wmx_conf_poll(cb._h, cb.slots) == EINVAL and wmx.wmx_conf_wait(cb._h, cb.slots) == EINVAL
 
     def state():
         return cb.next_slot(), cb.export_legs(), [cb.export_ring(g) for g in range(G)], [cb.sender_state(g) for g in range(G)]
@@ -254,3 +263,4 @@ def test_refusals_take_no_slot_and_change_nothing(cuda, wmx, script):
     assert all(np.array_equal(before[1][k], after[1][k]) for k in before[1])
     assert all(np.array_equal(a[0], b[0]) and a[1:] == b[1:] for a, b in zip(before[2], after[2]))
     cb.close()
+    assert cb.rows_in is None and cb.recv is None and cb.rows_out is None  # views of pinned rows that are gone

@@ -9,6 +9,9 @@ unless asked for) lets a test make "HIP call n of this entry point" fail.  For e
     checkpoint (wmx_chain_export_stream / _export_cohort) and submits again;
   * either way the next three submits deliver exactly what an undisturbed run delivers.
 
+The pipes, the paced tick (kind "rt") and the conference handle (kind "conf") rotate their slots through one implementation
+(wmix_amd/csrc/slot_ring.h): every kind walks it.
+
 The child process below does the work (it must load the variant library; this process has the product)."""
 import ctypes as C
 import json
@@ -114,9 +117,105 @@ def _child_rt():
     print(json.dumps(report))
 
 
+def _child_conf():
+    """the conference handle (wmx_conf_submit / _wait / _poll over three slots, the script of tests/test_conf_gpu.py) under the same faults:
+    a failing wait or poll changes nothing; a submit that fails before its first launch has taken no slot and moved no rotation, so the
+    same rows submitted again and the two ticks behind them are those of an undisturbed handle.  The cursors and the senders have no
+    import call: the walk ends at the first tick that is lost (the rule of the "rtp" kind)."""
+    from wmix_amd import _lib
+    from wmix_amd.conf import ConfBridge
+    from test_conf_gpu import G, K, LAYOUT, SEED, T
+    from test_host_tick_bridge_rtp_gpu import arrivals
+    L = _lib.lib()
+    assert "WMX_FAULT_INJECTION" in _lib.build_info()
+    L.wmx_debug_fail_nth_hip_call.argtypes = [C.c_long]
+    L.wmx_debug_hip_calls.restype = C.c_long
+    pk, recv = arrivals(SEED, T, G)
+
+    def make():
+        cb = ConfBridge(G, slots=3, max_packets=K)
+        cb.set_conferences(LAYOUT)
+        return cb
+
+    def submit(cb, t, arm=0):
+        k = cb.next_slot()
+        cb.rows_in[k][:, :, :172] = pk[t]
+        cb.recv[k][:] = recv[t]
+        slot = C.c_int(-1)
+        if arm:
+            L.wmx_debug_fail_nth_hip_call(arm)
+        rc = L.wmx_conf_submit(cb._h, C.byref(slot), cb._stream())
+        calls = L.wmx_debug_hip_calls()
+        L.wmx_debug_fail_nth_hip_call(0)
+        assert slot.value == (k if rc == 0 else -1)
+        return rc, k, calls
+
+    u = make()
+    want = np.zeros((T, G, 172), np.uint8)
+    for t in range(T):
+        rc, k, _ = submit(u, t)
+        assert rc == 0
+        u.wait(k)
+        want[t] = u.rows_out[k]
+    u.close()
+
+    f = make()
+
+    def clean(t, what):
+        rc, k, _ = submit(f, t)
+        assert rc == 0, (what, t, L.wmx_last_error())
+        f.wait(k)
+        assert np.array_equal(f.rows_out[k], want[t]), what
+
+    t = 0
+    for _ in range(6):  # past the first rotation: every submit from here on makes the same runtime calls
+        clean(t, "the first rotation")
+        t += 1
+    report = {"kind": "conf", "faults": 0, "before_first_launch": 0, "lost_steps": 0, "wait_faults": 0, "poll_faults": 0}
+    # wmx_conf_wait / wmx_conf_poll on a slot in flight: a failing call changes nothing
+    for name, fn in (("wait", L.wmx_conf_wait), ("poll", L.wmx_conf_poll)):
+        for j in (1, 2, 3, 4):
+            rc, k, _ = submit(f, t)
+            assert rc == 0
+            L.wmx_debug_fail_nth_hip_call(j)
+            rw = fn(f._h, k)
+            L.wmx_debug_fail_nth_hip_call(0)
+            assert rw <= -11000 or rw in (0, 1), (name, j, rw)
+            report[name + "_faults"] += rw < 0
+            f.wait(k)
+            assert np.array_equal(f.rows_out[k], want[t]), (name + " fault", j)
+            t += 1
+    i = 1
+    while True:
+        assert t + 3 < T, "ran out of ticks at fault %d" % i
+        nxt = f.next_slot()
+        rc, _, calls = submit(f, t, arm=i)
+        if rc == 0:  # the fault lies behind the last call of a submit: every call has had its turn
+            assert calls < i
+            f.wait(-1)
+            break
+        assert rc <= -11000, (i, rc)
+        report["faults"] += 1
+        if b"the tick is lost" in L.wmx_last_error():
+            report["lost_steps"] += 1
+            assert f.next_slot() == nxt  # the rotation and the slots in flight are as before all the same
+            break
+        report["before_first_launch"] += 1
+        assert f.next_slot() == nxt
+        for tt in (t, t + 1, t + 2):  # the same rows again, then two more ticks
+            clean(tt, "tick %d after fault %d" % (tt, i))
+        t += 3
+        i += 1
+    assert f.poll(-1)
+    f.close()
+    print(json.dumps(report))
+
+
 def _child(kind):
     if kind == "rt":
         return _child_rt()
+    if kind == "conf":
+        return _child_conf()
     import torch
     from wmix_amd import _lib, synth
     from wmix_amd.lifetime import Lifetime
@@ -238,7 +337,7 @@ def _child(kind):
     print(json.dumps(report))
 
 
-@pytest.mark.parametrize("kind", ["pcm", "rtp", "rt"])
+@pytest.mark.parametrize("kind", ["pcm", "rtp", "rt", "conf"])
 def test_every_fallible_call_of_a_submit(cuda, kind):
     # __graft_entry__.build() makes it; `make` brings it up to date when a source has changed since (nothing to do otherwise, a minute of
     # hipcc if the tree was not built that way at all)
@@ -254,6 +353,8 @@ def test_every_fallible_call_of_a_submit(cuda, kind):
     assert rep["before_first_launch"] >= 3 and rep["wait_faults"] >= 2, rep
     if kind == "pcm":
         assert rep["lost_steps"] >= 10 and rep["faults"] == rep["before_first_launch"] + rep["lost_steps"], rep
+    if kind == "conf":  # wmx_conf_poll makes one call that can fail, its device scope (the event is queried, and "not ready" is no error)
+        assert rep["poll_faults"] >= 1 and rep["lost_steps"] == 1, rep
 
 
 def test_the_product_build_has_no_fault_hooks(wmx):

@@ -90,6 +90,7 @@ def test_rt_rtp_equals_the_single_pipe(cuda, oracle_port):
         assert rt.tick(None) == slot
         got[k] = rt.gather(slot)
     rt.close()
+    assert rt.h_in is None and rt.h_out is None and rt.h_far is None and rt.h_far_rows is None  # views of pinned rows that are gone
     assert np.array_equal(got, want)
     rt = RtBatch(S, cuda, sub_batch=10, slots=1, kind="rtp")
     d_out.zero_()

@@ -66,6 +66,14 @@ def check(rc, what=""):
         raise WmxError("%s failed (rc=%d): %s" % (what or "wmx call", rc, msg))
 
 
+def host_rows(ptr, shape, dtype):
+    """numpy view of a pinned host buffer the library owns (the slots' rows of wmx_pipe, wmx_rt and wmx_conf): valid until the handle
+    is destroyed"""
+    import numpy as np
+    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    return np.frombuffer((C.c_uint8 * n).from_address(ptr), dtype=dtype).reshape(shape)
+
+
 # ---------------------------------------------------------------- the signatures: read from include/*.h, bound once by lib()
 # The scalar types the headers use.  Every pointer (`T *name`, `name[]`) is c_void_p whatever it points to -- None, an address
 # (.data_ptr(), .ctypes.data), byref(...), pointer(...) and ctypes arrays all pass -- except a returned `const char *`: c_char_p.

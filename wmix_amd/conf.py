@@ -5,15 +5,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, host_rows, lib
 from .rtp import CODEC, LAW
 
 OUT_ROW = 172
-
-
-def _view(ptr, shape, dtype):
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    return np.frombuffer((C.c_uint8 * n).from_address(ptr), dtype=dtype).reshape(shape)
 
 
 class ConfBridge:
@@ -27,9 +22,9 @@ class ConfBridge:
         self.in_row = lib().wmx_conf_in_row_bytes(self._h)
         L = lib()
         # datagram rows [n_legs, max_packets, 176], what recvfrom returned [n_legs, max_packets], datagrams out [n_legs, 172]
-        self.rows_in = [_view(L.wmx_conf_in(self._h, k), (n_legs, max_packets, self.in_row), np.uint8) for k in range(slots)]
-        self.recv = [_view(L.wmx_conf_recv(self._h, k), (n_legs, max_packets), np.int32) for k in range(slots)]
-        self.rows_out = [_view(L.wmx_conf_out(self._h, k), (n_legs, OUT_ROW), np.uint8) for k in range(slots)]
+        self.rows_in = [host_rows(L.wmx_conf_in(self._h, k), (n_legs, max_packets, self.in_row), np.uint8) for k in range(slots)]
+        self.recv = [host_rows(L.wmx_conf_recv(self._h, k), (n_legs, max_packets), np.int32) for k in range(slots)]
+        self.rows_out = [host_rows(L.wmx_conf_out(self._h, k), (n_legs, OUT_ROW), np.uint8) for k in range(slots)]
 
     @staticmethod
     def _stream():
@@ -183,6 +178,8 @@ class ConfBridge:
         return s.value, t.value
 
     def close(self):
+        """destroys the handle and its pinned rows: rows_in, recv and rows_out become None, and views taken from them earlier are invalid
+        from here on"""
         if self._h:
             self.rows_in = self.recv = self.rows_out = None  # views of memory that goes away
             lib().wmx_conf_destroy(self._h)

@@ -16,28 +16,28 @@
 // (wmx_conf_denoise) wmx_nsx_process_legs stands behind the sequencer and the DTMF detection and in front of the selection: each leg's
 // rows of the tick go through the leg's own fixed-point noise suppressor in place, in the order the load will consume them.
 //
-// PER SLOT (made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a 4-byte
-// boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and three events.  PER HANDLE: the mixer
+// PER SLOT (slot_ring.h, made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a
+// 4-byte boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and the events.  PER HANDLE: the mixer
 // (rings, layout, leg cursors, envelopes), the senders, the PCM rows between ingest and load, d_len, the host's mute and the mask
-// talker selection writes for the load, the copy-in and the copy-out stream.  wmx_conf_submit(slot k) queues H2D on the copy-in stream
+// talker selection writes for the load, the ring's copy-in and copy-out stream.  wmx_conf_submit(slot k) queues H2D on the copy-in stream
 // -> (event) -> the launches on the caller's stream -> (event) -> D2H on the copy-out stream -> (event) and returns at once: with three
 // slots the upload of tick t + 1 and the download of tick t - 1 run beside the launches of tick t.  The per-handle buffers are shared
 // by every tick, so the handle takes ONE compute stream, like wmx_pipe.
 #include <vector>
-#include "wmx_internal.h"
+#include "pipe_internal.h"
 #include "leg_calls.h"
 
 namespace {
 using wmx::kLegRow;
 using wmx::kLegRowBytes;
 constexpr int kInRow = 176;    // a datagram row in: 172 bytes, rows on 4-byte boundaries
-constexpr int kOutRow = 172;   // 12-byte RTP header + 160 G.711 codes
+using wmx::kDatagram;  // a datagram out: 12-byte RTP header + 160 G.711 codes
 static_assert(wmx::kLegMaxCalls == WMX_MIX_MAX_LEG_PACKETS, "leg_calls.h and include/wmix_amd.h name one limit");
 }  // namespace
 
 struct wmx_conf {
     int device;  // first member of every handle (wmx_handle_device)
-    int n_legs, slots, max_packets;
+    int n_legs, max_packets;
     wmx_mix *mix;
     wmx_rtp *snd;
     int16_t *d_pcm;    // [n_legs][max_packets][160] between ingest and load
@@ -59,17 +59,8 @@ struct wmx_conf {
     bool mute_on;
     int max_speakers, decay_shift;  // max_speakers 0: selection off
     uint32_t floor;
-    struct Slot {
-        uint8_t *h_in, *h_out;
-        int32_t *h_recv;
-        uint8_t *d_in, *d_out;
-        int32_t *d_recv;
-        hipEvent_t ev_in, ev_done, ev_out;
-        bool in_flight;
-    };
-    std::vector<Slot> slot;
-    hipStream_t s_in, s_out;
-    int next;
+    enum { kIn, kRecv, kOut };  // the slots' buffers (slot_ring.h)
+    wmx::SlotRing ring;
 };
 
 // the launches of one tick on rows that are on the device
@@ -110,8 +101,8 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         rc = wmx_mix_load_minus_legs(h->mix, h->d_pcm, kLegRowBytes, 8000, 1, 16, (long)K * kLegRow, kLegRow, K, h->d_len, load_mute, 1, stream);
     if (rc != 0) return rc;
     uint32_t bytes = 0;
-    rc = wmx_rtp_egress_rings(h->snd, h->mix, d_out, kOutRow, &bytes, stream);
-    if (rc == 0 && bytes != (uint32_t)kOutRow) {
+    rc = wmx_rtp_egress_rings(h->snd, h->mix, d_out, kDatagram, &bytes, stream);
+    if (rc == 0 && bytes != (uint32_t)kDatagram) {
         wmx::set_error("wmx_conf: egress made %u-byte datagrams", bytes);
         return WMX_ESTATE;
     }
@@ -126,27 +117,13 @@ static int conf_reset_denoiser(wmx_conf *h, const int32_t *host_idx, int n, void
     return wmx_nsx_reset_streams(h->nsx, all.data(), h->n_legs, stream);
 }
 
-static bool conf_slot_ok(const wmx_conf *h, int slot) { return h && slot >= 0 && slot < h->slots; }
-
 extern "C" {
 
 int wmx_conf_destroy(wmx_conf *h) {
     WMX_ON_DEVICE(h);
     if (!h) return 0;
     (void)hipDeviceSynchronize();
-    for (wmx_conf::Slot &s : h->slot) {
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        if (s.h_recv) (void)hipHostFree(s.h_recv);
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.d_out) (void)hipFree(s.d_out);
-        if (s.d_recv) (void)hipFree(s.d_recv);
-        if (s.ev_in) (void)hipEventDestroy(s.ev_in);
-        if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-        if (s.ev_out) (void)hipEventDestroy(s.ev_out);
-    }
-    if (h->s_in) (void)hipStreamDestroy(h->s_in);
-    if (h->s_out) (void)hipStreamDestroy(h->s_out);
+    h->ring.destroy();
     if (h->d_pcm) (void)hipFree(h->d_pcm);
     if (h->d_len) (void)hipFree(h->d_len);
     if (h->d_calls) (void)hipFree(h->d_calls);  // d_seq lies behind it
@@ -165,9 +142,9 @@ int wmx_conf_destroy(wmx_conf *h) {
 int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int law) {
     if (!out) return WMX_EINVAL;
     *out = nullptr;
-    if (n_legs < 1 || slots < 1 || slots > 16 || max_packets < 1 || max_packets > WMX_MIX_MAX_LEG_PACKETS || (law != WMX_LAW_A && law != WMX_LAW_U)) {
-        wmx::set_error("wmx_conf_create: n_legs=%d slots=%d (1 .. 16) max_packets=%d (1 .. %d) law=%d", n_legs, slots, max_packets,
-                       WMX_MIX_MAX_LEG_PACKETS, law);
+    if (n_legs < 1 || !wmx::slots_ok(slots) || max_packets < 1 || max_packets > WMX_MIX_MAX_LEG_PACKETS || (law != WMX_LAW_A && law != WMX_LAW_U)) {
+        wmx::set_error("wmx_conf_create: n_legs=%d slots=%d (1 .. %d) max_packets=%d (1 .. %d) law=%d", n_legs, slots, wmx::kMaxSlots,
+                       max_packets, WMX_MIX_MAX_LEG_PACKETS, law);
         return WMX_EINVAL;
     }
     wmx_conf *h = new wmx_conf();
@@ -176,9 +153,7 @@ int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int 
         return WMX_ENODEV;
     }
     h->n_legs = n_legs;
-    h->slots = slots;
     h->max_packets = max_packets;
-    h->slot.assign((size_t)slots, wmx_conf::Slot{});
     const size_t rows = (size_t)n_legs * (size_t)max_packets;
     int rc = wmx_mix_create(&h->mix, n_legs, 1, 8000);
     if (rc == 0) rc = wmx_rtp_create(&h->snd, n_legs, law);
@@ -200,24 +175,8 @@ int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int 
         if (e == hipSuccess) e = hipMemset(h->d_pcm, 0, rows * kLegRow * sizeof(int16_t));
         if (e == hipSuccess) h->d_mask = h->d_mute + n_legs;
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&h->h_mute), (size_t)n_legs, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking);
-        for (wmx_conf::Slot &s : h->slot) {
-            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.h_in), rows * kInRow, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.h_recv), rows * sizeof(int32_t), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.h_out), (size_t)n_legs * kOutRow, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMalloc(&s.d_in, rows * kInRow);
-            if (e == hipSuccess) e = hipMalloc(&s.d_recv, rows * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMalloc(&s.d_out, (size_t)n_legs * kOutRow);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming);
-            if (e == hipSuccess) {
-                memset(s.h_in, 0, rows * kInRow);
-                memset(s.h_recv, 0, rows * sizeof(int32_t));
-                memset(s.h_out, 0, (size_t)n_legs * kOutRow);
-            }
-        }
+        // kIn, kRecv, kOut
+        if (e == hipSuccess) e = h->ring.make(slots, {{rows * kInRow, true, -1}, {rows * sizeof(int32_t), true, -1}, {(size_t)n_legs * kDatagram, false, -1}});
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) rc = wmx::hip_fail(e, "wmx_conf_create: buffers / streams / events", __FILE__, __LINE__);
     }
@@ -379,12 +338,12 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
 }
 
 // ---- the slots' pinned rows
-int wmx_conf_slots(const wmx_conf *h) { return h ? h->slots : WMX_EINVAL; }
+int wmx_conf_slots(const wmx_conf *h) { return h ? h->ring.n() : WMX_EINVAL; }
 int wmx_conf_in_row_bytes(const wmx_conf *h) { return h ? kInRow : WMX_EINVAL; }
-uint8_t *wmx_conf_in(wmx_conf *h, int slot) { return conf_slot_ok(h, slot) ? h->slot[(size_t)slot].h_in : nullptr; }
-int32_t *wmx_conf_recv(wmx_conf *h, int slot) { return conf_slot_ok(h, slot) ? h->slot[(size_t)slot].h_recv : nullptr; }
-const uint8_t *wmx_conf_out(wmx_conf *h, int slot) { return conf_slot_ok(h, slot) ? h->slot[(size_t)slot].h_out : nullptr; }
-int wmx_conf_next_slot(const wmx_conf *h) { return h ? h->next : WMX_EINVAL; }
+uint8_t *wmx_conf_in(wmx_conf *h, int slot) { return h ? static_cast<uint8_t *>(h->ring.host(slot, wmx_conf::kIn)) : nullptr; }
+int32_t *wmx_conf_recv(wmx_conf *h, int slot) { return h ? static_cast<int32_t *>(h->ring.host(slot, wmx_conf::kRecv)) : nullptr; }
+const uint8_t *wmx_conf_out(wmx_conf *h, int slot) { return h ? static_cast<uint8_t *>(h->ring.host(slot, wmx_conf::kOut)) : nullptr; }
+int wmx_conf_next_slot(const wmx_conf *h) { return h ? h->ring.next : WMX_EINVAL; }
 wmx_mix *wmx_conf_mix(wmx_conf *h) { return h ? h->mix : nullptr; }
 wmx_rtp *wmx_conf_senders(wmx_conf *h) { return h ? h->snd : nullptr; }
 
@@ -413,49 +372,24 @@ int wmx_conf_submit(wmx_conf *h, int *slot, void *stream) {
         wmx::set_error("wmx_conf_submit: no layout (wmx_conf_set_conferences)");
         return WMX_EINVAL;
     }
-    const int k = h->next;
-    wmx_conf::Slot &s = h->slot[(size_t)k];
+    wmx::SlotRing &ring = h->ring;
+    const int k = ring.next;
     hipStream_t main = wmx::as_stream(stream);
-    if (s.in_flight) {  // only completes what an earlier submit promised
-        WMX_HIP(hipEventSynchronize(s.ev_out));
-        s.in_flight = false;
-    }
-    const size_t rows = (size_t)h->n_legs * (size_t)h->max_packets;
-    auto uploads = [&]() -> int {
-        WMX_HIP(hipMemcpyAsync(s.d_in, s.h_in, rows * kInRow, hipMemcpyHostToDevice, h->s_in));
-        WMX_HIP(hipMemcpyAsync(s.d_recv, s.h_recv, rows * sizeof(int32_t), hipMemcpyHostToDevice, h->s_in));
-        WMX_HIP(hipEventRecord(s.ev_in, h->s_in));
-        WMX_HIP(hipStreamWaitEvent(main, s.ev_in, 0));
-        return 0;
-    };
-    int rc = uploads();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(h->s_in);  // whatever was queued has read the rows: they may be rewritten and submitted again
-        (void)hipGetLastError();
-        return rc;
-    }
-    auto launches = [&]() -> int {
-        const int r = conf_launches(h, s.d_in, s.d_recv, s.d_out, stream);
-        if (r != 0) return r;
-        WMX_HIP(hipEventRecord(s.ev_done, main));
-        WMX_HIP(hipStreamWaitEvent(h->s_out, s.ev_done, 0));
-        WMX_HIP(hipMemcpyAsync(s.h_out, s.d_out, (size_t)h->n_legs * kOutRow, hipMemcpyDeviceToHost, h->s_out));
-        WMX_HIP(hipEventRecord(s.ev_out, h->s_out));
-        return 0;
-    };
-    rc = launches();
+    int rc = ring.retire(k);  // only completes what an earlier submit promised
+    if (rc == 0) rc = ring.upload(k, main);
+    if (rc != 0) return rc;
+    rc = conf_launches(h, static_cast<uint8_t *>(ring.dev(k, wmx_conf::kIn)), static_cast<int32_t *>(ring.dev(k, wmx_conf::kRecv)),
+                       static_cast<uint8_t *>(ring.dev(k, wmx_conf::kOut)), stream);
+    if (rc == 0) rc = ring.done(k, main);
+    if (rc == 0) rc = ring.download(k);  // a few KB: at once, behind the tick's own last launch
     if (rc != 0) {
         char why[512];
         snprintf(why, sizeof(why), "%s", wmx_last_error());
-        (void)hipStreamSynchronize(h->s_in);
-        (void)hipStreamSynchronize(main);
-        (void)hipStreamSynchronize(h->s_out);
-        (void)hipGetLastError();
+        ring.drain(main, true);
         wmx::set_error("wmx_conf_submit: the tick is lost (%s)", why);
         return rc;
     }
-    h->next = (k + 1) % h->slots;
-    s.in_flight = true;
+    ring.commit(k, false);
     if (slot) *slot = k;
     return 0;
 }
@@ -463,38 +397,13 @@ int wmx_conf_submit(wmx_conf *h, int *slot, void *stream) {
 // Blocks until the slot's datagrams are in its out rows (at once for a slot that is not in flight); slot < 0: every slot.
 int wmx_conf_wait(wmx_conf *h, int slot) {
     WMX_ON_DEVICE(h);
-    if (!h || slot >= h->slots) return WMX_EINVAL;
-    for (int k = 0; k < h->slots; k++) {
-        if (slot >= 0 && k != slot) continue;
-        wmx_conf::Slot &s = h->slot[(size_t)k];
-        if (s.in_flight) {
-            WMX_HIP(hipEventSynchronize(s.ev_out));
-            s.in_flight = false;
-        }
-    }
-    return 0;
+    return h ? h->ring.wait(slot) : WMX_EINVAL;
 }
 
 // Non-blocking wmx_conf_wait: 1 = the rows of `slot` (< 0: of every slot) are in host memory, 0 = still on their way.
 int wmx_conf_poll(wmx_conf *h, int slot) {
     WMX_ON_DEVICE(h);
-    if (!h || slot >= h->slots) return WMX_EINVAL;
-    int done = 1;
-    for (int k = 0; k < h->slots; k++) {
-        if (slot >= 0 && k != slot) continue;
-        wmx_conf::Slot &s = h->slot[(size_t)k];
-        if (!s.in_flight) continue;
-        const hipError_t q = hipEventQuery(s.ev_out);
-        if (q == hipSuccess) {
-            s.in_flight = false;
-        } else if (q == hipErrorNotReady) {
-            (void)hipGetLastError();
-            done = 0;
-        } else {
-            return wmx::hip_fail(q, "hipEventQuery(ev_out)", __FILE__, __LINE__);
-        }
-    }
-    return done;
+    return h ? h->ring.poll(slot) : WMX_EINVAL;
 }
 
 // the sequence rule's state of every leg (wmx_rtp_export_sequence); any pointer may be NULL; blocking

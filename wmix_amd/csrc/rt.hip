@@ -5,7 +5,7 @@
 // sub-batches, each a wmx_pipe (pipe.hip) with its own chain state, pinned host rows and device twins, all on ONE upload stream and
 // ONE download stream (two FIFOs: sub-batch 0's rows go up first and the DMA engines are never asked to interleave two uploads).
 // wmx_rt_submit queues the B sub-batches back to back on the caller's compute stream; the download of sub-batch b is queued by the
-// submit of b + 1 behind ITS noise suppressor (the blit kernel of a download starves a memory-bound kernel beside it, pipe.hip), the
+// submit of b + 1 behind ITS noise suppressor (the blit kernel of a download starves a memory-bound kernel beside it, slot_ring.h), the
 // last one by wmx_rt_wait.  Tick latency = upload(sub-batch 0) + compute(all) + download(sub-batch B - 1).
 #include "pipe_internal.h"
 
@@ -71,7 +71,7 @@ static int rt_make(wmx_rt **out, long n_streams, int sub_batch, int slots, bool 
                    unsigned stages, bool far_rows = false) {
     if (!out) return WMX_EINVAL;
     *out = nullptr;
-    if (n_streams < 1 || sub_batch < 1 || slots < 1 || slots > 16 || (n_streams + sub_batch - 1) / sub_batch > 4096) {
+    if (n_streams < 1 || sub_batch < 1 || !wmx::slots_ok(slots) || (n_streams + sub_batch - 1) / sub_batch > 4096) {
         wmx::set_error("wmx_rt_create: n_streams=%ld sub_batch=%d slots=%d", n_streams, sub_batch, slots);
         return WMX_EINVAL;
     }
@@ -173,7 +173,7 @@ static int submit_one(wmx_rt *h, size_t b, void *stream, void *vctx) {
     SubmitCtx *c = static_cast<SubmitCtx *>(vctx);
     if (c->lost) return 0;
     wmx_pipe *p = h->pipe[b];
-    p->next = c->k;
+    p->ring.set_next(c->k);
     // sub-batch 0 uploads the tick's far-end (unless it is on the device already), the others use its copy; with a far-end per stream
     // every sub-batch has (and uploads) its own far rows, or finds them at its streams' offset of d_far
     const int16_t *far_b = c->d_far;
@@ -195,7 +195,7 @@ static int submit_one(wmx_rt *h, size_t b, void *stream, void *vctx) {
 static int rt_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream) {
     const int k = h->next;
     for (wmx_pipe *p : h->pipe) {
-        const int rc = wmx::pipe_retire(p, k);
+        const int rc = p->ring.retire(k);
         if (rc != 0) return rc;  // before the first upload: nothing has moved
     }
     h->next = (k + 1) % h->slots;  // a tick takes its slot whatever becomes of its sub-batches
@@ -211,20 +211,13 @@ int wmx_rt_submit(wmx_rt *h, const int16_t *d_far, int *slot, void *stream) {
     return rt_submit(h, d_far, slot, stream);
 }
 
-// 1 when the previous tick has landed in host memory on every sub-batch, 0 when it has not, < 0 on an error.  Events are queried, never
-// waited for, and nothing is queued: a download still owed (`pending`, queued by wmx_rt_poll / _wait or the next submit) has not landed.
+// 1 when the previous tick has landed in host memory on every sub-batch, 0 when it has not, < 0 on an error.  Nothing is waited for and
+// nothing is queued: a download still owed (queued by wmx_rt_poll / _wait or the next submit) has not landed.
 static int rt_landed(wmx_rt *h) {
     const int last = (h->next + h->slots - 1) % h->slots;
     for (wmx_pipe *p : h->pipe) {
-        if (p->pending >= 0) return 0;
-        const wmx_pipe::Slot &s = p->slot[(size_t)last];
-        if (!s.in_flight) continue;
-        const hipError_t q = hipEventQuery(s.ev_out);
-        if (q == hipErrorNotReady) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        if (q != hipSuccess) return wmx::hip_fail(q, "wmx_rt_try_submit: hipEventQuery(ev_out)", __FILE__, __LINE__);
+        const int rc = p->ring.landed(last);
+        if (rc <= 0) return rc;
     }
     return 1;
 }
@@ -252,13 +245,11 @@ int wmx_rt_wait(wmx_rt *h) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
     int first = 0;
-    // queue every download still owed before blocking on the first
-    for (wmx_pipe *p : h->pipe)
-        if (p->pending >= 0) {
-            const int s = p->pending;
-            const int rc = wmx_pipe_wait(p, s);  // one sub-batch at most has a pending download after a complete submit: the last one
-            if (rc != 0 && first == 0) first = rc;
-        }
+    // queue every download still owed before blocking on the first (after a complete submit one sub-batch owes one: the last)
+    for (wmx_pipe *p : h->pipe) {
+        const int rc = p->ring.flush();
+        if (rc != 0 && first == 0) first = rc;
+    }
     for (wmx_pipe *p : h->pipe) {
         const int rc = wmx_pipe_wait(p, -1);
         if (rc != 0 && first == 0) first = rc;

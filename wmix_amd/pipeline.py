@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, host_rows, lib
 from .chain import AEC, AGC, NS, VAD
 
 DATAGRAM = 172  # 12-byte RTP header + 160 G.711 codes (20 ms at 8 kHz), src/rtp.h:33, src/rtp.c:86-95
@@ -71,13 +71,6 @@ class PcmChain(RtpChain):
         return pcm
 
 
-def _host_rows(ptr, shape, dtype):
-    """numpy view of a pinned host buffer the library owns"""
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    buf = (C.c_uint8 * n).from_address(ptr)
-    return np.frombuffer(buf, dtype=dtype).reshape(shape)
-
-
 class StreamingPipe:
     """Host-resident datagrams in, host-resident datagrams out, copies overlapped with compute (wmx_pipe_submit / _wait)."""
 
@@ -85,9 +78,9 @@ class StreamingPipe:
         self.c = chain
         self.SLOTS = chain.slots
         L = lib()
-        self.h_in = [_host_rows(L.wmx_pipe_in(chain._h, s), chain.row_shape, chain.row_dtype) for s in range(self.SLOTS)]
-        self.h_out = [_host_rows(L.wmx_pipe_out(chain._h, s), chain.row_shape, chain.row_dtype) for s in range(self.SLOTS)]
-        self.h_far = [_host_rows(L.wmx_pipe_far(chain._h, s), chain.far_shape, np.int16) for s in range(self.SLOTS)]
+        self.h_in = [host_rows(L.wmx_pipe_in(chain._h, s), chain.row_shape, chain.row_dtype) for s in range(self.SLOTS)]
+        self.h_out = [host_rows(L.wmx_pipe_out(chain._h, s), chain.row_shape, chain.row_dtype) for s in range(self.SLOTS)]
+        self.h_far = [host_rows(L.wmx_pipe_far(chain._h, s), chain.far_shape, np.int16) for s in range(self.SLOTS)]
 
     def submit(self, far=None):
         """Process the datagrams the caller has placed in h_in[slot] (slots are taken round robin); far: int16 CUDA [2, 80], or

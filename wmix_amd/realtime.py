@@ -14,9 +14,9 @@ import time
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, host_rows, lib
 from .chain import AEC, AGC, NS, VAD
-from .pipeline import DATAGRAM, PKT, _host_rows
+from .pipeline import DATAGRAM, PKT
 
 WMX_DROPPED = 1  # include/wmix_amd.h: wmx_rt_try_submit shed the tick
 
@@ -50,10 +50,10 @@ class RtBatch:
         self.lo = np.concatenate([[0], np.cumsum(self.batch_n)]).astype(np.int64)
         self.pipes = [L.wmx_rt_pipe(self._h, b) for b in range(self.B)]
         # numpy views of the library's pinned rows: h_in[b][slot] is [batch_n[b], row]
-        self.h_in = [[_host_rows(L.wmx_pipe_in(p, s), (n, self.row), self.row_dtype) for s in range(slots)] for p, n in zip(self.pipes, self.batch_n)]
-        self.h_out = [[_host_rows(L.wmx_pipe_out(p, s), (n, self.row), self.row_dtype) for s in range(slots)] for p, n in zip(self.pipes, self.batch_n)]
-        self.h_far = [_host_rows(L.wmx_rt_far(self._h, s), self.far_shape, np.int16) for s in range(slots)] if not far_rows else None
-        self.h_far_rows = ([[_host_rows(L.wmx_pipe_far(p, s), (n, self.row), np.int16) for s in range(slots)] for p, n in zip(self.pipes, self.batch_n)]
+        self.h_in = [[host_rows(L.wmx_pipe_in(p, s), (n, self.row), self.row_dtype) for s in range(slots)] for p, n in zip(self.pipes, self.batch_n)]
+        self.h_out = [[host_rows(L.wmx_pipe_out(p, s), (n, self.row), self.row_dtype) for s in range(slots)] for p, n in zip(self.pipes, self.batch_n)]
+        self.h_far = [host_rows(L.wmx_rt_far(self._h, s), self.far_shape, np.int16) for s in range(slots)] if not far_rows else None
+        self.h_far_rows = ([[host_rows(L.wmx_pipe_far(p, s), (n, self.row), np.int16) for s in range(slots)] for p, n in zip(self.pipes, self.batch_n)]
                            if far_rows else None)
 
     def locate(self, stream):
@@ -136,7 +136,10 @@ class RtBatch:
         return sum(lib().wmx_pipe_failed_steps(p) for p in self.pipes)
 
     def close(self):
+        """destroys the handle and its pinned rows: h_in, h_out, h_far and h_far_rows become None, and views taken from them earlier are
+        invalid from here on"""
         if self._h:
+            self.h_in = self.h_out = self.h_far = self.h_far_rows = None  # views of memory that goes away
             lib().wmx_rt_destroy(self._h)
             self._h = None
 
