@@ -1,7 +1,7 @@
 /* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
- *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise]
+ *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -25,6 +25,8 @@
  * (wmx_conf_export_dtmf): per report the leg, the key and whether it came from a packet.
  * --denoise: every leg's rows go through the leg's own fixed-point noise suppressor in front of talker selection and the mix
  * (wmx_conf_denoise); the JSON line then carries "denoise": 1.  It combines with every other flag.
+ * --level V: every leg's rows go through the leg's own AGC with compression gain V dB, behind the suppressor and in front of talker
+ * selection and the mix (wmx_conf_level); the JSON line then carries "level": V.  It combines with every other flag.
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -156,7 +158,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G, 
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
-                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise]\n";
+                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -164,7 +166,7 @@ int main(int argc, char **argv) {
     const int G = atoi(argv[2]), T = atoi(argv[3]);
     const char *sizes = NULL, *speakers = NULL, *platform = "alsa";
     unsigned long seed = 0;
-    int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0; /* max_gap -1: sequencing off */
+    int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0, level = -1; /* max_gap -1: sequencing off; level -1: levelling off */
     long correct = -1; /* -1: the library's default = platform/alsa */
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
@@ -184,6 +186,12 @@ int main(int argc, char **argv) {
             dtmf = 1;
         } else if (!strcmp(argv[i], "--denoise")) {
             denoise = 1;
+        } else if (!strcmp(argv[i], "--level") && i + 1 < argc) {
+            level = atoi(argv[++i]);
+            if (level < 0) {
+                fprintf(stderr, usage, argv[0]);
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--audio-only")) {
             audio_only = 1;
         } else if (!strcmp(argv[i], "--ulaw-every") && i + 1 < argc) {
@@ -232,6 +240,7 @@ int main(int argc, char **argv) {
     if (conceal) WMX_OK(wmx_conf_conceal(h, 1));
     if (dtmf) WMX_OK(wmx_conf_dtmf(h, 1, 1, DTMF_EVENT_PT));
     if (denoise) WMX_OK(wmx_conf_denoise(h, 1));
+    if (level >= 0) WMX_OK(wmx_conf_level(h, 1, level));
     int n_ulaw = 0;
     for (int g = 0; g < G; g++) {
         const int32_t leg = g;
@@ -332,6 +341,7 @@ int main(int argc, char **argv) {
         printf("], ");
     }
     if (denoise) printf("\"denoise\": 1, ");
+    if (level >= 0) printf("\"level\": %d, ", level);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

@@ -203,6 +203,23 @@ int wmx_agc_set_active(wmx_agc *h, const uint8_t *host_mask, void *stream);
 int wmx_agc_stream_state_bytes(const wmx_agc *h);
 int wmx_agc_export_stream(wmx_agc *h, int stream_index, void *host_blob);
 int wmx_agc_import_stream(wmx_agc *h, int stream_index, const void *host_blob);
+/* The ragged form for the legs of a conference bridge, on a handle created with chn == 1, freq == 8000: stream g is leg g, and a tick
+ * brings it 0 .. max_packets (1 .. WMX_MIX_MAX_LEG_PACKETS) rows of 160 samples (20 ms), slot k at d_pcm + g * leg_stride +
+ * k * packet_stride (strides in samples), with d_len[g * max_packets + k] == 320 where the slot holds a row.  Arguments, order and
+ * refusals are those of wmx_nsx_process_legs: the leg's rows are taken in the order the load makes its calls
+ * (wmix_amd/csrc/leg_calls.h): d_calls NULL, the slots with d_len == 320 in slot order; else d_calls[g] is the leg's call list
+ * (WMX_RTP_CALLS_*, what wmx_rtp_sequence_legs leaves), walked in list order, where a silence call or a data call naming a row that is
+ * not readable feeds NOTHING -- a lost packet is not 20 ms of silence to the level detector.  Each row taken is two 80-sample packets
+ * of the AGC, processed in place with the leg's own compression gain; the bits are those of wmx_agc_process over the same rows in the
+ * same order, which are one agc_process of the reference per leg.  A leg with no row this tick touches nothing: its state is neither
+ * loaded nor stored.  A row that is not taken -- a late packet, a duplicate, a refused packet -- keeps its bytes.  wmx_agc_set_active's
+ * mask holds here too.
+ * ALIGNMENT: d_pcm on a 2-byte boundary (the rows are read and written sample by sample as int16; the strides count samples, so
+ * every row then is).  Nothing wider is needed.
+ * WMX_EINVAL, nothing launched: a handle that is not 1 x 8000; max_packets outside 1 .. 4; d_pcm or d_len NULL; rows that overlap
+ * (packet_stride < 160, or with more than one leg leg_stride < max_packets * packet_stride); d_pcm on an odd address. */
+int wmx_agc_process_legs(wmx_agc *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                         const uint32_t *d_calls, void *stream);
 
 /* ------------------------------------------------------------------ AEC (float echo canceller)
  * Batched form of aec_init / aec_setFrameFar / aec_process / aec_process2 / aec_release
@@ -880,6 +897,22 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * suppressor is made the first time it is switched on, never inside a submit, and switching off and on again keeps its state.
  * wmx_conf_reset_legs also resets the listed legs' suppressor state.  wmx_conf_denoiser: the legs' wmx_nsx (NULL until the first
  * switch-on), for wmx_nsx_export_stream / wmx_nsx_import_stream on a leg.
+ * wmx_conf_level(h, on, value): between submits; off is the default.  On, wmx_agc_process_legs runs directly behind the denoiser (behind
+ * the ingest, wmx_rtp_sequence_legs -- it is given the call list exactly when the sequencer ran -- and wmx_rtp_detect_dtmf_legs) and in
+ * front of the selection: every row a leg's load will consume goes through that leg's own AGC (a wmx_agc stream of 1 x 8000, interval
+ * 10 ms, compression gain `value` dB: agc_init's `value`, the reference's wmix->volumeAgc), in place, in the order the load consumes
+ * them -- one agc_process of the reference per leg over those rows.  The keypad is judged on the row as it arrived, and a suppressed key
+ * goes in as the zeros it became; the selection, the concealment history and the load all see the levelled rows, so a quiet handset
+ * competes for a talker slot at the level it is heard at, and concealment's history is levelled audio that is not fed to the AGC
+ * again.  A lost packet feeds the AGC nothing; a late, duplicate or refused packet is not touched.  Mute and selection act at the
+ * load: a muted leg's rows are levelled all the same.  The first switch-on makes the AGC with `value` for every leg; on a handle that
+ * has one, a call with another `value` is wmx_agc_set_gain -- agc_addition for every leg, the state kept (blocking) -- and the same
+ * `value` changes no leg's gain.  A `value` that wmx_agc_create or wmx_agc_set_gain refuses is WMX_EINVAL and changes nothing, the
+ * switch included; with on == 0 the value is not looked at.  Off, the launches are those of a handle that never heard of it and the AGC's state does not move; the AGC is never made
+ * inside a submit, and switching off and on again keeps its state and every leg's gain.  wmx_conf_reset_legs gives the listed legs a
+ * fresh AGC state (wmx_agc_reset_streams) once the AGC has been made: a reset leg keeps its compression gain.  wmx_conf_leveller: the
+ * legs' wmx_agc (NULL until the first switch-on), for wmx_agc_set_gain_streams (one leg's volume), wmx_agc_stream_gain and
+ * wmx_agc_export_stream / wmx_agc_import_stream on a leg.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -901,6 +934,8 @@ int wmx_conf_dtmf(wmx_conf *h, int on, int suppress, int event_pt);
 int wmx_conf_export_dtmf(wmx_conf *h, uint32_t *count, uint8_t *ring, void *stream);
 int wmx_conf_denoise(wmx_conf *h, int on);
 wmx_nsx *wmx_conf_denoiser(wmx_conf *h);
+int wmx_conf_level(wmx_conf *h, int on, int value);
+wmx_agc *wmx_conf_leveller(wmx_conf *h);
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
 int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);

@@ -70,7 +70,14 @@ one row per leg against wmx_nsx_process on a dense plane of the same rows -- the
 own run-to-run spread stands beside the difference -- and then with one leg in eight sending against the dense call, which must
 process everyone.  Every side's rows are put back in front of every call, outside the timed region: a row cleaned over and over is
 silence, and silence takes the suppressor's short path.
-    python tools_dev/bridge_bench.py --pipe --denoise --steady --out profiles/bridge/bridge_denoise_bench.json"""
+    python tools_dev/bridge_bench.py --pipe --denoise --steady --out profiles/bridge/bridge_denoise_bench.json
+--pipe --level V adds (n), (o): the handle and the resident step of (b), (c) with levelling on at compression gain V (wmx_conf_level):
+(n) - (b), (o) - (c) are the launch of wmx_agc_process_legs, every row of the script through its leg's AGC.  Beside them the new kernel
+alone, device time (events), on as many legs: wmx_agc_process_legs on one row per leg against wmx_agc_process (its four-wave pipeline
+kernel) on a dense plane of the same rows -- the dense side twice in every repetition -- and then with one leg in eight sending; and all
+of that again with three rows per leg, the most the bench's max_packets holds.  Every
+side's rows are put back in front of every call, outside the timed region: a row levelled over and over ends at the limiter.
+    python tools_dev/bridge_bench.py --pipe --level 20 --steady --out profiles/bridge/bridge_level_bench.json"""
 import argparse
 import json
 import os
@@ -363,7 +370,50 @@ def denoise_kernel(legs, reps):
             "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
 
 
-def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False):
+def level_kernel(legs, reps, value, rows=1):
+    """wmx_agc_process_legs beside wmx_agc_process on the same rows, `rows` (1 .. 3) per leg: device milliseconds per launch"""
+    from wmix_amd.agc import AgcBatch
+    rng = np.random.default_rng(17)
+    t = np.arange(160 * rows)
+    voiced = rng.integers(300, 12000, (legs, 1)) * np.sin(2 * np.pi * rng.integers(150, 1500, (legs, 1)) * t / 8000) + rng.normal(0, 100, (legs, 160 * rows))
+    src = torch.from_numpy(np.clip(np.round(voiced), -32768, 32767).astype(np.int16)).cuda()
+    every, sparse_of = torch.full((legs, 3), 0, dtype=torch.int32, device="cuda"), torch.full((legs, 3), 0, dtype=torch.int32, device="cuda")
+    every[:, :rows] = 320
+    sparse_of[::8, :rows] = 320
+    handles = [AgcBatch(legs, 1, 8000, value) for _ in range(4)]
+    dense_rows = [torch.zeros((legs, 2 * rows, 80), dtype=torch.int16, device="cuda") for _ in range(2)]
+    leg_rows = [torch.zeros((legs, 3, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
+
+    def dense(k):
+        return (lambda: dense_rows[k].view(legs, 160 * rows).copy_(src)), (lambda: handles[k].process(dense_rows[k]))
+
+    def ragged(k, lens):
+        return (lambda: leg_rows[k][:, :rows].copy_(src.view(legs, rows, 160))), (lambda: handles[2 + k].process_legs(leg_rows[k], lens))
+
+    sides = [dense(0), ragged(0, every), dense(1), ragged(1, sparse_of)]
+    for prepare, f in sides * 20:
+        prepare()
+        f()
+    assert torch.equal(dense_rows[0].view(legs, rows, 160), leg_rows[0][:, :rows]), "the ragged call and the dense call differ"
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for _ in sides]
+    for r in range(reps):
+        for k, (prepare, f) in enumerate(sides):
+            prepare()
+            ev[k][r][0].record()
+            f()
+            ev[k][r][1].record()
+    torch.cuda.synchronize()
+    assert torch.equal(dense_rows[0].view(legs, rows, 160), leg_rows[0][:, :rows]), "the ragged call and the dense call differ"
+    d0, full, d1, sparse = (stats([a.elapsed_time(b) for a, b in side]) for side in ev)
+    for h in handles:
+        h.close()
+    return {"legs": legs, "value": value, "rows_per_leg": rows, "packets_per_row": 2, "wmx_agc_process_dense": d0, "wmx_agc_process_dense_again": d1,
+            "wmx_agc_process_legs_every_leg": full, "wmx_agc_process_legs_one_leg_in_eight": sparse,
+            "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4), "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4),
+            "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
+
+
+def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False, level=-1):
     import ctypes as C
     import time
     from wmix_amd._lib import check, lib
@@ -544,6 +594,33 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False):
             resident_dn()
             assert np.array_equal(cl.rows_out[k], m_out.cpu().numpy()), ("handle and resident step differ with denoising on, tick", t)
 
+    # (n), (o) the handle and the resident step of (b), (c) with levelling on: every row of the script through its leg's AGC
+    if level >= 0:
+        cn, co = ConfBridge(legs, 3, 3), ConfBridge(legs, 1, 3)
+        for x in (cn, co):
+            x.set_conferences(layout)
+            x.set_play_correct(0)
+            x.level(True, level)
+        for k in range(3):
+            cn.rows_in[k][:] = pk[k]
+            cn.recv[k][:] = recv[k]
+        o_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+        step["o"] = 0
+
+        def handle_lv():
+            return cn.submit()
+
+        def resident_lv():
+            i = step["o"] % CYC
+            step["o"] += 1
+            co.step_resident(r_in[i], r_recv[i], o_out)
+
+        for t in range(2 * CYC):
+            k = handle_lv()
+            cn.wait(k)
+            resident_lv()
+            assert np.array_equal(cn.rows_out[k], o_out.cpu().numpy()), ("handle and resident step differ with levelling on, tick", t)
+
     # (f), (g) the same two with a codec per leg: every ulaw_every-th leg on PCMU both ways, the others at the default
     mixed = ulaw_every > 0
     if mixed:
@@ -611,7 +688,7 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False):
         return (time.perf_counter() - t0) * 1e3 / n
 
     per_block = max(reps // BLOCKS, 8)
-    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": [], "h": [], "i": [], "j": [], "k": [], "l": [], "m": []}
+    ms = {"a": [], "b": [], "c": [], "d": [], "e": [], "f": [], "g": [], "h": [], "i": [], "j": [], "k": [], "l": [], "m": [], "n": [], "o": []}
     for _ in range(BLOCKS + 1):  # the first block warms up
         ms["a"].append(wall(parent, per_block, torch.cuda.synchronize))
         ms["b"].append(wall(handle, per_block, lambda: cb.wait(-1)))
@@ -625,6 +702,9 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False):
         if denoise:
             ms["l"].append(wall(handle_dn, per_block, lambda: cl.wait(-1)))
             ms["m"].append(wall(resident_dn, per_block, torch.cuda.synchronize))
+        if level >= 0:
+            ms["n"].append(wall(handle_lv, per_block, lambda: cn.wait(-1)))
+            ms["o"].append(wall(resident_lv, per_block, torch.cuda.synchronize))
         if mixed:
             ms["f"].append(wall(handle_mixed, per_block, lambda: cf.wait(-1)))
             ms["g"].append(wall(resident_mixed, per_block, torch.cuda.synchronize))
@@ -671,6 +751,13 @@ def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False):
                      "m_minus_c_ms": round(m_side["median_ms_per_tick"] - c["median_ms_per_tick"], 5)})
         cl.close()
         cm.close()
+    if level >= 0:
+        n_side, o_side = side(ms["n"]), side(ms["o"])
+        more.update({"steady": bool(steady), "level": level, "n_wmx_conf_3_slots_level_on": n_side, "o_step_resident_level_on": o_side,
+                     "n_minus_b_ms": round(n_side["median_ms_per_tick"] - b["median_ms_per_tick"], 5),
+                     "o_minus_c_ms": round(o_side["median_ms_per_tick"] - c["median_ms_per_tick"], 5)})
+        cn.close()
+        co.close()
     j, k = side(ms["j"]), side(ms["k"])
     keys_of_j = int(cj.export_dtmf()["count"].sum())
     assert keys_of_j == 0, keys_of_j  # the script is noise
@@ -763,6 +850,7 @@ if __name__ == "__main__":
     ap.add_argument("--ulaw-every", type=int, default=0, help="with --pipe: two more sides, every N-th leg on PCMU both ways (a codec per leg)")
     ap.add_argument("--loss-every", type=int, default=0, help="with --pipe: one packet in N never arrives, on all sides alike: the run path of the concealment")
     ap.add_argument("--denoise", action="store_true", help="with --pipe: two more sides with denoising on, and the new kernel alone beside the dense call")
+    ap.add_argument("--level", type=int, default=-1, help="with --pipe: two more sides with levelling on at this compression gain, and the new kernel alone beside the dense call")
     ap.add_argument("--steady", action="store_true", help="with --pipe: every leg sends one packet per tick, on all sides alike")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -775,9 +863,12 @@ if __name__ == "__main__":
         args.ragged, args.speakers = False, 0
     if args.pipe:
         res = {"tool": "bridge_bench --pipe", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every, args.loss_every, args.denoise, args.steady)}
+               "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every, args.loss_every, args.denoise, args.steady, args.level)}
         if args.denoise:
             res["denoise_kernel"] = denoise_kernel(res["pipe"]["legs"], args.reps)
+        if args.level >= 0:
+            res["level_kernel"] = level_kernel(res["pipe"]["legs"], args.reps, args.level)
+            res["level_kernel_three_rows"] = level_kernel(res["pipe"]["legs"], args.reps, args.level, rows=3)
         args.sizes = args.tick = ""
         args.ragged, args.speakers = False, 0
     if args.speakers:

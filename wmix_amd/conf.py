@@ -100,6 +100,32 @@ class ConfBridge:
         check(L.wmx_nsx_export_stream(nsx, int(leg), blob.ctypes.data), "wmx_nsx_export_stream")
         return blob
 
+    def level(self, on, value=20):
+        """every leg's rows go through the leg's own AGC with compression gain `value` dB, directly behind the denoiser and in front of
+        talker selection (wmx_conf_level), between submits; on a handle that has levelled before, another value is agc_addition for
+        every leg; off (the default) = the launches of before, and the AGC's state and gains stay"""
+        check(lib().wmx_conf_level(self._h, 1 if on else 0, int(value)), "wmx_conf_level")
+
+    def leveller_state(self, leg):
+        """the stream blob of one leg's AGC (wmx_agc_export_stream on wmx_conf_leveller), None before the first level(True)"""
+        L = lib()
+        agc = L.wmx_conf_leveller(self._h)
+        if not agc:
+            return None
+        blob = np.zeros(L.wmx_agc_stream_state_bytes(agc), np.uint8)
+        check(L.wmx_agc_export_stream(agc, int(leg), blob.ctypes.data), "wmx_agc_export_stream")
+        return blob
+
+    def set_leg_gain(self, legs, value):
+        """one leg's volume: agc_addition(value) for the listed legs' AGC (wmx_agc_set_gain_streams on wmx_conf_leveller), between
+        submits, ordered on the current stream; the state stays.  Needs a handle that has levelled before."""
+        L = lib()
+        agc = L.wmx_conf_leveller(self._h)
+        if not agc:
+            raise ValueError("set_leg_gain: no leveller yet (level(True, value) makes it)")
+        idx = np.ascontiguousarray(legs, dtype=np.int32)
+        check(L.wmx_agc_set_gain_streams(agc, idx.ctypes.data, idx.size, int(value), self._stream()), "wmx_agc_set_gain_streams")
+
     def set_codecs(self, legs, in_codec, out_law):
         """a G.711 codec per leg, as each call negotiated it (wmx_conf_set_codecs), between submits: in_codec "reference" (the default:
         A-law whatever arrives), "pcma", "pcmu" or "by_pt" (or WMX_CODEC_* 0 .. 3), out_law "a" / "u"; legs None = every leg"""
@@ -121,8 +147,8 @@ class ConfBridge:
 
     def reset_legs(self, legs=None):
         """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-        refused = 0, the concealment history and count zero, no key down and no digit reported, the noise suppressor as new; the leg
-        keeps its codec (None = every leg)"""
+        refused = 0, the concealment history and count zero, no key down and no digit reported, the noise suppressor and the AGC as
+        new; the leg keeps its codec and its compression gain (None = every leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

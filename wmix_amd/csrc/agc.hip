@@ -1,5 +1,6 @@
 // agc.hip -- batched legacy (fixed-point) AGC for gfx950: one LANE per stream (agc_kernel), and for mono packets one lane
-// per stream in four waves that split a packet's work (agc_pipe_kernel, further down).
+// per stream in four waves that split a packet's work (agc_pipe_kernel, further down); and for the legs of a conference bridge one
+// lane per leg over the 0 .. 4 rows a tick brought it (agc_legs_kernel, wmx_agc_process_legs).
 //
 // Replaces, for many independent streams per launch, wmix's agc_process() (src/webrtc.c:767-819)
 // over WebRtcAgc_Process in adaptive-digital mode, target 0 dBFS, limiter off
@@ -26,6 +27,7 @@
 #include "stage_life.h"
 #include "agc_gain_table.h"
 #include "spl_dev.h"
+#include "leg_calls.h"
 
 namespace wmx {
 namespace {
@@ -553,6 +555,57 @@ __global__ __launch_bounds__(256, CHN == 1 ? 4 : 2) void agc_pipe_kernel(int16_t
     }
 }
 
+// The ragged form for the legs of a conference bridge (wmx_agc_process_legs): 8 kHz mono, lane = leg and one wave per 64 legs like
+// agc_kernel, but a leg brings 0 .. 4 rows of 160 samples this tick, the count is known only here (len, calls) and the order is the
+// load's: the walk of leg_calls.h, where a call that adds nothing feeds nothing (a lost packet is not 20 ms of zeros to the level
+// detector).  Each row taken is two 80-sample packets of agc_packet, in place.  The lanes of a wave take different numbers of rows at
+// different slots: the walk is ONE rolled loop over the 4 calls x 2 packets whose body is predicated by the lane's `take` bit (the wave
+// skips an iteration nobody takes), not a branch tree per lane.  A leg with no row this tick neither loads nor stores its state; a
+// workgroup none of whose legs has a row leaves before it stages the gain table.  A row that is not taken is never addressed.
+template <bool PS>
+__global__ __launch_bounds__(64) void agc_legs_kernel(int16_t *s16, int32_t *s32, const int32_t *gain_table_g, const uint16_t *__restrict__ stream_table,
+                                                      int16_t *pcm, int n_legs, long leg_stride, long packet_stride, int max_packets,
+                                                      const uint32_t *__restrict__ len, const uint32_t *__restrict__ calls_in,
+                                                      const uint8_t *__restrict__ active) {
+    constexpr int PKT = 80;
+    static_assert(2 * PKT == kLegRow, "a row of the bridge is two packets of the 8 kHz AGC");
+    __shared__ int32_t gain_lds[PS ? 32 * 64 : 32];
+    const int leg = blockIdx.x * 64 + threadIdx.x;
+    uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
+    if (stream_active(active, leg, n_legs)) {
+        const LegWalk w = leg_calls_walk(len + (size_t)leg * max_packets, calls_in != nullptr, calls_in ? calls_in[leg] : 0u, max_packets);
+        list = w.list, take = w.data;
+    }
+    if (!__syncthreads_or(take != 0u)) return;  // nobody in this workgroup sent anything
+    if constexpr (PS)
+        stage_lane_tables(gain_lds, gain_table_g, stream_table, n_legs);
+    else if (threadIdx.x < 32)
+        gain_lds[threadIdx.x] = gain_table_g[threadIdx.x];
+    __syncthreads();
+    if (take == 0u) return;  // no stream, one that is switched off, or a leg without a row: state and rows untouched
+    using GT = typename std::conditional<PS, GainPerLane, GainShared>::type;
+    const GT gain_table{PS ? gain_lds + threadIdx.x : gain_lds};
+    int16_t r16[A16_WORDS];
+    int32_t r32[A32_WORDS];
+#pragma unroll
+    for (int f = 0; f < A32_WORDS; f++) r32[f] = s32[(size_t)f * n_legs + leg];
+#pragma unroll
+    for (int f = 0; f < A16_WORDS; f++) r16[f] = s16[(size_t)f * n_legs + leg];
+    const AgcRef S{r16, r32, 1};
+    int16_t *rows = pcm + (size_t)leg * leg_stride;
+#pragma unroll 1
+    for (uint32_t b = 0; b < 2u * (uint32_t)kLegMaxCalls; b++) {
+        const uint32_t j = b >> 1;
+        if (!((take >> j) & 1u)) continue;
+        int16_t *pkt = rows + (size_t)leg_calls_slot(list, j) * packet_stride + (size_t)(b & 1u) * PKT;
+        agc_packet<8, 1, GT>(S, gain_table, pkt, pkt, 1);
+    }
+#pragma unroll
+    for (int f = 0; f < A32_WORDS; f++) s32[(size_t)f * n_legs + leg] = r32[f];
+#pragma unroll
+    for (int f = 0; f < A16_WORDS; f++) s16[(size_t)f * n_legs + leg] = r16[f];
+}
+
 // idx == nullptr: every stream; else the n_idx listed ones (wmx_agc_reset_streams)
 __global__ void agc_fill_state(int16_t *s16, int32_t *s32, int n_streams, const int32_t *idx, int n_idx) {
     // WebRtcAgc_InitDigital digital_agc.c:259-282 + WebRtcAgc_InitVad :606-631
@@ -878,6 +931,40 @@ int wmx_agc_process(wmx_agc *h, const int16_t *d_in, int16_t *d_out, int n_packe
             AGC_LAUNCH(16, 0);
     }
 #undef AGC_LAUNCH
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// the legs of a conference bridge, each with the rows this tick brought it (include/wmix_amd.h; agc_legs_kernel)
+int wmx_agc_process_legs(wmx_agc *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                         const uint32_t *d_calls, void *stream) {
+    WMX_ON_DEVICE(h);
+    using namespace wmx;
+    if (!h || h->chn != 1 || h->freq != 8000) {
+        set_error("wmx_agc_process_legs: the handle must be 1 x 8000 (it is %d x %d)", h ? h->chn : 0, h ? h->freq : 0);
+        return WMX_EINVAL;
+    }
+    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls) {
+        set_error("wmx_agc_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kLegMaxCalls);
+        return WMX_EINVAL;
+    }
+    if (packet_stride < kLegRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
+        set_error("wmx_agc_process_legs: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", packet_stride,
+                  kLegRow, leg_stride, max_packets);
+        return WMX_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is
+        set_error("wmx_agc_process_legs: d_pcm %p is not on a 2-byte boundary (the rows are read and written as int16)", (void *)d_pcm);
+        return WMX_EINVAL;
+    }
+    const dim3 grid((unsigned)((h->n_streams + 63) / 64)), block(64);
+    hipStream_t s = as_stream(stream);
+    if (h->n_off_batch != 0)  // some leg has a compression gain of its own: per-lane tables
+        hipLaunchKernelGGL(agc_legs_kernel<true>, grid, block, 0, s, h->d_s16, h->d_s32, h->d_table, h->d_stream_table, d_pcm, h->n_streams,
+                           leg_stride, packet_stride, max_packets, d_len, d_calls, h->life.d_active);
+    else
+        hipLaunchKernelGGL(agc_legs_kernel<false>, grid, block, 0, s, h->d_s16, h->d_s32, h->d_table, (const uint16_t *)nullptr, d_pcm,
+                           h->n_streams, leg_stride, packet_stride, max_packets, d_len, d_calls, h->life.d_active);
     WMX_LAUNCH_CHECK();
     return 0;
 }

@@ -14,7 +14,9 @@
 // between the selection and the load: it turns every leg's list into rows that are all data -- a lost packet synthesised from the
 // leg's own history (wmix_amd/csrc/leg_plc.h) -- and the load is wmx_mix_load_minus_legs on those.  With denoising on
 // (wmx_conf_denoise) wmx_nsx_process_legs stands behind the sequencer and the DTMF detection and in front of the selection: each leg's
-// rows of the tick go through the leg's own fixed-point noise suppressor in place, in the order the load will consume them.
+// rows of the tick go through the leg's own fixed-point noise suppressor in place, in the order the load will consume them.  With
+// levelling on (wmx_conf_level) wmx_agc_process_legs stands directly behind it: the same rows, in the same order, through the leg's own
+// AGC with the leg's own compression gain.
 //
 // PER SLOT (slot_ring.h, made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a
 // 4-byte boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and the events.  PER HANDLE: the mixer
@@ -53,6 +55,9 @@ struct wmx_conf {
     int dtmf_pt;
     bool denoise_on;  // wmx_nsx_process_legs in front of the selection
     wmx_nsx *nsx;     // a suppressor stream per leg, made when denoising is first switched on
+    bool level_on;    // wmx_agc_process_legs behind the denoiser
+    wmx_agc *agc;     // an AGC stream per leg, made when levelling is first switched on
+    int level_value;  // the compression gain wmx_conf_level last gave every leg
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -82,6 +87,10 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         rc = wmx_nsx_process_legs(h->nsx, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
         if (rc != 0) return rc;
     }
+    if (h->level_on) {  // behind the denoiser: the level detector hears the cleaned row; selection, concealment and the load see the levelled rows
+        rc = wmx_agc_process_legs(h->agc, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
+        if (rc != 0) return rc;
+    }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
     if (h->max_speakers > 0) {
         rc = wmx_mix_select_speakers_legs(h->mix, h->d_pcm, kLegRowBytes, (long)K * kLegRow, kLegRow, K, h->d_len, host_mute, h->max_speakers,
@@ -109,12 +118,15 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
     return rc;
 }
 
-// the listed legs' suppressor streams (NULL = all) as ns_init leaves them
-static int conf_reset_denoiser(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
-    if (host_idx) return n > 0 ? wmx_nsx_reset_streams(h->nsx, host_idx, n, stream) : 0;
+// the listed legs' streams (NULL = all) of a per-leg stage as its init leaves them: the suppressor (ns_init), the AGC (agc_init, each
+// leg with the compression gain it has)
+template <class Stage>
+static int conf_reset_stage(wmx_conf *h, Stage *stage, int (*reset_streams)(Stage *, const int32_t *, int, void *), const int32_t *host_idx,
+                            int n, void *stream) {
+    if (host_idx) return n > 0 ? reset_streams(stage, host_idx, n, stream) : 0;
     std::vector<int32_t> all((size_t)h->n_legs);
     for (int g = 0; g < h->n_legs; g++) all[(size_t)g] = g;
-    return wmx_nsx_reset_streams(h->nsx, all.data(), h->n_legs, stream);
+    return reset_streams(stage, all.data(), h->n_legs, stream);
 }
 
 extern "C" {
@@ -131,6 +143,7 @@ int wmx_conf_destroy(wmx_conf *h) {
     if (h->d_mute) (void)hipFree(h->d_mute);  // d_mask lies behind it
     if (h->h_mute) (void)hipHostFree(h->h_mute);
     if (h->nsx) wmx_nsx_destroy(h->nsx);
+    if (h->agc) wmx_agc_destroy(h->agc);
     if (h->mix) wmx_mix_destroy(h->mix);
     if (h->snd) wmx_rtp_destroy(h->snd);
     delete h;
@@ -305,6 +318,35 @@ int wmx_conf_denoise(wmx_conf *h, int on) {
 // the legs' suppressor, for wmx_nsx_export_stream / wmx_nsx_import_stream on a leg; NULL until denoising is first switched on
 wmx_nsx *wmx_conf_denoiser(wmx_conf *h) { return h ? h->nsx : nullptr; }
 
+// on != 0: every leg's rows of the tick go through the leg's own AGC (wmx_agc_process_legs: 1 x 8000, interval 10 ms, compression gain
+// `value` dB as agc_init takes it) directly behind the denoiser and in front of the selection; 0 (the default): the launches of a handle
+// that never heard of it.  Between submits.  The AGC is made the first time it is switched on; on a made one another `value` is
+// agc_addition for every leg (wmx_agc_set_gain: the state stays), and off and on again keeps state and gains.  A value the AGC refuses
+// changes nothing, the switch included; off does not look at the value.
+int wmx_conf_level(wmx_conf *h, int on, int value) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (!on) {
+        h->level_on = false;
+        return 0;
+    }
+    if (!h->agc) {
+        const int rc = wmx_agc_create(&h->agc, h->n_legs, 1, 8000, 10, value);
+        if (rc != 0) return rc;
+        h->level_value = value;
+    } else if (value != h->level_value) {
+        const int rc = wmx_agc_set_gain(h->agc, value);
+        if (rc != 0) return rc;
+        h->level_value = value;
+    }
+    h->level_on = true;
+    return 0;
+}
+
+// the legs' AGC, for wmx_agc_set_gain_streams / wmx_agc_stream_gain / wmx_agc_export_stream / wmx_agc_import_stream on a leg; NULL until
+// levelling is first switched on
+wmx_agc *wmx_conf_leveller(wmx_conf *h) { return h ? h->agc : nullptr; }
+
 // a G.711 codec per leg (wmx_rtp_set_codecs over the legs; NULL = all): between submits, ordered on `stream`
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
     if (!h) return WMX_EINVAL;
@@ -320,8 +362,8 @@ int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uin
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
 
 // a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-// refused = 0, the concealment history and count zero, the DTMF state fresh, the noise suppressor as ns_init leaves it; the leg keeps
-// its codec
+// refused = 0, the concealment history and count zero, the DTMF state fresh, the noise suppressor as ns_init leaves it, the AGC as
+// agc_init leaves it; the leg keeps its codec and its compression gain
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
     // before the first of them: a bad index resets nothing
@@ -333,7 +375,8 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0) rc = wmx_rtp_reset_sequence(h->snd, host_idx, n, stream);
     if (rc == 0 && h->d_rep) rc = wmx_rtp_reset_conceal(h->snd, host_idx, n, stream);  // never switched on: no state to reset
     if (rc == 0 && h->dtmf_made) rc = wmx_rtp_reset_dtmf(h->snd, host_idx, n, stream);  // a new call inherits no half key press
-    if (rc == 0 && h->nsx) rc = conf_reset_denoiser(h, host_idx, n, stream);            // nor the old call's noise estimate
+    if (rc == 0 && h->nsx) rc = conf_reset_stage(h, h->nsx, wmx_nsx_reset_streams, host_idx, n, stream);  // nor the old call's noise estimate
+    if (rc == 0 && h->agc) rc = conf_reset_stage(h, h->agc, wmx_agc_reset_streams, host_idx, n, stream);  // nor its level estimate
     return rc;
 }
 
