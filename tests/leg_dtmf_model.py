@@ -1,7 +1,7 @@
 """A model of the bridge's DTMF rule (wmx_rtp_detect_dtmf_legs), written from the rule's text in the head of wmix_amd/csrc/leg_dtmf.h:
 per leg the debounce state, the last event timestamp, a count and a ring of eight; per tick the leg's datagram rows, what recvfrom
 returned, its PCM rows, lens and, with sequencing, the call list.  Python integers throughout the recurrence and the decision; nothing
-of the header's code.  Also the signals tests/test_leg_dtmf_host.py, tests/test_rtp_dtmf_gpu.py and tests/test_conf_dtmf_gpu.py
+of the header's code.  Also the signals tests/test_leg_dtmf_host.py, tests/test_rtp_dtmf_gpu.py and tests/conf_inputs.py
 share."""
 import numpy as np
 

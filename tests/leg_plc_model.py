@@ -4,6 +4,8 @@ numpy int64 and Python integers; nothing of wmix_amd/csrc/leg_plc.h.  Also the g
 tests/test_leg_plc_host.py and tests/test_rtp_conceal_gpu.py share."""
 import numpy as np
 
+from conf_inputs import alaw_decode, ulaw_decode  # noqa: F401  (tests/test_leg_plc_host.py takes them from here)
+
 HIST, ROW, LAG_MIN, LAG_MAX, BLEND, MAX_CALLS = 320, 160, 40, 120, 32, 4
 D, S = (lambda k: ("D", k)), ("S", None)
 
@@ -97,21 +99,6 @@ class LegsPlcModel:
 
 
 # ---- the generator of cases
-def alaw_decode(codes):
-    """G.711 A-law codes -> int16 (ITU-T G.711, the usual table-free form)"""
-    c = np.asarray(codes, np.int64) ^ 0x55
-    seg, mant = (c >> 4) & 7, c & 15
-    mag = np.where(seg == 0, (mant << 4) + 8, ((mant << 4) + 0x108) << np.maximum(seg - 1, 0))
-    return np.where(c & 0x80, mag, -mag).astype(np.int16)
-
-
-def ulaw_decode(codes):
-    """G.711 mu-law codes -> int16"""
-    c = ~np.asarray(codes, np.int64) & 0xFF
-    mag = ((((c & 15) << 3) + 0x84) << ((c >> 4) & 7)) - 0x84
-    return np.where(c & 0x80, -mag, mag).astype(np.int16)
-
-
 def audio(rng, n):
     """n samples of one of the three kinds: random A-law codes, random mu-law codes, a sine at full scale (+-32 767: the rule's
     overflow bounds) with a period somewhere in or around the lag range"""

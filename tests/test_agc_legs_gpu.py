@@ -7,9 +7,9 @@ state equal wmx_agc_process over a dense plane of the same rows in the same orde
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL
 from leg_level_model import ROW, level, rows_taken
 from leg_seq_model import pack
-from test_bridge_gpu import EINVAL
 from test_nsx_legs_gpu import IDLE_LEG, TICKS, script
 
 pytestmark = pytest.mark.gpu

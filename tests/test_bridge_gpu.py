@@ -9,39 +9,14 @@ import numpy as np
 import pytest
 
 import conftest
+from conf_inputs import EINVAL, NULL_HEAD
+from leg_oracle_model import OracleRings
 from oracle import loader as L
 
 pytestmark = pytest.mark.gpu
 
-NULL_HEAD = 0xFFFFFFFF
-EINVAL = -10001
-
 
 # ---------------------------------------------------------------- the load against P reference mixers per conference
-class OracleRings:
-    """n rings of one format, heads at byte `start`"""
-
-    def __init__(self, lib, n, ring_chn, ring_freq, start, rmode):
-        L.mix_bind(lib)
-        self.lib, self.size = lib, ring_chn * 2 * ring_freq
-        self.store = [np.zeros(self.size + 64, np.uint8) for _ in range(n)]
-        self.r = [L.MixRing() for _ in range(n)]
-        for k in range(n):
-            lib.orc_mix_ring_init(C.byref(self.r[k]), self.store[k].ctypes.data_as(C.c_void_p), ring_chn, ring_freq)
-            self.r[k].head_off, self.r[k].reduce_mode = start, rmode
-        self.play_correct = self.r[0].play_correct
-
-    def load(self, k, row, sbytes, freq, chn, head, tick, rarg):
-        """one wmix_load_data call into ring k; row holds the source and its look-ahead frame.  -> (head, tick)"""
-        row = np.ascontiguousarray(row)
-        t = C.c_uint32(tick)
-        h = self.lib.orc_load_data(C.byref(self.r[k]), row.ctypes.data_as(C.c_void_p), sbytes, freq, chn, 16, C.c_uint32(head), rarg, C.byref(t))
-        return h, t.value
-
-    def ring(self, k):
-        return self.store[k][:self.size].view(np.int16).copy()
-
-
 def oracle_minus(rings, P, src, sbytes, freq, chn, rarg, cursor, mute):
     """ring c*P+q <- the sources s != q of conference c that are not muted, in index order, every call from `cursor`.  Returns the
     cursor the calls end with (they all end with the same one: asserted)."""

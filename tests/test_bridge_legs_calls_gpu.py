@@ -1,14 +1,15 @@
 """wmx_mix_load_minus_legs_calls (wmix_amd/csrc/mix.hip, leg_cursor.h: leg_cursor_span_calls) through the Python mirror: the bridge load
-with a cursor per leg, fed a call list per leg.  The oracle is LegsOracle of tests/test_bridge_legs_gpu.py -- one reference ring per leg,
+with a cursor per leg, fed a call list per leg.  The oracle is LegsOracle of tests/leg_oracle_model.py -- one reference ring per leg,
 one cursor per source leg, one orc_load_data call per valid slot in slot order -- fed the REPAIRED rows: the call list of
 tests/leg_seq_model.py laid out as four slots, a silence call being a row of zeros with lens = sbytes (what WCT_SILENCE loads).
 Integers, np.array_equal."""
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL, NULL_HEAD
+from leg_oracle_model import LegsOracle
 from leg_seq_model import LegsSeqModel, pack, repaired_rows
-from test_bridge_gpu import EINVAL, NULL_HEAD
-from test_bridge_legs_gpu import LegsOracle, big_layout, main_layout, script
+from test_bridge_legs_gpu import big_layout, main_layout, script
 from test_rtp_sequence_gpu import arrivals
 
 pytestmark = pytest.mark.gpu

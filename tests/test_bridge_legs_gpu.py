@@ -2,92 +2,17 @@
 (wmix_amd/csrc/mix.hip, leg_cursor.h) through the Python mirror.  An RTP leg delivers 0, 1, 2 or 3 datagrams in a 20 ms tick; every
 wmix_thread_rtp_recv_pcma keeps a cursor of its own and calls wmix_load_data once per datagram that arrived (src/wmixTask.c:1266-1316).
 So the oracle is what tests/test_bridge_gpu.py uses -- one reference ring per leg, and for every ring the ordered orc_load_data calls
-of the other members of its conference -- with one cursor per SOURCE leg and as many calls per tick as that leg has valid slots.
-Integer results, np.array_equal."""
+of the other members of its conference -- with one cursor per SOURCE leg and as many calls per tick as that leg has valid slots:
+LegsOracle over OracleRings, both of tests/leg_oracle_model.py.  Integer results, np.array_equal."""
 import numpy as np
 import pytest
 
-from test_bridge_gpu import EINVAL, NULL_HEAD, OracleRings
+from conf_inputs import EINVAL, NULL_HEAD
+from leg_oracle_model import LegsOracle
 
 pytestmark = pytest.mark.gpu
 
 K = 3  # max_packets
-
-
-class LegsOracle:
-    """One reference ring per leg and one cursor per source leg.  `drop_rule`: leave out the calls include/wmix_amd.h names (the end
-    cursor more than one ring ahead of the mixer's tick, and that leg's later slots of the tick) and count them; without it every
-    call is made and the oracle itself asserts that none laps the play head."""
-
-    def __init__(self, lib, n, ring, rmode, play_correct, drop_rule=False):
-        self.rings = OracleRings(lib, n, ring[0], ring[1], 0, rmode)
-        self.size, self.pkg = self.rings.size, self.rings.size // 50  # 20 ms of ring
-        if play_correct is not None:
-            for r in self.rings.r:
-                r.play_correct = play_correct
-        self.correct = self.rings.r[0].play_correct
-        self.cursor = [(NULL_HEAD, 0)] * n
-        self.dropped = np.zeros(n, np.uint32)
-        self.drop_rule, self.n = drop_rule, n
-
-    @staticmethod
-    def samples_of_a_call(lib, ring, sbytes, freq, chn):
-        """ring samples one wmix_load_data call of this source format writes: the tick a fresh call on a scratch ring ends with"""
-        scratch = OracleRings(lib, 1, ring[0], ring[1], 0, 1)
-        end = scratch.load(0, np.zeros(sbytes // 2 + chn, np.int16), sbytes, freq, chn, NULL_HEAD, 0, 1)[1]
-        return (end - scratch.play_correct) // 2
-
-    def drain(self):
-        """the play thread's 20 ms (src/wmix.c:1347-1366) on every ring -> int16 [n, pkg / 2]"""
-        out = np.zeros((self.n, self.pkg // 2), np.int16)
-        for k, r in enumerate(self.rings.r):
-            ring = self.rings.store[k][:self.size].view(np.int16)
-            pos = (r.head_off // 2 + np.arange(self.pkg // 2)) % (self.size // 2)
-            out[k] = ring[pos]
-            ring[pos] = 0
-            r.head_off = (r.head_off + self.pkg) % self.size
-            r.tick += self.pkg
-        return out
-
-    def reset(self, legs):
-        for s in legs:
-            self.cursor[s], self.dropped[s] = (NULL_HEAD, 0), 0
-
-    def load(self, layout, src, lens, sbytes, freq, chn, n_out, mute):
-        """src [n, K, row], lens [n, K]: one tick.  Ring q <- for every other member s in list order, its valid slots in slot order."""
-        zeros = np.zeros(src.shape[2], np.int16)
-        for mem in layout:
-            if len(mem) < 2:
-                continue
-            for s in mem:
-                calls = [k for k in range(lens.shape[1]) if lens[s, k] == sbytes]
-                mix_tick = self.rings.r[s].tick
-                if self.drop_rule:  # the rule, restated: where would the call end?
-                    made, (h, tk) = [], self.cursor[s]
-                    for k in calls:
-                        tk = mix_tick + self.correct if h == NULL_HEAD or tk < mix_tick else tk
-                        if tk + 2 * n_out - mix_tick > self.size:
-                            break
-                        made.append(k)
-                        h, tk = 0, tk + 2 * n_out
-                    self.dropped[s] += len(calls) - len(made)
-                    calls = made
-                if not calls:
-                    continue
-                ends = set()
-                for q in mem:
-                    if q == s:
-                        continue
-                    h, tk = self.cursor[s]
-                    for k in calls:
-                        h, tk = self.rings.load(q, zeros if mute is not None and mute[s] else src[s, k], sbytes, freq, chn, h, tk, 1)
-                        assert tk - mix_tick <= self.size, "the reference laps the play head: leg %d" % s
-                    ends.add((h, tk))
-                assert len(ends) == 1
-                self.cursor[s] = ends.pop()
-
-    def cursors(self):
-        return np.array([c[0] for c in self.cursor], np.uint32), np.array([c[1] for c in self.cursor], np.uint32)
 
 
 def main_layout():

@@ -8,9 +8,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL, NULL_HEAD
 import conftest
+from leg_oracle_model import OracleRings
 from oracle import loader as L
-from test_bridge_gpu import EINVAL, NULL_HEAD, N, OracleRings, room, talkers, volume_add
+from test_bridge_gpu import N, room, talkers, volume_add
 
 pytestmark = pytest.mark.gpu
 

@@ -1,58 +1,20 @@
 """wmx_conf (wmix_amd/csrc/conf.hip) with every stage on at once, and with its switches changed on a running handle, against the composed
-replay of tests/conf_replay_model.py.  The stories are those of tests/test_conf_replay_model.py, which holds them against what they are
-for on the model alone; here the handle runs them.  Every test compares every datagram of every tick; after every tick speaking and
-env; at the end head, tick and dropped, every field of export_sequence, export_conceal and the three fields of export_codecs.  Bytes
-and integers, np.array_equal."""
+replay of tests/conf_replay_model.py.  The stories are those of tests/conf_stories.py, which tests/test_conf_replay_model.py holds
+against what they are for on the model alone; here the handle runs them, through handle_equals_replay() of tests/conf_harness.py.
+Every test compares every datagram of every tick; after every tick speaking and env; at the end head, tick and dropped, every field of
+export_sequence, export_conceal and the three fields of export_codecs.  Bytes and integers, np.array_equal."""
 import numpy as np
 import pytest
 
+from conf_harness import MODES, expected, handle_equals_replay, host_conf
+from conf_inputs import G, K, LAYOUT, SEED, T, ULAW, arrivals, fnv1a, ulaw_every_script
 from conf_replay_model import replay_story
+from conf_stories import (N_D, RANDOM_SEEDS, all_stages, all_stages_floor, all_stages_script, floor_of, random_schedule, sizes_script,
+                          sizes_story, slots_script, slots_story, switching, switching_script)
 from leg_codec_model import LAW_U, PCMU
 from leg_seq_model import COUNTERS
-from test_conf_gpu import G, K, LAYOUT, SEED, T, bridge, run
-from test_conf_replay_model import (N_D, RANDOM_SEEDS, all_stages, all_stages_floor, all_stages_script, floor_of, random_schedule,
-                                    sizes_script, sizes_story, slots_script, slots_story, switching, switching_script)
-from test_host_conf_codecs_gpu import ULAW, script as ulaw_every_script
-from test_host_conf_gpu import host_conf
-from test_host_tick_bridge_rtp_gpu import arrivals, fnv1a
 
 pytestmark = pytest.mark.gpu
-
-MODES = [(1, "wait"), (3, "ahead"), (3, "resident")]
-REPLAYED = {}  # a story's replay, made once and shared by the modes that run it
-
-
-def expected(key, lib, n, slots, story):
-    """story() -> (pk, recv, setup, before)"""
-    if key not in REPLAYED:
-        pk, recv, setup, before = story()
-        want, legs, m = replay_story(lib, n, slots, pk, recv, setup, before)
-        REPLAYED[key] = {"pk": pk, "recv": recv, "setup": setup, "before": before, "want": want, "legs": legs, "model": m}
-    return REPLAYED[key]
-
-
-def handle_equals_replay(e, slots, mode):
-    """the handle over the story of e, compared with the replay in all four ways"""
-    pk, recv, m = e["pk"], e["recv"], e["model"]
-    cb, seen = bridge(recv.shape[1], slots, None, recv.shape[2]), []
-    e["setup"](cb)
-    got = run(cb, pk, recv, mode, before=e["before"], after=lambda t, c: seen.append(c.export_legs()))
-    end, sq, concealed, codecs = cb.export_legs(), cb.export_sequence(), cb.export_conceal(), cb.export_codecs()
-    cb.close()
-    for t in range(recv.shape[0]):
-        for name in ("speaking", "env"):
-            assert np.array_equal(seen[t][name], e["legs"][t][name]), (name, "tick", t, seen[t][name], e["legs"][t][name])
-    assert np.array_equal(got, e["want"]), np.argwhere((got != e["want"]).any(2))[:6]
-    for name in ("head", "tick", "dropped"):
-        assert np.array_equal(end[name], e["legs"][-1][name]), (name, end[name], e["legs"][-1][name])
-    want = m.export_sequence()
-    assert sorted(want) == sorted(COUNTERS + ("next", "synced"))
-    for name in want:
-        assert np.array_equal(sq[name], want[name]), (name, sq[name], want[name])
-    assert np.array_equal(concealed, m.export_conceal()), (concealed, m.export_conceal())
-    want = m.export_codecs()
-    for name in ("in_codec", "out_law", "refused"):
-        assert np.array_equal(codecs[name], want[name]), (name, codecs[name], want[name])
 
 
 # ---- a. everything on
@@ -105,7 +67,7 @@ def test_every_size_class_and_a_ragged_last_block(cuda, oracle_port, mode):
 
 
 # ---- e. the C example, judged independently
-FLOOR_E = 950000  # between the levels of this script's packets (tests/test_host_conf_gpu.py)
+FLOOR_E = 950000  # between the levels of this script's packets (600 000 .. 1 270 000)
 
 
 def example_equals_replay(tmp_path, lib, flags, pk, recv, setup):

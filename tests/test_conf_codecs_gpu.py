@@ -1,97 +1,25 @@
 """wmx_conf_set_codecs (wmix_amd/csrc/conf.hip) through the Python mirror: a conference in which A-law legs and mu-law legs hear each
-other, each in the codec its call negotiated.  Shape, layout and script are those of tests/test_conf_gpu.py with the payload-type byte
-rewritten per leg; the reference is that file's tick-by-tick replay with the decode replaced by tests/leg_codec_model.py (the rule's
-table over the oracle's orc_G711a2PCM / orc_G711u2PCM) and one oracle sender per leg made with the leg's law.  Bytes and integers,
-np.array_equal."""
+other, each in the codec its call negotiated.  Shape, layout and script are those of tests/conf_inputs.py with the payload-type byte
+rewritten per leg (rewritten_script); the reference is codec_story() of tests/conf_single_replays.py: the tick-by-tick replay with the
+decode replaced by tests/leg_codec_model.py (the rule's table over the oracle's orc_G711a2PCM / orc_G711u2PCM) and one oracle sender
+per leg made with the leg's law (CodecReplay, tests/leg_oracle_model.py).  Bytes and integers, np.array_equal."""
 import numpy as np
 import pytest
 
-from leg_codec_model import BY_PT, LAW_A, LAW_U, PCMA, PCMU, REFERENCE, Decoders, ingest
-from leg_seq_model import COUNTERS, LegsSeqModel, repaired_rows
-from speakers_legs_model import SpeakersLegsModel
-from test_conf_gpu import G, K, LAYOUT, SEED, T, Replay, bridge, run
-from test_conf_sequence_gpu import seq_raw_of
-from test_host_tick_bridge_rtp_gpu import arrivals
+from conf_harness import bridge, run
+from conf_inputs import CHANGE_AT, EINVAL, G, K, LATER_ULAW_LEG, LAYOUT, RESET_AT, RESET_LEG, STRICT_A_LEG, T, ULAW_LEGS
+from conf_single_replays import codec_story, replay_sequenced
+from conf_stories import start
+from leg_codec_model import BY_PT, LAW_A, LAW_U, PCMA, PCMU
+from leg_oracle_model import CodecReplay, Replay
+from leg_seq_model import COUNTERS
 
 pytestmark = pytest.mark.gpu
-
-ULAW_LEGS, BY_PT_LEG, STRICT_A_LEG, LATER_ULAW_LEG, CHANGE_AT, RESET_LEG, RESET_AT = [1, 3, 6], 4, 7, 2, 15, 6, 25
-START = [(ULAW_LEGS, PCMU, LAW_U), ([BY_PT_LEG], BY_PT, LAW_A), ([STRICT_A_LEG], PCMA, LAW_A)]  # the rest: the default
-
-
-def rewritten_script():
-    """arrivals() with the payload type of every G.711 datagram rewritten: 0 on the mu-law legs (and on leg 2 from the tick it goes to
-    mu-law), alternating 8 / 0 per packet on the BY_PT leg, 8 with every fifth packet 0 on the strict A-law leg.  Payload type 96
-    (one packet in sixteen) stays on every leg, the default legs keep their 8s and 0s."""
-    pk, recv = arrivals(SEED, T, G)
-    nth = [0] * G
-    for t in range(T):
-        for g in range(G):
-            for k in range(K):
-                if recv[t, g, k] <= 0 or (pk[t, g, k, 1] & 0x7F) not in (8, 0):
-                    continue
-                pt = pk[t, g, k, 1] & 0x7F
-                if g in ULAW_LEGS or (g == LATER_ULAW_LEG and t >= CHANGE_AT):
-                    pt = 0
-                elif g == BY_PT_LEG:
-                    pt = 8 if nth[g] % 2 == 0 else 0
-                elif g == STRICT_A_LEG:
-                    pt = 0 if nth[g] % 5 == 4 else 8
-                nth[g] += 1
-                pk[t, g, k, 1] = 0x80 | pt
-    return pk, recv
-
-
-class CodecReplay(Replay):
-    """Replay of tests/test_conf_gpu.py with a codec per leg: the decode is the rule's, a leg's oracle sender is made with its law"""
-
-    def __init__(self, lib, n):
-        super().__init__(lib, n)
-        self.dec, self.in_codec, self.out_law, self.refused = Decoders(lib), [REFERENCE] * n, [LAW_A] * n, np.zeros(n, np.uint32)
-
-    def set_codecs(self, legs, in_codec, out_law):
-        for g in legs:
-            self.in_codec[g] = in_codec
-            if out_law != self.out_law[g]:  # the call goes on: seq and timestamp (the sender's first 8 bytes) stay
-                was = bytes(self.senders[g][:8])
-                self.init(self.senders[g], out_law)
-                for i, b in enumerate(was):
-                    self.senders[g][i] = b
-                self.out_law[g] = out_law
-
-    def decode(self, pk, recv, slots=K):
-        rows, lens, _ = ingest(self.dec, pk, recv, self.in_codec, self.refused)
-        pcm = np.zeros((self.n, slots, 161), np.int16)
-        pcm[:, :, :160] = rows
-        return pcm, lens
-
-    def fresh(self, legs):
-        super().fresh(legs)
-        for g in legs:  # a new call keeps the leg's codec; its sender starts again in the leg's law
-            self.init(self.senders[g], self.out_law[g])
-            self.refused[g] = 0
-
-
-def start(target):
-    for legs, in_codec, out_law in START:
-        target.set_codecs(legs, in_codec, out_law)
 
 
 @pytest.fixture(scope="module")
 def story(oracle_port):
-    """the script, every datagram the replay sends, its codec state at the end and leg 6's refused count in front of its reset"""
-    pk, recv = rewritten_script()
-    rp, out, seen = CodecReplay(oracle_port, G), np.zeros((T, G, 172), np.uint8), {}
-    start(rp)
-    for t in range(T):
-        if t == CHANGE_AT:
-            rp.set_codecs([LATER_ULAW_LEG], PCMU, LAW_U)
-        if t == RESET_AT:
-            seen["refused_before_reset"] = int(rp.refused[RESET_LEG])
-            rp.fresh([RESET_LEG])
-        pcm, lens = rp.decode(pk[t], recv[t])
-        out[t] = rp.tick(pcm, lens, LAYOUT)
-    return pk, recv, out, rp, seen
+    return codec_story(oracle_port)
 
 
 def test_the_script_reaches_what_it_is_for(oracle_port, story):
@@ -135,23 +63,6 @@ def test_every_datagram_is_the_replays(cuda, story, slots, mode):
     cb.close()
 
 
-def replay_sequenced(lib, pk, recv, select, codecs):
-    """the replay with sequence(True, 3) and speakers(*select); codecs: the legs as START sets them, else every leg at the default
-    -> (datagrams, the sequence model, per tick (speaking, env), the replay)"""
-    rp, model, spk = CodecReplay(lib, G), LegsSeqModel(G), SpeakersLegsModel(G)
-    if codecs:
-        start(rp)
-    out, sel = np.zeros((T, G, 172), np.uint8), []
-    for t in range(T):
-        pcm, lens = rp.decode(pk[t], recv[t])
-        _, new_lens, lists = model.tick(seq_raw_of(pk[t], recv[t]), lens, 3)
-        sp, mute = spk.step_legs(LAYOUT, pcm, new_lens, 320, select[0], select[1], select[2], None)
-        sel.append((sp.copy(), spk.env.copy()))
-        rows, rlens = repaired_rows(pcm, lists)
-        out[t] = rp.tick(rows, rlens, LAYOUT, mute)
-    return out, model, sel, rp
-
-
 def test_a_refused_packet_is_not_late_not_a_duplicate_and_not_heard(cuda, oracle_port, story):
     """sequence(True, 3) and speakers(2, floor, 3) on: the sequence model and the selection model are fed d_len as the codec rule leaves
     it.  A refused packet has consumed a sequence number, so what the sequence rule sees of it is a gap: lost, never late or dup."""
@@ -191,7 +102,6 @@ def test_a_refused_packet_is_not_late_not_a_duplicate_and_not_heard(cuda, oracle
 
 def test_codec_refusals_change_nothing(cuda, wmx):
     import torch
-    from test_bridge_gpu import EINVAL
     stream = torch.cuda.current_stream().cuda_stream
     cb = bridge()
     start(cb)

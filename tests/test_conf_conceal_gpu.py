@@ -1,36 +1,17 @@
 """wmx_conf_conceal (wmix_amd/csrc/conf.hip) through the Python mirror: the conference bridge with its legs sequenced and the gaps
-concealed from each leg's own history.  Layout, T, K, the replay and the runner are those of tests/test_conf_gpu.py, the scripts those of
-tests/test_conf_sequence_gpu.py.  The reference is the tick-by-tick replay fed the rows tests/leg_plc_model.py makes of the call lists
-of tests/leg_seq_model.py: four slots per leg, every one a data call.  Bytes and integers, np.array_equal."""
+concealed from each leg's own history.  Layout, T, K and the scripts are those of tests/conf_inputs.py, the runner that of
+tests/conf_harness.py.  The reference is replay_conceal() of tests/conf_single_replays.py: the tick-by-tick replay fed the rows
+tests/leg_plc_model.py makes of the call lists of tests/leg_seq_model.py, four slots per leg, every one a data call.  Bytes and
+integers, np.array_equal."""
 import numpy as np
 import pytest
 
-from leg_plc_model import LegsPlcModel, alaw_decode
-from leg_seq_model import COUNTERS, LegsSeqModel
-from test_conf_gpu import G, K, LAYOUT, T, Replay, bridge, run
-from test_conf_sequence_gpu import IN_CONF, clean_script, counters_equal, impair, replay_seq, rows_of, seq_raw_of
+from conf_harness import bridge, counters_equal, run
+from conf_inputs import EINVAL, G, IN_CONF, T, clean_script, impair, rows_of, tone_script
+from conf_single_replays import replay_conceal, replay_seq
+from leg_seq_model import COUNTERS
 
 pytestmark = pytest.mark.gpu
-
-
-def replay_conceal(lib, pk, recv, max_gap=3, fresh_at=None, plc_fresh=True):
-    """the tick-by-tick replay fed the concealment model's rows -> (datagrams [ticks, G, 172], the sequence model, the concealment
-    model, the replay).  plc_fresh=False: a reset leaves the concealment state as it was (what the device must NOT do)"""
-    rp, seq, plc = Replay(lib, G), LegsSeqModel(G), LegsPlcModel(G)
-    out = np.zeros((recv.shape[0], G, 172), np.uint8)
-    for t in range(recv.shape[0]):
-        if fresh_at and t in fresh_at:
-            rp.fresh(fresh_at[t])
-            seq.reset(fresh_at[t])
-            if plc_fresh:
-                plc.reset(fresh_at[t])
-        pcm, lens = rp.decode(pk[t], recv[t])
-        _, new_lens, lists = seq.tick(seq_raw_of(pk[t], recv[t]), lens, max_gap)
-        rows, rlens = plc.tick(pcm, new_lens, lists)
-        wide = np.zeros((G, 4, 161), np.int16)  # the oracle's look-ahead element
-        wide[:, :, :160] = rows
-        out[t] = rp.tick(wide, rlens, LAYOUT)
-    return out, seq, plc, rp
 
 
 @pytest.fixture(scope="module")
@@ -98,19 +79,6 @@ def test_a_clean_script_is_sent_as_with_concealment_off(cuda):
         assert not cb.export_conceal().any() and not any(cb.export_sequence()[name].any() for name in COUNTERS)
         cb.close()
     assert np.array_equal(sent[0], sent[1]) and (sent[0][:, IN_CONF, 12:] != 0xD5).any()
-
-
-def tone_script(lost_at):
-    """a steady, quiet script in which leg 6 sends a tone of period 50 -- one period of loud A-law codes, tiled through its packets --
-    and loses the packet of tick lost_at"""
-    script = clean_script(8, steady=True, quiet=True)
-    loud = np.array([c for c in range(256) if 2000 <= abs(int(alaw_decode([c])[0])) <= 8000], np.uint8)
-    one = np.random.default_rng(12).choice(loud, size=50)
-    for t in range(T):
-        s, _, _ = script[t][6][0]
-        script[t][6] = [(s, 8, one[(t * 160 + np.arange(160)) % 50])]
-    script[lost_at][6] = []
-    return script, alaw_decode(one)
 
 
 def test_the_other_legs_hear_the_tone_go_on_through_a_lost_packet(cuda, oracle_port):
@@ -183,7 +151,6 @@ def test_a_reset_leg_conceals_from_a_fresh_history(cuda, wmx, oracle_port):
 
 
 def test_conceal_refusals(cuda, wmx):
-    from test_bridge_gpu import EINVAL
     assert wmx.wmx_conf_conceal(None, 1) == EINVAL and wmx.wmx_conf_export_conceal(None, None, None) == EINVAL
     cb = bridge()
     assert not cb.export_conceal().any()

@@ -1,5 +1,5 @@
-"""wmx_conf_dtmf (wmix_amd/csrc/conf.hip) through the Python mirror: the conference bridge listening to its legs' keypads.  Layout, K,
-the runner and the script generator are those of tests/test_conf_gpu.py and tests/test_conf_sequence_gpu.py.  Leg 6 -- one of the four
+"""wmx_conf_dtmf (wmix_amd/csrc/conf.hip) through the Python mirror: the conference bridge listening to its legs' keypads.  Layout, K
+and the script generator (key_script) are those of tests/conf_inputs.py, the runner that of tests/conf_harness.py.  Leg 6 -- one of the four
 of the last conference -- negotiated mu-law by payload type and is silent (code 0xFF is a sample of exactly 0) but for the key it
 presses; leg 3 sends its keys as RFC 4733 packets beside its audio.  What the other legs are sent is compared between handles: with
 suppression on, a script with the key is sent as the script without it; with DTMF off, or on without suppression, nothing that is sent
@@ -7,54 +7,11 @@ changes.  Which blocks are tones is tests/leg_dtmf_model.py's to say.  Bytes and
 import numpy as np
 import pytest
 
-from leg_dtmf_model import FROM_PACKET, block_digit, digits_of, tone
-from leg_plc_model import ulaw_decode
-from test_bridge_gpu import EINVAL
-from test_conf_gpu import G, bridge, run
-from test_conf_sequence_gpu import clean_script, rows_of
+from conf_harness import bridge, run
+from conf_inputs import EINVAL, EVENT_LEG, G, KEY_AT, KEY_LEG, key_script
+from leg_dtmf_model import FROM_PACKET, digits_of
 
 pytestmark = pytest.mark.gpu
-
-TICKS, KEY_LEG, EVENT_LEG, KEY_AT = 24, 6, 3, 10
-ZERO = np.full(160, 0xFF, np.uint8)  # mu-law: 160 samples of 0
-
-
-def ulaw_encode(x):
-    """int16 -> G.711 mu-law codes (sign, segment, mantissa of the biased magnitude, inverted)"""
-    out = np.zeros(len(x), np.uint8)
-    for i, v in enumerate(int(s) for s in x):
-        mag = min(abs(v), 32635) + 0x84
-        seg = mag.bit_length() - 8
-        out[i] = ~((0x80 if v < 0 else 0) | (seg << 4) | ((mag >> (seg + 3)) & 0xF)) & 0xFF
-    return out
-
-
-def key_codes(code, packets):
-    """the key as mu-law packets, every one of which the rule calls a tone of `code` once decoded"""
-    rows = [ulaw_encode(tone(code, 4000.0, 4500.0, n0=160 * i, ph_row=0.4, ph_col=1.9)) for i in range(packets)]
-    assert all(block_digit(ulaw_decode(r)) == code for r in rows)
-    return rows
-
-
-def key_script(code=5, packets=5, events=()):
-    """-> (datagram rows, recv) of TICKS ticks: quiet talkers, one packet per tick and leg; leg 6 sends zeros, and from tick KEY_AT on
-    `packets` packets of the key (0: none); events: (tick, event, timestamp, end) packets leg 3 sends behind its audio"""
-    script = clean_script(3, steady=True, quiet=True, ticks=TICKS)
-    keys = key_codes(code, packets)
-    for t in range(TICKS):
-        s, _, _ = script[t][KEY_LEG][0]
-        script[t][KEY_LEG] = [(s, 0, keys[t - KEY_AT] if KEY_AT <= t < KEY_AT + packets else ZERO)]
-    for t, event, ts, end in events:
-        s = script[t][EVENT_LEG][-1][0]
-        payload = np.zeros(160, np.uint8)
-        payload[:4] = [event, (0x80 if end else 0) | 10, 0, 160]
-        script[t][EVENT_LEG].append(((s + 100) % 65536, 101, payload))
-    pk, recv = rows_of(script, ticks=TICKS)
-    for t, event, ts, end in events:
-        k = [k for k in range(pk.shape[2]) if recv[t, EVENT_LEG, k] > 0 and (pk[t, EVENT_LEG, k, 1] & 0x7F) == 101]
-        assert len(k) == 1
-        pk[t, EVENT_LEG, k[0], 4:8] = [(ts >> 24) & 0xFF, (ts >> 16) & 0xFF, (ts >> 8) & 0xFF, ts & 0xFF]
-    return pk, recv
 
 
 def handle(seq=False, conceal=False, speakers=True):

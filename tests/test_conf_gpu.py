@@ -1,118 +1,19 @@
 """wmx_conf (wmix_amd/csrc/conf.hip) through the Python mirror: a conference bridge of RTP/G.711 legs in one handle, datagram in, datagram
-out.  Every datagram of every tick is compared with the replay of tests/test_host_tick_bridge_rtp_gpu.py -- the oracle's ingest, one
+out.  Every datagram of every tick is compared with the whole-script replay of tests/conf_single_replays.py -- the oracle's ingest, one
 reference ring per leg with a cursor per source leg (LegsOracle), the drain and the oracle's egress, fed by the same scripted arrivals --
-which is wrapped here so that the layout, the mute and the calls can change between ticks.  Bytes, np.array_equal."""
+and with replay_with() of the same module, which goes tick by tick so that the layout, the mute and the calls can change between
+ticks.  The shape and the script are those of tests/conf_inputs.py, the runner that of tests/conf_harness.py.  Bytes, np.array_equal."""
 import ctypes as C
-import time
 
 import numpy as np
 import pytest
 
-from oracle import loader as L
-from speakers_legs_model import SpeakersLegsModel
-from test_bridge_gpu import EINVAL, NULL_HEAD
-from test_bridge_legs_gpu import LegsOracle
-from test_host_tick_bridge_rtp_gpu import arrivals, replay
+from conf_harness import bridge, run
+from conf_inputs import EINVAL, G, K, LAYOUT, NULL_HEAD, SEED, T, arrivals
+from conf_single_replays import replay, replay_with
+from leg_oracle_model import Replay
 
 pytestmark = pytest.mark.gpu
-
-LAYOUT = [[0, 1], [2, 3, 4], [5, 6, 7, 8]]  # leg 9 is in no conference
-T, G, K, SEED = 40, 10, 3, 20260
-
-
-class Replay:
-    """replay() of tests/test_host_tick_bridge_rtp_gpu.py one tick at a time"""
-
-    def __init__(self, lib, n, platform="alsa"):
-        self.ing = L._fn(lib, "orc_rtp_ingest", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
-        self.eg = L._fn(lib, "orc_rtp_egress", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p])
-        self.init = L._fn(lib, "orc_rtp_sender_init", None, [C.c_void_p, C.c_int])
-        self.senders = [(C.c_uint8 * 16)() for _ in range(n)]
-        for s in self.senders:
-            self.init(s, 0)
-        self.orc, self.n = LegsOracle(lib, n, (1, 8000), 1, L.PLATFORMS[platform][1]), n
-
-    def decode(self, pk, recv, slots=K):
-        pcm, lens = np.zeros((self.n, slots, 161), np.int16), np.zeros((self.n, slots), np.uint32)
-        for g in range(self.n):
-            for k in range(slots):
-                if recv[g, k] > 0:
-                    row, dec = np.ascontiguousarray(pk[g, k]), np.zeros(160, np.int16)
-                    lens[g, k] = self.ing(row.ctypes.data, dec.ctypes.data, None)
-                    pcm[g, k, :160] = dec
-        return pcm, lens
-
-    def tick(self, pcm, lens, layout, mute=None):
-        self.orc.load(layout, pcm, lens, 320, 8000, 1, 160, mute)
-        play, out = self.orc.drain(), np.zeros((self.n, 172), np.uint8)
-        for g in range(self.n):
-            row = np.ascontiguousarray(play[g])
-            assert self.eg(self.senders[g], 1, 8000, row.ctypes.data, 320, 1, 8000, out[g].ctypes.data) == 172
-        return out
-
-    def fresh(self, legs):
-        """a new call in these legs' slots: the reference ring, the receive thread's cursor and the sender as a new task makes them"""
-        self.orc.reset(legs)
-        for g in legs:
-            self.orc.rings.store[g][:] = 0
-            self.init(self.senders[g], 0)
-
-
-def replay_with(lib, pk, recv, layout_at, mute_at=None, fresh_at=None, select=None):
-    """-> (datagrams [T, n, 172], per tick (speaking, env) when `select` = (max_speakers, floor, shift) is given)"""
-    n = recv.shape[1]
-    rp, model, out, sel = Replay(lib, n), SpeakersLegsModel(n), np.zeros((recv.shape[0], n, 172), np.uint8), []
-    for t in range(recv.shape[0]):
-        if fresh_at and t in fresh_at:
-            rp.fresh(fresh_at[t])
-            model.reset(fresh_at[t])
-        pcm, lens = rp.decode(pk[t], recv[t])
-        mute = mute_at(t) if mute_at else None
-        if select:
-            sp, mute = model.step_legs(layout_at(t), pcm, lens, 320, select[0], select[1], select[2], mute)
-            sel.append((sp.copy(), model.env.copy()))
-        out[t] = rp.tick(pcm, lens, layout_at(t), mute)
-    return out, sel
-
-
-def run(cb, pk, recv, mode, before=None, after=None):
-    """the handle over the script.  mode "wait": submit and wait, tick by tick; "ahead": the rows of tick t + 1 are written and submitted
-    before tick t is waited for; "poll": as "ahead", but a tick is collected by asking cb.poll(slot) until it says yes (5 s at the most),
-    never by waiting; "resident": wmx_conf_step_resident on rows that are on the device.  before[t](cb) runs in front of tick t's submit,
-    after(t, cb) behind it."""
-    import torch
-    n_t, n = recv.shape[:2]
-    out, queued = np.zeros((n_t, n, 172), np.uint8), []
-
-    def collect(depth):
-        while len(queued) > depth:
-            t0, k0 = queued.pop(0)
-            if mode == "poll":
-                deadline = time.monotonic() + 5.0
-                while not cb.poll(k0):
-                    assert time.monotonic() < deadline, "tick %d has not landed in 5 s" % t0
-            else:
-                cb.wait(k0)
-            out[t0] = cb.rows_out[k0]
-
-    for t in range(n_t):
-        if before and t in before:
-            before[t](cb)
-        if mode == "resident":
-            rows = np.zeros((n, recv.shape[2], cb.in_row), np.uint8)
-            rows[:, :, :172] = pk[t]
-            out[t] = cb.step_resident(torch.from_numpy(rows).cuda(), torch.from_numpy(recv[t]).cuda()).cpu().numpy()
-        else:
-            k = cb.next_slot()
-            cb.rows_in[k][:, :, :172] = pk[t]
-            cb.recv[k][:] = recv[t]
-            assert cb.submit() == k
-            queued.append((t, k))
-            collect(1 if mode in ("ahead", "poll") else 0)
-        if after:
-            after(t, cb)
-    collect(0)
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -120,14 +21,6 @@ def script(oracle_port):
     pk, recv = arrivals(SEED, T, G)
     want, calls = replay(oracle_port, pk, recv, LAYOUT, "alsa")
     return pk, recv, want
-
-
-def bridge(n=G, slots=3, layout=LAYOUT, max_packets=K):
-    from wmix_amd.conf import ConfBridge
-    cb = ConfBridge(n, slots, max_packets)
-    if layout is not None:
-        cb.set_conferences(layout)
-    return cb
 
 
 @pytest.mark.parametrize("slots,mode", [(1, "wait"), (3, "ahead"), (3, "resident"), (2, "poll")])

@@ -1,34 +1,19 @@
 """tests/conf_replay_model.py anchored without a GPU.  First the composed replay reproduces, byte for byte, each single-purpose replay
-the suite already has, on that replay's own script with the matching switches.  Then the stories tests/test_conf_all_stages_gpu.py
-runs on the handle are held, on the model alone, against what they are for: a failing assertion there means the script is wrong, not
-the library.  The stories live here: a story is (rows, recv, setup, before) -- setup(target) in front of the first tick, before[t](target)
-in front of tick t -- and calls only the setters wmix_amd/conf.py and ConfReplay share."""
+of tests/conf_single_replays.py, on that replay's own script with the matching switches.  Then the stories of tests/conf_stories.py
+that tests/test_conf_all_stages_gpu.py runs on the handle are held, on the model alone, against what they are for: a failing assertion
+there means the script is wrong, not the library."""
 import numpy as np
 import pytest
 
-from conf_replay_model import ConfReplay, replay_story
+from conf_inputs import (CHANGE_AT, G, IN_CONF, K, LATER_ULAW_LEG, LAYOUT, RESET_AT, RESET_LEG, SEED, STRICT_A_LEG, T, arrivals, clean_script, impair,
+                         rows_of)
+from conf_replay_model import replay_story
+from conf_single_replays import codec_story, replay_conceal, replay_seq, replay_sequenced, replay_with
+from conf_stories import (C17, JOINED, LAYOUT_D, MUTED_D, N_D, RANDOM_SEEDS, RESET8_AT, SETTERS, TICKS_C, WITHOUT3, all_stages, all_stages_floor,
+                          all_stages_script, floor_of, random_schedule, sizes_script, sizes_story, slots_script, slots_story, start, switching,
+                          switching_script)
 from leg_codec_model import BY_PT, LAW_A, LAW_U, PCMA, PCMU, REFERENCE
 from leg_seq_model import COUNTERS
-from test_conf_codecs_gpu import BY_PT_LEG, STRICT_A_LEG, ULAW_LEGS, replay_sequenced, start
-from test_conf_codecs_gpu import story  # noqa: F401  (the fixture)
-from test_conf_conceal_gpu import replay_conceal
-from test_conf_gpu import G, K, LAYOUT, SEED, T, replay_with
-from test_conf_sequence_gpu import IN_CONF, clean_script, impair, replay_seq, rows_of
-from test_host_tick_bridge_rtp_gpu import arrivals
-
-WITHOUT3, JOINED = [[0, 1], [2, 4], [5, 6, 7, 8]], [[0, 1, 3], [2, 4], [5, 6, 7, 8]]
-
-
-def floor_of(lib, pk, recv, setup=None, percentile=40):
-    """the level below which `percentile` in a hundred of the script's decoded packets lie"""
-    m = ConfReplay(lib, recv.shape[1], recv.shape[2])
-    if setup:
-        setup(m)
-    levels = []
-    for t in range(recv.shape[0]):
-        pcm, lens = m.rp.decode(pk[t], recv[t], m.K)
-        levels += [int(np.abs(pcm[g, k].astype(np.int64)).sum()) for g, k in np.argwhere(lens == 320)]
-    return int(np.percentile(levels, percentile))
 
 
 def same(got, want):
@@ -152,8 +137,12 @@ def test_concealment_behind_a_reset_is_replay_conceal_with_fresh_at(oracle_port)
     assert np.array_equal(m.export_conceal(), plc.export()["concealed"]) and m.export_conceal()[3] == 1
 
 
-def test_codecs_are_the_story_of_the_codec_tests(oracle_port, story):  # noqa: F811
-    from test_conf_codecs_gpu import CHANGE_AT, LATER_ULAW_LEG, RESET_AT, RESET_LEG
+@pytest.fixture(scope="module")
+def story(oracle_port):
+    return codec_story(oracle_port)
+
+
+def test_codecs_are_the_story_of_the_codec_tests(oracle_port, story):
     pk, recv, want, rp, _ = story
 
     def setup(c):
@@ -167,7 +156,7 @@ def test_codecs_are_the_story_of_the_codec_tests(oracle_port, story):  # noqa: F
     assert np.array_equal(st["refused"], rp.refused) and st["in_codec"].tolist() == rp.in_codec and st["out_law"].tolist() == rp.out_law
 
 
-def test_codecs_sequenced_and_selected_are_the_codec_tests_replay(oracle_port, story):  # noqa: F811
+def test_codecs_sequenced_and_selected_are_the_codec_tests_replay(oracle_port, story):
     pk, recv = story[:2]
 
     def setup(c):
@@ -229,89 +218,6 @@ class Reach:
             self.n["ulaw"] += gaps if m.rp.in_codec[g] == PCMU else 0
 
 
-def retyped(packets, ulaw_from=None):
-    """the payload types of a script rewritten per leg, by the rule of rewritten_script() in tests/test_conf_codecs_gpu.py: 0 on the
-    mu-law legs (and on the legs of ulaw_from = {leg: tick} from that tick), alternating 8 / 0 per packet on the BY_PT leg, 8 with
-    every fifth packet 0 on the strict A-law leg; the default legs keep their 8s and 0s"""
-    nth, out = {}, []
-    for t, tick in enumerate(packets):
-        out.append([])
-        for g, now in enumerate(tick):
-            new = []
-            for s, pt, codes in now:
-                n = nth.get(g, 0)
-                if g in ULAW_LEGS or (ulaw_from and g in ulaw_from and t >= ulaw_from[g]):
-                    pt = 0
-                elif g == BY_PT_LEG:
-                    pt = 8 if n % 2 == 0 else 0
-                elif g == STRICT_A_LEG:
-                    pt = 0 if n % 5 == 4 else 8
-                nth[g] = n + 1
-                new.append((s, pt, codes))
-            out[-1].append(new)
-    return out
-
-
-def gap_behind(script, g, t):
-    """leg g delivers one packet in tick t and in tick t + 1 what it delivered anyway, which starts two numbers on: a gap of one in the
-    tick behind a reset_legs at t (where it delivered nothing in tick t + 1: the packet in front of its next one)"""
-    if not script[t + 1][g]:
-        s, pt, codes = next(now[g][0] for now in script[t + 2:] if now[g])
-        script[t + 1][g] = [((s - 1) % 65536, pt, codes[::-1].copy())]
-    s, pt, codes = script[t + 1][g][0]
-    script[t][g] = [((s - 2) % 65536, pt, codes[::-1].copy())]
-
-
-# ---- 3a: everything on
-MUTES_A = {6: [6, 2], 21: [5, 0], 33: None}
-CODEC_AT, RESET8_AT = 25, 30
-
-
-def all_stages_script():
-    script, _ = impair(retyped(clean_script(2), {2: CODEC_AT}), 3)
-    gap_behind(script, 3, 15)
-    gap_behind(script, 8, RESET8_AT)
-    return rows_of(script)
-
-
-def mask_of(legs, n=G):
-    if legs is None:
-        return None
-    mask = np.zeros(n, np.uint8)
-    mask[legs] = 1
-    return mask
-
-
-def all_stages(floor, without=None):
-    """-> (setup, before) of the story with everything on: mu-law legs, a BY_PT leg and a strict PCMA leg; sequence, conceal, speakers;
-    the host's mute changes three times; leg 3 leaves at tick 15 (and is reset) and joins legs 0 and 1 at tick 20; leg 2 goes to
-    mu-law at tick 25; leg 8 is a new call from tick 30 on.  without: one of "speakers", "conceal", "codecs", "mute" left out."""
-    def setup(c):
-        c.set_conferences(LAYOUT)
-        if without != "codecs":
-            start(c)
-        c.sequence(True, 3)
-        if without != "conceal":
-            c.conceal(True)
-        if without != "speakers":
-            c.speakers(2, floor, 3)
-
-    def leave(c):
-        c.set_conferences(WITHOUT3)
-        c.reset_legs([3])
-
-    before = {15: leave, 20: lambda c: c.set_conferences(JOINED), RESET8_AT: lambda c: c.reset_legs([8])}
-    if without != "codecs":
-        before[CODEC_AT] = lambda c: c.set_codecs([2], PCMU, LAW_U)
-    if without != "mute":
-        before.update({t: (lambda c, legs=legs: c.mute(mask_of(legs))) for t, legs in MUTES_A.items()})
-    return setup, before
-
-
-def all_stages_floor(lib, pk, recv):
-    return floor_of(lib, pk, recv, start)
-
-
 def test_the_all_stages_story_reaches_what_it_is_for(oracle_port):
     pk, recv = all_stages_script()
     floor = all_stages_floor(oracle_port, pk, recv)
@@ -348,77 +254,6 @@ def test_the_all_stages_story_reaches_what_it_is_for(oracle_port):
 
 
 # ---- 3b: switches changed on a running handle
-def switching_script():
-    return rows_of(impair(retyped(clean_script(11)), 12)[0])
-
-
-def switching(floor):
-    """the written-out story: sequence off -> sequence on -> conceal on -> speakers on -> conceal off -> conceal on -> sequence off
-    (concealment stays "on" and is not launched) -> sequence on -> speakers off; beside it every other setter twice, with a change"""
-    def setup(c):
-        c.set_conferences(LAYOUT)
-
-    def at(*calls):
-        return lambda c: [getattr(c, name)(*args) for name, args in calls]
-
-    before = {
-        3: at(("set_codecs", (ULAW_LEGS, PCMU, LAW_U))),
-        5: at(("sequence", (True, 3))),
-        7: at(("mute", (mask_of([7]),))),
-        10: at(("conceal", (True,))),
-        12: at(("set_codecs", ([BY_PT_LEG], BY_PT, LAW_A)), ("set_codecs", ([STRICT_A_LEG], PCMA, LAW_A))),
-        15: at(("speakers", (2, floor, 3))),
-        17: at(("set_conferences", (WITHOUT3,)), ("reset_legs", ([3],))),
-        20: at(("conceal", (False,))),
-        22: at(("set_conferences", (JOINED,)), ("mute", (mask_of([0, 6]),))),
-        25: at(("conceal", (True,))),
-        27: at(("reset_legs", ([5],)), ("speakers", (1, floor // 2, 2))),
-        29: at(("sequence", (False, 3))),
-        31: at(("mute", (None,))),
-        33: at(("sequence", (True, 2))),
-        37: at(("speakers", (0, 0, 3))),
-    }
-    return setup, before
-
-
-SETTERS = ("mute", "speakers", "sequence", "conceal", "set_codecs", "reset_legs", "set_conferences")
-
-
-def random_schedule(seed, floor, ticks=T, n=G):
-    """per tick at most one setter call drawn from SETTERS -> (setup, before, the calls as (tick, name, args))"""
-    rng = np.random.default_rng(seed)
-    calls = []
-    for t in range(1, ticks):
-        name = (SETTERS + ("nothing",) * 3)[int(rng.integers(0, len(SETTERS) + 3))]
-        if name == "mute":
-            args = (None if rng.integers(0, 4) == 0 else (rng.integers(0, 4, size=n) == 0).astype(np.uint8),)
-        elif name == "speakers":
-            args = [(0, 0, 3), (2, floor, 3), (1, floor // 2, 2), (3, 0, 4)][int(rng.integers(0, 4))]
-        elif name == "sequence":
-            args = (bool(rng.integers(0, 3)), int(rng.integers(0, 4)))
-        elif name == "conceal":
-            args = (bool(rng.integers(0, 3)),)
-        elif name == "set_codecs":
-            args = ([int(rng.integers(0, n))], int(rng.integers(0, 4)), int(rng.integers(0, 2)))
-        elif name == "reset_legs":
-            args = ([int(rng.integers(0, n))],)
-        elif name == "set_conferences":
-            args = ([LAYOUT, JOINED][int(rng.integers(0, 2))],)
-        else:
-            continue
-        calls.append((t, name, args))
-
-    def setup(c):
-        c.set_conferences(LAYOUT)
-        c.sequence(True, 3)
-        c.conceal(True)
-
-    return setup, {t: (lambda c, name=name, args=args: getattr(c, name)(*args)) for t, name, args in calls}, calls
-
-
-RANDOM_SEEDS = (101, 102, 103)
-
-
 class Recorder:
     """stands where the handle stands and writes down what a story calls"""
 
@@ -465,52 +300,6 @@ def test_a_random_schedule_is_runnable_and_switches(oracle_port, seed):
 
 
 # ---- 3c: other slot counts
-TICKS_C = 16
-
-
-def lose(script, seed, legs, runs):
-    """losses only: `runs` times a leg of `legs` loses 1 .. 3 packets in a row (the numbers are consumed, nothing arrives)"""
-    rng = np.random.default_rng(seed)
-    ticks = len(script)
-    for _ in range(runs):
-        g, t, n = int(rng.choice(legs)), int(rng.integers(2, ticks - 4)), int(rng.integers(1, 4))
-        for u in range(t, t + n):
-            script[u][g] = []
-    return script
-
-
-def slots_script(slots):
-    """K = 1: a steady script with runs of 1 .. 3 lost packets, so the lists are S D, S S D and S S S D on the only slot.  K = 2: the
-    impaired script at two slots.  K = 4: the same at four, and leg 5 loses three packets and delivers the next four in one tick --
-    S S S D fills the list and three packets overflow; behind them the next tick finds a gap of three again."""
-    if slots == 1:
-        script = lose(clean_script(21, steady=True, ticks=TICKS_C), 22, IN_CONF, 12)
-        for t, n in ((4, 3), (9, 2)):  # and for certain: three in a row, two in a row
-            for u in range(t, t + n):
-                script[u][6] = []
-    else:
-        script, _ = impair(clean_script(23 + slots, ticks=TICKS_C), 24, ticks=TICKS_C, slots=slots, restarts=((1, 6),))
-    if slots == 4:
-        steady = clean_script(29, steady=True, ticks=TICKS_C)
-        for t in range(TICKS_C):
-            script[t][5] = steady[t][5]
-        script[11][5] = [steady[t][5][0] for t in (11, 12, 13, 14)]
-        for t in (8, 9, 10, 12, 13, 14):
-            script[t][5] = []
-    return rows_of(script, ticks=TICKS_C, slots=slots)
-
-
-def slots_story(floor):
-    def setup(c):
-        c.set_conferences(LAYOUT)
-        c.set_codecs(ULAW_LEGS, PCMU, LAW_U)
-        c.sequence(True, 3)
-        c.conceal(True)
-        c.speakers(2, floor, 3)
-
-    return setup, {5: lambda c: c.mute(mask_of([6]))}
-
-
 @pytest.mark.parametrize("slots", [1, 2, 4])
 def test_the_slot_count_stories_reach_what_they_are_for(oracle_port, slots):
     pk, recv = slots_script(slots)
@@ -536,39 +325,6 @@ def test_the_slot_count_stories_reach_what_they_are_for(oracle_port, slots):
 
 
 # ---- 3d: every size class and a ragged last block
-N_D, TICKS_D = 35, 12
-C17 = [34, 32, 30, 28, 26, 24, 22, 20, 18, 33, 31, 29, 27, 25, 23, 21, 19]
-LAYOUT_D = [[1, 0], C17, [2], [7, 5, 3, 6, 4], [16, 15, 14, 13, 12, 11, 10, 9, 8]]  # sizes 2, 17, 1, 5, 9; leg 17 is in no conference
-MUTED_D = [21, 12]
-
-
-def sizes_script():
-    """steady, quiet, with losses; now and then a leg is loud for a tick, so that the number of eligible talkers moves"""
-    rng = np.random.default_rng(31)
-    script = clean_script(32, steady=True, quiet=True, legs=N_D, ticks=TICKS_D)
-    for t in range(TICKS_D):
-        for g in range(N_D):
-            if rng.integers(0, 10) == 0:
-                s, pt, _ = script[t][g][0]
-                script[t][g] = [(s, pt, rng.integers(0, 256, size=160).astype(np.uint8))]
-    script = lose(script, 33, [g for c in LAYOUT_D if len(c) >= 2 for g in c], 24)
-    return rows_of(script, legs=N_D, ticks=TICKS_D)
-
-
-FLOOR_D = 700000  # a quiet packet is below 10 000, a loud one 600 000 .. 1 270 000: a talker stays above it for a tick or two
-
-
-def sizes_story():
-    def setup(c):
-        c.set_conferences(LAYOUT_D)
-        c.sequence(True, 3)
-        c.conceal(True)
-        c.speakers(3, FLOOR_D, 3)
-        c.mute(mask_of(MUTED_D, N_D))
-
-    return setup, None
-
-
 def test_the_sizes_story_reaches_what_it_is_for(oracle_port):
     pk, recv = sizes_script()
     assert sorted(len(c) for c in LAYOUT_D) == [1, 2, 5, 9, 17] and sorted([g for c in LAYOUT_D for g in c] + [17]) == list(range(N_D)) and N_D % 4

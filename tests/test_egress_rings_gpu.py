@@ -4,7 +4,7 @@ seq and timestamp, byte for byte."""
 import numpy as np
 import pytest
 
-from test_bridge_gpu import EINVAL
+from conf_inputs import EINVAL
 
 pytestmark = pytest.mark.gpu
 

@@ -1,6 +1,6 @@
 """examples/host_conf.c --ulaw-every N: the conference bridge from plain C with every N-th leg on PCMU, both ways, run once at a small
-size.  The datagrams it sends are those of the replay with a codec per leg (tests/test_conf_codecs_gpu.py) for the same scripted
-arrivals, and its refused count is the replay's.  Bytes, np.array_equal."""
+size.  The datagrams it sends are those of the replay with a codec per leg (CodecReplay, tests/leg_oracle_model.py) for the same
+scripted arrivals (ulaw_every_script, tests/conf_inputs.py), and its refused count is the replay's.  Bytes, np.array_equal."""
 import os
 import subprocess
 
@@ -8,30 +8,18 @@ import numpy as np
 import pytest
 
 import conftest
+from conf_harness import host_conf
+from conf_inputs import EVERY, G, K, LAYOUT, SEED, T, ULAW, arrivals, fnv1a, ulaw_every_script
+from conf_single_replays import replay
 from leg_codec_model import LAW_U, PCMU
-from test_conf_codecs_gpu import CodecReplay
-from test_conf_gpu import K
-from test_host_conf_gpu import G, LAYOUT, SEED, T, host_conf
-from test_host_tick_bridge_rtp_gpu import arrivals, fnv1a, replay
+from leg_oracle_model import CodecReplay
 
 pytestmark = pytest.mark.gpu
-
-EVERY = 3
-ULAW = [g for g in range(G) if g % EVERY == EVERY - 1]
-
-
-def script():
-    """the example's script: arrivals() with every G.711 datagram of a mu-law leg carrying payload type 0"""
-    pk, recv = arrivals(SEED, T, G)
-    for g in ULAW:
-        audio = (recv[:, g] > 0) & np.isin(pk[:, g, :, 1] & 0x7F, (8, 0))
-        pk[:, g, :, 1] = np.where(audio, 0x80, pk[:, g, :, 1])
-    return pk, recv
 
 
 def test_host_conf_with_ulaw_legs_sends_what_the_replay_sends(tmp_path, oracle_port):
     info, got = host_conf(tmp_path, "--slots", "3", "--ulaw-every", str(EVERY))
-    pk, recv = script()
+    pk, recv = ulaw_every_script()
     rp, want = CodecReplay(oracle_port, G), np.zeros((T, G, 172), np.uint8)
     rp.set_codecs(ULAW, PCMU, LAW_U)
     for t in range(T):

@@ -5,9 +5,8 @@ the same script; on an in-order script in which every datagram is audio the flag
 import numpy as np
 import pytest
 
-from test_conf_gpu import K, run
-from test_host_conf_gpu import G, LAYOUT, SEED, T, host_conf
-from test_host_tick_bridge_rtp_gpu import arrivals, fnv1a
+from conf_harness import host_conf, run
+from conf_inputs import G, K, LAYOUT, SEED, T, arrivals, fnv1a
 
 pytestmark = pytest.mark.gpu
 

@@ -4,7 +4,7 @@ C ABI, and the legs of the other conferences are sent what they are sent without
 import numpy as np
 import pytest
 
-from test_host_conf_gpu import host_conf
+from conf_harness import host_conf
 
 pytestmark = pytest.mark.gpu
 

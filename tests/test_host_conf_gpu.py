@@ -1,7 +1,6 @@
 """examples/host_conf.c: a conference bridge of RTP/G.711 legs from plain C over wmx_conf_* alone, run once at a small size.  The datagrams
-it sends are the replay's (tests/test_host_tick_bridge_rtp_gpu.py) for the same scripted arrivals; with talker selection they are what
-the Python handle sends for the same script.  Bytes, np.array_equal."""
-import json
+it sends are those of the whole-script replay (tests/conf_single_replays.py) for the same scripted arrivals (tests/conf_inputs.py); with
+talker selection they are what the Python handle sends for the same script (run() of tests/conf_harness.py).  Bytes, np.array_equal."""
 import os
 import subprocess
 
@@ -9,22 +8,11 @@ import numpy as np
 import pytest
 
 import conftest
-from test_conf_gpu import K, run
-from test_host_tick_bridge_rtp_gpu import arrivals, fnv1a, replay
+from conf_harness import host_conf, run
+from conf_inputs import G, K, LAYOUT, SEED, T, arrivals, fnv1a
+from conf_single_replays import replay
 
 pytestmark = pytest.mark.gpu
-
-T, G, SEED = 40, 10, 20260
-LAYOUT = [[0, 1], [2, 3, 4], [5, 6, 7, 8]]
-
-
-def host_conf(tmp_path, *extra):
-    exe = os.path.join(conftest.ROOT, "examples", "host_conf")
-    assert os.path.exists(exe), "examples/host_conf missing: run __graft_entry__.build()"
-    out = tmp_path / "out.rtp"
-    r = subprocess.run([exe, str(out), str(G), str(T), "--sizes", "2,3,4", "--seed", str(SEED)] + list(extra), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    return json.loads(r.stdout.strip().splitlines()[-1]), np.fromfile(out, dtype=np.uint8).reshape(T, G, 172)
 
 
 def test_host_conf_sends_what_the_replay_sends(tmp_path, oracle_port):

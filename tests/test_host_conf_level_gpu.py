@@ -5,10 +5,8 @@ held against the replay in tests/test_conf_level_gpu.py.  Bytes, np.array_equal.
 import numpy as np
 import pytest
 
-from test_conf_gpu import K, run
-from test_host_conf_denoise_gpu import dtmf_script
-from test_host_conf_gpu import G, LAYOUT, SEED, T, host_conf
-from test_host_tick_bridge_rtp_gpu import arrivals, fnv1a
+from conf_harness import host_conf, run
+from conf_inputs import G, K, LAYOUT, SEED, T, arrivals, dtmf_script, fnv1a
 
 pytestmark = pytest.mark.gpu
 

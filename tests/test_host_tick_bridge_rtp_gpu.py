@@ -1,8 +1,7 @@
 """examples/host_tick.c --bridge-rtp: a conference bridge of RTP/G.711 legs from plain C -- wmx_rtp_ingest_legs, wmx_mix_load_minus_legs
-on the tick's mixer, wmx_tick_play, wmx_rtp_egress per 20 ms -- run once at a small size.  The datagrams it sends are compared with a
-Python replay built from the oracle's ingest, one reference ring per leg with a cursor per source leg, the drain and the oracle's
-egress, fed by the same scripted arrivals.  Bytes, np.array_equal."""
-import ctypes as C
+on the tick's mixer, wmx_tick_play, wmx_rtp_egress per 20 ms -- run once at a small size.  The datagrams it sends are compared with the
+whole-script replay of tests/conf_single_replays.py -- the oracle's ingest, one reference ring per leg with a cursor per source leg, the
+drain and the oracle's egress -- fed by the same scripted arrivals (arrivals() of tests/conf_inputs.py).  Bytes, np.array_equal."""
 import json
 import os
 import subprocess
@@ -11,78 +10,10 @@ import numpy as np
 import pytest
 
 import conftest
-from oracle import loader as L
-from test_bridge_legs_gpu import LegsOracle
+from conf_inputs import arrivals, fnv1a
+from conf_single_replays import replay
 
 pytestmark = pytest.mark.gpu
-
-MASK = (1 << 64) - 1
-
-
-class Lcg:
-    def __init__(self, seed):
-        self.s = seed
-
-    def next(self):
-        self.s = (self.s * 6364136223846793005 + 1442695040888963407) & MASK
-        return self.s >> 33
-
-
-def arrivals(seed, T, G):
-    """the example's script (examples/host_tick.c, bridge_rtp): datagram rows [T, G, 3, 172] and what recvfrom returned [T, G, 3]"""
-    rnd = Lcg(seed)
-    pk = np.full((T, G, 3, 172), 0xEE, np.uint8)
-    recv = np.zeros((T, G, 3), np.int32)
-    seq = [0] * G
-    for t in range(T):
-        for g in range(G):
-            u = rnd.next() % 8
-            recv[t, g] = [172 if u >= 2 else 0, 172 if u == 2 else (-1 if u == 3 else 0), 172 if u == 3 else 0]
-            for k in range(3):
-                if recv[t, g, k] <= 0:
-                    continue
-                v = rnd.next() % 16
-                pk[t, g, k, :12] = 0
-                pk[t, g, k, 0] = 0x80
-                pk[t, g, k, 1] = 0x80 | (96 if v == 0 else (0 if v == 1 else 8))
-                pk[t, g, k, 2], pk[t, g, k, 3] = (seq[g] >> 8) & 255, seq[g] & 255
-                seq[g] = (seq[g] + 1) & 0xFFFF
-                pk[t, g, k, 12:] = [rnd.next() & 255 for _ in range(160)]
-    return pk, recv
-
-
-def replay(lib, pk, recv, layout, platform):
-    T, G = recv.shape[:2]
-    ing = L._fn(lib, "orc_rtp_ingest", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
-    eg = L._fn(lib, "orc_rtp_egress", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p])
-    senders = [(C.c_uint8 * 16)() for _ in range(G)]
-    for s in senders:
-        L._fn(lib, "orc_rtp_sender_init", None, [C.c_void_p, C.c_int])(s, 0)
-    orc = LegsOracle(lib, G, (1, 8000), 1, L.PLATFORMS[platform][1])
-    out = np.zeros((T, G, 172), np.uint8)
-    calls = 0
-    for t in range(T):
-        pcm, lens = np.zeros((G, 3, 161), np.int16), np.zeros((G, 3), np.uint32)
-        for g in range(G):
-            for k in range(3):
-                if recv[t, g, k] > 0:
-                    row, dec = np.ascontiguousarray(pk[t, g, k]), np.zeros(160, np.int16)
-                    lens[g, k] = ing(row.ctypes.data, dec.ctypes.data, None)
-                    pcm[g, k, :160] = dec
-        calls += int((lens == 320).sum())
-        orc.load(layout, pcm, lens, 320, 8000, 1, 160, None)
-        play = orc.drain()
-        for g in range(G):
-            row = np.ascontiguousarray(play[g])
-            assert eg(senders[g], 1, 8000, row.ctypes.data, 320, 1, 8000, out[t, g].ctypes.data) == 172
-    return out, calls
-
-
-def fnv1a(data):
-    h = 1469598103934665603
-    for b in data.tobytes():
-        h = ((h ^ b) * 1099511628211) & MASK
-    return "%016x" % h
 
 
 def test_host_tick_bridge_rtp_sends_what_the_replay_sends(tmp_path, oracle_port):

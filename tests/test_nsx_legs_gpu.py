@@ -8,9 +8,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL
 from leg_denoise_model import ROW, rows_taken, suppress
 from leg_seq_model import pack
-from test_bridge_gpu import EINVAL
 
 pytestmark = pytest.mark.gpu
 

@@ -118,14 +118,13 @@ def _child_rt():
 
 
 def _child_conf():
-    """the conference handle (wmx_conf_submit / _wait / _poll over three slots, the script of tests/test_conf_gpu.py) under the same faults:
+    """the conference handle (wmx_conf_submit / _wait / _poll over three slots, the script of tests/conf_inputs.py) under the same faults:
     a failing wait or poll changes nothing; a submit that fails before its first launch has taken no slot and moved no rotation, so the
     same rows submitted again and the two ticks behind them are those of an undisturbed handle.  The cursors and the senders have no
     import call: the walk ends at the first tick that is lost (the rule of the "rtp" kind)."""
     from wmix_amd import _lib
     from wmix_amd.conf import ConfBridge
-    from test_conf_gpu import G, K, LAYOUT, SEED, T
-    from test_host_tick_bridge_rtp_gpu import arrivals
+    from conf_inputs import G, K, LAYOUT, SEED, T, arrivals
     L = _lib.lib()
     assert "WMX_FAULT_INJECTION" in _lib.build_info()
     L.wmx_debug_fail_nth_hip_call.argtypes = [C.c_long]

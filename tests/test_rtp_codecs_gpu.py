@@ -7,9 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL
 from leg_codec_model import BY_PT, LAW_A, LAW_U, PCMA, PCMU, REFERENCE, Decoders, ingest, slot
 from oracle import loader as L
-from test_bridge_gpu import EINVAL
 
 pytestmark = pytest.mark.gpu
 

@@ -6,8 +6,8 @@ Integers, np.array_equal."""
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL
 from leg_plc_model import LegsPlcModel, gen_case, pack, run_lengths
-from test_bridge_gpu import EINVAL
 
 pytestmark = pytest.mark.gpu
 

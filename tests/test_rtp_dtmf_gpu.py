@@ -8,9 +8,9 @@ event packets in the slots left over.  count, ring and the PCM rows are compared
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL
 from leg_dtmf_model import FROM_PACKET, ROW, LegsDtmfModel, event_row, noise, tone
 from leg_plc_model import D, S, pack
-from test_bridge_gpu import EINVAL
 
 pytestmark = pytest.mark.gpu
 

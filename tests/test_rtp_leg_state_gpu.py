@@ -7,7 +7,7 @@ np.array_equal."""
 import numpy as np
 import pytest
 
-from test_bridge_gpu import EINVAL
+from conf_inputs import EINVAL
 
 pytestmark = pytest.mark.gpu
 

@@ -7,8 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL
 from leg_seq_model import COUNTERS, LegsSeqModel
-from test_bridge_gpu import EINVAL
 
 pytestmark = pytest.mark.gpu
 

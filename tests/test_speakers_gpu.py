@@ -10,9 +10,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL, NULL_HEAD
 import conftest
+from leg_oracle_model import OracleRings
 from speakers_model import SpeakersModel, row_of_level, uniform_layout
-from test_bridge_gpu import EINVAL, NULL_HEAD, N, OracleRings, oracle_minus, room, talkers
+from test_bridge_gpu import N, oracle_minus, room, talkers
 from test_bridge_ragged_gpu import oracle_minus_conf
 
 pytestmark = pytest.mark.gpu

@@ -6,8 +6,8 @@ that hold them (the four sizes alone are 42)."""
 import numpy as np
 import pytest
 
+from conf_inputs import EINVAL
 from speakers_legs_model import SpeakersLegsModel
-from test_bridge_gpu import EINVAL
 
 pytestmark = pytest.mark.gpu
 
