@@ -1135,6 +1135,14 @@ int wmx_debug_ns_window(int L, float *host_window);
  * (device pointers) and compiled for the host. */
 int wmx_debug_div(const float *d_a, const float *d_b, float *d_q_ordinary, float *d_q_ieee, size_t n, void *stream);
 int wmx_debug_div_host(const float *a, const float *b, float *q, size_t n);
+/* Developer / test hook: the gate of the float AEC's near kernel that settles the two decisions taken from sdSum and seSum
+ * (divergeState, filter reset) from lane-parallel sums where the order of the additions cannot matter (wmix_amd/csrc/aec_gate.h).
+ * sd_rows, se_rows: [n][65] floats, prev_state: [n] divergeState in front of the block, out: [n][4] int32.  On the host:
+ * {decided, diverge, reset, 0} (diverge and reset mean nothing where decided is 0); on the device (device pointers; synchronises
+ * `stream`), one wave per row with the kernel's reduction and, for an undecided row, its ordered sums: {1 = settled by the gate /
+ * 0 = by the ordered sums, diverge, reset, 0}, final for every row. */
+int wmx_debug_aec_decide(const float *sd_rows, const float *se_rows, const int32_t *prev_state, int32_t *out, size_t n);
+int wmx_debug_aec_decide_device(const float *d_sd_rows, const float *d_se_rows, const int32_t *d_prev_state, int32_t *d_out, size_t n, void *stream);
 /* Same for the AEC kernel's table-driven powf: y[i] = x[i] ^ e[i]. */
 int wmx_debug_pow(const float *x, const float *e, float *y, size_t n);
 /* ... and evaluated on the device (device pointers; synchronises `stream`) */

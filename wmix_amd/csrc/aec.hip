@@ -27,7 +27,8 @@
 //                    A wave spends more of its life waiting for data than issuing (DESIGN_HISTORY.md section 5), so every
 //                    global request of a phase goes out in one batch, a phase early where registers allow, and
 //                    wave-uniform far-end data takes the scalar path.
-// Float expressions, their order and the ordered sums follow the reference exactly (-ffp-contract=off); powf is glibc's
+// Float expressions, their order and the ordered sums follow the reference exactly (-ffp-contract=off; sdSum and seSum, which feed
+// two comparisons only, are added in order where the order could decide one of them and not otherwise: aec_gate.h); powf is glibc's
 // own algorithm restated in libm_dev.h (bit for bit the host's), the rare log the library routine; cosf/sinf of the comfort
 // noise come from the host's libm through the plan.
 #include <algorithm>
@@ -40,6 +41,7 @@
 #include <vector>
 #include "wmx_internal.h"
 #include "aec_ctl.h"
+#include "aec_gate.h"
 #include "cohort_hip.h"
 #include "fft_regs.h"
 #include "libm_dev.h"
@@ -131,6 +133,11 @@ constexpr int kAecConstNearWords = sizeof(AecConstsNear) / 4;
 // it makes it 0, on x86 as on gfx950).  NaNs do reach this in the reference's own runs (the AEC's first blocks), so the one-instruction
 // median v_med3_f32(v, -32768, 32767), which answers a NaN with -32768, is not a substitute -- tried, aec_golden caught it.
 __device__ __forceinline__ float sat16f(float v) { return v > 32767.f ? 32767.f : (v < -32768.f ? -32768.f : v); }
+
+// conj(w) * t = (wr*t.x + wi*t.y, wr*t.y - wi*t.x): cmul_w (fft_ooura.h) with wi negated, the negation folded into the second
+// product's operand (a sign bit of the packed multiply) instead of an instruction of its own -- negating a product is exact, the
+// floats are those of `wi = -wi; cmul_w(wr, wi, t)`
+__device__ __forceinline__ v2f cmul_conj_w(float wr, float wi, v2f t) { return v2f{wr, wr} * t + v2f{wi, -wi} * swap(t); }
 
 // spectrum of a packed rdft array: bin b of a[] (StoreAsComplex / TimeToFrequency layout rules)
 __device__ __forceinline__ void unpack_bin(const float *a, int b, float &re, float &im) {
@@ -419,6 +426,10 @@ __device__ unsigned long long g_aec_prof[16];
 #define AEC_PROF(i)
 #define AEC_PROF_START
 #endif
+#ifdef WMX_AEC_GATE_PROF  // developer build only (make EXTRA=-DWMX_AEC_GATE_PROF): blocks whose sdSum / seSum decisions the lane-parallel
+                          // sums settled [0] and blocks that ran the ordered sums [1] (aec_gate.h), read with wmx_debug_aec_gate_prof
+__device__ unsigned long long g_aec_gate[2];
+#endif
 constexpr int AS_LDS0 = AS_DPOW;               // state words kept in LDS: everything after the filter taps
 constexpr int AS_LDS_WORDS = AS_WORDS - AS_DPOW;
 #ifndef WMX_AEC_FAS
@@ -590,8 +601,11 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         for (int p = 0; p < 12; p++) {
             // (yr, yi) += (xr*wr - xi*wi, xr*wi + xi*wr): cmul_w is those four products and two sums, as three packed instructions
             y2 = y2 + cmul_w(xr[p], xi[p], taps.t[p]);
-            const float nr = nq[(2 * (11 - p)) >> 3][(2 * (11 - p)) & 7], ni = nq[(2 * (11 - p) + 1) >> 3][(2 * (11 - p) + 1) & 7];  // ni == 0, wfBuf[1][.][64] == 0
-            y64 += nr * W.wn[p] - ni * 0.f;                                                    // used by lane 0 only
+            // bin 64: the reference's xfBuf[0]*wfBuf[0] - xfBuf[1]*wfBuf[1] with wfBuf[1][.][64] == 0.  The imaginary word of F.nyq is
+            // the constant +0.f wherever it is written (aec_far_kernel: `xi64`, the only store; the slab starts zeroed), so the
+            // second product is +0 and x - (+0) is x for every x, sign and NaN included: the term is not formed
+            const float nr = nq[(2 * (11 - p)) >> 3][(2 * (11 - p)) & 7];
+            y64 += nr * W.wn[p];  // used by lane 0 only
         }
         // ---- error e = d - y (aec_core.c:1286-1297): y = second half of the inverse transform of the packed spectrum
         //      (lane 0 carries (bin 0, bin 64)), one point per lane in registers: lanes 32..63 end up with y[2(l-32)], +1
@@ -745,12 +759,9 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
             }
             wait_vm();
 #pragma unroll
-            for (int q = 0; q < 8; q++)
-                if (q < cnt) xi[q] = -xi[q];
-#pragma unroll
             for (int q = 0; q < 8; q++) {
                 if (q >= cnt) continue;
-                st_pt(W.fa[q], lane, cmul_w(xr[q], xi[q], v2f{efr, efi}));  // (xr*efr - xi*efi, xr*efi + xi*efr)
+                st_pt(W.fa[q], lane, cmul_conj_w(xr[q], xi[q], v2f{efr, efi}));  // conj(X) * ef = (xr*efr + xi*efi, xr*efi - xi*efr)
             }
         }
         wave_sync();
@@ -875,6 +886,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         }
     }
     wave_sync();
+    AecGate gate = AecGate{0, 0, 0};
     // SmoothedPSD (aec_core.c:333-386).  Bin `lane` and bin 64 go through the same straight-line code (every lane forms bin
     // 64 from the same LDS words, lane 0 stores it): two independent dependency chains for the scheduler to interleave,
     // instead of a second loop iteration that runs for lane 0 alone.
@@ -910,37 +922,32 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
 #if !defined(WMX_AEC_EXP) || WMX_AEC_EXP < 1
         const Psd c = psd(kAecPart);
         if (lane == 0) put(kAecPart, c);
+        // sdSum and seSum feed two comparisons and nothing else: lane-parallel sums of the values still in registers settle both
+        // unless one of them lies within the summation error of its threshold (aec_gate.h)
+        float sd_t = a.sd, se_t = a.se;
+        aec_gate_wave_sums(sd_t, se_t);
+        gate = aec_gate_decide(sd_t + c.sd, se_t + c.se, Si[AS_DIVERGE]);
+        gate.decided = __builtin_amdgcn_readfirstlane(gate.decided);  // the same in every lane: a scalar branch below
 #endif
     }
     wave_sync();
     AEC_PROF(5);
-    // the two ordered sums advance side by side: lane 0 adds sd[0..64], lane 1 adds se[0..64] (index order each)
-    float sdSum, seSum;
-#if defined(WMX_AEC_EXP) && WMX_AEC_EXP >= 2
-    sdSum = AEC_ST(AS_SD), seSum = AEC_ST(AS_SE + 1);
-#else
-    {
-        const float *mine = &AEC_ST(lane == 1 ? AS_SE : AS_SD);
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < kAecPart; i += 8) {
-            const float4 a = *reinterpret_cast<const float4 *>(mine + i), b = *reinterpret_cast<const float4 *>(mine + i + 4);
-            acc += a.x;
-            acc += a.y;
-            acc += a.z;
-            acc += a.w;
-            acc += b.x;
-            acc += b.y;
-            acc += b.z;
-            acc += b.w;
-        }
-        acc += mine[kAecPart];
-        sdSum = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 0));
-        seSum = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 1));
-    }
+    int diverge = gate.diverge;
+    bool reset_filter = gate.reset;
+#ifdef WMX_AEC_GATE_PROF
+    if (lane == 0) atomicAdd(&g_aec_gate[gate.decided ? 0 : 1], 1ull);
 #endif
-    const int diverge = ((Si[AS_DIVERGE] ? 1.05f : 1.0f) * seSum > sdSum) ? 1 : 0;
-    const bool reset_filter = seSum > (19.95f * sdSum);
+    if (!gate.decided) {
+        // the two ordered sums advance side by side: lane 0 adds sd[0..64], lane 1 adds se[0..64] (index order each)
+        float sdSum, seSum;
+#if defined(WMX_AEC_EXP) && WMX_AEC_EXP >= 2
+        sdSum = AEC_ST(AS_SD), seSum = AEC_ST(AS_SE + 1);
+#else
+        aec_gate_ordered_sums(&AEC_ST(AS_SD), &AEC_ST(AS_SE), lane, sdSum, seSum);
+#endif
+        diverge = ((Si[AS_DIVERGE] ? 1.05f : 1.0f) * seSum > sdSum) ? 1 : 0;
+        reset_filter = seSum > (19.95f * sdSum);
+    }
     wave_sync();
     if (lane == 0) Si[AS_DIVERGE] = diverge;
     if (reset_filter) {  // memset(wfBuf, 0)
@@ -1366,7 +1373,17 @@ extern "C" int wmx_debug_aec_prof(unsigned long long *out16, int reset) {
     return 0;
 }
 #endif
-
+#ifdef WMX_AEC_GATE_PROF
+extern "C" int wmx_debug_aec_gate_prof(unsigned long long *out2, int reset) {
+    hipDeviceSynchronize();
+    hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_aec_gate), sizeof(unsigned long long) * 2);
+    if (reset) {
+        unsigned long long z[2] = {0, 0};
+        hipMemcpyToSymbol(HIP_SYMBOL(g_aec_gate), z, sizeof(z));
+    }
+    return 0;
+}
+#endif
 
 __global__ void aec_fill_state(float *state, const float *tmpl, int words, int n_streams) {
     const size_t total = (size_t)words * n_streams;
@@ -2057,4 +2074,65 @@ extern "C" int wmx_debug_pow(const float *x, const float *e, float *y, size_t n)
     if (!x || !e || !y) return WMX_EINVAL;
     for (size_t i = 0; i < n; i++) y[i] = wmx::fast_pow(x[i], e[i], &tab);
     return 0;
+}
+
+// The sdSum / seSum gate of the near kernel (aec_gate.h) on its own.  Rows of 65 floats (sd[0..64], se[0..64]) and the divergeState
+// in front of the block; out[i] = {decided, diverge, reset, 0}.  On the host: the lane-parallel sums in the device's order and the
+// decision function, the same source the kernel compiles (diverge / reset mean nothing where decided is 0) ...
+extern "C" int wmx_debug_aec_decide(const float *sd_rows, const float *se_rows, const int32_t *prev_state, int32_t *out, size_t n) {
+    if (!sd_rows || !se_rows || !prev_state || !out) return WMX_EINVAL;
+    for (size_t i = 0; i < n; i++) {
+        const wmx::AecGate g = wmx::aec_gate_decide(wmx::aec_gate_sum_host(sd_rows + 65 * i), wmx::aec_gate_sum_host(se_rows + 65 * i), prev_state[i]);
+        out[4 * i] = g.decided, out[4 * i + 1] = g.diverge, out[4 * i + 2] = g.reset, out[4 * i + 3] = 0;
+    }
+    return 0;
+}
+
+// ... and on the DEVICE (device pointers; synchronises `stream`), one wave per row: the kernel's own reduction and, where the gate
+// leaves a row undecided, the kernel's own ordered sums.  out[i] = {1 = settled by the gate / 0 = by the ordered sums, diverge,
+// reset, 0}: diverge and reset are final for every row.
+namespace wmx {
+namespace {
+__global__ __launch_bounds__(64) void dbg_aec_gate_kernel(const float *__restrict__ sd_rows, const float *__restrict__ se_rows,
+                                                          const int32_t *__restrict__ prev_state, int32_t *__restrict__ out) {
+    __shared__ alignas(16) float sd[BP], se[BP];
+    const int lane = threadIdx.x;
+    const size_t row = blockIdx.x;
+    const float a_sd = sd_rows[65 * row + lane], a_se = se_rows[65 * row + lane];
+    const float c_sd = sd_rows[65 * row + kAecPart], c_se = se_rows[65 * row + kAecPart];
+    const int prev = prev_state[row];
+    sd[lane] = a_sd, se[lane] = a_se;
+    if (lane == 0) sd[kAecPart] = c_sd, se[kAecPart] = c_se;
+    float sd_t = a_sd, se_t = a_se;
+    aec_gate_wave_sums(sd_t, se_t);
+    AecGate gate = aec_gate_decide(sd_t + c_sd, se_t + c_se, prev);
+    gate.decided = __builtin_amdgcn_readfirstlane(gate.decided);
+    wave_sync();
+    int diverge = gate.diverge, reset = gate.reset;
+    if (!gate.decided) {
+        float sdSum, seSum;
+        aec_gate_ordered_sums(sd, se, lane, sdSum, seSum);
+        diverge = ((prev ? 1.05f : 1.0f) * seSum > sdSum) ? 1 : 0;
+        reset = seSum > (19.95f * sdSum) ? 1 : 0;
+    }
+    if (lane == 0) {
+        out[4 * row] = gate.decided;
+        out[4 * row + 1] = diverge;
+        out[4 * row + 2] = reset;
+        out[4 * row + 3] = 0;
+    }
+}
+}  // namespace
+}  // namespace wmx
+
+extern "C" int wmx_debug_aec_decide_device(const float *d_sd_rows, const float *d_se_rows, const int32_t *d_prev_state, int32_t *d_out, size_t n,
+                                           void *stream) {
+    using namespace wmx;
+    if (!d_sd_rows || !d_se_rows || !d_prev_state || !d_out || n > 0x7fffffffu) return WMX_EINVAL;
+    if (n == 0) return 0;
+    if (current_device() < 0) return WMX_ENODEV;
+    hipLaunchKernelGGL(dbg_aec_gate_kernel, dim3((unsigned)n), dim3(64), 0, as_stream(stream), d_sd_rows, d_se_rows, d_prev_state, d_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "wmx_debug_aec_decide_device", __FILE__, __LINE__);
 }
