@@ -1,7 +1,7 @@
 /* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
- *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V]
+ *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -27,6 +27,10 @@
  * (wmx_conf_denoise); the JSON line then carries "denoise": 1.  It combines with every other flag.
  * --level V: every leg's rows go through the leg's own AGC with compression gain V dB, behind the suppressor and in front of talker
  * selection and the mix (wmx_conf_level); the JSON line then carries "level": V.  It combines with every other flag.
+ * --gate: every leg's rows go through the leg's own voice-activity gate, behind the AGC and in front of talker selection and the mix
+ * (wmx_conf_gate): a row is shifted right by the leg's `reduce`, which starts at 4 -- a call is heard in full from its fifth row; the JSON
+ * line then carries "gate": 1 and the rows judged voice and not, summed over the legs ("voiced", "unvoiced": wmx_conf_export_gate).  It
+ * combines with every other flag.
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -158,7 +162,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G, 
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
-                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V]\n";
+                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -166,7 +170,7 @@ int main(int argc, char **argv) {
     const int G = atoi(argv[2]), T = atoi(argv[3]);
     const char *sizes = NULL, *speakers = NULL, *platform = "alsa";
     unsigned long seed = 0;
-    int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0, level = -1; /* max_gap -1: sequencing off; level -1: levelling off */
+    int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0, level = -1, gate = 0; /* max_gap -1: sequencing off; level -1: levelling off */
     long correct = -1; /* -1: the library's default = platform/alsa */
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
@@ -186,6 +190,8 @@ int main(int argc, char **argv) {
             dtmf = 1;
         } else if (!strcmp(argv[i], "--denoise")) {
             denoise = 1;
+        } else if (!strcmp(argv[i], "--gate")) {
+            gate = 1;
         } else if (!strcmp(argv[i], "--level") && i + 1 < argc) {
             level = atoi(argv[++i]);
             if (level < 0) {
@@ -241,6 +247,7 @@ int main(int argc, char **argv) {
     if (dtmf) WMX_OK(wmx_conf_dtmf(h, 1, 1, DTMF_EVENT_PT));
     if (denoise) WMX_OK(wmx_conf_denoise(h, 1));
     if (level >= 0) WMX_OK(wmx_conf_level(h, 1, level));
+    if (gate) WMX_OK(wmx_conf_gate(h, 1));
     int n_ulaw = 0;
     for (int g = 0; g < G; g++) {
         const int32_t leg = g;
@@ -316,6 +323,14 @@ int main(int argc, char **argv) {
         if (!key_count || !key_ring) return 2;
         WMX_OK(wmx_conf_export_dtmf(h, key_count, key_ring, NULL));
     }
+    unsigned long n_voiced = 0, n_unvoiced = 0;
+    if (gate) {
+        uint32_t *cnt = calloc(2 * (size_t)G, sizeof(uint32_t));
+        if (!cnt) return 2;
+        WMX_OK(wmx_conf_export_gate(h, NULL, cnt, cnt + G, NULL));
+        for (int g = 0; g < G; g++) n_voiced += cnt[g], n_unvoiced += cnt[G + g];
+        free(cnt);
+    }
     uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
@@ -342,6 +357,7 @@ int main(int argc, char **argv) {
     }
     if (denoise) printf("\"denoise\": 1, ");
     if (level >= 0) printf("\"level\": %d, ", level);
+    if (gate) printf("\"gate\": 1, \"voiced\": %lu, \"unvoiced\": %lu, ", n_voiced, n_unvoiced);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

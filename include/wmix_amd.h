@@ -171,6 +171,29 @@ int wmx_vad_set_active(wmx_vad *h, const uint8_t *host_mask, void *stream);
 int wmx_vad_stream_state_bytes(const wmx_vad *h);
 int wmx_vad_export_stream(wmx_vad *h, int stream_index, void *host_blob);
 int wmx_vad_import_stream(wmx_vad *h, int stream_index, const void *host_blob);
+/* The ragged form for the legs of a conference bridge, on a handle created with chn == 1, freq == 8000 and an interval_ms that is a
+ * multiple of 20 (a packet of 160 samples, exactly one row): stream g is leg g, and a tick brings it 0 .. max_packets
+ * (1 .. WMX_MIX_MAX_LEG_PACKETS) rows of 160 samples (20 ms), slot k at d_pcm + g * leg_stride + k * packet_stride (strides in
+ * samples), with d_len[g * max_packets + k] == 320 where the slot holds a row.  Arguments, order and refusals are those of
+ * wmx_nsx_process_legs and wmx_agc_process_legs: the leg's rows are taken in the order the load makes its calls
+ * (wmix_amd/csrc/leg_calls.h): d_calls NULL, the slots with d_len == 320 in slot order; else d_calls[g] is the leg's call list
+ * (WMX_RTP_CALLS_*, what wmx_rtp_sequence_legs leaves), walked in list order, where a silence call or a data call naming a row that is
+ * not readable feeds NOTHING -- a lost packet is not 20 ms of zeros to the noise model.  Each row taken is one vad_process of the
+ * reference on one 160-sample packet, in place: the decision, one step of the leg's `reduce` (0 .. 4; a fresh stream starts at 4, so
+ * a new call is attenuated in its first rows and heard in full from its fifth), the row shifted right by it.  The bits are those of
+ * wmx_vad_process(h, rows, 1, n, ...) over the same rows in the same order.  A leg with no row this tick touches nothing: its state is
+ * neither loaded nor stored.  A row that is not taken -- a late packet, a duplicate, a refused packet -- keeps its bytes and is never
+ * addressed.  wmx_vad_set_active's mask holds here too.
+ * d_voice: NULL, or 2 * n_streams words on the device, owned by the caller (who zeroes them): word g is incremented per row taken of
+ * leg g whose decision, after hangover, is voice, word n_streams + g per row taken whose decision is not.
+ * ALIGNMENT: d_pcm on a 2-byte boundary is all that is required.  When d_pcm is on a 16-byte boundary and both strides are multiples
+ * of 8 samples a row travels as 16-byte words through registers; otherwise it is read and written sample by sample.  Same bits.
+ * WMX_EINVAL, nothing launched: a handle whose packet is not 160 samples of 1 x 8000; max_packets outside 1 .. 4; d_pcm or d_len NULL;
+ * rows that overlap (packet_stride < 160, or with more than one leg leg_stride < max_packets * packet_stride); d_pcm on an odd address.
+ * wmx_vad_export_reduce: `reduce` of every stream (int16, n_streams of them) as the work queued on `stream` leaves it; blocking. */
+int wmx_vad_process_legs(wmx_vad *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                         const uint32_t *d_calls, uint32_t *d_voice, void *stream);
+int wmx_vad_export_reduce(wmx_vad *h, int16_t *host_reduce, void *stream);
 
 /* ------------------------------------------------------------------ AGC (legacy fixed-point, adaptive digital)
  * Batched form of agc_init / agc_process / agc_addition / agc_release (src/webrtc.h:55-60,
@@ -913,6 +936,23 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * fresh AGC state (wmx_agc_reset_streams) once the AGC has been made: a reset leg keeps its compression gain.  wmx_conf_leveller: the
  * legs' wmx_agc (NULL until the first switch-on), for wmx_agc_set_gain_streams (one leg's volume), wmx_agc_stream_gain and
  * wmx_agc_export_stream / wmx_agc_import_stream on a leg.
+ * wmx_conf_gate(h, on): between submits; off is the default.  On, wmx_vad_process_legs runs directly behind the leveller (behind the
+ * ingest, wmx_rtp_sequence_legs -- it is given the call list exactly when the sequencer ran --, wmx_rtp_detect_dtmf_legs and the
+ * denoiser) and in front of the selection: every row a leg's load will consume is one vad_process of that leg's own voice-activity
+ * gate (a wmx_vad stream of 1 x 8000, interval 20 ms: WebRtcVad mode 3, the last stage of the reference's record heartbeat), in
+ * place, in the order the load consumes them -- the decision moves the leg's `reduce` one step in 0 .. 4 and the row is shifted
+ * right by it.  The keypad is judged on the row as it arrived; the selection, the concealment history and the load all see the gated
+ * rows, so a leg that sends only stationary room noise is heard 24 dB down and falls under a talker floor.  A lost packet feeds the
+ * gate nothing; a late, duplicate or refused packet is not touched.  Mute and selection act at the load: a muted leg's rows are
+ * gated all the same.  A FRESH GATE IS SHUT: vad_init leaves `reduce` at 4, so the first rows of a new call -- after the first
+ * switch-on and after wmx_conf_reset_legs -- are attenuated (>> 3, 2, 1 at best), and a call is heard in full from its fifth row.
+ * That is the reference's behaviour and is kept.  The first switch-on makes the VAD and two counters per leg; off, the launches are
+ * those of a handle that never heard of it and neither the VAD's state nor the counters move; the VAD is never made inside a submit,
+ * and switching off and on again keeps state and counters.  wmx_conf_reset_legs gives the listed legs a fresh gate
+ * (wmx_vad_reset_streams: `reduce` back to 4) and zeroes their counters once the gate has been made.  wmx_conf_gater: the legs'
+ * wmx_vad (NULL until the first switch-on), for wmx_vad_export_stream / wmx_vad_import_stream on a leg.  wmx_conf_export_gate: reduce
+ * (uint8, 0 .. 4), voiced and unvoiced (uint32: the rows taken that were judged voice, after hangover, and those that were not) of
+ * every leg, any pointer NULL; blocking; before the first switch-on reduce is 4 and the counts are 0.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -936,6 +976,9 @@ int wmx_conf_denoise(wmx_conf *h, int on);
 wmx_nsx *wmx_conf_denoiser(wmx_conf *h);
 int wmx_conf_level(wmx_conf *h, int on, int value);
 wmx_agc *wmx_conf_leveller(wmx_conf *h);
+int wmx_conf_gate(wmx_conf *h, int on);
+wmx_vad *wmx_conf_gater(wmx_conf *h);
+int wmx_conf_export_gate(wmx_conf *h, uint8_t *reduce, uint32_t *voiced, uint32_t *unvoiced, void *stream);
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
 int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);

@@ -77,7 +77,11 @@ alone, device time (events), on as many legs: wmx_agc_process_legs on one row pe
 kernel) on a dense plane of the same rows -- the dense side twice in every repetition -- and then with one leg in eight sending; and all
 of that again with three rows per leg, the most the bench's max_packets holds.  Every
 side's rows are put back in front of every call, outside the timed region: a row levelled over and over ends at the limiter.
-    python tools_dev/bridge_bench.py --pipe --level 20 --steady --out profiles/bridge/bridge_level_bench.json"""
+    python tools_dev/bridge_bench.py --pipe --level 20 --steady --out profiles/bridge/bridge_level_bench.json
+--gate-kernel N: nothing of the above; the gate's kernel alone, device time (events), on N legs: wmx_vad_process_legs on one row per leg
+against wmx_vad_process (1 x 8000, 20 ms packets, its four-wave pipeline kernel) on a dense plane of the same rows -- the dense side
+twice in every repetition -- and then with one leg in eight sending.
+    python tools_dev/bridge_bench.py --gate-kernel 4096 --out profiles/bridge/bridge_gate_bench.json"""
 import argparse
 import json
 import os
@@ -411,6 +415,52 @@ def level_kernel(legs, reps, value, rows=1):
             "wmx_agc_process_legs_every_leg": full, "wmx_agc_process_legs_one_leg_in_eight": sparse,
             "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4), "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4),
             "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
+
+
+def gate_kernel(legs, reps):
+    """wmx_vad_process_legs on one row per leg beside wmx_vad_process (1 x 8000, 20 ms, one call of one packet: its four-wave pipeline
+    kernel) on a dense plane of the same rows: device milliseconds per launch.  The dense side twice in every repetition, so that its
+    own run-to-run spread stands beside the difference; then with one leg in eight sending.  Every side's rows are put back in front of
+    every call, outside the timed region: a row gated over and over is silence."""
+    from wmix_amd.vad import VadBatch
+    rng = np.random.default_rng(19)
+    t = np.arange(160)
+    x = rng.integers(300, 12000, (legs, 1)) * np.sin(2 * np.pi * rng.integers(150, 1500, (legs, 1)) * t / 8000) + rng.normal(0, 100, (legs, 160))
+    src = torch.from_numpy(np.clip(np.round(x), -32768, 32767).astype(np.int16)).cuda()
+    every, sparse_of = torch.zeros((legs, 3), dtype=torch.int32, device="cuda"), torch.zeros((legs, 3), dtype=torch.int32, device="cuda")
+    every[:, 0] = 320
+    sparse_of[::8, 0] = 320
+    handles = [VadBatch(legs, 1, 8000, 20) for _ in range(4)]
+    dense_rows = [torch.zeros((legs, 1, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
+    leg_rows = [torch.zeros((legs, 3, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
+    voice = torch.zeros((2, legs), dtype=torch.int32, device="cuda")
+
+    def dense(k):
+        return (lambda: dense_rows[k].view(legs, 160).copy_(src)), (lambda: handles[k].process(dense_rows[k]))
+
+    def ragged(k, lens):
+        return (lambda: leg_rows[k][:, 0].copy_(src)), (lambda: handles[2 + k].process_legs(leg_rows[k], lens, None, voice))
+
+    sides = [dense(0), ragged(0, every), dense(1), ragged(1, sparse_of)]
+    for prepare, f in sides * 20:
+        prepare()
+        f()
+    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for _ in sides]
+    for r in range(reps):
+        for k, (prepare, f) in enumerate(sides):
+            prepare()
+            ev[k][r][0].record()
+            f()
+            ev[k][r][1].record()
+    torch.cuda.synchronize()
+    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
+    d0, full, d1, sparse = (stats([a.elapsed_time(b) for a, b in side]) for side in ev)
+    for h in handles:
+        h.close()
+    return {"legs": legs, "rows_per_leg": 1, "wmx_vad_process_dense": d0, "wmx_vad_process_dense_again": d1, "wmx_vad_process_legs_every_leg": full,
+            "wmx_vad_process_legs_one_leg_in_eight": sparse, "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4),
+            "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4), "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
 
 
 def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False, level=-1):
@@ -851,6 +901,7 @@ if __name__ == "__main__":
     ap.add_argument("--loss-every", type=int, default=0, help="with --pipe: one packet in N never arrives, on all sides alike: the run path of the concealment")
     ap.add_argument("--denoise", action="store_true", help="with --pipe: two more sides with denoising on, and the new kernel alone beside the dense call")
     ap.add_argument("--level", type=int, default=-1, help="with --pipe: two more sides with levelling on at this compression gain, and the new kernel alone beside the dense call")
+    ap.add_argument("--gate-kernel", type=int, default=0, help="wmx_vad_process_legs alone on this many legs beside wmx_vad_process on the same rows; nothing else")
     ap.add_argument("--steady", action="store_true", help="with --pipe: every leg sends one packet per tick, on all sides alike")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -861,6 +912,11 @@ if __name__ == "__main__":
                "runs": "the builder's own, one process, the sides alternating", "legs": legs_against_conf(args.reps)}
         args.sizes = args.tick = ""
         args.ragged, args.speakers = False, 0
+    if args.gate_kernel > 0:
+        res = {"tool": "bridge_bench --gate-kernel", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+               "runs": "the builder's own, one process, the sides alternating", "gate_kernel": gate_kernel(args.gate_kernel, args.reps), "load": [], "tick": None}
+        args.sizes = args.tick = ""
+        args.ragged, args.speakers, args.pipe = False, 0, False
     if args.pipe:
         res = {"tool": "bridge_bench --pipe", "device": torch.cuda.get_device_name(0), "reps": args.reps,
                "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every, args.loss_every, args.denoise, args.steady, args.level)}

@@ -126,6 +126,31 @@ class ConfBridge:
         idx = np.ascontiguousarray(legs, dtype=np.int32)
         check(L.wmx_agc_set_gain_streams(agc, idx.ctypes.data, idx.size, int(value), self._stream()), "wmx_agc_set_gain_streams")
 
+    def gate(self, on):
+        """every leg's rows go through the leg's own voice-activity gate (WebRtcVad mode 3; the row is shifted right by the leg's
+        `reduce`, 0 .. 4) directly behind the leveller and in front of talker selection (wmx_conf_gate), between submits; a fresh gate
+        is shut (`reduce` 4): a new call is heard in full from its fifth row.  off (the default) = the launches of before, and the
+        gate's state and counters stay"""
+        check(lib().wmx_conf_gate(self._h, 1 if on else 0), "wmx_conf_gate")
+
+    def gater_state(self, leg):
+        """the stream blob of one leg's VAD (wmx_vad_export_stream on wmx_conf_gater), None before the first gate(True)"""
+        L = lib()
+        vad = L.wmx_conf_gater(self._h)
+        if not vad:
+            return None
+        blob = np.zeros(L.wmx_vad_stream_state_bytes(vad), np.uint8)
+        check(L.wmx_vad_export_stream(vad, int(leg), blob.ctypes.data), "wmx_vad_export_stream")
+        return blob
+
+    def export_gate(self):
+        """dict(reduce: uint8 [n_legs], 0 .. 4; voiced, unvoiced: uint32 [n_legs], the rows judged voice and not) as the work queued on
+        the current stream leaves them; before the first gate(True): reduce 4, counts 0"""
+        r = {"reduce": np.zeros(self.n_legs, np.uint8), "voiced": np.zeros(self.n_legs, np.uint32), "unvoiced": np.zeros(self.n_legs, np.uint32)}
+        check(lib().wmx_conf_export_gate(self._h, r["reduce"].ctypes.data, r["voiced"].ctypes.data, r["unvoiced"].ctypes.data, self._stream()),
+              "wmx_conf_export_gate")
+        return r
+
     def set_codecs(self, legs, in_codec, out_law):
         """a G.711 codec per leg, as each call negotiated it (wmx_conf_set_codecs), between submits: in_codec "reference" (the default:
         A-law whatever arrives), "pcma", "pcmu" or "by_pt" (or WMX_CODEC_* 0 .. 3), out_law "a" / "u"; legs None = every leg"""
@@ -147,8 +172,8 @@ class ConfBridge:
 
     def reset_legs(self, legs=None):
         """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
-        refused = 0, the concealment history and count zero, no key down and no digit reported, the noise suppressor and the AGC as
-        new; the leg keeps its codec and its compression gain (None = every leg)"""
+        refused = 0, the concealment history and count zero, no key down and no digit reported, the noise suppressor, the AGC and the
+        gate as new (the gate shut, its counters zero); the leg keeps its codec and its compression gain (None = every leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

@@ -16,7 +16,8 @@
 // (wmx_conf_denoise) wmx_nsx_process_legs stands behind the sequencer and the DTMF detection and in front of the selection: each leg's
 // rows of the tick go through the leg's own fixed-point noise suppressor in place, in the order the load will consume them.  With
 // levelling on (wmx_conf_level) wmx_agc_process_legs stands directly behind it: the same rows, in the same order, through the leg's own
-// AGC with the leg's own compression gain.
+// AGC with the leg's own compression gain.  With the gate on (wmx_conf_gate) wmx_vad_process_legs stands directly behind that: the same
+// rows, in the same order, each one vad_process of the leg's own voice-activity gate, which shifts the row right by the leg's `reduce`.
 //
 // PER SLOT (slot_ring.h, made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a
 // 4-byte boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and the events.  PER HANDLE: the mixer
@@ -58,6 +59,9 @@ struct wmx_conf {
     bool level_on;    // wmx_agc_process_legs behind the denoiser
     wmx_agc *agc;     // an AGC stream per leg, made when levelling is first switched on
     int level_value;  // the compression gain wmx_conf_level last gave every leg
+    bool gate_on;      // wmx_vad_process_legs behind the leveller
+    wmx_vad *vad;      // a VAD stream per leg (1 x 8000, 20 ms), made when the gate is first switched on
+    uint32_t *d_gate;  // [2][n_legs] rows judged voice / not voice per leg, made with it
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -91,6 +95,10 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         rc = wmx_agc_process_legs(h->agc, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
         if (rc != 0) return rc;
     }
+    if (h->gate_on) {  // behind the leveller: the decision is made on the levelled row; selection, concealment and the load see the gated rows
+        rc = wmx_vad_process_legs(h->vad, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, h->d_gate, stream);
+        if (rc != 0) return rc;
+    }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
     if (h->max_speakers > 0) {
         rc = wmx_mix_select_speakers_legs(h->mix, h->d_pcm, kLegRowBytes, (long)K * kLegRow, kLegRow, K, h->d_len, host_mute, h->max_speakers,
@@ -119,7 +127,7 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
 }
 
 // the listed legs' streams (NULL = all) of a per-leg stage as its init leaves them: the suppressor (ns_init), the AGC (agc_init, each
-// leg with the compression gain it has)
+// leg with the compression gain it has), the gate (vad_init: `reduce` back to 4)
 template <class Stage>
 static int conf_reset_stage(wmx_conf *h, Stage *stage, int (*reset_streams)(Stage *, const int32_t *, int, void *), const int32_t *host_idx,
                             int n, void *stream) {
@@ -127,6 +135,20 @@ static int conf_reset_stage(wmx_conf *h, Stage *stage, int (*reset_streams)(Stag
     std::vector<int32_t> all((size_t)h->n_legs);
     for (int g = 0; g < h->n_legs; g++) all[(size_t)g] = g;
     return reset_streams(stage, all.data(), h->n_legs, stream);
+}
+
+// the listed legs' (NULL = all) two counters of the gate back to zero, ordered on `stream`
+static int conf_reset_gate_counts(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
+    hipStream_t s = wmx::as_stream(stream);
+    if (!host_idx) {
+        WMX_HIP(hipMemsetAsync(h->d_gate, 0, 2 * (size_t)h->n_legs * sizeof(uint32_t), s));
+        return 0;
+    }
+    for (int i = 0; i < n; i++) {
+        WMX_HIP(hipMemsetAsync(h->d_gate + host_idx[i], 0, sizeof(uint32_t), s));
+        WMX_HIP(hipMemsetAsync(h->d_gate + h->n_legs + host_idx[i], 0, sizeof(uint32_t), s));
+    }
+    return 0;
 }
 
 extern "C" {
@@ -144,6 +166,8 @@ int wmx_conf_destroy(wmx_conf *h) {
     if (h->h_mute) (void)hipHostFree(h->h_mute);
     if (h->nsx) wmx_nsx_destroy(h->nsx);
     if (h->agc) wmx_agc_destroy(h->agc);
+    if (h->vad) wmx_vad_destroy(h->vad);
+    if (h->d_gate) (void)hipFree(h->d_gate);
     if (h->mix) wmx_mix_destroy(h->mix);
     if (h->snd) wmx_rtp_destroy(h->snd);
     delete h;
@@ -347,6 +371,57 @@ int wmx_conf_level(wmx_conf *h, int on, int value) {
 // levelling is first switched on
 wmx_agc *wmx_conf_leveller(wmx_conf *h) { return h ? h->agc : nullptr; }
 
+// on != 0: every leg's rows of the tick go through the leg's own voice-activity gate (wmx_vad_process_legs: 1 x 8000, 20 ms, one row
+// one vad_process) directly behind the leveller and in front of the selection; 0 (the default): the launches of a handle that never
+// heard of it.  Between submits.  The VAD and the handle's counters are made the first time it is switched on -- every leg's `reduce`
+// at 4, as vad_init leaves it --; off and on again keeps both.
+int wmx_conf_gate(wmx_conf *h, int on) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (on && !h->vad) {
+        void *p = nullptr;
+        int rc = wmx::zeroed_block(&p, 2 * (size_t)h->n_legs * sizeof(uint32_t), "hipMemset(gate counters)");
+        if (rc != 0) return rc;
+        wmx_vad *vad = nullptr;
+        if ((rc = wmx_vad_create(&vad, h->n_legs, 1, 8000, 20)) != 0) {
+            (void)hipFree(p);
+            return rc;
+        }
+        h->vad = vad;
+        h->d_gate = static_cast<uint32_t *>(p);
+    }
+    h->gate_on = on != 0;
+    return 0;
+}
+
+// the legs' VAD, for wmx_vad_export_stream / wmx_vad_import_stream / wmx_vad_export_reduce; NULL until the gate is first switched on
+wmx_vad *wmx_conf_gater(wmx_conf *h) { return h ? h->vad : nullptr; }
+
+// reduce (uint8, 0 .. 4) and the rows judged voice / not voice (uint32) of every leg as the work queued on `stream` leaves them; any
+// pointer may be NULL; blocking.  Before the first switch-on: reduce 4, counts 0 -- what the first switch-on makes.
+int wmx_conf_export_gate(wmx_conf *h, uint8_t *reduce, uint32_t *voiced, uint32_t *unvoiced, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const size_t n = (size_t)h->n_legs;
+    if (!h->vad) {
+        if (reduce) memset(reduce, 4, n);
+        if (voiced) memset(voiced, 0, n * sizeof(uint32_t));
+        if (unvoiced) memset(unvoiced, 0, n * sizeof(uint32_t));
+        return 0;
+    }
+    hipStream_t s = wmx::as_stream(stream);
+    if (reduce) {
+        std::vector<int16_t> r(n);
+        const int rc = wmx_vad_export_reduce(h->vad, r.data(), stream);
+        if (rc != 0) return rc;
+        for (size_t g = 0; g < n; g++) reduce[g] = (uint8_t)r[g];
+    }
+    if (voiced) WMX_HIP(hipMemcpyAsync(voiced, h->d_gate, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (unvoiced) WMX_HIP(hipMemcpyAsync(unvoiced, h->d_gate + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    WMX_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 // a G.711 codec per leg (wmx_rtp_set_codecs over the legs; NULL = all): between submits, ordered on `stream`
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
     if (!h) return WMX_EINVAL;
@@ -363,7 +438,7 @@ int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_
 
 // a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
 // refused = 0, the concealment history and count zero, the DTMF state fresh, the noise suppressor as ns_init leaves it, the AGC as
-// agc_init leaves it; the leg keeps its codec and its compression gain
+// agc_init leaves it, the gate as vad_init leaves it (`reduce` 4) and its two counters zero; the leg keeps its codec and its compression gain
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
     // before the first of them: a bad index resets nothing
@@ -377,6 +452,8 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0 && h->dtmf_made) rc = wmx_rtp_reset_dtmf(h->snd, host_idx, n, stream);  // a new call inherits no half key press
     if (rc == 0 && h->nsx) rc = conf_reset_stage(h, h->nsx, wmx_nsx_reset_streams, host_idx, n, stream);  // nor the old call's noise estimate
     if (rc == 0 && h->agc) rc = conf_reset_stage(h, h->agc, wmx_agc_reset_streams, host_idx, n, stream);  // nor its level estimate
+    if (rc == 0 && h->vad) rc = conf_reset_stage(h, h->vad, wmx_vad_reset_streams, host_idx, n, stream);  // nor its noise model and hangover
+    if (rc == 0 && h->vad) rc = conf_reset_gate_counts(h, host_idx, n, stream);
     return rc;
 }
 

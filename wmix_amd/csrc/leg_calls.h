@@ -1,7 +1,7 @@
 // leg_calls.h -- the call list of one RTP leg of the bridge and the one walk over a leg's rows of a tick: which of its 0 .. 4 rows a
 // per-leg stage takes, and in which order.  What the sequence rule (leg_seq.h) writes and the cursor rule (leg_cursor.h), the
-// concealment rule (leg_plc.h), the DTMF rule (leg_dtmf.h), the denoiser of the legs (nsx_legs_kernel, nsx.hip) and their AGC
-// (agc_legs_kernel, agc.hip) read.
+// concealment rule (leg_plc.h), the DTMF rule (leg_dtmf.h), the denoiser of the legs (nsx_legs_kernel, nsx.hip), their AGC
+// (agc_legs_kernel, agc.hip) and their voice-activity gate (vad_legs_kernel, vad.hip) read.
 //
 // A ROW is the 160 samples of one datagram, 20 ms of 1 x 8000; it is readable when its d_len says 320 bytes.
 //
@@ -11,10 +11,10 @@
 // PER LEG AND TICK the leg's rows are taken in the order the load makes its calls: without a call list the slots k = 0 ..
 // max_packets - 1 with d_len == 320 in slot order; with one, the list wmx_rtp_sequence_legs leaves (leg_seq.h), in list order, where a
 // silence call or a data call naming a row that is not readable adds nothing: the load makes it with zeros, concealment fills it, it
-// is a block that is not a tone, and neither the noise estimator nor the level detector is fed.  A leg with no call this tick keeps
+// is a block that is not a tone, and neither the noise estimator nor the level detector nor the gate's noise model is fed.  A leg with no call this tick keeps
 // its state.  Every row is taken as the tick brought it.
 //
-// Plain C++ without HIP types: mix.hip, rtp.hip, nsx.hip and agc.hip include it for the device, tools_dev/san/leg_calls_san.cpp
+// Plain C++ without HIP types: mix.hip, rtp.hip, nsx.hip, agc.hip and vad.hip include it for the device, tools_dev/san/leg_calls_san.cpp
 // compiles it with g++ and tests/test_leg_calls_host.py compares every case with a model written from the text above.
 #pragma once
 #include <cstdint>

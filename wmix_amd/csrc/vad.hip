@@ -1,5 +1,6 @@
 // vad.hip -- batched voice-activity gate for gfx950: one LANE per stream (vad_kernel), and for the mono 10 ms packets of the
-// batched chain one lane per stream in FOUR waves that split a packet's work (vad_pipe_kernel, further down).
+// batched chain one lane per stream in FOUR waves that split a packet's work (vad_pipe_kernel, further down); and for the legs of a
+// conference bridge one lane per leg over the 0 .. 4 rows a tick brought it (vad_legs_kernel, wmx_vad_process_legs).
 //
 // Replaces, for many independent streams per launch, wmix's vad_process() (src/webrtc.c:91-151)
 // over WebRtcVad_Process in mode 3 (W:common_audio/vad/webrtc_vad.c:71-104, vad_core.c:124-674,
@@ -27,6 +28,7 @@
 #include <vector>
 #include "stage_life.h"
 #include "spl_dev.h"
+#include "leg_calls.h"
 
 namespace wmx {
 namespace {
@@ -1128,6 +1130,98 @@ __global__ __launch_bounds__(64) void vad_kernel(int16_t *s16, int32_t *s32, int
     }
     VAD_PROF(8);  // state out (issue)
 }
+
+// The ragged form for the legs of a conference bridge (wmx_vad_process_legs): 1 x 8000 with 20 ms packets, so a row of the bridge is
+// exactly one packet and one vad_process call.  Lane = leg and one wave per 64 legs like vad_kernel<160, 1>, state in registers and the
+// order statistics in LDS as there, but a leg brings 0 .. 4 rows this tick, the count is known only here (len, calls) and the order is
+// the load's: the walk of leg_calls.h, where a call that adds nothing feeds nothing (a lost packet is not 20 ms of zeros to the noise
+// model).  The lanes of a wave take different numbers of rows at different slots: the walk is ONE rolled loop over the 4 calls whose
+// body is predicated by the lane's `take` bit (the wave skips an iteration nobody takes), not a branch tree per lane.  A leg with no
+// row this tick neither loads nor stores its state, so a workgroup none of whose legs has a row leaves before it stages anything.  A row
+// that is not taken is never addressed.  FAST (base and strides on 16 bytes, chosen once per launch): a row is fetched as uint4's,
+// analysed from registers and written back as uint4's; otherwise sample by sample from memory.  voice: NULL, or [2][n_legs] counts
+// of the rows taken that were judged voice (after hangover) / not voice; a leg's two words are this lane's alone.
+template <bool FAST>
+__global__ __launch_bounds__(64) void vad_legs_kernel(int16_t *s16, int32_t *s32, int16_t *pcm, int n_legs, long leg_stride, long packet_stride,
+                                                      int max_packets, const uint32_t *__restrict__ len, const uint32_t *__restrict__ calls_in,
+                                                      uint32_t *voice, const uint8_t *__restrict__ active) {
+    constexpr int NB = 160, NV = NB / 8;
+    static_assert(NB == kLegRow, "a row of the bridge is one 20 ms packet of the 8 kHz VAD");
+    __shared__ int16_t lds[64 * (NB / 2 + NB / 2 + NB / 4 + NB / 4)];
+    __shared__ int16_t minlds[64 * kVadMinFields];
+    const int lane = threadIdx.x;
+    const int leg = blockIdx.x * 64 + lane;
+    uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
+    if (stream_active(active, leg, n_legs)) {
+        const LegWalk w = leg_calls_walk(len + (size_t)leg * max_packets, calls_in != nullptr, calls_in ? calls_in[leg] : 0u, max_packets);
+        list = w.list, take = w.data;
+    }
+    // no stream, one that is switched off, or a leg without a row: state and rows untouched.  Nothing here is staged for the workgroup
+    // and there is no barrier anywhere (lanes are independent, as in vad_kernel), so a workgroup nobody of which sent anything is gone
+    if (take == 0u) return;
+    int16_t r16[kVadRegFields];
+    int32_t r32[V32_WORDS];
+    const VadRef S{r16, r32, minlds + lane};
+    int16_t *g16 = s16 + leg;
+    int32_t *g32 = s32 + leg;
+#pragma unroll
+    for (int f = 0; f < V16_AGE; f++) r16[f] = g16[(size_t)f * n_legs];
+#pragma unroll
+    for (int f = V16_MEAN_VALUE; f < V16_WORDS; f++) r16[f - kVadMinFields] = g16[(size_t)f * n_legs];
+#pragma unroll
+    for (int f = 0; f < V32_WORDS; f++) r32[f] = g32[(size_t)f * n_legs];
+#pragma unroll 8
+    for (int f = 0; f < kVadMinFields; f++) minlds[f * 64 + lane] = g16[(size_t)(V16_AGE + f) * n_legs];
+    const LaneBuf hp120{lds + lane}, lp120{lds + lane + 64 * (NB / 2)}, hp60{lds + lane + 64 * NB}, lp60{lds + lane + 64 * (NB + NB / 4)};
+    int16_t *rows = pcm + (size_t)leg * leg_stride;
+    int reduce = S.h(V16_REDUCE);
+    uint32_t n_voice = 0, n_quiet = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)kLegMaxCalls; j++) {
+        if (!((take >> j) & 1u)) continue;
+        int16_t *frame = rows + (size_t)leg_calls_slot(list, j) * packet_stride;
+        uint4 *frame4 = reinterpret_cast<uint4 *>(frame);  // FAST only
+        uint4 raw[FAST ? NV : 1];
+        int r;
+        if constexpr (FAST) {
+#pragma unroll
+            for (int i = 0; i < NV; i++) raw[i] = frame4[i];
+            r = vad_packet<NB, 1>(S, RegSrc<NV>{raw}, hp120, lp120, hp60, lp60);
+        } else {
+            r = vad_packet<NB, 1>(S, MemSrc{frame}, hp120, lp120, hp60, lp60);
+        }
+        if (r == 0) {  // vad_process, src/webrtc.c:118-141: one step of reduce per decision, then the packet >> reduce
+            if (reduce < 4) reduce += 1;
+            n_quiet++;
+        } else {
+            if (reduce > 0) reduce -= 1;
+            n_voice++;
+        }
+        if constexpr (FAST) {
+            auto att = [&](unsigned w) {  // both int16 halves >> reduce (arithmetic)
+                const int lo = (int)(int16_t)(w & 0xffffu) >> reduce, hi = (int)(int16_t)(w >> 16) >> reduce;
+                return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16);
+            };
+#pragma unroll
+            for (int i = 0; i < NV; i++) frame4[i] = make_uint4(att(raw[i].x), att(raw[i].y), att(raw[i].z), att(raw[i].w));
+        } else {
+            for (int i = 0; i < NB; i++) frame[i] = (int16_t)(frame[i] >> reduce);
+        }
+    }
+    S.h(V16_REDUCE) = (int16_t)reduce;
+#pragma unroll
+    for (int f = 0; f < V16_AGE; f++) g16[(size_t)f * n_legs] = r16[f];
+#pragma unroll
+    for (int f = V16_MEAN_VALUE; f < V16_WORDS; f++) g16[(size_t)f * n_legs] = r16[f - kVadMinFields];
+#pragma unroll
+    for (int f = 0; f < V32_WORDS; f++) g32[(size_t)f * n_legs] = r32[f];
+#pragma unroll 8
+    for (int f = 0; f < kVadMinFields; f++) g16[(size_t)(V16_AGE + f) * n_legs] = minlds[f * 64 + lane];
+    if (voice) {
+        voice[leg] += n_voice;
+        voice[(size_t)n_legs + leg] += n_quiet;
+    }
+}
 #ifdef WMX_VAD_PROF
 extern "C" int wmx_debug_vad_prof(unsigned long long *out16, int reset) {
     (void)hipDeviceSynchronize();
@@ -1335,6 +1429,57 @@ int wmx_vad_process(wmx_vad *h, int16_t *d_pcm, int packets_per_call, int n_call
     }
 #undef VAD_LAUNCH
     WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// the legs of a conference bridge, each with the rows this tick brought it (include/wmix_amd.h; vad_legs_kernel)
+int wmx_vad_process_legs(wmx_vad *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                         const uint32_t *d_calls, uint32_t *d_voice, void *stream) {
+    WMX_ON_DEVICE(h);
+    using namespace wmx;
+    if (!h || h->chn != 1 || h->freq != 8000 || h->pkg != kLegRow) {
+        set_error("wmx_vad_process_legs: the handle must be 1 x 8000 with a packet of %d samples (it is %d x %d, %d samples)", kLegRow,
+                  h ? h->chn : 0, h ? h->freq : 0, h ? h->pkg : 0);
+        return WMX_EINVAL;
+    }
+    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls) {
+        set_error("wmx_vad_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kLegMaxCalls);
+        return WMX_EINVAL;
+    }
+    if (packet_stride < kLegRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
+        set_error("wmx_vad_process_legs: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", packet_stride,
+                  kLegRow, leg_stride, max_packets);
+        return WMX_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is
+        set_error("wmx_vad_process_legs: d_pcm %p is not on a 2-byte boundary (the rows are read and written as int16)", (void *)d_pcm);
+        return WMX_EINVAL;
+    }
+    const dim3 grid((unsigned)((h->n_streams + 63) / 64)), block(64);
+    hipStream_t s = as_stream(stream);
+    // every row on a 16-byte boundary: uint4 rows through registers; else sample by sample -- chosen once per launch
+    const bool fast = (leg_stride % 8) == 0 && (packet_stride % 8) == 0 && (reinterpret_cast<uintptr_t>(d_pcm) % 16) == 0;
+    if (fast)
+        hipLaunchKernelGGL(vad_legs_kernel<true>, grid, block, 0, s, h->d_s16, h->d_s32, d_pcm, h->n_streams, leg_stride, packet_stride,
+                           max_packets, d_len, d_calls, d_voice, h->life.d_active);
+    else
+        hipLaunchKernelGGL(vad_legs_kernel<false>, grid, block, 0, s, h->d_s16, h->d_s32, d_pcm, h->n_streams, leg_stride, packet_stride,
+                           max_packets, d_len, d_calls, d_voice, h->life.d_active);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// `reduce` of every stream as the work queued on `stream` leaves it: one copy of the field-major row; blocking
+int wmx_vad_export_reduce(wmx_vad *h, int16_t *host_reduce, void *stream) {
+    WMX_ON_DEVICE(h);
+    using namespace wmx;
+    if (!h || !host_reduce) {
+        set_error("wmx_vad_export_reduce: bad argument");
+        return WMX_EINVAL;
+    }
+    hipStream_t s = as_stream(stream);
+    WMX_HIP(hipMemcpyAsync(host_reduce, h->d_s16 + (size_t)V16_REDUCE * h->n_streams, (size_t)h->n_streams * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    WMX_HIP(hipStreamSynchronize(s));
     return 0;
 }
 
