@@ -1,8 +1,9 @@
 """The conference handle (wmix_amd/conf.py) and the C example (examples/host_conf.c) as the tests run them, and the one comparison of
 a handle with its composed replay.
 
-The rule of the family -- tests/conf_replay_model.py, every leg_*_model.py, conf_inputs.py, conf_stories.py, conf_single_replays.py,
-this module, and the test modules of the conference handle -- is that none of them imports a module named test_*.  A new stage is one
+The rule of the family -- tests/conf_replay_model.py, every leg_*_model.py (leg_rows_model.py holds the row walk they share),
+leg_stage_inputs.py, leg_gate_inputs.py, legs_kernel_harness.py, conf_inputs.py, conf_stories.py, conf_single_replays.py, this module,
+and the test modules of the conference handle and of the stages' kernels -- is that none of them imports a module named test_*.  A new stage is one
 setter and one line in ConfReplay.tick, one story in conf_stories.py, and one test module that imports support modules only."""
 import json
 import os
@@ -109,11 +110,12 @@ def expected(key, lib, n, max_packets, story):
 
 def handle_equals_replay(e, slots, mode):
     """the handle over the story of e = expected(...) against the replay: every datagram of every tick; speaking and env after every
-    tick; head, tick and dropped at the end, every field of export_sequence, export_conceal and the three fields of export_codecs.
+    tick; head, tick and dropped at the end, every field of export_sequence, export_conceal, the three fields of export_codecs and the
+    three of export_gate (before the first gate(True) both sides say reduce 4, counts 0).
     -> e, for what the caller asserts of the model"""
     pk, recv, m = e["pk"], e["recv"], e["model"]
-    exports = lambda cb: (cb.export_legs(), cb.export_sequence(), cb.export_conceal(), cb.export_codecs())  # noqa: E731
-    got, seen, (end, sq, concealed, codecs) = handle(recv.shape[1], slots, pk, recv, e["setup"], e["before"], mode, exports)
+    exports = lambda cb: (cb.export_legs(), cb.export_sequence(), cb.export_conceal(), cb.export_codecs(), cb.export_gate())  # noqa: E731
+    got, seen, (end, sq, concealed, codecs, gate) = handle(recv.shape[1], slots, pk, recv, e["setup"], e["before"], mode, exports)
     for t in range(recv.shape[0]):
         for name in ("speaking", "env"):
             assert np.array_equal(seen[t][name], e["legs"][t][name]), (name, "tick", t, seen[t][name], e["legs"][t][name])
@@ -128,4 +130,7 @@ def handle_equals_replay(e, slots, mode):
     want = m.export_codecs()
     for name in ("in_codec", "out_law", "refused"):
         assert np.array_equal(codecs[name], want[name]), (name, codecs[name], want[name])
+    want = m.export_gate()
+    for name in ("reduce", "voiced", "unvoiced"):
+        assert gate[name].dtype == want[name].dtype and np.array_equal(gate[name], want[name]), (name, gate[name], want[name])
     return e

@@ -4,7 +4,7 @@ composed of the models each stage already has, in the order the header states:
     decode by the leg's codec (CodecReplay of tests/leg_oracle_model.py; a refused packet is invisible from here on)
     -> if sequencing is on: tests/leg_seq_model.py, which rewrites the lens and makes the call lists
     -> the stages per leg, each if it is on, each on the rows the one before it left: tests/leg_dtmf_model.py (on the row as it
-       arrived; a suppressed key leaves zeros), tests/leg_denoise_model.py, tests/leg_level_model.py
+       arrived; a suppressed key leaves zeros), tests/leg_denoise_model.py, tests/leg_level_model.py, tests/leg_gate_model.py
     -> if max_speakers > 0: tests/speakers_legs_model.py on the rows as those stages left them and the rewritten lens; the host's mute
        goes in, the mask comes out
     -> the load: sequencing and concealment on: the four rows of tests/leg_plc_model.py, all data, under the mask;
@@ -13,7 +13,8 @@ composed of the models each stage already has, in the order the header states:
 
 State moves only for a stage that is launched: with sequencing off neither the sequence model nor the concealment model is ticked, with
 concealment off the concealment model is not, and a stage per leg that is off is not ticked either.  The leveller's model is made by
-the first level(True, ...), as the handle makes its AGC.  The setters are those of wmix_amd/conf.py, so one story (a function that calls
+the first level(True, ...), as the handle makes its AGC, and the gate's by the first gate(True), as it makes its VAD: before that
+export_gate() says what the handle says, reduce 4 and counts 0.  The setters are those of wmix_amd/conf.py, so one story (a function that calls
 setters, tests/conf_stories.py) drives the handle and this class alike.  This is the only text of the per-tick rule in the tests: a new
 stage is one setter and one line in tick().  Nothing of wmix_amd is imported or read."""
 import numpy as np
@@ -21,6 +22,7 @@ import numpy as np
 from conf_inputs import seq_raw_of
 from leg_denoise_model import LegsDenoiseModel
 from leg_dtmf_model import LegsDtmfModel
+from leg_gate_model import LegsGateModel
 from leg_level_model import LegsLevelModel
 from leg_oracle_model import CodecReplay
 from leg_plc_model import LegsPlcModel
@@ -36,8 +38,9 @@ class ConfReplay:
         self.layout, self.host_mute = [], None
         self.max_speakers, self.floor, self.decay_shift = 0, 0, 3
         self.seq_on, self.max_gap, self.conceal_on = False, 3, False
-        self.keys, self.dn, self.lv = LegsDtmfModel(n_legs), LegsDenoiseModel(lib, n_legs), None
+        self.keys, self.dn, self.lv, self.gt = LegsDtmfModel(n_legs), LegsDenoiseModel(lib, n_legs), None, None
         self.dtmf_on, self.dtmf_suppress, self.dtmf_pt, self.denoise_on, self.level_on, self.level_value = False, False, 101, False, False, None
+        self.gate_on, self.gate_seen = False, []  # export_gate() behind every tick
         self.levels = []  # of every row the selection was shown, as it was shown it: for a story's choice of floor
         self.lists = [[] for _ in range(n_legs)]  # the call lists of the last tick in which the sequencer ran: for the tests' reach
         self.load_mute = None  # what the last tick's load was given
@@ -81,13 +84,19 @@ class ConfReplay:
     def set_leg_gain(self, legs, value):
         self.lv.set_gain(value, legs)
 
+    def gate(self, on):
+        if on and self.gt is None:
+            self.gt = LegsGateModel(self.lib, self.n)
+        self.gate_on = bool(on)
+
     def reset_legs(self, legs=None):
-        """a new call in a used slot: cursor, dropped, env, ring, sender, sequence state, refused, concealment state, keypad, suppressor
-        and AGC; the codec and the leg's gain stay"""
+        """a new call in a used slot: cursor, dropped, env, ring, sender, sequence state, refused, concealment state, keypad, suppressor,
+        AGC and gate (shut, its counts zero); the codec and the leg's gain stay"""
         legs = list(range(self.n) if legs is None else legs)
         self.rp.fresh(legs)
-        for model in (self.spk, self.seq, self.plc, self.keys, self.dn) + (() if self.lv is None else (self.lv,)):
-            model.reset(legs)
+        for model in (self.spk, self.seq, self.plc, self.keys, self.dn, self.lv, self.gt):
+            if model is not None:
+                model.reset(legs)
 
     # ---- one tick
     def tick(self, pk_t, recv_t):
@@ -104,6 +113,8 @@ class ConfReplay:
             self.dn.tick(pcm, heard, lists)
         if self.level_on:  # directly behind the suppressor
             self.lv.tick(pcm, heard, lists)
+        if self.gate_on:  # directly behind the leveller
+            self.gt.tick(pcm, heard, lists)
         self.levels += [int(np.abs(pcm[g, k, :160].astype(np.int64)).sum()) for g, k in np.argwhere(heard == 320)]
         mute = self.host_mute
         if self.max_speakers > 0:
@@ -117,7 +128,9 @@ class ConfReplay:
         else:
             load, rlens = pcm, lens
         self.load_mute = None if mute is None else np.array(mute, np.uint8)
-        return self.rp.tick(load, rlens, self.layout, mute)
+        out = self.rp.tick(load, rlens, self.layout, mute)
+        self.gate_seen.append(self.export_gate())
+        return out
 
     # ---- what the handle exports
     def export_legs(self):
@@ -129,6 +142,11 @@ class ConfReplay:
 
     def export_conceal(self):
         return self.plc.export()["concealed"]
+
+    def export_gate(self):
+        if self.gt is None:
+            return {"reduce": np.full(self.n, 4, np.uint8), "voiced": np.zeros(self.n, np.uint32), "unvoiced": np.zeros(self.n, np.uint32)}
+        return self.gt.export()
 
     def export_codecs(self):
         return {"in_codec": np.array(self.rp.in_codec, np.uint8), "out_law": np.array(self.rp.out_law, np.uint8), "refused": self.rp.refused.copy()}

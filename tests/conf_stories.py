@@ -234,13 +234,17 @@ def sizes_story():
     return setup, None
 
 
-# ---- the stages per leg: denoise and level
-def turn_on(c, stage):
-    c.denoise(True) if stage == "denoise" else c.level(True, VALUE)
+# ---- the stages per leg: denoise, level and gate
+def turn_on(c, stage, on=True):
+    c.level(on, VALUE) if stage == "level" else getattr(c, stage)(on)
+
+
+def plain_setup(c):
+    c.set_conferences(LAYOUT)
 
 
 def alone(stage):
-    """the plain script with one stage per leg on: "denoise" or "level" """
+    """the plain script with one stage per leg on from the first tick: "denoise", "level" or "gate" """
     def setup(c):
         c.set_conferences(LAYOUT)
         turn_on(c, stage)
@@ -248,9 +252,10 @@ def alone(stage):
     return arrivals(SEED, T, G) + (setup, None)
 
 
-def everything(lib, impaired=True, level=None, floor_from=None):
+def everything(lib, impaired=True, level=None, floor_from=None, gate=False):
     """the all-stages story with a key pressed in it, dtmf(True, True, 101) and denoise(True); level None: no more (the story of the
-    denoise tests), True / False: level(level, VALUE) behind them.  The floor: four in ten of the rows the selection is shown -- cleaned
+    denoise tests), True / False: level(level, VALUE) behind them; gate: gate(True) behind those, with the floor of the story without it.
+    The floor: four in ten of the rows the selection is shown -- cleaned
     rows, levelled rows -- lie below it in the replay of the story itself, or of the story with level = floor_from."""
     script = retyped(with_key(clean_script(2)), {2: CODEC_AT})
     if impaired:
@@ -259,7 +264,7 @@ def everything(lib, impaired=True, level=None, floor_from=None):
     gap_behind(script, 8, RESET8_AT)
     pk, recv = rows_of(script)
 
-    def story(floor, level):
+    def story(floor, level, gate=False):
         # codecs, sequence, conceal, speakers(2, floor); mutes, a leg that leaves, joins elsewhere, changes its codec; two resets
         setup0, before = all_stages(floor)
 
@@ -269,25 +274,26 @@ def everything(lib, impaired=True, level=None, floor_from=None):
             c.denoise(True)
             if level is not None:
                 c.level(level, VALUE)
+            if gate:
+                c.gate(True)
 
         return setup, before
 
     shown = replay_story(lib, G, K, pk, recv, *story(0, level if floor_from is None else floor_from))[2].levels
-    return (pk, recv) + story(int(np.percentile(shown, 40)), level)
+    return (pk, recv) + story(int(np.percentile(shown, 40)), level, gate)
+
+
+ON_AT, RESET_ON_AT, RESET_ON_LEG, OFF_AT, RESET_OFF_AT, RESET_OFF_LEG, ON_AGAIN_AT = 8, 16, 1, 22, 26, 6, 30
 
 
 def switched(stage):
-    """the stage on at tick 8 (level: legs 1 and 6 get a gain of their own at 12); leg 1 a new call at 16; off at 22; leg 6 reset at 26
-    while the stage is off; on again at 30"""
-    def setup(c):
-        c.set_conferences(LAYOUT)
-
-    before = {8: lambda c: turn_on(c, stage), 16: lambda c: c.reset_legs([1]),
-              22: lambda c: c.denoise(False) if stage == "denoise" else c.level(False),
-              26: lambda c: c.reset_legs([6]), 30: lambda c: turn_on(c, stage)}
+    """the stage on at tick 8 (level: legs 1 and 6 get a gain of their own at 12); leg 1 a new call at 16 while it is on; off at 22; leg 6
+    reset at 26 while the stage is off; on again at 30"""
+    before = {ON_AT: lambda c: turn_on(c, stage), RESET_ON_AT: lambda c: c.reset_legs([RESET_ON_LEG]), OFF_AT: lambda c: turn_on(c, stage, False),
+              RESET_OFF_AT: lambda c: c.reset_legs([RESET_OFF_LEG]), ON_AGAIN_AT: lambda c: turn_on(c, stage)}
     if stage == "level":
         before[12] = lambda c: c.set_leg_gain([1, 6], 9)
-    return arrivals(SEED, T, G) + (setup, before)
+    return arrivals(SEED, T, G) + (plain_setup, before)
 
 
 def regained():

@@ -1,12 +1,11 @@
 """What the tests of the per-leg voice-activity gate feed the kernel and its model: the alternating-spurts signal and the ragged script
-of tests/test_vad_legs_gpu.py.  numpy, tests/conf_inputs.py's signals and the row schedule of tests/test_nsx_legs_gpu.py only: no
+of tests/test_vad_legs_gpu.py.  numpy, tests/conf_inputs.py's signals and the row schedule of tests/leg_stage_inputs.py only: no
 oracle, no GPU, nothing of wmix_amd."""
 import numpy as np
 
 from conf_inputs import alaw_decode, voiced
-from test_nsx_legs_gpu import OTHER_LENS, random_list
+from leg_stage_inputs import OTHER_LENS, ROW, random_list
 
-ROW = 160
 N, TICKS = 70, 40          # one full workgroup and one of 6 lanes
 SPURT = 25                 # rows of noise, then as many of noise plus voice
 QUIET_LEG, NOISE_LEG, CODES_LEG = 3, 10, 17

@@ -13,9 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from leg_level_model import rows_taken
-
-ROW = 160
+from leg_rows_model import ROW, legs_fed
 
 
 class OrcVadCore(C.Structure):  # orc_vad_core, oracle/orc_vad.h
@@ -90,11 +88,9 @@ class LegsGateModel:
 
     def tick(self, pcm, lens, lists=None):
         """pcm int16 [n, K, >= 160] (rewritten in place), lens [n, K], lists: None or per leg the call list -> per leg the slots fed"""
-        fed = []
-        for g in range(len(self.h)):
-            fed.append(rows_taken(lens[g], None if lists is None else lists[g]))
-            assert len(set(fed[g])) == len(fed[g]), "a call list names a slot twice"
-            for slot in fed[g]:
+        fed = legs_fed(lens, lists)
+        for g, slots in enumerate(fed):
+            for slot in slots:
                 pcm[g][slot][:ROW] = self.feed(g, pcm[g][slot])
         return fed
 

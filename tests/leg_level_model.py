@@ -1,25 +1,16 @@
 """A model of the bridge's per-leg gain control (wmx_agc_process_legs), written from the text in include/wmix_amd.h: per leg the ordered
 rows fed so far and the leg's compression gain; per tick the leg's PCM rows, lens and, with sequencing, the call list.  The rows a
-leg's load will consume -- without a list the slots with len == 320 in slot order, with one the list's data calls that name such a
-slot, in list order; a silence call feeds nothing -- are appended to the leg's history and the oracle's AGC (oracle/orc_agc.c, 1 x 8000,
-80 frames a call: two calls a row) is run over the whole history from a fresh handle: the last rows of its output are the tick's
+leg's load will consume (rows_taken of tests/leg_rows_model.py, whose history-based tick this model shares) are appended to the
+leg's history and the oracle's AGC (oracle/orc_agc.c, 1 x 8000, 80 frames a call: two calls a row) is run over the whole history from a fresh handle: the last rows of its output are the tick's
 levelled rows.  The outputs of a prefix do not depend on what follows, so running again from the start each tick is the stream a
 persistent AGC produces.  A leg's gain that changed on the way (agc_addition) is replayed in front of the call it was in force from.
 Nothing of wmix_amd is imported or read."""
 import numpy as np
 
+from leg_rows_model import ROW, LegsHistoryModel
 from oracle import loader as L
 
-ROW = 160
 CALLS_PER_ROW = 2  # the AGC's packet at 8 kHz is 80 samples
-
-
-def rows_taken(lens, calls=None):
-    """the slots of one leg whose rows are fed this tick, in feeding order.  lens [K]; calls None or [("D", slot) / ("S", None)]"""
-    n_slots = len(lens)
-    if calls is None:
-        return [k for k in range(n_slots) if int(lens[k]) == 320]
-    return [slot for kind, slot in calls[:4] if kind == "D" and slot < n_slots and int(lens[slot]) == 320]
 
 
 def level(lib, rows, value, additions=None):
@@ -34,12 +25,11 @@ def level(lib, rows, value, additions=None):
     return L.run_agc_handle(lib, 1, 8000, int(value), rows.reshape(-1), 80, additions=add, prefix="orc").reshape(-1, ROW)
 
 
-class LegsLevelModel:
+class LegsLevelModel(LegsHistoryModel):
     """n legs; tick() takes what the ingest, the sequencer, the DTMF stage and the denoiser left and leaves what the kernel leaves"""
 
     def __init__(self, lib, n, value):
-        self.lib = lib
-        self.history = [[] for _ in range(n)]
+        super().__init__(lib, n)
         self.first = [int(value)] * n                # the gain the leg's handle was made with (agc_init)
         self.gain = [int(value)] * n                 # the gain in force
         self.additions = [{} for _ in range(n)]      # {rows fed before it: value}
@@ -55,15 +45,5 @@ class LegsLevelModel:
         for g in (range(len(self.history)) if legs is None else legs):
             self.history[g], self.additions[g], self.first[g] = [], {}, self.gain[g]
 
-    def tick(self, pcm, lens, lists=None):
-        """pcm int16 [n, K, >= 160] (rewritten in place), lens [n, K], lists: None or per leg the call list -> per leg the slots fed"""
-        fed = []
-        for g, history in enumerate(self.history):
-            fed.append(rows_taken(lens[g], None if lists is None else lists[g]))
-            assert len(set(fed[g])) == len(fed[g]), "a call list names a slot twice"
-            if fed[g]:
-                history += [np.array(pcm[g][slot][:ROW], np.int16) for slot in fed[g]]
-                out = level(self.lib, history, self.first[g], self.additions[g])[-len(fed[g]):]
-                for slot, row in zip(fed[g], out):
-                    pcm[g][slot][:ROW] = row
-        return fed
+    def run(self, g):
+        return level(self.lib, self.history[g], self.first[g], self.additions[g])

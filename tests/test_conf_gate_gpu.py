@@ -1,17 +1,18 @@
 """wmx_conf_gate (wmix_amd/csrc/conf.hip) through the Python mirror: the conference bridge with every leg's rows going through the leg's
-own voice-activity gate.  The replay is ConfGateReplay of tests/conf_gate_replay.py -- ConfReplay with tests/leg_gate_model.py where
+own voice-activity gate.  The replay is ConfReplay of tests/conf_replay_model.py, which ticks tests/leg_gate_model.py where
 include/wmix_amd.h places the stage: directly behind the AGC and in front of the selection, the concealment and the load, which see the
-gated rows.  Layout, K = 3 and the scripts are those of tests/conf_inputs.py, the runner and the handle / replay comparison those of
+gated rows; the stories are those of tests/conf_stories.py.  Layout, K = 3 and the scripts are those of tests/conf_inputs.py, the runner and the handle / replay comparison those of
 tests/conf_harness.py: every datagram of every tick and speaking / env after every tick are compared, and at the end head, tick and
 dropped and what the sequencer, the concealment and the codecs export; export_gate is compared after every tick.  Bytes and integers,
 np.array_equal."""
 import numpy as np
 import pytest
 
-from conf_gate_replay import (ConfGateReplay, OFF_AT, ON_AGAIN_AT, ON_AT, RESET_OFF_AT, RESET_OFF_LEG, RESET_ON_AT, RESET_ON_LEG, every_stage, expected, gate_alone,
-                              plain_setup, replay_story, switched)
-from conf_harness import MODES, bridge, handle, handle_equals_replay, run
+from conf_harness import MODES, bridge, expected, handle, handle_equals_replay, run
 from conf_inputs import EINVAL, G, K, KEY_LEG, SEED, T, arrivals, noise_script, ulaw_decode
+from conf_replay_model import ConfReplay, replay_story
+from conf_stories import (OFF_AT, ON_AGAIN_AT, ON_AT, RESET_OFF_AT, RESET_OFF_LEG, RESET_ON_AT, RESET_ON_LEG, alone, everything, plain_setup,
+                          switched)
 from leg_codec_model import LAW_U, PCMU
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def gate_equals(got, want, where):
 # ---- a. the gate alone
 @pytest.mark.parametrize("slots,mode", MODES)
 def test_gate_alone(cuda, oracle_port, slots, mode):
-    e = handle_equals_replay(expected("alone", oracle_port, G, K, gate_alone), slots, mode)
+    e = handle_equals_replay(expected("gate alone", oracle_port, G, K, lambda: alone("gate")), slots, mode)
     pk, recv, want, m = e["pk"], e["recv"], e["want"], e["model"]
     plain, _, _ = replay_story(oracle_port, G, K, pk, recv, plain_setup)
     # the oracle on random codes: a call's first four rows are attenuated (reduce 4, 3, 2, 1), from the fifth on the gate is open
@@ -45,20 +46,20 @@ def test_gate_alone(cuda, oracle_port, slots, mode):
 # ---- b. every stage on, on the impaired schedule
 @pytest.mark.parametrize("slots,mode", MODES)
 def test_every_stage_on(cuda, oracle_port, slots, mode):
-    e = handle_equals_replay(expected("everything", oracle_port, G, K, lambda: every_stage(oracle_port)), slots, mode)
+    e = handle_equals_replay(expected("gate everything", oracle_port, G, K, lambda: everything(oracle_port, True, True, gate=True)), slots, mode)
     m, st = e["model"], e["model"].export_sequence()
     assert m.keys.export()["count"][KEY_LEG] >= 1 and m.export_conceal().sum() >= 1 and not m.export_legs()["dropped"].any()
     assert st["lost"].any() and st["late"].any() and st["dup"].any()
     assert m.level_on and m.denoise_on and m.gate_on and m.gt.voiced.all()
     # the same story with the gate off sends other bytes
-    off = expected("everything off", oracle_port, G, K, lambda: every_stage(oracle_port, gate=False))
+    off = expected(("level", "everything"), oracle_port, G, K, lambda: everything(oracle_port, True, True))  # the level tests' replay
     assert np.array_equal(off["pk"], e["pk"]) and off["model"].gt is None and not np.array_equal(off["want"], e["want"])
 
 
 # ---- c. the gate switched on a running handle, a leg reset while it is on and one while it is off
 @pytest.mark.parametrize("slots,mode", MODES)
 def test_gate_switched_on_a_running_handle_and_reset_legs(cuda, oracle_port, slots, mode):
-    e = handle_equals_replay(expected("switched", oracle_port, G, K, switched), slots, mode)
+    e = handle_equals_replay(expected("gate switched", oracle_port, G, K, lambda: switched("gate")), slots, mode)
     pk, recv, before, want, m = e["pk"], e["recv"], e["before"], e["want"], e["model"]
     resets = {t: f for t, f in before.items() if t in (RESET_ON_AT, RESET_OFF_AT)}
     plain, _, _ = replay_story(oracle_port, G, K, pk, recv, plain_setup, resets)
@@ -84,10 +85,10 @@ def test_gate_switched_on_a_running_handle_and_reset_legs(cuda, oracle_port, slo
 # ---- d. export_gate after every tick
 @pytest.mark.parametrize("slots,mode", MODES)
 def test_export_gate_equals_the_model_after_every_tick(cuda, oracle_port, slots, mode):
-    e = expected("switched", oracle_port, G, K, switched)
+    e = expected("gate switched", oracle_port, G, K, lambda: switched("gate"))
     cb, seen = bridge(G, slots, None), []
     e["setup"](cb)
-    gate_equals(cb.export_gate(), ConfGateReplay(oracle_port, G, K).export_gate(), "before the first switch-on")
+    gate_equals(cb.export_gate(), ConfReplay(oracle_port, G, K).export_gate(), "before the first switch-on")
     got = run(cb, e["pk"], e["recv"], mode, before=e["before"], after=lambda t, c: seen.append(c.export_gate()))
     cb.close()
     assert np.array_equal(got, e["want"])

@@ -8,7 +8,7 @@ import pytest
 from conf_inputs import G, SEED, T, alaw_decode, arrivals, ulaw_decode, ulaw_encode
 from leg_gate_inputs import CASES, CODES_LEG, LAST_GROUP, N, NOISE_LEG, QUIET_LEG, ROW, TICKS, case_seed, leg_signal, script, spurts
 from leg_gate_model import LegsGateModel, gate, was_voice
-from leg_level_model import rows_taken
+from leg_rows_model import rows_taken
 from oracle import loader as L
 
 

@@ -332,67 +332,43 @@ def legs_against_conf(reps, freq=8000):
             "ratio_steady_over_conf": round(b["median_ms"] / a["median_ms"], 3), "ratio_jitter_over_conf": round(c["median_ms"] / a["median_ms"], 3)}
 
 
-def denoise_kernel(legs, reps):
-    """wmx_nsx_process_legs beside wmx_nsx_process on the same rows: device milliseconds per launch"""
-    from wmix_amd.nsx import NsxBatch
-    rng = np.random.default_rng(17)
-    noise = np.clip(np.round(rng.normal(0, 400, (legs, 160))), -32768, 32767).astype(np.int16)
-    src = torch.from_numpy(noise).cuda()
-    every, sparse_of = torch.full((legs, 3), 0, dtype=torch.int32, device="cuda"), torch.full((legs, 3), 0, dtype=torch.int32, device="cuda")
-    every[:, 0] = 320
-    sparse_of[::8, 0] = 320
-    handles = [NsxBatch(legs, 1, 8000) for _ in range(4)]
-    dense_rows = [torch.zeros((legs, 2, 80), dtype=torch.int16, device="cuda") for _ in range(2)]
-    leg_rows = [torch.zeros((legs, 3, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
-
-    def dense(k):
-        return (lambda: dense_rows[k].view(legs, 160).copy_(src)), (lambda: handles[k].process(dense_rows[k]))
-
-    def ragged(k, lens):
-        return (lambda: leg_rows[k][:, 0].copy_(src)), (lambda: handles[2 + k].process_legs(leg_rows[k], lens))
-
-    sides = [dense(0), ragged(0, every), dense(1), ragged(1, sparse_of)]
-    for prepare, f in sides * 20:
-        prepare()
-        f()
-    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for _ in sides]
-    for r in range(reps):
-        for k, (prepare, f) in enumerate(sides):
-            prepare()
-            ev[k][r][0].record()
-            f()
-            ev[k][r][1].record()
-    torch.cuda.synchronize()
-    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
-    d0, full, d1, sparse = (stats([a.elapsed_time(b) for a, b in side]) for side in ev)
-    for h in handles:
-        h.close()
-    return {"legs": legs, "rows_per_leg": 1, "blocks_per_row": 2, "wmx_nsx_process_dense": d0, "wmx_nsx_process_dense_again": d1,
-            "wmx_nsx_process_legs_every_leg": full, "wmx_nsx_process_legs_one_leg_in_eight": sparse,
-            "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4), "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4),
-            "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
-
-
-def level_kernel(legs, reps, value, rows=1):
-    """wmx_agc_process_legs beside wmx_agc_process on the same rows, `rows` (1 .. 3) per leg: device milliseconds per launch"""
+def stage_kernel(stage, legs, reps, value=None, rows=1):
+    """A per-leg stage's ragged entry point beside its dense one on the same rows, `rows` (1 .. 3) per leg: device milliseconds per launch.
+    stage "denoise": wmx_nsx_process_legs beside wmx_nsx_process, on noise; "level": wmx_agc_process_legs beside wmx_agc_process with the
+    compression gain `value`, on voiced rows; "gate": wmx_vad_process_legs beside wmx_vad_process (1 x 8000, 20 ms, one call of one packet:
+    its four-wave pipeline kernel), on voiced rows.  The dense side twice in every repetition, so that its own run-to-run spread stands
+    beside the difference; then with one leg in eight sending.  Every side's rows are put back in front of every call, outside the timed
+    region: a row gated over and over is silence."""
     from wmix_amd.agc import AgcBatch
-    rng = np.random.default_rng(17)
-    t = np.arange(160 * rows)
-    voiced = rng.integers(300, 12000, (legs, 1)) * np.sin(2 * np.pi * rng.integers(150, 1500, (legs, 1)) * t / 8000) + rng.normal(0, 100, (legs, 160 * rows))
-    src = torch.from_numpy(np.clip(np.round(voiced), -32768, 32767).astype(np.int16)).cuda()
-    every, sparse_of = torch.full((legs, 3), 0, dtype=torch.int32, device="cuda"), torch.full((legs, 3), 0, dtype=torch.int32, device="cuda")
+    from wmix_amd.nsx import NsxBatch
+    from wmix_amd.vad import VadBatch
+    # the batch, the dense plane's [packets, samples] of a leg, the seed, what stands between "legs" and the timings, what process_legs takes more
+    make, dense_shape, seed, head, extras = {
+        "denoise": (lambda: NsxBatch(legs, 1, 8000), (2 * rows, 80), 17, {"rows_per_leg": rows, "blocks_per_row": 2}, ()),
+        "level": (lambda: AgcBatch(legs, 1, 8000, value), (2 * rows, 80), 17, {"value": value, "rows_per_leg": rows, "packets_per_row": 2}, ()),
+        "gate": (lambda: VadBatch(legs, 1, 8000, 20), (rows, 160), 19, {"rows_per_leg": rows},
+                 (None, torch.zeros((2, legs), dtype=torch.int32, device="cuda"))),
+    }[stage]
+    name = {"denoise": "wmx_nsx_process", "level": "wmx_agc_process", "gate": "wmx_vad_process"}[stage]
+    rng = np.random.default_rng(seed)
+    if stage == "denoise":
+        x = rng.normal(0, 400, (legs, 160 * rows))
+    else:
+        t = np.arange(160 * rows)
+        x = rng.integers(300, 12000, (legs, 1)) * np.sin(2 * np.pi * rng.integers(150, 1500, (legs, 1)) * t / 8000) + rng.normal(0, 100, (legs, 160 * rows))
+    src = torch.from_numpy(np.clip(np.round(x), -32768, 32767).astype(np.int16)).cuda()
+    every, sparse_of = torch.zeros((legs, 3), dtype=torch.int32, device="cuda"), torch.zeros((legs, 3), dtype=torch.int32, device="cuda")
     every[:, :rows] = 320
     sparse_of[::8, :rows] = 320
-    handles = [AgcBatch(legs, 1, 8000, value) for _ in range(4)]
-    dense_rows = [torch.zeros((legs, 2 * rows, 80), dtype=torch.int16, device="cuda") for _ in range(2)]
+    handles = [make() for _ in range(4)]
+    dense_rows = [torch.zeros((legs,) + dense_shape, dtype=torch.int16, device="cuda") for _ in range(2)]
     leg_rows = [torch.zeros((legs, 3, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
 
     def dense(k):
         return (lambda: dense_rows[k].view(legs, 160 * rows).copy_(src)), (lambda: handles[k].process(dense_rows[k]))
 
     def ragged(k, lens):
-        return (lambda: leg_rows[k][:, :rows].copy_(src.view(legs, rows, 160))), (lambda: handles[2 + k].process_legs(leg_rows[k], lens))
+        return (lambda: leg_rows[k][:, :rows].copy_(src.view(legs, rows, 160))), (lambda: handles[2 + k].process_legs(leg_rows[k], lens, *extras))
 
     sides = [dense(0), ragged(0, every), dense(1), ragged(1, sparse_of)]
     for prepare, f in sides * 20:
@@ -411,55 +387,8 @@ def level_kernel(legs, reps, value, rows=1):
     d0, full, d1, sparse = (stats([a.elapsed_time(b) for a, b in side]) for side in ev)
     for h in handles:
         h.close()
-    return {"legs": legs, "value": value, "rows_per_leg": rows, "packets_per_row": 2, "wmx_agc_process_dense": d0, "wmx_agc_process_dense_again": d1,
-            "wmx_agc_process_legs_every_leg": full, "wmx_agc_process_legs_one_leg_in_eight": sparse,
-            "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4), "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4),
-            "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
-
-
-def gate_kernel(legs, reps):
-    """wmx_vad_process_legs on one row per leg beside wmx_vad_process (1 x 8000, 20 ms, one call of one packet: its four-wave pipeline
-    kernel) on a dense plane of the same rows: device milliseconds per launch.  The dense side twice in every repetition, so that its
-    own run-to-run spread stands beside the difference; then with one leg in eight sending.  Every side's rows are put back in front of
-    every call, outside the timed region: a row gated over and over is silence."""
-    from wmix_amd.vad import VadBatch
-    rng = np.random.default_rng(19)
-    t = np.arange(160)
-    x = rng.integers(300, 12000, (legs, 1)) * np.sin(2 * np.pi * rng.integers(150, 1500, (legs, 1)) * t / 8000) + rng.normal(0, 100, (legs, 160))
-    src = torch.from_numpy(np.clip(np.round(x), -32768, 32767).astype(np.int16)).cuda()
-    every, sparse_of = torch.zeros((legs, 3), dtype=torch.int32, device="cuda"), torch.zeros((legs, 3), dtype=torch.int32, device="cuda")
-    every[:, 0] = 320
-    sparse_of[::8, 0] = 320
-    handles = [VadBatch(legs, 1, 8000, 20) for _ in range(4)]
-    dense_rows = [torch.zeros((legs, 1, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
-    leg_rows = [torch.zeros((legs, 3, 160), dtype=torch.int16, device="cuda") for _ in range(2)]
-    voice = torch.zeros((2, legs), dtype=torch.int32, device="cuda")
-
-    def dense(k):
-        return (lambda: dense_rows[k].view(legs, 160).copy_(src)), (lambda: handles[k].process(dense_rows[k]))
-
-    def ragged(k, lens):
-        return (lambda: leg_rows[k][:, 0].copy_(src)), (lambda: handles[2 + k].process_legs(leg_rows[k], lens, None, voice))
-
-    sides = [dense(0), ragged(0, every), dense(1), ragged(1, sparse_of)]
-    for prepare, f in sides * 20:
-        prepare()
-        f()
-    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for _ in sides]
-    for r in range(reps):
-        for k, (prepare, f) in enumerate(sides):
-            prepare()
-            ev[k][r][0].record()
-            f()
-            ev[k][r][1].record()
-    torch.cuda.synchronize()
-    assert torch.equal(dense_rows[0].view(legs, 160), leg_rows[0][:, 0]), "the ragged call and the dense call differ"
-    d0, full, d1, sparse = (stats([a.elapsed_time(b) for a, b in side]) for side in ev)
-    for h in handles:
-        h.close()
-    return {"legs": legs, "rows_per_leg": 1, "wmx_vad_process_dense": d0, "wmx_vad_process_dense_again": d1, "wmx_vad_process_legs_every_leg": full,
-            "wmx_vad_process_legs_one_leg_in_eight": sparse, "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4),
+    return {"legs": legs, **head, name + "_dense": d0, name + "_dense_again": d1, name + "_legs_every_leg": full,
+            name + "_legs_one_leg_in_eight": sparse, "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4),
             "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4), "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
 
 
@@ -914,17 +843,17 @@ if __name__ == "__main__":
         args.ragged, args.speakers = False, 0
     if args.gate_kernel > 0:
         res = {"tool": "bridge_bench --gate-kernel", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-               "runs": "the builder's own, one process, the sides alternating", "gate_kernel": gate_kernel(args.gate_kernel, args.reps), "load": [], "tick": None}
+               "runs": "the builder's own, one process, the sides alternating", "gate_kernel": stage_kernel("gate", args.gate_kernel, args.reps), "load": [], "tick": None}
         args.sizes = args.tick = ""
         args.ragged, args.speakers, args.pipe = False, 0, False
     if args.pipe:
         res = {"tool": "bridge_bench --pipe", "device": torch.cuda.get_device_name(0), "reps": args.reps,
                "runs": "the builder's own, one process, the sides alternating", "pipe": conf_pipe(args.reps, args.ulaw_every, args.loss_every, args.denoise, args.steady, args.level)}
         if args.denoise:
-            res["denoise_kernel"] = denoise_kernel(res["pipe"]["legs"], args.reps)
+            res["denoise_kernel"] = stage_kernel("denoise", res["pipe"]["legs"], args.reps)
         if args.level >= 0:
-            res["level_kernel"] = level_kernel(res["pipe"]["legs"], args.reps, args.level)
-            res["level_kernel_three_rows"] = level_kernel(res["pipe"]["legs"], args.reps, args.level, rows=3)
+            res["level_kernel"] = stage_kernel("level", res["pipe"]["legs"], args.reps, args.level)
+            res["level_kernel_three_rows"] = stage_kernel("level", res["pipe"]["legs"], args.reps, args.level, rows=3)
         args.sizes = args.tick = ""
         args.ragged, args.speakers = False, 0
     if args.speakers:

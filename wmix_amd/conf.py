@@ -90,15 +90,19 @@ class ConfBridge:
         selection (wmx_conf_denoise), between submits; off (the default) = the launches of before, and the suppressor's state stays"""
         check(lib().wmx_conf_denoise(self._h, 1 if on else 0), "wmx_conf_denoise")
 
+    def _stage_state(self, getter, prefix, leg):
+        """the stream blob of one leg in the batch `getter` gives (<prefix>_export_stream), None while the handle has none"""
+        L = lib()
+        batch = getattr(L, getter)(self._h)
+        if not batch:
+            return None
+        blob = np.zeros(getattr(L, prefix + "_stream_state_bytes")(batch), np.uint8)
+        check(getattr(L, prefix + "_export_stream")(batch, int(leg), blob.ctypes.data), prefix + "_export_stream")
+        return blob
+
     def denoiser_state(self, leg):
         """the stream blob of one leg's suppressor (wmx_nsx_export_stream on wmx_conf_denoiser), None before the first denoise(True)"""
-        L = lib()
-        nsx = L.wmx_conf_denoiser(self._h)
-        if not nsx:
-            return None
-        blob = np.zeros(L.wmx_nsx_stream_state_bytes(nsx), np.uint8)
-        check(L.wmx_nsx_export_stream(nsx, int(leg), blob.ctypes.data), "wmx_nsx_export_stream")
-        return blob
+        return self._stage_state("wmx_conf_denoiser", "wmx_nsx", leg)
 
     def level(self, on, value=20):
         """every leg's rows go through the leg's own AGC with compression gain `value` dB, directly behind the denoiser and in front of
@@ -108,13 +112,7 @@ class ConfBridge:
 
     def leveller_state(self, leg):
         """the stream blob of one leg's AGC (wmx_agc_export_stream on wmx_conf_leveller), None before the first level(True)"""
-        L = lib()
-        agc = L.wmx_conf_leveller(self._h)
-        if not agc:
-            return None
-        blob = np.zeros(L.wmx_agc_stream_state_bytes(agc), np.uint8)
-        check(L.wmx_agc_export_stream(agc, int(leg), blob.ctypes.data), "wmx_agc_export_stream")
-        return blob
+        return self._stage_state("wmx_conf_leveller", "wmx_agc", leg)
 
     def set_leg_gain(self, legs, value):
         """one leg's volume: agc_addition(value) for the listed legs' AGC (wmx_agc_set_gain_streams on wmx_conf_leveller), between
@@ -135,13 +133,7 @@ class ConfBridge:
 
     def gater_state(self, leg):
         """the stream blob of one leg's VAD (wmx_vad_export_stream on wmx_conf_gater), None before the first gate(True)"""
-        L = lib()
-        vad = L.wmx_conf_gater(self._h)
-        if not vad:
-            return None
-        blob = np.zeros(L.wmx_vad_stream_state_bytes(vad), np.uint8)
-        check(L.wmx_vad_export_stream(vad, int(leg), blob.ctypes.data), "wmx_vad_export_stream")
-        return blob
+        return self._stage_state("wmx_conf_gater", "wmx_vad", leg)
 
     def export_gate(self):
         """dict(reduce: uint8 [n_legs], 0 .. 4; voiced, unvoiced: uint32 [n_legs], the rows judged voice and not) as the work queued on

@@ -339,6 +339,20 @@ __device__ void agc_packet(const AgcRef &S, const GT gain_table, const int16_t *
     }
 }
 
+// A lane's whole state between its field-major rows (g16, g32: the stream's column, n: streams) and its registers
+__device__ __forceinline__ void agc_state_in(int16_t *r16, int32_t *r32, const int16_t *g16, const int32_t *g32, int n) {
+#pragma unroll
+    for (int f = 0; f < A32_WORDS; f++) r32[f] = g32[(size_t)f * n];
+#pragma unroll
+    for (int f = 0; f < A16_WORDS; f++) r16[f] = g16[(size_t)f * n];
+}
+__device__ __forceinline__ void agc_state_out(const int16_t *r16, const int32_t *r32, int16_t *g16, int32_t *g32, int n) {
+#pragma unroll
+    for (int f = 0; f < A32_WORDS; f++) g32[(size_t)f * n] = r32[f];
+#pragma unroll
+    for (int f = 0; f < A16_WORDS; f++) g16[(size_t)f * n] = r16[f];
+}
+
 template <int L, int CHN, bool PS>
 __global__ __launch_bounds__(64) void agc_kernel(int16_t *s16, int32_t *s32, const int32_t *gain_table_g, const uint16_t *__restrict__ stream_table,
                                                  const int16_t *in, int16_t *out, int n_streams, int n_packets, long stream_stride,
@@ -362,19 +376,13 @@ __global__ __launch_bounds__(64) void agc_kernel(int16_t *s16, int32_t *s32, con
     } else {
         int16_t r16[A16_WORDS];
         int32_t r32[A32_WORDS];
-#pragma unroll
-        for (int f = 0; f < A32_WORDS; f++) r32[f] = s32[(size_t)f * n_streams + stream];
-#pragma unroll
-        for (int f = 0; f < A16_WORDS; f++) r16[f] = s16[(size_t)f * n_streams + stream];
+        agc_state_in(r16, r32, s16 + stream, s32 + stream, n_streams);
         const AgcRef S{r16, r32, 1};
         for (int p = 0; p < n_packets; p++) {
             const size_t off = (size_t)stream * stream_stride + (size_t)p * packet_stride;
             agc_packet<L, CHN, GT>(S, gain_table, in + off, out + off, chn_rt);
         }
-#pragma unroll
-        for (int f = 0; f < A32_WORDS; f++) s32[(size_t)f * n_streams + stream] = r32[f];
-#pragma unroll
-        for (int f = 0; f < A16_WORDS; f++) s16[(size_t)f * n_streams + stream] = r16[f];
+        agc_state_out(r16, r32, s16 + stream, s32 + stream, n_streams);
     }
 }
 
@@ -419,10 +427,7 @@ __global__ __launch_bounds__(256, CHN == 1 ? 4 : 2) void agc_pipe_kernel(int16_t
     int32_t r32[A32_WORDS];
     const AgcRef S{r16, r32, 1};
     if (wave == 3) {
-#pragma unroll
-        for (int f = 0; f < A32_WORDS; f++) r32[f] = s32[(size_t)f * n_streams + stream];
-#pragma unroll
-        for (int f = 0; f < A16_WORDS; f++) r16[f] = s16[(size_t)f * n_streams + stream];
+        agc_state_in(r16, r32, s16 + stream, s32 + stream, n_streams);
     }
     auto sample = [](const uint4 (&raw)[VPS], int i) -> int16_t {  // mono sample i of a sub-frame (compile-time i)
         if constexpr (CHN == 1) {
@@ -548,10 +553,7 @@ __global__ __launch_bounds__(256, CHN == 1 ? 4 : 2) void agc_pipe_kernel(int16_t
     }
     if (nk) pass2(n_packets - 1);
     if (wave == 3 && live) {
-#pragma unroll
-        for (int f = 0; f < A32_WORDS; f++) s32[(size_t)f * n_streams + stream] = r32[f];
-#pragma unroll
-        for (int f = 0; f < A16_WORDS; f++) s16[(size_t)f * n_streams + stream] = r16[f];
+        agc_state_out(r16, r32, s16 + stream, s32 + stream, n_streams);
     }
 }
 
@@ -573,7 +575,7 @@ __global__ __launch_bounds__(64) void agc_legs_kernel(int16_t *s16, int32_t *s32
     const int leg = blockIdx.x * 64 + threadIdx.x;
     uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
     if (stream_active(active, leg, n_legs)) {
-        const LegWalk w = leg_calls_walk(len + (size_t)leg * max_packets, calls_in != nullptr, calls_in ? calls_in[leg] : 0u, max_packets);
+        const LegWalk w = leg_calls_walk_leg(len, calls_in, (size_t)leg, max_packets);
         list = w.list, take = w.data;
     }
     if (!__syncthreads_or(take != 0u)) return;  // nobody in this workgroup sent anything
@@ -587,10 +589,7 @@ __global__ __launch_bounds__(64) void agc_legs_kernel(int16_t *s16, int32_t *s32
     const GT gain_table{PS ? gain_lds + threadIdx.x : gain_lds};
     int16_t r16[A16_WORDS];
     int32_t r32[A32_WORDS];
-#pragma unroll
-    for (int f = 0; f < A32_WORDS; f++) r32[f] = s32[(size_t)f * n_legs + leg];
-#pragma unroll
-    for (int f = 0; f < A16_WORDS; f++) r16[f] = s16[(size_t)f * n_legs + leg];
+    agc_state_in(r16, r32, s16 + leg, s32 + leg, n_legs);
     const AgcRef S{r16, r32, 1};
     int16_t *rows = pcm + (size_t)leg * leg_stride;
 #pragma unroll 1
@@ -600,10 +599,7 @@ __global__ __launch_bounds__(64) void agc_legs_kernel(int16_t *s16, int32_t *s32
         int16_t *pkt = rows + (size_t)leg_calls_slot(list, j) * packet_stride + (size_t)(b & 1u) * PKT;
         agc_packet<8, 1, GT>(S, gain_table, pkt, pkt, 1);
     }
-#pragma unroll
-    for (int f = 0; f < A32_WORDS; f++) s32[(size_t)f * n_legs + leg] = r32[f];
-#pragma unroll
-    for (int f = 0; f < A16_WORDS; f++) s16[(size_t)f * n_legs + leg] = r16[f];
+    agc_state_out(r16, r32, s16 + leg, s32 + leg, n_legs);
 }
 
 // idx == nullptr: every stream; else the n_idx listed ones (wmx_agc_reset_streams)
@@ -944,19 +940,7 @@ int wmx_agc_process_legs(wmx_agc *h, int16_t *d_pcm, long leg_stride, long packe
         set_error("wmx_agc_process_legs: the handle must be 1 x 8000 (it is %d x %d)", h ? h->chn : 0, h ? h->freq : 0);
         return WMX_EINVAL;
     }
-    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls) {
-        set_error("wmx_agc_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kLegMaxCalls);
-        return WMX_EINVAL;
-    }
-    if (packet_stride < kLegRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
-        set_error("wmx_agc_process_legs: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", packet_stride,
-                  kLegRow, leg_stride, max_packets);
-        return WMX_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is
-        set_error("wmx_agc_process_legs: d_pcm %p is not on a 2-byte boundary (the rows are read and written as int16)", (void *)d_pcm);
-        return WMX_EINVAL;
-    }
+    if (int rc = legs_rows_check("wmx_agc_process_legs", h->n_streams, d_pcm, leg_stride, packet_stride, max_packets, d_len)) return rc;
     const dim3 grid((unsigned)((h->n_streams + 63) / 64)), block(64);
     hipStream_t s = as_stream(stream);
     if (h->n_off_batch != 0)  // some leg has a compression gain of its own: per-lane tables

@@ -75,6 +75,7 @@ struct wmx_conf {
 // the launches of one tick on rows that are on the device
 static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream) {
     const int K = h->max_packets;
+    const uint32_t *calls = h->seq_on ? h->d_calls : nullptr;  // the stages' order: the sequencer's list, or the slots'
     int rc = wmx_rtp_ingest_legs_codecs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kLegRow, kLegRow, h->d_len,
                                         h->seq_on ? h->d_seq : nullptr, stream);
     if (rc != 0) return rc;
@@ -84,19 +85,19 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
     }
     if (h->dtmf_on) {  // in front of the selection: it and the load must see a suppressed row
         rc = wmx_rtp_detect_dtmf_legs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kLegRow, kLegRow, h->d_len,
-                                      h->seq_on ? h->d_calls : nullptr, h->dtmf_pt, h->dtmf_suppress ? 1 : 0, stream);
+                                      calls, h->dtmf_pt, h->dtmf_suppress ? 1 : 0, stream);
         if (rc != 0) return rc;
     }
     if (h->denoise_on) {  // behind the keypad, which is judged on the row as it arrived; selection, concealment and the load see the cleaned rows
-        rc = wmx_nsx_process_legs(h->nsx, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
+        rc = wmx_nsx_process_legs(h->nsx, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, calls, stream);
         if (rc != 0) return rc;
     }
     if (h->level_on) {  // behind the denoiser: the level detector hears the cleaned row; selection, concealment and the load see the levelled rows
-        rc = wmx_agc_process_legs(h->agc, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, stream);
+        rc = wmx_agc_process_legs(h->agc, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, calls, stream);
         if (rc != 0) return rc;
     }
     if (h->gate_on) {  // behind the leveller: the decision is made on the levelled row; selection, concealment and the load see the gated rows
-        rc = wmx_vad_process_legs(h->vad, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, h->seq_on ? h->d_calls : nullptr, h->d_gate, stream);
+        rc = wmx_vad_process_legs(h->vad, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, calls, h->d_gate, stream);
         if (rc != 0) return rc;
     }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;

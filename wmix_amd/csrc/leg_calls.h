@@ -14,9 +14,13 @@
 // is a block that is not a tone, and neither the noise estimator nor the level detector nor the gate's noise model is fed.  A leg with no call this tick keeps
 // its state.  Every row is taken as the tick brought it.
 //
-// Plain C++ without HIP types: mix.hip, rtp.hip, nsx.hip, agc.hip and vad.hip include it for the device, tools_dev/san/leg_calls_san.cpp
-// compiles it with g++ and tests/test_leg_calls_host.py compares every case with a model written from the text above.
+// Plain C++ without HIP types: mix.hip, rtp.hip, nsx.hip, agc.hip and vad.hip include it for the device (the four kernels that walk a
+// batch's legs -- DTMF in rtp.hip, nsx_legs_kernel, agc_legs_kernel, vad_legs_kernel -- through leg_calls_walk_leg), wmx_internal.h for
+// the argument check the three stages' entry points share (legs_rows_check), tools_dev/san/leg_calls_san.cpp compiles it with g++ and
+// tests/test_leg_calls_host.py compares every case with a model written from the text above; the stage models of the tests take the
+// same rows through rows_taken of tests/leg_rows_model.py.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -87,6 +91,11 @@ WMX_CALLS_FN LegWalk leg_calls_walk(const uint32_t *len, bool have_calls, uint32
     for (uint32_t j = 0; j < (uint32_t)kLegMaxCalls; j++)
         if (j < w.count && !leg_calls_adds_nothing(w.list, j, w.readable)) w.data |= 1u << j;
     return w;
+}
+
+// The walk of leg `leg` of a batch.  len: [n_legs][max_packets]; calls_in: NULL, or one call word per leg.
+WMX_CALLS_FN LegWalk leg_calls_walk_leg(const uint32_t *len, const uint32_t *calls_in, size_t leg, int max_packets) {
+    return leg_calls_walk(len + leg * (size_t)max_packets, calls_in != nullptr, calls_in ? calls_in[leg] : 0u, max_packets);
 }
 
 }  // namespace wmx

@@ -1151,7 +1151,7 @@ __global__ __launch_bounds__((64 * NsxShape<128, 1>::WPB)) __attribute__((amdgpu
     const long s = (long)blockIdx.x * WPB + wave;
     uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
     if (stream_active(active, (int)s, n_legs)) {
-        const LegWalk w = leg_calls_walk(len + s * max_packets, calls_in != nullptr, calls_in ? calls_in[s] : 0u, max_packets);
+        const LegWalk w = leg_calls_walk_leg(len, calls_in, (size_t)s, max_packets);
         list = w.list, take = w.data;
     }
     list = (uint32_t)__builtin_amdgcn_readfirstlane((int)list);
@@ -1383,19 +1383,7 @@ int wmx_nsx_process_legs(wmx_nsx *h, int16_t *d_pcm, long leg_stride, long packe
         set_error("wmx_nsx_process_legs: the handle must be 1 x 8000 (it is %d x %d)", h ? h->chn : 0, h ? h->freq : 0);
         return WMX_EINVAL;
     }
-    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls) {
-        set_error("wmx_nsx_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kLegMaxCalls);
-        return WMX_EINVAL;
-    }
-    if (packet_stride < kLegRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
-        set_error("wmx_nsx_process_legs: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", packet_stride,
-                  kLegRow, leg_stride, max_packets);
-        return WMX_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is
-        set_error("wmx_nsx_process_legs: d_pcm %p is not on a 2-byte boundary (the rows are read and written as int16)", (void *)d_pcm);
-        return WMX_EINVAL;
-    }
+    if (int rc = legs_rows_check("wmx_nsx_process_legs", h->n_streams, d_pcm, leg_stride, packet_stride, max_packets, d_len)) return rc;
     constexpr int WPB = NsxShape<128, 1>::WPB;
     hipLaunchKernelGGL(nsx_legs_kernel, dim3((unsigned)((h->n_streams + WPB - 1) / WPB)), dim3(64 * WPB), 0, as_stream(stream), h->d_state,
                        h->d_hist, h->d_consts, d_pcm, h->n_streams, leg_stride, packet_stride, max_packets, d_len, d_calls, h->overdrive,

@@ -590,7 +590,7 @@ __global__ __launch_bounds__(32 * kDtmfLegsPerBlock) void rtp_detect_dtmf_legs_k
     const bool live = leg < (size_t)n_legs;
     uint32_t list = 0, blocks = 0, quiet = (1u << kLegMaxCalls) - 1u;  // quiet bit j: block j is none, or not to be read
     if (live) {
-        const LegWalk walk = leg_calls_walk(len + leg * (size_t)max_packets, calls_in != nullptr, calls_in ? calls_in[leg] : 0u, max_packets);
+        const LegWalk walk = leg_calls_walk_leg(len, calls_in, leg, max_packets);
         list = walk.list, blocks = walk.count, quiet &= ~walk.data;
     }
     int16_t *rows = pcm + (live ? leg : 0) * (size_t)source_stride;

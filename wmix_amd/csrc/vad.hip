@@ -547,6 +547,49 @@ __device__ __forceinline__ int vad_packet(const VadRef &S, const Src p, LaneBuf 
     return v > 0 ? 1 : v;
 }
 
+// vad_process, src/webrtc.c:118-141: one step of reduce per decision r (0: not voice), then the packet >> reduce
+__device__ __forceinline__ int vad_reduce_step(int reduce, int r) {
+    if (r == 0) {
+        if (reduce < 4) reduce += 1;
+    } else {
+        if (reduce > 0) reduce -= 1;
+    }
+    return reduce;
+}
+// both int16 halves of a packed pair >> reduce (arithmetic)
+__device__ __forceinline__ unsigned vad_att_pair(unsigned w, int reduce) {
+    const int lo = (int)(int16_t)(w & 0xffffu) >> reduce, hi = (int)(int16_t)(w >> 16) >> reduce;
+    return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16);
+}
+__device__ __forceinline__ uint4 vad_att_quad(uint4 v, int reduce) {
+    return make_uint4(vad_att_pair(v.x, reduce), vad_att_pair(v.y, reduce), vad_att_pair(v.z, reduce), vad_att_pair(v.w, reduce));
+}
+
+// A lane's whole state between its field-major rows (g16, g32: the stream's column, n: streams) and the lane: everything but the
+// order statistics in registers, those in the lane's column of minlds.  In: every row requested before the first one is used.
+__device__ __forceinline__ void vad_state_in(int16_t *r16, int32_t *r32, int16_t *minlds, int lane, const int16_t *g16, const int32_t *g32,
+                                             int n) {
+#pragma unroll
+    for (int f = 0; f < V16_AGE; f++) r16[f] = g16[(size_t)f * n];
+#pragma unroll
+    for (int f = V16_MEAN_VALUE; f < V16_WORDS; f++) r16[f - kVadMinFields] = g16[(size_t)f * n];
+#pragma unroll
+    for (int f = 0; f < V32_WORDS; f++) r32[f] = g32[(size_t)f * n];
+#pragma unroll 8
+    for (int f = 0; f < kVadMinFields; f++) minlds[f * 64 + lane] = g16[(size_t)(V16_AGE + f) * n];
+}
+__device__ __forceinline__ void vad_state_out(const int16_t *r16, const int32_t *r32, const int16_t *minlds, int lane, int16_t *g16,
+                                              int32_t *g32, int n) {
+#pragma unroll
+    for (int f = 0; f < V16_AGE; f++) g16[(size_t)f * n] = r16[f];
+#pragma unroll
+    for (int f = V16_MEAN_VALUE; f < V16_WORDS; f++) g16[(size_t)f * n] = r16[f - kVadMinFields];
+#pragma unroll
+    for (int f = 0; f < V32_WORDS; f++) g32[(size_t)f * n] = r32[f];
+#pragma unroll 8
+    for (int f = 0; f < kVadMinFields; f++) g16[(size_t)(V16_AGE + f) * n] = minlds[f * 64 + lane];
+}
+
 // ================================================================== the 10 ms mono packet as a four-wave pipeline
 // vad_kernel above runs a stream in one lane from end to end: 65 536 streams are 1 024 waves, one per SIMD, and the launch
 // lasts as long as one wave's chain of ~9 000 dependent-issue instructions -- 60 % of it the six channels of the GMM
@@ -959,17 +1002,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 80 ? 
         }
         S.h(V16_OVER_HANG) = over_hang;
         S.h(V16_NUM_SPEECH) = num_speech;
-        int reduce = S.h(V16_REDUCE);
-        if (vadflag == 0) {
-            if (reduce < 4) reduce += 1;
-        } else {
-            if (reduce > 0) reduce -= 1;
-        }
+        const int reduce = vad_reduce_step(S.h(V16_REDUCE), vadflag);
         S.h(V16_REDUCE) = (int16_t)reduce;
-        auto att = [&](unsigned w) {  // both int16 halves >> reduce (arithmetic)
-            const int lo = (int)(int16_t)(w & 0xffffu) >> reduce, hi = (int)(int16_t)(w >> 16) >> reduce;
-            return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16);
-        };
         // mono: >> 0 leaves the packet as it is, and vad_process works in place: nothing to fetch or store.  Two channels: the packet
         // always comes back as the mean on both channels (src/webrtc.c:145-150), attenuated or not.
         if (live && it == 0 && (CHN == 2 || reduce != 0)) {
@@ -990,7 +1024,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB == 80 ? 
 #pragma unroll
                 for (int j = 0; j < NVC; j++)
                     frame4[j0 + j] = CHN == 2 ? make_uint4(dup(again[j].x), dup(again[j].y), dup(again[j].z), dup(again[j].w))
-                                              : make_uint4(att(again[j].x), att(again[j].y), att(again[j].z), att(again[j].w));
+                                              : vad_att_quad(again[j], reduce);
             }
             // the next analysis of this call reads what this very lane has just stored: the stores must have left the wave, nothing more
             // (a workgroup-scope fence; the agent-scope __threadfence() that stood here is a cache write-back per packet and workgroup)
@@ -1025,12 +1059,11 @@ __global__ __launch_bounds__(64) void vad_kernel(int16_t *s16, int32_t *s32, int
     int16_t r16[kVadRegFields];
     int32_t r32[V32_WORDS];
     const VadRef S{r16, r32, minlds + lane};
-    const int16_t *g16 = s16 + stream;
-    const int32_t *g32 = s32 + stream;
 #ifdef WMX_VAD_PROF
     if (threadIdx.x == 0) g_t_prev = clock64();
 #endif
-    // state in: every row requested before the first one is used (coalesced: field-major rows)
+    const int16_t *g16 = s16 + stream;
+    const int32_t *g32 = s32 + stream;
 #pragma unroll
     for (int f = 0; f < V16_AGE; f++) r16[f] = g16[(size_t)f * n_streams];
 #pragma unroll
@@ -1071,17 +1104,9 @@ __global__ __launch_bounds__(64) void vad_kernel(int16_t *s16, int32_t *s32, int
             int reduce = S.h(V16_REDUCE);
             VAD_PROF(1);  // packet in (issue only: the loads are consumed inside the first loop)
             const int r = vad_packet<NB, RATIO>(S, RegSrc<NV>{raw}, hp120, lp120, hp60, lp60);
-            if (r == 0) {
-                if (reduce < 4) reduce += 1;
-            } else {
-                if (reduce > 0) reduce -= 1;
-            }
-            auto att = [&](unsigned w) {  // both int16 halves >> reduce (arithmetic)
-                const int lo = (int)(int16_t)(w & 0xffffu) >> reduce, hi = (int)(int16_t)(w >> 16) >> reduce;
-                return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16);
-            };
+            reduce = vad_reduce_step(reduce, r);
 #pragma unroll
-            for (int j = 0; j < NV; j++) frame4[j] = make_uint4(att(raw[j].x), att(raw[j].y), att(raw[j].z), att(raw[j].w));
+            for (int j = 0; j < NV; j++) frame4[j] = vad_att_quad(raw[j], reduce);
             S.h(V16_REDUCE) = (int16_t)reduce;
             VAD_PROF(7);  // hangover + attenuate + packet out
         }
@@ -1100,11 +1125,7 @@ __global__ __launch_bounds__(64) void vad_kernel(int16_t *s16, int32_t *s32, int
         int reduce = S.h(V16_REDUCE);
         for (int it = 0; it < packets_per_call; it++) {
             const int r = vad_packet<NB, RATIO>(S, MemSrc{frame}, hp120, lp120, hp60, lp60);  // always packet 0 (quirk 1)
-            if (r == 0) {
-                if (reduce < 4) reduce += 1;
-            } else {
-                if (reduce > 0) reduce -= 1;
-            }
+            reduce = vad_reduce_step(reduce, r);
             if (it == 0)  // for (cReduce = cLen; cReduce < pkgFrame; ...) only covers anything when cLen == 0
                 for (int i = 0; i < PKG; i++) frame[i] = (int16_t)(frame[i] >> reduce);
         }
@@ -1153,7 +1174,7 @@ __global__ __launch_bounds__(64) void vad_legs_kernel(int16_t *s16, int32_t *s32
     const int leg = blockIdx.x * 64 + lane;
     uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
     if (stream_active(active, leg, n_legs)) {
-        const LegWalk w = leg_calls_walk(len + (size_t)leg * max_packets, calls_in != nullptr, calls_in ? calls_in[leg] : 0u, max_packets);
+        const LegWalk w = leg_calls_walk_leg(len, calls_in, (size_t)leg, max_packets);
         list = w.list, take = w.data;
     }
     // no stream, one that is switched off, or a leg without a row: state and rows untouched.  Nothing here is staged for the workgroup
@@ -1162,16 +1183,7 @@ __global__ __launch_bounds__(64) void vad_legs_kernel(int16_t *s16, int32_t *s32
     int16_t r16[kVadRegFields];
     int32_t r32[V32_WORDS];
     const VadRef S{r16, r32, minlds + lane};
-    int16_t *g16 = s16 + leg;
-    int32_t *g32 = s32 + leg;
-#pragma unroll
-    for (int f = 0; f < V16_AGE; f++) r16[f] = g16[(size_t)f * n_legs];
-#pragma unroll
-    for (int f = V16_MEAN_VALUE; f < V16_WORDS; f++) r16[f - kVadMinFields] = g16[(size_t)f * n_legs];
-#pragma unroll
-    for (int f = 0; f < V32_WORDS; f++) r32[f] = g32[(size_t)f * n_legs];
-#pragma unroll 8
-    for (int f = 0; f < kVadMinFields; f++) minlds[f * 64 + lane] = g16[(size_t)(V16_AGE + f) * n_legs];
+    vad_state_in(r16, r32, minlds, lane, s16 + leg, s32 + leg, n_legs);
     const LaneBuf hp120{lds + lane}, lp120{lds + lane + 64 * (NB / 2)}, hp60{lds + lane + 64 * NB}, lp60{lds + lane + 64 * (NB + NB / 4)};
     int16_t *rows = pcm + (size_t)leg * leg_stride;
     int reduce = S.h(V16_REDUCE);
@@ -1190,33 +1202,20 @@ __global__ __launch_bounds__(64) void vad_legs_kernel(int16_t *s16, int32_t *s32
         } else {
             r = vad_packet<NB, 1>(S, MemSrc{frame}, hp120, lp120, hp60, lp60);
         }
-        if (r == 0) {  // vad_process, src/webrtc.c:118-141: one step of reduce per decision, then the packet >> reduce
-            if (reduce < 4) reduce += 1;
+        reduce = vad_reduce_step(reduce, r);
+        if (r == 0)
             n_quiet++;
-        } else {
-            if (reduce > 0) reduce -= 1;
+        else
             n_voice++;
-        }
         if constexpr (FAST) {
-            auto att = [&](unsigned w) {  // both int16 halves >> reduce (arithmetic)
-                const int lo = (int)(int16_t)(w & 0xffffu) >> reduce, hi = (int)(int16_t)(w >> 16) >> reduce;
-                return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16);
-            };
 #pragma unroll
-            for (int i = 0; i < NV; i++) frame4[i] = make_uint4(att(raw[i].x), att(raw[i].y), att(raw[i].z), att(raw[i].w));
+            for (int i = 0; i < NV; i++) frame4[i] = vad_att_quad(raw[i], reduce);
         } else {
             for (int i = 0; i < NB; i++) frame[i] = (int16_t)(frame[i] >> reduce);
         }
     }
     S.h(V16_REDUCE) = (int16_t)reduce;
-#pragma unroll
-    for (int f = 0; f < V16_AGE; f++) g16[(size_t)f * n_legs] = r16[f];
-#pragma unroll
-    for (int f = V16_MEAN_VALUE; f < V16_WORDS; f++) g16[(size_t)f * n_legs] = r16[f - kVadMinFields];
-#pragma unroll
-    for (int f = 0; f < V32_WORDS; f++) g32[(size_t)f * n_legs] = r32[f];
-#pragma unroll 8
-    for (int f = 0; f < kVadMinFields; f++) g16[(size_t)(V16_AGE + f) * n_legs] = minlds[f * 64 + lane];
+    vad_state_out(r16, r32, minlds, lane, s16 + leg, s32 + leg, n_legs);
     if (voice) {
         voice[leg] += n_voice;
         voice[(size_t)n_legs + leg] += n_quiet;
@@ -1442,19 +1441,7 @@ int wmx_vad_process_legs(wmx_vad *h, int16_t *d_pcm, long leg_stride, long packe
                   h ? h->chn : 0, h ? h->freq : 0, h ? h->pkg : 0);
         return WMX_EINVAL;
     }
-    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls) {
-        set_error("wmx_vad_process_legs: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", max_packets, kLegMaxCalls);
-        return WMX_EINVAL;
-    }
-    if (packet_stride < kLegRow || (h->n_streams > 1 && leg_stride < packet_stride * max_packets)) {
-        set_error("wmx_vad_process_legs: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", packet_stride,
-                  kLegRow, leg_stride, max_packets);
-        return WMX_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is
-        set_error("wmx_vad_process_legs: d_pcm %p is not on a 2-byte boundary (the rows are read and written as int16)", (void *)d_pcm);
-        return WMX_EINVAL;
-    }
+    if (int rc = legs_rows_check("wmx_vad_process_legs", h->n_streams, d_pcm, leg_stride, packet_stride, max_packets, d_len)) return rc;
     const dim3 grid((unsigned)((h->n_streams + 63) / 64)), block(64);
     hipStream_t s = as_stream(stream);
     // every row on a 16-byte boundary: uint4 rows through registers; else sample by sample -- chosen once per launch

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/wmix_amd.h"
 #include "build_flags.h"
+#include "leg_calls.h"
 
 // Fault injection (developer variant only: -DWMX_FAULT_INJECTION, recorded by wmx_build_info and refused by the Python mirror like every
 // variant build).  Every runtime call that goes through WMX_HIP first passes a countdown; when it reaches zero the call is
@@ -78,6 +79,27 @@ static inline int idx_check(const int32_t *host_idx, int n, int count, const cha
             set_error("%s %d is outside the %s's %d", what, (int)host_idx[i], whose, count);
             return WMX_EINVAL;
         }
+    return 0;
+}
+
+// ---- what the per-leg stages of the bridge share (wmx_nsx_process_legs, wmx_agc_process_legs, wmx_vad_process_legs): the rows of
+// n_streams legs as [leg_stride][packet_stride] samples with max_packets slots per leg and their lengths.  The handle's own shape is
+// the stage's check; `entry` names the entry point in the error text.
+static inline int legs_rows_check(const char *entry, int n_streams, const int16_t *d_pcm, long leg_stride, long packet_stride,
+                                  int max_packets, const uint32_t *d_len) {
+    if (!d_pcm || !d_len || max_packets < 1 || max_packets > kLegMaxCalls) {
+        set_error("%s: max_packets=%d must be 1 .. %d, and neither d_pcm nor d_len NULL", entry, max_packets, kLegMaxCalls);
+        return WMX_EINVAL;
+    }
+    if (packet_stride < kLegRow || (n_streams > 1 && leg_stride < packet_stride * max_packets)) {
+        set_error("%s: rows that overlap (packet_stride %ld < %d, or leg_stride %ld shorter than %d rows)", entry, packet_stride, kLegRow,
+                  leg_stride, max_packets);
+        return WMX_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {  // the strides count samples: every row is then where d_pcm is
+        set_error("%s: d_pcm %p is not on a 2-byte boundary (the rows are read and written as int16)", entry, (const void *)d_pcm);
+        return WMX_EINVAL;
+    }
     return 0;
 }
 

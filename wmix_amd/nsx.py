@@ -4,6 +4,7 @@ import ctypes as C
 
 import torch
 
+from ._legs import process_legs
 from .lifetime import Lifetime
 from ._lib import check, lib
 
@@ -45,14 +46,7 @@ class NsxBatch(Lifetime):
         """the legs of a conference bridge (wmx_nsx_process_legs; a 1 x 8000 batch): pcm int16 CUDA [n_streams, max_packets, >= 160],
         cleaned in place; lens uint32 (or int32 bits) CUDA [n_streams, max_packets], 320 where the slot holds a row; calls None (the
         readable slots in slot order) or the call lists [n_streams] the sequencer leaves.  A leg with no row this tick touches nothing."""
-        assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() == 3 and pcm.shape[0] == self.n_streams and pcm.stride(2) == 1
-        k = pcm.shape[1]
-        assert lens.is_cuda and lens.element_size() == 4 and lens.is_contiguous() and tuple(lens.shape) == (self.n_streams, k)
-        assert calls is None or (calls.is_cuda and calls.element_size() == 4 and calls.is_contiguous() and tuple(calls.shape) == (self.n_streams,))
-        check(lib().wmx_nsx_process_legs(self._h, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), k, lens.data_ptr(),
-                                         None if calls is None else calls.data_ptr(), torch.cuda.current_stream().cuda_stream),
-              "wmx_nsx_process_legs")
-        return pcm
+        return process_legs(self, "wmx_nsx_process_legs", pcm, lens, calls)
 
     def close(self):
         if self._h:

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from ._legs import process_legs
 from .lifetime import Lifetime
 from ._lib import check, lib
 
@@ -42,15 +43,8 @@ class VadBatch(Lifetime):
         max_packets, >= 160], gated in place; lens uint32 (or int32 bits) CUDA [n_streams, max_packets], 320 where the slot holds a row;
         calls None (the readable slots in slot order) or the call lists [n_streams] the sequencer leaves; voice None or 4-byte words CUDA
         [2, n_streams], incremented per row taken that is judged voice / not voice.  A leg with no row this tick touches nothing."""
-        assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() == 3 and pcm.shape[0] == self.n_streams and pcm.stride(2) == 1
-        k = pcm.shape[1]
-        assert lens.is_cuda and lens.element_size() == 4 and lens.is_contiguous() and tuple(lens.shape) == (self.n_streams, k)
-        assert calls is None or (calls.is_cuda and calls.element_size() == 4 and calls.is_contiguous() and tuple(calls.shape) == (self.n_streams,))
         assert voice is None or (voice.is_cuda and voice.element_size() == 4 and voice.is_contiguous() and tuple(voice.shape) == (2, self.n_streams))
-        check(lib().wmx_vad_process_legs(self._h, pcm.data_ptr(), pcm.stride(0), pcm.stride(1), k, lens.data_ptr(),
-                                         None if calls is None else calls.data_ptr(), None if voice is None else voice.data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream), "wmx_vad_process_legs")
-        return pcm
+        return process_legs(self, "wmx_vad_process_legs", pcm, lens, calls, None if voice is None else voice.data_ptr())
 
     def export_reduce(self):
         """`reduce` (0 .. 4) of every stream as the work queued on the current stream leaves it: int16 [n_streams]"""
