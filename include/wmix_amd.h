@@ -1154,8 +1154,21 @@ wmx_pkgfifo *wmx_tick_fifo(wmx_tick *h);
 
 /* Developer / test hook: the cross-lane FFT executors of the kernels, stand-alone, one transform per wavefront, in place
  * (wmix_amd/csrc/fft_debug.hip lists the kinds: Ooura rdft 128 / 256 through the LDS executor, aec_rdft_128 through the LDS,
- * 16-lane-register and one-point-per-lane executors, the SPL fixed-point real FFT of orders 7 and 8). */
+ * 16-lane-register and one-point-per-lane executors, the SPL fixed-point real FFT of orders 7 and 8).  The SPL kinds, on
+ * [n_batch][n + 2] int16: 8 / 9 forward / inverse of order 7 and 10 / 11 of order 8 through the register executors the product
+ * kernels run (spl_cfft128, spl_cfft256); 12 / 13 order 8 through the generic LDS executor spl_cfft, kept as their cross-check.
+ * The inverse kinds 9, 11 and 13 write the transform's scale count to d_aux[n_batch]. */
 int wmx_debug_fft(int kind, int n_batch, void *d_data, int32_t *d_aux, void *stream);
+/* Developer / test hook: the fixed-point primitives of the VAD, AGC, NSX and AECM kernels (wmix_amd/csrc/spl_dev.h, spl_fx.h) on the
+ * device (device pointers to n int32 each; synchronises `stream`), y[i] = f(a[i], b[i], c[i]).  The int32 operands are narrowed the
+ * way the callee's parameter does (the low bits are kept); operands a kind does not take are not read and may be NULL.
+ *   0 norm_w16(a)   1 norm_w32(a)   2 norm_u32(a)   3 size_in_bits(a)   4 div_w32_w16(a, b)   5 div_u32_u16(a, b)
+ *   6 sqrt_floor(a)   7 spl_sqrt(a)   8 mul_rsft_round(a, b, c) with c in 1 .. 31   9 agc_scalediff32(a, b, c)   10 agc_mul32(a, b)
+ *   11 spl_scalediff32(a, b, c)   12 pk_abs16(a)   13 pk_max_u16(a, b)
+ * Wave reductions, d_a and d_y [n / 64][64] with n a multiple of 64, one wavefront per row, every lane storing what it holds:
+ *   16 wave_sum   17 wave_max   18 wave_min   19 wave_umax   20 wave_umin
+ * WMX_EINVAL: any other kind, a NULL operand the kind takes, n not a multiple of 64 for a wave kind. */
+int wmx_debug_spl(int kind, const int32_t *d_a, const int32_t *d_b, const int32_t *d_c, int32_t *d_y, size_t n, void *stream);
 /* Developer / test hook: the NS kernels' table-driven log (kind 0, x >= 1), exp (kind 1) and tanh (kind 2) evaluated on the host
  * from the same source (wmix_amd/csrc/libm_dev.h), for sweeping against libm without a GPU. */
 int wmx_debug_ns_libm(int kind, const float *x, float *y, size_t n);

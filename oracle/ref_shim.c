@@ -163,3 +163,57 @@ int ref_run_chain(int chn, int freq, int agc_value, unsigned stages, const int16
 {
     return ref_run_chain_iv(chn, freq, 10, agc_value, stages, far, near, out, frames_per_call, n_calls);
 }
+
+/* The SPL primitives and real FFTs of the reference on whole arrays (tests/test_spl_primitives_oracle.py), declared here as
+ * signal_processing_library.h and real_fft.h declare them.
+ * kind 0: WebRtcSpl_SqrtFloor(a), 1: WebRtcSpl_Sqrt(a), 2: WebRtcSpl_DivW32W16(a, (int16_t)b), 3: WebRtcSpl_DivU32U16(a, (uint16_t)b).
+ * The caller keeps (INT32_MIN, -1) away from kind 2: the reference's division traps on it. */
+int32_t WebRtcSpl_SqrtFloor(int32_t value);
+int32_t WebRtcSpl_Sqrt(int32_t value);
+int32_t WebRtcSpl_DivW32W16(int32_t num, int16_t den);
+uint32_t WebRtcSpl_DivU32U16(uint32_t num, uint16_t den);
+struct RealFFT;
+struct RealFFT *WebRtcSpl_CreateRealFFT(int order);
+void WebRtcSpl_FreeRealFFT(struct RealFFT *self);
+int WebRtcSpl_RealForwardFFT(struct RealFFT *self, const int16_t *real_data_in, int16_t *complex_data_out);
+int WebRtcSpl_RealInverseFFT(struct RealFFT *self, const int16_t *complex_data_in, int16_t *real_data_out);
+
+int ref_spl_sweep(int kind, const int32_t *a, const int32_t *b, int32_t *y, size_t n)
+{
+    if (kind < 0 || kind > 3) return -1;
+    for (size_t i = 0; i < n; i++) {
+        switch (kind) {
+            case 0: y[i] = WebRtcSpl_SqrtFloor(a[i]); break;
+            case 1: y[i] = WebRtcSpl_Sqrt(a[i]); break;
+            case 2: y[i] = WebRtcSpl_DivW32W16(a[i], (int16_t)b[i]); break;
+            default: y[i] = (int32_t)WebRtcSpl_DivU32U16((uint32_t)a[i], (uint16_t)b[i]); break;
+        }
+    }
+    return 0;
+}
+
+/* forward: in [n_batch][n], out [n_batch][n + 2]; inverse: in [n_batch][n + 2], out [n_batch][n], scale [n_batch]; n = 1 << order */
+int ref_spl_real_fft_batch(int order, int n_batch, const int16_t *in, int16_t *out)
+{
+    struct RealFFT *f = WebRtcSpl_CreateRealFFT(order);
+    if (!f) return -100;
+    const size_t n = (size_t)1 << order;
+    for (int k = 0; k < n_batch; k++) WebRtcSpl_RealForwardFFT(f, in + k * n, out + k * (n + 2));
+    WebRtcSpl_FreeRealFFT(f);
+    return 0;
+}
+
+void WebRtcSpl_Init(void);
+
+int ref_spl_real_ifft_batch(int order, int n_batch, const int16_t *in, int16_t *out, int32_t *scale)
+{
+    /* the inverse transform finds its largest |value| through a function pointer that WebRtcSpl_Init sets (spl_init.c), as the modules'
+     * own Create / Init routines call it before their first transform */
+    WebRtcSpl_Init();
+    struct RealFFT *f = WebRtcSpl_CreateRealFFT(order);
+    if (!f) return -100;
+    const size_t n = (size_t)1 << order;
+    for (int k = 0; k < n_batch; k++) scale[k] = WebRtcSpl_RealInverseFFT(f, in + k * (n + 2), out + k * n);
+    WebRtcSpl_FreeRealFFT(f);
+    return 0;
+}

@@ -49,10 +49,12 @@ def test_register_executors_on_more_vectors(wmx, cuda):
 
 @pytest.mark.parametrize("order", [7, 8])
 def test_spl_fixed_point_fft_known_answers(wmx, cuda, order):
+    """kinds 8 / 9 and 10 / 11: the register executors the product kernels run; 12 / 13: the generic LDS executor of order 8"""
     n = 1 << order
     x = np.zeros((12, n + 2), np.int16)
     x[:, :n] = X["fft_in_%d" % order]
-    got = run(wmx, cuda, 8 if order == 7 else 10, x)
-    assert np.array_equal(got, X["fft_fwd_%d" % order])
-    got, sc = run(wmx, cuda, 9 if order == 7 else 11, X["ifft_in_%d" % order].copy(), aux=True)
-    assert np.array_equal(got[:, :n], X["ifft_out_%d" % order]) and np.array_equal(sc, X["ifft_scale_%d" % order])
+    for fwd_kind, inv_kind in ((8, 9),) if order == 7 else ((10, 11), (12, 13)):
+        got = run(wmx, cuda, fwd_kind, x)
+        assert np.array_equal(got, X["fft_fwd_%d" % order])
+        got, sc = run(wmx, cuda, inv_kind, X["ifft_in_%d" % order].copy(), aux=True)
+        assert np.array_equal(got[:, :n], X["ifft_out_%d" % order]) and np.array_equal(sc, X["ifft_scale_%d" % order])

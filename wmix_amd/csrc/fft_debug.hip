@@ -7,8 +7,11 @@
 //   kind 4 / 5   aec_rdft_forward_128 / inverse_128: LDS executor with the frozen rdft_w tables   (AEC far kernel)
 //   kind 6       aec_rdft_forward_128 through the register executor (fft64_regs in 16-lane groups + rdft128_fwd_bin_u)
 //   kind 7       aec_rdft_inverse_128 through the one-point-per-lane executor (rdft128_inv_point_lanes + fft64_lanes)
-//   kind 8 / 9   WebRtcSpl_RealForwardFFT / RealInverseFFT, order 7 (int16 data; kind 9 returns the scale in d_aux)
-//   kind 10 / 11 the same, order 8                                                                 (NSX, AECM)
+//   kind 8 / 9   WebRtcSpl_RealForwardFFT / RealInverseFFT, order 7, through the register executor spl_cfft128 (int16 data; the
+//                inverse kinds 9 / 11 / 13 return the scale count in d_aux)                        (NSX at 8 kHz, AECM)
+//   kind 10 / 11 the same, order 8, through the register executor spl_cfft256, entered and left as nsx.hip does   (NSX at 16 / 32 kHz)
+//   kind 12 / 13 the same, order 8, through the generic LDS executor spl_cfft<8, .>: no product kernel runs it any more; it is
+//                kept as the readable cross-check of the two register executors (tests/test_spl_primitives_gpu.py)
 #include <vector>
 #include "wmx_internal.h"
 #include "fft_regs.h"
@@ -86,21 +89,24 @@ __global__ __launch_bounds__(64) void dbg_aec_lanes_inv(const FftTables *__restr
     x[2 * lane + 1] = pt.y;
 }
 
-template <int ORDER, bool INV>
+// GENERIC: the LDS executor spl_cfft instead of the register executor of the order
+template <int ORDER, bool INV, bool GENERIC = false>
 __global__ __launch_bounds__(64) void dbg_spl_fft(const SplTwiddles *__restrict__ tw, int16_t *data, int32_t *aux, int n_batch) {
     constexpr int N = 1 << ORDER;
     __shared__ SplTwiddles S;
-    __shared__ int32_t cx[N];
+    __shared__ __attribute__((aligned(16))) int32_t cx[N];  // the register executors read 8 / 16 bytes per lane
     const int lane = threadIdx.x;
     for (int i = lane; i < (int)(sizeof(SplTwiddles) / 4); i += 64) reinterpret_cast<int32_t *>(&S)[i] = reinterpret_cast<const int32_t *>(tw)[i];
     int16_t *x = data + (size_t)blockIdx.x * (N + 2);
     if (!INV) {  // real_fft.c:46-70
         for (int i = lane; i < N; i += 64) cx[bitrev<ORDER>(i)] = (int32_t)(uint16_t)x[i];
         wave_sync();
-        if constexpr (ORDER == 7)
+        if constexpr (GENERIC)
+            spl_cfft<ORDER, false>(cx, S, lane);
+        else if constexpr (ORDER == 7)
             spl_cfft128<false>(cx, S, lane);
         else
-            spl_cfft<ORDER, false>(cx, S, lane);
+            spl_cfft256<false>(cx, S, lane);
         for (int i = lane; i <= N / 2; i += 64) {
             x[2 * i] = lo16(cx[i]);
             x[2 * i + 1] = hi16(cx[i]);
@@ -113,10 +119,12 @@ __global__ __launch_bounds__(64) void dbg_spl_fft(const SplTwiddles *__restrict_
         }
         wave_sync();
         int sc;
-        if constexpr (ORDER == 7)
+        if constexpr (GENERIC)
+            sc = spl_cfft<ORDER, true>(cx, S, lane);
+        else if constexpr (ORDER == 7)
             sc = spl_cfft128<true>(cx, S, lane);
         else
-            sc = spl_cfft<ORDER, true>(cx, S, lane);
+            sc = spl_cfft256<true>(cx, S, lane);
         for (int i = lane; i < N; i += 64) x[i] = lo16(cx[i]);
         if (lane == 0) aux[blockIdx.x] = sc;
     }
@@ -125,11 +133,11 @@ __global__ __launch_bounds__(64) void dbg_spl_fft(const SplTwiddles *__restrict_
 }  // namespace
 }  // namespace wmx
 
-// d_data: [n_batch][n] float for kinds 0..7 (n = 128 or 256), [n_batch][n + 2] int16 for kinds 8..11; transformed in place.
-// d_aux: [n_batch] int32, written by kinds 9 and 11 (the inverse transform's scale count); may be NULL otherwise.
+// d_data: [n_batch][n] float for kinds 0..7 (n = 128 or 256), [n_batch][n + 2] int16 for kinds 8..13; transformed in place.
+// d_aux: [n_batch] int32, written by kinds 9, 11 and 13 (the inverse transform's scale count); may be NULL otherwise.
 extern "C" int wmx_debug_fft(int kind, int n_batch, void *d_data, int32_t *d_aux, void *stream) {
     using namespace wmx;
-    if (kind < 0 || kind > 11 || n_batch < 1 || !d_data) return WMX_EINVAL;
+    if (kind < 0 || kind > 13 || n_batch < 1 || !d_data) return WMX_EINVAL;
     hipStream_t s = as_stream(stream);
     if (kind <= 7) {
         FftTables h;
@@ -158,7 +166,7 @@ extern "C" int wmx_debug_fft(int kind, int n_batch, void *d_data, int32_t *d_aux
         if (e != hipSuccess) return hip_fail(e, "debug fft launch", __FILE__, __LINE__);
         return 0;
     }
-    if ((kind == 9 || kind == 11) && !d_aux) return WMX_EINVAL;
+    if ((kind == 9 || kind == 11 || kind == 13) && !d_aux) return WMX_EINVAL;
     SplTwiddles *d_sin = nullptr;
     {
         SplTwiddles h;
@@ -172,7 +180,9 @@ extern "C" int wmx_debug_fft(int kind, int n_batch, void *d_data, int32_t *d_aux
         case 8: hipLaunchKernelGGL((dbg_spl_fft<7, false>), grid, blk, 0, s, d_sin, x, d_aux, n_batch); break;
         case 9: hipLaunchKernelGGL((dbg_spl_fft<7, true>), grid, blk, 0, s, d_sin, x, d_aux, n_batch); break;
         case 10: hipLaunchKernelGGL((dbg_spl_fft<8, false>), grid, blk, 0, s, d_sin, x, d_aux, n_batch); break;
-        default: hipLaunchKernelGGL((dbg_spl_fft<8, true>), grid, blk, 0, s, d_sin, x, d_aux, n_batch); break;
+        case 11: hipLaunchKernelGGL((dbg_spl_fft<8, true>), grid, blk, 0, s, d_sin, x, d_aux, n_batch); break;
+        case 12: hipLaunchKernelGGL((dbg_spl_fft<8, false, true>), grid, blk, 0, s, d_sin, x, d_aux, n_batch); break;
+        default: hipLaunchKernelGGL((dbg_spl_fft<8, true, true>), grid, blk, 0, s, d_sin, x, d_aux, n_batch); break;
     }
     const hipError_t e = hipGetLastError();
     (void)hipStreamSynchronize(s);
