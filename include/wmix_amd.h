@@ -1203,6 +1203,15 @@ int wmx_debug_aec_decide_device(const float *d_sd_rows, const float *d_se_rows, 
 int wmx_debug_pow(const float *x, const float *e, float *y, size_t n);
 /* ... and evaluated on the device (device pointers; synchronises `stream`) */
 int wmx_debug_pow_device(const float *d_x, const float *d_e, float *d_y, size_t n, void *stream);
+/* Developer / test hook: the lane-mask constants the wave-per-stream kernels test instead of comparing the lane id
+ * (wmix_amd/csrc/lane_sites.h).  wmx_debug_lane_sites(): how many there are; wmx_debug_lane_site_name(site): the name of one (NULL
+ * outside the list).  wmx_debug_lane_masks launches ONE workgroup of block_threads threads (a multiple of 64, at most 1024) and
+ * writes d_out[site][thread] (device pointer, sites x block_threads int32; synchronises `stream`): bit 0 = the mask says the
+ * thread's lane is selected, bit 1 = the arithmetic predicate of the lane id says so.  Only the lanes whose bit is set in
+ * diverge_mask evaluate and store (inside a divergent branch); all ones: every lane, no branch. */
+int wmx_debug_lane_sites(void);
+const char *wmx_debug_lane_site_name(int site);
+int wmx_debug_lane_masks(int block_threads, uint64_t diverge_mask, int32_t *d_out, void *stream);
 
 #ifdef __cplusplus
 }

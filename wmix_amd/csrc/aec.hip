@@ -156,14 +156,23 @@ __device__ __forceinline__ void unpack_bin(const float *a, int b, float &re, flo
 // One 128-point real transform per 16-lane group, data in registers (fft_regs.h).  `src(p)` supplies complex
 // point p of the time-domain input; the result of the complex passes goes to `row` (natural order), where
 // rdft128_fwd_bin() finishes the real split for whoever reads a bin.
-template <class Src>
-__device__ __forceinline__ void aec_fft_fwd(float *row, const FftTables *T, int gl, Src src) {
+// `map`: nothing, or HwLanes where gl is fft_index of the hardware lane id.
+template <class Src, class... Map>
+__device__ __forceinline__ void aec_fft_fwd_map(float *row, const FftTables *T, int gl, Src src, Map... map) {
     Cx v[4];
 #pragma unroll
     for (int m = 0; m < 4; m++) v[m] = src(fft64_src_point(gl, m));
-    fft64_regs<false>(v, T, gl);
+    fft64_regs<false>(v, T, gl, map...);
 #pragma unroll
     for (int m = 0; m < 4; m++) *reinterpret_cast<float2 *>(row + 2 * (gl + 16 * m)) = make_float2(v[m].r, v[m].i);
+}
+template <class Src>
+__device__ __forceinline__ void aec_fft_fwd(float *row, const FftTables *T, int gl, Src src) {
+    aec_fft_fwd_map(row, T, gl, src);
+}
+template <class Src>
+__device__ __forceinline__ void aec_fft_fwd(float *row, const FftTables *T, int gl, HwLanes hw, Src src) {
+    aec_fft_fwd_map(row, T, gl, src, hw);
 }
 
 // ================================================================== far-end kernel
@@ -532,6 +541,10 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     // The lane-derived LDS addresses (gather points, twiddle and window slots) are loop invariant; left alone the
     // compiler hoists ~100 of them out of the packet loop and pins them in VGPRs for the whole kernel.  Recomputing
     // them per block costs a few VALU ops and frees the registers.
+    // `lane_in` is the hardware lane id (aec_near_kernel: threadIdx.x & 63, blocks of 64 * kAecWavesPerBlock threads): the tests of
+    // the lane alone are mask constants (lanes<>, lane_sites.h), and the transforms are entered through their HwLanes forms
+    using namespace site;
+    constexpr HwLanes hw{};
     int lane = opaque_lane(lane_in);
     int *Si = reinterpret_cast<int *>(W.st) - AS_LDS0;
     const float mu = MULT == 1 ? 0.6f : 0.5f, err_thr = MULT == 1 ? 2e-6f : 1.5e-6f;  // aec_core.c:1530-1538
@@ -550,7 +563,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         dctr++;
         if (dctr == 10 * MULT) dctr = 0;
         if (dctr == 0) blk_flags |= kAecFlagDelayEst;
-        if (lane == 0) {
+        if (lanes<aec_lane0>()) {
             Si[AS_NOISECTR] = nctr;
             Si[AS_DELAYCTR] = dctr;
         }
@@ -610,9 +623,9 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         // ---- error e = d - y (aec_core.c:1286-1297): y = second half of the inverse transform of the packed spectrum
         //      (lane 0 carries (bin 0, bin 64)), one point per lane in registers: lanes 32..63 end up with y[2(l-32)], +1
         AEC_PROF(1);
-        v2f pt = rdft128_inv_point_lanes(v2f{y2.x, lane == 0 ? y64 : y2.y}, &K.tab, lane);
-        pt = fft64_lanes<true>(pt, &K.tab, lane);
-        if (lane >= 32) {
+        v2f pt = rdft128_inv_point_lanes(v2f{y2.x, lanes<aec_lane0>() ? y64 : y2.y}, &K.tab, lane, hw);
+        pt = fft64_lanes<true>(pt, &K.tab, lane, hw);
+        if (lanes<aec_upper>()) {
             const int i = 2 * (lane - 32);
             W.enew[i] = W.cur[i] - pt.x * scale;
             W.enew[i + 1] = W.cur[i + 1] - pt.y * scale;
@@ -625,15 +638,15 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     //      the NLP.  The reference transforms d before it filters the far end; nothing between the two reads the other's
     //      result, so the near transforms wait for the error and share its instruction stream.
     {
-        const bool win = g & 1, err = g >= 2;
-        aec_fft_fwd(W.fa[g], &K.tab, gl, [&](int p) {
+        const bool win = lanes<aec_win>(), err = lanes<aec_err>();
+        aec_fft_fwd(W.fa[g], &K.tab, gl, hw, [&](int p) {
             const int i = 2 * (p & 31);
             float x0, x1, h0, h1;
             if (p < 32) {  // p is a compile-time property of the point index m (fft64_src_point): no divergence
                 const float *prev = &AEC_ST(err ? AS_EPREV : AS_DPREV);
                 x0 = prev[i], x1 = prev[i + 1];
                 h0 = K.hanning[i], h1 = K.hanning[i + 1];
-                if (g == 2) x0 = 0.f, x1 = 0.f;
+                if (lanes<aec_ef>()) x0 = 0.f, x1 = 0.f;
             } else {
                 const float *now = err ? W.enew : W.cur;
                 x0 = now[i], x1 = now[i + 1];
@@ -648,7 +661,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     // windowed near spectrum, kept in registers across the filter update (bin = lane; lane 0 also bin 64)
     float dwr, dwi, dw64, dfr, dfi, df64;
     {
-        const SplitLane cf = rdft128_fwd_coef(&K.tab, lane);
+        const SplitLane cf = rdft128_fwd_coef(&K.tab, lane, hw);
         const v2f dwb = rdft128_fwd_bin_u(W.fa[1], cf, lane), dfb = rdft128_fwd_bin_u(W.fa[0], cf, lane);
         dwr = dwb.x, dwi = dwb.y, dw64 = W.fa[1][0] - W.fa[1][1];  // bin 64 = a[0] - a[1] (used by lane 0)
         dfr = dfb.x, dfi = dfb.y, df64 = W.fa[0][0] - W.fa[0][1];
@@ -684,7 +697,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         put(lane, a);
 #if !defined(WMX_AEC_EXP) || WMX_AEC_EXP < 1
         const Pw c = power(kAecPart, df64, 0.f);
-        if (lane == 0) put(kAecPart, c);
+        if (lanes<aec_lane0>()) put(kAecPart, c);
 #endif
     }
     // ---- ScaleErrorSignal (aec_core.c:172-194); ef stays in registers (bin = lane; lane 0 also bin 64), and so
@@ -692,7 +705,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     float ewr, ewi, ew64, efr, efi, ef64r, ef64i = 0.f;
     {
         {
-            const SplitLane cf = rdft128_fwd_coef(&K.tab, lane);
+            const SplitLane cf = rdft128_fwd_coef(&K.tab, lane, hw);
             const v2f ewb = rdft128_fwd_bin_u(W.fa[3], cf, lane), efb = rdft128_fwd_bin_u(W.fa[2], cf, lane);
             ewr = ewb.x, ewi = ewb.y, ew64 = W.fa[3][0] - W.fa[3][1];
             efr = efb.x, efi = efb.y, ef64r = W.fa[2][0] - W.fa[2][1];
@@ -767,7 +780,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         wave_sync();
         // fft[1] is overwritten with the Nyquist product (aec_core.c:245-248): lane j patches partition base + j
         // (LDS runs a wave's accesses in order, so this lands after lane 0's store above)
-        if (lane < cnt) fa_row(W, lane)[1] = nyq_r * e64r - nyq_i * e64i;
+        if (pass == 0 ? lanes<aec_upd8>() : lanes<aec_upd4>()) fa_row(W, lane)[1] = nyq_r * e64r - nyq_i * e64i;
         wave_sync();
         AEC_RELANE();
         if (pass == 0) {
@@ -776,8 +789,8 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
             float *row0 = W.fa[g], *row1 = W.fa[4 + g];
             Cx2 v[4];
 #pragma unroll
-            for (int m = 0; m < 4; m++) v[m] = rdft128_inv_point_x2(row0, row1, &K.tab, gl, m);
-            fft64_regs_x2<true>(v, &K.tab, gl);
+            for (int m = 0; m < 4; m++) v[m] = rdft128_inv_point_x2(row0, row1, &K.tab, gl, m, hw);
+            fft64_regs_x2<true>(v, &K.tab, gl, hw);
             // points 0..31 (m = 0, 1) scaled, points 32..63 zeroed; the forward gather wants points
             // rev4(gl) + {0, 32, 16, 48}: two of them from lane rev4(gl), two zeros
             const v2f sc = bc(scale), z = bc(0.f);
@@ -786,7 +799,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
             v[2] = Cx2{v2f{row_bitrev(cr.x, lane), row_bitrev(cr.y, lane)}, v2f{row_bitrev(ci.x, lane), row_bitrev(ci.y, lane)}};
             v[1] = Cx2{z, z};
             v[3] = Cx2{z, z};
-            fft64_regs_x2<false>(v, &K.tab, gl);
+            fft64_regs_x2<false>(v, &K.tab, gl, hw);
 #pragma unroll
             for (int m = 0; m < 4; m++) {
                 *reinterpret_cast<float2 *>(row0 + 2 * (gl + 16 * m)) = make_float2(v[m].r.x, v[m].i.x);
@@ -797,10 +810,10 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
             float *row = W.fa[g];
             Cx v[4];
             {
-                const v2f p0 = rdft128_inv_point_m<0>(row, &K.tab, gl), p1 = rdft128_inv_point_m<1>(row, &K.tab, gl);
-                const v2f p2 = rdft128_inv_point_m<2>(row, &K.tab, gl), p3 = rdft128_inv_point_m<3>(row, &K.tab, gl);
+                const v2f p0 = rdft128_inv_point_m<0>(row, &K.tab, gl, hw), p1 = rdft128_inv_point_m<1>(row, &K.tab, gl, hw);
+                const v2f p2 = rdft128_inv_point_m<2>(row, &K.tab, gl, hw), p3 = rdft128_inv_point_m<3>(row, &K.tab, gl, hw);
                 v[0] = Cx{p0.x, p0.y}, v[1] = Cx{p1.x, p1.y}, v[2] = Cx{p2.x, p2.y}, v[3] = Cx{p3.x, p3.y};
-                fft64_regs<true>(v, &K.tab, gl);
+                fft64_regs<true>(v, &K.tab, gl, hw);
             }
             const Cx a = Cx{row_bitrev(v[0].r * scale, lane), row_bitrev(v[0].i * scale, lane)};
             const Cx c = Cx{row_bitrev(v[1].r * scale, lane), row_bitrev(v[1].i * scale, lane)};
@@ -808,21 +821,21 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
             v[1] = Cx{0.f, 0.f};
             v[2] = c;
             v[3] = Cx{0.f, 0.f};
-            fft64_regs<false>(v, &K.tab, gl);
+            fft64_regs<false>(v, &K.tab, gl, hw);
 #pragma unroll
             for (int m = 0; m < 4; m++) *reinterpret_cast<float2 *>(row + 2 * (gl + 16 * m)) = make_float2(v[m].r, v[m].i);
         }
         wave_sync();
         AEC_RELANE();
         {
-            const SplitLane cf = rdft128_fwd_coef(&K.tab, lane);
+            const SplitLane cf = rdft128_fwd_coef(&K.tab, lane, hw);
 #pragma unroll
             for (int q = 0; q < 8; q++) {
                 if (q >= cnt) continue;
                 const v2f d = rdft128_fwd_bin_u(W.fa[q], cf, lane);
                 taps.t[base + q] = taps.t[base + q] + d;  // lane 0's imaginary half adds 0 (wfBuf[1][pos] is never touched, aec_core.c:262-268)
             }
-            if (lane < cnt) W.wn[base + lane] += fa_row(W, lane)[0] - fa_row(W, lane)[1];  // wfBuf[0][pos + 64] += fft[1]: bin 64 = a[0] - a[1]
+            if (pass == 0 ? lanes<aec_upd8>() : lanes<aec_upd4>()) W.wn[base + lane] += fa_row(W, lane)[0] - fa_row(W, lane)[1];  // wfBuf[0][pos + 64] += fft[1]: bin 64 = a[0] - a[1]
         }
         wave_sync();
     }
@@ -840,10 +853,13 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         for (int p = 0; p < 12; p++) {
             float *dst = W.fa[p >> 1] + (p & 1) * 66;
             dst[lane] = taps.t[p].x * taps.t[p].x + taps.t[p].y * taps.t[p].y;
-            if (lane == 0) dst[64] = W.wn[p] * W.wn[p] + 0.f * 0.f;
+        }
+        if (lanes<aec_lane0>()) {
+#pragma unroll
+            for (int p = 0; p < 12; p++) (W.fa[p >> 1] + (p & 1) * 66)[64] = W.wn[p] * W.wn[p] + 0.f * 0.f;
         }
         wave_sync();
-        if (lane < 12) {
+        if (lanes<aec_parts>()) {
             const float *src = W.fa[lane >> 1] + (lane & 1) * 66;
             float en = 0.f;
             for (int j = 0; j < kAecPart1; j++) en += src[j];
@@ -858,7 +874,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
                 delayIdx = p;
             }
         wave_sync();
-        if (lane == 0) Si[AS_DELAYIDX] = delayIdx;
+        if (lanes<aec_lane0>()) Si[AS_DELAYIDX] = delayIdx;
     }
     AEC_PROF(4);
     // xfw = windowed far spectrum consumed delayIdx blocks ago; the windowed near / error spectra come back from registers
@@ -870,7 +886,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         }
         xw[lane] = xwr_pre;
         xw[66 + lane] = xwi_pre;
-        if (lane == 0) {
+        if (lanes<aec_lane0>()) {
             xw[kAecPart] = uniform_ld(Xw + kAecPart);
             xw[66 + kAecPart] = uniform_ld(Xw + kAecPart1 + kAecPart);
         }
@@ -878,7 +894,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         dw[66 + lane] = dwi;
         ew[lane] = ewr;
         ew[66 + lane] = ewi;
-        if (lane == 0) {
+        if (lanes<aec_lane0>()) {
             dw[kAecPart] = dw64;
             dw[66 + kAecPart] = 0.f;
             ew[kAecPart] = ew64;
@@ -921,7 +937,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         put(lane, a);
 #if !defined(WMX_AEC_EXP) || WMX_AEC_EXP < 1
         const Psd c = psd(kAecPart);
-        if (lane == 0) put(kAecPart, c);
+        if (lanes<aec_lane0>()) put(kAecPart, c);
         // sdSum and seSum feed two comparisons and nothing else: lane-parallel sums of the values still in registers settle both
         // unless one of them lies within the summation error of its threshold (aec_gate.h)
         float sd_t = a.sd, se_t = a.se;
@@ -935,7 +951,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     int diverge = gate.diverge;
     bool reset_filter = gate.reset;
 #ifdef WMX_AEC_GATE_PROF
-    if (lane == 0) atomicAdd(&g_aec_gate[gate.decided ? 0 : 1], 1ull);
+    if (lanes<aec_lane0>()) atomicAdd(&g_aec_gate[gate.decided ? 0 : 1], 1ull);
 #endif
     if (!gate.decided) {
         // the two ordered sums advance side by side: lane 0 adds sd[0..64], lane 1 adds se[0..64] (index order each)
@@ -949,12 +965,13 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         reset_filter = seSum > (19.95f * sdSum);
     }
     wave_sync();
-    if (lane == 0) Si[AS_DIVERGE] = diverge;
+    if (lanes<aec_lane0>()) Si[AS_DIVERGE] = diverge;
     if (reset_filter) {  // memset(wfBuf, 0)
 #pragma unroll
-        for (int p = 0; p < 12; p++) {
-            taps.t[p] = v2f{0.f, 0.f};
-            if (lane == 0) W.wn[p] = 0.f;
+        for (int p = 0; p < 12; p++) taps.t[p] = v2f{0.f, 0.f};
+        if (lanes<aec_lane0>()) {  // one region for the twelve stores: two tests of a mask constant are not merged as two compares were
+#pragma unroll
+            for (int p = 0; p < 12; p++) W.wn[p] = 0.f;
         }
     }
     AEC_PROF(6);
@@ -971,7 +988,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     const uint2 jl = jump[(lane + 63) & 63], j64 = jump[63];
     const AecNoiseEntry nz = noise_tab[((nseed * jl.x + jl.y) & 0x7FFFFFFFu) >> 16];
     const float nz_c = nz.c, nz_s = nz.s;
-    if (lane == 0) Si[AS_NSEED] = (int)((nseed * j64.x + j64.y) & 0x7FFFFFFFu);
+    if (lanes<aec_lane0>()) Si[AS_NSEED] = (int)((nseed * j64.x + j64.y) & 0x7FFFFFFFu);
     // coherences (aec_core.c:440-449), bin `lane` and bin 64 side by side
     {
         auto coh = [&](int b, float &cde, float &cxd) {
@@ -993,7 +1010,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         }
         t0[lane] = a0;
         t1[lane] = a1;
-        if (lane == 0) {
+        if (lanes<aec_lane0>()) {
             if (diverge) {
                 ew[kAecPart] = dw[kAecPart];
                 ew[66 + kAecPart] = dw[66 + kAecPart];
@@ -1009,7 +1026,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     hNlXdAvg = t1[5] * prefSize, hNlDeAvg = t0[5] * prefSize;
 #else
     {
-        const float *mine = lane == 1 ? t0 : t1;
+        const float *mine = lanes<aec_lane1>() ? t0 : t1;
         float acc = 0.f;
 #pragma unroll
         for (int i = minPref; i < prefSize + minPref; i++) acc += mine[i];
@@ -1068,7 +1085,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
 #endif
         // qsort(hNlPref) + the two order statistics (aec_core.c:1017-1022): rank by counting
         constexpr int i75 = (int)(0.75f * (prefSize - 1)), i50 = (int)(0.5f * (prefSize - 1));
-        if (lane < prefSize) {
+        if (MULT == 1 ? lanes<aec_pref24>() : lanes<aec_pref12>()) {
             const float v = t2[minPref + lane];
             int rank = 0;
             for (int i = 0; i < prefSize; i++) {
@@ -1107,7 +1124,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     else
         overDriveSm = 0.9f * overDriveSm + 0.1f * overDrive;
     // every lane holds the same scalars; lane 0 publishes them
-    if (lane == 0) {
+    if (lanes<aec_lane0>()) {
         AEC_ST(AS_HNLXDAVGMIN) = hNlXdAvgMin;
         AEC_ST(AS_HNLFBMIN) = hNlFbMin;
         AEC_ST(AS_HNLFBLOCALMIN) = hNlFbLocalMin;
@@ -1157,19 +1174,19 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     // inverse transform, overlap-add with the sqrt-Hanning window, saturate, queue 64 output samples
     // (aec_core.c:1089-1101, 1341): points 0..31 are the first half, 32..63 the new overlap tail
     {
-        if (lane == 0) out_spec.y = out_nyq;
-        v2f pt = rdft128_inv_point_lanes(out_spec, &K.tab, lane);
-        pt = fft64_lanes<true>(pt, &K.tab, lane);
+        if (lanes<aec_lane0>()) out_spec.y = out_nyq;
+        v2f pt = rdft128_inv_point_lanes(out_spec, &K.tab, lane, hw);
+        pt = fft64_lanes<true>(pt, &K.tab, lane, hw);
         // lane l holds samples 2l, 2l+1: lanes 0..31 the output half, lanes 32..63 the new overlap tail
         const int i = 2 * (lane & 31);
-        if (lane < 32) {
+        if (lanes<aec_lower>()) {
             const float o0 = sat16f(pt.x * scale * K.hanning[i] + AEC_ST(AS_OUTBUF + i));
             const float o1 = sat16f(pt.y * scale * K.hanning[i + 1] + AEC_ST(AS_OUTBUF + i + 1));
             AEC_ST(AS_OUT_RING + ring_at(bp.out_wr, i)) = o0;
             AEC_ST(AS_OUT_RING + ring_at(bp.out_wr, i + 1)) = o1;
         }
         wave_sync();  // the tail overwrites outBuf only after every lane has read it
-        if (lane >= 32) {
+        if (lanes<aec_upper>()) {
             AEC_ST(AS_OUTBUF + i) = pt.x * scale * K.hanning[kAecPart - i];
             AEC_ST(AS_OUTBUF + i + 1) = pt.y * scale * K.hanning[kAecPart - i - 1];
         }

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstring>
 #include "wmx_internal.h"  // wave_sync()
+#include "lane_sites.h"
 
 namespace wmx {
 
@@ -192,10 +193,11 @@ __device__ __forceinline__ v2f cmul_w(float wr, float wi, v2f t) { return v2f{wr
 //           o3 = w2*(-ti - tr, tr - ti)             == -w2*(tr + ti, ti - tr): rotated the other way, W3 = (-w2, 0)
 // with m = 0 outside block 1 (tr - 0*ti == tr).  Products with 0 and 1 and sign changes are exact, so each output is
 // the reference's value (a zero result may carry the other sign; nothing downstream can see that).
-__device__ __forceinline__ void bfly4_v(int b, const FftTables *T, v2f v[4]) {
+// b1: "b == 1", handed in by callers that hold it as a lane-mask constant (wmx_internal.h lanes<>, fft_regs.h HwLanes)
+__device__ __forceinline__ void bfly4_v(int b, const FftTables *T, v2f v[4], bool b1) {
     const v2f x0 = v[0] + v[1], x1 = v[0] - v[1], x2 = v[2] + v[3], x3 = v[2] - v[3];
     v[0] = x0 + x2;
-    const float m = b == 1 ? 1.f : 0.f;
+    const float m = b1 ? 1.f : 0.f;
     const float w1r = T->W1[b][0], w1i = T->W1[b][1], w2r = T->W2[b][0], w2i = T->W2[b][1];
     const float w3r = T->W3[b][0], w3i = T->W3[b][1];
     v2f t1 = add_i(x1, x3);  // (x1r - x3i, x1i + x3r)
@@ -208,21 +210,22 @@ __device__ __forceinline__ void bfly4_v(int b, const FftTables *T, v2f v[4]) {
     v[1] = cmul_w(w1r, w1i, t1);
     v[3] = cmul_w(w3r, w3i, t3);
 }
+__device__ __forceinline__ void bfly4_v(int b, const FftTables *T, v2f v[4]) { bfly4_v(b, T, v, b == 1); }
 
 __device__ __forceinline__ void bfly4(int b, const FftTables *T, Cx A, Cx B, Cx C, Cx D, float2 &o0, float2 &o1, float2 &o2,
-                                      float2 &o3) {
+                                      float2 &o3, bool b1) {
     v2f v[4] = {cx(A), cx(B), cx(C), cx(D)};
-    bfly4_v(b, T, v);
+    bfly4_v(b, T, v, b1);
     o0 = make_float2(v[0].x, v[0].y);
     o1 = make_float2(v[1].x, v[1].y);
     o2 = make_float2(v[2].x, v[2].y);
     o3 = make_float2(v[3].x, v[3].y);
 }
 
-__device__ __forceinline__ void bfly4_store(float *a, int p0, int hc, int b, const FftTables *T, Cx A, Cx B, Cx C, Cx D) {
+__device__ __forceinline__ void bfly4_store(float *a, int p0, int hc, int b, const FftTables *T, Cx A, Cx B, Cx C, Cx D, bool b1) {
     const int p1 = p0 + hc, p2 = p1 + hc, p3 = p2 + hc;
     float2 o0, o1, o2, o3;
-    bfly4(b, T, A, B, C, D, o0, o1, o2, o3);
+    bfly4(b, T, A, B, C, D, o0, o1, o2, o3, b1);
     *reinterpret_cast<float2 *>(a + 2 * p0) = o0;
     *reinterpret_cast<float2 *>(a + 2 * p1) = o1;
     *reinterpret_cast<float2 *>(a + 2 * p2) = o2;
@@ -263,10 +266,22 @@ __device__ __forceinline__ Cx ld_cx(const float *a, int p) {
     return Cx{v.x, v.y};
 }
 
+// A predicate of the lane alone: the mask constant M where the caller's lane is the hardware lane id (HW; wmx_internal.h lanes<>),
+// the arithmetic form otherwise (dead code under HW)
+template <bool HW, uint64_t M>
+__device__ __forceinline__ bool lane_pred(bool arith) {
+    if constexpr (HW)
+        return lanes<M>();
+    else
+        return arith;
+}
+
 // The complex passes (bitrv2 + cftfsub / cftbsub) for NC = n/2 complex points in LDS, one transform per wave:
 // every pass has NC/4 butterflies, lane k takes butterfly k.
-template <int NC, bool INVERSE>
+template <int NC, bool INVERSE, bool HW = false>
 __device__ __forceinline__ void fft_complex_passes(float *a, const FftTables *T, int lane) {
+    using namespace site;
+    constexpr uint64_t kAct = NC == 128 ? oo128_act : oo64_act;
     static_assert(NC / 4 <= 64, "one butterfly per lane");
     constexpr int BITS = (NC == 128) ? 7 : 6;
     constexpr int NB = NC / 4;  // butterflies per radix-4 pass
@@ -274,7 +289,7 @@ __device__ __forceinline__ void fft_complex_passes(float *a, const FftTables *T,
     // rev(g) over BITS-2 bits + {0, NC/2, NC/4, 3NC/4}[j].
     {
         Cx A{0.f, 0.f}, B = A, C = A, D = A;
-        const bool act = lane < NB;
+        const bool act = lane_pred<HW, kAct>(lane < NB);
         if (act) {
             const int r0 = dev_bitrev(lane, BITS - 2);
             A = ld_cx(a, r0);
@@ -283,21 +298,23 @@ __device__ __forceinline__ void fft_complex_passes(float *a, const FftTables *T,
             D = ld_cx(a, r0 + 3 * NC / 4);
         }
         wave_sync();
-        if (act) bfly4_store(a, 4 * lane, 1, lane, T, A, B, C, D);
+        if (act) bfly4_store(a, 4 * lane, 1, lane, T, A, B, C, D, lane_pred<HW, oo_p1_b1>(lane == 1));
         wave_sync();
     }
     // twiddled passes with stride 4, 16 while 4*hc < NC
 #pragma unroll
     for (int hc = 4; hc * 4 < NC; hc *= 4) {
-        if (lane < NB) {
+        if (lane_pred<HW, kAct>(lane < NB)) {
             const int b = lane / hc, j = lane % hc, p0 = b * 4 * hc + j;
-            bfly4_store(a, p0, hc, b, T, ld_cx(a, p0), ld_cx(a, p0 + hc), ld_cx(a, p0 + 2 * hc), ld_cx(a, p0 + 3 * hc));
+            const bool b1 = hc == 4 ? lane_pred<HW, oo_hc4_b1>(b == 1) : lane_pred<HW, oo_hc16_b1>(b == 1);
+            bfly4_store(a, p0, hc, b, T, ld_cx(a, p0), ld_cx(a, p0 + hc), ld_cx(a, p0 + 2 * hc), ld_cx(a, p0 + 3 * hc), b1);
         }
         wave_sync();
     }
     constexpr int HC = (NC == 128) ? 64 : 16;  // stride of the closing pass
     if constexpr (HC * 4 == NC) {
-        if (lane < HC) {
+        static_assert(HC == 16, "site::oo64_close");
+        if (lane_pred<HW, oo64_close>(lane < HC)) {
             const int p0 = lane, p1 = p0 + HC, p2 = p1 + HC, p3 = p2 + HC;
             const Cx A = ld_cx(a, p0), B = ld_cx(a, p1), C = ld_cx(a, p2), D = ld_cx(a, p3);
             float2 o0, o1, o2, o3;
@@ -328,11 +345,11 @@ __device__ __forceinline__ void fft_complex_passes(float *a, const FftTables *T,
 }
 
 // fft4g.c:1234-1284 rftfsub / rftbsub: conjugate pairs (q, NC - q), q = 1 .. NC/2 - 1.
-template <int NC, bool INVERSE>
+template <int NC, bool INVERSE, bool HW = false>
 __device__ __forceinline__ void fft_real_split(float *a, const FftTables *T, int lane) {
+    using namespace site;
     constexpr int NQ = NC / 2;  // table length n/4
-    for (int q = lane; q < NQ; q += 64) {
-        if (q == 0) continue;
+    auto pair = [&](int q) {
         const int j = 2 * q, k = 2 * NC - j;
         const float wkr = 0.5f - T->c[NQ - q], wki = T->c[q];
         const float aj = a[j], aj1 = a[j + 1], ak = a[k], ak1 = a[k + 1];
@@ -350,9 +367,16 @@ __device__ __forceinline__ void fft_real_split(float *a, const FftTables *T, int
             a[k] = ak + yr;
             a[k + 1] = yi - ak1;
         }
+    };
+    if constexpr (HW) {  // q = lane is the one pass of the loop: for all lanes (NQ == 64) or for site::oo64_split (NQ == 32)
+        static_assert(NQ == 64 || NQ == 32, "site::oo64_split");
+        if ((NQ == 64 || lanes<oo64_split>()) && !lanes<oo_lane0>()) pair(lane);
+    } else {
+        for (int q = lane; q < NQ; q += 64)
+            if (q != 0) pair(q);
     }
     if constexpr (INVERSE) {
-        if (lane == 0) {
+        if (lane_pred<HW, oo_lane0>(lane == 0)) {
             a[1] = -a[1];
             a[NC + 1] = -a[NC + 1];
         }
@@ -361,11 +385,11 @@ __device__ __forceinline__ void fft_real_split(float *a, const FftTables *T, int
 }
 
 // WebRtc_rdft(n, +1, a) / aec_rdft_forward_128(a).  n = 2*NC.
-template <int NC>
+template <int NC, bool HW = false>
 __device__ __forceinline__ void rdft_forward(float *a, const FftTables *T, int lane) {
-    fft_complex_passes<NC, false>(a, T, lane);
-    fft_real_split<NC, false>(a, T, lane);
-    if (lane == 0) {
+    fft_complex_passes<NC, false, HW>(a, T, lane);
+    fft_real_split<NC, false, HW>(a, T, lane);
+    if (lane_pred<HW, site::oo_lane0>(lane == 0)) {
         const float a0 = a[0], a1 = a[1];
         a[0] = a0 + a1;
         a[1] = a0 - a1;
@@ -374,17 +398,26 @@ __device__ __forceinline__ void rdft_forward(float *a, const FftTables *T, int l
 }
 
 // WebRtc_rdft(n, -1, a) / aec_rdft_inverse_128(a); unnormalised like the reference.
-template <int NC>
+template <int NC, bool HW = false>
 __device__ __forceinline__ void rdft_inverse(float *a, const FftTables *T, int lane) {
-    if (lane == 0) {
+    if (lane_pred<HW, site::oo_lane0>(lane == 0)) {
         const float a0 = a[0], a1 = a[1];
         const float h = 0.5f * (a0 - a1);
         a[1] = h;
         a[0] = a0 - h;
     }
     wave_sync();
-    fft_real_split<NC, true>(a, T, lane);
-    fft_complex_passes<NC, true>(a, T, lane);
+    fft_real_split<NC, true, HW>(a, T, lane);
+    fft_complex_passes<NC, true, HW>(a, T, lane);
+}
+// ... for a caller whose `lane` is the hardware lane id
+template <int NC>
+__device__ __forceinline__ void rdft_forward(float *a, const FftTables *T, int lane, HwLanes) {
+    rdft_forward<NC, true>(a, T, lane);
+}
+template <int NC>
+__device__ __forceinline__ void rdft_inverse(float *a, const FftTables *T, int lane, HwLanes) {
+    rdft_inverse<NC, true>(a, T, lane);
 }
 
 }  // namespace wmx

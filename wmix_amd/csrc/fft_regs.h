@@ -19,6 +19,7 @@
 #pragma once
 #include <cstddef>
 #include "fft_ooura.h"
+#include "lane_sites.h"
 
 namespace wmx {
 
@@ -35,6 +36,7 @@ namespace wmx {
 // v_mov_b32 2.0, v_mov_b32_dpp 4.0, v_permlane16_swap / v_permlane32_swap 7.6, v_cndmask_b32 4.0 behind its v_cmp (4.0), ds_bpermute 24 of
 // the LDS pipe.  Per register pair an exchange costs 10 (copy + two DPP moves) or 7.6 (swap); the contiguous-row mapping used before
 // needed a quad_perm fetch + select per register for lane bits 0 / 1 (16 per pair).
+// The HwLanes overloads (wmx_internal.h) additionally take g / gl to be fft_group / fft_index of the hardware lane id.
 __device__ __forceinline__ int fft_group(int lane) { return lane & 3; }
 __device__ __forceinline__ int fft_index(int lane) { return lane >> 2; }
 template <int CTRL, int BANK_MASK = 0xf>
@@ -96,9 +98,17 @@ __device__ __forceinline__ void fft64_regs(v2f v[4], const FftTables *T, int gl)
     bfly4_close_v<INVERSE>(v);
 }
 template <bool INVERSE>
-__device__ __forceinline__ void fft64_regs(Cx c[4], const FftTables *T, int gl) {
+__device__ __forceinline__ void fft64_regs(v2f v[4], const FftTables *T, int gl, HwLanes) {
+    bfly4_v(gl, T, v, lanes<site::fft_p1_b1>());
+    transpose4<1, 2>(v);
+    bfly4_v(gl >> 2, T, v, lanes<site::fft_p2_b1>());
+    transpose4<4, 8>(v);
+    bfly4_close_v<INVERSE>(v);
+}
+template <bool INVERSE, class... Map>  // Map: nothing, or HwLanes
+__device__ __forceinline__ void fft64_regs(Cx c[4], const FftTables *T, int gl, Map... map) {
     v2f v[4] = {cx(c[0]), cx(c[1]), cx(c[2]), cx(c[3])};
-    fft64_regs<INVERSE>(v, T, gl);
+    fft64_regs<INVERSE>(v, T, gl, map...);
 #pragma unroll
     for (int m = 0; m < 4; m++) c[m] = Cx{v[m].x, v[m].y};
 }
@@ -114,13 +124,13 @@ struct Cx2 {
 };
 __device__ __forceinline__ v2f bc(float x) { return v2f{x, x}; }
 
-__device__ __forceinline__ void bfly4_x2(int b, const FftTables *T, Cx2 v[4]) {
+__device__ __forceinline__ void bfly4_x2(int b, const FftTables *T, Cx2 v[4], bool b1) {  // b1: "b == 1" (see bfly4_v)
     // the straight-line butterfly of bfly4_v (fft_ooura.h), element-wise on the two packed transforms
     const v2f x0r = v[0].r + v[1].r, x0i = v[0].i + v[1].i, x1r = v[0].r - v[1].r, x1i = v[0].i - v[1].i;
     const v2f x2r = v[2].r + v[3].r, x2i = v[2].i + v[3].i, x3r = v[2].r - v[3].r, x3i = v[2].i - v[3].i;
     v[0].r = x0r + x2r;
     v[0].i = x0i + x2i;
-    const v2f m = bc(b == 1 ? 1.f : 0.f);
+    const v2f m = bc(b1 ? 1.f : 0.f);
     const v2f w1r = bc(T->W1[b][0]), w1i = bc(T->W1[b][1]), w2r = bc(T->W2[b][0]), w2i = bc(T->W2[b][1]);
     const v2f w3r = bc(T->W3[b][0]), w3i = bc(T->W3[b][1]);
     v2f tr = x0r - x2r, ti = x0i - x2i;
@@ -146,6 +156,7 @@ __device__ __forceinline__ void bfly4_x2(int b, const FftTables *T, Cx2 v[4]) {
     v[3].r = w3r * tr - w3i * ti;
     v[3].i = w3r * ti + w3i * tr;
 }
+__device__ __forceinline__ void bfly4_x2(int b, const FftTables *T, Cx2 v[4]) { bfly4_x2(b, T, v, b == 1); }
 
 template <bool INVERSE>
 __device__ __forceinline__ void bfly4_close_x2(Cx2 v[4]) {
@@ -187,6 +198,14 @@ __device__ __forceinline__ void fft64_regs_x2(Cx2 v[4], const FftTables *T, int 
     transpose4_x2<4, 8>(v);
     bfly4_close_x2<INVERSE>(v);
 }
+template <bool INVERSE>
+__device__ __forceinline__ void fft64_regs_x2(Cx2 v[4], const FftTables *T, int gl, HwLanes) {
+    bfly4_x2(gl, T, v, lanes<site::fft_p1_b1>());
+    transpose4_x2<1, 2>(v);
+    bfly4_x2(gl >> 2, T, v, lanes<site::fft_p2_b1>());
+    transpose4_x2<4, 8>(v);
+    bfly4_close_x2<INVERSE>(v);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // (64 - p) & 63, kept from the optimiser: scaled to a byte offset it would become (p * -8) & 0x1f8 with a full 32-bit
@@ -212,34 +231,43 @@ __device__ __forceinline__ void st_pt(float *row, int p, v2f c) { *reinterpret_c
 // these are the same floats.  M fixes the case at compile time (M odd <=> p >= 32); p == 32 (own == other) runs with
 // zero coefficients, p == 0 (the a[1] fix-up, fft4g.c:349-351) is selected in.
 template <int M>
-__device__ __forceinline__ v2f rdft128_inv_point_m(const float *a, const FftTables *T, int b) {
+__device__ __forceinline__ v2f rdft128_inv_point_m(const float *a, const FftTables *T, int b, bool b0) {  // b0: "b == 0"
     constexpr int OFF = M == 0 ? 0 : (M == 1 ? 32 : (M == 2 ? 16 : 48));
     const int p = dev_bitrev(b, 4) + OFF;
     const v2f own = ld_pt(a, p), other = ld_pt(a, mirror64(p));
     const int q = (M & 1) ? 64 - p : p;
     float wr = 0.5f - T->c[32 - q], wi = T->c[q];
     if constexpr (M == 1) {
-        wr = b == 0 ? 0.f : wr;  // p == 32: re = a[64], im = -a[65]
-        wi = b == 0 ? 0.f : wi;
+        wr = b0 ? 0.f : wr;  // p == 32: re = a[64], im = -a[65]
+        wi = b0 ? 0.f : wi;
     }
     const v2f x = own + v2f{-other.x, other.y};
     const v2f y = (M & 1) ? cmul_w(wr, wi, x) : cmul_w(wr, -wi, x);  // (wr*xr -+ wi*xi, wr*xi +- wi*xr)
     v2f out = conj_add(own, y);  // {own.x - y.x, -own.y + y.y}
     if constexpr (M == 0) {
         const float h = 0.5f * (own.x - own.y);
-        out = b == 0 ? v2f{own.x - h, -h} : out;
+        out = b0 ? v2f{own.x - h, -h} : out;
     }
     return out;
 }
+template <int M>
+__device__ __forceinline__ v2f rdft128_inv_point_m(const float *a, const FftTables *T, int b) {
+    return rdft128_inv_point_m<M>(a, T, b, b == 0);
+}
+template <int M>
+__device__ __forceinline__ v2f rdft128_inv_point_m(const float *a, const FftTables *T, int gl, HwLanes) {  // b = gl
+    return rdft128_inv_point_m<M>(a, T, gl, lanes<site::fft_inv_b0>());
+}
 
 // the same point of two rows, as a packed pair for fft64_regs_x2
-__device__ __forceinline__ Cx2 rdft128_inv_point_x2(const float *a0, const float *a1, const FftTables *T, int b, int m) {
+template <class... Map>  // Map: nothing, or HwLanes with b = gl
+__device__ __forceinline__ Cx2 rdft128_inv_point_x2(const float *a0, const float *a1, const FftTables *T, int b, int m, Map... map) {
     v2f u, w;
     switch (m) {  // m is a compile-time constant at every call site (unrolled loops)
-        case 0: u = rdft128_inv_point_m<0>(a0, T, b), w = rdft128_inv_point_m<0>(a1, T, b); break;
-        case 1: u = rdft128_inv_point_m<1>(a0, T, b), w = rdft128_inv_point_m<1>(a1, T, b); break;
-        case 2: u = rdft128_inv_point_m<2>(a0, T, b), w = rdft128_inv_point_m<2>(a1, T, b); break;
-        default: u = rdft128_inv_point_m<3>(a0, T, b), w = rdft128_inv_point_m<3>(a1, T, b); break;
+        case 0: u = rdft128_inv_point_m<0>(a0, T, b, map...), w = rdft128_inv_point_m<0>(a1, T, b, map...); break;
+        case 1: u = rdft128_inv_point_m<1>(a0, T, b, map...), w = rdft128_inv_point_m<1>(a1, T, b, map...); break;
+        case 2: u = rdft128_inv_point_m<2>(a0, T, b, map...), w = rdft128_inv_point_m<2>(a1, T, b, map...); break;
+        default: u = rdft128_inv_point_m<3>(a0, T, b, map...), w = rdft128_inv_point_m<3>(a1, T, b, map...); break;
     }
     return Cx2{v2f{u.x, w.x}, v2f{u.y, w.y}};
 }
@@ -253,13 +281,20 @@ __device__ __forceinline__ Cx2 rdft128_inv_point_x2(const float *a0, const float
 struct SplitLane {
     float wr, wi, z;
 };
-__device__ __forceinline__ SplitLane rdft128_fwd_coef(const FftTables *T, int lane) {
-    const int q = lane < 32 ? lane : 64 - lane;
+// lower, wr0, l0, l32: lane < 32, (lane & 31) == 0, lane == 0, lane == 32
+__device__ __forceinline__ SplitLane rdft128_fwd_coef(const FftTables *T, int lane, bool lower, bool wr0, bool l0, bool l32) {
+    const int q = lower ? lane : 64 - lane;
     float wr = 0.5f - T->c[32 - q], wi = T->c[q];
-    wi = lane < 32 ? wi : -wi;
-    wr = (lane & 31) == 0 ? 0.f : wr;
-    wi = lane == 0 ? 0.5f : (lane == 32 ? 0.f : wi);
-    return SplitLane{wr, wi, lane == 0 ? 0.f : 1.f};
+    wi = lower ? wi : -wi;
+    wr = wr0 ? 0.f : wr;
+    wi = l0 ? 0.5f : (l32 ? 0.f : wi);
+    return SplitLane{wr, wi, l0 ? 0.f : 1.f};
+}
+__device__ __forceinline__ SplitLane rdft128_fwd_coef(const FftTables *T, int lane) {
+    return rdft128_fwd_coef(T, lane, lane < 32, (lane & 31) == 0, lane == 0, lane == 32);
+}
+__device__ __forceinline__ SplitLane rdft128_fwd_coef(const FftTables *T, int lane, HwLanes) {
+    return rdft128_fwd_coef(T, lane, lanes<site::fwd_lower>(), lanes<site::fwd_wr0>(), lanes<site::fwd_lane0>(), lanes<site::fwd_lane32>());
 }
 __device__ __forceinline__ v2f rdft128_fwd_bin_u(const float *a, SplitLane s, int lane) {
     const v2f own = ld_pt(a, lane), other = ld_pt(a, mirror64(lane));
@@ -284,9 +319,13 @@ __device__ __forceinline__ v2f lane_fetch(v2f v, int src_lane) {
 }
 
 // KIND 0: twiddled pass (block class b), 1: closing forward, 2: closing inverse
+// The predicates of (j, b) as a set: j odd, j >= 2, and the two rotations of block 1 (b == 1 with j == 1 / j == 3)
+struct Bfly4Pred {
+    bool j_odd, j_hi, rot_p, rot_m;
+};
 template <int KIND>
-__device__ __forceinline__ v2f bfly4_lane(int j, int b, const FftTables *T, v2f A, v2f B, v2f C, v2f D) {
-    const float s1 = (j & 1) ? -1.f : 1.f, s2 = (j & 2) ? -1.f : 1.f;
+__device__ __forceinline__ v2f bfly4_lane(int j, int b, const FftTables *T, v2f A, v2f B, v2f C, v2f D, Bfly4Pred P) {
+    const float s1 = P.j_odd ? -1.f : 1.f, s2 = P.j_hi ? -1.f : 1.f;
     if constexpr (KIND == 2) {
         A.y = -A.y;
         B.y = -B.y;
@@ -295,14 +334,14 @@ __device__ __forceinline__ v2f bfly4_lane(int j, int b, const FftTables *T, v2f 
     const v2f xb = v2f{fmaf(s1, D.x, C.x), fmaf(s1, D.y, C.y)};
     v2f r;  // what is added to / subtracted from xa
     if constexpr (KIND == 2)
-        r = (j & 1) ? v2f{-xb.y, -xb.x} : v2f{xb.x, -xb.y};
+        r = P.j_odd ? v2f{-xb.y, -xb.x} : v2f{xb.x, -xb.y};
     else
-        r = (j & 1) ? v2f{-xb.y, xb.x} : xb;
+        r = P.j_odd ? v2f{-xb.y, xb.x} : xb;
     v2f t = v2f{fmaf(s2, r.x, xa.x), fmaf(s2, r.y, xa.y)};
     if constexpr (KIND != 0) return t;
     // twiddle of output j in block b: W_0 = 1; blocks 0 and 1 come out of the table like any other (bfly4_v,
     // fft_ooura.h), block 1 with its outputs 1 and 3 rotated first
-    const float ms = (b == 1 && (j & 1)) ? (j == 1 ? 1.f : -1.f) : 0.f;
+    const float ms = P.rot_p ? 1.f : (P.rot_m ? -1.f : 0.f);
     t = __builtin_elementwise_fma(v2f{-ms, ms}, swap(t), t);  // ms is 0 or +-1: exact product, one rounding (see bfly4_v)
     // W1, W2, W3 lie behind one another (FftTables): entry (j - 1) * 32 + b of the three as one array, entry 0 (= W1[0]) for
     // j == 0 -- an index computation; as a select among four pointers it compiles to nested predicated regions, a dozen scalar
@@ -313,42 +352,68 @@ __device__ __forceinline__ v2f bfly4_lane(int j, int b, const FftTables *T, v2f 
     const float *wp = &T->W1[0][0] + 2 * (j == 0 ? 0 : (j - 1) * 32 + b);
     return cmul_w(wp[0], wp[1], t);
 }
+template <int KIND>
+__device__ __forceinline__ v2f bfly4_lane(int j, int b, const FftTables *T, v2f A, v2f B, v2f C, v2f D) {
+    const bool rot = b == 1 && (j & 1);
+    return bfly4_lane<KIND>(j, b, T, A, B, C, D, Bfly4Pred{(j & 1) != 0, (j & 2) != 0, rot && j == 1, rot && j != 1});
+}
 
-template <bool INVERSE>
+template <bool INVERSE, bool HW = false>
 __device__ __forceinline__ v2f fft64_lanes(v2f pt, const FftTables *T, int lane) {
+    using namespace site;
     {  // pass 1: butterfly lane>>2 gathers the bit-reversed points rev4(bt) + {0, 32, 16, 48}
         const int bt = lane >> 2, r0 = dev_bitrev(bt, 4);
         const v2f A = lane_fetch(pt, r0), B = lane_fetch(pt, r0 + 32), C = lane_fetch(pt, r0 + 16), D = lane_fetch(pt, r0 + 48);
-        pt = bfly4_lane<0>(lane & 3, bt, T, A, B, C, D);
+        if constexpr (HW)
+            pt = bfly4_lane<0>(lane & 3, bt, T, A, B, C, D, Bfly4Pred{lanes<l1_j_odd>(), lanes<l1_j_hi>(), lanes<l1_rot_p>(), lanes<l1_rot_m>()});
+        else
+            pt = bfly4_lane<0>(lane & 3, bt, T, A, B, C, D);
     }
     {  // pass 2: stride 4
         const int base = lane & 0x33;
         const v2f A = lane_fetch(pt, base), B = lane_fetch(pt, base + 4), C = lane_fetch(pt, base + 8), D = lane_fetch(pt, base + 12);
-        pt = bfly4_lane<0>((lane >> 2) & 3, lane >> 4, T, A, B, C, D);
+        if constexpr (HW)
+            pt = bfly4_lane<0>((lane >> 2) & 3, lane >> 4, T, A, B, C, D, Bfly4Pred{lanes<l2_j_odd>(), lanes<l2_j_hi>(), lanes<l2_rot_p>(), lanes<l2_rot_m>()});
+        else
+            pt = bfly4_lane<0>((lane >> 2) & 3, lane >> 4, T, A, B, C, D);
     }
     {  // closing pass: stride 16, no twiddles
         const int base = lane & 15;
         const v2f A = lane_fetch(pt, base), B = lane_fetch(pt, base + 16), C = lane_fetch(pt, base + 32), D = lane_fetch(pt, base + 48);
-        pt = bfly4_lane<INVERSE ? 2 : 1>(lane >> 4, 0, T, A, B, C, D);
+        if constexpr (HW)
+            pt = bfly4_lane<INVERSE ? 2 : 1>(lane >> 4, 0, T, A, B, C, D, Bfly4Pred{lanes<l3_j_odd>(), lanes<l3_j_hi>(), false, false});
+        else
+            pt = bfly4_lane<INVERSE ? 2 : 1>(lane >> 4, 0, T, A, B, C, D);
     }
     return pt;
+}
+template <bool INVERSE>
+__device__ __forceinline__ v2f fft64_lanes(v2f pt, const FftTables *T, int lane, HwLanes) {
+    return fft64_lanes<INVERSE, true>(pt, T, lane);
 }
 
 // rdft128_inv_point for point == lane with the packed spectrum in registers: `own` = bin lane (lane 0: (a[0], a[1]) =
 // (bin 0, bin 64), both real), partner = bin 64 - lane fetched from its lane.
-__device__ __forceinline__ v2f rdft128_inv_point_lanes(v2f own, const FftTables *T, int lane) {
+// lower, l0, l32: lane < 32, lane == 0, lane == 32
+__device__ __forceinline__ v2f rdft128_inv_point_lanes(v2f own, const FftTables *T, int lane, bool lower, bool l0, bool l32) {
     const v2f other = lane_fetch(own, mirror64(lane));
-    const int q = lane < 32 ? lane : 64 - lane;
+    const int q = lower ? lane : 64 - lane;
     const float wkr = 0.5f - T->c[32 - q], wki = T->c[q];
-    const v2f aj = lane < 32 ? own : other, ak = lane < 32 ? other : own;  // pair (j = 2q, k = 128 - 2q)
+    const v2f aj = lower ? own : other, ak = lower ? other : own;  // pair (j = 2q, k = 128 - 2q)
     const float xr = aj.x - ak.x, xi = aj.y + ak.y;
     const float yr = wkr * xr + wki * xi, yi = wkr * xi - wki * xr;
-    float re = lane < 32 ? aj.x - yr : ak.x + yr;
-    float im = lane < 32 ? yi - aj.y : yi - ak.y;
+    float re = lower ? aj.x - yr : ak.x + yr;
+    float im = lower ? yi - aj.y : yi - ak.y;
     const float h = 0.5f * (own.x - own.y);  // lane 0: a[0] = own.x, a[1] = own.y
-    re = lane == 0 ? own.x - h : (lane == 32 ? own.x : re);
-    im = lane == 0 ? -h : (lane == 32 ? -own.y : im);
+    re = l0 ? own.x - h : (l32 ? own.x : re);
+    im = l0 ? -h : (l32 ? -own.y : im);
     return v2f{re, im};
+}
+__device__ __forceinline__ v2f rdft128_inv_point_lanes(v2f own, const FftTables *T, int lane) {
+    return rdft128_inv_point_lanes(own, T, lane, lane < 32, lane == 0, lane == 32);
+}
+__device__ __forceinline__ v2f rdft128_inv_point_lanes(v2f own, const FftTables *T, int lane, HwLanes) {
+    return rdft128_inv_point_lanes(own, T, lane, lanes<site::inv_lower>(), lanes<site::inv_lane0>(), lanes<site::inv_lane32>());
 }
 
 // value held by the lane with index rev4(gl) of the same transform (ds_bpermute: no LDS memory, no barrier)

@@ -40,6 +40,7 @@
 #include "fft_ooura.h"
 #include "libm_dev.h"
 #include "ns_layout.h"
+#include "lane_sites.h"
 
 namespace wmx {
 namespace {
@@ -150,6 +151,10 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
     constexpr int chn = CHN;  // 1 or 2 (ns_init takes nothing else): compile-time, so the mono kernel carries no high band
     // Lane-derived addresses are loop invariant; left alone the compiler hoists them out of the packet loop and
     // keeps them in VGPRs for the whole kernel.  Re-deriving them per phase is a few VALU ops and frees the registers.
+    // `lane_in` is the hardware lane id (ns_kernel: threadIdx.x & 63, blocks of 64 * kNsWavesPerBlock threads), so what a test of
+    // the lane alone selects in group k is a mask constant (lanes<>, lane_sites.h: site::ns<L> and the ns_* entries)
+    using SL = site::ns<L>;
+    static_assert(SL::M == Y::M && SL::MP == Y::MP && SL::B == Y::B, "lane_sites.h restates the layout");
     int lane = lane_in;
 #define NS_RELANE() asm volatile("" : "+v"(lane))
     NS_RELANE();
@@ -181,7 +186,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
     //      buffer (UpdateBuffer, ns_core.c:855-873).  All loads before the stores.
     // the stream's 24 scalar state words in one coalesced load; read back lane by lane (every field is read at most
     // once per frame, before it is written)
-    const float scv = lane < 24 ? ST(Y::SCALARS + lane) : 0.f;
+    const float scv = lanes<site::ns_scalars>() ? ST(Y::SCALARS + lane) : 0.f;
 #define SCF(f) lane_value(scv, Y::f - Y::SCALARS)
 #define SCI(f) __float_as_int(lane_value(scv, Y::f - Y::SCALARS))
     float buf[NT], hb[NT], synt[NT];
@@ -193,7 +198,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         // fetches both with clamped addresses and selects.
         constexpr int KEEP = L - B;  // samples carried over from the previous frame
         const bool all_old = 64 * k + 63 < KEEP, all_new = 64 * k >= KEEP;
-        const bool is_old = all_old || (!all_new && i < KEEP);
+        static_assert(KEEP == SL::KEEP, "lane_sites.h restates the layout");
+        const bool is_old = all_old || (!all_new && lanes_in(SL::old(k)));
         float o = 0.f, oh = 0.f;
         int16_t n = 0, nh = 0;
         if (!all_new) o = ST(Y::IN_BUF + (is_old ? i + B : 0));
@@ -201,7 +207,11 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         buf[k] = is_old ? o : (float)n;
         // syntBuf: its first KEEP samples carry the overlap, the rest is the zeros UpdateBuffer shifted in (ns_core.c:855-873): known, not
         // stored, not read -- 1 280 bytes per frame less traffic together with the store below
-        synt[k] = (64 * k < KEEP && i < KEEP) ? ST(Y::SYNT_BUF + (i < KEEP ? i : 0)) : 0.f;
+        // (a group entirely below KEEP needs no test; the mixed group reads under its mask, the address clamped for the others)
+        if (64 * k + 63 < KEEP)
+            synt[k] = ST(Y::SYNT_BUF + i);
+        else
+            synt[k] = (64 * k < KEEP && lanes_in(SL::old(k))) ? ST(Y::SYNT_BUF + (lanes_in(SL::old(k)) ? i : 0)) : 0.f;
         hb[k] = 0.f;
         if (chn == 2) {
             if (!all_new) oh = ST(Y::HB_BUF + (is_old ? i + B : 0));
@@ -238,7 +248,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         // whatever they were -- 640 bytes per frame that the kernel, which runs at three quarters of the device-copy rate, need not write
         const int i = lane + 64 * k;
         if (64 * k + 63 < B) continue;  // a compile-time fact per group
-        if (i >= B) {
+        if (64 * k >= B || lanes_in(SL::kept(k))) {
             ST(Y::IN_BUF + i) = buf[k];
             if (chn == 2) ST(Y::HB_BUF + i) = hb[k];
         }
@@ -274,8 +284,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         const float overdrive = 1.1f, denoise_bound = 0.125f;  // policy 2, ns_core.c:1030-1033
 
         NS_RELANE();
-        rdft_forward<NC>(W.fa, &K.tab, lane);
-        if (lane < Y::MP - M) W.r0[M + lane] = 0.f;  // the previous frame's time-domain stages (tdst) spilled into r0's zero tail
+        rdft_forward<NC>(W.fa, &K.tab, lane, HwLanes{});
+        if (lanes<SL::tail()>()) W.r0[M + lane] = 0.f;  // the previous frame's time-domain stages (tdst) spilled into r0's zero tail
         NS_PROF(1);
 
         NS_RELANE();
@@ -286,8 +296,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             // and in the last group (bin M - 1 alone) every lane evaluates that bin and lane 0 stores it -- the log chains of
             // the groups then sit in one basic block and overlap, instead of one serial pass for lane 0.
             const int b0 = lane + 64 * k;
-            const bool ok = (64 * k + 63 < M) || b0 < M;
-            const int b = ok ? b0 : M - 1;
+            const bool ok = (64 * k + 63 < M) || lanes_in(SL::bin_ok(k));
+            const int b = (64 * k + 63 < M) ? b0 : M - 1;  // the last group: b0 == M - 1 where ok
             float re, im, mg;
             if (k == NI - 1) {  // only bin M - 1 (Nyquist): real
                 re = W.fa[1];
@@ -295,7 +305,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
                 mg = fabsf(re) + 1.f;
             } else {
                 const float a0 = W.fa[2 * b], a1 = W.fa[2 * b + 1];
-                const bool dc = k == 0 && b == 0;  // bin 0 is real; fa[1] holds the Nyquist value
+                const bool dc = k == 0 && lanes<site::ns_dc>();  // bin 0 is real; fa[1] holds the Nyquist value
                 re = a0;
                 im = dc ? 0.f : a1;
                 const float g = sqrtf(re * re + im * im) + 1.f;
@@ -310,9 +320,11 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             W.lmagn[b] = lm;
             W.pause[b] = pz;
             W.r0[b] = re * re + im * im;
-            W.r1[b] = b >= kStartBand ? K.logi[b] * lm : 0.f;  // terms of the start-up sums (i >= 5, ns_core.c:1092)
-            W.r2[b] = b >= 1 ? lm : 0.f;                       // spectral flatness skips bin 0 (ns_core.c:540)
-            W.snrp[b] = b >= kStartBand ? lm : 0.f;            // snrp is free until ComputeSnr
+            static_assert(kStartBand == 5, "site::ns_from_band");
+            const bool from_band = k > 0 || lanes<site::ns_from_band>(), from_1 = k > 0 || lanes<site::ns_from_1>();
+            W.r1[b] = from_band ? K.logi[b] * lm : 0.f;  // terms of the start-up sums (i >= 5, ns_core.c:1092)
+            W.r2[b] = from_1 ? lm : 0.f;                 // spectral flatness skips bin 0 (ns_core.c:540)
+            W.snrp[b] = from_band ? lm : 0.f;            // snrp is free until ComputeSnr
         }
         wave_sync();
         NS_PROF(2);
@@ -320,7 +332,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         float signal_energy, sum_magn, avg_magn, flat_mean, avg_pause, sum_log_magn = 0.f, sum_log_i_log_magn = 0.f;
         {
             const float *mine =
-                lane == 1 ? W.magn : (lane == 2 ? W.r2 : (lane == 3 ? W.pause : (lane == 4 ? W.snrp : (lane == 5 ? W.r1 : W.r0))));
+                lanes<site::ns_pick1>() ? W.magn : (lanes<site::ns_pick2>() ? W.r2 : (lanes<site::ns_pick3>() ? W.pause : (lanes<site::ns_pick4>() ? W.snrp : (lanes<site::ns_pick5>() ? W.r1 : W.r0))));
             const float acc = sum_lanes<Y::MP / 4>(mine);
             // the four divisions by M the frame makes of these sums, each in its own lane: one division sequence for the wave
             // instead of one per wave-uniform quotient (same operands, same operation)
@@ -359,8 +371,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int b0 = lane + 64 * k;
-            const bool ok = (64 * k + 63 < M) || b0 < M;  // compile-time true except in the last group (bin M - 1 alone)
-            const int b = ok ? b0 : M - 1;
+            const bool ok = (64 * k + 63 < M) || lanes_in(SL::bin_ok(k));  // compile-time true except in the last group (bin M - 1 alone)
+            const int b = (64 * k + 63 < M) ? b0 : M - 1;
             const float lm = W.lmagn[b];
             float quant = pf_quant[k], lq = 0.f;
 #pragma unroll
@@ -456,8 +468,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int b0 = lane + 64 * k;
-            const bool ok = (64 * k + 63 < M) || b0 < M;  // see the noise estimation loop
-            const int b = ok ? b0 : M - 1;
+            const bool ok = (64 * k + 63 < M) || lanes_in(SL::bin_ok(k));  // see the noise estimation loop
+            const int b = (64 * k + 63 < M) ? b0 : M - 1;
             const float mg = W.magn[b], nz = W.noise[b];
             const float np = pf_nprev[k];
             // div_ordinary: magnitudes are 0 (a stream's first frame) or in [1, 2^24] (|X| + 1 of 256 int16 samples), noise
@@ -479,8 +491,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int b0 = lane + 64 * k;
-            const bool ok = (64 * k + 63 < M) || b0 < M;  // see the noise estimation loop
-            const int b = ok ? b0 : M - 1;
+            const bool ok = (64 * k + 63 < M) || lanes_in(SL::bin_ok(k));  // see the noise estimation loop
+            const int b = (64 * k + 63 < M) ? b0 : M - 1;
             // the prior SNR (ComputeSnr, ns_core.c:566-588): only this lane's bin is needed, so a register and not an LDS array
             const float sp = 0.98f * t_prev[k] + (1.f - 0.98f) * t_snrq[k];
             const float t1 = 1.f + 2.f * sp;
@@ -505,7 +517,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         }
         float cov, var_pause, var_magn, ksum;
         {
-            const float acc = sum_lanes<Y::MP / 4>(lane == 1 ? W.r2 : (lane == 2 ? W.lmagn : (lane == 3 ? W.sprob : W.r0)));
+            const float acc = sum_lanes<Y::MP / 4>(lanes<site::ns_pick1>() ? W.r2 : (lanes<site::ns_pick2>() ? W.lmagn : (lanes<site::ns_pick3>() ? W.sprob : W.r0)));
             const float mean = acc / ((float)M);  // one division sequence, as above
             cov = lane_value(mean, 0);
             var_pause = lane_value(mean, 1);
@@ -528,7 +540,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         if (update_flag >= 1) {
             const int countdown = SCI(S_COUNTDOWN) - 1;
             if (countdown > 0) {
-                if (lane == 0) {
+                if (lanes<site::ns_lane0>()) {
                     // counter++ as a no-return 32-bit atomic on the dword that holds the uint16 (a counter never exceeds
                     // the 500-frame window, so the low half cannot carry into the high one): nothing waits for HBM
                     auto bump = [&](int i) { atomicAdd(reinterpret_cast<unsigned *>(hist) + (i >> 1), (i & 1) ? 0x10000u : 1u); };
@@ -700,7 +712,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             if (feat_diff < thr_diff) width = 2.f * 4.0f;
             const float a2 = width * (feat_diff - thr_diff);
             // the three indicator tanh's are wave-uniform scalars: evaluate them in lanes 0..2 of one call
-            const float th = fast_tanh(lane == 1 ? a1 : (lane == 2 ? a2 : a0), K.lm);
+            const float th = fast_tanh(lanes<site::ns_pick1>() ? a1 : (lanes<site::ns_pick2>() ? a2 : a0), K.lm);
             const float ind0 = 0.5f * (lane_value(th, 0) + 1.f);
             const float ind1 = 0.5f * (lane_value(th, 1) + 1.f);
             const float ind2 = 0.5f * (lane_value(th, 2) + 1.f);
@@ -714,8 +726,8 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int b0 = lane + 64 * k;
-            const bool ok = (64 * k + 63 < M) || b0 < M;
-            const int b = ok ? b0 : M - 1;
+            const bool ok = (64 * k + 63 < M) || lanes_in(SL::bin_ok(k));
+            const int b = (64 * k + 63 < M) ? b0 : M - 1;  // the last group: b0 == M - 1 where ok
             float inv = fast_exp(-W.sprob[b], K.lm);  // still the log likelihood ratio average of this bin
             inv = gain_prior * inv;
             const float spb = 1.f / (1.f + inv);
@@ -729,11 +741,11 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 #pragma unroll
         for (int k = 0; k < NI; k++) {
             const int b0 = lane + 64 * k;
-            const bool ok = (64 * k + 63 < M) || b0 < M;  // see the noise estimation loop
-            const int b = ok ? b0 : M - 1;
+            const bool ok = (64 * k + 63 < M) || lanes_in(SL::bin_ok(k));  // see the noise estimation loop
+            const int b = (64 * k + 63 < M) ? b0 : M - 1;
             const float ps = W.sprob[b], pn = 1.f - ps, mg = W.magn[b], np = pf_nprev[k];
             float gamma_old = 0.9f;
-            if (b > 0 && W.sprob[b - 1] > 0.2f) gamma_old = 0.99f;
+            if ((k > 0 || lanes<site::ns_from_1>()) && W.sprob[b - 1] > 0.2f) gamma_old = 0.99f;
             const float tmp = gamma_old * np + (1.f - gamma_old) * (pn * mg + ps * np);
             float gamma = 0.9f;
             if (ps > 0.2f) gamma = 0.99f;
@@ -777,9 +789,9 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
             ST(Y::MAGN_PREV + b) = mg;
             ST(Y::NOISE_PREV + b) = nz;
             W.snrp[b] = f;  // the filter, for the high-band gain
-            if (b == 0)
+            if (k == 0 && lanes<site::ns_dc>())
                 W.fa[0] = re;
-            else if (b == M - 1)
+            else if (k == NI - 1)  // b == M - 1: only in the last group, and for every lane of it that is `ok`
                 W.fa[1] = re;
             else {
                 W.fa[2 * b] = re;
@@ -789,7 +801,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
         wave_sync();
         NS_PROF(9);
         NS_RELANE();
-        rdft_inverse<NC>(W.fa, &K.tab, lane);
+        rdft_inverse<NC>(W.fa, &K.tab, lane, HwLanes{});
         NS_PROF(10);
         float td[NT];
 #pragma unroll
@@ -807,7 +819,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 #pragma unroll
             for (int k = 0; k < NT; k++) W.fa[lane + 64 * k] = e1[k];
             wave_sync();
-            const float acc = sum_lanes<L / 4>(lane == 1 ? W.fa : tdst);
+            const float acc = sum_lanes<L / 4>(lanes<site::ns_pick1>() ? W.fa : tdst);
             const float energy2 = lane_value(acc, 0), energy1 = lane_value(acc, 1);
             float gain = sqrtf(energy2 / (energy1 + 1.f));
             float factor1 = 1.f, factor2 = 1.f;
@@ -854,7 +866,7 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
 #pragma unroll
     for (int k = 0; k < NT; k++) {
         const int i = lane + 64 * k;
-        if (i >= B) ST(Y::SYNT_BUF + i - B) = synt[k];
+        if (64 * k >= B || (64 * k + 63 >= B && lanes_in(SL::kept(k)))) ST(Y::SYNT_BUF + i - B) = synt[k];
         tdst[i] = sat16f(synt[k]);
         // HB output: the OLDEST block of the (already slid) high-band buffer, times the gain (zero-energy frames pass
         // it through unscaled, ns_core.c:1255-1265)

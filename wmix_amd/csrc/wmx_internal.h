@@ -308,6 +308,54 @@ __device__ __forceinline__ void row_st(GlobalF row, unsigned idx, float v) {
     *(GlobalF)((char __attribute__((address_space(1))) *)row + 4u * idx) = v;
 }
 
+// ---- lane predicates as scalar mask constants
+// A test such as `lane == 0`, `lane < 32` or `(lane & 3) == 2` selects a set of lanes that is known when the kernel is compiled, but
+// the compiler cannot know that `lane` is the hardware lane id and spends a v_cmp (and often the v_and / v_lshr in front of it) per
+// test on the vector ALU.  lanes<M>() is the same predicate taken from the scalar side: "this lane is in M", bit l of M standing for
+// hardware lane l, ANDed with EXEC as every predicate is.  A select on it is s_mov_b64 + v_cndmask_b32, an `if` an s_and_saveexec_b64
+// of the constant; no vector compare.
+// PRECONDITION: the caller's `lane` IS the hardware lane id -- wave64, lane = threadIdx.x & 63 (or threadIdx.x in a 64-thread
+// block) and a block size that is a multiple of 64.  A kernel that relabels its lanes keeps the arithmetic form.
+// tests/test_lane_masks_gpu.py evaluates every mask in use (lane_sites.h) beside the arithmetic predicate it replaces.
+template <uint64_t M>
+__device__ __forceinline__ bool lanes() {
+    return __builtin_amdgcn_inverse_ballot_w64(M);
+}
+// ... and for a mask that is a constant only once its loop is unrolled (the group index k of a `#pragma unroll` loop is no constant
+// expression): `m` must be the same in every lane, and must fold to a constant for the predicate to be free
+__device__ __forceinline__ bool lanes_in(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// HwLanes: tag of the overloads (fft_ooura.h, fft_regs.h) for callers whose `lane` is the hardware lane id: every predicate of the lane
+// alone is then a mask constant of lane_sites.h.  The overloads without the tag keep the arithmetic form and hold under any mapping.
+struct HwLanes {};
+// the mask builders: call sites read as the test they replace
+constexpr uint64_t lane_lt(int n) { return n <= 0 ? 0ull : (n >= 64 ? ~0ull : (1ull << n) - 1ull); }  // lane < n
+constexpr uint64_t lane_ge(int n) { return ~lane_lt(n); }                                             // lane >= n
+constexpr uint64_t lane_eq(int n) { return n < 0 || n > 63 ? 0ull : 1ull << n; }                      // lane == n
+constexpr uint64_t lane_plus_lt(int off, int n) { return lane_lt(n - off); }                           // lane + off < n
+constexpr uint64_t lane_plus_ge(int off, int n) { return lane_ge(n - off); }                           // lane + off >= n
+constexpr uint64_t lanes_where(int and_mask, int value) {                                            // (lane & and_mask) == value
+    uint64_t m = 0;
+    for (int l = 0; l < 64; l++)
+        if ((l & and_mask) == value) m |= 1ull << l;
+    return m;
+}
+constexpr uint64_t every(int period, int phase) {  // lane % period == phase
+    uint64_t m = 0;
+    for (int l = 0; l < 64; l++)
+        if (l % period == phase) m |= 1ull << l;
+    return m;
+}
+constexpr uint64_t lane_bit(int k) { return lanes_where(1 << k, 1 << k); }  // bit k of the lane id is set
+// the lane sets of the register FFTs (fft_regs.h): a transform is the 16 lanes with the same g = lane & 3, gl = lane >> 2 its index
+constexpr uint64_t fft_g_eq(int g) { return every(4, g); }                   // g == n
+constexpr uint64_t fft_g_ge(int g) {                                         // g >= n
+    uint64_t m = 0;
+    for (int k = g < 0 ? 0 : g; k < 4; k++) m |= every(4, k);
+    return m;
+}
+constexpr uint64_t fft_gl_eq(int n) { return lanes_where(0x3c, n << 2); }    // gl == n          (pass 1: butterfly b = gl)
+constexpr uint64_t fft_gl_hi_eq(int n) { return lanes_where(0x30, n << 4); }  // (gl >> 2) == n  (pass 2: butterfly b = gl >> 2)
+
 // refill of block-layout state ([stream][words]) for a list of streams: one workgroup per listed stream
 template <class T>
 __global__ void fill_rows_idx(T *state, const T *tmpl, int words, const int32_t *idx, int n_idx) {
