@@ -1,7 +1,7 @@
 /* host_conf.c -- a conference bridge of RTP/G.711 legs from plain C: the library's C ABI alone (wmx_conf_*), not even the HIP runtime API.
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
- *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate]
+ *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -31,6 +31,9 @@
  * (wmx_conf_gate): a row is shifted right by the leg's `reduce`, which starts at 4 -- a call is heard in full from its fifth row; the JSON
  * line then carries "gate": 1 and the rows judged voice and not, summed over the legs ("voiced", "unvoiced": wmx_conf_export_gate).  It
  * combines with every other flag.
+ * --echo D: every leg's rows go through the leg's own echo canceller between the suppressor and the AGC, with what the bridge sent to
+ * that leg as the far end and D ms (0 .. 500) as every leg's reported delay (wmx_conf_echo); the JSON line then carries "echo": D and the
+ * legs whose canceller has left its start-up ("echo_running": wmx_conf_export_echo).  It combines with every other flag.
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -162,7 +165,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G, 
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
-                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate]\n";
+                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -170,7 +173,7 @@ int main(int argc, char **argv) {
     const int G = atoi(argv[2]), T = atoi(argv[3]);
     const char *sizes = NULL, *speakers = NULL, *platform = "alsa";
     unsigned long seed = 0;
-    int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0, level = -1, gate = 0; /* max_gap -1: sequencing off; level -1: levelling off */
+    int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0, level = -1, gate = 0, echo = -1; /* max_gap -1: sequencing off; level -1: levelling off; echo -1: off */
     long correct = -1; /* -1: the library's default = platform/alsa */
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
@@ -192,6 +195,12 @@ int main(int argc, char **argv) {
             denoise = 1;
         } else if (!strcmp(argv[i], "--gate")) {
             gate = 1;
+        } else if (!strcmp(argv[i], "--echo") && i + 1 < argc) {
+            echo = atoi(argv[++i]);
+            if (echo < 0) {
+                fprintf(stderr, usage, argv[0]);
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--level") && i + 1 < argc) {
             level = atoi(argv[++i]);
             if (level < 0) {
@@ -248,6 +257,7 @@ int main(int argc, char **argv) {
     if (denoise) WMX_OK(wmx_conf_denoise(h, 1));
     if (level >= 0) WMX_OK(wmx_conf_level(h, 1, level));
     if (gate) WMX_OK(wmx_conf_gate(h, 1));
+    if (echo >= 0) WMX_OK(wmx_conf_echo(h, 1, echo));
     int n_ulaw = 0;
     for (int g = 0; g < G; g++) {
         const int32_t leg = g;
@@ -331,6 +341,14 @@ int main(int argc, char **argv) {
         for (int g = 0; g < G; g++) n_voiced += cnt[g], n_unvoiced += cnt[G + g];
         free(cnt);
     }
+    int echo_running = 0;
+    if (echo >= 0) {
+        int32_t *startup = calloc((size_t)G, sizeof(int32_t));
+        if (!startup) return 2;
+        WMX_OK(wmx_conf_export_echo(h, startup, NULL, NULL, NULL, NULL));
+        for (int g = 0; g < G; g++) echo_running += startup[g] == 0;
+        free(startup);
+    }
     uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
@@ -358,6 +376,7 @@ int main(int argc, char **argv) {
     if (denoise) printf("\"denoise\": 1, ");
     if (level >= 0) printf("\"level\": %d, ", level);
     if (gate) printf("\"gate\": 1, \"voiced\": %lu, \"unvoiced\": %lu, ", n_voiced, n_unvoiced);
+    if (echo >= 0) printf("\"echo\": %d, \"echo_running\": %d, ", echo, echo_running);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

@@ -455,6 +455,44 @@ int wmx_aecm_import_cohort(wmx_aecm *h, int cohort, const void *host_blob);
 int wmx_aecm_run_cohorts(wmx_aecm *h, int mode, const int16_t *d_far, long far_packet_stride, long far_group_stride,
                          const int16_t *d_near, int16_t *d_out, int n_packets, long stream_stride, long packet_stride,
                          const int32_t *delay_ms, const uint8_t *cohort_on, int32_t *cohort_rc, void *stream);
+/* Echo control for the legs of a conference bridge: one canceller per leg, the leg's own sent audio as its far end.
+ * wmx_aecm_create_legs makes n_legs cancellers, each the reference's handle aec_init(1, 8000, 20) that lives as long as the call does:
+ * stream g is leg g, with a near state, far-end buffers AND a control plane of its own, all on the device -- a leg's call pattern
+ * differs from every other leg's from the first jittered tick, so nothing is planned on the host and there are no cohorts: every
+ * cohort entry point (wmx_aecm_run, _run_cohorts, _cohorts, _add_ / _retire_ / _reset_cohort, _coalesce, _live_cohorts, _cohort_key,
+ * _cohort_state_bytes, _export_ / _import_cohort) returns WMX_ESTATE with a text on such a handle.  About 49 KB per leg, of which
+ * 34.8 KB are the 256 far spectra the canceller looks back into.
+ * wmx_aecm_process_legs, per tick, for every leg, in this order:
+ *   1. the near rows.  Rows, strides, lengths, call lists and their refusals are those of wmx_nsx_process_legs: the leg's rows are
+ *      taken in the order the load makes its calls, every row taken is ONE aec_process of 160 frames with the leg's reported delay, in
+ *      place; a silence call or a data call on a row that is not readable feeds nothing; a row that is not taken -- late, duplicate,
+ *      refused -- keeps its bytes.
+ *   2. the far row.  d_far + g * far_leg_stride: the 160 samples this tick sent to leg g (what its speaker plays), one
+ *      aec_setFrameFar of 160 frames.
+ * d_pcm == NULL && d_len == NULL: far only; d_far == NULL: rows only; a far-only and a rows-only call compose to the combined one.  A
+ * leg with no row this tick still buffers its far row: its far ring and control plane move, its near state (3.4 KB) is neither loaded
+ * nor stored.  A leg switched off by wmx_aecm_set_active does neither step.  The bits are the reference's handle called in that
+ * order (and those of wmx_aecm_run_cohorts with one cohort per leg, called alike); farendOld[1] starts as zeros, as above.
+ * WHAT IT DOES: with a speech-like far end, an echo of 0.3 x far delayed by 517 samples and a reported delay of 20 ms, the echo's rms
+ * falls to 0.10 - 0.14 of what it was within five seconds.  Stationary coloured noise and a tiled one-second excerpt do not
+ * converge: the delay estimator needs a signal that is not periodic.  An echo path shorter than the reported delay is non-causal and
+ * is not cancelled (517 -> 37 samples at 60 ms: 0.6).
+ * WMX_EINVAL, nothing launched: a handle not made by wmx_aecm_create_legs; d_pcm and d_len and d_far all NULL; with rows, what
+ * wmx_nsx_process_legs refuses; d_far on an odd address, or far_leg_stride < 160 with more than one leg.
+ * wmx_aecm_set_delay_legs: the reported delay (ms in the sound card's buffers, 0 .. 500, else WMX_EINVAL and nothing changes -- the
+ * wrapper's "-1, output unwritten" therefore cannot occur at run time) of the n legs listed in the host array idx, NULL: of all legs.
+ * 0 at create; kept across wmx_aecm_reset_streams, like the AGC's gain.
+ * wmx_aecm_export_legs: device arrays of n_legs int32, any of them NULL -- ec_startup (1 until the far ring has filled to the
+ * reported delay), the far ring's fill in ms, knownDelay (samples), and the delay estimator's last_delay in 64-sample blocks (-2 before a
+ * first estimate).
+ * On such a handle wmx_aecm_reset_streams leaves the listed legs as aec_init does, far end and control plane included (cohort ignored);
+ * wmx_aecm_set_active works as on any handle; wmx_aecm_export_stream / _import_stream carry the leg's WHOLE state -- near state,
+ * far-end buffers, control plane, reported delay -- in one versioned blob of wmx_aecm_stream_state_bytes (cohort ignored). */
+int wmx_aecm_create_legs(wmx_aecm **out, int n_legs);
+int wmx_aecm_process_legs(wmx_aecm *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                          const uint32_t *d_calls, const int16_t *d_far, long far_leg_stride, void *stream);
+int wmx_aecm_set_delay_legs(wmx_aecm *h, const int32_t *idx, int n, int delay_ms, void *stream);
+int wmx_aecm_export_legs(wmx_aecm *h, int32_t *d_startup, int32_t *d_far_ms, int32_t *d_known_delay, int32_t *d_delay_blocks, void *stream);
 /* the fixed-point stage handles of a chain made with WMX_CHAIN_NSX / WMX_CHAIN_AECM (NULL otherwise) */
 wmx_nsx *wmx_chain_nsx(wmx_chain *h);
 wmx_aecm *wmx_chain_aecm(wmx_chain *h);
@@ -666,6 +704,11 @@ int wmx_rtp_ingest_legs(int n_legs, int max_packets, const uint8_t *d_packets, l
  * wmx_rtp_reset_streams: seq = timestamp = 0 for the n senders host_idx lists (NULL = all), on `stream`: what
  * wmix_thread_rtp_send_pcma starts a call from (src/wmixTask.c:1058).  A bad index: WMX_EINVAL, nothing reset. */
 int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet_stride, uint32_t *packet_bytes, void *stream);
+/* What each leg was sent, as its phone's speaker plays it: the 160 G.711 codes behind the 12-byte header of leg g's outgoing datagram
+ * (d_packets + g * packet_stride, what wmx_rtp_egress_rings has just written) decoded with leg g's outgoing law (wmx_rtp_set_codecs;
+ * the law of create until then) into d_pcm + g * pcm_leg_stride (samples; d_pcm on a 2-byte boundary).  The far end of the leg's echo
+ * canceller (wmx_aecm_process_legs).  WMX_EINVAL: a NULL pointer, packet_stride < 172, pcm_leg_stride < 160 with more than one leg. */
+int wmx_rtp_decode_sent_legs(wmx_rtp *h, const uint8_t *d_packets, long packet_stride, int16_t *d_pcm, long pcm_leg_stride, void *stream);
 int wmx_rtp_reset_streams(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
 int wmx_rtp_export(wmx_rtp *h, int stream_index, uint16_t *seq, uint32_t *timestamp);
 /* Reorder, de-duplicate and gap-fill legs by RTP sequence number, between wmx_rtp_ingest_legs and the selection / the load
@@ -953,6 +996,21 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * wmx_vad (NULL until the first switch-on), for wmx_vad_export_stream / wmx_vad_import_stream on a leg.  wmx_conf_export_gate: reduce
  * (uint8, 0 .. 4), voiced and unvoiced (uint32: the rows taken that were judged voice, after hangover, and those that were not) of
  * every leg, any pointer NULL; blocking; before the first switch-on reduce is 4 and the counts are 0.
+ * wmx_conf_echo(h, on, delay_ms): between submits; off is the default.  A speakerphone or a hybrid on one leg returns the whole
+ * conference to every other ear, wins a talker slot doing so, and concealment then repeats it: the classic reason a bridge has a
+ * canceller per port.  The far end of leg g is the datagram the handle itself sent to leg g.  On, wmx_aecm_process_legs runs twice per
+ * tick: with the ROWS alone between the denoiser and the leveller (behind the DTMF detection where the denoiser is off) -- the order of
+ * the reference's record heartbeat, NS -> AEC -> AGC -> VAD (src/wmix.c:613-709) --, every row a leg's load will consume one
+ * aec_process of 160 frames of the leg's own canceller (aec_init(1, 8000, 20) in the AECM build) with the leg's reported delay, in
+ * place, in the order the load consumes them; and with the FAR ROW alone behind wmx_rtp_egress_rings: the 160 G.711 codes of the
+ * datagram this tick sent to the leg, decoded with the law they were encoded in (wmx_rtp_decode_sent_legs), one aec_setFrameFar.  The
+ * selection, the concealment history and the load see the cancelled rows.  A leg with no row this tick still buffers its far row.  The
+ * first switch-on makes the canceller (about 49 KB per leg) and the far rows, every leg at delay_ms; a later one sets every leg to
+ * delay_ms again; a delay outside 0 .. 500 is WMX_EINVAL and changes nothing, the switch included; off does not look at it, runs the
+ * launches of a handle that never heard of it, and off and on again keeps the state.  wmx_conf_reset_legs gives the listed legs a
+ * fresh canceller, far end and control plane included; the reported delay stays.  wmx_conf_canceller: the legs' wmx_aecm (NULL until
+ * the first switch-on), for wmx_aecm_set_delay_legs and wmx_aecm_export_stream / _import_stream on a leg.  wmx_conf_export_echo:
+ * what wmx_aecm_export_legs gives, into host arrays of n_legs int32, any pointer NULL; blocking; before the first switch-on 1, 0, 0, -2.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -979,6 +1037,9 @@ wmx_agc *wmx_conf_leveller(wmx_conf *h);
 int wmx_conf_gate(wmx_conf *h, int on);
 wmx_vad *wmx_conf_gater(wmx_conf *h);
 int wmx_conf_export_gate(wmx_conf *h, uint8_t *reduce, uint32_t *voiced, uint32_t *unvoiced, void *stream);
+int wmx_conf_echo(wmx_conf *h, int on, int delay_ms);
+wmx_aecm *wmx_conf_canceller(wmx_conf *h);
+int wmx_conf_export_echo(wmx_conf *h, int32_t *startup, int32_t *far_ms, int32_t *known_delay, int32_t *delay_blocks, void *stream);
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
 int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);

@@ -81,7 +81,10 @@ side's rows are put back in front of every call, outside the timed region: a row
 --gate-kernel N: nothing of the above; the gate's kernel alone, device time (events), on N legs: wmx_vad_process_legs on one row per leg
 against wmx_vad_process (1 x 8000, 20 ms packets, its four-wave pipeline kernel) on a dense plane of the same rows -- the dense side
 twice in every repetition -- and then with one leg in eight sending.
-    python tools_dev/bridge_bench.py --gate-kernel 4096 --out profiles/bridge/bridge_gate_bench.json"""
+    python tools_dev/bridge_bench.py --gate-kernel 4096 --out profiles/bridge/bridge_gate_bench.json
+--echo D: nothing of the above; the resident tick of wmx_conf on --echo-legs legs (4 096) with echo control off and on at a reported delay
+of D ms, and wmx_aecm_process_legs alone on one row per leg, device time (events)
+    python tools_dev/bridge_bench.py --echo 20 --out profiles/bridge/bridge_echo_bench.json"""
 import argparse
 import json
 import os
@@ -390,6 +393,65 @@ def stage_kernel(stage, legs, reps, value=None, rows=1):
     return {"legs": legs, **head, name + "_dense": d0, name + "_dense_again": d1, name + "_legs_every_leg": full,
             name + "_legs_one_leg_in_eight": sparse, "dense_again_over_dense": round(d1["median_ms"] / d0["median_ms"], 4),
             "legs_over_dense": round(full["median_ms"] / d0["median_ms"], 4), "one_in_eight_over_dense": round(sparse["median_ms"] / d0["median_ms"], 4)}
+
+
+def echo_tick(legs, reps, delay_ms):
+    """--echo D: the resident step of wmx_conf on `legs` legs in conferences of 8, every leg one packet per tick, with echo control off and
+    on (wmx_conf_echo, reported delay D), two handles, the sides alternating tick by tick, device time per tick (events) behind 40 ticks
+    of warm-up -- every canceller is past its start-up --; and wmx_aecm_process_legs alone, rows and far row in one call, one row per leg."""
+    from wmix_amd.aecm import AecmBatch
+    from wmix_amd.conf import ConfBridge
+    layout = [list(range(c, min(c + 8, legs))) for c in range(0, legs, 8)]
+    rng = np.random.default_rng(13)
+    CYC = 3
+    pk = rng.integers(0, 256, (CYC, legs, 3, 176), dtype=np.uint8)
+    pk[..., :12] = 0
+    pk[..., 0], pk[..., 1] = 0x80, 0x88
+    recv = np.zeros((CYC, legs, 3), np.int32)
+    recv[:, :, 0] = 172
+    r_in, r_recv = torch.from_numpy(pk).cuda(), torch.from_numpy(recv).cuda()
+    r_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+    sides = {}
+    for name in ("off", "on"):
+        cb = ConfBridge(legs, 1, 3)
+        cb.set_conferences(layout)
+        cb.set_play_correct(0)
+        if name == "on":
+            cb.echo(True, delay_ms)
+        sides[name] = cb
+    ms = {"off": [], "on": []}
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for i in range(40 + reps):
+        for name, cb in sides.items():
+            a.record()
+            cb.step_resident(r_in[i % CYC], r_recv[i % CYC], r_out)
+            b.record()
+            b.synchronize()
+            if i >= 40:
+                ms[name].append(a.elapsed_time(b))
+    running = int((sides["on"].export_echo()["startup"] == 0).sum())
+    for cb in sides.values():
+        cb.close()
+    ab = AecmBatch.create_legs(legs)
+    ab.set_delay_legs(delay_ms)
+    rows = torch.from_numpy(rng.integers(-3000, 3000, (legs, 1, 160)).astype(np.int16)).cuda()
+    far = torch.from_numpy(rng.integers(-3000, 3000, (legs, 160)).astype(np.int16)).cuda()
+    lens = torch.full((legs, 1), 320, dtype=torch.int32, device="cuda")
+    alone = []
+    for i in range(40 + reps):
+        work = rows.clone()
+        a.record()
+        ab.process_legs(work, lens, None, far)
+        b.record()
+        b.synchronize()
+        if i >= 40:
+            alone.append(a.elapsed_time(b))
+    state_bytes = int(ab.export_stream(0).size)
+    ab.close()
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    return {"legs": legs, "conferences": len(layout), "delay_ms": delay_ms, "legs_past_startup": running, "ms_per_tick_echo_off": med["off"],
+            "ms_per_tick_echo_on": med["on"], "ms_per_tick_added": med["on"] - med["off"], "aecm_process_legs_one_row_ms": float(np.median(alone)),
+            "bytes_per_leg_blob": state_bytes}
 
 
 def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False, level=-1):
@@ -831,6 +893,8 @@ if __name__ == "__main__":
     ap.add_argument("--denoise", action="store_true", help="with --pipe: two more sides with denoising on, and the new kernel alone beside the dense call")
     ap.add_argument("--level", type=int, default=-1, help="with --pipe: two more sides with levelling on at this compression gain, and the new kernel alone beside the dense call")
     ap.add_argument("--gate-kernel", type=int, default=0, help="wmx_vad_process_legs alone on this many legs beside wmx_vad_process on the same rows; nothing else")
+    ap.add_argument("--echo", type=int, default=-1, help="the resident tick on --echo-legs legs with echo control off and on at this reported delay (ms), and the kernel alone; nothing else")
+    ap.add_argument("--echo-legs", type=int, default=4096)
     ap.add_argument("--steady", action="store_true", help="with --pipe: every leg sends one packet per tick, on all sides alike")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -844,6 +908,11 @@ if __name__ == "__main__":
     if args.gate_kernel > 0:
         res = {"tool": "bridge_bench --gate-kernel", "device": torch.cuda.get_device_name(0), "reps": args.reps,
                "runs": "the builder's own, one process, the sides alternating", "gate_kernel": stage_kernel("gate", args.gate_kernel, args.reps), "load": [], "tick": None}
+        args.sizes = args.tick = ""
+        args.ragged, args.speakers, args.pipe = False, 0, False
+    if args.echo >= 0:
+        res = {"tool": "bridge_bench --echo", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+               "runs": "the builder's own, one process, the sides alternating", "echo": echo_tick(args.echo_legs, args.reps, args.echo), "load": [], "tick": None}
         args.sizes = args.tick = ""
         args.ragged, args.speakers, args.pipe = False, 0, False
     if args.pipe:

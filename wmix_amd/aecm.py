@@ -6,6 +6,7 @@ import ctypes as C
 import torch
 
 from .lifetime import Lifetime
+from ._legs import process_legs
 from ._lib import check, lib
 
 
@@ -22,6 +23,51 @@ class AecmBatch(Lifetime):
         self.n_streams, self.chn, self.freq = n_streams, chn, freq
         self.pkt = lib().wmx_aecm_packet_samples(self._h)
         self.state_bytes = lib().wmx_aecm_state_bytes(self._h)
+
+    # ---- echo control for the legs of a conference bridge (wmx_aecm_create_legs: one canceller per leg, no cohorts)
+    @classmethod
+    def create_legs(cls, n_legs):
+        """n_legs cancellers, each aec_init(1, 8000, 20) with far-end buffers and a control plane of its own on the device"""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        rc = lib().wmx_aecm_create_legs(C.byref(self._h), n_legs)
+        if rc != 0:
+            self._h = None
+            check(rc, "wmx_aecm_create_legs")
+        self.n_streams, self.chn, self.freq, self.n_cohorts = n_legs, 1, 8000, 0
+        self.pkt = lib().wmx_aecm_packet_samples(self._h)
+        self.state_bytes = lib().wmx_aecm_state_bytes(self._h)
+        return self
+
+    def process_legs(self, pcm, lens, calls=None, far=None, far_leg_stride=None):
+        """wmx_aecm_process_legs on the current stream: the rows this tick brought each leg (pcm int16 CUDA [n_legs, max_packets,
+        >= 160], lens, calls as the other stages' process_legs; pcm None and lens None: no rows), then the row it was sent (far int16
+        CUDA [n_legs, >= 160], or an address with far_leg_stride; None: rows only)"""
+        if far is not None and not isinstance(far, int):
+            assert far.is_cuda and far.dtype == torch.int16 and far.dim() == 2 and far.shape[0] == self.n_streams and far.shape[1] >= 160
+            assert far.stride(1) == 1
+            far, far_leg_stride = far.data_ptr(), far.stride(0)
+        extras = (far, int(far_leg_stride or 0))
+        if pcm is None:
+            assert lens is None and calls is None
+            check(lib().wmx_aecm_process_legs(self._h, None, 0, 0, 1, None, None, *extras, torch.cuda.current_stream().cuda_stream),
+                  "wmx_aecm_process_legs")
+            return None
+        return process_legs(self, "wmx_aecm_process_legs", pcm, lens, calls, *extras)
+
+    def set_delay_legs(self, delay_ms, legs=None):
+        """the reported delay (0 .. 500 ms) of the listed legs, None: of all; kept across reset_streams"""
+        import numpy as np
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        check(lib().wmx_aecm_set_delay_legs(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, int(delay_ms),
+                                            torch.cuda.current_stream().cuda_stream), "wmx_aecm_set_delay_legs")
+
+    def export_legs(self):
+        """-> (ec_startup, far ring fill in ms, knownDelay, the estimator's last_delay): numpy int32 [n_legs] each"""
+        out = torch.zeros((4, self.n_streams), dtype=torch.int32, device="cuda")
+        check(lib().wmx_aecm_export_legs(self._h, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
+                                         torch.cuda.current_stream().cuda_stream), "wmx_aecm_export_legs")
+        return tuple(out.cpu().numpy())
 
     def _run(self, mode, far, near, out, n_packets, stream_stride, packet_stride, delay_ms):
         fp = far.data_ptr() if far is not None else None

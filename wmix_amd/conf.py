@@ -143,6 +143,35 @@ class ConfBridge:
               "wmx_conf_export_gate")
         return r
 
+    def echo(self, on, delay_ms=20):
+        """every leg's rows go through the leg's own fixed-point echo canceller between the denoiser and the leveller, with what the
+        handle sent to that leg as the far end and delay_ms (0 .. 500) as every leg's reported delay (wmx_conf_echo), between submits;
+        off (the default) = the launches of before, and the cancellers' state stays"""
+        check(lib().wmx_conf_echo(self._h, 1 if on else 0, int(delay_ms)), "wmx_conf_echo")
+
+    def canceller_state(self, leg):
+        """the blob of one leg's canceller -- near state, far end, control plane, delay (wmx_aecm_export_stream on wmx_conf_canceller);
+        None before the first echo(True)"""
+        return self._stage_state("wmx_conf_canceller", "wmx_aecm", leg)
+
+    def set_leg_echo_delay(self, legs, delay_ms):
+        """the reported delay of the listed legs' cancellers (wmx_aecm_set_delay_legs on wmx_conf_canceller), between submits, ordered on
+        the current stream.  Needs a handle that has cancelled before."""
+        L = lib()
+        aecm = L.wmx_conf_canceller(self._h)
+        if not aecm:
+            raise ValueError("set_leg_echo_delay: no canceller yet (echo(True, delay_ms) makes it)")
+        idx = np.ascontiguousarray(legs, dtype=np.int32)
+        check(L.wmx_aecm_set_delay_legs(aecm, idx.ctypes.data, idx.size, int(delay_ms), self._stream()), "wmx_aecm_set_delay_legs")
+
+    def export_echo(self):
+        """dict(startup, far_ms, known_delay, delay_blocks: int32 [n_legs]) as the work queued on the current stream leaves them; before
+        the first echo(True): 1, 0, 0, -2"""
+        r = {name: np.zeros(self.n_legs, np.int32) for name in ("startup", "far_ms", "known_delay", "delay_blocks")}
+        check(lib().wmx_conf_export_echo(self._h, r["startup"].ctypes.data, r["far_ms"].ctypes.data, r["known_delay"].ctypes.data,
+                                         r["delay_blocks"].ctypes.data, self._stream()), "wmx_conf_export_echo")
+        return r
+
     def set_codecs(self, legs, in_codec, out_law):
         """a G.711 codec per leg, as each call negotiated it (wmx_conf_set_codecs), between submits: in_codec "reference" (the default:
         A-law whatever arrives), "pcma", "pcmu" or "by_pt" (or WMX_CODEC_* 0 .. 3), out_law "a" / "u"; legs None = every leg"""

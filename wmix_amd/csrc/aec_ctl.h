@@ -16,6 +16,14 @@
 #include <cstddef>
 #include <cstring>
 
+// RingIdx (and the AECM's control plane, aecm_ctl.h) runs on the host and, for the legs of a conference bridge, on the device
+// (aecm_legs_kernel): the pattern of WMX_CALLS_FN in leg_calls.h
+#if defined(__HIPCC__)
+#define WMX_CTL_FN __host__ __device__
+#else
+#define WMX_CTL_FN
+#endif
+
 namespace wmx {
 
 constexpr int kAecPart = 64, kAecPart1 = 65, kAecFrame = 80;
@@ -98,15 +106,15 @@ struct AecPlan {
 // index-only ring buffer: same arithmetic as W:common_audio/ring_buffer.c:112-247
 struct RingIdx {
     int count = 0, rd = 0, wr = 0, diff_wrap = 0;
-    void init(int n) {
+    WMX_CTL_FN void init(int n) {
         count = n;
         rd = wr = 0;
         diff_wrap = 0;
     }
-    bool same_as(const RingIdx &o) const { return count == o.count && rd == o.rd && wr == o.wr && diff_wrap == o.diff_wrap; }
-    int avail_read() const { return diff_wrap ? count - rd + wr : wr - rd; }
-    int avail_write() const { return count - avail_read(); }
-    int move_read(int n) {
+    WMX_CTL_FN bool same_as(const RingIdx &o) const { return count == o.count && rd == o.rd && wr == o.wr && diff_wrap == o.diff_wrap; }
+    WMX_CTL_FN int avail_read() const { return diff_wrap ? count - rd + wr : wr - rd; }
+    WMX_CTL_FN int avail_write() const { return count - avail_read(); }
+    WMX_CTL_FN int move_read(int n) {
         const int fr = avail_write(), readable = avail_read();
         int pos = rd;
         if (n > readable) n = readable;
@@ -124,7 +132,7 @@ struct RingIdx {
         return n;
     }
     // returns the number of elements written; *pos = first slot (mod count)
-    int write(int n, int *pos) {
+    WMX_CTL_FN int write(int n, int *pos) {
         const int fr = avail_write(), w = fr < n ? fr : n;
         int left = w;
         const int margin = count - wr;
@@ -137,7 +145,7 @@ struct RingIdx {
         wr += left;
         return w;
     }
-    int read(int n, int *pos) {
+    WMX_CTL_FN int read(int n, int *pos) {
         const int readable = avail_read(), k = readable < n ? readable : n;
         *pos = rd % count;
         move_read(k);

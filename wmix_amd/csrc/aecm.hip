@@ -204,6 +204,53 @@ __device__ uint32_t binary_spectrum(const uint16_t *mag, int32_t *mean, int q, i
 // flight, five cache write-backs per packet and cohort made this kernel 0.45 ms for 4 096 far-ends, 14 x the single one.
 __device__ __forceinline__ void wave_handoff_global() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
+// The far half of one 80-sample frame, what aecm_far_kernel does per frame of a plan and aecm_legs_kernel per frame of a leg's row:
+// far ring (or the replayed farendOld slot) -> farendOld -> the 144-sample far frame ring.  The caller hands off behind it.
+// UNI: the plan lies in LDS and its words are made wave-uniform where they are read (aecm_legs_kernel); the two batch kernels read
+// theirs from global memory as they always have.
+template <bool UNI>
+__device__ __forceinline__ int plan_word(const int &w) {
+    if constexpr (UNI) return uni(w);
+    return w;
+}
+template <bool UNI>
+__device__ __forceinline__ void aecm_far_frame(const AecmFarBufs &F, const AecmFramePlan &fp, int lane) {
+    for (int i = lane; i < kAecmFrame; i += 64) {
+        int16_t v;
+        if (plan_word<UNI>(fp.far_src) >= 0) {
+            int pos = plan_word<UNI>(fp.far_src) + i;
+            pos -= pos >= kAecmFarRing ? kAecmFarRing : 0;
+            v = F.ring[pos];
+            F.old[plan_word<UNI>(fp.old_slot) * kAecmFrame + i] = v;
+        } else {
+            v = F.old[plan_word<UNI>(fp.old_slot) * kAecmFrame + i];
+        }
+        int w = plan_word<UNI>(fp.ring_w) + i;
+        w -= w >= kAecmFrameRing ? kAecmFrameRing : 0;
+        F.frame[w] = v;
+    }
+}
+
+// The far half of one 64-sample block: the block's samples from the frame ring, |X| with its Q-domain and the binary spectrum into
+// history slot blk_t.  mean: the 32 running thresholds of the binary far spectrum, staged in LDS.  The caller hands off behind it.
+template <bool UNI>
+__device__ __forceinline__ void aecm_far_block(AecmWave &W, const AecmConsts &K, const AecmFarBufs &F, int32_t *mean, int &far_init,
+                                               const AecmFramePlan &fp, int b, int lane) {
+    int r = plan_word<UNI>(fp.blk_r[b]) + lane;
+    r -= r >= kAecmFrameRing ? kAecmFrameRing : 0;
+    const int16_t nw = F.frame[r];
+    uint32_t sum;
+    const int far_q = time_to_freq(W, K, lane, F.x_prev[lane], nw, W.dfw, W.xfa, &sum);
+    const int slot = plan_word<UNI>(fp.blk_t[b]) & (kAecmHist - 1);
+    for (int k = lane; k < 65; k += 64) F.hist[slot * kAecmBP + k] = W.xfa[k];
+    const uint32_t bin = binary_spectrum(W.xfa, mean, far_q, far_init, lane);
+    if (lane == 0) {
+        F.hist_q[slot] = far_q;
+        F.hist_bin[slot] = bin;
+    }
+    F.x_prev[lane] = nw;
+}
+
 __global__ __launch_bounds__(64) void aecm_far_kernel(AecmFarBufs F_all, const AecmConsts *__restrict__ consts, AecmPlan *plans, int n_plans,
                                                      int n_classes, const int32_t *__restrict__ plan_of, const int16_t *far, long far_stride,
                                                      long far_group_stride, int chn, int plan_by_value, const AecmPlan plan_value,
@@ -260,36 +307,11 @@ __global__ __launch_bounds__(64) void aecm_far_kernel(AecmFarBufs F_all, const A
         if (!pl.has_near || pl.passthrough) continue;
         for (int f = 0; f < pl.n_frames; f++) {
             const AecmFramePlan &fp = pl.fr[f];
-            for (int i = lane; i < kAecmFrame; i += 64) {
-                int16_t v;
-                if (fp.far_src >= 0) {
-                    int pos = fp.far_src + i;
-                    pos -= pos >= kAecmFarRing ? kAecmFarRing : 0;
-                    v = F.ring[pos];
-                    F.old[fp.old_slot * kAecmFrame + i] = v;
-                } else {
-                    v = F.old[fp.old_slot * kAecmFrame + i];
-                }
-                int w = fp.ring_w + i;
-                w -= w >= kAecmFrameRing ? kAecmFrameRing : 0;
-                F.frame[w] = v;
-            }
+            aecm_far_frame<false>(F, fp, lane);
             wave_handoff_global();
             wave_sync();
             for (int b = 0; b < fp.n_blocks; b++) {
-                int r = fp.blk_r[b] + lane;
-                r -= r >= kAecmFrameRing ? kAecmFrameRing : 0;
-                const int16_t nw = F.frame[r];
-                uint32_t sum;
-                const int far_q = time_to_freq(W, K, lane, F.x_prev[lane], nw, W.dfw, W.xfa, &sum);
-                const int slot = fp.blk_t[b] & (kAecmHist - 1);
-                for (int k = lane; k < 65; k += 64) F.hist[slot * kAecmBP + k] = W.xfa[k];
-                const uint32_t bin = binary_spectrum(W.xfa, mean, far_q, far_init, lane);
-                if (lane == 0) {
-                    F.hist_q[slot] = far_q;
-                    F.hist_bin[slot] = bin;
-                }
-                F.x_prev[lane] = nw;
+                aecm_far_block<false>(W, K, F, mean, far_init, fp, b, lane);
                 wave_handoff_global();
                 wave_sync();
             }
@@ -807,6 +829,41 @@ __device__ void aecm_block(AecmWave &W, const AecmConsts &K, const AecmFarBufs &
 #endif
 }
 
+// The near half of a frame, what aecm_near_kernel does per frame of a plan and aecm_legs_kernel per frame of a leg's row: the frame's 80
+// samples (in0: sample lane, in1: sample 64 + lane) into the near frame ring ...
+__device__ __forceinline__ void aecm_near_frame_in(int16_t *near_ring, int ring_w, int lane, int16_t in0, int16_t in1) {
+    int w = ring_w + lane;
+    w -= w >= kAecmFrameRing ? kAecmFrameRing : 0;
+    near_ring[w] = in0;
+    if (lane < kAecmFrame - 64) {
+        int w2 = ring_w + 64 + lane;
+        w2 -= w2 >= kAecmFrameRing ? kAecmFrameRing : 0;
+        near_ring[w2] = in1;
+    }
+}
+// ... and one 64-sample block: from the near frame ring through aecm_block into the out frame ring
+template <bool UNI>
+__device__ __forceinline__ void aecm_near_block(AecmWave &W, const AecmConsts &K, const AecmFarBufs &F, const LdsScal sc, const AecmFramePlan &fp,
+                                                int b, int mult, int lane) {
+    int16_t *near_ring = reinterpret_cast<int16_t *>(&W.st[A_NEAR_RING]), *out_ring = reinterpret_cast<int16_t *>(&W.st[A_OUT_RING]);
+    int16_t *d_prev = reinterpret_cast<int16_t *>(&W.st[A_D_PREV]);
+    int r = plan_word<UNI>(fp.blk_r[b]) + lane;
+    r -= r >= kAecmFrameRing ? kAecmFrameRing : 0;
+    int16_t t_prev = d_prev[lane], t_new = near_ring[r];
+    aecm_block(W, K, F, sc, plan_word<UNI>(fp.blk_t[b]), mult, lane, t_prev, t_new);
+    d_prev[lane] = t_prev;
+    int ow = plan_word<UNI>(fp.blk_out_w[b]) + lane;
+    ow -= ow >= kAecmFrameRing ? kAecmFrameRing : 0;
+    out_ring[ow] = t_new;
+    wave_sync();
+}
+// ... and the frame's 80 output samples out of the out frame ring: sample i of the frame for i = lane, lane + 64
+__device__ __forceinline__ int16_t aecm_out_sample(const int16_t *out_ring, int out_r, int i) {
+    int r = out_r + i;
+    r -= r >= kAecmFrameRing ? kAecmFrameRing : 0;
+    return out_ring[r];
+}
+
 // One wave per stream, kAecmWavesPerBlock streams per workgroup.
 #ifndef WMX_AECM_WPE
 #define WMX_AECM_WPE 7  // 0.63 / 0.53 / 0.48 / 0.445 ms at 3 / 4 / 5 / 6 waves per SIMD when first measured; 22.6 KB of LDS per workgroup allow 7
@@ -842,7 +899,6 @@ __global__ __launch_bounds__(64 * kAecmWavesPerBlock) __attribute__((amdgpu_wave
     plans += plan_of ? __builtin_amdgcn_readfirstlane(plan_of[grp]) : grp;  // [packet][class]
     const LdsScal sc{&W.st[A_SCAL]};
     int16_t *near_ring = reinterpret_cast<int16_t *>(&W.st[A_NEAR_RING]), *out_ring = reinterpret_cast<int16_t *>(&W.st[A_OUT_RING]);
-    int16_t *d_prev = reinterpret_cast<int16_t *>(&W.st[A_D_PREV]);
     for (int p = 0; p < n_plans; p++) {
         const AecmPlan &pl = plans[(size_t)p * n_classes];
         if (!pl.has_near) continue;
@@ -867,28 +923,9 @@ __global__ __launch_bounds__(64 * kAecmWavesPerBlock) __attribute__((amdgpu_wave
         for (int f = 0; f < 2; f++) {
             if (f >= pl.n_frames) break;
             const AecmFramePlan &fp = pl.fr[f];
-            {
-                int w = fp.ring_w + lane;
-                w -= w >= kAecmFrameRing ? kAecmFrameRing : 0;
-                near_ring[w] = in0[f];
-                if (lane < kAecmFrame - 64) {
-                    int w2 = fp.ring_w + 64 + lane;
-                    w2 -= w2 >= kAecmFrameRing ? kAecmFrameRing : 0;
-                    near_ring[w2] = in1[f];
-                }
-            }
+            aecm_near_frame_in(near_ring, fp.ring_w, lane, in0[f], in1[f]);
             wave_sync();
-            for (int b = 0; b < fp.n_blocks; b++) {
-                int r = fp.blk_r[b] + lane;
-                r -= r >= kAecmFrameRing ? kAecmFrameRing : 0;
-                int16_t t_prev = d_prev[lane], t_new = near_ring[r];
-                aecm_block(W, K, F, sc, fp.blk_t[b], mult, lane, t_prev, t_new);
-                d_prev[lane] = t_prev;
-                int ow = fp.blk_out_w[b] + lane;
-                ow -= ow >= kAecmFrameRing ? kAecmFrameRing : 0;
-                out_ring[ow] = t_new;
-                wave_sync();
-            }
+            for (int b = 0; b < fp.n_blocks; b++) aecm_near_block<false>(W, K, F, sc, fp, b, mult, lane);
             if (!pl.discard_out)
                 for (int i = lane; i < kAecmFrame; i += 64) {
                     int r = fp.out_r + i;
@@ -904,6 +941,166 @@ __global__ __launch_bounds__(64 * kAecmWavesPerBlock) __attribute__((amdgpu_wave
         const int4 *src = reinterpret_cast<const int4 *>(W.st);
         for (int i = lane; i < A_WORDS / 4; i += 64) dst[i] = src[i];
     }
+}
+
+// ---------------------------------------------------------------- the legs of a conference bridge: one wave per leg
+// wmx_aecm_process_legs.  Leg g has what a batch shares per cohort all to itself -- a far-end slab (far_cohort(F_all, g)), a control
+// plane (ctl_all[g]) and a reported delay -- because its far end is what the bridge sent to IT and its call pattern is its own from
+// the first jittered tick.  So nothing is planned on the host: the wave moves its leg's AecmCtl through LDS, lane 0 runs the same
+// aecm_ctl.h text over the tick's calls (wave-uniform work; the plan of the call in hand lives in LDS and is never uploaded), and
+// the wave then does per frame what the two kernels above split between them: the far part (aecm_far_frame, aecm_far_block), then
+// the near part (aecm_near_block), with the far kernel's hand-off between the far part's global stores and the near part's loads.
+// Per tick and leg: the rows the load will consume (leg_calls_walk_leg, take = data) in call order, each one aec_process of 160
+// frames in place -- the whole row is read before any of it is written --, then the tick's far row, one aec_setFrameFar.  pcm NULL:
+// no rows (far only); far NULL: rows only.  A leg with no row neither loads nor stores its 3.4 KB of near state: its far ring and its
+// control plane move, and the wave is gone before the state load.  A leg that is switched off does neither step.  A workgroup none
+// of whose legs has work leaves before it stages AecmConsts; one that only buffers far rows never stages them.
+struct alignas(16) AecmLegWave {
+    int32_t ctl_words[sizeof(AecmCtl) / 4];  // the leg's control plane while the wave runs (AecmCtl has initialisers: raw words in LDS)
+    __device__ __forceinline__ AecmCtl &ctl() { return *reinterpret_cast<AecmCtl *>(ctl_words); }
+    AecmPlan plan;         // the plan of the call in hand: lane 0 writes it, the wave reads it
+    int32_t mean_far[32];  // the running thresholds of the binary far spectrum (the far kernel keeps them in its idle W.st)
+};
+static_assert(sizeof(AecmCtl) % 4 == 0 && sizeof(AecmPlan) % 4 == 0, "moved as 32-bit words");
+#ifndef WMX_AECM_LEGS_WPE
+#define WMX_AECM_LEGS_WPE 6  // 24.2 KB of LDS per workgroup: 6 workgroups of 4 waves per compute unit
+#endif
+__global__ __launch_bounds__(64 * kAecmWavesPerBlock) __attribute__((amdgpu_waves_per_eu(WMX_AECM_LEGS_WPE, WMX_AECM_LEGS_WPE))) void aecm_legs_kernel(
+    int32_t *__restrict__ state, AecmFarBufs F_all, const AecmConsts *__restrict__ consts, AecmCtl *ctl_all, const int32_t *__restrict__ delay_ms,
+    int16_t *pcm, int n_legs, long leg_stride, long packet_stride, int max_packets, const uint32_t *__restrict__ len,
+    const uint32_t *__restrict__ calls_in, const int16_t *far, long far_leg_stride, const uint8_t *__restrict__ active) {
+    __shared__ AecmConsts K;
+    __shared__ AecmWave WS[kAecmWavesPerBlock];
+    __shared__ AecmLegWave LS[kAecmWavesPerBlock];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const long g = (long)blockIdx.x * kAecmWavesPerBlock + wave;
+    const bool live = stream_active(active, (int)g, n_legs);
+    uint32_t list = 0, take = 0;  // take bit j: call j of the list is a data call on a readable row
+    if (live && pcm) {
+        const LegWalk w = leg_calls_walk_leg(len, calls_in, (size_t)g, max_packets);
+        list = (uint32_t)uni((int)w.list), take = (uint32_t)uni((int)w.data);
+    }
+    const bool far_row = live && far != nullptr, work = take != 0u || far_row;
+    if (!__syncthreads_or(work)) return;  // nobody in this workgroup has a row or a far row
+    if (__syncthreads_or(take != 0u)) {
+        const int4 *src = reinterpret_cast<const int4 *>(consts);
+        int4 *dst = reinterpret_cast<int4 *>(&K);
+        for (int i = threadIdx.x; i < (int)(sizeof(AecmConsts) / 16); i += blockDim.x) dst[i] = src[i];
+    }
+    AecmWave &W = WS[wave];
+    AecmLegWave &L = LS[wave];
+    const long gl = live ? g : 0;
+    int32_t *st = state + gl * (long)A_WORDS;
+    int32_t *ctl_g = reinterpret_cast<int32_t *>(ctl_all + gl);
+    const AecmFarBufs F = far_cohort(F_all, (int)gl);
+    constexpr int kCtlWords = (int)(sizeof(AecmCtl) / 4), kPlanWords = (int)(sizeof(AecmPlan) / 4);
+    if (work)
+        for (int i = lane; i < kCtlWords; i += 64) L.ctl_words[i] = ctl_g[i];
+    if (take != 0u) {
+        const int4 *src = reinterpret_cast<const int4 *>(st);
+        int4 *dst = reinterpret_cast<int4 *>(W.st);
+        for (int i = lane; i < A_WORDS / 4; i += 64) dst[i] = src[i];
+        if (lane < 32) L.mean_far[lane] = F.mean_far[lane];
+    }
+    __syncthreads();
+    if (!work) return;  // no leg, one that is switched off, or nothing for it this tick: nothing touched
+    if (take != 0u) {
+        int far_init = uni(F.mean_far[32]);
+        const int ms = uni(delay_ms[gl]);
+        const LdsScal sc{&W.st[A_SCAL]};
+        int16_t *near_ring = reinterpret_cast<int16_t *>(&W.st[A_NEAR_RING]), *out_ring = reinterpret_cast<int16_t *>(&W.st[A_OUT_RING]);
+        int16_t *rows = pcm + (size_t)g * leg_stride;
+#pragma unroll 1
+        for (uint32_t j = 0; j < (uint32_t)kLegMaxCalls; j++) {
+            if (!((take >> j) & 1u)) continue;
+            int16_t *row = rows + (size_t)leg_calls_slot(list, j) * packet_stride;
+            for (int i = lane; i < kPlanWords; i += 64) reinterpret_cast<int32_t *>(&L.plan)[i] = 0;
+            wave_sync();
+            if (lane == 0) L.ctl().process(kLegRow, ms, &L.plan);  // 0: the delay was validated where it was set
+            wave_sync();
+            if (uni(L.plan.passthrough)) continue;  // start-up: out = near (echo_control_mobile.c:341-352), and the call is in place
+            // the whole row is read before anything is written
+            int16_t in0[2], in1[2];
+#pragma unroll
+            for (int f = 0; f < 2; f++) {
+                in0[f] = row[f * kAecmFrame + lane];
+                in1[f] = lane < kAecmFrame - 64 ? row[f * kAecmFrame + 64 + lane] : (int16_t)0;
+            }
+#pragma unroll 1
+            for (int f = 0; f < 2; f++) {
+                const AecmFramePlan &fp = L.plan.fr[f];
+                const int ring_w = uni(fp.ring_w), n_blocks = uni(fp.n_blocks);
+                aecm_near_frame_in(near_ring, ring_w, lane, f ? in0[1] : in0[0], f ? in1[1] : in1[0]);
+                aecm_far_frame<true>(F, fp, lane);
+                wave_handoff_global();
+                wave_sync();
+#pragma unroll 1
+                for (int b = 0; b < n_blocks; b++) {
+                    aecm_far_block<true>(W, K, F, L.mean_far, far_init, fp, b, lane);
+                    wave_handoff_global();
+                    wave_sync();
+                }
+#pragma unroll 1
+                for (int b = 0; b < n_blocks; b++) aecm_near_block<true>(W, K, F, sc, fp, b, 1, lane);
+                const int out_r = uni(fp.out_r);
+                for (int i = lane; i < kAecmFrame; i += 64) row[f * kAecmFrame + i] = aecm_out_sample(out_ring, out_r, i);
+            }
+            wave_sync();  // every lane has read the plan before lane 0 writes the next
+        }
+        if (lane < 32) F.mean_far[lane] = L.mean_far[lane];
+        if (lane == 0) F.mean_far[32] = far_init;
+    }
+    if (far_row) {  // aec_setFrameFar behind the rows: what this tick sent to the leg (WebRtcAecm_BufferFarend)
+        if (lane == 0) {
+            L.plan.far_w = L.plan.far_n = 0;
+            L.ctl().buffer_farend(kLegRow, &L.plan);
+        }
+        wave_sync();
+        const int far_w = uni(L.plan.far_w), far_n = uni(L.plan.far_n);  // far_n < 160: the ring is full, the rest is dropped
+        const int16_t *src = far + (size_t)g * far_leg_stride;
+        for (int i = lane; i < far_n; i += 64) {
+            int pos = far_w + i;
+            pos -= pos >= kAecmFarRing ? kAecmFarRing : 0;
+            F.ring[pos] = src[i];
+        }
+    }
+    wave_sync();
+    for (int i = lane; i < kCtlWords; i += 64) ctl_g[i] = L.ctl_words[i];
+    if (take != 0u) {
+        int4 *dst = reinterpret_cast<int4 *>(st);
+        const int4 *src = reinterpret_cast<const int4 *>(W.st);
+        for (int i = lane; i < A_WORDS / 4; i += 64) dst[i] = src[i];
+    }
+}
+
+// aec_init for the listed legs of a legs handle (idx NULL: leg j = j): near state from the template, far-end slab zero, a fresh control
+// plane; the reported delay stays.  One workgroup per listed leg.
+__global__ __launch_bounds__(256) void aecm_legs_reset(int32_t *state, const int32_t *tmpl, char *far_slabs, size_t slab_bytes, AecmCtl *ctl_all,
+                                                       const int32_t *idx, int n_idx) {
+    for (int j = blockIdx.x; j < n_idx; j += gridDim.x) {
+        const size_t g = (size_t)(idx ? idx[j] : j);
+        int32_t *dst = state + g * A_WORDS;
+        for (int i = threadIdx.x; i < A_WORDS; i += blockDim.x) dst[i] = tmpl[i];
+        int32_t *slab = reinterpret_cast<int32_t *>(far_slabs + g * slab_bytes);
+        for (size_t i = threadIdx.x; i < slab_bytes / 4; i += blockDim.x) slab[i] = 0;
+        if (threadIdx.x == 0) ctl_all[g].init(8000);
+    }
+}
+// the reported delay of the listed legs (idx NULL: all n)
+__global__ void aecm_legs_set_delay(int32_t *delay, const int32_t *idx, int n, int delay_ms) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) delay[idx ? idx[j] : j] = delay_ms;
+}
+// wmx_aecm_export_legs: any output may be NULL
+__global__ void aecm_legs_export(const AecmCtl *ctl_all, const int32_t *state, int n_legs, int32_t *startup, int32_t *far_ms, int32_t *known_delay,
+                                 int32_t *delay_blocks) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_legs) return;
+    const AecmCtl &c = ctl_all[g];
+    if (startup) startup[g] = c.ec_startup;
+    if (far_ms) far_ms[g] = c.farend.avail_read() / 8;
+    if (known_delay) known_delay[g] = c.known_delay;
+    if (delay_blocks) delay_blocks[g] = state[(size_t)g * A_WORDS + A_SCAL + M_LAST_DELAY];
 }
 
 __global__ void aecm_set_cohort(int *stream_cohort, const int32_t *idx, int n_idx, int cohort) {
@@ -997,7 +1194,21 @@ struct wmx_aecm {
     wmx::StreamLife life;
     wmx::AecmConsts *d_consts;
     wmx::AecmFarBufs far;
+    // a handle made by wmx_aecm_create_legs (stream g = leg g): no host cohorts -- per leg a far-end slab, a control plane and a
+    // reported delay, all on the device (aecm_legs_kernel)
+    bool legs = false;
+    void *d_leg_far = nullptr;           // [n_streams] slabs of leg_slab_bytes
+    size_t leg_slab_bytes = 0;
+    wmx::AecmCtl *d_leg_ctl = nullptr;   // [n_streams]
+    int32_t *d_leg_delay = nullptr;      // [n_streams] reported delay, ms; kept across resets
 };
+
+// the cohort entry points on a legs handle: there are no cohorts to speak of
+#define WMX_AECM_NO_LEGS(h, name)                                                                                          \
+    if ((h) && (h)->legs) {                                                                                                \
+        wmx::set_error(name ": the handle was made by wmx_aecm_create_legs -- one control plane per leg on the device, no cohorts"); \
+        return WMX_ESTATE;                                                                                                 \
+    }
 
 extern "C" {
 
@@ -1008,15 +1219,21 @@ int wmx_aecm_destroy(wmx_aecm *h) {
     if (h->d_consts) (void)hipFree(h->d_consts);
     if (h->d_tmpl) (void)hipFree(h->d_tmpl);
     if (h->d_stream_cohort) (void)hipFree(h->d_stream_cohort);
+    if (h->d_leg_far) (void)hipFree(h->d_leg_far);
+    if (h->d_leg_ctl) (void)hipFree(h->d_leg_ctl);
+    if (h->d_leg_delay) (void)hipFree(h->d_leg_delay);
     h->co.release();
     h->life.release();
     delete h;
     return 0;
 }
 
-static void aecm_carve_far(wmx_aecm *h) {  // the far-end allocation (32-bit arrays first: alignment); one slab per cohort
+static void aecm_carve_slabs(wmx_aecm *h, void *base, size_t slab_bytes);
+static void aecm_carve_far(wmx_aecm *h) { aecm_carve_slabs(h, h->co.d_far, h->co.slab_bytes); }
+// the far-end allocation (32-bit arrays first: alignment); one slab per cohort, or per leg
+static void aecm_carve_slabs(wmx_aecm *h, void *base, size_t slab_bytes) {
     using namespace wmx;
-    char *p = static_cast<char *>(h->co.d_far);
+    char *p = static_cast<char *>(base);
     h->far.mean_far = reinterpret_cast<int32_t *>(p);
     p += sizeof(int32_t) * 36;
     h->far.hist_q = reinterpret_cast<int32_t *>(p);
@@ -1032,8 +1249,9 @@ static void aecm_carve_far(wmx_aecm *h) {  // the far-end allocation (32-bit arr
     h->far.frame = reinterpret_cast<int16_t *>(p);
     p += sizeof(int16_t) * kAecmFrameRing;
     h->far.x_prev = reinterpret_cast<int16_t *>(p);
-    h->far.group_bytes = h->co.slab_bytes;
+    h->far.group_bytes = slab_bytes;
 }
+static int aecm_make(wmx_aecm **out, int n_streams, int chn, int freq, int interval_ms, int n_cohorts, bool legs);
 
 
 int wmx_aecm_create(wmx_aecm **out, int n_streams, int chn, int freq, int interval_ms) {
@@ -1041,6 +1259,13 @@ int wmx_aecm_create(wmx_aecm **out, int n_streams, int chn, int freq, int interv
 }
 
 int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, int interval_ms, int n_cohorts) {
+    return aecm_make(out, n_streams, chn, freq, interval_ms, n_cohorts, false);
+}
+
+// One canceller per leg of a conference bridge, aec_init(1, 8000, 20) each (include/wmix_amd.h; aecm_legs_kernel)
+int wmx_aecm_create_legs(wmx_aecm **out, int n_legs) { return aecm_make(out, n_legs, 1, 8000, 20, 1, true); }
+
+static int aecm_make(wmx_aecm **out, int n_streams, int chn, int freq, int interval_ms, int n_cohorts, bool legs) {
     using namespace wmx;
     if (!out) return WMX_EINVAL;
     *out = nullptr;
@@ -1062,7 +1287,8 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     h->chn = chn;
     h->freq = freq;
     h->pkg = freq / 1000 * ((freq <= 8000 && interval_ms % 20 == 0) ? 20 : 10);  // src/webrtc.c:239-248
-    h->co.init(n_cohorts, freq);  // made together, equal planes: one class until something tells them apart
+    h->legs = legs;
+    if (!legs) h->co.init(n_cohorts, freq);  // made together, equal planes: one class until something tells them apart
     h->d_tmpl = nullptr;
     h->d_stream_cohort = nullptr;
     h->d_state = nullptr;
@@ -1122,7 +1348,14 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     h->co.slab_bytes = (far_raw + 255) / 256 * 256;  // per cohort
     WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_state, (size_t)A_WORDS * n_streams * sizeof(int32_t)));
     WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_consts, sizeof(AecmConsts)));
-    {
+    if (legs) {  // per leg what a batch keeps per cohort, and the control plane with it; filled by aecm_legs_reset below
+        h->leg_slab_bytes = h->co.slab_bytes;
+        WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_leg_far, h->leg_slab_bytes * (size_t)n_streams));
+        WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(reinterpret_cast<void **>(&h->d_leg_ctl), sizeof(AecmCtl) * (size_t)n_streams));
+        WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(reinterpret_cast<void **>(&h->d_leg_delay), sizeof(int32_t) * (size_t)n_streams));
+        WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMemset(h->d_leg_delay, 0, sizeof(int32_t) * (size_t)n_streams));
+        aecm_carve_slabs(h, h->d_leg_far, h->leg_slab_bytes);
+    } else {
         const int rc = h->co.reserve(n_cohorts, [h] { aecm_carve_far(h); });
         if (rc != 0) {
             wmx_aecm_destroy(h);
@@ -1137,7 +1370,12 @@ int wmx_aecm_create_cohorts(wmx_aecm **out, int n_streams, int chn, int freq, in
     WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMalloc(&h->d_tmpl, A_WORDS * sizeof(int32_t)));
     WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMemcpy(h->d_consts, K.get(), sizeof(AecmConsts), hipMemcpyHostToDevice));
     WMX_CREATE_TRY(wmx_aecm_destroy(h), hipMemcpy(h->d_tmpl, st.data(), A_WORDS * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(aecm_fill_state, dim3(1024), dim3(256), 0, nullptr, h->d_state, h->d_tmpl, (int)A_WORDS, n_streams);
+    if (legs)
+        hipLaunchKernelGGL(aecm_legs_reset, dim3((unsigned)(n_streams < 4096 ? n_streams : 4096)), dim3(256), 0, nullptr, h->d_state,
+                           (const int32_t *)h->d_tmpl, static_cast<char *>(h->d_leg_far), h->leg_slab_bytes, h->d_leg_ctl, (const int32_t *)nullptr,
+                           n_streams);
+    else
+        hipLaunchKernelGGL(aecm_fill_state, dim3(1024), dim3(256), 0, nullptr, h->d_state, h->d_tmpl, (int)A_WORDS, n_streams);
     WMX_CREATE_TRY(wmx_aecm_destroy(h), hipGetLastError());
     WMX_CREATE_TRY(wmx_aecm_destroy(h), hipDeviceSynchronize());
     *out = h;
@@ -1150,6 +1388,7 @@ int wmx_aecm_state_bytes(const wmx_aecm *h) { return h ? (int)wmx::A_WORDS * 4 :
 // Same contract as wmx_aec_run: mode bit 1 = aec_setFrameFar, bit 2 = aec_process, 3 = aec_process2.
 int wmx_aecm_run(wmx_aecm *h, int mode, const int16_t *d_far, long far_packet_stride, const int16_t *d_near, int16_t *d_out, int n_packets,
                  long stream_stride, long packet_stride, int delay_ms, void *stream) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_run");
     return wmx_aecm_run_cohorts(h, mode, d_far, far_packet_stride, 0, d_near, d_out, n_packets, stream_stride, packet_stride,
                                 h ? h->co.same_delays(delay_ms) : nullptr, nullptr, nullptr, stream);
 }
@@ -1166,6 +1405,7 @@ int wmx_aecm_run_cohorts(wmx_aecm *h, int mode, const int16_t *d_far, long far_p
         wmx::set_error("wmx_aecm_run: bad argument");
         return WMX_EINVAL;
     }
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_run_cohorts");
     using namespace wmx;
     hipStream_t s = as_stream(stream);
     auto far = [&](hipStream_t fs, const CohortLaunch<AecmPlan> &L) {
@@ -1191,6 +1431,72 @@ int wmx_aecm_run_cohorts(wmx_aecm *h, int mode, const int16_t *d_far, long far_p
                        packet_stride, delay_ms, cohort_on, cohort_rc, s, [](int) { return 0; }, [](auto loop) { return loop(); }, far, near);
 }
 
+// the legs of a conference bridge: the rows this tick brought each leg, then the row it was sent (include/wmix_amd.h; aecm_legs_kernel)
+int wmx_aecm_process_legs(wmx_aecm *h, int16_t *d_pcm, long leg_stride, long packet_stride, int max_packets, const uint32_t *d_len,
+                          const uint32_t *d_calls, const int16_t *d_far, long far_leg_stride, void *stream) {
+    WMX_ON_DEVICE(h);
+    using namespace wmx;
+    if (!h || !h->legs) {
+        set_error("wmx_aecm_process_legs: the handle must be 1 x 8000 with 20 ms packets, made by wmx_aecm_create_legs (it is %d x %d%s)",
+                  h ? h->chn : 0, h ? h->freq : 0, h ? ", made for cohorts" : "");
+        return WMX_EINVAL;
+    }
+    const bool rows = d_pcm || d_len;  // both NULL: far only
+    if (!rows && !d_far) {
+        set_error("wmx_aecm_process_legs: neither rows (d_pcm and d_len NULL) nor a far row (d_far NULL)");
+        return WMX_EINVAL;
+    }
+    if (rows)
+        if (int rc = legs_rows_check("wmx_aecm_process_legs", h->n_streams, d_pcm, leg_stride, packet_stride, max_packets, d_len)) return rc;
+    if (d_far && (reinterpret_cast<uintptr_t>(d_far) % sizeof(int16_t) != 0 || (h->n_streams > 1 && far_leg_stride < kLegRow))) {
+        set_error("wmx_aecm_process_legs: d_far %p is not on a 2-byte boundary, or far rows that overlap (far_leg_stride %ld < %d)",
+                  (const void *)d_far, far_leg_stride, kLegRow);
+        return WMX_EINVAL;
+    }
+    const unsigned grid = (unsigned)((h->n_streams + kAecmWavesPerBlock - 1) / kAecmWavesPerBlock);
+    hipLaunchKernelGGL(aecm_legs_kernel, dim3(grid), dim3(64 * kAecmWavesPerBlock), 0, as_stream(stream), h->d_state, h->far, h->d_consts,
+                       h->d_leg_ctl, (const int32_t *)h->d_leg_delay, rows ? d_pcm : nullptr, h->n_streams, leg_stride, packet_stride,
+                       rows ? max_packets : 1, d_len, d_calls, d_far, far_leg_stride, (const uint8_t *)h->life.d_active);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// the reported delay of the listed legs (idx NULL: all), what aec_process is given with every row from now on
+int wmx_aecm_set_delay_legs(wmx_aecm *h, const int32_t *idx, int n, int delay_ms, void *stream) {
+    using namespace wmx;
+    if (h && (!h->legs || delay_ms < 0 || delay_ms > 500)) {
+        set_error("wmx_aecm_set_delay_legs: delay_ms=%d must be 0 .. 500, on a handle made by wmx_aecm_create_legs", delay_ms);
+        return WMX_EINVAL;
+    }
+    if (h && !idx) {
+        WMX_ON_DEVICE(h);
+        hipLaunchKernelGGL(aecm_legs_set_delay, dim3((unsigned)((h->n_streams + 255) / 256)), dim3(256), 0, as_stream(stream), h->d_leg_delay,
+                           (const int32_t *)nullptr, h->n_streams, delay_ms);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    }
+    return reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+        hipLaunchKernelGGL(aecm_legs_set_delay, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_leg_delay, d_idx, n, delay_ms);
+        WMX_LAUNCH_CHECK();
+        return 0;
+    });
+}
+
+// per leg: ec_startup, the far ring's fill in ms, knownDelay and the estimator's last_delay (-2 before a first estimate); device arrays
+// of n_legs int32, any of them NULL
+int wmx_aecm_export_legs(wmx_aecm *h, int32_t *d_startup, int32_t *d_far_ms, int32_t *d_known_delay, int32_t *d_delay_blocks, void *stream) {
+    WMX_ON_DEVICE(h);
+    using namespace wmx;
+    if (!h || !h->legs) {
+        set_error("wmx_aecm_export_legs: the handle must be made by wmx_aecm_create_legs");
+        return WMX_EINVAL;
+    }
+    hipLaunchKernelGGL(aecm_legs_export, dim3((unsigned)((h->n_streams + 255) / 256)), dim3(256), 0, as_stream(stream),
+                       (const AecmCtl *)h->d_leg_ctl, (const int32_t *)h->d_state, h->n_streams, d_startup, d_far_ms, d_known_delay, d_delay_blocks);
+    WMX_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // extern "C"
 // Library-internal (wmx_internal.h): the far kernel of the next wmx_aecm_run_* call may start at this point of `stream`, beside
 // whatever the caller launches between now and that call (wmx_chain_process: the NSX)
@@ -1205,11 +1511,36 @@ static constexpr uint32_t kAecmBlobVersion = 1;  // bump when the meaning of a s
 static wmx::StreamBlob aecm_blob(const wmx_aecm *h) {
     return {wmx::blob_tag("AECM"), wmx::blob_layout((uint32_t)h->freq, kAecmBlobVersion), {{h->d_state, 4, wmx::A_WORDS}}, 0};
 }
-int wmx_aecm_stream_state_bytes(const wmx_aecm *h) { return wmx::stream_state_bytes(h, aecm_blob); }
-int wmx_aecm_cohort_state_bytes(const wmx_aecm *h) { return h ? h->co.blob_bytes() : WMX_EINVAL; }
-int wmx_aecm_export_stream(wmx_aecm *h, int stream_index, void *host_blob) { return wmx::export_stream(h, stream_index, host_blob, aecm_blob); }
+// a leg's whole state in one blob: [header | near state | far-end slab | control plane | reported delay]
+static constexpr uint32_t kAecmLegBlobVersion = 1;
+static wmx::StreamBlob aecm_leg_blob(const wmx_aecm *h) {
+    return {wmx::blob_tag("AEMl"), wmx::blob_layout((uint32_t)h->freq, kAecmLegBlobVersion),
+            {{h->d_state, 4, wmx::A_WORDS}, {h->d_leg_far, 1, h->leg_slab_bytes}}, sizeof(wmx::AecmCtl) + sizeof(int32_t)};
+}
+int wmx_aecm_stream_state_bytes(const wmx_aecm *h) {
+    return h && h->legs ? wmx::stream_state_bytes(h, aecm_leg_blob) : wmx::stream_state_bytes(h, aecm_blob);
+}
+int wmx_aecm_cohort_state_bytes(const wmx_aecm *h) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_cohort_state_bytes");
+    return h ? h->co.blob_bytes() : WMX_EINVAL;
+}
+int wmx_aecm_export_stream(wmx_aecm *h, int stream_index, void *host_blob) {
+    if (h && h->legs)
+        return wmx::export_stream(h, stream_index, host_blob, aecm_leg_blob, [=](char *tail) {
+            WMX_HIP(hipMemcpy(tail, h->d_leg_ctl + stream_index, sizeof(wmx::AecmCtl), hipMemcpyDeviceToHost));
+            WMX_HIP(hipMemcpy(tail + sizeof(wmx::AecmCtl), h->d_leg_delay + stream_index, sizeof(int32_t), hipMemcpyDeviceToHost));
+            return 0;
+        });
+    return wmx::export_stream(h, stream_index, host_blob, aecm_blob);
+}
 
 int wmx_aecm_import_stream(wmx_aecm *h, int stream_index, const void *host_blob, int cohort) {
+    if (h && h->legs)  // (cohort: ignored)
+        return wmx::import_stream(h, stream_index, host_blob, aecm_leg_blob, true, wmx::NoHook{}, [=](const char *tail) {
+            WMX_HIP(hipMemcpy(h->d_leg_ctl + stream_index, tail, sizeof(wmx::AecmCtl), hipMemcpyHostToDevice));
+            WMX_HIP(hipMemcpy(h->d_leg_delay + stream_index, tail + sizeof(wmx::AecmCtl), sizeof(int32_t), hipMemcpyHostToDevice));
+            return 0;
+        });
     const bool cohort_ok = !h || (cohort >= -1 && cohort < h->co.n());
     return wmx::import_stream(h, stream_index, host_blob, aecm_blob, cohort_ok, wmx::NoHook{}, [=](const char *) {
         if (cohort >= 0 && h->d_stream_cohort) WMX_HIP(hipMemcpy(h->d_stream_cohort + stream_index, &cohort, sizeof(int), hipMemcpyHostToDevice));
@@ -1218,6 +1549,7 @@ int wmx_aecm_import_stream(wmx_aecm *h, int stream_index, const void *host_blob,
 }
 
 int wmx_aecm_export_cohort(wmx_aecm *h, int cohort, void *host_blob) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_export_cohort");
     WMX_ON_DEVICE(h);
     using namespace wmx;
     if (!h || !host_blob || cohort < 0 || cohort >= h->co.n()) return WMX_EINVAL;
@@ -1225,18 +1557,29 @@ int wmx_aecm_export_cohort(wmx_aecm *h, int cohort, void *host_blob) {
 }
 
 int wmx_aecm_import_cohort(wmx_aecm *h, int cohort, const void *host_blob) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_import_cohort");
     WMX_ON_DEVICE(h);
     using namespace wmx;
     if (!h || !host_blob || cohort < 0 || cohort >= h->co.n()) return WMX_EINVAL;
     return h->co.import_blob(cohort, blob_tag("AEMc"), blob_layout((uint32_t)h->freq, kAecmBlobVersion), host_blob);
 }
 
-int wmx_aecm_cohorts(const wmx_aecm *h) { return h ? h->co.n() : WMX_EINVAL; }
-int wmx_aecm_cohort_key(const wmx_aecm *h, int cohort, int32_t *key8) { return wmx::cohort_key(h, cohort, key8); }
-int wmx_aecm_live_cohorts(const wmx_aecm *h) { return h ? h->co.live_count() : WMX_EINVAL; }
+int wmx_aecm_cohorts(const wmx_aecm *h) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_cohorts");
+    return h ? h->co.n() : WMX_EINVAL;
+}
+int wmx_aecm_cohort_key(const wmx_aecm *h, int cohort, int32_t *key8) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_cohort_key");
+    return wmx::cohort_key(h, cohort, key8);
+}
+int wmx_aecm_live_cohorts(const wmx_aecm *h) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_live_cohorts");
+    return h ? h->co.live_count() : WMX_EINVAL;
+}
 
 // wmx_aec_coalesce for the fixed-point canceller (include/wmix_amd.h; cohort_hip.h: coalesce)
 int wmx_aecm_coalesce(wmx_aecm *h, int max_pairs, int32_t *merged_from, int32_t *merged_into, int cap, int *n_merged, void *stream) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_coalesce");
     WMX_ON_DEVICE(h);
     using namespace wmx;
     auto merge = [h](const AecmPairChecks &go, int n_go, hipStream_t s) {
@@ -1258,21 +1601,35 @@ int wmx_aecm_coalesce(wmx_aecm *h, int max_pairs, int32_t *merged_from, int32_t 
 }
 
 // aec_init for a cohort's shared part in the AECM build: control plane, far-end ring, farendOld, far spectrum history
-int wmx_aecm_reset_cohort(wmx_aecm *h, int cohort, void *stream) { return wmx::reset_cohort(h, cohort, stream); }
+int wmx_aecm_reset_cohort(wmx_aecm *h, int cohort, void *stream) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_reset_cohort");
+    return wmx::reset_cohort(h, cohort, stream);
+}
 
 // A new cohort (a join time of its own), as wmx_aec_add_cohort: a retired id when there is one, else the next, buffers doubling
 int wmx_aecm_add_cohort(wmx_aecm *h, int *cohort, void *stream) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_add_cohort");
     WMX_ON_DEVICE(h);
     if (!h || !cohort) return WMX_EINVAL;
     const int rc = h->co.add(h->d_stream_cohort, h->n_streams, wmx::as_stream(stream), cohort, [h] { aecm_carve_far(h); });
     return rc != 0 ? rc : wmx_aecm_reset_cohort(h, *cohort, stream);
 }
 
-int wmx_aecm_retire_cohort(wmx_aecm *h, int cohort) { return wmx::retire_cohort(h, cohort); }
+int wmx_aecm_retire_cohort(wmx_aecm *h, int cohort) {
+    WMX_AECM_NO_LEGS(h, "wmx_aecm_retire_cohort");
+    return wmx::retire_cohort(h, cohort);
+}
 
 // aec_release + aec_init for the listed streams in the AECM build; cohort >= 0 also makes them members of that cohort
 int wmx_aecm_reset_streams(wmx_aecm *h, const int32_t *idx, int n, int cohort, void *stream) {
     using namespace wmx;
+    if (h && h->legs)  // the leg as aec_init leaves it, far end and control plane included; its reported delay stays (cohort: ignored)
+        return reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
+            hipLaunchKernelGGL(aecm_legs_reset, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(256), 0, s, h->d_state, (const int32_t *)h->d_tmpl,
+                               static_cast<char *>(h->d_leg_far), h->leg_slab_bytes, h->d_leg_ctl, d_idx, n);
+            WMX_LAUNCH_CHECK();
+            return 0;
+        });
     const int refused = h && (cohort < -1 || cohort >= h->co.n()) ? WMX_EINVAL : 0;
     return reset_streams(h, idx, n, stream, [=](hipStream_t s, const int32_t *d_idx) {
         hipLaunchKernelGGL((fill_rows_idx<int32_t>), dim3((unsigned)(n < 4096 ? n : 4096)), dim3(256), 0, s, h->d_state, (const int32_t *)h->d_tmpl,

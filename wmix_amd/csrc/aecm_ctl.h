@@ -7,6 +7,9 @@
 // output ring's read-pointer rewind.  All streams of a batch are driven in lockstep against one shared far-end, so this
 // runs once per packet on the host with indices only (RingIdx = ring_buffer.c arithmetic) and is handed to the kernels as
 // a plan.  What IS data dependent -- the binary-spectrum delay estimate -- runs per stream on the GPU (aecm.hip).
+// For the legs of a conference bridge (wmx_aecm_create_legs) nothing runs in lockstep: every leg has an AecmCtl of its own in device
+// memory and aecm_legs_kernel runs this same text per leg (WMX_CTL_FN: host and device, the pattern of leg_calls.h);
+// tools_dev/san/leg_echo_san.cpp compiles it with g++ and tests/test_leg_echo_ctl_host.py holds every call against the oracle's handle.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -54,7 +57,7 @@ struct AecmCtl {
     int block_t = 0;
 
     // every word that decides the plane's future equal (see AecCtl::same_as): such planes, called alike, stay equal for ever
-    bool same_as(const AecmCtl &o) const {
+    WMX_CTL_FN bool same_as(const AecmCtl &o) const {
         return fs == o.fs && mult == o.mult && farend.same_as(o.farend) && frame_ring.same_as(o.frame_ring) && out_ring.same_as(o.out_ring) &&
                known_delay == o.known_delay && time_for_delay_change == o.time_for_delay_change && ec_startup == o.ec_startup &&
                check_buff_size == o.check_buff_size && buf_size_start == o.buf_size_start && counter == o.counter && sum == o.sum &&
@@ -62,7 +65,7 @@ struct AecmCtl {
                filt_delay == o.filt_delay && last_delay_diff == o.last_delay_diff && block_t == o.block_t;
     }
 
-    void init(int freq) {  // WebRtcAecm_Init echo_control_mobile.c:177-231, WebRtcAecm_InitCore aecm_core.c:401-546
+    WMX_CTL_FN void init(int freq) {  // WebRtcAecm_Init echo_control_mobile.c:177-231, WebRtcAecm_InitCore aecm_core.c:401-546
         *this = AecmCtl();
         fs = freq;
         mult = freq / 8000;
@@ -71,7 +74,7 @@ struct AecmCtl {
         out_ring.init(kAecmFrameRing);
     }
 
-    void delay_comp() {  // echo_control_mobile.c:693-720
+    WMX_CTL_FN void delay_comp() {  // echo_control_mobile.c:693-720
         const int n_far = farend.avail_read(), n_snd = ms_in_snd * 8 * mult, delay_new = n_snd - n_far;
         if (delay_new > 256 - kAecmFrame * mult) {
             int add = (n_snd >> 1) - n_far > kAecmFrame ? (n_snd >> 1) - n_far : kAecmFrame;
@@ -80,7 +83,7 @@ struct AecmCtl {
         }
     }
 
-    void est_buf_delay() {  // echo_control_mobile.c:633-691
+    WMX_CTL_FN void est_buf_delay() {  // echo_control_mobile.c:633-691
         const short n_far = (short)farend.avail_read(), n_snd = (short)(ms_in_snd * 8 * mult);
         short delay_new = (short)(n_snd - n_far);
         if (delay_new < kAecmFrame) {
@@ -101,7 +104,7 @@ struct AecmCtl {
         if (time_for_delay_change > 25) known_delay = (int)filt_delay - 160 > 0 ? (int)filt_delay - 160 : 0;
     }
 
-    int buffer_farend(int n, AecmPlan *pl) {  // echo_control_mobile.c:233-275
+    WMX_CTL_FN int buffer_farend(int n, AecmPlan *pl) {  // echo_control_mobile.c:233-275
         if (n != 80 && n != 160) return -1;
         if (!ec_startup) delay_comp();
         pl->has_far = 1;
@@ -110,7 +113,7 @@ struct AecmCtl {
     }
 
     // WebRtcAecm_ProcessFrame's ring bookkeeping, aecm_core.c:569-664
-    void process_frame(AecmFramePlan *fp) {
+    WMX_CTL_FN void process_frame(AecmFramePlan *fp) {
         int pos;
         frame_ring.write(kAecmFrame, &fp->ring_w);
         fp->n_blocks = 0;
@@ -128,7 +131,7 @@ struct AecmCtl {
 
     // returns what WebRtcAecm_Process returns: 0, or -1 for a delay outside [0, 500] ms -- AFTER the packet has been
     // processed; the wmix wrapper then drops the packet's output and stops (src/webrtc.c:382-387)
-    int process(int n, int ms, AecmPlan *pl) {  // echo_control_mobile.c:277-482
+    WMX_CTL_FN int process(int n, int ms, AecmPlan *pl) {  // echo_control_mobile.c:277-482
         int ret = 0;
         if (n != 80 && n != 160) return -1;
         if (ms < 0)

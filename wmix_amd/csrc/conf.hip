@@ -18,6 +18,9 @@
 // levelling on (wmx_conf_level) wmx_agc_process_legs stands directly behind it: the same rows, in the same order, through the leg's own
 // AGC with the leg's own compression gain.  With the gate on (wmx_conf_gate) wmx_vad_process_legs stands directly behind that: the same
 // rows, in the same order, each one vad_process of the leg's own voice-activity gate, which shifts the row right by the leg's `reduce`.
+// With echo control on (wmx_conf_echo) wmx_aecm_process_legs stands between the denoiser and the leveller -- the heartbeat's order --
+// with the rows alone, and a second time behind the egress with the far row alone: what wmx_rtp_decode_sent_legs makes of the
+// datagram the tick has just sent to the leg.
 //
 // PER SLOT (slot_ring.h, made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a
 // 4-byte boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and the events.  PER HANDLE: the mixer
@@ -62,6 +65,9 @@ struct wmx_conf {
     bool gate_on;      // wmx_vad_process_legs behind the leveller
     wmx_vad *vad;      // a VAD stream per leg (1 x 8000, 20 ms), made when the gate is first switched on
     uint32_t *d_gate;  // [2][n_legs] rows judged voice / not voice per leg, made with it
+    bool echo_on;         // wmx_aecm_process_legs behind the denoiser (rows) and behind the egress (the far row)
+    wmx_aecm *aecm;       // a canceller per leg (wmx_aecm_create_legs), made when echo control is first switched on
+    int16_t *d_echo_far;  // [n_legs][160] what the tick sent to each leg, decoded; made with it
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -90,6 +96,10 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
     }
     if (h->denoise_on) {  // behind the keypad, which is judged on the row as it arrived; selection, concealment and the load see the cleaned rows
         rc = wmx_nsx_process_legs(h->nsx, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, calls, stream);
+        if (rc != 0) return rc;
+    }
+    if (h->echo_on) {  // behind the denoiser and in front of the leveller, the heartbeat's order (NS -> AEC -> AGC -> VAD): the rows only
+        rc = wmx_aecm_process_legs(h->aecm, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, calls, nullptr, 0, stream);
         if (rc != 0) return rc;
     }
     if (h->level_on) {  // behind the denoiser: the level detector hears the cleaned row; selection, concealment and the load see the levelled rows
@@ -123,6 +133,10 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
     if (rc == 0 && bytes != (uint32_t)kDatagram) {
         wmx::set_error("wmx_conf: egress made %u-byte datagrams", bytes);
         return WMX_ESTATE;
+    }
+    if (rc == 0 && h->echo_on) {  // the far end of leg g is the datagram just made for it, as its speaker plays it: far only
+        rc = wmx_rtp_decode_sent_legs(h->snd, d_out, kDatagram, h->d_echo_far, kLegRow, stream);
+        if (rc == 0) rc = wmx_aecm_process_legs(h->aecm, nullptr, 0, 0, 1, nullptr, nullptr, h->d_echo_far, kLegRow, stream);
     }
     return rc;
 }
@@ -169,6 +183,8 @@ int wmx_conf_destroy(wmx_conf *h) {
     if (h->agc) wmx_agc_destroy(h->agc);
     if (h->vad) wmx_vad_destroy(h->vad);
     if (h->d_gate) (void)hipFree(h->d_gate);
+    if (h->aecm) wmx_aecm_destroy(h->aecm);
+    if (h->d_echo_far) (void)hipFree(h->d_echo_far);
     if (h->mix) wmx_mix_destroy(h->mix);
     if (h->snd) wmx_rtp_destroy(h->snd);
     delete h;
@@ -423,6 +439,73 @@ int wmx_conf_export_gate(wmx_conf *h, uint8_t *reduce, uint32_t *voiced, uint32_
     return 0;
 }
 
+// on != 0: every leg's rows of the tick go through the leg's own fixed-point echo canceller (wmx_aecm_process_legs: aec_init(1, 8000, 20)
+// per leg, every row one aec_process with delay_ms reported) behind the denoiser and in front of the leveller, and behind the egress the
+// datagram the tick sent to the leg, decoded with the law it was encoded in, is the canceller's far row; 0 (the default): the launches
+// of a handle that never heard of it.  Between submits.  The canceller and the far rows are made the first time it is switched on, every
+// leg at delay_ms; on a made one delay_ms is set for every leg again; off and on again keeps the state.  A delay outside 0 .. 500 changes
+// nothing, the switch included; off does not look at it.
+int wmx_conf_echo(wmx_conf *h, int on, int delay_ms) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (!on) {
+        h->echo_on = false;
+        return 0;
+    }
+    if (delay_ms < 0 || delay_ms > 500) {
+        wmx::set_error("wmx_conf_echo: delay_ms=%d must be 0 .. 500", delay_ms);
+        return WMX_EINVAL;
+    }
+    if (!h->aecm) {
+        void *p = nullptr;
+        int rc = wmx::zeroed_block(&p, (size_t)h->n_legs * kLegRow * sizeof(int16_t), "hipMemset(far rows)");
+        if (rc != 0) return rc;
+        wmx_aecm *a = nullptr;
+        if ((rc = wmx_aecm_create_legs(&a, h->n_legs)) != 0) {
+            (void)hipFree(p);
+            return rc;
+        }
+        h->aecm = a;
+        h->d_echo_far = static_cast<int16_t *>(p);
+    }
+    const int rc = wmx_aecm_set_delay_legs(h->aecm, nullptr, 0, delay_ms, nullptr);
+    if (rc != 0) return rc;
+    WMX_HIP(hipStreamSynchronize(nullptr));  // (the setters without a stream are complete when they return)
+    h->echo_on = true;
+    return 0;
+}
+
+// the legs' canceller, for wmx_aecm_set_delay_legs / wmx_aecm_export_stream / wmx_aecm_import_stream on a leg; NULL until echo control is
+// first switched on
+wmx_aecm *wmx_conf_canceller(wmx_conf *h) { return h ? h->aecm : nullptr; }
+
+// ec_startup, the far ring's fill in ms, knownDelay and the estimator's last_delay (int32 each) of every leg as the work queued on
+// `stream` leaves them (wmx_aecm_export_legs); any pointer may be NULL; blocking.  Before the first switch-on: 1, 0, 0, -2 -- what the
+// first switch-on makes.
+int wmx_conf_export_echo(wmx_conf *h, int32_t *startup, int32_t *far_ms, int32_t *known_delay, int32_t *delay_blocks, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const size_t n = (size_t)h->n_legs;
+    int32_t *host[4] = {startup, far_ms, known_delay, delay_blocks};
+    if (!h->aecm) {
+        const int32_t fresh[4] = {1, 0, 0, -2};
+        for (int i = 0; i < 4; i++)
+            for (size_t g = 0; host[i] && g < n; g++) host[i][g] = fresh[i];
+        return 0;
+    }
+    hipStream_t s = wmx::as_stream(stream);
+    int32_t *d = nullptr;
+    WMX_HIP(hipMalloc(reinterpret_cast<void **>(&d), 4 * n * sizeof(int32_t)));
+    int rc = wmx_aecm_export_legs(h->aecm, d, d + n, d + 2 * n, d + 3 * n, stream);
+    hipError_t e = hipSuccess;
+    for (int i = 0; rc == 0 && e == hipSuccess && i < 4; i++)
+        if (host[i]) e = hipMemcpyAsync(host[i], d + (size_t)i * n, n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d);
+    if (rc == 0 && e != hipSuccess) rc = wmx::hip_fail(e, "wmx_conf_export_echo", __FILE__, __LINE__);
+    return rc;
+}
+
 // a G.711 codec per leg (wmx_rtp_set_codecs over the legs; NULL = all): between submits, ordered on `stream`
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream) {
     if (!h) return WMX_EINVAL;
@@ -455,6 +538,9 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0 && h->agc) rc = conf_reset_stage(h, h->agc, wmx_agc_reset_streams, host_idx, n, stream);  // nor its level estimate
     if (rc == 0 && h->vad) rc = conf_reset_stage(h, h->vad, wmx_vad_reset_streams, host_idx, n, stream);  // nor its noise model and hangover
     if (rc == 0 && h->vad) rc = conf_reset_gate_counts(h, host_idx, n, stream);
+    if (rc == 0 && h->aecm)  // nor the old call's echo path, far end and start-up; the reported delay stays
+        rc = conf_reset_stage(h, h->aecm, +[](wmx_aecm *a, const int32_t *idx, int k, void *st) { return wmx_aecm_reset_streams(a, idx, k, -1, st); },
+                              host_idx, n, stream);
     return rc;
 }
 

@@ -379,6 +379,21 @@ __global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restri
     }
 }
 
+// What a leg was sent, as its phone's speaker plays it (wmx_rtp_decode_sent_legs): the 160 codes of the leg's outgoing datagram decoded
+// with the law they were encoded in -- the leg's own out_law once a stream has left the default (laws), else the handle's.  One lane
+// per sample; the far end of the leg's echo canceller (aecm.hip, aecm_legs_kernel).
+__global__ __launch_bounds__(256) void rtp_decode_sent_legs_kernel(const uint8_t *__restrict__ packets, long packet_stride, int16_t *__restrict__ pcm,
+                                                                    long pcm_leg_stride, int n_legs, int law_all, const uint8_t *__restrict__ laws) {
+    const size_t total = (size_t)n_legs * kRtpG711Payload;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t leg = t / kRtpG711Payload;
+        const int c = (int)(t - leg * kRtpG711Payload);
+        const int law = laws ? (int)laws[leg] : law_all;
+        const uint32_t code = packets[leg * (size_t)packet_stride + kRtpHeader + c];
+        pcm[leg * (size_t)pcm_leg_stride + c] = (int16_t)(law == WMX_LAW_A ? dec_alaw(code) : dec_ulaw(code));
+    }
+}
+
 // The sequence rule (leg_seq.h) for every leg, one lane per leg: the lane reads its leg's up to four slots (d_len: which are calls;
 // d_seq_raw: header bytes 2..3 as stored, swapped here), sorts the candidates' keys in registers, walks them, writes the call list,
 // zeroes d_len of the slots that make no call and stores the state it read.  WIDE: max_packets == 4 and d_seq_raw on an 8-byte
@@ -844,6 +859,22 @@ int wmx_rtp_egress_rings(wmx_rtp *h, wmx_mix *m, uint8_t *d_packets, long packet
     WMX_LAUNCH_CHECK();
     mix_played(m, 2u * kRtpG711Payload);
     if (packet_bytes) *packet_bytes = (uint32_t)(kRtpHeader + kRtpG711Payload);
+    return 0;
+}
+
+// The payload of each leg's outgoing datagram decoded with that leg's outgoing law (include/wmix_amd.h): the far end of its canceller
+int wmx_rtp_decode_sent_legs(wmx_rtp *h, const uint8_t *d_packets, long packet_stride, int16_t *d_pcm, long pcm_leg_stride, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !d_packets || !d_pcm || packet_stride < kRtpHeader + kRtpG711Payload || (h->n_streams > 1 && pcm_leg_stride < kRtpG711Payload) ||
+        reinterpret_cast<uintptr_t>(d_pcm) % sizeof(int16_t) != 0) {
+        set_error("wmx_rtp_decode_sent_legs: bad arguments (packet_stride %ld >= %d, pcm_leg_stride %ld >= %d, d_pcm on a 2-byte boundary)",
+                  packet_stride, kRtpHeader + kRtpG711Payload, pcm_leg_stride, kRtpG711Payload);
+        return WMX_EINVAL;
+    }
+    const uint8_t *laws = h->codecs_default ? nullptr : h->codec.at<uint8_t>(kCodecOutLaw);
+    hipLaunchKernelGGL(rtp_decode_sent_legs_kernel, dim3(wmx::stream_grid((size_t)h->n_streams * kRtpG711Payload, 256)), dim3(256), 0,
+                       as_stream(stream), d_packets, packet_stride, d_pcm, pcm_leg_stride, h->n_streams, h->law, laws);
+    WMX_LAUNCH_CHECK();
     return 0;
 }
 
