@@ -535,12 +535,38 @@ __device__ __forceinline__ int opaque_lane(int x) {
     return x;
 }
 
+// What a wave keeps in registers for the whole launch (aec_near_kernel forms it behind the barrier, before the stream-active test,
+// with all 64 lanes on): lane constants that every block would otherwise rebuild several times.
+struct AecPins {
+    SplitLane cf;   // rdft128_fwd_coef of the lane: two table reads and five selects, four times per block
+};
+__device__ __forceinline__ AecPins aec_pins(const AecConstsNear &K, int lane) {
+    AecPins P;
+    P.cf = rdft128_fwd_coef(&K.tab, lane, HwLanes{});
+    pin_vgpr(P.cf.wr), pin_vgpr(P.cf.wi), pin_vgpr(P.cf.z);
+    return P;
+}
+
 template <int MULT>  // 1: 8 kHz, 2: 16 kHz
 __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *__restrict__ curves_g, const PowTables *__restrict__ powtab, AecWaveLds &W, AecTaps &taps,
-                                          const AecFarBufs &F, const AecBlkPlan &bp, const AecNoiseEntry *__restrict__ noise_tab, const int lane_in) {
-    // The lane-derived LDS addresses (gather points, twiddle and window slots) are loop invariant; left alone the
-    // compiler hoists ~100 of them out of the packet loop and pins them in VGPRs for the whole kernel.  Recomputing
-    // them per block costs a few VALU ops and frees the registers.
+                                          const AecFarBufs &F, const AecBlkPlan &bp, const AecNoiseEntry *__restrict__ noise_tab, const AecPins &pins,
+                                          const int lane_in) {
+    // The lane-derived LDS addresses (gather points, twiddle and window slots, lane * 4 / lane * 8 + the wave's base, the mirrored
+    // index) are loop invariant; left alone the compiler hoists ~100 of them out of the packet loop, keeps them in VGPRs for the whole
+    // kernel and spills (128 VGPRs + 176 B of scratch).  The budget is 128 VGPRs -- four waves per SIMD -- and no scratch
+    // (tests/test_kernel_budget.py).  Inside it:
+    //   kept for the LAUNCH   `pins` (AecPins): the forward split's coefficients, 3 registers that replace a dozen vector instructions and
+    //                         two LDS reads at each of their four uses per block;
+    //   formed once per BLOCK everything the compiler derives from `lane` below: the lane is laundered on entry (opaque_lane: what
+    //                         is derived from it cannot leave the block loop) and ONCE more, in front of the output transform
+    //                         (AEC_RELANE), so that the addresses of the phases before it die there -- with that one cut the block
+    //                         fits 127 registers; with none it spills 64 B, and with a cut per phase, as this code had when it sat
+    //                         at 125 - 128 registers without the pin, every phase re-derives its addresses (+ 80 vector instructions
+    //                         per block);
+    //   still recomputed      the PCM offsets per sub-frame and the state-out addresses (aec_near_kernel, behind the packet loop):
+    //                         carried across the block loop they cost 17 registers that are not there.
+    // Left out: the signs and rotations of fft64_lanes as eight pinned coefficient vectors -- twelve selects less per block, but
+    // eight registers that the per-block addresses use better (profiles/pinned_lanes/static_counts.txt).
     // `lane_in` is the hardware lane id (aec_near_kernel: threadIdx.x & 63, blocks of 64 * kAecWavesPerBlock threads): the tests of
     // the lane alone are mask constants (lanes<>, lane_sites.h), and the transforms are entered through their HwLanes forms
     using namespace site;
@@ -587,7 +613,6 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     W.cur[lane] = AEC_ST(AS_NEAR_RING + ring_at(bp.near_rd, lane));
     wave_sync();
     AEC_PROF(0);
-    AEC_RELANE();
     // ---- FilterFar (aec_core.c:148-170): y = sum_p X_{n-p} * W_p, partitions in order; lane 0 also does bin 64
     {
         // all 24 far-spectrum values of this lane requested at once (one memory round trip, not one per few partitions);
@@ -632,7 +657,6 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         }
     }
     wave_sync();
-    AEC_RELANE();
     // ---- four transforms side by side, one per lane group: rdft(d) and rdft(d * w) of the near block [dprev | cur]
     //      (aec_core.c:1177-1195, 934-949), ef = rdft([0 | e]) (aec_core.c:1299-1309) and the windowed rdft([eprev | e] * w) of
     //      the NLP.  The reference transforms d before it filters the far end; nothing between the two reads the other's
@@ -657,11 +681,10 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     }
     wave_sync();
     AEC_PROF(2);
-    AEC_RELANE();
     // windowed near spectrum, kept in registers across the filter update (bin = lane; lane 0 also bin 64)
     float dwr, dwi, dw64, dfr, dfi, df64;
     {
-        const SplitLane cf = rdft128_fwd_coef(&K.tab, lane, hw);
+        const SplitLane cf = pins.cf;
         const v2f dwb = rdft128_fwd_bin_u(W.fa[1], cf, lane), dfb = rdft128_fwd_bin_u(W.fa[0], cf, lane);
         dwr = dwb.x, dwi = dwb.y, dw64 = W.fa[1][0] - W.fa[1][1];  // bin 64 = a[0] - a[1] (used by lane 0)
         dfr = dfb.x, dfi = dfb.y, df64 = W.fa[0][0] - W.fa[0][1];
@@ -705,7 +728,7 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     float ewr, ewi, ew64, efr, efi, ef64r, ef64i = 0.f;
     {
         {
-            const SplitLane cf = rdft128_fwd_coef(&K.tab, lane, hw);
+            const SplitLane cf = pins.cf;
             const v2f ewb = rdft128_fwd_bin_u(W.fa[3], cf, lane), efb = rdft128_fwd_bin_u(W.fa[2], cf, lane);
             ewr = ewb.x, ewi = ewb.y, ew64 = W.fa[3][0] - W.fa[3][1];
             efr = efb.x, efi = efb.y, ef64r = W.fa[2][0] - W.fa[2][1];
@@ -733,7 +756,6 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
 #endif
     }
     wave_sync();  // rows 2, 3 are read; the filter update overwrites the work rows
-    AEC_RELANE();
     // ---- FilterAdaptation (aec_core.c:222-270): conj(X_{n-p}) * ef -> time domain, zero the second half,
     //      back to frequency, add to partition p.  Four groups of 16 lanes; partitions 0..7 first (two per group),
     //      then 8..11, through the same eight work rows.
@@ -782,7 +804,6 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         // (LDS runs a wave's accesses in order, so this lands after lane 0's store above)
         if (pass == 0 ? lanes<aec_upd8>() : lanes<aec_upd4>()) fa_row(W, lane)[1] = nyq_r * e64r - nyq_i * e64i;
         wave_sync();
-        AEC_RELANE();
         if (pass == 0) {
             // partitions g and 4 + g of this group as one packed pair (fft_regs.h, Cx2): every lane reads its (and its
             // mirror's) points of both rows before any lane of the group stores to them
@@ -826,9 +847,8 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
             for (int m = 0; m < 4; m++) *reinterpret_cast<float2 *>(row + 2 * (gl + 16 * m)) = make_float2(v[m].r, v[m].i);
         }
         wave_sync();
-        AEC_RELANE();
         {
-            const SplitLane cf = rdft128_fwd_coef(&K.tab, lane, hw);
+            const SplitLane cf = pins.cf;
 #pragma unroll
             for (int q = 0; q < 8; q++) {
                 if (q >= cnt) continue;
@@ -841,7 +861,6 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
     }
     AEC_PROF(3);
 
-    AEC_RELANE();
     // ================================================= NonLinearProcessing (aec_core.c:911-1141)
     constexpr int prefSize = 24 / MULT, minPref = 4 / MULT;
     const float gc0 = MULT == 1 ? 0.9f : 0.93f, gc1 = MULT == 1 ? 0.1f : 0.07f;  // kNormalSmoothingCoefficients
@@ -975,7 +994,6 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         }
     }
     AEC_PROF(6);
-    AEC_RELANE();
     // ComfortNoise's random phases (aec_core.c:476-489).  WebRtcSpl_RandUArray draws 64 numbers per block, seed -> seed * 69069 + 1 mod
     // 2^31 each; bin b's phase comes from draw b: lane l >= 1 takes draw l, lane 0 draw 64 (bin 64's) -- k draws are one multiply-add
     // with precomputed (a_k, c_k), so every lane reaches its draw from the stream's state in one step, and the state moves on by the
@@ -1136,7 +1154,6 @@ __device__ __forceinline__ void aec_block(const AecConstsNear &K, const float *_
         Si[AS_HNLMINCTR] = hNlMinCtr;
     }
     AEC_PROF(7);
-    AEC_RELANE();
     // OverdriveAndSuppress (aec_core.c:272-293) + ComfortNoise (:462-547) + packing for the inverse transform
     const int noise_off = (blk_flags & kAecFlagNoiseInit) ? AS_DINIT : AS_DMIN;
     v2f out_spec = v2f{0.f, 0.f};
@@ -1292,6 +1309,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(WMX_AEC_WAVES, WMX_AEC_WAVES))) __
     // the only block-level barrier: LDS writes drained, then s_barrier -- spelled out because __syncthreads() would also
     // wait for every outstanding global load (the state requests above) in all eight waves
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const AecPins pins = aec_pins(K, lane);  // the constants are in LDS, every lane of every wave is still here
     if (!live) return;
     const PowTables *powtab = reinterpret_cast<const PowTables *>(consts_g + kAecConstWords);  // stays in global memory (L1 / L2 hits)
     AecWaveLds &W = Wv[wave];
@@ -1347,7 +1365,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(WMX_AEC_WAVES, WMX_AEC_WAVES))) __
             }
             wave_sync();
             for (int k = 0; k < sp.n_blocks; k++)
-                aec_block<MULT>(K, consts_g + kAecConstNearWords, powtab, W, taps, F, pl.blk[sp.first_blk + k], noise_tab, lane);
+                aec_block<MULT>(K, consts_g + kAecConstNearWords, powtab, W, taps, F, pl.blk[sp.first_blk + k], noise_tab, pins, lane);
             for (int i = opaque_lane(lane); keep && i < kAecFrame; i += 64) {
                 const int16_t v = (int16_t)AEC_ST(AS_OUT_RING + ring_at(sp.out_rd, i));
                 for (int c = 0; c < chn; c++) out[(s * kAecFrame + i) * chn + c] = v;

@@ -151,6 +151,13 @@ __device__ void ns_frame(const NsConstLds<L> &K, NsWaveLds<L> &W, float *__restr
     constexpr int chn = CHN;  // 1 or 2 (ns_init takes nothing else): compile-time, so the mono kernel carries no high band
     // Lane-derived addresses are loop invariant; left alone the compiler hoists them out of the packet loop and
     // keeps them in VGPRs for the whole kernel.  Re-deriving them per phase is a few VALU ops and frees the registers.
+    // Nothing lane-derived is pinned here, on purpose.  The budget is what the LDS-bound occupancy leaves free -- 96 VGPRs at 16 / 32 kHz
+    // (five waves per SIMD), 72 at 8 kHz (seven), no scratch (tests/test_kernel_budget.py) -- and the kernel uses 70 / 76 and 56 / 59 of
+    // it.  Built and measured inside that budget: the wave's LDS base in a VGPR, the fp64 literal 1 / 720 of fast_exp in a VGPR pair,
+    // the exp scale as a high-word add, and all but two of the NS_RELANE below removed (the entry's and the one behind the noise
+    // estimation: 85 / 90 and 70 / 72 VGPRs) -- 100 vector instructions less in the kernel, 57 less issued per frame, and no time:
+    // SQ_WAVE_CYCLES and the step did not move (profiles/pinned_lanes/: what goes are v_mov_b32 and address adds, the cheapest
+    // instructions there are, beside fp64 chains that set the pace).  So every phase still re-derives its addresses.
     // `lane_in` is the hardware lane id (ns_kernel: threadIdx.x & 63, blocks of 64 * kNsWavesPerBlock threads), so what a test of
     // the lane alone selects in group k is a mask constant (lanes<>, lane_sites.h: site::ns<L> and the ns_* entries)
     using SL = site::ns<L>;

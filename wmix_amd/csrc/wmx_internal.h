@@ -308,6 +308,12 @@ __device__ __forceinline__ void row_st(GlobalF row, unsigned idx, float v) {
     *(GlobalF)((char __attribute__((address_space(1))) *)row + 4u * idx) = v;
 }
 
+// ---- values kept in a VGPR for the rest of the kernel
+// A lane constant that a kernel forms once (a coefficient vector, an address) and wants to KEEP: behind the empty asm the value has
+// no origin, so the register allocator can neither rematerialise it at every use nor fold it back into the instructions that made
+// it.  Costs nothing at run time.  Use it with all 64 lanes active: a value formed under a divergent branch is garbage in the others.
+__device__ __forceinline__ void pin_vgpr(float &x) { asm volatile("" : "+v"(x)); }
+
 // ---- lane predicates as scalar mask constants
 // A test such as `lane == 0`, `lane < 32` or `(lane & 3) == 2` selects a set of lanes that is known when the kernel is compiled, but
 // the compiler cannot know that `lane` is the hardware lane id and spends a v_cmp (and often the v_and / v_lshr in front of it) per
