@@ -2,6 +2,7 @@
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
  *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]
+ *             [--prompt LEN,EVERY[,REPEAT[,GAP]]]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -34,6 +35,12 @@
  * --echo D: every leg's rows go through the leg's own echo canceller between the suppressor and the AGC, with what the bridge sent to
  * that leg as the far end and D ms (0 .. 500) as every leg's reported delay (wmx_conf_echo); the JSON line then carries "echo": D and the
  * legs whose canceller has left its start-up ("echo_running": wmx_conf_export_echo).  It combines with every other flag.
+ * --prompt LEN,EVERY[,REPEAT[,GAP]]: an announcement.  The handle gets a prompt store (wmx_conf_prompts) with one clip of LEN samples of
+ * 1 x 8000 -- sample i is (next & 16383) - 8192 of a second LCG of the same kind, seeded with S + 1, so the network's script is the one
+ * without the flag -- and at tick 0 every EVERY-th leg (EVERY - 1, 2 EVERY - 1, ...) starts playing it (wmx_conf_play): REPEAT passes
+ * (default 1; 0: until the run ends) with GAP ticks of pause between two (default 0).  Each of those legs hears the clip on top of its
+ * conference, or alone if it is in none.  The JSON line then carries "prompt": LEN, the legs playing ("prompt_legs") and the prompts that
+ * ran to their end, summed over the legs ("prompt_done": wmx_conf_export_prompts).  It combines with every other flag.
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -165,7 +172,8 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G, 
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
-                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]\n";
+                        " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]"
+                        " [--prompt LEN,EVERY[,REPEAT[,GAP]]]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -175,6 +183,8 @@ int main(int argc, char **argv) {
     unsigned long seed = 0;
     int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0, level = -1, gate = 0, echo = -1; /* max_gap -1: sequencing off; level -1: levelling off; echo -1: off */
     long correct = -1; /* -1: the library's default = platform/alsa */
+    long prompt_len = 0; /* 0: no prompt */
+    int prompt_every = 0, prompt_repeat = 1, prompt_gap = 0;
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
             sizes = argv[++i];
@@ -199,6 +209,11 @@ int main(int argc, char **argv) {
             echo = atoi(argv[++i]);
             if (echo < 0) {
                 fprintf(stderr, usage, argv[0]);
+                return 2;
+            }
+        } else if (!strcmp(argv[i], "--prompt") && i + 1 < argc) {
+            if (sscanf(argv[++i], "%ld,%d,%d,%d", &prompt_len, &prompt_every, &prompt_repeat, &prompt_gap) < 2 || prompt_len < 1 || prompt_every < 1) {
+                fprintf(stderr, "host_conf: --prompt LEN,EVERY[,REPEAT[,GAP]], LEN >= 1, EVERY >= 1\n");
                 return 2;
             }
         } else if (!strcmp(argv[i], "--level") && i + 1 < argc) {
@@ -258,6 +273,22 @@ int main(int argc, char **argv) {
     if (level >= 0) WMX_OK(wmx_conf_level(h, 1, level));
     if (gate) WMX_OK(wmx_conf_gate(h, 1));
     if (echo >= 0) WMX_OK(wmx_conf_echo(h, 1, echo));
+    int n_prompt_legs = 0;
+    if (prompt_len > 0) { /* what is wrong with REPEAT or GAP is the library's to say */
+        int16_t *pcm = malloc((size_t)prompt_len * sizeof(int16_t));
+        int clip = -1;
+        if (!pcm) return 2;
+        lcg_state = seed + 1;
+        for (long i = 0; i < prompt_len; i++) pcm[i] = (int16_t)((int32_t)(lcg_next() & 16383u) - 8192);
+        WMX_OK(wmx_conf_prompts(h, 1, prompt_len));
+        WMX_OK(wmx_conf_add_clip(h, pcm, prompt_len, &clip));
+        free(pcm);
+        for (int g = prompt_every - 1; g < G; g += prompt_every) {
+            const int32_t leg = g;
+            WMX_OK(wmx_conf_play(h, &leg, 1, clip, prompt_repeat, prompt_gap, NULL));
+            n_prompt_legs++;
+        }
+    }
     int n_ulaw = 0;
     for (int g = 0; g < G; g++) {
         const int32_t leg = g;
@@ -349,6 +380,14 @@ int main(int argc, char **argv) {
         for (int g = 0; g < G; g++) echo_running += startup[g] == 0;
         free(startup);
     }
+    unsigned long n_prompt_done = 0;
+    if (prompt_len > 0) {
+        uint32_t *done = calloc((size_t)G, sizeof(uint32_t));
+        if (!done) return 2;
+        WMX_OK(wmx_conf_export_prompts(h, NULL, NULL, NULL, done, NULL));
+        for (int g = 0; g < G; g++) n_prompt_done += done[g];
+        free(done);
+    }
     uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
@@ -377,6 +416,7 @@ int main(int argc, char **argv) {
     if (level >= 0) printf("\"level\": %d, ", level);
     if (gate) printf("\"gate\": 1, \"voiced\": %lu, \"unvoiced\": %lu, ", n_voiced, n_unvoiced);
     if (echo >= 0) printf("\"echo\": %d, \"echo_running\": %d, ", echo, echo_running);
+    if (prompt_len > 0) printf("\"prompt\": %ld, \"prompt_legs\": %d, \"prompt_done\": %lu, ", prompt_len, n_prompt_legs, n_prompt_done);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

@@ -641,6 +641,48 @@ int wmx_mix_export_leg_cursors(const wmx_mix *m, uint32_t *host_head, uint32_t *
  * the old call had loaded ahead of the play head.  Head and tick are the mixer's, not the ring's, and stay.  A bad index: WMX_EINVAL,
  * nothing reset. */
 int wmx_mix_reset_rings(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
+/* A prompt per ring: an announcement, a beep or hold music played into ring r by a task of its own, as wmix_task_play_wav
+ * (src/wmixTask.c:1353-1595) plays a file into the daemon's ring -- a chunk per wmix_load_data call with the task's own cursor, and at the
+ * end of the file it stops or sleeps `interval` and starts over, `repeat` times.  Only a mixer of 1 x 8000 rings has prompts: clips are
+ * stored in the ring's own format (wmx_pcm_zoom converts anything else, once), so nothing is resampled in a tick.
+ * wmx_mix_prompts(m, max_clips, max_samples): the store, made ONCE and blocking -- one arena of max_samples int16, one clip table
+ * (offset, samples) of max_clips entries and one 32-byte state entry per ring; a second call is WMX_ESTATE.  wmx_mix_add_clip appends a
+ * clip from HOST memory (blocking copy) and gives its index; clips stay until the mixer is destroyed.  Refused with nothing stored:
+ * 0 samples, a full table, an arena too small (WMX_EINVAL), no store (WMX_ESTATE).
+ * wmx_mix_play(m, host_idx, n, clip, repeat, gap_ticks, stream): the n rings host_idx lists (NULL = every ring) start `clip` from its
+ * first sample with a FRESH cursor (the reference's NULL head: a new task); repeat = passes, 0 = until stopped; gap_ticks (0 .. 65 535)
+ * = ticks of pause between two passes, the reference's `interval`.  A play over a playing ring replaces it; what is in the ring plays
+ * out.  wmx_mix_stop: the listed rings go idle.  wmx_mix_reset_prompts: idle and done = 0, what a new call in a reused slot does; a mixer
+ * without a store has nothing to reset.  All three are ordered on `stream`; a bad ring or clip index, a negative repeat or a gap outside
+ * its range is WMX_EINVAL and changes nothing; play and stop without a store are WMX_ESTATE.
+ * wmx_mix_load_prompts(m, stream): ONE tick of every ring's prompt, one launch, one wave per ring; call it behind the tick's load and in
+ * front of its drain -- ring r then receives the other legs' calls first and the prompt's call last, and volumeAdd saturates, so the
+ * order is part of the result.  The rule (wmix_amd/csrc/leg_prompt.h), per ring:
+ *   idle: nothing.   wait > 0: wait--, no call.   Otherwise ONE wmix_load_data call of n = min(160, samples - pos) samples (2 n bytes of
+ *   8000 / 1 / 16, reduce 1) with the task's cursor, pos += n; inside a pass the cursor is kept from call to call.   pos == samples on
+ *   the last pass: idle, done++.   pos == samples with passes left: left-- unless endless, pos = 0, wait = gap_ticks, and the cursor is
+ *   FRESH again, as the reference resets it behind its sleep (`head.U8 = wmix->head.U8; tick = 0`, src/wmixTask.c:1580-1581): the first
+ *   call of EVERY pass jumps to head + VIEW_PLAY_CORRECT, so the pause heard between two passes is gap_ticks ticks (plus the 320 - 2 n
+ *   bytes a short last call leaves unwritten) at every play_correct.
+ * A repeated play inherits the reference's rule for the ring's end: a pass that begins where head + play_correct lies behind it starts
+ * at the ring's START (src/wmix.c:1666-1673), so with play_correct 3 200 the passes that begin in the last 200 ms of a one-second lap
+ * land on top of one another there; one long pass, or a platform with play_correct 0, has no such seam.
+ * A ring in no conference, or alone in one, still plays its prompt.  The call never laps the play head (one call per tick, at most
+ * play_correct + 320 bytes ahead).  Without a store wmx_mix_load_prompts launches nothing, and neither does it in a tick in which no ring
+ * can still be playing: the host keeps, per ring, the launch by which its prompt has ended for certain, from the clip's length, repeat
+ * and gap_ticks (never for an endless play), so a bridge that plays a beep now and then pays for the launch only while it sounds.
+ * The reference's `reduce`, which ducks everything else under a prompt, is NOT reproduced: reduceMode is per destination ring and the
+ * bridge load evaluates a source once for all destinations.  wmx_mix_export_prompts: per ring the clip (int32, -1 when idle), the samples consumed of the current pass, the
+ * passes left (0 while playing: endless) and the prompts that ran to their end since the ring's reset (uint32), as the work queued on
+ * `stream` leaves them; any pointer NULL; blocking; without a store -1, 0, 0, 0. */
+int wmx_mix_prompts(wmx_mix *m, int max_clips, long max_samples);
+int wmx_mix_add_clip(wmx_mix *m, const int16_t *host_pcm, long samples, int *clip);
+int wmx_mix_play(wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream);
+int wmx_mix_stop(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
+int wmx_mix_reset_prompts(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
+int wmx_mix_load_prompts(wmx_mix *m, void *stream);
+int wmx_mix_export_prompts(const wmx_mix *m, int32_t *host_clip, uint32_t *host_pos, uint32_t *host_left, uint32_t *host_done,
+                           void *stream);
 int wmx_mix_drain(wmx_mix *m, int16_t *d_out, uint32_t bytes, long out_stride, void *stream);
 int wmx_mix_export(const wmx_mix *m, int group, int16_t *host_ring, uint32_t *head_off, uint32_t *tick);
 
@@ -1011,6 +1053,20 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * fresh canceller, far end and control plane included; the reported delay stays.  wmx_conf_canceller: the legs' wmx_aecm (NULL until
  * the first switch-on), for wmx_aecm_set_delay_legs and wmx_aecm_export_stream / _import_stream on a leg.  wmx_conf_export_echo:
  * what wmx_aecm_export_legs gives, into host arrays of n_legs int32, any pointer NULL; blocking; before the first switch-on 1, 0, 0, -2.
+ * Prompts: announcements and hold music per leg.  The bridge is one reference daemon per leg, and a prompt to leg g is a wmix_play on
+ * daemon g: one more task, with its own cursor, loading ring g beside the receive threads of the other legs.  wmx_conf_prompts(h,
+ * max_clips, max_samples) makes the store once (wmx_mix_prompts on the handle's mixer; between submits, blocking; a second call is
+ * WMX_ESTATE), and nothing is allocated in a submit afterwards; wmx_conf_add_clip appends a clip of 1 x 8000 int16 from host memory
+ * (wmx_mix_add_clip; other formats are the caller's to convert).  wmx_conf_play(h, host_idx, n, clip, repeat, gap_ticks, stream) /
+ * wmx_conf_stop(h, host_idx, n, stream): wmx_mix_play / wmx_mix_stop over the legs (NULL = every leg), between submits, ordered on
+ * `stream` like wmx_conf_set_codecs.  With a store a tick calls wmx_mix_load_prompts (which launches only while a leg can be playing)
+ * BEHIND the load of the legs and IN FRONT OF wmx_rtp_egress_rings: within a tick ring g receives the other legs' calls first and the prompt's call last.  The rule per leg and tick
+ * is the one stated at wmx_mix_load_prompts.  A prompt passes none of the per-leg stages: it is not sequenced, concealed, denoised,
+ * levelled, gated or ranked by talker selection, and env / speaking do not see it; with echo control on it is part of what the leg is
+ * sent, hence in the leg's far row.  A leg in no conference, or alone in one, receives no legs and still plays its prompt: hold music.
+ * wmx_conf_reset_legs sets the listed legs idle with done = 0 once the store exists.  wmx_conf_export_prompts: wmx_mix_export_prompts
+ * of the handle's legs.  A handle that never makes the store runs exactly the launches it ran before.  The reference's `reduce`
+ * (ducking the conference under the prompt) and resampling inside the tick are left out, for the reasons given at wmx_mix_load_prompts.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -1042,6 +1098,11 @@ wmx_aecm *wmx_conf_canceller(wmx_conf *h);
 int wmx_conf_export_echo(wmx_conf *h, int32_t *startup, int32_t *far_ms, int32_t *known_delay, int32_t *delay_blocks, void *stream);
 int wmx_conf_set_codecs(wmx_conf *h, const int32_t *host_idx, int n, int in_codec, int out_law, void *stream);
 int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uint32_t *refused, void *stream);
+int wmx_conf_prompts(wmx_conf *h, int max_clips, long max_samples);
+int wmx_conf_add_clip(wmx_conf *h, const int16_t *host_pcm, long samples, int *clip);
+int wmx_conf_play(wmx_conf *h, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream);
+int wmx_conf_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
+int wmx_conf_export_prompts(wmx_conf *h, int32_t *clip, uint32_t *pos, uint32_t *left, uint32_t *done, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
 int wmx_conf_slots(const wmx_conf *h);

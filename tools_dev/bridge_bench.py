@@ -84,7 +84,11 @@ twice in every repetition -- and then with one leg in eight sending.
     python tools_dev/bridge_bench.py --gate-kernel 4096 --out profiles/bridge/bridge_gate_bench.json
 --echo D: nothing of the above; the resident tick of wmx_conf on --echo-legs legs (4 096) with echo control off and on at a reported delay
 of D ms, and wmx_aecm_process_legs alone on one row per leg, device time (events)
-    python tools_dev/bridge_bench.py --echo 20 --out profiles/bridge/bridge_echo_bench.json"""
+    python tools_dev/bridge_bench.py --echo 20 --out profiles/bridge/bridge_echo_bench.json
+--prompts N: nothing of the above; the resident tick of wmx_conf on --prompt-legs legs (4 096) without a prompt store, with a store nobody
+plays from, and with N legs playing an endless clip (wmx_conf_play), device time (events).  With a library that has no prompts in
+WMIX_AMD_LIB (the parent's) it measures the first of the three alone.
+    python tools_dev/bridge_bench.py --prompts 4096 --out profiles/bridge/bridge_prompts_bench.json"""
 import argparse
 import json
 import os
@@ -452,6 +456,55 @@ def echo_tick(legs, reps, delay_ms):
     return {"legs": legs, "conferences": len(layout), "delay_ms": delay_ms, "legs_past_startup": running, "ms_per_tick_echo_off": med["off"],
             "ms_per_tick_echo_on": med["on"], "ms_per_tick_added": med["on"] - med["off"], "aecm_process_legs_one_row_ms": float(np.median(alone)),
             "bytes_per_leg_blob": state_bytes}
+
+
+def prompts_tick(legs, reps, playing):
+    """--prompts N: the resident step of wmx_conf on `legs` legs in conferences of 8, every leg one packet per tick, on up to three
+    handles, the sides alternating tick by tick, device time per tick (events) behind 40 ticks of warm-up: a handle without a prompt
+    store; one with a store nobody plays from; one on which the first N legs play an endless clip of 1 000 samples.  A library that
+    has no prompts (the parent's, given in WMIX_AMD_LIB) runs the first side alone: the parent's own figure, by the same tool."""
+    from wmix_amd._lib import lib
+    from wmix_amd.conf import ConfBridge
+    layout = [list(range(c, min(c + 8, legs))) for c in range(0, legs, 8)]
+    rng = np.random.default_rng(13)
+    CYC = 3
+    pk = rng.integers(0, 256, (CYC, legs, 3, 176), dtype=np.uint8)
+    pk[..., :12] = 0
+    pk[..., 0], pk[..., 1] = 0x80, 0x88
+    recv = np.zeros((CYC, legs, 3), np.int32)
+    recv[:, :, 0] = 172
+    r_in, r_recv = torch.from_numpy(pk).cuda(), torch.from_numpy(recv).cuda()
+    r_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+    has = getattr(lib(), "wmx_conf_prompts", None) is not None
+    sides = {}
+    for name in ("no_store", "store_idle", "playing") if has else ("no_store",):
+        cb = ConfBridge(legs, 1, 3)
+        cb.set_conferences(layout)
+        if name != "no_store":
+            cb.prompts(4, 4000)
+            clip = cb.add_clip(rng.integers(-8000, 8000, 1000).astype(np.int16))
+            if name == "playing" and playing > 0:
+                cb.play(list(range(min(playing, legs))), clip, 0, 0)
+        sides[name] = cb
+    ms = {name: [] for name in sides}
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for i in range(40 + reps):
+        for name, cb in sides.items():
+            a.record()
+            cb.step_resident(r_in[i % CYC], r_recv[i % CYC], r_out)
+            b.record()
+            b.synchronize()
+            if i >= 40:
+                ms[name].append(a.elapsed_time(b))
+    still = int((sides["playing"].export_prompts()["clip"] >= 0).sum()) if has else 0
+    for cb in sides.values():
+        cb.close()
+    out = {"legs": legs, "conferences": len(layout), "legs_asked_to_play": playing if has else 0, "legs_playing_at_the_end": still,
+           "library_has_prompts": bool(has)}
+    out.update({"ms_per_tick_" + name: stats(v) for name, v in ms.items()})
+    # per playing leg and tick: 320 bytes of clip read, 320 of ring read and 320 written, the 32-byte state entry read and written, 8 of table
+    out["hbm_bytes_per_playing_leg_and_tick"] = 320 * 3 + 32 * 2 + 8
+    return out
 
 
 def conf_pipe(reps, ulaw_every=0, loss_every=0, denoise=False, steady=False, level=-1):
@@ -895,6 +948,8 @@ if __name__ == "__main__":
     ap.add_argument("--gate-kernel", type=int, default=0, help="wmx_vad_process_legs alone on this many legs beside wmx_vad_process on the same rows; nothing else")
     ap.add_argument("--echo", type=int, default=-1, help="the resident tick on --echo-legs legs with echo control off and on at this reported delay (ms), and the kernel alone; nothing else")
     ap.add_argument("--echo-legs", type=int, default=4096)
+    ap.add_argument("--prompts", type=int, default=-1, help="the resident tick on --prompt-legs legs without a prompt store, with one nobody plays from, and with this many legs playing an endless clip; nothing else")
+    ap.add_argument("--prompt-legs", type=int, default=4096)
     ap.add_argument("--steady", action="store_true", help="with --pipe: every leg sends one packet per tick, on all sides alike")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -913,6 +968,11 @@ if __name__ == "__main__":
     if args.echo >= 0:
         res = {"tool": "bridge_bench --echo", "device": torch.cuda.get_device_name(0), "reps": args.reps,
                "runs": "the builder's own, one process, the sides alternating", "echo": echo_tick(args.echo_legs, args.reps, args.echo), "load": [], "tick": None}
+        args.sizes = args.tick = ""
+        args.ragged, args.speakers, args.pipe = False, 0, False
+    if args.prompts >= 0:
+        res = {"tool": "bridge_bench --prompts", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+               "runs": "the builder's own, one process, the sides alternating", "prompts": prompts_tick(args.prompt_legs, args.reps, args.prompts), "load": [], "tick": None}
         args.sizes = args.tick = ""
         args.ragged, args.speakers, args.pipe = False, 0, False
     if args.pipe:

@@ -188,13 +188,58 @@ class ConfBridge:
               "wmx_conf_export_codecs")
         return r
 
+    def prompts(self, max_clips, max_samples):
+        """make the prompt store, once (wmx_conf_prompts): max_clips clips of max_samples samples of 1 x 8000 int16 in all, between
+        submits, blocking; from then on a tick in which a leg can be playing has one more launch, the legs' prompts, behind the load of
+        the legs"""
+        check(lib().wmx_conf_prompts(self._h, int(max_clips), int(max_samples)), "wmx_conf_prompts")
+
+    def add_clip(self, pcm, freq=8000, channels=1):
+        """append a clip -> its index (wmx_conf_add_clip; blocking).  pcm: int16, interleaved when channels == 2; anything but
+        1 x 8000 goes through the reference's own converter first (pcm_zoom of wmix_amd/mix.py)"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+        if (channels, freq) != (1, 8000) and pcm.size:
+            from .mix import pcm_zoom
+            pcm = np.ascontiguousarray(pcm_zoom(channels, freq, torch.from_numpy(pcm).cuda().reshape(1, -1), 1, 8000)[0].cpu().numpy())
+        clip = C.c_int(-1)
+        check(lib().wmx_conf_add_clip(self._h, pcm.ctypes.data if pcm.size else None, pcm.size, C.byref(clip)), "wmx_conf_add_clip")
+        return clip.value
+
+    def play(self, legs, clip, repeat=1, gap_ticks=0):
+        """the listed legs (None = every leg) start `clip` from its first sample (wmx_conf_play), between submits, ordered on the current
+        stream: repeat passes (0 = until stopped), gap_ticks ticks of 20 ms between two; a play over a playing leg replaces it"""
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_conf_play(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, int(clip), int(repeat),
+                                  int(gap_ticks), self._stream()), "wmx_conf_play")
+
+    def stop(self, legs=None):
+        """the listed legs (None = every leg) go idle (wmx_conf_stop); what is in their rings plays out"""
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_conf_stop(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, self._stream()),
+              "wmx_conf_stop")
+
+    def export_prompts(self):
+        """dict(clip: int32 [n_legs], -1 when idle; pos, left, done: uint32 [n_legs] -- the samples consumed of the current pass, the
+        passes left (0 while playing: until stopped), the prompts that ran to their end since the leg's reset) as the work queued on the
+        current stream leaves them; without a store: -1, 0, 0, 0"""
+        r = {"clip": np.zeros(self.n_legs, np.int32), "pos": np.zeros(self.n_legs, np.uint32), "left": np.zeros(self.n_legs, np.uint32),
+             "done": np.zeros(self.n_legs, np.uint32)}
+        check(lib().wmx_conf_export_prompts(self._h, r["clip"].ctypes.data, r["pos"].ctypes.data, r["left"].ctypes.data, r["done"].ctypes.data,
+                                            self._stream()), "wmx_conf_export_prompts")
+        return r
+
     def set_play_correct(self, n_bytes):
         check(lib().wmx_conf_set_play_correct(self._h, n_bytes), "wmx_conf_set_play_correct")
 
     def reset_legs(self, legs=None):
         """a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
         refused = 0, the concealment history and count zero, no key down and no digit reported, the noise suppressor, the AGC and the
-        gate as new (the gate shut, its counters zero); the leg keeps its codec and its compression gain (None = every leg)"""
+        gate as new (the gate shut, its counters zero), no prompt playing and none counted; the leg keeps its codec and its compression
+        gain (None = every leg)"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return

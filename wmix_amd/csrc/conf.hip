@@ -20,7 +20,9 @@
 // rows, in the same order, each one vad_process of the leg's own voice-activity gate, which shifts the row right by the leg's `reduce`.
 // With echo control on (wmx_conf_echo) wmx_aecm_process_legs stands between the denoiser and the leveller -- the heartbeat's order --
 // with the rows alone, and a second time behind the egress with the far row alone: what wmx_rtp_decode_sent_legs makes of the
-// datagram the tick has just sent to the leg.
+// datagram the tick has just sent to the leg.  With a prompt store (wmx_conf_prompts) wmx_mix_load_prompts stands behind the load and in
+// front of the egress: every leg that plays a clip loads its next 20 ms into its own ring (wmix_amd/csrc/leg_prompt.h), behind what the
+// other legs of its conference loaded there.
 //
 // PER SLOT (slot_ring.h, made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a
 // 4-byte boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and the events.  PER HANDLE: the mixer
@@ -68,6 +70,7 @@ struct wmx_conf {
     bool echo_on;         // wmx_aecm_process_legs behind the denoiser (rows) and behind the egress (the far row)
     wmx_aecm *aecm;       // a canceller per leg (wmx_aecm_create_legs), made when echo control is first switched on
     int16_t *d_echo_far;  // [n_legs][160] what the tick sent to each leg, decoded; made with it
+    bool prompts_made;  // wmx_mix_load_prompts behind the load: the mixer holds the store (wmx_conf_prompts)
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
@@ -128,6 +131,10 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
     else
         rc = wmx_mix_load_minus_legs(h->mix, h->d_pcm, kLegRowBytes, 8000, 1, 16, (long)K * kLegRow, kLegRow, K, h->d_len, load_mute, 1, stream);
     if (rc != 0) return rc;
+    if (h->prompts_made) {  // behind the legs' calls, so that a ring receives its prompt's call last; in front of the drain
+        rc = wmx_mix_load_prompts(h->mix, stream);
+        if (rc != 0) return rc;
+    }
     uint32_t bytes = 0;
     rc = wmx_rtp_egress_rings(h->snd, h->mix, d_out, kDatagram, &bytes, stream);
     if (rc == 0 && bytes != (uint32_t)kDatagram) {
@@ -518,11 +525,51 @@ int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uin
     return wmx_rtp_export_codecs(h->snd, in_codec, out_law, refused, stream);
 }
 
+// ---- prompts: announcements and hold music per leg (wmix_amd/csrc/leg_prompt.h; the mixer owns the store, as it owns the rings)
+// max_clips clips of max_samples samples in all, 1 x 8000 int16, and one state entry per leg: once, between submits, blocking; a
+// second call is WMX_ESTATE.  From then on every tick calls wmx_mix_load_prompts behind the load; it launches while a leg can be
+// playing.
+int wmx_conf_prompts(wmx_conf *h, int max_clips, long max_samples) {
+    if (!h) return WMX_EINVAL;
+    const int rc = wmx_mix_prompts(h->mix, max_clips, max_samples);
+    if (rc == 0) h->prompts_made = true;
+    return rc;
+}
+
+// one more clip (a blocking copy of host memory) -> its index in *clip; 0 samples, a full table, an arena too small: WMX_EINVAL; no
+// store: WMX_ESTATE; nothing is stored then
+int wmx_conf_add_clip(wmx_conf *h, const int16_t *host_pcm, long samples, int *clip) {
+    if (!h) return WMX_EINVAL;
+    return wmx_mix_add_clip(h->mix, host_pcm, samples, clip);
+}
+
+// the listed legs (NULL = every leg) start `clip` from its first sample with a fresh cursor: repeat passes (0: until stopped), gap_ticks
+// (0 .. 65 535) ticks of pause between two; ordered on `stream`.  A bad leg or clip index changes nothing.
+int wmx_conf_play(wmx_conf *h, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_mix_play(h->mix, host_idx, n, clip, repeat, gap_ticks, stream);
+}
+
+// the listed legs (NULL = every leg) go idle; what is in their rings plays out; ordered on `stream`
+int wmx_conf_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_mix_stop(h->mix, host_idx, n, stream);
+}
+
+// clip (int32, -1 when idle), the samples consumed of the current pass, the passes left (uint32; 0 while playing: until stopped) and the
+// prompts that ran to their end since the leg's reset (uint32) of every leg as the work queued on `stream` leaves them; any pointer may
+// be NULL; blocking.  Without a store: -1, 0, 0, 0.
+int wmx_conf_export_prompts(wmx_conf *h, int32_t *clip, uint32_t *pos, uint32_t *left, uint32_t *done, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_mix_export_prompts(h->mix, clip, pos, left, done, stream);
+}
+
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }
 
 // a new call in a used slot: fresh cursor, dropped = 0, env = 0, the ring zeroed, seq = timestamp = 0, the sequence rule unsynced,
 // refused = 0, the concealment history and count zero, the DTMF state fresh, the noise suppressor as ns_init leaves it, the AGC as
-// agc_init leaves it, the gate as vad_init leaves it (`reduce` 4) and its two counters zero; the leg keeps its codec and its compression gain
+// agc_init leaves it, the gate as vad_init leaves it (`reduce` 4) and its two counters zero, no prompt playing and done = 0; the leg keeps
+// its codec and its compression gain
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h || (host_idx && n < 0)) return WMX_EINVAL;
     // before the first of them: a bad index resets nothing
@@ -541,6 +588,7 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0 && h->aecm)  // nor the old call's echo path, far end and start-up; the reported delay stays
         rc = conf_reset_stage(h, h->aecm, +[](wmx_aecm *a, const int32_t *idx, int k, void *st) { return wmx_aecm_reset_streams(a, idx, k, -1, st); },
                               host_idx, n, stream);
+    if (rc == 0 && h->prompts_made) rc = wmx_mix_reset_prompts(h->mix, host_idx, n, stream);  // nor the old call's announcement
     return rc;
 }
 

@@ -23,6 +23,7 @@
 #include "bridge_layout.h"
 #include "speakers.h"
 #include "leg_cursor.h"
+#include "leg_prompt.h"
 
 namespace wmx {
 namespace {
@@ -488,6 +489,50 @@ __global__ __launch_bounds__(256) void leg_reset_kernel(uint32_t *__restrict__ h
     }
 }
 
+// ---- a prompt per leg (leg_prompt.h)
+// One wave = one leg, no loop over legs: the state entry is read before anything is stored, so it and the clip's table entry are
+// wave-uniform (scalar) loads, and an idle leg's wave exits after the one load.  The rule's inputs are all wave-uniform, so the wave
+// evaluates it once, on the scalar side; the lanes take the call's up to 160 ring samples -- ring[pos] = volumeAdd(ring[pos], clip[i]),
+// with the ring's wrap -- and lane 0 writes the state back.  A clip index, an offset, a length or a cursor read from memory never
+// addresses anything as it is: the index is held against the table, offset and length against the arena (a clip that does not fit has
+// no samples, and the rule sets its leg idle), the call's start is reduced into the ring.  Ring g is touched by wave g alone.
+__global__ __launch_bounds__(256) void prompt_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, LegPrompt *__restrict__ state,
+                                                     const PromptClip *__restrict__ table, uint32_t n_clips,
+                                                     const int16_t *__restrict__ arena, uint32_t arena_samples, LegMixState ms, int n_groups) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int g = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    if (g >= n_groups) return;
+    LegPrompt p = state[g];
+    if (p.clip < 0) return;
+    const bool known = (uint32_t)p.clip < n_clips;
+    const PromptClip c = table[known ? (uint32_t)p.clip : 0u];
+    const uint32_t off = c.off < arena_samples ? c.off : 0u;
+    const uint32_t samples = known && c.off < arena_samples && c.samples <= arena_samples - off ? c.samples : 0u;
+    const PromptCall call = leg_prompt_tick(ms, samples, p);
+    const uint32_t start = (call.start / 2u) % ring_samples;
+    const uint32_t n = call.n < (uint32_t)kLegRow ? call.n : (uint32_t)kLegRow;  // from + n <= samples (leg_prompt_tick)
+    int16_t *ring = rings + (size_t)g * ring_samples;
+    const int16_t *src = arena + off + call.from;
+    for (uint32_t i = lane; i < n; i += 64u) {
+        uint32_t pos = start + i;  // both < ring_samples
+        pos -= pos >= ring_samples ? ring_samples : 0u;
+        ring[pos] = volume_add(ring[pos], src[i]);
+    }
+    if (lane == 0u) state[g] = p;
+}
+
+// play, stop and reset: `value` for the listed legs (NULL: every leg); keep_done: the leg's done count stays
+__global__ __launch_bounds__(256) void prompt_set_kernel(LegPrompt *__restrict__ state, const int32_t *__restrict__ idx, int n, int n_groups,
+                                                         LegPrompt value, int keep_done) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int r = idx ? idx[i] : i;
+        if (r < 0 || r >= n_groups) continue;
+        LegPrompt v = value;
+        if (keep_done) v.done = state[r].done;
+        state[r] = v;
+    }
+}
+
 constexpr size_t kMappedMaxBytes = 64 * 1024;  // legacy staging (legacy_stage.h): above this the DMA engines win, the call is copied
 
 }  // namespace
@@ -530,6 +575,18 @@ struct wmx_mix {
     uint32_t *d_leg_head = nullptr, *d_leg_tick = nullptr, *d_leg_dropped = nullptr;
     wmx::LegSpanEntry *d_leg_span = nullptr;
     uint2 *d_leg_win = nullptr;
+    // a prompt per leg (leg_prompt.h), made once by wmx_mix_prompts: one block -- the state entries in front, the clip table behind
+    // them, the arena behind that -- and what the host knows of it
+    wmx::LegPrompt *d_prompt = nullptr;
+    wmx::PromptClip *d_clip_tab = nullptr;
+    int16_t *d_clip_arena = nullptr;
+    std::vector<wmx::PromptClip> clips;  // the clips added so far
+    size_t clip_cap = 0, arena_cap = 0, arena_used = 0;  // clips; samples
+    // Which launch of wmx_mix_load_prompts (counted in prompt_now) is the first that finds ring r idle for certain: an upper bound the
+    // host keeps from what play, stop and reset were given (UINT64_MAX: an endless play).  A tick in which no ring can still be
+    // playing launches nothing.
+    std::vector<uint64_t> prompt_end;
+    uint64_t prompt_now = 0, prompt_last = 0;  // prompt_last: the largest of prompt_end
 };
 
 // rtp.hip's view of the mixer (wmx_rtp_egress_rings plays the rings itself) and wmx_mix_drain's bookkeeping for it
@@ -679,6 +736,7 @@ int wmx_mix_destroy(wmx_mix *m) {
     if (m->d_env) (void)hipFree(m->d_env);
     if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
     if (m->d_leg_span) (void)hipFree(m->d_leg_span);
+    if (m->d_prompt) (void)hipFree(m->d_prompt);
     delete m;
     return 0;
 }
@@ -1018,6 +1076,164 @@ int wmx_mix_export_leg_cursors(const wmx_mix *m, uint32_t *host_head, uint32_t *
     if (host_head) WMX_HIP(hipMemcpy(host_head, m->d_leg_head, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (host_tick) WMX_HIP(hipMemcpy(host_tick, m->d_leg_tick, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (host_dropped) WMX_HIP(hipMemcpy(host_dropped, m->d_leg_dropped, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- a prompt per leg (include/wmix_amd.h, leg_prompt.h)
+// The store: made once, blocking.  Clips are in the ring's own format, so only a mixer of 1 x 8000 rings has one.
+int wmx_mix_prompts(wmx_mix *m, int max_clips, long max_samples) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    if (m->d_prompt) {
+        set_error("wmx_mix_prompts: the mixer has its store already (%zu clips, %zu samples)", m->clip_cap, m->arena_cap);
+        return WMX_ESTATE;
+    }
+    if (m->chn != 1 || m->freq != 8000 || max_clips < 1 || max_clips > (1 << 20) || max_samples < 1 || max_samples > (1L << 30)) {
+        set_error("wmx_mix_prompts: max_clips=%d (1 .. 2^20) max_samples=%ld (1 .. 2^30), and rings of 1 x 8000 (these: %d x %d)", max_clips,
+                  max_samples, m->chn, m->freq);
+        return WMX_EINVAL;
+    }
+    const size_t n = (size_t)m->n_groups, state_bytes = n * sizeof(LegPrompt), tab_bytes = (size_t)max_clips * sizeof(PromptClip);
+    void *p = nullptr;
+    const int rc = zeroed_block(&p, state_bytes + tab_bytes + (size_t)max_samples * sizeof(int16_t), "hipMemset(prompts)");
+    if (rc) return rc;
+    const std::vector<LegPrompt> idle(n, leg_prompt_idle(0u));
+    const hipError_t e = hipMemcpy(p, idle.data(), state_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "hipMemcpy(prompt states)", __FILE__, __LINE__);
+    }
+    m->d_prompt = static_cast<LegPrompt *>(p);
+    m->d_clip_tab = reinterpret_cast<PromptClip *>(m->d_prompt + n);
+    m->d_clip_arena = reinterpret_cast<int16_t *>(m->d_clip_tab + max_clips);
+    m->clip_cap = (size_t)max_clips;
+    m->arena_cap = (size_t)max_samples;
+    m->arena_used = 0;
+    m->clips.clear();
+    m->clips.reserve(m->clip_cap);
+    m->prompt_end.assign(n, 0);
+    m->prompt_now = m->prompt_last = 0;
+    return 0;
+}
+
+// One more clip behind the last: a blocking copy into arena and table entries that no leg refers to yet, so nothing in flight reads them.
+int wmx_mix_add_clip(wmx_mix *m, const int16_t *host_pcm, long samples, int *clip) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    if (!m->d_prompt) {
+        set_error("wmx_mix_add_clip: no store (wmx_mix_prompts)");
+        return WMX_ESTATE;
+    }
+    if (!host_pcm || samples < 1 || m->clips.size() >= m->clip_cap || (size_t)samples > m->arena_cap - m->arena_used) {
+        set_error("wmx_mix_add_clip: %ld samples (at least 1) into a store with %zu of %zu clips and %zu of %zu samples used", samples,
+                  m->clips.size(), m->clip_cap, m->arena_used, m->arena_cap);
+        return WMX_EINVAL;
+    }
+    const PromptClip c{(uint32_t)m->arena_used, (uint32_t)samples};
+    WMX_HIP(hipMemcpy(m->d_clip_arena + m->arena_used, host_pcm, (size_t)samples * sizeof(int16_t), hipMemcpyHostToDevice));
+    WMX_HIP(hipMemcpy(m->d_clip_tab + m->clips.size(), &c, sizeof(c), hipMemcpyHostToDevice));
+    if (clip) *clip = (int)m->clips.size();
+    m->clips.push_back(c);
+    m->arena_used += (size_t)samples;
+    return 0;
+}
+
+// `value` into the listed legs' state entries (NULL = every leg), ordered on `stream`; ticks: the launches of wmx_mix_load_prompts
+// after which such a leg is idle again for certain (0: it is idle now; UINT64_MAX: an endless play)
+static int prompt_set(wmx_mix *m, const char *who, const int32_t *host_idx, int n, const wmx::LegPrompt &value, bool keep_done, uint64_t ticks,
+                      void *stream) {
+    using namespace wmx;
+    if (host_idx && n < 0) return WMX_EINVAL;
+    if (idx_check(host_idx, n, m->n_groups, who, "mixer")) return WMX_EINVAL;
+    if (host_idx && n == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    const int count = host_idx ? n : m->n_groups;
+    if (host_idx) {
+        const int rcu = upload_idx(m->d_reset_idx, m->reset_cap, host_idx, n, s);
+        if (rcu) return rcu;
+    }
+    hipLaunchKernelGGL(prompt_set_kernel, dim3(stream_grid((size_t)count, 256)), dim3(256), 0, s, m->d_prompt,
+                       host_idx ? (const int32_t *)m->d_reset_idx : (const int32_t *)nullptr, count, m->n_groups, value, keep_done ? 1 : 0);
+    WMX_LAUNCH_CHECK();
+    const uint64_t end = ticks == UINT64_MAX ? UINT64_MAX : m->prompt_now + ticks;
+    for (int i = 0; i < count; i++) m->prompt_end[(size_t)(host_idx ? host_idx[i] : i)] = end;
+    m->prompt_last = 0;
+    for (const uint64_t e : m->prompt_end) m->prompt_last = e > m->prompt_last ? e : m->prompt_last;
+    return 0;
+}
+
+int wmx_mix_play(wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    if (!m->d_prompt) {
+        set_error("wmx_mix_play: no store (wmx_mix_prompts)");
+        return WMX_ESTATE;
+    }
+    if (clip < 0 || (size_t)clip >= m->clips.size() || repeat < 0 || gap_ticks < 0 || (uint32_t)gap_ticks > kPromptMaxGap) {
+        set_error("wmx_mix_play: clip=%d (the store holds %zu) repeat=%d (0 = until stopped) gap_ticks=%d (0 .. %u)", clip, m->clips.size(), repeat,
+                  gap_ticks, kPromptMaxGap);
+        return WMX_EINVAL;
+    }
+    // a pass is one call per started 160 samples; between two passes lie gap_ticks ticks without one (leg_prompt.h)
+    const uint64_t per_pass = ((uint64_t)m->clips[(size_t)clip].samples + kLegRow - 1) / kLegRow;
+    const uint64_t ticks = repeat == 0 ? UINT64_MAX : (uint64_t)repeat * per_pass + (uint64_t)(repeat - 1) * (uint64_t)gap_ticks;
+    return prompt_set(m, "wmx_mix_play: ring", host_idx, n, leg_prompt_play(clip, (uint32_t)repeat, (uint32_t)gap_ticks, 0u), true, ticks, stream);
+}
+
+int wmx_mix_stop(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(m);
+    if (!m) return WMX_EINVAL;
+    if (!m->d_prompt) {
+        wmx::set_error("wmx_mix_stop: no store (wmx_mix_prompts)");
+        return WMX_ESTATE;
+    }
+    return prompt_set(m, "wmx_mix_stop: ring", host_idx, n, wmx::leg_prompt_idle(0u), true, 0, stream);
+}
+
+// a new call in a reused slot: idle, done = 0; a mixer without a store has nothing to reset
+int wmx_mix_reset_prompts(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(m);
+    if (!m || (host_idx && n < 0)) return WMX_EINVAL;
+    if (wmx::idx_check(host_idx, n, m->n_groups, "wmx_mix_reset_prompts: ring", "mixer")) return WMX_EINVAL;
+    if (!m->d_prompt) return 0;
+    return prompt_set(m, "wmx_mix_reset_prompts: ring", host_idx, n, wmx::leg_prompt_idle(0u), false, 0, stream);
+}
+
+int wmx_mix_export_prompts(const wmx_mix *m, int32_t *host_clip, uint32_t *host_pos, uint32_t *host_left, uint32_t *host_done, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    const size_t n = (size_t)m->n_groups;
+    std::vector<LegPrompt> st(n, leg_prompt_idle(0u));  // no store: every leg idle
+    if (m->d_prompt) {
+        WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+        WMX_HIP(hipMemcpy(st.data(), m->d_prompt, n * sizeof(LegPrompt), hipMemcpyDeviceToHost));
+    }
+    for (size_t r = 0; r < n; r++) {
+        if (host_clip) host_clip[r] = st[r].clip < 0 ? -1 : st[r].clip;
+        if (host_pos) host_pos[r] = st[r].pos;
+        if (host_left) host_left[r] = st[r].left;
+        if (host_done) host_done[r] = st[r].done;
+    }
+    return 0;
+}
+
+// One tick of every leg's prompt: one launch, one wave per ring, behind the tick's load and in front of its drain.  No store, or no
+// ring that can still be playing (prompt_end): no launch.
+int wmx_mix_load_prompts(wmx_mix *m, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m) return WMX_EINVAL;
+    if (!m->d_prompt || m->prompt_last <= m->prompt_now) return 0;
+    const unsigned waves = 4, grid = ((unsigned)m->n_groups + waves - 1) / waves;
+    hipLaunchKernelGGL(prompt_kernel, dim3(grid), dim3(64 * waves), 0, as_stream(stream), m->d_rings, m->ring_bytes / 2, m->d_prompt,
+                       (const PromptClip *)m->d_clip_tab, (uint32_t)m->clips.size(), (const int16_t *)m->d_clip_arena, (uint32_t)m->arena_cap,
+                       cursor_state(m), m->n_groups);
+    WMX_LAUNCH_CHECK();
+    m->prompt_now++;  // behind the check: a launch that failed has moved no leg
     return 0;
 }
 
