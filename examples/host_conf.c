@@ -2,7 +2,7 @@
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
  *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]
- *             [--prompt LEN,EVERY[,REPEAT[,GAP]]]
+ *             [--prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]]]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -35,12 +35,15 @@
  * --echo D: every leg's rows go through the leg's own echo canceller between the suppressor and the AGC, with what the bridge sent to
  * that leg as the far end and D ms (0 .. 500) as every leg's reported delay (wmx_conf_echo); the JSON line then carries "echo": D and the
  * legs whose canceller has left its start-up ("echo_running": wmx_conf_export_echo).  It combines with every other flag.
- * --prompt LEN,EVERY[,REPEAT[,GAP]]: an announcement.  The handle gets a prompt store (wmx_conf_prompts) with one clip of LEN samples of
+ * --prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]]: an announcement.  The handle gets a prompt store (wmx_conf_prompts) with one clip of LEN samples of
  * 1 x 8000 -- sample i is (next & 16383) - 8192 of a second LCG of the same kind, seeded with S + 1, so the network's script is the one
  * without the flag -- and at tick 0 every EVERY-th leg (EVERY - 1, 2 EVERY - 1, ...) starts playing it (wmx_conf_play): REPEAT passes
  * (default 1; 0: until the run ends) with GAP ticks of pause between two (default 0).  Each of those legs hears the clip on top of its
  * conference, or alone if it is in none.  The JSON line then carries "prompt": LEN, the legs playing ("prompt_legs") and the prompts that
- * ran to their end, summed over the legs ("prompt_done": wmx_conf_export_prompts).  It combines with every other flag.
+ * ran to their end, summed over the legs ("prompt_done": wmx_conf_export_prompts).  With the fifth field the play is
+ * wmx_conf_play_duck(..., REDUCE): while the clip makes calls the rest of the conference reaches the leg divided by REDUCE + 1 (0 .. 15,
+ * the reference's `reduce`), and the JSON line also carries "prompt_reduce": REDUCE and the legs whose next tick would be ducked
+ * ("prompt_ducking": wmx_conf_export_duck); four fields run what they ran before.  It combines with every other flag.
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -173,7 +176,7 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G, 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
                         " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]"
-                        " [--prompt LEN,EVERY[,REPEAT[,GAP]]]\n";
+                        " [--prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]]]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -184,7 +187,7 @@ int main(int argc, char **argv) {
     int slots = 3, have_seed = 0, max_gap = -1, conceal = 0, denoise = 0, level = -1, gate = 0, echo = -1; /* max_gap -1: sequencing off; level -1: levelling off; echo -1: off */
     long correct = -1; /* -1: the library's default = platform/alsa */
     long prompt_len = 0; /* 0: no prompt */
-    int prompt_every = 0, prompt_repeat = 1, prompt_gap = 0;
+    int prompt_every = 0, prompt_repeat = 1, prompt_gap = 0, prompt_reduce = -1; /* -1: no fifth field, wmx_conf_play */
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
             sizes = argv[++i];
@@ -212,8 +215,10 @@ int main(int argc, char **argv) {
                 return 2;
             }
         } else if (!strcmp(argv[i], "--prompt") && i + 1 < argc) {
-            if (sscanf(argv[++i], "%ld,%d,%d,%d", &prompt_len, &prompt_every, &prompt_repeat, &prompt_gap) < 2 || prompt_len < 1 || prompt_every < 1) {
-                fprintf(stderr, "host_conf: --prompt LEN,EVERY[,REPEAT[,GAP]], LEN >= 1, EVERY >= 1\n");
+            const int fields = sscanf(argv[++i], "%ld,%d,%d,%d,%d", &prompt_len, &prompt_every, &prompt_repeat, &prompt_gap, &prompt_reduce);
+            if (fields < 5) prompt_reduce = -1;
+            if (fields < 2 || prompt_len < 1 || prompt_every < 1) {
+                fprintf(stderr, "host_conf: --prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]], LEN >= 1, EVERY >= 1\n");
                 return 2;
             }
         } else if (!strcmp(argv[i], "--level") && i + 1 < argc) {
@@ -274,7 +279,7 @@ int main(int argc, char **argv) {
     if (gate) WMX_OK(wmx_conf_gate(h, 1));
     if (echo >= 0) WMX_OK(wmx_conf_echo(h, 1, echo));
     int n_prompt_legs = 0;
-    if (prompt_len > 0) { /* what is wrong with REPEAT or GAP is the library's to say */
+    if (prompt_len > 0) { /* what is wrong with REPEAT, GAP or REDUCE is the library's to say */
         int16_t *pcm = malloc((size_t)prompt_len * sizeof(int16_t));
         int clip = -1;
         if (!pcm) return 2;
@@ -285,7 +290,10 @@ int main(int argc, char **argv) {
         free(pcm);
         for (int g = prompt_every - 1; g < G; g += prompt_every) {
             const int32_t leg = g;
-            WMX_OK(wmx_conf_play(h, &leg, 1, clip, prompt_repeat, prompt_gap, NULL));
+            if (prompt_reduce == -1)
+                WMX_OK(wmx_conf_play(h, &leg, 1, clip, prompt_repeat, prompt_gap, NULL));
+            else
+                WMX_OK(wmx_conf_play_duck(h, &leg, 1, clip, prompt_repeat, prompt_gap, prompt_reduce, NULL));
             n_prompt_legs++;
         }
     }
@@ -388,6 +396,14 @@ int main(int argc, char **argv) {
         for (int g = 0; g < G; g++) n_prompt_done += done[g];
         free(done);
     }
+    int n_prompt_ducking = 0;
+    if (prompt_len > 0 && prompt_reduce != -1) {
+        uint8_t *divisor = calloc((size_t)G, 1);
+        if (!divisor) return 2;
+        WMX_OK(wmx_conf_export_duck(h, divisor, NULL));
+        for (int g = 0; g < G; g++) n_prompt_ducking += divisor[g] > 1;
+        free(divisor);
+    }
     uint64_t sum = 1469598103934665603ull; /* FNV-1a over the datagrams that went out */
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
@@ -417,6 +433,7 @@ int main(int argc, char **argv) {
     if (gate) printf("\"gate\": 1, \"voiced\": %lu, \"unvoiced\": %lu, ", n_voiced, n_unvoiced);
     if (echo >= 0) printf("\"echo\": %d, \"echo_running\": %d, ", echo, echo_running);
     if (prompt_len > 0) printf("\"prompt\": %ld, \"prompt_legs\": %d, \"prompt_done\": %lu, ", prompt_len, n_prompt_legs, n_prompt_done);
+    if (prompt_len > 0 && prompt_reduce != -1) printf("\"prompt_reduce\": %d, \"prompt_ducking\": %d, ", prompt_reduce, n_prompt_ducking);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

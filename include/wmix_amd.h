@@ -515,6 +515,8 @@ int wmx_mix_set(wmx_mix *m, uint32_t head_off, uint32_t tick, int reduce_mode); 
  * WMX_EINVAL.  (The legacy wmix_load_data of wmix_compat.h reads WMIX_AMD_PLAY_CORRECT=<bytes> from the environment.) */
 int wmx_mix_set_play_correct(wmx_mix *m, uint32_t bytes);
 int wmx_mix_ring_bytes(const wmx_mix *m);
+/* wmx_mix_load, wmx_mix_load_minus and wmx_mix_load_minus_conf divide by the mixer's own reduce_mode alone: no ring is ducked under
+ * its prompt (wmx_mix_play_duck) by them.  Only wmx_mix_load_minus_legs and wmx_mix_load_minus_legs_calls duck. */
 int wmx_mix_load(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample, int n_src,
                  long group_stride, long source_stride, int reduce, uint32_t *head, uint32_t *tick, void *stream);
 /* The bridge load: a mixer whose n_groups rings are read as n_groups / parties conferences of `parties` consecutive rings; ring
@@ -526,7 +528,7 @@ int wmx_mix_load(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, 
  * ON THE DEVICE, non-zero = that participant's source is not loaded anywhere (they still hear the others).
  * One launch, every source read once: the saturating add is order dependent, so this is NOT "total minus own"
  * (wmix_amd/csrc/mix_minus.h).  WMX_EINVAL, nothing launched: parties < 2, parties > WMX_MIX_MAX_PARTIES, n_groups % parties != 0,
- * and whatever wmx_mix_load refuses. */
+ * and whatever wmx_mix_load refuses.  It ducks no ring under a prompt (see wmx_mix_load). */
 #define WMX_MIX_MAX_PARTIES 32
 int wmx_mix_load_minus(wmx_mix *m, int parties, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
                        long conf_stride, long source_stride, const uint8_t *d_mute, int reduce, uint32_t *head, uint32_t *tick,
@@ -550,7 +552,7 @@ int wmx_mix_load_minus(wmx_mix *m, int parties, const int16_t *d_src, uint32_t s
  * uploads nothing (wmix_amd/csrc/bridge_layout.h).
  * WMX_EINVAL, nothing launched, rings, layout and cursors unchanged: a conference of more than WMX_MIX_MAX_PARTIES members, a ring
  * index outside [0, n_groups), a ring listed twice (in one conference or in two), host_off that does not ascend from 0,
- * wmx_mix_load_minus_conf without a layout, and whatever wmx_mix_load refuses. */
+ * wmx_mix_load_minus_conf without a layout, and whatever wmx_mix_load refuses.  It ducks no ring under a prompt (see wmx_mix_load). */
 int wmx_mix_set_conferences(wmx_mix *m, int n_conf, const int32_t *host_off, const int32_t *host_members, void *stream);
 int wmx_mix_conferences(const wmx_mix *m);
 int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len, int freq, int channels, int sample,
@@ -671,13 +673,31 @@ int wmx_mix_reset_rings(wmx_mix *m, const int32_t *host_idx, int n, void *stream
  * play_correct + 320 bytes ahead).  Without a store wmx_mix_load_prompts launches nothing, and neither does it in a tick in which no ring
  * can still be playing: the host keeps, per ring, the launch by which its prompt has ended for certain, from the clip's length, repeat
  * and gap_ticks (never for an endless play), so a bridge that plays a beep now and then pays for the launch only while it sounds.
- * The reference's `reduce`, which ducks everything else under a prompt, is NOT reproduced: reduceMode is per destination ring and the
- * bridge load evaluates a source once for all destinations.  wmx_mix_export_prompts: per ring the clip (int32, -1 when idle), the samples consumed of the current pass, the
+ * wmx_mix_play_duck(..., reduce, stream): wmx_mix_play with the reference's `reduce` (0 .. 15, wmixConf.h:72; anything else is
+ * WMX_EINVAL), the argument of every play call of the reference (wmix.h:48-98): while the prompt plays, everything else loaded into its
+ * ring is divided by D = reduce + 1 and the prompt itself is not.  wmx_mix_play is this with reduce 0.  The rule (leg_prompt.h, REDUCE):
+ * ring r is DUCKED in a tick exactly when its prompt makes a call in that tick and was started with reduce > 0 -- on the state as the
+ * tick's load finds it, in front of wmx_mix_load_prompts: playing, no pause left, samples left.  In a ducked tick every call another leg
+ * makes into ring r adds trunc(c / D) per sample, the C division BEFORE the saturating add (src/wmix.c:1675-1676, 1685; a silence call
+ * or a muted source adds 0 as ever); the prompt's own call is undivided and still last.  The pause between two passes is not ducked,
+ * the first tick of the next pass is (src/wmixTask.c:1525-1527, 1555-1557); stop, reset and the end of the last pass release the duck; a
+ * play over a playing ring replaces the divisor.  The play task takes the mode only if reduceMode == 1, so rings are ducked only while
+ * the mixer's reduce_mode is 1; on any other mixer a ducking play is an ordinary play.  For a ducked ring the load's rdce is
+ * (reduce == D) ? 1 : D with the load's own `reduce`.  Only wmx_mix_load_minus_legs and wmx_mix_load_minus_legs_calls duck: in a tick in
+ * which a ducking play can still be making calls (the host's bound, as for wmx_mix_load_prompts) they launch one block per conference
+ * in front of the sweeps, which fills the ducked members' rings by the plain ordered fold -- the members other than itself in list order,
+ * x = clamp16(x + c / D) -- and the sweeps leave those rings alone; every other ring comes out of the two sweeps as ever, the ducked
+ * member's source in it undivided.  Every other tick launches exactly what it launched before.  A ducked ring in no conference, or
+ * alone in one, has nothing to duck.  wmx_mix_export_duck: per ring (n_groups bytes) the divisor the next load will apply, 1 for none,
+ * as the work queued on `stream` leaves it; blocking; 1 everywhere without a store or on a mixer whose reduce_mode is not 1.
+ * wmx_mix_export_prompts: per ring the clip (int32, -1 when idle), the samples consumed of the current pass, the
  * passes left (0 while playing: endless) and the prompts that ran to their end since the ring's reset (uint32), as the work queued on
  * `stream` leaves them; any pointer NULL; blocking; without a store -1, 0, 0, 0. */
 int wmx_mix_prompts(wmx_mix *m, int max_clips, long max_samples);
 int wmx_mix_add_clip(wmx_mix *m, const int16_t *host_pcm, long samples, int *clip);
 int wmx_mix_play(wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream);
+int wmx_mix_play_duck(wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, int reduce, void *stream);
+int wmx_mix_export_duck(const wmx_mix *m, uint8_t *host_divisor, void *stream);
 int wmx_mix_stop(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
 int wmx_mix_reset_prompts(wmx_mix *m, const int32_t *host_idx, int n, void *stream);
 int wmx_mix_load_prompts(wmx_mix *m, void *stream);
@@ -1065,8 +1085,13 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * levelled, gated or ranked by talker selection, and env / speaking do not see it; with echo control on it is part of what the leg is
  * sent, hence in the leg's far row.  A leg in no conference, or alone in one, receives no legs and still plays its prompt: hold music.
  * wmx_conf_reset_legs sets the listed legs idle with done = 0 once the store exists.  wmx_conf_export_prompts: wmx_mix_export_prompts
- * of the handle's legs.  A handle that never makes the store runs exactly the launches it ran before.  The reference's `reduce`
- * (ducking the conference under the prompt) and resampling inside the tick are left out, for the reasons given at wmx_mix_load_prompts.
+ * of the handle's legs.  A handle that never makes the store runs exactly the launches it ran before.  wmx_conf_play_duck(...,
+ * reduce, stream): wmx_mix_play_duck over the legs -- the reference's `reduce`, 0 .. 15: while the prompt makes calls the rest of the
+ * conference reaches leg g divided by reduce + 1, the prompt undivided on top, so that "one minute left" is understood over five people
+ * talking; the gap between two passes is not ducked; the rule is stated at wmx_mix_play_duck.  With echo control on the far row of a
+ * ducked leg is the ducked mix it was sent.  Only ticks in which a ducking prompt can be making a call run the ducking form of the
+ * load.  wmx_conf_export_duck: wmx_mix_export_duck of the handle's legs.  Resampling inside the tick is left out, for the reason
+ * given at wmx_mix_prompts.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -1101,8 +1126,10 @@ int wmx_conf_export_codecs(wmx_conf *h, uint8_t *in_codec, uint8_t *out_law, uin
 int wmx_conf_prompts(wmx_conf *h, int max_clips, long max_samples);
 int wmx_conf_add_clip(wmx_conf *h, const int16_t *host_pcm, long samples, int *clip);
 int wmx_conf_play(wmx_conf *h, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream);
+int wmx_conf_play_duck(wmx_conf *h, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, int reduce, void *stream);
 int wmx_conf_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
 int wmx_conf_export_prompts(wmx_conf *h, int32_t *clip, uint32_t *pos, uint32_t *left, uint32_t *done, void *stream);
+int wmx_conf_export_duck(wmx_conf *h, uint8_t *divisor, void *stream);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
 int wmx_conf_slots(const wmx_conf *h);

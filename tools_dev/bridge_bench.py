@@ -88,7 +88,11 @@ of D ms, and wmx_aecm_process_legs alone on one row per leg, device time (events
 --prompts N: nothing of the above; the resident tick of wmx_conf on --prompt-legs legs (4 096) without a prompt store, with a store nobody
 plays from, and with N legs playing an endless clip (wmx_conf_play), device time (events).  With a library that has no prompts in
 WMIX_AMD_LIB (the parent's) it measures the first of the three alone.
-    python tools_dev/bridge_bench.py --prompts 4096 --out profiles/bridge/bridge_prompts_bench.json"""
+    python tools_dev/bridge_bench.py --prompts 4096 --out profiles/bridge/bridge_prompts_bench.json
+--prompts N --duck R adds the duck (wmx_conf_play_duck): a fourth side on which the N legs play the clip with reduce = R, so that every
+conference of 8 has all its rings ducked in every tick, and a fifth on which one leg of every conference does, the other seven
+playing with reduce 0.  A library without wmx_conf_play_duck (the parent's) runs the first three alone.
+    python tools_dev/bridge_bench.py --prompts 4096 --duck 1 --out file.json    (profiles/bridge/bridge_duck_bench.json is made of such runs)"""
 import argparse
 import json
 import os
@@ -458,11 +462,13 @@ def echo_tick(legs, reps, delay_ms):
             "bytes_per_leg_blob": state_bytes}
 
 
-def prompts_tick(legs, reps, playing):
+def prompts_tick(legs, reps, playing, duck=0):
     """--prompts N: the resident step of wmx_conf on `legs` legs in conferences of 8, every leg one packet per tick, on up to three
     handles, the sides alternating tick by tick, device time per tick (events) behind 40 ticks of warm-up: a handle without a prompt
     store; one with a store nobody plays from; one on which the first N legs play an endless clip of 1 000 samples.  A library that
-    has no prompts (the parent's, given in WMIX_AMD_LIB) runs the first side alone: the parent's own figure, by the same tool."""
+    has no prompts (the parent's, given in WMIX_AMD_LIB) runs the first side alone: the parent's own figure, by the same tool.
+    duck = R > 0: two more handles, the N legs playing with reduce = R, and one leg of every conference with reduce = R beside seven with
+    reduce 0; a library without wmx_conf_play_duck leaves them out."""
     from wmix_amd._lib import lib
     from wmix_amd.conf import ConfBridge
     layout = [list(range(c, min(c + 8, legs))) for c in range(0, legs, 8)]
@@ -476,15 +482,23 @@ def prompts_tick(legs, reps, playing):
     r_in, r_recv = torch.from_numpy(pk).cuda(), torch.from_numpy(recv).cuda()
     r_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
     has = getattr(lib(), "wmx_conf_prompts", None) is not None
+    has_duck = duck > 0 and playing > 0 and getattr(lib(), "wmx_conf_play_duck", None) is not None
     sides = {}
-    for name in ("no_store", "store_idle", "playing") if has else ("no_store",):
+    names = ("no_store", "store_idle", "playing") if has else ("no_store",)
+    for name in names + (("duck_all", "duck_one_per_conference") if has_duck else ()):
         cb = ConfBridge(legs, 1, 3)
         cb.set_conferences(layout)
         if name != "no_store":
             cb.prompts(4, 4000)
             clip = cb.add_clip(rng.integers(-8000, 8000, 1000).astype(np.int16))
+            who = list(range(min(playing, legs)))
             if name == "playing" and playing > 0:
-                cb.play(list(range(min(playing, legs))), clip, 0, 0)
+                cb.play(who, clip, 0, 0)
+            if name == "duck_all":
+                cb.play(who, clip, 0, 0, reduce=duck)
+            if name == "duck_one_per_conference":
+                cb.play([g for g in who if g % 8], clip, 0, 0)
+                cb.play([g for g in who if g % 8 == 0], clip, 0, 0, reduce=duck)
         sides[name] = cb
     ms = {name: [] for name in sides}
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -497,10 +511,14 @@ def prompts_tick(legs, reps, playing):
             if i >= 40:
                 ms[name].append(a.elapsed_time(b))
     still = int((sides["playing"].export_prompts()["clip"] >= 0).sum()) if has else 0
+    ducked = {name: int((sides[name].export_duck() > 1).sum()) for name in ("duck_all", "duck_one_per_conference")} if has_duck else {}
     for cb in sides.values():
         cb.close()
     out = {"legs": legs, "conferences": len(layout), "legs_asked_to_play": playing if has else 0, "legs_playing_at_the_end": still,
-           "library_has_prompts": bool(has)}
+           "library_has_prompts": bool(has), "library_ducks": bool(has_duck)}
+    if has_duck:
+        out["reduce"] = duck
+        out["rings_ducked_at_the_end"] = ducked
     out.update({"ms_per_tick_" + name: stats(v) for name, v in ms.items()})
     # per playing leg and tick: 320 bytes of clip read, 320 of ring read and 320 written, the 32-byte state entry read and written, 8 of table
     out["hbm_bytes_per_playing_leg_and_tick"] = 320 * 3 + 32 * 2 + 8
@@ -948,6 +966,7 @@ if __name__ == "__main__":
     ap.add_argument("--gate-kernel", type=int, default=0, help="wmx_vad_process_legs alone on this many legs beside wmx_vad_process on the same rows; nothing else")
     ap.add_argument("--echo", type=int, default=-1, help="the resident tick on --echo-legs legs with echo control off and on at this reported delay (ms), and the kernel alone; nothing else")
     ap.add_argument("--echo-legs", type=int, default=4096)
+    ap.add_argument("--duck", type=int, default=0, help="with --prompts N: two more sides, the N legs playing with this reduce (1 .. 15), and one leg of every conference of 8")
     ap.add_argument("--prompts", type=int, default=-1, help="the resident tick on --prompt-legs legs without a prompt store, with one nobody plays from, and with this many legs playing an endless clip; nothing else")
     ap.add_argument("--prompt-legs", type=int, default=4096)
     ap.add_argument("--steady", action="store_true", help="with --pipe: every leg sends one packet per tick, on all sides alike")
@@ -972,7 +991,8 @@ if __name__ == "__main__":
         args.ragged, args.speakers, args.pipe = False, 0, False
     if args.prompts >= 0:
         res = {"tool": "bridge_bench --prompts", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-               "runs": "the builder's own, one process, the sides alternating", "prompts": prompts_tick(args.prompt_legs, args.reps, args.prompts), "load": [], "tick": None}
+               "runs": "the builder's own, one process, the sides alternating",
+               "prompts": prompts_tick(args.prompt_legs, args.reps, args.prompts, args.duck), "load": [], "tick": None}
         args.sizes = args.tick = ""
         args.ragged, args.speakers, args.pipe = False, 0, False
     if args.pipe:

@@ -205,14 +205,20 @@ class ConfBridge:
         check(lib().wmx_conf_add_clip(self._h, pcm.ctypes.data if pcm.size else None, pcm.size, C.byref(clip)), "wmx_conf_add_clip")
         return clip.value
 
-    def play(self, legs, clip, repeat=1, gap_ticks=0):
+    def play(self, legs, clip, repeat=1, gap_ticks=0, reduce=0):
         """the listed legs (None = every leg) start `clip` from its first sample (wmx_conf_play), between submits, ordered on the current
-        stream: repeat passes (0 = until stopped), gap_ticks ticks of 20 ms between two; a play over a playing leg replaces it"""
+        stream: repeat passes (0 = until stopped), gap_ticks ticks of 20 ms between two; a play over a playing leg replaces it.
+        reduce (0 .. 15, the reference's argument; wmx_conf_play_duck): while the prompt makes calls the rest of the conference reaches
+        the leg divided by reduce + 1, the prompt undivided on top; the gap between two passes is not ducked"""
         idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
         if idx is not None and idx.size == 0:
             return
-        check(lib().wmx_conf_play(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, int(clip), int(repeat),
-                                  int(gap_ticks), self._stream()), "wmx_conf_play")
+        ptr, n = (None, 0) if idx is None else (idx.ctypes.data, idx.size)
+        if reduce:
+            check(lib().wmx_conf_play_duck(self._h, ptr, n, int(clip), int(repeat), int(gap_ticks), int(reduce), self._stream()),
+                  "wmx_conf_play_duck")
+        else:
+            check(lib().wmx_conf_play(self._h, ptr, n, int(clip), int(repeat), int(gap_ticks), self._stream()), "wmx_conf_play")
 
     def stop(self, legs=None):
         """the listed legs (None = every leg) go idle (wmx_conf_stop); what is in their rings plays out"""
@@ -230,6 +236,13 @@ class ConfBridge:
              "done": np.zeros(self.n_legs, np.uint32)}
         check(lib().wmx_conf_export_prompts(self._h, r["clip"].ctypes.data, r["pos"].ctypes.data, r["left"].ctypes.data, r["done"].ctypes.data,
                                             self._stream()), "wmx_conf_export_prompts")
+        return r
+
+    def export_duck(self):
+        """uint8 [n_legs]: the divisor the next tick's load applies to what the others add to each leg's ring, 1 for none
+        (wmx_conf_export_duck), as the work queued on the current stream leaves it"""
+        r = np.ones(self.n_legs, np.uint8)
+        check(lib().wmx_conf_export_duck(self._h, r.ctypes.data, self._stream()), "wmx_conf_export_duck")
         return r
 
     def set_play_correct(self, n_bytes):

@@ -550,6 +550,13 @@ int wmx_conf_play(wmx_conf *h, const int32_t *host_idx, int n, int clip, int rep
     return wmx_mix_play(h->mix, host_idx, n, clip, repeat, gap_ticks, stream);
 }
 
+// the same with the reference's `reduce` (0 .. 15): while the prompt makes calls the rest of the conference reaches the leg divided by
+// reduce + 1 (leg_prompt.h, REDUCE)
+int wmx_conf_play_duck(wmx_conf *h, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, int reduce, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_mix_play_duck(h->mix, host_idx, n, clip, repeat, gap_ticks, reduce, stream);
+}
+
 // the listed legs (NULL = every leg) go idle; what is in their rings plays out; ordered on `stream`
 int wmx_conf_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
     if (!h) return WMX_EINVAL;
@@ -562,6 +569,12 @@ int wmx_conf_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
 int wmx_conf_export_prompts(wmx_conf *h, int32_t *clip, uint32_t *pos, uint32_t *left, uint32_t *done, void *stream) {
     if (!h) return WMX_EINVAL;
     return wmx_mix_export_prompts(h->mix, clip, pos, left, done, stream);
+}
+
+// per leg the divisor the next tick's load applies to what the others add to its ring, 1 for none; blocking
+int wmx_conf_export_duck(wmx_conf *h, uint8_t *divisor, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_mix_export_duck(h->mix, divisor, stream);
 }
 
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes) { return h ? wmx_mix_set_play_correct(h->mix, bytes) : WMX_EINVAL; }

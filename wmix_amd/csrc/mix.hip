@@ -104,10 +104,12 @@ __global__ __launch_bounds__(256) void drain_kernel(int16_t *__restrict__ rings,
 // unrolled, `q < n` predicates): no scratch.  load_minus_conf_kernel keeps a copy of the sweeps (see there).  ring(q): the address of member q's sample in this column.  value(q, c): sets c to what
 // source q adds and returns true, or returns false and leaves the 0 -- a muted source, or one that does not cover the column, adds 0,
 // which is what not calling wmix_load_data for it leaves.  SKIP_EMPTY: a column for which every value() returned false is not written.
+// DUCK: member q with bit q of `ducked` set is not written -- its ring is duck_fold_kernel's this tick (leg_prompt.h, REDUCE); its
+// source counts for everybody else as ever.
 // The kernels' closures capture BY VALUE and are taken by reference here: with reference captures the compiler no longer hoists the
 // schedule entry's per-column arithmetic out of the sweep (5 % more instructions, 2 % more time on 65 536 conferences of 8).
-template <int PMAX, bool SKIP_EMPTY, class Ring, class Value>
-__device__ __forceinline__ void minus_sweeps(int n, const Ring &ring, const Value &value) {
+template <int PMAX, bool SKIP_EMPTY, bool DUCK = false, class Ring, class Value>
+__device__ __forceinline__ void minus_sweeps(int n, const Ring &ring, const Value &value, uint32_t ducked = 0u) {
     int c[PMAX], y[PMAX];
     bool any = false;
     ClampMap f = clamp_map_identity();
@@ -126,7 +128,7 @@ __device__ __forceinline__ void minus_sweeps(int n, const Ring &ring, const Valu
 #pragma unroll
     for (int q = PMAX - 1; q >= 0; q--) {
         if (q < n) {
-            *ring(q) = clamp_map_apply(g, (int16_t)y[q]);
+            if (!DUCK || !((ducked >> q) & 1u)) *ring(q) = clamp_map_apply(g, (int16_t)y[q]);
             g = clamp_map_add_then((int16_t)c[q], g);
         }
     }
@@ -436,16 +438,20 @@ __global__ __launch_bounds__(256) void leg_cursor_kernel(const int32_t *__restri
 // exits.  A source whose span does not cover the column adds 0, which is what not calling wmix_load_data leaves; a column no
 // source covers is not written.  A leg's span covers no ring sample twice (leg_cursor.h), a ring is in one conference only and a
 // column is one thread's: no two threads touch the same ring sample.  CALLS: a call whose bit in the span's silence mask (pad) is set
-// adds 0 like a source that does not cover the column.
-template <int PMAX, bool CALLS>
+// adds 0 like a source that does not cover the column.  DUCK (a tick in which a ring can be ducked under its prompt): the members in the
+// slot's mask `duck` are not written here; duck_fold_kernel, in front of this launch, has filled their rings.  Without DUCK `duck` is
+// not read.
+template <int PMAX, bool CALLS, bool DUCK>
 __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
                                                               const LoadEntry *__restrict__ sch, uint32_t n_out, uint32_t n_pad,
                                                               const int32_t *__restrict__ tab, const uint2 *__restrict__ win,
                                                               const LegSpanEntry *__restrict__ span, const int32_t *__restrict__ members,
-                                                              long source_stride, long packet_stride, int rdce, int n_groups, int n_slots) {
+                                                              long source_stride, long packet_stride, int rdce, int n_groups, int n_slots,
+                                                              const uint32_t *__restrict__ duck) {
     const size_t total = (size_t)n_pad * n_slots;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t / n_pad));
+        const uint32_t ducked = DUCK ? duck[slot] : 0u;
         const uint2 w = win[slot];
         const uint32_t wstart = w.x < ring_samples ? w.x : 0u, wlen = w.y < ring_samples ? w.y : ring_samples;
         const int32_t *mem = members + tab[2 * (size_t)slot];
@@ -459,7 +465,7 @@ __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restric
                 const int32_t ri = mem[q];
                 return (size_t)(ri >= 0 && ri < n_groups ? ri : 0);
             };
-            minus_sweeps<PMAX, true>(
+            minus_sweeps<PMAX, true, DUCK>(
                 n, [=](int q) { return rings + ring_of(q) * ring_samples + pos; },
                 [=](int q, int &c) {
                     const size_t r = ring_of(q);
@@ -472,7 +478,8 @@ __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restric
                     const uint32_t k = (e.slots >> (2u * j)) & 3u;
                     c = load_entry_value(src + r * source_stride + (size_t)k * packet_stride, sch[d - j * n_out], rdce);
                     return true;
-                });
+                },
+                ducked);
         }
     }
 }
@@ -496,6 +503,14 @@ __global__ __launch_bounds__(256) void leg_reset_kernel(uint32_t *__restrict__ h
 // with the ring's wrap -- and lane 0 writes the state back.  A clip index, an offset, a length or a cursor read from memory never
 // addresses anything as it is: the index is held against the table, offset and length against the arena (a clip that does not fit has
 // no samples, and the rule sets its leg idle), the call's start is reduced into the ring.  Ring g is touched by wave g alone.
+// the clip a state entry names, held against the table and the arena: a clip that does not fit has no samples
+__device__ __forceinline__ PromptClip prompt_clip_of(int32_t clip, const PromptClip *__restrict__ table, uint32_t n_clips, uint32_t arena_samples) {
+    const bool known = clip >= 0 && (uint32_t)clip < n_clips;
+    const PromptClip c = table[known ? (uint32_t)clip : 0u];
+    const uint32_t off = c.off < arena_samples ? c.off : 0u;
+    return PromptClip{off, known && c.off < arena_samples && c.samples <= arena_samples - off ? c.samples : 0u};
+}
+
 __global__ __launch_bounds__(256) void prompt_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, LegPrompt *__restrict__ state,
                                                      const PromptClip *__restrict__ table, uint32_t n_clips,
                                                      const int16_t *__restrict__ arena, uint32_t arena_samples, LegMixState ms, int n_groups) {
@@ -504,10 +519,8 @@ __global__ __launch_bounds__(256) void prompt_kernel(int16_t *__restrict__ rings
     if (g >= n_groups) return;
     LegPrompt p = state[g];
     if (p.clip < 0) return;
-    const bool known = (uint32_t)p.clip < n_clips;
-    const PromptClip c = table[known ? (uint32_t)p.clip : 0u];
-    const uint32_t off = c.off < arena_samples ? c.off : 0u;
-    const uint32_t samples = known && c.off < arena_samples && c.samples <= arena_samples - off ? c.samples : 0u;
+    const PromptClip c = prompt_clip_of(p.clip, table, n_clips, arena_samples);
+    const uint32_t off = c.off, samples = c.samples;
     const PromptCall call = leg_prompt_tick(ms, samples, p);
     const uint32_t start = (call.start / 2u) % ring_samples;
     const uint32_t n = call.n < (uint32_t)kLegRow ? call.n : (uint32_t)kLegRow;  // from + n <= samples (leg_prompt_tick)
@@ -519,6 +532,80 @@ __global__ __launch_bounds__(256) void prompt_kernel(int16_t *__restrict__ rings
         ring[pos] = volume_add(ring[pos], src[i]);
     }
     if (lane == 0u) state[g] = p;
+}
+
+// ---- the duck: the conference under a leg's prompt (leg_prompt.h, REDUCE)
+// Launched in front of the DUCK form of load_minus_legs_kernel, behind leg_cursor_kernel, and only in a tick in which the host knows
+// that some ring can be ducked.  One block of four waves = one conference of the layout, no loop over conferences.  First, in every
+// wave, lane p = member p (leg_cursor_kernel's dealing) reads its leg's prompt entry and evaluates leg_prompt_ducks on it -- the state as
+// the tick finds it: the prompts' step comes behind the load -- and a ballot makes the slot's mask of ducked members, which the first
+// lane of the block leaves in duck[slot] for the sweeps, which then do not write those rings.  The mask is wave-uniform; a wave whose
+// mask is empty exits there.  Otherwise a scalar loop runs over the ducked members g, the block's threads take the columns of the
+// conference's window (a fold is a chain of dependent loads, so the columns are spread over the waves rather than walked by one), and
+// per column a scalar loop runs over the members other than g in list order with the sweeps' own span / slot / silence-mask lookup:
+//   x = ring_g[pos];  x = volumeAdd(x, c_s / rdce) for every s != g that covers the column;  ring_g[pos] = x, once, if any did
+// with rdce = (reduce == D) ? 1 : D, the load's line (src/wmix.c:1675-1676) on a daemon whose reduceMode the play task holds at D.
+// The divisor comes out of leg_prompt_divisor, 1 .. 16 whatever the entry holds; member and clip indices are held against n_groups and
+// the table as everywhere.  Ring g's column is one lane's, ring g is in this conference only and the sweeps leave it alone: no two
+// threads touch one ring sample.
+__global__ __launch_bounds__(256) void duck_fold_kernel(int16_t *__restrict__ rings, uint32_t ring_samples, const int16_t *__restrict__ src,
+                                                        const LoadEntry *__restrict__ sch, uint32_t n_out, const int32_t *__restrict__ tab,
+                                                        const uint2 *__restrict__ win, const LegSpanEntry *__restrict__ span,
+                                                        const int32_t *__restrict__ members, long source_stride, long packet_stride, int reduce,
+                                                        const LegPrompt *__restrict__ state, const PromptClip *__restrict__ table,
+                                                        uint32_t n_clips, uint32_t arena_samples, uint32_t *__restrict__ duck, int n_groups,
+                                                        int n_slots) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int slot = (int)blockIdx.x;
+    if (slot >= n_slots) return;
+    const int32_t *mem = members + tab[2 * (size_t)slot];
+    int n = tab[2 * (size_t)slot + 1];
+    n = n < 0 ? 0 : (n > kBridgeMaxParties ? kBridgeMaxParties : n);
+    uint32_t div = 1u;
+    if ((int)lane < n) {
+        const int32_t r = mem[lane];
+        if (r >= 0 && r < n_groups) {
+            const LegPrompt p = state[r];
+            div = leg_prompt_ducks(p, prompt_clip_of(p.clip, table, n_clips, arena_samples).samples);
+        }
+    }
+    const uint32_t mask = (uint32_t)__ballot(div > 1u);  // n <= 32: the lanes behind it bring 1
+    if (threadIdx.x == 0u) duck[slot] = mask;
+    if (!mask) return;
+    const uint2 w = win[slot];
+    const uint32_t wstart = w.x < ring_samples ? w.x : 0u, wlen = w.y < ring_samples ? w.y : ring_samples;
+    // a member index read from memory never addresses anything as it is
+    auto ring_of = [=](int q) {
+        const int32_t ri = mem[q];
+        return (size_t)(ri >= 0 && ri < n_groups ? ri : 0);
+    };
+    for (uint32_t rest = mask; rest; rest &= rest - 1u) {
+        const int g = __builtin_ctz(rest);  // < n
+        uint32_t D = (uint32_t)__builtin_amdgcn_readlane((int)div, g);
+        D = D < 1u ? 1u : (D > kPromptMaxReduce + 1u ? kPromptMaxReduce + 1u : D);
+        const int rdce = reduce == (int)D ? 1 : (int)D;
+        int16_t *ring = rings + ring_of(g) * ring_samples;
+        for (uint32_t col = threadIdx.x; col < wlen; col += blockDim.x) {
+            uint32_t pos = wstart + col;  // both < ring_samples
+            pos -= pos >= ring_samples ? ring_samples : 0u;
+            int16_t x = ring[pos];
+            bool any = false;
+            for (int q = 0; q < n; q++) {
+                if (q == g) continue;
+                const size_t r = ring_of(q);
+                const LegSpanEntry e = span[r];
+                const uint32_t st = e.start < ring_samples ? e.start : 0u;
+                const uint32_t d = pos >= st ? pos - st : pos + ring_samples - st;
+                if (d >= e.len || d >= (uint32_t)kLegMaxCalls * n_out) continue;
+                const uint32_t j = (d >= n_out) + (d >= 2 * n_out) + (d >= 3 * n_out);  // the call, 0 .. 3, and its sample
+                if ((e.pad >> j) & 1u) continue;  // a silence call; without call lists the mask is 0
+                const uint32_t k = (e.slots >> (2u * j)) & 3u;
+                x = volume_add(x, load_entry_value(src + r * source_stride + (size_t)k * packet_stride, sch[d - j * n_out], rdce));
+                any = true;
+            }
+            if (any) ring[pos] = x;
+        }
+    }
 }
 
 // play, stop and reset: `value` for the listed legs (NULL: every leg); keep_done: the leg's done count stays
@@ -587,6 +674,12 @@ struct wmx_mix {
     // playing launches nothing.
     std::vector<uint64_t> prompt_end;
     uint64_t prompt_now = 0, prompt_last = 0;  // prompt_last: the largest of prompt_end
+    // The duck (leg_prompt.h, REDUCE): whether ring r's play was started with reduce > 0, and the largest prompt_end among those that
+    // were.  Only a tick in front of it can find a ring ducked; every other tick's load of the legs is the plain one.  d_duck: the
+    // mask of ducked members per layout slot, duck_fold_kernel's word to the sweeps; part of the store's block.
+    std::vector<uint8_t> prompt_ducks;
+    uint64_t duck_last = 0;
+    uint32_t *d_duck = nullptr;
 };
 
 // rtp.hip's view of the mixer (wmx_rtp_egress_rings plays the rings itself) and wmx_mix_drain's bookkeeping for it
@@ -1002,6 +1095,9 @@ static int load_minus_legs_any(const char *who, wmx_mix *m, const int16_t *d_src
     const int n_slots = m->conf.slots();
     if (!n_out || !n_slots) return 0;
     const int rdce = (reduce == m->reduce_mode) ? 1 : m->reduce_mode;  // src/wmix.c:1675-1676
+    // The duck (leg_prompt.h, REDUCE): only while a play with reduce > 0 can still be making calls, and only on a mixer whose own
+    // reduce_mode is 1, the mode the play task takes.  Every other tick launches what it launched before there were prompts.
+    const bool duck = m->d_prompt && m->reduce_mode == 1 && m->duck_last > m->prompt_now;
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(with_calls ? leg_cursor_kernel<true> : leg_cursor_kernel<false>, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0,
                        s, (const int32_t *)m->d_conf_tab, (const int32_t *)m->d_conf_members, d_len, srcU8Len, max_packets, d_mute, cursor_state(m), n_out,
@@ -1009,16 +1105,25 @@ static int load_minus_legs_any(const char *who, wmx_mix *m, const int16_t *d_src
     WMX_LAUNCH_CHECK();
     // whole waves per conference, enough for the longest window of legs that write side by side; a longer one is walked in strides
     const uint32_t n_pad = (n_out * (uint32_t)span_calls + 63) / 64 * 64;
+    if (duck) {  // one block per conference: the ducked members' rings, and the slot's mask for the sweeps
+        hipLaunchKernelGGL(duck_fold_kernel, dim3((unsigned)n_slots), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p,
+                           n_out, (const int32_t *)m->d_conf_tab, (const uint2 *)m->d_leg_win, (const LegSpanEntry *)m->d_leg_span,
+                           (const int32_t *)m->d_conf_members, source_stride, packet_stride, reduce, (const LegPrompt *)m->d_prompt,
+                           (const PromptClip *)m->d_clip_tab, (uint32_t)m->clips.size(), (uint32_t)m->arena_cap, m->d_duck, m->n_groups, n_slots);
+        WMX_LAUNCH_CHECK();
+    }
     for (int k = 0; k < kBridgeClasses; k++) {
         const int first = m->conf.class_begin[k], n_class = m->conf.class_begin[k + 1] - first;
         if (!n_class) continue;
         const unsigned grid = stream_grid((size_t)n_pad * n_class, 256);
-        auto kernel = with_calls ? kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, true>; })
-                                 : kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, false>; });
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p, n_out, n_pad,
-                           (const int32_t *)m->d_conf_tab + 2 * (size_t)first, (const uint2 *)m->d_leg_win + first,
+        auto plain = with_calls ? kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, true, false>; })
+                                : kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, false, false>; });
+        auto ducking = with_calls ? kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, true, true>; })
+                                  : kernel_of_class(k, [](auto pmax) { return load_minus_legs_kernel<decltype(pmax)::value, false, true>; });
+        hipLaunchKernelGGL(duck ? ducking : plain, dim3(grid), dim3(256), 0, s, m->d_rings, m->ring_bytes / 2, d_src, (const LoadEntry *)ent->p,
+                           n_out, n_pad, (const int32_t *)m->d_conf_tab + 2 * (size_t)first, (const uint2 *)m->d_leg_win + first,
                            (const LegSpanEntry *)m->d_leg_span, (const int32_t *)m->d_conf_members, source_stride, packet_stride, rdce,
-                           m->n_groups, n_class);
+                           m->n_groups, n_class, duck ? (const uint32_t *)m->d_duck + first : (const uint32_t *)nullptr);
         WMX_LAUNCH_CHECK();
     }
     return m->sched.used(ent, s);
@@ -1095,8 +1200,9 @@ int wmx_mix_prompts(wmx_mix *m, int max_clips, long max_samples) {
         return WMX_EINVAL;
     }
     const size_t n = (size_t)m->n_groups, state_bytes = n * sizeof(LegPrompt), tab_bytes = (size_t)max_clips * sizeof(PromptClip);
+    const size_t duck_bytes = (n / 2 + 1) * sizeof(uint32_t);  // a layout has at most n_groups / 2 conferences that load
     void *p = nullptr;
-    const int rc = zeroed_block(&p, state_bytes + tab_bytes + (size_t)max_samples * sizeof(int16_t), "hipMemset(prompts)");
+    const int rc = zeroed_block(&p, state_bytes + tab_bytes + duck_bytes + (size_t)max_samples * sizeof(int16_t), "hipMemset(prompts)");
     if (rc) return rc;
     const std::vector<LegPrompt> idle(n, leg_prompt_idle(0u));
     const hipError_t e = hipMemcpy(p, idle.data(), state_bytes, hipMemcpyHostToDevice);
@@ -1106,7 +1212,8 @@ int wmx_mix_prompts(wmx_mix *m, int max_clips, long max_samples) {
     }
     m->d_prompt = static_cast<LegPrompt *>(p);
     m->d_clip_tab = reinterpret_cast<PromptClip *>(m->d_prompt + n);
-    m->d_clip_arena = reinterpret_cast<int16_t *>(m->d_clip_tab + max_clips);
+    m->d_duck = reinterpret_cast<uint32_t *>(m->d_clip_tab + max_clips);
+    m->d_clip_arena = reinterpret_cast<int16_t *>(m->d_duck + (n / 2 + 1));
     m->clip_cap = (size_t)max_clips;
     m->arena_cap = (size_t)max_samples;
     m->arena_used = 0;
@@ -1114,6 +1221,8 @@ int wmx_mix_prompts(wmx_mix *m, int max_clips, long max_samples) {
     m->clips.reserve(m->clip_cap);
     m->prompt_end.assign(n, 0);
     m->prompt_now = m->prompt_last = 0;
+    m->prompt_ducks.assign(n, 0);
+    m->duck_last = 0;
     return 0;
 }
 
@@ -1141,9 +1250,9 @@ int wmx_mix_add_clip(wmx_mix *m, const int16_t *host_pcm, long samples, int *cli
 }
 
 // `value` into the listed legs' state entries (NULL = every leg), ordered on `stream`; ticks: the launches of wmx_mix_load_prompts
-// after which such a leg is idle again for certain (0: it is idle now; UINT64_MAX: an endless play)
+// after which such a leg is idle again for certain (0: it is idle now; UINT64_MAX: an endless play); ducks: a play with reduce > 0
 static int prompt_set(wmx_mix *m, const char *who, const int32_t *host_idx, int n, const wmx::LegPrompt &value, bool keep_done, uint64_t ticks,
-                      void *stream) {
+                      bool ducks, void *stream) {
     using namespace wmx;
     if (host_idx && n < 0) return WMX_EINVAL;
     if (idx_check(host_idx, n, m->n_groups, who, "mixer")) return WMX_EINVAL;
@@ -1158,29 +1267,49 @@ static int prompt_set(wmx_mix *m, const char *who, const int32_t *host_idx, int 
                        host_idx ? (const int32_t *)m->d_reset_idx : (const int32_t *)nullptr, count, m->n_groups, value, keep_done ? 1 : 0);
     WMX_LAUNCH_CHECK();
     const uint64_t end = ticks == UINT64_MAX ? UINT64_MAX : m->prompt_now + ticks;
-    for (int i = 0; i < count; i++) m->prompt_end[(size_t)(host_idx ? host_idx[i] : i)] = end;
-    m->prompt_last = 0;
-    for (const uint64_t e : m->prompt_end) m->prompt_last = e > m->prompt_last ? e : m->prompt_last;
+    for (int i = 0; i < count; i++) {
+        const size_t r = (size_t)(host_idx ? host_idx[i] : i);
+        m->prompt_end[r] = end;
+        m->prompt_ducks[r] = ducks ? 1 : 0;
+    }
+    m->prompt_last = m->duck_last = 0;
+    for (size_t r = 0; r < m->prompt_end.size(); r++) {
+        const uint64_t e = m->prompt_end[r];
+        m->prompt_last = e > m->prompt_last ? e : m->prompt_last;
+        if (m->prompt_ducks[r]) m->duck_last = e > m->duck_last ? e : m->duck_last;
+    }
     return 0;
 }
 
-int wmx_mix_play(wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream) {
+// reduce: the reference's argument of every play call, 0 .. 15 -- while the prompt makes calls the others are loaded into the ring
+// divided by reduce + 1 (leg_prompt.h, REDUCE)
+static int play_any(const char *who, wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, int reduce, void *stream) {
     WMX_ON_DEVICE(m);
     using namespace wmx;
     if (!m) return WMX_EINVAL;
     if (!m->d_prompt) {
-        set_error("wmx_mix_play: no store (wmx_mix_prompts)");
+        set_error("%s: no store (wmx_mix_prompts)", who);
         return WMX_ESTATE;
     }
-    if (clip < 0 || (size_t)clip >= m->clips.size() || repeat < 0 || gap_ticks < 0 || (uint32_t)gap_ticks > kPromptMaxGap) {
-        set_error("wmx_mix_play: clip=%d (the store holds %zu) repeat=%d (0 = until stopped) gap_ticks=%d (0 .. %u)", clip, m->clips.size(), repeat,
-                  gap_ticks, kPromptMaxGap);
+    if (clip < 0 || (size_t)clip >= m->clips.size() || repeat < 0 || gap_ticks < 0 || (uint32_t)gap_ticks > kPromptMaxGap || reduce < 0 ||
+        (uint32_t)reduce > kPromptMaxReduce) {
+        set_error("%s: clip=%d (the store holds %zu) repeat=%d (0 = until stopped) gap_ticks=%d (0 .. %u) reduce=%d (0 .. %u)", who, clip,
+                  m->clips.size(), repeat, gap_ticks, kPromptMaxGap, reduce, kPromptMaxReduce);
         return WMX_EINVAL;
     }
     // a pass is one call per started 160 samples; between two passes lie gap_ticks ticks without one (leg_prompt.h)
     const uint64_t per_pass = ((uint64_t)m->clips[(size_t)clip].samples + kLegRow - 1) / kLegRow;
     const uint64_t ticks = repeat == 0 ? UINT64_MAX : (uint64_t)repeat * per_pass + (uint64_t)(repeat - 1) * (uint64_t)gap_ticks;
-    return prompt_set(m, "wmx_mix_play: ring", host_idx, n, leg_prompt_play(clip, (uint32_t)repeat, (uint32_t)gap_ticks, 0u), true, ticks, stream);
+    return prompt_set(m, who, host_idx, n, leg_prompt_play(clip, (uint32_t)repeat, (uint32_t)gap_ticks, 0u, (uint32_t)reduce), true, ticks,
+                      reduce > 0, stream);
+}
+
+int wmx_mix_play(wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, void *stream) {
+    return play_any("wmx_mix_play: ring", m, host_idx, n, clip, repeat, gap_ticks, 0, stream);
+}
+
+int wmx_mix_play_duck(wmx_mix *m, const int32_t *host_idx, int n, int clip, int repeat, int gap_ticks, int reduce, void *stream) {
+    return play_any("wmx_mix_play_duck: ring", m, host_idx, n, clip, repeat, gap_ticks, reduce, stream);
 }
 
 int wmx_mix_stop(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
@@ -1190,7 +1319,7 @@ int wmx_mix_stop(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
         wmx::set_error("wmx_mix_stop: no store (wmx_mix_prompts)");
         return WMX_ESTATE;
     }
-    return prompt_set(m, "wmx_mix_stop: ring", host_idx, n, wmx::leg_prompt_idle(0u), true, 0, stream);
+    return prompt_set(m, "wmx_mix_stop: ring", host_idx, n, wmx::leg_prompt_idle(0u), true, 0, false, stream);
 }
 
 // a new call in a reused slot: idle, done = 0; a mixer without a store has nothing to reset
@@ -1199,7 +1328,7 @@ int wmx_mix_reset_prompts(wmx_mix *m, const int32_t *host_idx, int n, void *stre
     if (!m || (host_idx && n < 0)) return WMX_EINVAL;
     if (wmx::idx_check(host_idx, n, m->n_groups, "wmx_mix_reset_prompts: ring", "mixer")) return WMX_EINVAL;
     if (!m->d_prompt) return 0;
-    return prompt_set(m, "wmx_mix_reset_prompts: ring", host_idx, n, wmx::leg_prompt_idle(0u), false, 0, stream);
+    return prompt_set(m, "wmx_mix_reset_prompts: ring", host_idx, n, wmx::leg_prompt_idle(0u), false, 0, false, stream);
 }
 
 int wmx_mix_export_prompts(const wmx_mix *m, int32_t *host_clip, uint32_t *host_pos, uint32_t *host_left, uint32_t *host_done, void *stream) {
@@ -1217,6 +1346,26 @@ int wmx_mix_export_prompts(const wmx_mix *m, int32_t *host_clip, uint32_t *host_
         if (host_pos) host_pos[r] = st[r].pos;
         if (host_left) host_left[r] = st[r].left;
         if (host_done) host_done[r] = st[r].done;
+    }
+    return 0;
+}
+
+// Per ring the divisor the next load of the legs applies to what the others add there (1: none): leg_prompt_ducks on the states as the
+// work queued on `stream` leaves them.  Without a store, and on a mixer whose reduce_mode is not 1, nothing ducks.
+int wmx_mix_export_duck(const wmx_mix *m, uint8_t *host_divisor, void *stream) {
+    WMX_ON_DEVICE(m);
+    using namespace wmx;
+    if (!m || !host_divisor) return WMX_EINVAL;
+    const size_t n = (size_t)m->n_groups;
+    memset(host_divisor, 1, n);
+    if (!m->d_prompt || m->reduce_mode != 1) return 0;
+    std::vector<LegPrompt> st(n);
+    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+    WMX_HIP(hipMemcpy(st.data(), m->d_prompt, n * sizeof(LegPrompt), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < n; r++) {
+        const int32_t c = st[r].clip;
+        const uint32_t samples = c >= 0 && (size_t)c < m->clips.size() ? m->clips[(size_t)c].samples : 0u;
+        host_divisor[r] = (uint8_t)leg_prompt_ducks(st[r], samples);
     }
     return 0;
 }
