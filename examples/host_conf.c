@@ -2,7 +2,7 @@
  *
  *   host_conf out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]
  *             [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]
- *             [--prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]]]
+ *             [--prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]]] [--record LEG[,CHN,FREQ[,SECONDS]]]... [--record-dir DIR]
  *
  * What the daemon runs as one receive thread and one send thread per leg plus the play thread (src/wmixTask.c:1266-1316, 1058-1143;
  * src/wmix.c:1347-1366), for n_legs legs per 20 ms tick: the host writes the datagrams that arrived into a slot's pinned rows, submits
@@ -44,6 +44,13 @@
  * wmx_conf_play_duck(..., REDUCE): while the clip makes calls the rest of the conference reaches the leg divided by REDUCE + 1 (0 .. 15,
  * the reference's `reduce`), and the JSON line also carries "prompt_reduce": REDUCE and the legs whose next tick would be ducked
  * ("prompt_ducking": wmx_conf_export_duck); four fields run what they ran before.  It combines with every other flag.
+ * --record LEG[,CHN,FREQ[,SECONDS]] (may be repeated) and --record-dir DIR (default "."): what leg LEG HEARS -- its conference without
+ * itself, its prompt on top; a leg that sits in a conference muted and unfed is the recorder of the whole conference -- is written to
+ * DIR/leg<LEG>.wav as PCM of CHN x FREQ (default 1 x 8000; one format per handle, so every --record names the same), for SECONDS
+ * seconds, 50 rows each (default 0: until the run ends).  The handle gets a store of as many taps as there are --record
+ * (wmx_conf_recorders) and every listed leg starts at tick 0 (wmx_conf_record); the rows come back in the slot, beside the datagrams
+ * (wmx_conf_rec, wmx_conf_rec_legs).  The file is the canonical 44-byte header and the rows as they come; the two lengths of the header
+ * are patched in when the tap has written its last row.  The JSON line then carries "record_taps" and the rows written ("record_rows").
  * out.rtp receives n_ticks x n_legs datagrams of 172 bytes; one JSON line goes to stdout. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -76,6 +83,38 @@ static uint64_t lcg_state;
 static uint32_t lcg_next(void) {
     lcg_state = lcg_state * 6364136223846793005ull + 1442695040888963407ull;
     return (uint32_t)(lcg_state >> 33);
+}
+
+/* --record: one PCM WAV per tap.  The canonical header: RIFF <36 + data> WAVE fmt <16> PCM chn freq <bytes per second> <bytes per frame>
+ * <16 bits> data <data>, little endian; written with both lengths 0 and patched when the tap ends */
+#define MAX_RECORDS 64
+struct recording {
+    int leg, seconds;
+    FILE *f;
+    unsigned long rows, bytes;
+};
+static void put_le(uint8_t *p, uint32_t v, int n) {
+    for (int i = 0; i < n; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+static int wav_begin(FILE *f, int chn, int freq) {
+    uint8_t hd[44];
+    memcpy(hd, "RIFF\0\0\0\0WAVEfmt ", 16);
+    put_le(hd + 16, 16, 4), put_le(hd + 20, 1, 2), put_le(hd + 22, (uint32_t)chn, 2), put_le(hd + 24, (uint32_t)freq, 4);
+    put_le(hd + 28, (uint32_t)freq * (uint32_t)chn * 2u, 4), put_le(hd + 32, (uint32_t)chn * 2u, 2), put_le(hd + 34, 16, 2);
+    memcpy(hd + 36, "data\0\0\0\0", 8);
+    return fwrite(hd, 1, sizeof(hd), f) == sizeof(hd) ? 0 : -1;
+}
+static int wav_end(struct recording *r) {
+    uint8_t len[4];
+    int rc = 0;
+    if (!r->f) return 0;
+    put_le(len, 36u + (uint32_t)r->bytes, 4);
+    if (fseek(r->f, 4, SEEK_SET) != 0 || fwrite(len, 1, 4, r->f) != 4) rc = -1;
+    put_le(len, (uint32_t)r->bytes, 4);
+    if (fseek(r->f, 40, SEEK_SET) != 0 || fwrite(len, 1, 4, r->f) != 4) rc = -1;
+    if (fclose(r->f) != 0) rc = -1;
+    r->f = NULL;
+    return rc;
 }
 
 /* --sizes a,b,c: consecutive legs.  The list goes to the library as it stands: what is wrong with it is the library's to say */
@@ -173,10 +212,30 @@ static long arrivals(uint8_t *in, int32_t *recv, int row, uint16_t *seq, int G, 
     return arrived;
 }
 
+/* the slot's recorded rows into their files: row i is valid exactly when rec_legs[i] >= 0, and is that leg's; a tap that has written
+ * its last row (50 x SECONDS of them) is closed there */
+static int collect_rows(wmx_conf *h, int k, struct recording *rec, int n_rec, int rec_row) {
+    const int16_t *rows = wmx_conf_rec(h, k);
+    const int32_t *legs = wmx_conf_rec_legs(h, k);
+    int failed = 0;
+    if (!rows || !legs) return 1;
+    for (int i = 0; i < n_rec; i++) {
+        if (legs[i] < 0) continue;
+        for (int j = 0; j < n_rec; j++) {
+            if (rec[j].leg != legs[i] || !rec[j].f) continue;
+            if (fwrite((const uint8_t *)rows + (size_t)i * (size_t)rec_row, 1, (size_t)rec_row, rec[j].f) != (size_t)rec_row) failed = 1;
+            rec[j].rows++, rec[j].bytes += (unsigned long)rec_row;
+            if (rec[j].seconds > 0 && rec[j].rows == 50ul * (unsigned long)rec[j].seconds && wav_end(&rec[j]) != 0) failed = 1;
+            break;
+        }
+    }
+    return failed;
+}
+
 int main(int argc, char **argv) {
     const char *usage = "usage: %s out.rtp n_legs n_ticks --sizes a,b,c --seed S [--slots K] [--speakers N[,floor[,shift]]] [--platform alsa|hi3516|t31]"
                         " [--sequence G] [--conceal] [--audio-only] [--ulaw-every N] [--dtmf] [--denoise] [--level V] [--gate] [--echo D]"
-                        " [--prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]]]\n";
+                        " [--prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]]] [--record LEG[,CHN,FREQ[,SECONDS]]]... [--record-dir DIR]\n";
     if (argc < 4) {
         fprintf(stderr, usage, argv[0]);
         return 2;
@@ -188,6 +247,9 @@ int main(int argc, char **argv) {
     long correct = -1; /* -1: the library's default = platform/alsa */
     long prompt_len = 0; /* 0: no prompt */
     int prompt_every = 0, prompt_repeat = 1, prompt_gap = 0, prompt_reduce = -1; /* -1: no fifth field, wmx_conf_play */
+    static struct recording rec[MAX_RECORDS];
+    int n_rec = 0, rec_chn = 0, rec_freq = 0;
+    const char *rec_dir = ".";
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--sizes") && i + 1 < argc) {
             sizes = argv[++i];
@@ -221,6 +283,18 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "host_conf: --prompt LEN,EVERY[,REPEAT[,GAP[,REDUCE]]], LEN >= 1, EVERY >= 1\n");
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--record") && i + 1 < argc) {
+            int leg = -1, chn = 1, freq = 8000, seconds = 0;
+            const int fields = sscanf(argv[++i], "%d,%d,%d,%d", &leg, &chn, &freq, &seconds);
+            if (fields < 1 || fields == 2 || leg < 0 || seconds < 0 || n_rec == MAX_RECORDS || (n_rec && (chn != rec_chn || freq != rec_freq))) {
+                fprintf(stderr, "host_conf: --record LEG[,CHN,FREQ[,SECONDS]], at most %d of them and ONE format for all\n", MAX_RECORDS);
+                return 2;
+            }
+            rec_chn = chn, rec_freq = freq; /* what is wrong with the format or the leg is the library's to say */
+            rec[n_rec].leg = leg, rec[n_rec].seconds = seconds;
+            n_rec++;
+        } else if (!strcmp(argv[i], "--record-dir") && i + 1 < argc) {
+            rec_dir = argv[++i];
         } else if (!strcmp(argv[i], "--level") && i + 1 < argc) {
             level = atoi(argv[++i]);
             if (level < 0) {
@@ -304,6 +378,24 @@ int main(int argc, char **argv) {
         WMX_OK(wmx_conf_set_codecs(h, &leg, 1, WMX_CODEC_PCMU, WMX_LAW_U, NULL));
         n_ulaw++;
     }
+    int rec_row = 0; /* the bytes of a recorded row */
+    if (n_rec > 0) {
+        WMX_OK(wmx_conf_recorders(h, n_rec, rec_chn, rec_freq));
+        rec_row = wmx_conf_rec_row_bytes(h);
+        for (int i = 0; i < n_rec; i++) {
+            char path[4096];
+            const int32_t leg = rec[i].leg;
+            int32_t tap = -1;
+            snprintf(path, sizeof(path), "%s/leg%d.wav", rec_dir, rec[i].leg);
+            WMX_OK(wmx_conf_record(h, &leg, 1, 50 * rec[i].seconds, &tap, NULL));
+            if (tap < 0 || tap >= n_rec) return 4;
+            if (!rec[i].f && (!(rec[i].f = fopen(path, "wb")) || wav_begin(rec[i].f, rec_chn, rec_freq) != 0)) {
+                fprintf(stderr, "host_conf: cannot write %s\n", path);
+                return 7;
+            }
+        }
+    }
+    int rec_failed = 0;
     const int row = wmx_conf_in_row_bytes(h);
     uint8_t *out = calloc((size_t)T * G * RTP_BYTES, 1);
     uint16_t *seq = calloc((size_t)G, sizeof(uint16_t));
@@ -318,6 +410,7 @@ int main(int argc, char **argv) {
         if (tick_of[k] >= 0) {                                                                                  \
             WMX_OK(wmx_conf_wait(h, (k)));                                                                      \
             memcpy(out + (size_t)tick_of[k] * G * RTP_BYTES, wmx_conf_out(h, (k)), (size_t)G * RTP_BYTES);      \
+            if (n_rec > 0) rec_failed |= collect_rows(h, (k), rec, n_rec, rec_row);                             \
             tick_of[k] = -1;                                                                                    \
         }                                                                                                       \
     } while (0)
@@ -332,8 +425,13 @@ int main(int argc, char **argv) {
             arrived += arrivals(wmx_conf_in(h, nk), wmx_conf_recv(h, nk), row, seq, G, t + 1);
         }
     }
-    for (int k = 0; k < slots; k++) COLLECT(k);
+    for (int i = 0, first = wmx_conf_next_slot(h); i < slots; i++) COLLECT((first + i) % slots); /* oldest first: the recorded rows are appended */
     const double wall = now_ms() - t0;
+    unsigned long n_rec_rows = 0;
+    for (int i = 0; i < n_rec; i++) { /* the taps that ran until the end */
+        if (wav_end(&rec[i]) != 0) rec_failed = 1;
+        n_rec_rows += rec[i].rows;
+    }
     uint32_t *dropped = calloc((size_t)G, sizeof(uint32_t));
     if (!dropped) return 2;
     WMX_OK(wmx_conf_export_legs(h, NULL, NULL, dropped, NULL, NULL, NULL));
@@ -408,7 +506,7 @@ int main(int argc, char **argv) {
     for (size_t i = 0; i < (size_t)T * G * RTP_BYTES; i++) sum = (sum ^ out[i]) * 1099511628211ull;
     wmx_conf_destroy(h);
     FILE *f = fopen(argv[1], "wb");
-    int rc = (!f || fwrite(out, 1, (size_t)T * G * RTP_BYTES, f) != (size_t)T * G * RTP_BYTES) ? 7 : 0;
+    int rc = (!f || fwrite(out, 1, (size_t)T * G * RTP_BYTES, f) != (size_t)T * G * RTP_BYTES || rec_failed) ? 7 : 0;
     if (f) fclose(f);
     printf("{\"groups\": %d, \"ticks\": %d, \"platform\": \"%s\", \"bridge_rtp_seed\": %lu, \"bridge_sizes\": [", G, T, platform, seed);
     for (int c = 0; c < n_conf; c++) printf("%s%d", c ? ", " : "", (int)(conf_off[c + 1] - conf_off[c]));
@@ -434,6 +532,7 @@ int main(int argc, char **argv) {
     if (echo >= 0) printf("\"echo\": %d, \"echo_running\": %d, ", echo, echo_running);
     if (prompt_len > 0) printf("\"prompt\": %ld, \"prompt_legs\": %d, \"prompt_done\": %lu, ", prompt_len, n_prompt_legs, n_prompt_done);
     if (prompt_len > 0 && prompt_reduce != -1) printf("\"prompt_reduce\": %d, \"prompt_ducking\": %d, ", prompt_reduce, n_prompt_ducking);
+    if (n_rec > 0) printf("\"record_taps\": %d, \"record_format\": [%d, %d], \"record_rows\": %lu, ", n_rec, rec_chn, rec_freq, n_rec_rows);
     printf("\"slots\": %d, \"speakers\": %d, \"datagrams_in\": %ld, \"dropped\": %lu, \"datagrams_fnv1a\": \"%016llx\", \"wall_ms\": %.3f, "
            "\"ms_per_tick\": %.4f, \"rc\": %d}\n",
            slots, max_speakers, arrived, n_dropped, (unsigned long long)sum, wall, wall / T, rc);

@@ -883,6 +883,30 @@ int wmx_rtp_detect_dtmf_legs(wmx_rtp *h, int max_packets, const uint8_t *d_in, l
                              const uint32_t *d_calls, int event_pt, int suppress, void *stream);
 int wmx_rtp_reset_dtmf(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
 int wmx_rtp_export_dtmf(wmx_rtp *h, uint32_t *count, uint8_t *ring, void *stream);
+/* Recording taps: what a ring is about to play, as PCM (wmix_amd/csrc/leg_record.h; the reference's wmix_thread_record_wav,
+ * src/wmixTask.c:410-505, on the daemon that a leg of the bridge is).  The senders hold the store, as they hold the DTMF state.
+ * wmx_rtp_recorders(h, max_taps, chn, freq): the store, once, blocking; max_taps taps of ONE format, chn 1 or 2, freq 1 .. 48 000; a
+ *   second call is WMX_ESTATE.  wmx_rtp_record_row_bytes: the bytes of a row, constant: what wmix_pcm_zoom writes for one package of 320
+ *   bytes of 1 x 8000 (one zoom call per package: the reader that keeps up; the reference's recorder reads 1 .. 5 packages per call
+ *   depending on thread timing); 0 without a store.
+ * wmx_rtp_record(h, host_idx, n, ticks, host_taps_out, stream): the n listed streams start, ordered on `stream`: a stream that has a
+ *   tap is restarted in place, the others take the lowest free taps; `ticks` rows each, 0 = until stopped; host_taps_out (n int32 or
+ *   NULL) takes the taps.  Fewer free taps than needed: WMX_ESTATE and nothing started.
+ * wmx_rtp_record_stop(h, host_idx, n, stream): the listed streams' taps (NULL = every tap) are free from the next tick on, written
+ *   stays.  wmx_rtp_reset_record: the same with written = 0, what a new call in a used slot needs; without a store it does nothing.
+ * wmx_rtp_record_rings(h, mix, d_rows, row_stride, d_legs, stream): one tick of every tap, IN FRONT OF wmx_rtp_egress_rings on the same
+ *   mixer (n_streams rings of 1 x 8000, the play head on a package boundary: anything else is WMX_EINVAL): a running tap reads ring
+ *   `leg` at the play head WITHOUT zeroing it, gathers through wmix_pcm_zoom's schedule 1 x 8000 -> chn x freq and writes the row to
+ *   d_rows + tap * row_stride (int16 elements) and its leg to d_legs[tap]; a free tap writes -1 and no row.  A tap with left == 1
+ *   frees itself behind the row.
+ * wmx_rtp_export_record: leg (int32, -1 free), left and written (uint32) of every TAP, any pointer NULL; blocking. */
+int wmx_rtp_recorders(wmx_rtp *h, int max_taps, int chn, int freq);
+int wmx_rtp_record_row_bytes(const wmx_rtp *h);
+int wmx_rtp_record(wmx_rtp *h, const int32_t *host_idx, int n, int ticks, int32_t *host_taps_out, void *stream);
+int wmx_rtp_record_stop(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
+int wmx_rtp_reset_record(wmx_rtp *h, const int32_t *host_idx, int n, void *stream);
+int wmx_rtp_record_rings(wmx_rtp *h, wmx_mix *m, int16_t *d_rows, long row_stride, int32_t *d_legs, void *stream);
+int wmx_rtp_export_record(wmx_rtp *h, int32_t *leg, uint32_t *left, uint32_t *written, void *stream);
 /* A G.711 codec per stream, as each call negotiated it (wmix_amd/csrc/leg_codec.h holds the rule).  The reference's receive thread
  * accepts payload types 8 and 0 alike and decodes both with G711a2PCM (src/rtp.c:88-95, src/wmixTask.c:1282), and a send thread has one
  * law.  Here the handle keeps, per stream and ON THE DEVICE, in_codec, out_law and a `refused` counter:
@@ -1092,6 +1116,29 @@ wmx_rtp *wmx_pipe_senders(wmx_pipe *h);
  * ducked leg is the ducked mix it was sent.  Only ticks in which a ducking prompt can be making a call run the ducking form of the
  * load.  wmx_conf_export_duck: wmx_mix_export_duck of the handle's legs.  Resampling inside the tick is left out, for the reason
  * given at wmx_mix_prompts.
+ * Recording: what a leg hears, as PCM (the reference's wmix_record on the daemon that the leg is; the rule is stated at
+ * wmx_rtp_recorders and in wmix_amd/csrc/leg_record.h).  wmx_conf_recorders(h, max_taps, chn, freq): once per handle, between submits,
+ * blocking; makes the store (one format per handle: chn 1 or 2, freq whatever wmx_pcm_zoom accepts up to 48 000) and two more `down`
+ * buffers per slot, max_taps rows of wmx_conf_rec_row_bytes(h) bytes back to back and max_taps int32; a second call is WMX_ESTATE.  The
+ * row length is constant -- the zoom is stateless and every call has 320 bytes in: ONE wmix_pcm_zoom call per package, the reader that
+ * keeps up, where the reference's recorder reads 1 .. 5 packages per call depending on thread timing -- and is the number the zoom
+ * writes, not wmix_len_of_out's bound.  wmx_conf_record(h, host_idx, n, ticks, taps_out, stream): the listed legs each take the lowest
+ * free tap and record from the next tick on, `ticks` rows (0 = until stopped; the reference counts seconds by bytes of the source format
+ * and breaks behind the write that completes second `time`: 50 x time packages, one package for time == 0); a leg that has a tap is
+ * restarted in place; too few free taps is WMX_ESTATE with nothing started.  wmx_conf_record_stop (NULL = every tap) and
+ * wmx_conf_reset_legs end the recording of the legs they name, as the reference's wmix_reset ends its record threads: the tap is free
+ * from the next tick on.  In a tick in which a tap is running wmx_rtp_record_rings stands BEHIND wmx_mix_load_prompts and IN FRONT OF
+ * wmx_rtp_egress_rings, and the slot's two buffers are downloaded with the datagrams: wmx_conf_rec(h, slot) and wmx_conf_rec_legs(h,
+ * slot) are valid after wmx_conf_wait(h, slot), like wmx_conf_out; row i is valid in that slot exactly when rec_legs[i] >= 0, and is leg
+ * rec_legs[i]'s.  A TAPPED LEG'S ROW is the 160 samples its datagram of the tick encodes, converted: everybody of its conference but the
+ * leg itself, its prompt on top, ducked if it is ducked -- NOT the leg's own voice.  A RECORDER OF A CONFERENCE is one more leg of it: a
+ * member, muted (wmx_conf_mute), never fed, its datagram ignored; its row holds everybody.  Nothing else about the tick changes: ring,
+ * datagram, every counter and every stage's state are what they are without the tap.  wmx_conf_export_record: leg, left and written of
+ * every TAP (wmx_rtp_export_record).  wmx_conf_step_resident_rec(h, d_in, d_recv, d_out, d_rec, rec_stride, d_rec_legs, stream): the
+ * resident step with taps, d_rec max_taps rows rec_stride int16 apart and d_rec_legs max_taps int32 on the device; plain
+ * wmx_conf_step_resident while a tap is running is WMX_ESTATE before anything is launched, so a recording never silently loses a
+ * tick.  A handle without a store (wmx_conf_rec is NULL), and a tick in which no tap is running, run exactly the launches and copies
+ * they ran before.
  * wmx_conf_mix / wmx_conf_senders: the handle's mixer and senders, for wmx_mix_export / wmx_rtp_export.
  * Use ONE compute stream per handle: the PCM rows, d_len and the masks between the launches are per handle, not per slot.
  * WMX_EINVAL: slots outside 1 .. 16, max_packets outside 1 .. 4, a law that is not WMX_LAW_A / WMX_LAW_U (create); a submit or resident
@@ -1130,6 +1177,13 @@ int wmx_conf_play_duck(wmx_conf *h, const int32_t *host_idx, int n, int clip, in
 int wmx_conf_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
 int wmx_conf_export_prompts(wmx_conf *h, int32_t *clip, uint32_t *pos, uint32_t *left, uint32_t *done, void *stream);
 int wmx_conf_export_duck(wmx_conf *h, uint8_t *divisor, void *stream);
+int wmx_conf_recorders(wmx_conf *h, int max_taps, int chn, int freq);
+int wmx_conf_record(wmx_conf *h, const int32_t *host_idx, int n, int ticks, int32_t *taps_out, void *stream);
+int wmx_conf_record_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
+int wmx_conf_export_record(wmx_conf *h, int32_t *leg, uint32_t *left, uint32_t *written, void *stream);
+int wmx_conf_rec_row_bytes(const wmx_conf *h);
+const int16_t *wmx_conf_rec(wmx_conf *h, int slot);
+const int32_t *wmx_conf_rec_legs(wmx_conf *h, int slot);
 int wmx_conf_set_play_correct(wmx_conf *h, uint32_t bytes);
 int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *stream);
 int wmx_conf_slots(const wmx_conf *h);
@@ -1142,6 +1196,8 @@ int wmx_conf_submit(wmx_conf *h, int *slot, void *stream);
 int wmx_conf_wait(wmx_conf *h, int slot);
 int wmx_conf_poll(wmx_conf *h, int slot);
 int wmx_conf_step_resident(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream);
+int wmx_conf_step_resident_rec(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, int16_t *d_rec, long rec_stride,
+                               int32_t *d_rec_legs, void *stream);
 int wmx_conf_export_legs(wmx_conf *h, uint32_t *head, uint32_t *tick, uint32_t *dropped, uint32_t *env, uint8_t *speaking, void *stream);
 wmx_mix *wmx_conf_mix(wmx_conf *h);
 wmx_rtp *wmx_conf_senders(wmx_conf *h);

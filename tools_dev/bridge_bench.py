@@ -92,7 +92,15 @@ WMIX_AMD_LIB (the parent's) it measures the first of the three alone.
 --prompts N --duck R adds the duck (wmx_conf_play_duck): a fourth side on which the N legs play the clip with reduce = R, so that every
 conference of 8 has all its rings ducked in every tick, and a fifth on which one leg of every conference does, the other seven
 playing with reduce 0.  A library without wmx_conf_play_duck (the parent's) runs the first three alone.
-    python tools_dev/bridge_bench.py --prompts 4096 --duck 1 --out file.json    (profiles/bridge/bridge_duck_bench.json is made of such runs)"""
+    python tools_dev/bridge_bench.py --prompts 4096 --duck 1 --out file.json    (profiles/bridge/bridge_duck_bench.json is made of such runs)
+--record N [--record-format CHN,FREQ]: nothing of the above; the tick of wmx_conf on --record-legs legs (4 096) in conferences of 8 without
+a recording store, with a store of N taps of which none is running, and with the N taps running, one per conference (on the first leg
+of every conference, then the second, ...): the resident step, device time (events), and the handle with 3 slots, wall clock per tick over
+blocks of ticks -- the recorded rows are downloaded with the datagrams there, so the added D2H bytes are in it.  The two sides with a store
+are ONE handle, its taps stopped and started between the blocks.  A library without
+wmx_conf_recorders (the parent's, given in WMIX_AMD_LIB) runs the first side alone, and so does --record-alone with this one: the two
+are then the same program on two libraries.
+    python tools_dev/bridge_bench.py --record 512 --record-format 2,16000 --out file.json    (profiles/bridge/bridge_record_bench.json is made of such runs)"""
 import argparse
 import json
 import os
@@ -522,6 +530,100 @@ def prompts_tick(legs, reps, playing, duck=0):
     out.update({"ms_per_tick_" + name: stats(v) for name, v in ms.items()})
     # per playing leg and tick: 320 bytes of clip read, 320 of ring read and 320 written, the 32-byte state entry read and written, 8 of table
     out["hbm_bytes_per_playing_leg_and_tick"] = 320 * 3 + 32 * 2 + 8
+    return out
+
+
+def record_tick(legs, reps, taps, chn, freq, alone=False):
+    """--record N: see the head of this file.  Two handles per clock: one without a store, and one with a store that is measured in both
+    states, its taps stopped and its taps running, block by block in turn -- so that what is compared is one handle with itself, not two
+    handles whose streams the runtime happened to place on other hardware queues.  The order of the sides rotates from block to block."""
+    import time
+    from wmix_amd._lib import check, lib
+    from wmix_amd.conf import ConfBridge
+    L = lib()
+    layout = [list(range(c, min(c + 8, legs))) for c in range(0, legs, 8)]
+    rng = np.random.default_rng(13)
+    CYC = 3
+    pk = rng.integers(0, 256, (CYC, legs, 3, 176), dtype=np.uint8)
+    pk[..., :12] = 0
+    pk[..., 0], pk[..., 1] = 0x80, 0x88
+    recv = np.zeros((CYC, legs, 3), np.int32)
+    recv[:, :, 0] = 172
+    r_in, r_recv = torch.from_numpy(pk).cuda(), torch.from_numpy(recv).cuda()
+    r_out = torch.zeros((legs, 172), dtype=torch.uint8, device="cuda")
+    has = getattr(L, "wmx_conf_recorders", None) is not None and not alone
+    tapped = [(k % len(layout)) * 8 + k // len(layout) for k in range(taps)]  # one per conference, then a second one, ...
+    assert max(tapped, default=0) < legs and len(set(tapped)) == taps
+    made = {}
+    for slots in (1, 3):
+        for store in ((False, True) if has else (False,)):
+            cb = ConfBridge(legs, slots, 3)
+            cb.set_conferences(layout)
+            cb.set_play_correct(0)
+            if store:
+                cb.recorders(taps, chn, freq)
+            for k in range(slots if slots == 3 else 0):
+                cb.rows_in[k][:] = pk[k]
+                cb.recv[k][:] = recv[k]
+            made[(slots, store)] = cb
+    names = ("no_store", "store_idle", "recording") if has else ("no_store",)
+    row = made[(1, True)].rec_row_bytes if has else 0
+    d_rows = torch.zeros((max(taps, 1), max(row // 2, 1)), dtype=torch.int16, device="cuda")
+    d_legs = torch.full((max(taps, 1),), -1, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    tick = {1: 0, 3: 0}
+
+    def enter(slots, name):  # the state of the side, outside every timed region
+        cb = made[(slots, name != "no_store")]
+        if name == "store_idle":
+            cb.record_stop()
+        if name == "recording":
+            cb.record(tapped, ticks=0)
+        cb.wait(-1)
+        torch.cuda.synchronize()
+        return cb
+
+    def step(cb, name):
+        i = tick[1] % CYC
+        tick[1] += 1
+        if name == "recording":
+            check(L.wmx_conf_step_resident_rec(cb._h, r_in[i].data_ptr(), r_recv[i].data_ptr(), r_out.data_ptr(), d_rows.data_ptr(), d_rows.stride(0),
+                                               d_legs.data_ptr(), stream), "wmx_conf_step_resident_rec")
+        else:  # the C call, as on the recording side: the tick is a handful of launches, and a wrapper's checks would be in its time
+            check(L.wmx_conf_step_resident(cb._h, r_in[i].data_ptr(), r_recv[i].data_ptr(), r_out.data_ptr(), stream), "wmx_conf_step_resident")
+
+    per_block = max(reps // BLOCKS, 8)
+    ms, wall = {name: [] for name in names}, {name: [] for name in names}
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for blk in range(2 * BLOCKS + 1):  # the first block warms up
+        for name in names[blk % len(names):] + names[:blk % len(names)]:
+            cb = enter(1, name)
+            for _ in range(per_block):
+                a.record()
+                step(cb, name)
+                b.record()
+                b.synchronize()
+                if blk:
+                    ms[name].append(a.elapsed_time(b))
+            if name == "recording":  # the rows are the rings' heads as the egress encoded them: every tapped leg's row is there
+                assert d_legs.cpu().tolist() == tapped and bool(d_rows.any())
+            cb = enter(3, name)
+            t0 = time.perf_counter()
+            for _ in range(per_block):
+                cb.submit()
+            cb.wait(-1)
+            if blk:
+                wall[name].append((time.perf_counter() - t0) * 1e3 / per_block)
+    written = int(made[(3, True)].export_record()["written"].sum()) if has else 0
+    for cb in made.values():
+        cb.close()
+    out = {"legs": legs, "conferences": len(layout), "taps": taps if has else 0, "format": [chn, freq], "row_bytes": row,
+           "library_records": bool(has), "rows_written_by_the_handle_since_its_last_start": written, "ticks_per_block": per_block,
+           "d2h_bytes_per_tick_datagrams": legs * 172, "d2h_bytes_per_tick_added_while_recording": taps * (row + 4) if has else 0}
+    out.update({"resident_ms_per_tick_" + name: stats(v) for name, v in ms.items()})
+    for name, v in wall.items():
+        out["handle_wall_ms_per_tick_" + name] = {"median_ms": round(float(np.median(v)), 5), "blocks_ms": [round(x, 5) for x in v],
+                                                   "spread": round((max(v) - min(v)) / float(np.median(v)), 4)}
     return out
 
 
@@ -969,6 +1071,10 @@ if __name__ == "__main__":
     ap.add_argument("--duck", type=int, default=0, help="with --prompts N: two more sides, the N legs playing with this reduce (1 .. 15), and one leg of every conference of 8")
     ap.add_argument("--prompts", type=int, default=-1, help="the resident tick on --prompt-legs legs without a prompt store, with one nobody plays from, and with this many legs playing an endless clip; nothing else")
     ap.add_argument("--prompt-legs", type=int, default=4096)
+    ap.add_argument("--record", type=int, default=-1, help="the tick on --record-legs legs without a recording store, with an idle one of this many taps, and with the taps running, one per conference of 8; nothing else")
+    ap.add_argument("--record-format", default="1,8000", help="with --record: CHN,FREQ of the store")
+    ap.add_argument("--record-legs", type=int, default=4096)
+    ap.add_argument("--record-alone", action="store_true", help="with --record: the side without a store alone, as a library without recording runs it")
     ap.add_argument("--steady", action="store_true", help="with --pipe: every leg sends one packet per tick, on all sides alike")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -993,6 +1099,13 @@ if __name__ == "__main__":
         res = {"tool": "bridge_bench --prompts", "device": torch.cuda.get_device_name(0), "reps": args.reps,
                "runs": "the builder's own, one process, the sides alternating",
                "prompts": prompts_tick(args.prompt_legs, args.reps, args.prompts, args.duck), "load": [], "tick": None}
+        args.sizes = args.tick = ""
+        args.ragged, args.speakers, args.pipe = False, 0, False
+    if args.record >= 0:
+        chn, freq = (int(v) for v in args.record_format.split(","))
+        res = {"tool": "bridge_bench --record", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+               "runs": "the builder's own, one process, the sides alternating",
+               "record": record_tick(args.record_legs, args.reps, args.record, chn, freq, args.record_alone), "load": [], "tick": None}
         args.sizes = args.tick = ""
         args.ragged, args.speakers, args.pipe = False, 0, False
     if args.pipe:

@@ -25,6 +25,7 @@ class ConfBridge:
         self.rows_in = [host_rows(L.wmx_conf_in(self._h, k), (n_legs, max_packets, self.in_row), np.uint8) for k in range(slots)]
         self.recv = [host_rows(L.wmx_conf_recv(self._h, k), (n_legs, max_packets), np.int32) for k in range(slots)]
         self.rows_out = [host_rows(L.wmx_conf_out(self._h, k), (n_legs, OUT_ROW), np.uint8) for k in range(slots)]
+        self.max_taps, self.rec_row_bytes, self.rec_rows, self.rec_legs = 0, 0, None, None  # until recorders()
 
     @staticmethod
     def _stream():
@@ -245,6 +246,62 @@ class ConfBridge:
         check(lib().wmx_conf_export_duck(self._h, r.ctypes.data, self._stream()), "wmx_conf_export_duck")
         return r
 
+    def recorders(self, max_taps, channels=1, freq=8000):
+        """make the recording store, once (wmx_conf_recorders): max_taps taps of one format, channels (1, 2) x freq (up to 48 000),
+        between submits, blocking; every slot gets its rows.  From then on a tick in which a tap is running has one more launch in front
+        of the egress and downloads the rows with the datagrams"""
+        check(lib().wmx_conf_recorders(self._h, int(max_taps), int(channels), int(freq)), "wmx_conf_recorders")
+        L = lib()
+        self.max_taps, self.rec_row_bytes = int(max_taps), L.wmx_conf_rec_row_bytes(self._h)
+        self.rec_rows = [host_rows(L.wmx_conf_rec(self._h, k), (self.max_taps, self.rec_row_bytes // 2), np.int16) for k in range(self.slots)]
+        self.rec_legs = [host_rows(L.wmx_conf_rec_legs(self._h, k), (self.max_taps,), np.int32) for k in range(self.slots)]
+
+    def record(self, legs, seconds=0, ticks=None):
+        """the listed legs start recording with the next tick (wmx_conf_record) -> the taps they took, int32.  What is recorded is what the
+        leg HEARS: its conference without itself, its prompt on top -- a recorder of a whole conference is one more leg of it, muted and
+        never fed.  seconds: 50 x seconds rows, 0 = until stopped (the reference's `time` == 0 is one package: ticks=1); ticks, where
+        given, is the count of rows itself.  A leg that has a tap is restarted in place; too few free taps raises and starts nothing"""
+        idx = np.ascontiguousarray(legs, dtype=np.int32)
+        taps = np.full(idx.size, -1, np.int32)
+        n = int(ticks) if ticks is not None else 50 * int(seconds)
+        check(lib().wmx_conf_record(self._h, idx.ctypes.data, idx.size, n, taps.ctypes.data, self._stream()), "wmx_conf_record")
+        return taps
+
+    def record_stop(self, legs=None):
+        """the listed legs' taps (None = every tap) are free from the next tick on (wmx_conf_record_stop)"""
+        idx = None if legs is None else np.ascontiguousarray(legs, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(lib().wmx_conf_record_stop(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size, self._stream()),
+              "wmx_conf_record_stop")
+
+    def recorded(self, slot):
+        """-> (legs int32 [max_taps], rows int16 [max_taps, row_samples]) of a slot, views of its pinned rows, valid after wait(slot):
+        row i is valid exactly when legs[i] >= 0, and is that leg's"""
+        return self.rec_legs[slot], self.rec_rows[slot]
+
+    def export_record(self):
+        """dict(leg: int32 [max_taps], -1 when free; left, written: uint32 [max_taps] -- the rows still to record (0 while running: until
+        stopped) and the rows written since the tap was started) as the work queued on the current stream leaves them"""
+        r = {"leg": np.zeros(self.max_taps, np.int32), "left": np.zeros(self.max_taps, np.uint32), "written": np.zeros(self.max_taps, np.uint32)}
+        check(lib().wmx_conf_export_record(self._h, r["leg"].ctypes.data, r["left"].ctypes.data, r["written"].ctypes.data, self._stream()),
+              "wmx_conf_export_record")
+        return r
+
+    def step_resident_rec(self, d_in, d_recv, d_out=None):
+        """step_resident with the taps: -> (datagrams uint8 [n_legs, 172], legs int32 [max_taps], rows int16 [max_taps, row_samples]),
+        all on the device"""
+        if d_out is None:
+            d_out = torch.zeros((self.n_legs, OUT_ROW), dtype=torch.uint8, device=d_in.device)
+        assert d_in.is_cuda and d_in.dtype == torch.uint8 and d_in.is_contiguous() and tuple(d_in.shape) == (self.n_legs, self.max_packets, self.in_row)
+        assert d_recv.is_cuda and d_recv.dtype == torch.int32 and d_recv.is_contiguous() and tuple(d_recv.shape) == (self.n_legs, self.max_packets)
+        assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and tuple(d_out.shape) == (self.n_legs, OUT_ROW)
+        rows = torch.zeros((self.max_taps, self.rec_row_bytes // 2), dtype=torch.int16, device=d_in.device)
+        legs = torch.full((self.max_taps,), -1, dtype=torch.int32, device=d_in.device)
+        check(lib().wmx_conf_step_resident_rec(self._h, d_in.data_ptr(), d_recv.data_ptr(), d_out.data_ptr(), rows.data_ptr(), rows.stride(0),
+                                               legs.data_ptr(), self._stream()), "wmx_conf_step_resident_rec")
+        return d_out, legs, rows
+
     def set_play_correct(self, n_bytes):
         check(lib().wmx_conf_set_play_correct(self._h, n_bytes), "wmx_conf_set_play_correct")
 
@@ -311,7 +368,7 @@ class ConfBridge:
         """destroys the handle and its pinned rows: rows_in, recv and rows_out become None, and views taken from them earlier are invalid
         from here on"""
         if self._h:
-            self.rows_in = self.recv = self.rows_out = None  # views of memory that goes away
+            self.rows_in = self.recv = self.rows_out = self.rec_rows = self.rec_legs = None  # views of memory that goes away
             lib().wmx_conf_destroy(self._h)
             self._h = None
 

@@ -22,7 +22,9 @@
 // with the rows alone, and a second time behind the egress with the far row alone: what wmx_rtp_decode_sent_legs makes of the
 // datagram the tick has just sent to the leg.  With a prompt store (wmx_conf_prompts) wmx_mix_load_prompts stands behind the load and in
 // front of the egress: every leg that plays a clip loads its next 20 ms into its own ring (wmix_amd/csrc/leg_prompt.h), behind what the
-// other legs of its conference loaded there.
+// other legs of its conference loaded there.  With a recording store (wmx_conf_recorders) wmx_rtp_record_rings stands behind that and
+// directly in front of the egress, in the ticks in which a tap is running: what the egress is about to encode for a tapped leg, as PCM
+// in the store's format (wmix_amd/csrc/leg_record.h), into two more `down` buffers of the slot.
 //
 // PER SLOT (slot_ring.h, made once, `slots` of them): pinned host rows -- n_legs x max_packets datagram rows of 176 bytes (172 on a
 // 4-byte boundary), what recvfrom returned per row, n_legs x 172 bytes out -- their device twins and the events.  PER HANDLE: the mixer
@@ -71,18 +73,22 @@ struct wmx_conf {
     wmx_aecm *aecm;       // a canceller per leg (wmx_aecm_create_legs), made when echo control is first switched on
     int16_t *d_echo_far;  // [n_legs][160] what the tick sent to each leg, decoded; made with it
     bool prompts_made;  // wmx_mix_load_prompts behind the load: the mixer holds the store (wmx_conf_prompts)
+    bool rec_made;      // wmx_rtp_record_rings in front of the egress: the senders hold the store (wmx_conf_recorders)
+    int rec_taps;       // the store's taps and the bytes of a row: the slots' kRec is rec_taps rows, kRecLegs rec_taps int32
+    size_t rec_row_bytes;
     uint8_t *d_mute;   // [n_legs] the host's mute
     uint8_t *d_mask;   // [n_legs] what selection leaves for the load
     uint8_t *h_mute;   // pinned: the upload's source
     bool mute_on;
     int max_speakers, decay_shift;  // max_speakers 0: selection off
     uint32_t floor;
-    enum { kIn, kRecv, kOut };  // the slots' buffers (slot_ring.h)
+    enum { kIn, kRecv, kOut, kRec, kRecLegs };  // the slots' buffers (slot_ring.h); the last two from wmx_conf_recorders on
     wmx::SlotRing ring;
 };
 
-// the launches of one tick on rows that are on the device
-static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, void *stream) {
+// the launches of one tick on rows that are on the device; d_rec NULL: the taps are not launched (no store, or none is running)
+static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, int16_t *d_rec, long rec_stride,
+                         int32_t *d_rec_legs, void *stream) {
     const int K = h->max_packets;
     const uint32_t *calls = h->seq_on ? h->d_calls : nullptr;  // the stages' order: the sequencer's list, or the slots'
     int rc = wmx_rtp_ingest_legs_codecs(h->snd, K, d_in, (long)K * kInRow, kInRow, d_recv, h->d_pcm, (long)K * kLegRow, kLegRow, h->d_len,
@@ -133,6 +139,10 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
     if (rc != 0) return rc;
     if (h->prompts_made) {  // behind the legs' calls, so that a ring receives its prompt's call last; in front of the drain
         rc = wmx_mix_load_prompts(h->mix, stream);
+        if (rc != 0) return rc;
+    }
+    if (d_rec) {  // behind everything that loads a ring, so that the row is what the egress encodes; it zeroes nothing
+        rc = wmx_rtp_record_rings(h->snd, h->mix, d_rec, rec_stride, d_rec_legs, stream);
         if (rc != 0) return rc;
     }
     uint32_t bytes = 0;
@@ -602,7 +612,65 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
         rc = conf_reset_stage(h, h->aecm, +[](wmx_aecm *a, const int32_t *idx, int k, void *st) { return wmx_aecm_reset_streams(a, idx, k, -1, st); },
                               host_idx, n, stream);
     if (rc == 0 && h->prompts_made) rc = wmx_mix_reset_prompts(h->mix, host_idx, n, stream);  // nor the old call's announcement
+    if (rc == 0 && h->rec_made) rc = wmx_rtp_reset_record(h->snd, host_idx, n, stream);  // nor its recording: wmix_reset ends the record threads
     return rc;
+}
+
+// ---- recording: what a leg hears as PCM (wmix_amd/csrc/leg_record.h; the senders own the store, as they own the DTMF state)
+// max_taps taps of one format, chn (1, 2) x freq (1 .. 48 000): once, between submits, blocking; a second call is WMX_ESTATE.  Every slot
+// gets two more down buffers: max_taps rows of wmx_conf_rec_row_bytes() and max_taps int32.  From then on a tick in which a tap is
+// running calls wmx_rtp_record_rings in front of the egress and downloads the two; every other tick launches and copies what it did.
+int wmx_conf_recorders(wmx_conf *h, int max_taps, int chn, int freq) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    int rc = h->ring.wait(-1);  // the ring takes buffers only while it is idle
+    if (rc == 0) rc = wmx_rtp_recorders(h->snd, max_taps, chn, freq);
+    if (rc != 0) return rc;
+    // rows back to back: those of the two formats the kernel moves 16 bytes at a time (320 and 640 bytes) stay on 16-byte boundaries
+    const size_t row_bytes = (size_t)wmx_rtp_record_row_bytes(h->snd);
+    hipError_t e = h->ring.add({(size_t)max_taps * row_bytes, false, -1});
+    if (e == hipSuccess) e = h->ring.add({(size_t)max_taps * sizeof(int32_t), false, -1});
+    for (int k = 0; e == hipSuccess && k < h->ring.n(); k++) {  // until a tap has run in a slot, no row of it is valid
+        memset(h->ring.host(k, wmx_conf::kRecLegs), 0xFF, (size_t)max_taps * sizeof(int32_t));
+        e = hipMemset(h->ring.dev(k, wmx_conf::kRecLegs), 0xFF, (size_t)max_taps * sizeof(int32_t));
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return wmx::hip_fail(e, "wmx_conf_recorders: the slots' rows", __FILE__, __LINE__);
+    h->rec_taps = max_taps;
+    h->rec_row_bytes = row_bytes;
+    h->rec_made = true;
+    return 0;
+}
+
+// the listed legs each take the lowest free tap (a leg that has one is restarted in place) and record `ticks` rows from the next tick
+// on, 0 = until stopped; taps_out (n int32, or NULL) takes the taps.  Too few free taps: WMX_ESTATE, nothing started.
+int wmx_conf_record(wmx_conf *h, const int32_t *host_idx, int n, int ticks, int32_t *taps_out, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_record(h->snd, host_idx, n, ticks, taps_out, stream);
+}
+
+// the listed legs' taps (NULL = every tap) are free from the next tick on; their written counts stay
+int wmx_conf_record_stop(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_record_stop(h->snd, host_idx, n, stream);
+}
+
+// leg (int32, -1: free), left and written (uint32) of every TAP as the work queued on `stream` leaves them; any pointer may be NULL;
+// blocking.  Without a store: WMX_ESTATE.
+int wmx_conf_export_record(wmx_conf *h, int32_t *leg, uint32_t *left, uint32_t *written, void *stream) {
+    if (!h) return WMX_EINVAL;
+    return wmx_rtp_export_record(h->snd, leg, left, written, stream);
+}
+
+// the bytes of a row, constant: what wmix_pcm_zoom writes for one package of 320 bytes; 0 without a store
+int wmx_conf_rec_row_bytes(const wmx_conf *h) { return h ? (int)h->rec_row_bytes : WMX_EINVAL; }
+// valid after wmx_conf_wait(h, slot), like wmx_conf_out: row i is valid exactly when rec_legs[i] >= 0, and is that leg's.  NULL without
+// a store.
+const int16_t *wmx_conf_rec(wmx_conf *h, int slot) {
+    return h && h->rec_made ? static_cast<int16_t *>(h->ring.host(slot, wmx_conf::kRec)) : nullptr;
+}
+const int32_t *wmx_conf_rec_legs(wmx_conf *h, int slot) {
+    return h && h->rec_made ? static_cast<int32_t *>(h->ring.host(slot, wmx_conf::kRecLegs)) : nullptr;
 }
 
 // ---- the slots' pinned rows
@@ -627,7 +695,35 @@ int wmx_conf_step_resident(wmx_conf *h, const uint8_t *d_in, const int32_t *d_re
         wmx::set_error("wmx_conf_step_resident: no layout (wmx_conf_set_conferences)");
         return WMX_EINVAL;
     }
-    return conf_launches(h, d_in, d_recv, d_out, stream);
+    if (h->rec_made && wmx::rtp_record_running(h->snd)) {  // before anything is launched: a recording never silently loses a tick
+        wmx::set_error("wmx_conf_step_resident: a recording tap is running and this call has no rows for it (wmx_conf_step_resident_rec)");
+        return WMX_ESTATE;
+    }
+    return conf_launches(h, d_in, d_recv, d_out, nullptr, 0, nullptr, stream);
+}
+
+// The resident step with taps: d_rec max_taps rows rec_stride int16 apart (>= wmx_conf_rec_row_bytes() / 2), d_rec_legs max_taps int32,
+// both on the device; every tap writes its entry of d_rec_legs, a running one its row.  Without a store: WMX_ESTATE.
+int wmx_conf_step_resident_rec(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv, uint8_t *d_out, int16_t *d_rec, long rec_stride,
+                               int32_t *d_rec_legs, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !d_in || !d_recv || !d_out || !d_rec || !d_rec_legs) {
+        wmx::set_error("wmx_conf_step_resident_rec: bad argument");
+        return WMX_EINVAL;
+    }
+    if (!h->rec_made) {
+        wmx::set_error("wmx_conf_step_resident_rec: no store (wmx_conf_recorders)");
+        return WMX_ESTATE;
+    }
+    if (wmx_mix_conferences(h->mix) < 1) {
+        wmx::set_error("wmx_conf_step_resident_rec: no layout (wmx_conf_set_conferences)");
+        return WMX_EINVAL;
+    }
+    if (rec_stride < (long)(wmx_rtp_record_row_bytes(h->snd) / 2)) {
+        wmx::set_error("wmx_conf_step_resident_rec: rec_stride %ld < the %d samples of a row", rec_stride, wmx_rtp_record_row_bytes(h->snd) / 2);
+        return WMX_EINVAL;
+    }
+    return conf_launches(h, d_in, d_recv, d_out, d_rec, rec_stride, d_rec_legs, stream);
 }
 
 // Queue the next slot: its in / recv rows must hold this tick's arrivals.  Blocks only if that slot is still in flight from `slots`
@@ -646,10 +742,16 @@ int wmx_conf_submit(wmx_conf *h, int *slot, void *stream) {
     int rc = ring.retire(k);  // only completes what an earlier submit promised
     if (rc == 0) rc = ring.upload(k, main);
     if (rc != 0) return rc;
+    // The taps: launched, and their two buffers downloaded, only in a tick in which one is running -- the host knows from its copy of
+    // leg_record.h's state.  In every other tick the slot's legs say -1 from here: a host write of max_taps words, no copy.
+    const bool rec = h->rec_made && wmx::rtp_record_running(h->snd);
+    if (h->rec_made && !rec) memset(ring.host(k, wmx_conf::kRecLegs), 0xFF, (size_t)h->rec_taps * sizeof(int32_t));
     rc = conf_launches(h, static_cast<uint8_t *>(ring.dev(k, wmx_conf::kIn)), static_cast<int32_t *>(ring.dev(k, wmx_conf::kRecv)),
-                       static_cast<uint8_t *>(ring.dev(k, wmx_conf::kOut)), stream);
+                       static_cast<uint8_t *>(ring.dev(k, wmx_conf::kOut)), rec ? static_cast<int16_t *>(ring.dev(k, wmx_conf::kRec)) : nullptr,
+                       (long)(h->rec_row_bytes / sizeof(int16_t)), rec ? static_cast<int32_t *>(ring.dev(k, wmx_conf::kRecLegs)) : nullptr, stream);
     if (rc == 0) rc = ring.done(k, main);
-    if (rc == 0) rc = ring.download(k);  // a few KB: at once, behind the tick's own last launch
+    // a few KB: at once, behind the tick's own last launch
+    if (rc == 0) rc = ring.download(k, nullptr, rec ? ~0u : ~(1u << wmx_conf::kRec | 1u << wmx_conf::kRecLegs));
     if (rc != 0) {
         char why[512];
         snprintf(why, sizeof(why), "%s", wmx_last_error());

@@ -17,6 +17,7 @@
 #include "leg_plc.h"
 #include "leg_codec.h"
 #include "leg_dtmf.h"
+#include "leg_record.h"
 
 namespace wmx {
 namespace {
@@ -141,6 +142,13 @@ struct wmx_rtp {
     wmx::LegState dtmf;   // the DTMF rule (leg_dtmf.h): ring (uint64), count, ts and flags (uint32 each)
     // no stream has left in_codec REFERENCE / out_law = law, so the launches are those of a handle that knows no codecs
     bool codecs_default;
+    // the recording taps (leg_record.h), made once by wmx_rtp_recorders: the taps' state on the device with the store's gather list
+    // behind it (one block), and the host's copy of the state, stepped beside every launch: the rule reads nothing the device computes
+    wmx::LegRecord *d_rec = nullptr;
+    const int32_t *d_rec_idx = nullptr;
+    std::vector<wmx::LegRecord> rec;
+    int rec_chn = 0, rec_freq = 0, rec_mode = 0;
+    uint32_t rec_row = 0;  // the samples of a row: what the zoom writes for one package
 };
 
 namespace wmx {
@@ -377,6 +385,55 @@ __global__ __launch_bounds__(256) void rtp_egress_rings_kernel(int16_t *__restri
             seq[ring] = (sq + 1) & 0xFFFFu;  // rtpHeader.seq++ after the send (uint16 wrap)
         }
     }
+}
+
+// The recording taps (wmx_rtp_record_rings, leg_record.h): in front of the kernel above, what it is about to play, as PCM in the
+// store's format.  One wave = one tap, no loop over taps: the state entry is read before anything is stored, so it is a wave-uniform
+// (scalar) load, the rule is evaluated once on the scalar side, and a free tap's wave leaves behind its one store of -1.  The ring is
+// read and NOT zeroed: the egress still has to play it.  The host has checked that the head is a multiple of 160 samples and the ring a
+// multiple of 160 long, so the row's 160 samples lie in one piece from a 16-byte boundary on; a leg index read from memory never
+// addresses anything as it is: it is held against n_rings, and a gather index against the package.
+// MODE kRecIdentity (1 x 8000): 20 lanes move 16 bytes each.  kRecDouble (2 x 8000, the zoom's 1 -> 2 duplication): 40 lanes load four
+// samples and store them twice over, 16 bytes.  kRecGather: every other format, and rows that are not on 16-byte boundaries, sample by
+// sample through the store's list (zoom_gather_list).
+enum { kRecGather, kRecIdentity, kRecDouble };
+template <int MODE>
+__global__ __launch_bounds__(256) void rtp_record_rings_kernel(const int16_t *__restrict__ rings, uint32_t ring_samples, uint32_t head_sample,
+                                                                LegRecord *__restrict__ state, const int32_t *__restrict__ idx, uint32_t row_samples,
+                                                                int16_t *__restrict__ rows, long row_stride, int32_t *__restrict__ legs, int n_taps,
+                                                                int n_rings) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int tap = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    if (tap >= n_taps) return;
+    LegRecord r = state[tap];
+    const int32_t leg = leg_record_tick(r);
+    const bool known = leg >= 0 && leg < n_rings;  // a leg the mixer does not have writes no row, and its tap runs out all the same
+    if (lane == 0u) legs[tap] = known ? leg : -1;
+    if (leg < 0) return;
+    if (known) {
+        const int16_t *src = rings + (size_t)leg * ring_samples + head_sample;  // head_sample + 160 <= ring_samples
+        int16_t *dst = rows + (size_t)tap * row_stride;
+        if (MODE == kRecIdentity) {
+            if (lane < (uint32_t)kRecordRowIn / 8u) reinterpret_cast<uint4 *>(dst)[lane] = reinterpret_cast<const uint4 *>(src)[lane];
+        } else if (MODE == kRecDouble) {
+            if (lane < (uint32_t)kRecordRowIn / 4u) {
+                const uint2 x = reinterpret_cast<const uint2 *>(src)[lane];
+                const uint32_t a = x.x & 0xFFFFu, b = x.x >> 16, c = x.y & 0xFFFFu, d = x.y >> 16;
+                reinterpret_cast<uint4 *>(dst)[lane] = make_uint4(a | (a << 16), b | (b << 16), c | (c << 16), d | (d << 16));
+            }
+        } else {
+            for (uint32_t i = lane; i < row_samples; i += 64u) {
+                const uint32_t from = (uint32_t)idx[i];
+                dst[i] = src[from < (uint32_t)kRecordRowIn ? from : (uint32_t)kRecordRowIn - 1u];
+            }
+        }
+    }
+    if (lane == 0u) state[tap] = r;
+}
+
+// start, stop and reset: one tap's entry
+__global__ void rtp_record_set_kernel(LegRecord *__restrict__ state, int tap, LegRecord value) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) state[tap] = value;
 }
 
 // What a leg was sent, as its phone's speaker plays it (wmx_rtp_decode_sent_legs): the 160 codes of the leg's outgoing datagram decoded
@@ -675,6 +732,9 @@ inline bool aligned_to(const void *p, long stride_bytes, int a) { return (reinte
 
 using namespace wmx;
 
+// conf.hip's question in front of a tick: has it a tap that writes a row?  (the host's copy of leg_record.h's state: no download)
+bool wmx::rtp_record_running(const wmx_rtp *h) { return h->d_rec && leg_record_any(h->rec.data(), (int)h->rec.size()); }
+
 extern "C" {
 
 int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
@@ -714,6 +774,7 @@ int wmx_rtp_destroy(wmx_rtp *h) {
     WMX_ON_DEVICE(h);
     if (!h) return 0;
     for (LegState *st : {&h->send, &h->seq, &h->codec, &h->plc, &h->dtmf}) st->destroy();
+    if (h->d_rec) (void)hipFree(h->d_rec);  // the gather list lies behind it
     delete h;
     return 0;
 }
@@ -1027,6 +1088,185 @@ int wmx_rtp_export_dtmf(wmx_rtp *h, uint32_t *count, uint8_t *ring, void *stream
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
     return h->dtmf.export_to({ring, count}, as_stream(stream));
+}
+
+// ---- the recording taps (include/wmix_amd.h, leg_record.h)
+// the store, once and blocking: max_taps taps of one format, chn x freq
+int wmx_rtp_recorders(wmx_rtp *h, int max_taps, int chn, int freq) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (h->d_rec) {
+        set_error("wmx_rtp_recorders: the senders have their store already (%zu taps of %d x %d)", h->rec.size(), h->rec_chn, h->rec_freq);
+        return WMX_ESTATE;
+    }
+    if (max_taps < 1 || max_taps > (1 << 20) || chn < 1 || chn > 2 || freq < 1 || freq > kRecordMaxFreq) {
+        set_error("wmx_rtp_recorders: max_taps=%d (1 .. 2^20) chn=%d (1, 2) freq=%d (1 .. %d)", max_taps, chn, freq, kRecordMaxFreq);
+        return WMX_EINVAL;
+    }
+    zoom_gather_list(1, kRtpG711Payload * 50, 2u * kRecordRowIn, chn, freq, h->idx);
+    const size_t row = h->idx.size(), state_bytes = (size_t)max_taps * sizeof(LegRecord);
+    if (row == 0) {
+        set_error("wmx_rtp_recorders: wmix_pcm_zoom writes nothing for a package of 1 x 8000 -> %d x %d", chn, freq);
+        return WMX_EINVAL;
+    }
+    bool identity = row == (size_t)kRecordRowIn, twice = row == 2u * kRecordRowIn;
+    for (size_t i = 0; i < row; i++) {
+        if (h->idx[i] < 0 || h->idx[i] >= kRecordRowIn) {
+            set_error("wmx_rtp_recorders: the zoom's list reads sample %d of a package of %d", (int)h->idx[i], kRecordRowIn);
+            return WMX_EINVAL;
+        }
+        identity = identity && h->idx[i] == (int32_t)i;
+        twice = twice && h->idx[i] == (int32_t)(i / 2);
+    }
+    void *p = nullptr;
+    WMX_HIP(hipMalloc(&p, state_bytes + row * sizeof(int32_t)));
+    const std::vector<LegRecord> fresh((size_t)max_taps, leg_record_free(0u));
+    hipError_t e = hipMemcpy(p, fresh.data(), state_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(static_cast<uint8_t *>(p) + state_bytes, h->idx.data(), row * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "hipMemcpy(recording taps)", __FILE__, __LINE__);
+    }
+    h->d_rec = static_cast<LegRecord *>(p);
+    h->d_rec_idx = reinterpret_cast<const int32_t *>(h->d_rec + max_taps);
+    h->rec = fresh;
+    h->rec_chn = chn, h->rec_freq = freq;
+    h->rec_row = (uint32_t)row;
+    h->rec_mode = identity ? kRecIdentity : (twice ? kRecDouble : kRecGather);
+    return 0;
+}
+
+int wmx_rtp_record_row_bytes(const wmx_rtp *h) { return h ? (int)(h->rec_row * sizeof(int16_t)) : WMX_EINVAL; }
+
+// tap `k` takes `value` on the host and, ordered on `s`, on the device
+static int record_set(wmx_rtp *h, size_t k, const LegRecord &value, hipStream_t s) {
+    hipLaunchKernelGGL(rtp_record_set_kernel, dim3(1), dim3(64), 0, s, h->d_rec, (int)k, value);
+    WMX_LAUNCH_CHECK();
+    h->rec[k] = value;
+    return 0;
+}
+
+static int record_store(const wmx_rtp *h, const char *who) {
+    if (h->d_rec) return 0;
+    set_error("%s: no store (wmx_rtp_recorders)", who);
+    return WMX_ESTATE;
+}
+
+// the n listed legs start: a leg that has a tap in place, the others at the lowest free taps; ticks rows each, 0 = until stopped.
+// host_taps_out (n int32, or NULL) takes the taps.  Too few free taps: WMX_ESTATE and nothing started.
+int wmx_rtp_record(wmx_rtp *h, const int32_t *host_idx, int n, int ticks, int32_t *host_taps_out, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !host_idx || n < 0 || ticks < 0) {
+        set_error("wmx_rtp_record: a list of n >= 0 legs and ticks >= 0 (0: until stopped)");
+        return WMX_EINVAL;
+    }
+    const int rcs = record_store(h, "wmx_rtp_record");
+    if (rcs) return rcs;
+    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_record: leg", "handle")) return WMX_EINVAL;
+    std::vector<int32_t> taps((size_t)n);
+    if (!leg_record_assign(h->rec.data(), (int)h->rec.size(), host_idx, n, taps.data())) {
+        set_error("wmx_rtp_record: %d legs and fewer free taps among the store's %zu; nothing started", n, h->rec.size());
+        return WMX_ESTATE;
+    }
+    for (int i = 0; i < n; i++) {
+        const int rc = record_set(h, (size_t)taps[(size_t)i], leg_record_start(host_idx[i], (uint32_t)ticks), as_stream(stream));
+        if (rc) return rc;
+        if (host_taps_out) host_taps_out[i] = taps[(size_t)i];
+    }
+    return 0;
+}
+
+// the taps of the n listed legs (NULL = every tap) are free from the next tick on: keep_written: a stop; otherwise the leg's reset
+static int record_end(wmx_rtp *h, const char *who, const int32_t *host_idx, int n, bool keep_written, void *stream) {
+    if ((host_idx && n < 0) || idx_check(host_idx, n, h->n_streams, who, "handle")) return WMX_EINVAL;
+    for (size_t k = 0; k < h->rec.size(); k++) {
+        const LegRecord was = h->rec[k];
+        bool listed = !host_idx;
+        for (int i = 0; host_idx && was.leg >= 0 && i < n && !listed; i++) listed = was.leg == host_idx[i];
+        if (!listed) continue;
+        const LegRecord now = keep_written ? leg_record_stop(was) : leg_record_reset();
+        if (now.leg == was.leg && now.left == was.left && now.written == was.written) continue;  // a free tap, as it is already
+        const int rc = record_set(h, k, now, as_stream(stream));
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int wmx_rtp_record_stop(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const int rcs = record_store(h, "wmx_rtp_record_stop");
+    return rcs ? rcs : record_end(h, "wmx_rtp_record_stop: leg", host_idx, n, true, stream);
+}
+
+// what a new call in a used slot needs: the leg's recording ends, as wmix_reset ends the daemon's record threads.  No store: nothing.
+int wmx_rtp_reset_record(wmx_rtp *h, const int32_t *host_idx, int n, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    if (!h->d_rec) return (host_idx && n < 0) || idx_check(host_idx, n, h->n_streams, "wmx_rtp_reset_record: leg", "handle") ? WMX_EINVAL : 0;
+    return record_end(h, "wmx_rtp_reset_record: leg", host_idx, n, false, stream);
+}
+
+// leg (int32, -1: free), left and written (uint32) of every tap as the work queued on `stream` leaves them; any pointer may be NULL;
+// blocking
+int wmx_rtp_export_record(wmx_rtp *h, int32_t *leg, uint32_t *left, uint32_t *written, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h) return WMX_EINVAL;
+    const int rcs = record_store(h, "wmx_rtp_export_record");
+    if (rcs) return rcs;
+    std::vector<LegRecord> st(h->rec.size());
+    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
+    WMX_HIP(hipMemcpy(st.data(), h->d_rec, st.size() * sizeof(LegRecord), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < st.size(); k++) {
+        if (leg) leg[k] = st[k].leg;
+        if (left) left[k] = st[k].left;
+        if (written) written[k] = st[k].written;
+    }
+    return 0;
+}
+
+// One tick of every tap, in front of wmx_rtp_egress_rings on the same mixer: a running tap's row -- ring `leg` from the play head on,
+// through the store's zoom -- into d_rows + tap * row_stride (int16 elements), its leg into d_legs[tap]; a free tap: -1 and no row.
+int wmx_rtp_record_rings(wmx_rtp *h, wmx_mix *m, int16_t *d_rows, long row_stride, int32_t *d_legs, void *stream) {
+    WMX_ON_DEVICE(h);
+    if (!h || !m || !d_rows || !d_legs) {
+        set_error("wmx_rtp_record_rings: bad arguments");
+        return WMX_EINVAL;
+    }
+    const int rcs = record_store(h, "wmx_rtp_record_rings");
+    if (rcs) return rcs;
+    const MixPlayView v = mix_play_view(m);
+    if (v.chn != 1 || v.freq != kRtpG711Payload * 50 || v.n_groups != h->n_streams || v.device != h->device) {
+        set_error("wmx_rtp_record_rings: a mixer of %d rings of %d x %d on device %d; the senders are %d on device %d and tap rings of 1 x 8000",
+                  v.n_groups, v.chn, v.freq, v.device, h->n_streams, h->device);
+        return WMX_EINVAL;
+    }
+    const uint32_t ring_samples = v.ring_bytes / 2, head_sample = (v.head_off / 2) % ring_samples;
+    // the conference handle's mixer: it is drained a package at a time, so a row never straddles the ring's end
+    if (v.head_off % (2u * kRecordRowIn) != 0 || ring_samples % (uint32_t)kRecordRowIn != 0 || reinterpret_cast<uintptr_t>(v.d_rings) % 16 != 0) {
+        set_error("wmx_rtp_record_rings: the play head (byte %u of %u) is not on a package of %d bytes: this mixer has been drained otherwise",
+                  v.head_off, v.ring_bytes, 2 * kRecordRowIn);
+        return WMX_EINVAL;
+    }
+    const size_t n_taps = h->rec.size();
+    if (row_stride < (long)h->rec_row && n_taps > 1) {
+        set_error("wmx_rtp_record_rings: rows that overlap (row_stride %ld < %u samples)", row_stride, h->rec_row);
+        return WMX_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(d_rows) % sizeof(int16_t) != 0 || reinterpret_cast<uintptr_t>(d_legs) % sizeof(int32_t) != 0) {
+        set_error("wmx_rtp_record_rings: d_rows on a 2-byte and d_legs on a 4-byte boundary");
+        return WMX_EINVAL;
+    }
+    const int mode = aligned_to(d_rows, row_stride * 2, 16) ? h->rec_mode : kRecGather;
+    auto kernel = mode == kRecIdentity ? rtp_record_rings_kernel<kRecIdentity>
+                                       : (mode == kRecDouble ? rtp_record_rings_kernel<kRecDouble> : rtp_record_rings_kernel<kRecGather>);
+    const unsigned waves = 4, grid = ((unsigned)n_taps + waves - 1) / waves;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), 0, as_stream(stream), (const int16_t *)v.d_rings, ring_samples, head_sample, h->d_rec,
+                       h->d_rec_idx, h->rec_row, d_rows, row_stride, d_legs, (int)n_taps, h->n_streams);
+    WMX_LAUNCH_CHECK();
+    for (LegRecord &r : h->rec) (void)leg_record_tick(r);  // behind the check: a launch that failed has moved no tap
+    return 0;
 }
 
 // ---- the codec rule per stream (include/wmix_amd.h, leg_codec.h): fresh is refused 0, in_codec REFERENCE, out_law the law of create

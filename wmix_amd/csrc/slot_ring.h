@@ -32,7 +32,7 @@ constexpr int kMaxSlots = 16;  // what wmx_pipe_create*, wmx_rt_create* and wmx_
 inline bool slots_ok(int slots) { return slots >= 1 && slots <= kMaxSlots; }
 
 struct SlotRing {
-    static constexpr int kMaxBufs = 3;
+    static constexpr int kMaxBufs = 5;
     struct Buf {
         size_t bytes;
         bool up;    // host -> device in upload(); otherwise device -> host in download()
@@ -74,6 +74,31 @@ struct SlotRing {
                 if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
         }
         return e;
+    }
+    // One more buffer in every slot of a ring that is IDLE (no slot in flight, nothing pending: the owner has waited for every slot),
+    // for an owner that learns of a buffer behind make() -- the conference handle's recording rows.  Its index is buf.size() - 1
+    // afterwards; on a failure the ring is what it was.
+    hipError_t add(Buf b) {
+        if ((int)buf.size() >= kMaxBufs || b.alias >= 0) return hipErrorInvalidValue;
+        const size_t at = buf.size();
+        hipError_t e = hipSuccess;
+        for (Slot &s : slot) {
+            s.h[at] = s.d[at] = nullptr;
+            if (e == hipSuccess) e = hipHostMalloc(&s.h[at], b.bytes, hipHostMallocDefault);
+            if (e == hipSuccess) memset(s.h[at], 0, b.bytes);
+            if (e == hipSuccess) e = hipMalloc(&s.d[at], b.bytes);
+            if (e == hipSuccess) e = hipMemset(s.d[at], 0, b.bytes);
+        }
+        if (e != hipSuccess) {
+            for (Slot &s : slot) {
+                if (s.h[at]) (void)hipHostFree(s.h[at]);
+                if (s.d[at]) (void)hipFree(s.d[at]);
+                s.h[at] = s.d[at] = nullptr;
+            }
+            return e;
+        }
+        buf.push_back(b);
+        return hipSuccess;
     }
     // safe on a ring that make() left half made; the caller has waited for the device
     void destroy() {
@@ -128,13 +153,13 @@ struct SlotRing {
     }
     // The down buffers of slot k, behind `gate` (an event of the compute stream, or NULL) AND the slot's own ev_done: a gate is recorded on
     // whatever stream the gating step was given, and nothing but the caller's habit of using one stream orders that behind slot k's
-    // last launch (the second wait costs nothing when the stream is the same).
-    int download(int k, hipEvent_t gate = nullptr) {
+    // last launch (the second wait costs nothing when the stream is the same).  `which`: the down buffers whose bit is set, as in upload().
+    int download(int k, hipEvent_t gate = nullptr, unsigned which = ~0u) {
         Slot &s = slot[(size_t)k];
         if (gate && gate != s.ev_done) WMX_HIP(hipStreamWaitEvent(s_out, gate, 0));
         WMX_HIP(hipStreamWaitEvent(s_out, s.ev_done, 0));
         for (size_t b = 0; b < buf.size(); b++)
-            if (!buf[b].up) WMX_HIP(hipMemcpyAsync(s.h[b], s.d[b], buf[b].bytes, hipMemcpyDeviceToHost, s_out));
+            if (!buf[b].up && (which >> b & 1u)) WMX_HIP(hipMemcpyAsync(s.h[b], s.d[b], buf[b].bytes, hipMemcpyDeviceToHost, s_out));
         WMX_HIP(hipEventRecord(s.ev_out, s_out));
         return 0;
     }

@@ -262,6 +262,9 @@ struct MixPlayView {
 MixPlayView mix_play_view(const wmx_mix *m);
 void mix_played(wmx_mix *m, uint32_t bytes);
 
+// conf.hip -> rtp.hip: whether the coming wmx_rtp_record_rings has a tap that writes a row (leg_record.h; the host's copy of the state)
+bool rtp_record_running(const wmx_rtp *h);
+
 #ifdef __HIPCC__
 // Hand-off of LDS data between lanes of ONE wavefront.  A wave's LDS instructions are executed in issue order by the
 // hardware, so a ds_read issued after a ds_write of another lane of the same wave already sees the data.  What is needed

@@ -161,6 +161,58 @@ class RtpSenders:
               "wmx_rtp_export_dtmf")
         return r
 
+    def recorders(self, max_taps, channels=1, freq=8000):
+        """the recording store, once (wmx_rtp_recorders): max_taps taps of one format -> the int16 samples of a row"""
+        check(lib().wmx_rtp_recorders(self._h, int(max_taps), int(channels), int(freq)), "wmx_rtp_recorders")
+        self.max_taps = int(max_taps)
+        return lib().wmx_rtp_record_row_bytes(self._h) // 2
+
+    def record(self, streams, ticks=0):
+        """the listed streams start recording, `ticks` rows each, 0 = until stopped (wmx_rtp_record) -> the taps they took, int32"""
+        import numpy as np
+        idx = np.ascontiguousarray(streams, dtype=np.int32)
+        taps = np.full(idx.size, -1, np.int32)
+        check(lib().wmx_rtp_record(self._h, idx.ctypes.data, idx.size, int(ticks), taps.ctypes.data, torch.cuda.current_stream().cuda_stream),
+              "wmx_rtp_record")
+        return taps
+
+    def _record_end(self, name, streams):
+        import numpy as np
+        idx = None if streams is None else np.ascontiguousarray(streams, dtype=np.int32)
+        if idx is not None and idx.size == 0:
+            return
+        check(getattr(lib(), name)(self._h, None if idx is None else idx.ctypes.data, 0 if idx is None else idx.size,
+                                   torch.cuda.current_stream().cuda_stream), name)
+
+    def record_stop(self, streams=None):
+        """the listed streams' taps (None = every tap) are free from the next tick on: wmx_rtp_record_stop"""
+        self._record_end("wmx_rtp_record_stop", streams)
+
+    def reset_record(self, streams=None):
+        """the same with written = 0, what a new call needs: wmx_rtp_reset_record"""
+        self._record_end("wmx_rtp_reset_record", streams)
+
+    def record_rings(self, mix, rows=None, legs=None):
+        """one tick of every tap in front of egress_rings(mix) (wmx_rtp_record_rings) -> (legs int32 CUDA [max_taps], rows int16 CUDA
+        [max_taps, row_samples]): a running tap's row and leg, -1 and no row for a free one; the rings are not zeroed"""
+        n = lib().wmx_rtp_record_row_bytes(self._h) // 2
+        dev = torch.device("cuda", torch.cuda.current_device())
+        rows = torch.zeros((self.max_taps, n), dtype=torch.int16, device=dev) if rows is None else rows
+        legs = torch.full((self.max_taps,), -1, dtype=torch.int32, device=dev) if legs is None else legs
+        assert rows.is_cuda and rows.dtype == torch.int16 and rows.stride(1) == 1 and tuple(rows.shape) == (self.max_taps, n)
+        assert legs.is_cuda and legs.dtype == torch.int32 and legs.is_contiguous() and tuple(legs.shape) == (self.max_taps,)
+        check(lib().wmx_rtp_record_rings(self._h, mix._h, rows.data_ptr(), rows.stride(0), legs.data_ptr(), torch.cuda.current_stream().cuda_stream),
+              "wmx_rtp_record_rings")
+        return legs, rows
+
+    def export_record(self):
+        """dict(leg: int32, left, written: uint32; [max_taps] each) as the work queued on the current stream leaves them"""
+        import numpy as np
+        r = {"leg": np.zeros(self.max_taps, np.int32), "left": np.zeros(self.max_taps, np.uint32), "written": np.zeros(self.max_taps, np.uint32)}
+        check(lib().wmx_rtp_export_record(self._h, r["leg"].ctypes.data, r["left"].ctypes.data, r["written"].ctypes.data,
+                                          torch.cuda.current_stream().cuda_stream), "wmx_rtp_export_record")
+        return r
+
     def set_codecs(self, streams, in_codec, out_law):
         """in_codec ("reference", "pcma", "pcmu", "by_pt") and out_law ("a", "u") of the listed streams (None = all): wmx_rtp_set_codecs"""
         import numpy as np
