@@ -36,6 +36,7 @@
 #include <vector>
 #include "pipe_internal.h"
 #include "leg_calls.h"
+#include "leg_state.h"
 
 namespace {
 using wmx::kLegRow;
@@ -68,7 +69,7 @@ struct wmx_conf {
     int level_value;  // the compression gain wmx_conf_level last gave every leg
     bool gate_on;      // wmx_vad_process_legs behind the leveller
     wmx_vad *vad;      // a VAD stream per leg (1 x 8000, 20 ms), made when the gate is first switched on
-    uint32_t *d_gate;  // [2][n_legs] rows judged voice / not voice per leg, made with it
+    wmx::LegState gate;  // rows judged voice / not voice per leg ([2][n_legs]: a table of two columns, leg_state.h), made with it
     bool echo_on;         // wmx_aecm_process_legs behind the denoiser (rows) and behind the egress (the far row)
     wmx_aecm *aecm;       // a canceller per leg (wmx_aecm_create_legs), made when echo control is first switched on
     int16_t *d_echo_far;  // [n_legs][160] what the tick sent to each leg, decoded; made with it
@@ -116,7 +117,7 @@ static int conf_launches(wmx_conf *h, const uint8_t *d_in, const int32_t *d_recv
         if (rc != 0) return rc;
     }
     if (h->gate_on) {  // behind the leveller: the decision is made on the levelled row; selection, concealment and the load see the gated rows
-        rc = wmx_vad_process_legs(h->vad, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, calls, h->d_gate, stream);
+        rc = wmx_vad_process_legs(h->vad, h->d_pcm, (long)K * kLegRow, kLegRow, K, h->d_len, calls, h->gate.at<uint32_t>(wmx::kGateVoiced), stream);
         if (rc != 0) return rc;
     }
     const uint8_t *host_mute = h->mute_on ? h->d_mute : nullptr, *load_mute = host_mute;
@@ -169,20 +170,6 @@ static int conf_reset_stage(wmx_conf *h, Stage *stage, int (*reset_streams)(Stag
     return reset_streams(stage, all.data(), h->n_legs, stream);
 }
 
-// the listed legs' (NULL = all) two counters of the gate back to zero, ordered on `stream`
-static int conf_reset_gate_counts(wmx_conf *h, const int32_t *host_idx, int n, void *stream) {
-    hipStream_t s = wmx::as_stream(stream);
-    if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(h->d_gate, 0, 2 * (size_t)h->n_legs * sizeof(uint32_t), s));
-        return 0;
-    }
-    for (int i = 0; i < n; i++) {
-        WMX_HIP(hipMemsetAsync(h->d_gate + host_idx[i], 0, sizeof(uint32_t), s));
-        WMX_HIP(hipMemsetAsync(h->d_gate + h->n_legs + host_idx[i], 0, sizeof(uint32_t), s));
-    }
-    return 0;
-}
-
 extern "C" {
 
 int wmx_conf_destroy(wmx_conf *h) {
@@ -199,7 +186,7 @@ int wmx_conf_destroy(wmx_conf *h) {
     if (h->nsx) wmx_nsx_destroy(h->nsx);
     if (h->agc) wmx_agc_destroy(h->agc);
     if (h->vad) wmx_vad_destroy(h->vad);
-    if (h->d_gate) (void)hipFree(h->d_gate);
+    h->gate.destroy();
     if (h->aecm) wmx_aecm_destroy(h->aecm);
     if (h->d_echo_far) (void)hipFree(h->d_echo_far);
     if (h->mix) wmx_mix_destroy(h->mix);
@@ -225,6 +212,7 @@ int wmx_conf_create(wmx_conf **out, int n_legs, int slots, int max_packets, int 
     }
     h->n_legs = n_legs;
     h->max_packets = max_packets;
+    h->gate = wmx::LegState("hipMemset(gate counters)", "handle", n_legs, wmx::kLegGateColumns);
     const size_t rows = (size_t)n_legs * (size_t)max_packets;
     int rc = wmx_mix_create(&h->mix, n_legs, 1, 8000);
     if (rc == 0) rc = wmx_rtp_create(&h->snd, n_legs, law);
@@ -413,16 +401,9 @@ int wmx_conf_gate(wmx_conf *h, int on) {
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
     if (on && !h->vad) {
-        void *p = nullptr;
-        int rc = wmx::zeroed_block(&p, 2 * (size_t)h->n_legs * sizeof(uint32_t), "hipMemset(gate counters)");
+        int rc = h->gate.make();
+        if (rc == 0) rc = wmx_vad_create(&h->vad, h->n_legs, 1, 8000, 20);
         if (rc != 0) return rc;
-        wmx_vad *vad = nullptr;
-        if ((rc = wmx_vad_create(&vad, h->n_legs, 1, 8000, 20)) != 0) {
-            (void)hipFree(p);
-            return rc;
-        }
-        h->vad = vad;
-        h->d_gate = static_cast<uint32_t *>(p);
     }
     h->gate_on = on != 0;
     return 0;
@@ -437,23 +418,14 @@ int wmx_conf_export_gate(wmx_conf *h, uint8_t *reduce, uint32_t *voiced, uint32_
     WMX_ON_DEVICE(h);
     if (!h) return WMX_EINVAL;
     const size_t n = (size_t)h->n_legs;
-    if (!h->vad) {
-        if (reduce) memset(reduce, 4, n);
-        if (voiced) memset(voiced, 0, n * sizeof(uint32_t));
-        if (unvoiced) memset(unvoiced, 0, n * sizeof(uint32_t));
-        return 0;
-    }
-    hipStream_t s = wmx::as_stream(stream);
-    if (reduce) {
+    if (reduce && !h->vad) memset(reduce, 4, n);
+    if (reduce && h->vad) {
         std::vector<int16_t> r(n);
         const int rc = wmx_vad_export_reduce(h->vad, r.data(), stream);
         if (rc != 0) return rc;
         for (size_t g = 0; g < n; g++) reduce[g] = (uint8_t)r[g];
     }
-    if (voiced) WMX_HIP(hipMemcpyAsync(voiced, h->d_gate, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (unvoiced) WMX_HIP(hipMemcpyAsync(unvoiced, h->d_gate + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    WMX_HIP(hipStreamSynchronize(s));
-    return 0;
+    return h->gate.export_to({voiced, unvoiced}, wmx::as_stream(stream));
 }
 
 // on != 0: every leg's rows of the tick go through the leg's own fixed-point echo canceller (wmx_aecm_process_legs: aec_init(1, 8000, 20)
@@ -607,7 +579,7 @@ int wmx_conf_reset_legs(wmx_conf *h, const int32_t *host_idx, int n, void *strea
     if (rc == 0 && h->nsx) rc = conf_reset_stage(h, h->nsx, wmx_nsx_reset_streams, host_idx, n, stream);  // nor the old call's noise estimate
     if (rc == 0 && h->agc) rc = conf_reset_stage(h, h->agc, wmx_agc_reset_streams, host_idx, n, stream);  // nor its level estimate
     if (rc == 0 && h->vad) rc = conf_reset_stage(h, h->vad, wmx_vad_reset_streams, host_idx, n, stream);  // nor its noise model and hangover
-    if (rc == 0 && h->vad) rc = conf_reset_gate_counts(h, host_idx, n, stream);
+    if (rc == 0 && h->vad) rc = h->gate.reset("wmx_conf_reset_legs: leg", host_idx, n, wmx::as_stream(stream));
     if (rc == 0 && h->aecm)  // nor the old call's echo path, far end and start-up; the reported delay stays
         rc = conf_reset_stage(h, h->aecm, +[](wmx_aecm *a, const int32_t *idx, int k, void *st) { return wmx_aecm_reset_streams(a, idx, k, -1, st); },
                               host_idx, n, stream);

@@ -24,6 +24,7 @@
 #include "speakers.h"
 #include "leg_cursor.h"
 #include "leg_prompt.h"
+#include "leg_state.h"
 
 namespace wmx {
 namespace {
@@ -484,18 +485,6 @@ __global__ __launch_bounds__(256) void load_minus_legs_kernel(int16_t *__restric
     }
 }
 
-// fresh cursors (leg_cursor_fresh) and no drops for the listed rings, or for every ring
-__global__ __launch_bounds__(256) void leg_reset_kernel(uint32_t *__restrict__ head, uint32_t *__restrict__ tick, uint32_t *__restrict__ dropped,
-                                                        const int32_t *__restrict__ idx, int n, int n_groups) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int r = idx ? idx[i] : i;
-        if (r < 0 || r >= n_groups) continue;
-        head[r] = UINT32_MAX;
-        tick[r] = 0;
-        dropped[r] = 0;
-    }
-}
-
 // ---- a prompt per leg (leg_prompt.h)
 // One wave = one leg, no loop over legs: the state entry is read before anything is stored, so it and the clip's table entry are
 // wave-uniform (scalar) loads, and an idle leg's wave exits after the one load.  The rule's inputs are all wave-uniform, so the wave
@@ -651,17 +640,16 @@ struct wmx_mix {
     int32_t *d_conf_members = nullptr, *d_conf_tab = nullptr;
     uint32_t *d_conf_lead = nullptr;
     size_t conf_cap_members = 0, conf_cap_slots = 0;
-    // talker selection (speakers.h): one envelope and one speaking flag per ring, made by the first call that needs them (one block:
-    // d_speaking lies behind the envelopes); the index list of wmx_mix_reset_speakers
-    uint32_t *d_env = nullptr;
-    uint8_t *d_speaking = nullptr;
-    int32_t *d_reset_idx = nullptr;
-    size_t reset_cap = 0;
-    // a cursor per leg (leg_cursor.h): head, tick and the drop count of every ring, the span table and the windows the cursor kernel
-    // writes for the load kernels (one block, made by the first call that needs it)
-    uint32_t *d_leg_head = nullptr, *d_leg_tick = nullptr, *d_leg_dropped = nullptr;
+    // talker selection (speakers.h): one envelope and one speaking flag per ring, and a cursor per leg (leg_cursor.h): head, tick and the
+    // drop count of every ring -- two tables (leg_state.h), each made by the first call that needs it
+    wmx::LegState talkers, cursors;
+    // what leg_cursor_kernel rewrites every tick for the load kernels, scratch and not state: the span table and the windows (one
+    // zeroed block, made with the cursors)
     wmx::LegSpanEntry *d_leg_span = nullptr;
     uint2 *d_leg_win = nullptr;
+    // the index list of prompt_set
+    int32_t *d_prompt_idx = nullptr;
+    size_t prompt_idx_cap = 0;
     // a prompt per leg (leg_prompt.h), made once by wmx_mix_prompts: one block -- the state entries in front, the clip table behind
     // them, the arena behind that -- and what the host knows of it
     wmx::LegPrompt *d_prompt = nullptr;
@@ -826,8 +814,9 @@ int wmx_mix_destroy(wmx_mix *m) {
     if (m->d_conf_members) (void)hipFree(m->d_conf_members);
     if (m->d_conf_tab) (void)hipFree(m->d_conf_tab);
     if (m->d_conf_lead) (void)hipFree(m->d_conf_lead);
-    if (m->d_env) (void)hipFree(m->d_env);
-    if (m->d_reset_idx) (void)hipFree(m->d_reset_idx);
+    m->talkers.destroy();
+    m->cursors.destroy();
+    if (m->d_prompt_idx) (void)hipFree(m->d_prompt_idx);
     if (m->d_leg_span) (void)hipFree(m->d_leg_span);
     if (m->d_prompt) (void)hipFree(m->d_prompt);
     delete m;
@@ -849,6 +838,8 @@ int wmx_mix_create(wmx_mix **out, int n_groups, int ring_chn, int ring_freq) {
         return WMX_ENODEV;
     }
     m->n_groups = n_groups;
+    m->cursors = LegState("hipMemset(leg cursors)", "mixer", n_groups, kLegCursorColumns);
+    m->talkers = LegState("hipMemset(speakers)", "mixer", n_groups, kLegTalkerColumns);
     m->chn = ring_chn;
     m->freq = ring_freq;
     m->ring_bytes = (uint32_t)(ring_chn * 2) * (uint32_t)ring_freq;  // WMIX_BUFF_SIZE, src/wmixConf.h:124
@@ -1042,20 +1033,18 @@ int wmx_mix_load_minus_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU8Len,
 }
 
 // ---- a cursor per leg (include/wmix_amd.h, leg_cursor.h)
-// the cursors (fresh), the drop counts (zero), the span table and the windows, from the first call that needs them on: one block,
-// the 16-byte span entries in front.  A layout has at most n_groups / 2 conferences that load.
+// the cursors (fresh) and the drop counts (zero), and the scratch of the span table and the windows (the 16-byte span entries in
+// front), from the first call that needs them on.  A layout has at most n_groups / 2 conferences that load.
 static int legs_state(wmx_mix *m) {
     using namespace wmx;
-    if (m->d_leg_span) return 0;
-    const size_t n = (size_t)m->n_groups, n_win = n / 2 + 1, head_off = n * sizeof(LegSpanEntry) + n_win * sizeof(uint2);
+    const int rc = m->cursors.make();
+    if (rc || m->d_leg_span) return rc;
+    const size_t n = (size_t)m->n_groups;
     void *p = nullptr;
-    const int rc = zeroed_block(&p, head_off + 3 * n * sizeof(uint32_t), "hipMemset(leg cursors)", head_off, 0xff, n * sizeof(uint32_t));
-    if (rc) return rc;  // 0xff: UINT32_MAX, no cursor yet
+    const int rcb = zeroed_block(&p, n * sizeof(LegSpanEntry) + (n / 2 + 1) * sizeof(uint2), "hipMemset(leg spans)");
+    if (rcb) return rcb;
     m->d_leg_span = static_cast<LegSpanEntry *>(p);
     m->d_leg_win = reinterpret_cast<uint2 *>(m->d_leg_span + n);
-    m->d_leg_head = reinterpret_cast<uint32_t *>(m->d_leg_win + n_win);
-    m->d_leg_tick = m->d_leg_head + n;
-    m->d_leg_dropped = m->d_leg_head + 2 * n;
     return 0;
 }
 
@@ -1101,7 +1090,8 @@ static int load_minus_legs_any(const char *who, wmx_mix *m, const int16_t *d_src
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(with_calls ? leg_cursor_kernel<true> : leg_cursor_kernel<false>, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0,
                        s, (const int32_t *)m->d_conf_tab, (const int32_t *)m->d_conf_members, d_len, srcU8Len, max_packets, d_mute, cursor_state(m), n_out,
-                       m->d_leg_head, m->d_leg_tick, m->d_leg_dropped, m->d_leg_span, m->d_leg_win, m->n_groups, n_slots, d_calls);
+                       m->cursors.at<uint32_t>(kCursorHead), m->cursors.at<uint32_t>(kCursorTick), m->cursors.at<uint32_t>(kCursorDropped), m->d_leg_span,
+                       m->d_leg_win, m->n_groups, n_slots, d_calls);
     WMX_LAUNCH_CHECK();
     // whole waves per conference, enough for the longest window of legs that write side by side; a longer one is walked in strides
     const uint32_t n_pad = (n_out * (uint32_t)span_calls + 63) / 64 * 64;
@@ -1145,43 +1135,15 @@ int wmx_mix_load_minus_legs_calls(wmx_mix *m, const int16_t *d_src, uint32_t src
 
 int wmx_mix_reset_leg_cursors(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(m);
-    using namespace wmx;
-    if (!m || (host_idx && n < 0)) return WMX_EINVAL;
-    if (idx_check(host_idx, n, m->n_groups, "wmx_mix_reset_leg_cursors: ring", "mixer")) return WMX_EINVAL;
-    const bool fresh = !m->d_leg_span;
-    const int rcs = legs_state(m);
-    if (rcs || fresh) return rcs;  // just made: fresh already
-    hipStream_t s = as_stream(stream);
-    if (host_idx && n == 0) return 0;
-    const int count = host_idx ? n : m->n_groups;
-    if (host_idx) {
-        const int rcu = upload_idx(m->d_reset_idx, m->reset_cap, host_idx, n, s);
-        if (rcu) return rcu;
-    }
-    hipLaunchKernelGGL(leg_reset_kernel, dim3(stream_grid((size_t)count, 256)), dim3(256), 0, s, m->d_leg_head, m->d_leg_tick, m->d_leg_dropped,
-                       host_idx ? (const int32_t *)m->d_reset_idx : (const int32_t *)nullptr, count, m->n_groups);
-    WMX_LAUNCH_CHECK();
-    return 0;
+    if (!m) return WMX_EINVAL;
+    const int rc = m->cursors.reset("wmx_mix_reset_leg_cursors: ring", host_idx, n, wmx::as_stream(stream));
+    return rc ? rc : legs_state(m);  // the first call makes the scratch too: no load allocates behind it
 }
 
 int wmx_mix_export_leg_cursors(const wmx_mix *m, uint32_t *host_head, uint32_t *host_tick, uint32_t *host_dropped, void *stream) {
     WMX_ON_DEVICE(m);
-    using namespace wmx;
     if (!m) return WMX_EINVAL;
-    const size_t n = (size_t)m->n_groups;
-    if (!m->d_leg_span) {  // no leg has loaded on this mixer
-        for (size_t r = 0; r < n; r++) {
-            if (host_head) host_head[r] = UINT32_MAX;
-            if (host_tick) host_tick[r] = 0;
-            if (host_dropped) host_dropped[r] = 0;
-        }
-        return 0;
-    }
-    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
-    if (host_head) WMX_HIP(hipMemcpy(host_head, m->d_leg_head, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (host_tick) WMX_HIP(hipMemcpy(host_tick, m->d_leg_tick, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (host_dropped) WMX_HIP(hipMemcpy(host_dropped, m->d_leg_dropped, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
+    return m->cursors.export_to({host_head, host_tick, host_dropped}, wmx::as_stream(stream));
 }
 
 // ---- a prompt per leg (include/wmix_amd.h, leg_prompt.h)
@@ -1260,11 +1222,11 @@ static int prompt_set(wmx_mix *m, const char *who, const int32_t *host_idx, int 
     hipStream_t s = as_stream(stream);
     const int count = host_idx ? n : m->n_groups;
     if (host_idx) {
-        const int rcu = upload_idx(m->d_reset_idx, m->reset_cap, host_idx, n, s);
+        const int rcu = upload_idx(m->d_prompt_idx, m->prompt_idx_cap, host_idx, n, s);
         if (rcu) return rcu;
     }
     hipLaunchKernelGGL(prompt_set_kernel, dim3(stream_grid((size_t)count, 256)), dim3(256), 0, s, m->d_prompt,
-                       host_idx ? (const int32_t *)m->d_reset_idx : (const int32_t *)nullptr, count, m->n_groups, value, keep_done ? 1 : 0);
+                       host_idx ? (const int32_t *)m->d_prompt_idx : (const int32_t *)nullptr, count, m->n_groups, value, keep_done ? 1 : 0);
     WMX_LAUNCH_CHECK();
     const uint64_t end = ticks == UINT64_MAX ? UINT64_MAX : m->prompt_now + ticks;
     for (int i = 0; i < count; i++) {
@@ -1387,18 +1349,6 @@ int wmx_mix_load_prompts(wmx_mix *m, void *stream) {
 }
 
 // ---- talker selection (include/wmix_amd.h, speakers.h)
-// the envelopes and the speaking flags, zero, from the first call that needs them on
-static int speakers_state(wmx_mix *m) {
-    if (m->d_env) return 0;
-    const size_t n = (size_t)m->n_groups;
-    void *p = nullptr;
-    const int rc = wmx::zeroed_block(&p, n * sizeof(uint32_t) + n, "hipMemset(speakers)");
-    if (rc) return rc;
-    m->d_env = static_cast<uint32_t *>(p);
-    m->d_speaking = reinterpret_cast<uint8_t *>(m->d_env + n);
-    return 0;
-}
-
 static int speakers_check(const char *who, const void *m, const void *d_src, uint32_t srcU8Len, int max_speakers, int decay_shift,
                           const void *d_mute_out) {
     using namespace wmx;
@@ -1425,7 +1375,7 @@ static int speakers_launch(wmx_mix *m, int n_slots, int parties, const int16_t *
     if (n_slots < 1) return 0;
     const unsigned grid = stream_grid((size_t)n_slots * 64, 256);
     hipLaunchKernelGGL(select_speakers_kernel, dim3(grid), dim3(256), 0, s, d_src, srcU8Len / 2, parties, conf_stride, source_stride, tab, members,
-                       d_mute, max_speakers, floor, decay_shift, m->d_env, m->d_speaking, d_mute_out, n_slots);
+                       d_mute, max_speakers, floor, decay_shift, m->talkers.at<uint32_t>(kTalkerEnv), m->talkers.at<uint8_t>(kTalkerSpeaking), d_mute_out, n_slots);
     WMX_LAUNCH_CHECK();
     return 0;
 }
@@ -1440,7 +1390,7 @@ int wmx_mix_select_speakers(wmx_mix *m, int parties, const int16_t *d_src, uint3
         set_error("wmx_mix_select_speakers: parties=%d must be 2 .. %d and divide the mixer's %d rings", parties, WMX_MIX_MAX_PARTIES, m->n_groups);
         return WMX_EINVAL;
     }
-    const int rcs = speakers_state(m);
+    const int rcs = m->talkers.make();
     if (rcs) return rcs;
     // every ring is a member of a conference: nothing to clear
     return speakers_launch(m, m->n_groups / parties, parties, d_src, srcU8Len, conf_stride, source_stride, nullptr, nullptr, d_mute, max_speakers,
@@ -1460,10 +1410,11 @@ int wmx_mix_select_speakers_conf(wmx_mix *m, const int16_t *d_src, uint32_t srcU
         set_error("wmx_mix_select_speakers_conf: no layout (wmx_mix_set_conferences)");
         return WMX_EINVAL;
     }
-    const int rcs = speakers_state(m);
+    const int rcs = m->talkers.make();
     if (rcs) return rcs;
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(speakers_clear_kernel, dim3(stream_grid((size_t)m->n_groups, 256)), dim3(256), 0, s, m->d_speaking, d_mute_out, m->n_groups);
+    hipLaunchKernelGGL(speakers_clear_kernel, dim3(stream_grid((size_t)m->n_groups, 256)), dim3(256), 0, s, m->talkers.at<uint8_t>(kTalkerSpeaking), d_mute_out,
+                       m->n_groups);
     WMX_LAUNCH_CHECK();
     return speakers_launch(m, m->conf.slots(), 0, d_src, srcU8Len, 0, source_stride, m->d_conf_tab, m->d_conf_members, d_mute, max_speakers, floor,
                            decay_shift, d_mute_out, s);
@@ -1496,16 +1447,17 @@ int wmx_mix_select_speakers_legs(wmx_mix *m, const int16_t *d_src, uint32_t srcU
         set_error("wmx_mix_select_speakers_legs: no layout (wmx_mix_set_conferences)");
         return WMX_EINVAL;
     }
-    const int rcs = speakers_state(m);
+    const int rcs = m->talkers.make();
     if (rcs) return rcs;
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(speakers_clear_kernel, dim3(stream_grid((size_t)m->n_groups, 256)), dim3(256), 0, s, m->d_speaking, d_mute_out, m->n_groups);
+    hipLaunchKernelGGL(speakers_clear_kernel, dim3(stream_grid((size_t)m->n_groups, 256)), dim3(256), 0, s, m->talkers.at<uint8_t>(kTalkerSpeaking), d_mute_out,
+                       m->n_groups);
     WMX_LAUNCH_CHECK();
     const int n_slots = m->conf.slots();
     if (n_slots < 1) return 0;
     hipLaunchKernelGGL(select_speakers_legs_kernel, dim3(stream_grid((size_t)n_slots * 64, 256)), dim3(256), 0, s, d_src, srcU8Len / 2, srcU8Len,
                        source_stride, packet_stride, max_packets, d_len, (const int32_t *)m->d_conf_tab, (const int32_t *)m->d_conf_members, d_mute,
-                       max_speakers, floor, decay_shift, m->d_env, m->d_speaking, d_mute_out, m->n_groups, n_slots);
+                       max_speakers, floor, decay_shift, m->talkers.at<uint32_t>(kTalkerEnv), m->talkers.at<uint8_t>(kTalkerSpeaking), d_mute_out, m->n_groups, n_slots);
     WMX_LAUNCH_CHECK();
     return 0;
 }
@@ -1527,42 +1479,17 @@ int wmx_mix_reset_rings(wmx_mix *m, const int32_t *host_idx, int n, void *stream
     return 0;
 }
 
+// env = 0; the speaking flags are the next selection's to write
 int wmx_mix_reset_speakers(wmx_mix *m, const int32_t *host_idx, int n, void *stream) {
     WMX_ON_DEVICE(m);
-    using namespace wmx;
-    if (!m || (host_idx && n < 0)) return WMX_EINVAL;
-    if (idx_check(host_idx, n, m->n_groups, "wmx_mix_reset_speakers: ring", "mixer")) return WMX_EINVAL;
-    const bool fresh = !m->d_env;
-    const int rcs = speakers_state(m);
-    if (rcs || fresh) return rcs;  // just made: zero already
-    hipStream_t s = as_stream(stream);
-    if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(m->d_env, 0, (size_t)m->n_groups * sizeof(uint32_t), s));
-        return 0;
-    }
-    if (n == 0) return 0;
-    const int rcu = upload_idx(m->d_reset_idx, m->reset_cap, host_idx, n, s);
-    if (rcu) return rcu;
-    hipLaunchKernelGGL((fill_rows_idx<uint32_t>), dim3(stream_grid((size_t)n * 64, 64)), dim3(64), 0, s, m->d_env, (const uint32_t *)nullptr, 1,
-                       (const int32_t *)m->d_reset_idx, n);
-    WMX_LAUNCH_CHECK();
-    return 0;
+    if (!m) return WMX_EINVAL;
+    return m->talkers.reset("wmx_mix_reset_speakers: ring", host_idx, n, wmx::as_stream(stream), wmx::kTalkerEnv, wmx::kTalkerEnv + 1);
 }
 
 int wmx_mix_export_speakers(const wmx_mix *m, uint32_t *host_env, uint8_t *host_speaking, void *stream) {
     WMX_ON_DEVICE(m);
-    using namespace wmx;
     if (!m) return WMX_EINVAL;
-    const size_t n = (size_t)m->n_groups;
-    if (!m->d_env) {  // no selection has run on this mixer
-        if (host_env) memset(host_env, 0, n * sizeof(uint32_t));
-        if (host_speaking) memset(host_speaking, 0, n);
-        return 0;
-    }
-    WMX_HIP(hipStreamSynchronize(as_stream(stream)));
-    if (host_env) WMX_HIP(hipMemcpy(host_env, m->d_env, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (host_speaking) WMX_HIP(hipMemcpy(host_speaking, m->d_speaking, n, hipMemcpyDeviceToHost));
-    return 0;
+    return m->talkers.export_to({host_env, host_speaking}, wmx::as_stream(stream));
 }
 
 // the play thread's drain (src/wmix.c:1347-1366): read `bytes` at the ring head into d_out (per group), zero what

@@ -8,7 +8,6 @@
 // encode.  Ingest replaces rtp_recv's payload-size rule + G711a2PCM (src/rtp.c:86-95, src/wmixTask.c:1278-1282).
 // The zoom's float32 phase walk is data independent and runs once per call on the host (mix.hip) -- the kernel
 // gathers through the list.  Integer path: bit-exact.
-#include <initializer_list>
 #include <vector>
 #include "wmx_internal.h"
 #include "g711_dev.h"
@@ -18,117 +17,7 @@
 #include "leg_codec.h"
 #include "leg_dtmf.h"
 #include "leg_record.h"
-
-namespace wmx {
-namespace {
-
-// ---- state per leg: one table, three functions.  A rule's state is ONE device block of columns: column c holds one entry of
-// col[c].bytes per leg, its fresh value the byte col[c].fill repeated, and the columns lie behind one another in table order -- so a
-// table lists its widest column first and every column starts on its entry's alignment.  A state is made by the first call that
-// needs it (make), put back to fresh for a list of legs or for all (reset) and read out (export_to).
-struct LegColumn {
-    size_t bytes;
-    int fill;
-};
-
-struct LegState {
-    static constexpr int kMaxColumns = 7;
-    const char *what = "";  // names the state in an error text
-    size_t n_legs = 0;
-    int n_cols = 0;
-    LegColumn col[kMaxColumns] = {};
-    uint8_t *p = nullptr;  // NULL: not made, every leg is fresh
-
-    LegState() = default;
-    LegState(const char *what_, int n_legs_, std::initializer_list<LegColumn> cols) : what(what_), n_legs((size_t)n_legs_) {
-        for (const LegColumn &c : cols) col[n_cols++] = c;
-    }
-    size_t offset(int c) const {  // of column c in the block; c = n_cols: the block's size
-        size_t per_leg = 0;
-        for (int i = 0; i < c; i++) per_leg += col[i].bytes;
-        return per_leg * n_legs;
-    }
-    template <class T>
-    T *at(int c) const {
-        return p ? reinterpret_cast<T *>(p + offset(c)) : nullptr;
-    }
-    // the columns c .. run_end - 1 hold one fill byte (same_width: and one width): one memset sets them
-    int run_end(int c, bool same_width) const {
-        int e = c + 1;
-        while (e < n_cols && col[e].fill == col[c].fill && (!same_width || col[e].bytes == col[c].bytes)) e++;
-        return e;
-    }
-
-    // the block, fresh and complete on the device when this returns
-    int make() {
-        if (p) return 0;
-        void *q = nullptr;
-        WMX_HIP(hipMalloc(&q, offset(n_cols)));
-        hipError_t e = hipSuccess;
-        for (int c = 0; c < n_cols && e == hipSuccess; c = run_end(c, false))
-            e = hipMemset(static_cast<uint8_t *>(q) + offset(c), col[c].fill, offset(run_end(c, false)) - offset(c));
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            (void)hipFree(q);
-            return hip_fail(e, what, __FILE__, __LINE__);
-        }
-        p = static_cast<uint8_t *>(q);
-        return 0;
-    }
-
-    // the listed legs (NULL = all) fresh again, on `s`.  A bad index: WMX_EINVAL and nothing touched.  `who` opens the error text.
-    int reset(const char *who, const int32_t *host_idx, int n, hipStream_t s) {
-        if ((host_idx && n < 0) || idx_check(host_idx, n, (int)n_legs, who, "handle")) return WMX_EINVAL;
-        if (!p) return make();  // made just now: fresh already
-        if (!host_idx) {
-            for (int c = 0; c < n_cols; c = run_end(c, false))
-                WMX_HIP(hipMemsetAsync(p + offset(c), col[c].fill, offset(run_end(c, false)) - offset(c), s));
-            return 0;
-        }
-        // a handful of legs at a time: nothing of the list goes to the device.  The leg's entry in each column; columns of one width
-        // are the rows of one 2-D memset
-        for (int i = 0; i < n; i++)
-            for (int c = 0; c < n_cols; c = run_end(c, true)) {
-                uint8_t *entry = p + offset(c) + (size_t)host_idx[i] * col[c].bytes;
-                const int rows = run_end(c, true) - c;
-                if (rows == 1)
-                    WMX_HIP(hipMemsetAsync(entry, col[c].fill, col[c].bytes, s));
-                else
-                    WMX_HIP(hipMemset2DAsync(entry, n_legs * col[c].bytes, col[c].fill, col[c].bytes, (size_t)rows, s));
-            }
-        return 0;
-    }
-
-    // dst[c], where not NULL, takes column c of every leg as the work queued on `s` leaves it; blocking
-    int export_to(std::initializer_list<void *> dst, hipStream_t s) const {
-        if (p) WMX_HIP(hipStreamSynchronize(s));
-        int c = 0;
-        for (void *d : dst) {
-            const size_t bytes = n_legs * col[c].bytes;
-            if (d && p)
-                WMX_HIP(hipMemcpy(d, p + offset(c), bytes, hipMemcpyDeviceToHost));
-            else if (d)
-                memset(d, col[c].fill, bytes);  // never made: fresh
-            c++;
-        }
-        return 0;
-    }
-
-    void destroy() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-};
-
-// the columns of the handle's five states
-enum { kSendSeq, kSendTs };
-enum { kSeqSynced, kSeqNext, kSeqLost, kSeqLate, kSeqDup, kSeqResync, kSeqOverflow, kSeqWords };
-enum { kCodecRefused, kCodecIn, kCodecOutLaw };
-enum { kPlcColHist, kPlcColConcealed };
-enum { kDtmfRing, kDtmfCount, kDtmfTs, kDtmfFlags };
-
-}  // namespace
-}  // namespace wmx
+#include "leg_state.h"
 
 struct wmx_rtp {
     int device;  // the HIP device the state lives on (current device at create); every entry point switches to it
@@ -756,11 +645,11 @@ int wmx_rtp_create(wmx_rtp **out, int n_streams, int law) {
     h->law = law;
     h->codecs_default = true;
     // the tables.  Every fresh value is zero (unsynced, counters 0, an empty history, no key down) but the codecs'
-    h->send = LegState("wmx_rtp_create: hipMalloc/hipMemset", n_streams, {{4, 0}, {4, 0}});  // rtp_header(..., seq 0, timestamp 0, ssrc 0)
-    h->seq = LegState("hipMemset(sequence state)", n_streams, {{4, 0}, {4, 0}, {4, 0}, {4, 0}, {4, 0}, {4, 0}, {4, 0}});
-    h->codec = LegState("hipMemset(codec state)", n_streams, {{4, 0}, {1, WMX_CODEC_REFERENCE}, {1, law}});
-    h->plc = LegState("hipMemset(concealment state)", n_streams, {{kPlcHist * sizeof(int16_t), 0}, {4, 0}});
-    h->dtmf = LegState("hipMemset(DTMF state)", n_streams, {{8, 0}, {4, 0}, {4, 0}, {4, 0}});
+    h->send = LegState("wmx_rtp_create: hipMalloc/hipMemset", "handle", n_streams, kLegSendColumns);
+    h->seq = LegState("hipMemset(sequence state)", "handle", n_streams, kLegSeqColumns);
+    h->codec = LegState("hipMemset(codec state)", "handle", n_streams, leg_codec_columns(law));
+    h->plc = LegState("hipMemset(concealment state)", "handle", n_streams, kLegPlcColumns);
+    h->dtmf = LegState("hipMemset(DTMF state)", "handle", n_streams, kLegDtmfColumns);
     const int rc = h->send.make();
     if (rc) {
         wmx_rtp_destroy(h);
@@ -973,12 +862,9 @@ int wmx_rtp_reset_sequence(wmx_rtp *h, const int32_t *host_idx, int n, void *str
     if (!h) return WMX_EINVAL;
     hipStream_t s = as_stream(stream);
     const int rc = h->seq.reset("wmx_rtp_reset_sequence: leg", host_idx, n, s);
-    uint32_t *refused = h->codec.at<uint32_t>(kCodecRefused);
-    if (rc || !refused) return rc;
+    if (rc || !h->codec.p) return rc;  // no codec state: its counter is fresh
     // the receive side's other counter (leg_codec.h); the leg's codec stays
-    if (!host_idx) WMX_HIP(hipMemsetAsync(refused, 0, (size_t)h->n_streams * sizeof(uint32_t), s));
-    for (int i = 0; host_idx && i < n; i++) WMX_HIP(hipMemsetAsync(refused + host_idx[i], 0, sizeof(uint32_t), s));
-    return 0;
+    return h->codec.reset("wmx_rtp_reset_sequence: leg", host_idx, n, s, kCodecRefused, kCodecRefused + 1);
 }
 
 // next (uint16), synced (uint8) and the five counters (uint32) of every leg as the work queued on `stream` leaves them; any pointer may
@@ -1279,23 +1165,15 @@ int wmx_rtp_set_codecs(wmx_rtp *h, const int32_t *host_idx, int n, int in_codec,
                   out_law);
         return WMX_EINVAL;
     }
-    if (idx_check(host_idx, n, h->n_streams, "wmx_rtp_set_codecs: stream", "handle")) return WMX_EINVAL;
-    const int rcs = h->codec.make();
-    if (rcs) return rcs;
     hipStream_t s = as_stream(stream);
-    uint8_t *d_in_codec = h->codec.at<uint8_t>(kCodecIn), *d_out_law = h->codec.at<uint8_t>(kCodecOutLaw);
+    int rc = h->codec.set("wmx_rtp_set_codecs: stream", kCodecIn, in_codec, host_idx, n, s);
+    if (rc == 0) rc = h->codec.set("wmx_rtp_set_codecs: stream", kCodecOutLaw, out_law, host_idx, n, s);
+    if (rc) return rc;
     const bool is_default = in_codec == WMX_CODEC_REFERENCE && out_law == h->law;
-    if (!host_idx) {
-        WMX_HIP(hipMemsetAsync(d_in_codec, in_codec, (size_t)h->n_streams, s));
-        WMX_HIP(hipMemsetAsync(d_out_law, out_law, (size_t)h->n_streams, s));
+    if (!host_idx)
         h->codecs_default = is_default;
-        return 0;
-    }
-    for (int i = 0; i < n; i++) {  // a handful of legs at a time: nothing of the list goes to the device
-        WMX_HIP(hipMemsetAsync(d_in_codec + host_idx[i], in_codec, 1, s));
-        WMX_HIP(hipMemsetAsync(d_out_law + host_idx[i], out_law, 1, s));
-    }
-    if (n > 0 && !is_default) h->codecs_default = false;
+    else if (n > 0 && !is_default)
+        h->codecs_default = false;
     return 0;
 }
 
